@@ -13,7 +13,13 @@ search path over the whole query batch through the product class (``ShardedFlatI
 cascade on every shard -> ONE RCCL all-gather of the packed per-shard top-k (nq*k*12 bytes per rank) -> merge.
 ``config.strong_10M`` carries the strong-scaling line of the fixed 10 M-row index for the same N.
 
-The JSON line also carries:
+A plain run does only what the headline needs: build the index, warm up, time the --steps steps, write the outputs
+of the last timed step (``--dump-outputs DIR``: ``scores.npy`` float32 and ``ids.npy`` float64, nq x k each) and print
+the line.  Everything below -- the per-kernel roofline, the latency and extra legs, the encoder, the CPU baseline, the
+self-check of the answers and the strong-scaling line -- runs only with ``--full``; the ``--no-*`` / ``--legs``
+switches narrow what ``--full`` runs.
+
+With --full the JSON line also carries:
   roofline      dominant kernel of the timed region -- the main stage of the search cascade,
                 k_scan_qreg_i8<12,true> (k_scan_coarse8<false,true,..> under CSS_KNN_QREG=0) on the int8 shadow rows (int8 MFMA peak; `frac_of_bf16_peak`
                 beside it; the bf16 scan where the library takes that) -- measured with HIP events on the
@@ -95,7 +101,15 @@ def parse_args(argv=None):
                                                    "80m,clustered10m (default all; profiling passes isolate one population per kernel)")
     ap.add_argument("--no-check", action="store_true", help="skip the self-check of the timed region's answers")
     ap.add_argument("--allow-debug", action="store_true", help="print a line (marked invalid) although a *_DBG switch is set")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: roofline, extra legs, "
+                                                        "encoder, CPU baseline, self-check, strong scaling")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's top-k as DIR/scores.npy (float32) "
+                                                          "and DIR/ids.npy (float64)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.only_encoder and not a.full:
+        ap.error("--only-encoder is a --full measurement: add --full")
     allowed = ("nq1", "e2e", "masked", "exact", "clustered", "noshadow", "80m", "clustered10m")
     legs = set(allowed) if a.legs == "all" else {x for x in a.legs.split(",") if x and x != "none"}
     if legs - set(allowed):
@@ -104,6 +118,9 @@ def parse_args(argv=None):
         legs = set()
     if a.no_heavy_extra:
         legs -= {"noshadow", "80m", "clustered10m"}
+    if not a.full:   # a plain run: the headline alone
+        legs = set()
+        a.no_cpu_baseline = a.no_encoder = a.no_check = a.no_strong = True
     a.legs = legs
     return a
 
@@ -599,6 +616,30 @@ def check_answers(index, q_host, D, I, id_base, k, log, nq_check=256, n_rescore=
             "sample_violations": viol}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, D, I, log):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the top-k scores (float32) and
+    global row ids (float64, exact below 2**53) of every query -- as DIR/scores.npy and DIR/ids.npy.  Past 64 MB in
+    all, a fixed, seeded sample of the query rows, whose indices go to DIR/query_rows.npy."""
+    import numpy as np
+
+    Dh = D.cpu().numpy().astype(np.float32)
+    Ih = I.cpu().numpy().astype(np.float64)
+    arrays = {"scores": Dh, "ids": Ih}
+    row_bytes = Dh.shape[1] * (4 + 8)
+    if Dh.shape[0] * row_bytes > DUMP_LIMIT_BYTES:
+        n = DUMP_LIMIT_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(Dh.shape[0], size=n, replace=False))
+        arrays = {"scores": Dh[rows], "ids": Ih[rows], "query_rows": rows.astype(np.float64)}
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    log(f"outputs of the last timed step: {', '.join(f'{k_}.npy {a.shape}' for k_, a in arrays.items())} in {out}")
+
+
 def timed_steps(step, fence, nsteps):
     t0 = time.perf_counter()
     for _ in range(nsteps):
@@ -752,7 +793,7 @@ def _main(argv, platform_factory):
         step()
     fence()
     nat.prof_reset()
-    nat.prof_enable(True)
+    nat.prof_enable(args.full)   # per-kernel HIP events: only the roofline reads them
     elapsed = timed_steps(step, fence, args.steps)
     nat.prof_enable(False)
     elapsed = max_over_ranks(elapsed)
@@ -764,6 +805,8 @@ def _main(argv, platform_factory):
     if world > 1:   # every shard contributes to the merged answer
         owners = torch.bincount((I.flatten() // args.rows).clamp_(max=world - 1), minlength=world)
         assert int((owners > 0).sum()) == world, owners.tolist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, D, I, log)
     D_timed, I_timed = D.clone(), I.clone()   # (checked after the latency legs below: see check_answers)
 
     # ---- roofline of the dominant kernel (HIP events on the launch stream) ----
@@ -1103,6 +1146,7 @@ def _main(argv, platform_factory):
             "vs_baseline": None,
             "dtype": "f32 (int8/bf16 MFMA candidate scan in a measured error band + exact fp32 rescoring)",
             "data": "synthetic" if hip else f"synthetic, on the {plat.name} platform (control-flow rehearsal: NOT a measurement)",
+            "full": args.full,
             "config": {"workload": f"nq={args.nq} k={args.k} {rows_total}x{args.dim} fp32 flat IP index, {world} GPU "
                                    f"({args.rows} rows/GPU): {cfg_name}",
                        "rows_total": rows_total, "rows_per_gpu": shard, "dim": args.dim, "nq": args.nq, "k": args.k,

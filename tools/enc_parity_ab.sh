@@ -2,7 +2,7 @@
 # usage: tools/enc_parity_ab.sh "ENV=.." ... -> ms per batch + min cosine vs the fp32 oracle per variant ("-" = default env)
 for v in "$@"; do
   e="$v"; if [ "$v" = "-" ]; then e=""; fi
-  env $e timeout -k 10 300 python bench.py --only-encoder 2>/dev/null | python -c "
+  env $e timeout -k 10 300 python bench.py --full --only-encoder 2>/dev/null | python -c "
 import json,sys
 try:
     e=json.loads(sys.stdin.read())['encode']

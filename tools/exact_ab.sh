@@ -2,7 +2,7 @@
 # A/B timing of the exact fp32 legs (bench.py --legs exact) under different env settings, back to back on one box.
 for e in "$@"; do
   if [ "$e" = "-" ]; then e="A=1"; fi
-  out=$(env $e timeout -k 10 300 python3 bench.py --no-encoder --no-cpu-baseline --legs exact --allow-debug --steps 3 --warmup 1 2>/dev/null)
+  out=$(env $e timeout -k 10 300 python3 bench.py --full --no-encoder --no-cpu-baseline --legs exact --allow-debug --steps 3 --warmup 1 2>/dev/null)
   echo "$out" | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1]); r=d['roofline']

@@ -3,7 +3,7 @@
 # usage: tools/nq1_ab.sh "ENV1=.. ENV2=.." ...   (use "-" for the default environment)
 for e in "$@"; do
   if [ "$e" = "-" ]; then e=""; fi
-  out=$(env $e timeout -k 10 200 python3 bench.py --no-encoder --no-cpu-baseline --legs nq1 --allow-debug 2>/dev/null)
+  out=$(env $e timeout -k 10 200 python3 bench.py --full --no-encoder --no-cpu-baseline --legs nq1 --allow-debug 2>/dev/null)
   echo "$out" | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1]); x=d['extra']

@@ -8,7 +8,7 @@ shift
 O=gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-extra --enc-steps 2 $*"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-extra --enc-steps 2 $*"
 rocprofv3 -L > $O/counters_available.txt 2>&1 || true
 timeout -k 10 500 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE \
     -d $O/pmc_a -o run --output-format csv -- python3 bench.py $ARGS > $O/pmc_a.json 2> $O/pmc_a.err || exit 3

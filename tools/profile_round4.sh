@@ -10,7 +10,7 @@ TAG=${1:-r04}
 O=gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
-LIGHT="--no-cpu-baseline --no-encoder"
+LIGHT="--full --no-cpu-baseline --no-encoder"
 stats() {   # name, bench args...
     local name=$1; shift
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats_$name -o run --output-format csv -- python3 bench.py "$@" \
@@ -25,14 +25,14 @@ pmc() {     # dir name, counters (quoted), bench args...
     echo "[profile] pmc $name done"
 }
 if [ "$2" = "full" ]; then
-    timeout -k 10 900 python3 bench.py > $O/bench.json 2> $O/bench.err || exit 1
+    timeout -k 10 900 python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
     echo "[profile] full bench done"
 fi
 # --- kernel-trace stats, one leg each ---------------------------------------------------------------------------
 stats headline $LIGHT --legs none || exit 2                       # k_scan_coarse8<false,true,false,4096,true>: 1000 q x 10 M
 stats nq1 $LIGHT --legs nq1 --steps 2 --warmup 1 || exit 3        # k_sweep_cascade<1,3,true>: single query, k = 10 and k' = 100
 stats exact $LIGHT --legs exact --steps 2 --warmup 1 || exit 4    # k_scan_small<1,..> (nq = 1) and k_scan_mfma (256 queries)
-stats encoder --only-encoder --enc-fixed-only --no-cpu-baseline --enc-steps 5 || exit 5
+stats encoder --full --only-encoder --enc-fixed-only --no-cpu-baseline --enc-steps 5 || exit 5
 # --- HBM-side traffic (FETCH_SIZE, WRITE_SIZE: separate passes) -----------------------------------------------------
 P="--steps 3 --warmup 1 $LIGHT --legs nq1,exact"
 pmc pmc_fetch FETCH_SIZE $P || exit 6
@@ -40,7 +40,7 @@ pmc pmc_write WRITE_SIZE $P || exit 7
 python3 tools/pmc_summarise.py $O/pmc_fetch $O/pmc_write $O/pmc_hbm_traffic.json \
   --note "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on python3 bench.py $P" \
   --workload '{"rows_per_gpu": 10000000, "dim": 768, "nq": 1000, "k": 10}'
-E="--only-encoder --enc-fixed-only --no-cpu-baseline --enc-steps 3"
+E="--full --only-encoder --enc-fixed-only --no-cpu-baseline --enc-steps 3"
 pmc pmc_fetch_enc FETCH_SIZE $E || exit 8
 pmc pmc_write_enc WRITE_SIZE $E || exit 9
 python3 tools/pmc_summarise.py $O/pmc_fetch_enc $O/pmc_write_enc $O/pmc_hbm_traffic_encoder.json --all \
