@@ -45,37 +45,6 @@ struct LayerW {
     float *bo_f = nullptr, *b2_f = nullptr; // bias + beta of the LayerNorm whose output is the residual (EPI_RES)
 };
 
-// Process-wide switches, read from the environment ONCE (thread-safe static init); all are A/B-experiment knobs,
-// the defaults are the product configuration.
-struct EncEnv {
-    int resid = 2;        // CSS_ENC_RESID: residual stream storage in bf16 mode (see forward_typed)
-    int gemm4w = 0;       // CSS_GEMM_4W: bit mask of the folded GEMMs that run on k_gemm4w (1 QKV, 2 O, 4 FFN1, 8 FFN2)
-    int dbg = 0;          // CSS_GEMM_DBG bit0: skip epilogue, bit1: skip MFMA, bit2: skip loads (timing experiments)
-    bool big_tiles = true;   // CSS_GEMM_TILE=128: the 128x128 tiles everywhere
-    bool mfma16 = true;      // CSS_GEMM_MFMA=32: 32x32x16 MFMA kernel (k_gemm) instead of k_gemm16
-    bool loop8 = true;       // CSS_GEMM_LOOP=old: the round-1 main loop (k_gemm16) instead of k_gemm8p
-    bool fuse_ln = true;     // CSS_ENC_FUSE_LN=0: separate LayerNorm kernels also for large batches
-    float att_range = -1.f;  // CSS_ATT_RANGE: default of css_encoder_set_attention_range (0 = always the safe softmax pass)
-    int cg_qkv = 0, cg_ffn1 = 0, cg_o = 0, cg_ffn2 = 0;   // CSS_GEMM_CG="qkv,ffn1,o,ffn2": column-group tile walk of k_gemm8p (0 = N-fastest)
-    int grid_qkv = 0, grid_ffn1 = 0, grid_o = 0, grid_ffn2 = 0;   // CSS_GEMM_GRID="qkv,ffn1,o,ffn2": blocks of k_gemm8p (0 = automatic)
-    EncEnv() {
-        if (const char* t = getenv("CSS_GEMM_TILE")) big_tiles = atoi(t) != 128;
-        if (const char* t = getenv("CSS_GEMM_DBG")) dbg = atoi(t);
-        if (const char* t = getenv("CSS_ENC_RESID")) resid = atoi(t);
-        if (const char* t = getenv("CSS_GEMM_4W")) gemm4w = atoi(t);
-        if (const char* t = getenv("CSS_GEMM_MFMA")) mfma16 = atoi(t) != 32;
-        if (const char* t = getenv("CSS_GEMM_LOOP")) loop8 = std::string(t) != "old";
-        if (const char* t = getenv("CSS_ENC_FUSE_LN")) fuse_ln = atoi(t) != 0;
-        if (const char* t = getenv("CSS_ATT_RANGE")) att_range = (float)atof(t);
-        if (const char* t = getenv("CSS_GEMM_CG")) sscanf(t, "%d,%d,%d,%d", &cg_qkv, &cg_ffn1, &cg_o, &cg_ffn2);
-        if (const char* t = getenv("CSS_GEMM_GRID")) sscanf(t, "%d,%d,%d,%d", &grid_qkv, &grid_ffn1, &grid_o, &grid_ffn2);
-    }
-};
-const EncEnv& enc_env() {
-    static const EncEnv env;
-    return env;
-}
-
 __global__ void k_synth_fill(float* p, size_t n, uint64_t seed, float mean, float std) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -334,7 +303,7 @@ int launch_gemm_t(const void* A, const void* W, const float* bias, void* C, int 
     grid = std::max(8, grid / 8 * 8);
     ProfScope ps(prof, st);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), lds, st, (const TIn*)A, (const TIn*)W, bias, C, M, N, K,
-                       qscale_cols, qscale, enc_env().dbg);
+                       qscale_cols, qscale);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
@@ -352,7 +321,7 @@ int launch_gemm8p(const void* A, const void* W, const float* bias, void* C, int 
     int rc_ = css::ensure_dynamic_lds((const void*)kern, lds, dev_);
     if (rc_ != CSS_OK) return rc_;
     const int ntiles = (N / 256) * ((M + 255) / 256);
-    int grid = std::min(ntiles, side.grid > 0 ? std::min(side.grid, num_cus) : num_cus);
+    int grid = std::min(ntiles, num_cus);
     grid = std::max(8, grid / 8 * 8);
     ProfScope ps(prof, st);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, (const bf16_t*)A, (const bf16_t*)W, bias, (bf16_t*)C, M, N, K,
@@ -360,27 +329,6 @@ int launch_gemm8p(const void* A, const void* W, const float* bias, void* C, int 
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
-// k_gemm4w launch (the LayerNorm-folded GEMMs on four 128 x 128 waves per block; CSS_GEMM_4W=0 keeps k_gemm8p)
-template <int EPI, int TAG = 0>
-int launch_gemm4w(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int qscale_cols,
-                  float qscale, const G8Side& side, int num_cus, hipStream_t st, const char* prof) {
-    CSS_REQUIRE(N % 256 == 0 && K % 64 == 0 && K >= 256 && (size_t)M * K * 2 < ((size_t)1 << 32), "gemm4w: bad shape %d x %d x %d", M, N, K);
-    auto kern = k_gemm4w<EPI, TAG>;
-    constexpr size_t lds = 2 * 65536;
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    int rc_ = css::ensure_dynamic_lds((const void*)kern, lds, dev_);
-    if (rc_ != CSS_OK) return rc_;
-    const int ntiles = (N / 256) * ((M + 255) / 256);
-    int grid = std::min(ntiles, side.grid > 0 ? std::min(side.grid, num_cus) : num_cus);
-    grid = std::max(8, grid / 8 * 8);
-    ProfScope ps(prof, st);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, (const bf16_t*)A, (const bf16_t*)W, bias, (bf16_t*)C, M, N, K,
-                       qscale_cols, qscale, side);
-    CSS_LAUNCH_CHECK();
-    return CSS_OK;
-}
-// CSS_GEMM_TILE=128 selects the 128x128 variant (A/B experiments)
 
 template <typename TIn, int EPI>
 int launch_gemm(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int qscale_cols,
@@ -396,34 +344,32 @@ int launch_gemm(const void* A, const void* W, const float* bias, void* C, int M,
         CSS_LAUNCH_CHECK();
         return CSS_OK;
     }
-    const EncEnv& env = enc_env();
-    if (env.big_tiles && M >= 1024 && N % 256 == 0) {
+    if (M >= 1024 && N % 256 == 0) {
         // ring: 2 stages x 128 B rows.  Rings of 3 / 4 x 64 B rows and 5 x 64 B with two stages per step were
         // measured slower (more barriers, same LDS fill rate) and are not kept.
-        if constexpr (sizeof(TIn) == 2 && (EPI == EPI_QKV || EPI == EPI_GELU)) {
-            if (env.loop8 && K % 128 == 0 && (size_t)M * K * 2 < ((size_t)1 << 32))
-                return launch_gemm8p<EPI>(A, W, bias, C, M, N, K, qscale_cols, qscale, G8Side{}, num_cus, st, prof);
-        }
         if constexpr (sizeof(TIn) == 2) {
-            if (env.mfma16) {  // product mode: the 16x16x32 MFMA variant (CSS_GEMM_MFMA=32 selects k_gemm for A/B runs)
-                CSS_REQUIRE(K % 64 == 0 && K / 64 >= 3, "gemm: K=%d must be a multiple of 64 (>= 192)", K);
-                auto kern = k_gemm16<EPI>;
-                constexpr size_t lds = 2 * 512 * 128;
-                int dev_ = 0;
-                (void)hipGetDevice(&dev_);
-                int rc_ = css::ensure_dynamic_lds((const void*)kern, lds, dev_);
-                if (rc_ != CSS_OK) return rc_;
-                const int ntiles = (N / 256) * ((M + 255) / 256);
-                int grid = std::min(ntiles, num_cus);
-                grid = std::max(8, grid / 8 * 8);
-                ProfScope ps(prof, st);
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, (const bf16_t*)A, (const bf16_t*)W, bias, C, M, N, K,
-                                   qscale_cols, qscale);
-                CSS_LAUNCH_CHECK();
-                return CSS_OK;
-            }
+            static_assert(EPI == EPI_QKV || EPI == EPI_GELU, "bf16 GEMMs write bf16 rows");
+            if (K % 128 == 0 && (size_t)M * K * 2 < ((size_t)1 << 32))
+                return launch_gemm8p<EPI>(A, W, bias, C, M, N, K, qscale_cols, qscale, G8Side{}, num_cus, st, prof);
+            // the 16x16x32 MFMA variant: the chip holds a higher clock under it than under 32x32x16
+            CSS_REQUIRE(K % 64 == 0 && K / 64 >= 3, "gemm: K=%d must be a multiple of 64 (>= 192)", K);
+            auto kern = k_gemm16<EPI>;
+            constexpr size_t lds = 2 * 512 * 128;
+            int dev_ = 0;
+            (void)hipGetDevice(&dev_);
+            int rc_ = css::ensure_dynamic_lds((const void*)kern, lds, dev_);
+            if (rc_ != CSS_OK) return rc_;
+            const int ntiles = (N / 256) * ((M + 255) / 256);
+            int grid = std::min(ntiles, num_cus);
+            grid = std::max(8, grid / 8 * 8);
+            ProfScope ps(prof, st);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, (const bf16_t*)A, (const bf16_t*)W, bias, C, M, N, K,
+                               qscale_cols, qscale);
+            CSS_LAUNCH_CHECK();
+            return CSS_OK;
+        } else {
+            return launch_gemm_t<TIn, EPI, 2, 4, 4, 2, 2, 128, 1>(A, W, bias, C, M, N, K, qscale_cols, qscale, num_cus, st, prof);
         }
-        return launch_gemm_t<TIn, EPI, 2, 4, 4, 2, 2, 128, 1>(A, W, bias, C, M, N, K, qscale_cols, qscale, num_cus, st, prof);
     }
     return launch_gemm_t<TIn, EPI, 2, 2, 2, 2, 4, 64, 1>(A, W, bias, C, M, N, K, qscale_cols, qscale, num_cus, st, prof);
 }
@@ -442,28 +388,23 @@ int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, 
         CSS_LAUNCH_CHECK();
     }
     const int maxL = c.max_seq_len;
-    // Residual stream storage (bf16 mode): CSS_ENC_RESID 0 = fp32 rows (x32) + fp32 branch outputs,
-    // 1 = bf16 residual (the row the next GEMM reads anyway) + fp32 branch outputs, 2 = both bf16.
-    const int rmode = BF ? enc_env().resid : 0;
-    // attention-output / FFN2 projection into `pre32` (fp32, or bf16 rows when rmode == 2)
+    // Residual stream storage: fp32 rows (x32) and fp32 branch outputs in fp32 mode; in bf16 mode both are bf16
+    // (the residual is the row the next GEMM reads anyway).
+    // attention-output / FFN2 projection into `pre32` (fp32, or bf16 rows in bf16 mode)
     auto launch_branch_out = [&](const void* a, const void* w, const float* bias, int K, const char* prof) -> int {
-        if (rmode == 2) return launch_gemm<TIn, EPI_QKV>(a, w, bias, e->pre32, T, H, K, 0, 1.0f, e->num_cus, st, prof);
-        return launch_gemm<TIn, EPI_RESID>(a, w, bias, e->pre32, T, H, K, 0, 1.0f, e->num_cus, st, prof);
+        if constexpr (BF) return launch_gemm<TIn, EPI_QKV>(a, w, bias, e->pre32, T, H, K, 0, 1.0f, e->num_cus, st, prof);
+        else return launch_gemm<TIn, EPI_RESID>(a, w, bias, e->pre32, T, H, K, 0, 1.0f, e->num_cus, st, prof);
     };
     // x = LN(pre + x); `last`: the fp32 row is needed by the pooling
     auto launch_ln = [&](const float* g, const float* b, bool last) -> int {
         ProfScope ps("enc_layernorm", st);
         const dim3 grid((T + 3) / 4), blk(256);
-        bf16_t* o16 = BF ? (bf16_t*)e->x16 : nullptr;
-        if (rmode == 0)
-            hipLaunchKernelGGL((k_layernorm<768, float, float>), grid, blk, 0, st, (const float*)e->pre32, (const float*)e->x32, g, b,
-                               c.ln_eps, e->x32, o16, T);
-        else if (rmode == 1)
-            hipLaunchKernelGGL((k_layernorm<768, float, bf16_t>), grid, blk, 0, st, (const float*)e->pre32, (const bf16_t*)e->x16, g, b,
-                               c.ln_eps, last ? e->x32 : (float*)nullptr, o16, T);
-        else
+        if constexpr (BF)
             hipLaunchKernelGGL((k_layernorm<768, bf16_t, bf16_t>), grid, blk, 0, st, (const bf16_t*)e->pre32, (const bf16_t*)e->x16, g, b,
-                               c.ln_eps, last ? e->x32 : (float*)nullptr, o16, T);
+                               c.ln_eps, last ? e->x32 : (float*)nullptr, (bf16_t*)e->x16, T);
+        else
+            hipLaunchKernelGGL((k_layernorm<768, float, float>), grid, blk, 0, st, (const float*)e->pre32, (const float*)e->x32, g, b,
+                               c.ln_eps, e->x32, (bf16_t*)nullptr, T);
         CSS_LAUNCH_CHECK();
         return CSS_OK;
     };
@@ -532,13 +473,8 @@ int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, i
         // x = LN(pre[0]) -> qkv; zeroes stats[1]
         side.stats_in = e->stats[0];
         side.stats_out = e->stats[1];
-        side.cgroup = enc_env().cg_qkv;
-        side.grid = enc_env().grid_qkv;
-        const int g4 = enc_env().gemm4w;
-        if ((rc = (g4 & 1) ? launch_gemm4w<EPI_AFF_QKV>(pre[0], L.wqkv_f, L.dqkv, e->qkv, T, 3 * H, H, H, 0.125f * 1.44269504088896341f,
-                                                          side, e->num_cus, st, "enc_gemm_qkv")
-                           : launch_gemm8p<EPI_AFF_QKV, true>(pre[0], L.wqkv_f, L.dqkv, e->qkv, T, 3 * H, H, H, 0.125f * 1.44269504088896341f,
-                                                                side, e->num_cus, st, "enc_gemm_qkv")) != CSS_OK)
+        if ((rc = launch_gemm8p<EPI_AFF_QKV, true>(pre[0], L.wqkv_f, L.dqkv, e->qkv, T, 3 * H, H, H, 0.125f * 1.44269504088896341f,
+                                                   side, e->num_cus, st, "enc_gemm_qkv")) != CSS_OK)
             return rc;
         {
             ProfScope ps("enc_attention", st);
@@ -551,26 +487,17 @@ int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, i
         // pre[1] = ctx Wo^T + (bo + beta) + gamma (pre[0] - mu) rs; stats[1] += row sums
         side.pprev = pre[0];
         side.cvec = g_in;
-        side.cgroup = enc_env().cg_o;
-        side.grid = enc_env().grid_o;
-        if ((rc = (g4 & 2) ? launch_gemm4w<EPI_RES, 1>(e->ctx, L.wo_p, L.bo_f, pre[1], T, H, H, 0, 1.0f, side, e->num_cus, st, "enc_gemm_o")
-                           : launch_gemm8p<EPI_RES, true, 1>(e->ctx, L.wo_p, L.bo_f, pre[1], T, H, H, 0, 1.0f, side, e->num_cus, st, "enc_gemm_o")) != CSS_OK)
+        if ((rc = launch_gemm8p<EPI_RES, true, 1>(e->ctx, L.wo_p, L.bo_f, pre[1], T, H, H, 0, 1.0f, side, e->num_cus, st, "enc_gemm_o")) != CSS_OK)
             return rc;
         // x1 = LN1(pre[1]) -> ffn = gelu(x1 W1^T + b1); zeroes stats[0]
         side.stats_in = e->stats[1];
         side.stats_out = e->stats[0];
-        side.cgroup = enc_env().cg_ffn1;
-        side.grid = enc_env().grid_ffn1;
-        if ((rc = (g4 & 4) ? launch_gemm4w<EPI_AFF_GELU>(pre[1], L.w1_f, L.d1, e->ffn, T, F, H, 0, 1.0f, side, e->num_cus, st, "enc_gemm_ffn1")
-                           : launch_gemm8p<EPI_AFF_GELU, true>(pre[1], L.w1_f, L.d1, e->ffn, T, F, H, 0, 1.0f, side, e->num_cus, st, "enc_gemm_ffn1")) != CSS_OK)
+        if ((rc = launch_gemm8p<EPI_AFF_GELU, true>(pre[1], L.w1_f, L.d1, e->ffn, T, F, H, 0, 1.0f, side, e->num_cus, st, "enc_gemm_ffn1")) != CSS_OK)
             return rc;
         // pre[0] = ffn W2^T + (b2 + beta1) + gamma1 (pre[1] - mu) rs; stats[0] += row sums
         side.pprev = pre[1];
         side.cvec = L.ln1g;
-        side.cgroup = enc_env().cg_ffn2;
-        side.grid = enc_env().grid_ffn2;
-        if ((rc = (g4 & 8) ? launch_gemm4w<EPI_RES>(e->ffn, L.w2_p, L.b2_f, pre[0], T, H, F, 0, 1.0f, side, e->num_cus, st, "enc_gemm_ffn2")
-                           : launch_gemm8p<EPI_RES, true>(e->ffn, L.w2_p, L.b2_f, pre[0], T, H, F, 0, 1.0f, side, e->num_cus, st, "enc_gemm_ffn2")) != CSS_OK)
+        if ((rc = launch_gemm8p<EPI_RES, true>(e->ffn, L.w2_p, L.b2_f, pre[0], T, H, F, 0, 1.0f, side, e->num_cus, st, "enc_gemm_ffn2")) != CSS_OK)
             return rc;
         g_in = L.ln2g;
         b_in = L.ln2b;
@@ -598,9 +525,7 @@ int forward_any(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, in
     CSS_REQUIRE(B >= 1 && T >= B, "css_encoder_forward: bad batch (B=%d, tokens=%d)", B, T);
     CSS_REQUIRE(max_len >= 1 && max_len <= e->cfg.max_seq_len, "css_encoder_forward: max_len=%d outside [1, %d]", max_len,
                 e->cfg.max_seq_len);
-    const EncEnv& env = enc_env();
-    if (e->cfg.compute == 0 && env.fuse_ln && env.big_tiles && env.loop8 && T >= 1024 && e->cfg.ffn % 256 == 0 &&
-        (size_t)T * e->cfg.ffn * 2 < ((size_t)1 << 32))
+    if (e->cfg.compute == 0 && T >= 1024 && e->cfg.ffn % 256 == 0 && (size_t)T * e->cfg.ffn * 2 < ((size_t)1 << 32))
         return forward_folded_bf16(e, ids, cu, B, T, max_len, normalize, out, st);
     e->x32_valid = true;
     return e->cfg.compute == 0 ? forward_typed<bf16_t>(e, ids, cu, B, T, max_len, normalize, out, st)
@@ -625,11 +550,9 @@ int css_encoder_create(const css_encoder_cfg* cfg, int device, css_encoder** out
     int rc = css::check_device(device);
     if (rc != CSS_OK) return rc;
     DeviceGuard g(device);
-    (void)enc_env();
     css_encoder* e = new css_encoder();
     e->cfg = *cfg;
     e->device = device;
-    if (enc_env().att_range >= 0.f) e->att_range = enc_env().att_range;
     {
         hipDeviceProp_t p;
         if (hipGetDeviceProperties(&p, device) == hipSuccess) e->num_cus = p.multiProcessorCount;
@@ -779,7 +702,7 @@ int css_encoder_debug_read(css_encoder* e, const char* what, float* out_host, in
     bool typed = true;  // operand-typed (bf16 in product mode) vs always fp32
     if (w == "x32") {
         CSS_REQUIRE(e->x32_valid, "css_encoder_debug_read: the last forward ran the LayerNorm-folded path, which does not "
-                                  "materialise x32 (set CSS_ENC_FUSE_LN=0)");
+                                  "materialise x32");
         src = e->x32;
         typed = false;
     }

@@ -109,13 +109,8 @@ __global__ __launch_bounds__(256) void k_embed_ln(const int32_t* __restrict__ id
 // block: O projection 2.00 ms, 28 % of the bf16 peak).  A consumer GEMM's LDS-DMA fetches 16-byte pieces by per-lane
 // addresses anyway; its K-step u = block column u, LDS chunk cl = piece (j = cl >> 2, lg = cl & 3), i.e. the K order
 // inside a 64-column block is permuted -- and the consumer's weights carry the same permutation (k_fold_ln, `perm`).
-// Bytes from one 16-row block row to the next: the H / 64 blocks + CSS_PREBLK_PAD bytes of padding.  Without it the
-// stride is a multiple of 4 KiB (768 columns: 24 KiB, 3072: 96 KiB), and the eight waves of a GEMM block, which fetch
-// eight consecutive block rows at the same K step, all land on the same L2 channels (256-byte interleave).
-#ifndef CSS_PREBLK_PAD
-#define CSS_PREBLK_PAD 0
-#endif
-__host__ __device__ __forceinline__ size_t preblk_rowstride(int H) { return (size_t)(H >> 6) * 2048 + CSS_PREBLK_PAD; }
+// Bytes from one 16-row block row to the next: the H / 64 blocks, no padding.
+__host__ __device__ __forceinline__ size_t preblk_rowstride(int H) { return (size_t)(H >> 6) * 2048; }
 // G8_BBLK: the WEIGHTS of the GEMMs with blocked A operands are stored in the blocked layout too ([N][K] through
 // preblk_elem: contiguous 1-KiB DMA pieces, fragment reads without a swizzle; 0: row-major with the K order permuted)
 #ifndef G8_BBLK
@@ -368,11 +363,10 @@ __device__ __forceinline__ v4f gelu_poly4(v4f x) {
 // vmcnt bookkeeping is exact: the only vector-memory operations in the steady state are
 // PPW LDS-DMA instructions per stage and E unconditional stores per tile (rows beyond M land
 // in the slack rows every activation buffer has).
-// dbg: timing experiments only (bit0 skip epilogue, bit1 skip MFMA, bit2 skip loads).
 template <typename TIn, int EPI, int WM, int WN, int TM, int TN, int NST, int RB, int SPS>
 __global__ __launch_bounds__(WM* WN * 64) void k_gemm(const TIn* __restrict__ A, const TIn* __restrict__ W,
                                                       const float* __restrict__ bias, void* __restrict__ Cout, int M,
-                                                      int N, int K, int qscale_cols, float qscale, int dbg) {
+                                                      int N, int K, int qscale_cols, float qscale) {
     static_assert(RB == 64 || RB == 128, "stage rows are 64 or 128 bytes of K");
     constexpr int BK = RB / (int)sizeof(TIn);  // K elements per stage
     constexpr bool BF = sizeof(TIn) == 2;
@@ -459,9 +453,7 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm(const TIn* __restrict__ A,
     int it_tile = 0, it_kt = 0, gi = 0;  // gi: global stage index of the next stage to issue
     set_src(0);
     for (int p = 0; p < NST - SPS && gi < total; ++p) {
-        if (!(dbg & 4)) {
-            GM_ISSUE(it_kt, gi % NST)
-        }
+        GM_ISSUE(it_kt, gi % NST)
         ++gi;
         if (++it_kt == KT) {
             it_kt = 0;
@@ -474,8 +466,7 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm(const TIn* __restrict__ A,
         const int younger = min(Y, total - 1 - (g + SPS - 1));  // stages issued after them, allowed in flight
         // this tile's first NST-SPS stages were issued before the previous tile's epilogue stores
         const bool stores_younger = ct_tile > 0 && (kt + SPS - 1) < NST - SPS;
-        if (dbg & 5) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (stores_younger) {
+        if (stores_younger) {
             // (KT >= NST: the Y younger stages exist here)
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Y * PPW + E) : "memory");
         } else if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((Y >= 2 ? 2 : 0) * PPW) : "memory");
@@ -494,49 +485,46 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm(const TIn* __restrict__ A,
 #pragma unroll
         for (int u = 0; u < SPS; ++u)
             if (gi < total) {
-                if (!(dbg & 4)) {
-                    GM_ISSUE(it_kt, gi % NST)
-                }
+                GM_ISSUE(it_kt, gi % NST)
                 ++gi;
                 if (++it_kt == KT) {
                     it_kt = 0;
                     if (++it_tile < my_ntiles) set_src(it_tile);
                 }
             }
-        if (!(dbg & 2))
 #pragma unroll
         for (int u = 0; u < SPS; ++u) {
-        const char* Ab = smem + ((g + u) % NST) * STAGE;
-        const char* Bb = Ab + A_BYTES;
+            const char* Ab = smem + ((g + u) % NST) * STAGE;
+            const char* Bb = Ab + A_BYTES;
 #pragma unroll
-        for (int c = 0; c < CPR / 2; ++c) {
-            v4f a[TM], b[TN];
+            for (int c = 0; c < CPR / 2; ++c) {
+                v4f a[TM], b[TN];
 #pragma unroll
-            for (int m = 0; m < TM; ++m)
-                a[m] = *reinterpret_cast<const v4f*>(Ab + (RB == 64 ? swz64_byte(wr * (TM * 32) + 32 * m + fr, 2 * c + fh)
-                                                                   : swz_byte(wr * (TM * 32) + 32 * m + fr, 2 * c + fh)));
+                for (int m = 0; m < TM; ++m)
+                    a[m] = *reinterpret_cast<const v4f*>(Ab + (RB == 64 ? swz64_byte(wr * (TM * 32) + 32 * m + fr, 2 * c + fh)
+                                                                       : swz_byte(wr * (TM * 32) + 32 * m + fr, 2 * c + fh)));
 #pragma unroll
-            for (int n = 0; n < TN; ++n)
-                b[n] = *reinterpret_cast<const v4f*>(Bb + (RB == 64 ? swz64_byte(wc * (TN * 32) + 32 * n + fr, 2 * c + fh)
-                                                                   : swz_byte(wc * (TN * 32) + 32 * n + fr, 2 * c + fh)));
+                for (int n = 0; n < TN; ++n)
+                    b[n] = *reinterpret_cast<const v4f*>(Bb + (RB == 64 ? swz64_byte(wc * (TN * 32) + 32 * n + fr, 2 * c + fh)
+                                                                       : swz_byte(wc * (TN * 32) + 32 * n + fr, 2 * c + fh)));
 #pragma unroll
-            for (int m = 0; m < TM; ++m)
+                for (int m = 0; m < TM; ++m)
 #pragma unroll
-                for (int n = 0; n < TN; ++n) {
-                    // transposed product: MFMA rows <- W rows (output columns), MFMA columns <-
-                    // tokens.  Each lane then owns ONE output row (token) and 4 consecutive
-                    // output columns per register group: 16-B (fp32) / 8-B (bf16) epilogue stores.
-                    if constexpr (BF) {
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, b[n]),
-                                                                            __builtin_bit_cast(v8bf, a[m]), acc[m][n], 0, 0, 0);
-                    } else {
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[n].x, a[m].x, acc[m][n], 0, 0, 0);
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[n].y, a[m].y, acc[m][n], 0, 0, 0);
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[n].z, a[m].z, acc[m][n], 0, 0, 0);
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[n].w, a[m].w, acc[m][n], 0, 0, 0);
+                    for (int n = 0; n < TN; ++n) {
+                        // transposed product: MFMA rows <- W rows (output columns), MFMA columns <-
+                        // tokens.  Each lane then owns ONE output row (token) and 4 consecutive
+                        // output columns per register group: 16-B (fp32) / 8-B (bf16) epilogue stores.
+                        if constexpr (BF) {
+                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, b[n]),
+                                                                                __builtin_bit_cast(v8bf, a[m]), acc[m][n], 0, 0, 0);
+                        } else {
+                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[n].x, a[m].x, acc[m][n], 0, 0, 0);
+                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[n].y, a[m].y, acc[m][n], 0, 0, 0);
+                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[n].z, a[m].z, acc[m][n], 0, 0, 0);
+                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[n].w, a[m].w, acc[m][n], 0, 0, 0);
+                        }
                     }
-                }
-        }
+            }
         }
         kt += SPS;
         if (kt == KT) {
@@ -546,60 +534,58 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm(const TIn* __restrict__ A,
             const int tile = xfirst + jx + ct_tile * per_x;
             const int row0 = (tile / ntn) * BM, col0 = (tile % ntn) * BN;
             const int cbase = col0 + wc * (TN * 32) + 4 * fh;
-            if (!(dbg & 1)) {
 #pragma unroll
-                for (int m = 0; m < TM; ++m) {
-                    const size_t rbase = (size_t)(row0 + wr * (TM * 32) + 32 * m + fr) * N + cbase;  // may be a slack row
+            for (int m = 0; m < TM; ++m) {
+                const size_t rbase = (size_t)(row0 + wr * (TM * 32) + 32 * m + fr) * N + cbase;  // may be a slack row
 #pragma unroll
-                    for (int n = 0; n < TN; ++n) {
-                        uint2 packed[4];  // bf16 outputs: 4 columns per register group, packed 2 per dword
+                for (int n = 0; n < TN; ++n) {
+                    uint2 packed[4];  // bf16 outputs: 4 columns per register group, packed 2 per dword
 #pragma unroll
-                        for (int g4 = 0; g4 < 4; ++g4) {
-                            const int col = cbase + 32 * n + 8 * g4;
-                            const float4 bv = *reinterpret_cast<const float4*>(&sbias[wc * (TN * 32) + 32 * n + 8 * g4 + 4 * fh]);
-                            float4 v;
-                            v.x = acc[m][n][4 * g4 + 0] + bv.x;
-                            v.y = acc[m][n][4 * g4 + 1] + bv.y;
-                            v.z = acc[m][n][4 * g4 + 2] + bv.z;
-                            v.w = acc[m][n][4 * g4 + 3] + bv.w;
-                            if constexpr (EPI == EPI_GELU) {
-                                if constexpr (BF) {
-                                    v.x = gelu_erf_fast(v.x); v.y = gelu_erf_fast(v.y); v.z = gelu_erf_fast(v.z); v.w = gelu_erf_fast(v.w);
-                                } else {
-                                    v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w);
-                                }
-                            }
-                            if constexpr (EPI == EPI_QKV) {
-                                const float sc = col < qscale_cols ? qscale : 1.0f;  // qscale_cols is a multiple of 4
-                                v.x *= sc; v.y *= sc; v.z *= sc; v.w *= sc;
-                            }
-                            if constexpr (EPI == EPI_RESID || !BF) {
-                                *reinterpret_cast<float4*>(reinterpret_cast<float*>(Cout) + rbase + 32 * n + 8 * g4) = v;
-                            } else if constexpr (OUT16) {
-                                packed[g4].x = (unsigned)f2bf(v.x) | ((unsigned)f2bf(v.y) << 16);
-                                packed[g4].y = (unsigned)f2bf(v.z) | ((unsigned)f2bf(v.w) << 16);
+                    for (int g4 = 0; g4 < 4; ++g4) {
+                        const int col = cbase + 32 * n + 8 * g4;
+                        const float4 bv = *reinterpret_cast<const float4*>(&sbias[wc * (TN * 32) + 32 * n + 8 * g4 + 4 * fh]);
+                        float4 v;
+                        v.x = acc[m][n][4 * g4 + 0] + bv.x;
+                        v.y = acc[m][n][4 * g4 + 1] + bv.y;
+                        v.z = acc[m][n][4 * g4 + 2] + bv.z;
+                        v.w = acc[m][n][4 * g4 + 3] + bv.w;
+                        if constexpr (EPI == EPI_GELU) {
+                            if constexpr (BF) {
+                                v.x = gelu_erf_fast(v.x); v.y = gelu_erf_fast(v.y); v.z = gelu_erf_fast(v.z); v.w = gelu_erf_fast(v.w);
                             } else {
-                                ushort4 h;
-                                h.x = f2bf(v.x); h.y = f2bf(v.y); h.z = f2bf(v.z); h.w = f2bf(v.w);
-                                *reinterpret_cast<ushort4*>(reinterpret_cast<bf16_t*>(Cout) + rbase + 32 * n + 8 * g4) = h;
+                                v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w);
                             }
                         }
-                        if constexpr (OUT16) {
-                            // A lane holds columns 8 g4 + 4 fh + {0..3}; its partner (lane ^ 32) the other half of each
-                            // 8-column group.  Swap halves so that every lane stores 16 B (8 consecutive bf16): row-per-
-                            // lane 8-B stores are store-issue bound (MI355X_MICROARCH.md), 16-B stores halve the count.
+                        if constexpr (EPI == EPI_QKV) {
+                            const float sc = col < qscale_cols ? qscale : 1.0f;  // qscale_cols is a multiple of 4
+                            v.x *= sc; v.y *= sc; v.z *= sc; v.w *= sc;
+                        }
+                        if constexpr (EPI == EPI_RESID || !BF) {
+                            *reinterpret_cast<float4*>(reinterpret_cast<float*>(Cout) + rbase + 32 * n + 8 * g4) = v;
+                        } else if constexpr (OUT16) {
+                            packed[g4].x = (unsigned)f2bf(v.x) | ((unsigned)f2bf(v.y) << 16);
+                            packed[g4].y = (unsigned)f2bf(v.z) | ((unsigned)f2bf(v.w) << 16);
+                        } else {
+                            ushort4 h;
+                            h.x = f2bf(v.x); h.y = f2bf(v.y); h.z = f2bf(v.z); h.w = f2bf(v.w);
+                            *reinterpret_cast<ushort4*>(reinterpret_cast<bf16_t*>(Cout) + rbase + 32 * n + 8 * g4) = h;
+                        }
+                    }
+                    if constexpr (OUT16) {
+                        // A lane holds columns 8 g4 + 4 fh + {0..3}; its partner (lane ^ 32) the other half of each
+                        // 8-column group.  Swap halves so that every lane stores 16 B (8 consecutive bf16): row-per-
+                        // lane 8-B stores are store-issue bound (MI355X_MICROARCH.md), 16-B stores halve the count.
 #pragma unroll
-                            for (int j = 0; j < 2; ++j) {
-                                // (v_permlane32_swap_b32 does this exchange without the LDS crossbar; measured 1 % slower)
-                                const uint2 mine_a = packed[2 * j], mine_b = packed[2 * j + 1];
-                                const uint2 send = fh ? mine_a : mine_b;
-                                uint2 recv;
-                                recv.x = (unsigned)__shfl_xor((int)send.x, 32);
-                                recv.y = (unsigned)__shfl_xor((int)send.y, 32);
-                                // fh = 0 stores columns 16 j + 0..7 of the 32-column tile, fh = 1 columns 16 j + 8..15
-                                const uint4 o = fh ? make_uint4(recv.x, recv.y, mine_b.x, mine_b.y) : make_uint4(mine_a.x, mine_a.y, recv.x, recv.y);
-                                *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(Cout) + rbase - 4 * fh + 32 * n + 16 * j + 8 * fh) = o;
-                            }
+                        for (int j = 0; j < 2; ++j) {
+                            // (v_permlane32_swap_b32 does this exchange without the LDS crossbar; measured 1 % slower)
+                            const uint2 mine_a = packed[2 * j], mine_b = packed[2 * j + 1];
+                            const uint2 send = fh ? mine_a : mine_b;
+                            uint2 recv;
+                            recv.x = (unsigned)__shfl_xor((int)send.x, 32);
+                            recv.y = (unsigned)__shfl_xor((int)send.y, 32);
+                            // fh = 0 stores columns 16 j + 0..7 of the 32-column tile, fh = 1 columns 16 j + 8..15
+                            const uint4 o = fh ? make_uint4(recv.x, recv.y, mine_b.x, mine_b.y) : make_uint4(mine_a.x, mine_a.y, recv.x, recv.y);
+                            *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(Cout) + rbase - 4 * fh + 32 * n + 16 * j + 8 * fh) = o;
                         }
                     }
                 }
@@ -631,8 +617,8 @@ __global__ __launch_bounds__(512) void k_gemm16(const bf16_t* __restrict__ A, co
                                                 int K, int qscale_cols, float qscale) {
     constexpr int NW = 8, WN = 4, TM = 8, TN = 4, BM = 256, BN = 256, RB = 128;
     constexpr int A_BYTES = BM * RB, STAGE = (BM + BN) * RB, PPW = 8;
-    constexpr bool OUT32 = EPI == EPI_RESID;          // fp32 rows (verification-style residual storage)
-    constexpr int E = OUT32 ? TM * TN : 2 * TM;       // store instructions per wave per tile (vmcnt bookkeeping)
+    static_assert(EPI == EPI_QKV || EPI == EPI_GELU, "bf16 output epilogues");
+    constexpr int E = 2 * TM;                         // store instructions per wave per tile (vmcnt bookkeeping)
     static_assert(E <= 63, "vmcnt is a 6-bit counter");
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][A_BYTES | B_BYTES]
     __shared__ __attribute__((aligned(16))) float sbias[BN];
@@ -741,13 +727,12 @@ __global__ __launch_bounds__(512) void k_gemm16(const bf16_t* __restrict__ A, co
         }
         if (++kt == KT) {
             const int tile = xfirst + jx + ct_tile * per_x;
-            const int row0 = (tile / ntn) * BM + wr * 128 + lq, col0 = (tile % ntn) * BN + wc * 64;
+            const int col0 = (tile % ntn) * BN + wc * 64;
             float4 bv[TN];
 #pragma unroll
             for (int n = 0; n < TN; ++n) bv[n] = *reinterpret_cast<const float4*>(&sbias[wc * 64 + 16 * n + 4 * lg]);
 #pragma unroll
             for (int m = 0; m < TM; ++m) {
-                const size_t rbase = (size_t)(row0 + 16 * m) * N + col0;  // may be a slack row
                 char* mine = sepi[wave];
 #pragma unroll
                 for (int n = 0; n < TN; ++n) {
@@ -763,24 +748,18 @@ __global__ __launch_bounds__(512) void k_gemm16(const bf16_t* __restrict__ A, co
                         const float sc = col0 + 16 * n < qscale_cols ? qscale : 1.0f;  // qscale_cols is a multiple of 16
                         v.x *= sc; v.y *= sc; v.z *= sc; v.w *= sc;
                     }
-                    if constexpr (OUT32) {
-                        *reinterpret_cast<float4*>(reinterpret_cast<float*>(Cout) + rbase + 16 * n + 4 * lg) = v;
-                    } else {
-                        uint2 pk;
-                        pk.x = (unsigned)f2bf(v.x) | ((unsigned)f2bf(v.y) << 16);
-                        pk.y = (unsigned)f2bf(v.z) | ((unsigned)f2bf(v.w) << 16);
-                        *reinterpret_cast<uint2*>(mine + lq * EPI_ROW + (16 * n + 4 * lg) * 2) = pk;
-                    }
+                    uint2 pk;
+                    pk.x = (unsigned)f2bf(v.x) | ((unsigned)f2bf(v.y) << 16);
+                    pk.y = (unsigned)f2bf(v.z) | ((unsigned)f2bf(v.w) << 16);
+                    *reinterpret_cast<uint2*>(mine + lq * EPI_ROW + (16 * n + 4 * lg) * 2) = pk;
                 }
-                if constexpr (!OUT32) {
-                    // read the 16 x 64 block back row-wise: lane j -> row 8 t + (j >> 3), 16-B chunk j & 7
+                // read the 16 x 64 block back row-wise: lane j -> row 8 t + (j >> 3), 16-B chunk j & 7
 #pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        const int rr = 8 * t + (lane >> 3);
-                        const uint4 o = *reinterpret_cast<const uint4*>(mine + rr * EPI_ROW + (lane & 7) * 16);
-                        const size_t g = (size_t)((tile / ntn) * BM + wr * 128 + 16 * m + rr) * N + col0 + (lane & 7) * 8;
-                        *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(Cout) + g) = o;
-                    }
+                for (int t = 0; t < 2; ++t) {
+                    const int rr = 8 * t + (lane >> 3);
+                    const uint4 o = *reinterpret_cast<const uint4*>(mine + rr * EPI_ROW + (lane & 7) * 16);
+                    const size_t g = (size_t)((tile / ntn) * BM + wr * 128 + 16 * m + rr) * N + col0 + (lane & 7) * 8;
+                    *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(Cout) + g) = o;
                 }
             }
 #pragma unroll
@@ -851,12 +830,6 @@ __device__ __forceinline__ void row_stats_decode(v4u32 raw, float inv_h, float e
     rs = rsqrtf(fmaxf(var, 0.f) + eps);
     mrs = mu * rs;
 }
-__device__ __forceinline__ int g8_tile(int idx, int xfirst, int ntn, int cg, int cg_per) {
-    if (cg == 0) return xfirst + idx;
-    const int g = idx / cg_per, rem = idx - g * cg_per;
-    const int r = rem / cg, c = g * cg + (rem - r * cg);
-    return xfirst + r * ntn + c;
-}
 struct G8Side {
     const long long* stats_in;   // [T][2] raw row sums of the GEMM's input pre (AFF) / of the residual's pre (RES)
     const float* cvec;       // [N]    RES: gamma of the LayerNorm that makes the residual (its beta is in `bias`)
@@ -864,19 +837,7 @@ struct G8Side {
     long long* stats_out;    // [T][2] RES: row sums of the pre written by this GEMM; AFF: zeroed for the next EPI_RES GEMM
     float inv_h;             // 1 / hidden
     float eps;
-    int cgroup;              // > 0: tile walk in column groups of `cgroup` tile columns (see G8_TILE)
-    int grid;                // host side only: blocks to launch (0 = one per CU)
 };
-#if defined(G8_EXP) && (G8_EXP & 16)
-#define G8_SIDE_WAVES 2
-#else
-#define G8_SIDE_WAVES 6
-#endif
-// -DG8_ABL=<bits>: timing ablations of the main loop (results invalid): 1 no MFMAs, 2 no LDS fragment reads, 4 no LDS-DMA
-// issue (profiles/r04_gemm_loop_ablations.txt).  The product build has none of them.
-#ifndef G8_ABL
-#define G8_ABL 0
-#endif
 
 constexpr int G8_HT = 16384;
 constexpr int G8_A0 = 0, G8_B0 = 1, G8_B1 = 2, G8_A1 = 3;
@@ -917,15 +878,9 @@ __global__ __launch_bounds__(512) void k_gemm8p(const bf16_t* __restrict__ A, co
     const int KT = K / 64;                 // even (host check)
     const int total = my_ntiles * KT;      // K steps of this block
     if (total == 0) return;
-    // Tile walk inside the XCD's range.  Default: N-fastest, so the 32 blocks of an XCD work side by side on a few
-    // row panels x ALL tile columns -- the whole weight matrix passes through the XCD's 4 MiB L2 once per round
-    // (FFN1: 4.7 MB of weights x 18 rounds x 8 XCDs = 680 MB of L2 misses per launch for 156 MB of operands).  With
-    // side.cgroup = g (and a rectangular range: whole row panels) the XCD finishes column group 0 (g tile columns:
-    // g x 393 KB of weights, resident) for all its row panels before group 1: activations are read ntn / g times,
-    // weights once per XCD.
-    const int cg = (side.cgroup > 0 && ntn % side.cgroup == 0 && xfirst % ntn == 0 && xcount % ntn == 0) ? side.cgroup : 0;
-    const int cg_per = cg ? (xcount / ntn) * cg : 1;   // tiles per column group
-#define G8_TILE(IDX_) g8_tile((IDX_), xfirst, ntn, cg, cg_per)
+    // Tile walk inside the XCD's range: N-fastest, so the 32 blocks of an XCD work side by side on a few row panels x
+    // ALL tile columns.
+#define G8_TILE(IDX_) (xfirst + (IDX_))
 
     // ---- DMA bookkeeping: one 32-bit source offset per half-tile kind (its first 1-KiB piece; the second piece is 8
     // rows further and its swizzled chunk differs by XOR 4), advanced independently.  Rows beyond M read the slack
@@ -966,7 +921,7 @@ __global__ __launch_bounds__(512) void k_gemm8p(const bf16_t* __restrict__ A, co
 // step the cursor keeps re-reading the last tile: harmless -- the slot it lands in is never read again -- and it
 // keeps the issue free of branches)
 #define G8_ISSUE(KIND_, DB_)                                                                                  \
-    if (!(G8_ABL & 4)) {                                                                                      \
+    {                                                                                                         \
         const char* base_ = reinterpret_cast<const char*>(((KIND_) == G8_A0 || (KIND_) == G8_A1) ? A : W);    \
         const bool ablk_ = ABLK && (G8_BBLK || (KIND_) == G8_A0 || (KIND_) == G8_A1);   /* (blocked: K step = next 2-KiB block, half j = 1 follows) */ \
         const unsigned o0_ = srco[KIND_] + (unsigned)it_kt[KIND_] * (ablk_ ? 2048u : 128u);                   \
@@ -986,7 +941,7 @@ __global__ __launch_bounds__(512) void k_gemm8p(const bf16_t* __restrict__ A, co
 // side data of tile TI_ -> sbias[TI_ & 1]: 1-KiB DMA pieces, one per wave (0: bias / d row, 1: gamma row, 2..5: the
 // tile's 256 row-statistic pairs)
 #define G8_BIAS(TI_)                                                                                          \
-    if (wave < ((AFF || RES) ? G8_SIDE_WAVES : 1) && !((AFF) && wave == 1)) {                                 \
+    if (wave < ((AFF || RES) ? 6 : 1) && !((AFF) && wave == 1)) {                                             \
         const int tile_b = G8_TILE(jx + (TI_) * per_x);                                                       \
         const float* sp_ = wave == 0 ? bias + (tile_b % ntn) * BN                                             \
                          : (wave == 1 ? side.cvec + (tile_b % ntn) * BN                                       \
@@ -1044,36 +999,19 @@ __global__ __launch_bounds__(512) void k_gemm8p(const bf16_t* __restrict__ A, co
     const int a_o0 = ABLK ? wr * 8192 + lane * 16 : swz_byte(wr * 64 + lq, lg), a_o1 = ABLK ? a_o0 + 1024 : (a_o0 ^ 64);
     const int b_o0 = (ABLK && G8_BBLK) ? wc * 4096 + lane * 16 : swz_byte(wc * 32 + lq, lg), b_o1 = (ABLK && G8_BBLK) ? b_o0 + 1024 : (b_o0 ^ 64);
     v4f a[4][2], b0[2][2], b1[2][2];
-    if (G8_ABL & 2) {   // (ablation build: the fragments are never read from LDS -- opaque non-zero register contents instead)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                a[j][c] = v4f{1.25f, -0.75f, 0.5f, 2.0f};
-                asm volatile("" : "+v"(a[j][c]));
-            }
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                b0[n][c] = v4f{0.3f, 1.5f, -0.9f, 0.7f};
-                b1[n][c] = v4f{-1.1f, 0.2f, 0.6f, 1.3f};
-                asm volatile("" : "+v"(b0[n][c]), "+v"(b1[n][c]));
-            }
-    }
 #define G8_READ_A(S_, D_)                                                                                     \
-    if (!(G8_ABL & 2)) _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                        \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                         \
         a[j][0] = *reinterpret_cast<const v4f*>(smem + ((D_) * 4 + ((S_) ? G8_A1 : G8_A0)) * G8_HT + j * 2048 + a_o0); \
         a[j][1] = *reinterpret_cast<const v4f*>(smem + ((D_) * 4 + ((S_) ? G8_A1 : G8_A0)) * G8_HT + j * 2048 + a_o1); \
     }
 #define G8_READ_B(S_, D_, B_)                                                                                 \
-    if (!(G8_ABL & 2)) _Pragma("unroll") for (int n = 0; n < 2; ++n) {                                        \
+    _Pragma("unroll") for (int n = 0; n < 2; ++n) {                                                         \
         B_[n][0] = *reinterpret_cast<const v4f*>(smem + ((D_) * 4 + ((S_) ? G8_B1 : G8_B0)) * G8_HT + n * 2048 + b_o0); \
         B_[n][1] = *reinterpret_cast<const v4f*>(smem + ((D_) * 4 + ((S_) ? G8_B1 : G8_B0)) * G8_HT + n * 2048 + b_o1); \
     }
 // transposed product (MFMA rows <- W rows, columns <- tokens): a lane owns one token row and 4 consecutive columns
 #define G8_MFMA(MH_, NH_, B_)                                                                                 \
-    if (!(G8_ABL & 1)) {                                                                                      \
+    {                                                                                                         \
         __builtin_amdgcn_s_setprio(1);                                                                        \
         _Pragma("unroll") for (int c = 0; c < 2; ++c)                                                         \
             _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                     \
@@ -1097,13 +1035,8 @@ __global__ __launch_bounds__(512) void k_gemm8p(const bf16_t* __restrict__ A, co
 // row statistics of the current tile (in LDS since the previous tile's first K step): wave row 0 turns the 256 raw
 // (sum, sum^2) pairs into (rs, mu rs) in place, once per tile, during the tile's second K step; the epilogues of all
 // waves read them many barriers later.  (Inline-asm LDS access: see the header comment.)
-#if defined(G8_EXP) && (G8_EXP & 8)
-#define G8_DO_DECODE 0
-#else
-#define G8_DO_DECODE 1
-#endif
 #define G8_DECODE()                                                                                           \
-    if ((AFF || RES) && kt == 1 && wr == 0 && G8_DO_DECODE) {                                                 \
+    if ((AFF || RES) && kt == 1 && wr == 0) {                                                                 \
         const unsigned so_ = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)&sbias[ct_tile & 1][2][(wave * 64 + lane) * 4]; \
         v4u32 raw_;                                                                                           \
         asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(raw_) : "v"(so_) : "memory");      \
@@ -1243,23 +1176,13 @@ __global__ __launch_bounds__(512) void k_gemm8p(const bf16_t* __restrict__ A, co
                              : "v"(go_) : "memory");
                 const char* pb = reinterpret_cast<const char*>(side.pprev) + blk_o;
 #pragma unroll
-                for (int m = 0; m < ((G8_ABL & 8) ? 0 : 8); ++m) {
-#if defined(G8_EXP) && (G8_EXP & 2)
-                    pv[2 * m] = pv[2 * m + 1] = v4u{0u, 0u, 0u, 0u};
-#else
+                for (int m = 0; m < 8; ++m) {
                     pv[2 * m] = *reinterpret_cast<const v4u*>(pb + m * blk_m);
                     pv[2 * m + 1] = *reinterpret_cast<const v4u*>(pb + m * blk_m + 1024);
-#endif
                 }
             }
-            if (G8_ABL & 8) {   // (timing build without the epilogue's arithmetic and stores: the accumulators stay live)
 #pragma unroll
-                for (int m = 0; m < 8; ++m)
-#pragma unroll
-                    for (int n = 0; n < 4; ++n) asm volatile("" ::"v"(acc[m][n]));
-            }
-#pragma unroll
-            for (int m = 0; m < ((G8_ABL & 8) ? 0 : 8); ++m) {
+            for (int m = 0; m < 8; ++m) {
                 uint2 pk[4];
                 v4f s1v = {0.f, 0.f, 0.f, 0.f}, s2v = {0.f, 0.f, 0.f, 0.f};
                 if constexpr (RES) {
@@ -1281,10 +1204,8 @@ __global__ __launch_bounds__(512) void k_gemm8p(const bf16_t* __restrict__ A, co
                 for (int n = 0; n < 4; ++n) {
                     v4f v = acc[m][n];
                     if constexpr (AFF) {
-#if !defined(G8_EXP) || !(G8_EXP & 4)
                         const float rsn = rs_m[m] * sc[n];
                         v = __builtin_elementwise_fma(v, v4f{rsn, rsn, rsn, rsn}, dj[n]);
-#endif
                     }
                     if constexpr (RES) {
                         // acc holds branch + bias + beta; residual = gamma (p rs - mu rs) + beta
@@ -1301,9 +1222,7 @@ __global__ __launch_bounds__(512) void k_gemm8p(const bf16_t* __restrict__ A, co
                         s2v = __builtin_elementwise_fma(v, v, s2v);
                     }
                     if constexpr (DO_GELU) {
-#if !defined(G8_EXP) || !(G8_EXP & 32)
                         v = gelu_poly4(v);
-#endif
                     } else if constexpr (DO_QSCALE && !AFF) {
                         v[0] *= sc[n]; v[1] *= sc[n]; v[2] *= sc[n]; v[3] *= sc[n];
                     }
@@ -1332,11 +1251,6 @@ __global__ __launch_bounds__(512) void k_gemm8p(const bf16_t* __restrict__ A, co
                 if constexpr (OBLK) {
                     // blocked layout: this lane's two 16-byte pieces of block m, straight from the registers
                     char* cb_ = reinterpret_cast<char*>(Cout) + blk_o + m * blk_m;
-#if defined(G8_EXP) && (G8_EXP & 64)
-                    asm volatile("" ::"v"(pk[0]), "v"(pk[1]), "v"(pk[2]), "v"(pk[3]));   // (timing build: no output stores)
-                    cb_ = nullptr;
-                    if (cb_)
-#endif
                     if constexpr (RES) {
                         // a pre tensor (151 MB at 256 x 384) is the A operand of the very next GEMM: plain stores leave it in the
                         // Infinity Cache for that reader (measured in one session: 18.64 -> 18.48 ms per forward; plain stores of
@@ -1393,396 +1307,6 @@ __global__ __launch_bounds__(512) void k_gemm8p(const bf16_t* __restrict__ A, co
 #undef G8_TILE
 #undef G8_ISSUE
 #undef G8_SET_SRC
-}
-
-// ---------------------------------------------------------------- k_gemm4w: FOUR waves of 128 x 128, one per SIMD
-// The LayerNorm-folded GEMMs (blocked A, blocked weights, blocked output: EPI_AFF_* / EPI_RES) on the loop that
-// tools/gemm_lab.hip v5 measured against the 8-phase loop of k_gemm8p (round 4): per K step a 4-wave block reads 128 KB of
-// fragments from LDS instead of 192 KB (two waves x 128 x 64 per SIMD re-read what one 128 x 128 wave reads once), and
-// the loop -- bound by LDS traffic + LDS-DMA issue, profiles/r04_gemm_loop_ablations.txt -- ran 1.37-1.40 PFLOP/s against
-// 1.09-1.15 on the FFN1 shape with the epilogue switched off.  What it takes:
-//  * the 256 accumulator registers of a wave live in AGPRs: every MFMA is inline asm with a "+a" accumulator operand
-//    (hipcc left to itself keeps part of them in VGPRs and spills: gemm_lab v3, 500 TFLOP/s);
-//  * a hand-placed stream (every asm statement clobbers "memory", so the written order is the issued order): the 64
-//    MFMAs of a half K step carry the 16 fragment reads of the NEXT half step, one per 4 MFMAs (two A sets, ONE B set: B
-//    fragment n is dead behind the 8 MFMAs that use it), the second half also the 16 LDS-DMA pieces of the stage after
-//    next (saddr-form inline asm: scalar base per piece, lane * 16 as the only vector offset);
-//  * ONE block barrier per K step, in its middle: behind it stage g + 1 has landed for every wave and every wave has
-//    finished reading stage g - 1's slot;
-//  * tiles outside, K steps inside (accumulators loop-carried through the inner loop only).
-// Side data, statistics and epilogue arithmetic are k_gemm8p's (same fixed-order sums: bit-identical outputs).
-template <int EPI, int TAG = 0>
-__global__ __launch_bounds__(256) void k_gemm4w(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
-                                                const float* __restrict__ bias, bf16_t* __restrict__ Cout, int M, int N,
-                                                int K, int qscale_cols, float qscale, G8Side side) {
-    static_assert(EPI == EPI_AFF_QKV || EPI == EPI_AFF_GELU || EPI == EPI_RES, "LayerNorm-folded epilogues (blocked operands and output)");
-    constexpr bool AFF = EPI == EPI_AFF_QKV || EPI == EPI_AFF_GELU;
-    constexpr bool RES = EPI == EPI_RES;
-    constexpr bool DO_GELU = EPI == EPI_AFF_GELU;
-    constexpr bool DO_QSCALE = EPI == EPI_AFF_QKV;
-    constexpr int NW = 4, BM = 256, BN = 256, STAGE = 65536, A_BYTES = 32768;
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 stages][A: 16 blocks x 2 KiB | B: 16 blocks x 2 KiB]
-    __shared__ __attribute__((aligned(16))) float sbias[2][6][BN];   // side data of two tiles (parity): k_gemm8p's layout
-    __shared__ __attribute__((aligned(16))) float spart[NW][64 * 4];  // RES: a wave's row sums, slot = lane
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 1, wc = wave & 1;
-    const int lq = lane & 15, lg = lane >> 4;
-
-    const int ntn = N / BN, ntm = (M + BM - 1) / BM;
-    const int nwg = ntn * ntm;
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3, per_x = gridDim.x >> 3;
-    const int q = nwg / 8, r = nwg % 8;
-    const int xfirst = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int xcount = q + (xcd < r ? 1 : 0);
-    const int my_ntiles = jx < xcount ? (xcount - jx + per_x - 1) / per_x : 0;
-    const int KT = K / 64;
-    const int total = my_ntiles * KT;
-    if (total == 0) return;
-    const int cg = (side.cgroup > 0 && ntn % side.cgroup == 0 && xfirst % ntn == 0 && xcount % ntn == 0) ? side.cgroup : 0;
-    const int cg_per = cg ? (xcount / ntn) * cg : 1;
-#define G4_TILE(IDX_) g8_tile((IDX_), xfirst, ntn, cg, cg_per)
-
-    // ---- LDS-DMA: piece I (0..7: the two 1-KiB halves of this wave's four A blocks, 8..15: of its four B blocks) of stage
-    // gi into slot gi & 1.  A block = 16 rows x 64 columns of the blocked operand, 2 KiB contiguous at
-    // (row >> 4) * rowstride + (k >> 6) * 2048: the scalar base carries tile, block row and K step, the lanes only lane * 16.
-    const size_t rsK = preblk_rowstride(K);
-    const unsigned voff = (unsigned)lane * 16u;
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-    int it_tile = 0, it_kt = 0, gi = 0;
-    const char* kA;   // this wave's first A block of stage gi
-    const char* kB;
-    unsigned lds_dst;
-    auto set_stage = [&]() {
-        const int tile_ = G4_TILE(jx + it_tile * per_x);
-        const int r0_ = (tile_ / ntn) * BM, c0_ = (tile_ % ntn) * BN;
-        kA = reinterpret_cast<const char*>(A) + (size_t)((r0_ >> 4) + 4 * wave) * rsK + (size_t)it_kt * 2048;
-        kB = reinterpret_cast<const char*>(W) + (size_t)((c0_ >> 4) + 4 * wave) * rsK + (size_t)it_kt * 2048;
-        lds_dst = lds0 + (gi & 1) * STAGE + wave * 8192;
-    };
-// (s_mov, not s_add, inside the asm: an s_add would clobber SCC between an s_add_u32 / s_addc_u32 pair of the compiler's own
-// address arithmetic, which it is free to schedule around the statement -- found as wrong high address halves)
-#define G4_DMA(SBASE_, IMM_)                                                                                  \
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(SBASE_), "s"(lds_dst + (IMM_)) : "memory")
-#define G4_PIECE(I_)                                                                                          \
-    switch (I_) {                                                                                             \
-        case 0: G4_DMA(kA, 0); break;                                                                         \
-        case 1: G4_DMA(kA + 1024, 1024); break;                                                               \
-        case 2: G4_DMA(kA + rsK, 2048); break;                                                                \
-        case 3: G4_DMA(kA + rsK + 1024, 3072); break;                                                         \
-        case 4: G4_DMA(kA + 2 * rsK, 4096); break;                                                            \
-        case 5: G4_DMA(kA + 2 * rsK + 1024, 5120); break;                                                     \
-        case 6: G4_DMA(kA + 3 * rsK, 6144); break;                                                            \
-        case 7: G4_DMA(kA + 3 * rsK + 1024, 7168); break;                                                     \
-        case 8: G4_DMA(kB, 32768); break;                                                                     \
-        case 9: G4_DMA(kB + 1024, 33792); break;                                                              \
-        case 10: G4_DMA(kB + rsK, 34816); break;                                                              \
-        case 11: G4_DMA(kB + rsK + 1024, 35840); break;                                                       \
-        case 12: G4_DMA(kB + 2 * rsK, 36864); break;                                                          \
-        case 13: G4_DMA(kB + 2 * rsK + 1024, 37888); break;                                                   \
-        case 14: G4_DMA(kB + 3 * rsK, 38912); break;                                                          \
-        default: G4_DMA(kB + 3 * rsK + 1024, 39936); break;                                                   \
-    }
-    // (stages beyond the last one repeat a K step of the last tile into a slot nobody reads any more: no branches in the stream)
-#define G4_STAGE_DONE()                                                                                       \
-    {                                                                                                         \
-        ++gi;                                                                                                 \
-        if (++it_kt == KT) {                                                                                  \
-            it_kt = 0;                                                                                        \
-            if (it_tile + 1 < my_ntiles) ++it_tile;                                                           \
-        }                                                                                                     \
-        set_stage();                                                                                          \
-    }
-#define G4_ISSUE_ALL()                                                                                        \
-    G4_PIECE(0) G4_PIECE(1) G4_PIECE(2) G4_PIECE(3) G4_PIECE(4) G4_PIECE(5) G4_PIECE(6) G4_PIECE(7)          \
-    G4_PIECE(8) G4_PIECE(9) G4_PIECE(10) G4_PIECE(11) G4_PIECE(12) G4_PIECE(13) G4_PIECE(14) G4_PIECE(15)    \
-    G4_STAGE_DONE()
-    // side data of tile TI_ -> sbias[TI_ & 1]: six 1-KiB pieces (0: bias / d row, 1: gamma row (RES), 2..5: the tile's 256
-    // row-statistic pairs), piece p by wave p & 3
-#define G4_SIDE_PIECE(TI_, P_)                                                                                \
-    if (!(AFF && (P_) == 1)) {                                                                                \
-        const int tile_b = G4_TILE(jx + (TI_) * per_x);                                                       \
-        const float* sp_ = (P_) == 0 ? bias + (tile_b % ntn) * BN                                             \
-                         : ((P_) == 1 ? side.cvec + (tile_b % ntn) * BN                                       \
-                                      : reinterpret_cast<const float*>(side.stats_in + (size_t)(tile_b / ntn) * BM * 2) + ((P_) - 2) * 256);  \
-        __builtin_amdgcn_global_load_lds(                                                                     \
-            (const __attribute__((address_space(1))) void*)(sp_ + 4 * lane),                                  \
-            (__attribute__((address_space(3))) void*)(&sbias[(TI_) & 1][P_][0]), 16, 0, 0);                    \
-    }
-#define G4_SIDE(TI_)                                                                                          \
-    {                                                                                                         \
-        if (wave == 0) { G4_SIDE_PIECE(TI_, 0) G4_SIDE_PIECE(TI_, 4) }                                        \
-        else if (wave == 1) { G4_SIDE_PIECE(TI_, 1) G4_SIDE_PIECE(TI_, 5) }                                   \
-        else if (wave == 2) { G4_SIDE_PIECE(TI_, 2) }                                                         \
-        else { G4_SIDE_PIECE(TI_, 3) }                                                                        \
-    }
-
-    // ---- fragments: block b of an operand at b * 2048, its half c at + 1024, this lane's piece at lane * 16
-    unsigned fa_base[2], fb_base[2];   // [0]: the slot being multiplied, [1]: the other one; swapped after every K step
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-        fa_base[sl] = lds0 + sl * STAGE + wr * 16384 + lane * 16;
-        fb_base[sl] = lds0 + sl * STAGE + A_BYTES + wc * 16384 + lane * 16;
-    }
-    v4f acc[8][8];
-    v4f fa[2][8], fb[8];
-#define G4_MFMA(ACC_, BF_, AF_) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(ACC_) : "v"(BF_), "v"(AF_) : "memory")
-#define G4_READ(DST_, BASE_, OFF_) asm volatile("ds_read_b128 %0, %1 offset:" #OFF_ : "=v"(DST_) : "v"(BASE_) : "memory")
-    // fragment IDX_ (block) of half C_ from base BASE_
-#define G4_READ_SW(DST_, BASE_, IDX_, C_)                                                                     \
-    if ((C_) == 0) {                                                                                          \
-        switch (IDX_) {                                                                                       \
-            case 0: G4_READ(DST_, BASE_, 0); break;                                                           \
-            case 1: G4_READ(DST_, BASE_, 2048); break;                                                        \
-            case 2: G4_READ(DST_, BASE_, 4096); break;                                                        \
-            case 3: G4_READ(DST_, BASE_, 6144); break;                                                        \
-            case 4: G4_READ(DST_, BASE_, 8192); break;                                                        \
-            case 5: G4_READ(DST_, BASE_, 10240); break;                                                       \
-            case 6: G4_READ(DST_, BASE_, 12288); break;                                                       \
-            default: G4_READ(DST_, BASE_, 14336); break;                                                      \
-        }                                                                                                     \
-    } else {                                                                                                  \
-        switch (IDX_) {                                                                                       \
-            case 0: G4_READ(DST_, BASE_, 1024); break;                                                        \
-            case 1: G4_READ(DST_, BASE_, 3072); break;                                                        \
-            case 2: G4_READ(DST_, BASE_, 5120); break;                                                        \
-            case 3: G4_READ(DST_, BASE_, 7168); break;                                                        \
-            case 4: G4_READ(DST_, BASE_, 9216); break;                                                        \
-            case 5: G4_READ(DST_, BASE_, 11264); break;                                                       \
-            case 6: G4_READ(DST_, BASE_, 13312); break;                                                       \
-            default: G4_READ(DST_, BASE_, 15360); break;                                                      \
-        }                                                                                                     \
-    }
-    // side action J_ of a block that multiplies half C_; the next half is half 1 - C_ of slot SL_ (0: current, 1: other).
-    // 0..7: next A fragments; 8..14: next B fragments 0..6 (their MFMAs are done); B fragment 7 follows the block
-#define G4_FRAG(SL_, C_, J_)                                                                                  \
-    if ((J_) < 8) { G4_READ_SW(fa[1 - (C_)][(J_) & 7], fa_base[SL_], (J_) & 7, 1 - (C_)) }                     \
-    else if ((J_) < 15) { G4_READ_SW(fb[((J_) - 8) & 7], fb_base[SL_], ((J_) - 8) & 7, 1 - (C_)) }
-#define G4_FRAG_LAST(SL_, C_) G4_READ_SW(fb[7], fb_base[SL_], 7, 1 - (C_))
-#define G4_QUAD(C_, J_)                                                                                       \
-    G4_MFMA(acc[4 * ((J_) % 2) + 0][(J_) / 2], fb[(J_) / 2], fa[C_][4 * ((J_) % 2) + 0]);                     \
-    G4_MFMA(acc[4 * ((J_) % 2) + 1][(J_) / 2], fb[(J_) / 2], fa[C_][4 * ((J_) % 2) + 1]);                     \
-    G4_MFMA(acc[4 * ((J_) % 2) + 2][(J_) / 2], fb[(J_) / 2], fa[C_][4 * ((J_) % 2) + 2]);                     \
-    G4_MFMA(acc[4 * ((J_) % 2) + 3][(J_) / 2], fb[(J_) / 2], fa[C_][4 * ((J_) % 2) + 3]);
-    // accumulators := bias row of parity PAR_ (AFF: zeros; the d row is applied in the epilogue)
-#define G4_ACC_FROM_BIAS(PAR_)                                                                                \
-    {                                                                                                         \
-        _Pragma("unroll") for (int n = 0; n < 8; ++n) {                                                       \
-            v4f bv_ = v4f{0.f, 0.f, 0.f, 0.f};                                                                \
-            if constexpr (!AFF) bv_ = *reinterpret_cast<const v4f*>(&sbias[PAR_][0][wc * 128 + 16 * n + 4 * lg]); \
-            _Pragma("unroll") for (int m = 0; m < 8; ++m) acc[m][n] = bv_;                                    \
-        }                                                                                                     \
-        asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");   /* (accumulator writes -> MFMAs inside asm: no hazard pass sees them) */ \
-    }
-    // EPI_RES: statistics of the PREVIOUS tile (partials of the wave row's two waves in spart since that tile's epilogue)
-    // -> one fixed-order sum per row, then fixed-point integer atomics.  Wave wc handles slots 32 wc .. 32 wc + 31
-    // (slot s = rows s and 64 + s of the wave row's 128-row block).
-    int flush_row0 = 0;
-#define G4_STATS_FLUSH()                                                                                      \
-    if constexpr (RES) {                                                                                      \
-        if (lane < 32) {                                                                                      \
-            const int sl_ = 32 * wc + lane;                                                                   \
-            const v4f q0_ = *reinterpret_cast<const v4f*>(&spart[2 * wr][sl_ * 4]);                            \
-            const v4f q1_ = *reinterpret_cast<const v4f*>(&spart[2 * wr + 1][sl_ * 4]);                        \
-            const v4f t_ = q0_ + q1_;                                                                         \
-            unsigned long long* so_ = reinterpret_cast<unsigned long long*>(side.stats_out) + (size_t)(flush_row0 + sl_) * 2; \
-            atomicAdd(so_, (unsigned long long)__float2ll_rn(t_[0] * kStatScale1));                           \
-            atomicAdd(so_ + 1, (unsigned long long)__float2ll_rn(t_[1] * kStatScale2));                       \
-            atomicAdd(so_ + 128, (unsigned long long)__float2ll_rn(t_[2] * kStatScale1));                     \
-            atomicAdd(so_ + 129, (unsigned long long)__float2ll_rn(t_[3] * kStatScale2));                     \
-        }                                                                                                     \
-    }
-
-    // ---- prologue: side data of tile 0, stages 0 and 1 on their way; stage 0 landed for everybody; its half 0 read
-    set_stage();
-    G4_SIDE(0)
-    G4_ISSUE_ALL()
-    G4_ISSUE_ALL()
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        G4_READ_SW(fa[0][j], fa_base[0], j, 0)
-        G4_READ_SW(fb[j], fb_base[0], j, 0)
-    }
-    G4_ACC_FROM_BIAS(0)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-
-    for (int ct_tile = 0; ct_tile < my_ntiles; ++ct_tile) {
-#pragma unroll 1
-        for (int kt = 0; kt < KT; ++kt) {
-            // ---- block (g, 0): MFMAs on A set 0, the half-1 fragments of this stage behind them
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                // (B fragment 7 was read behind the previous block, 14 reads ago, and is multiplied from here on)
-                if (j == 14) asm volatile("s_waitcnt lgkmcnt(14)" ::: "memory");
-                G4_QUAD(0, j)
-                G4_FRAG(0, 0, j)
-            }
-            G4_FRAG_LAST(0, 0)
-            // ---- middle of the step
-            // (vmcnt(0) also behind an epilogue: its stores may complete before the older LDS-DMA pieces -- loads and stores are
-            // not ordered against each other -- so a count that lets "the 32 stores" stay outstanding proves nothing)
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (kt == 0 && ct_tile + 1 < my_ntiles) G4_SIDE(ct_tile + 1)
-            if ((AFF || RES) && kt == 1) {   // raw (sum, sum^2) pairs -> (rs, mu rs) in place: 64 rows per wave
-                float* sp_ = &sbias[ct_tile & 1][2][(wave * 64 + lane) * 4];
-                const v4u32 raw_ = *reinterpret_cast<const v4u32*>(sp_);
-                float rs_, mrs_;
-                row_stats_decode(raw_, side.inv_h, side.eps, rs_, mrs_);
-                sp_[0] = rs_;
-                sp_[1] = mrs_;
-            }
-            if (RES && kt == 2 && ct_tile > 0) G4_STATS_FLUSH()
-            // ---- block (g, 1): MFMAs on A set 1, the half-0 fragments of stage g + 1 behind them, the DMA of stage g + 2
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                G4_QUAD(1, j)
-                G4_FRAG(1, 1, j)
-                G4_PIECE(j)
-            }
-            G4_FRAG_LAST(1, 1)
-            G4_STAGE_DONE()
-            asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory");   // everything but B fragment 7 (used last) is there
-            {
-                const unsigned ta = fa_base[0], tb = fb_base[0];
-                fa_base[0] = fa_base[1];
-                fa_base[1] = ta;
-                fb_base[0] = fb_base[1];
-                fb_base[1] = tb;
-            }
-        }
-        // ---- epilogue of output tile ct_tile: k_gemm8p's arithmetic on the wave's two 64-column strips
-        asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");   // (the last MFMAs inside asm -> accumulator reads: no hazard pass sees them)
-        {
-            const int tile = G4_TILE(jx + ct_tile * per_x);
-            const int par = ct_tile & 1;
-            typedef unsigned v4u __attribute__((ext_vector_type(4)));
-            typedef float v2f __attribute__((ext_vector_type(2)));
-            const size_t blk_m = preblk_rowstride(N);
-            float keep[4] = {0.f, 0.f, 0.f, 0.f};   // row sums this lane reports: rows lq + 16 (lg + 4 j), (sum, sum^2)
-            if constexpr (AFF) {
-                // statistics the next EPI_RES GEMM adds into: zero this tile's rows (first tile column, wave column 0)
-                if (tile % ntn == 0 && wc == 0) {
-                    v4u* zp = reinterpret_cast<v4u*>(side.stats_out + (size_t)((tile / ntn) * BM + wr * 128) * 2);
-                    zp[lane] = v4u{0u, 0u, 0u, 0u};
-                    zp[lane + 64] = v4u{0u, 0u, 0u, 0u};
-                }
-            }
-            const float* rsp = &sbias[par][2][(wr * 128 + lq) * 4];   // (rs, mu rs) of row block m at + 64 m floats
-#ifndef G4_DBG
-#define G4_DBG 0   // -DG4_DBG=1: timing build without the epilogue's arithmetic and stores (results invalid)
-#endif
-#pragma unroll
-            for (int h = 0; h < (G4_DBG & 1 ? 0 : 2); ++h) {
-                const int w64 = 2 * wc + h;   // the 64-column strip of the tile (k_gemm8p's wave column)
-                const int col0 = (tile % ntn) * BN + w64 * 64;
-                float sc[4];
-#pragma unroll
-                for (int n = 0; n < 4; ++n) sc[n] = (DO_QSCALE && col0 + 16 * n < qscale_cols) ? qscale : 1.0f;
-                v4f dj[4], gj[4];
-                if constexpr (AFF) {
-#pragma unroll
-                    for (int n = 0; n < 4; ++n) dj[n] = *reinterpret_cast<const v4f*>(&sbias[par][0][w64 * 64 + 16 * n + 4 * lg]) * sc[n];
-                }
-                const size_t blk_o = (size_t)(((tile / ntn) * BM + wr * 128) >> 4) * blk_m + (size_t)((tile % ntn) * 4 + w64) * 2048 + lane * 16;
-                v4u pv[16];
-                if constexpr (RES) {
-#pragma unroll
-                    for (int n = 0; n < 4; ++n) gj[n] = *reinterpret_cast<const v4f*>(&sbias[par][1][w64 * 64 + 16 * n + 4 * lg]);
-                    const char* pb = reinterpret_cast<const char*>(side.pprev) + blk_o;
-#pragma unroll
-                    for (int m = 0; m < 8; ++m) {
-                        pv[2 * m] = *reinterpret_cast<const v4u*>(pb + m * blk_m);
-                        pv[2 * m + 1] = *reinterpret_cast<const v4u*>(pb + m * blk_m + 1024);
-                    }
-                }
-#pragma unroll
-                for (int m = 0; m < 8; ++m) {
-                    uint2 pk[4];
-                    v4f s1v = {0.f, 0.f, 0.f, 0.f}, s2v = {0.f, 0.f, 0.f, 0.f};
-                    const v2f st = *reinterpret_cast<const v2f*>(rsp + 64 * m);
-                    const float rs_ = st[0], mrs_ = st[1];
-#pragma unroll
-                    for (int n = 0; n < 4; ++n) {
-                        v4f v = acc[m][4 * h + n];
-                        if constexpr (AFF) {
-                            const float rsn = rs_ * sc[n];
-                            v = __builtin_elementwise_fma(v, v4f{rsn, rsn, rsn, rsn}, dj[n]);
-                        }
-                        if constexpr (RES) {
-                            // acc holds branch + bias + beta; residual = gamma (p rs - mu rs) + beta
-                            const unsigned pwx = pv[2 * m + (n >> 1)][2 * (n & 1)], pwy = pv[2 * m + (n >> 1)][2 * (n & 1) + 1];
-                            v4f pf;
-                            pf[0] = __uint_as_float(pwx << 16);
-                            pf[1] = __uint_as_float(pwx & 0xFFFF0000u);
-                            pf[2] = __uint_as_float(pwy << 16);
-                            pf[3] = __uint_as_float(pwy & 0xFFFF0000u);
-                            const v4f u = __builtin_elementwise_fma(pf, v4f{rs_, rs_, rs_, rs_}, v4f{-mrs_, -mrs_, -mrs_, -mrs_});
-                            v = __builtin_elementwise_fma(gj[n], u, v);
-                            s1v += v;
-                            s2v = __builtin_elementwise_fma(v, v, s2v);
-                        }
-                        if constexpr (DO_GELU) v = gelu_poly4(v);
-                        pk[n].x = (unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16);
-                        pk[n].y = (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16);
-                    }
-                    if constexpr (RES) {
-                        // row sums over this strip's 64 columns: 4 values per lane, then the 4 lanes lg = 0..3 of the row
-                        float r1 = (s1v[0] + s1v[1]) + (s1v[2] + s1v[3]), r2 = (s2v[0] + s2v[1]) + (s2v[2] + s2v[3]);
-                        {
-                            const auto a1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(r1), __float_as_uint(r1), false, false);
-                            const auto a2 = __builtin_amdgcn_permlane16_swap(__float_as_uint(r2), __float_as_uint(r2), false, false);
-                            r1 = __uint_as_float(a1[0]) + __uint_as_float(a1[1]);
-                            r2 = __uint_as_float(a2[0]) + __uint_as_float(a2[1]);
-                            const auto b1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(r1), __float_as_uint(r1), false, false);
-                            const auto b2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(r2), __float_as_uint(r2), false, false);
-                            r1 = __uint_as_float(b1[0]) + __uint_as_float(b1[1]);
-                            r2 = __uint_as_float(b2[0]) + __uint_as_float(b2[1]);
-                        }
-                        if (lg == (m & 3)) {
-                            keep[2 * (m >> 2)] += r1;       // (strip 0 then strip 1: k_gemm8p adds its four strips in that order too)
-                            keep[2 * (m >> 2) + 1] += r2;
-                        }
-                    }
-                    char* cb_ = reinterpret_cast<char*>(Cout) + blk_o + m * blk_m;
-                    if constexpr (RES) {   // (a pre tensor is the A operand of the very next GEMM: plain stores, see k_gemm8p)
-                        *reinterpret_cast<v4u*>(cb_) = v4u{pk[0].x, pk[0].y, pk[1].x, pk[1].y};
-                        *reinterpret_cast<v4u*>(cb_ + 1024) = v4u{pk[2].x, pk[2].y, pk[3].x, pk[3].y};
-                    } else {
-                        __builtin_nontemporal_store(v4u{pk[0].x, pk[0].y, pk[1].x, pk[1].y}, reinterpret_cast<v4u*>(cb_));
-                        __builtin_nontemporal_store(v4u{pk[2].x, pk[2].y, pk[3].x, pk[3].y}, reinterpret_cast<v4u*>(cb_ + 1024));
-                    }
-                }
-            }
-            if constexpr (RES) {
-                *reinterpret_cast<v4f*>(&spart[wave][lane * 4]) = v4f{keep[0], keep[1], keep[2], keep[3]};
-                flush_row0 = __builtin_amdgcn_readfirstlane((tile / ntn) * BM + wr * 128);
-            }
-            G4_ACC_FROM_BIAS((ct_tile + 1) & 1)
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // (the surplus DMA pieces and fragment reads)
-    if constexpr (RES) {   // statistics of the block's last tile
-        __builtin_amdgcn_s_barrier();
-        G4_STATS_FLUSH()
-    }
-#undef G4_TILE
-#undef G4_DMA
-#undef G4_PIECE
-#undef G4_STAGE_DONE
-#undef G4_ISSUE_ALL
-#undef G4_SIDE_PIECE
-#undef G4_SIDE
-#undef G4_MFMA
-#undef G4_READ
-#undef G4_READ_SW
-#undef G4_FRAG
-#undef G4_FRAG_LAST
-#undef G4_QUAD
-#undef G4_ACC_FROM_BIAS
-#undef G4_STATS_FLUSH
 }
 
 // ---------------------------------------------------------------- skinny GEMM (M <= 64 tokens)
@@ -1902,7 +1426,7 @@ __device__ __forceinline__ int vswz_byte(int row, int chunk) { return row * 128 
 // caller checks sum in (2^-100, 2^100) for every query of the block and otherwise repeats the block with SAFE =
 // true, the online softmax with a running maximum (reference 0 until a score exceeds it).  Attention logits of
 // a trained encoder are a few tens at most (|score| < 69 = 100 ln 2 is the fast path's range), so the repeat is a
-// guard, not a path that runs; tests force it with CSS_ATT_RANGE=0.
+// guard, not a path that runs; tests force it with css_encoder_set_attention_range(e, 0).
 // BLK: qkv is in the blocked layout of k_gemm8p's EPI_AFF_QKV epilogue (preblk_elem with H = 3 * hidden: head h of
 // q / k / v = block column h / heads + h / 2 heads + h; 16-byte piece cl = 4 j + lg of a token = dims 32 j + 4 lg + {0..3}
 // and 32 j + 16 + 4 lg + {0..3}).  K tile rows in LDS keep the pieces in piece order (the q fragments are the same pieces
@@ -1991,7 +1515,6 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
 
     int cur = 0;
     for (int kt = 0; kt < nkt; ++kt) {
-#if !defined(ATT_DBG) || !(ATT_DBG & (1 | 128))
         if (kt + 1 < nkt) {
             if constexpr (BLK) {
                 AT_DMA(kt + 1, cur ^ 1)   // (buffer cur ^ 1 was last read in tile kt - 1, behind that tile's barrier)
@@ -1999,7 +1522,6 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
                 AT_GLOAD(kt + 1)
             }
         }
-#endif
         const char* Kb = Ks + cur * 8192;
         const char* Vb = Vs + cur * 8192;
 
@@ -2016,12 +1538,8 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
                 const float* bl = bt + (key0 + 4 * fh - qic + (maxL - 1));
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {   // (the table has 64 entries of padding)
-#if defined(ATT_DBG) && (ATT_DBG & 4)
-                    s[r] = 0.f;
-#else
                     if constexpr (SAFE) s[r] = bl[(r & 3) + 8 * (r >> 2)] - mrun;
                     else s[r] = bl[(r & 3) + 8 * (r >> 2)];
-#endif
                 }
                 if (key0 + 32 > L) {
 #pragma unroll
@@ -2029,14 +1547,12 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
                         if (key0 + 4 * fh + (r & 3) + 8 * (r >> 2) >= L) s[r] = -INFINITY;
                 }
             }
-#if !defined(ATT_DBG) || !(ATT_DBG & 32)
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const v4f kf = *reinterpret_cast<const v4f*>(Kb + (BLK ? (2 * sub + (fr >> 4)) * 2048 + (2 * ks + fh) * 256 + (fr & 15) * 16
                                                                        : swz_byte(sub * 32 + fr, 2 * ks + fh)));
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, kf), __builtin_bit_cast(v8bf, qf[ks]), s, 0, 0, 0);
             }
-#endif
             if constexpr (SAFE) {
                 float mloc = s[0];
 #pragma unroll
@@ -2067,13 +1583,7 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
             float lsum0 = 0.f, lsum1 = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
-#if defined(ATT_DBG) && (ATT_DBG & 2)
-                const float p0 = s[r], p1 = s[r + 1];
-#elif defined(ATT_DBG) && (ATT_DBG & 64)
-                const float p0 = s[r] * s[r], p1 = s[r + 1] * s[r + 1];
-#else
                 const float p0 = __builtin_amdgcn_exp2f(s[r]), p1 = __builtin_amdgcn_exp2f(s[r + 1]);
-#endif
                 s[r] = p0;
                 s[r + 1] = p1;
                 lsum0 += p0;
@@ -2086,9 +1596,6 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
                 v8bf pf;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) pf[j] = (__bf16)s[8 * st + j];
-#if defined(ATT_DBG) && (ATT_DBG & 8)
-                oacc[st][0] += (float)pf[0] + (float)pf[7];
-#else
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
                     // lane (d = 32*mt + fr, half fh): keys {16st+4fh+0..3} and {16st+8+4fh+0..3}
@@ -2107,20 +1614,15 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
                     const v8bf vf = __builtin_bit_cast(v8bf, both);
                     oacc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[mt], 0, 0, 0);
                 }
-#endif
             }
         }
-#if !defined(ATT_DBG) || !(ATT_DBG & (16 | 128))
         if constexpr (BLK) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the next tile have landed
         } else if (kt + 1 < nkt) {
             AT_SSTORE(cur ^ 1)
         }
         __syncthreads();
-#endif
-#if !defined(ATT_DBG) || !(ATT_DBG & 128)
         cur ^= 1;
-#endif
     }
 #undef AT_GLOAD
 #undef AT_SSTORE

@@ -22,7 +22,7 @@
 //                      flagged queries): 16 lanes per row, VALU FMAs, DPP row reduction,
 //                      block-shared sorted top-k lists in LDS, grid-wide threshold.   HBM bound
 //   k_scan_mfma_split  exact batched scan on split bf16 operands (3 MFMAs per product);
-//   k_scan_mfma        the same on fp32-input MFMA (CSS_KNN_BATCH=fp32, verification)
+//   k_scan_mfma        the same on fp32-input MFMA (CSS_SEARCH_EXACT_FP32, verification)
 //   k_merge_final      per query: merge the per-block lists into the final top-k.
 #include "css_common.h"
 #include "css_knn_kernels.h"
@@ -644,7 +644,7 @@ __global__ __launch_bounds__(256, 1) void k_scan_mfma(const float* __restrict__ 
         // Measured at 10 M rows x 256 queries (rocprofv3 --pmc FETCH_SIZE, 30.72 GB algorithmic): unpaced 52.0 GB
         // (1.69 x) in 49.0 ms; poll 8 / lag 12: 34.0 GB (1.11 x) in 50.6 ms; poll 4 / lag 8: 33.2 GB, 51.9 ms; poll
         // 16 / lag 16: 43.0 GB, 49.8 ms.  The kernel is bound by the fp32 MFMA pipe, not by HBM, so the saved traffic
-        // buys no time here (it frees HBM for whatever else runs on the chip); CSS_KNN_PACE=0 turns it off.
+        // buys no time here (it frees HBM for whatever else runs on the chip).
         // The look is issued here and used after the MFMAs of the step; the spin is bounded, so a sibling that is
         // not resident only costs a wait.
         int sib_lo = 1 << 30;
@@ -1393,15 +1393,19 @@ bool want_shadow(css_index* ix, int64_t ncap) {
     return (double)ncap * ix->dpad * 6.0 <= 0.8 * (double)tot;
 }
 
-// int8 rows for the 1..4-query sweep (k_sweep_coarse_i8): only next to bf16 shadow rows, rows of at most 1024
-// elements (the fp32 accumulation term of the sweep's error bound, cz_eps) and 7 bytes per element within 80 % of the HBM
-// (CSS_KNN_I8=0 switches them off).
-bool want_i8(css_index* ix, int64_t ncap) {
-    static const bool env_on = [] {
+// CSS_KNN_I8=0 switches every int8 row copy off (read once)
+bool i8_rows_allowed() {
+    static const bool on = [] {
         const char* e = getenv("CSS_KNN_I8");
         return !(e && e[0] == '0');
     }();
-    if (!env_on || ix->dpad % 64 != 0 || ix->dpad > 1024) return false;
+    return on;
+}
+
+// int8 rows for the 1..4-query sweep (k_sweep_coarse_i8): only next to bf16 shadow rows, rows of at most 1024
+// elements (the fp32 accumulation term of the sweep's error bound, cz_eps) and 7 bytes per element within 80 % of the HBM.
+bool want_i8(css_index* ix, int64_t ncap) {
+    if (!i8_rows_allowed() || ix->dpad % 64 != 0 || ix->dpad > 1024) return false;
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) return false;
     return (double)ncap * ix->dpad * 7.0 <= 0.8 * (double)tot;
@@ -1413,11 +1417,7 @@ bool want_i8(css_index* ix, int64_t ncap) {
 // product, rows a whole number of 256-element K-step pairs, at most 1024 elements); css_index_set_shadow(ix, 2) forces
 // it (tests), policy 0 forbids every shadow copy.
 bool want_i8_only(css_index* ix, int64_t ncap) {
-    static const bool env_on = [] {
-        const char* e = getenv("CSS_KNN_I8");
-        return !(e && e[0] == '0');
-    }();
-    if (!env_on || ix->metric != CSS_METRIC_IP || ix->dpad % 256 != 0 || ix->dpad > 1024) return false;
+    if (!i8_rows_allowed() || ix->metric != CSS_METRIC_IP || ix->dpad % 256 != 0 || ix->dpad > 1024) return false;
     if (ix->shadow_policy == 0) return false;
     if (ix->shadow_policy == 2) return true;
     if (ix->shadow_policy == 1) return false;   // "always bf16" that did not fit: nothing
@@ -1541,36 +1541,22 @@ int ingest(css_index* ix, const float* x_dev, int64_t n, int normalize, bool syn
     return CSS_OK;
 }
 
-// ---- environment switches (experiments and verification): read once, never written afterwards
+// ---- environment switches (benchmark labels and forced test paths): read once, never written afterwards
 struct KnnEnv {
-    int batch = 0;        // CSS_KNN_BATCH: "split" = 1 (split-operand candidate scan for every batch), "fp32" = 2 (fp32-MFMA scan)
-    bool exact_k = true;        // CSS_KNN_EXACTK=0: two-eps thresholds from coarse scores only in the int8 scan's selects
     int batch_i8 = 1;           // CSS_KNN_SCAN=bf16 / i8: batches always scan the bf16 / the int8 shadow rows (1 = where it pays)
     bool sweep_i8 = true;       // CSS_KNN_SWEEP=bf16: 1..4 queries sweep the bf16 shadow rows even where int8 rows exist (A/B runs)
-    bool eps_measured = true;   // CSS_KNN_EPS=apriori: unit-roundoff error band instead of the measured one (cz_eps)
     int growth = 0;       // CSS_KNN_GROWTH=4|8|16: growth factor of the nested row sample (batched MFMA cascade); 0: by k
     int growth_sweep = 0;   // CSS_KNN_GROWTH_SWEEP=4|8|16: the same for the few-query sweep cascades (0 = by shape: launch_scan_coarse)
     int sweep_fused = 1;    // CSS_KNN_SWEEP_FUSED=0 / 2: the 1..4-query cascade never / always as ONE launch (k_sweep_cascade); 1 = where it pays
     int qreg = 1;           // CSS_KNN_QREG=0: the int8 batch scan's later stages on k_scan_coarse8 instead of k_scan_qreg_i8 (A/B runs)
     int qreg_min = 1024;    // CSS_KNN_QREG_MIN=<tile tasks>: stages with fewer (row tile, query tile) pairs stay on k_scan_coarse8 (two per block: measured, launch_scan_coarse)
     int sweep_mfma = 1;     // CSS_KNN_SWEEP_MFMA=0: 3..32 queries never take the int8-MFMA sweep (A/B runs); 2: at every index size (tests)
-    int sweep_maxq = -1;    // CSS_KNN_SWEEP_MAXQ=n: searches of up to n (0..4) queries take the sweep cascade (A/B runs); -1 = by size
     int fs_spins = CZ_FS_SPINS;   // CSS_KNN_FS_SPINS=n: polls before a waiting wave of k_sweep_cascade gives up (tests: 0 = at once)
-    int fs_blocks = 0;      // CSS_KNN_FS_BLOCKS=n: at most n blocks of k_sweep_cascade per CU (A/B runs); 0 = what fits
-    int mfma_shape = 16;  // CSS_KNN_MFMA=32: 32x32x16 MFMA in k_scan_coarse (A/B runs)
-    int pacing = 1;       // CSS_KNN_PACE=0: no sibling pacing in k_scan_coarse (A/B runs)
-    int dbg = 0;          // CSS_KNN_DBG: timing ablations of k_scan_coarse (results are wrong when set)
-    int loop8 = 1;        // CSS_KNN_LOOP=old: the round-1 main loop (k_scan_coarse) instead of k_scan_coarse8 (A/B runs)
-    int pass2 = 1;        // CSS_KNN_PASS2=0: flagged queries go straight to the exact fp32 sweep (A/B runs)
-    int noshadow_ranges = 1;   // CSS_KNN_NOSHADOW=split: shadow-less batches through the split-operand scan (A/B runs)
 };
 const KnnEnv& knn_env() {
     static const KnnEnv env = [] {
         KnnEnv e;
-        if (const char* m = getenv("CSS_KNN_BATCH")) e.batch = std::string(m) == "split" ? 1 : (std::string(m) == "fp32" ? 2 : 0);
-        if (const char* m = getenv("CSS_KNN_EPS")) e.eps_measured = strcmp(m, "apriori") != 0;
         if (const char* m = getenv("CSS_KNN_SWEEP")) e.sweep_i8 = strcmp(m, "bf16") != 0;
-        if (const char* m = getenv("CSS_KNN_EXACTK")) e.exact_k = m[0] != '0';
         if (const char* m = getenv("CSS_KNN_SCAN")) e.batch_i8 = strcmp(m, "bf16") == 0 ? 0 : (strcmp(m, "i8") == 0 ? 2 : 1);
         if (const char* m = getenv("CSS_KNN_GROWTH")) {
             const int v = atoi(m);
@@ -1581,18 +1567,10 @@ const KnnEnv& knn_env() {
             e.growth_sweep = (v == 4 || v == 8 || v == 16) ? v : 0;
         }
         if (const char* m = getenv("CSS_KNN_SWEEP_FUSED")) e.sweep_fused = m[0] == '0' ? 0 : (m[0] == '2' ? 2 : 1);
-        if (const char* m = getenv("CSS_KNN_FS_BLOCKS")) e.fs_blocks = std::max(0, atoi(m));
         if (const char* m = getenv("CSS_KNN_FS_SPINS")) e.fs_spins = std::max(0, atoi(m));
         if (const char* m = getenv("CSS_KNN_QREG")) e.qreg = m[0] == '0' ? 0 : 1;
         if (const char* m = getenv("CSS_KNN_QREG_MIN")) e.qreg_min = std::max(0, atoi(m));
         if (const char* m = getenv("CSS_KNN_SWEEP_MFMA")) e.sweep_mfma = m[0] == '0' ? 0 : (m[0] == '2' ? 2 : 1);
-        if (const char* m = getenv("CSS_KNN_SWEEP_MAXQ")) e.sweep_maxq = std::min(4, std::max(0, atoi(m)));
-        if (const char* m = getenv("CSS_KNN_MFMA")) e.mfma_shape = atoi(m) == 32 ? 32 : 16;
-        if (const char* m = getenv("CSS_KNN_PACE")) e.pacing = m[0] == '0' ? 0 : 1;
-        if (const char* m = getenv("CSS_KNN_DBG")) e.dbg = atoi(m);
-        if (const char* m = getenv("CSS_KNN_LOOP")) e.loop8 = std::string(m) == "old" ? 0 : 1;
-        if (const char* m = getenv("CSS_KNN_PASS2")) e.pass2 = m[0] == '0' ? 0 : 1;
-        if (const char* m = getenv("CSS_KNN_NOSHADOW")) e.noshadow_ranges = std::string(m) == "split" ? 0 : 1;
         return e;
     }();
     return env;
@@ -1739,7 +1717,7 @@ constexpr int kSplitExtra = 4;
 // 144 fp32 accumulation steps 2^-16.8 -- together < 3.6 x 2^-16; 2^-14 leaves a margin
 constexpr float kSplitEps = 6.103515625e-05f;
 
-// Exact fp32 batched scan (CSS_SEARCH_EXACT_FP32 with more than 16 queries, CSS_KNN_BATCH=fp32):
+// Exact fp32 batched scan (CSS_SEARCH_EXACT_FP32 with more than 16 queries):
 // v_mfma_f32_32x32x2_f32, bit-exact fmaf chains, scores written as they are.
 template <int METRIC>
 int launch_scan_fp32mfma(css_index* ix, int nq, int k, float* D_dev, int64_t* I_dev, hipStream_t st) {
@@ -1761,7 +1739,7 @@ int launch_scan_fp32mfma(css_index* ix, int nq, int k, float* D_dev, int64_t* I_
     if ((rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
     // sibling pacing (see the kernel) where a strip has siblings; the counters share the cascade's pacing words
     int* pace = nullptr;
-    if (knn_env().pacing && nqtiles > 1 && nstrips * nqtiles <= ix->num_cus) {   // (all blocks resident: one per CU)
+    if (nqtiles > 1 && nstrips * nqtiles <= ix->num_cus) {   // (all blocks resident: one per CU)
         if ((rc = grow(&ix->cpace, &ix->cpace_cap, (size_t)nstrips * nqtiles)) != CSS_OK) return rc;
         pace = ix->cpace;
         CSS_HIP_TRY(hipMemsetAsync(pace, 0, (size_t)nstrips * nqtiles * sizeof(int), st));
@@ -1793,7 +1771,7 @@ constexpr int kRescoreGrid = 4096;
 struct EpsSet {   // what cz_eps needs to know about the operands a scan read
     float eps_rel;        // a-priori bound relative to ||q|| max||x||
     const float* qerr2;   // per query ||q - q^||^2 (null: fp32 queries)
-    int measured;         // 0: a-priori only; else the word of maxn2 with the rows' measured error (1 bf16, 2 int8)
+    int measured;         // the word of maxn2 with the rows' measured error (1 bf16, 2 int8)
 };
 int launch_final_select(css_index* ix, int nq, int k, EpsSet e1, EpsSet e2, bool exact_k, int l2, int closed_n,
                         const float* qpad, const float* qnorm2, int* gthr, int* flags, int* nflag, int* flag_list, float* D_dev, int64_t* I_dev, float* thr2,
@@ -1968,8 +1946,7 @@ inline bool sweep_uses_i8(css_index* ix) {
 // (`rows`: the rows one cascade covers -- the index, or one range of a shadow-less index)
 inline bool batch_i8_wanted(css_index* ix, int k, int64_t rows, int64_t nq) {
     const KnnEnv& e = knn_env();
-    if (e.batch_i8 == 0 || ix->metric != CSS_METRIC_IP || ix->dpad % 256 != 0 || ix->dpad > 1024 || !e.loop8 || e.mfma_shape != 16)
-        return false;
+    if (e.batch_i8 == 0 || ix->metric != CSS_METRIC_IP || ix->dpad % 256 != 0 || ix->dpad > 1024) return false;
     if (e.batch_i8 == 2) return true;
     // (round 4, later stages on k_scan_qreg_i8, ms int8 / bf16: k = 100, 1000 queries: 4 M rows 4.1 / 6.1, 2 M 2.7 / 3.3, 1 M 2.0 /
     // 2.0, 300 k 1.3 / 0.9; 256 queries: 2 M 1.0 / 1.4, 1 M 0.87 / 0.75.  k = 10: 1 M 1.04 / 1.57, 300 k 0.53 / 0.64 (256 queries
@@ -2001,7 +1978,7 @@ int launch_sweep_coarse_nq(css_index* ix, const float* qpad, int nq, int64_t cou
 }
 
 // 3..32 queries, inner product, int8 rows in view: does the sweep on the int8 MFMA (k_sweep_mfma_i8) answer sooner than what
-// it replaces -- the VALU sweep (3, 4 queries) or the 256-query tiles of the batch scan?  tools/knn_fewq_probe.py, one
+// it replaces -- the VALU sweep (3, 4 queries) or the 256-query tiles of the batch scan?  One
 // session, ms with / without, 3 .. 16 queries: 10 M rows k = 10 1.65 / 1.92-2.07, k = 100 1.83-1.85 / 2.75-3.26; 1 M rows
 // 0.32-0.33 / 0.34-0.41 and 0.46-0.48 / 0.45-0.58; 100 k rows 0.13-0.14 / 0.15-0.16 but 0.22 / 0.18-0.20 at k = 100 (a
 // select with 100 exactly scored rows behind every stage); 20 k rows 0.11-0.12 / 0.11 and 0.17-0.19 / 0.13-0.15.
@@ -2087,7 +2064,6 @@ int launch_sweep_cascade_t(css_index* ix, const float* qpad, int nq, const FsSch
         per_cu_cached = 1;
     int per_cu = per_cu_cached;
     per_cu = std::min(per_cu, 3);   // (12 waves per CU already draw the whole HBM rate: 2 / 3 / 4 blocks 1.305 / 1.302 / 1.316 ms at 10 M rows)
-    if (const int cap = knn_env().fs_blocks) per_cu = std::min(per_cu, cap);
     const int grid = (int)std::min<int64_t>((int64_t)ix->num_cus * std::min(per_cu, 8), (sc.first[sc.nstage] + 3) / 4);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, I8 ? (const void*)ix->x8 : (const void*)ix->xh,
                        I8 ? (const float*)ix->x8s : (const float*)nullptr, qpad, ix->cand_s, ix->cand_i, ix->cand_n, ix->cthr,
@@ -2138,9 +2114,9 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     const float i8_rel = sqrtf((float)ix->dpad) / 254.f;
     const float eps_rel = i8 ? ((sweep && !sweep_mfma) ? i8_rel : 2.f * i8_rel + i8_rel * i8_rel) + 0.00048828125f
                              : (sweep ? 0.00390625f + 0.00048828125f : 0.0078125f + 0.00048828125f);
-    // ... tightened by the rounding errors actually measured at ingest / query prep (cz_eps); CSS_KNN_EPS=apriori for A/B.
+    // ... tightened by the rounding errors actually measured at ingest / query prep (cz_eps).
     // measured = the word of maxn2 that holds the rows' error: 1 = bf16 rows, 2 = int8 rows
-    const int measured = env.eps_measured ? (i8 ? 2 : 1) : 0;
+    const int measured = i8 ? 2 : 1;
     // (the int8 queries' error norms: sized HERE, before the pointer below is taken -- until round 4 the buffer grew further
     // down, so the selects of the first int8 search with more queries than any before read the freed, shorter one: zeros on
     // a fresh device, i.e. a band without the query term; stale bytes otherwise, i.e. everything flagged -- 744 of 1000
@@ -2148,7 +2124,7 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     if (i8 && (!sweep || sweep_mfma) && (rc_early = grow(&ix->qerr2_i8, &ix->qerr2_i8_cap, (size_t)q0 + nq_pad)) != CSS_OK) return rc_early;
     const float* qerr2 = (sweep && !sweep_mfma) ? nullptr : (i8 ? ix->qerr2_i8 + q0 : ix->qerr2 + q0);
     // the second pass over flagged queries reads the bf16 rows with bf16 queries
-    const EpsSet eps_p2{0.0078125f + 0.00048828125f, ix->qerr2 + q0, env.eps_measured ? 1 : 0};
+    const EpsSet eps_p2{0.0078125f + 0.00048828125f, ix->qerr2 + q0, 1};
     const int l2 = ix->metric == CSS_METRIC_L2 ? 1 : 0;
     const float* xn2 = l2 ? ix->xnorm2 : nullptr;  // L2: coarse score = 2 x.q - ||x||^2
     int rc;
@@ -2165,8 +2141,7 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     // per pass over the fp32 rows): 22 flagged of 1000 queries cost 2.9 ms of a 7 ms batch at 1 M clustered rows.
     // (the second pass reads the bf16 rows: a shadow-less range scanned from int8 scratch rows sends its flagged queries
     // straight to the exact sweep -- and, through the feedback of batch_uses_i8, the next searches to bf16 ranges)
-    const bool pass2 = !sweep && env.pass2 && env.loop8 && env.mfma_shape == 16 && ix->dpad % 128 == 0 && ix->ntotal > CZ_CAP &&
-                       ix->xh != nullptr;
+    const bool pass2 = !sweep && ix->dpad % 128 == 0 && ix->ntotal > CZ_CAP && ix->xh != nullptr;
     const int f2 = pass2 ? std::min(nq_pad, kF2Max) : 0;   // (a multiple of CZ_T)
     int* flag_listB = nullptr;
     int* nflagB = nullptr;
@@ -2255,7 +2230,7 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
         if (fused && (rc = grow(&ix->fs_state, &ix->fs_state_cap, (size_t)CZ_FS_WORDS)) != CSS_OK) return rc;
     }
     constexpr int kPaceGroups = 512, kPaceStages = 20;
-    const bool use_pace = !sweep && env.pacing;
+    const bool use_pace = !sweep;
     if (use_pace && (rc = grow(&ix->cpace, &ix->cpace_cap, (size_t)kPaceGroups * kPaceStages)) != CSS_OK) return rc;
 
     {
@@ -2291,29 +2266,20 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     }
     const size_t lds = (size_t)CZ_NST * CZ_STAGE;
     typedef void (*scan_fn)(const unsigned short*, const unsigned short*, const float*, float*, uint32_t*, int*, int64_t, int,
-                            int, int64_t, int64_t, int, int*, const uint32_t*, const float*, int, const int*, const float*,
+                            int, int64_t, int64_t, int, int*, const uint32_t*, const float*, const int*, const float*,
                             const float*);
-    // (the DBG instantiations honour CSS_KNN_DBG; the product kernels carry no timing switches)
-    // v_mfma_f32_16x16x32_bf16 by default: same cycles per flop and LDS traffic as 32x32x16, but the chip holds a
-    // higher clock under it (measured in one session: main stage 11.1 ms vs 12.1 ms); CSS_KNN_MFMA=32 for A/B runs
-    const bool m16 = env.mfma_shape == 16;
-    // the 8-phase ping-pong loop (k_scan_coarse8) wherever its shape constraints hold; CSS_KNN_LOOP=old for A/B runs
-    const bool loop8 = env.loop8 && m16 && ix->dpad % 128 == 0;
+    // the 8-phase ping-pong loop (k_scan_coarse8) wherever its shape constraints hold
+    const bool loop8 = ix->dpad % 128 == 0;
     const bool i8b = i8 && !sweep;   // (batch_uses_i8 implies the 8-phase loop)
     // one-eps thresholds from exactly scored top-k candidates (k_coarse_select): the int8 scan, whose band is wide
-    // (CSS_KNN_EXACTK=0 for A/B runs; the scores are inner products: batch_uses_i8)
-    const bool exact_k = (i8b || sweep_mfma) && env.exact_k && k * 2 <= CZ_EXK;   // (both operands int8: the widest band)
-    const scan_fn f_stage0 = i8b ? k_scan_coarse8<true, false, false, CZ_CAP, true>
-                                 : (loop8 ? k_scan_coarse8<true, false>
-                                          : (m16 ? k_scan_coarse<true, false, false, 16> : k_scan_coarse<true, false>));
-    const scan_fn f_mid = i8b ? (env.dbg ? k_scan_coarse8<false, false, true, CZ_CAP, true> : k_scan_coarse8<false, false, false, CZ_CAP, true>)
-                              : (loop8 ? (env.dbg ? k_scan_coarse8<false, false, true> : k_scan_coarse8<false, false>)
-                                       : (env.dbg ? k_scan_coarse<false, false, true>
-                                                  : (m16 ? k_scan_coarse<false, false, false, 16> : k_scan_coarse<false, false>)));
-    const scan_fn f_main = i8b ? (env.dbg ? k_scan_coarse8<false, true, true, CZ_CAP, true> : k_scan_coarse8<false, true, false, CZ_CAP, true>)
-                               : (loop8 ? (env.dbg ? k_scan_coarse8<false, true, true> : k_scan_coarse8<false, true>)
-                                        : (env.dbg ? k_scan_coarse<false, true, true>
-                                                   : (m16 ? k_scan_coarse<false, true, false, 16> : k_scan_coarse<false, true>)));
+    // (the scores are inner products: batch_uses_i8)
+    const bool exact_k = (i8b || sweep_mfma) && k * 2 <= CZ_EXK;   // (both operands int8: the widest band)
+    const scan_fn f_stage0 = i8b ? k_scan_coarse8<true, false, CZ_CAP, true>
+                                 : (loop8 ? k_scan_coarse8<true, false> : k_scan_coarse<true, false>);
+    const scan_fn f_mid = i8b ? k_scan_coarse8<false, false, CZ_CAP, true>
+                              : (loop8 ? k_scan_coarse8<false, false> : k_scan_coarse<false, false>);
+    const scan_fn f_main = i8b ? k_scan_coarse8<false, true, CZ_CAP, true>
+                               : (loop8 ? k_scan_coarse8<false, true> : k_scan_coarse<false, true>);
     const unsigned short* scan_rows = i8b ? reinterpret_cast<const unsigned short*>(ix->x8) : ix->xh;
     const float* scan_xsc = i8b ? ix->x8s : nullptr;
     const float* scan_qsc = i8b ? ix->qscale : nullptr;
@@ -2361,15 +2327,15 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
             // 0 / 1024 / 4096 / never: 300 k rows 0.31, 0.35, 0.56 / 0.26, 0.31, 0.53 / 0.26, 0.31, 0.56 / 0.25, 0.31, 0.56;
             // 3 M rows (1024 / 4096 / never) 0.70, 0.79, 2.25 / 0.73, 0.84, 2.28 / 0.78, 0.90, 2.56; 10 M rows 1.88, 1.99,
             // 6.45 / 1.88, 2.01, 6.52 / 2.05, 2.27, 7.36.
-            if (i8b && !stage0 && !env.dbg && qreg_applies(ix, nqt) && count * nqt >= env.qreg_min) {
+            if (i8b && !stage0 && qreg_applies(ix, nqt) && count * nqt >= env.qreg_min) {
                 if ((rc = launch_scan_qreg(ix, nqt, count, s, gr - 1, s == 1, st)) != CSS_OK) return rc;
             } else {
                 // (int8 rows: no sibling pacing -- a row tile fetched by every query-tile block on its own is still only
                 // ~3.5 TB/s worst case at this scan's speed, and the coupling costs more than the HBM traffic it saves:
                 // 9.65 vs 9.02 ms per batch; the bf16 scan reads twice the bytes per row and needs it)
-                int* pace = (env.pacing && !i8b && grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace + (size_t)stage_idx * kPaceGroups : nullptr;
+                int* pace = (!i8b && grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace + (size_t)stage_idx * kPaceGroups : nullptr;
                 hipLaunchKernelGGL(f, dim3(grid), dim3(512), lds, st, scan_rows, ix->qh, ix->cthr, ix->cand_s, ix->cand_i,
-                                   ix->cand_n, ix->ntotal, ix->dpad, nqt, count, s, gr - 1, pace, ix->cur_mask, xn2, env.dbg,
+                                   ix->cand_n, ix->ntotal, ix->dpad, nqt, count, s, gr - 1, pace, ix->cur_mask, xn2,
                                    (const int*)nullptr, scan_xsc, scan_qsc);
                 CSS_LAUNCH_CHECK();
             }
@@ -2394,13 +2360,13 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     if (pass2) {
         // every launch below reads the flagged count from device memory and returns at once when there is nothing to do
         ProfScope ps("knn_coarse_pass2", st);
-        const scan_fn f_all = k_scan_coarse8<false, true, false, CZ_CAP2>;   // every row tile against thr2 (the gate also makes tile = ordinal)
+        const scan_fn f_all = k_scan_coarse8<false, true, CZ_CAP2>;   // every row tile against thr2 (the gate also makes tile = ordinal)
         if ((rc = css::ensure_dynamic_lds((const void*)f_all, lds, ix->device)) != CSS_OK) return rc;
         const int nqt2 = f2 / CZ_T;
         {
-            int* pace = (env.pacing && grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace + (size_t)stage_idx * kPaceGroups : nullptr;
+            int* pace = (grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace + (size_t)stage_idx * kPaceGroups : nullptr;
             hipLaunchKernelGGL(f_all, dim3(grid), dim3(512), lds, st, ix->xh, ix->qh2, ix->thr2, ix->cand_s2, ix->cand_i2,
-                               ix->cand_n2, ix->ntotal, ix->dpad, nqt2, ntiles, (int64_t)1, 1 << 30, pace, ix->cur_mask, xn2, 0,
+                               ix->cand_n2, ix->ntotal, ix->dpad, nqt2, ntiles, (int64_t)1, 1 << 30, pace, ix->cur_mask, xn2,
                                (const int*)nflag, (const float*)nullptr, (const float*)nullptr);
         }
         hipLaunchKernelGGL(k_rescore_parts<true>, dim3(kRescoreGrid), dim3(256), 0, st, ix->cand_s2, ix->cand_i2, ix->cand_n2,
@@ -2638,12 +2604,12 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
     // 3 or 4 queries are VALU-bound in that sweep (10 M rows: 2.65 ms at k = 10): they, and up to 16 queries, sweep on the
     // int8 MFMA where that applies (mfma_sweep_applies); where not, 3 or 4 queries are sooner through the int8 scan of
     // batches from 3 M rows on (1.98 ms; 1 M rows: sweep 0.34 vs scan 0.39 ms; k = 100 goes through the bf16 scan, 3.2 ms
-    // against the sweep's 2.8-2.9); two queries always sweep (1.36 vs 1.93 ms).  tools/knn_fewq_probe.py, one session.
+    // against the sweep's 2.8-2.9); two queries always sweep (1.36 vs 1.93 ms).  One session.
     const bool i8_scan_ok = ix->x8 != nullptr && ix->metric == CSS_METRIC_IP && ix->dpad % 256 == 0 && ix->dpad <= 1024 &&
-                            env.batch_i8 != 0 && env.loop8 && env.mfma_shape == 16;
+                            env.batch_i8 != 0;
     const bool mfma_sweep_ok = mfma_sweep_applies(ix, nq, k);
-    const int sweep_max = env.sweep_maxq >= 0 ? env.sweep_maxq : ((k <= 32 && ix->ntotal >= 3000000 && i8_scan_ok) ? 2 : 4);   // VALU sweep
-    const bool sweep_base = ix->ntotal > 0 && k <= CSS_KERNEL_MAX_K && env.batch == 0 && (ix->xh != nullptr || ix->x8 != nullptr) &&
+    const int sweep_max = (k <= 32 && ix->ntotal >= 3000000 && i8_scan_ok) ? 2 : 4;   // VALU sweep
+    const bool sweep_base = ix->ntotal > 0 && k <= CSS_KERNEL_MAX_K && (ix->xh != nullptr || ix->x8 != nullptr) &&
                             (ix->search_mode == CSS_SEARCH_COARSE ||
                              (ix->search_mode == CSS_SEARCH_AUTO && (nq > 4 || k > 32 || ix->ntotal >= 100000)));
     const bool sweep_i8 = sweep_base && ix->x8 != nullptr && (nq <= sweep_max || mfma_sweep_ok) && sweep_uses_i8(ix);
@@ -2676,8 +2642,8 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
     // 0.099 / 0.119, 1 M 0.25 / 0.64).  Round 2 switched at 1.2 M / 0.4 M rows: the cascade has since lost most of its
     // fixed cost and the few-query sweep reads int8 rows.
     const bool coarse_pays = nq > 4 || k > 32 || ix->ntotal >= 100000;
-    const bool want_split = mode == CSS_SEARCH_SPLIT || env.batch == 1;   // split-operand candidate scan from the fp32 rows
-    const bool want_candidates = env.batch == 0 && (mode == CSS_SEARCH_COARSE || (mode == CSS_SEARCH_AUTO && coarse_pays));
+    const bool want_split = mode == CSS_SEARCH_SPLIT;   // split-operand candidate scan from the fp32 rows
+    const bool want_candidates = mode == CSS_SEARCH_COARSE || (mode == CSS_SEARCH_AUTO && coarse_pays);
     // Which shadow rows this search reads is decided HERE, once (the per-index int8 feedback counts searches, not chunks).
     // An index with int8 rows only takes the candidate path where the int8 rows are chosen; otherwise it goes on like an
     // index without shadow rows (bf16 scratch ranges for batches, the exact kernels for a few queries).
@@ -2696,8 +2662,8 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
         }
     }
     // no shadow rows: batches take the same cascade over bf16 rows rounded on the fly, one row range at a time
-    // (CSS_KNN_NOSHADOW=split, a k beyond the MFMA kernels, or no HBM left for the scratch rows: the split-operand scan)
-    if (want_candidates && ix->xh == nullptr && nq > 16 && env.noshadow_ranges && ix->dpad % 128 == 0) {
+    // (a k beyond the MFMA kernels, or no HBM left for the scratch rows: the split-operand scan)
+    if (want_candidates && ix->xh == nullptr && nq > 16 && ix->dpad % 128 == 0) {
         rc = search_noshadow_ranges(ix, nq, k, D_dev, I_dev, st, ix->x8 == nullptr);
         if (rc != kNoRangeScratch) return rc;
     }
@@ -2717,7 +2683,7 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
                                            : launch_scan_fp32mfma<CSS_METRIC_L2>(ix, (int)nq, k, D_dev, I_dev, st);
     }
     // exact fp32 arithmetic inside the scan: fp32-input MFMA for batches, VALU sweeps for up to 16 queries
-    if (batch_ok && (mode == CSS_SEARCH_EXACT_FP32 || env.batch == 2)) {
+    if (batch_ok && mode == CSS_SEARCH_EXACT_FP32) {
         return ix->metric == CSS_METRIC_IP ? launch_scan_fp32mfma<CSS_METRIC_IP>(ix, (int)nq, k, D_dev, I_dev, st)
                                            : launch_scan_fp32mfma<CSS_METRIC_L2>(ix, (int)nq, k, D_dev, I_dev, st);
     }

@@ -195,11 +195,10 @@ __global__ void k_coarse_init(float* thr, int* cand_n, int* flags, int* nflag, i
 // allow-bitmap test of a masked search (filter / tombstone push-down): bit r&31 of word r>>5
 #define CZ_ALLOWED(MASK_, ROW_) ((MASK_) == nullptr || (((MASK_)[(ROW_) >> 5] >> ((ROW_) & 31)) & 1u))
 
-// Epilogue of one 256x256 tile of k_scan_coarse (uses the kernel's locals).  Accumulator geometry by MFMA shape MS:
-//   32x32x16: lane (lq = lane & 31, lg = lane >> 5): query 32 m + lq, register r = row (r&3) + 8 (r>>2) + 4 lg of row tile n
-//   16x16x32: lane (lq = lane & 15, lg = lane >> 4): query 16 m + lq, register r = row 4 lg + r of row tile n
-#define CZ_QOFF(M_) (MS * (M_) + lq)
-#define CZ_ROFF(N_, R_) (MS == 32 ? 32 * (N_) + ((R_) & 3) + 8 * ((R_) >> 2) + 4 * lg : 16 * (N_) + 4 * lg + (R_))
+// Epilogue of one 256x256 tile of k_scan_coarse (uses the kernel's locals).  Accumulator geometry of the 16x16x32 MFMA:
+//   lane (lq = lane & 15, lg = lane >> 4): query 16 m + lq, register r = row 4 lg + r of row tile n
+#define CZ_QOFF(M_) (16 * (M_) + lq)
+#define CZ_ROFF(N_, R_) (16 * (N_) + 4 * lg + (R_))
 // Wave-local hit list of k_scan_coarse8 (CZ_STAGED kernels): [score | row | query] arrays of CZ_WCAP entries per wave.
 // CZ_FLUSH: every lane takes entries lane, lane + 64, ...: one returning atomic per entry, all of a pass in flight
 // together.  (Inline-asm LDS access: compiler-visible LDS traffic next to the pending LDS-DMA of the ring costs a
@@ -267,8 +266,7 @@ _Pragma("unroll")                                                               
                                 acc[m][n][4 * rg + e] = (float)__float_as_int(acc[m][n][4 * rg + e]) * svs_[e];        \
                     }                                                                                                  \
             }                                                                                                          \
-            if (dbg & 1) {                                                                                             \
-            } else if constexpr (STAGE0) {                                                                             \
+            if constexpr (STAGE0) {                                                                                    \
                 const int64_t u = u0 + (int64_t)ct_tile * ustep;                                                       \
 _Pragma("unroll")                                                                                                      \
                 for (int m = 0; m < TM; ++m) {                                                                         \
@@ -315,7 +313,7 @@ _Pragma("unroll")                                                               
                     }                                                                                                  \
                     anym |= __ballot(mx_ >= thr_q) != 0ull ? 1u << m : 0u;                                             \
                 }                                                                                                      \
-                if (anym != 0u && !(dbg & 2)) {   /* dbg bit1 (timing experiments): votes only, no appends */           \
+                if (anym != 0u) {                                                                                      \
                     const bool edge = row0 + 64 > ntotal || mask != nullptr;   /* wave uniform */                      \
                     if constexpr (CZ_STAGED) {                                                                         \
                         /* k_scan_coarse8 (16x16 tiles: TM = 8, TN = 4, NR = 4).  The 8 waves of a block and the blocks     \
@@ -338,7 +336,7 @@ _Pragma("unroll")                                                               
                             for (int n = 0; n < TN; ++n)                                                               \
 _Pragma("unroll")                                                                                                      \
                                 for (int r = 0; r < NR; ++r) h |= (acc[m][n][r] >= thr_q ? 1u : 0u) << (n * NR + r);   \
-                            const unsigned qv = (unsigned)(qtile * CZ_T + wr * 128 + MS * m + lq);                     \
+                            const unsigned qv = (unsigned)(qtile * CZ_T + wr * 128 + 16 * m + lq);                     \
 _Pragma("nounroll")                                                                                                    \
                             while (true) {                                                                             \
                                 const bool has = h != 0u;                                                              \
@@ -424,17 +422,18 @@ _Pragma("unroll")                                                               
 // row tiles): the nqt blocks that share a row tile sit on one XCD (blockIdx % 8) and walk side by side, so the
 // tile's rows are fetched from HBM once per XCD L2.
 // Wave grid 2 (query halves) x 4 (row quarters); a wave's 128 queries x 64 rows are 8 x 4 accumulator tiles of
-// 16x16 (MS = 16, default: a lane owns 8 query columns x 16 rows) or 4 x 2 tiles of 32x32 (MS = 32).
+// 16x16 (a lane owns 8 query columns x 16 rows).  v_mfma_f32_16x16x32_bf16: same cycles per flop and LDS traffic as
+// 32x32x16, but the chip holds a higher clock under it (measured in one session: main stage 11.1 ms vs 12.1 ms).
 // STAGE0: every score is written to slot (tile ordinal * 256 + row in tile); otherwise scores >= thr are
 // appended.  MAIN only gives the last (stride 1, 3/4 of the rows) stage its own name in profiles.
-template <bool STAGE0, bool MAIN, bool DBG = false, int MS = 32>
+template <bool STAGE0, bool MAIN>
 __global__ __launch_bounds__(512) void k_scan_coarse(const unsigned short* __restrict__ xh,
                                                      const unsigned short* __restrict__ qh,
                                                      const float* __restrict__ thr, float* __restrict__ cand_s,
                                                      uint32_t* __restrict__ cand_i, int* __restrict__ cand_n,
                                                      int64_t ntotal, int K, int nqt, int64_t count, int64_t stride,
                                                      int gm1, int* __restrict__ pace_cnt, const uint32_t* __restrict__ mask,
-                                                     const float* __restrict__ xn2, int dbg_arg, const int* __restrict__ gate,
+                                                     const float* __restrict__ xn2, const int* __restrict__ gate,
                                                      const float* __restrict__ xsc, const float* __restrict__ qsc) {
     constexpr int KCAP = CZ_CAP;   // candidate slots per query (the shared epilogue macros)
     constexpr bool I8 = false;     // (the int8 operands exist in k_scan_coarse8 only; xsc / qsc are null here)
@@ -445,20 +444,14 @@ __global__ __launch_bounds__(512) void k_scan_coarse(const unsigned short* __res
     (void)ssq;
     (void)sxs_base;
     (void)gate;
-    // dbg (CSS_KNN_DBG, timing experiments only, honoured by the DBG instantiation alone so that the product
-    // kernel carries no such branches): bit0 skip the epilogue, bit1 skip MFMA + LDS reads, bit2 skip the
-    // LDS-DMA loads, bit3 LDS reads without MFMAs, bit4 MFMAs without LDS reads, bit5 half of the LDS reads
-    const int dbg = DBG ? dbg_arg : 0;
-    static_assert(MS == 32 || MS == 16, "MFMA shape: 32x32x16 or 16x16x32");
-    constexpr int NW = 8, WN = 4, TM = 128 / MS, TN = 64 / MS, NR = MS == 32 ? 16 : 4;
-    typedef typename std::conditional<MS == 32, f32x16, v4f>::type acc_t;
+    constexpr int NW = 8, WN = 4, TM = 8, TN = 4, NR = 4;
     constexpr int A_BYTES = CZ_T * CZ_RB;
     constexpr int PPW = (2 * CZ_T / 8) / NW;  // 1-KiB LDS-DMA pieces (8 rows) per wave per stage = 8
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave / WN, wc = wave % WN;
-    const int lq = MS == 32 ? (lane & 31) : (lane & 15), lg = MS == 32 ? (lane >> 5) : (lane >> 4);
+    const int lq = lane & 15, lg = lane >> 4;
 
     const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3, per_x = gridDim.x >> 3;
     const int slots = per_x / nqt;
@@ -525,7 +518,7 @@ __global__ __launch_bounds__(512) void k_scan_coarse(const unsigned short* __res
                                          (__attribute__((address_space(3))) void*)(smem + (SLOT_) * CZ_STAGE + dst[i]), 16, 0, 0); \
     }
 
-    acc_t acc[TM][TN];
+    v4f acc[TM][TN];
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
@@ -535,9 +528,7 @@ __global__ __launch_bounds__(512) void k_scan_coarse(const unsigned short* __res
 
     int it_tile = 0, it_kt = 0, gi = 0;
     CZ_SET_SRC(0)
-    if (!(dbg & 4)) {
-        CZ_ISSUE(0, 0)
-    }
+    CZ_ISSUE(0, 0)
     gi = 1;
     if (++it_kt == KT) {
         it_kt = 0;
@@ -566,107 +557,59 @@ __global__ __launch_bounds__(512) void k_scan_coarse(const unsigned short* __res
         __builtin_amdgcn_s_barrier();  // stage g landed for every wave; the slot of stage g-1 is free
         const char* Ab = smem + (g & 1) * CZ_STAGE;
         const char* Bb = Ab + A_BYTES;
-// the DMA of stage g+1 (into the other slot); ISSUE_FIRST: before this step's fragment reads, else after the first ones
+// the DMA of stage g+1 (into the other slot), issued behind this step's first fragment reads
 #define CZ_ISSUE_NEXT()                                                  \
         if (gi < total) {                                                \
-            if (!(dbg & 4)) {                                            \
-                CZ_ISSUE(it_kt, gi & 1)                                  \
-            }                                                            \
+            CZ_ISSUE(it_kt, gi & 1)                                      \
             ++gi;                                                        \
             if (++it_kt == KT) {                                         \
                 it_kt = 0;                                               \
                 if (++it_tile < my_ntiles) CZ_SET_SRC(it_tile)           \
             }                                                            \
         }
-        if constexpr (DBG) {
+        // MFMA rows <- index rows, MFMA columns <- queries: lane (lq, lg) holds query lq and index rows 4 lg + r of the
+        // 16-row tile in register r
+        // (explicitly double-buffered fragment reads pinned with sched_barrier measured 2 % slower than
+        // hipcc's own read / wait / 4-MFMA groups: LDS latency is not what bounds this loop)
+        // the first fragment reads go out right behind the barrier, the 8 DMA instructions of the next stage
+        // (slow to issue) follow while those reads are in flight
+        {   // (first k-step in two halves of the query tiles: fewer fragments live across the DMA issue)
+            v4f b[TN], a[TM / 2];
+#pragma unroll
+            for (int n = 0; n < TN; ++n) b[n] = *reinterpret_cast<const v4f*>(Bb + cz_swz(wc * 64 + 16 * n + lq, lg));
+#pragma unroll
+            for (int m = 0; m < TM / 2; ++m) a[m] = *reinterpret_cast<const v4f*>(Ab + cz_swz(wr * 128 + 16 * m + lq, lg));
+            __builtin_amdgcn_sched_barrier(0);
             CZ_ISSUE_NEXT()
-        }
-        // C_: 16-wide k step 0..3 (MS = 32: chunk 2 C_ + lg) or 32-wide k step 0..1 (MS = 16: chunk 4 C_ + lg)
-#define CZ_READ(A_, B_, C_)                                                                                            \
-    _Pragma("unroll") for (int m = 0; m < TM; ++m)                                                                    \
-        A_[m] = *reinterpret_cast<const v4f*>(Ab + cz_swz(wr * 128 + MS * m + lq, (MS == 32 ? 2 : 4) * (C_) + lg));   \
-    _Pragma("unroll") for (int n = 0; n < TN; ++n)                                                                    \
-        B_[n] = *reinterpret_cast<const v4f*>(Bb + cz_swz(wc * 64 + MS * n + lq, (MS == 32 ? 2 : 4) * (C_) + lg));
-#define CZ_MFMA(A_, B_)                                                                                                \
-    _Pragma("unroll") for (int m = 0; m < TM; ++m)                                                                    \
-        _Pragma("unroll") for (int n = 0; n < TN; ++n) {                                                              \
-            if constexpr (MS == 32)                                                                                    \
-                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, B_[n]),                  \
-                                                                    __builtin_bit_cast(v8bf, A_[m]), acc[m][n], 0, 0, 0); \
-            else                                                                                                       \
-                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, B_[n]),                  \
-                                                                    __builtin_bit_cast(v8bf, A_[m]), acc[m][n], 0, 0, 0); \
-        }
-        // MFMA rows <- index rows, MFMA columns <- queries: lane (fr, fh) holds query fr and index rows
-        // (r&3) + 8(r>>2) + 4 fh of the 32-row tile in register r
-        if constexpr (!DBG) {
-            // (explicitly double-buffered fragment reads pinned with sched_barrier measured 2 % slower than
-            // hipcc's own read / wait / 4-MFMA groups: LDS latency is not what bounds this loop)
-            // the first fragment reads go out right behind the barrier, the 8 DMA instructions of the next stage
-            // (slow to issue) follow while those reads are in flight
-            {   // (first k-step in two halves of the query tiles: fewer fragments live across the DMA issue)
-                constexpr int CM = (MS == 32 ? 2 : 4);  // chunk index multiplier of this MFMA shape
-                v4f b[TN], a[TM / 2];
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int n = 0; n < TN; ++n) b[n] = *reinterpret_cast<const v4f*>(Bb + cz_swz(wc * 64 + MS * n + lq, lg));
-#pragma unroll
-                for (int m = 0; m < TM / 2; ++m) a[m] = *reinterpret_cast<const v4f*>(Ab + cz_swz(wr * 128 + MS * m + lq, lg));
-                __builtin_amdgcn_sched_barrier(0);
-                CZ_ISSUE_NEXT()
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    if (h == 1) {
-#pragma unroll
-                        for (int m = 0; m < TM / 2; ++m)
-                            a[m] = *reinterpret_cast<const v4f*>(Ab + cz_swz(wr * 128 + MS * (TM / 2 + m) + lq, lg));
-                    }
+            for (int h = 0; h < 2; ++h) {
+                if (h == 1) {
 #pragma unroll
                     for (int m = 0; m < TM / 2; ++m)
-#pragma unroll
-                        for (int n = 0; n < TN; ++n) {
-                            if constexpr (MS == 32)
-                                acc[h * (TM / 2) + m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                                    __builtin_bit_cast(v8bf, b[n]), __builtin_bit_cast(v8bf, a[m]), acc[h * (TM / 2) + m][n], 0, 0, 0);
-                            else
-                                acc[h * (TM / 2) + m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                                    __builtin_bit_cast(v8bf, b[n]), __builtin_bit_cast(v8bf, a[m]), acc[h * (TM / 2) + m][n], 0, 0, 0);
-                        }
+                        a[m] = *reinterpret_cast<const v4f*>(Ab + cz_swz(wr * 128 + 16 * (TM / 2 + m) + lq, lg));
                 }
-                (void)CM;
-            }
 #pragma unroll
-            for (int c = 1; c < (MS == 32 ? 4 : 2); ++c) {
-                v4f a[TM], b[TN];
-                CZ_READ(a, b, c)
-                CZ_MFMA(a, b)
-            }
-        } else if (!(dbg & 2)) {
-            v4f a[TM], b[TN];
+                for (int m = 0; m < TM / 2; ++m)
 #pragma unroll
-            for (int c = 0; c < (MS == 32 ? 4 : 2); ++c) {
-                if ((dbg & 32) && (c & 1)) {
-                    // bit5: odd k-steps reuse the previous fragments (half the LDS read traffic; wrong results)
-                } else if (!(dbg & 16)) {
-                    CZ_READ(a, b, c)
-                } else {
-#pragma unroll
-                    for (int m = 0; m < TM; ++m) a[m] = v4f{1.f, 2.f, 3.f, 4.f};
-#pragma unroll
-                    for (int n = 0; n < TN; ++n) b[n] = v4f{1.f, 2.f, 3.f, 4.f};
-                }
-                if (dbg & 8) {
-#pragma unroll
-                    for (int m = 0; m < TM; ++m) asm volatile("" ::"v"(a[m]));
-#pragma unroll
-                    for (int n = 0; n < TN; ++n) asm volatile("" ::"v"(b[n]));
-                } else {
-                    CZ_MFMA(a, b)
-                }
+                    for (int n = 0; n < TN; ++n)
+                        acc[h * (TM / 2) + m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                            __builtin_bit_cast(v8bf, b[n]), __builtin_bit_cast(v8bf, a[m]), acc[h * (TM / 2) + m][n], 0, 0, 0);
             }
         }
-#undef CZ_READ
-#undef CZ_MFMA
+        {   // second 32-wide k step: chunks 4 + lg
+            v4f a[TM], b[TN];
+#pragma unroll
+            for (int m = 0; m < TM; ++m) a[m] = *reinterpret_cast<const v4f*>(Ab + cz_swz(wr * 128 + 16 * m + lq, 4 + lg));
+#pragma unroll
+            for (int n = 0; n < TN; ++n) b[n] = *reinterpret_cast<const v4f*>(Bb + cz_swz(wc * 64 + 16 * n + lq, 4 + lg));
+#pragma unroll
+            for (int m = 0; m < TM; ++m)
+#pragma unroll
+                for (int n = 0; n < TN; ++n)
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, b[n]),
+                                                                        __builtin_bit_cast(v8bf, a[m]), acc[m][n], 0, 0, 0);
+        }
 #undef CZ_ISSUE_NEXT
         if (++kt == KT) {
             CZ_EPILOGUE();
@@ -685,7 +628,7 @@ __global__ __launch_bounds__(512) void k_scan_coarse(const unsigned short* __res
 // instructions] s_barrier [MFMAs] s_barrier; wave row 1 runs one barrier behind wave row 0, so one wave of every SIMD
 // issues MFMAs while its partner reads and issues DMA; half-tile slots (A = queries, B = index rows) are refilled
 // three ahead behind a counted vmcnt(6).  Accumulator geometry, thresholds, candidate appends and sibling pacing
-// are those of k_scan_coarse<.., 16> (the epilogue macro is shared).  Needs K % 128 == 0 and 256 slack rows behind
+// are those of k_scan_coarse (the epilogue macro is shared).  Needs K % 128 == 0 and 256 slack rows behind
 // the shadow rows (the last tile reads them; their scores are masked by row < ntotal).
 // Measured (10 M x 768, 1000 queries, main stage): see DESIGN.md section 3.
 // one MFMA of the 8-phase loop: bf16 16x16x32, or int8 16x16x64 with the int32 accumulators kept in the v4f registers
@@ -711,18 +654,17 @@ constexpr int C8_A0 = 0, C8_B0 = 1, C8_B1 = 2, C8_A1 = 3;
 // 2^24 for rows of up to 1024 elements) are converted once per tile, score = acc * s_row * s_query: the row scale is
 // applied in the epilogue, the query scale is folded into the thresholds (thr / s_query) and into the scores that
 // leave the kernel.  Inner product only (the L2 form 2 x.q - ||x||^2 does not factor).
-template <bool STAGE0, bool MAIN, bool DBG = false, int KCAP_T = CZ_CAP, bool I8 = false>
+template <bool STAGE0, bool MAIN, int KCAP_T = CZ_CAP, bool I8 = false>
 __global__ __launch_bounds__(512) void k_scan_coarse8(const unsigned short* __restrict__ xh,
                                                       const unsigned short* __restrict__ qh,
                                                       const float* __restrict__ thr, float* __restrict__ cand_s,
                                                       uint32_t* __restrict__ cand_i, int* __restrict__ cand_n,
                                                       int64_t ntotal, int K, int nqt_arg, int64_t count, int64_t stride,
                                                       int gm1, int* __restrict__ pace_cnt, const uint32_t* __restrict__ mask,
-                                                      const float* __restrict__ xn2, int dbg_arg, const int* __restrict__ gate,
+                                                      const float* __restrict__ xn2, const int* __restrict__ gate,
                                                       const float* __restrict__ xsc, const float* __restrict__ qsc) {
-    constexpr int MS = 16, TM = 8, TN = 4, NR = 4;
+    constexpr int TM = 8, TN = 4, NR = 4;
     constexpr int KCAP = KCAP_T;
-    const int dbg = DBG ? dbg_arg : 0;   // CSS_KNN_DBG (timing experiments): bit0 skips the epilogue
     (void)MAIN;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][4][C8_HT]
     const int tid = threadIdx.x, lane = tid & 63;

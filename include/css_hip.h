@@ -226,15 +226,15 @@ int css_encoder_forward_dev(css_encoder* enc, const int32_t* input_ids_dev, cons
 /* bf16 attention computes softmax rows as exp2(score) / sum WITHOUT a running maximum while every row sum of a
  * block stays in (1 / range, range) and repeats the block with the running-maximum (online) softmax otherwise --
  * same result, the guard only protects the fp32 range.  Default 2^100 (|logit| < 69); range = 0 always takes the
- * running-maximum pass (verification; env default CSS_ATT_RANGE). */
+ * running-maximum pass (verification). */
 int css_encoder_set_attention_range(css_encoder* enc, float range);
 
 /* Test/diagnostic hook: copy an activation buffer of the LAST forward back to the
  * host as fp32 ("x32" [T,H] final hidden states, "qkv" [T,3H], "ctx" [T,H],
  * "ffn" [T,F], "pre32" [T,H]; with num_layers = 1 these are the layer-0 probes).
  * bf16 batches of >= 1024 tokens run with LayerNorm folded into the GEMM epilogues and
- * never materialise "x32" / "pre32" as such: "x32" is then an error (CSS_ENC_FUSE_LN=0
- * keeps the separate LayerNorm kernels), "pre32" / "ctx" / "ffn" hold that path's buffers. */
+ * never materialise "x32" / "pre32" as such: "x32" is then an error, "pre32" / "ctx" / "ffn"
+ * hold that path's buffers. */
 int css_encoder_debug_read(css_encoder* enc, const char* what, float* out_host, int64_t numel);
 
 /* Host-only helper (no device needed): bucket of a relative position

@@ -519,22 +519,3 @@ def test_real_checkpoint_directory_matches_transformers_when_one_is_supplied():
         enc.close()
         assert np.abs(got - ref).max() < tol and (got * ref).sum(1).min() > 1 - 1e-3, compute
 
-
-def test_four_wave_gemm_variant_keeps_the_folded_path_bit_reproducible_and_inside_the_tolerance():
-    """k_gemm4w (css_encoder_kernels.h: the LayerNorm-folded GEMMs on four 128 x 128 waves per block, accumulators in
-    AGPRs, hand-placed instruction stream) is opt-in -- it measured slower end to end than k_gemm8p -- and
-    stays under test: the folded-path parity test once more in a child process with all four GEMMs on it
-    (CSS_GEMM_4W is read once per process)."""
-    import os
-    import subprocess
-    import sys
-    from pathlib import Path
-
-    root = Path(__file__).resolve().parent.parent
-    env = dict(os.environ, CSS_GEMM_4W="15")
-    r = subprocess.run([sys.executable, "-m", "pytest", str(root / "tests" / "test_encoder_gpu.py"), "-q", "-x", "-m", "gpu",
-                        "-p", "no:cacheprovider", "-k", "folded_layernorm_path_matches or trained_like_outlier"],
-                       cwd=str(root), env=env, capture_output=True, text=True, timeout=600)
-    tail = "\n".join(r.stdout.splitlines()[-15:])
-    assert r.returncode == 0, f"folded-path tests under CSS_GEMM_4W=15 failed:\n{tail}\n{r.stderr[-2000:]}"
-    assert " passed" in tail
