@@ -59,6 +59,8 @@ class EncoderCfg(ctypes.Structure):
         ("max_seq_len", c_int),
         ("ln_eps", c_float),
         ("compute", c_int),
+        ("arch", c_int),      # 0 = MPNet, 1 = BERT
+        ("pooling", c_int),   # 0 = mean, 1 = CLS
     ]
 
 

@@ -1,4 +1,5 @@
-// css_encoder.hip -- MPNet sentence encoder (all-mpnet-base-v2 architecture) on gfx950.
+// css_encoder.hip -- MPNet (all-mpnet-base-v2 architecture) and BERT (all-MiniLM-L6-v2, bge-*-en-v1.5) sentence
+// encoders on gfx950.
 //
 // Replaces, behind include/css_hip.h, what the reference reaches through
 // SentenceTransformer.encode() (src/embeddings.py:184-188, :216-222): MPNet
@@ -9,6 +10,8 @@
 // Pipeline per forward (one stream, no host syncs between kernels):
 //   k_embed_ln -> 12 x [ k_gemm<QKV> -> attention -> k_gemm<RESID> -> k_layernorm
 //                        -> k_gemm<GELU> -> k_gemm<RESID> -> k_layernorm ] -> k_pool_norm
+// BERT is the same post-LN stack with absolute positions (+ token-type row 0, folded into the position table when the
+// weights are finalised), no relative position bias, and mean or CLS pooling (css_encoder_cfg.arch / .pooling).
 // Residual stream / LayerNorm / softmax / pooling are fp32; GEMM and attention
 // operands are bf16 (MFMA) in the product mode, fp32 in the verification mode.
 #include "css_common.h"
@@ -32,6 +35,9 @@ struct Param {
     int64_t numel = 0;
     uint32_t synth_id = 0;
     float mean = 0.f, std = 0.02f;
+    bool owned = true;     // false: a view into a fused tensor (q/k/v rows of the QKV weight / bias)
+    bool synth = true;     // filled by css_encoder_init_synthetic (MPNet fills the fused tensor, BERT its q/k/v views)
+    bool required = true;  // a checkpoint must name it (MPNet q/k/v views: the fused tensor or all three views)
 };
 
 struct LayerW {
@@ -65,6 +71,13 @@ __global__ void k_zero_row(float* p, int n) {
     if (i < n) p[i] = 0.f;
 }
 
+// BERT: out[p][c] = pemb[p][c] + row[c] (token-type row 0 folded into the position table)
+__global__ void k_add_row(const float* __restrict__ pemb, const float* __restrict__ row, float* __restrict__ out, int rows,
+                          int H) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (size_t)rows * H) out[i] = pemb[i] + row[i % H];
+}
+
 }  // namespace
 
 // Bucket of a relative position (rel = key - query), transformers'
@@ -91,6 +104,9 @@ struct css_encoder {
     hipStream_t stream = nullptr;
     std::map<std::string, Param> params;
     float *wemb = nullptr, *pemb = nullptr, *embg = nullptr, *embb = nullptr, *relw = nullptr;
+    float *tte = nullptr;        // BERT token_type_embeddings [2][H]
+    float *pemb_eff = nullptr;   // position table the embedding kernels read: pemb (MPNet), pemb + tte[0] (BERT)
+    std::vector<void*> extra;    // device buffers owned outside `params` (BERT fused QKV, pemb_eff)
     std::vector<LayerW> layers;
     float* bias_tab = nullptr;  // [heads][2*maxL-1]
     int* bucket_dev = nullptr;
@@ -133,11 +149,18 @@ int alloc_param(css_encoder* e, const std::string& name, int64_t numel, uint32_t
     return CSS_OK;
 }
 
+// The LayerNorm-folded bf16 path (forward_folded_bf16) is built for hidden 768 / head_dim 64 and N % 256 GEMMs.
+bool folded_shape(const css_encoder_cfg& c) {
+    return c.compute == 0 && c.hidden == 768 && c.heads * 64 == c.hidden && c.ffn % 256 == 0;
+}
+
 // HF key names.  q/k/v are views into the fused
-// [3H, H] weight / [3H] bias, in that order.
+// [3H, H] weight / [3H] bias, in that order.  MPNet: transformers' MPNetModel names (the fused tensor may be given
+// whole or as its three views); BERT: BertModel names (query / key / value are the only names of the fused rows).
 int build_params(css_encoder* e) {
     const css_encoder_cfg& c = e->cfg;
     const int64_t H = c.hidden, F = c.ffn;
+    const bool bert = c.arch == CSS_ENCODER_ARCH_BERT;
     int rc;
 #define AP(name, n, sid, mean, std, ptr) \
     if ((rc = alloc_param(e, name, n, sid, mean, std, ptr)) != CSS_OK) return rc
@@ -145,18 +168,36 @@ int build_params(css_encoder* e) {
     AP("embeddings.position_embeddings.weight", (int64_t)c.max_pos * H, 1, 0.f, 0.02f, &e->pemb);
     AP("embeddings.LayerNorm.weight", H, 2, 1.f, 0.1f, &e->embg);
     AP("embeddings.LayerNorm.bias", H, 3, 0.f, 0.05f, &e->embb);
-    AP("encoder.relative_attention_bias.weight", (int64_t)c.rel_buckets * c.heads, 4, 0.f, 0.1f, &e->relw);
+    if (bert) {
+        AP("embeddings.token_type_embeddings.weight", 2 * H, 5, 0.f, 0.02f, &e->tte);
+        CSS_HIP_TRY(hipMalloc((void**)&e->pemb_eff, (size_t)c.max_pos * H * 4));
+        e->extra.push_back(e->pemb_eff);
+    } else {
+        AP("encoder.relative_attention_bias.weight", (int64_t)c.rel_buckets * c.heads, 4, 0.f, 0.1f, &e->relw);
+        e->pemb_eff = e->pemb;
+    }
     e->layers.resize(c.num_layers);
     for (int i = 0; i < c.num_layers; ++i) {
         LayerW& L = e->layers[i];
         const std::string pre = "encoder.layer." + std::to_string(i) + ".";
         const uint32_t base = 16 + 16 * i;
-        AP(pre + "attention.attn.qkv.weight", 3 * H * H, base + 0, 0.f, 0.02f, &L.wqkv);
-        AP(pre + "attention.attn.qkv.bias", 3 * H, base + 1, 0.f, 0.05f, &L.bqkv);
-        AP(pre + "attention.attn.o.weight", H * H, base + 6, 0.f, 0.02f, &L.wo);
-        AP(pre + "attention.attn.o.bias", H, base + 7, 0.f, 0.05f, &L.bo);
-        AP(pre + "attention.LayerNorm.weight", H, base + 8, 1.f, 0.1f, &L.ln1g);
-        AP(pre + "attention.LayerNorm.bias", H, base + 9, 0.f, 0.05f, &L.ln1b);
+        if (bert) {
+            CSS_HIP_TRY(hipMalloc((void**)&L.wqkv, (size_t)3 * H * H * 4));
+            e->extra.push_back(L.wqkv);
+            CSS_HIP_TRY(hipMalloc((void**)&L.bqkv, (size_t)3 * H * 4));
+            e->extra.push_back(L.bqkv);
+            AP(pre + "attention.output.dense.weight", H * H, base + 6, 0.f, 0.02f, &L.wo);
+            AP(pre + "attention.output.dense.bias", H, base + 7, 0.f, 0.05f, &L.bo);
+            AP(pre + "attention.output.LayerNorm.weight", H, base + 8, 1.f, 0.1f, &L.ln1g);
+            AP(pre + "attention.output.LayerNorm.bias", H, base + 9, 0.f, 0.05f, &L.ln1b);
+        } else {
+            AP(pre + "attention.attn.qkv.weight", 3 * H * H, base + 0, 0.f, 0.02f, &L.wqkv);
+            AP(pre + "attention.attn.qkv.bias", 3 * H, base + 1, 0.f, 0.05f, &L.bqkv);
+            AP(pre + "attention.attn.o.weight", H * H, base + 6, 0.f, 0.02f, &L.wo);
+            AP(pre + "attention.attn.o.bias", H, base + 7, 0.f, 0.05f, &L.bo);
+            AP(pre + "attention.LayerNorm.weight", H, base + 8, 1.f, 0.1f, &L.ln1g);
+            AP(pre + "attention.LayerNorm.bias", H, base + 9, 0.f, 0.05f, &L.ln1b);
+        }
         AP(pre + "intermediate.dense.weight", F * H, base + 10, 0.f, 0.02f, &L.w1);
         AP(pre + "intermediate.dense.bias", F, base + 11, 0.f, 0.05f, &L.b1);
         AP(pre + "output.dense.weight", H * F, base + 12, 0.f, 0.02f, &L.w2);
@@ -165,22 +206,30 @@ int build_params(css_encoder* e) {
         AP(pre + "output.LayerNorm.bias", H, base + 15, 0.f, 0.05f, &L.ln2b);
         // q/k/v views (weights: rows [0,H) [H,2H) [2H,3H) of the fused matrix)
         const char* nm[3] = {"q", "k", "v"};
+        const char* bnm[3] = {"query", "key", "value"};
         for (int j = 0; j < 3; ++j) {
+            const std::string vn = bert ? pre + "attention.self." + bnm[j] : pre + "attention.attn." + nm[j];
             Param w;
             w.p = L.wqkv + (size_t)j * H * H;
             w.numel = H * H;
-            w.synth_id = base + 2 * j;  // informational; synthetic init fills the fused tensors
-            e->params[pre + "attention.attn." + nm[j] + ".weight"] = w;
-            Param b;
+            w.synth_id = base + 2 * j;  // MPNet: informational (synthetic init fills the fused tensors); BERT: its seed
+            w.owned = false;
+            w.synth = bert;
+            w.required = bert;
+            Param b = w;
             b.p = L.bqkv + (size_t)j * H;
             b.numel = H;
-            e->params[pre + "attention.attn." + nm[j] + ".bias"] = b;
+            b.synth_id = base + 2 * j + 1;
+            b.mean = 0.f;
+            b.std = 0.05f;
+            e->params[vn + ".weight"] = w;
+            e->params[vn + ".bias"] = b;
         }
         CSS_HIP_TRY(hipMalloc((void**)&L.wqkv_h, (size_t)3 * H * H * 2));
         CSS_HIP_TRY(hipMalloc((void**)&L.wo_h, (size_t)H * H * 2));
         CSS_HIP_TRY(hipMalloc((void**)&L.w1_h, (size_t)F * H * 2));
         CSS_HIP_TRY(hipMalloc((void**)&L.w2_h, (size_t)H * F * 2));
-        if (c.compute == 0) {
+        if (folded_shape(c)) {
             CSS_HIP_TRY(hipMalloc((void**)&L.wqkv_f, (size_t)3 * H * H * 2));
             CSS_HIP_TRY(hipMalloc((void**)&L.w1_f, (size_t)F * H * 2));
             CSS_HIP_TRY(hipMalloc((void**)&L.w2_p, (size_t)H * F * 2));
@@ -192,6 +241,7 @@ int build_params(css_encoder* e) {
         }
     }
 #undef AP
+    if (bert) return CSS_OK;   // no relative position bias
     const int maxL = c.max_seq_len;
     CSS_HIP_TRY(hipMalloc((void**)&e->bias_tab, (size_t)c.heads * (2 * maxL - 1) * sizeof(float)));
     CSS_HIP_TRY(hipMalloc((void**)&e->bucket_dev, (size_t)(2 * maxL - 1) * sizeof(int)));
@@ -227,9 +277,15 @@ int finalize_weights(css_encoder* e) {
         hipLaunchKernelGGL(k_f32_to_bf16, dim3(1024), dim3(256), 0, st, L.w1, L.w1_h, F * H);
         hipLaunchKernelGGL(k_f32_to_bf16, dim3(1024), dim3(256), 0, st, L.w2, L.w2_h, H * F);
     }
-    const int n = c.heads * (2 * c.max_seq_len - 1);
-    hipLaunchKernelGGL(k_build_bias_tab, dim3((n + 255) / 256), dim3(256), 0, st, e->relw, e->bucket_dev, c.heads,
-                       c.max_seq_len, c.compute == 0 ? 1.44269504088896341f : 1.0f, e->bias_tab);
+    if (c.arch == CSS_ENCODER_ARCH_BERT) {
+        const size_t n = (size_t)c.max_pos * H;
+        hipLaunchKernelGGL(k_add_row, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, e->pemb, e->tte, e->pemb_eff,
+                           c.max_pos, (int)H);
+    } else {
+        const int n = c.heads * (2 * c.max_seq_len - 1);
+        hipLaunchKernelGGL(k_build_bias_tab, dim3((n + 255) / 256), dim3(256), 0, st, e->relw, e->bucket_dev, c.heads,
+                           c.max_seq_len, c.compute == 0 ? 1.44269504088896341f : 1.0f, e->bias_tab);
+    }
     CSS_LAUNCH_CHECK();
     CSS_HIP_TRY(hipStreamSynchronize(st));
     e->weights_ready = true;
@@ -333,14 +389,24 @@ int launch_gemm8p(const void* A, const void* W, const float* bias, void* C, int 
 template <typename TIn, int EPI>
 int launch_gemm(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int qscale_cols,
                 float qscale, int num_cus, hipStream_t st, const char* prof) {
-    if (M <= 64 && N % 32 == 0 && K % 768 == 0) {  // single-query / tiny batches: weight-streaming kernel (K/4 = 12n fragment steps)
+    if (M <= 64 && N % 32 == 0 && K % 384 == 0) {  // single-query / tiny batches: weight-streaming kernel (K/4 = 12n fragment steps)
         ProfScope ps(prof, st);
-        if (M <= 32)
-            hipLaunchKernelGGL((k_gemm_skinny<TIn, EPI, 1>), dim3(N / 32), dim3(256), 0, st, (const TIn*)A, (const TIn*)W,
-                               bias, C, M, N, K, qscale_cols, qscale);
-        else
-            hipLaunchKernelGGL((k_gemm_skinny<TIn, EPI, 2>), dim3(N / 32), dim3(256), 0, st, (const TIn*)A, (const TIn*)W,
-                               bias, C, M, N, K, qscale_cols, qscale);
+        // K % 768 == 0: groups of 12 fragment steps; K = 384 (hidden 384: 6 bf16 / 12 fp32 steps per wave): groups of 6
+        if (K % 768 == 0) {
+            if (M <= 32)
+                hipLaunchKernelGGL((k_gemm_skinny<TIn, EPI, 1>), dim3(N / 32), dim3(256), 0, st, (const TIn*)A, (const TIn*)W,
+                                   bias, C, M, N, K, qscale_cols, qscale);
+            else
+                hipLaunchKernelGGL((k_gemm_skinny<TIn, EPI, 2>), dim3(N / 32), dim3(256), 0, st, (const TIn*)A, (const TIn*)W,
+                                   bias, C, M, N, K, qscale_cols, qscale);
+        } else {
+            if (M <= 32)
+                hipLaunchKernelGGL((k_gemm_skinny<TIn, EPI, 1, 6>), dim3(N / 32), dim3(256), 0, st, (const TIn*)A,
+                                   (const TIn*)W, bias, C, M, N, K, qscale_cols, qscale);
+            else
+                hipLaunchKernelGGL((k_gemm_skinny<TIn, EPI, 2, 6>), dim3(N / 32), dim3(256), 0, st, (const TIn*)A,
+                                   (const TIn*)W, bias, C, M, N, K, qscale_cols, qscale);
+        }
         CSS_LAUNCH_CHECK();
         return CSS_OK;
     }
@@ -374,17 +440,45 @@ int launch_gemm(const void* A, const void* W, const float* bias, void* C, int M,
     return launch_gemm_t<TIn, EPI, 2, 2, 2, 2, 4, 64, 1>(A, W, bias, C, M, N, K, qscale_cols, qscale, num_cus, st, prof);
 }
 
-template <typename TIn>
+// Position id of a sequence's first token: MPNet padding_idx + 1 (cumsum(mask) * mask + padding_idx), BERT 0.
+int pos_offset(const css_encoder_cfg& c) { return c.arch == CSS_ENCODER_ARCH_BERT ? 0 : 2; }
+
+// Softmax scale 1 / sqrt(head_dim), folded into the q columns of the QKV GEMM (bf16: times log2(e), exp2 softmax).
+float qk_scale(const css_encoder_cfg& c, bool bf) {
+    const float s = 1.0f / std::sqrt((float)(c.hidden / c.heads));   // exactly 0.125 at head_dim 64
+    return bf ? s * 1.44269504088896341f : s;
+}
+
+template <int HD, bool BLK, bool BIAS>
+void launch_attention_bf16_t(css_encoder* e, const int32_t* cu, int B, int max_len, hipStream_t st) {
+    const int maxL = e->cfg.max_seq_len;
+    const size_t lds = 4 * 8192 + (BIAS ? (size_t)(2 * maxL - 1 + 64) * 4 : 0);
+    const int nqb = (max_len + 127) / 128;
+    hipLaunchKernelGGL((k_attention_bf16<HD, BLK, BIAS>), dim3(B * nqb * e->cfg.heads), dim3(256), lds, st,
+                       (const bf16_t*)e->qkv, cu, e->bias_tab, maxL, e->cfg.hidden, (bf16_t*)e->ctx, nqb, e->cfg.heads,
+                       e->att_range);
+}
+
+// bf16 attention of the architecture: MPNet (head_dim 64, relative bias), BERT (head_dim 64 or 32, no bias)
+template <bool BLK>
+void launch_attention_bf16(css_encoder* e, const int32_t* cu, int B, int max_len, hipStream_t st) {
+    if (e->cfg.arch != CSS_ENCODER_ARCH_BERT) launch_attention_bf16_t<64, BLK, true>(e, cu, B, max_len, st);
+    else if (e->cfg.hidden / e->cfg.heads == 64) launch_attention_bf16_t<64, BLK, false>(e, cu, B, max_len, st);
+    else if constexpr (!BLK) launch_attention_bf16_t<32, false, false>(e, cu, B, max_len, st);
+}
+
+template <typename TIn, int H>
 int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int T, int max_len, int normalize,
                   float* out, hipStream_t st) {
     const css_encoder_cfg& c = e->cfg;
-    const int H = c.hidden, F = c.ffn;
+    const int F = c.ffn;
     constexpr bool BF = sizeof(TIn) == 2;
     int rc;
     {
         ProfScope ps("enc_embed_ln", st);
-        hipLaunchKernelGGL(k_embed_ln<768>, dim3((T + 3) / 4), dim3(256), 0, st, ids, cu, B, e->wemb, e->pemb,
-                           e->embg, e->embb, c.ln_eps, c.vocab, c.max_pos, e->x32, BF ? (bf16_t*)e->x16 : nullptr, T);
+        hipLaunchKernelGGL(k_embed_ln<H>, dim3((T + 3) / 4), dim3(256), 0, st, ids, cu, B, e->wemb, e->pemb_eff,
+                           e->embg, e->embb, c.ln_eps, c.vocab, c.max_pos, pos_offset(c), e->x32,
+                           BF ? (bf16_t*)e->x16 : nullptr, T);
         CSS_LAUNCH_CHECK();
     }
     const int maxL = c.max_seq_len;
@@ -400,10 +494,10 @@ int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, 
         ProfScope ps("enc_layernorm", st);
         const dim3 grid((T + 3) / 4), blk(256);
         if constexpr (BF)
-            hipLaunchKernelGGL((k_layernorm<768, bf16_t, bf16_t>), grid, blk, 0, st, (const bf16_t*)e->pre32, (const bf16_t*)e->x16, g, b,
+            hipLaunchKernelGGL((k_layernorm<H, bf16_t, bf16_t>), grid, blk, 0, st, (const bf16_t*)e->pre32, (const bf16_t*)e->x16, g, b,
                                c.ln_eps, last ? e->x32 : (float*)nullptr, (bf16_t*)e->x16, T);
         else
-            hipLaunchKernelGGL((k_layernorm<768, float, float>), grid, blk, 0, st, (const float*)e->pre32, (const float*)e->x32, g, b,
+            hipLaunchKernelGGL((k_layernorm<H, float, float>), grid, blk, 0, st, (const float*)e->pre32, (const float*)e->x32, g, b,
                                c.ln_eps, e->x32, (bf16_t*)nullptr, T);
         CSS_LAUNCH_CHECK();
         return CSS_OK;
@@ -412,17 +506,17 @@ int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, 
         const LayerW& L = e->layers[li];
         const void* xin = BF ? e->x16 : (const void*)e->x32;
         const void* wqkv = BF ? (const void*)L.wqkv_h : (const void*)L.wqkv;
-        if ((rc = launch_gemm<TIn, EPI_QKV>(xin, wqkv, L.bqkv, e->qkv, T, 3 * H, H, H, BF ? 0.125f * 1.44269504088896341f : 0.125f, e->num_cus, st, "enc_gemm_qkv")) != CSS_OK)
+        if ((rc = launch_gemm<TIn, EPI_QKV>(xin, wqkv, L.bqkv, e->qkv, T, 3 * H, H, H, qk_scale(c, BF), e->num_cus, st, "enc_gemm_qkv")) != CSS_OK)
             return rc;
         {
             ProfScope ps("enc_attention", st);
             if constexpr (BF) {
-                const size_t lds = 4 * 8192 + (size_t)(2 * maxL - 1 + 64) * 4;
-                const int nqb = (max_len + 127) / 128;
-                hipLaunchKernelGGL((k_attention_bf16<64, false>), dim3(B * nqb * c.heads), dim3(256), lds, st,
-                                   (const bf16_t*)e->qkv, cu, e->bias_tab, maxL, H, (bf16_t*)e->ctx, nqb, c.heads, e->att_range);
+                launch_attention_bf16<false>(e, cu, B, max_len, st);
+            } else if (H / c.heads == 64) {
+                hipLaunchKernelGGL(k_attention_f32<64>, dim3(B, max_len, c.heads), dim3(64), 0, st, (const float*)e->qkv, cu,
+                                   e->bias_tab, maxL, H, (float*)e->ctx);
             } else {
-                hipLaunchKernelGGL(k_attention_f32, dim3(B, max_len, c.heads), dim3(64), 0, st, (const float*)e->qkv, cu,
+                hipLaunchKernelGGL(k_attention_f32<32>, dim3(B, max_len, c.heads), dim3(64), 0, st, (const float*)e->qkv, cu,
                                    e->bias_tab, maxL, H, (float*)e->ctx);
             }
             CSS_LAUNCH_CHECK();
@@ -441,9 +535,13 @@ int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, 
     {
         ProfScope ps("enc_pool", st);
         constexpr int kPoolSlices = 8;
-        // partial sums live in pre32 (free after the last LayerNorm): [B][8][H] floats
-        hipLaunchKernelGGL(k_pool_partial<768>, dim3(B, kPoolSlices), dim3(256), 0, st, e->x32, cu, kPoolSlices, e->pre32);
-        hipLaunchKernelGGL(k_pool_final<768>, dim3(B), dim3(256), 0, st, e->pre32, cu, kPoolSlices, normalize, out);
+        if (c.pooling == CSS_ENCODER_POOL_CLS) {
+            hipLaunchKernelGGL(k_pool_cls<H>, dim3(B), dim3(256), 0, st, e->x32, cu, normalize, out);
+        } else {
+            // partial sums live in pre32 (free after the last LayerNorm): [B][8][H] floats
+            hipLaunchKernelGGL(k_pool_partial<H>, dim3(B, kPoolSlices), dim3(256), 0, st, e->x32, cu, kPoolSlices, e->pre32);
+            hipLaunchKernelGGL(k_pool_final<H>, dim3(B), dim3(256), 0, st, e->pre32, cu, kPoolSlices, normalize, out);
+        }
         CSS_LAUNCH_CHECK();
     }
     return CSS_OK;
@@ -455,13 +553,13 @@ int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, 
 int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int T, int max_len, int normalize,
                         float* out, hipStream_t st) {
     const css_encoder_cfg& c = e->cfg;
-    const int H = c.hidden, F = c.ffn, maxL = c.max_seq_len;
+    const int H = c.hidden, F = c.ffn;
     int rc;
     bf16_t* pre[2] = {(bf16_t*)e->x16, (bf16_t*)e->pre32};
     {
         ProfScope ps("enc_embed_ln", st);
-        hipLaunchKernelGGL(k_embed_pre<768>, dim3((T + 15) / 16), dim3(256), 0, st, ids, cu, B, e->wemb, e->pemb, c.vocab,
-                           c.max_pos, pre[0], e->stats[0], T, kStatScale1, kStatScale2);
+        hipLaunchKernelGGL(k_embed_pre<768>, dim3((T + 15) / 16), dim3(256), 0, st, ids, cu, B, e->wemb, e->pemb_eff, c.vocab,
+                           c.max_pos, pos_offset(c), pre[0], e->stats[0], T, kStatScale1, kStatScale2);
         CSS_LAUNCH_CHECK();
     }
     const float *g_in = e->embg, *b_in = e->embb;  // the LayerNorm that turns pre[0] into the layer input
@@ -473,15 +571,12 @@ int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, i
         // x = LN(pre[0]) -> qkv; zeroes stats[1]
         side.stats_in = e->stats[0];
         side.stats_out = e->stats[1];
-        if ((rc = launch_gemm8p<EPI_AFF_QKV, true>(pre[0], L.wqkv_f, L.dqkv, e->qkv, T, 3 * H, H, H, 0.125f * 1.44269504088896341f,
+        if ((rc = launch_gemm8p<EPI_AFF_QKV, true>(pre[0], L.wqkv_f, L.dqkv, e->qkv, T, 3 * H, H, H, qk_scale(c, true),
                                                    side, e->num_cus, st, "enc_gemm_qkv")) != CSS_OK)
             return rc;
         {
             ProfScope ps("enc_attention", st);
-            const size_t lds = 4 * 8192 + (size_t)(2 * maxL - 1 + 64) * 4;
-            const int nqb = (max_len + 127) / 128;
-            hipLaunchKernelGGL((k_attention_bf16<64, true>), dim3(B * nqb * c.heads), dim3(256), lds, st, (const bf16_t*)e->qkv, cu,
-                               e->bias_tab, maxL, H, (bf16_t*)e->ctx, nqb, c.heads, e->att_range);
+            launch_attention_bf16<true>(e, cu, B, max_len, st);
             CSS_LAUNCH_CHECK();
         }
         // pre[1] = ctx Wo^T + (bo + beta) + gamma (pre[0] - mu) rs; stats[1] += row sums
@@ -507,9 +602,14 @@ int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, i
         constexpr int kPoolSlices = 8;
         // partial sums live in ffn (free after the last FFN2; capacity >= 8 B rows of 8 H bytes): [B][8][H] floats
         float* part = (float*)e->ffn;
-        hipLaunchKernelGGL(k_pool_partial_ln<768>, dim3(B, kPoolSlices), dim3(256), 0, st, (const bf16_t*)pre[0], e->stats[0], g_in,
-                           b_in, 1.0f / H, c.ln_eps, cu, kPoolSlices, part);
-        hipLaunchKernelGGL(k_pool_final<768>, dim3(B), dim3(256), 0, st, part, cu, kPoolSlices, normalize, out);
+        if (c.pooling == CSS_ENCODER_POOL_CLS) {
+            hipLaunchKernelGGL(k_pool_cls_ln<768>, dim3(B), dim3(256), 0, st, (const bf16_t*)pre[0], e->stats[0], g_in, b_in,
+                               1.0f / H, c.ln_eps, cu, normalize, out);
+        } else {
+            hipLaunchKernelGGL(k_pool_partial_ln<768>, dim3(B, kPoolSlices), dim3(256), 0, st, (const bf16_t*)pre[0], e->stats[0],
+                               g_in, b_in, 1.0f / H, c.ln_eps, cu, kPoolSlices, part);
+            hipLaunchKernelGGL(k_pool_final<768>, dim3(B), dim3(256), 0, st, part, cu, kPoolSlices, normalize, out);
+        }
         CSS_LAUNCH_CHECK();
     }
     e->x32_valid = false;
@@ -525,11 +625,16 @@ int forward_any(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, in
     CSS_REQUIRE(B >= 1 && T >= B, "css_encoder_forward: bad batch (B=%d, tokens=%d)", B, T);
     CSS_REQUIRE(max_len >= 1 && max_len <= e->cfg.max_seq_len, "css_encoder_forward: max_len=%d outside [1, %d]", max_len,
                 e->cfg.max_seq_len);
-    if (e->cfg.compute == 0 && T >= 1024 && e->cfg.ffn % 256 == 0 && (size_t)T * e->cfg.ffn * 2 < ((size_t)1 << 32))
+    // Hidden 384 (BERT small: GEMM N in {384, 1152, 1536}, K in {384, 1536}) always takes the unfolded path: its GEMMs
+    // run on the 128x128 k_gemm tile (k_gemm8p for N = 1536) and k_gemm_skinny for <= 64 tokens.
+    if (folded_shape(e->cfg) && T >= 1024 && (size_t)T * e->cfg.ffn * 2 < ((size_t)1 << 32))
         return forward_folded_bf16(e, ids, cu, B, T, max_len, normalize, out, st);
     e->x32_valid = true;
-    return e->cfg.compute == 0 ? forward_typed<bf16_t>(e, ids, cu, B, T, max_len, normalize, out, st)
-                               : forward_typed<float>(e, ids, cu, B, T, max_len, normalize, out, st);
+    if (e->cfg.hidden == 384)
+        return e->cfg.compute == 0 ? forward_typed<bf16_t, 384>(e, ids, cu, B, T, max_len, normalize, out, st)
+                                   : forward_typed<float, 384>(e, ids, cu, B, T, max_len, normalize, out, st);
+    return e->cfg.compute == 0 ? forward_typed<bf16_t, 768>(e, ids, cu, B, T, max_len, normalize, out, st)
+                               : forward_typed<float, 768>(e, ids, cu, B, T, max_len, normalize, out, st);
 }
 
 }  // namespace
@@ -538,14 +643,28 @@ extern "C" {
 
 int css_encoder_create(const css_encoder_cfg* cfg, int device, css_encoder** out) {
     CSS_REQUIRE(cfg && out, "css_encoder_create: NULL argument");
-    CSS_REQUIRE(cfg->hidden == 768 && cfg->heads * 64 == cfg->hidden,
-                "css_encoder_create: kernels are built for hidden=768, head_dim=64 (got hidden=%d heads=%d)", cfg->hidden,
-                cfg->heads);
+    CSS_REQUIRE(cfg->arch == CSS_ENCODER_ARCH_MPNET || cfg->arch == CSS_ENCODER_ARCH_BERT,
+                "css_encoder_create: arch must be 0 (MPNet) or 1 (BERT) (got %d)", cfg->arch);
+    CSS_REQUIRE(cfg->pooling == CSS_ENCODER_POOL_MEAN || cfg->pooling == CSS_ENCODER_POOL_CLS,
+                "css_encoder_create: pooling must be 0 (mean) or 1 (CLS) (got %d)", cfg->pooling);
+    const bool bert = cfg->arch == CSS_ENCODER_ARCH_BERT;
+    if (bert)
+        CSS_REQUIRE((cfg->hidden == 384 || cfg->hidden == 768) && cfg->heads >= 1 && cfg->hidden % cfg->heads == 0 &&
+                        (cfg->hidden / cfg->heads == 32 || cfg->hidden / cfg->heads == 64),
+                    "css_encoder_create: BERT kernels are built for hidden 384 / 768 with head_dim 32 / 64 (got hidden=%d "
+                    "heads=%d)", cfg->hidden, cfg->heads);
+    else
+        CSS_REQUIRE(cfg->hidden == 768 && cfg->heads * 64 == cfg->hidden,
+                    "css_encoder_create: kernels are built for hidden=768, head_dim=64 (got hidden=%d heads=%d)", cfg->hidden,
+                    cfg->heads);
     CSS_REQUIRE(cfg->ffn % 128 == 0 && cfg->ffn >= 128, "css_encoder_create: ffn must be a multiple of 128");
     CSS_REQUIRE(cfg->num_layers >= 1 && cfg->num_layers <= 64, "css_encoder_create: num_layers out of range");
     CSS_REQUIRE(cfg->max_seq_len >= 1 && cfg->max_seq_len <= 512, "css_encoder_create: max_seq_len outside [1, 512]");
-    CSS_REQUIRE(cfg->max_pos >= cfg->max_seq_len + 2, "css_encoder_create: max_pos must be >= max_seq_len + 2");
-    CSS_REQUIRE(cfg->vocab >= 4 && cfg->rel_buckets >= 4 && cfg->rel_buckets % 4 == 0, "css_encoder_create: bad vocab / rel_buckets");
+    CSS_REQUIRE(cfg->max_pos >= cfg->max_seq_len + pos_offset(*cfg), "css_encoder_create: max_pos must be >= max_seq_len + %d",
+                pos_offset(*cfg));
+    CSS_REQUIRE(cfg->vocab >= 4 && (bert || (cfg->rel_buckets >= 4 && cfg->rel_buckets % 4 == 0)),
+                "css_encoder_create: bad vocab / rel_buckets");
+    CSS_REQUIRE(cfg->pad_id >= 0 && cfg->pad_id < cfg->vocab, "css_encoder_create: pad_id outside the vocabulary");
     CSS_REQUIRE(cfg->compute == 0 || cfg->compute == 1, "css_encoder_create: compute must be 0 (bf16) or 1 (fp32)");
     int rc = css::check_device(device);
     if (rc != CSS_OK) return rc;
@@ -577,13 +696,10 @@ int css_encoder_free(css_encoder* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto& kv : e->graphs)
         if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-    for (auto& kv : e->params) {
-        // q/k/v views alias the fused tensors: free only owning entries
-        const std::string& n = kv.first;
-        const bool view = n.find(".attn.q.") != std::string::npos || n.find(".attn.k.") != std::string::npos ||
-                          n.find(".attn.v.") != std::string::npos;
-        if (!view && kv.second.p) (void)hipFree(kv.second.p);
-    }
+    for (auto& kv : e->params)   // q/k/v views alias the fused tensors: free only owning entries
+        if (kv.second.owned && kv.second.p) (void)hipFree(kv.second.p);
+    for (void* p : e->extra)
+        if (p) (void)hipFree(p);
     for (auto& L : e->layers) {
         if (L.wqkv_h) (void)hipFree(L.wqkv_h);
         if (L.wo_h) (void)hipFree(L.wo_h);
@@ -614,8 +730,11 @@ int css_encoder_load_weights(css_encoder* e, const css_tensor* tensors, int n) {
         std::string name = tensors[i].name;
         const std::string pfx = "0.auto_model.";  // sentence-transformers module prefix
         if (name.compare(0, pfx.size(), pfx) == 0) name = name.substr(pfx.size());
-        if (name.compare(0, 6, "mpnet.") == 0) name = name.substr(6);
+        const bool bert = e->cfg.arch == CSS_ENCODER_ARCH_BERT;
+        const std::string apfx = bert ? "bert." : "mpnet.";   // the architecture's own model prefix
+        if (name.compare(0, apfx.size(), apfx) == 0) name = name.substr(apfx.size());
         if (name.compare(0, 7, "pooler.") == 0 || name == "embeddings.position_ids") continue;  // unused
+        if (bert && name == "embeddings.token_type_ids") continue;   // (a buffer of BertEmbeddings)
         auto it = e->params.find(name);
         CSS_REQUIRE(it != e->params.end(), "css_encoder_load_weights: unknown parameter '%s'", name.c_str());
         CSS_REQUIRE(it->second.numel == tensors[i].numel, "css_encoder_load_weights: '%s' has %lld elements, expected %lld",
@@ -625,8 +744,7 @@ int css_encoder_load_weights(css_encoder* e, const css_tensor* tensors, int n) {
     }
     for (const auto& kv : e->params) {
         const std::string& nm = kv.first;
-        const bool view = nm.find(".attn.q.") != std::string::npos || nm.find(".attn.k.") != std::string::npos ||
-                          nm.find(".attn.v.") != std::string::npos;
+        const bool view = !kv.second.required;
         const size_t fq = nm.find(".attn.qkv.");
         if (fq != std::string::npos) {
             // fused [3H, H] weight / [3H] bias: given as one tensor, or as its three HF views q, k, v -- not both
@@ -652,18 +770,17 @@ int css_encoder_init_synthetic(css_encoder* e, uint64_t seed) {
     std::lock_guard<std::mutex> lk(e->mu);
     DeviceGuard g(e->device);
     for (auto& kv : e->params) {
-        const std::string& n = kv.first;
-        const bool view = n.find(".attn.q.") != std::string::npos || n.find(".attn.k.") != std::string::npos ||
-                          n.find(".attn.v.") != std::string::npos;
-        if (view) continue;
+        if (!kv.second.synth) continue;   // (MPNet q/k/v views: the fused tensor is filled)
         const Param& p = kv.second;
         hipLaunchKernelGGL(k_synth_fill, dim3(1024), dim3(256), 0, e->stream, p.p, (size_t)p.numel,
                            css_synth_tensor_seed(seed, p.synth_id), p.mean, p.std);
     }
-    // padding_idx rows are zero at init (word_embeddings[pad], position_embeddings[pad])
+    // padding_idx rows are zero at init (word_embeddings[pad], and for MPNet position_embeddings[pad]; BERT's position
+    // table has no padding row)
     const int H = e->cfg.hidden;
     hipLaunchKernelGGL(k_zero_row, dim3((H + 255) / 256), dim3(256), 0, e->stream, e->wemb + (size_t)e->cfg.pad_id * H, H);
-    hipLaunchKernelGGL(k_zero_row, dim3((H + 255) / 256), dim3(256), 0, e->stream, e->pemb + (size_t)e->cfg.pad_id * H, H);
+    if (e->cfg.arch != CSS_ENCODER_ARCH_BERT)
+        hipLaunchKernelGGL(k_zero_row, dim3((H + 255) / 256), dim3(256), 0, e->stream, e->pemb + (size_t)e->cfg.pad_id * H, H);
     CSS_LAUNCH_CHECK();
     return finalize_weights(e);
 }

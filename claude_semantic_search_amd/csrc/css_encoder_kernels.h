@@ -39,15 +39,22 @@ __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((unsig
 __device__ __forceinline__ int swz_byte(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // ---------------------------------------------------------------- embeddings + LN
-// One wave per token.  H = hidden (multiple of 256 so that each lane owns H/64
-// contiguous... here: lane handles float4 columns lane*4 + 256*t).
+// One wave per token.  H = hidden (a multiple of 128): lane handles the float4 columns lane + 64 i; with
+// H % 256 != 0 (hidden 384: 96 float4 per row) the lanes of the last round beyond H / 4 hold zeros.
+// pos_off: position id of a sequence's first token (MPNet: padding_idx + 1 = 2; BERT: 0, its token-type row 0 is
+// folded into the position table at weight-load time).
+template <int H>
+__device__ __forceinline__ bool ln_col_ok(int idx) {   // float4 column idx of a row exists
+    return H % 256 == 0 || idx < H / 4;
+}
 template <int H>
 __global__ __launch_bounds__(256) void k_embed_ln(const int32_t* __restrict__ ids, const int32_t* __restrict__ cu,
                                                   int B, const float* __restrict__ wemb,
                                                   const float* __restrict__ pemb, const float* __restrict__ gamma,
                                                   const float* __restrict__ beta, float eps, int vocab, int max_pos,
-                                                  float* __restrict__ out32, bf16_t* __restrict__ out16, int T) {
-    constexpr int NV = H / 256;  // float4 per lane
+                                                  int pos_off, float* __restrict__ out32, bf16_t* __restrict__ out16, int T) {
+    static_assert(H % 128 == 0, "float4 columns of a row cover whole 32-lane halves");
+    constexpr int NV = (H / 4 + 63) / 64;  // float4 per lane
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= T) return;
@@ -59,7 +66,7 @@ __global__ __launch_bounds__(256) void k_embed_ln(const int32_t* __restrict__ id
     }
     int id = ids[t];
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    int pos = (t - cu[lo]) + 2;  // packed (no pads): cumsum(mask)*mask + padding_idx(1)
+    int pos = (t - cu[lo]) + pos_off;  // packed (no pads): MPNet cumsum(mask)*mask + padding_idx(1); BERT arange
     pos = pos < max_pos ? pos : max_pos - 1;
     const float4* w4 = reinterpret_cast<const float4*>(wemb + (size_t)id * H);
     const float4* p4 = reinterpret_cast<const float4*>(pemb + (size_t)pos * H);
@@ -67,6 +74,8 @@ __global__ __launch_bounds__(256) void k_embed_ln(const int32_t* __restrict__ id
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!ln_col_ok<H>(lane + 64 * i)) continue;
         const float4 a = w4[lane + 64 * i], b = p4[lane + 64 * i];
         v[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
@@ -75,6 +84,7 @@ __global__ __launch_bounds__(256) void k_embed_ln(const int32_t* __restrict__ id
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
+        if (!ln_col_ok<H>(lane + 64 * i)) continue;
         const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
         q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
     }
@@ -83,6 +93,7 @@ __global__ __launch_bounds__(256) void k_embed_ln(const int32_t* __restrict__ id
     const float4* b4 = reinterpret_cast<const float4*>(beta);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
+        if (!ln_col_ok<H>(lane + 64 * i)) continue;
         const float4 g = g4[lane + 64 * i], b = b4[lane + 64 * i];
         float4 o;
         o.x = (v[i].x - mean) * rstd * g.x + b.x;
@@ -130,7 +141,7 @@ __host__ __device__ __forceinline__ int preblk_kpos(int k) {   // position of or
 template <int H>
 __global__ __launch_bounds__(256) void k_embed_pre(const int32_t* __restrict__ ids, const int32_t* __restrict__ cu,
                                                    int B, const float* __restrict__ wemb,
-                                                   const float* __restrict__ pemb, int vocab, int max_pos,
+                                                   const float* __restrict__ pemb, int vocab, int max_pos, int pos_off,
                                                    bf16_t* __restrict__ pre, long long* __restrict__ stats, int T,
                                                    float scale1, float scale2) {
     // One block = one 16-token block row of the blocked layout: thread (lq = tid & 15, g = tid >> 4) writes the 16-byte
@@ -149,7 +160,7 @@ __global__ __launch_bounds__(256) void k_embed_pre(const int32_t* __restrict__ i
         }
         int id = ids[t];
         id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-        int pos = (t - cu[lo]) + 2;
+        int pos = (t - cu[lo]) + pos_off;
         pos = pos < max_pos ? pos : max_pos - 1;
         const float* wr_ = wemb + (size_t)id * H;
         const float* pr_ = pemb + (size_t)pos * H;
@@ -239,7 +250,8 @@ __global__ __launch_bounds__(256) void k_layernorm(const TPre* __restrict__ in, 
                                                    const float* __restrict__ gamma,
                                                    const float* __restrict__ beta, float eps,
                                                    float* __restrict__ out32, bf16_t* __restrict__ out16, int T) {
-    constexpr int NV = H / 256;
+    static_assert(H % 128 == 0, "float4 columns of a row cover whole 32-lane halves");
+    constexpr int NV = (H / 4 + 63) / 64;   // (k_embed_ln: the lanes beyond H / 4 of the last round idle)
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= T) return;
@@ -249,6 +261,8 @@ __global__ __launch_bounds__(256) void k_layernorm(const TPre* __restrict__ in, 
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!ln_col_ok<H>(lane + 64 * i)) continue;
         const float4 a = ln_load4<TPre>(xrow, lane + 64 * i), b = ln_load4<TRes>(rrow, lane + 64 * i);
         v[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
@@ -257,6 +271,7 @@ __global__ __launch_bounds__(256) void k_layernorm(const TPre* __restrict__ in, 
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
+        if (!ln_col_ok<H>(lane + 64 * i)) continue;
         const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
         q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
     }
@@ -265,6 +280,7 @@ __global__ __launch_bounds__(256) void k_layernorm(const TPre* __restrict__ in, 
     const float4* b4 = reinterpret_cast<const float4*>(beta);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
+        if (!ln_col_ok<H>(lane + 64 * i)) continue;
         const float4 g = g4[lane + 64 * i], b = b4[lane + 64 * i];
         float4 o;
         o.x = (v[i].x - mean) * rstd * g.x + b.x;
@@ -1316,7 +1332,7 @@ __global__ __launch_bounds__(512) void k_gemm8p(const bf16_t* __restrict__ A, co
 // block owns 32 output columns, its 4 waves split K four ways and stream their W slices
 // straight into MFMA fragments (no LDS, deep load queue), then reduce through LDS.
 // Same transposed product / epilogue semantics as k_gemm.
-template <typename TIn, int EPI, int MT>
+template <typename TIn, int EPI, int MT, int UNR = 12>
 __global__ __launch_bounds__(256) void k_gemm_skinny(const TIn* __restrict__ A, const TIn* __restrict__ W,
                                                      const float* __restrict__ bias, void* __restrict__ Cout, int M,
                                                      int N, int K, int qscale_cols, float qscale) {
@@ -1341,10 +1357,9 @@ __global__ __launch_bounds__(256) void k_gemm_skinny(const TIn* __restrict__ A, 
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-    // groups of 12 fragment steps are loaded back to back (12 x 16 B of W and of each token
+    // groups of UNR fragment steps are loaded back to back (12 x 16 B of W and of each token
     // tile per lane in flight) before their MFMAs: the kernel lives on memory-level parallelism
-    constexpr int UNR = 12;
-    const int nsteps = kq / KS;  // multiple of 12 for K in {768, 3072} (host check)
+    const int nsteps = kq / KS;  // multiple of UNR: 12 for K % 768 == 0, 6 for K = 384 (hidden 384; host check)
     for (int s0 = 0; s0 < nsteps; s0 += UNR) {
         v4f wf[UNR], af[MT][UNR];
 #pragma unroll
@@ -1436,25 +1451,34 @@ __device__ __forceinline__ int vswz_byte(int row, int chunk) { return row * 128 
 __device__ __forceinline__ int vblk_byte(int key, int cl) {   // V tile (64 keys) in BLK mode: slot of piece cl of key
     return (key >> 4) * 2048 + (cl >> 2) * 1024 + (cl & 3) * 256 + (((key & 15) ^ ((cl & 3) << 2)) << 4);
 }
-template <int HD, bool SAFE, bool BLK>
+// HD: head_dim 64, or 32 (BERT hidden 384; row-major qkv only): K / V tiles keep their 128-B LDS rows and use the first
+// HD / 8 16-byte chunks of each (swizzles unchanged), QK^T takes HD / 16 K-steps of 32x32x16 and O^T = V^T.P^T is HD / 32
+// output tiles of 32 dims.  BIAS = false (BERT): no position bias, the score accumulators start at 0 (SAFE: -mrun) and
+// the block loads no bias table.
+template <int HD, bool SAFE, bool BLK, bool BIAS>
 __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char* Ks, char* Vs, const float* bt, int tok0, int L,
                                            int head, int hidden, int maxL, int qic, const v4f (&qf)[4], f32x16 (&oacc)[2]) {
+    static_assert(HD == 64 || (HD == 32 && !BLK), "head_dim 64, or 32 on row-major qkv");
+    constexpr int CH = HD / 8;          // 16-byte chunks of a K / V row
+    constexpr int SROWS = 256 / CH;     // key rows per staging pass (row-major qkv)
+    constexpr int NPASS = 64 / SROWS;   // staging passes per 64-key tile
+    constexpr int NKS = HD / 16, NMT = HD / 32;
     const int tid = threadIdx.x, lane = tid & 63;
     const int fr = lane & 31, fh = lane >> 5;
     const int ld = 3 * hidden;  // row stride of qkv in elements
     const int nkt = (L + 63) / 64;
-    // staging, 2 passes of 32 keys x 8 chunks.  Row-major qkv: 8 lanes = the 8 chunks of one key row.  BLK: 16 lanes = one
-    // piece of 16 consecutive keys (even keys first: the K tile's swizzle then spreads 8 lanes over 8 bank groups)
-    const int srow = BLK ? 2 * (tid & 7) + ((tid >> 3) & 1) + 16 * (tid >> 7) : tid >> 3;
-    const int schunk = BLK ? (tid >> 4) & 7 : tid & 7;
+    // staging, NPASS passes of SROWS keys x CH chunks.  Row-major qkv: CH lanes = the chunks of one key row.  BLK: 16 lanes
+    // = one piece of 16 consecutive keys (even keys first: the K tile's swizzle then spreads 8 lanes over 8 bank groups)
+    const int srow = BLK ? 2 * (tid & 7) + ((tid >> 3) & 1) + 16 * (tid >> 7) : tid / CH;
+    const int schunk = BLK ? (tid >> 4) & 7 : tid % CH;
     const unsigned brs = (unsigned)(preblk_rowstride(ld) / 2);   // BLK: elements per 16-token block row (T * 3 hidden < 2^31)
     const unsigned poff = (unsigned)((schunk >> 2) * 512 + (schunk & 3) * 128);
     const bf16_t* kblk = qkv + (size_t)(head + hidden / 64) * 1024;
     const bf16_t* vblk = qkv + (size_t)(head + hidden / 32) * 1024;
     v4f rk[2], rv[2];
 #define AT_GLOAD(KT_)                                                                               \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                 \
-        int key = (KT_) * 64 + srow + 32 * i;                                                       \
+    _Pragma("unroll") for (int i = 0; i < NPASS; ++i) {                                             \
+        int key = (KT_) * 64 + srow + SROWS * i;                                                    \
         key = key < L ? key : L - 1;                                                                \
         if constexpr (BLK) {   /* uniform base (k / v block column of this head) + a 32-bit element offset per lane */ \
             const unsigned t_ = (unsigned)(tok0 + key);                                             \
@@ -1468,9 +1492,9 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
         }                                                                                           \
     }
 #define AT_SSTORE(BUF)                                                                              \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                 \
-        *reinterpret_cast<v4f*>(Ks + (BUF) * 8192 + swz_byte(srow + 32 * i, schunk)) = rk[i];       \
-        *reinterpret_cast<v4f*>(Vs + (BUF) * 8192 + (BLK ? vblk_byte(srow + 32 * i, schunk) : vswz_byte(srow + 32 * i, schunk))) = rv[i]; \
+    _Pragma("unroll") for (int i = 0; i < NPASS; ++i) {                                             \
+        *reinterpret_cast<v4f*>(Ks + (BUF) * 8192 + swz_byte(srow + SROWS * i, schunk)) = rk[i];    \
+        *reinterpret_cast<v4f*>(Vs + (BUF) * 8192 + (BLK ? vblk_byte(srow + SROWS * i, schunk) : vswz_byte(srow + SROWS * i, schunk))) = rv[i]; \
     }
     // BLK: K / V tiles go global -> LDS by LDS-DMA (no staging registers, no ds_write): a tile is 4 key blocks x 2 KiB per
     // operand, wave w copies key block w in two 1-KiB pieces (4 pieces of 16 keys each).  The K tile is the block image
@@ -1500,7 +1524,7 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
     }
     __syncthreads();
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
+    for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[mt][r] = 0.f;
     float mrun = 0.f, lrun = 0.f;   // SAFE: mrun = reference of the exponentials = running maximum after the first tile
@@ -1535,11 +1559,16 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
             // pre-scaled by log2(e)/8 and bias_tab by log2(e), so the softmax uses v_exp_f32 (exp2) directly.
             f32x16 s;
             {
-                const float* bl = bt + (key0 + 4 * fh - qic + (maxL - 1));
+                if constexpr (BIAS) {
+                    const float* bl = bt + (key0 + 4 * fh - qic + (maxL - 1));
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {   // (the table has 64 entries of padding)
-                    if constexpr (SAFE) s[r] = bl[(r & 3) + 8 * (r >> 2)] - mrun;
-                    else s[r] = bl[(r & 3) + 8 * (r >> 2)];
+                    for (int r = 0; r < 16; ++r) {   // (the table has 64 entries of padding)
+                        if constexpr (SAFE) s[r] = bl[(r & 3) + 8 * (r >> 2)] - mrun;
+                        else s[r] = bl[(r & 3) + 8 * (r >> 2)];
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) s[r] = SAFE ? -mrun : 0.f;
                 }
                 if (key0 + 32 > L) {
 #pragma unroll
@@ -1548,7 +1577,7 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
                 }
             }
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
+            for (int ks = 0; ks < NKS; ++ks) {
                 const v4f kf = *reinterpret_cast<const v4f*>(Kb + (BLK ? (2 * sub + (fr >> 4)) * 2048 + (2 * ks + fh) * 256 + (fr & 15) * 16
                                                                        : swz_byte(sub * 32 + fr, 2 * ks + fh)));
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, kf), __builtin_bit_cast(v8bf, qf[ks]), s, 0, 0, 0);
@@ -1575,7 +1604,7 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
                     mrun += d;
                     lrun *= alpha;
 #pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
+                    for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) oacc[mt][r] *= alpha;
                 }
@@ -1597,7 +1626,7 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
 #pragma unroll
                 for (int j = 0; j < 8; ++j) pf[j] = (__bf16)s[8 * st + j];
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
+                for (int mt = 0; mt < NMT; ++mt) {
                     // lane (d = 32*mt + fr, half fh): keys {16st+4fh+0..3} and {16st+8+4fh+0..3}
                     // (BLK: the lane offset is made opaque per read pair: with plain loop-invariant addresses hipcc hoists
                     // the transposed reads of a whole tile, 248 bytes of scratch per lane and Q fragments reloaded in the loop)
@@ -1631,15 +1660,18 @@ __device__ __forceinline__ float attn_pass(const bf16_t* __restrict__ qkv, char*
 }
 
 // `range`: the fast pass is kept when every row sum lies in (1 / range, range); 0 forces the SAFE pass (tests).
-template <int HD, bool BLK>
+// HD = 64 (MPNet, BERT-base) or 32 (BERT hidden 384, row-major qkv); BIAS = false: no position bias (BERT), dynamic LDS
+// is then the K / V tiles alone (4 * 8192 bytes).
+template <int HD, bool BLK, bool BIAS = true>
 __global__ __launch_bounds__(256, 4) void k_attention_bf16(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ cu,
                                                         const float* __restrict__ bias_tab, int maxL, int hidden,
                                                         bf16_t* __restrict__ ctx, int nqb, int heads, float range) {
-    static_assert(HD == 64, "head_dim 64");
+    static_assert(HD == 64 || (HD == 32 && !BLK), "head_dim 64, or 32 on row-major qkv");
+    constexpr int NKS = HD / 16, NMT = HD / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;                 // [2][64 keys][128 B]  (swizzled)
     char* Vs = smem + 2 * 8192;      // [2][64 keys][128 B]  (row-major, halves exchanged: vswz_byte)
-    float* bt = reinterpret_cast<float*>(smem + 4 * 8192);  // [2*maxL-1] + 64 (padding read by the last, partial tile)
+    float* bt = reinterpret_cast<float*>(smem + 4 * 8192);  // [2*maxL-1] + 64 (padding read by the last, partial tile); BIAS only
 
     // 1-D grid of B * nqb * heads blocks.  The nqb query blocks of one (sequence, head) read the same K / V rows:
     // they get consecutive slots of ONE XCD (blocks l, l + 8, l + 16, ... share an XCD under round-robin dispatch;
@@ -1660,7 +1692,7 @@ __global__ __launch_bounds__(256, 4) void k_attention_bf16(const bf16_t* __restr
     const int qi = q0 + wave * 32 + fr;
     const int qic = qi < L ? qi : L - 1;
     // Q fragments as B operand: lane holds Q[query][16*ks + 8*fh + j]
-    v4f qf[4];
+    v4f qf[4] = {};
     {
         if constexpr (BLK) {   // piece cl = 2 ks + fh of this token's row in the q block of `head` (see attn_pass)
             const int t_ = tok0 + qic;
@@ -1670,10 +1702,10 @@ __global__ __launch_bounds__(256, 4) void k_attention_bf16(const bf16_t* __restr
         } else {
             const bf16_t* qp = qkv + (size_t)(tok0 + qic) * (3 * hidden) + head * HD;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const v4f*>(qp + 16 * ks + 8 * fh);
+            for (int ks = 0; ks < NKS; ++ks) qf[ks] = *reinterpret_cast<const v4f*>(qp + 16 * ks + 8 * fh);
         }
     }
-    {
+    if constexpr (BIAS) {
         const float* bsrc = bias_tab + (size_t)head * (2 * maxL - 1);
         for (int i = tid; i < 2 * maxL - 1 + 64; i += 256) bt[i] = i < 2 * maxL - 1 ? bsrc[i] : 0.f;
     }
@@ -1683,16 +1715,16 @@ __global__ __launch_bounds__(256, 4) void k_attention_bf16(const bf16_t* __restr
     // every tile's first 32 keys -- every tile waited for the NEXT tile's global loads issued a few instructions
     // earlier, and the register prefetch hid nothing (round 2: 2.5 ms per batch).
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(qf[ks]));
+    for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(qf[ks]));
 
     f32x16 oacc[2];
     float ltot = 0.f;
     bool ok = false;
     if (range > 0.f) {
-        ltot = attn_pass<HD, false, BLK>(qkv, Ks, Vs, bt, tok0, L, head, hidden, maxL, qic, qf, oacc);
+        ltot = attn_pass<HD, false, BLK, BIAS>(qkv, Ks, Vs, bt, tok0, L, head, hidden, maxL, qic, qf, oacc);
         ok = ltot < range && ltot * range > 1.0f;   // (NaN compares false)
     }
-    if (!__syncthreads_and(ok)) ltot = attn_pass<HD, true, BLK>(qkv, Ks, Vs, bt, tok0, L, head, hidden, maxL, qic, qf, oacc);
+    if (!__syncthreads_and(ok)) ltot = attn_pass<HD, true, BLK, BIAS>(qkv, Ks, Vs, bt, tok0, L, head, hidden, maxL, qic, qf, oacc);
     const float inv = 1.0f / ltot;
     if constexpr (BLK) {
         // ctx in the blocked layout (preblk_elem, H = hidden; it is the O projection's A operand): lane (query fr, half fh)
@@ -1724,9 +1756,10 @@ __global__ __launch_bounds__(256, 4) void k_attention_bf16(const bf16_t* __restr
     // full 128-B line as 16-B stores.  Rows padded to 144 B (as k_gemm8p's epilogue).
     {
         constexpr int OROW = 144;
+        constexpr int LPR = HD / 8, RPI = 64 / LPR;   // lanes per output row (16-B stores), rows per wave instruction
         char* ow = smem + wave * (32 * OROW);
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
+        for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 ushort4 h;
@@ -1740,19 +1773,22 @@ __global__ __launch_bounds__(256, 4) void k_attention_bf16(const bf16_t* __restr
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int row = 8 * t + (lane >> 3);
-            const v4f o = *reinterpret_cast<const v4f*>(ow + row * OROW + (lane & 7) * 16);
+        for (int t = 0; t < 32 / RPI; ++t) {
+            const int row = RPI * t + lane / LPR;
+            const v4f o = *reinterpret_cast<const v4f*>(ow + row * OROW + (lane % LPR) * 16);
             const int q = q0 + wave * 32 + row;
-            if (q < L) *reinterpret_cast<v4f*>(ctx + (size_t)(tok0 + q) * hidden + head * HD + (lane & 7) * 8) = o;
+            if (q < L) *reinterpret_cast<v4f*>(ctx + (size_t)(tok0 + q) * hidden + head * HD + (lane % LPR) * 8) = o;
         }
     }
 }
 
-// fp32 verification attention: one wave per (sequence, head, query); plain loops.
+// fp32 verification attention: one wave per (sequence, head, query); plain loops.  HD = head_dim (64 or 32: lane = output
+// dim, lanes >= HD only take part in the score loop); bias_tab = nullptr: no position bias (BERT).
+template <int HD>
 __global__ __launch_bounds__(64) void k_attention_f32(const float* __restrict__ qkv, const int32_t* __restrict__ cu,
                                                       const float* __restrict__ bias_tab, int maxL, int hidden,
                                                       float* __restrict__ ctx) {
+    static_assert(HD == 64 || HD == 32, "head_dim 64 or 32");
     __shared__ float sc[512];
     const int b = blockIdx.x, head = blockIdx.z, qi = blockIdx.y;
     const int tok0 = cu[b];
@@ -1760,14 +1796,14 @@ __global__ __launch_bounds__(64) void k_attention_f32(const float* __restrict__ 
     if (qi >= L) return;
     const int lane = threadIdx.x;
     const int ld = 3 * hidden;
-    const float* q = qkv + (size_t)(tok0 + qi) * ld + head * 64;  // already scaled by 1/8
-    const float* bt = bias_tab + (size_t)head * (2 * maxL - 1);
+    const float* q = qkv + (size_t)(tok0 + qi) * ld + head * HD;  // already scaled by 1/sqrt(HD)
+    const float* bt = bias_tab ? bias_tab + (size_t)head * (2 * maxL - 1) : nullptr;
     float mx = -INFINITY;
     for (int j = lane; j < L; j += 64) {
-        const float* kk = qkv + (size_t)(tok0 + j) * ld + hidden + head * 64;
+        const float* kk = qkv + (size_t)(tok0 + j) * ld + hidden + head * HD;
         float s = 0.f;
-        for (int d = 0; d < 64; ++d) s = fmaf(q[d], kk[d], s);
-        s += bt[j - qi + (maxL - 1)];
+        for (int d = 0; d < HD; ++d) s = fmaf(q[d], kk[d], s);
+        if (bt) s += bt[j - qi + (maxL - 1)];
         sc[j] = s;
         mx = fmaxf(mx, s);
     }
@@ -1780,9 +1816,10 @@ __global__ __launch_bounds__(64) void k_attention_f32(const float* __restrict__ 
     }
     sum = wave_allsum(sum);
     __syncthreads();
+    if (lane >= HD) return;
     float o = 0.f;  // lane = output dim d
-    for (int j = 0; j < L; ++j) o = fmaf(sc[j], qkv[(size_t)(tok0 + j) * ld + 2 * hidden + head * 64 + lane], o);
-    ctx[(size_t)(tok0 + qi) * hidden + head * 64 + lane] = o / sum;
+    for (int j = 0; j < L; ++j) o = fmaf(sc[j], qkv[(size_t)(tok0 + j) * ld + 2 * hidden + head * HD + lane], o);
+    ctx[(size_t)(tok0 + qi) * hidden + head * HD + lane] = o / sum;
 }
 
 // ---------------------------------------------------------------- pooling
@@ -1906,6 +1943,62 @@ __global__ __launch_bounds__(256) void k_pool_final(const float* __restrict__ pa
         const int c = tid + 256 * i;
         if (c < H) out[(size_t)b * H + c] = normalize ? acc[i] / nrm : acc[i];
     }
+}
+
+// CLS pooling (sentence-transformers Pooling with pooling_mode_cls_token): the row of token 0 of every sequence, then
+// the optional e / max(||e||, 1e-12) of k_pool_final.  One block per sequence; thread tid owns columns tid + 256 i.
+template <int H>
+__device__ __forceinline__ void cls_pool_write(const float (&v)[(H + 255) / 256], int normalize, float* __restrict__ orow) {
+    __shared__ float red[4];
+    const int tid = threadIdx.x;
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < (H + 255) / 256; ++i) ss += v[i] * v[i];   // (columns >= H hold 0)
+    ss = wave_allsum(ss);
+    if ((tid & 63) == 0) red[tid >> 6] = ss;
+    __syncthreads();
+    const float nrm = fmaxf(sqrtf(red[0] + red[1] + red[2] + red[3]), 1e-12f);
+#pragma unroll
+    for (int i = 0; i < (H + 255) / 256; ++i) {
+        const int c = tid + 256 * i;
+        if (c < H) orow[c] = normalize ? v[i] / nrm : v[i];
+    }
+}
+
+// fp32 token rows y [T][H] (the last LayerNorm's output)
+template <int H>
+__global__ __launch_bounds__(256) void k_pool_cls(const float* __restrict__ y, const int32_t* __restrict__ cu, int normalize,
+                                                  float* __restrict__ out) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* row = y + (size_t)cu[b] * H;
+    float v[(H + 255) / 256];
+#pragma unroll
+    for (int i = 0; i < (H + 255) / 256; ++i) {
+        const int c = tid + 256 * i;
+        v[i] = c < H ? row[c] : 0.f;
+    }
+    cls_pool_write<H>(v, normalize, out + (size_t)b * H);
+}
+
+// LayerNorm-folded path: the row is the last pre tensor (bf16, blocked layout) and the last LayerNorm is applied on the
+// way with its row statistics, as k_pool_partial_ln does: LN(p)[c] = gamma[c] (p[c] rs - mu rs) + beta[c].
+template <int H>
+__global__ __launch_bounds__(256) void k_pool_cls_ln(const bf16_t* __restrict__ pre, const long long* __restrict__ stats,
+                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                     float inv_h, float eps, const int32_t* __restrict__ cu, int normalize,
+                                                     float* __restrict__ out) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int t = cu[b];
+    const v4u32 raw = *reinterpret_cast<const v4u32*>(stats + (size_t)t * 2);
+    float rs, mrs;
+    row_stats_decode(raw, inv_h, eps, rs, mrs);
+    float v[(H + 255) / 256];
+#pragma unroll
+    for (int i = 0; i < (H + 255) / 256; ++i) {
+        const int c = tid + 256 * i;
+        v[i] = c < H ? fmaf(gamma[c], fmaf(bf2f(pre[preblk_elem(t, c, H)]), rs, -mrs), beta[c]) : 0.f;
+    }
+    cls_pool_write<H>(v, normalize, out + (size_t)b * H);
 }
 
 // ---------------------------------------------------------------- weights

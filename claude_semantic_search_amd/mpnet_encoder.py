@@ -1,4 +1,5 @@
-"""``MpnetEncoder``: the sentence encoder on the MI355X behind the six
+"""``MpnetEncoder``: the sentence encoder on the MI355X (MPNet, or BERT checkpoints such as all-MiniLM-L6-v2 and
+bge-*-en-v1.5; ``parse_model_config``) behind the six
 ``SentenceTransformer`` members the reference touches:
 ``.to(dev)``, ``.max_seq_length``, ``.get_sentence_embedding_dimension()``,
 ``.device`` and ``.encode(str|list, batch_size=, normalize_embeddings=,
@@ -28,7 +29,106 @@ from . import _native as nat
 from .tokenizer import HashTokenizer, WordPieceTokenizer, make_wordpiece  # noqa: F401
 
 DEFAULT_CFG = dict(num_layers=12, hidden=768, heads=12, ffn=3072, vocab=30527, max_pos=514, rel_buckets=32,
-                   pad_id=1, max_seq_len=384, ln_eps=1e-5)
+                   pad_id=1, max_seq_len=384, ln_eps=1e-5, arch="mpnet", pooling="mean", normalize=True)
+#: all-MiniLM-L6-v2 geometry (BERT, hidden 384, 12 heads of 32, mean pooling + Normalize); synthetic-weight runs
+#: override num_layers / pooling as needed
+BERT_SMALL_CFG = dict(num_layers=6, hidden=384, heads=12, ffn=1536, vocab=30522, max_pos=512, rel_buckets=0,
+                      pad_id=0, max_seq_len=512, ln_eps=1e-12, arch="bert", pooling="mean", normalize=True)
+#: bge-base-en-v1.5 geometry (BERT, hidden 768, 12 heads of 64, CLS pooling + Normalize)
+BERT_BASE_CFG = dict(BERT_SMALL_CFG, num_layers=12, hidden=768, ffn=3072, pooling="cls")
+
+_ARCH_ID = {"mpnet": 0, "bert": 1}
+_POOL_ID = {"mean": 0, "cls": 1}
+_KERNEL_LIMIT_SEQ = 512
+_ST_MODULES = {"sentence_transformers.models.Transformer": "transformer",
+               "sentence_transformers.models.Pooling": "pooling",
+               "sentence_transformers.models.Normalize": "normalize"}
+
+
+def _pooling_mode(pcfg: dict) -> str:
+    """mean / cls from a sentence-transformers ``Pooling`` config; any other mode raises ``ValueError`` naming it."""
+    if "pooling_mode" in pcfg and isinstance(pcfg["pooling_mode"], str):   # (the short form some versions write)
+        mode = pcfg["pooling_mode"]
+        if mode not in ("mean", "cls"):
+            raise ValueError(f"unsupported pooling mode: pooling_mode={mode!r} (supported: 'mean', 'cls')")
+        return mode
+    on = sorted(k for k, v in pcfg.items() if k.startswith("pooling_mode_") and v)
+    bad = [k for k in on if k not in ("pooling_mode_mean_tokens", "pooling_mode_cls_token")]
+    if bad:
+        raise ValueError(f"unsupported pooling mode: {', '.join(bad)} (supported: pooling_mode_mean_tokens, "
+                         "pooling_mode_cls_token)")
+    if len(on) != 1:
+        raise ValueError(f"pooling config must enable exactly one of pooling_mode_mean_tokens / pooling_mode_cls_token "
+                         f"(enabled: {on or 'none'})")
+    return "mean" if on[0] == "pooling_mode_mean_tokens" else "cls"
+
+
+def parse_model_config(model_dir: Union[str, Path]) -> dict:
+    """The encoder configuration of a checkpoint directory (no GPU needed): ``config.json`` of the transformer
+    (``model_type`` mpnet or bert, ``hidden_act`` gelu, geometry, ``layer_norm_eps``, ``pad_token_id``,
+    ``max_position_embeddings``) plus the sentence-transformers modules: the pooling mode from ``1_Pooling/config.json``
+    (mean or CLS) and whether a ``Normalize`` module follows (``modules.json``).  A directory without ``modules.json`` is
+    taken as Transformer + mean Pooling + Normalize (the all-mpnet-base-v2 pipeline).  Anything the kernels do not
+    implement raises ``ValueError`` naming the field."""
+    model_dir = Path(model_dir)
+    root = model_dir / "0_Transformer" if (model_dir / "0_Transformer").is_dir() else model_dir
+    hf = json.loads((root / "config.json").read_text())
+    model_type = hf.get("model_type", "mpnet")
+    if model_type not in _ARCH_ID:
+        raise ValueError(f"unsupported model_type {model_type!r} (supported: 'mpnet', 'bert')")
+    act = hf.get("hidden_act", "gelu")
+    if act != "gelu":
+        raise ValueError(f"unsupported hidden_act {act!r} (the encoder implements the exact erf 'gelu')")
+    bert = model_type == "bert"
+    hidden, heads = int(hf.get("hidden_size", 768)), int(hf.get("num_attention_heads", 12))
+    if heads < 1 or hidden % heads:
+        raise ValueError(f"hidden_size {hidden} is not a multiple of num_attention_heads {heads}")
+    head_dim = hidden // heads
+    if bert:
+        if hidden not in (384, 768):
+            raise ValueError(f"unsupported hidden_size {hidden} for model_type 'bert' (supported: 384, 768)")
+        if head_dim not in (32, 64):
+            raise ValueError(f"unsupported head_dim {head_dim} (hidden_size / num_attention_heads) for model_type "
+                             "'bert' (supported: 32, 64)")
+        if int(hf.get("type_vocab_size", 2)) != 2:
+            raise ValueError(f"unsupported type_vocab_size {hf['type_vocab_size']} (supported: 2)")
+        pet = hf.get("position_embedding_type", "absolute")
+        if pet != "absolute":
+            raise ValueError(f"unsupported position_embedding_type {pet!r} (supported: 'absolute')")
+    elif hidden != 768 or head_dim != 64:
+        raise ValueError(f"unsupported geometry for model_type 'mpnet': hidden_size {hidden}, head_dim {head_dim} "
+                         "(supported: 768, 64)")
+    max_pos = int(hf.get("max_position_embeddings", 512 if bert else 514))
+    cfg = dict(DEFAULT_CFG)
+    cfg.update(num_layers=int(hf.get("num_hidden_layers", 12)), hidden=hidden, heads=heads,
+               ffn=int(hf.get("intermediate_size", 4 * hidden)), vocab=int(hf.get("vocab_size", 30522 if bert else 30527)),
+               max_pos=max_pos, rel_buckets=int(hf.get("relative_attention_num_buckets", 0 if bert else 32)),
+               pad_id=int(hf.get("pad_token_id", 0 if bert else 1)),
+               ln_eps=float(hf.get("layer_norm_eps", 1e-12 if bert else 1e-5)), arch=model_type)
+    if bert:
+        cfg["max_seq_len"] = min(max_pos, _KERNEL_LIMIT_SEQ)
+    # sentence-transformers modules
+    mods_file = model_dir / "modules.json"
+    if mods_file.is_file():
+        mods = sorted(json.loads(mods_file.read_text()), key=lambda m: int(m.get("idx", 0)))
+        kinds = []
+        for m in mods:
+            kind = _ST_MODULES.get(m.get("type", ""))
+            if kind is None:
+                raise ValueError(f"unsupported sentence-transformers module {m.get('type')!r} in modules.json (supported: "
+                                 "Transformer, Pooling, Normalize)")
+            kinds.append(kind)
+        if kinds not in (["transformer", "pooling"], ["transformer", "pooling", "normalize"]):
+            raise ValueError(f"unsupported module list in modules.json: {kinds} (supported: Transformer, Pooling "
+                             "[, Normalize])")
+        pdir = model_dir / mods[1].get("path", "1_Pooling")
+        pcfg = json.loads((pdir / "config.json").read_text()) if (pdir / "config.json").is_file() else {}
+        cfg["pooling"] = _pooling_mode(pcfg) if pcfg else "mean"
+        wdim = pcfg.get("word_embedding_dimension")
+        if wdim is not None and int(wdim) != hidden:
+            raise ValueError(f"Pooling word_embedding_dimension {wdim} differs from hidden_size {hidden}")
+        cfg["normalize"] = kinds[-1] == "normalize"
+    return cfg
 
 
 def _is_model_dir(c: Path) -> bool:
@@ -138,21 +238,17 @@ class MpnetEncoder:
                     f"model '{model_name_or_path}' not found locally (no network): pass a directory in HF layout, "
                     "or synthetic_seed=<int> for seeded synthetic weights"
                 )
-            root = model_dir / "0_Transformer" if (model_dir / "0_Transformer").is_dir() else model_dir
-            hf = json.loads((root / "config.json").read_text())
-            cfg.update(num_layers=hf.get("num_hidden_layers", 12), hidden=hf.get("hidden_size", 768),
-                       heads=hf.get("num_attention_heads", 12), ffn=hf.get("intermediate_size", 3072),
-                       vocab=hf.get("vocab_size", 30527), max_pos=hf.get("max_position_embeddings", 514),
-                       rel_buckets=hf.get("relative_attention_num_buckets", 32), pad_id=hf.get("pad_token_id", 1),
-                       ln_eps=hf.get("layer_norm_eps", 1e-5))
+            cfg = parse_model_config(model_dir)
         if cfg_overrides:
             cfg.update(cfg_overrides)
+        if cfg["arch"] not in _ARCH_ID or cfg["pooling"] not in _POOL_ID:
+            raise ValueError(f"arch must be one of {sorted(_ARCH_ID)} and pooling one of {sorted(_POOL_ID)}")
         self.cfg = cfg
         self._device_index = int(device)
         self.compute = compute
         c = nat.EncoderCfg(cfg["num_layers"], cfg["hidden"], cfg["heads"], cfg["ffn"], cfg["vocab"], cfg["max_pos"],
                            cfg["rel_buckets"], cfg["pad_id"], cfg["max_seq_len"], cfg["ln_eps"],
-                           0 if compute == "bf16" else 1)
+                           0 if compute == "bf16" else 1, _ARCH_ID[cfg["arch"]], _POOL_ID[cfg["pooling"]])
         h = ctypes.c_void_p()
         nat.check(nat.lib().css_encoder_create(ctypes.byref(c), self._device_index, ctypes.byref(h)))
         self._h = h
@@ -191,7 +287,7 @@ class MpnetEncoder:
 
     # -- weights ------------------------------------------------------------
     def load_state_dict(self, sd: Dict[str, np.ndarray]) -> None:
-        names = [k for k in sd if "pooler." not in k and "position_ids" not in k]
+        names = [k for k in sd if "pooler." not in k and "position_ids" not in k and "token_type_ids" not in k]
         arr = (nat.Tensor * len(names))()
         keep = []
         for i, k in enumerate(names):
@@ -257,6 +353,7 @@ class MpnetEncoder:
             return np.zeros((0, self.cfg["hidden"]), dtype=np.float32)
         out = np.empty((len(texts), self.cfg["hidden"]), dtype=np.float32)
         bs = max(1, int(batch_size))
+        norm = bool(self.cfg.get("normalize", True) or normalize_embeddings)
         # Super-batches of 16 device batches: the next one is tokenised on a host thread (both the C++ tokenizer and
         # the forward release the GIL) while the GPU encodes the current one; texts are length-sorted inside a
         # super-batch (packed var-len batches have no padding, sorting only keeps a batch's attention tiles even).
@@ -274,8 +371,8 @@ class MpnetEncoder:
             order = sorted(range(len(toks)), key=lambda i: -len(toks[i]))
             for s in range(0, len(order), bs):
                 idx = order[s:s + bs]
-                # Normalize() is a module of the model: outputs are unit norm regardless of the flag
-                out[[base + i for i in idx]] = self.encode_ids([toks[i] for i in idx], normalize=True)
+                # a Normalize() module of the model makes outputs unit norm regardless of the flag
+                out[[base + i for i in idx]] = self.encode_ids([toks[i] for i in idx], normalize=norm)
                 if bar is not None:
                     bar.update(1)
 

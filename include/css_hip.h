@@ -184,11 +184,15 @@ int css_merge_topk_dev(const float* D_parts_dev, const int64_t* I_parts_dev, int
 int css_merge_topk_packed_dev(const void* packed_dev, int nparts, int64_t record_bytes, int64_t nq, int k,
                               int metric, float* D_out_dev, int64_t* I_out_dev, int device, void* stream);
 
-/* ---- MPNet sentence encoder (all-mpnet-base-v2 architecture) ---- */
+/* ---- sentence encoder: MPNet (all-mpnet-base-v2 architecture) or BERT ---- */
+#define CSS_ENCODER_ARCH_MPNET 0
+#define CSS_ENCODER_ARCH_BERT 1
+#define CSS_ENCODER_POOL_MEAN 0
+#define CSS_ENCODER_POOL_CLS 1
 typedef struct css_encoder_cfg {
     int num_layers;       /* 12 */
-    int hidden;           /* 768 */
-    int heads;            /* 12 (head_dim = hidden / heads must be 64) */
+    int hidden;           /* 768 (BERT: 384 or 768) */
+    int heads;            /* 12 (head_dim = hidden / heads: 64; BERT: 32 at hidden 384, 64 at hidden 768) */
     int ffn;              /* 3072 */
     int vocab;            /* 30527 */
     int max_pos;          /* 514 */
@@ -197,6 +201,12 @@ typedef struct css_encoder_cfg {
     int max_seq_len;      /* 384 (kernel limit 512) */
     float ln_eps;         /* 1e-5 */
     int compute;          /* 0 = bf16 MFMA (product), 1 = fp32 verification mode */
+    /* Trailing fields: 0 keeps the MPNet / mean-pooling meaning of a zeroed or shorter-initialised struct. */
+    int arch;             /* CSS_ENCODER_ARCH_MPNET (0) or CSS_ENCODER_ARCH_BERT (1): BERT = absolute positions 0..L-1
+                             plus token_type_embeddings row 0, no relative bias, tensor names of transformers' BertModel
+                             (max_pos >= max_seq_len, rel_buckets ignored, 2 token types) */
+    int pooling;          /* CSS_ENCODER_POOL_MEAN (0): masked mean of the token rows; CSS_ENCODER_POOL_CLS (1): row of
+                             token 0 of every sequence */
 } css_encoder_cfg;
 
 typedef struct css_tensor {
@@ -214,7 +224,7 @@ int css_encoder_init_synthetic(css_encoder* enc, uint64_t seed);
 int css_encoder_export_weight(const css_encoder* enc, const char* name, float* out_host, int64_t numel);
 /* Packed var-len batch: input_ids[cu_seqlens[B]] tokens, sequence b occupies
  * [cu_seqlens[b], cu_seqlens[b+1]); every length in [1, max_seq_len].
- * out: [B, hidden] fp32 = masked mean-pool (+ L2 normalise when normalize != 0).
+ * out: [B, hidden] fp32 = masked mean-pool or CLS row (cfg.pooling) (+ L2 normalise when normalize != 0).
  * The same batch gives the same bits on every run (row statistics of the folded
  * LayerNorm are accumulated with integer atomics); another batch composition may take
  * another kernel path (GEMM tile walk, folded / separate LayerNorm): bf16 rounding noise. */
