@@ -79,6 +79,8 @@ PROTOTYPES = {
     "css_index_free": (c_int, [c_void_p]),
     "css_index_reset": (c_int, [c_void_p]),
     "css_index_reserve": (c_int, [c_void_p, c_int64]),
+    "css_index_remove_rows": (c_int, [c_void_p, c_void_p, POINTER(c_int64)]),
+    "css_index_bounds": (c_int, [c_void_p, POINTER(c_float)]),
     "css_index_ntotal": (c_int, [c_void_p, POINTER(c_int64)]),
     "css_index_dim": (c_int, [c_void_p, POINTER(c_int)]),
     "css_index_metric": (c_int, [c_void_p, POINTER(c_int)]),

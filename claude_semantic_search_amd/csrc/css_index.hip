@@ -15,6 +15,8 @@
 // Kernels (DESIGN.md has the rooflines):
 //   k_ingest_rows      one wave per row: optional synthetic generation, fused
 //                      x/(||x||+1e-8), zero pad, squared norm, bf16 shadow.  HBM bound
+//   k_compact_rows     css_index_remove_rows: survivors re-ingested at their new slots, window after
+//                      window (k_keep_prefix, k_compact_gather, k_rows_maxima).  HBM bound
 //   k_scan_coarse,     default search path: coarse bf16 scores (MFMA scan for
 //   k_sweep_coarse,    batches, HBM-bound sweep for 1..4 queries) inside a rigorous
 //   k_coarse_select    error band, then exact fp32 rescoring of the band (css_knn_coarse.h)
@@ -89,6 +91,8 @@ struct css_index {
     char* h_stage = nullptr;
     static constexpr size_t kHostStage = 64 * 1024;   // bytes, each way
     float* stage = nullptr;   size_t stage_cap = 0;     // floats
+    // css_index_remove_rows: keep bits and their popcount prefix of ONE window of rows (at most 2 MiB each)
+    uint32_t* compact_bits = nullptr; uint32_t* compact_pre = nullptr; size_t compact_cap = 0;   // words
     // coarse + rescore path (css_knn_coarse.h)
     unsigned short* qh = nullptr; size_t qh_cap = 0;    // bf16 queries
     float* cthr = nullptr;    size_t cthr_cap = 0;
@@ -149,7 +153,9 @@ int grow(T** p, size_t* cap, size_t need) {
 
 // ------------------------------------------------------------------ ingest
 // One wave per row.  SYNTH: value = css_synth_normal(seed, (first_row+row)*dim + c).
-template <bool SYNTH>
+// STORE = false: nothing but the running maxima is written (dst unused; pass norm2 / dsth / err2_out / dst8 as null):
+// css_index_remove_rows re-measures the rows it leaves in place with the arithmetic of the ingest.
+template <bool SYNTH, bool STORE = true>
 __device__ __forceinline__ void ingest_row(int64_t row, int lane, const float* __restrict__ src, float* __restrict__ dst,
                                            float* __restrict__ norm2, int dim, int dpad, int normalize, uint64_t seed,
                                            int64_t first_row, unsigned short* __restrict__ dsth, int* __restrict__ maxn2,
@@ -167,7 +173,7 @@ __device__ __forceinline__ void ingest_row(int64_t row, int lane, const float* _
     amax = wave_allmax(amax);
     // reference: x / (||x||_2 + 1e-8)  (src/storage.py:349-350, :426)
     const float nrm = sqrtf(ss) + 1e-8f;
-    float* d = dst + row * (int64_t)dpad;
+    float* d = STORE ? dst + row * (int64_t)dpad : nullptr;
     // int8 shadow row: byte = rint(v / s8), s8 = max|v| / 127 (of the values as stored, i.e. after normalisation)
     if (normalize) amax = amax / nrm;
     const float s8 = amax > 0.f ? amax / 127.f : 1.f, inv8 = amax > 0.f ? 127.f / amax : 0.f;
@@ -179,7 +185,7 @@ __device__ __forceinline__ void ingest_row(int64_t row, int lane, const float* _
             v = SYNTH ? css_synth_normal(seed, base + (uint64_t)c) : s[c];
             if (normalize) v = v / nrm;
         }
-        d[c] = v;
+        if (STORE) d[c] = v;
         const __bf16 h = (__bf16)v;   // the rounding every bf16 copy of this row uses (shadow rows, k_rows_to_bf16*)
         if (dsth) dsth[row * (int64_t)dpad + c] = __builtin_bit_cast(unsigned short, h);
         s2 = fmaf(v, v, s2);
@@ -221,6 +227,85 @@ __global__ __launch_bounds__(256) void k_ingest_rows(const float* __restrict__ s
     if (row >= n) return;
     ingest_row<SYNTH>(row, threadIdx.x & 63, src, dst, norm2, dim, dpad, normalize, seed, first_row, dsth, maxn2, err2_out, dst8,
                       dst8s);
+}
+
+// ------------------------------------------------------------------ remove rows (css_index_remove_rows)
+// In-place stream compaction of the rows behind the first removed one, window after window (the host plans the
+// windows: css_index_remove_rows; DESIGN.md "remove_ids" has the hazard argument).  `bits` / `pre` cover ONE window:
+// bit (r & 31) of bits[r >> 5] set = row r of the window survives, pre[w] = survivors of the window in words < w.
+constexpr int64_t kCompactWindowRows = 1ll << 24;   // rows per launch (one wave per row, as ingest())
+constexpr int64_t kCompactWords = kCompactWindowRows / 32;
+
+// Exclusive popcount prefix over the keep words of one window; ONE block of 1024 threads (<= 2 MB of words).
+__global__ __launch_bounds__(1024) void k_keep_prefix(const uint32_t* __restrict__ bits, uint32_t* __restrict__ pre, int words) {
+    __shared__ uint32_t part[1024];
+    const int t = threadIdx.x;
+    const int per = (words + 1023) / 1024;
+    const int w0 = min(t * per, words), w1 = min(w0 + per, words);
+    uint32_t s = 0;
+    for (int w = w0; w < w1; ++w) s += (uint32_t)__popc(bits[w]);
+    part[t] = s;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {   // Hillis-Steele inclusive scan
+        const uint32_t v = t >= off ? part[t - off] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - s;
+    for (int w = w0; w < w1; ++w) {
+        pre[w] = run;
+        run += (uint32_t)__popc(bits[w]);
+    }
+}
+
+// window-local number of the surviving row r among the survivors, or -1 (wave-uniform)
+__device__ __forceinline__ int64_t compact_slot(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ pre, int64_t r) {
+    const uint32_t w = bits[r >> 5];
+    const int b = (int)(r & 31);
+    if (!((w >> b) & 1u)) return -1;
+    return (int64_t)pre[r >> 5] + __popc(w & ((1u << b) - 1u));
+}
+
+// One wave per row of the window.  Survivor r (every row when bits is null): fp32 row read at src + r * dpad, and
+// the row re-ingested (normalize = 0) at slot `compact_slot` of the destination arrays: ingest_row writes the fp32 row,
+// its norm and the shadow rows the index keeps, and raises the three maxima -- the bits of an ingest of that row.
+// The caller guarantees that no destination slot of the launch is a source row of the launch.
+__global__ __launch_bounds__(256) void k_compact_rows(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ pre,
+                                                      int64_t n, const float* src, float* dst, float* norm2, int dim, int dpad,
+                                                      unsigned short* dsth, int* __restrict__ maxn2, unsigned char* dst8,
+                                                      float* dst8s) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const int64_t o = bits ? compact_slot(bits, pre, r) : r;
+    if (o < 0) return;
+    ingest_row<false>(0, threadIdx.x & 63, src + r * (int64_t)dpad, dst + o * (int64_t)dpad, norm2 + o, dim, dpad, 0, 0ull, 0ll,
+                      dsth ? dsth + o * (int64_t)dpad : nullptr, maxn2, (float*)nullptr, dst8 ? dst8 + o * (int64_t)dpad : nullptr,
+                      dst8 ? dst8s + o : nullptr);
+}
+
+// Bounce, first half: the fp32 rows of the window's survivors, packed into the scratch rows (16 bytes per lane, whole
+// 128-byte lines; the scratch is read again at once by k_compact_rows, so plain stores).
+__global__ __launch_bounds__(256) void k_compact_gather(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ pre,
+                                                        int64_t n, const float* __restrict__ src, float* __restrict__ scratch,
+                                                        int dpad) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const int64_t o = compact_slot(bits, pre, r);
+    if (o < 0) return;
+    typedef float nt_f4 __attribute__((ext_vector_type(4)));
+    const nt_f4* s = reinterpret_cast<const nt_f4*>(src + r * (int64_t)dpad);
+    nt_f4* d = reinterpret_cast<nt_f4*>(scratch + o * (int64_t)dpad);
+    for (int c = threadIdx.x & 63; c < dpad / 4; c += 64) d[c] = __builtin_nontemporal_load(s + c);
+}
+
+// The rows that stay where they are (below the first removed row): the three maxima only, nothing written to the rows.
+__global__ __launch_bounds__(256) void k_rows_maxima(const float* __restrict__ rows, int64_t n, int dim, int dpad,
+                                                     int* __restrict__ maxn2) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    ingest_row<false, false>(0, threadIdx.x & 63, rows + r * (int64_t)dpad, (float*)nullptr, (float*)nullptr, dim, dpad, 0, 0ull,
+                             0ll, (unsigned short*)nullptr, maxn2, (float*)nullptr, (unsigned char*)nullptr, (float*)nullptr);
 }
 
 // ------------------------------------------------------------------ scan (small nq)
@@ -2755,7 +2840,8 @@ int css_index_free(css_index* ix) {
     void* ptrs[] = {ix->xb, ix->xnorm2, ix->xh, ix->x8, ix->x8s, ix->maxn2, ix->q_raw, ix->qpad, ix->qnorm2, ix->qerr2, ix->qerr2_i8, ix->qscale, ix->gthr, ix->qsplit,
                     ix->part_s, ix->part_i, ix->out_i, ix->stage, ix->qh, ix->cthr, ix->cand_n,
                     ix->cflags, ix->cand_s, ix->cand_i, ix->cpace, ix->fs_state, ix->mask_ws, ix->excl_ws, ix->fix_s, ix->fix_i, ix->fix_lock,
-                    ix->qh2, ix->thr2, ix->rs_work, ix->cand_n2, ix->cand_s2, ix->cand_i2, ix->flagB, ix->xh_tmp, ix->x8s_tmp, ix->rng_d, ix->rng_i};
+                    ix->qh2, ix->thr2, ix->rs_work, ix->cand_n2, ix->cand_s2, ix->cand_i2, ix->flagB, ix->xh_tmp, ix->x8s_tmp, ix->rng_d, ix->rng_i,
+                    ix->compact_bits, ix->compact_pre};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);  // (hipFree waits for the device: nothing enqueued by a _dev call still runs)
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -2777,6 +2863,139 @@ int css_index_reset(css_index* ix) {
     if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ws_ev, 0));   // a search enqueued on another stream still reads maxn2
     CSS_HIP_TRY(hipMemsetAsync(ix->maxn2, 0, 3 * sizeof(int), ix->stream));
     CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    return CSS_OK;
+}
+
+namespace {
+// The compaction proper (css_index_remove_rows): rows [first, n) of which `kept - first` survive.  Everything is
+// enqueued on the index's stream; the caller waits for it.  Host memory read by the copies (keep, *patch) stays
+// valid until then.
+int compact_rows(css_index* ix, const uint32_t* keep, int64_t n, int64_t first, uint32_t* patch) {
+    const hipStream_t st = ix->stream;
+    const int dpad = ix->dpad;
+    int rc;
+    // the rows below the first removed one stay: one read for the maxima
+    for (int64_t c0 = 0; c0 < first; c0 += kCompactWindowRows) {
+        const int64_t nc = std::min(kCompactWindowRows, first - c0);
+        hipLaunchKernelGGL(k_rows_maxima, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, st, ix->xb + (size_t)c0 * dpad, nc, ix->dim,
+                           dpad, ix->maxn2);
+        CSS_LAUNCH_CHECK();
+    }
+    // bounce rows: what 64 MiB hold, a whole number of keep words, never more than one launch covers
+    // (and never more than the rows that can move)
+    const int64_t W = std::min<int64_t>({kCompactWindowRows, std::max<int64_t>(32, ((64ll << 20) / ((int64_t)dpad * 4)) / 32 * 32),
+                                         (int64_t)((n - (first & ~31ll) + 31) / 32 * 32)});
+    const int64_t words = (n + 31) / 32;
+    const size_t need_words = (size_t)std::min<int64_t>(kCompactWords, words);
+    if (need_words > ix->compact_cap) {
+        if (ix->compact_bits) CSS_HIP_TRY(hipFree(ix->compact_bits));
+        if (ix->compact_pre) CSS_HIP_TRY(hipFree(ix->compact_pre));
+        ix->compact_bits = ix->compact_pre = nullptr;
+        ix->compact_cap = 0;
+        hipError_t e = hipMalloc((void**)&ix->compact_bits, need_words * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&ix->compact_pre, need_words * sizeof(uint32_t));
+        if (e != hipSuccess) return css::hip_fail(e, "hipMalloc(compaction bitmap)", __FILE__, __LINE__);
+        ix->compact_cap = need_words;
+    }
+    const uint32_t tail_mask = (n & 31) ? ((1u << (n & 31)) - 1u) : 0xFFFFFFFFu;
+    int64_t s0 = first & ~31ll;   // windows start on a keep word
+    int64_t dnext = first;        // next free slot
+    // the word that holds the first removed row: its lower rows stay where they are and are not part of the move
+    *patch = keep[first >> 5] & ~((1u << (first & 31)) - 1u);
+    while (s0 < n) {
+        const int64_t src0 = std::max(s0, first);
+        const int64_t gap = src0 - dnext;   // free slots below the window's first source row
+        // gap >= L: every destination of the window lies below its sources whatever the bits are
+        int64_t L = gap >= W ? std::min(gap / 32 * 32, kCompactWindowRows) : W;
+        L = std::min(L, n - s0);
+        const int64_t w0 = s0 >> 5, nw = (L + 31) / 32;
+        int64_t surv = 0;
+        for (int64_t w = 0; w < nw; ++w) {
+            uint32_t v = (w0 + w == (first >> 5)) ? *patch : keep[w0 + w];
+            if (w0 + w == words - 1) v &= tail_mask;
+            surv += __builtin_popcount(v);
+        }
+        if (surv > 0) {
+            CSS_HIP_TRY(hipMemcpyAsync(ix->compact_bits, keep + w0, (size_t)nw * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            if (w0 == (first >> 5))
+                CSS_HIP_TRY(hipMemcpyAsync(ix->compact_bits, patch, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_keep_prefix, dim3(1), dim3(1024), 0, st, ix->compact_bits, ix->compact_pre, (int)nw);
+            CSS_LAUNCH_CHECK();
+            const unsigned blocks = (unsigned)((L + 3) / 4);
+            float* dst = ix->xb + (size_t)dnext * dpad;
+            unsigned short* dh = ix->xh ? ix->xh + (size_t)dnext * dpad : nullptr;
+            unsigned char* d8 = ix->x8 ? ix->x8 + (size_t)dnext * dpad : nullptr;
+            float* d8s = ix->x8 ? ix->x8s + dnext : nullptr;
+            const float* src = ix->xb + (size_t)s0 * dpad;
+            if (dnext + surv <= src0) {   // destinations wholly below the sources: straight into place
+                hipLaunchKernelGGL(k_compact_rows, dim3(blocks), dim3(256), 0, st, ix->compact_bits, ix->compact_pre, L, src, dst,
+                                   ix->xnorm2 + dnext, ix->dim, dpad, dh, ix->maxn2, d8, d8s);
+                CSS_LAUNCH_CHECK();
+            } else {                      // they overlap: through the scratch rows, the kernel boundary orders read and overwrite
+                if ((rc = grow(&ix->stage, &ix->stage_cap, (size_t)W * dpad)) != CSS_OK) return rc;
+                hipLaunchKernelGGL(k_compact_gather, dim3(blocks), dim3(256), 0, st, ix->compact_bits, ix->compact_pre, L, src,
+                                   ix->stage, dpad);
+                CSS_LAUNCH_CHECK();
+                hipLaunchKernelGGL(k_compact_rows, dim3((unsigned)((surv + 3) / 4)), dim3(256), 0, st, (const uint32_t*)nullptr,
+                                   (const uint32_t*)nullptr, surv, ix->stage, dst, ix->xnorm2 + dnext, ix->dim, dpad, dh, ix->maxn2,
+                                   d8, d8s);
+                CSS_LAUNCH_CHECK();
+            }
+        }
+        dnext += surv;
+        s0 += L;
+    }
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t* removed_out) {
+    CSS_REQUIRE(ix && removed_out, "css_index_remove_rows: NULL argument");
+    *removed_out = 0;
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);   // (a search in progress may have the row view narrowed)
+    const int64_t n = ix->ntotal;
+    if (n == 0) return CSS_OK;
+    CSS_REQUIRE(keep_bits_host, "css_index_remove_rows: keep_bits is NULL");
+    const int64_t words = (n + 31) / 32;
+    const uint32_t tail_mask = (n & 31) ? ((1u << (n & 31)) - 1u) : 0xFFFFFFFFu;
+    int64_t first = -1, kept = 0;
+    for (int64_t w = 0; w < words; ++w) {
+        const uint32_t valid = w == words - 1 ? tail_mask : 0xFFFFFFFFu;
+        const uint32_t v = keep_bits_host[w] & valid;
+        kept += __builtin_popcount(v);
+        if (first < 0 && v != valid) first = w * 32 + __builtin_ctz(~v & valid);
+    }
+    if (first < 0) return CSS_OK;   // nothing to remove: no device work
+    DeviceGuard g(ix->device);
+    // pending asynchronous adds, and searches on other streams that still read the rows and maxn2
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
+    if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ws_ev, 0));
+    CSS_HIP_TRY(hipMemsetAsync(ix->maxn2, 0, 3 * sizeof(int), ix->stream));
+    uint32_t patch = 0;
+    const int rc = kept > 0 ? compact_rows(ix, keep_bits_host, n, first, &patch) : CSS_OK;
+    // later adds and searches on any stream are ordered behind the compaction (as css_index_reset)
+    const hipError_t e = hipStreamSynchronize(ix->stream);
+    if (rc != CSS_OK) return rc;
+    if (e != hipSuccess) return css::hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    ix->ntotal = kept;
+    ix->ntotal_pub.store(kept);
+    if (kept == 0 && !ix->xh) ix->shadow = -1;   // emptied: as css_index_reset
+    for (css_index::I8Feedback* f : {&ix->fb_batch, &ix->fb_sweep}) {   // (it described other rows; its copy has landed)
+        f->pending = false;
+        f->backoff = 0;
+    }
+    *removed_out = n - kept;
+    return CSS_OK;
+}
+
+int css_index_bounds(css_index* ix, float out[3]) {
+    CSS_REQUIRE(ix && out, "css_index_bounds: NULL argument");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    DeviceGuard g(ix->device);
+    CSS_HIP_TRY(hipDeviceSynchronize());   // diagnostics: whichever stream the last add ran on
+    CSS_HIP_TRY(hipMemcpy(out, ix->maxn2, 3 * sizeof(float), hipMemcpyDeviceToHost));
     return CSS_OK;
 }
 

@@ -47,6 +47,30 @@ def pack_allow_bits(allow, ntotal: int) -> np.ndarray:
     return out.view("<u4")
 
 
+def keep_mask_from_ids(ids, ntotal: int) -> np.ndarray:
+    """What ``remove_ids`` is given -> boolean keep mask of ``ntotal`` entries (True = the row stays).
+
+    ``ids`` is an array-like of integer row ids, or a boolean mask of length ``ntotal`` meaning "remove".  faiss'
+    semantics: ids outside ``[0, ntotal)`` and repeated ids are ignored, so the number of rows removed is
+    ``ntotal - keep.sum()``.  A mask of another length and ids that are not integers raise ``ValueError``."""
+    a = np.asarray(ids)
+    if a.dtype == np.bool_:
+        if a.ndim != 1 or a.shape[0] != ntotal:
+            raise ValueError(f"remove_ids: a boolean mask must have ntotal={ntotal} entries, got shape {a.shape}")
+        return ~a
+    if a.size == 0:
+        return np.ones(ntotal, dtype=np.bool_)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"remove_ids: ids must be integers or a boolean mask, got dtype {a.dtype}")
+    a = a.reshape(-1)
+    if a.dtype == np.uint64:
+        a = a[a < np.uint64(ntotal)]
+    a = a.astype(np.int64, copy=False)
+    keep = np.ones(ntotal, dtype=np.bool_)
+    keep[a[(a >= 0) & (a < ntotal)]] = False
+    return keep
+
+
 class IndexFlat:
     """Exact brute-force index in HBM (``faiss.IndexFlat`` semantics)."""
 
@@ -88,6 +112,26 @@ class IndexFlat:
 
     def reserve(self, n: int) -> None:
         nat.check(nat.lib().css_index_reserve(self._handle(), int(n)))
+
+    def remove_ids(self, ids) -> int:
+        """``faiss.IndexFlat.remove_ids``: drop the rows named by ``ids`` (integer row ids, or a boolean mask of
+        ``ntotal`` entries meaning "remove"), in place in HBM; later rows shift down.  Ids out of range or repeated
+        are ignored.  Returns the number of rows removed."""
+        n = self.ntotal
+        keep = keep_mask_from_ids(ids, n)
+        if n == 0 or bool(keep.all()):
+            return 0
+        bits = pack_allow_bits(keep, n)
+        removed = ctypes.c_int64(0)
+        nat.check(nat.lib().css_index_remove_rows(self._handle(), bits.ctypes.data, ctypes.byref(removed)))
+        return int(removed.value)
+
+    def bounds(self) -> dict:
+        """Diagnostics: the running maxima over the rows that the error bands of the candidate scans are built from
+        (``max ||x||^2``, ``max ||x - bf16(x)||^2``, ``max ||x - int8(x)||^2``)."""
+        out = (ctypes.c_float * 3)()
+        nat.check(nat.lib().css_index_bounds(self._handle(), out))
+        return {"max_norm2": float(out[0]), "max_bf16_err2": float(out[1]), "max_int8_err2": float(out[2])}
 
     def add(self, x, normalize: bool = False) -> None:
         """Append rows; ids are ``ntotal .. ntotal+n-1`` (``src/storage.py:358-365``).
@@ -251,17 +295,21 @@ _FOURCC = {METRIC_INNER_PRODUCT: b"IxFI", METRIC_L2: b"IxF2"}
 _FAISS_METRIC = {METRIC_INNER_PRODUCT: 0, METRIC_L2: 1}
 
 
+def _write_header(f, index, n: int) -> None:
+    f.write(_FOURCC[index.metric_type])
+    f.write(struct.pack("<i", index.d))
+    f.write(struct.pack("<q", n))
+    f.write(struct.pack("<q", 1 << 20))
+    f.write(struct.pack("<q", 1 << 20))
+    f.write(struct.pack("<B", 1))
+    f.write(struct.pack("<i", _FAISS_METRIC[index.metric_type]))
+    f.write(struct.pack("<Q", n * index.d))
+
+
 def write_index(index: IndexFlat, path: str, chunk_rows: int = 1 << 18) -> None:
     n = index.ntotal
     with open(path, "wb") as f:
-        f.write(_FOURCC[index.metric_type])
-        f.write(struct.pack("<i", index.d))
-        f.write(struct.pack("<q", n))
-        f.write(struct.pack("<q", 1 << 20))
-        f.write(struct.pack("<q", 1 << 20))
-        f.write(struct.pack("<B", 1))
-        f.write(struct.pack("<i", _FAISS_METRIC[index.metric_type]))
-        f.write(struct.pack("<Q", n * index.d))
+        _write_header(f, index, n)
         for r0 in range(0, n, chunk_rows):
             m = min(chunk_rows, n - r0)
             f.write(index.reconstruct_n(r0, m).tobytes())

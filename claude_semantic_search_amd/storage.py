@@ -135,6 +135,25 @@ def _row_to_chunk(row) -> Chunk:
     return Chunk(id=row["id"], text=row["text"], metadata=meta, embedding=None)
 
 
+class _LiveRows:
+    """The live rows of an index, seen as an index of their own by ``flat_index.write_index``: row ``i`` is row
+    ``ids[i]`` of ``index`` (``ids`` ascending).  Rows are exported run by run; nothing is copied into a second index."""
+
+    def __init__(self, index, ids):
+        self._index = index
+        self._ids = np.asarray(ids, dtype=np.int64)
+        self.d, self.metric_type, self.ntotal = index.d, index.metric_type, int(self._ids.shape[0])
+
+    def reconstruct_n(self, row0: int, n: int) -> np.ndarray:
+        out = np.empty((n, self.d), dtype=np.float32)
+        step = 1 << 16
+        for s in range(0, n, step):
+            part = self._ids[row0 + s:row0 + min(s + step, n)]
+            lo, hi = int(part[0]), int(part[-1]) + 1
+            out[s:s + part.shape[0]] = self._index.reconstruct_n(lo, hi - lo)[part - lo]
+        return out
+
+
 class HybridStorage:
     def __init__(self, config: Optional[StorageConfig] = None) -> None:
         self.config: StorageConfig = config or StorageConfig()
@@ -692,15 +711,21 @@ class HybridStorage:
             if not live:
                 return
             old = self.faiss_index
-            fresh = self._create_cpu_index()
-            fresh.reserve(len(live))
             ids = [r["faiss_id"] for r in live]
-            step = 1 << 16
-            for s in range(0, len(ids), step):
-                part = ids[s:s + step]
-                lo, hi = part[0], part[-1] + 1
-                block = old.reconstruct_n(lo, hi - lo)
-                fresh.add(block[np.asarray(part) - lo])  # already normalised
+            # An index that can drop rows in place (IndexFlat.remove_ids) is compacted where it lies: the compacted
+            # file is streamed from its live rows and the index itself shrinks only once both files have changed.
+            # Others (the sharded facade) are rebuilt into a second index.
+            in_place = hasattr(old, "remove_ids")
+            fresh = None
+            if not in_place:
+                fresh = self._create_cpu_index()
+                fresh.reserve(len(live))
+                step = 1 << 16
+                for s in range(0, len(ids), step):
+                    part = ids[s:s + step]
+                    lo, hi = part[0], part[-1] + 1
+                    block = old.reconstruct_n(lo, hi - lo)
+                    fresh.add(block[np.asarray(part) - lo])  # already normalised
             fwd: Dict[str, int] = {}
             rev: Dict[int, str] = {}
             updates = []
@@ -713,7 +738,10 @@ class HybridStorage:
             # file beside the index, then ONE transaction with the new ids + a flag, then the rename, then the flag
             # is cleared.  A crash at any point leaves a state the next initialize() completes or discards.
             compact = str(self.index_path) + ".compact"
-            self._write_index_atomically(fresh, compact)
+            if in_place:
+                self._write_index_atomically(_LiveRows(old, ids), compact)
+            else:
+                self._write_index_atomically(fresh, compact)
             cur.executemany("UPDATE chunks SET faiss_id = ? WHERE id = ?", updates)
             cur.execute("INSERT OR REPLACE INTO storage_meta (key, value) VALUES ('pending_compact', ?)", (str(len(live)),))
             self.db.commit()
@@ -722,13 +750,19 @@ class HybridStorage:
             _fsync_dir(self.index_path.parent)
             cur.execute("DELETE FROM storage_meta WHERE key = 'pending_compact'")
             self.db.commit()
+            if in_place:                        # (the live index shrinks only once both files have changed)
+                dead = np.ones(old.ntotal, dtype=np.bool_)
+                dead[np.asarray(ids, dtype=np.int64)] = False
+                old.remove_ids(np.flatnonzero(dead))
             self.chunk_id_to_faiss_id = fwd     # (in-memory maps change only once both files have)
             self.faiss_id_to_chunk_id = rev
-            self.faiss_index = fresh
-            self._saved_rows = fresh.ntotal
+            if not in_place:
+                self.faiss_index = fresh
+            self._saved_rows = self.faiss_index.ntotal
             self.total_chunks = len(live)
             self._mutations += 1
-            old.close()
+            if not in_place:
+                old.close()
         self.logger.info("Flat index rebuilt")
 
     def close(self) -> None:

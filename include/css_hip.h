@@ -80,6 +80,18 @@ int css_index_create(int dim, int metric, int device, css_index** out);
 int css_index_free(css_index* ix);
 int css_index_reset(css_index* ix);                 /* ntotal := 0, keeps capacity */
 int css_index_reserve(css_index* ix, int64_t n);    /* capacity >= n rows, no copy later */
+/* faiss IndexFlat::remove_ids: drop the rows whose bit is CLEAR in keep_bits (layout of allow_bits: bit (r & 31)
+ * of word r >> 5, local row numbering, ceil(ntotal / 32) words, host memory; bits beyond ntotal are ignored);
+ * surviving rows keep their order and move down, so row r becomes row r - (removed rows below r).
+ * *removed_out = number of rows dropped.  In place on the device: capacity and id_base are kept, rows below the
+ * first removed one are not moved, and the index ends in the state of one freshly built from the survivors (the
+ * reduced-precision row copies and the error-band maxima included).  Extra device memory does not grow with
+ * ntotal: at most 128 MiB of bounce rows (the staging buffer of css_index_add) and 4 MiB of keep bits and their
+ * prefix counts.  Waits for pending adds and searches and for its own work before it returns. */
+int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t* removed_out);
+/* Diagnostics: the three running maxima the error bands are built from (max ||x||^2, max ||x - bf16(x)||^2,
+ * max ||x - int8(x)||^2) as floats.  Waits for the device. */
+int css_index_bounds(css_index* ix, float out[3]);
 int css_index_ntotal(const css_index* ix, int64_t* n);
 int css_index_dim(const css_index* ix, int* dim);
 int css_index_metric(const css_index* ix, int* metric);
