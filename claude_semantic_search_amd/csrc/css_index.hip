@@ -26,6 +26,8 @@
 //   k_scan_mfma_split  exact batched scan on split bf16 operands (3 MFMAs per product);
 //   k_scan_mfma        the same on fp32-input MFMA (CSS_SEARCH_EXACT_FP32, verification)
 //   k_merge_final      per query: merge the per-block lists into the final top-k.
+//   k_range_small      css_index_range_search: the exact fp32 sweep with a radius test and a variable-length
+//                      hit list instead of top-k lists (css_knn_range.h).   HBM bound
 #include "css_common.h"
 #include "css_knn_kernels.h"
 #include "../../include/css_synth.h"
@@ -37,6 +39,7 @@
 #include <cfloat>
 #include <cmath>
 #include <mutex>
+#include <new>
 #include <shared_mutex>
 #include <type_traits>
 #include <vector>
@@ -119,6 +122,10 @@ struct css_index {
     int64_t range_rows = 0;   // css_index_set_range_rows: rows per range (0: from the free HBM, at most 2^24)
     float* rng_d = nullptr;   int64_t* rng_i = nullptr;  size_t rng_cap = 0;
     const int* last_nswept = nullptr;                    // device counter behind css_index_last_swept
+    // css_index_range_search (css_knn_range.h): hit counters of the 16 query slots of a sweep and the hit pool,
+    // range_cap entries (score + row) per slot; grown to the counted size when a sweep overflowed it
+    unsigned int* range_cnt = nullptr;
+    float* range_s = nullptr; uint32_t* range_i = nullptr; size_t range_cap = 0;
     // rows written by css_index_add_dev / _add_synthetic on the CALLER's stream: searches, reallocation and
     // export wait for this event before touching rows, norms or maxn2
     hipEvent_t ingest_ev = nullptr;
@@ -2481,6 +2488,80 @@ int make_sweep_geom(const css_index* ix, int k, SweepGeom* sg) {
     return CSS_OK;
 }
 
+// ------------------------------------------------------------------ range search (css_knn_range.h)
+#include "css_knn_range.h"
+
+constexpr int kRangeSlots = 16;              // query slots of one sweep (counters, pool segments)
+constexpr size_t kRangeInitialCap = 4096;    // pool entries per slot before the first growth
+
+template <int NQ, int TT, int METRIC>
+int launch_range_small_t(css_index* ix, const float* qpad, int nq_real, float radius, int G, int64_t gpb, hipStream_t st) {
+    const size_t lds = (size_t)NQ * ix->dpad * 4;
+    auto kern = k_range_small<NQ, TT, METRIC>;
+    int rc;
+    if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
+    ProfScope ps("knn_range_small", st);
+    hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, st, (const float4*)ix->xb, qpad, ix->ntotal, ix->dpad / 64, gpb, nq_real,
+                       ix->cur_mask, radius, ix->range_cnt, ix->range_s, ix->range_i, (unsigned int)ix->range_cap);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+template <int NQ>
+int launch_range_small_nq(css_index* ix, const float* qpad, int nq_real, float radius, int G, int64_t gpb, hipStream_t st) {
+    const bool ip = ix->metric == CSS_METRIC_IP;
+    if (ix->dpad == 768)
+        return ip ? launch_range_small_t<NQ, 12, CSS_METRIC_IP>(ix, qpad, nq_real, radius, G, gpb, st)
+                  : launch_range_small_t<NQ, 12, CSS_METRIC_L2>(ix, qpad, nq_real, radius, G, gpb, st);
+    return ip ? launch_range_small_t<NQ, 0, CSS_METRIC_IP>(ix, qpad, nq_real, radius, G, gpb, st)
+              : launch_range_small_t<NQ, 0, CSS_METRIC_L2>(ix, qpad, nq_real, radius, G, gpb, st);
+}
+
+// queries per sweep: the largest instantiated NQ (16, 8, 2) whose query rows fit 64 KiB of LDS (dim <= 8192: at least 2)
+int range_nq_sweep(const css_index* ix) {
+    const int64_t fit = (64 * 1024) / ((int64_t)ix->dpad * 4);
+    return fit >= 16 ? 16 : (fit >= 8 ? 8 : 2);
+}
+
+// One sweep of all rows for queries qpad[0 .. nqc) (nqc <= range_nq_sweep): counters zeroed, kernel, counters back on
+// the host (waits for the stream).
+int range_sweep(css_index* ix, const float* qpad, int nqc, float radius, unsigned int* cnt_host, hipStream_t st) {
+    const int64_t ngroups = (ix->ntotal + 3) / 4;
+    const int64_t G0 = std::max<int64_t>(1, std::min<int64_t>((int64_t)ix->num_cus * 8, (ngroups + 63) / 64));
+    const int64_t gpb = (ngroups + G0 - 1) / G0;
+    const int G = (int)((ngroups + gpb - 1) / gpb);
+    CSS_HIP_TRY(hipMemsetAsync(ix->range_cnt, 0, kRangeSlots * sizeof(unsigned int), st));
+    int rc;
+    if (nqc <= 1) rc = launch_range_small_nq<1>(ix, qpad, nqc, radius, G, gpb, st);
+    else if (nqc <= 2) rc = launch_range_small_nq<2>(ix, qpad, nqc, radius, G, gpb, st);
+    else if (nqc <= 8) rc = launch_range_small_nq<8>(ix, qpad, nqc, radius, G, gpb, st);
+    else rc = launch_range_small_nq<16>(ix, qpad, nqc, radius, G, gpb, st);
+    if (rc != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(cnt_host, ix->range_cnt, kRangeSlots * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    return CSS_OK;
+}
+
+// The hit pool with `cap` entries per slot (nothing of the old one is kept: a grown pool is filled by a new sweep).
+// No room: CSS_ERR_OOM, the pool is gone (the next call starts from the initial size) and the index is untouched.
+int range_pool_alloc(css_index* ix, size_t cap) {
+    if (ix->range_s) (void)hipFree(ix->range_s);
+    if (ix->range_i) (void)hipFree(ix->range_i);
+    ix->range_s = nullptr;
+    ix->range_i = nullptr;
+    ix->range_cap = 0;
+    if (hipMalloc((void**)&ix->range_s, kRangeSlots * cap * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&ix->range_i, kRangeSlots * cap * sizeof(uint32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (ix->range_s) (void)hipFree(ix->range_s);
+        ix->range_s = nullptr;
+        ix->range_i = nullptr;
+        return CSS_ERR_OOM;
+    }
+    ix->range_cap = cap;
+    return CSS_OK;
+}
+
 // RAII: the index narrowed to rows [row0, row0 + n) with `xh` as their bf16 shadow rows -- every launcher below reads
 // rows, norms, count, id base and the allow-bitmap through the css_index fields, so a row range is searched exactly
 // like an index of its own.  Caller holds ws_mu (export and css_index_ntotal do not look at these fields unguarded).
@@ -2841,7 +2922,7 @@ int css_index_free(css_index* ix) {
                     ix->part_s, ix->part_i, ix->out_i, ix->stage, ix->qh, ix->cthr, ix->cand_n,
                     ix->cflags, ix->cand_s, ix->cand_i, ix->cpace, ix->fs_state, ix->mask_ws, ix->excl_ws, ix->fix_s, ix->fix_i, ix->fix_lock,
                     ix->qh2, ix->thr2, ix->rs_work, ix->cand_n2, ix->cand_s2, ix->cand_i2, ix->flagB, ix->xh_tmp, ix->x8s_tmp, ix->rng_d, ix->rng_i,
-                    ix->compact_bits, ix->compact_pre};
+                    ix->compact_bits, ix->compact_pre, ix->range_cnt, ix->range_s, ix->range_i};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);  // (hipFree waits for the device: nothing enqueued by a _dev call still runs)
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -3351,6 +3432,186 @@ int css_merge_topk_packed_dev(const void* packed, int nparts, int64_t record_byt
     const float* Dp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed) + 8 * nq * k);
     return merge_parts(Dp, Ip, nparts, record_bytes / 4, record_bytes / 8, nq, k, metric, D, I, device, stream,
                        "css_merge_topk_packed_dev");
+}
+
+// ------------------------------------------------------------------ range search (variable-length results)
+struct css_range_result {
+    int64_t nq = 0;
+    std::vector<int64_t> lims;   // nq + 1
+    std::vector<float> D;
+    std::vector<int64_t> I;
+};
+
+namespace {
+// Queries already on the device (ix->q_raw).  Caller holds ws_mu and a shared lock on mu; everything runs on the
+// index's own stream and has finished when this returns.
+int range_search_locked(css_index* ix, int64_t nq, float radius, int normalize_q, css_range_result* res) {
+    hipStream_t st = ix->stream;
+    int rc;
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    if ((rc = grow(&ix->qpad, &ix->qpad_cap, (size_t)(nq + 256) * ix->dpad)) != CSS_OK) return rc;
+    if ((rc = grow(&ix->qnorm2, &ix->qnorm2_cap, (size_t)nq + 256)) != CSS_OK) return rc;
+    if (!ix->range_cnt) {
+        hipError_t e = hipMalloc((void**)&ix->range_cnt, kRangeSlots * sizeof(unsigned int));
+        if (e != hipSuccess) return css::hip_fail(e, "hipMalloc(range counters)", __FILE__, __LINE__);
+    }
+    if (ix->range_cap == 0 && range_pool_alloc(ix, kRangeInitialCap) != CSS_OK) {
+        css::set_error("css_index_range_search: no device memory for the initial hit pool");
+        return CSS_ERR_OOM;
+    }
+    // query prep: the row kernel of ingest (normalise, zero pad), as every search
+    hipLaunchKernelGGL(k_ingest_rows<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, ix->q_raw, ix->qpad, ix->qnorm2, nq,
+                       ix->dim, ix->dpad, normalize_q, 0ull, 0ll, (unsigned short*)nullptr, (int*)nullptr, (float*)nullptr,
+                       (unsigned char*)nullptr, (float*)nullptr);
+    CSS_LAUNCH_CHECK();
+    const int nq_sweep = range_nq_sweep(ix);
+    const bool ip = ix->metric == CSS_METRIC_IP;
+    std::vector<float> hs;
+    std::vector<uint32_t> hi;
+    std::vector<uint32_t> order;
+    unsigned int cnt[kRangeSlots];
+    for (int64_t q0 = 0; q0 < nq; q0 += nq_sweep) {
+        const int nqc = (int)std::min<int64_t>(nq_sweep, nq - q0);
+        const float* qp = ix->qpad + (size_t)q0 * ix->dpad;
+        if ((rc = range_sweep(ix, qp, nqc, radius, cnt, st)) != CSS_OK) return rc;
+        size_t most = 0, total = 0;
+        for (int j = 0; j < nqc; ++j) {
+            most = std::max<size_t>(most, cnt[j]);
+            total += cnt[j];
+        }
+        if (most > ix->range_cap) {
+            // the sweep counted every hit: grow to that size and sweep ONCE more (never a loop)
+            if (range_pool_alloc(ix, most) != CSS_OK) {
+                css::set_error("css_index_range_search: no device memory for the hit pool: %zu hits for one query "
+                               "(%zu for %d queries of the batch)", most, total, nqc);
+                return CSS_ERR_OOM;
+            }
+            if ((rc = range_sweep(ix, qp, nqc, radius, cnt, st)) != CSS_OK) return rc;
+            for (int j = 0; j < nqc; ++j)
+                if (cnt[j] > ix->range_cap) {   // (rows and mask cannot change under the locks held)
+                    css::set_error("css_index_range_search: internal: the second sweep counted more hits than the first");
+                    return CSS_ERR_STATE;
+                }
+            total = 0;
+            for (int j = 0; j < nqc; ++j) total += cnt[j];
+        }
+        try {
+            res->D.reserve(res->D.size() + total);
+            res->I.reserve(res->I.size() + total);
+            for (int j = 0; j < nqc; ++j) {
+                const size_t c = cnt[j];
+                hs.resize(c);
+                hi.resize(c);
+                order.resize(c);
+                if (c) {
+                    CSS_HIP_TRY(hipMemcpyAsync(hs.data(), ix->range_s + (size_t)j * ix->range_cap, c * sizeof(float), hipMemcpyDeviceToHost, st));
+                    CSS_HIP_TRY(hipMemcpyAsync(hi.data(), ix->range_i + (size_t)j * ix->range_cap, c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                    CSS_HIP_TRY(hipStreamSynchronize(st));
+                }
+                // the defined order, formed here on the host: best score first, equal scores by ascending id
+                for (size_t i = 0; i < c; ++i) order[i] = (uint32_t)i;
+                std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+                    if (hs[a] != hs[b]) return ip ? hs[a] > hs[b] : hs[a] < hs[b];
+                    return hi[a] < hi[b];
+                });
+                for (size_t i = 0; i < c; ++i) {
+                    res->D.push_back(hs[order[i]]);
+                    res->I.push_back(ix->id_base + (int64_t)hi[order[i]]);
+                }
+                res->lims[(size_t)(q0 + j + 1)] = (int64_t)res->D.size();
+            }
+        } catch (const std::bad_alloc&) {
+            css::set_error("css_index_range_search: no host memory for %zu hits of %d queries", total, nqc);
+            return CSS_ERR_OOM;
+        }
+    }
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_range_search(css_index* ix, const float* q_host, int64_t nq, float radius, int normalize_q,
+                           const uint32_t* allow_bits_host, css_range_result** out) {
+    CSS_REQUIRE(ix, "css_index_range_search: NULL index");
+    CSS_REQUIRE(out, "css_index_range_search: out is NULL");
+    *out = nullptr;
+    CSS_REQUIRE(nq >= 0 && nq < (1 << 24), "css_index_range_search: nq=%lld out of range", (long long)nq);
+    CSS_REQUIRE(!std::isnan(radius), "css_index_range_search: the radius is NaN");
+    CSS_REQUIRE(nq == 0 || q_host, "css_index_range_search: NULL buffer");
+    css_range_result* res = new (std::nothrow) css_range_result();
+    if (res) {
+        try {
+            res->lims.assign((size_t)nq + 1, 0);
+            res->nq = nq;
+        } catch (const std::bad_alloc&) {
+            delete res;
+            res = nullptr;
+        }
+    }
+    if (!res) {
+        css::set_error("css_index_range_search: no host memory for the result of %lld queries", (long long)nq);
+        return CSS_ERR_OOM;
+    }
+    int rc = CSS_OK;
+    {
+        std::shared_lock<std::shared_mutex> lk(ix->mu);
+        std::lock_guard<std::mutex> wl(ix->ws_mu);
+        if (nq > 0 && ix->ntotal > 0) {
+            DeviceGuard g(ix->device);
+            rc = [&]() -> int {
+                CSS_REQUIRE(ix->ntotal < 0xFFFFFFFFll, "css_index_range_search: %lld rows exceed the 32-bit row numbers of the hit pool",
+                            (long long)ix->ntotal);
+                int r;
+                // the previous search may still be running on another stream and owns the shared workspaces until its event
+                if (ix->ws_pending && ix->ws_stream != ix->stream) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ws_ev, 0));
+                if ((r = grow(&ix->q_raw, &ix->q_raw_cap, (size_t)nq * ix->dim)) != CSS_OK) return r;
+                const uint32_t* mask_dev = nullptr;
+                if (allow_bits_host) {
+                    const size_t words = (size_t)((ix->ntotal + 31) / 32);
+                    if ((r = grow(&ix->mask_ws, &ix->mask_ws_cap, words)) != CSS_OK) return r;
+                    CSS_HIP_TRY(hipMemcpyAsync(ix->mask_ws, allow_bits_host, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+                    mask_dev = ix->mask_ws;
+                }
+                CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw, q_host, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream));
+                MaskScope ms(ix, mask_dev);
+                r = range_search_locked(ix, nq, radius, normalize_q, res);
+                // (also after a failure: whatever was launched before the error still uses the workspaces)
+                if (hipEventRecord(ix->ws_ev, ix->stream) == hipSuccess) {
+                    ix->ws_stream = ix->stream;
+                    ix->ws_pending = true;
+                } else {
+                    (void)hipDeviceSynchronize();
+                    ix->ws_pending = false;
+                }
+                return r;
+            }();
+        }
+    }
+    if (rc != CSS_OK) {
+        delete res;
+        return rc;
+    }
+    *out = res;
+    return CSS_OK;
+}
+
+int css_range_result_lims(const css_range_result* r, int64_t* lims_host) {
+    CSS_REQUIRE(r && lims_host, "css_range_result_lims: NULL argument");
+    memcpy(lims_host, r->lims.data(), r->lims.size() * sizeof(int64_t));
+    return CSS_OK;
+}
+
+int css_range_result_read(const css_range_result* r, float* D_host, int64_t* I_host) {
+    CSS_REQUIRE(r, "css_range_result_read: NULL result");
+    if (r->D.empty()) return CSS_OK;
+    CSS_REQUIRE(D_host && I_host, "css_range_result_read: NULL buffer");
+    memcpy(D_host, r->D.data(), r->D.size() * sizeof(float));
+    memcpy(I_host, r->I.data(), r->I.size() * sizeof(int64_t));
+    return CSS_OK;
+}
+
+int css_range_result_free(css_range_result* r) {
+    delete r;
+    return CSS_OK;
 }
 
 }  // extern "C"

@@ -174,6 +174,34 @@ class IndexFlat:
                                                         D.ctypes.data, I.ctypes.data))
         return D, I
 
+    def range_search(self, q, thresh: float, normalize: bool = False, allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``faiss.IndexFlat.range_search``: ``(lims[nq+1] int64, D[total] float32, I[total] int64)``; query ``j``'s
+        hits are ``D/I[lims[j]:lims[j+1]]`` -- EVERY row with ``score > thresh`` (inner product) or squared distance
+        ``< thresh`` (L2), strict as in faiss.  Unlike faiss the order inside a query is defined: best score first,
+        equal scores by ascending id.  Scores come from an exact fp32 sweep of the fp32 rows (``css_index_range_search``);
+        ``allow`` restricts the answer as in ``search``."""
+        a = _as_f32_2d(q, self.d, "range_search")
+        nq = a.shape[0]
+        h = self._handle()
+        bits = None
+        if allow is not None:
+            bits = pack_allow_bits(allow, self.ntotal)
+        res = ctypes.c_void_p()
+        nat.check(nat.lib().css_index_range_search(h, a.ctypes.data if nq else None, nq, float(thresh),
+                                                   1 if normalize else 0,
+                                                   bits.ctypes.data if bits is not None else None, ctypes.byref(res)))
+        try:
+            lims = np.zeros(nq + 1, dtype=np.int64)
+            nat.check(nat.lib().css_range_result_lims(res, lims.ctypes.data))
+            total = int(lims[nq])
+            D = np.empty(total, dtype=np.float32)
+            I = np.empty(total, dtype=np.int64)
+            if total:
+                nat.check(nat.lib().css_range_result_read(res, D.ctypes.data, I.ctypes.data))
+        finally:
+            nat.lib().css_range_result_free(res)
+        return lims, D, I
+
     def search_dev(self, q_ptr: int, nq: int, k: int, D_ptr: int, I_ptr: int, stream: int = 0,
                    normalize: bool = False, allow_bits_ptr: int = 0) -> None:
         """Device-pointer twin: ``q_ptr``/``D_ptr``/``I_ptr`` are device addresses

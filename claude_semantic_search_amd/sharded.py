@@ -45,7 +45,7 @@ class ShardedFlatIndex:
     """``IndexFlat`` semantics over ``world`` row shards.
 
     ``local_index`` must offer ``ntotal``, ``add(x, normalize=)``, ``add_synthetic``, ``set_id_base`` and
-    ``search_dev``/``search``; ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
+    ``search_dev``/``search`` (``range_search`` for ``range_search``); ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
     implementations; tests substitute doubles.
     """
 
@@ -258,6 +258,68 @@ class ShardedFlatIndex:
         D, I = self.search_tensors(qt, k, normalize, allow=allow)
         return D.cpu().numpy(), I.cpu().numpy()
 
+    # -- range search ------------------------------------------------------------------------------------------
+    def _to_global_np(self, I: np.ndarray) -> np.ndarray:
+        """``_to_global`` for a host array of local row numbers (no -1 entries)."""
+        if len(self.segments) <= 1 or I.size == 0:
+            return I
+        l0 = np.array([s[0] for s in self.segments], dtype=np.int64)
+        g0 = np.array([s[1] for s in self.segments], dtype=np.int64)
+        seg = np.clip(np.searchsorted(l0, I, side="right") - 1, 0, None)
+        return I - l0[seg] + g0[seg]
+
+    def range_search(self, q, thresh: float, normalize: bool = False, allow=None):
+        """``IndexFlat.range_search`` over the shards: ``(lims, D, I)`` with global ids on every rank, each query's hits
+        best score first and equal scores by ascending id.  Every rank range-searches its shard (local allow-mask as in
+        ``search_tensors``); the variable-length lists then take two collective steps -- one all-gather of the
+        per-query counts, one of the payload (ids, scores) padded to the largest rank's size -- and every rank merges
+        per query.  With one rank there is no exchange.  Results live on the host, as the local call returns them."""
+        import torch
+
+        qa = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.d)
+        nq = qa.shape[0]
+        loc = self._local_allow(allow)
+        if loc is not None:
+            lims, D, I = self.local.range_search(qa, thresh, normalize=normalize, allow=loc)
+        else:
+            lims, D, I = self.local.range_search(qa, thresh, normalize=normalize)
+        lims = np.asarray(lims, dtype=np.int64)
+        D = np.asarray(D, dtype=np.float32)
+        I = self._to_global_np(np.asarray(I, dtype=np.int64))
+        if (self.world == 1 and not self.exchange_when_single) or nq == 0:   # (nq is the same on every rank)
+            return lims, D, I
+        gloo = self.dist.get_backend(self.group) == "gloo"
+        dev = "cpu" if gloo else f"cuda:{self.device_index or 0}"
+        # step 1: the per-query hit counts of every rank
+        counts = torch.from_numpy(np.diff(lims)).to(dev)
+        all_counts = torch.empty(self.world * nq, dtype=torch.int64, device=dev)
+        self.dist.all_gather_into_tensor(all_counts, counts, group=self.group)
+        all_counts = all_counts.cpu().numpy().reshape(self.world, nq)
+        totals = all_counts.sum(axis=1)
+        most = int(totals.max())
+        if most == 0:
+            return np.zeros(nq + 1, dtype=np.int64), np.empty(0, np.float32), np.empty(0, np.int64)
+        # step 2: the payload, every rank's record padded to the largest one: [most int64 ids][most float32 scores]
+        record = (12 * most + 15) // 16 * 16
+        send = np.zeros(record, dtype=np.uint8)
+        send[:8 * I.shape[0]] = I.view(np.uint8)
+        send[8 * most:8 * most + 4 * D.shape[0]] = D.view(np.uint8)
+        recv = torch.empty(self.world * record, dtype=torch.uint8, device=dev)
+        self.dist.all_gather_into_tensor(recv, torch.from_numpy(send).to(dev), group=self.group)
+        recv = recv.cpu().numpy().reshape(self.world, record)
+        ids, scores, qid = [], [], []
+        for r in range(self.world):
+            t = int(totals[r])
+            ids.append(recv[r, :8 * t].view(np.int64))
+            scores.append(recv[r, 8 * most:8 * most + 4 * t].view(np.float32))
+            qid.append(np.repeat(np.arange(nq, dtype=np.int64), all_counts[r]))
+        ids, scores, qid = np.concatenate(ids), np.concatenate(scores), np.concatenate(qid)
+        # per-query merge: query, then best score first (IP descending, L2 ascending), then ascending id
+        order = np.lexsort((ids, -scores if self.metric == 0 else scores, qid))
+        out_lims = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum(all_counts.sum(axis=0), out=out_lims[1:])
+        return out_lims, np.ascontiguousarray(scores[order]), np.ascontiguousarray(ids[order])
+
     # -- rows back out (index files, compaction) ---------------------------------------------------------------
     def reconstruct_n(self, row0: int, n: int) -> np.ndarray:
         """Rows ``[row0, row0 + n)`` in GLOBAL numbering on every rank (collective).  Each row lives on exactly one
@@ -321,6 +383,9 @@ class ShardedIndexFacade:
 
     def search(self, q, k: int, normalize: bool = False, allow=None):
         return self.sh.search(np.asarray(q, dtype=np.float32), int(k), normalize=normalize, allow=allow)
+
+    def range_search(self, q, thresh: float, normalize: bool = False, allow=None):
+        return self.sh.range_search(np.asarray(q, dtype=np.float32), float(thresh), normalize=normalize, allow=allow)
 
     def reconstruct_n(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
         return self.sh.reconstruct_n(int(row0), self.ntotal - int(row0) if n is None else int(n))

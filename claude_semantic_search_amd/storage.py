@@ -379,17 +379,75 @@ class HybridStorage:
                     continue
                 if filters and not self._matches_filters(data, filters):
                     continue
-                res = SearchResult(chunk_id=chunk_id, similarity=float(score))
-                meta = None
-                if cfg.include_metadata:
-                    meta = json.loads(data["metadata"]) if data["metadata"] else {}
-                    res.metadata = meta
-                if cfg.include_text:
-                    res.text = data["text"]
-                if cfg.include_metadata and cfg.include_text:
-                    res.chunk = Chunk(id=chunk_id, text=data["text"], metadata=dict(meta), embedding=None)
-                out.append(res)
+                out.append(self._make_result(chunk_id, score, data, cfg))
                 if len(out) >= cfg.top_k:
+                    break
+            return out
+
+    @staticmethod
+    def _make_result(chunk_id: str, score: float, data: Dict[str, Any], cfg: SearchConfig) -> SearchResult:
+        res = SearchResult(chunk_id=chunk_id, similarity=float(score))
+        meta = None
+        if cfg.include_metadata:
+            meta = json.loads(data["metadata"]) if data["metadata"] else {}
+            res.metadata = meta
+        if cfg.include_text:
+            res.text = data["text"]
+        if cfg.include_metadata and cfg.include_text:
+            res.chunk = Chunk(id=chunk_id, text=data["text"], metadata=dict(meta), embedding=None)
+        return res
+
+    def search_range(self, query_embedding, threshold: Optional[float] = None, filters: Optional[Dict[str, Any]] = None,
+                     config: Optional[SearchConfig] = None, limit: Optional[int] = None) -> List[SearchResult]:
+        """EVERY live chunk with ``similarity >= threshold`` (default ``config.similarity_threshold``) that matches
+        ``filters``, best first -- not capped by ``max_results`` / ``top_k`` as ``search()`` is, only by ``limit`` when
+        given.  An L2 storage (``normalize_embeddings=False``) reports squared distances, so there the meaning is
+        ``distance <= threshold``, nearest first.  The index call is strict (``IndexFlat.range_search``, faiss'
+        comparison): it is handed the neighbouring float32 of the threshold, which makes ``>=`` / ``<=`` exact.
+        Tombstones and filters go into the allow mask with ``filter_pushdown``, otherwise the hits are filtered
+        afterwards exactly as in ``search()``; both give the same list (no over-fetch is involved here)."""
+        cfg = config or SearchConfig()
+        thr = float(cfg.similarity_threshold if threshold is None else threshold)
+        if thr != thr:
+            raise ValueError("search_range: the threshold is NaN")
+        if not self.faiss_index or (limit is not None and limit <= 0):
+            return []
+        with self._lock:
+            ntotal = self.faiss_index.ntotal
+            if ntotal == 0:
+                return []
+            q = np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
+            with np.errstate(over="ignore"):
+                t32 = np.float32(thr)
+            if self.config.normalize_embeddings:
+                # score >= thr  <=>  score >= (smallest float32 >= thr)  <=>  score > the float32 below that one
+                if float(t32) < thr:
+                    t32 = np.nextafter(t32, np.float32(np.inf))
+                radius = np.nextafter(t32, np.float32(-np.inf))
+            else:
+                if float(t32) > thr:
+                    t32 = np.nextafter(t32, np.float32(-np.inf))
+                radius = np.nextafter(t32, np.float32(np.inf))
+            allow = None
+            if self.config.filter_pushdown and (filters or len(self.faiss_id_to_chunk_id) < ntotal):
+                allow = self._allow_mask(filters or {}, ntotal)
+            if allow is not None:
+                _, sims, ids = self.faiss_index.range_search(q, float(radius), normalize=self.config.normalize_embeddings,
+                                                             allow=allow)
+            else:
+                _, sims, ids = self.faiss_index.range_search(q, float(radius), normalize=self.config.normalize_embeddings)
+            out: List[SearchResult] = []
+            for score, fid in zip(sims.tolist(), ids.tolist()):
+                chunk_id = self.faiss_id_to_chunk_id.get(fid)
+                if not chunk_id:  # tombstone: row deleted from SQLite, vector still in the index
+                    continue
+                data = self._get_chunk_data(chunk_id)
+                if not data:
+                    continue
+                if filters and not self._matches_filters(data, filters):
+                    continue
+                out.append(self._make_result(chunk_id, score, data, cfg))
+                if limit is not None and len(out) >= limit:
                     break
             return out
 

@@ -12,6 +12,7 @@
  *   faiss_index.ntotal                       src/storage.py:358,421  -> css_index_ntotal
  *   q / (norm + 1e-8), reshape(1,-1)         src/storage.py:424-429  -> css_index_search(normalize_q=1)
  *   faiss_index.search(q, k) -> (D, I)       src/storage.py:436      -> css_index_search
+ *   faiss_index.range_search(q, r)           (not called by the reference) -> css_index_range_search
  *   faiss.write_index / read_index payload   src/storage.py:306,879  -> css_index_export / css_index_add
  *   faiss.index_cpu_to_gpu / get_num_gpus    src/storage.py:283, src/gpu_utils.py:117-118
  *                                                                    -> css_device_count / css_device_info
@@ -183,6 +184,33 @@ int css_index_search_masked(css_index* ix, const float* q_host, int64_t nq, int 
 int css_index_search_masked_dev(css_index* ix, const float* q_dev, int64_t nq, int k, int normalize_q,
                                 const uint32_t* allow_bits_dev, float* D_dev, int64_t* I_dev,
                                 void* stream);
+
+/* Range search (faiss IndexFlat::range_search): EVERY row with score > radius (inner product) / squared distance
+ * < radius (L2) -- strict, faiss' comparison -- as a variable-length hit list behind a handle.
+ *  - Query j's hits are D / I[lims[j] .. lims[j+1]), lims[0] = 0 (nq + 1 entries).  Ids are global (id_base added),
+ *    int64, never -1, never repeated inside a query.  nq = 0 and an empty index give lims of zeros.
+ *  - Order inside a query is defined (faiss leaves it open): best score first (IP descending, L2 ascending), equal
+ *    scores by ascending id.  The sort runs on the HOST side of the library, per query segment, after the copy back
+ *    (the device appends hits in whatever order its waves reach them).
+ *  - Scores are formed by an exact fp32 sweep of the fp32 rows (fmaf chains over the padded row, the arithmetic of
+ *    CSS_SEARCH_EXACT_FP32; L2 from differences, never negative).  The float compared with the radius is the float
+ *    returned.  Nothing depends on the reduced-precision row copies (css_index_set_shadow) or on the search mode.
+ *  - One sweep of the rows serves up to 16 queries; longer batches are walked 16 queries at a time (a correctness
+ *    path, not a fast one).  A sweep counts every hit even where its device pool is too small; the pool is then grown
+ *    to the counted size and the sweep repeated ONCE.
+ *  - normalize_q, allow_bits_host (may be NULL), rows appended by css_index_add_dev / css_index_add_synthetic on other
+ *    streams and the shared workspaces behave as for css_index_search_masked.  A NaN radius is CSS_ERR_INVALID.
+ *  - If the counted result cannot be allocated (device pool or host memory) the call returns CSS_ERR_OOM with the hit
+ *    count in the message; the index stays usable.  *out is NULL after every failure.
+ *  - The handle owns host memory only and is complete when the call returns: it is independent of the index (which may
+ *    be searched, changed or freed while the handle lives) and may be read from any thread.  css_range_result_lims
+ *    writes nq + 1 entries, css_range_result_read lims[nq] entries each; css_range_result_free(NULL) is allowed. */
+typedef struct css_range_result css_range_result;
+int css_index_range_search(css_index* ix, const float* q_host, int64_t nq, float radius, int normalize_q,
+                           const uint32_t* allow_bits_host, css_range_result** out);
+int css_range_result_lims(const css_range_result* r, int64_t* lims_host);
+int css_range_result_read(const css_range_result* r, float* D_host, int64_t* I_host);
+int css_range_result_free(css_range_result* r);
 
 /* Merge `nparts` per-shard results ([nparts, nq, k] each) into the global
  * top-k by (score, id); used after the RCCL all-gather of per-shard top-k. */
