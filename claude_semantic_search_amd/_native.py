@@ -101,6 +101,9 @@ PROTOTYPES = {
     "css_index_search_masked": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "css_index_search_masked_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                             c_void_p]),
+    "css_index_search_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "css_index_search_rows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
     "css_index_range_search": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p, POINTER(c_void_p)]),
     "css_range_result_lims": (c_int, [c_void_p, c_void_p]),
     "css_range_result_read": (c_int, [c_void_p, c_void_p, c_void_p]),

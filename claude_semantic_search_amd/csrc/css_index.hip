@@ -28,6 +28,8 @@
 //   k_merge_final      per query: merge the per-block lists into the final top-k.
 //   k_range_small      css_index_range_search: the exact fp32 sweep with a radius test and a variable-length
 //                      hit list instead of top-k lists (css_knn_range.h).   HBM bound
+//   k_gather_queries,  css_index_search_rows: stored rows copied into a query buffer in front of the ordinary
+//   k_drop_self        search for k + 1, and the anchor compacted out of its results behind it (a wave per query)
 #include "css_common.h"
 #include "css_knn_kernels.h"
 #include "../../include/css_synth.h"
@@ -126,6 +128,14 @@ struct css_index {
     // range_cap entries (score + row) per slot; grown to the counted size when a sweep overflowed it
     unsigned int* range_cnt = nullptr;
     float* range_s = nullptr; uint32_t* range_i = nullptr; size_t range_cap = 0;
+    // css_index_search_rows: the gathered query rows [nq, dim] (not q_raw: the host search copies into that before it
+    // has waited for ws_ev), one invalid-id flag per query, the search's own [nq, k + 1] results in front of
+    // k_drop_self, and the device copy of a host id list
+    float* rowq = nullptr;    size_t rowq_cap = 0;      // floats
+    int* rowq_flag = nullptr; size_t rowq_flag_cap = 0;
+    float* rowq_d = nullptr;  size_t rowq_d_cap = 0;    // entries
+    int64_t* rowq_i = nullptr; size_t rowq_i_cap = 0;
+    int64_t* rowq_ids = nullptr; size_t rowq_ids_cap = 0;
     // rows written by css_index_add_dev / _add_synthetic on the CALLER's stream: searches, reallocation and
     // export wait for this event before touching rows, norms or maxn2
     hipEvent_t ingest_ev = nullptr;
@@ -617,6 +627,66 @@ __global__ void k_fill_pad(float* __restrict__ D, int64_t* __restrict__ I, int64
     if (i < n) {
         D[i] = pad;
         I[i] = -1;
+    }
+}
+
+// ---- css_index_search_rows: stored rows as queries.  Two bandwidth-trivial launches around the ordinary search.
+// One wave per anchor: the fp32 row of global id ids[j] -> raw query row j ([nq, dim], what css_index_search_dev
+// takes), 16 bytes per lane where the rows allow it.  An id outside [id_base, id_base + ntotal) reads nothing: its
+// query is a zero row and flag[j] = 1 (k_drop_self pads that result row).
+__global__ __launch_bounds__(256) void k_gather_queries(const float* __restrict__ xb, const int64_t* __restrict__ ids,
+                                                        float* __restrict__ q, int* __restrict__ flag, int64_t nq,
+                                                        int64_t ntotal, int64_t id_base, int dim, int dpad) {
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (j >= nq) return;
+    const uint64_t r = (uint64_t)ids[j] - (uint64_t)id_base;   // (unsigned: an id below id_base wraps beyond ntotal)
+    const bool ok = r < (uint64_t)ntotal;
+    if (lane == 0) flag[j] = ok ? 0 : 1;
+    const float* src = xb + (ok ? (size_t)r * dpad : 0);
+    float* dst = q + (size_t)j * dim;
+    if ((dim & 3) == 0) {   // (rows of q then start on 16-byte boundaries like those of xb)
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int c = lane; c < dim / 4; c += 64)
+            reinterpret_cast<float4*>(dst)[c] = ok ? reinterpret_cast<const float4*>(src)[c] : zero;
+    } else {
+        for (int c = lane; c < dim; c += 64) dst[c] = ok ? src[c] : 0.f;
+    }
+}
+
+// One wave per query: stable compaction of its kk = k + (exclude ? 1 : 0) sorted results to k.  exclude: the entry
+// whose id is the anchor's goes if it is there, otherwise the last one does (ids are unique inside a row, so at most
+// one entry goes and k always remain; the pads of a short row travel along).  A flagged query is padded entirely.
+__global__ __launch_bounds__(256) void k_drop_self(const float* __restrict__ Ds, const int64_t* __restrict__ Is,
+                                                   const int64_t* __restrict__ ids, const int* __restrict__ flag,
+                                                   int64_t nq, int kk, int k, int exclude, float pad,
+                                                   float* __restrict__ D, int64_t* __restrict__ I) {
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (j >= nq) return;
+    float* Dj = D + (size_t)j * k;
+    int64_t* Ij = I + (size_t)j * k;
+    int kept = 0;
+    if (!flag[j]) {
+        const int64_t anchor = ids[j];
+        for (int c0 = 0; c0 < kk; c0 += 64) {
+            const int c = c0 + lane;
+            const bool in = c < kk;
+            const int64_t id = in ? Is[(size_t)j * kk + c] : -1;
+            const float s = in ? Ds[(size_t)j * kk + c] : pad;
+            const bool keep = in && !(exclude && id == anchor);
+            const unsigned long long b = __ballot(keep);
+            const int pos = kept + __popcll(b & ((1ull << lane) - 1ull));
+            if (keep && pos < k) {
+                Dj[pos] = s;
+                Ij[pos] = id;
+            }
+            kept += __popcll(b);
+        }
+    }
+    for (int c = kept + lane; c < k; c += 64) {
+        Dj[c] = pad;
+        Ij[c] = -1;
     }
 }
 
@@ -2922,7 +2992,8 @@ int css_index_free(css_index* ix) {
                     ix->part_s, ix->part_i, ix->out_i, ix->stage, ix->qh, ix->cthr, ix->cand_n,
                     ix->cflags, ix->cand_s, ix->cand_i, ix->cpace, ix->fs_state, ix->mask_ws, ix->excl_ws, ix->fix_s, ix->fix_i, ix->fix_lock,
                     ix->qh2, ix->thr2, ix->rs_work, ix->cand_n2, ix->cand_s2, ix->cand_i2, ix->flagB, ix->xh_tmp, ix->x8s_tmp, ix->rng_d, ix->rng_i,
-                    ix->compact_bits, ix->compact_pre, ix->range_cnt, ix->range_s, ix->range_i};
+                    ix->compact_bits, ix->compact_pre, ix->range_cnt, ix->range_s, ix->range_i,
+                    ix->rowq, ix->rowq_flag, ix->rowq_d, ix->rowq_i, ix->rowq_ids};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);  // (hipFree waits for the device: nothing enqueued by a _dev call still runs)
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -3416,6 +3487,110 @@ int css_index_search(css_index* ix, const float* q_host, int64_t nq, int k, int 
     return css_index_search_masked(ix, q_host, nq, k, normalize_q, nullptr, D_host, I_host);
 }
 
+
+namespace {
+// The anchors' rows gathered as queries, the ordinary search (search_any_k: every mode, shadow policy, k and chunking
+// as css_index_search_masked_dev has them) at k + 1 when the anchor is to go, and the compaction to k.  The gather
+// reads the real rows before any search narrows the handle to a row range.  Everything is enqueued on `st`.  Caller
+// holds ws_mu and a shared lock on mu.
+int search_rows_enqueue(css_index* ix, const int64_t* ids_dev, int64_t nq, int k, int exclude_self,
+                        const uint32_t* allow_dev, float* D_dev, int64_t* I_dev, hipStream_t st) {
+    const int kk = k + (exclude_self ? 1 : 0);
+    int rc;
+    // the previous search may still own the shared workspaces; rows appended on another stream must have landed
+    if (ix->ws_pending && ix->ws_stream != st) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ws_ev, 0));
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    if ((rc = grow(&ix->rowq, &ix->rowq_cap, (size_t)nq * ix->dim)) != CSS_OK) return rc;
+    if ((rc = grow(&ix->rowq_flag, &ix->rowq_flag_cap, (size_t)nq)) != CSS_OK) return rc;
+    if ((rc = grow(&ix->rowq_d, &ix->rowq_d_cap, (size_t)nq * kk)) != CSS_OK) return rc;
+    if ((rc = grow(&ix->rowq_i, &ix->rowq_i_cap, (size_t)nq * kk)) != CSS_OK) return rc;
+    const dim3 grid((unsigned)((nq + 3) / 4));
+    hipLaunchKernelGGL(k_gather_queries, grid, dim3(256), 0, st, (const float*)ix->xb, ids_dev, ix->rowq, ix->rowq_flag, nq,
+                       ix->ntotal, ix->id_base, ix->dim, ix->dpad);
+    CSS_LAUNCH_CHECK();
+    rc = search_any_k(ix, ix->rowq, nq, kk, 0, allow_dev, ix->rowq_d, ix->rowq_i, st);
+    if (rc == CSS_OK) {
+        hipLaunchKernelGGL(k_drop_self, grid, dim3(256), 0, st, (const float*)ix->rowq_d, (const int64_t*)ix->rowq_i, ids_dev,
+                           (const int*)ix->rowq_flag, nq, kk, k, exclude_self ? 1 : 0,
+                           ix->metric == CSS_METRIC_IP ? -FLT_MAX : FLT_MAX, D_dev, I_dev);
+        CSS_LAUNCH_CHECK();
+    }
+    // (also after a failed search: whatever was launched still uses the gathered rows)
+    if (hipEventRecord(ix->ws_ev, st) == hipSuccess) {
+        ix->ws_stream = st;
+        ix->ws_pending = true;
+    } else {
+        (void)hipDeviceSynchronize();
+        ix->ws_pending = false;
+    }
+    return rc;
+}
+
+int check_search_rows_k(int k, int exclude_self) {
+    const int kmax = exclude_self ? CSS_MAX_K - 1 : CSS_MAX_K;
+    CSS_REQUIRE(k >= 1 && k <= kmax, "css_index_search_rows: k=%d outside [1, %d]%s", k, kmax,
+                exclude_self ? " (exclude_self searches for k + 1)" : "");
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_search_rows_dev(css_index* ix, const int64_t* ids_dev, int64_t nq, int k, int exclude_self,
+                              const uint32_t* allow_bits_dev, float* D_dev, int64_t* I_dev, void* stream) {
+    CSS_REQUIRE(ix, "css_index_search_rows_dev: NULL index");
+    CSS_REQUIRE(nq >= 0 && nq < (1 << 24), "css_index_search_rows_dev: nq=%lld out of range", (long long)nq);
+    int rc;
+    if ((rc = check_search_rows_k(k, exclude_self)) != CSS_OK) return rc;
+    if (nq == 0) return CSS_OK;
+    CSS_REQUIRE(ids_dev && D_dev && I_dev, "css_index_search_rows_dev: NULL buffer");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    DeviceGuard g(ix->device);
+    return search_rows_enqueue(ix, ids_dev, nq, k, exclude_self, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
+}
+
+int css_index_search_rows(css_index* ix, const int64_t* ids_host, int64_t nq, int k, int exclude_self,
+                          const uint32_t* allow_bits_host, float* D_host, int64_t* I_host) {
+    CSS_REQUIRE(ix, "css_index_search_rows: NULL index");
+    CSS_REQUIRE(nq >= 0 && nq < (1 << 24), "css_index_search_rows: nq=%lld out of range", (long long)nq);
+    int rc;
+    if ((rc = check_search_rows_k(k, exclude_self)) != CSS_OK) return rc;
+    if (nq == 0) return CSS_OK;
+    CSS_REQUIRE(ids_host && D_host && I_host, "css_index_search_rows: NULL buffer");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    for (int64_t j = 0; j < nq; ++j)
+        CSS_REQUIRE(ids_host[j] >= ix->id_base && ids_host[j] - ix->id_base < ix->ntotal,
+                    "css_index_search_rows: id %lld (query %lld) outside [%lld, %lld)", (long long)ids_host[j], (long long)j,
+                    (long long)ix->id_base, (long long)(ix->id_base + ix->ntotal));
+    DeviceGuard g(ix->device);
+    if ((rc = grow(&ix->rowq_ids, &ix->rowq_ids_cap, (size_t)nq)) != CSS_OK) return rc;
+    const size_t need = (size_t)nq * k;
+    if (need > ix->out_cap) {
+        if (ix->out_i) CSS_HIP_TRY(hipFree(ix->out_i));
+        ix->out_i = nullptr;
+        ix->out_cap = 0;
+        CSS_HIP_TRY(hipMalloc((void**)&ix->out_i, need * (sizeof(int64_t) + sizeof(float))));
+        ix->out_cap = need;
+    }
+    const uint32_t* mask_dev = nullptr;
+    if (allow_bits_host) {   // (ntotal > 0: an id passed the range check)
+        const size_t words = (size_t)((ix->ntotal + 31) / 32);
+        if ((rc = grow(&ix->mask_ws, &ix->mask_ws_cap, words)) != CSS_OK) return rc;
+        CSS_HIP_TRY(hipMemcpyAsync(ix->mask_ws, allow_bits_host, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+        mask_dev = ix->mask_ws;
+    }
+    CSS_HIP_TRY(hipMemcpyAsync(ix->rowq_ids, ids_host, (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream));
+    float* const d_out = reinterpret_cast<float*>(ix->out_i + need);   // (layout of css_index_search_masked: ids, then scores)
+    rc = search_rows_enqueue(ix, ix->rowq_ids, nq, k, exclude_self, mask_dev, d_out, ix->out_i, ix->stream);
+    if (rc != CSS_OK) {
+        (void)hipStreamSynchronize(ix->stream);   // (the copies above read the caller's memory)
+        return rc;
+    }
+    CSS_HIP_TRY(hipMemcpyAsync(D_host, d_out, need * 4, hipMemcpyDeviceToHost, ix->stream));
+    CSS_HIP_TRY(hipMemcpyAsync(I_host, ix->out_i, need * 8, hipMemcpyDeviceToHost, ix->stream));
+    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    return CSS_OK;
+}
 
 int css_merge_topk_dev(const float* Dp, const int64_t* Ip, int nparts, int64_t nq, int k, int metric, float* D,
                        int64_t* I, int device, void* stream) {

@@ -71,6 +71,31 @@ def keep_mask_from_ids(ids, ntotal: int) -> np.ndarray:
     return keep
 
 
+def ids_as_int64(ids, what: str = "search_by_ids") -> np.ndarray:
+    """Array-like of integer row ids -> contiguous 1-D int64 array; anything else (floats, booleans, strings, ids
+    beyond int64) raises ``ValueError``."""
+    a = np.asarray(ids)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{what}: ids must be integers, got dtype {a.dtype}")
+    a = a.reshape(-1)
+    if a.dtype == np.uint64 and bool((a > np.uint64(np.iinfo(np.int64).max)).any()):
+        raise ValueError(f"{what}: id beyond int64")
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def drop_self(D: np.ndarray, I: np.ndarray, ids: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """Host statement of the library's ``k_drop_self``: ``[nq, k + 1]`` sorted results -> ``[nq, k]`` without the
+    anchor ``ids[j]`` of row ``j`` -- its entry goes where it is present, the last entry otherwise; order is kept.
+    (The sharded index drops the anchor here, after the merge of the shards' lists.)"""
+    nq, kk = I.shape
+    gone = I == np.asarray(ids, dtype=np.int64).reshape(-1, 1)
+    pos = np.where(gone.any(axis=1), gone.argmax(axis=1), kk - 1)
+    keep = np.arange(kk)[None, :] != pos[:, None]
+    return (np.ascontiguousarray(D[keep].reshape(nq, kk - 1)), np.ascontiguousarray(I[keep].reshape(nq, kk - 1)))
+
+
 class IndexFlat:
     """Exact brute-force index in HBM (``faiss.IndexFlat`` semantics)."""
 
@@ -212,6 +237,41 @@ class IndexFlat:
                                                         ctypes.c_void_p(allow_bits_ptr) if allow_bits_ptr else None,
                                                         ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr),
                                                         ctypes.c_void_p(stream)))
+
+    def search_by_ids(self, ids, k: int, exclude_self: bool = True, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Related rows: query ``j`` is the STORED row of global id ``ids[j]`` (``id_base`` included), taken as it lies
+        in HBM -- nothing is exported or uploaded, no normalisation is applied; repeated ids are fine.  Returns
+        ``(D[nq,k], I[nq,k])`` in the layout of ``search``.  ``exclude_self=True``: ``ids[j]`` never appears in row
+        ``j`` and the row is the exact top-k of the allowed rows without the anchor (copies of the anchor under other
+        ids are ordinary results; the anchor need not be allowed itself); ``k <= MAX_K - 1``.  ``exclude_self=False``:
+        what ``search(rows, k)`` returns.  An id outside the index raises (``css_index_search_rows``)."""
+        a = ids_as_int64(ids)
+        k = int(k)
+        kmax = nat.MAX_K - 1 if exclude_self else nat.MAX_K
+        if k < 1 or k > kmax:
+            raise ValueError(f"k={k} outside [1, {kmax}]")
+        nq = a.shape[0]
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        bits = None
+        if allow is not None:
+            bits = pack_allow_bits(allow, self.ntotal)
+        if nq:
+            nat.check(nat.lib().css_index_search_rows(self._handle(), a.ctypes.data, nq, k, 1 if exclude_self else 0,
+                                                      bits.ctypes.data if bits is not None else None,
+                                                      D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    def search_by_ids_dev(self, ids_ptr: int, nq: int, k: int, D_ptr: int, I_ptr: int, stream: int = 0,
+                          exclude_self: bool = True, allow_bits_ptr: int = 0) -> None:
+        """Device-pointer twin of ``search_by_ids``: ``ids_ptr`` = device address of ``nq`` int64 ids, enqueued on
+        ``stream``.  The ids cannot be checked without a wait: a query whose id is outside the index gets a fully
+        padded row, the other queries are unaffected."""
+        nat.check(nat.lib().css_index_search_rows_dev(self._handle(), ctypes.c_void_p(ids_ptr), int(nq), int(k),
+                                                      1 if exclude_self else 0,
+                                                      ctypes.c_void_p(allow_bits_ptr) if allow_bits_ptr else None,
+                                                      ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr),
+                                                      ctypes.c_void_p(stream)))
 
     def set_search_mode(self, mode: str) -> None:
         """``"auto"`` (default: bf16 candidate scan + exact fp32 rescoring where the index keeps shadow

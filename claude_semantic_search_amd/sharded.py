@@ -45,7 +45,7 @@ class ShardedFlatIndex:
     """``IndexFlat`` semantics over ``world`` row shards.
 
     ``local_index`` must offer ``ntotal``, ``add(x, normalize=)``, ``add_synthetic``, ``set_id_base`` and
-    ``search_dev``/``search`` (``range_search`` for ``range_search``); ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
+    ``search_dev``/``search`` (``range_search`` for ``range_search``, ``reconstruct_n`` for ``search_by_ids``); ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
     implementations; tests substitute doubles.
     """
 
@@ -320,6 +320,42 @@ class ShardedFlatIndex:
         np.cumsum(all_counts.sum(axis=0), out=out_lims[1:])
         return out_lims, np.ascontiguousarray(scores[order]), np.ascontiguousarray(ids[order])
 
+    # -- related rows ----------------------------------------------------------------------------------------------
+    def search_by_ids(self, ids, k: int, exclude_self: bool = True, allow=None):
+        """``IndexFlat.search_by_ids`` over the shards (collective: every rank passes the same arguments): ``ids`` are
+        GLOBAL row ids.  The rank that owns an anchor supplies its stored row, every other rank zeros, and ONE sum
+        all-reduce of the ``[nq, d]`` buffer hands every rank every query (exact: one non-zero contribution per row).
+        Then the usual search runs for ``k + 1`` -- local masked search, one all-gather, merge -- and the anchor's
+        global id is dropped after the merge (copies of the anchor on any shard stay).  An id outside
+        ``[0, ntotal_global)`` raises ``ValueError`` on every rank, before any collective."""
+        import torch
+
+        from .flat_index import MAX_K, drop_self, ids_as_int64
+
+        a = ids_as_int64(ids)
+        k = int(k)
+        kmax = MAX_K - 1 if exclude_self else MAX_K
+        if k < 1 or k > kmax:
+            raise ValueError(f"k={k} outside [1, {kmax}]")
+        bad = a[(a < 0) | (a >= self.ntotal_global)]
+        if bad.size:
+            raise ValueError(f"search_by_ids: id {int(bad[0])} outside [0, {self.ntotal_global})")
+        nq = a.shape[0]
+        if nq == 0:
+            return np.empty((0, k), dtype=np.float32), np.empty((0, k), dtype=np.int64)
+        rows = np.zeros((nq, self.d), dtype=np.float32)
+        for l0, g0, m in self.segments:
+            for j in np.flatnonzero((a >= g0) & (a < g0 + m)):
+                rows[j] = self.local.reconstruct_n(l0 + int(a[j]) - g0, 1)[0]
+        if self.world > 1:
+            t = torch.from_numpy(rows)
+            if self.dist.get_backend(self.group) != "gloo":
+                t = t.to(f"cuda:{self.device_index or 0}")
+            self.dist.all_reduce(t, group=self.group)
+            rows = t.cpu().numpy()
+        D, I = self.search(rows, k + 1 if exclude_self else k, normalize=False, allow=allow)
+        return drop_self(D, I, a) if exclude_self else (D, I)
+
     # -- rows back out (index files, compaction) ---------------------------------------------------------------
     def reconstruct_n(self, row0: int, n: int) -> np.ndarray:
         """Rows ``[row0, row0 + n)`` in GLOBAL numbering on every rank (collective).  Each row lives on exactly one
@@ -386,6 +422,9 @@ class ShardedIndexFacade:
 
     def range_search(self, q, thresh: float, normalize: bool = False, allow=None):
         return self.sh.range_search(np.asarray(q, dtype=np.float32), float(thresh), normalize=normalize, allow=allow)
+
+    def search_by_ids(self, ids, k: int, exclude_self: bool = True, allow=None):
+        return self.sh.search_by_ids(ids, int(k), exclude_self=exclude_self, allow=allow)
 
     def reconstruct_n(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
         return self.sh.reconstruct_n(int(row0), self.ntotal - int(row0) if n is None else int(n))

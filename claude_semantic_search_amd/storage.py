@@ -367,22 +367,77 @@ class HybridStorage:
                 sims, ids = self.faiss_index.search(q, k, normalize=self.config.normalize_embeddings, allow=allow)
             else:
                 sims, ids = self.faiss_index.search(q, k, normalize=self.config.normalize_embeddings)
-            out: List[SearchResult] = []
-            for score, fid in zip(sims[0].tolist(), ids[0].tolist()):
-                if score < cfg.similarity_threshold:
-                    continue
-                chunk_id = self.faiss_id_to_chunk_id.get(fid)
-                if not chunk_id:  # tombstone: row deleted from SQLite, vector still in the index
-                    continue
-                data = self._get_chunk_data(chunk_id)
-                if not data:
-                    continue
-                if filters and not self._matches_filters(data, filters):
-                    continue
-                out.append(self._make_result(chunk_id, score, data, cfg))
-                if len(out) >= cfg.top_k:
-                    break
-            return out
+            return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
+
+    _NO_SESSION = object()   # _results_in_rank_order: no session is left out
+
+    def _results_in_rank_order(self, sims, ids, cfg: SearchConfig, filters: Optional[Dict[str, Any]],
+                               skip_session: Any = _NO_SESSION) -> List[SearchResult]:
+        """The hits of one query, best first, through the reference's post-processing (``src/storage.py:438-492``):
+        threshold, tombstone skip, SQLite row, filters, stop at ``top_k``.  ``skip_session``: chunks of that session
+        are left out as well (``search_related``)."""
+        out: List[SearchResult] = []
+        for score, fid in zip(sims, ids):
+            if score < cfg.similarity_threshold:
+                continue
+            chunk_id = self.faiss_id_to_chunk_id.get(fid)
+            if not chunk_id:  # tombstone: row deleted from SQLite, vector still in the index
+                continue
+            data = self._get_chunk_data(chunk_id)
+            if not data:
+                continue
+            if filters and not self._matches_filters(data, filters):
+                continue
+            if skip_session is not self._NO_SESSION and data["session_id"] == skip_session:
+                continue
+            out.append(self._make_result(chunk_id, score, data, cfg))
+            if len(out) >= cfg.top_k:
+                break
+        return out
+
+    def search_related(self, chunk_id: str, config: Optional[SearchConfig] = None,
+                       filters: Optional[Dict[str, Any]] = None, same_session: bool = False) -> List[SearchResult]:
+        """Chunks related to a stored chunk -- what the reference's ``related_to`` / ``--related-to`` offers and never
+        does (its ``filters["related_to"]`` names no column, so ``_matches_filters`` ignores it; the key stays ignored
+        inside ``filters`` here too).  The anchor's STORED row is the query, read where it lies in HBM
+        (``IndexFlat.search_by_ids``), and the anchor is never returned.  No second normalisation is applied:
+        ``search()`` re-applies ``x / (||x|| + 1e-8)`` to its query, so its scores for the same vector can differ from
+        these in the last bits.
+        ``same_session=False`` (the reference's default for its ``same_session`` flag) also leaves out every chunk
+        whose ``session_id`` equals the anchor's (an anchor without a session has no session mates);
+        ``same_session=True`` leaves out the anchor only.  Threshold, tombstones, ``filters``, ``top_k`` and
+        ``max_results`` mean what they mean in ``search()``: without ``filter_pushdown`` the best
+        ``min(max_results, ntotal - 1, MAX_K - 1)`` rows are fetched and filtered in rank order; with it, filters,
+        tombstones and the session rule form the allow mask and ``top_k`` rows are fetched.
+        An unknown or deleted ``chunk_id`` raises ``KeyError``; an empty index and one holding only the anchor give ``[]``."""
+        cfg = config or SearchConfig()
+        if not self.faiss_index:
+            return []
+        with self._lock:
+            ntotal = self.faiss_index.ntotal
+            if ntotal == 0:
+                return []
+            fid = self.chunk_id_to_faiss_id.get(chunk_id)
+            data = self._get_chunk_data(chunk_id) if fid is not None and fid < ntotal else None
+            if not data:
+                raise KeyError(chunk_id)
+            k = min(cfg.max_results, ntotal - 1, fi.MAX_K - 1)
+            if k <= 0:
+                return []
+            session = data["session_id"]
+            skip = self._NO_SESSION if same_session or session is None else session
+            allow = None
+            if self.config.filter_pushdown:
+                allow = self._allow_mask(filters or {}, ntotal)
+                if skip is not self._NO_SESSION:
+                    allow = allow.copy()   # (the cached mask stays as it is)
+                    mates = self.db.cursor().execute("SELECT faiss_id FROM chunks WHERE session_id = ? AND faiss_id IS NOT NULL",
+                                                     (session,)).fetchall()
+                    mates = np.array([r[0] for r in mates], dtype=np.int64)
+                    allow[mates[mates < ntotal]] = False
+                k = max(1, min(k, cfg.top_k))
+            sims, ids = self.faiss_index.search_by_ids([fid], k, exclude_self=True, allow=allow)
+            return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters, skip)
 
     @staticmethod
     def _make_result(chunk_id: str, score: float, data: Dict[str, Any], cfg: SearchConfig) -> SearchResult:

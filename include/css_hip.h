@@ -185,6 +185,30 @@ int css_index_search_masked_dev(css_index* ix, const float* q_dev, int64_t nq, i
                                 const uint32_t* allow_bits_dev, float* D_dev, int64_t* I_dev,
                                 void* stream);
 
+/* Search by id ("related rows"; what faiss users write as search-by-id-excluding-self): query j is the stored fp32 row
+ * whose GLOBAL id is ids[j] (id_base included), exactly as it lies in HBM.
+ *  - No query normalisation is applied; repeated ids are allowed.  The result has the layout and order of
+ *    css_index_search_masked (D[nq,k], I[nq,k], IP descending / L2 ascending squared distance, ties to the lower id,
+ *    -1 with -FLT_MAX / +FLT_MAX padding), and allow_bits (may be NULL) means what it means there.
+ *  - exclude_self != 0: id ids[j] never appears in row j, and the row is the exact top-k of (allowed rows minus the
+ *    anchor).  Exact duplicates of the anchor stored under other ids are ordinary results; the anchor itself need not be
+ *    allowed by allow_bits.  The search runs for k + 1, so 1 <= k <= CSS_MAX_K - 1 (k == CSS_MAX_K: CSS_ERR_INVALID).
+ *  - exclude_self == 0: the result of css_index_search_masked with those rows as queries; 1 <= k <= CSS_MAX_K.
+ *  - Three steps on the device: one wave per anchor gathers its row into a query buffer, the search of
+ *    css_index_search_masked_dev runs unchanged on that buffer (search mode, reduced-precision copies, k > 128 passes
+ *    and query chunking as there), one wave per query then drops the anchor -- or, where the anchor is not among the
+ *    k + 1 (masked out, or an inner-product row that is not its own best match), the last entry.
+ *  - Host form: an id outside [id_base, id_base + ntotal) is CSS_ERR_INVALID, the message names the id, and nothing is
+ *    enqueued (so every call on an empty index with nq > 0 fails).  Device form: the ids cannot be looked at without
+ *    a wait, so a query with an invalid id returns a fully padded row, its neighbours are unaffected (an empty index:
+ *    every row padded), and the call waits for the device no more than css_index_search_masked_dev does.
+ *  - nq == 0 is a no-op.  Rows appended on other streams, the serialisation of the searches of one index and the
+ *    shared workspaces are those of css_index_search_masked_dev. */
+int css_index_search_rows(css_index* ix, const int64_t* ids_host, int64_t nq, int k, int exclude_self,
+                          const uint32_t* allow_bits_host, float* D_host, int64_t* I_host);
+int css_index_search_rows_dev(css_index* ix, const int64_t* ids_dev, int64_t nq, int k, int exclude_self,
+                              const uint32_t* allow_bits_dev, float* D_dev, int64_t* I_dev, void* stream);
+
 /* Range search (faiss IndexFlat::range_search): EVERY row with score > radius (inner product) / squared distance
  * < radius (L2) -- strict, faiss' comparison -- as a variable-length hit list behind a handle.
  *  - Query j's hits are D / I[lims[j] .. lims[j+1]), lims[0] = 0 (nq + 1 entries).  Ids are global (id_base added),
