@@ -30,7 +30,14 @@
 //                      hit list instead of top-k lists (css_knn_range.h).   HBM bound
 //   k_gather_queries,  css_index_search_rows: stored rows copied into a query buffer in front of the ordinary
 //   k_drop_self        search for k + 1, and the anchor compacted out of its results behind it (a wave per query)
+//
+// Host plumbing, one place per rule: every workspace is a DevBuf (css_devbuf.h: owning, freed with the index, one of
+// three growth policies); WsTurn is a search's turn at the shared workspaces (wait for the previous stream's event,
+// record at the end); prep_queries, upload_allow_bits, reserve_out / fetch_out are the query preparation, the mask
+// upload and the result staging of every entry point; sweep_grid is the grid of both exact sweeps.  The sweep body of
+// k_scan_small and k_range_small is deliberately NOT shared (css_knn_range.h says why).
 #include "css_common.h"
+#include "css_devbuf.h"
 #include "css_knn_kernels.h"
 #include "../../include/css_synth.h"
 
@@ -61,22 +68,22 @@ struct css_index {
     int shadow_policy = -1;        // css_index_set_shadow: -1 automatic, 0 never, 1 always
     int search_mode = CSS_SEARCH_AUTO;
     const uint32_t* cur_mask = nullptr;  // allow-bitmap of the search in progress (set under ws_mu)
-    uint32_t* mask_ws = nullptr;   size_t mask_ws_cap = 0;   // device copy of a host bitmap
-    uint32_t* excl_ws = nullptr;   size_t excl_ws_cap = 0;   // k > 128: allow-bitmap minus the rows earlier passes returned
-    int* maxn2 = nullptr;          // device, 3 words: bits of max ||row||^2, max ||row - bf16(row)||^2, max ||row - int8(row)||^2 (cz_eps)
+    DevBuf<uint32_t> mask_ws;      // device copy of a host bitmap (upload_allow_bits)
+    DevBuf<uint32_t> excl_ws;      // k > 128: allow-bitmap minus the rows earlier passes returned
+    DevBuf<int> maxn2;             // device, 3 words: bits of max ||row||^2, max ||row - bf16(row)||^2, max ||row - int8(row)||^2 (cz_eps)
     // int8 shadow rows (kept next to the bf16 ones when there is room): signed byte = round(x / s), s = max|x| / 127 per
     // row; read by the 1..4-query sweep and by the int8 MFMA scan of batches
     unsigned char* x8 = nullptr;
     float* x8s = nullptr;
     hipStream_t stream = nullptr;
     int num_cus = 256;
-    // reusable workspaces (grown on demand, guarded by ws_mu)
-    float* q_raw = nullptr;   size_t q_raw_cap = 0;     // floats
-    float* qpad = nullptr;    size_t qpad_cap = 0;      // floats
-    float* qnorm2 = nullptr;  size_t qnorm2_cap = 0;    // floats
-    float* qerr2 = nullptr;   size_t qerr2_cap = 0;     // per query: ||q - bf16(q)||^2 (cz_eps)
-    float* qerr2_i8 = nullptr; size_t qerr2_i8_cap = 0; // per query: ||q - int8(q)||^2 (int8 MFMA scan)
-    float* qscale = nullptr;  size_t qscale_cap = 0;    // per query: scale of its int8 row
+    // reusable workspaces (DevBuf: grown on demand, freed with the index; guarded by ws_mu)
+    DevBuf<float> q_raw;                // floats
+    DevBuf<float> qpad;                 // floats
+    DevBuf<float> qnorm2;               // floats
+    DevBuf<float> qerr2;                // per query: ||q - bf16(q)||^2 (cz_eps)
+    DevBuf<float> qerr2_i8;             // per query: ||q - int8(q)||^2 (int8 MFMA scan)
+    DevBuf<float> qscale;               // per query: scale of its int8 row
     // int8 policy feedback: the flagged count of the last search that read the int8 rows travels to pinned host memory
     // behind the search (no synchronisation); the next search of that kind looks at it when it has landed
     struct I8Feedback {
@@ -87,55 +94,57 @@ struct css_index {
         int backoff = 0;   // searches left on the bf16 rows after an int8 search that flagged too many queries
     };
     I8Feedback fb_batch, fb_sweep;
-    unsigned short* qsplit = nullptr; size_t qsplit_cap = 0;  // bf16 (h,l) pairs
-    int* gthr = nullptr;      size_t gthr_cap = 0;      // ints
-    float* part_s = nullptr;  uint32_t* part_i = nullptr; size_t part_cap = 0;  // entries
-    int64_t* out_i = nullptr; size_t out_cap = 0;      // entries (12 bytes each); a call's rows: [nq * k ids | nq * k scores]
+    DevBuf<unsigned short> qsplit;      // bf16 (h,l) pairs
+    DevBuf<int> gthr;                   // ints
+    DevBuf<float> part_s;  DevBuf<uint32_t> part_i;   // entries
+    DevBuf<char> out_i;                 // bytes, 12 per entry; a call's rows: [nq * k ids | nq * k scores] (reserve_out)
     // pinned staging of the host API for the reference's call shape (one query, k' = 100: 3 KB in, 1.2 KB out): pageable
     // copies of that size cost a staging pass and a wait each
     char* h_stage = nullptr;
     static constexpr size_t kHostStage = 64 * 1024;   // bytes, each way
-    float* stage = nullptr;   size_t stage_cap = 0;     // floats
+    DevBuf<float> stage;                // floats
     // css_index_remove_rows: keep bits and their popcount prefix of ONE window of rows (at most 2 MiB each)
-    uint32_t* compact_bits = nullptr; uint32_t* compact_pre = nullptr; size_t compact_cap = 0;   // words
+    DevBuf<uint32_t> compact_bits, compact_pre;   // words
     // coarse + rescore path (css_knn_coarse.h)
-    unsigned short* qh = nullptr; size_t qh_cap = 0;    // bf16 queries
-    float* cthr = nullptr;    size_t cthr_cap = 0;
-    int* cand_n = nullptr;    size_t cand_n_cap = 0;
-    int* cflags = nullptr;    size_t cflags_cap = 0;    // [nq_pad] flags | [nq_pad] flagged list | [1] count | [1] fix-up blocks done
-    float* cand_s = nullptr;  size_t cand_s_cap = 0;
-    uint32_t* cand_i = nullptr; size_t cand_i_cap = 0;
-    int* cpace = nullptr;     size_t cpace_cap = 0;     // sibling pacing counters [stage][group]
-    int* fs_state = nullptr;  size_t fs_state_cap = 0;  // k_sweep_cascade: ticket / stage counters / threshold key words
+    DevBuf<unsigned short> qh;          // bf16 queries
+    DevBuf<float> cthr;
+    DevBuf<int> cand_n;
+    DevBuf<int> cflags;                 // [nq_pad] flags | [nq_pad] flagged list | [1] count | [1] fix-up blocks done
+    DevBuf<float> cand_s;
+    DevBuf<uint32_t> cand_i;
+    DevBuf<int> cpace;                  // sibling pacing counters [stage][group]
+    DevBuf<int> fs_state;               // k_sweep_cascade: ticket / stage counters / threshold key words
     // device-side exact fix-up of flagged queries (k_scan_small<FIX>): one global list + lock per query
-    float* fix_s = nullptr;   uint32_t* fix_i = nullptr; size_t fix_cap = 0;    // entries [nq_pad][k]
-    int* fix_lock = nullptr;  size_t fix_lock_cap = 0;
+    DevBuf<float> fix_s;  DevBuf<uint32_t> fix_i;     // entries [nq_pad][k]
+    DevBuf<int> fix_lock;
     // second coarse pass over flagged queries (launch_scan_coarse): up to kF2Max slots with CZ_CAP2 candidates each
-    unsigned short* qh2 = nullptr; size_t qh2_cap = 0;   // bf16 rows of the flagged queries
-    float* thr2 = nullptr;    size_t thr2_cap = 0;
-    int* rs_work = nullptr;   size_t rs_work_cap = 0;   // [count | (query, part) items] of the band rescoring
-    int* cand_n2 = nullptr;   size_t cand_n2_cap = 0;
-    float* cand_s2 = nullptr; size_t cand_s2_cap = 0;
-    uint32_t* cand_i2 = nullptr; size_t cand_i2_cap = 0;
-    int* flagB = nullptr;     size_t flagB_cap = 0;      // [nq_pad] list | [1] count | [1] fix-up blocks done: queries left to the exact sweep
+    DevBuf<unsigned short> qh2;         // bf16 rows of the flagged queries
+    DevBuf<float> thr2;
+    DevBuf<int> rs_work;                // [count | (query, part) items] of the band rescoring
+    DevBuf<int> cand_n2;
+    DevBuf<float> cand_s2;
+    DevBuf<uint32_t> cand_i2;
+    DevBuf<int> flagB;                  // [nq_pad] list | [1] count | [1] fix-up blocks done: queries left to the exact sweep
     // shadow-less indexes: bf16 rows of one row range at a time + the per-range top-k lists (search_noshadow_ranges)
-    unsigned short* xh_tmp = nullptr; size_t xh_tmp_cap = 0;
-    float* x8s_tmp = nullptr; size_t x8s_tmp_cap = 0;   // row scales when the scratch rows are int8
+    DevBuf<unsigned short> xh_tmp;
+    DevBuf<float> x8s_tmp;              // row scales when the scratch rows are int8
     int64_t range_rows = 0;   // css_index_set_range_rows: rows per range (0: from the free HBM, at most 2^24)
-    float* rng_d = nullptr;   int64_t* rng_i = nullptr;  size_t rng_cap = 0;
+    DevBuf<float> rng_d;  DevBuf<int64_t> rng_i;
     const int* last_nswept = nullptr;                    // device counter behind css_index_last_swept
     // css_index_range_search (css_knn_range.h): hit counters of the 16 query slots of a sweep and the hit pool,
-    // range_cap entries (score + row) per slot; grown to the counted size when a sweep overflowed it
-    unsigned int* range_cnt = nullptr;
-    float* range_s = nullptr; uint32_t* range_i = nullptr; size_t range_cap = 0;
+    // range_cap() entries (score + row) per slot; grown to the counted size when a sweep overflowed it
+    DevBuf<unsigned int> range_cnt;
+    DevBuf<float> range_s;  DevBuf<uint32_t> range_i;
+    static constexpr int kRangeSlots = 16;   // query slots of one sweep (counters, pool segments)
+    size_t range_cap() const { return range_s.cap / kRangeSlots; }
     // css_index_search_rows: the gathered query rows [nq, dim] (not q_raw: the host search copies into that before it
     // has waited for ws_ev), one invalid-id flag per query, the search's own [nq, k + 1] results in front of
     // k_drop_self, and the device copy of a host id list
-    float* rowq = nullptr;    size_t rowq_cap = 0;      // floats
-    int* rowq_flag = nullptr; size_t rowq_flag_cap = 0;
-    float* rowq_d = nullptr;  size_t rowq_d_cap = 0;    // entries
-    int64_t* rowq_i = nullptr; size_t rowq_i_cap = 0;
-    int64_t* rowq_ids = nullptr; size_t rowq_ids_cap = 0;
+    DevBuf<float> rowq;                 // floats
+    DevBuf<int> rowq_flag;
+    DevBuf<float> rowq_d;               // entries
+    DevBuf<int64_t> rowq_i;
+    DevBuf<int64_t> rowq_ids;
     // rows written by css_index_add_dev / _add_synthetic on the CALLER's stream: searches, reallocation and
     // export wait for this event before touching rows, norms or maxn2
     hipEvent_t ingest_ev = nullptr;
@@ -154,19 +163,6 @@ struct css_index {
 namespace {
 
 constexpr int kWaves = 4;  // waves per block in the scan kernels
-
-template <typename T>
-int grow(T** p, size_t* cap, size_t need) {
-    if (need <= *cap) return CSS_OK;
-    size_t ncap = std::max(need, *cap * 2);
-    if (*p) CSS_HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    hipError_t e = hipMalloc((void**)p, ncap * sizeof(T));
-    if (e != hipSuccess) return css::hip_fail(e, "hipMalloc(workspace)", __FILE__, __LINE__);
-    *cap = ncap;
-    return CSS_OK;
-}
 
 // ------------------------------------------------------------------ ingest
 // One wave per row.  SYNTH: value = css_synth_normal(seed, (first_row+row)*dim + c).
@@ -1588,52 +1584,41 @@ bool want_i8_only(css_index* ix, int64_t ncap) {
     return (double)ncap * ix->dpad * 5.0 <= 0.8 * (double)tot;
 }
 
-// (Re)allocate the row storage for exactly ncap rows, carrying the ntotal existing rows over.
+// (Re)allocate the row storage for exactly ncap rows, carrying the ntotal existing rows over.  The new arrays are
+// owned here until the swap at the end: whatever returns early frees them.
 int reallocate_rows(css_index* ix, int64_t ncap) {
-    float* nxb = nullptr;
-    float* nn2 = nullptr;
-    unsigned short* nxh = nullptr;
-    hipError_t e = hipMalloc((void**)&nxb, (size_t)ncap * ix->dpad * sizeof(float));
-    if (e != hipSuccess) return css::hip_fail(e, "hipMalloc(index rows)", __FILE__, __LINE__);
-    e = hipMalloc((void**)&nn2, ((size_t)ncap + 256) * sizeof(float));  // +256: the coarse scan reads whole tiles of norms
-    if (e != hipSuccess) {
-        (void)hipFree(nxb);
-        return css::hip_fail(e, "hipMalloc(index norms)", __FILE__, __LINE__);
-    }
+    DevBuf<float> nxb, nn2, nx8s;
+    DevBuf<unsigned short> nxh;
+    DevBuf<unsigned char> nx8;
+    int rc;
+    if ((rc = nxb.grow_exact((size_t)ncap * ix->dpad, "hipMalloc(index rows)")) != CSS_OK) return rc;
+    // +256: the coarse scan reads whole tiles of norms
+    if ((rc = nn2.grow_exact((size_t)ncap + 256, "hipMalloc(index norms)")) != CSS_OK) return rc;
     // the shadow can only be carried over (or started on an empty index), never rebuilt here
     const bool can_shadow = ix->xh != nullptr || ix->ntotal == 0;
-    if (can_shadow && want_shadow(ix, ncap)) {
-        // (+256 rows: k_scan_coarse8 reads whole 256-row tiles; scores of rows >= ntotal are masked)
-        if (hipMalloc((void**)&nxh, ((size_t)ncap + 256) * ix->dpad * sizeof(unsigned short)) != hipSuccess) {
-            (void)hipGetLastError();  // no room: batched search falls back to the split-operand kernel
-            nxh = nullptr;
-        }
-    }
+    // (+256 rows: k_scan_coarse8 reads whole 256-row tiles; scores of rows >= ntotal are masked)
+    // no room: batched search falls back to the split-operand kernel
+    if (can_shadow && want_shadow(ix, ncap)) (void)nxh.try_exact(((size_t)ncap + 256) * ix->dpad);
     // the int8 rows of the few-query sweep ride along with the bf16 ones when 7 bytes per element still fit
-    unsigned char* nx8 = nullptr;
-    float* nx8s = nullptr;
-    const bool i8_only = !nxh && ((ix->x8 != nullptr && ix->xh == nullptr) || ix->ntotal == 0) && want_i8_only(ix, ncap);
-    if ((nxh && (ix->x8 != nullptr || ix->ntotal == 0) && want_i8(ix, ncap)) || i8_only) {
-        if (hipMalloc((void**)&nx8, ((size_t)ncap + 256) * ix->dpad) != hipSuccess ||
-            hipMalloc((void**)&nx8s, ((size_t)ncap + 256) * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (nx8) (void)hipFree(nx8);
-            nx8 = nullptr;
-            nx8s = nullptr;
+    const bool i8_only = !nxh.p && ((ix->x8 != nullptr && ix->xh == nullptr) || ix->ntotal == 0) && want_i8_only(ix, ncap);
+    if ((nxh.p && (ix->x8 != nullptr || ix->ntotal == 0) && want_i8(ix, ncap)) || i8_only) {
+        if (!nx8.try_exact(((size_t)ncap + 256) * ix->dpad) || !nx8s.try_exact((size_t)ncap + 256)) {
+            (void)nx8.drop();
+            (void)nx8s.drop();
         }
     }
     if (ix->ntotal > 0) {
         if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
-        if (nx8) {
-            CSS_HIP_TRY(hipMemcpyAsync(nx8, ix->x8, (size_t)ix->ntotal * ix->dpad, hipMemcpyDeviceToDevice, ix->stream));
-            CSS_HIP_TRY(hipMemcpyAsync(nx8s, ix->x8s, (size_t)ix->ntotal * sizeof(float), hipMemcpyDeviceToDevice, ix->stream));
+        if (nx8.p) {
+            CSS_HIP_TRY(hipMemcpyAsync(nx8.p, ix->x8, (size_t)ix->ntotal * ix->dpad, hipMemcpyDeviceToDevice, ix->stream));
+            CSS_HIP_TRY(hipMemcpyAsync(nx8s.p, ix->x8s, (size_t)ix->ntotal * sizeof(float), hipMemcpyDeviceToDevice, ix->stream));
         }
-        CSS_HIP_TRY(hipMemcpyAsync(nxb, ix->xb, (size_t)ix->ntotal * ix->dpad * sizeof(float),
+        CSS_HIP_TRY(hipMemcpyAsync(nxb.p, ix->xb, (size_t)ix->ntotal * ix->dpad * sizeof(float),
                                    hipMemcpyDeviceToDevice, ix->stream));
-        CSS_HIP_TRY(hipMemcpyAsync(nn2, ix->xnorm2, (size_t)ix->ntotal * sizeof(float), hipMemcpyDeviceToDevice,
+        CSS_HIP_TRY(hipMemcpyAsync(nn2.p, ix->xnorm2, (size_t)ix->ntotal * sizeof(float), hipMemcpyDeviceToDevice,
                                    ix->stream));
-        if (nxh)
-            CSS_HIP_TRY(hipMemcpyAsync(nxh, ix->xh, (size_t)ix->ntotal * ix->dpad * sizeof(unsigned short),
+        if (nxh.p)
+            CSS_HIP_TRY(hipMemcpyAsync(nxh.p, ix->xh, (size_t)ix->ntotal * ix->dpad * sizeof(unsigned short),
                                        hipMemcpyDeviceToDevice, ix->stream));
         CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
     }
@@ -1642,12 +1627,12 @@ int reallocate_rows(css_index* ix, int64_t ncap) {
     if (ix->xh) CSS_HIP_TRY(hipFree(ix->xh));
     if (ix->x8) CSS_HIP_TRY(hipFree(ix->x8));
     if (ix->x8s) CSS_HIP_TRY(hipFree(ix->x8s));
-    ix->xb = nxb;
-    ix->xnorm2 = nn2;
-    ix->xh = nxh;
-    ix->x8 = nx8;
-    ix->x8s = nx8s;
-    ix->shadow = nxh ? 1 : 0;
+    ix->xb = nxb.release();
+    ix->xnorm2 = nn2.release();
+    ix->xh = nxh.release();
+    ix->x8 = nx8.release();
+    ix->x8s = nx8s.release();
+    ix->shadow = ix->xh ? 1 : 0;
     ix->cap = ncap;
     return CSS_OK;
 }
@@ -1694,10 +1679,10 @@ int ingest(css_index* ix, const float* x_dev, int64_t n, int normalize, bool syn
         float* d8s = ix->x8 ? ix->x8s + r0 : nullptr;
         if (synth)
             hipLaunchKernelGGL(k_ingest_rows<true>, dim3(blocks), dim3(256), 0, st, nullptr, dst, n2, nc, ix->dim, ix->dpad,
-                               normalize, seed, first_row + c0, dh, ix->maxn2, (float*)nullptr, d8, d8s);
+                               normalize, seed, first_row + c0, dh, ix->maxn2.p, (float*)nullptr, d8, d8s);
         else
             hipLaunchKernelGGL(k_ingest_rows<false>, dim3(blocks), dim3(256), 0, st, x_dev + (size_t)c0 * ix->dim, dst, n2, nc,
-                               ix->dim, ix->dpad, normalize, 0ull, 0ll, dh, ix->maxn2, (float*)nullptr, d8, d8s);
+                               ix->dim, ix->dpad, normalize, 0ull, 0ll, dh, ix->maxn2.p, (float*)nullptr, d8, d8s);
         CSS_LAUNCH_CHECK();
     }
     return CSS_OK;
@@ -1745,10 +1730,20 @@ struct SweepGeom {
     int64_t gpb;    // row groups (of 4) per block
 };
 
+// what only k_scan_small<FIX> reads (launch_fixup); the plain sweep passes it empty
+struct FixArgs {
+    const int* flag_list = nullptr;   // the flagged queries
+    const int* nflag = nullptr;       // their count; the blocks-done word sits behind it
+    float* fix_s = nullptr;           // one global list and lock per query
+    uint32_t* fix_i = nullptr;
+    int* fix_lock = nullptr;
+    float* D = nullptr;               // result rows of the chunk
+    int64_t* I = nullptr;
+};
+
 template <int NQ, int TT, int METRIC, bool FIX>
 int launch_scan_small_t(css_index* ix, const float* qpad, int nq_real, int k, int* gthr, const SweepGeom& sg,
-                        hipStream_t st, const int* flag_list, const int* nflag, float* fix_s, uint32_t* fix_i,
-                        int* fix_lock, float* D_dev, int64_t* I_dev) {
+                        hipStream_t st, const FixArgs& fx) {
     const int T = ix->dpad / 64;
     const size_t lds = (size_t)NQ * ix->dpad * 4 + (size_t)NQ * k * 8 + NQ * 8 + (FIX ? (size_t)4 * k * 8 : 0);
     auto kern = k_scan_small<NQ, TT, METRIC, FIX>;
@@ -1756,41 +1751,27 @@ int launch_scan_small_t(css_index* ix, const float* qpad, int nq_real, int k, in
     if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
     ProfScope ps(FIX ? "knn_fix_scan" : "knn_scan_small", st);
     hipLaunchKernelGGL(kern, dim3(sg.G), dim3(256), lds, st, (const float4*)ix->xb, qpad, ix->ntotal, T, k, sg.gpb, gthr,
-                       ix->part_s, ix->part_i, nq_real, ix->cur_mask, flag_list, nflag, fix_s, fix_i, fix_lock,
-                       FIX ? const_cast<int*>(nflag) + 1 : (int*)nullptr,   // the blocks-done word sits behind the flagged count
-                       ix->id_base, D_dev, I_dev);
+                       ix->part_s.p, ix->part_i.p, nq_real, ix->cur_mask, fx.flag_list, fx.nflag, fx.fix_s, fx.fix_i, fx.fix_lock,
+                       FIX ? const_cast<int*>(fx.nflag) + 1 : (int*)nullptr, ix->id_base, fx.D, fx.I);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 
 template <int NQ, bool FIX>
 int launch_scan_small_nq(css_index* ix, const float* qpad, int nq_real, int k, int* gthr, const SweepGeom& sg,
-                         hipStream_t st, const int* flag_list = nullptr, const int* nflag = nullptr,
-                         float* fix_s = nullptr, uint32_t* fix_i = nullptr, int* fix_lock = nullptr, float* D_dev = nullptr,
-                         int64_t* I_dev = nullptr) {
+                         hipStream_t st, const FixArgs& fx = FixArgs()) {
     const bool ip = ix->metric == CSS_METRIC_IP;
-    if (ix->dpad == 768) {
-        return ip ? launch_scan_small_t<NQ, 12, CSS_METRIC_IP, FIX>(ix, qpad, nq_real, k, gthr, sg, st, flag_list, nflag, fix_s, fix_i, fix_lock, D_dev, I_dev)
-                  : launch_scan_small_t<NQ, 12, CSS_METRIC_L2, FIX>(ix, qpad, nq_real, k, gthr, sg, st, flag_list, nflag, fix_s, fix_i, fix_lock, D_dev, I_dev);
-    }
-    return ip ? launch_scan_small_t<NQ, 0, CSS_METRIC_IP, FIX>(ix, qpad, nq_real, k, gthr, sg, st, flag_list, nflag, fix_s, fix_i, fix_lock, D_dev, I_dev)
-              : launch_scan_small_t<NQ, 0, CSS_METRIC_L2, FIX>(ix, qpad, nq_real, k, gthr, sg, st, flag_list, nflag, fix_s, fix_i, fix_lock, D_dev, I_dev);
+    if (ix->dpad == 768)
+        return ip ? launch_scan_small_t<NQ, 12, CSS_METRIC_IP, FIX>(ix, qpad, nq_real, k, gthr, sg, st, fx)
+                  : launch_scan_small_t<NQ, 12, CSS_METRIC_L2, FIX>(ix, qpad, nq_real, k, gthr, sg, st, fx);
+    return ip ? launch_scan_small_t<NQ, 0, CSS_METRIC_IP, FIX>(ix, qpad, nq_real, k, gthr, sg, st, fx)
+              : launch_scan_small_t<NQ, 0, CSS_METRIC_L2, FIX>(ix, qpad, nq_real, k, gthr, sg, st, fx);
 }
 
+// the per-block top-k lists of the exact scans: [q][block][k] scores and rows
 int grow_part(css_index* ix, size_t entries) {
-    if (entries <= ix->part_cap) return CSS_OK;
-    size_t ncap = std::max(entries, ix->part_cap * 2);
-    if (ix->part_s) CSS_HIP_TRY(hipFree(ix->part_s));
-    if (ix->part_i) CSS_HIP_TRY(hipFree(ix->part_i));
-    ix->part_s = nullptr;
-    ix->part_i = nullptr;
-    ix->part_cap = 0;
-    hipError_t e = hipMalloc((void**)&ix->part_s, ncap * sizeof(float));
-    if (e != hipSuccess) return css::hip_fail(e, "hipMalloc(part_s)", __FILE__, __LINE__);
-    e = hipMalloc((void**)&ix->part_i, ncap * sizeof(uint32_t));
-    if (e != hipSuccess) return css::hip_fail(e, "hipMalloc(part_i)", __FILE__, __LINE__);
-    ix->part_cap = ncap;
-    return CSS_OK;
+    const int rc = ix->part_s.grow(entries, "hipMalloc(part_s)");
+    return rc != CSS_OK ? rc : ix->part_i.grow(entries, "hipMalloc(part_i)");
 }
 
 inline int host_f2key(float f) {
@@ -1802,10 +1783,10 @@ inline int host_f2key(float f) {
 // Queries [q0, q0+nqc) (nqc <= 16) against the whole index, results to D/I rows q0...
 int search_chunk_small(css_index* ix, int q0, int nqc, int k, const SweepGeom& sg, float* D_dev, int64_t* I_dev,
                        hipStream_t st) {
-    int* gthr = ix->gthr + q0;
+    int* gthr = ix->gthr.p + q0;
     hipLaunchKernelGGL(k_fill_int, dim3(1), dim3(64), 0, st, gthr, nqc, host_f2key(-INFINITY));
     CSS_LAUNCH_CHECK();
-    const float* qp = ix->qpad + (size_t)q0 * ix->dpad;
+    const float* qp = ix->qpad.p + (size_t)q0 * ix->dpad;
     int rc;
     if (nqc <= 1) rc = launch_scan_small_nq<1, false>(ix, qp, nqc, k, gthr, sg, st);
     else if (nqc <= 2) rc = launch_scan_small_nq<2, false>(ix, qp, nqc, k, gthr, sg, st);
@@ -1816,12 +1797,12 @@ int search_chunk_small(css_index* ix, int q0, int nqc, int k, const SweepGeom& s
     {
         ProfScope ps("knn_merge", st);
         if (ix->metric == CSS_METRIC_IP)
-            hipLaunchKernelGGL(k_merge_final<CSS_METRIC_IP>, dim3(nqc), dim3(256), 0, st, ix->part_s, ix->part_i, sg.G,
-                               k, gthr, ix->qnorm2 + q0, ix->id_base, D_dev + (size_t)q0 * k,
+            hipLaunchKernelGGL(k_merge_final<CSS_METRIC_IP>, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G,
+                               k, gthr, ix->qnorm2.p + q0, ix->id_base, D_dev + (size_t)q0 * k,
                                I_dev + (size_t)q0 * k, 0, (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
         else
-            hipLaunchKernelGGL(k_merge_final<CSS_METRIC_L2>, dim3(nqc), dim3(256), 0, st, ix->part_s, ix->part_i, sg.G,
-                               k, gthr, ix->qnorm2 + q0, ix->id_base, D_dev + (size_t)q0 * k,
+            hipLaunchKernelGGL(k_merge_final<CSS_METRIC_L2>, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G,
+                               k, gthr, ix->qnorm2.p + q0, ix->id_base, D_dev + (size_t)q0 * k,
                                I_dev + (size_t)q0 * k, 0, (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
         CSS_LAUNCH_CHECK();
     }
@@ -1829,42 +1810,31 @@ int search_chunk_small(css_index* ix, int q0, int nqc, int k, const SweepGeom& s
 }
 
 // Device-side exact fix-up of the queries a candidate path flagged (overflowing buffer or band, band not closed):
-// one launch that returns at once when nothing is flagged (nflag[1]: its blocks-done counter, zeroed with the count).  All pointers are already offset to the chunk's
-// first query; the flagging kernel has reset gthr / fix lists / locks of every flagged query.
+// one launch that returns at once when nothing is flagged (nflag[1]: its blocks-done counter, zeroed with the count).
+// qpad, gthr, D_dev and I_dev are already offset to the chunk's first query; the flagging kernel has reset gthr / fix
+// lists / locks of every flagged query.
 int launch_fixup(css_index* ix, const float* qpad, int nq, int k, int* gthr, const int* flag_list, const int* nflag,
-                 float* fix_s, uint32_t* fix_i, int* fix_lock, float* D_dev, int64_t* I_dev, const SweepGeom& sg,
-                 hipStream_t st) {
-    int rc;
-    if (sg.nq_sweep >= 8) rc = launch_scan_small_nq<8, true>(ix, qpad, 8, k, gthr, sg, st, flag_list, nflag, fix_s, fix_i, fix_lock, D_dev, I_dev);
-    else if (sg.nq_sweep >= 2) rc = launch_scan_small_nq<2, true>(ix, qpad, 2, k, gthr, sg, st, flag_list, nflag, fix_s, fix_i, fix_lock, D_dev, I_dev);
-    else rc = launch_scan_small_nq<1, true>(ix, qpad, 1, k, gthr, sg, st, flag_list, nflag, fix_s, fix_i, fix_lock, D_dev, I_dev);
-    return rc;
+                 float* D_dev, int64_t* I_dev, const SweepGeom& sg, hipStream_t st) {
+    const FixArgs fx{flag_list, nflag, ix->fix_s.p, ix->fix_i.p, ix->fix_lock.p, D_dev, I_dev};
+    if (sg.nq_sweep >= 8) return launch_scan_small_nq<8, true>(ix, qpad, 8, k, gthr, sg, st, fx);
+    if (sg.nq_sweep >= 2) return launch_scan_small_nq<2, true>(ix, qpad, 2, k, gthr, sg, st, fx);
+    return launch_scan_small_nq<1, true>(ix, qpad, 1, k, gthr, sg, st, fx);
 }
 
 // workspaces shared by the candidate paths: thresholds, candidate buffers, flags, fix-up lists for nq_pad queries
 int grow_candidate_ws(css_index* ix, size_t nq_pad, int k) {
     int rc;
-    if ((rc = grow(&ix->cthr, &ix->cthr_cap, nq_pad)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->cand_n, &ix->cand_n_cap, (size_t)nq_pad * CZ_NS)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->rs_work, &ix->rs_work_cap, 1 + (size_t)nq_pad * CZ_PARTS)) != CSS_OK) return rc;
+    if ((rc = ix->cthr.grow(nq_pad)) != CSS_OK) return rc;
+    if ((rc = ix->cand_n.grow((size_t)nq_pad * CZ_NS)) != CSS_OK) return rc;
+    if ((rc = ix->rs_work.grow(1 + (size_t)nq_pad * CZ_PARTS)) != CSS_OK) return rc;
     ix->last_nflag = nullptr;
     ix->last_nswept = nullptr;
-    if ((rc = grow(&ix->cflags, &ix->cflags_cap, 2 * nq_pad + 2)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->cand_s, &ix->cand_s_cap, nq_pad * CZ_CAP)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->cand_i, &ix->cand_i_cap, nq_pad * CZ_CAP)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->fix_lock, &ix->fix_lock_cap, nq_pad)) != CSS_OK) return rc;
-    const size_t need = nq_pad * (size_t)k;
-    if (need > ix->fix_cap) {
-        if (ix->fix_s) CSS_HIP_TRY(hipFree(ix->fix_s));
-        if (ix->fix_i) CSS_HIP_TRY(hipFree(ix->fix_i));
-        ix->fix_s = nullptr;
-        ix->fix_i = nullptr;
-        ix->fix_cap = 0;
-        CSS_HIP_TRY(hipMalloc((void**)&ix->fix_s, need * sizeof(float)));
-        CSS_HIP_TRY(hipMalloc((void**)&ix->fix_i, need * sizeof(uint32_t)));
-        ix->fix_cap = need;
-    }
-    return CSS_OK;
+    if ((rc = ix->cflags.grow(2 * nq_pad + 2)) != CSS_OK) return rc;
+    if ((rc = ix->cand_s.grow(nq_pad * CZ_CAP)) != CSS_OK) return rc;
+    if ((rc = ix->cand_i.grow(nq_pad * CZ_CAP)) != CSS_OK) return rc;
+    if ((rc = ix->fix_lock.grow(nq_pad)) != CSS_OK) return rc;
+    if ((rc = ix->fix_s.grow_exact(nq_pad * (size_t)k, "hipMalloc(fix_s)")) != CSS_OK) return rc;
+    return ix->fix_i.grow_exact(nq_pad * (size_t)k, "hipMalloc(fix_i)");
 }
 
 // second coarse pass over flagged queries: slots (query rows) and candidates per slot
@@ -1894,28 +1864,28 @@ int launch_scan_fp32mfma(css_index* ix, int nq, int k, float* D_dev, int64_t* I_
     int rc;
     if ((rc = grow_part(ix, (size_t)nq * nstrips * k)) != CSS_OK) return rc;
     if (nq_pad > nq)
-        CSS_HIP_TRY(hipMemsetAsync(ix->qpad + (size_t)nq * ix->dpad, 0, (size_t)(nq_pad - nq) * ix->dpad * 4, st));
-    hipLaunchKernelGGL(k_fill_int, dim3((nq_pad + 255) / 256), dim3(256), 0, st, ix->gthr, nq_pad, host_f2key(-INFINITY));
+        CSS_HIP_TRY(hipMemsetAsync(ix->qpad.p + (size_t)nq * ix->dpad, 0, (size_t)(nq_pad - nq) * ix->dpad * 4, st));
+    hipLaunchKernelGGL(k_fill_int, dim3((nq_pad + 255) / 256), dim3(256), 0, st, ix->gthr.p, nq_pad, host_f2key(-INFINITY));
     CSS_LAUNCH_CHECK();
     auto kern = k_scan_mfma<METRIC>;
     if ((rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
     // sibling pacing (see the kernel) where a strip has siblings; the counters share the cascade's pacing words
     int* pace = nullptr;
     if (nqtiles > 1 && nstrips * nqtiles <= ix->num_cus) {   // (all blocks resident: one per CU)
-        if ((rc = grow(&ix->cpace, &ix->cpace_cap, (size_t)nstrips * nqtiles)) != CSS_OK) return rc;
-        pace = ix->cpace;
+        if ((rc = ix->cpace.grow((size_t)nstrips * nqtiles)) != CSS_OK) return rc;
+        pace = ix->cpace.p;
         CSS_HIP_TRY(hipMemsetAsync(pace, 0, (size_t)nstrips * nqtiles * sizeof(int), st));
     }
     {
         ProfScope ps("knn_scan_mfma", st);
-        hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(256), lds, st, ix->xb, ix->xnorm2, ix->qpad, nq,
-                           ix->ntotal, ix->dpad, k, nstrips, nqtiles, tps, ix->gthr, ix->part_s, ix->part_i, ix->cur_mask, pace);
+        hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(256), lds, st, ix->xb, ix->xnorm2, ix->qpad.p, nq,
+                           ix->ntotal, ix->dpad, k, nstrips, nqtiles, tps, ix->gthr.p, ix->part_s.p, ix->part_i.p, ix->cur_mask, pace);
         CSS_LAUNCH_CHECK();
     }
     {
         ProfScope ps("knn_merge", st);
-        hipLaunchKernelGGL(k_merge_final<METRIC>, dim3(nq), dim3(256), 0, st, ix->part_s, ix->part_i, nstrips, k,
-                           ix->gthr, ix->qnorm2, ix->id_base, D_dev, I_dev, METRIC == CSS_METRIC_L2 ? 1 : 0,
+        hipLaunchKernelGGL(k_merge_final<METRIC>, dim3(nq), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, nstrips, k,
+                           ix->gthr.p, ix->qnorm2.p, ix->id_base, D_dev, I_dev, METRIC == CSS_METRIC_L2 ? 1 : 0,
                            (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
         CSS_LAUNCH_CHECK();
     }
@@ -1942,17 +1912,17 @@ int launch_final_select(css_index* ix, int nq, int k, EpsSet e1, EpsSet e2, bool
     const float eps_rel = e1.eps_rel;
     const float* qerr2 = e1.qerr2;
     const int measured = e1.measured;
-    hipLaunchKernelGGL(k_coarse_select<true>, dim3(nq), dim3(256), 0, st, ix->cand_s, ix->cand_i, ix->cand_n, ix->cthr, flags,
-                       nflag, flag_list, qnorm2, ix->maxn2, eps_rel, l2, k, closed_n, gthr, qerr2, measured, ix->fix_s, ix->fix_i, ix->fix_lock,
+    hipLaunchKernelGGL(k_coarse_select<true>, dim3(nq), dim3(256), 0, st, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, ix->cthr.p, flags,
+                       nflag, flag_list, qnorm2, ix->maxn2.p, eps_rel, l2, k, closed_n, gthr, qerr2, measured, ix->fix_s.p, ix->fix_i.p, ix->fix_lock.p,
                        exact_k ? qpad : (const float*)nullptr, exact_k ? (const float*)ix->xb : (const float*)nullptr, ix->dpad);
     // (a work list of the live parts pays from a few dozen queries on; a handful of queries launch all their parts)
     const bool plan = nq > 16;
-    if (plan) hipLaunchKernelGGL(k_rescore_plan, dim3(1), dim3(1024), 0, st, (const int*)ix->cand_n, nq, ix->rs_work, ix->rs_work + 1);
-    hipLaunchKernelGGL(k_rescore_parts<false>, dim3(std::min(kRescoreGrid, nq * CZ_PARTS)), dim3(256), 0, st, ix->cand_s,
-                       ix->cand_i, ix->cand_n, CZ_CAP, nq, (const int*)nullptr, (const int*)nullptr, (const float*)nullptr, l2, qpad,
-                       ix->xb, ix->dpad, plan ? (const int*)ix->rs_work : (const int*)nullptr,
-                       plan ? (const int*)(ix->rs_work + 1) : (const int*)nullptr);
-    hipLaunchKernelGGL(k_coarse_final, dim3(nq), dim3(256), 0, st, ix->cand_s, ix->cand_i, ix->cand_n, flags, qnorm2, ix->maxn2,
+    if (plan) hipLaunchKernelGGL(k_rescore_plan, dim3(1), dim3(1024), 0, st, (const int*)ix->cand_n.p, nq, ix->rs_work.p, ix->rs_work.p + 1);
+    hipLaunchKernelGGL(k_rescore_parts<false>, dim3(std::min(kRescoreGrid, nq * CZ_PARTS)), dim3(256), 0, st, ix->cand_s.p,
+                       ix->cand_i.p, ix->cand_n.p, CZ_CAP, nq, (const int*)nullptr, (const int*)nullptr, (const float*)nullptr, l2, qpad,
+                       ix->xb, ix->dpad, plan ? (const int*)ix->rs_work.p : (const int*)nullptr,
+                       plan ? (const int*)(ix->rs_work.p + 1) : (const int*)nullptr);
+    hipLaunchKernelGGL(k_coarse_final, dim3(nq), dim3(256), 0, st, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, flags, qnorm2, ix->maxn2.p,
                        e2.eps_rel, l2, k, qpad, ix->dpad, ix->id_base, D_dev, I_dev, thr2, qh2, f2, e2.qerr2, e2.measured);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
@@ -1964,9 +1934,9 @@ int launch_scan_split_rescore(css_index* ix, int q0, int nq, int k, float* D_dev
     // queries [q0, q0 + nq) of the padded query rows; nq <= 4096 and q0 a multiple of 256 (the caller chunks: the
     // candidate buffers are 32 KiB per query, and only the last chunk has padding rows to clear)
     const int kp = k + kSplitExtra;
-    float* const qpad = ix->qpad + (size_t)q0 * ix->dpad;
-    float* const qnorm2 = ix->qnorm2 + q0;
-    int* const gthr = ix->gthr + q0;
+    float* const qpad = ix->qpad.p + (size_t)q0 * ix->dpad;
+    float* const qnorm2 = ix->qnorm2.p + q0;
+    int* const gthr = ix->gthr.p + q0;
     D_dev += (size_t)q0 * k;
     I_dev += (size_t)q0 * k;
     const bool big = nq > 128 && kp <= 14;  // 256x256 tiles (8 waves) for real batches
@@ -1983,20 +1953,20 @@ int launch_scan_split_rescore(css_index* ix, int q0, int nq, int k, float* D_dev
     int rc;
     if ((rc = grow_part(ix, (size_t)nq * nstrips * kp)) != CSS_OK) return rc;
     if ((rc = grow_candidate_ws(ix, (size_t)nq_pad, k)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->qsplit, &ix->qsplit_cap, (size_t)nq_pad * ix->dpad * 2)) != CSS_OK) return rc;
-    int* flags = ix->cflags;
-    int* flag_list = ix->cflags + nq_pad;
-    int* nflag = ix->cflags + 2 * nq_pad;
+    if ((rc = ix->qsplit.grow((size_t)nq_pad * ix->dpad * 2)) != CSS_OK) return rc;
+    int* flags = ix->cflags.p;
+    int* flag_list = ix->cflags.p + nq_pad;
+    int* nflag = ix->cflags.p + 2 * nq_pad;
     ix->last_nflag = nflag;
     ix->last_nswept = nflag;
     if (nq_pad > nq)
         CSS_HIP_TRY(hipMemsetAsync(qpad + (size_t)nq * ix->dpad, 0, (size_t)(nq_pad - nq) * ix->dpad * 4, st));
     hipLaunchKernelGGL(k_fill_int, dim3((nq_pad + 255) / 256), dim3(256), 0, st, gthr, nq_pad, host_f2key(-INFINITY));
-    hipLaunchKernelGGL(k_coarse_init, dim3((nq_pad + 255) / 256), dim3(256), 0, st, ix->cthr, ix->cand_n, flags, nflag,
+    hipLaunchKernelGGL(k_coarse_init, dim3((nq_pad + 255) / 256), dim3(256), 0, st, ix->cthr.p, ix->cand_n.p, flags, nflag,
                        nq, nq_pad, 0, (int*)nullptr, 0, (int*)nullptr, (float*)nullptr, (int*)nullptr, 0, (int*)nullptr,
                        (const float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0, 0, 0);
     const int64_t ne = (int64_t)nq_pad * ix->dpad;
-    hipLaunchKernelGGL(k_split_queries, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, qpad, ix->qsplit,
+    hipLaunchKernelGGL(k_split_queries, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, qpad, ix->qsplit.p,
                        (int64_t)nq_pad, ix->dpad);
     CSS_LAUNCH_CHECK();
     ProfScope all("knn_split_cascade", st);
@@ -2005,29 +1975,28 @@ int launch_scan_split_rescore(css_index* ix, int q0, int nq, int k, float* D_dev
         if (big) {
             auto kern = k_scan_mfma_split<METRIC, 8, 8>;
             if ((rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
-            hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(512), lds, st, ix->xb, ix->xnorm2, ix->qsplit, nq,
-                               ix->ntotal, ix->dpad, kp, nstrips, nqtiles, tps, gthr, ix->part_s, ix->part_i, ix->cur_mask);
+            hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(512), lds, st, ix->xb, ix->xnorm2, ix->qsplit.p, nq,
+                               ix->ntotal, ix->dpad, kp, nstrips, nqtiles, tps, gthr, ix->part_s.p, ix->part_i.p, ix->cur_mask);
         } else {
             auto kern = k_scan_mfma_split<METRIC, 4, 4>;
             if ((rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
-            hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(256), lds, st, ix->xb, ix->xnorm2, ix->qsplit, nq,
-                               ix->ntotal, ix->dpad, kp, nstrips, nqtiles, tps, gthr, ix->part_s, ix->part_i, ix->cur_mask);
+            hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(256), lds, st, ix->xb, ix->xnorm2, ix->qsplit.p, nq,
+                               ix->ntotal, ix->dpad, kp, nstrips, nqtiles, tps, gthr, ix->part_s.p, ix->part_i.p, ix->cur_mask);
         }
         CSS_LAUNCH_CHECK();
     }
     // the kp best split scores of every query -> its candidate buffer (scores stay in the scan's form: IP dot
     // products, L2 2 x.q - ||x||^2, the form k_coarse_select expects of coarse scores)
-    hipLaunchKernelGGL(k_merge_final<METRIC>, dim3(nq), dim3(256), 0, st, ix->part_s, ix->part_i, nstrips, kp, gthr,
-                       qnorm2, ix->id_base, D_dev, I_dev, METRIC == CSS_METRIC_L2 ? 1 : 0, ix->cand_s, ix->cand_i,
-                       ix->cand_n);
+    hipLaunchKernelGGL(k_merge_final<METRIC>, dim3(nq), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, nstrips, kp, gthr,
+                       qnorm2, ix->id_base, D_dev, I_dev, METRIC == CSS_METRIC_L2 ? 1 : 0, ix->cand_s.p, ix->cand_i.p,
+                       ix->cand_n.p);
     if ((rc = launch_final_select(ix, nq, k, EpsSet{kSplitEps, nullptr, 0}, EpsSet{kSplitEps, nullptr, 0}, false, METRIC == CSS_METRIC_L2 ? 1 : 0, kp, qpad, qnorm2, gthr, flags, nflag,
                                   flag_list, D_dev, I_dev, nullptr, nullptr, 0, st)) != CSS_OK)
         return rc;
-    return launch_fixup(ix, qpad, nq, k, gthr, flag_list, nflag, ix->fix_s, ix->fix_i, ix->fix_lock, D_dev, I_dev,
-                        sg, st);
+    return launch_fixup(ix, qpad, nq, k, gthr, flag_list, nflag, D_dev, I_dev, sg, st);
 }
 
-// Coarse bf16 scan + exact rescoring (css_knn_coarse.h) for queries [q0, q0 + nq) of ix->qpad; nq <= 4096.
+// Coarse bf16 scan + exact rescoring (css_knn_coarse.h) for queries [q0, q0 + nq) of ix->qpad.p; nq <= 4096.
 template <int NQ, int TT, bool MAIN>
 int launch_sweep_coarse_t(css_index* ix, const float* qpad, int nq, int64_t count, int64_t stride, int gm1, bool stage0,
                           hipStream_t st) {
@@ -2036,7 +2005,7 @@ int launch_sweep_coarse_t(css_index* ix, const float* qpad, int nq, int64_t coun
     auto kern = k_sweep_coarse<NQ, TT, MAIN>;
     int rc;
     if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, ix->xh, qpad, ix->cthr, ix->cand_s, ix->cand_i, ix->cand_n,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, ix->xh, qpad, ix->cthr.p, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p,
                        ix->ntotal, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, ix->cur_mask,
                        ix->metric == CSS_METRIC_L2 ? ix->xnorm2 : nullptr);
     CSS_LAUNCH_CHECK();
@@ -2052,8 +2021,8 @@ int launch_sweep_coarse_i8_t(css_index* ix, const float* qpad, int nq, int64_t c
     auto kern = k_sweep_coarse_i8<NQ, TT, MAIN>;
     int rc;
     if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, ix->x8, ix->x8s, qpad, ix->cthr, ix->cand_s, ix->cand_i,
-                       ix->cand_n, ix->ntotal, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, ix->cur_mask,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, ix->x8, ix->x8s, qpad, ix->cthr.p, ix->cand_s.p, ix->cand_i.p,
+                       ix->cand_n.p, ix->ntotal, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, ix->cur_mask,
                        ix->metric == CSS_METRIC_L2 ? ix->xnorm2 : nullptr);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
@@ -2157,14 +2126,14 @@ inline bool mfma_sweep_applies(const css_index* ix, int64_t nq, int k) {
     return ix->ntotal >= (k <= 32 ? 50000 : 1000000);
 }
 
-// one cascade stage of the int8 MFMA sweep (3..32 queries: k_sweep_mfma_i8); the int8 queries sit in ix->qh
+// one cascade stage of the int8 MFMA sweep (3..32 queries: k_sweep_mfma_i8); the int8 queries sit in ix->qh.p
 int launch_sweep_mfma(css_index* ix, int nq, int64_t count, int64_t stride, int gm1, bool stage0, hipStream_t st) {
     const int grid = (int)std::min<int64_t>((int64_t)ix->num_cus * 8, count);
     const bool main_stage = stride == 1 && !stage0;
-    const signed char* q8 = reinterpret_cast<const signed char*>(ix->qh);
+    const signed char* q8 = reinterpret_cast<const signed char*>(ix->qh.p);
 #define CSS_LAUNCH_SWEEP_MFMA(KS_, MAIN_, NG_)                                                                         \
-    hipLaunchKernelGGL((k_sweep_mfma_i8<KS_, MAIN_, NG_>), dim3(grid), dim3(256), 0, st, ix->x8, ix->x8s, q8, ix->qscale, ix->cthr,  \
-                       ix->cand_s, ix->cand_i, ix->cand_n, ix->ntotal, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, \
+    hipLaunchKernelGGL((k_sweep_mfma_i8<KS_, MAIN_, NG_>), dim3(grid), dim3(256), 0, st, ix->x8, ix->x8s, q8, ix->qscale.p, ix->cthr.p,  \
+                       ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, ix->ntotal, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, \
                        ix->cur_mask)
     if (nq <= 16) {
         if (ix->dpad == 768) {
@@ -2195,8 +2164,8 @@ int launch_scan_qreg_t(css_index* ix, int nqt, int64_t count, int64_t stride, in
     int rc;
     if ((rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
     hipLaunchKernelGGL(kern, dim3(qreg_grid(ix)), dim3(256), lds, st, (const unsigned char*)ix->x8,
-                       reinterpret_cast<const signed char*>(ix->qh), (const float*)ix->cthr, ix->cand_s, ix->cand_i, ix->cand_n,
-                       ix->ntotal, nqt, count, stride, gm1, ix->cur_mask, (const float*)ix->x8s, (const float*)ix->qscale);
+                       reinterpret_cast<const signed char*>(ix->qh.p), (const float*)ix->cthr.p, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p,
+                       ix->ntotal, nqt, count, stride, gm1, ix->cur_mask, (const float*)ix->x8s, (const float*)ix->qscale.p);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
@@ -2228,9 +2197,9 @@ int launch_sweep_cascade_t(css_index* ix, const float* qpad, int nq, const FsSch
     per_cu = std::min(per_cu, 3);   // (12 waves per CU already draw the whole HBM rate: 2 / 3 / 4 blocks 1.305 / 1.302 / 1.316 ms at 10 M rows)
     const int grid = (int)std::min<int64_t>((int64_t)ix->num_cus * std::min(per_cu, 8), (sc.first[sc.nstage] + 3) / 4);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, I8 ? (const void*)ix->x8 : (const void*)ix->xh,
-                       I8 ? (const float*)ix->x8s : (const float*)nullptr, qpad, ix->cand_s, ix->cand_i, ix->cand_n, ix->cthr,
-                       flags, ix->ntotal, ix->dpad, nq, sc, ix->fs_state, ix->cur_mask,
-                       ix->metric == CSS_METRIC_L2 ? ix->xnorm2 : nullptr, qnorm2, (const int*)ix->maxn2, eps_rel, l2, k, measured,
+                       I8 ? (const float*)ix->x8s : (const float*)nullptr, qpad, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, ix->cthr.p,
+                       flags, ix->ntotal, ix->dpad, nq, sc, ix->fs_state.p, ix->cur_mask,
+                       ix->metric == CSS_METRIC_L2 ? ix->xnorm2 : nullptr, qnorm2, (const int*)ix->maxn2.p, eps_rel, l2, k, measured,
                        knn_env().fs_spins);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
@@ -2261,8 +2230,8 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
                        const SweepGeom& sg, bool sweep, bool use_i8, bool record_fb, const float* q_raw = nullptr,
                        int normalize_q = 0) {
     const KnnEnv& env = knn_env();
-    const float* qpad = ix->qpad + (size_t)q0 * ix->dpad;
-    const float* qnorm2 = ix->qnorm2 + q0;
+    const float* qpad = ix->qpad.p + (size_t)q0 * ix->dpad;
+    const float* qnorm2 = ix->qnorm2.p + q0;
     D_dev += (size_t)q0 * k;
     I_dev += (size_t)q0 * k;
     // 3..32 queries on int8 rows (inner product): the sweep on the int8 MFMA (k_sweep_mfma_i8): int8 queries too
@@ -2283,18 +2252,18 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     // down, so the selects of the first int8 search with more queries than any before read the freed, shorter one: zeros on
     // a fresh device, i.e. a band without the query term; stale bytes otherwise, i.e. everything flagged -- 744 of 1000
     // queries and 33 ms in the third index of one process, tools/seq_probe.py)
-    if (i8 && (!sweep || sweep_mfma) && (rc_early = grow(&ix->qerr2_i8, &ix->qerr2_i8_cap, (size_t)q0 + nq_pad)) != CSS_OK) return rc_early;
-    const float* qerr2 = (sweep && !sweep_mfma) ? nullptr : (i8 ? ix->qerr2_i8 + q0 : ix->qerr2 + q0);
+    if (i8 && (!sweep || sweep_mfma) && (rc_early = ix->qerr2_i8.grow((size_t)q0 + nq_pad)) != CSS_OK) return rc_early;
+    const float* qerr2 = (sweep && !sweep_mfma) ? nullptr : (i8 ? ix->qerr2_i8.p + q0 : ix->qerr2.p + q0);
     // the second pass over flagged queries reads the bf16 rows with bf16 queries
-    const EpsSet eps_p2{0.0078125f + 0.00048828125f, ix->qerr2 + q0, 1};
+    const EpsSet eps_p2{0.0078125f + 0.00048828125f, ix->qerr2.p + q0, 1};
     const int l2 = ix->metric == CSS_METRIC_L2 ? 1 : 0;
     const float* xn2 = l2 ? ix->xnorm2 : nullptr;  // L2: coarse score = 2 x.q - ||x||^2
     int rc;
-    if (!sweep && (rc = grow(&ix->qh, &ix->qh_cap, (size_t)nq_pad * ix->dpad)) != CSS_OK) return rc;
+    if (!sweep && (rc = ix->qh.grow((size_t)nq_pad * ix->dpad)) != CSS_OK) return rc;
     if ((rc = grow_candidate_ws(ix, (size_t)nq_pad, k)) != CSS_OK) return rc;
-    int* flags = ix->cflags;
-    int* flag_list = ix->cflags + nq_pad;
-    int* nflag = ix->cflags + 2 * nq_pad;
+    int* flags = ix->cflags.p;
+    int* flag_list = ix->cflags.p + nq_pad;
+    int* nflag = ix->cflags.p + 2 * nq_pad;
     ix->last_nflag = nflag;
     // Second pass (batches on indexes whose rows can overflow a 4096-slot buffer at all): flagged queries -- band or
     // buffer overflow: dense clusters, duplicate floods -- are scanned once more, together, against the threshold the
@@ -2309,17 +2278,17 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     int* nflagB = nullptr;
     ix->last_nswept = nflag;
     if (pass2) {
-        const size_t qh2_before = ix->qh2_cap;
-        if ((rc = grow(&ix->qh2, &ix->qh2_cap, (size_t)f2 * ix->dpad)) != CSS_OK) return rc;
+        const size_t qh2_before = ix->qh2.cap;
+        if ((rc = ix->qh2.grow((size_t)f2 * ix->dpad)) != CSS_OK) return rc;
         // slots beyond the flagged count are scanned with a +inf threshold; their rows must still be finite numbers
-        if (ix->qh2_cap != qh2_before) CSS_HIP_TRY(hipMemsetAsync(ix->qh2, 0, ix->qh2_cap * sizeof(unsigned short), st));
-        if ((rc = grow(&ix->thr2, &ix->thr2_cap, (size_t)f2)) != CSS_OK) return rc;
-        if ((rc = grow(&ix->cand_n2, &ix->cand_n2_cap, (size_t)f2 * CZ_NS)) != CSS_OK) return rc;
-        if ((rc = grow(&ix->cand_s2, &ix->cand_s2_cap, (size_t)f2 * CZ_CAP2)) != CSS_OK) return rc;
-        if ((rc = grow(&ix->cand_i2, &ix->cand_i2_cap, (size_t)f2 * CZ_CAP2)) != CSS_OK) return rc;
-        if ((rc = grow(&ix->flagB, &ix->flagB_cap, (size_t)nq_pad + 2)) != CSS_OK) return rc;
-        flag_listB = ix->flagB;
-        nflagB = ix->flagB + nq_pad;
+        if (ix->qh2.cap != qh2_before) CSS_HIP_TRY(hipMemsetAsync(ix->qh2.p, 0, ix->qh2.cap * sizeof(unsigned short), st));
+        if ((rc = ix->thr2.grow((size_t)f2)) != CSS_OK) return rc;
+        if ((rc = ix->cand_n2.grow((size_t)f2 * CZ_NS)) != CSS_OK) return rc;
+        if ((rc = ix->cand_s2.grow((size_t)f2 * CZ_CAP2)) != CSS_OK) return rc;
+        if ((rc = ix->cand_i2.grow((size_t)f2 * CZ_CAP2)) != CSS_OK) return rc;
+        if ((rc = ix->flagB.grow((size_t)nq_pad + 2)) != CSS_OK) return rc;
+        flag_listB = ix->flagB.p;
+        nflagB = ix->flagB.p + nq_pad;
         ix->last_nswept = nflagB;
     }
 
@@ -2389,40 +2358,40 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
             first += 4 * count;   // tickets are quarter tiles
         }
         fsched.first[sched.size()] = (int)first;
-        if (fused && (rc = grow(&ix->fs_state, &ix->fs_state_cap, (size_t)CZ_FS_WORDS)) != CSS_OK) return rc;
+        if (fused && (rc = ix->fs_state.grow((size_t)CZ_FS_WORDS)) != CSS_OK) return rc;
     }
     constexpr int kPaceGroups = 512, kPaceStages = 20;
     const bool use_pace = !sweep;
-    if (use_pace && (rc = grow(&ix->cpace, &ix->cpace_cap, (size_t)kPaceGroups * kPaceStages)) != CSS_OK) return rc;
+    if (use_pace && (rc = ix->cpace.grow((size_t)kPaceGroups * kPaceStages)) != CSS_OK) return rc;
 
     {
         if (!sweep && i8) {   // int8 query rows (into the same buffer: half its bytes), their scales and error norms
-            if ((rc = grow(&ix->qscale, &ix->qscale_cap, (size_t)nq_pad)) != CSS_OK) return rc;
-            if ((rc = grow(&ix->qerr2_i8, &ix->qerr2_i8_cap, (size_t)q0 + nq_pad)) != CSS_OK) return rc;
+            if ((rc = ix->qscale.grow((size_t)nq_pad)) != CSS_OK) return rc;
+            if ((rc = ix->qerr2_i8.grow((size_t)q0 + nq_pad)) != CSS_OK) return rc;
             hipLaunchKernelGGL(k_rows_to_i8, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, st, qpad,
-                               reinterpret_cast<signed char*>(ix->qh), ix->qscale, ix->qerr2_i8 + q0, nq, nq_pad, ix->dpad);
+                               reinterpret_cast<signed char*>(ix->qh.p), ix->qscale.p, ix->qerr2_i8.p + q0, nq, nq_pad, ix->dpad);
             CSS_LAUNCH_CHECK();
         } else if (!sweep) {
             const int64_t ne = (int64_t)nq_pad * ix->dpad;
-            hipLaunchKernelGGL(k_rows_to_bf16, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, qpad, ix->qh,
+            hipLaunchKernelGGL(k_rows_to_bf16, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, qpad, ix->qh.p,
                                (int64_t)nq, (int64_t)nq_pad, ix->dpad);
             CSS_LAUNCH_CHECK();
         }
         const int npace = use_pace ? kPaceGroups * kPaceStages : 0;
         const int ninit = std::max(std::max(std::max(std::max(nq_pad, npace), f2), fused ? CZ_FS_KEYWORDS : 0),
                                    q_raw != nullptr ? nq * 64 : 0);   // (query prep: one wave per query)
-        hipLaunchKernelGGL(k_coarse_init, dim3((ninit + 255) / 256), dim3(256), 0, st, ix->cthr, ix->cand_n, flags,
-                           nflag, nq, nq_pad, (int)(n0 * CZ_T), use_pace ? ix->cpace : (int*)nullptr, npace,
-                           pass2 ? ix->cand_n2 : (int*)nullptr, pass2 ? ix->thr2 : (float*)nullptr, nflagB, f2,
-                           fused ? ix->fs_state : (int*)nullptr, q_raw, ix->qpad + (size_t)q0 * ix->dpad, ix->qnorm2 + q0,
-                           ix->qerr2 + q0, ix->dim, ix->dpad, normalize_q);
+        hipLaunchKernelGGL(k_coarse_init, dim3((ninit + 255) / 256), dim3(256), 0, st, ix->cthr.p, ix->cand_n.p, flags,
+                           nflag, nq, nq_pad, (int)(n0 * CZ_T), use_pace ? ix->cpace.p : (int*)nullptr, npace,
+                           pass2 ? ix->cand_n2.p : (int*)nullptr, pass2 ? ix->thr2.p : (float*)nullptr, nflagB, f2,
+                           fused ? ix->fs_state.p : (int*)nullptr, q_raw, ix->qpad.p + (size_t)q0 * ix->dpad, ix->qnorm2.p + q0,
+                           ix->qerr2.p + q0, ix->dim, ix->dpad, normalize_q);
         CSS_LAUNCH_CHECK();
         if (sweep_mfma) {   // int8 query rows (16, zero padded), their scales and error norms -- behind the init launch, which may have prepared qpad
-            if ((rc = grow(&ix->qh, &ix->qh_cap, (size_t)nq_pad * ix->dpad)) != CSS_OK) return rc;
-            if ((rc = grow(&ix->qscale, &ix->qscale_cap, (size_t)nq_pad)) != CSS_OK) return rc;
-            if ((rc = grow(&ix->qerr2_i8, &ix->qerr2_i8_cap, (size_t)q0 + nq_pad)) != CSS_OK) return rc;
+            if ((rc = ix->qh.grow((size_t)nq_pad * ix->dpad)) != CSS_OK) return rc;
+            if ((rc = ix->qscale.grow((size_t)nq_pad)) != CSS_OK) return rc;
+            if ((rc = ix->qerr2_i8.grow((size_t)q0 + nq_pad)) != CSS_OK) return rc;
             hipLaunchKernelGGL(k_rows_to_i8, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, st, qpad,
-                               reinterpret_cast<signed char*>(ix->qh), ix->qscale, ix->qerr2_i8 + q0, nq, nq_pad, ix->dpad);
+                               reinterpret_cast<signed char*>(ix->qh.p), ix->qscale.p, ix->qerr2_i8.p + q0, nq, nq_pad, ix->dpad);
             CSS_LAUNCH_CHECK();
         }
     }
@@ -2444,7 +2413,7 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
                                : (loop8 ? k_scan_coarse8<false, true> : k_scan_coarse<false, true>);
     const unsigned short* scan_rows = i8b ? reinterpret_cast<const unsigned short*>(ix->x8) : ix->xh;
     const float* scan_xsc = i8b ? ix->x8s : nullptr;
-    const float* scan_qsc = i8b ? ix->qscale : nullptr;
+    const float* scan_qsc = i8b ? ix->qscale.p : nullptr;
     if (!sweep)
         for (scan_fn f : {f_stage0, f_mid, f_main})
             if ((rc = css::ensure_dynamic_lds((const void*)f, lds, ix->device)) != CSS_OK) return rc;
@@ -2461,8 +2430,8 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
             else rc = launch_sweep_cascade_nq<4>(ix, qpad, nq, fsched, flags, qnorm2, eps_rel, l2, k, measured, st, i8);
             if (rc != CSS_OK) return rc;
         }
-        if ((rc = launch_final_select(ix, nq, k, EpsSet{eps_rel, qerr2, measured}, eps_p2, exact_k, l2, 0, qpad, qnorm2, ix->gthr + q0, flags, nflag, flag_list, D_dev,
-                                      I_dev, pass2 ? ix->thr2 : nullptr, pass2 ? ix->qh2 : nullptr, f2, st)) != CSS_OK)
+        if ((rc = launch_final_select(ix, nq, k, EpsSet{eps_rel, qerr2, measured}, eps_p2, exact_k, l2, 0, qpad, qnorm2, ix->gthr.p + q0, flags, nflag, flag_list, D_dev,
+                                      I_dev, pass2 ? ix->thr2.p : nullptr, pass2 ? ix->qh2.p : nullptr, f2, st)) != CSS_OK)
             return rc;
     } else {
     ProfScope all(sweep ? "knn_sweep_cascade" : "knn_coarse_cascade", st);
@@ -2495,23 +2464,23 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
                 // (int8 rows: no sibling pacing -- a row tile fetched by every query-tile block on its own is still only
                 // ~3.5 TB/s worst case at this scan's speed, and the coupling costs more than the HBM traffic it saves:
                 // 9.65 vs 9.02 ms per batch; the bf16 scan reads twice the bytes per row and needs it)
-                int* pace = (!i8b && grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace + (size_t)stage_idx * kPaceGroups : nullptr;
-                hipLaunchKernelGGL(f, dim3(grid), dim3(512), lds, st, scan_rows, ix->qh, ix->cthr, ix->cand_s, ix->cand_i,
-                                   ix->cand_n, ix->ntotal, ix->dpad, nqt, count, s, gr - 1, pace, ix->cur_mask, xn2,
+                int* pace = (!i8b && grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace.p + (size_t)stage_idx * kPaceGroups : nullptr;
+                hipLaunchKernelGGL(f, dim3(grid), dim3(512), lds, st, scan_rows, ix->qh.p, ix->cthr.p, ix->cand_s.p, ix->cand_i.p,
+                                   ix->cand_n.p, ix->ntotal, ix->dpad, nqt, count, s, gr - 1, pace, ix->cur_mask, xn2,
                                    (const int*)nullptr, scan_xsc, scan_qsc);
                 CSS_LAUNCH_CHECK();
             }
         }
         ++stage_idx;
         if (s == 1) {
-            if ((rc = launch_final_select(ix, nq, k, EpsSet{eps_rel, qerr2, measured}, eps_p2, exact_k, l2, 0, qpad, qnorm2, ix->gthr + q0, flags, nflag, flag_list, D_dev,
-                                          I_dev, pass2 ? ix->thr2 : nullptr, pass2 ? ix->qh2 : nullptr, f2, st)) != CSS_OK)
+            if ((rc = launch_final_select(ix, nq, k, EpsSet{eps_rel, qerr2, measured}, eps_p2, exact_k, l2, 0, qpad, qnorm2, ix->gthr.p + q0, flags, nflag, flag_list, D_dev,
+                                          I_dev, pass2 ? ix->thr2.p : nullptr, pass2 ? ix->qh2.p : nullptr, f2, st)) != CSS_OK)
                 return rc;
             break;
         }
-        hipLaunchKernelGGL(k_coarse_select<false>, dim3(nq), dim3(256), 0, st, ix->cand_s, ix->cand_i, ix->cand_n,
-                           ix->cthr, flags, nflag, flag_list, qnorm2, ix->maxn2, eps_rel, l2, k, 0, ix->gthr + q0, qerr2, measured, ix->fix_s,
-                           ix->fix_i, ix->fix_lock, exact_k ? qpad : (const float*)nullptr,
+        hipLaunchKernelGGL(k_coarse_select<false>, dim3(nq), dim3(256), 0, st, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p,
+                           ix->cthr.p, flags, nflag, flag_list, qnorm2, ix->maxn2.p, eps_rel, l2, k, 0, ix->gthr.p + q0, qerr2, measured, ix->fix_s.p,
+                           ix->fix_i.p, ix->fix_lock.p, exact_k ? qpad : (const float*)nullptr,
                            exact_k ? (const float*)ix->xb : (const float*)nullptr, ix->dpad);
         CSS_LAUNCH_CHECK();
     }
@@ -2526,42 +2495,45 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
         if ((rc = css::ensure_dynamic_lds((const void*)f_all, lds, ix->device)) != CSS_OK) return rc;
         const int nqt2 = f2 / CZ_T;
         {
-            int* pace = (grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace + (size_t)stage_idx * kPaceGroups : nullptr;
-            hipLaunchKernelGGL(f_all, dim3(grid), dim3(512), lds, st, ix->xh, ix->qh2, ix->thr2, ix->cand_s2, ix->cand_i2,
-                               ix->cand_n2, ix->ntotal, ix->dpad, nqt2, ntiles, (int64_t)1, 1 << 30, pace, ix->cur_mask, xn2,
+            int* pace = (grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace.p + (size_t)stage_idx * kPaceGroups : nullptr;
+            hipLaunchKernelGGL(f_all, dim3(grid), dim3(512), lds, st, ix->xh, ix->qh2.p, ix->thr2.p, ix->cand_s2.p, ix->cand_i2.p,
+                               ix->cand_n2.p, ix->ntotal, ix->dpad, nqt2, ntiles, (int64_t)1, 1 << 30, pace, ix->cur_mask, xn2,
                                (const int*)nflag, (const float*)nullptr, (const float*)nullptr);
         }
-        hipLaunchKernelGGL(k_rescore_parts<true>, dim3(kRescoreGrid), dim3(256), 0, st, ix->cand_s2, ix->cand_i2, ix->cand_n2,
-                           CZ_CAP2, f2, nflag, flag_list, ix->thr2, l2, qpad, ix->xb, ix->dpad, (const int*)nullptr, (const int*)nullptr);
-        hipLaunchKernelGGL(k_coarse_select2<CZ_CAP2>, dim3(f2), dim3(256), 0, st, ix->cand_s2, ix->cand_i2, ix->cand_n2, nflag,
+        hipLaunchKernelGGL(k_rescore_parts<true>, dim3(kRescoreGrid), dim3(256), 0, st, ix->cand_s2.p, ix->cand_i2.p, ix->cand_n2.p,
+                           CZ_CAP2, f2, nflag, flag_list, ix->thr2.p, l2, qpad, ix->xb, ix->dpad, (const int*)nullptr, (const int*)nullptr);
+        hipLaunchKernelGGL(k_coarse_select2<CZ_CAP2>, dim3(f2), dim3(256), 0, st, ix->cand_s2.p, ix->cand_i2.p, ix->cand_n2.p, nflag,
                            flag_list, f2, nflagB, flag_listB, l2, k, ix->id_base, D_dev, I_dev);
         CSS_LAUNCH_CHECK();
         // what overflowed the second pass too (tens of thousands of rows inside one band): exact fp32 sweep
-        return launch_fixup(ix, qpad, nq, k, ix->gthr + q0, flag_listB, nflagB, ix->fix_s, ix->fix_i, ix->fix_lock, D_dev, I_dev,
-                            sg, st);
+        return launch_fixup(ix, qpad, nq, k, ix->gthr.p + q0, flag_listB, nflagB, D_dev, I_dev, sg, st);
     }
     // queries whose candidate buffer or band overflowed (thousands of duplicate rows, a zero query): exact
     // fp32 sweep on the device, two launches that return at once when the flag count is zero
-    return launch_fixup(ix, qpad, nq, k, ix->gthr + q0, flag_list, nflag, ix->fix_s, ix->fix_i, ix->fix_lock, D_dev, I_dev,
-                        sg, st);
+    return launch_fixup(ix, qpad, nq, k, ix->gthr.p + q0, flag_list, nflag, D_dev, I_dev, sg, st);
+}
+
+// grid of the exact fp32 sweeps (k_scan_small, k_range_small) over the rows in view: enough blocks to fill the chip
+// (8 per CU) but at least ~64 row groups of work each
+void sweep_grid(const css_index* ix, int* G, int64_t* gpb) {
+    const int64_t ngroups = (ix->ntotal + 3) / 4;
+    const int64_t G0 = std::max<int64_t>(1, std::min<int64_t>((int64_t)ix->num_cus * 8, (ngroups + 63) / 64));
+    *gpb = (ngroups + G0 - 1) / G0;
+    *G = (int)((ngroups + *gpb - 1) / *gpb);
 }
 
 // sweep geometry of the small-batch kernel (also the exact fix-up of the candidate paths) for the rows in view
 int make_sweep_geom(const css_index* ix, int k, SweepGeom* sg) {
     sg->nq_sweep = (int)std::min<int64_t>(16, (64 * 1024) / ((int64_t)ix->dpad * 4 + (int64_t)k * 8 + 8));
     CSS_REQUIRE(sg->nq_sweep >= 1, "css_index_search: dim=%d too large for the scan kernel", ix->dim);
-    // enough blocks to fill the chip (8 per CU) but at least ~64 row groups of work each
-    const int64_t ngroups = (ix->ntotal + 3) / 4;
-    int64_t G = std::max<int64_t>(1, std::min<int64_t>((int64_t)ix->num_cus * 8, (ngroups + 63) / 64));
-    sg->gpb = (ngroups + G - 1) / G;
-    sg->G = (int)((ngroups + sg->gpb - 1) / sg->gpb);
+    sweep_grid(ix, &sg->G, &sg->gpb);
     return CSS_OK;
 }
 
 // ------------------------------------------------------------------ range search (css_knn_range.h)
 #include "css_knn_range.h"
 
-constexpr int kRangeSlots = 16;              // query slots of one sweep (counters, pool segments)
+constexpr int kRangeSlots = css_index::kRangeSlots;
 constexpr size_t kRangeInitialCap = 4096;    // pool entries per slot before the first growth
 
 template <int NQ, int TT, int METRIC>
@@ -2572,7 +2544,7 @@ int launch_range_small_t(css_index* ix, const float* qpad, int nq_real, float ra
     if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
     ProfScope ps("knn_range_small", st);
     hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, st, (const float4*)ix->xb, qpad, ix->ntotal, ix->dpad / 64, gpb, nq_real,
-                       ix->cur_mask, radius, ix->range_cnt, ix->range_s, ix->range_i, (unsigned int)ix->range_cap);
+                       ix->cur_mask, radius, ix->range_cnt.p, ix->range_s.p, ix->range_i.p, (unsigned int)ix->range_cap());
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
@@ -2596,18 +2568,17 @@ int range_nq_sweep(const css_index* ix) {
 // One sweep of all rows for queries qpad[0 .. nqc) (nqc <= range_nq_sweep): counters zeroed, kernel, counters back on
 // the host (waits for the stream).
 int range_sweep(css_index* ix, const float* qpad, int nqc, float radius, unsigned int* cnt_host, hipStream_t st) {
-    const int64_t ngroups = (ix->ntotal + 3) / 4;
-    const int64_t G0 = std::max<int64_t>(1, std::min<int64_t>((int64_t)ix->num_cus * 8, (ngroups + 63) / 64));
-    const int64_t gpb = (ngroups + G0 - 1) / G0;
-    const int G = (int)((ngroups + gpb - 1) / gpb);
-    CSS_HIP_TRY(hipMemsetAsync(ix->range_cnt, 0, kRangeSlots * sizeof(unsigned int), st));
+    int G;
+    int64_t gpb;
+    sweep_grid(ix, &G, &gpb);
+    CSS_HIP_TRY(hipMemsetAsync(ix->range_cnt.p, 0, kRangeSlots * sizeof(unsigned int), st));
     int rc;
     if (nqc <= 1) rc = launch_range_small_nq<1>(ix, qpad, nqc, radius, G, gpb, st);
     else if (nqc <= 2) rc = launch_range_small_nq<2>(ix, qpad, nqc, radius, G, gpb, st);
     else if (nqc <= 8) rc = launch_range_small_nq<8>(ix, qpad, nqc, radius, G, gpb, st);
     else rc = launch_range_small_nq<16>(ix, qpad, nqc, radius, G, gpb, st);
     if (rc != CSS_OK) return rc;
-    CSS_HIP_TRY(hipMemcpyAsync(cnt_host, ix->range_cnt, kRangeSlots * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipMemcpyAsync(cnt_host, ix->range_cnt.p, kRangeSlots * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     CSS_HIP_TRY(hipStreamSynchronize(st));
     return CSS_OK;
 }
@@ -2615,21 +2586,7 @@ int range_sweep(css_index* ix, const float* qpad, int nqc, float radius, unsigne
 // The hit pool with `cap` entries per slot (nothing of the old one is kept: a grown pool is filled by a new sweep).
 // No room: CSS_ERR_OOM, the pool is gone (the next call starts from the initial size) and the index is untouched.
 int range_pool_alloc(css_index* ix, size_t cap) {
-    if (ix->range_s) (void)hipFree(ix->range_s);
-    if (ix->range_i) (void)hipFree(ix->range_i);
-    ix->range_s = nullptr;
-    ix->range_i = nullptr;
-    ix->range_cap = 0;
-    if (hipMalloc((void**)&ix->range_s, kRangeSlots * cap * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&ix->range_i, kRangeSlots * cap * sizeof(uint32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        if (ix->range_s) (void)hipFree(ix->range_s);
-        ix->range_s = nullptr;
-        ix->range_i = nullptr;
-        return CSS_ERR_OOM;
-    }
-    ix->range_cap = cap;
-    return CSS_OK;
+    return try_exact_pair(ix->range_s, ix->range_i, kRangeSlots * cap) ? CSS_OK : CSS_ERR_OOM;
 }
 
 // RAII: the index narrowed to rows [row0, row0 + n) with `xh` as their bf16 shadow rows -- every launcher below reads
@@ -2717,7 +2674,7 @@ int search_noshadow_ranges(css_index* ix, int64_t nq, int k, float* D_dev, int64
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return kNoRangeScratch;
     const size_t row_b = (size_t)ix->dpad * 2;
-    int64_t rows_fit = (int64_t)((free_b + ix->xh_tmp_cap * 2) / 2 / row_b);          // half of what is free (incl. our own scratch)
+    int64_t rows_fit = (int64_t)((free_b + ix->xh_tmp.cap * 2) / 2 / row_b);          // half of what is free (incl. our own scratch)
     rows_fit = std::min<int64_t>(rows_fit, 16ll << 20) / CZ_T * CZ_T;
     int64_t S = std::min<int64_t>((ntotal + CZ_T - 1) / CZ_T * CZ_T, rows_fit);
     if (S < std::min<int64_t>(ntotal, 1ll << 20)) return kNoRangeScratch;
@@ -2726,67 +2683,41 @@ int search_noshadow_ranges(css_index* ix, int64_t nq, int k, float* D_dev, int64
     // same quantiser as k_ingest_rows, whose running maximum of the int8 error norms covers every row of the index
     // (allow_i8 = false: an index with int8 rows of its own whose int8 choice was already declined for this search)
     const bool use_i8 = allow_i8 && batch_i8_wanted(ix, k, std::min<int64_t>(S, ntotal), nq);
-    if (use_i8 && (rc = grow(&ix->x8s_tmp, &ix->x8s_tmp_cap, (size_t)S + 256)) != CSS_OK) return rc;
-    if ((size_t)S * ix->dpad > ix->xh_tmp_cap) {   // (exact size: grow() would double a multi-GB buffer)
-        if (ix->xh_tmp) CSS_HIP_TRY(hipFree(ix->xh_tmp));
-        ix->xh_tmp = nullptr;
-        ix->xh_tmp_cap = 0;
-        if (hipMalloc((void**)&ix->xh_tmp, (size_t)S * row_b) != hipSuccess) {
-            (void)hipGetLastError();
-            return kNoRangeScratch;
-        }
-        ix->xh_tmp_cap = (size_t)S * ix->dpad;
-    }
+    if (use_i8 && (rc = ix->x8s_tmp.grow((size_t)S + 256)) != CSS_OK) return rc;
+    if (!ix->xh_tmp.try_exact((size_t)S * ix->dpad)) return kNoRangeScratch;   // (exact size: grow() would double a multi-GB buffer)
     const int nranges = (int)((ntotal + S - 1) / S);
     float* Dp = D_dev;
     int64_t* Ip = I_dev;
-    if (nranges > 1) {
-        const size_t need = (size_t)nranges * nq * k;
-        if (need > ix->rng_cap) {
-            if (ix->rng_d) CSS_HIP_TRY(hipFree(ix->rng_d));
-            if (ix->rng_i) CSS_HIP_TRY(hipFree(ix->rng_i));
-            ix->rng_d = nullptr;
-            ix->rng_i = nullptr;
-            ix->rng_cap = 0;
-            if (hipMalloc((void**)&ix->rng_d, need * sizeof(float)) != hipSuccess ||
-                hipMalloc((void**)&ix->rng_i, need * sizeof(int64_t)) != hipSuccess) {   // (nothing enqueued yet: the fallback is safe)
-                (void)hipGetLastError();
-                if (ix->rng_d) (void)hipFree(ix->rng_d);
-                ix->rng_d = nullptr;
-                ix->rng_i = nullptr;
-                return kNoRangeScratch;
-            }
-            ix->rng_cap = need;
-        }
-    }
+    // (nothing enqueued yet: the fallback is safe)
+    if (nranges > 1 && !try_exact_pair(ix->rng_d, ix->rng_i, (size_t)nranges * nq * k)) return kNoRangeScratch;
     ProfScope all("knn_noshadow_ranges", st);
     for (int r = 0; r < nranges; ++r) {
         const int64_t row0 = (int64_t)r * S, n = std::min<int64_t>(S, ntotal - row0);
         if (use_i8) {
             ProfScope ps("knn_rows_to_i8", st);
             const float* src_ = ix->xb + (size_t)row0 * ix->dpad;
-            signed char* dst_ = reinterpret_cast<signed char*>(ix->xh_tmp);
+            signed char* dst_ = reinterpret_cast<signed char*>(ix->xh_tmp.p);
             const dim3 grid_((unsigned)((n + 3) / 4));
             switch (ix->dpad) {   // (dpad % 256 == 0 and <= 1024: batch_i8_wanted)
-                case 256: hipLaunchKernelGGL(k_rows_to_i8_wide<4>, grid_, dim3(256), 0, st, src_, dst_, ix->x8s_tmp, n); break;
-                case 512: hipLaunchKernelGGL(k_rows_to_i8_wide<8>, grid_, dim3(256), 0, st, src_, dst_, ix->x8s_tmp, n); break;
-                case 768: hipLaunchKernelGGL(k_rows_to_i8_wide<12>, grid_, dim3(256), 0, st, src_, dst_, ix->x8s_tmp, n); break;
-                default: hipLaunchKernelGGL(k_rows_to_i8_wide<16>, grid_, dim3(256), 0, st, src_, dst_, ix->x8s_tmp, n); break;
+                case 256: hipLaunchKernelGGL(k_rows_to_i8_wide<4>, grid_, dim3(256), 0, st, src_, dst_, ix->x8s_tmp.p, n); break;
+                case 512: hipLaunchKernelGGL(k_rows_to_i8_wide<8>, grid_, dim3(256), 0, st, src_, dst_, ix->x8s_tmp.p, n); break;
+                case 768: hipLaunchKernelGGL(k_rows_to_i8_wide<12>, grid_, dim3(256), 0, st, src_, dst_, ix->x8s_tmp.p, n); break;
+                default: hipLaunchKernelGGL(k_rows_to_i8_wide<16>, grid_, dim3(256), 0, st, src_, dst_, ix->x8s_tmp.p, n); break;
             }
             CSS_LAUNCH_CHECK();
         } else {
             ProfScope ps("knn_rows_to_bf16", st);
             const int64_t n8 = n * ix->dpad / 8;   // (dpad is a multiple of 64)
             const unsigned blocks = (unsigned)std::min<int64_t>((n8 + 255) / 256, (int64_t)ix->num_cus * 64);
-            hipLaunchKernelGGL(k_rows_to_bf16_x8, dim3(blocks), dim3(256), 0, st, ix->xb + (size_t)row0 * ix->dpad, ix->xh_tmp, n8);
+            hipLaunchKernelGGL(k_rows_to_bf16_x8, dim3(blocks), dim3(256), 0, st, ix->xb + (size_t)row0 * ix->dpad, ix->xh_tmp.p, n8);
             CSS_LAUNCH_CHECK();
         }
         if (nranges > 1) {
-            Dp = ix->rng_d + (size_t)r * nq * k;
-            Ip = ix->rng_i + (size_t)r * nq * k;
+            Dp = ix->rng_d.p + (size_t)r * nq * k;
+            Ip = ix->rng_i.p + (size_t)r * nq * k;
         }
-        RowView view(ix, row0, n, use_i8 ? nullptr : ix->xh_tmp, use_i8 ? reinterpret_cast<unsigned char*>(ix->xh_tmp) : nullptr,
-                     use_i8 ? ix->x8s_tmp : nullptr);
+        RowView view(ix, row0, n, use_i8 ? nullptr : ix->xh_tmp.p, use_i8 ? reinterpret_cast<unsigned char*>(ix->xh_tmp.p) : nullptr,
+                     use_i8 ? ix->x8s_tmp.p : nullptr);
         SweepGeom sg;
         if ((rc = make_sweep_geom(ix, k, &sg)) != CSS_OK) return rc;
         const int chunk = coarse_max_chunk(ix);
@@ -2797,8 +2728,45 @@ int search_noshadow_ranges(css_index* ix, int64_t nq, int k, float* D_dev, int64
         }
     }
     if (nranges > 1)
-        return merge_parts(ix->rng_d, ix->rng_i, nranges, nq * k, nq * k, nq, k, ix->metric, D_dev, I_dev, ix->device, st,
+        return merge_parts(ix->rng_d.p, ix->rng_i.p, nranges, nq * k, nq * k, nq, k, ix->metric, D_dev, I_dev, ix->device, st,
                            "css_index_search");
+    return CSS_OK;
+}
+
+// RAII: one turn at the shared workspaces for what the caller enqueues on `st`.  The previous turn may still be
+// running on another stream and owns the workspaces until its event: wait for it (a turn on the same stream is
+// ordered already).  The end of the scope records the event for the next turn -- also after a failed enqueue, because
+// whatever was launched before the error still uses the workspaces -- and when that cannot be recorded the device is
+// drained instead.  Turns nest (search_any_k around search_dev_locked): the outermost record is the last.  Caller
+// holds ws_mu, and returns `rc` when it is not CSS_OK.
+struct WsTurn {
+    css_index* ix;
+    hipStream_t st;
+    int rc = CSS_OK;
+    WsTurn(css_index* i, hipStream_t s) : ix(i), st(s) {
+        if (!(ix->ws_pending && ix->ws_stream != st)) return;
+        const hipError_t e = hipStreamWaitEvent(st, ix->ws_ev, 0);
+        if (e != hipSuccess) rc = css::hip_fail(e, "hipStreamWaitEvent(st, ix->ws_ev, 0)", __FILE__, __LINE__);
+    }
+    WsTurn(const WsTurn&) = delete;
+    ~WsTurn() {
+        if (hipEventRecord(ix->ws_ev, st) == hipSuccess) {
+            ix->ws_stream = st;
+            ix->ws_pending = true;
+        } else {
+            (void)hipDeviceSynchronize();
+            ix->ws_pending = false;
+        }
+    }
+};
+
+// Query prep of every search: the row kernel of ingest (normalise, zero pad, squared norm) from raw [nq, dim] rows
+// into qpad / qnorm2, and ||q - bf16(q)||^2 into `qerr2` where the caller keeps it.
+int prep_queries(css_index* ix, const float* src, int64_t nq, int normalize_q, float* qerr2, hipStream_t st) {
+    hipLaunchKernelGGL(k_ingest_rows<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, src, ix->qpad.p, ix->qnorm2.p, nq,
+                       ix->dim, ix->dpad, normalize_q, 0ull, 0ll, (unsigned short*)nullptr, (int*)nullptr, qerr2,
+                       (unsigned char*)nullptr, (float*)nullptr);
+    CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 
@@ -2807,18 +2775,9 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
                        int64_t* I_dev, hipStream_t st);
 int search_dev_locked(css_index* ix, const float* q_dev, int64_t nq, int k, int normalize_q, float* D_dev,
                       int64_t* I_dev, hipStream_t st) {
-    // the previous search may still be running on another stream and owns the shared workspaces until its event
-    if (ix->ws_pending && ix->ws_stream != st) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ws_ev, 0));
-    const int rc = search_dev_enqueue(ix, q_dev, nq, k, normalize_q, D_dev, I_dev, st);
-    // (also after a failed enqueue: whatever was launched before the error still uses the workspaces)
-    if (hipEventRecord(ix->ws_ev, st) == hipSuccess) {
-        ix->ws_stream = st;
-        ix->ws_pending = true;
-    } else {
-        (void)hipDeviceSynchronize();
-        ix->ws_pending = false;
-    }
-    return rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    return search_dev_enqueue(ix, q_dev, nq, k, normalize_q, D_dev, I_dev, st);
 }
 int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int normalize_q, float* D_dev,
                        int64_t* I_dev, hipStream_t st) {
@@ -2829,12 +2788,12 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
     int rc;
     // rows appended on another stream (css_index_add_dev / _add_synthetic) must have landed
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
-    if ((rc = grow(&ix->qpad, &ix->qpad_cap, (size_t)(nq + 256) * ix->dpad)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->qnorm2, &ix->qnorm2_cap, (size_t)nq + 256)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->qerr2, &ix->qerr2_cap, (size_t)nq + 256)) != CSS_OK) return rc;
+    if ((rc = ix->qpad.grow((size_t)(nq + 256) * ix->dpad)) != CSS_OK) return rc;
+    if ((rc = ix->qnorm2.grow((size_t)nq + 256)) != CSS_OK) return rc;
+    if ((rc = ix->qerr2.grow((size_t)nq + 256)) != CSS_OK) return rc;
     // (int8 rows: the int8 queries' error norms of every chunk of this search -- never reallocated between two chunks)
-    if (ix->x8 != nullptr && (rc = grow(&ix->qerr2_i8, &ix->qerr2_i8_cap, (size_t)nq + 256)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->gthr, &ix->gthr_cap, (size_t)nq + 256)) != CSS_OK) return rc;
+    if (ix->x8 != nullptr && (rc = ix->qerr2_i8.grow((size_t)nq + 256)) != CSS_OK) return rc;
+    if ((rc = ix->gthr.grow((size_t)nq + 256)) != CSS_OK) return rc;
     // 1..4 queries through the sweep cascade: its init launch prepares the query rows as well (one launch less in front
     // of a 1.4 ms search).  Which shadow rows a search reads is decided once (the per-index int8 feedback counts searches).
     // 3 or 4 queries are VALU-bound in that sweep (10 M rows: 2.65 ms at k = 10): they, and up to 16 queries, sweep on the
@@ -2850,14 +2809,7 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
                              (ix->search_mode == CSS_SEARCH_AUTO && (nq > 4 || k > 32 || ix->ntotal >= 100000)));
     const bool sweep_i8 = sweep_base && ix->x8 != nullptr && (nq <= sweep_max || mfma_sweep_ok) && sweep_uses_i8(ix);
     const bool sweep_path = sweep_base && ((mfma_sweep_ok && sweep_i8) || (nq <= sweep_max && (sweep_i8 || ix->xh != nullptr)));
-    // query prep: same row kernel as ingest (normalise, zero pad, squared norm)
-    if (!sweep_path) {
-        const int64_t blocks = (nq + 3) / 4;
-        hipLaunchKernelGGL(k_ingest_rows<false>, dim3((unsigned)blocks), dim3(256), 0, st, q_dev, ix->qpad,
-                           ix->qnorm2, nq, ix->dim, ix->dpad, normalize_q, 0ull, 0ll, (unsigned short*)nullptr,
-                           (int*)nullptr, ix->qerr2, (unsigned char*)nullptr, (float*)nullptr);
-        CSS_LAUNCH_CHECK();
-    }
+    if (!sweep_path && (rc = prep_queries(ix, q_dev, nq, normalize_q, ix->qerr2.p, st)) != CSS_OK) return rc;
     if (ix->ntotal == 0) {
         const int64_t n = nq * k;
         hipLaunchKernelGGL(k_fill_pad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, n,
@@ -2962,8 +2914,8 @@ int css_index_create(int dim, int metric, int device, css_index** out) {
         return css::hip_fail(e, "hipEventCreate", __FILE__, __LINE__);
     }
     e = hipEventCreateWithFlags(&ix->ingest_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void**)&ix->maxn2, 3 * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(ix->maxn2, 0, 3 * sizeof(int));
+    if (e == hipSuccess && !ix->maxn2.try_exact(3)) e = hipErrorOutOfMemory;
+    if (e == hipSuccess) e = hipMemset(ix->maxn2.p, 0, 3 * sizeof(int));
     // (null-stream memset vs the non-blocking streams every later launch uses: order it here, once)
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
@@ -2988,19 +2940,15 @@ int css_index_free(css_index* ix) {
             (void)hipEventDestroy(f->ev);
             (void)hipHostFree(f->h_nflag);
         }
-    void* ptrs[] = {ix->xb, ix->xnorm2, ix->xh, ix->x8, ix->x8s, ix->maxn2, ix->q_raw, ix->qpad, ix->qnorm2, ix->qerr2, ix->qerr2_i8, ix->qscale, ix->gthr, ix->qsplit,
-                    ix->part_s, ix->part_i, ix->out_i, ix->stage, ix->qh, ix->cthr, ix->cand_n,
-                    ix->cflags, ix->cand_s, ix->cand_i, ix->cpace, ix->fs_state, ix->mask_ws, ix->excl_ws, ix->fix_s, ix->fix_i, ix->fix_lock,
-                    ix->qh2, ix->thr2, ix->rs_work, ix->cand_n2, ix->cand_s2, ix->cand_i2, ix->flagB, ix->xh_tmp, ix->x8s_tmp, ix->rng_d, ix->rng_i,
-                    ix->compact_bits, ix->compact_pre, ix->range_cnt, ix->range_s, ix->range_i,
-                    ix->rowq, ix->rowq_flag, ix->rowq_d, ix->rowq_i, ix->rowq_ids};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);  // (hipFree waits for the device: nothing enqueued by a _dev call still runs)
+    // the row storage here, every workspace by its DevBuf in `delete ix` (hipFree waits for the device: nothing
+    // enqueued by a _dev call still runs)
+    for (void* p : {(void*)ix->xb, (void*)ix->xnorm2, (void*)ix->xh, (void*)ix->x8, (void*)ix->x8s})
+        if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
     if (ix->ingest_ev) (void)hipEventDestroy(ix->ingest_ev);
     if (ix->ws_ev) (void)hipEventDestroy(ix->ws_ev);
     (void)hipStreamDestroy(ix->stream);
-    delete ix;
+    delete ix;   // (inside the DeviceGuard: the DevBuf members free on the index's device)
     return CSS_OK;
 }
 
@@ -3013,7 +2961,7 @@ int css_index_reset(css_index* ix) {
     DeviceGuard g(ix->device);
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
     if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ws_ev, 0));   // a search enqueued on another stream still reads maxn2
-    CSS_HIP_TRY(hipMemsetAsync(ix->maxn2, 0, 3 * sizeof(int), ix->stream));
+    CSS_HIP_TRY(hipMemsetAsync(ix->maxn2.p, 0, 3 * sizeof(int), ix->stream));
     CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
     return CSS_OK;
 }
@@ -3030,7 +2978,7 @@ int compact_rows(css_index* ix, const uint32_t* keep, int64_t n, int64_t first, 
     for (int64_t c0 = 0; c0 < first; c0 += kCompactWindowRows) {
         const int64_t nc = std::min(kCompactWindowRows, first - c0);
         hipLaunchKernelGGL(k_rows_maxima, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, st, ix->xb + (size_t)c0 * dpad, nc, ix->dim,
-                           dpad, ix->maxn2);
+                           dpad, ix->maxn2.p);
         CSS_LAUNCH_CHECK();
     }
     // bounce rows: what 64 MiB hold, a whole number of keep words, never more than one launch covers
@@ -3039,16 +2987,8 @@ int compact_rows(css_index* ix, const uint32_t* keep, int64_t n, int64_t first, 
                                          (int64_t)((n - (first & ~31ll) + 31) / 32 * 32)});
     const int64_t words = (n + 31) / 32;
     const size_t need_words = (size_t)std::min<int64_t>(kCompactWords, words);
-    if (need_words > ix->compact_cap) {
-        if (ix->compact_bits) CSS_HIP_TRY(hipFree(ix->compact_bits));
-        if (ix->compact_pre) CSS_HIP_TRY(hipFree(ix->compact_pre));
-        ix->compact_bits = ix->compact_pre = nullptr;
-        ix->compact_cap = 0;
-        hipError_t e = hipMalloc((void**)&ix->compact_bits, need_words * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&ix->compact_pre, need_words * sizeof(uint32_t));
-        if (e != hipSuccess) return css::hip_fail(e, "hipMalloc(compaction bitmap)", __FILE__, __LINE__);
-        ix->compact_cap = need_words;
-    }
+    if ((rc = ix->compact_bits.grow_exact(need_words, "hipMalloc(compaction bitmap)")) != CSS_OK) return rc;
+    if ((rc = ix->compact_pre.grow_exact(need_words, "hipMalloc(compaction bitmap)")) != CSS_OK) return rc;
     const uint32_t tail_mask = (n & 31) ? ((1u << (n & 31)) - 1u) : 0xFFFFFFFFu;
     int64_t s0 = first & ~31ll;   // windows start on a keep word
     int64_t dnext = first;        // next free slot
@@ -3068,10 +3008,10 @@ int compact_rows(css_index* ix, const uint32_t* keep, int64_t n, int64_t first, 
             surv += __builtin_popcount(v);
         }
         if (surv > 0) {
-            CSS_HIP_TRY(hipMemcpyAsync(ix->compact_bits, keep + w0, (size_t)nw * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            CSS_HIP_TRY(hipMemcpyAsync(ix->compact_bits.p, keep + w0, (size_t)nw * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             if (w0 == (first >> 5))
-                CSS_HIP_TRY(hipMemcpyAsync(ix->compact_bits, patch, sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_keep_prefix, dim3(1), dim3(1024), 0, st, ix->compact_bits, ix->compact_pre, (int)nw);
+                CSS_HIP_TRY(hipMemcpyAsync(ix->compact_bits.p, patch, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_keep_prefix, dim3(1), dim3(1024), 0, st, ix->compact_bits.p, ix->compact_pre.p, (int)nw);
             CSS_LAUNCH_CHECK();
             const unsigned blocks = (unsigned)((L + 3) / 4);
             float* dst = ix->xb + (size_t)dnext * dpad;
@@ -3080,16 +3020,16 @@ int compact_rows(css_index* ix, const uint32_t* keep, int64_t n, int64_t first, 
             float* d8s = ix->x8 ? ix->x8s + dnext : nullptr;
             const float* src = ix->xb + (size_t)s0 * dpad;
             if (dnext + surv <= src0) {   // destinations wholly below the sources: straight into place
-                hipLaunchKernelGGL(k_compact_rows, dim3(blocks), dim3(256), 0, st, ix->compact_bits, ix->compact_pre, L, src, dst,
-                                   ix->xnorm2 + dnext, ix->dim, dpad, dh, ix->maxn2, d8, d8s);
+                hipLaunchKernelGGL(k_compact_rows, dim3(blocks), dim3(256), 0, st, ix->compact_bits.p, ix->compact_pre.p, L, src, dst,
+                                   ix->xnorm2 + dnext, ix->dim, dpad, dh, ix->maxn2.p, d8, d8s);
                 CSS_LAUNCH_CHECK();
             } else {                      // they overlap: through the scratch rows, the kernel boundary orders read and overwrite
-                if ((rc = grow(&ix->stage, &ix->stage_cap, (size_t)W * dpad)) != CSS_OK) return rc;
-                hipLaunchKernelGGL(k_compact_gather, dim3(blocks), dim3(256), 0, st, ix->compact_bits, ix->compact_pre, L, src,
-                                   ix->stage, dpad);
+                if ((rc = ix->stage.grow((size_t)W * dpad)) != CSS_OK) return rc;
+                hipLaunchKernelGGL(k_compact_gather, dim3(blocks), dim3(256), 0, st, ix->compact_bits.p, ix->compact_pre.p, L, src,
+                                   ix->stage.p, dpad);
                 CSS_LAUNCH_CHECK();
                 hipLaunchKernelGGL(k_compact_rows, dim3((unsigned)((surv + 3) / 4)), dim3(256), 0, st, (const uint32_t*)nullptr,
-                                   (const uint32_t*)nullptr, surv, ix->stage, dst, ix->xnorm2 + dnext, ix->dim, dpad, dh, ix->maxn2,
+                                   (const uint32_t*)nullptr, surv, ix->stage.p, dst, ix->xnorm2 + dnext, ix->dim, dpad, dh, ix->maxn2.p,
                                    d8, d8s);
                 CSS_LAUNCH_CHECK();
             }
@@ -3123,7 +3063,7 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
     // pending asynchronous adds, and searches on other streams that still read the rows and maxn2
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
     if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ws_ev, 0));
-    CSS_HIP_TRY(hipMemsetAsync(ix->maxn2, 0, 3 * sizeof(int), ix->stream));
+    CSS_HIP_TRY(hipMemsetAsync(ix->maxn2.p, 0, 3 * sizeof(int), ix->stream));
     uint32_t patch = 0;
     const int rc = kept > 0 ? compact_rows(ix, keep_bits_host, n, first, &patch) : CSS_OK;
     // later adds and searches on any stream are ordered behind the compaction (as css_index_reset)
@@ -3147,7 +3087,7 @@ int css_index_bounds(css_index* ix, float out[3]) {
     std::lock_guard<std::mutex> wl(ix->ws_mu);
     DeviceGuard g(ix->device);
     CSS_HIP_TRY(hipDeviceSynchronize());   // diagnostics: whichever stream the last add ran on
-    CSS_HIP_TRY(hipMemcpy(out, ix->maxn2, 3 * sizeof(float), hipMemcpyDeviceToHost));
+    CSS_HIP_TRY(hipMemcpy(out, ix->maxn2.p, 3 * sizeof(float), hipMemcpyDeviceToHost));
     return CSS_OK;
 }
 
@@ -3283,12 +3223,12 @@ int css_index_add(css_index* ix, const float* x_host, int64_t n, int normalize) 
     if (rc != CSS_OK) return rc;
     // stage through a bounded device buffer so huge adds do not double the footprint
     const int64_t chunk = std::max<int64_t>(1, (64ll << 20) / ((int64_t)ix->dim * 4));
-    if ((rc = grow(&ix->stage, &ix->stage_cap, (size_t)std::min(n, chunk) * ix->dim)) != CSS_OK) return rc;
+    if ((rc = ix->stage.grow((size_t)std::min(n, chunk) * ix->dim)) != CSS_OK) return rc;
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t m = std::min(chunk, n - r0);
-        CSS_HIP_TRY(hipMemcpyAsync(ix->stage, x_host + (size_t)r0 * ix->dim, (size_t)m * ix->dim * 4,
+        CSS_HIP_TRY(hipMemcpyAsync(ix->stage.p, x_host + (size_t)r0 * ix->dim, (size_t)m * ix->dim * 4,
                                    hipMemcpyHostToDevice, ix->stream));
-        if ((rc = ingest(ix, ix->stage, m, normalize, false, 0, 0, ix->stream)) != CSS_OK) return rc;
+        if ((rc = ingest(ix, ix->stage.p, m, normalize, false, 0, 0, ix->stream)) != CSS_OK) return rc;
         CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
         ix->ntotal += m;
         ix->ntotal_pub.store(ix->ntotal);
@@ -3365,6 +3305,36 @@ struct MaskScope {
     ~MaskScope() { ix->cur_mask = nullptr; }
 };
 
+// Host entry points, all on the index's own stream.  The caller's allow-bitmap (one bit per row; null or an empty
+// index: no mask) copied into mask_ws:
+int upload_allow_bits(css_index* ix, const uint32_t* bits_host, const uint32_t** mask_dev) {
+    *mask_dev = nullptr;
+    if (!bits_host || ix->ntotal == 0) return CSS_OK;
+    const size_t words = (size_t)((ix->ntotal + 31) / 32);
+    int rc;
+    if ((rc = ix->mask_ws.grow(words)) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(ix->mask_ws.p, bits_host, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+    *mask_dev = ix->mask_ws.p;
+    return CSS_OK;
+}
+
+// the device rows of a call's n = nq * k results in out_i: the ids at the front of the allocation, then their scores
+int reserve_out(css_index* ix, size_t n, float** d_out, int64_t** i_out) {
+    const int rc = ix->out_i.grow_exact(n * (sizeof(int64_t) + sizeof(float)), "hipMalloc(out_i)");
+    if (rc != CSS_OK) return rc;
+    *i_out = reinterpret_cast<int64_t*>(ix->out_i.p);
+    *d_out = reinterpret_cast<float*>(*i_out + n);
+    return CSS_OK;
+}
+
+// ... and back into the caller's D / I; everything on the stream has finished when this returns
+int fetch_out(css_index* ix, size_t n, const float* d_out, const int64_t* i_out, float* D_host, int64_t* I_host) {
+    CSS_HIP_TRY(hipMemcpyAsync(D_host, d_out, n * 4, hipMemcpyDeviceToHost, ix->stream));
+    CSS_HIP_TRY(hipMemcpyAsync(I_host, i_out, n * 8, hipMemcpyDeviceToHost, ix->stream));
+    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    return CSS_OK;
+}
+
 // Any k in [1, CSS_MAX_K].  Up to CSS_KERNEL_MAX_K: one search.  Beyond: per query, ceil(k / CSS_KERNEL_MAX_K) passes of
 // the SAME search paths, pass p over the allowed rows the passes before it did not return (exclusion bitmap), its
 // results written straight into columns [p * 128, ..) of the query's output row; the comparator is total (score, then
@@ -3381,21 +3351,22 @@ int search_any_k(css_index* ix, const float* q_dev, int64_t nq, int k, int norma
     CSS_REQUIRE(nq < (1 << 24), "css_index_search: nq=%lld out of range", (long long)nq);
     int rc;
     const int64_t words = (ix->ntotal + 31) / 32;
-    if (ix->ws_pending && ix->ws_stream != st) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ws_ev, 0));   // excl_ws is a shared workspace
-    if ((rc = grow(&ix->excl_ws, &ix->excl_ws_cap, (size_t)words)) != CSS_OK) return rc;
+    WsTurn turn(ix, st);   // excl_ws is a shared workspace, in use until the final sort is enqueued
+    if (turn.rc != CSS_OK) return turn.rc;
+    if ((rc = ix->excl_ws.grow((size_t)words)) != CSS_OK) return rc;
     for (int64_t q = 0; q < nq; ++q) {
-        hipLaunchKernelGGL(k_mask_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, ix->excl_ws, allow_dev, words);
+        hipLaunchKernelGGL(k_mask_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, ix->excl_ws.p, allow_dev, words);
         CSS_LAUNCH_CHECK();
         for (int p = 0; p < k; p += CSS_KERNEL_MAX_K) {
             const int kk = std::min(CSS_KERNEL_MAX_K, k - p);
             float* Dq = D_dev + (size_t)q * k + p;
             int64_t* Iq = I_dev + (size_t)q * k + p;
             {
-                MaskScope ms(ix, ix->excl_ws);
+                MaskScope ms(ix, ix->excl_ws.p);
                 if ((rc = search_dev_locked(ix, q_dev + (size_t)q * ix->dim, 1, kk, normalize_q, Dq, Iq, st)) != CSS_OK) return rc;
             }
             if (p + kk < k) {
-                hipLaunchKernelGGL(k_mask_clear, dim3(1), dim3(CSS_KERNEL_MAX_K), 0, st, ix->excl_ws, (const int64_t*)Iq, kk, ix->id_base);
+                hipLaunchKernelGGL(k_mask_clear, dim3(1), dim3(CSS_KERNEL_MAX_K), 0, st, ix->excl_ws.p, (const int64_t*)Iq, kk, ix->id_base);
                 CSS_LAUNCH_CHECK();
             }
         }
@@ -3403,10 +3374,6 @@ int search_any_k(css_index* ix, const float* q_dev, int64_t nq, int k, int norma
     if (ix->metric == CSS_METRIC_IP) hipLaunchKernelGGL(k_sort_rows<CSS_METRIC_IP>, dim3((unsigned)nq), dim3(1024), 0, st, D_dev, I_dev, k);
     else hipLaunchKernelGGL(k_sort_rows<CSS_METRIC_L2>, dim3((unsigned)nq), dim3(1024), 0, st, D_dev, I_dev, k);
     CSS_LAUNCH_CHECK();
-    if (hipEventRecord(ix->ws_ev, st) == hipSuccess) {   // (the exclusion bitmap is in use until here)
-        ix->ws_stream = st;
-        ix->ws_pending = true;
-    }
     return CSS_OK;
 }
 }  // namespace
@@ -3437,49 +3404,32 @@ int css_index_search_masked(css_index* ix, const float* q_host, int64_t nq, int 
     std::lock_guard<std::mutex> wl(ix->ws_mu);
     DeviceGuard g(ix->device);
     int rc;
-    if ((rc = grow(&ix->q_raw, &ix->q_raw_cap, (size_t)nq * ix->dim)) != CSS_OK) return rc;
-    {
-        size_t need = (size_t)nq * k;
-        if (need > ix->out_cap) {
-            if (ix->out_i) CSS_HIP_TRY(hipFree(ix->out_i));
-            ix->out_i = nullptr;
-            ix->out_cap = 0;
-            CSS_HIP_TRY(hipMalloc((void**)&ix->out_i, need * (sizeof(int64_t) + sizeof(float))));
-            ix->out_cap = need;
-        }
-    }
+    if ((rc = ix->q_raw.grow((size_t)nq * ix->dim)) != CSS_OK) return rc;
+    float* d_out;
+    int64_t* i_out;
+    if ((rc = reserve_out(ix, (size_t)nq * k, &d_out, &i_out)) != CSS_OK) return rc;
     const size_t q_bytes = (size_t)nq * ix->dim * 4, out_bytes = (size_t)nq * k * 12;
     const bool staged = q_bytes <= css_index::kHostStage && out_bytes <= css_index::kHostStage;
     if (staged && ix->h_stage == nullptr)
         CSS_HIP_TRY(hipHostMalloc((void**)&ix->h_stage, 2 * css_index::kHostStage, hipHostMallocDefault));
-    const uint32_t* mask_dev = nullptr;
-    if (allow_bits_host && ix->ntotal > 0) {
-        const size_t words = (size_t)((ix->ntotal + 31) / 32);
-        if ((rc = grow(&ix->mask_ws, &ix->mask_ws_cap, words)) != CSS_OK) return rc;
-        CSS_HIP_TRY(hipMemcpyAsync(ix->mask_ws, allow_bits_host, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
-        mask_dev = ix->mask_ws;
-    }
-    // (the output rows of THIS call sit at the front of the allocation: ids of nq * k entries, then their scores)
-    float* const d_out = reinterpret_cast<float*>(ix->out_i + (size_t)nq * k);
+    const uint32_t* mask_dev;
+    if ((rc = upload_allow_bits(ix, allow_bits_host, &mask_dev)) != CSS_OK) return rc;
     if (staged) {
         memcpy(ix->h_stage, q_host, q_bytes);
-        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw, ix->h_stage, q_bytes, hipMemcpyHostToDevice, ix->stream));
+        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, ix->h_stage, q_bytes, hipMemcpyHostToDevice, ix->stream));
     } else {
-        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw, q_host, q_bytes, hipMemcpyHostToDevice, ix->stream));
+        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, q_host, q_bytes, hipMemcpyHostToDevice, ix->stream));
     }
-    if ((rc = search_any_k(ix, ix->q_raw, nq, k, normalize_q, mask_dev, d_out, ix->out_i, ix->stream)) != CSS_OK) return rc;
+    if ((rc = search_any_k(ix, ix->q_raw.p, nq, k, normalize_q, mask_dev, d_out, i_out, ix->stream)) != CSS_OK) return rc;
     if (staged) {   // one copy into pinned memory, one wait
         char* back = ix->h_stage + css_index::kHostStage;
-        CSS_HIP_TRY(hipMemcpyAsync(back, ix->out_i, out_bytes, hipMemcpyDeviceToHost, ix->stream));
+        CSS_HIP_TRY(hipMemcpyAsync(back, i_out, out_bytes, hipMemcpyDeviceToHost, ix->stream));
         CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
         memcpy(I_host, back, (size_t)nq * k * 8);
         memcpy(D_host, back + (size_t)nq * k * 8, (size_t)nq * k * 4);
         return CSS_OK;
     }
-    CSS_HIP_TRY(hipMemcpyAsync(D_host, d_out, (size_t)nq * k * 4, hipMemcpyDeviceToHost, ix->stream));
-    CSS_HIP_TRY(hipMemcpyAsync(I_host, ix->out_i, (size_t)nq * k * 8, hipMemcpyDeviceToHost, ix->stream));
-    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
-    return CSS_OK;
+    return fetch_out(ix, (size_t)nq * k, d_out, i_out, D_host, I_host);
 }
 
 int css_index_search(css_index* ix, const float* q_host, int64_t nq, int k, int normalize_q, float* D_host,
@@ -3497,33 +3447,24 @@ int search_rows_enqueue(css_index* ix, const int64_t* ids_dev, int64_t nq, int k
                         const uint32_t* allow_dev, float* D_dev, int64_t* I_dev, hipStream_t st) {
     const int kk = k + (exclude_self ? 1 : 0);
     int rc;
-    // the previous search may still own the shared workspaces; rows appended on another stream must have landed
-    if (ix->ws_pending && ix->ws_stream != st) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ws_ev, 0));
+    WsTurn turn(ix, st);   // (until the end: whatever is launched uses the gathered rows)
+    if (turn.rc != CSS_OK) return turn.rc;
+    // rows appended on another stream must have landed
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
-    if ((rc = grow(&ix->rowq, &ix->rowq_cap, (size_t)nq * ix->dim)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->rowq_flag, &ix->rowq_flag_cap, (size_t)nq)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->rowq_d, &ix->rowq_d_cap, (size_t)nq * kk)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->rowq_i, &ix->rowq_i_cap, (size_t)nq * kk)) != CSS_OK) return rc;
+    if ((rc = ix->rowq.grow((size_t)nq * ix->dim)) != CSS_OK) return rc;
+    if ((rc = ix->rowq_flag.grow((size_t)nq)) != CSS_OK) return rc;
+    if ((rc = ix->rowq_d.grow((size_t)nq * kk)) != CSS_OK) return rc;
+    if ((rc = ix->rowq_i.grow((size_t)nq * kk)) != CSS_OK) return rc;
     const dim3 grid((unsigned)((nq + 3) / 4));
-    hipLaunchKernelGGL(k_gather_queries, grid, dim3(256), 0, st, (const float*)ix->xb, ids_dev, ix->rowq, ix->rowq_flag, nq,
+    hipLaunchKernelGGL(k_gather_queries, grid, dim3(256), 0, st, (const float*)ix->xb, ids_dev, ix->rowq.p, ix->rowq_flag.p, nq,
                        ix->ntotal, ix->id_base, ix->dim, ix->dpad);
     CSS_LAUNCH_CHECK();
-    rc = search_any_k(ix, ix->rowq, nq, kk, 0, allow_dev, ix->rowq_d, ix->rowq_i, st);
-    if (rc == CSS_OK) {
-        hipLaunchKernelGGL(k_drop_self, grid, dim3(256), 0, st, (const float*)ix->rowq_d, (const int64_t*)ix->rowq_i, ids_dev,
-                           (const int*)ix->rowq_flag, nq, kk, k, exclude_self ? 1 : 0,
-                           ix->metric == CSS_METRIC_IP ? -FLT_MAX : FLT_MAX, D_dev, I_dev);
-        CSS_LAUNCH_CHECK();
-    }
-    // (also after a failed search: whatever was launched still uses the gathered rows)
-    if (hipEventRecord(ix->ws_ev, st) == hipSuccess) {
-        ix->ws_stream = st;
-        ix->ws_pending = true;
-    } else {
-        (void)hipDeviceSynchronize();
-        ix->ws_pending = false;
-    }
-    return rc;
+    if ((rc = search_any_k(ix, ix->rowq.p, nq, kk, 0, allow_dev, ix->rowq_d.p, ix->rowq_i.p, st)) != CSS_OK) return rc;
+    hipLaunchKernelGGL(k_drop_self, grid, dim3(256), 0, st, (const float*)ix->rowq_d.p, (const int64_t*)ix->rowq_i.p, ids_dev,
+                       (const int*)ix->rowq_flag.p, nq, kk, k, exclude_self ? 1 : 0,
+                       ix->metric == CSS_METRIC_IP ? -FLT_MAX : FLT_MAX, D_dev, I_dev);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
 }
 
 int check_search_rows_k(int k, int exclude_self) {
@@ -3563,33 +3504,19 @@ int css_index_search_rows(css_index* ix, const int64_t* ids_host, int64_t nq, in
                     "css_index_search_rows: id %lld (query %lld) outside [%lld, %lld)", (long long)ids_host[j], (long long)j,
                     (long long)ix->id_base, (long long)(ix->id_base + ix->ntotal));
     DeviceGuard g(ix->device);
-    if ((rc = grow(&ix->rowq_ids, &ix->rowq_ids_cap, (size_t)nq)) != CSS_OK) return rc;
-    const size_t need = (size_t)nq * k;
-    if (need > ix->out_cap) {
-        if (ix->out_i) CSS_HIP_TRY(hipFree(ix->out_i));
-        ix->out_i = nullptr;
-        ix->out_cap = 0;
-        CSS_HIP_TRY(hipMalloc((void**)&ix->out_i, need * (sizeof(int64_t) + sizeof(float))));
-        ix->out_cap = need;
-    }
-    const uint32_t* mask_dev = nullptr;
-    if (allow_bits_host) {   // (ntotal > 0: an id passed the range check)
-        const size_t words = (size_t)((ix->ntotal + 31) / 32);
-        if ((rc = grow(&ix->mask_ws, &ix->mask_ws_cap, words)) != CSS_OK) return rc;
-        CSS_HIP_TRY(hipMemcpyAsync(ix->mask_ws, allow_bits_host, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
-        mask_dev = ix->mask_ws;
-    }
-    CSS_HIP_TRY(hipMemcpyAsync(ix->rowq_ids, ids_host, (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream));
-    float* const d_out = reinterpret_cast<float*>(ix->out_i + need);   // (layout of css_index_search_masked: ids, then scores)
-    rc = search_rows_enqueue(ix, ix->rowq_ids, nq, k, exclude_self, mask_dev, d_out, ix->out_i, ix->stream);
+    if ((rc = ix->rowq_ids.grow((size_t)nq)) != CSS_OK) return rc;
+    float* d_out;
+    int64_t* i_out;
+    if ((rc = reserve_out(ix, (size_t)nq * k, &d_out, &i_out)) != CSS_OK) return rc;
+    const uint32_t* mask_dev;
+    if ((rc = upload_allow_bits(ix, allow_bits_host, &mask_dev)) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(ix->rowq_ids.p, ids_host, (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream));
+    rc = search_rows_enqueue(ix, ix->rowq_ids.p, nq, k, exclude_self, mask_dev, d_out, i_out, ix->stream);
     if (rc != CSS_OK) {
         (void)hipStreamSynchronize(ix->stream);   // (the copies above read the caller's memory)
         return rc;
     }
-    CSS_HIP_TRY(hipMemcpyAsync(D_host, d_out, need * 4, hipMemcpyDeviceToHost, ix->stream));
-    CSS_HIP_TRY(hipMemcpyAsync(I_host, ix->out_i, need * 8, hipMemcpyDeviceToHost, ix->stream));
-    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
-    return CSS_OK;
+    return fetch_out(ix, (size_t)nq * k, d_out, i_out, D_host, I_host);
 }
 
 int css_merge_topk_dev(const float* Dp, const int64_t* Ip, int nparts, int64_t nq, int k, int metric, float* D,
@@ -3618,27 +3545,20 @@ struct css_range_result {
 };
 
 namespace {
-// Queries already on the device (ix->q_raw).  Caller holds ws_mu and a shared lock on mu; everything runs on the
+// Queries already on the device (ix->q_raw.p).  Caller holds ws_mu and a shared lock on mu; everything runs on the
 // index's own stream and has finished when this returns.
 int range_search_locked(css_index* ix, int64_t nq, float radius, int normalize_q, css_range_result* res) {
     hipStream_t st = ix->stream;
     int rc;
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
-    if ((rc = grow(&ix->qpad, &ix->qpad_cap, (size_t)(nq + 256) * ix->dpad)) != CSS_OK) return rc;
-    if ((rc = grow(&ix->qnorm2, &ix->qnorm2_cap, (size_t)nq + 256)) != CSS_OK) return rc;
-    if (!ix->range_cnt) {
-        hipError_t e = hipMalloc((void**)&ix->range_cnt, kRangeSlots * sizeof(unsigned int));
-        if (e != hipSuccess) return css::hip_fail(e, "hipMalloc(range counters)", __FILE__, __LINE__);
-    }
-    if (ix->range_cap == 0 && range_pool_alloc(ix, kRangeInitialCap) != CSS_OK) {
+    if ((rc = ix->qpad.grow((size_t)(nq + 256) * ix->dpad)) != CSS_OK) return rc;
+    if ((rc = ix->qnorm2.grow((size_t)nq + 256)) != CSS_OK) return rc;
+    if ((rc = ix->range_cnt.grow_exact(kRangeSlots, "hipMalloc(range counters)")) != CSS_OK) return rc;
+    if (ix->range_cap() == 0 && range_pool_alloc(ix, kRangeInitialCap) != CSS_OK) {
         css::set_error("css_index_range_search: no device memory for the initial hit pool");
         return CSS_ERR_OOM;
     }
-    // query prep: the row kernel of ingest (normalise, zero pad), as every search
-    hipLaunchKernelGGL(k_ingest_rows<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, ix->q_raw, ix->qpad, ix->qnorm2, nq,
-                       ix->dim, ix->dpad, normalize_q, 0ull, 0ll, (unsigned short*)nullptr, (int*)nullptr, (float*)nullptr,
-                       (unsigned char*)nullptr, (float*)nullptr);
-    CSS_LAUNCH_CHECK();
+    if ((rc = prep_queries(ix, ix->q_raw.p, nq, normalize_q, nullptr, st)) != CSS_OK) return rc;
     const int nq_sweep = range_nq_sweep(ix);
     const bool ip = ix->metric == CSS_METRIC_IP;
     std::vector<float> hs;
@@ -3647,14 +3567,14 @@ int range_search_locked(css_index* ix, int64_t nq, float radius, int normalize_q
     unsigned int cnt[kRangeSlots];
     for (int64_t q0 = 0; q0 < nq; q0 += nq_sweep) {
         const int nqc = (int)std::min<int64_t>(nq_sweep, nq - q0);
-        const float* qp = ix->qpad + (size_t)q0 * ix->dpad;
+        const float* qp = ix->qpad.p + (size_t)q0 * ix->dpad;
         if ((rc = range_sweep(ix, qp, nqc, radius, cnt, st)) != CSS_OK) return rc;
         size_t most = 0, total = 0;
         for (int j = 0; j < nqc; ++j) {
             most = std::max<size_t>(most, cnt[j]);
             total += cnt[j];
         }
-        if (most > ix->range_cap) {
+        if (most > ix->range_cap()) {
             // the sweep counted every hit: grow to that size and sweep ONCE more (never a loop)
             if (range_pool_alloc(ix, most) != CSS_OK) {
                 css::set_error("css_index_range_search: no device memory for the hit pool: %zu hits for one query "
@@ -3663,7 +3583,7 @@ int range_search_locked(css_index* ix, int64_t nq, float radius, int normalize_q
             }
             if ((rc = range_sweep(ix, qp, nqc, radius, cnt, st)) != CSS_OK) return rc;
             for (int j = 0; j < nqc; ++j)
-                if (cnt[j] > ix->range_cap) {   // (rows and mask cannot change under the locks held)
+                if (cnt[j] > ix->range_cap()) {   // (rows and mask cannot change under the locks held)
                     css::set_error("css_index_range_search: internal: the second sweep counted more hits than the first");
                     return CSS_ERR_STATE;
                 }
@@ -3679,8 +3599,8 @@ int range_search_locked(css_index* ix, int64_t nq, float radius, int normalize_q
                 hi.resize(c);
                 order.resize(c);
                 if (c) {
-                    CSS_HIP_TRY(hipMemcpyAsync(hs.data(), ix->range_s + (size_t)j * ix->range_cap, c * sizeof(float), hipMemcpyDeviceToHost, st));
-                    CSS_HIP_TRY(hipMemcpyAsync(hi.data(), ix->range_i + (size_t)j * ix->range_cap, c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                    CSS_HIP_TRY(hipMemcpyAsync(hs.data(), ix->range_s.p + (size_t)j * ix->range_cap(), c * sizeof(float), hipMemcpyDeviceToHost, st));
+                    CSS_HIP_TRY(hipMemcpyAsync(hi.data(), ix->range_i.p + (size_t)j * ix->range_cap(), c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
                     CSS_HIP_TRY(hipStreamSynchronize(st));
                 }
                 // the defined order, formed here on the host: best score first, equal scores by ascending id
@@ -3736,28 +3656,14 @@ int css_index_range_search(css_index* ix, const float* q_host, int64_t nq, float
                 CSS_REQUIRE(ix->ntotal < 0xFFFFFFFFll, "css_index_range_search: %lld rows exceed the 32-bit row numbers of the hit pool",
                             (long long)ix->ntotal);
                 int r;
-                // the previous search may still be running on another stream and owns the shared workspaces until its event
-                if (ix->ws_pending && ix->ws_stream != ix->stream) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ws_ev, 0));
-                if ((r = grow(&ix->q_raw, &ix->q_raw_cap, (size_t)nq * ix->dim)) != CSS_OK) return r;
-                const uint32_t* mask_dev = nullptr;
-                if (allow_bits_host) {
-                    const size_t words = (size_t)((ix->ntotal + 31) / 32);
-                    if ((r = grow(&ix->mask_ws, &ix->mask_ws_cap, words)) != CSS_OK) return r;
-                    CSS_HIP_TRY(hipMemcpyAsync(ix->mask_ws, allow_bits_host, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
-                    mask_dev = ix->mask_ws;
-                }
-                CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw, q_host, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream));
+                WsTurn turn(ix, ix->stream);
+                if (turn.rc != CSS_OK) return turn.rc;
+                if ((r = ix->q_raw.grow((size_t)nq * ix->dim)) != CSS_OK) return r;
+                const uint32_t* mask_dev;
+                if ((r = upload_allow_bits(ix, allow_bits_host, &mask_dev)) != CSS_OK) return r;
+                CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, q_host, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream));
                 MaskScope ms(ix, mask_dev);
-                r = range_search_locked(ix, nq, radius, normalize_q, res);
-                // (also after a failure: whatever was launched before the error still uses the workspaces)
-                if (hipEventRecord(ix->ws_ev, ix->stream) == hipSuccess) {
-                    ix->ws_stream = ix->stream;
-                    ix->ws_pending = true;
-                } else {
-                    (void)hipDeviceSynchronize();
-                    ix->ws_pending = false;
-                }
-                return r;
+                return range_search_locked(ix, nq, radius, normalize_q, res);
             }();
         }
     }

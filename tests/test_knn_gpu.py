@@ -1062,6 +1062,69 @@ def test_searches_of_one_index_on_two_streams_do_not_share_workspaces_concurrent
     ix.close()
 
 
+def test_mixed_entry_points_on_different_streams_take_turns_at_the_workspaces():
+    """The hand-over of the shared workspaces is one scope (WsTurn) behind EVERY entry point, so the mix is tested,
+    not only search_dev against search_dev: a 300-query search_dev on stream 1, a 37-anchor search_by_ids_dev on
+    stream 2 (its gathered rows, then the same cascade), a host range_search (exact sweep + hit pool, index stream)
+    and a host search with k = 200 (two passes per query and the exclusion bitmap, index stream), enqueued back to
+    back for four rounds without a wait between the device calls, must return what each returned alone, bit for
+    bit.  1 M x 256 rows, chosen so that the 300-query batch is still running when the next call is enqueued; its
+    duration (knn_coarse_cascade scope) has NOT been measured on an MI355X yet: if it turns out under ~0.3 ms, raise
+    the row count (at most the 1.5 M x 768 of the test above)."""
+    import torch
+
+    from claude_semantic_search_amd.flat_index import IndexFlatIP
+
+    n, d, k = 1_000_000, 256, 10
+    ix = IndexFlatIP(d)
+    ix.reserve(n)
+    ix.add_synthetic(n, seed=71, first_row=0, normalize=True)
+    dev = torch.device("cuda:0")
+    qa = torch.from_numpy(synth.rows(300, d, 72)).to(dev)
+    ids = torch.arange(37, dtype=torch.int64, device=dev) * 27011 + 5
+    qr = synth.rows(3, d, 73)
+    qk = synth.rows(2, d, 74)
+    radius = 0.215   # scores of unit rows are ~N(0, 1/256): 3.44 sigma, ~300 of 1 M rows per query
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+
+    def out(nq):
+        return (torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int64, device=dev))
+
+    def run_a():
+        D, I = out(300)
+        ix.search_dev(qa.data_ptr(), 300, k, D.data_ptr(), I.data_ptr(), stream=s1.cuda_stream, normalize=True)
+        return D, I
+
+    def run_b():
+        D, I = out(37)
+        ix.search_by_ids_dev(ids.data_ptr(), 37, k, D.data_ptr(), I.data_ptr(), stream=s2.cuda_stream)
+        return D, I
+
+    torch.cuda.synchronize()
+    Da, Ia = run_a()
+    torch.cuda.synchronize()
+    Db, Ib = run_b()
+    torch.cuda.synchronize()
+    lims, Dr, Ir = ix.range_search(qr, radius, normalize=True)
+    torch.cuda.synchronize()
+    Dk, Ik = ix.search(qk, 200, normalize=True)
+    torch.cuda.synchronize()
+    hits = np.diff(lims)
+    assert hits.min() >= 50 and hits.max() <= 2000, hits   # the radius does what the comment says
+    assert torch.equal(Ib[:, 0] == ids, torch.zeros(37, dtype=torch.bool, device=dev)) and int(Ib.min()) >= 0
+    for _ in range(4):
+        Da2, Ia2 = run_a()
+        Db2, Ib2 = run_b()
+        lims2, Dr2, Ir2 = ix.range_search(qr, radius, normalize=True)
+        Dk2, Ik2 = ix.search(qk, 200, normalize=True)
+        torch.cuda.synchronize()
+        assert torch.equal(Ia, Ia2) and torch.equal(Da, Da2)
+        assert torch.equal(Ib, Ib2) and torch.equal(Db, Db2)
+        assert np.array_equal(lims, lims2) and np.array_equal(Ir, Ir2) and np.array_equal(Dr, Dr2)
+        assert np.array_equal(Ik, Ik2) and np.array_equal(Dk, Dk2)
+    ix.close()
+
+
 def test_two_host_threads_search_own_and_shared_indexes(tmp_path):
     """The concurrency contract of css_hip.h through the C ABI without Python in the way: tests/native/cabi_threads.cc
     (the driver of the CPU sanitizer builds, tests/test_cabi_sanitizers.py) linked against the product library; two
