@@ -4,6 +4,7 @@
 #include "css_common.h"
 
 #include <algorithm>
+#include <utility>
 
 namespace css {
 
@@ -34,6 +35,10 @@ struct DevBuf {
         p = nullptr;
         cap = 0;
         return old;
+    }
+    void swap(DevBuf& o) {   // (the row storage: built in locals, swapped in whole)
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
     }
     int grow(size_t need, const char* what = "hipMalloc(workspace)") {
         return need <= cap ? CSS_OK : alloc(std::max(need, cap * 2), what);

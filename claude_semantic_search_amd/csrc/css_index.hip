@@ -31,8 +31,10 @@
 //   k_gather_queries,  css_index_search_rows: stored rows copied into a query buffer in front of the ordinary
 //   k_drop_self        search for k + 1, and the anchor compacted out of its results behind it (a wave per query)
 //
-// Host plumbing, one place per rule: every workspace is a DevBuf (css_devbuf.h: owning, freed with the index, one of
-// three growth policies); WsTurn is a search's turn at the shared workspaces (wait for the previous stream's event,
+// Host plumbing, one place per rule: the row storage and every workspace are DevBufs (css_devbuf.h: owning, freed with
+// the index, one of three growth policies); a search reads the rows through a Rows value taken under the shared lock
+// (rows_of; a row range is Rows::range) and nothing under the shared lock writes a row field of css_index; WsTurn is a
+// search's turn at the shared workspaces (wait for the previous stream's event,
 // record at the end); prep_queries, upload_allow_bits, reserve_out / fetch_out are the query preparation, the mask
 // upload and the result staging of every entry point; sweep_grid is the grid of both exact sweeps.  The sweep body of
 // k_scan_small and k_range_small is deliberately NOT shared (css_knn_range.h says why).
@@ -57,24 +59,24 @@ using namespace css;
 
 struct css_index {
     int dim = 0, dpad = 0, metric = 0, device = 0;
-    int64_t ntotal = 0, cap = 0, id_base = 0;
-    // what css_index_ntotal reports: searches of shadow-less indexes temporarily narrow xb / xnorm2 / ntotal / id_base
-    // to a row range (RowView, under ws_mu), and a concurrent reader must not see that
+    int64_t ntotal = 0, cap = 0, id_base = 0;   // cap: rows the storage below holds (the DevBuf caps are in elements)
+    // a mirror of ntotal that css_index_ntotal reads without a lock (it must not wait behind a long add): set_ntotal
+    // is the one place that writes the two
     std::atomic<int64_t> ntotal_pub{0};
-    float* xb = nullptr;
-    float* xnorm2 = nullptr;
-    unsigned short* xh = nullptr;  // bf16 shadow rows [cap][dpad] for the coarse scan (nullptr: not kept)
+    // row storage: written and reallocated under the exclusive lock on mu only; a search reads it through a Rows value
+    DevBuf<float> xb;              // [cap][dpad]
+    DevBuf<float> xnorm2;          // [cap + 256]
+    DevBuf<unsigned short> xh;     // bf16 shadow rows [cap + 256][dpad] for the coarse scan (empty: not kept)
     int shadow = -1;               // -1 undecided, 0 off, 1 on (CSS_KNN_SHADOW, HBM headroom)
     int shadow_policy = -1;        // css_index_set_shadow: -1 automatic, 0 never, 1 always
     int search_mode = CSS_SEARCH_AUTO;
-    const uint32_t* cur_mask = nullptr;  // allow-bitmap of the search in progress (set under ws_mu)
     DevBuf<uint32_t> mask_ws;      // device copy of a host bitmap (upload_allow_bits)
     DevBuf<uint32_t> excl_ws;      // k > 128: allow-bitmap minus the rows earlier passes returned
     DevBuf<int> maxn2;             // device, 3 words: bits of max ||row||^2, max ||row - bf16(row)||^2, max ||row - int8(row)||^2 (cz_eps)
     // int8 shadow rows (kept next to the bf16 ones when there is room): signed byte = round(x / s), s = max|x| / 127 per
     // row; read by the 1..4-query sweep and by the int8 MFMA scan of batches
-    unsigned char* x8 = nullptr;
-    float* x8s = nullptr;
+    DevBuf<unsigned char> x8;      // [cap + 256][dpad]
+    DevBuf<float> x8s;             // [cap + 256]
     hipStream_t stream = nullptr;
     int num_cus = 256;
     // reusable workspaces (DevBuf: grown on demand, freed with the index; guarded by ws_mu)
@@ -161,6 +163,35 @@ struct css_index {
 };
 
 namespace {
+
+// What a search reads of the rows, as a value: taken once per entry point under the shared lock on mu (rows_of),
+// handed down to every launcher next to `ix`, never written back.  mask: the device allow-bitmap of the call, one
+// bit per row (null: every row allowed).
+struct Rows {
+    const float* xb;
+    const float* xnorm2;
+    const unsigned short* xh;
+    const unsigned char* x8;
+    const float* x8s;
+    int64_t n, id_base;
+    const uint32_t* mask;
+    // rows [row0, row0 + cnt) as rows of their own, with the range's bf16 OR int8 scratch rows as their shadow (the
+    // other kind null): search_noshadow_ranges
+    Rows range(int64_t row0, int64_t cnt, int dpad, const unsigned short* xh_rows, const unsigned char* x8_rows,
+               const float* x8_scales) const {
+        return Rows{xb + (size_t)row0 * dpad, xnorm2 + row0, xh_rows, x8_rows, x8_scales, cnt, id_base + row0,
+                    mask ? mask + row0 / 32 : nullptr};   // (row0 is a multiple of 256)
+    }
+};
+// the one place that reads the row fields of the index for a search; caller holds mu (shared is enough)
+Rows rows_of(const css_index* ix, const uint32_t* mask = nullptr) {
+    return Rows{ix->xb.p, ix->xnorm2.p, ix->xh.p, ix->x8.p, ix->x8s.p, ix->ntotal, ix->id_base, mask};
+}
+// caller holds mu exclusively
+void set_ntotal(css_index* ix, int64_t n) {
+    ix->ntotal = n;
+    ix->ntotal_pub.store(n);
+}
 
 constexpr int kWaves = 4;  // waves per block in the scan kernels
 
@@ -1585,7 +1616,7 @@ bool want_i8_only(css_index* ix, int64_t ncap) {
 }
 
 // (Re)allocate the row storage for exactly ncap rows, carrying the ntotal existing rows over.  The new arrays are
-// owned here until the swap at the end: whatever returns early frees them.
+// owned here until the swap at the end (whatever returns early frees them), the old ones from there on.
 int reallocate_rows(css_index* ix, int64_t ncap) {
     DevBuf<float> nxb, nn2, nx8s;
     DevBuf<unsigned short> nxh;
@@ -1595,13 +1626,13 @@ int reallocate_rows(css_index* ix, int64_t ncap) {
     // +256: the coarse scan reads whole tiles of norms
     if ((rc = nn2.grow_exact((size_t)ncap + 256, "hipMalloc(index norms)")) != CSS_OK) return rc;
     // the shadow can only be carried over (or started on an empty index), never rebuilt here
-    const bool can_shadow = ix->xh != nullptr || ix->ntotal == 0;
+    const bool can_shadow = ix->xh.p != nullptr || ix->ntotal == 0;
     // (+256 rows: k_scan_coarse8 reads whole 256-row tiles; scores of rows >= ntotal are masked)
     // no room: batched search falls back to the split-operand kernel
     if (can_shadow && want_shadow(ix, ncap)) (void)nxh.try_exact(((size_t)ncap + 256) * ix->dpad);
     // the int8 rows of the few-query sweep ride along with the bf16 ones when 7 bytes per element still fit
-    const bool i8_only = !nxh.p && ((ix->x8 != nullptr && ix->xh == nullptr) || ix->ntotal == 0) && want_i8_only(ix, ncap);
-    if ((nxh.p && (ix->x8 != nullptr || ix->ntotal == 0) && want_i8(ix, ncap)) || i8_only) {
+    const bool i8_only = !nxh.p && ((ix->x8.p != nullptr && ix->xh.p == nullptr) || ix->ntotal == 0) && want_i8_only(ix, ncap);
+    if ((nxh.p && (ix->x8.p != nullptr || ix->ntotal == 0) && want_i8(ix, ncap)) || i8_only) {
         if (!nx8.try_exact(((size_t)ncap + 256) * ix->dpad) || !nx8s.try_exact((size_t)ncap + 256)) {
             (void)nx8.drop();
             (void)nx8s.drop();
@@ -1610,29 +1641,24 @@ int reallocate_rows(css_index* ix, int64_t ncap) {
     if (ix->ntotal > 0) {
         if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
         if (nx8.p) {
-            CSS_HIP_TRY(hipMemcpyAsync(nx8.p, ix->x8, (size_t)ix->ntotal * ix->dpad, hipMemcpyDeviceToDevice, ix->stream));
-            CSS_HIP_TRY(hipMemcpyAsync(nx8s.p, ix->x8s, (size_t)ix->ntotal * sizeof(float), hipMemcpyDeviceToDevice, ix->stream));
+            CSS_HIP_TRY(hipMemcpyAsync(nx8.p, ix->x8.p, (size_t)ix->ntotal * ix->dpad, hipMemcpyDeviceToDevice, ix->stream));
+            CSS_HIP_TRY(hipMemcpyAsync(nx8s.p, ix->x8s.p, (size_t)ix->ntotal * sizeof(float), hipMemcpyDeviceToDevice, ix->stream));
         }
-        CSS_HIP_TRY(hipMemcpyAsync(nxb.p, ix->xb, (size_t)ix->ntotal * ix->dpad * sizeof(float),
+        CSS_HIP_TRY(hipMemcpyAsync(nxb.p, ix->xb.p, (size_t)ix->ntotal * ix->dpad * sizeof(float),
                                    hipMemcpyDeviceToDevice, ix->stream));
-        CSS_HIP_TRY(hipMemcpyAsync(nn2.p, ix->xnorm2, (size_t)ix->ntotal * sizeof(float), hipMemcpyDeviceToDevice,
+        CSS_HIP_TRY(hipMemcpyAsync(nn2.p, ix->xnorm2.p, (size_t)ix->ntotal * sizeof(float), hipMemcpyDeviceToDevice,
                                    ix->stream));
         if (nxh.p)
-            CSS_HIP_TRY(hipMemcpyAsync(nxh.p, ix->xh, (size_t)ix->ntotal * ix->dpad * sizeof(unsigned short),
+            CSS_HIP_TRY(hipMemcpyAsync(nxh.p, ix->xh.p, (size_t)ix->ntotal * ix->dpad * sizeof(unsigned short),
                                        hipMemcpyDeviceToDevice, ix->stream));
         CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
     }
-    if (ix->xb) CSS_HIP_TRY(hipFree(ix->xb));
-    if (ix->xnorm2) CSS_HIP_TRY(hipFree(ix->xnorm2));
-    if (ix->xh) CSS_HIP_TRY(hipFree(ix->xh));
-    if (ix->x8) CSS_HIP_TRY(hipFree(ix->x8));
-    if (ix->x8s) CSS_HIP_TRY(hipFree(ix->x8s));
-    ix->xb = nxb.release();
-    ix->xnorm2 = nn2.release();
-    ix->xh = nxh.release();
-    ix->x8 = nx8.release();
-    ix->x8s = nx8s.release();
-    ix->shadow = ix->xh ? 1 : 0;
+    ix->xb.swap(nxb);
+    ix->xnorm2.swap(nn2);
+    ix->xh.swap(nxh);
+    ix->x8.swap(nx8);
+    ix->x8s.swap(nx8s);
+    ix->shadow = ix->xh.p ? 1 : 0;
     ix->cap = ncap;
     return CSS_OK;
 }
@@ -1642,20 +1668,14 @@ int ensure_capacity(css_index* ix, int64_t need) {
         int64_t ncap = std::max<int64_t>(need, ix->cap + ix->cap / 2);
         return reallocate_rows(ix, std::max<int64_t>(ncap, 1024));
     }
-    if (ix->ntotal == 0 && !ix->xh && ix->shadow < 0 && ix->cap > 0 && want_shadow(ix, ix->cap)) {
+    if (ix->ntotal == 0 && !ix->xh.p && ix->shadow < 0 && ix->cap > 0 && want_shadow(ix, ix->cap)) {
         // emptied index (css_index_reset): start a shadow again if there is room now
-        if (hipMalloc((void**)&ix->xh, ((size_t)ix->cap + 256) * ix->dpad * sizeof(unsigned short)) != hipSuccess) {
-            (void)hipGetLastError();
-            ix->xh = nullptr;
-        }
-        ix->shadow = ix->xh ? 1 : 0;
-        if (ix->xh && !ix->x8 && want_i8(ix, ix->cap)) {
-            if (hipMalloc((void**)&ix->x8, ((size_t)ix->cap + 256) * ix->dpad) != hipSuccess ||
-                hipMalloc((void**)&ix->x8s, ((size_t)ix->cap + 256) * sizeof(float)) != hipSuccess) {
-                (void)hipGetLastError();
-                if (ix->x8) (void)hipFree(ix->x8);
-                ix->x8 = nullptr;
-                ix->x8s = nullptr;
+        (void)ix->xh.try_exact(((size_t)ix->cap + 256) * ix->dpad);
+        ix->shadow = ix->xh.p ? 1 : 0;
+        if (ix->xh.p && !ix->x8.p && want_i8(ix, ix->cap)) {   // (the int8 pair whole or not at all, as reallocate_rows)
+            if (!ix->x8.try_exact(((size_t)ix->cap + 256) * ix->dpad) || !ix->x8s.try_exact((size_t)ix->cap + 256)) {
+                (void)ix->x8.drop();
+                (void)ix->x8s.drop();
             }
         }
     }
@@ -1672,11 +1692,11 @@ int ingest(css_index* ix, const float* x_dev, int64_t n, int normalize, bool syn
         const int64_t nc = std::min<int64_t>(kRowsPerLaunch, n - c0);
         const int64_t r0 = ix->ntotal + c0;
         const unsigned blocks = (unsigned)((nc + 3) / 4);
-        float* dst = ix->xb + (size_t)r0 * ix->dpad;
-        float* n2 = ix->xnorm2 + r0;
-        unsigned short* dh = ix->xh ? ix->xh + (size_t)r0 * ix->dpad : nullptr;
-        unsigned char* d8 = ix->x8 ? ix->x8 + (size_t)r0 * ix->dpad : nullptr;
-        float* d8s = ix->x8 ? ix->x8s + r0 : nullptr;
+        float* dst = ix->xb.p + (size_t)r0 * ix->dpad;
+        float* n2 = ix->xnorm2.p + r0;
+        unsigned short* dh = ix->xh.p ? ix->xh.p + (size_t)r0 * ix->dpad : nullptr;
+        unsigned char* d8 = ix->x8.p ? ix->x8.p + (size_t)r0 * ix->dpad : nullptr;
+        float* d8s = ix->x8.p ? ix->x8s.p + r0 : nullptr;
         if (synth)
             hipLaunchKernelGGL(k_ingest_rows<true>, dim3(blocks), dim3(256), 0, st, nullptr, dst, n2, nc, ix->dim, ix->dpad,
                                normalize, seed, first_row + c0, dh, ix->maxn2.p, (float*)nullptr, d8, d8s);
@@ -1742,7 +1762,7 @@ struct FixArgs {
 };
 
 template <int NQ, int TT, int METRIC, bool FIX>
-int launch_scan_small_t(css_index* ix, const float* qpad, int nq_real, int k, int* gthr, const SweepGeom& sg,
+int launch_scan_small_t(css_index* ix, const Rows& rows, const float* qpad, int nq_real, int k, int* gthr, const SweepGeom& sg,
                         hipStream_t st, const FixArgs& fx) {
     const int T = ix->dpad / 64;
     const size_t lds = (size_t)NQ * ix->dpad * 4 + (size_t)NQ * k * 8 + NQ * 8 + (FIX ? (size_t)4 * k * 8 : 0);
@@ -1750,22 +1770,22 @@ int launch_scan_small_t(css_index* ix, const float* qpad, int nq_real, int k, in
     int rc;
     if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
     ProfScope ps(FIX ? "knn_fix_scan" : "knn_scan_small", st);
-    hipLaunchKernelGGL(kern, dim3(sg.G), dim3(256), lds, st, (const float4*)ix->xb, qpad, ix->ntotal, T, k, sg.gpb, gthr,
-                       ix->part_s.p, ix->part_i.p, nq_real, ix->cur_mask, fx.flag_list, fx.nflag, fx.fix_s, fx.fix_i, fx.fix_lock,
-                       FIX ? const_cast<int*>(fx.nflag) + 1 : (int*)nullptr, ix->id_base, fx.D, fx.I);
+    hipLaunchKernelGGL(kern, dim3(sg.G), dim3(256), lds, st, (const float4*)rows.xb, qpad, rows.n, T, k, sg.gpb, gthr,
+                       ix->part_s.p, ix->part_i.p, nq_real, rows.mask, fx.flag_list, fx.nflag, fx.fix_s, fx.fix_i, fx.fix_lock,
+                       FIX ? const_cast<int*>(fx.nflag) + 1 : (int*)nullptr, rows.id_base, fx.D, fx.I);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 
 template <int NQ, bool FIX>
-int launch_scan_small_nq(css_index* ix, const float* qpad, int nq_real, int k, int* gthr, const SweepGeom& sg,
+int launch_scan_small_nq(css_index* ix, const Rows& rows, const float* qpad, int nq_real, int k, int* gthr, const SweepGeom& sg,
                          hipStream_t st, const FixArgs& fx = FixArgs()) {
     const bool ip = ix->metric == CSS_METRIC_IP;
     if (ix->dpad == 768)
-        return ip ? launch_scan_small_t<NQ, 12, CSS_METRIC_IP, FIX>(ix, qpad, nq_real, k, gthr, sg, st, fx)
-                  : launch_scan_small_t<NQ, 12, CSS_METRIC_L2, FIX>(ix, qpad, nq_real, k, gthr, sg, st, fx);
-    return ip ? launch_scan_small_t<NQ, 0, CSS_METRIC_IP, FIX>(ix, qpad, nq_real, k, gthr, sg, st, fx)
-              : launch_scan_small_t<NQ, 0, CSS_METRIC_L2, FIX>(ix, qpad, nq_real, k, gthr, sg, st, fx);
+        return ip ? launch_scan_small_t<NQ, 12, CSS_METRIC_IP, FIX>(ix, rows, qpad, nq_real, k, gthr, sg, st, fx)
+                  : launch_scan_small_t<NQ, 12, CSS_METRIC_L2, FIX>(ix, rows, qpad, nq_real, k, gthr, sg, st, fx);
+    return ip ? launch_scan_small_t<NQ, 0, CSS_METRIC_IP, FIX>(ix, rows, qpad, nq_real, k, gthr, sg, st, fx)
+              : launch_scan_small_t<NQ, 0, CSS_METRIC_L2, FIX>(ix, rows, qpad, nq_real, k, gthr, sg, st, fx);
 }
 
 // the per-block top-k lists of the exact scans: [q][block][k] scores and rows
@@ -1781,28 +1801,28 @@ inline int host_f2key(float f) {
 }
 
 // Queries [q0, q0+nqc) (nqc <= 16) against the whole index, results to D/I rows q0...
-int search_chunk_small(css_index* ix, int q0, int nqc, int k, const SweepGeom& sg, float* D_dev, int64_t* I_dev,
-                       hipStream_t st) {
+int search_chunk_small(css_index* ix, const Rows& rows, int q0, int nqc, int k, const SweepGeom& sg, float* D_dev,
+                       int64_t* I_dev, hipStream_t st) {
     int* gthr = ix->gthr.p + q0;
     hipLaunchKernelGGL(k_fill_int, dim3(1), dim3(64), 0, st, gthr, nqc, host_f2key(-INFINITY));
     CSS_LAUNCH_CHECK();
     const float* qp = ix->qpad.p + (size_t)q0 * ix->dpad;
     int rc;
-    if (nqc <= 1) rc = launch_scan_small_nq<1, false>(ix, qp, nqc, k, gthr, sg, st);
-    else if (nqc <= 2) rc = launch_scan_small_nq<2, false>(ix, qp, nqc, k, gthr, sg, st);
+    if (nqc <= 1) rc = launch_scan_small_nq<1, false>(ix, rows, qp, nqc, k, gthr, sg, st);
+    else if (nqc <= 2) rc = launch_scan_small_nq<2, false>(ix, rows, qp, nqc, k, gthr, sg, st);
     else if (nqc <= 8)  // (an NQ=4 instantiation spills under hipcc 7.2; 3..8 share NQ=8)
-         rc = launch_scan_small_nq<8, false>(ix, qp, nqc, k, gthr, sg, st);
-    else rc = launch_scan_small_nq<16, false>(ix, qp, nqc, k, gthr, sg, st);
+         rc = launch_scan_small_nq<8, false>(ix, rows, qp, nqc, k, gthr, sg, st);
+    else rc = launch_scan_small_nq<16, false>(ix, rows, qp, nqc, k, gthr, sg, st);
     if (rc != CSS_OK) return rc;
     {
         ProfScope ps("knn_merge", st);
         if (ix->metric == CSS_METRIC_IP)
             hipLaunchKernelGGL(k_merge_final<CSS_METRIC_IP>, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G,
-                               k, gthr, ix->qnorm2.p + q0, ix->id_base, D_dev + (size_t)q0 * k,
+                               k, gthr, ix->qnorm2.p + q0, rows.id_base, D_dev + (size_t)q0 * k,
                                I_dev + (size_t)q0 * k, 0, (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
         else
             hipLaunchKernelGGL(k_merge_final<CSS_METRIC_L2>, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G,
-                               k, gthr, ix->qnorm2.p + q0, ix->id_base, D_dev + (size_t)q0 * k,
+                               k, gthr, ix->qnorm2.p + q0, rows.id_base, D_dev + (size_t)q0 * k,
                                I_dev + (size_t)q0 * k, 0, (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
         CSS_LAUNCH_CHECK();
     }
@@ -1813,12 +1833,12 @@ int search_chunk_small(css_index* ix, int q0, int nqc, int k, const SweepGeom& s
 // one launch that returns at once when nothing is flagged (nflag[1]: its blocks-done counter, zeroed with the count).
 // qpad, gthr, D_dev and I_dev are already offset to the chunk's first query; the flagging kernel has reset gthr / fix
 // lists / locks of every flagged query.
-int launch_fixup(css_index* ix, const float* qpad, int nq, int k, int* gthr, const int* flag_list, const int* nflag,
-                 float* D_dev, int64_t* I_dev, const SweepGeom& sg, hipStream_t st) {
+int launch_fixup(css_index* ix, const Rows& rows, const float* qpad, int nq, int k, int* gthr, const int* flag_list,
+                 const int* nflag, float* D_dev, int64_t* I_dev, const SweepGeom& sg, hipStream_t st) {
     const FixArgs fx{flag_list, nflag, ix->fix_s.p, ix->fix_i.p, ix->fix_lock.p, D_dev, I_dev};
-    if (sg.nq_sweep >= 8) return launch_scan_small_nq<8, true>(ix, qpad, 8, k, gthr, sg, st, fx);
-    if (sg.nq_sweep >= 2) return launch_scan_small_nq<2, true>(ix, qpad, 2, k, gthr, sg, st, fx);
-    return launch_scan_small_nq<1, true>(ix, qpad, 1, k, gthr, sg, st, fx);
+    if (sg.nq_sweep >= 8) return launch_scan_small_nq<8, true>(ix, rows, qpad, 8, k, gthr, sg, st, fx);
+    if (sg.nq_sweep >= 2) return launch_scan_small_nq<2, true>(ix, rows, qpad, 2, k, gthr, sg, st, fx);
+    return launch_scan_small_nq<1, true>(ix, rows, qpad, 1, k, gthr, sg, st, fx);
 }
 
 // workspaces shared by the candidate paths: thresholds, candidate buffers, flags, fix-up lists for nq_pad queries
@@ -1852,10 +1872,10 @@ constexpr float kSplitEps = 6.103515625e-05f;
 // Exact fp32 batched scan (CSS_SEARCH_EXACT_FP32 with more than 16 queries):
 // v_mfma_f32_32x32x2_f32, bit-exact fmaf chains, scores written as they are.
 template <int METRIC>
-int launch_scan_fp32mfma(css_index* ix, int nq, int k, float* D_dev, int64_t* I_dev, hipStream_t st) {
+int launch_scan_fp32mfma(css_index* ix, const Rows& rows, int nq, int k, float* D_dev, int64_t* I_dev, hipStream_t st) {
     const int nq_pad = (nq + MF_BN - 1) / MF_BN * MF_BN;  // <= nq + 127 (qpad / gthr have 256 rows of slack)
     const int nqtiles = nq_pad / MF_BN;
-    const int64_t ntiles = (ix->ntotal + MF_BM - 1) / MF_BM;
+    const int64_t ntiles = (rows.n + MF_BM - 1) / MF_BM;
     const size_t lds = (size_t)(2 * MF_BM * MF_BK + 2 * MF_BN * MF_BK + 4 * 32 * 33 + MF_BM) * 4 + (size_t)MF_BN * k * 8;
     // strips in multiples of 8 for the XCD-aware block decode
     int nstrips = std::max(8, ix->num_cus / nqtiles / 8 * 8);
@@ -1878,14 +1898,14 @@ int launch_scan_fp32mfma(css_index* ix, int nq, int k, float* D_dev, int64_t* I_
     }
     {
         ProfScope ps("knn_scan_mfma", st);
-        hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(256), lds, st, ix->xb, ix->xnorm2, ix->qpad.p, nq,
-                           ix->ntotal, ix->dpad, k, nstrips, nqtiles, tps, ix->gthr.p, ix->part_s.p, ix->part_i.p, ix->cur_mask, pace);
+        hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(256), lds, st, rows.xb, rows.xnorm2, ix->qpad.p, nq,
+                           rows.n, ix->dpad, k, nstrips, nqtiles, tps, ix->gthr.p, ix->part_s.p, ix->part_i.p, rows.mask, pace);
         CSS_LAUNCH_CHECK();
     }
     {
         ProfScope ps("knn_merge", st);
         hipLaunchKernelGGL(k_merge_final<METRIC>, dim3(nq), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, nstrips, k,
-                           ix->gthr.p, ix->qnorm2.p, ix->id_base, D_dev, I_dev, METRIC == CSS_METRIC_L2 ? 1 : 0,
+                           ix->gthr.p, ix->qnorm2.p, rows.id_base, D_dev, I_dev, METRIC == CSS_METRIC_L2 ? 1 : 0,
                            (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
         CSS_LAUNCH_CHECK();
     }
@@ -1905,32 +1925,33 @@ struct EpsSet {   // what cz_eps needs to know about the operands a scan read
     const float* qerr2;   // per query ||q - q^||^2 (null: fp32 queries)
     int measured;         // the word of maxn2 with the rows' measured error (1 bf16, 2 int8)
 };
-int launch_final_select(css_index* ix, int nq, int k, EpsSet e1, EpsSet e2, bool exact_k, int l2, int closed_n,
-                        const float* qpad, const float* qnorm2, int* gthr, int* flags, int* nflag, int* flag_list, float* D_dev, int64_t* I_dev, float* thr2,
-                        unsigned short* qh2, int f2, hipStream_t st) {
+int launch_final_select(css_index* ix, const Rows& rows, int nq, int k, EpsSet e1, EpsSet e2, bool exact_k, int l2,
+                        int closed_n, const float* qpad, const float* qnorm2, int* gthr, int* flags, int* nflag,
+                        int* flag_list, float* D_dev, int64_t* I_dev, float* thr2, unsigned short* qh2, int f2,
+                        hipStream_t st) {
     // e1: the scan that filled the buffers; e2: the second pass over flagged queries (always bf16 rows and queries)
     const float eps_rel = e1.eps_rel;
     const float* qerr2 = e1.qerr2;
     const int measured = e1.measured;
     hipLaunchKernelGGL(k_coarse_select<true>, dim3(nq), dim3(256), 0, st, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, ix->cthr.p, flags,
                        nflag, flag_list, qnorm2, ix->maxn2.p, eps_rel, l2, k, closed_n, gthr, qerr2, measured, ix->fix_s.p, ix->fix_i.p, ix->fix_lock.p,
-                       exact_k ? qpad : (const float*)nullptr, exact_k ? (const float*)ix->xb : (const float*)nullptr, ix->dpad);
+                       exact_k ? qpad : (const float*)nullptr, exact_k ? (const float*)rows.xb : (const float*)nullptr, ix->dpad);
     // (a work list of the live parts pays from a few dozen queries on; a handful of queries launch all their parts)
     const bool plan = nq > 16;
     if (plan) hipLaunchKernelGGL(k_rescore_plan, dim3(1), dim3(1024), 0, st, (const int*)ix->cand_n.p, nq, ix->rs_work.p, ix->rs_work.p + 1);
     hipLaunchKernelGGL(k_rescore_parts<false>, dim3(std::min(kRescoreGrid, nq * CZ_PARTS)), dim3(256), 0, st, ix->cand_s.p,
                        ix->cand_i.p, ix->cand_n.p, CZ_CAP, nq, (const int*)nullptr, (const int*)nullptr, (const float*)nullptr, l2, qpad,
-                       ix->xb, ix->dpad, plan ? (const int*)ix->rs_work.p : (const int*)nullptr,
+                       rows.xb, ix->dpad, plan ? (const int*)ix->rs_work.p : (const int*)nullptr,
                        plan ? (const int*)(ix->rs_work.p + 1) : (const int*)nullptr);
     hipLaunchKernelGGL(k_coarse_final, dim3(nq), dim3(256), 0, st, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, flags, qnorm2, ix->maxn2.p,
-                       e2.eps_rel, l2, k, qpad, ix->dpad, ix->id_base, D_dev, I_dev, thr2, qh2, f2, e2.qerr2, e2.measured);
+                       e2.eps_rel, l2, k, qpad, ix->dpad, rows.id_base, D_dev, I_dev, thr2, qh2, f2, e2.qerr2, e2.measured);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 
 template <int METRIC>
-int launch_scan_split_rescore(css_index* ix, int q0, int nq, int k, float* D_dev, int64_t* I_dev, const SweepGeom& sg,
-                              hipStream_t st) {
+int launch_scan_split_rescore(css_index* ix, const Rows& rows, int q0, int nq, int k, float* D_dev, int64_t* I_dev,
+                              const SweepGeom& sg, hipStream_t st) {
     // queries [q0, q0 + nq) of the padded query rows; nq <= 4096 and q0 a multiple of 256 (the caller chunks: the
     // candidate buffers are 32 KiB per query, and only the last chunk has padding rows to clear)
     const int kp = k + kSplitExtra;
@@ -1943,7 +1964,7 @@ int launch_scan_split_rescore(css_index* ix, int q0, int nq, int k, float* D_dev
     const int BMs = big ? 256 : MF_BM, BNs = big ? 256 : MF_BN;
     const int nq_pad = (nq + BNs - 1) / BNs * BNs;  // <= nq + 255 (qpad / gthr have 256 rows of slack)
     const int nqtiles = nq_pad / BNs;
-    const int64_t ntiles = (ix->ntotal + BMs - 1) / BMs;
+    const int64_t ntiles = (rows.n + BMs - 1) / BMs;
     // staging + lists (the slow-path scratch borrows a staging buffer); <= 80 KiB means two blocks share a CU
     const size_t lds = (size_t)(2 * BMs * MF_BK + 2 * BNs * MF_BK + BMs + 4) * 4 + (size_t)BNs * kp * 8;
     const int bpc = (!big && lds <= 80 * 1024) ? 2 : 1;
@@ -1975,60 +1996,59 @@ int launch_scan_split_rescore(css_index* ix, int q0, int nq, int k, float* D_dev
         if (big) {
             auto kern = k_scan_mfma_split<METRIC, 8, 8>;
             if ((rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
-            hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(512), lds, st, ix->xb, ix->xnorm2, ix->qsplit.p, nq,
-                               ix->ntotal, ix->dpad, kp, nstrips, nqtiles, tps, gthr, ix->part_s.p, ix->part_i.p, ix->cur_mask);
+            hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(512), lds, st, rows.xb, rows.xnorm2, ix->qsplit.p, nq,
+                               rows.n, ix->dpad, kp, nstrips, nqtiles, tps, gthr, ix->part_s.p, ix->part_i.p, rows.mask);
         } else {
             auto kern = k_scan_mfma_split<METRIC, 4, 4>;
             if ((rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
-            hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(256), lds, st, ix->xb, ix->xnorm2, ix->qsplit.p, nq,
-                               ix->ntotal, ix->dpad, kp, nstrips, nqtiles, tps, gthr, ix->part_s.p, ix->part_i.p, ix->cur_mask);
+            hipLaunchKernelGGL(kern, dim3(nstrips * nqtiles), dim3(256), lds, st, rows.xb, rows.xnorm2, ix->qsplit.p, nq,
+                               rows.n, ix->dpad, kp, nstrips, nqtiles, tps, gthr, ix->part_s.p, ix->part_i.p, rows.mask);
         }
         CSS_LAUNCH_CHECK();
     }
     // the kp best split scores of every query -> its candidate buffer (scores stay in the scan's form: IP dot
     // products, L2 2 x.q - ||x||^2, the form k_coarse_select expects of coarse scores)
     hipLaunchKernelGGL(k_merge_final<METRIC>, dim3(nq), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, nstrips, kp, gthr,
-                       qnorm2, ix->id_base, D_dev, I_dev, METRIC == CSS_METRIC_L2 ? 1 : 0, ix->cand_s.p, ix->cand_i.p,
+                       qnorm2, rows.id_base, D_dev, I_dev, METRIC == CSS_METRIC_L2 ? 1 : 0, ix->cand_s.p, ix->cand_i.p,
                        ix->cand_n.p);
-    if ((rc = launch_final_select(ix, nq, k, EpsSet{kSplitEps, nullptr, 0}, EpsSet{kSplitEps, nullptr, 0}, false, METRIC == CSS_METRIC_L2 ? 1 : 0, kp, qpad, qnorm2, gthr, flags, nflag,
+    if ((rc = launch_final_select(ix, rows, nq, k, EpsSet{kSplitEps, nullptr, 0}, EpsSet{kSplitEps, nullptr, 0}, false, METRIC == CSS_METRIC_L2 ? 1 : 0, kp, qpad, qnorm2, gthr, flags, nflag,
                                   flag_list, D_dev, I_dev, nullptr, nullptr, 0, st)) != CSS_OK)
         return rc;
-    return launch_fixup(ix, qpad, nq, k, gthr, flag_list, nflag, D_dev, I_dev, sg, st);
+    return launch_fixup(ix, rows, qpad, nq, k, gthr, flag_list, nflag, D_dev, I_dev, sg, st);
 }
 
 // Coarse bf16 scan + exact rescoring (css_knn_coarse.h) for queries [q0, q0 + nq) of ix->qpad.p; nq <= 4096.
 template <int NQ, int TT, bool MAIN>
-int launch_sweep_coarse_t(css_index* ix, const float* qpad, int nq, int64_t count, int64_t stride, int gm1, bool stage0,
-                          hipStream_t st) {
+int launch_sweep_coarse_t(css_index* ix, const Rows& rows, const float* qpad, int nq, int64_t count, int64_t stride,
+                          int gm1, bool stage0, hipStream_t st) {
     const size_t lds = (size_t)NQ * ix->dpad * sizeof(float);
     const int grid = (int)std::min<int64_t>((int64_t)ix->num_cus * 8, count);
     auto kern = k_sweep_coarse<NQ, TT, MAIN>;
     int rc;
     if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, ix->xh, qpad, ix->cthr.p, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p,
-                       ix->ntotal, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, ix->cur_mask,
-                       ix->metric == CSS_METRIC_L2 ? ix->xnorm2 : nullptr);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, rows.xh, qpad, ix->cthr.p, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p,
+                       rows.n, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, rows.mask,
+                       ix->metric == CSS_METRIC_L2 ? rows.xnorm2 : nullptr);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 
 template <int NQ, int TT, bool MAIN>
-int launch_sweep_coarse_i8_t(css_index* ix, const float* qpad, int nq, int64_t count, int64_t stride, int gm1, bool stage0,
-                             hipStream_t st) {
+int launch_sweep_coarse_i8_t(css_index* ix, const Rows& rows, const float* qpad, int nq, int64_t count, int64_t stride,
+                             int gm1, bool stage0, hipStream_t st) {
     const int steps = TT > 0 ? TT : (ix->dpad / 16 + 15) / 16;
     const size_t lds = ((size_t)NQ * 256 * steps + NQ) * sizeof(float);
     const int grid = (int)std::min<int64_t>((int64_t)ix->num_cus * 8, count);
     auto kern = k_sweep_coarse_i8<NQ, TT, MAIN>;
     int rc;
     if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, ix->x8, ix->x8s, qpad, ix->cthr.p, ix->cand_s.p, ix->cand_i.p,
-                       ix->cand_n.p, ix->ntotal, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, ix->cur_mask,
-                       ix->metric == CSS_METRIC_L2 ? ix->xnorm2 : nullptr);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, rows.x8, rows.x8s, qpad, ix->cthr.p, ix->cand_s.p, ix->cand_i.p,
+                       ix->cand_n.p, rows.n, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, rows.mask,
+                       ix->metric == CSS_METRIC_L2 ? rows.xnorm2 : nullptr);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 
-// (the int8 rows exist only next to bf16 shadow rows; a RowView of a shadow-less index never gets here)
 // Rows whose int8 copy is poor (a few dominant elements set the row scale and the rest rounds to nothing) make the
 // measured band so wide that the buffers overflow and the queries end in the fix-up: results stay exact, the search
 // gets slow.  So the use of the int8 rows adapts per index: `permille` = flagged share of the last int8 search above
@@ -2058,8 +2078,8 @@ inline int i8_feedback_record(css_index::I8Feedback& f, const int* nflag_dev, in
     return CSS_OK;
 }
 // 1..4 queries: any flagged query sends the next searches back to the bf16 sweep
-inline bool sweep_uses_i8(css_index* ix) {
-    if (ix->x8 == nullptr || !knn_env().sweep_i8) return false;
+inline bool sweep_uses_i8(css_index* ix, const Rows& rows) {
+    if (rows.x8 == nullptr || !knn_env().sweep_i8) return false;
     return i8_feedback_allows(ix->fb_sweep, 0);
 }
 // batches: the int8 MFMA scan -- inner product, rows a whole (even) number of 128-B K steps, the 8-phase loop's shape --
@@ -2074,8 +2094,8 @@ inline bool sweep_uses_i8(css_index* ix) {
 // Its wider band also flags more queries on clustered rows (10 M rows in 20 000 clusters: 23 % of the queries, 14.8 ms
 // against the bf16 scan's 13.3 with none flagged), so the choice adapts per index: when an int8 batch flagged more than
 // 5 % of its queries the next 16 batches read the bf16 rows, then int8 is tried again.  (Caller holds ws_mu.)
-// (`rows`: the rows one cascade covers -- the index, or one range of a shadow-less index)
-inline bool batch_i8_wanted(css_index* ix, int k, int64_t rows, int64_t nq) {
+// (`nrows`: the rows one cascade covers -- the index, or one range of a shadow-less index)
+inline bool batch_i8_wanted(css_index* ix, int k, int64_t nrows, int64_t nq) {
     const KnnEnv& e = knn_env();
     if (e.batch_i8 == 0 || ix->metric != CSS_METRIC_IP || ix->dpad % 256 != 0 || ix->dpad > 1024) return false;
     if (e.batch_i8 == 2) return true;
@@ -2085,7 +2105,7 @@ inline bool batch_i8_wanted(css_index* ix, int k, int64_t rows, int64_t nq) {
     // (fewer than 256 queries, k = 100, ms int8 / bf16, 33 / 64 / 128 / 255 queries: 10 M rows 1.89 / 3.19, 2.08 / 3.33, 2.19 /
     // 3.45, 2.50 / 3.87; 2 M rows 0.73 / 0.82 .. 0.99 / 1.08: the query count is no condition any more)
     (void)nq;
-    const bool pays = k <= 32 ? rows >= 300000 : (k * 2 <= CZ_EXK && rows >= 2000000);
+    const bool pays = k <= 32 ? nrows >= 300000 : (k * 2 <= CZ_EXK && nrows >= 2000000);
     if (!pays) return false;
     // (with <= 256 flagged queries the second pass is one query tile of bf16 scan -- a quarter of a 1000-query bf16 step --
     // and the int8 search still wins: 10 M rows in 20 000 clusters, 33 flagged: 12.8 ms against 13.3 on bf16 rows)
@@ -2093,19 +2113,19 @@ inline bool batch_i8_wanted(css_index* ix, int k, int64_t rows, int64_t nq) {
 }
 
 template <int NQ>
-int launch_sweep_coarse_nq(css_index* ix, const float* qpad, int nq, int64_t count, int64_t stride, int gm1, bool stage0,
-                           hipStream_t st, bool i8) {
+int launch_sweep_coarse_nq(css_index* ix, const Rows& rows, const float* qpad, int nq, int64_t count, int64_t stride,
+                           int gm1, bool stage0, hipStream_t st, bool i8) {
     const bool main_stage = stride == 1 && !stage0;
     if (i8) {
         if (ix->dpad == 768)
-            return main_stage ? launch_sweep_coarse_i8_t<NQ, 3, true>(ix, qpad, nq, count, stride, gm1, stage0, st)
-                              : launch_sweep_coarse_i8_t<NQ, 3, false>(ix, qpad, nq, count, stride, gm1, stage0, st);
-        return launch_sweep_coarse_i8_t<NQ, 0, false>(ix, qpad, nq, count, stride, gm1, stage0, st);
+            return main_stage ? launch_sweep_coarse_i8_t<NQ, 3, true>(ix, rows, qpad, nq, count, stride, gm1, stage0, st)
+                              : launch_sweep_coarse_i8_t<NQ, 3, false>(ix, rows, qpad, nq, count, stride, gm1, stage0, st);
+        return launch_sweep_coarse_i8_t<NQ, 0, false>(ix, rows, qpad, nq, count, stride, gm1, stage0, st);
     }
     if (ix->dpad == 768)
-        return main_stage ? launch_sweep_coarse_t<NQ, 6, true>(ix, qpad, nq, count, stride, gm1, stage0, st)
-                          : launch_sweep_coarse_t<NQ, 6, false>(ix, qpad, nq, count, stride, gm1, stage0, st);
-    return launch_sweep_coarse_t<NQ, 0, false>(ix, qpad, nq, count, stride, gm1, stage0, st);
+        return main_stage ? launch_sweep_coarse_t<NQ, 6, true>(ix, rows, qpad, nq, count, stride, gm1, stage0, st)
+                          : launch_sweep_coarse_t<NQ, 6, false>(ix, rows, qpad, nq, count, stride, gm1, stage0, st);
+    return launch_sweep_coarse_t<NQ, 0, false>(ix, rows, qpad, nq, count, stride, gm1, stage0, st);
 }
 
 // 3..32 queries, inner product, int8 rows in view: does the sweep on the int8 MFMA (k_sweep_mfma_i8) answer sooner than what
@@ -2113,28 +2133,29 @@ int launch_sweep_coarse_nq(css_index* ix, const float* qpad, int nq, int64_t cou
 // session, ms with / without, 3 .. 16 queries: 10 M rows k = 10 1.65 / 1.92-2.07, k = 100 1.83-1.85 / 2.75-3.26; 1 M rows
 // 0.32-0.33 / 0.34-0.41 and 0.46-0.48 / 0.45-0.58; 100 k rows 0.13-0.14 / 0.15-0.16 but 0.22 / 0.18-0.20 at k = 100 (a
 // select with 100 exactly scored rows behind every stage); 20 k rows 0.11-0.12 / 0.11 and 0.17-0.19 / 0.13-0.15.
-inline bool mfma_sweep_applies(const css_index* ix, int64_t nq, int k) {
+inline bool mfma_sweep_applies(const css_index* ix, const Rows& rows, int64_t nq, int k) {
     const int mode = knn_env().sweep_mfma;
-    if (mode == 0 || ix->x8 == nullptr || ix->metric != CSS_METRIC_IP || ix->dpad > 1024 || nq < 3 || nq > 32) return false;
+    if (mode == 0 || rows.x8 == nullptr || ix->metric != CSS_METRIC_IP || ix->dpad > 1024 || nq < 3 || nq > 32) return false;
     if (mode == 2) return true;
     // 17..32 queries (two fragment sets per lane), ms with / without: k = 10: 10 M rows 1.78 / 1.66 (the batch scan with the
     // queries in registers is ahead there), 1 M rows 0.33 / 0.38, 100 k rows 0.13 / 0.155; k = 100: 10 M rows 2.0 / 3.2-3.3
     // (the bf16 scan: fewer than 256 queries), 1 M rows 0.56-0.59 / 0.53
     // (k = 100 at 10 M rows was measured against the bf16 scan; the int8 batch scan, which such a search takes since, is at
     // 1.89 ms for 33 queries: the sweep stays with k <= 32)
-    if (nq > 16) return k <= 32 && ix->ntotal >= 50000 && ix->ntotal < 4000000;
-    return ix->ntotal >= (k <= 32 ? 50000 : 1000000);
+    if (nq > 16) return k <= 32 && rows.n >= 50000 && rows.n < 4000000;
+    return rows.n >= (k <= 32 ? 50000 : 1000000);
 }
 
 // one cascade stage of the int8 MFMA sweep (3..32 queries: k_sweep_mfma_i8); the int8 queries sit in ix->qh.p
-int launch_sweep_mfma(css_index* ix, int nq, int64_t count, int64_t stride, int gm1, bool stage0, hipStream_t st) {
+int launch_sweep_mfma(css_index* ix, const Rows& rows, int nq, int64_t count, int64_t stride, int gm1, bool stage0,
+                      hipStream_t st) {
     const int grid = (int)std::min<int64_t>((int64_t)ix->num_cus * 8, count);
     const bool main_stage = stride == 1 && !stage0;
     const signed char* q8 = reinterpret_cast<const signed char*>(ix->qh.p);
 #define CSS_LAUNCH_SWEEP_MFMA(KS_, MAIN_, NG_)                                                                         \
-    hipLaunchKernelGGL((k_sweep_mfma_i8<KS_, MAIN_, NG_>), dim3(grid), dim3(256), 0, st, ix->x8, ix->x8s, q8, ix->qscale.p, ix->cthr.p,  \
-                       ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, ix->ntotal, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, \
-                       ix->cur_mask)
+    hipLaunchKernelGGL((k_sweep_mfma_i8<KS_, MAIN_, NG_>), dim3(grid), dim3(256), 0, st, rows.x8, rows.x8s, q8, ix->qscale.p, ix->cthr.p,  \
+                       ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, rows.n, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, \
+                       rows.mask)
     if (nq <= 16) {
         if (ix->dpad == 768) {
             if (main_stage) CSS_LAUNCH_SWEEP_MFMA(12, true, 1);
@@ -2158,30 +2179,32 @@ int launch_sweep_mfma(css_index* ix, int nq, int64_t count, int64_t stride, int 
 // one later stage of the int8 batch scan with the queries in registers (k_scan_qreg_i8): two 4-wave blocks per CU
 inline int qreg_grid(const css_index* ix) { return std::max(8, ix->num_cus * 2 / 8 * 8); }
 template <int KS>
-int launch_scan_qreg_t(css_index* ix, int nqt, int64_t count, int64_t stride, int gm1, bool main_stage, hipStream_t st) {
+int launch_scan_qreg_t(css_index* ix, const Rows& rows, int nqt, int64_t count, int64_t stride, int gm1,
+                       bool main_stage, hipStream_t st) {
     const size_t lds = qr_lds_bytes<KS>();
     auto kern = main_stage ? k_scan_qreg_i8<KS, true> : k_scan_qreg_i8<KS, false>;
     int rc;
     if ((rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
-    hipLaunchKernelGGL(kern, dim3(qreg_grid(ix)), dim3(256), lds, st, (const unsigned char*)ix->x8,
+    hipLaunchKernelGGL(kern, dim3(qreg_grid(ix)), dim3(256), lds, st, (const unsigned char*)rows.x8,
                        reinterpret_cast<const signed char*>(ix->qh.p), (const float*)ix->cthr.p, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p,
-                       ix->ntotal, nqt, count, stride, gm1, ix->cur_mask, (const float*)ix->x8s, (const float*)ix->qscale.p);
+                       rows.n, nqt, count, stride, gm1, rows.mask, (const float*)rows.x8s, (const float*)ix->qscale.p);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 inline bool qreg_applies(const css_index* ix, int nqt) {
     return knn_env().qreg && (ix->dpad == 256 || ix->dpad == 512 || ix->dpad == 768) && (qreg_grid(ix) / 8) / nqt >= 1;
 }
-int launch_scan_qreg(css_index* ix, int nqt, int64_t count, int64_t stride, int gm1, bool main_stage, hipStream_t st) {
-    if (ix->dpad == 768) return launch_scan_qreg_t<12>(ix, nqt, count, stride, gm1, main_stage, st);
-    if (ix->dpad == 512) return launch_scan_qreg_t<8>(ix, nqt, count, stride, gm1, main_stage, st);
-    return launch_scan_qreg_t<4>(ix, nqt, count, stride, gm1, main_stage, st);
+int launch_scan_qreg(css_index* ix, const Rows& rows, int nqt, int64_t count, int64_t stride, int gm1, bool main_stage,
+                     hipStream_t st) {
+    if (ix->dpad == 768) return launch_scan_qreg_t<12>(ix, rows, nqt, count, stride, gm1, main_stage, st);
+    if (ix->dpad == 512) return launch_scan_qreg_t<8>(ix, rows, nqt, count, stride, gm1, main_stage, st);
+    return launch_scan_qreg_t<4>(ix, rows, nqt, count, stride, gm1, main_stage, st);
 }
 
 // the whole sweep cascade in one launch (k_sweep_cascade); sc: the schedule as tickets
 template <int NQ, int TT, bool I8>
-int launch_sweep_cascade_t(css_index* ix, const float* qpad, int nq, const FsSched& sc, int* flags, const float* qnorm2,
-                           float eps_rel, int l2, int k, int measured, hipStream_t st) {
+int launch_sweep_cascade_t(css_index* ix, const Rows& rows, const float* qpad, int nq, const FsSched& sc, int* flags,
+                           const float* qnorm2, float eps_rel, int l2, int k, int measured, hipStream_t st) {
     const int steps = I8 ? (TT > 0 ? TT : (ix->dpad / 16 + 15) / 16) : 0;
     const size_t lds = (size_t)cz_fs_lds_floats(NQ, I8 ? 256 * steps : ix->dpad) * sizeof(float);
     auto kern = k_sweep_cascade<NQ, TT, I8>;
@@ -2196,22 +2219,22 @@ int launch_sweep_cascade_t(css_index* ix, const float* qpad, int nq, const FsSch
     int per_cu = per_cu_cached;
     per_cu = std::min(per_cu, 3);   // (12 waves per CU already draw the whole HBM rate: 2 / 3 / 4 blocks 1.305 / 1.302 / 1.316 ms at 10 M rows)
     const int grid = (int)std::min<int64_t>((int64_t)ix->num_cus * std::min(per_cu, 8), (sc.first[sc.nstage] + 3) / 4);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, I8 ? (const void*)ix->x8 : (const void*)ix->xh,
-                       I8 ? (const float*)ix->x8s : (const float*)nullptr, qpad, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, ix->cthr.p,
-                       flags, ix->ntotal, ix->dpad, nq, sc, ix->fs_state.p, ix->cur_mask,
-                       ix->metric == CSS_METRIC_L2 ? ix->xnorm2 : nullptr, qnorm2, (const int*)ix->maxn2.p, eps_rel, l2, k, measured,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, I8 ? (const void*)rows.x8 : (const void*)rows.xh,
+                       I8 ? (const float*)rows.x8s : (const float*)nullptr, qpad, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, ix->cthr.p,
+                       flags, rows.n, ix->dpad, nq, sc, ix->fs_state.p, rows.mask,
+                       ix->metric == CSS_METRIC_L2 ? rows.xnorm2 : nullptr, qnorm2, (const int*)ix->maxn2.p, eps_rel, l2, k, measured,
                        knn_env().fs_spins);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 template <int NQ>
-int launch_sweep_cascade_nq(css_index* ix, const float* qpad, int nq, const FsSched& sc, int* flags, const float* qnorm2,
-                            float eps_rel, int l2, int k, int measured, hipStream_t st, bool i8) {
+int launch_sweep_cascade_nq(css_index* ix, const Rows& rows, const float* qpad, int nq, const FsSched& sc, int* flags,
+                            const float* qnorm2, float eps_rel, int l2, int k, int measured, hipStream_t st, bool i8) {
     if (i8)
-        return ix->dpad == 768 ? launch_sweep_cascade_t<NQ, 3, true>(ix, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st)
-                               : launch_sweep_cascade_t<NQ, 0, true>(ix, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st);
-    return ix->dpad == 768 ? launch_sweep_cascade_t<NQ, 6, false>(ix, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st)
-                           : launch_sweep_cascade_t<NQ, 0, false>(ix, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st);
+        return ix->dpad == 768 ? launch_sweep_cascade_t<NQ, 3, true>(ix, rows, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st)
+                               : launch_sweep_cascade_t<NQ, 0, true>(ix, rows, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st);
+    return ix->dpad == 768 ? launch_sweep_cascade_t<NQ, 6, false>(ix, rows, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st)
+                           : launch_sweep_cascade_t<NQ, 0, false>(ix, rows, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st);
 }
 
 // grid of the persistent k_scan_coarse launches and the largest query chunk it can serve: the nqt blocks
@@ -2226,7 +2249,7 @@ inline int coarse_max_chunk(const css_index* ix) { return std::min(4096, coarse_
 // flagged count is what the feedback sees.
 // q_raw != null (sweep only): the raw query rows, still to be prepared (normalize_q as in search_dev_enqueue) -- the init
 // launch of the cascade does it.
-int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64_t* I_dev, hipStream_t st,
+int launch_scan_coarse(css_index* ix, const Rows& rows, int q0, int nq, int k, float* D_dev, int64_t* I_dev, hipStream_t st,
                        const SweepGeom& sg, bool sweep, bool use_i8, bool record_fb, const float* q_raw = nullptr,
                        int normalize_q = 0) {
     const KnnEnv& env = knn_env();
@@ -2235,7 +2258,7 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     D_dev += (size_t)q0 * k;
     I_dev += (size_t)q0 * k;
     // 3..32 queries on int8 rows (inner product): the sweep on the int8 MFMA (k_sweep_mfma_i8): int8 queries too
-    const bool sweep_mfma = sweep && use_i8 && mfma_sweep_applies(ix, nq, k);
+    const bool sweep_mfma = sweep && use_i8 && mfma_sweep_applies(ix, rows, nq, k);
     const int nq_pad = sweep ? (sweep_mfma ? (nq <= 16 ? 16 : 32) : nq) : (nq + CZ_T - 1) / CZ_T * CZ_T;
     const int nqt = sweep ? 1 : nq_pad / CZ_T;
     // error of one coarse score relative to ||q|| max||x||: both operands bf16 (MFMA scan) or rows only (sweep)
@@ -2257,7 +2280,7 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     // the second pass over flagged queries reads the bf16 rows with bf16 queries
     const EpsSet eps_p2{0.0078125f + 0.00048828125f, ix->qerr2.p + q0, 1};
     const int l2 = ix->metric == CSS_METRIC_L2 ? 1 : 0;
-    const float* xn2 = l2 ? ix->xnorm2 : nullptr;  // L2: coarse score = 2 x.q - ||x||^2
+    const float* xn2 = l2 ? rows.xnorm2 : nullptr;  // L2: coarse score = 2 x.q - ||x||^2
     int rc;
     if (!sweep && (rc = ix->qh.grow((size_t)nq_pad * ix->dpad)) != CSS_OK) return rc;
     if ((rc = grow_candidate_ws(ix, (size_t)nq_pad, k)) != CSS_OK) return rc;
@@ -2272,7 +2295,7 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     // per pass over the fp32 rows): 22 flagged of 1000 queries cost 2.9 ms of a 7 ms batch at 1 M clustered rows.
     // (the second pass reads the bf16 rows: a shadow-less range scanned from int8 scratch rows sends its flagged queries
     // straight to the exact sweep -- and, through the feedback of batch_uses_i8, the next searches to bf16 ranges)
-    const bool pass2 = !sweep && ix->dpad % 128 == 0 && ix->ntotal > CZ_CAP && ix->xh != nullptr;
+    const bool pass2 = !sweep && ix->dpad % 128 == 0 && rows.n > CZ_CAP && rows.xh != nullptr;
     const int f2 = pass2 ? std::min(nq_pad, kF2Max) : 0;   // (a multiple of CZ_T)
     int* flag_listB = nullptr;
     int* nflagB = nullptr;
@@ -2303,12 +2326,12 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     // there -- measured at 10 M rows, k = 10: g = 4 / 8 / 16 (7 / 5 / 4 stages) all take 2.71-2.72 ms, the call is the
     // 15.36 GB of shadow rows at the sweep's bandwidth plus ~0.25 ms -- and with k = 100 (the reference's call shape)
     // g = 16 overflows the 4096-slot buffers (~k g candidates per stage) and lands in the exact fix-up: 10 ms.
-    const int64_t ntiles = (ix->ntotal + CZ_T - 1) / CZ_T;
+    const int64_t ntiles = (rows.n + CZ_T - 1) / CZ_T;
     // (int8 scan: its band is ~4 x wider, growth 8 would append ~2500 rows per query in the main stage)
     // (3..32 queries on the int8 MFMA: one launch per stage, so below ~4 M rows fewer, larger stages win -- ms at growth 4 / 8,
     // k = 10: 1 M rows 0.33 / 0.27, 100 k rows 0.13 / 0.10, 10 M rows 1.59 / 1.55-1.67; k = 100 overflows the buffers at
     // growth 8 and 10 M rows, as the VALU sweep did)
-    const int g_sweep = env.growth_sweep ? env.growth_sweep : ((sweep_mfma && k <= 32 && ix->ntotal < 4000000) ? 8 : 4);
+    const int g_sweep = env.growth_sweep ? env.growth_sweep : ((sweep_mfma && k <= 32 && rows.n < 4000000) ? 8 : 4);
     const int g = sweep ? g_sweep : (env.growth ? env.growth : ((k <= 32 && !i8) ? 8 : 4));
     struct Stage {
         int64_t stride;
@@ -2341,7 +2364,7 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
     // 1..4 queries: the stages and the selects between them as ONE launch (k_sweep_cascade), quarter tiles as tickets in stage order
     // (measured, ms one launch / one per stage: 10 M rows, 1 query k = 10 1.35 / 1.41, k = 100 1.40 / 1.56, 2 queries 1.40 /
     // 1.47, 4 queries 2.68 / 2.69; 100 k rows: 0.085 / 0.095, 0.118 / 0.125, but 2 queries 0.117 / 0.111, 4: 0.186 / 0.155)
-    bool fused = sweep && !sweep_mfma && env.sweep_fused && (env.sweep_fused == 2 || nq == 1 || ix->ntotal >= 1000000) &&
+    bool fused = sweep && !sweep_mfma && env.sweep_fused && (env.sweep_fused == 2 || nq == 1 || rows.n >= 1000000) &&
                  (int)sched.size() <= CZ_FS_MAXST && ntiles < (int64_t)1 << 28;
     FsSched fsched{};
     if (fused) {
@@ -2411,8 +2434,8 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
                               : (loop8 ? k_scan_coarse8<false, false> : k_scan_coarse<false, false>);
     const scan_fn f_main = i8b ? k_scan_coarse8<false, true, CZ_CAP, true>
                                : (loop8 ? k_scan_coarse8<false, true> : k_scan_coarse<false, true>);
-    const unsigned short* scan_rows = i8b ? reinterpret_cast<const unsigned short*>(ix->x8) : ix->xh;
-    const float* scan_xsc = i8b ? ix->x8s : nullptr;
+    const unsigned short* scan_rows = i8b ? reinterpret_cast<const unsigned short*>(rows.x8) : rows.xh;
+    const float* scan_xsc = i8b ? rows.x8s : nullptr;
     const float* scan_qsc = i8b ? ix->qscale.p : nullptr;
     if (!sweep)
         for (scan_fn f : {f_stage0, f_mid, f_main})
@@ -2425,12 +2448,12 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
         ProfScope all("knn_sweep_cascade", st);
         {
             ProfScope ps("knn_sweep_fused", st);
-            if (nq <= 1) rc = launch_sweep_cascade_nq<1>(ix, qpad, nq, fsched, flags, qnorm2, eps_rel, l2, k, measured, st, i8);
-            else if (nq <= 2) rc = launch_sweep_cascade_nq<2>(ix, qpad, nq, fsched, flags, qnorm2, eps_rel, l2, k, measured, st, i8);
-            else rc = launch_sweep_cascade_nq<4>(ix, qpad, nq, fsched, flags, qnorm2, eps_rel, l2, k, measured, st, i8);
+            if (nq <= 1) rc = launch_sweep_cascade_nq<1>(ix, rows, qpad, nq, fsched, flags, qnorm2, eps_rel, l2, k, measured, st, i8);
+            else if (nq <= 2) rc = launch_sweep_cascade_nq<2>(ix, rows, qpad, nq, fsched, flags, qnorm2, eps_rel, l2, k, measured, st, i8);
+            else rc = launch_sweep_cascade_nq<4>(ix, rows, qpad, nq, fsched, flags, qnorm2, eps_rel, l2, k, measured, st, i8);
             if (rc != CSS_OK) return rc;
         }
-        if ((rc = launch_final_select(ix, nq, k, EpsSet{eps_rel, qerr2, measured}, eps_p2, exact_k, l2, 0, qpad, qnorm2, ix->gthr.p + q0, flags, nflag, flag_list, D_dev,
+        if ((rc = launch_final_select(ix, rows, nq, k, EpsSet{eps_rel, qerr2, measured}, eps_p2, exact_k, l2, 0, qpad, qnorm2, ix->gthr.p + q0, flags, nflag, flag_list, D_dev,
                                       I_dev, pass2 ? ix->thr2.p : nullptr, pass2 ? ix->qh2.p : nullptr, f2, st)) != CSS_OK)
             return rc;
     } else {
@@ -2443,12 +2466,12 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
         const int64_t count = stage0 ? W : (W - 1) - (W - 1) / gr;
         if (count > 0 && sweep_mfma) {
             ProfScope ps(s == 1 && !stage0 ? "knn_sweep_mfma_main" : "knn_sweep_mfma_stage", st);
-            if ((rc = launch_sweep_mfma(ix, nq, count, s, std::max(1, gr - 1), stage0, st)) != CSS_OK) return rc;
+            if ((rc = launch_sweep_mfma(ix, rows, nq, count, s, std::max(1, gr - 1), stage0, st)) != CSS_OK) return rc;
         } else if (count > 0 && sweep) {
             ProfScope ps(s == 1 && !stage0 ? "knn_sweep_coarse_main" : "knn_sweep_coarse_stage", st);
-            if (nq <= 1) rc = launch_sweep_coarse_nq<1>(ix, qpad, nq, count, s, gr - 1, stage0, st, i8);
-            else if (nq <= 2) rc = launch_sweep_coarse_nq<2>(ix, qpad, nq, count, s, gr - 1, stage0, st, i8);
-            else rc = launch_sweep_coarse_nq<4>(ix, qpad, nq, count, s, gr - 1, stage0, st, i8);
+            if (nq <= 1) rc = launch_sweep_coarse_nq<1>(ix, rows, qpad, nq, count, s, gr - 1, stage0, st, i8);
+            else if (nq <= 2) rc = launch_sweep_coarse_nq<2>(ix, rows, qpad, nq, count, s, gr - 1, stage0, st, i8);
+            else rc = launch_sweep_coarse_nq<4>(ix, rows, qpad, nq, count, s, gr - 1, stage0, st, i8);
             if (rc != CSS_OK) return rc;
         } else if (count > 0) {
             const scan_fn f = stage0 ? f_stage0 : (s == 1 ? f_main : f_mid);
@@ -2459,21 +2482,21 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
             // 3 M rows (1024 / 4096 / never) 0.70, 0.79, 2.25 / 0.73, 0.84, 2.28 / 0.78, 0.90, 2.56; 10 M rows 1.88, 1.99,
             // 6.45 / 1.88, 2.01, 6.52 / 2.05, 2.27, 7.36.
             if (i8b && !stage0 && qreg_applies(ix, nqt) && count * nqt >= env.qreg_min) {
-                if ((rc = launch_scan_qreg(ix, nqt, count, s, gr - 1, s == 1, st)) != CSS_OK) return rc;
+                if ((rc = launch_scan_qreg(ix, rows, nqt, count, s, gr - 1, s == 1, st)) != CSS_OK) return rc;
             } else {
                 // (int8 rows: no sibling pacing -- a row tile fetched by every query-tile block on its own is still only
                 // ~3.5 TB/s worst case at this scan's speed, and the coupling costs more than the HBM traffic it saves:
                 // 9.65 vs 9.02 ms per batch; the bf16 scan reads twice the bytes per row and needs it)
                 int* pace = (!i8b && grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace.p + (size_t)stage_idx * kPaceGroups : nullptr;
                 hipLaunchKernelGGL(f, dim3(grid), dim3(512), lds, st, scan_rows, ix->qh.p, ix->cthr.p, ix->cand_s.p, ix->cand_i.p,
-                                   ix->cand_n.p, ix->ntotal, ix->dpad, nqt, count, s, gr - 1, pace, ix->cur_mask, xn2,
+                                   ix->cand_n.p, rows.n, ix->dpad, nqt, count, s, gr - 1, pace, rows.mask, xn2,
                                    (const int*)nullptr, scan_xsc, scan_qsc);
                 CSS_LAUNCH_CHECK();
             }
         }
         ++stage_idx;
         if (s == 1) {
-            if ((rc = launch_final_select(ix, nq, k, EpsSet{eps_rel, qerr2, measured}, eps_p2, exact_k, l2, 0, qpad, qnorm2, ix->gthr.p + q0, flags, nflag, flag_list, D_dev,
+            if ((rc = launch_final_select(ix, rows, nq, k, EpsSet{eps_rel, qerr2, measured}, eps_p2, exact_k, l2, 0, qpad, qnorm2, ix->gthr.p + q0, flags, nflag, flag_list, D_dev,
                                           I_dev, pass2 ? ix->thr2.p : nullptr, pass2 ? ix->qh2.p : nullptr, f2, st)) != CSS_OK)
                 return rc;
             break;
@@ -2481,7 +2504,7 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
         hipLaunchKernelGGL(k_coarse_select<false>, dim3(nq), dim3(256), 0, st, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p,
                            ix->cthr.p, flags, nflag, flag_list, qnorm2, ix->maxn2.p, eps_rel, l2, k, 0, ix->gthr.p + q0, qerr2, measured, ix->fix_s.p,
                            ix->fix_i.p, ix->fix_lock.p, exact_k ? qpad : (const float*)nullptr,
-                           exact_k ? (const float*)ix->xb : (const float*)nullptr, ix->dpad);
+                           exact_k ? (const float*)rows.xb : (const float*)nullptr, ix->dpad);
         CSS_LAUNCH_CHECK();
     }
     }
@@ -2496,37 +2519,37 @@ int launch_scan_coarse(css_index* ix, int q0, int nq, int k, float* D_dev, int64
         const int nqt2 = f2 / CZ_T;
         {
             int* pace = (grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace.p + (size_t)stage_idx * kPaceGroups : nullptr;
-            hipLaunchKernelGGL(f_all, dim3(grid), dim3(512), lds, st, ix->xh, ix->qh2.p, ix->thr2.p, ix->cand_s2.p, ix->cand_i2.p,
-                               ix->cand_n2.p, ix->ntotal, ix->dpad, nqt2, ntiles, (int64_t)1, 1 << 30, pace, ix->cur_mask, xn2,
+            hipLaunchKernelGGL(f_all, dim3(grid), dim3(512), lds, st, rows.xh, ix->qh2.p, ix->thr2.p, ix->cand_s2.p, ix->cand_i2.p,
+                               ix->cand_n2.p, rows.n, ix->dpad, nqt2, ntiles, (int64_t)1, 1 << 30, pace, rows.mask, xn2,
                                (const int*)nflag, (const float*)nullptr, (const float*)nullptr);
         }
         hipLaunchKernelGGL(k_rescore_parts<true>, dim3(kRescoreGrid), dim3(256), 0, st, ix->cand_s2.p, ix->cand_i2.p, ix->cand_n2.p,
-                           CZ_CAP2, f2, nflag, flag_list, ix->thr2.p, l2, qpad, ix->xb, ix->dpad, (const int*)nullptr, (const int*)nullptr);
+                           CZ_CAP2, f2, nflag, flag_list, ix->thr2.p, l2, qpad, rows.xb, ix->dpad, (const int*)nullptr, (const int*)nullptr);
         hipLaunchKernelGGL(k_coarse_select2<CZ_CAP2>, dim3(f2), dim3(256), 0, st, ix->cand_s2.p, ix->cand_i2.p, ix->cand_n2.p, nflag,
-                           flag_list, f2, nflagB, flag_listB, l2, k, ix->id_base, D_dev, I_dev);
+                           flag_list, f2, nflagB, flag_listB, l2, k, rows.id_base, D_dev, I_dev);
         CSS_LAUNCH_CHECK();
         // what overflowed the second pass too (tens of thousands of rows inside one band): exact fp32 sweep
-        return launch_fixup(ix, qpad, nq, k, ix->gthr.p + q0, flag_listB, nflagB, D_dev, I_dev, sg, st);
+        return launch_fixup(ix, rows, qpad, nq, k, ix->gthr.p + q0, flag_listB, nflagB, D_dev, I_dev, sg, st);
     }
     // queries whose candidate buffer or band overflowed (thousands of duplicate rows, a zero query): exact
     // fp32 sweep on the device, two launches that return at once when the flag count is zero
-    return launch_fixup(ix, qpad, nq, k, ix->gthr.p + q0, flag_list, nflag, D_dev, I_dev, sg, st);
+    return launch_fixup(ix, rows, qpad, nq, k, ix->gthr.p + q0, flag_list, nflag, D_dev, I_dev, sg, st);
 }
 
 // grid of the exact fp32 sweeps (k_scan_small, k_range_small) over the rows in view: enough blocks to fill the chip
 // (8 per CU) but at least ~64 row groups of work each
-void sweep_grid(const css_index* ix, int* G, int64_t* gpb) {
-    const int64_t ngroups = (ix->ntotal + 3) / 4;
+void sweep_grid(const css_index* ix, const Rows& rows, int* G, int64_t* gpb) {
+    const int64_t ngroups = (rows.n + 3) / 4;
     const int64_t G0 = std::max<int64_t>(1, std::min<int64_t>((int64_t)ix->num_cus * 8, (ngroups + 63) / 64));
     *gpb = (ngroups + G0 - 1) / G0;
     *G = (int)((ngroups + *gpb - 1) / *gpb);
 }
 
 // sweep geometry of the small-batch kernel (also the exact fix-up of the candidate paths) for the rows in view
-int make_sweep_geom(const css_index* ix, int k, SweepGeom* sg) {
+int make_sweep_geom(const css_index* ix, const Rows& rows, int k, SweepGeom* sg) {
     sg->nq_sweep = (int)std::min<int64_t>(16, (64 * 1024) / ((int64_t)ix->dpad * 4 + (int64_t)k * 8 + 8));
     CSS_REQUIRE(sg->nq_sweep >= 1, "css_index_search: dim=%d too large for the scan kernel", ix->dim);
-    sweep_grid(ix, &sg->G, &sg->gpb);
+    sweep_grid(ix, rows, &sg->G, &sg->gpb);
     return CSS_OK;
 }
 
@@ -2537,26 +2560,28 @@ constexpr int kRangeSlots = css_index::kRangeSlots;
 constexpr size_t kRangeInitialCap = 4096;    // pool entries per slot before the first growth
 
 template <int NQ, int TT, int METRIC>
-int launch_range_small_t(css_index* ix, const float* qpad, int nq_real, float radius, int G, int64_t gpb, hipStream_t st) {
+int launch_range_small_t(css_index* ix, const Rows& rows, const float* qpad, int nq_real, float radius, int G,
+                         int64_t gpb, hipStream_t st) {
     const size_t lds = (size_t)NQ * ix->dpad * 4;
     auto kern = k_range_small<NQ, TT, METRIC>;
     int rc;
     if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
     ProfScope ps("knn_range_small", st);
-    hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, st, (const float4*)ix->xb, qpad, ix->ntotal, ix->dpad / 64, gpb, nq_real,
-                       ix->cur_mask, radius, ix->range_cnt.p, ix->range_s.p, ix->range_i.p, (unsigned int)ix->range_cap());
+    hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, st, (const float4*)rows.xb, qpad, rows.n, ix->dpad / 64, gpb, nq_real,
+                       rows.mask, radius, ix->range_cnt.p, ix->range_s.p, ix->range_i.p, (unsigned int)ix->range_cap());
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 
 template <int NQ>
-int launch_range_small_nq(css_index* ix, const float* qpad, int nq_real, float radius, int G, int64_t gpb, hipStream_t st) {
+int launch_range_small_nq(css_index* ix, const Rows& rows, const float* qpad, int nq_real, float radius, int G,
+                          int64_t gpb, hipStream_t st) {
     const bool ip = ix->metric == CSS_METRIC_IP;
     if (ix->dpad == 768)
-        return ip ? launch_range_small_t<NQ, 12, CSS_METRIC_IP>(ix, qpad, nq_real, radius, G, gpb, st)
-                  : launch_range_small_t<NQ, 12, CSS_METRIC_L2>(ix, qpad, nq_real, radius, G, gpb, st);
-    return ip ? launch_range_small_t<NQ, 0, CSS_METRIC_IP>(ix, qpad, nq_real, radius, G, gpb, st)
-              : launch_range_small_t<NQ, 0, CSS_METRIC_L2>(ix, qpad, nq_real, radius, G, gpb, st);
+        return ip ? launch_range_small_t<NQ, 12, CSS_METRIC_IP>(ix, rows, qpad, nq_real, radius, G, gpb, st)
+                  : launch_range_small_t<NQ, 12, CSS_METRIC_L2>(ix, rows, qpad, nq_real, radius, G, gpb, st);
+    return ip ? launch_range_small_t<NQ, 0, CSS_METRIC_IP>(ix, rows, qpad, nq_real, radius, G, gpb, st)
+              : launch_range_small_t<NQ, 0, CSS_METRIC_L2>(ix, rows, qpad, nq_real, radius, G, gpb, st);
 }
 
 // queries per sweep: the largest instantiated NQ (16, 8, 2) whose query rows fit 64 KiB of LDS (dim <= 8192: at least 2)
@@ -2567,16 +2592,17 @@ int range_nq_sweep(const css_index* ix) {
 
 // One sweep of all rows for queries qpad[0 .. nqc) (nqc <= range_nq_sweep): counters zeroed, kernel, counters back on
 // the host (waits for the stream).
-int range_sweep(css_index* ix, const float* qpad, int nqc, float radius, unsigned int* cnt_host, hipStream_t st) {
+int range_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, float radius, unsigned int* cnt_host,
+                hipStream_t st) {
     int G;
     int64_t gpb;
-    sweep_grid(ix, &G, &gpb);
+    sweep_grid(ix, rows, &G, &gpb);
     CSS_HIP_TRY(hipMemsetAsync(ix->range_cnt.p, 0, kRangeSlots * sizeof(unsigned int), st));
     int rc;
-    if (nqc <= 1) rc = launch_range_small_nq<1>(ix, qpad, nqc, radius, G, gpb, st);
-    else if (nqc <= 2) rc = launch_range_small_nq<2>(ix, qpad, nqc, radius, G, gpb, st);
-    else if (nqc <= 8) rc = launch_range_small_nq<8>(ix, qpad, nqc, radius, G, gpb, st);
-    else rc = launch_range_small_nq<16>(ix, qpad, nqc, radius, G, gpb, st);
+    if (nqc <= 1) rc = launch_range_small_nq<1>(ix, rows, qpad, nqc, radius, G, gpb, st);
+    else if (nqc <= 2) rc = launch_range_small_nq<2>(ix, rows, qpad, nqc, radius, G, gpb, st);
+    else if (nqc <= 8) rc = launch_range_small_nq<8>(ix, rows, qpad, nqc, radius, G, gpb, st);
+    else rc = launch_range_small_nq<16>(ix, rows, qpad, nqc, radius, G, gpb, st);
     if (rc != CSS_OK) return rc;
     CSS_HIP_TRY(hipMemcpyAsync(cnt_host, ix->range_cnt.p, kRangeSlots * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     CSS_HIP_TRY(hipStreamSynchronize(st));
@@ -2588,44 +2614,6 @@ int range_sweep(css_index* ix, const float* qpad, int nqc, float radius, unsigne
 int range_pool_alloc(css_index* ix, size_t cap) {
     return try_exact_pair(ix->range_s, ix->range_i, kRangeSlots * cap) ? CSS_OK : CSS_ERR_OOM;
 }
-
-// RAII: the index narrowed to rows [row0, row0 + n) with `xh` as their bf16 shadow rows -- every launcher below reads
-// rows, norms, count, id base and the allow-bitmap through the css_index fields, so a row range is searched exactly
-// like an index of its own.  Caller holds ws_mu (export and css_index_ntotal do not look at these fields unguarded).
-struct RowView {
-    css_index* ix;
-    float* xb;
-    float* xnorm2;
-    unsigned short* xh;
-    unsigned char* x8;
-    float* x8s;
-    int64_t ntotal, id_base;
-    const uint32_t* mask;
-    // xh_rows / x8_rows + x8_scales: the range's bf16 OR int8 scratch rows (the other kind null)
-    RowView(css_index* i, int64_t row0, int64_t n, unsigned short* xh_rows, unsigned char* x8_rows = nullptr,
-            float* x8_scales = nullptr)
-        : ix(i), xb(i->xb), xnorm2(i->xnorm2), xh(i->xh), x8(i->x8), x8s(i->x8s), ntotal(i->ntotal), id_base(i->id_base),
-          mask(i->cur_mask) {
-        ix->xb = xb + (size_t)row0 * ix->dpad;
-        ix->xnorm2 = xnorm2 + row0;
-        ix->xh = xh_rows;
-        ix->x8 = x8_rows;
-        ix->x8s = x8_scales;
-        ix->ntotal = n;
-        ix->id_base = id_base + row0;
-        if (mask) ix->cur_mask = mask + row0 / 32;   // (row0 is a multiple of 256)
-    }
-    ~RowView() {
-        ix->xb = xb;
-        ix->xnorm2 = xnorm2;
-        ix->xh = xh;
-        ix->x8 = x8;
-        ix->x8s = x8s;
-        ix->ntotal = ntotal;
-        ix->id_base = id_base;
-        ix->cur_mask = mask;
-    }
-};
 
 int merge_parts(const float* Dp, const int64_t* Ip, int nparts, int64_t stride_d, int64_t stride_i, int64_t nq, int k,
                 int metric, float* D, int64_t* I, int device, void* stream, const char* who) {
@@ -2668,9 +2656,10 @@ int merge_parts(const float* Dp, const int64_t* Ip, int nparts, int64_t stride_d
 // (internal, never crosses the C ABI: "no scratch memory for the row ranges -- take the fallback"; distinct from every
 // css_status so that an error of an inner launch can never be mistaken for it)
 constexpr int kNoRangeScratch = 1;
-int search_noshadow_ranges(css_index* ix, int64_t nq, int k, float* D_dev, int64_t* I_dev, hipStream_t st, bool allow_i8) {
+int search_noshadow_ranges(css_index* ix, const Rows& rows, int64_t nq, int k, float* D_dev, int64_t* I_dev, hipStream_t st,
+                           bool allow_i8) {
     int rc;
-    const int64_t ntotal = ix->ntotal;
+    const int64_t ntotal = rows.n;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return kNoRangeScratch;
     const size_t row_b = (size_t)ix->dpad * 2;
@@ -2695,7 +2684,7 @@ int search_noshadow_ranges(css_index* ix, int64_t nq, int k, float* D_dev, int64
         const int64_t row0 = (int64_t)r * S, n = std::min<int64_t>(S, ntotal - row0);
         if (use_i8) {
             ProfScope ps("knn_rows_to_i8", st);
-            const float* src_ = ix->xb + (size_t)row0 * ix->dpad;
+            const float* src_ = rows.xb + (size_t)row0 * ix->dpad;
             signed char* dst_ = reinterpret_cast<signed char*>(ix->xh_tmp.p);
             const dim3 grid_((unsigned)((n + 3) / 4));
             switch (ix->dpad) {   // (dpad % 256 == 0 and <= 1024: batch_i8_wanted)
@@ -2709,21 +2698,22 @@ int search_noshadow_ranges(css_index* ix, int64_t nq, int k, float* D_dev, int64
             ProfScope ps("knn_rows_to_bf16", st);
             const int64_t n8 = n * ix->dpad / 8;   // (dpad is a multiple of 64)
             const unsigned blocks = (unsigned)std::min<int64_t>((n8 + 255) / 256, (int64_t)ix->num_cus * 64);
-            hipLaunchKernelGGL(k_rows_to_bf16_x8, dim3(blocks), dim3(256), 0, st, ix->xb + (size_t)row0 * ix->dpad, ix->xh_tmp.p, n8);
+            hipLaunchKernelGGL(k_rows_to_bf16_x8, dim3(blocks), dim3(256), 0, st, rows.xb + (size_t)row0 * ix->dpad, ix->xh_tmp.p, n8);
             CSS_LAUNCH_CHECK();
         }
         if (nranges > 1) {
             Dp = ix->rng_d.p + (size_t)r * nq * k;
             Ip = ix->rng_i.p + (size_t)r * nq * k;
         }
-        RowView view(ix, row0, n, use_i8 ? nullptr : ix->xh_tmp.p, use_i8 ? reinterpret_cast<unsigned char*>(ix->xh_tmp.p) : nullptr,
-                     use_i8 ? ix->x8s_tmp.p : nullptr);
+        const Rows sub = rows.range(row0, n, ix->dpad, use_i8 ? nullptr : ix->xh_tmp.p,
+                                    use_i8 ? reinterpret_cast<const unsigned char*>(ix->xh_tmp.p) : nullptr,
+                                    use_i8 ? ix->x8s_tmp.p : nullptr);
         SweepGeom sg;
-        if ((rc = make_sweep_geom(ix, k, &sg)) != CSS_OK) return rc;
+        if ((rc = make_sweep_geom(ix, sub, k, &sg)) != CSS_OK) return rc;
         const int chunk = coarse_max_chunk(ix);
         for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
             const int nqc = (int)std::min<int64_t>(chunk, nq - q0);
-            if ((rc = launch_scan_coarse(ix, (int)q0, nqc, k, Dp, Ip, st, sg, false, use_i8,
+            if ((rc = launch_scan_coarse(ix, sub, (int)q0, nqc, k, Dp, Ip, st, sg, false, use_i8,
                                          r == nranges - 1 && q0 + nqc == nq)) != CSS_OK) return rc;
         }
     }
@@ -2771,15 +2761,15 @@ int prep_queries(css_index* ix, const float* src, int64_t nq, int normalize_q, f
 }
 
 // q_dev: raw [nq, dim] device queries.  Caller holds ws_mu and a shared lock on mu.
-int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int normalize_q, float* D_dev,
+int search_dev_enqueue(css_index* ix, const Rows& rows, const float* q_dev, int64_t nq, int k, int normalize_q, float* D_dev,
                        int64_t* I_dev, hipStream_t st);
-int search_dev_locked(css_index* ix, const float* q_dev, int64_t nq, int k, int normalize_q, float* D_dev,
+int search_dev_locked(css_index* ix, const Rows& rows, const float* q_dev, int64_t nq, int k, int normalize_q, float* D_dev,
                       int64_t* I_dev, hipStream_t st) {
     WsTurn turn(ix, st);
     if (turn.rc != CSS_OK) return turn.rc;
-    return search_dev_enqueue(ix, q_dev, nq, k, normalize_q, D_dev, I_dev, st);
+    return search_dev_enqueue(ix, rows, q_dev, nq, k, normalize_q, D_dev, I_dev, st);
 }
-int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int normalize_q, float* D_dev,
+int search_dev_enqueue(css_index* ix, const Rows& rows, const float* q_dev, int64_t nq, int k, int normalize_q, float* D_dev,
                        int64_t* I_dev, hipStream_t st) {
     CSS_REQUIRE(k >= 1 && k <= CSS_MAX_K, "css_index_search: k=%d outside [1, %d]", k, CSS_MAX_K);
     CSS_REQUIRE(nq >= 0 && nq < (1 << 24), "css_index_search: nq=%lld out of range", (long long)nq);
@@ -2792,7 +2782,7 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
     if ((rc = ix->qnorm2.grow((size_t)nq + 256)) != CSS_OK) return rc;
     if ((rc = ix->qerr2.grow((size_t)nq + 256)) != CSS_OK) return rc;
     // (int8 rows: the int8 queries' error norms of every chunk of this search -- never reallocated between two chunks)
-    if (ix->x8 != nullptr && (rc = ix->qerr2_i8.grow((size_t)nq + 256)) != CSS_OK) return rc;
+    if (rows.x8 != nullptr && (rc = ix->qerr2_i8.grow((size_t)nq + 256)) != CSS_OK) return rc;
     if ((rc = ix->gthr.grow((size_t)nq + 256)) != CSS_OK) return rc;
     // 1..4 queries through the sweep cascade: its init launch prepares the query rows as well (one launch less in front
     // of a 1.4 ms search).  Which shadow rows a search reads is decided once (the per-index int8 feedback counts searches).
@@ -2800,17 +2790,17 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
     // int8 MFMA where that applies (mfma_sweep_applies); where not, 3 or 4 queries are sooner through the int8 scan of
     // batches from 3 M rows on (1.98 ms; 1 M rows: sweep 0.34 vs scan 0.39 ms; k = 100 goes through the bf16 scan, 3.2 ms
     // against the sweep's 2.8-2.9); two queries always sweep (1.36 vs 1.93 ms).  One session.
-    const bool i8_scan_ok = ix->x8 != nullptr && ix->metric == CSS_METRIC_IP && ix->dpad % 256 == 0 && ix->dpad <= 1024 &&
+    const bool i8_scan_ok = rows.x8 != nullptr && ix->metric == CSS_METRIC_IP && ix->dpad % 256 == 0 && ix->dpad <= 1024 &&
                             env.batch_i8 != 0;
-    const bool mfma_sweep_ok = mfma_sweep_applies(ix, nq, k);
-    const int sweep_max = (k <= 32 && ix->ntotal >= 3000000 && i8_scan_ok) ? 2 : 4;   // VALU sweep
-    const bool sweep_base = ix->ntotal > 0 && k <= CSS_KERNEL_MAX_K && (ix->xh != nullptr || ix->x8 != nullptr) &&
+    const bool mfma_sweep_ok = mfma_sweep_applies(ix, rows, nq, k);
+    const int sweep_max = (k <= 32 && rows.n >= 3000000 && i8_scan_ok) ? 2 : 4;   // VALU sweep
+    const bool sweep_base = rows.n > 0 && k <= CSS_KERNEL_MAX_K && (rows.xh != nullptr || rows.x8 != nullptr) &&
                             (ix->search_mode == CSS_SEARCH_COARSE ||
-                             (ix->search_mode == CSS_SEARCH_AUTO && (nq > 4 || k > 32 || ix->ntotal >= 100000)));
-    const bool sweep_i8 = sweep_base && ix->x8 != nullptr && (nq <= sweep_max || mfma_sweep_ok) && sweep_uses_i8(ix);
-    const bool sweep_path = sweep_base && ((mfma_sweep_ok && sweep_i8) || (nq <= sweep_max && (sweep_i8 || ix->xh != nullptr)));
+                             (ix->search_mode == CSS_SEARCH_AUTO && (nq > 4 || k > 32 || rows.n >= 100000)));
+    const bool sweep_i8 = sweep_base && rows.x8 != nullptr && (nq <= sweep_max || mfma_sweep_ok) && sweep_uses_i8(ix, rows);
+    const bool sweep_path = sweep_base && ((mfma_sweep_ok && sweep_i8) || (nq <= sweep_max && (sweep_i8 || rows.xh != nullptr)));
     if (!sweep_path && (rc = prep_queries(ix, q_dev, nq, normalize_q, ix->qerr2.p, st)) != CSS_OK) return rc;
-    if (ix->ntotal == 0) {
+    if (rows.n == 0) {
         const int64_t n = nq * k;
         hipLaunchKernelGGL(k_fill_pad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, n,
                            ix->metric == CSS_METRIC_IP ? -FLT_MAX : FLT_MAX);
@@ -2819,7 +2809,7 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
     }
     CSS_REQUIRE(k <= CSS_KERNEL_MAX_K, "css_index_search: internal: k=%d reached the scan kernels (limit %d)", k, CSS_KERNEL_MAX_K);
     SweepGeom sg;
-    if ((rc = make_sweep_geom(ix, k, &sg)) != CSS_OK) return rc;
+    if ((rc = make_sweep_geom(ix, rows, k, &sg)) != CSS_OK) return rc;
 
     const int mode = ix->search_mode;
     const bool batch_ok = nq > 16 && k <= kMfmaMaxK && ix->dpad % MF_BK == 0;  // the MFMA scan kernels apply
@@ -2829,21 +2819,21 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
     // the exact kernels keep k-entry lists per block), with k = 10 from ~100 k rows on (50 k 0.093 / 0.074, 100 k
     // 0.099 / 0.119, 1 M 0.25 / 0.64).  Round 2 switched at 1.2 M / 0.4 M rows: the cascade has since lost most of its
     // fixed cost and the few-query sweep reads int8 rows.
-    const bool coarse_pays = nq > 4 || k > 32 || ix->ntotal >= 100000;
+    const bool coarse_pays = nq > 4 || k > 32 || rows.n >= 100000;
     const bool want_split = mode == CSS_SEARCH_SPLIT;   // split-operand candidate scan from the fp32 rows
     const bool want_candidates = mode == CSS_SEARCH_COARSE || (mode == CSS_SEARCH_AUTO && coarse_pays);
     // Which shadow rows this search reads is decided HERE, once (the per-index int8 feedback counts searches, not chunks).
     // An index with int8 rows only takes the candidate path where the int8 rows are chosen; otherwise it goes on like an
     // index without shadow rows (bf16 scratch ranges for batches, the exact kernels for a few queries).
-    if (want_candidates && (ix->xh != nullptr || ix->x8 != nullptr)) {
+    if (want_candidates && (rows.xh != nullptr || rows.x8 != nullptr)) {
         const bool sweep = sweep_path;
-        const bool use_i8 = ix->x8 != nullptr && (sweep ? sweep_i8 : batch_i8_wanted(ix, k, ix->ntotal, nq));
-        if (use_i8 || ix->xh != nullptr) {
-            if (sweep) return launch_scan_coarse(ix, 0, (int)nq, k, D_dev, I_dev, st, sg, true, use_i8, true, q_dev, normalize_q);
+        const bool use_i8 = rows.x8 != nullptr && (sweep ? sweep_i8 : batch_i8_wanted(ix, k, rows.n, nq));
+        if (use_i8 || rows.xh != nullptr) {
+            if (sweep) return launch_scan_coarse(ix, rows, 0, (int)nq, k, D_dev, I_dev, st, sg, true, use_i8, true, q_dev, normalize_q);
             const int chunk = coarse_max_chunk(ix);
             for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
                 const int nqc = (int)std::min<int64_t>(chunk, nq - q0);
-                if ((rc = launch_scan_coarse(ix, (int)q0, nqc, k, D_dev, I_dev, st, sg, false, use_i8, q0 + nqc == nq)) != CSS_OK)
+                if ((rc = launch_scan_coarse(ix, rows, (int)q0, nqc, k, D_dev, I_dev, st, sg, false, use_i8, q0 + nqc == nq)) != CSS_OK)
                     return rc;
             }
             return CSS_OK;
@@ -2851,34 +2841,34 @@ int search_dev_enqueue(css_index* ix, const float* q_dev, int64_t nq, int k, int
     }
     // no shadow rows: batches take the same cascade over bf16 rows rounded on the fly, one row range at a time
     // (a k beyond the MFMA kernels, or no HBM left for the scratch rows: the split-operand scan)
-    if (want_candidates && ix->xh == nullptr && nq > 16 && ix->dpad % 128 == 0) {
-        rc = search_noshadow_ranges(ix, nq, k, D_dev, I_dev, st, ix->x8 == nullptr);
+    if (want_candidates && rows.xh == nullptr && nq > 16 && ix->dpad % 128 == 0) {
+        rc = search_noshadow_ranges(ix, rows, nq, k, D_dev, I_dev, st, rows.x8 == nullptr);
         if (rc != kNoRangeScratch) return rc;
     }
-    if (batch_ok && k + kSplitExtra <= kMfmaMaxK && (want_split || (want_candidates && ix->xh == nullptr))) {
+    if (batch_ok && k + kSplitExtra <= kMfmaMaxK && (want_split || (want_candidates && rows.xh == nullptr))) {
         for (int64_t q0 = 0; q0 < nq; q0 += 4096) {   // (chunked like the bf16 cascade: candidate buffers are per query)
             const int nqc = (int)std::min<int64_t>(4096, nq - q0);
-            rc = ix->metric == CSS_METRIC_IP ? launch_scan_split_rescore<CSS_METRIC_IP>(ix, (int)q0, nqc, k, D_dev, I_dev, sg, st)
-                                             : launch_scan_split_rescore<CSS_METRIC_L2>(ix, (int)q0, nqc, k, D_dev, I_dev, sg, st);
+            rc = ix->metric == CSS_METRIC_IP ? launch_scan_split_rescore<CSS_METRIC_IP>(ix, rows, (int)q0, nqc, k, D_dev, I_dev, sg, st)
+                                             : launch_scan_split_rescore<CSS_METRIC_L2>(ix, rows, (int)q0, nqc, k, D_dev, I_dev, sg, st);
             if (rc != CSS_OK) return rc;
         }
         return CSS_OK;
     }
     // shadow-less batches whose k leaves no room for the split scan's extra ranks (k = 61 .. 64): the fp32-input MFMA
     // scan, not 16-query VALU sweeps
-    if (batch_ok && (want_split || (want_candidates && ix->xh == nullptr))) {
-        return ix->metric == CSS_METRIC_IP ? launch_scan_fp32mfma<CSS_METRIC_IP>(ix, (int)nq, k, D_dev, I_dev, st)
-                                           : launch_scan_fp32mfma<CSS_METRIC_L2>(ix, (int)nq, k, D_dev, I_dev, st);
+    if (batch_ok && (want_split || (want_candidates && rows.xh == nullptr))) {
+        return ix->metric == CSS_METRIC_IP ? launch_scan_fp32mfma<CSS_METRIC_IP>(ix, rows, (int)nq, k, D_dev, I_dev, st)
+                                           : launch_scan_fp32mfma<CSS_METRIC_L2>(ix, rows, (int)nq, k, D_dev, I_dev, st);
     }
     // exact fp32 arithmetic inside the scan: fp32-input MFMA for batches, VALU sweeps for up to 16 queries
     if (batch_ok && mode == CSS_SEARCH_EXACT_FP32) {
-        return ix->metric == CSS_METRIC_IP ? launch_scan_fp32mfma<CSS_METRIC_IP>(ix, (int)nq, k, D_dev, I_dev, st)
-                                           : launch_scan_fp32mfma<CSS_METRIC_L2>(ix, (int)nq, k, D_dev, I_dev, st);
+        return ix->metric == CSS_METRIC_IP ? launch_scan_fp32mfma<CSS_METRIC_IP>(ix, rows, (int)nq, k, D_dev, I_dev, st)
+                                           : launch_scan_fp32mfma<CSS_METRIC_L2>(ix, rows, (int)nq, k, D_dev, I_dev, st);
     }
     if ((rc = grow_part(ix, (size_t)sg.nq_sweep * sg.G * k)) != CSS_OK) return rc;
     for (int64_t q0 = 0; q0 < nq; q0 += sg.nq_sweep) {
         const int nqc = (int)std::min<int64_t>(sg.nq_sweep, nq - q0);
-        if ((rc = search_chunk_small(ix, (int)q0, nqc, k, sg, D_dev, I_dev, st)) != CSS_OK) return rc;
+        if ((rc = search_chunk_small(ix, rows, (int)q0, nqc, k, sg, D_dev, I_dev, st)) != CSS_OK) return rc;
     }
     return CSS_OK;
 }
@@ -2940,24 +2930,21 @@ int css_index_free(css_index* ix) {
             (void)hipEventDestroy(f->ev);
             (void)hipHostFree(f->h_nflag);
         }
-    // the row storage here, every workspace by its DevBuf in `delete ix` (hipFree waits for the device: nothing
-    // enqueued by a _dev call still runs)
-    for (void* p : {(void*)ix->xb, (void*)ix->xnorm2, (void*)ix->xh, (void*)ix->x8, (void*)ix->x8s})
-        if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
     if (ix->ingest_ev) (void)hipEventDestroy(ix->ingest_ev);
     if (ix->ws_ev) (void)hipEventDestroy(ix->ws_ev);
     (void)hipStreamDestroy(ix->stream);
-    delete ix;   // (inside the DeviceGuard: the DevBuf members free on the index's device)
+    // the row storage and every workspace by their DevBufs, inside the DeviceGuard: they free on the index's device
+    // (hipFree waits for the device: nothing enqueued by a _dev call still runs)
+    delete ix;
     return CSS_OK;
 }
 
 int css_index_reset(css_index* ix) {
     CSS_REQUIRE(ix, "css_index_reset: NULL index");
     std::unique_lock<std::shared_mutex> lk(ix->mu);
-    ix->ntotal = 0;
-    ix->ntotal_pub.store(0);
-    if (!ix->xh) ix->shadow = -1;
+    set_ntotal(ix, 0);
+    if (!ix->xh.p) ix->shadow = -1;
     DeviceGuard g(ix->device);
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
     if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ws_ev, 0));   // a search enqueued on another stream still reads maxn2
@@ -2977,7 +2964,7 @@ int compact_rows(css_index* ix, const uint32_t* keep, int64_t n, int64_t first, 
     // the rows below the first removed one stay: one read for the maxima
     for (int64_t c0 = 0; c0 < first; c0 += kCompactWindowRows) {
         const int64_t nc = std::min(kCompactWindowRows, first - c0);
-        hipLaunchKernelGGL(k_rows_maxima, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, st, ix->xb + (size_t)c0 * dpad, nc, ix->dim,
+        hipLaunchKernelGGL(k_rows_maxima, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, st, ix->xb.p + (size_t)c0 * dpad, nc, ix->dim,
                            dpad, ix->maxn2.p);
         CSS_LAUNCH_CHECK();
     }
@@ -3014,14 +3001,14 @@ int compact_rows(css_index* ix, const uint32_t* keep, int64_t n, int64_t first, 
             hipLaunchKernelGGL(k_keep_prefix, dim3(1), dim3(1024), 0, st, ix->compact_bits.p, ix->compact_pre.p, (int)nw);
             CSS_LAUNCH_CHECK();
             const unsigned blocks = (unsigned)((L + 3) / 4);
-            float* dst = ix->xb + (size_t)dnext * dpad;
-            unsigned short* dh = ix->xh ? ix->xh + (size_t)dnext * dpad : nullptr;
-            unsigned char* d8 = ix->x8 ? ix->x8 + (size_t)dnext * dpad : nullptr;
-            float* d8s = ix->x8 ? ix->x8s + dnext : nullptr;
-            const float* src = ix->xb + (size_t)s0 * dpad;
+            float* dst = ix->xb.p + (size_t)dnext * dpad;
+            unsigned short* dh = ix->xh.p ? ix->xh.p + (size_t)dnext * dpad : nullptr;
+            unsigned char* d8 = ix->x8.p ? ix->x8.p + (size_t)dnext * dpad : nullptr;
+            float* d8s = ix->x8.p ? ix->x8s.p + dnext : nullptr;
+            const float* src = ix->xb.p + (size_t)s0 * dpad;
             if (dnext + surv <= src0) {   // destinations wholly below the sources: straight into place
                 hipLaunchKernelGGL(k_compact_rows, dim3(blocks), dim3(256), 0, st, ix->compact_bits.p, ix->compact_pre.p, L, src, dst,
-                                   ix->xnorm2 + dnext, ix->dim, dpad, dh, ix->maxn2.p, d8, d8s);
+                                   ix->xnorm2.p + dnext, ix->dim, dpad, dh, ix->maxn2.p, d8, d8s);
                 CSS_LAUNCH_CHECK();
             } else {                      // they overlap: through the scratch rows, the kernel boundary orders read and overwrite
                 if ((rc = ix->stage.grow((size_t)W * dpad)) != CSS_OK) return rc;
@@ -3029,7 +3016,7 @@ int compact_rows(css_index* ix, const uint32_t* keep, int64_t n, int64_t first, 
                                    ix->stage.p, dpad);
                 CSS_LAUNCH_CHECK();
                 hipLaunchKernelGGL(k_compact_rows, dim3((unsigned)((surv + 3) / 4)), dim3(256), 0, st, (const uint32_t*)nullptr,
-                                   (const uint32_t*)nullptr, surv, ix->stage.p, dst, ix->xnorm2 + dnext, ix->dim, dpad, dh, ix->maxn2.p,
+                                   (const uint32_t*)nullptr, surv, ix->stage.p, dst, ix->xnorm2.p + dnext, ix->dim, dpad, dh, ix->maxn2.p,
                                    d8, d8s);
                 CSS_LAUNCH_CHECK();
             }
@@ -3045,7 +3032,7 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
     CSS_REQUIRE(ix && removed_out, "css_index_remove_rows: NULL argument");
     *removed_out = 0;
     std::unique_lock<std::shared_mutex> lk(ix->mu);
-    std::lock_guard<std::mutex> wl(ix->ws_mu);   // (a search in progress may have the row view narrowed)
+    std::lock_guard<std::mutex> wl(ix->ws_mu);   // (stage, compact_bits / compact_pre, ws_pending)
     const int64_t n = ix->ntotal;
     if (n == 0) return CSS_OK;
     CSS_REQUIRE(keep_bits_host, "css_index_remove_rows: keep_bits is NULL");
@@ -3070,9 +3057,8 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
     const hipError_t e = hipStreamSynchronize(ix->stream);
     if (rc != CSS_OK) return rc;
     if (e != hipSuccess) return css::hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
-    ix->ntotal = kept;
-    ix->ntotal_pub.store(kept);
-    if (kept == 0 && !ix->xh) ix->shadow = -1;   // emptied: as css_index_reset
+    set_ntotal(ix, kept);
+    if (kept == 0 && !ix->xh.p) ix->shadow = -1;   // emptied: as css_index_reset
     for (css_index::I8Feedback* f : {&ix->fb_batch, &ix->fb_sweep}) {   // (it described other rows; its copy has landed)
         f->pending = false;
         f->backoff = 0;
@@ -3172,9 +3158,9 @@ int css_index_last_swept(css_index* ix, int64_t* n) {
 int css_index_shadow_info(css_index* ix, int* has_bf16, int* has_int8) {
     CSS_REQUIRE(ix && has_bf16 && has_int8, "css_index_shadow_info: NULL argument");
     std::shared_lock<std::shared_mutex> lk(ix->mu);
-    std::lock_guard<std::mutex> wl(ix->ws_mu);   // (a RowView of a running enqueue swaps xh)
-    *has_bf16 = ix->xh != nullptr ? 1 : 0;
-    *has_int8 = ix->x8 != nullptr ? 1 : 0;
+    const Rows rows = rows_of(ix);
+    *has_bf16 = rows.xh != nullptr ? 1 : 0;
+    *has_int8 = rows.x8 != nullptr ? 1 : 0;
     return CSS_OK;
 }
 
@@ -3189,16 +3175,9 @@ int css_index_set_shadow(css_index* ix, int policy) {
     }
     DeviceGuard g(ix->device);
     ix->shadow_policy = policy;
-    if (ix->xh) {  // start over: the next add decides again
-        CSS_HIP_TRY(hipFree(ix->xh));
-        ix->xh = nullptr;
-    }
-    if (ix->x8) {
-        CSS_HIP_TRY(hipFree(ix->x8));
-        CSS_HIP_TRY(hipFree(ix->x8s));
-        ix->x8 = nullptr;
-        ix->x8s = nullptr;
-    }
+    CSS_HIP_TRY(ix->xh.drop());   // start over: the next add decides again
+    CSS_HIP_TRY(ix->x8.drop());
+    CSS_HIP_TRY(ix->x8s.drop());
     ix->shadow = -1;
     return CSS_OK;
 }
@@ -3230,8 +3209,7 @@ int css_index_add(css_index* ix, const float* x_host, int64_t n, int normalize) 
                                    hipMemcpyHostToDevice, ix->stream));
         if ((rc = ingest(ix, ix->stage.p, m, normalize, false, 0, 0, ix->stream)) != CSS_OK) return rc;
         CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
-        ix->ntotal += m;
-        ix->ntotal_pub.store(ix->ntotal);
+        set_ntotal(ix, ix->ntotal + m);
     }
     return CSS_OK;
 }
@@ -3251,8 +3229,7 @@ int css_index_add_dev(css_index* ix, const float* x_dev, int64_t n, int normaliz
         const int64_t m = std::min<int64_t>(1ll << 30, n - r0);
         if ((rc = ingest(ix, x_dev + (size_t)r0 * ix->dim, m, normalize, false, 0, 0, (hipStream_t)stream)) != CSS_OK)
             return rc;
-        ix->ntotal += m;
-        ix->ntotal_pub.store(ix->ntotal);
+        set_ntotal(ix, ix->ntotal + m);
     }
     // the rows are written asynchronously on the caller's stream: later searches / reallocations / exports wait for this
     CSS_HIP_TRY(hipEventRecord(ix->ingest_ev, (hipStream_t)stream));
@@ -3274,8 +3251,7 @@ int css_index_add_synthetic(css_index* ix, int64_t n, uint64_t seed, int64_t fir
         const int64_t m = std::min<int64_t>(1ll << 30, n - r0);
         if ((rc = ingest(ix, nullptr, m, normalize, true, seed, first_row + r0, (hipStream_t)stream)) != CSS_OK)
             return rc;
-        ix->ntotal += m;
-        ix->ntotal_pub.store(ix->ntotal);
+        set_ntotal(ix, ix->ntotal + m);
     }
     CSS_HIP_TRY(hipEventRecord(ix->ingest_ev, (hipStream_t)stream));
     ix->ingest_pending = true;
@@ -3286,35 +3262,28 @@ int css_index_export(const css_index* cix, int64_t row0, int64_t n, float* x_out
     css_index* ix = const_cast<css_index*>(cix);
     CSS_REQUIRE(ix && x_out_host, "css_index_export: NULL argument");
     std::shared_lock<std::shared_mutex> lk(ix->mu);
-    std::lock_guard<std::mutex> wl(ix->ws_mu);   // (a search may have the index narrowed to a row range while it enqueues)
-    CSS_REQUIRE(row0 >= 0 && n >= 0 && row0 + n <= ix->ntotal, "css_index_export: rows [%lld, %lld) outside [0, %lld)",
-                (long long)row0, (long long)(row0 + n), (long long)ix->ntotal);
+    const Rows rows = rows_of(ix);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && row0 + n <= rows.n, "css_index_export: rows [%lld, %lld) outside [0, %lld)",
+                (long long)row0, (long long)(row0 + n), (long long)rows.n);
     if (n == 0) return CSS_OK;
     DeviceGuard g(ix->device);
     if (ix->ingest_pending) CSS_HIP_TRY(hipEventSynchronize(ix->ingest_ev));
-    CSS_HIP_TRY(hipMemcpy2D(x_out_host, (size_t)ix->dim * 4, ix->xb + (size_t)row0 * ix->dpad, (size_t)ix->dpad * 4,
+    CSS_HIP_TRY(hipMemcpy2D(x_out_host, (size_t)ix->dim * 4, rows.xb + (size_t)row0 * ix->dpad, (size_t)ix->dpad * 4,
                             (size_t)ix->dim * 4, (size_t)n, hipMemcpyDeviceToHost));
     return CSS_OK;
 }
 
-// RAII: the allow-bitmap of the search in progress (read by the kernel launchers); caller holds ws_mu
 namespace {
-struct MaskScope {
-    css_index* ix;
-    MaskScope(css_index* i, const uint32_t* m) : ix(i) { ix->cur_mask = m; }
-    ~MaskScope() { ix->cur_mask = nullptr; }
-};
-
 // Host entry points, all on the index's own stream.  The caller's allow-bitmap (one bit per row; null or an empty
-// index: no mask) copied into mask_ws:
-int upload_allow_bits(css_index* ix, const uint32_t* bits_host, const uint32_t** mask_dev) {
-    *mask_dev = nullptr;
-    if (!bits_host || ix->ntotal == 0) return CSS_OK;
-    const size_t words = (size_t)((ix->ntotal + 31) / 32);
+// index: no mask) copied into mask_ws and made the mask of the call's rows:
+int upload_allow_bits(css_index* ix, const uint32_t* bits_host, Rows* rows) {
+    rows->mask = nullptr;
+    if (!bits_host || rows->n == 0) return CSS_OK;
+    const size_t words = (size_t)((rows->n + 31) / 32);
     int rc;
     if ((rc = ix->mask_ws.grow(words)) != CSS_OK) return rc;
     CSS_HIP_TRY(hipMemcpyAsync(ix->mask_ws.p, bits_host, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
-    *mask_dev = ix->mask_ws.p;
+    rows->mask = ix->mask_ws.p;
     return CSS_OK;
 }
 
@@ -3341,32 +3310,29 @@ int fetch_out(css_index* ix, size_t n, const float* d_out, const int64_t* i_out,
 // id), so the concatenation is the exact top-k, and one final sort puts entries whose scores came from different
 // summation orders (fix-up sweep vs rescoring: <= 1e-6 apart) in order.  Everything is enqueued on `st`; nothing
 // waits for the device.  Caller holds ws_mu and a shared lock on mu.
-int search_any_k(css_index* ix, const float* q_dev, int64_t nq, int k, int normalize_q, const uint32_t* allow_dev,
-                 float* D_dev, int64_t* I_dev, hipStream_t st) {
+int search_any_k(css_index* ix, const Rows& rows, const float* q_dev, int64_t nq, int k, int normalize_q, float* D_dev,
+                 int64_t* I_dev, hipStream_t st) {
     CSS_REQUIRE(k >= 1 && k <= CSS_MAX_K, "css_index_search: k=%d outside [1, %d]", k, CSS_MAX_K);
-    if (k <= CSS_KERNEL_MAX_K || ix->ntotal == 0 || nq == 0) {
-        MaskScope ms(ix, allow_dev);
-        return search_dev_locked(ix, q_dev, nq, k, normalize_q, D_dev, I_dev, st);
-    }
+    if (k <= CSS_KERNEL_MAX_K || rows.n == 0 || nq == 0)
+        return search_dev_locked(ix, rows, q_dev, nq, k, normalize_q, D_dev, I_dev, st);
     CSS_REQUIRE(nq < (1 << 24), "css_index_search: nq=%lld out of range", (long long)nq);
     int rc;
-    const int64_t words = (ix->ntotal + 31) / 32;
+    const int64_t words = (rows.n + 31) / 32;
     WsTurn turn(ix, st);   // excl_ws is a shared workspace, in use until the final sort is enqueued
     if (turn.rc != CSS_OK) return turn.rc;
     if ((rc = ix->excl_ws.grow((size_t)words)) != CSS_OK) return rc;
+    Rows pass = rows;   // the same rows under the exclusion bitmap
+    pass.mask = ix->excl_ws.p;
     for (int64_t q = 0; q < nq; ++q) {
-        hipLaunchKernelGGL(k_mask_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, ix->excl_ws.p, allow_dev, words);
+        hipLaunchKernelGGL(k_mask_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, ix->excl_ws.p, rows.mask, words);
         CSS_LAUNCH_CHECK();
         for (int p = 0; p < k; p += CSS_KERNEL_MAX_K) {
             const int kk = std::min(CSS_KERNEL_MAX_K, k - p);
             float* Dq = D_dev + (size_t)q * k + p;
             int64_t* Iq = I_dev + (size_t)q * k + p;
-            {
-                MaskScope ms(ix, ix->excl_ws.p);
-                if ((rc = search_dev_locked(ix, q_dev + (size_t)q * ix->dim, 1, kk, normalize_q, Dq, Iq, st)) != CSS_OK) return rc;
-            }
+            if ((rc = search_dev_locked(ix, pass, q_dev + (size_t)q * ix->dim, 1, kk, normalize_q, Dq, Iq, st)) != CSS_OK) return rc;
             if (p + kk < k) {
-                hipLaunchKernelGGL(k_mask_clear, dim3(1), dim3(CSS_KERNEL_MAX_K), 0, st, ix->excl_ws.p, (const int64_t*)Iq, kk, ix->id_base);
+                hipLaunchKernelGGL(k_mask_clear, dim3(1), dim3(CSS_KERNEL_MAX_K), 0, st, ix->excl_ws.p, (const int64_t*)Iq, kk, rows.id_base);
                 CSS_LAUNCH_CHECK();
             }
         }
@@ -3385,7 +3351,7 @@ int css_index_search_masked_dev(css_index* ix, const float* q_dev, int64_t nq, i
     std::shared_lock<std::shared_mutex> lk(ix->mu);
     std::lock_guard<std::mutex> wl(ix->ws_mu);
     DeviceGuard g(ix->device);
-    return search_any_k(ix, q_dev, nq, k, normalize_q, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
+    return search_any_k(ix, rows_of(ix, allow_bits_dev), q_dev, nq, k, normalize_q, D_dev, I_dev, (hipStream_t)stream);
 }
 
 int css_index_search_dev(css_index* ix, const float* q_dev, int64_t nq, int k, int normalize_q, float* D_dev,
@@ -3412,15 +3378,15 @@ int css_index_search_masked(css_index* ix, const float* q_host, int64_t nq, int 
     const bool staged = q_bytes <= css_index::kHostStage && out_bytes <= css_index::kHostStage;
     if (staged && ix->h_stage == nullptr)
         CSS_HIP_TRY(hipHostMalloc((void**)&ix->h_stage, 2 * css_index::kHostStage, hipHostMallocDefault));
-    const uint32_t* mask_dev;
-    if ((rc = upload_allow_bits(ix, allow_bits_host, &mask_dev)) != CSS_OK) return rc;
+    Rows rows = rows_of(ix);
+    if ((rc = upload_allow_bits(ix, allow_bits_host, &rows)) != CSS_OK) return rc;
     if (staged) {
         memcpy(ix->h_stage, q_host, q_bytes);
         CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, ix->h_stage, q_bytes, hipMemcpyHostToDevice, ix->stream));
     } else {
         CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, q_host, q_bytes, hipMemcpyHostToDevice, ix->stream));
     }
-    if ((rc = search_any_k(ix, ix->q_raw.p, nq, k, normalize_q, mask_dev, d_out, i_out, ix->stream)) != CSS_OK) return rc;
+    if ((rc = search_any_k(ix, rows, ix->q_raw.p, nq, k, normalize_q, d_out, i_out, ix->stream)) != CSS_OK) return rc;
     if (staged) {   // one copy into pinned memory, one wait
         char* back = ix->h_stage + css_index::kHostStage;
         CSS_HIP_TRY(hipMemcpyAsync(back, i_out, out_bytes, hipMemcpyDeviceToHost, ix->stream));
@@ -3440,11 +3406,10 @@ int css_index_search(css_index* ix, const float* q_host, int64_t nq, int k, int 
 
 namespace {
 // The anchors' rows gathered as queries, the ordinary search (search_any_k: every mode, shadow policy, k and chunking
-// as css_index_search_masked_dev has them) at k + 1 when the anchor is to go, and the compaction to k.  The gather
-// reads the real rows before any search narrows the handle to a row range.  Everything is enqueued on `st`.  Caller
-// holds ws_mu and a shared lock on mu.
-int search_rows_enqueue(css_index* ix, const int64_t* ids_dev, int64_t nq, int k, int exclude_self,
-                        const uint32_t* allow_dev, float* D_dev, int64_t* I_dev, hipStream_t st) {
+// as css_index_search_masked_dev has them) at k + 1 when the anchor is to go, and the compaction to k.  Everything is
+// enqueued on `st`.  Caller holds ws_mu and a shared lock on mu.
+int search_rows_enqueue(css_index* ix, const Rows& rows, const int64_t* ids_dev, int64_t nq, int k, int exclude_self,
+                        float* D_dev, int64_t* I_dev, hipStream_t st) {
     const int kk = k + (exclude_self ? 1 : 0);
     int rc;
     WsTurn turn(ix, st);   // (until the end: whatever is launched uses the gathered rows)
@@ -3456,10 +3421,10 @@ int search_rows_enqueue(css_index* ix, const int64_t* ids_dev, int64_t nq, int k
     if ((rc = ix->rowq_d.grow((size_t)nq * kk)) != CSS_OK) return rc;
     if ((rc = ix->rowq_i.grow((size_t)nq * kk)) != CSS_OK) return rc;
     const dim3 grid((unsigned)((nq + 3) / 4));
-    hipLaunchKernelGGL(k_gather_queries, grid, dim3(256), 0, st, (const float*)ix->xb, ids_dev, ix->rowq.p, ix->rowq_flag.p, nq,
-                       ix->ntotal, ix->id_base, ix->dim, ix->dpad);
+    hipLaunchKernelGGL(k_gather_queries, grid, dim3(256), 0, st, rows.xb, ids_dev, ix->rowq.p, ix->rowq_flag.p, nq, rows.n,
+                       rows.id_base, ix->dim, ix->dpad);
     CSS_LAUNCH_CHECK();
-    if ((rc = search_any_k(ix, ix->rowq.p, nq, kk, 0, allow_dev, ix->rowq_d.p, ix->rowq_i.p, st)) != CSS_OK) return rc;
+    if ((rc = search_any_k(ix, rows, ix->rowq.p, nq, kk, 0, ix->rowq_d.p, ix->rowq_i.p, st)) != CSS_OK) return rc;
     hipLaunchKernelGGL(k_drop_self, grid, dim3(256), 0, st, (const float*)ix->rowq_d.p, (const int64_t*)ix->rowq_i.p, ids_dev,
                        (const int*)ix->rowq_flag.p, nq, kk, k, exclude_self ? 1 : 0,
                        ix->metric == CSS_METRIC_IP ? -FLT_MAX : FLT_MAX, D_dev, I_dev);
@@ -3486,7 +3451,7 @@ int css_index_search_rows_dev(css_index* ix, const int64_t* ids_dev, int64_t nq,
     std::shared_lock<std::shared_mutex> lk(ix->mu);
     std::lock_guard<std::mutex> wl(ix->ws_mu);
     DeviceGuard g(ix->device);
-    return search_rows_enqueue(ix, ids_dev, nq, k, exclude_self, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
+    return search_rows_enqueue(ix, rows_of(ix, allow_bits_dev), ids_dev, nq, k, exclude_self, D_dev, I_dev, (hipStream_t)stream);
 }
 
 int css_index_search_rows(css_index* ix, const int64_t* ids_host, int64_t nq, int k, int exclude_self,
@@ -3499,19 +3464,19 @@ int css_index_search_rows(css_index* ix, const int64_t* ids_host, int64_t nq, in
     CSS_REQUIRE(ids_host && D_host && I_host, "css_index_search_rows: NULL buffer");
     std::shared_lock<std::shared_mutex> lk(ix->mu);
     std::lock_guard<std::mutex> wl(ix->ws_mu);
+    Rows rows = rows_of(ix);
     for (int64_t j = 0; j < nq; ++j)
-        CSS_REQUIRE(ids_host[j] >= ix->id_base && ids_host[j] - ix->id_base < ix->ntotal,
+        CSS_REQUIRE(ids_host[j] >= rows.id_base && ids_host[j] - rows.id_base < rows.n,
                     "css_index_search_rows: id %lld (query %lld) outside [%lld, %lld)", (long long)ids_host[j], (long long)j,
-                    (long long)ix->id_base, (long long)(ix->id_base + ix->ntotal));
+                    (long long)rows.id_base, (long long)(rows.id_base + rows.n));
     DeviceGuard g(ix->device);
     if ((rc = ix->rowq_ids.grow((size_t)nq)) != CSS_OK) return rc;
     float* d_out;
     int64_t* i_out;
     if ((rc = reserve_out(ix, (size_t)nq * k, &d_out, &i_out)) != CSS_OK) return rc;
-    const uint32_t* mask_dev;
-    if ((rc = upload_allow_bits(ix, allow_bits_host, &mask_dev)) != CSS_OK) return rc;
+    if ((rc = upload_allow_bits(ix, allow_bits_host, &rows)) != CSS_OK) return rc;
     CSS_HIP_TRY(hipMemcpyAsync(ix->rowq_ids.p, ids_host, (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream));
-    rc = search_rows_enqueue(ix, ix->rowq_ids.p, nq, k, exclude_self, mask_dev, d_out, i_out, ix->stream);
+    rc = search_rows_enqueue(ix, rows, ix->rowq_ids.p, nq, k, exclude_self, d_out, i_out, ix->stream);
     if (rc != CSS_OK) {
         (void)hipStreamSynchronize(ix->stream);   // (the copies above read the caller's memory)
         return rc;
@@ -3547,7 +3512,7 @@ struct css_range_result {
 namespace {
 // Queries already on the device (ix->q_raw.p).  Caller holds ws_mu and a shared lock on mu; everything runs on the
 // index's own stream and has finished when this returns.
-int range_search_locked(css_index* ix, int64_t nq, float radius, int normalize_q, css_range_result* res) {
+int range_search_locked(css_index* ix, const Rows& rows, int64_t nq, float radius, int normalize_q, css_range_result* res) {
     hipStream_t st = ix->stream;
     int rc;
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
@@ -3568,7 +3533,7 @@ int range_search_locked(css_index* ix, int64_t nq, float radius, int normalize_q
     for (int64_t q0 = 0; q0 < nq; q0 += nq_sweep) {
         const int nqc = (int)std::min<int64_t>(nq_sweep, nq - q0);
         const float* qp = ix->qpad.p + (size_t)q0 * ix->dpad;
-        if ((rc = range_sweep(ix, qp, nqc, radius, cnt, st)) != CSS_OK) return rc;
+        if ((rc = range_sweep(ix, rows, qp, nqc, radius, cnt, st)) != CSS_OK) return rc;
         size_t most = 0, total = 0;
         for (int j = 0; j < nqc; ++j) {
             most = std::max<size_t>(most, cnt[j]);
@@ -3581,7 +3546,7 @@ int range_search_locked(css_index* ix, int64_t nq, float radius, int normalize_q
                                "(%zu for %d queries of the batch)", most, total, nqc);
                 return CSS_ERR_OOM;
             }
-            if ((rc = range_sweep(ix, qp, nqc, radius, cnt, st)) != CSS_OK) return rc;
+            if ((rc = range_sweep(ix, rows, qp, nqc, radius, cnt, st)) != CSS_OK) return rc;
             for (int j = 0; j < nqc; ++j)
                 if (cnt[j] > ix->range_cap()) {   // (rows and mask cannot change under the locks held)
                     css::set_error("css_index_range_search: internal: the second sweep counted more hits than the first");
@@ -3611,7 +3576,7 @@ int range_search_locked(css_index* ix, int64_t nq, float radius, int normalize_q
                 });
                 for (size_t i = 0; i < c; ++i) {
                     res->D.push_back(hs[order[i]]);
-                    res->I.push_back(ix->id_base + (int64_t)hi[order[i]]);
+                    res->I.push_back(rows.id_base + (int64_t)hi[order[i]]);
                 }
                 res->lims[(size_t)(q0 + j + 1)] = (int64_t)res->D.size();
             }
@@ -3650,20 +3615,19 @@ int css_index_range_search(css_index* ix, const float* q_host, int64_t nq, float
     {
         std::shared_lock<std::shared_mutex> lk(ix->mu);
         std::lock_guard<std::mutex> wl(ix->ws_mu);
-        if (nq > 0 && ix->ntotal > 0) {
+        Rows rows = rows_of(ix);
+        if (nq > 0 && rows.n > 0) {
             DeviceGuard g(ix->device);
             rc = [&]() -> int {
-                CSS_REQUIRE(ix->ntotal < 0xFFFFFFFFll, "css_index_range_search: %lld rows exceed the 32-bit row numbers of the hit pool",
-                            (long long)ix->ntotal);
+                CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "css_index_range_search: %lld rows exceed the 32-bit row numbers of the hit pool",
+                            (long long)rows.n);
                 int r;
                 WsTurn turn(ix, ix->stream);
                 if (turn.rc != CSS_OK) return turn.rc;
                 if ((r = ix->q_raw.grow((size_t)nq * ix->dim)) != CSS_OK) return r;
-                const uint32_t* mask_dev;
-                if ((r = upload_allow_bits(ix, allow_bits_host, &mask_dev)) != CSS_OK) return r;
+                if ((r = upload_allow_bits(ix, allow_bits_host, &rows)) != CSS_OK) return r;
                 CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, q_host, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream));
-                MaskScope ms(ix, mask_dev);
-                return range_search_locked(ix, nq, radius, normalize_q, res);
+                return range_search_locked(ix, rows, nq, radius, normalize_q, res);
             }();
         }
     }

@@ -1125,6 +1125,79 @@ def test_mixed_entry_points_on_different_streams_take_turns_at_the_workspaces():
     ix.close()
 
 
+@pytest.mark.parametrize("metric", [0, 1])
+def test_readers_see_the_whole_index_while_a_ranged_search_enqueues(metric):
+    """A search reads the rows through a value taken under the shared lock and never writes the index's row fields,
+    so whoever else holds the shared lock sees the whole index while a shadow-less batch walks its row ranges.  4096 x
+    128 rows, id_base 1000, ranges of 1024 rows (4 ranges; 17 queries: the smallest batch that takes the ranged path;
+    the mask, rows 1 mod 3, is cut at the range boundaries).  One thread repeats the masked batch, the other reads
+    ntotal, shadow_info, a row export and a search_by_ids whose anchors sit in the first, second and last range: 20
+    rounds each, every value bit for bit what the same call returned alone.  Its duration on an MI355X is unmeasured
+    until someone has run it there."""
+    import threading
+
+    from claude_semantic_search_amd import _native as nat
+    from claude_semantic_search_amd.flat_index import IndexFlat
+
+    norm = metric == 0
+    n, d, nq, k = 4096, 128, 17, 5
+    ix = IndexFlat(d, metric)
+    ix.set_shadow(False)
+    ix.add(synth.rows(n, d, 811), normalize=norm)
+    ix.set_id_base(1000)
+    ix.set_range_rows(1024)
+    q = synth.rows(nq, d, 812)
+    allow = (np.arange(n) % 3) == 1
+    anchors = [1000, 3047, 5095]
+
+    D0, I0 = ix.search(q, k, normalize=norm, allow=allow)
+    assert ix.ntotal == n
+    info0 = ix.shadow_info()
+    assert info0 == {"bf16": False, "int8": False}
+    x0 = ix.reconstruct_n(0, n)
+    Da0, Ia0 = ix.search_by_ids(anchors, 5)
+    assert I0.min() >= 1000 and bool(allow[I0 - 1000].all())
+
+    rounds = 20
+    errors = []
+
+    def searcher():
+        try:
+            for r in range(rounds):
+                if r == 0:
+                    nat.prof_reset()
+                    nat.prof_enable(True)
+                D, I = ix.search(q, k, normalize=norm, allow=allow)
+                if r == 0:
+                    nat.prof_enable(False)
+                    assert nat.prof_read("knn_noshadow_ranges")[1] == 1
+                assert np.array_equal(I, I0) and np.array_equal(D, D0), r
+        except BaseException as e:   # noqa: BLE001  (reported by the main thread)
+            errors.append(e)
+
+    def reader():
+        try:
+            for r in range(rounds):
+                assert ix.ntotal == n, r
+                assert ix.shadow_info() == info0, r
+                assert np.array_equal(ix.reconstruct_n(1500, 700), x0[1500:2200]), r
+                Da, Ia = ix.search_by_ids(anchors, 5)
+                assert np.array_equal(Ia, Ia0) and np.array_equal(Da, Da0), r
+        except BaseException as e:   # noqa: BLE001
+            errors.append(e)
+
+    threads = [threading.Thread(target=searcher), threading.Thread(target=reader)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    nat.prof_enable(False)
+    nat.prof_reset()
+    ix.close()
+    if errors:
+        raise errors[0]
+
+
 def test_two_host_threads_search_own_and_shared_indexes(tmp_path):
     """The concurrency contract of css_hip.h through the C ABI without Python in the way: tests/native/cabi_threads.cc
     (the driver of the CPU sanitizer builds, tests/test_cabi_sanitizers.py) linked against the product library; two
