@@ -30,6 +30,8 @@
 //                      hit list instead of top-k lists (css_knn_range.h).   HBM bound
 //   k_gather_queries,  css_index_search_rows: stored rows copied into a query buffer in front of the ordinary
 //   k_drop_self        search for k + 1, and the anchor compacted out of its results behind it (a wave per query)
+//   k_collapse_groups, css_index_search_grouped: a pass's results collapsed to the first row of every group label, and
+//   k_mask_drop_groups the groups already found dropped from the exclusion bitmap of the next pass (css_knn_group.h)
 //
 // Host plumbing, one place per rule: the row storage and every workspace are DevBufs (css_devbuf.h: owning, freed with
 // the index, one of three growth policies); a search reads the rows through a Rows value taken under the shared lock
@@ -77,6 +79,9 @@ struct css_index {
     // row; read by the 1..4-query sweep and by the int8 MFMA scan of batches
     DevBuf<unsigned char> x8;      // [cap + 256][dpad]
     DevBuf<float> x8s;             // [cap + 256]
+    // group labels of the rows (css_index_set_groups): [cap], -1 = a group of its own; empty until labels are first set.
+    // Part of the row storage: it follows the rows through reallocation, ingest, reset and css_index_remove_rows
+    DevBuf<int32_t> labels;
     hipStream_t stream = nullptr;
     int num_cus = 256;
     // reusable workspaces (DevBuf: grown on demand, freed with the index; guarded by ws_mu)
@@ -147,6 +152,13 @@ struct css_index {
     DevBuf<float> rowq_d;               // entries
     DevBuf<int64_t> rowq_i;
     DevBuf<int64_t> rowq_ids;
+    // css_index_search_grouped: the [nq, kk] results of a pass, the groups found so far ([nq, k] labels next to the
+    // call's output rows) and per query [group count | exhausted flag]
+    DevBuf<float> grp_d;                // entries
+    DevBuf<int64_t> grp_i;
+    DevBuf<int32_t> grp_l;
+    DevBuf<int> grp_state;              // [nq] counts | [nq] flags
+    int64_t last_group_passes = 0;      // search passes of the last grouped call (css_index_last_group_passes)
     // rows written by css_index_add_dev / _add_synthetic on the CALLER's stream: searches, reallocation and
     // export wait for this event before touching rows, norms or maxn2
     hipEvent_t ingest_ev = nullptr;
@@ -175,17 +187,18 @@ struct Rows {
     const float* x8s;
     int64_t n, id_base;
     const uint32_t* mask;
+    const int32_t* labels;   // group labels, one per row (null: none were ever set)
     // rows [row0, row0 + cnt) as rows of their own, with the range's bf16 OR int8 scratch rows as their shadow (the
     // other kind null): search_noshadow_ranges
     Rows range(int64_t row0, int64_t cnt, int dpad, const unsigned short* xh_rows, const unsigned char* x8_rows,
                const float* x8_scales) const {
         return Rows{xb + (size_t)row0 * dpad, xnorm2 + row0, xh_rows, x8_rows, x8_scales, cnt, id_base + row0,
-                    mask ? mask + row0 / 32 : nullptr};   // (row0 is a multiple of 256)
+                    mask ? mask + row0 / 32 : nullptr, labels ? labels + row0 : nullptr};   // (row0 is a multiple of 256)
     }
 };
 // the one place that reads the row fields of the index for a search; caller holds mu (shared is enough)
 Rows rows_of(const css_index* ix, const uint32_t* mask = nullptr) {
-    return Rows{ix->xb.p, ix->xnorm2.p, ix->xh.p, ix->x8.p, ix->x8s.p, ix->ntotal, ix->id_base, mask};
+    return Rows{ix->xb.p, ix->xnorm2.p, ix->xh.p, ix->x8.p, ix->x8s.p, ix->ntotal, ix->id_base, mask, ix->labels.p};
 }
 // caller holds mu exclusively
 void set_ntotal(css_index* ix, int64_t n) {
@@ -1564,6 +1577,8 @@ __global__ void k_fill_int(int* p, int n, int v) {
     if (i < n) p[i] = v;
 }
 
+#include "css_knn_group.h"
+
 // ---------------------------------------------------------------- host side
 // bf16 shadow rows for the coarse scan: kept when the metric is inner product, rows are a whole number
 // of 64-element K stages and fp32 + bf16 rows fit in 80 % of the HBM (CSS_KNN_SHADOW=0/1 overrides).
@@ -1621,8 +1636,14 @@ int reallocate_rows(css_index* ix, int64_t ncap) {
     DevBuf<float> nxb, nn2, nx8s;
     DevBuf<unsigned short> nxh;
     DevBuf<unsigned char> nx8;
+    DevBuf<int32_t> nlab;
     int rc;
     if ((rc = nxb.grow_exact((size_t)ncap * ix->dpad, "hipMalloc(index rows)")) != CSS_OK) return rc;
+    // the label column only where labels were set: all -1 (0xFF bytes), then the existing rows' labels
+    if (ix->labels.p) {
+        if ((rc = nlab.grow_exact((size_t)ncap, "hipMalloc(group labels)")) != CSS_OK) return rc;
+        CSS_HIP_TRY(hipMemsetAsync(nlab.p, 0xFF, (size_t)ncap * sizeof(int32_t), ix->stream));
+    }
     // +256: the coarse scan reads whole tiles of norms
     if ((rc = nn2.grow_exact((size_t)ncap + 256, "hipMalloc(index norms)")) != CSS_OK) return rc;
     // the shadow can only be carried over (or started on an empty index), never rebuilt here
@@ -1651,8 +1672,12 @@ int reallocate_rows(css_index* ix, int64_t ncap) {
         if (nxh.p)
             CSS_HIP_TRY(hipMemcpyAsync(nxh.p, ix->xh.p, (size_t)ix->ntotal * ix->dpad * sizeof(unsigned short),
                                        hipMemcpyDeviceToDevice, ix->stream));
-        CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+        if (nlab.p)
+            CSS_HIP_TRY(hipMemcpyAsync(nlab.p, ix->labels.p, (size_t)ix->ntotal * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                                       ix->stream));
     }
+    if (ix->ntotal > 0 || nlab.p) CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    ix->labels.swap(nlab);
     ix->xb.swap(nxb);
     ix->xnorm2.swap(nn2);
     ix->xh.swap(nxh);
@@ -1697,6 +1722,8 @@ int ingest(css_index* ix, const float* x_dev, int64_t n, int normalize, bool syn
         unsigned short* dh = ix->xh.p ? ix->xh.p + (size_t)r0 * ix->dpad : nullptr;
         unsigned char* d8 = ix->x8.p ? ix->x8.p + (size_t)r0 * ix->dpad : nullptr;
         float* d8s = ix->x8.p ? ix->x8s.p + r0 : nullptr;
+        // appended rows are ungrouped (the slots may hold the labels of rows removed earlier)
+        if (ix->labels.p) CSS_HIP_TRY(hipMemsetAsync(ix->labels.p + r0, 0xFF, (size_t)nc * sizeof(int32_t), st));
         if (synth)
             hipLaunchKernelGGL(k_ingest_rows<true>, dim3(blocks), dim3(256), 0, st, nullptr, dst, n2, nc, ix->dim, ix->dpad,
                                normalize, seed, first_row + c0, dh, ix->maxn2.p, (float*)nullptr, d8, d8s);
@@ -2950,6 +2977,7 @@ int css_index_reset(css_index* ix) {
     if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ws_ev, 0));   // a search enqueued on another stream still reads maxn2
     CSS_HIP_TRY(hipMemsetAsync(ix->maxn2.p, 0, 3 * sizeof(int), ix->stream));
     CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    CSS_HIP_TRY(ix->labels.drop());   // the labels go with the rows: the index is again one that never set any
     return CSS_OK;
 }
 
@@ -3026,6 +3054,36 @@ int compact_rows(css_index* ix, const uint32_t* keep, int64_t n, int64_t first, 
     }
     return CSS_OK;
 }
+
+// The label column through the same keep bits, OUT OF PLACE into `dst` (all -1 beforehand): a second 4-byte-per-row
+// buffer has none of the overlap hazards of the row windows above, and the caller swaps it in.  Enqueued behind
+// compact_rows on the index's stream (it reuses compact_bits / compact_pre); `keep` stays valid until the caller waited.
+int compact_labels(css_index* ix, const uint32_t* keep, int64_t n, int32_t* dst) {
+    const hipStream_t st = ix->stream;
+    const int64_t words = (n + 31) / 32;
+    const uint32_t tail_mask = (n & 31) ? ((1u << (n & 31)) - 1u) : 0xFFFFFFFFu;
+    const size_t need_words = (size_t)std::min<int64_t>(kCompactWords, words);
+    int rc;
+    if ((rc = ix->compact_bits.grow_exact(need_words, "hipMalloc(compaction bitmap)")) != CSS_OK) return rc;
+    if ((rc = ix->compact_pre.grow_exact(need_words, "hipMalloc(compaction bitmap)")) != CSS_OK) return rc;
+    int64_t dnext = 0;
+    for (int64_t s0 = 0; s0 < n; s0 += kCompactWindowRows) {
+        const int64_t L = std::min(kCompactWindowRows, n - s0);
+        const int64_t w0 = s0 >> 5, nw = (L + 31) / 32;
+        int64_t surv = 0;
+        for (int64_t w = 0; w < nw; ++w) surv += __builtin_popcount(keep[w0 + w] & (w0 + w == words - 1 ? tail_mask : 0xFFFFFFFFu));
+        if (surv > 0) {
+            CSS_HIP_TRY(hipMemcpyAsync(ix->compact_bits.p, keep + w0, (size_t)nw * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_keep_prefix, dim3(1), dim3(1024), 0, st, ix->compact_bits.p, ix->compact_pre.p, (int)nw);
+            CSS_LAUNCH_CHECK();
+            hipLaunchKernelGGL(k_compact_labels, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, st, ix->compact_bits.p,
+                               ix->compact_pre.p, L, (const int32_t*)ix->labels.p + s0, dst + dnext);
+            CSS_LAUNCH_CHECK();
+        }
+        dnext += surv;
+    }
+    return CSS_OK;
+}
 }  // namespace
 
 int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t* removed_out) {
@@ -3050,13 +3108,21 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
     // pending asynchronous adds, and searches on other streams that still read the rows and maxn2
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
     if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ws_ev, 0));
+    DevBuf<int32_t> nlab;   // the compacted label column (only where labels were set)
+    if (ix->labels.p && kept > 0) {
+        int rc0;
+        if ((rc0 = nlab.grow_exact((size_t)ix->cap, "hipMalloc(group labels)")) != CSS_OK) return rc0;
+        CSS_HIP_TRY(hipMemsetAsync(nlab.p, 0xFF, (size_t)ix->cap * sizeof(int32_t), ix->stream));
+    }
     CSS_HIP_TRY(hipMemsetAsync(ix->maxn2.p, 0, 3 * sizeof(int), ix->stream));
     uint32_t patch = 0;
-    const int rc = kept > 0 ? compact_rows(ix, keep_bits_host, n, first, &patch) : CSS_OK;
+    int rc = kept > 0 ? compact_rows(ix, keep_bits_host, n, first, &patch) : CSS_OK;
+    if (rc == CSS_OK && nlab.p) rc = compact_labels(ix, keep_bits_host, n, nlab.p);
     // later adds and searches on any stream are ordered behind the compaction (as css_index_reset)
     const hipError_t e = hipStreamSynchronize(ix->stream);
     if (rc != CSS_OK) return rc;
     if (e != hipSuccess) return css::hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    if (nlab.p) ix->labels.swap(nlab);
     set_ntotal(ix, kept);
     if (kept == 0 && !ix->xh.p) ix->shadow = -1;   // emptied: as css_index_reset
     for (css_index::I8Feedback* f : {&ix->fb_batch, &ix->fb_sweep}) {   // (it described other rows; its copy has landed)
@@ -3401,6 +3467,212 @@ int css_index_search_masked(css_index* ix, const float* q_host, int64_t nq, int 
 int css_index_search(css_index* ix, const float* q_host, int64_t nq, int k, int normalize_q, float* D_host,
                      int64_t* I_host) {
     return css_index_search_masked(ix, q_host, nq, k, normalize_q, nullptr, D_host, I_host);
+}
+
+// ------------------------------------------------------------------ group labels and grouped search
+int css_index_set_groups(css_index* ix, int64_t row0, int64_t n, const int32_t* labels_host) {
+    CSS_REQUIRE(ix, "css_index_set_groups: NULL index");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_set_groups: rows [%lld, %lld + %lld) outside [0, %lld)",
+                (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
+    if (n == 0) return CSS_OK;
+    CSS_REQUIRE(labels_host, "css_index_set_groups: labels is NULL");
+    DeviceGuard g(ix->device);
+    // rows appended on another stream write their -1 there: they must have landed before labels go over them
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
+    int rc;
+    if (!ix->labels.p) {   // first labels of this index: the column, every row ungrouped
+        if ((rc = ix->labels.grow_exact((size_t)ix->cap, "hipMalloc(group labels)")) != CSS_OK) return rc;
+        CSS_HIP_TRY(hipMemsetAsync(ix->labels.p, 0xFF, (size_t)ix->cap * sizeof(int32_t), ix->stream));
+    }
+    // negative labels are stored as -1: through a bounded host buffer
+    const int64_t chunk = 1ll << 20;
+    std::vector<int32_t> buf;
+    try {
+        buf.resize((size_t)std::min(n, chunk));
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_index_set_groups: out of host memory");
+        return CSS_ERR_OOM;
+    }
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t m = std::min(chunk, n - r0);
+        for (int64_t i = 0; i < m; ++i) buf[(size_t)i] = std::max<int32_t>(labels_host[r0 + i], -1);
+        CSS_HIP_TRY(hipMemcpyAsync(ix->labels.p + row0 + r0, buf.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice,
+                                   ix->stream));
+        CSS_HIP_TRY(hipStreamSynchronize(ix->stream));   // (buf is written again)
+    }
+    return CSS_OK;
+}
+
+int css_index_get_groups(css_index* ix, int64_t row0, int64_t n, int32_t* labels_out_host) {
+    CSS_REQUIRE(ix, "css_index_get_groups: NULL index");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    const Rows rows = rows_of(ix);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= rows.n - row0, "css_index_get_groups: rows [%lld, %lld + %lld) outside [0, %lld)",
+                (long long)row0, (long long)row0, (long long)n, (long long)rows.n);
+    if (n == 0) return CSS_OK;
+    CSS_REQUIRE(labels_out_host, "css_index_get_groups: labels_out is NULL");
+    if (!rows.labels) {
+        std::fill(labels_out_host, labels_out_host + n, (int32_t)-1);
+        return CSS_OK;
+    }
+    DeviceGuard g(ix->device);
+    if (ix->ingest_pending) CSS_HIP_TRY(hipEventSynchronize(ix->ingest_ev));
+    CSS_HIP_TRY(hipMemcpy(labels_out_host, rows.labels + row0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return CSS_OK;
+}
+
+namespace {
+// n ints from the device, through the pinned staging where it is there and large enough; waits for the stream
+int read_ints(css_index* ix, const int* dev, size_t n, int* host) {
+    const size_t bytes = n * sizeof(int);
+    if (ix->h_stage != nullptr && bytes <= css_index::kHostStage) {
+        char* back = ix->h_stage + css_index::kHostStage;
+        CSS_HIP_TRY(hipMemcpyAsync(back, dev, bytes, hipMemcpyDeviceToHost, ix->stream));
+        CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+        memcpy(host, back, bytes);
+        return CSS_OK;
+    }
+    CSS_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ix->stream));
+    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    return CSS_OK;
+}
+
+int launch_collapse(css_index* ix, const Rows& rows, int64_t q0, int64_t nqp, int kk, int k, float* Dg, int64_t* Ig,
+                    int32_t* Lg, hipStream_t st) {
+    hipLaunchKernelGGL(k_collapse_groups, dim3((unsigned)((nqp + 3) / 4)), dim3(256), 0, st, (const float*)ix->grp_d.p,
+                       (const int64_t*)ix->grp_i.p, rows.labels, rows.id_base, q0, nqp, kk, k,
+                       ix->metric == CSS_METRIC_IP ? -FLT_MAX : FLT_MAX, Dg, Ig, Lg, ix->grp_state.p);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// The passes of css_index_search_grouped over labelled rows (rows.labels set, rows.n > 0), on the index's own stream;
+// Dg / Ig / Lg: device [nq, k].  Pass 1 serves the whole batch: the ordinary search for kk rows (the smaller list class
+// of {32, 128} that holds 2k, else 128), one collapse launch, ONE readback of every query's [group count | exhausted].
+// A query that has neither k groups nor a padded pass goes on alone, as the k > 128 path walks queries: its exclusion
+// bitmap starts as the caller's bitmap and loses, in front of every pass, all rows of the groups found so far
+// (k_mask_drop_groups; returned ungrouped rows one by one, k_mask_clear), so every pass of 128 rows brings at least one
+// new group and a query takes at most k passes.  Scores of different passes may come from different summation orders:
+// a query that took several passes is sorted once more (k_sort_rows), and its labels are gathered again behind that.
+// Waits for the device (the pass count depends on the data).  Caller holds ws_mu and a shared lock on mu.
+int search_grouped_passes(css_index* ix, const Rows& rows, const float* q_dev, int64_t nq, int k, int normalize_q, float* Dg,
+                          int64_t* Ig, int32_t* Lg) {
+    const hipStream_t st = ix->stream;
+    WsTurn turn(ix, st);   // excl_ws and the grp_* buffers are shared workspaces
+    if (turn.rc != CSS_OK) return turn.rc;
+    int rc;
+    const int kk1 = 2 * k <= 32 ? 32 : CSS_KERNEL_MAX_K;
+    if ((rc = ix->grp_d.grow((size_t)nq * kk1 + CSS_KERNEL_MAX_K)) != CSS_OK) return rc;
+    if ((rc = ix->grp_i.grow((size_t)nq * kk1 + CSS_KERNEL_MAX_K)) != CSS_OK) return rc;
+    if ((rc = ix->grp_state.grow((size_t)nq * 2)) != CSS_OK) return rc;   // [count, exhausted] per query
+    CSS_HIP_TRY(hipMemsetAsync(ix->grp_state.p, 0, (size_t)nq * 2 * sizeof(int), st));
+    if ((rc = search_any_k(ix, rows, q_dev, nq, kk1, normalize_q, ix->grp_d.p, ix->grp_i.p, st)) != CSS_OK) return rc;
+    if ((rc = launch_collapse(ix, rows, 0, nq, kk1, k, Dg, Ig, Lg, st)) != CSS_OK) return rc;
+    ix->last_group_passes = 1;
+    std::vector<int> state((size_t)nq * 2);
+    if ((rc = read_ints(ix, ix->grp_state.p, state.size(), state.data())) != CSS_OK) return rc;
+    const int64_t words = (rows.n + 31) / 32;
+    const unsigned drop_grid = (unsigned)std::min<int64_t>((rows.n + 255) / 256, (int64_t)ix->num_cus * 8);
+    for (int64_t q = 0; q < nq; ++q) {
+        if (state[2 * q] >= k || state[2 * q + 1]) continue;
+        if ((rc = ix->excl_ws.grow((size_t)words)) != CSS_OK) return rc;
+        Rows pass = rows;   // the same rows under the exclusion bitmap
+        pass.mask = ix->excl_ws.p;
+        hipLaunchKernelGGL(k_mask_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, ix->excl_ws.p, rows.mask, words);
+        CSS_LAUNCH_CHECK();
+        int qs[2] = {state[2 * q], 0};
+        for (int p = 0; p < k && qs[0] < k && !qs[1]; ++p) {
+            {
+                ProfScope ps("knn_mask_drop_groups", st);
+                hipLaunchKernelGGL(k_mask_drop_groups, dim3(drop_grid), dim3(256), 0, st, ix->excl_ws.p, rows.labels, rows.n,
+                                   (const int32_t*)(Lg + (size_t)q * k), (const int*)(ix->grp_state.p + 2 * q));
+                CSS_LAUNCH_CHECK();
+            }
+            hipLaunchKernelGGL(k_mask_clear, dim3(1), dim3(CSS_KERNEL_MAX_K), 0, st, ix->excl_ws.p,
+                               (const int64_t*)(Ig + (size_t)q * k), k, rows.id_base);
+            CSS_LAUNCH_CHECK();
+            if ((rc = search_dev_locked(ix, pass, q_dev + (size_t)q * ix->dim, 1, CSS_KERNEL_MAX_K, normalize_q, ix->grp_d.p,
+                                        ix->grp_i.p, st)) != CSS_OK) return rc;
+            if ((rc = launch_collapse(ix, rows, q, 1, CSS_KERNEL_MAX_K, k, Dg, Ig, Lg, st)) != CSS_OK) return rc;
+            ++ix->last_group_passes;
+            if ((rc = read_ints(ix, ix->grp_state.p + 2 * q, 2, qs)) != CSS_OK) return rc;
+        }
+        float* Dq = Dg + (size_t)q * k;
+        int64_t* Iq = Ig + (size_t)q * k;
+        if (ix->metric == CSS_METRIC_IP) hipLaunchKernelGGL(k_sort_rows<CSS_METRIC_IP>, dim3(1), dim3(1024), 0, st, Dq, Iq, k);
+        else hipLaunchKernelGGL(k_sort_rows<CSS_METRIC_L2>, dim3(1), dim3(1024), 0, st, Dq, Iq, k);
+        CSS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_gather_labels, dim3(1), dim3(CSS_KERNEL_MAX_K), 0, st, (const int64_t*)Iq, rows.labels, rows.id_base,
+                           (int64_t)k, Lg + (size_t)q * k);
+        CSS_LAUNCH_CHECK();
+    }
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_search_grouped(css_index* ix, const float* q_host, int64_t nq, int k, int normalize_q,
+                             const uint32_t* allow_bits_host, float* D_host, int64_t* I_host, int32_t* G_host) {
+    CSS_REQUIRE(ix, "css_index_search_grouped: NULL index");
+    CSS_REQUIRE(nq >= 0 && nq < (1 << 24), "css_index_search_grouped: nq=%lld out of range", (long long)nq);
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "css_index_search_grouped: k=%d outside [1, %d]", k, CSS_KERNEL_MAX_K);
+    if (nq == 0) return CSS_OK;
+    CSS_REQUIRE(q_host && D_host && I_host, "css_index_search_grouped: NULL buffer");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    DeviceGuard g(ix->device);
+    int rc;
+    const size_t n = (size_t)nq * k;
+    if ((rc = ix->q_raw.grow((size_t)nq * ix->dim)) != CSS_OK) return rc;
+    if ((rc = ix->grp_l.grow(n)) != CSS_OK) return rc;
+    float* d_out;
+    int64_t* i_out;
+    if ((rc = reserve_out(ix, n, &d_out, &i_out)) != CSS_OK) return rc;
+    const size_t q_bytes = (size_t)nq * ix->dim * 4, out_bytes = n * 16;
+    const bool staged = q_bytes <= css_index::kHostStage && out_bytes <= css_index::kHostStage;
+    if (staged && ix->h_stage == nullptr)
+        CSS_HIP_TRY(hipHostMalloc((void**)&ix->h_stage, 2 * css_index::kHostStage, hipHostMallocDefault));
+    Rows rows = rows_of(ix);
+    if ((rc = upload_allow_bits(ix, allow_bits_host, &rows)) != CSS_OK) return rc;
+    if (staged) {
+        memcpy(ix->h_stage, q_host, q_bytes);
+        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, ix->h_stage, q_bytes, hipMemcpyHostToDevice, ix->stream));
+    } else {
+        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, q_host, q_bytes, hipMemcpyHostToDevice, ix->stream));
+    }
+    // no labels (or no rows): every row is a group of its own, and the answer is the masked search's, G = -1
+    const bool labelled = rows.labels != nullptr && rows.n > 0;
+    if (labelled) {
+        rc = search_grouped_passes(ix, rows, ix->q_raw.p, nq, k, normalize_q, d_out, i_out, ix->grp_l.p);
+    } else {
+        rc = search_any_k(ix, rows, ix->q_raw.p, nq, k, normalize_q, d_out, i_out, ix->stream);
+        ix->last_group_passes = 1;
+    }
+    if (rc != CSS_OK) {
+        (void)hipStreamSynchronize(ix->stream);   // (the copies above read the caller's memory)
+        return rc;
+    }
+    if (G_host && !labelled) std::fill(G_host, G_host + n, (int32_t)-1);
+    const bool want_g = G_host && labelled;
+    if (staged) {   // one wait: [ids | scores] and the labels into pinned memory
+        char* back = ix->h_stage + css_index::kHostStage;
+        CSS_HIP_TRY(hipMemcpyAsync(back, i_out, n * 12, hipMemcpyDeviceToHost, ix->stream));
+        if (want_g) CSS_HIP_TRY(hipMemcpyAsync(back + n * 12, ix->grp_l.p, n * 4, hipMemcpyDeviceToHost, ix->stream));
+        CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+        memcpy(I_host, back, n * 8);
+        memcpy(D_host, back + n * 8, n * 4);
+        if (want_g) memcpy(G_host, back + n * 12, n * 4);
+        return CSS_OK;
+    }
+    if (want_g) CSS_HIP_TRY(hipMemcpyAsync(G_host, ix->grp_l.p, n * 4, hipMemcpyDeviceToHost, ix->stream));
+    return fetch_out(ix, n, d_out, i_out, D_host, I_host);
+}
+
+int css_index_last_group_passes(css_index* ix, int64_t* n) {
+    CSS_REQUIRE(ix && n, "css_index_last_group_passes: NULL argument");
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    *n = ix->last_group_passes;
+    return CSS_OK;
 }
 
 

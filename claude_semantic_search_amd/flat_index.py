@@ -96,6 +96,45 @@ def drop_self(D: np.ndarray, I: np.ndarray, ids: np.ndarray) -> Tuple[np.ndarray
     return (np.ascontiguousarray(D[keep].reshape(nq, kk - 1)), np.ascontiguousarray(I[keep].reshape(nq, kk - 1)))
 
 
+MAX_GROUP_K = nat.MAX_GROUP_K
+
+
+def labels_as_int32(labels, what: str = "set_groups") -> np.ndarray:
+    """Array-like of integer group labels -> contiguous 1-D int32 array; anything else (floats, booleans, strings,
+    more than one dimension, values beyond int32) raises ``ValueError``.  Negative labels mean "ungrouped"."""
+    a = np.asarray(labels)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{what}: labels must be integers, got dtype {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"{what}: labels must be one-dimensional, got shape {a.shape}")
+    if a.size and (int(a.min()) < np.iinfo(np.int32).min or int(a.max()) > np.iinfo(np.int32).max):
+        raise ValueError(f"{what}: label beyond int32")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def collapse_groups(D, I, G, k: int, metric: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The collapse rule of ``search_grouped``, stated in numpy for best-first lists that already carry labels:
+    ``D, I, G`` are ``[nq, kk]`` (scores, ids, group labels; pads ``I = -1`` at the tail).  An entry survives iff its
+    label is negative (an ungrouped row is a group of its own) or no earlier entry of its row has the same label; the
+    first ``k`` survivors are returned in order as ``[nq, k]``, padded like ``search`` with ``G = -1``.  Because the
+    list is best first, a survivor is the best row of its group, and every group absent from the list has its best
+    row below the list's last entry.  (The sharded index merges the shards' grouped lists with this.)"""
+    D, I, G = np.asarray(D, np.float32), np.asarray(I, np.int64), np.asarray(G, np.int32)
+    nq, kk = I.shape
+    k = int(k)
+    Do = np.full((nq, k), -np.finfo(np.float32).max if metric == METRIC_INNER_PRODUCT else np.finfo(np.float32).max,
+                 dtype=np.float32)
+    Io = np.full((nq, k), -1, dtype=np.int64)
+    Go = np.full((nq, k), -1, dtype=np.int32)
+    for j in range(nq):
+        first = np.zeros(kk, dtype=np.bool_)
+        first[np.unique(G[j], return_index=True)[1]] = True   # first occurrence of every label value
+        sel = np.flatnonzero((I[j] >= 0) & (first | (G[j] < 0)))[:k]
+        Do[j, :sel.size], Io[j, :sel.size] = D[j, sel], I[j, sel]
+        Go[j, :sel.size] = np.maximum(G[j, sel], -1)
+    return Do, Io, Go
+
+
 class IndexFlat:
     """Exact brute-force index in HBM (``faiss.IndexFlat`` semantics)."""
 
@@ -226,6 +265,62 @@ class IndexFlat:
         finally:
             nat.lib().css_range_result_free(res)
         return lims, D, I
+
+    # -- group labels and grouped search ------------------------------------
+    def set_groups(self, labels, row0: int = 0) -> None:
+        """Group labels of rows ``[row0, row0 + len(labels))`` in LOCAL row numbering (like ``allow``): an integer
+        array that fits int32.  A negative label means "ungrouped" and is stored as ``-1``; rows never given a label
+        are ungrouped too.  The labels follow the rows through growth, ``remove_ids`` (compacted with them) and
+        ``reset`` (forgotten); rows added later start ungrouped."""
+        a = labels_as_int32(labels)
+        row0 = int(row0)
+        n = self.ntotal
+        if row0 < 0 or row0 + a.shape[0] > n:
+            raise ValueError(f"set_groups: rows [{row0}, {row0 + a.shape[0]}) outside [0, {n})")
+        if a.shape[0]:
+            nat.check(nat.lib().css_index_set_groups(self._handle(), row0, a.shape[0], a.ctypes.data))
+
+    def get_groups(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """The labels of rows ``[row0, row0 + n)`` (default: to the end) as int32; ``-1`` = ungrouped."""
+        row0 = int(row0)
+        total = self.ntotal
+        n = total - row0 if n is None else int(n)
+        if row0 < 0 or n < 0 or row0 + n > total:
+            raise ValueError(f"get_groups: rows [{row0}, {row0 + n}) outside [0, {total})")
+        out = np.empty(n, dtype=np.int32)
+        if n:
+            nat.check(nat.lib().css_index_get_groups(self._handle(), row0, n, out.ctypes.data))
+        return out
+
+    def search_grouped(self, q, k: int, normalize: bool = False, allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The ``k`` best GROUPS per query (``css_index_search_grouped``): ``(D[nq,k], I[nq,k], G[nq,k] int32)`` -- score
+        and global id of each group's best allowed row and the group's label, best group first, ties to the lower id,
+        padded like ``search`` with ``G = -1``.  An ungrouped row (label ``-1``) is a group of its own.  Exact: the
+        ordinary search runs for 32 or 128 rows, the list is collapsed on the device, and queries that still lack
+        groups run further passes without the rows of the groups already found.  ``1 <= k <= 128``."""
+        a = _as_f32_2d(q, self.d, "search_grouped")
+        k = int(k)
+        if k < 1 or k > MAX_GROUP_K:
+            raise ValueError(f"k={k} outside [1, {MAX_GROUP_K}]")
+        nq = a.shape[0]
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        G = np.empty((nq, k), dtype=np.int32)
+        bits = None
+        if allow is not None:
+            bits = pack_allow_bits(allow, self.ntotal)
+        if nq:
+            nat.check(nat.lib().css_index_search_grouped(self._handle(), a.ctypes.data, nq, k, 1 if normalize else 0,
+                                                         bits.ctypes.data if bits is not None else None,
+                                                         D.ctypes.data, I.ctypes.data, G.ctypes.data))
+        return D, I, G
+
+    def last_group_passes(self) -> int:
+        """Diagnostics: search passes of the last ``search_grouped`` call (1 when the first pass sufficed for every
+        query)."""
+        n = ctypes.c_int64(0)
+        nat.check(nat.lib().css_index_last_group_passes(self._handle(), ctypes.byref(n)))
+        return int(n.value)
 
     def search_dev(self, q_ptr: int, nq: int, k: int, D_ptr: int, I_ptr: int, stream: int = 0,
                    normalize: bool = False, allow_bits_ptr: int = 0) -> None:

@@ -320,6 +320,66 @@ class ShardedFlatIndex:
         np.cumsum(all_counts.sum(axis=0), out=out_lims[1:])
         return out_lims, np.ascontiguousarray(scores[order]), np.ascontiguousarray(ids[order])
 
+    # -- grouped search ----------------------------------------------------------------------------------------
+    def set_groups(self, global_labels, row0: int = 0) -> None:
+        """``IndexFlat.set_groups`` in GLOBAL numbering (collective: every rank passes the same labels): labels of the
+        global rows ``[row0, row0 + len(global_labels))``; every rank writes the part its shard holds, through the
+        segment table like ``local_rows_of``.  A label means the same group on every shard."""
+        from .flat_index import labels_as_int32
+
+        g = labels_as_int32(global_labels)
+        row0 = int(row0)
+        if row0 < 0 or row0 + g.shape[0] > self.ntotal_global:
+            raise ValueError(f"set_groups: rows [{row0}, {row0 + g.shape[0]}) outside [0, {self.ntotal_global})")
+        for l0, g0, n in self.segments:
+            lo, hi = max(g0, row0), min(g0 + n, row0 + g.shape[0])
+            if hi > lo:
+                self.local.set_groups(g[lo - row0:hi - row0], row0=l0 + (lo - g0))
+
+    def search_grouped(self, q, k: int, normalize: bool = False, allow=None):
+        """``IndexFlat.search_grouped`` over the shards: ``(D, I, G)`` with global ids on every rank.  Every rank runs
+        the grouped search of its shard (local allow-mask as in ``search_tensors``), maps its ids to global, and ONE
+        all-gather moves the ``nq * k`` (id, score, label) records of every rank; every rank then merges per query on
+        the host: sort by (score, id), then ``flat_index.collapse_groups``.  Exact: a group of the global top-k is
+        among the top-k groups of the shard that holds its best row, because every group ranked above it on that
+        shard also ranks above it globally.  With one rank there is no exchange."""
+        import torch
+
+        from .flat_index import MAX_GROUP_K, collapse_groups
+
+        qa = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.d)
+        nq, k = qa.shape[0], int(k)
+        if k < 1 or k > MAX_GROUP_K:
+            raise ValueError(f"k={k} outside [1, {MAX_GROUP_K}]")
+        loc = self._local_allow(allow)
+        if loc is not None:
+            D, I, G = self.local.search_grouped(qa, k, normalize=normalize, allow=loc)
+        else:
+            D, I, G = self.local.search_grouped(qa, k, normalize=normalize)
+        D, G = np.ascontiguousarray(D, dtype=np.float32), np.ascontiguousarray(G, dtype=np.int32)
+        I = np.asarray(I, dtype=np.int64)
+        if len(self.segments) > 1:
+            I = np.where(I >= 0, self._to_global_np(np.maximum(I, 0)), -1)
+        I = np.ascontiguousarray(I)
+        if (self.world == 1 and not self.exchange_when_single) or nq == 0:
+            return D, I, G
+        n = nq * k
+        send = np.empty(16 * n, dtype=np.uint8)                      # [n int64 ids][n float32 scores][n int32 labels]
+        send[:8 * n] = I.reshape(-1).view(np.uint8)
+        send[8 * n:12 * n] = D.reshape(-1).view(np.uint8)
+        send[12 * n:] = G.reshape(-1).view(np.uint8)
+        dev = "cpu" if self.dist.get_backend(self.group) == "gloo" else f"cuda:{self.device_index or 0}"
+        recv = torch.empty(self.world * 16 * n, dtype=torch.uint8, device=dev)
+        self.dist.all_gather_into_tensor(recv, torch.from_numpy(send).to(dev), group=self.group)
+        recv = recv.cpu().numpy().reshape(self.world, 16 * n)
+        Ig = np.concatenate([recv[r, :8 * n].view(np.int64).reshape(nq, k) for r in range(self.world)], axis=1)
+        Dg = np.concatenate([recv[r, 8 * n:12 * n].view(np.float32).reshape(nq, k) for r in range(self.world)], axis=1)
+        Gg = np.concatenate([recv[r, 12 * n:].view(np.int32).reshape(nq, k) for r in range(self.world)], axis=1)
+        for j in range(nq):   # best first by (score, id), pads last
+            order = np.lexsort((Ig[j], -Dg[j] if self.metric == 0 else Dg[j], Ig[j] < 0))
+            Ig[j], Dg[j], Gg[j] = Ig[j][order], Dg[j][order], Gg[j][order]
+        return collapse_groups(Dg, Ig, Gg, k, self.metric)
+
     # -- related rows ----------------------------------------------------------------------------------------------
     def search_by_ids(self, ids, k: int, exclude_self: bool = True, allow=None):
         """``IndexFlat.search_by_ids`` over the shards (collective: every rank passes the same arguments): ``ids`` are
@@ -425,6 +485,12 @@ class ShardedIndexFacade:
 
     def search_by_ids(self, ids, k: int, exclude_self: bool = True, allow=None):
         return self.sh.search_by_ids(ids, int(k), exclude_self=exclude_self, allow=allow)
+
+    def set_groups(self, labels, row0: int = 0) -> None:
+        self.sh.set_groups(labels, row0=row0)
+
+    def search_grouped(self, q, k: int, normalize: bool = False, allow=None):
+        return self.sh.search_grouped(np.asarray(q, dtype=np.float32), int(k), normalize=normalize, allow=allow)
 
     def reconstruct_n(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
         return self.sh.reconstruct_n(int(row0), self.ntotal - int(row0) if n is None else int(n))

@@ -175,6 +175,11 @@ class HybridStorage:
         self._saved_rows = -1  # rows known to be in index_path (-1: unknown)
         self._allow_cache: Dict[str, Any] = {}  # filter key -> (stamp, allow mask); push-down only
         self._mutations = 0  # bumped by every change of the chunk set (part of the allow-cache stamp)
+        # search_sessions: dense group labels per session_id (order of first appearance by faiss_id), and which rows
+        # of WHICH index object already carry theirs (labels are pushed lazily, in front of a grouped search)
+        self._session_labels: Dict[str, int] = {}
+        self._labels_index: Optional[Any] = None
+        self._labels_synced = 0
 
         self.total_chunks: int = 0
         self.embedding_dim: int = self.config.embedding_dim
@@ -438,6 +443,63 @@ class HybridStorage:
                 k = max(1, min(k, cfg.top_k))
             sims, ids = self.faiss_index.search_by_ids([fid], k, exclude_self=True, allow=allow)
             return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters, skip)
+
+    def _sync_session_labels(self, ntotal: int) -> None:
+        """Bring the index's group labels up to date with SQLite: row = ``faiss_id``, label = a dense integer per
+        ``session_id`` in order of first appearance; rows without a session (or without a chunk) stay ungrouped
+        (``-1``).  Only the tail ``[synced, ntotal)`` is pushed after adds; everything is pushed when the index
+        object was replaced (load, restore, ``clear_all_data``, a rebuild into a second index) or compacted."""
+        if self._labels_index is not self.faiss_index:
+            self._labels_index, self._labels_synced = self.faiss_index, 0
+            self._session_labels = {}
+        lo = self._labels_synced
+        if lo >= ntotal:
+            return
+        labels = np.full(ntotal - lo, -1, dtype=np.int32)
+        rows = self.db.cursor().execute(
+            "SELECT faiss_id, session_id FROM chunks WHERE faiss_id >= ? AND faiss_id < ? AND session_id IS NOT NULL "
+            "ORDER BY faiss_id", (lo, ntotal)).fetchall()
+        for fid, session in rows:
+            labels[fid - lo] = self._session_labels.setdefault(session, len(self._session_labels))
+        self.faiss_index.set_groups(labels, row0=lo)
+        self._labels_synced = ntotal
+
+    def search_sessions(self, query_embedding, config: Optional[SearchConfig] = None,
+                        filters: Optional[Dict[str, Any]] = None) -> List[SearchResult]:
+        """The best chunk of each of the ``top_k`` best SESSIONS, in rank order -- "which conversations are nearest",
+        where ``search()`` may return ``top_k`` chunks of one long conversation.  A session is ranked by its best
+        chunk; a chunk without a ``session_id`` counts as a session of its own.  The collapse happens inside the index
+        (``IndexFlat.search_grouped``: exact, however many chunks one session has), not over an over-fetched list.
+
+        Threshold, tombstones, ``filters`` and ``filter_pushdown`` mean what they mean in ``search()``.  With
+        ``filter_pushdown`` the filters form the allow mask, a session is represented by its best MATCHING chunk and
+        ``top_k`` groups are fetched.  Without it, ``min(max_results, 128)`` groups are fetched when there are filters
+        and groups whose best row fails a filter are dropped on the host, as ``search()`` drops rows: such a session is
+        then missing even if another of its chunks matches.  Tombstones are masked out in both modes, so a deleted
+        chunk never stands for its session.  An index object without ``search_grouped`` raises
+        ``NotImplementedError``."""
+        cfg = config or SearchConfig()
+        if not self.faiss_index:
+            return []
+        if not hasattr(self.faiss_index, "search_grouped") or not hasattr(self.faiss_index, "set_groups"):
+            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no grouped search (search_grouped / set_groups)")
+        with self._lock:
+            ntotal = self.faiss_index.ntotal
+            if ntotal == 0 or cfg.top_k <= 0:
+                return []
+            q = np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
+            pushdown = bool(self.config.filter_pushdown)
+            allow = None
+            if (pushdown and filters) or len(self.faiss_id_to_chunk_id) < ntotal:
+                allow = self._allow_mask((filters or {}) if pushdown else {}, ntotal)
+            k = cfg.top_k if (pushdown or not filters) else max(cfg.top_k, cfg.max_results)
+            k = max(1, min(k, ntotal, fi.MAX_GROUP_K))
+            self._sync_session_labels(ntotal)
+            if allow is not None:
+                sims, ids, _ = self.faiss_index.search_grouped(q, k, normalize=self.config.normalize_embeddings, allow=allow)
+            else:
+                sims, ids, _ = self.faiss_index.search_grouped(q, k, normalize=self.config.normalize_embeddings)
+            return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
 
     @staticmethod
     def _make_result(chunk_id: str, score: float, data: Dict[str, Any], cfg: SearchConfig) -> SearchResult:
@@ -874,6 +936,7 @@ class HybridStorage:
             self._saved_rows = self.faiss_index.ntotal
             self.total_chunks = len(live)
             self._mutations += 1
+            self._labels_index = None   # (search_sessions pushes every label again: the rows were renumbered)
             if not in_place:
                 old.close()
         self.logger.info("Flat index rebuilt")

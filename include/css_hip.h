@@ -209,6 +209,41 @@ int css_index_search_rows(css_index* ix, const int64_t* ids_host, int64_t nq, in
 int css_index_search_rows_dev(css_index* ix, const int64_t* ids_dev, int64_t nq, int k, int exclude_self,
                               const uint32_t* allow_bits_dev, float* D_dev, int64_t* I_dev, void* stream);
 
+/* Group labels and grouped search ("which conversations are nearest": Elasticsearch "collapse", Qdrant "search groups",
+ * Milvus "grouping search"): the best row of each of the k best groups, exactly.
+ *  - Labels.  Every row has an int32 group label.  A row that was never given one has -1, and so does a row given a
+ *    negative one; each such row is a group of its own and never collapses with anything.  Labels are per index, in
+ *    LOCAL row numbering like allow_bits (id_base plays no part).  css_index_set_groups writes the labels of rows
+ *    [row0, row0 + n), css_index_get_groups reads them back; a range outside [0, ntotal) is CSS_ERR_INVALID.  Both wait
+ *    for pending asynchronous adds; set takes the index exclusively (like css_index_add), get shares it (like
+ *    css_index_export).  The column (4 bytes per row of capacity) is allocated by the first css_index_set_groups: an
+ *    index that never sets labels pays nothing.  It follows the rows: kept through capacity growth, -1 for appended
+ *    rows, compacted by css_index_remove_rows with the same keep bits (afterwards get_groups = labels[keep]),
+ *    forgotten by css_index_reset.
+ *  - css_index_search_grouped.  For every query: the k best groups among the allowed rows.  A group is ranked by its
+ *    best allowed row under the index's total order (score, then lower id); the output is that row's score D, its
+ *    GLOBAL id I and the group's label G (-1 for an ungrouped row; G_host may be NULL).  Layout, order, tie rule and
+ *    padding are those of css_index_search_masked (I = -1, D = -FLT_MAX / +FLT_MAX) with G = -1 in padded slots;
+ *    normalize_q and allow_bits_host mean what they mean there.  1 <= k <= 128 (the kernels' list size), anything else
+ *    is CSS_ERR_INVALID.  Fewer than k groups among the allowed rows: a padded tail.  An empty index: fully padded
+ *    rows.  nq == 0 is a no-op.  An index with no labels at all returns exactly what css_index_search_masked returns
+ *    for the same k.
+ *  - Exactness.  In a best-first list of the top kk rows the first occurrences of distinct groups are exactly the best
+ *    groups, each with its best row, and every group that is absent has its best row below entry kk -- so the result
+ *    is exact whatever over-fetch is used.  Pass 1 searches the whole batch for kk rows (32 when 2k <= 32, else 128)
+ *    and collapses them on the device.  A query that then has neither k groups nor a padded list goes on alone: every
+ *    further pass searches 128 rows under an exclusion bitmap from which ALL rows of the groups already found were
+ *    dropped, so it brings at least one new group (at most k passes per query; one group that fills the lists costs
+ *    one extra pass, not one pass per 128 of its rows).  Queries that took several passes are sorted once more.
+ *  - The pass count depends on the data, so only a host form exists: it waits for the device between passes.
+ *    css_index_last_group_passes: search passes of the last grouped call (1 when pass 1 sufficed for every query). */
+int css_index_set_groups(css_index* ix, int64_t row0, int64_t n, const int32_t* labels_host);
+int css_index_get_groups(css_index* ix, int64_t row0, int64_t n, int32_t* labels_out_host);
+int css_index_search_grouped(css_index* ix, const float* q_host, int64_t nq, int k, int normalize_q,
+                             const uint32_t* allow_bits_host, float* D_host, int64_t* I_host,
+                             int32_t* G_host /* may be NULL */);
+int css_index_last_group_passes(css_index* ix, int64_t* n);   /* diagnostics: search passes of the last grouped call */
+
 /* Range search (faiss IndexFlat::range_search): EVERY row with score > radius (inner product) / squared distance
  * < radius (L2) -- strict, faiss' comparison -- as a variable-length hit list behind a handle.
  *  - Query j's hits are D / I[lims[j] .. lims[j+1]), lims[0] = 0 (nq + 1 entries).  Ids are global (id_base added),
