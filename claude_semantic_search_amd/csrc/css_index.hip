@@ -32,6 +32,8 @@
 //   k_drop_self        search for k + 1, and the anchor compacted out of its results behind it (a wave per query)
 //   k_collapse_groups, css_index_search_grouped: a pass's results collapsed to the first row of every group label, and
 //   k_mask_drop_groups the groups already found dropped from the exclusion bitmap of the next pass (css_knn_group.h)
+//   k_mmr_select       css_index_search_diverse: k of a pool of the best rows picked greedily by maximal marginal
+//                      relevance, similarities from the stored fp32 rows (css_knn_diverse.h)
 //
 // Host plumbing, one place per rule: the row storage and every workspace are DevBufs (css_devbuf.h: owning, freed with
 // the index, one of three growth policies); a search reads the rows through a Rows value taken under the shared lock
@@ -159,6 +161,9 @@ struct css_index {
     DevBuf<int32_t> grp_l;
     DevBuf<int> grp_state;              // [nq] counts | [nq] flags
     int64_t last_group_passes = 0;      // search passes of the last grouped call (css_index_last_group_passes)
+    // css_index_search_diverse: the [nq, fetch] pool lists of the search in front of k_mmr_select
+    DevBuf<float> div_d;                // entries
+    DevBuf<int64_t> div_i;
     // rows written by css_index_add_dev / _add_synthetic on the CALLER's stream: searches, reallocation and
     // export wait for this event before touching rows, norms or maxn2
     hipEvent_t ingest_ev = nullptr;
@@ -1578,6 +1583,7 @@ __global__ void k_fill_int(int* p, int n, int v) {
 }
 
 #include "css_knn_group.h"
+#include "css_knn_diverse.h"
 
 // ---------------------------------------------------------------- host side
 // bf16 shadow rows for the coarse scan: kept when the metric is inner product, rows are a whole number
@@ -3674,6 +3680,105 @@ int css_index_last_group_passes(css_index* ix, int64_t* n) {
     *n = ix->last_group_passes;
     return CSS_OK;
 }
+
+// ------------------------------------------------------------------ diversified search (MMR over a pool of the best rows)
+namespace {
+// lam in [0, 1], fetch 0 (automatic: the two list classes of the grouped search) or in [1, 128], 1 <= k <= fetch
+int check_diverse_args(const char* fn, int k, int* fetch, float lam) {
+    CSS_REQUIRE(lam >= 0.f && lam <= 1.f, "%s: lam=%g outside [0, 1]", fn, (double)lam);   // (a NaN fails both)
+    CSS_REQUIRE(*fetch >= 0 && *fetch <= CSS_KERNEL_MAX_K, "%s: fetch=%d outside [0, %d] (0: automatic)", fn, *fetch,
+                CSS_KERNEL_MAX_K);
+    if (*fetch == 0) *fetch = (k <= 8) ? 32 : CSS_KERNEL_MAX_K;   // 4k <= 32
+    CSS_REQUIRE(k >= 1 && k <= *fetch, "%s: k=%d outside [1, fetch=%d]", fn, k, *fetch);
+    return CSS_OK;
+}
+
+// The ordinary search for the pool (search_any_k: every mode, shadow policy and mask as css_index_search_masked_dev
+// has them) into the owned pool lists, and the selection behind it.  Everything is enqueued on `st`; nothing waits
+// for the device.  Caller holds ws_mu and a shared lock on mu.
+int search_diverse_enqueue(css_index* ix, const Rows& rows, const float* q_dev, int64_t nq, int k, int fetch, float lam,
+                           int normalize_q, float* D_dev, int64_t* I_dev, hipStream_t st) {
+    int rc;
+    WsTurn turn(ix, st);   // (until the end: the selection reads the pool lists)
+    if (turn.rc != CSS_OK) return turn.rc;
+    // rows appended on another stream must have landed (an empty pool search does not wait for them itself)
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    if ((rc = ix->div_d.grow((size_t)nq * fetch)) != CSS_OK) return rc;
+    if ((rc = ix->div_i.grow((size_t)nq * fetch)) != CSS_OK) return rc;
+    if ((rc = search_any_k(ix, rows, q_dev, nq, fetch, normalize_q, ix->div_d.p, ix->div_i.p, st)) != CSS_OK) return rc;
+    ProfScope ps("knn_mmr_select", st);
+    if (ix->metric == CSS_METRIC_IP)
+        hipLaunchKernelGGL(k_mmr_select<CSS_METRIC_IP>, dim3((unsigned)nq), dim3(256), 0, st, (const float*)ix->div_d.p,
+                           (const int64_t*)ix->div_i.p, rows.xb, rows.n, rows.id_base, ix->dim, ix->dpad, fetch, k, lam,
+                           -FLT_MAX, D_dev, I_dev);
+    else
+        hipLaunchKernelGGL(k_mmr_select<CSS_METRIC_L2>, dim3((unsigned)nq), dim3(256), 0, st, (const float*)ix->div_d.p,
+                           (const int64_t*)ix->div_i.p, rows.xb, rows.n, rows.id_base, ix->dim, ix->dpad, fetch, k, lam,
+                           FLT_MAX, D_dev, I_dev);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_search_diverse_dev(css_index* ix, const float* q_dev, int64_t nq, int k, int fetch, float lam, int normalize_q,
+                                 const uint32_t* allow_bits_dev, float* D_dev, int64_t* I_dev, void* stream) {
+    CSS_REQUIRE(ix, "css_index_search_diverse_dev: NULL index");
+    CSS_REQUIRE(nq >= 0 && nq < (1 << 24), "css_index_search_diverse_dev: nq=%lld out of range", (long long)nq);
+    int rc;
+    if ((rc = check_diverse_args("css_index_search_diverse_dev", k, &fetch, lam)) != CSS_OK) return rc;
+    if (nq == 0) return CSS_OK;
+    CSS_REQUIRE(q_dev && D_dev && I_dev, "css_index_search_diverse_dev: NULL buffer");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    DeviceGuard g(ix->device);
+    return search_diverse_enqueue(ix, rows_of(ix, allow_bits_dev), q_dev, nq, k, fetch, lam, normalize_q, D_dev, I_dev,
+                                  (hipStream_t)stream);
+}
+
+int css_index_search_diverse(css_index* ix, const float* q_host, int64_t nq, int k, int fetch, float lam, int normalize_q,
+                             const uint32_t* allow_bits_host, float* D_host, int64_t* I_host) {
+    CSS_REQUIRE(ix, "css_index_search_diverse: NULL index");
+    CSS_REQUIRE(nq >= 0 && nq < (1 << 24), "css_index_search_diverse: nq=%lld out of range", (long long)nq);
+    int rc;
+    if ((rc = check_diverse_args("css_index_search_diverse", k, &fetch, lam)) != CSS_OK) return rc;
+    if (nq == 0) return CSS_OK;
+    CSS_REQUIRE(q_host && D_host && I_host, "css_index_search_diverse: NULL buffer");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    DeviceGuard g(ix->device);
+    const size_t n = (size_t)nq * k;
+    if ((rc = ix->q_raw.grow((size_t)nq * ix->dim)) != CSS_OK) return rc;
+    float* d_out;
+    int64_t* i_out;
+    if ((rc = reserve_out(ix, n, &d_out, &i_out)) != CSS_OK) return rc;
+    const size_t q_bytes = (size_t)nq * ix->dim * 4, out_bytes = n * 12;
+    const bool staged = q_bytes <= css_index::kHostStage && out_bytes <= css_index::kHostStage;
+    if (staged && ix->h_stage == nullptr)
+        CSS_HIP_TRY(hipHostMalloc((void**)&ix->h_stage, 2 * css_index::kHostStage, hipHostMallocDefault));
+    Rows rows = rows_of(ix);
+    if ((rc = upload_allow_bits(ix, allow_bits_host, &rows)) != CSS_OK) return rc;
+    if (staged) {
+        memcpy(ix->h_stage, q_host, q_bytes);
+        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, ix->h_stage, q_bytes, hipMemcpyHostToDevice, ix->stream));
+    } else {
+        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, q_host, q_bytes, hipMemcpyHostToDevice, ix->stream));
+    }
+    rc = search_diverse_enqueue(ix, rows, ix->q_raw.p, nq, k, fetch, lam, normalize_q, d_out, i_out, ix->stream);
+    if (rc != CSS_OK) {
+        (void)hipStreamSynchronize(ix->stream);   // (the copies above read the caller's memory)
+        return rc;
+    }
+    if (staged) {   // one copy into pinned memory, one wait
+        char* back = ix->h_stage + css_index::kHostStage;
+        CSS_HIP_TRY(hipMemcpyAsync(back, i_out, out_bytes, hipMemcpyDeviceToHost, ix->stream));
+        CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+        memcpy(I_host, back, n * 8);
+        memcpy(D_host, back + n * 8, n * 4);
+        return CSS_OK;
+    }
+    return fetch_out(ix, n, d_out, i_out, D_host, I_host);
+}
+
 
 
 namespace {

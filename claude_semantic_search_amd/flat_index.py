@@ -135,6 +135,67 @@ def collapse_groups(D, I, G, k: int, metric: int) -> Tuple[np.ndarray, np.ndarra
     return Do, Io, Go
 
 
+MAX_DIVERSE_FETCH = nat.MAX_DIVERSE_FETCH
+
+
+def diverse_args(k, fetch, lam) -> Tuple[int, int, float]:
+    """The argument rules of ``search_diverse`` (``css_index_search_diverse``): ``(k, fetch, lam)`` with the automatic
+    pool size resolved -- ``fetch = 0`` means 32 if ``4k <= 32``, otherwise 128.  ``lam`` outside ``[0, 1]`` (or NaN),
+    ``fetch`` outside ``[0, 128]`` and ``k`` outside ``[1, fetch]`` raise ``ValueError``."""
+    k, fetch, lam = int(k), int(fetch), float(lam)
+    if not (0.0 <= lam <= 1.0):   # (a NaN fails both comparisons)
+        raise ValueError(f"lam={lam} outside [0, 1]")
+    if fetch < 0 or fetch > MAX_DIVERSE_FETCH:
+        raise ValueError(f"fetch={fetch} outside [0, {MAX_DIVERSE_FETCH}] (0: automatic)")
+    if fetch == 0:
+        fetch = 32 if 4 * k <= 32 else MAX_DIVERSE_FETCH
+    if k < 1 or k > fetch:
+        raise ValueError(f"k={k} outside [1, fetch={fetch}]")
+    return k, fetch, lam
+
+
+def mmr_select(S, I, X, k: int, lam: float, metric: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The selection rule of ``search_diverse`` (the library's ``k_mmr_select``), stated in numpy.  ``S, I`` are
+    ``[nq, m]`` best-first lists (scores, ids; pads ``I = -1`` at the tail) and ``X`` is ``[nq, m, d]``, the candidates'
+    stored rows (rows of pads are not looked at).  Everything is float32.  Relevance is ``S`` for the inner product and
+    ``-S`` for L2; ``sim(a, b)`` is ``<x_a, x_b>`` resp. ``-sum((x_a - x_b)^2)``.  Pick 0 is candidate 0; pick ``t`` is the
+    unpicked valid candidate with the largest ``lam * rel - (1 - lam) * max_{u < t} sim(c, p_u)``, ties to the smaller
+    list position.  Returns ``(D[nq, k], I[nq, k])`` in PICK order: the picks' own scores and ids, padded like
+    ``search``.  (The sharded index selects with this after the exchange of the pool's rows.)"""
+    S, I, X = np.asarray(S, np.float32), np.asarray(I, np.int64), np.asarray(X, np.float32)
+    nq, m = I.shape
+    k, lam = int(k), np.float32(lam)
+    oml = np.float32(1.0) - lam
+    Do = np.full((nq, k), -np.finfo(np.float32).max if metric == METRIC_INNER_PRODUCT else np.finfo(np.float32).max,
+                 dtype=np.float32)
+    Io = np.full((nq, k), -1, dtype=np.int64)
+    for j in range(nq):
+        valid = I[j] >= 0
+        npick = min(k, int(valid.sum()))
+        if npick == 0 or not valid[0]:
+            continue
+        rel = S[j] if metric == METRIC_INNER_PRODUCT else -S[j]
+        pen = np.full(m, -np.inf if lam != 1 else 0.0, dtype=np.float32)   # (lam == 1: the term is 0 whatever the rows hold)
+        free = valid.copy()
+        last = 0
+        for t in range(npick):
+            if t:
+                if lam != 1:
+                    if metric == METRIC_INNER_PRODUCT:
+                        sim = (X[j] * X[j, last][None, :]).sum(axis=1, dtype=np.float32)
+                    else:
+                        diff = X[j] - X[j, last][None, :]
+                        sim = -(diff * diff).sum(axis=1, dtype=np.float32)
+                    pen = np.where(free, np.maximum(pen, sim), pen)
+                v = np.where(free, lam * rel - oml * pen, -np.inf).astype(np.float32)
+                v[np.isnan(v)] = -np.inf
+                cand = np.flatnonzero(free)
+                last = int(cand[np.argmax(v[cand])])        # (argmax returns the first maximum: the smaller position)
+            free[last] = False
+            Do[j, t], Io[j, t] = S[j, last], I[j, last]
+    return Do, Io
+
+
 class IndexFlat:
     """Exact brute-force index in HBM (``faiss.IndexFlat`` semantics)."""
 
@@ -321,6 +382,41 @@ class IndexFlat:
         n = ctypes.c_int64(0)
         nat.check(nat.lib().css_index_last_group_passes(self._handle(), ctypes.byref(n)))
         return int(n.value)
+
+    # -- diversified search (MMR) --------------------------------------------
+    def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False,
+                       allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``k`` rows per query picked by maximal marginal relevance from the ``fetch`` best rows
+        (``css_index_search_diverse``): ``(D[nq,k], I[nq,k])`` in PICK order, ``D`` the ordinary query scores, padded like
+        ``search``.  Pick 0 is the best row; every further pick maximises ``lam * relevance - (1 - lam) * (largest
+        similarity to a row already picked)``, similarities formed in fp32 from the stored rows inside the index --
+        near-copies of one passage do not fill the answer.  ``lam = 1`` is ``search(q, k)``.  ``1 <= k <= fetch <= 128``;
+        ``fetch = 0`` chooses 32 (``4k <= 32``) or 128.  ``allow`` restricts the pool as in ``search``."""
+        a = _as_f32_2d(q, self.d, "search_diverse")
+        k, fetch, lam = diverse_args(k, fetch, lam)
+        nq = a.shape[0]
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        h = self._handle()
+        bits = None
+        if allow is not None:
+            bits = pack_allow_bits(allow, self.ntotal)
+        if nq:
+            nat.check(nat.lib().css_index_search_diverse(h, a.ctypes.data, nq, k, fetch, lam, 1 if normalize else 0,
+                                                         bits.ctypes.data if bits is not None else None,
+                                                         D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    def search_diverse_dev(self, q_ptr: int, nq: int, k: int, D_ptr: int, I_ptr: int, stream: int = 0, lam: float = 0.5,
+                           fetch: int = 0, normalize: bool = False, allow_bits_ptr: int = 0) -> None:
+        """Device-pointer twin of ``search_diverse`` (argument order of ``search_dev``): everything is enqueued on
+        ``stream``, nothing waits for the device."""
+        k, fetch, lam = diverse_args(k, fetch, lam)
+        nat.check(nat.lib().css_index_search_diverse_dev(self._handle(), ctypes.c_void_p(q_ptr), int(nq), k, fetch, lam,
+                                                         1 if normalize else 0,
+                                                         ctypes.c_void_p(allow_bits_ptr) if allow_bits_ptr else None,
+                                                         ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr),
+                                                         ctypes.c_void_p(stream)))
 
     def search_dev(self, q_ptr: int, nq: int, k: int, D_ptr: int, I_ptr: int, stream: int = 0,
                    normalize: bool = False, allow_bits_ptr: int = 0) -> None:

@@ -45,7 +45,7 @@ class ShardedFlatIndex:
     """``IndexFlat`` semantics over ``world`` row shards.
 
     ``local_index`` must offer ``ntotal``, ``add(x, normalize=)``, ``add_synthetic``, ``set_id_base`` and
-    ``search_dev``/``search`` (``range_search`` for ``range_search``, ``reconstruct_n`` for ``search_by_ids``); ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
+    ``search_dev``/``search`` (``range_search`` for ``range_search``, ``reconstruct_n`` for ``search_by_ids`` and ``search_diverse``); ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
     implementations; tests substitute doubles.
     """
 
@@ -380,6 +380,47 @@ class ShardedFlatIndex:
             Ig[j], Dg[j], Gg[j] = Ig[j][order], Dg[j][order], Gg[j][order]
         return collapse_groups(Dg, Ig, Gg, k, self.metric)
 
+    # -- diversified search ------------------------------------------------------------------------------------
+    def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
+        """``IndexFlat.search_diverse`` over the shards (collective: every rank passes the same arguments): ``(D, I)``
+        with global ids, in pick order, on every rank.  Three steps: (1) the usual search for ``fetch`` rows -- local
+        masked search, the one packed all-gather, the merge -- after which every rank holds the global pool; (2) the
+        rank that owns a candidate supplies its stored row, every other rank zeros, and ONE sum all-reduce of the
+        ``[nq, fetch, d]`` buffer hands every rank every candidate's row (exact: one non-zero contribution per row, the
+        trick of ``search_by_ids``); (3) ``flat_index.mmr_select`` runs on every rank.  The exchange of step 2 is
+        ``nq * fetch * d * 4`` bytes (393 KB per query at ``fetch = 128``, ``d = 768``), so the call is meant for few
+        queries -- the interactive search, not a batch job.  With one rank (and no forced exchange) the whole call is
+        the local index's ``search_diverse``, selection on the device included."""
+        import torch
+
+        from .flat_index import diverse_args, mmr_select
+
+        qa = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.d)
+        k, fetch, lam = diverse_args(k, fetch, lam)
+        nq = qa.shape[0]
+        if self.world == 1 and not self.exchange_when_single:
+            loc = self._local_allow(allow)
+            kw = {"allow": loc} if loc is not None else {}
+            D, I = self.local.search_diverse(qa, k, lam=lam, fetch=fetch, normalize=normalize, **kw)
+            I = np.asarray(I, dtype=np.int64)
+            if len(self.segments) > 1:
+                I = np.where(I >= 0, self._to_global_np(np.maximum(I, 0)), -1)
+            return np.ascontiguousarray(D, dtype=np.float32), np.ascontiguousarray(I)
+        if nq == 0:
+            return np.empty((0, k), dtype=np.float32), np.empty((0, k), dtype=np.int64)
+        S, I = self.search(qa, fetch, normalize=normalize, allow=allow)
+        rows = np.zeros((nq, fetch, self.d), dtype=np.float32)
+        for l0, g0, m in self.segments:
+            for j, c in np.argwhere((I >= g0) & (I < g0 + m)):
+                rows[j, c] = self.local.reconstruct_n(l0 + int(I[j, c]) - g0, 1)[0]
+        if self.world > 1:
+            t = torch.from_numpy(rows)
+            if self.dist.get_backend(self.group) != "gloo":
+                t = t.to(f"cuda:{self.device_index or 0}")
+            self.dist.all_reduce(t, group=self.group)
+            rows = t.cpu().numpy()
+        return mmr_select(S, I, rows, k, lam, self.metric)
+
     # -- related rows ----------------------------------------------------------------------------------------------
     def search_by_ids(self, ids, k: int, exclude_self: bool = True, allow=None):
         """``IndexFlat.search_by_ids`` over the shards (collective: every rank passes the same arguments): ``ids`` are
@@ -491,6 +532,10 @@ class ShardedIndexFacade:
 
     def search_grouped(self, q, k: int, normalize: bool = False, allow=None):
         return self.sh.search_grouped(np.asarray(q, dtype=np.float32), int(k), normalize=normalize, allow=allow)
+
+    def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
+        return self.sh.search_diverse(np.asarray(q, dtype=np.float32), int(k), lam=lam, fetch=fetch, normalize=normalize,
+                                      allow=allow)
 
     def reconstruct_n(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
         return self.sh.reconstruct_n(int(row0), self.ntotal - int(row0) if n is None else int(n))

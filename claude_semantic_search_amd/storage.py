@@ -501,6 +501,42 @@ class HybridStorage:
                 sims, ids, _ = self.faiss_index.search_grouped(q, k, normalize=self.config.normalize_embeddings)
             return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
 
+    def search_diverse(self, query_embedding, config: Optional[SearchConfig] = None,
+                       filters: Optional[Dict[str, Any]] = None, lam: float = 0.5) -> List[SearchResult]:
+        """``top_k`` chunks picked by maximal marginal relevance (``IndexFlat.search_diverse``) -- where ``search()``
+        returns the same stack trace or prompt pasted into ten conversations ten times, this returns it once and goes
+        on to other passages.  The first result is ``search()``'s first; every further one trades its similarity to
+        the query against its similarity to the chunks already chosen (``lam = 1``: ``search()``'s order, ``lam = 0``:
+        diversity alone).  Results come in PICK order, each with its ordinary similarity, so they are not sorted by it.
+        The pool is the best 32 rows (``4 * k <= 32``) or 128, and the selection runs inside the index over the stored
+        rows.
+
+        Threshold, tombstones, ``filters`` and ``filter_pushdown`` mean what they mean in ``search()``; the threshold
+        is applied to the picks in pick order.  Tombstones always go into the allow mask, so a deleted chunk neither
+        is picked nor repels others.  With ``filter_pushdown`` the filters go there too and ``k = top_k`` picks are
+        made.  Without it and with filters, ``k = min(max(top_k, max_results), 128)`` picks are made and filtered in
+        pick order, as ``search()`` filters rows: a chunk that fails the filter still stood in the way of its
+        near-copies.  An index object without ``search_diverse`` raises ``NotImplementedError``."""
+        cfg = config or SearchConfig()
+        if not self.faiss_index:
+            return []
+        if not hasattr(self.faiss_index, "search_diverse"):
+            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no diversified search (search_diverse)")
+        with self._lock:
+            ntotal = self.faiss_index.ntotal
+            if ntotal == 0 or cfg.top_k <= 0:
+                return []
+            q = np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
+            pushdown = bool(self.config.filter_pushdown)
+            allow = None
+            if (pushdown and filters) or len(self.faiss_id_to_chunk_id) < ntotal:
+                allow = self._allow_mask((filters or {}) if pushdown else {}, ntotal)
+            k = cfg.top_k if (pushdown or not filters) else max(cfg.top_k, cfg.max_results)
+            k = max(1, min(k, fi.MAX_DIVERSE_FETCH))
+            kw = {"allow": allow} if allow is not None else {}
+            sims, ids = self.faiss_index.search_diverse(q, k, lam=lam, normalize=self.config.normalize_embeddings, **kw)
+            return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
+
     @staticmethod
     def _make_result(chunk_id: str, score: float, data: Dict[str, Any], cfg: SearchConfig) -> SearchResult:
         res = SearchResult(chunk_id=chunk_id, similarity=float(score))

@@ -244,6 +244,42 @@ int css_index_search_grouped(css_index* ix, const float* q_host, int64_t nq, int
                              int32_t* G_host /* may be NULL */);
 int css_index_last_group_passes(css_index* ix, int64_t* n);   /* diagnostics: search passes of the last grouped call */
 
+/* Diversified search (maximal marginal relevance, MMR; langchain's max_marginal_relevance_search, the "diversity"
+ * option of vector stores): k rows picked greedily from a pool of the best rows, each pick trading its score against
+ * its similarity to the rows already picked -- so near-copies of one passage do not fill the answer.  Per query, with
+ * m = fetch and the weight lam in [0, 1]:
+ *  1. Candidates.  The ordinary ranked, masked search for m rows (what css_index_search_masked returns for k = m: search
+ *     mode, reduced-precision copies, mask as there): a best-first list (s_c, id_c), c = 0 .. m'-1, of m' <= m valid
+ *     entries with the pads at the tail.
+ *  2. Relevance.  rel_c = s_c for the inner product, rel_c = -s_c for L2.
+ *  3. Similarity.  sim(a, b) is formed in fp32 from the STORED fp32 rows, never from the bf16 or int8 copies:
+ *     <x_a, x_b> for the inner product; -||x_a - x_b||^2 for L2, summed as squared differences (so copies of a row give
+ *     exactly 0; norms minus twice the product would not).
+ *  4. Picks.  p_0 = 0.  For t >= 1: pen_c = max over u < t of sim(c, p_u), v_c = lam * rel_c - (1 - lam) * pen_c in fp32
+ *     (two products and a difference, each rounded), and p_t is the unpicked valid c with the largest v_c; ties go to the
+ *     smaller c, i.e. the better score, then the lower id.
+ *  5. Output.  D[j, t] = s_{p_t}, I[j, t] = id_{p_t} for t < min(k, m'), in PICK order (not sorted by D), then padded
+ *     like css_index_search (I = -1, D = -FLT_MAX / +FLT_MAX).  D is the ordinary query score, so thresholds keep their
+ *     meaning.
+ *  - lam = 1 picks the first k entries of the pool: what css_index_search_masked returns for k.  (A score's last bits
+ *    depend on the kernel that formed it, which the search chooses by nq, k and the index size; D here carries the bits
+ *    of the search for m rows.)  lam = 0 ignores the query beyond the choice of the pool.
+ *  - Limits: 1 <= k <= fetch <= 128 (the kernels' list size).  fetch = 0 means automatic: 32 if 4k <= 32, otherwise 128
+ *    -- the two list classes of the grouped search.  lam outside [0, 1] or NaN, and any other value of k or fetch, is
+ *    CSS_ERR_INVALID; the message names the argument.
+ *  - An empty index gives fully padded rows; nq == 0 is a no-op.  normalize_q, allow_bits, rows appended on other
+ *    streams, the serialisation of the searches of one index and the shared workspaces are those of
+ *    css_index_search_masked / _dev.
+ *  - On the device: the pool search writes into lists the index owns ([nq, fetch]); then one 256-thread block per query
+ *    keeps rel, pen and the candidates' rows in LDS, updates pen against the LAST pick only -- (k - 1) * m' row pairs
+ *    are read in place per query, there is no gathered copy and no m x m matrix -- and closes every step with a
+ *    block-wide argmax.  Nothing depends on a readback: the _dev form enqueues everything on `stream` and returns. */
+int css_index_search_diverse(css_index* ix, const float* q_host, int64_t nq, int k, int fetch, float lam,
+                             int normalize_q, const uint32_t* allow_bits_host, float* D_host, int64_t* I_host);
+int css_index_search_diverse_dev(css_index* ix, const float* q_dev, int64_t nq, int k, int fetch, float lam,
+                                 int normalize_q, const uint32_t* allow_bits_dev, float* D_dev, int64_t* I_dev,
+                                 void* stream);
+
 /* Range search (faiss IndexFlat::range_search): EVERY row with score > radius (inner product) / squared distance
  * < radius (L2) -- strict, faiss' comparison -- as a variable-length hit list behind a handle.
  *  - Query j's hits are D / I[lims[j] .. lims[j+1]), lims[0] = 0 (nq + 1 entries).  Ids are global (id_base added),
