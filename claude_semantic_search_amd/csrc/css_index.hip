@@ -39,8 +39,9 @@
 // the index, one of three growth policies); a search reads the rows through a Rows value taken under the shared lock
 // (rows_of; a row range is Rows::range) and nothing under the shared lock writes a row field of css_index; WsTurn is a
 // search's turn at the shared workspaces (wait for the previous stream's event,
-// record at the end); prep_queries, upload_allow_bits, reserve_out / fetch_out are the query preparation, the mask
-// upload and the result staging of every entry point; sweep_grid is the grid of both exact sweeps.  The sweep body of
+// record at the end); CallScope is the lock and device frame of every search entry point and HostCall the whole frame
+// of the host ones (allow-bitmap and input up, result rows reserved, results back; pinned staging for small calls);
+// prep_queries is the query preparation of every search; sweep_grid is the grid of both exact sweeps.  The sweep body of
 // k_scan_small and k_range_small is deliberately NOT shared (css_knn_range.h says why).
 #include "css_common.h"
 #include "css_devbuf.h"
@@ -55,6 +56,7 @@
 #include <cmath>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <shared_mutex>
 #include <type_traits>
 #include <vector>
@@ -111,6 +113,7 @@ struct css_index {
     // copies of that size cost a staging pass and a wait each
     char* h_stage = nullptr;
     static constexpr size_t kHostStage = 64 * 1024;   // bytes, each way
+    static bool fits_host_stage(size_t bytes) { return bytes <= kHostStage; }
     DevBuf<float> stage;                // floats
     // css_index_remove_rows: keep bits and their popcount prefix of ONE window of rows (at most 2 MiB each)
     DevBuf<uint32_t> compact_bits, compact_pre;   // words
@@ -2783,6 +2786,32 @@ struct WsTurn {
     }
 };
 
+// The lock and device frame of every search entry point, host or `_dev`: the shared lock on mu, ws_mu, the rows as a
+// value (mask_dev: the device allow-bitmap of a `_dev` call) and the index's device made current.  on_empty = false
+// leaves the device alone when the index has no rows (css_index_range_search answers that without one).
+struct CallScope {
+    css_index* ix;
+    std::shared_lock<std::shared_mutex> lk;
+    std::lock_guard<std::mutex> wl;
+    Rows rows;
+    std::optional<DeviceGuard> dev;
+    explicit CallScope(css_index* i, const uint32_t* mask_dev = nullptr, bool on_empty = true)
+        : ix(i), lk(i->mu), wl(i->ws_mu), rows(rows_of(i, mask_dev)) {
+        if (on_empty || rows.n > 0) dev.emplace(i->device);
+    }
+};
+
+// the score of an output slot that no row fills: the worst of the metric
+inline float pad_score(const css_index* ix) { return ix->metric == CSS_METRIC_IP ? -FLT_MAX : FLT_MAX; }
+
+// `nrows` output rows of k entries each put in best-first order (score, then id)
+int launch_sort_rows(css_index* ix, float* D, int64_t* I, int64_t nrows, int k, hipStream_t st) {
+    if (ix->metric == CSS_METRIC_IP) hipLaunchKernelGGL(k_sort_rows<CSS_METRIC_IP>, dim3((unsigned)nrows), dim3(1024), 0, st, D, I, k);
+    else hipLaunchKernelGGL(k_sort_rows<CSS_METRIC_L2>, dim3((unsigned)nrows), dim3(1024), 0, st, D, I, k);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
 // Query prep of every search: the row kernel of ingest (normalise, zero pad, squared norm) from raw [nq, dim] rows
 // into qpad / qnorm2, and ||q - bf16(q)||^2 into `qerr2` where the caller keeps it.
 int prep_queries(css_index* ix, const float* src, int64_t nq, int normalize_q, float* qerr2, hipStream_t st) {
@@ -2835,8 +2864,7 @@ int search_dev_enqueue(css_index* ix, const Rows& rows, const float* q_dev, int6
     if (!sweep_path && (rc = prep_queries(ix, q_dev, nq, normalize_q, ix->qerr2.p, st)) != CSS_OK) return rc;
     if (rows.n == 0) {
         const int64_t n = nq * k;
-        hipLaunchKernelGGL(k_fill_pad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, n,
-                           ix->metric == CSS_METRIC_IP ? -FLT_MAX : FLT_MAX);
+        hipLaunchKernelGGL(k_fill_pad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, n, pad_score(ix));
         CSS_LAUNCH_CHECK();
         return CSS_OK;
     }
@@ -3368,13 +3396,77 @@ int reserve_out(css_index* ix, size_t n, float** d_out, int64_t** i_out) {
     return CSS_OK;
 }
 
-// ... and back into the caller's D / I; everything on the stream has finished when this returns
-int fetch_out(css_index* ix, size_t n, const float* d_out, const int64_t* i_out, float* D_host, int64_t* I_host) {
-    CSS_HIP_TRY(hipMemcpyAsync(D_host, d_out, n * 4, hipMemcpyDeviceToHost, ix->stream));
-    CSS_HIP_TRY(hipMemcpyAsync(I_host, i_out, n * 8, hipMemcpyDeviceToHost, ix->stream));
-    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
-    return CSS_OK;
-}
+// RAII: the frame of a host entry point around what it enqueues on the index's own stream.  The scope (CallScope)
+// holds the locks, the device and the call's rows; upload() brings the caller's allow-bitmap and input over and
+// reserves the result rows; finish() brings the results back.  Between the two the entry point enqueues its own
+// search with `rows`, `d_out`, `i_out` (and `g_out`).  Input and results go through the pinned halves of h_stage
+// (front: in, back: out) when BOTH fit kHostStage -- one copy and one wait, against a staging pass and a wait per
+// pageable copy -- and directly otherwise.  The back half belongs to the scope only inside finish(): read_ints uses it
+// in between.
+extern "C++" {   // (upload is a template, and this part of the file is inside extern "C")
+struct HostCall : CallScope {
+    using CallScope::CallScope;
+    static constexpr size_t kEntry = sizeof(int64_t) + sizeof(float);   // an [id | score] entry of out_i
+    size_t n = 0;   // result entries
+    float* d_out = nullptr;
+    int64_t* i_out = nullptr;
+    int32_t* g_out = nullptr;   // the trailing int32 column of the results, where the call has one
+    bool staged = false, enqueued = false;
+    // the ONE size of a result entry: the staging decision and the offsets of the copy back both use it
+    size_t record() const { return kEntry + (g_out ? sizeof(int32_t) : 0); }
+
+    // `count` elements from `src` into `dst`, the allow-bitmap (null: every row) into the mask of `rows`, and n_out
+    // result entries reserved: [ids | scores] in out_i, their int32 column in `column` where the call names one
+    template <typename T>
+    int upload(const uint32_t* bits_host, DevBuf<T>& dst, const T* src, size_t count, size_t n_out = 0,
+               DevBuf<int32_t>* column = nullptr) {
+        int rc;
+        n = n_out;
+        if ((rc = dst.grow(count)) != CSS_OK) return rc;
+        if (column) {
+            if ((rc = column->grow(n)) != CSS_OK) return rc;
+            g_out = column->p;
+        }
+        if (n && (rc = reserve_out(ix, n, &d_out, &i_out)) != CSS_OK) return rc;
+        const size_t bytes = count * sizeof(T);
+        staged = css_index::fits_host_stage(bytes) && css_index::fits_host_stage(n * record());
+        if (staged && ix->h_stage == nullptr)
+            CSS_HIP_TRY(hipHostMalloc((void**)&ix->h_stage, 2 * css_index::kHostStage, hipHostMallocDefault));
+        enqueued = true;
+        if ((rc = upload_allow_bits(ix, bits_host, &rows)) != CSS_OK) return rc;
+        const void* from = staged ? memcpy(ix->h_stage, src, bytes) : src;
+        CSS_HIP_TRY(hipMemcpyAsync(dst.p, from, bytes, hipMemcpyHostToDevice, ix->stream));
+        return CSS_OK;
+    }
+    // a failed call returns only when the stream is idle: the copies enqueued above read the caller's memory
+    int wait_if_failed(int rc) {
+        if (rc != CSS_OK && enqueued) (void)hipStreamSynchronize(ix->stream);
+        return rc;
+    }
+    // rc: what upload() and the enqueue returned.  The results into the caller's D / I (and G: null, or a call
+    // without the column, copies none); everything on the stream has finished when this returns.
+    int finish(int rc, float* D_host, int64_t* I_host, int32_t* G_host = nullptr) {
+        if (rc != CSS_OK) return wait_if_failed(rc);
+        const hipStream_t st = ix->stream;
+        if (!g_out) G_host = nullptr;
+        if (staged) {   // one wait: [ids | scores] in one copy, and the column, into pinned memory
+            char* back = ix->h_stage + css_index::kHostStage;
+            CSS_HIP_TRY(hipMemcpyAsync(back, i_out, n * kEntry, hipMemcpyDeviceToHost, st));
+            if (G_host) CSS_HIP_TRY(hipMemcpyAsync(back + n * kEntry, g_out, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            CSS_HIP_TRY(hipStreamSynchronize(st));
+            memcpy(I_host, back, n * sizeof(int64_t));
+            memcpy(D_host, back + n * sizeof(int64_t), n * sizeof(float));
+            if (G_host) memcpy(G_host, back + n * kEntry, n * sizeof(int32_t));
+            return CSS_OK;
+        }
+        CSS_HIP_TRY(hipMemcpyAsync(D_host, d_out, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipMemcpyAsync(I_host, i_out, n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        if (G_host) CSS_HIP_TRY(hipMemcpyAsync(G_host, g_out, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipStreamSynchronize(st));
+        return CSS_OK;
+    }
+};
+}  // extern "C++"
 
 // Any k in [1, CSS_MAX_K].  Up to CSS_KERNEL_MAX_K: one search.  Beyond: per query, ceil(k / CSS_KERNEL_MAX_K) passes of
 // the SAME search paths, pass p over the allowed rows the passes before it did not return (exclusion bitmap), its
@@ -3409,10 +3501,7 @@ int search_any_k(css_index* ix, const Rows& rows, const float* q_dev, int64_t nq
             }
         }
     }
-    if (ix->metric == CSS_METRIC_IP) hipLaunchKernelGGL(k_sort_rows<CSS_METRIC_IP>, dim3((unsigned)nq), dim3(1024), 0, st, D_dev, I_dev, k);
-    else hipLaunchKernelGGL(k_sort_rows<CSS_METRIC_L2>, dim3((unsigned)nq), dim3(1024), 0, st, D_dev, I_dev, k);
-    CSS_LAUNCH_CHECK();
-    return CSS_OK;
+    return launch_sort_rows(ix, D_dev, I_dev, nq, k, st);
 }
 }  // namespace
 
@@ -3420,10 +3509,8 @@ int css_index_search_masked_dev(css_index* ix, const float* q_dev, int64_t nq, i
                                 const uint32_t* allow_bits_dev, float* D_dev, int64_t* I_dev, void* stream) {
     CSS_REQUIRE(ix, "css_index_search_dev: NULL index");
     CSS_REQUIRE(nq == 0 || (q_dev && D_dev && I_dev), "css_index_search_dev: NULL buffer");
-    std::shared_lock<std::shared_mutex> lk(ix->mu);
-    std::lock_guard<std::mutex> wl(ix->ws_mu);
-    DeviceGuard g(ix->device);
-    return search_any_k(ix, rows_of(ix, allow_bits_dev), q_dev, nq, k, normalize_q, D_dev, I_dev, (hipStream_t)stream);
+    CallScope cs(ix, allow_bits_dev);
+    return search_any_k(ix, cs.rows, q_dev, nq, k, normalize_q, D_dev, I_dev, (hipStream_t)stream);
 }
 
 int css_index_search_dev(css_index* ix, const float* q_dev, int64_t nq, int k, int normalize_q, float* D_dev,
@@ -3438,36 +3525,10 @@ int css_index_search_masked(css_index* ix, const float* q_host, int64_t nq, int 
     if (nq == 0) return CSS_OK;
     CSS_REQUIRE(q_host && D_host && I_host, "css_index_search: NULL buffer");
     CSS_REQUIRE(k >= 1 && k <= CSS_MAX_K, "css_index_search: k=%d outside [1, %d]", k, CSS_MAX_K);
-    std::shared_lock<std::shared_mutex> lk(ix->mu);
-    std::lock_guard<std::mutex> wl(ix->ws_mu);
-    DeviceGuard g(ix->device);
-    int rc;
-    if ((rc = ix->q_raw.grow((size_t)nq * ix->dim)) != CSS_OK) return rc;
-    float* d_out;
-    int64_t* i_out;
-    if ((rc = reserve_out(ix, (size_t)nq * k, &d_out, &i_out)) != CSS_OK) return rc;
-    const size_t q_bytes = (size_t)nq * ix->dim * 4, out_bytes = (size_t)nq * k * 12;
-    const bool staged = q_bytes <= css_index::kHostStage && out_bytes <= css_index::kHostStage;
-    if (staged && ix->h_stage == nullptr)
-        CSS_HIP_TRY(hipHostMalloc((void**)&ix->h_stage, 2 * css_index::kHostStage, hipHostMallocDefault));
-    Rows rows = rows_of(ix);
-    if ((rc = upload_allow_bits(ix, allow_bits_host, &rows)) != CSS_OK) return rc;
-    if (staged) {
-        memcpy(ix->h_stage, q_host, q_bytes);
-        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, ix->h_stage, q_bytes, hipMemcpyHostToDevice, ix->stream));
-    } else {
-        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, q_host, q_bytes, hipMemcpyHostToDevice, ix->stream));
-    }
-    if ((rc = search_any_k(ix, rows, ix->q_raw.p, nq, k, normalize_q, d_out, i_out, ix->stream)) != CSS_OK) return rc;
-    if (staged) {   // one copy into pinned memory, one wait
-        char* back = ix->h_stage + css_index::kHostStage;
-        CSS_HIP_TRY(hipMemcpyAsync(back, i_out, out_bytes, hipMemcpyDeviceToHost, ix->stream));
-        CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
-        memcpy(I_host, back, (size_t)nq * k * 8);
-        memcpy(D_host, back + (size_t)nq * k * 8, (size_t)nq * k * 4);
-        return CSS_OK;
-    }
-    return fetch_out(ix, (size_t)nq * k, d_out, i_out, D_host, I_host);
+    HostCall hc(ix);
+    int rc = hc.upload(allow_bits_host, ix->q_raw, q_host, (size_t)nq * ix->dim, (size_t)nq * k);
+    if (rc == CSS_OK) rc = search_any_k(ix, hc.rows, ix->q_raw.p, nq, k, normalize_q, hc.d_out, hc.i_out, ix->stream);
+    return hc.finish(rc, D_host, I_host);
 }
 
 int css_index_search(css_index* ix, const float* q_host, int64_t nq, int k, int normalize_q, float* D_host,
@@ -3532,7 +3593,7 @@ namespace {
 // n ints from the device, through the pinned staging where it is there and large enough; waits for the stream
 int read_ints(css_index* ix, const int* dev, size_t n, int* host) {
     const size_t bytes = n * sizeof(int);
-    if (ix->h_stage != nullptr && bytes <= css_index::kHostStage) {
+    if (ix->h_stage != nullptr && css_index::fits_host_stage(bytes)) {
         char* back = ix->h_stage + css_index::kHostStage;
         CSS_HIP_TRY(hipMemcpyAsync(back, dev, bytes, hipMemcpyDeviceToHost, ix->stream));
         CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
@@ -3548,7 +3609,7 @@ int launch_collapse(css_index* ix, const Rows& rows, int64_t q0, int64_t nqp, in
                     int32_t* Lg, hipStream_t st) {
     hipLaunchKernelGGL(k_collapse_groups, dim3((unsigned)((nqp + 3) / 4)), dim3(256), 0, st, (const float*)ix->grp_d.p,
                        (const int64_t*)ix->grp_i.p, rows.labels, rows.id_base, q0, nqp, kk, k,
-                       ix->metric == CSS_METRIC_IP ? -FLT_MAX : FLT_MAX, Dg, Ig, Lg, ix->grp_state.p);
+                       pad_score(ix), Dg, Ig, Lg, ix->grp_state.p);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
@@ -3606,9 +3667,7 @@ int search_grouped_passes(css_index* ix, const Rows& rows, const float* q_dev, i
         }
         float* Dq = Dg + (size_t)q * k;
         int64_t* Iq = Ig + (size_t)q * k;
-        if (ix->metric == CSS_METRIC_IP) hipLaunchKernelGGL(k_sort_rows<CSS_METRIC_IP>, dim3(1), dim3(1024), 0, st, Dq, Iq, k);
-        else hipLaunchKernelGGL(k_sort_rows<CSS_METRIC_L2>, dim3(1), dim3(1024), 0, st, Dq, Iq, k);
-        CSS_LAUNCH_CHECK();
+        if ((rc = launch_sort_rows(ix, Dq, Iq, 1, k, st)) != CSS_OK) return rc;
         hipLaunchKernelGGL(k_gather_labels, dim3(1), dim3(CSS_KERNEL_MAX_K), 0, st, (const int64_t*)Iq, rows.labels, rows.id_base,
                            (int64_t)k, Lg + (size_t)q * k);
         CSS_LAUNCH_CHECK();
@@ -3624,54 +3683,19 @@ int css_index_search_grouped(css_index* ix, const float* q_host, int64_t nq, int
     CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "css_index_search_grouped: k=%d outside [1, %d]", k, CSS_KERNEL_MAX_K);
     if (nq == 0) return CSS_OK;
     CSS_REQUIRE(q_host && D_host && I_host, "css_index_search_grouped: NULL buffer");
-    std::shared_lock<std::shared_mutex> lk(ix->mu);
-    std::lock_guard<std::mutex> wl(ix->ws_mu);
-    DeviceGuard g(ix->device);
-    int rc;
+    HostCall hc(ix);
     const size_t n = (size_t)nq * k;
-    if ((rc = ix->q_raw.grow((size_t)nq * ix->dim)) != CSS_OK) return rc;
-    if ((rc = ix->grp_l.grow(n)) != CSS_OK) return rc;
-    float* d_out;
-    int64_t* i_out;
-    if ((rc = reserve_out(ix, n, &d_out, &i_out)) != CSS_OK) return rc;
-    const size_t q_bytes = (size_t)nq * ix->dim * 4, out_bytes = n * 16;
-    const bool staged = q_bytes <= css_index::kHostStage && out_bytes <= css_index::kHostStage;
-    if (staged && ix->h_stage == nullptr)
-        CSS_HIP_TRY(hipHostMalloc((void**)&ix->h_stage, 2 * css_index::kHostStage, hipHostMallocDefault));
-    Rows rows = rows_of(ix);
-    if ((rc = upload_allow_bits(ix, allow_bits_host, &rows)) != CSS_OK) return rc;
-    if (staged) {
-        memcpy(ix->h_stage, q_host, q_bytes);
-        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, ix->h_stage, q_bytes, hipMemcpyHostToDevice, ix->stream));
-    } else {
-        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, q_host, q_bytes, hipMemcpyHostToDevice, ix->stream));
-    }
+    int rc = hc.upload(allow_bits_host, ix->q_raw, q_host, (size_t)nq * ix->dim, n, &ix->grp_l);
     // no labels (or no rows): every row is a group of its own, and the answer is the masked search's, G = -1
-    const bool labelled = rows.labels != nullptr && rows.n > 0;
-    if (labelled) {
-        rc = search_grouped_passes(ix, rows, ix->q_raw.p, nq, k, normalize_q, d_out, i_out, ix->grp_l.p);
-    } else {
-        rc = search_any_k(ix, rows, ix->q_raw.p, nq, k, normalize_q, d_out, i_out, ix->stream);
+    const bool labelled = hc.rows.labels != nullptr && hc.rows.n > 0;
+    if (rc == CSS_OK && labelled) {
+        rc = search_grouped_passes(ix, hc.rows, ix->q_raw.p, nq, k, normalize_q, hc.d_out, hc.i_out, hc.g_out);
+    } else if (rc == CSS_OK) {
+        rc = search_any_k(ix, hc.rows, ix->q_raw.p, nq, k, normalize_q, hc.d_out, hc.i_out, ix->stream);
         ix->last_group_passes = 1;
+        if (rc == CSS_OK && G_host) std::fill(G_host, G_host + n, (int32_t)-1);
     }
-    if (rc != CSS_OK) {
-        (void)hipStreamSynchronize(ix->stream);   // (the copies above read the caller's memory)
-        return rc;
-    }
-    if (G_host && !labelled) std::fill(G_host, G_host + n, (int32_t)-1);
-    const bool want_g = G_host && labelled;
-    if (staged) {   // one wait: [ids | scores] and the labels into pinned memory
-        char* back = ix->h_stage + css_index::kHostStage;
-        CSS_HIP_TRY(hipMemcpyAsync(back, i_out, n * 12, hipMemcpyDeviceToHost, ix->stream));
-        if (want_g) CSS_HIP_TRY(hipMemcpyAsync(back + n * 12, ix->grp_l.p, n * 4, hipMemcpyDeviceToHost, ix->stream));
-        CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
-        memcpy(I_host, back, n * 8);
-        memcpy(D_host, back + n * 8, n * 4);
-        if (want_g) memcpy(G_host, back + n * 12, n * 4);
-        return CSS_OK;
-    }
-    if (want_g) CSS_HIP_TRY(hipMemcpyAsync(G_host, ix->grp_l.p, n * 4, hipMemcpyDeviceToHost, ix->stream));
-    return fetch_out(ix, n, d_out, i_out, D_host, I_host);
+    return hc.finish(rc, D_host, I_host, labelled ? G_host : nullptr);
 }
 
 int css_index_last_group_passes(css_index* ix, int64_t* n) {
@@ -3710,11 +3734,11 @@ int search_diverse_enqueue(css_index* ix, const Rows& rows, const float* q_dev, 
     if (ix->metric == CSS_METRIC_IP)
         hipLaunchKernelGGL(k_mmr_select<CSS_METRIC_IP>, dim3((unsigned)nq), dim3(256), 0, st, (const float*)ix->div_d.p,
                            (const int64_t*)ix->div_i.p, rows.xb, rows.n, rows.id_base, ix->dim, ix->dpad, fetch, k, lam,
-                           -FLT_MAX, D_dev, I_dev);
+                           pad_score(ix), D_dev, I_dev);
     else
         hipLaunchKernelGGL(k_mmr_select<CSS_METRIC_L2>, dim3((unsigned)nq), dim3(256), 0, st, (const float*)ix->div_d.p,
                            (const int64_t*)ix->div_i.p, rows.xb, rows.n, rows.id_base, ix->dim, ix->dpad, fetch, k, lam,
-                           FLT_MAX, D_dev, I_dev);
+                           pad_score(ix), D_dev, I_dev);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
@@ -3728,10 +3752,8 @@ int css_index_search_diverse_dev(css_index* ix, const float* q_dev, int64_t nq, 
     if ((rc = check_diverse_args("css_index_search_diverse_dev", k, &fetch, lam)) != CSS_OK) return rc;
     if (nq == 0) return CSS_OK;
     CSS_REQUIRE(q_dev && D_dev && I_dev, "css_index_search_diverse_dev: NULL buffer");
-    std::shared_lock<std::shared_mutex> lk(ix->mu);
-    std::lock_guard<std::mutex> wl(ix->ws_mu);
-    DeviceGuard g(ix->device);
-    return search_diverse_enqueue(ix, rows_of(ix, allow_bits_dev), q_dev, nq, k, fetch, lam, normalize_q, D_dev, I_dev,
+    CallScope cs(ix, allow_bits_dev);
+    return search_diverse_enqueue(ix, cs.rows, q_dev, nq, k, fetch, lam, normalize_q, D_dev, I_dev,
                                   (hipStream_t)stream);
 }
 
@@ -3743,43 +3765,12 @@ int css_index_search_diverse(css_index* ix, const float* q_host, int64_t nq, int
     if ((rc = check_diverse_args("css_index_search_diverse", k, &fetch, lam)) != CSS_OK) return rc;
     if (nq == 0) return CSS_OK;
     CSS_REQUIRE(q_host && D_host && I_host, "css_index_search_diverse: NULL buffer");
-    std::shared_lock<std::shared_mutex> lk(ix->mu);
-    std::lock_guard<std::mutex> wl(ix->ws_mu);
-    DeviceGuard g(ix->device);
-    const size_t n = (size_t)nq * k;
-    if ((rc = ix->q_raw.grow((size_t)nq * ix->dim)) != CSS_OK) return rc;
-    float* d_out;
-    int64_t* i_out;
-    if ((rc = reserve_out(ix, n, &d_out, &i_out)) != CSS_OK) return rc;
-    const size_t q_bytes = (size_t)nq * ix->dim * 4, out_bytes = n * 12;
-    const bool staged = q_bytes <= css_index::kHostStage && out_bytes <= css_index::kHostStage;
-    if (staged && ix->h_stage == nullptr)
-        CSS_HIP_TRY(hipHostMalloc((void**)&ix->h_stage, 2 * css_index::kHostStage, hipHostMallocDefault));
-    Rows rows = rows_of(ix);
-    if ((rc = upload_allow_bits(ix, allow_bits_host, &rows)) != CSS_OK) return rc;
-    if (staged) {
-        memcpy(ix->h_stage, q_host, q_bytes);
-        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, ix->h_stage, q_bytes, hipMemcpyHostToDevice, ix->stream));
-    } else {
-        CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, q_host, q_bytes, hipMemcpyHostToDevice, ix->stream));
-    }
-    rc = search_diverse_enqueue(ix, rows, ix->q_raw.p, nq, k, fetch, lam, normalize_q, d_out, i_out, ix->stream);
-    if (rc != CSS_OK) {
-        (void)hipStreamSynchronize(ix->stream);   // (the copies above read the caller's memory)
-        return rc;
-    }
-    if (staged) {   // one copy into pinned memory, one wait
-        char* back = ix->h_stage + css_index::kHostStage;
-        CSS_HIP_TRY(hipMemcpyAsync(back, i_out, out_bytes, hipMemcpyDeviceToHost, ix->stream));
-        CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
-        memcpy(I_host, back, n * 8);
-        memcpy(D_host, back + n * 8, n * 4);
-        return CSS_OK;
-    }
-    return fetch_out(ix, n, d_out, i_out, D_host, I_host);
+    HostCall hc(ix);
+    rc = hc.upload(allow_bits_host, ix->q_raw, q_host, (size_t)nq * ix->dim, (size_t)nq * k);
+    if (rc == CSS_OK)
+        rc = search_diverse_enqueue(ix, hc.rows, ix->q_raw.p, nq, k, fetch, lam, normalize_q, hc.d_out, hc.i_out, ix->stream);
+    return hc.finish(rc, D_host, I_host);
 }
-
-
 
 namespace {
 // The anchors' rows gathered as queries, the ordinary search (search_any_k: every mode, shadow policy, k and chunking
@@ -3803,8 +3794,7 @@ int search_rows_enqueue(css_index* ix, const Rows& rows, const int64_t* ids_dev,
     CSS_LAUNCH_CHECK();
     if ((rc = search_any_k(ix, rows, ix->rowq.p, nq, kk, 0, ix->rowq_d.p, ix->rowq_i.p, st)) != CSS_OK) return rc;
     hipLaunchKernelGGL(k_drop_self, grid, dim3(256), 0, st, (const float*)ix->rowq_d.p, (const int64_t*)ix->rowq_i.p, ids_dev,
-                       (const int*)ix->rowq_flag.p, nq, kk, k, exclude_self ? 1 : 0,
-                       ix->metric == CSS_METRIC_IP ? -FLT_MAX : FLT_MAX, D_dev, I_dev);
+                       (const int*)ix->rowq_flag.p, nq, kk, k, exclude_self ? 1 : 0, pad_score(ix), D_dev, I_dev);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
@@ -3825,10 +3815,8 @@ int css_index_search_rows_dev(css_index* ix, const int64_t* ids_dev, int64_t nq,
     if ((rc = check_search_rows_k(k, exclude_self)) != CSS_OK) return rc;
     if (nq == 0) return CSS_OK;
     CSS_REQUIRE(ids_dev && D_dev && I_dev, "css_index_search_rows_dev: NULL buffer");
-    std::shared_lock<std::shared_mutex> lk(ix->mu);
-    std::lock_guard<std::mutex> wl(ix->ws_mu);
-    DeviceGuard g(ix->device);
-    return search_rows_enqueue(ix, rows_of(ix, allow_bits_dev), ids_dev, nq, k, exclude_self, D_dev, I_dev, (hipStream_t)stream);
+    CallScope cs(ix, allow_bits_dev);
+    return search_rows_enqueue(ix, cs.rows, ids_dev, nq, k, exclude_self, D_dev, I_dev, (hipStream_t)stream);
 }
 
 int css_index_search_rows(css_index* ix, const int64_t* ids_host, int64_t nq, int k, int exclude_self,
@@ -3839,26 +3827,15 @@ int css_index_search_rows(css_index* ix, const int64_t* ids_host, int64_t nq, in
     if ((rc = check_search_rows_k(k, exclude_self)) != CSS_OK) return rc;
     if (nq == 0) return CSS_OK;
     CSS_REQUIRE(ids_host && D_host && I_host, "css_index_search_rows: NULL buffer");
-    std::shared_lock<std::shared_mutex> lk(ix->mu);
-    std::lock_guard<std::mutex> wl(ix->ws_mu);
-    Rows rows = rows_of(ix);
+    HostCall hc(ix);
+    const Rows& rows = hc.rows;   // (the host id range check comes before anything is enqueued)
     for (int64_t j = 0; j < nq; ++j)
         CSS_REQUIRE(ids_host[j] >= rows.id_base && ids_host[j] - rows.id_base < rows.n,
                     "css_index_search_rows: id %lld (query %lld) outside [%lld, %lld)", (long long)ids_host[j], (long long)j,
                     (long long)rows.id_base, (long long)(rows.id_base + rows.n));
-    DeviceGuard g(ix->device);
-    if ((rc = ix->rowq_ids.grow((size_t)nq)) != CSS_OK) return rc;
-    float* d_out;
-    int64_t* i_out;
-    if ((rc = reserve_out(ix, (size_t)nq * k, &d_out, &i_out)) != CSS_OK) return rc;
-    if ((rc = upload_allow_bits(ix, allow_bits_host, &rows)) != CSS_OK) return rc;
-    CSS_HIP_TRY(hipMemcpyAsync(ix->rowq_ids.p, ids_host, (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream));
-    rc = search_rows_enqueue(ix, rows, ix->rowq_ids.p, nq, k, exclude_self, d_out, i_out, ix->stream);
-    if (rc != CSS_OK) {
-        (void)hipStreamSynchronize(ix->stream);   // (the copies above read the caller's memory)
-        return rc;
-    }
-    return fetch_out(ix, (size_t)nq * k, d_out, i_out, D_host, I_host);
+    rc = hc.upload(allow_bits_host, ix->rowq_ids, ids_host, (size_t)nq, (size_t)nq * k);
+    if (rc == CSS_OK) rc = search_rows_enqueue(ix, rows, ix->rowq_ids.p, nq, k, exclude_self, hc.d_out, hc.i_out, ix->stream);
+    return hc.finish(rc, D_host, I_host);
 }
 
 int css_merge_topk_dev(const float* Dp, const int64_t* Ip, int nparts, int64_t nq, int k, int metric, float* D,
@@ -3887,11 +3864,19 @@ struct css_range_result {
 };
 
 namespace {
-// Queries already on the device (ix->q_raw.p).  Caller holds ws_mu and a shared lock on mu; everything runs on the
-// index's own stream and has finished when this returns.
-int range_search_locked(css_index* ix, const Rows& rows, int64_t nq, float radius, int normalize_q, css_range_result* res) {
+// nq > 0 queries over hc.rows.n > 0 rows, inside the caller's host frame: the turn at the workspaces first, then the
+// frame's upload of bitmap and queries (into q_raw; no result rows: `res` is filled here).  Everything runs on the
+// index's own stream and has finished when this returns CSS_OK.
+int range_search_locked(css_index* ix, HostCall& hc, const float* q_host, const uint32_t* allow_bits_host, int64_t nq,
+                        float radius, int normalize_q, css_range_result* res) {
     hipStream_t st = ix->stream;
     int rc;
+    CSS_REQUIRE(hc.rows.n < 0xFFFFFFFFll, "css_index_range_search: %lld rows exceed the 32-bit row numbers of the hit pool",
+                (long long)hc.rows.n);
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    if ((rc = hc.upload(allow_bits_host, ix->q_raw, q_host, (size_t)nq * ix->dim)) != CSS_OK) return rc;
+    const Rows& rows = hc.rows;
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
     if ((rc = ix->qpad.grow((size_t)(nq + 256) * ix->dpad)) != CSS_OK) return rc;
     if ((rc = ix->qnorm2.grow((size_t)nq + 256)) != CSS_OK) return rc;
@@ -3989,24 +3974,10 @@ int css_index_range_search(css_index* ix, const float* q_host, int64_t nq, float
         return CSS_ERR_OOM;
     }
     int rc = CSS_OK;
-    {
-        std::shared_lock<std::shared_mutex> lk(ix->mu);
-        std::lock_guard<std::mutex> wl(ix->ws_mu);
-        Rows rows = rows_of(ix);
-        if (nq > 0 && rows.n > 0) {
-            DeviceGuard g(ix->device);
-            rc = [&]() -> int {
-                CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "css_index_range_search: %lld rows exceed the 32-bit row numbers of the hit pool",
-                            (long long)rows.n);
-                int r;
-                WsTurn turn(ix, ix->stream);
-                if (turn.rc != CSS_OK) return turn.rc;
-                if ((r = ix->q_raw.grow((size_t)nq * ix->dim)) != CSS_OK) return r;
-                if ((r = upload_allow_bits(ix, allow_bits_host, &rows)) != CSS_OK) return r;
-                CSS_HIP_TRY(hipMemcpyAsync(ix->q_raw.p, q_host, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream));
-                return range_search_locked(ix, rows, nq, radius, normalize_q, res);
-            }();
-        }
+    if (nq > 0) {   // (an empty index or no query touches no device)
+        HostCall hc(ix, nullptr, false);
+        if (hc.rows.n > 0)
+            rc = hc.wait_if_failed(range_search_locked(ix, hc, q_host, allow_bits_host, nq, radius, normalize_q, res));
     }
     if (rc != CSS_OK) {
         delete res;

@@ -225,12 +225,35 @@ class IndexFlat:
             raise RuntimeError("index has been freed")
         return self._h
 
+    def _read_i64(self, fn) -> int:
+        n = ctypes.c_int64(0)
+        nat.check(fn(self._handle(), ctypes.byref(n)))
+        return int(n.value)
+
+    def _allow_bits(self, allow):
+        """``allow`` packed against ``ntotal``: ``(bitmap, its address)``, ``(None, None)`` without a mask.  The
+        address is good while the bitmap is referenced."""
+        if allow is None:
+            return None, None
+        bits = pack_allow_bits(allow, self.ntotal)
+        return bits, bits.ctypes.data
+
+    def _topk(self, fn, x, k: int, args, allow, groups: bool = False):
+        """The frame of the top-k searches: ``fn(handle, x, nq, k, *args, allow bits, D, I[, G])`` into fresh
+        ``[nq, k]`` arrays -- scores, ids and, with ``groups``, int32 labels; no query, no call."""
+        nq = x.shape[0]
+        out = (np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int64))
+        if groups:
+            out += (np.empty((nq, k), dtype=np.int32),)
+        bits, bits_ptr = self._allow_bits(allow)
+        if nq:
+            nat.check(fn(self._handle(), x.ctypes.data, nq, k, *args, bits_ptr, *(o.ctypes.data for o in out)))
+        return out
+
     # -- faiss surface ----------------------------------------------------
     @property
     def ntotal(self) -> int:
-        n = ctypes.c_int64(0)
-        nat.check(nat.lib().css_index_ntotal(self._handle(), ctypes.byref(n)))
-        return int(n.value)
+        return self._read_i64(nat.lib().css_index_ntotal)
 
     def reset(self) -> None:
         nat.check(nat.lib().css_index_reset(self._handle()))
@@ -287,17 +310,7 @@ class IndexFlat:
         k = int(k)
         if k < 1 or k > nat.MAX_K:
             raise ValueError(f"k={k} outside [1, {nat.MAX_K}]")
-        nq = a.shape[0]
-        D = np.empty((nq, k), dtype=np.float32)
-        I = np.empty((nq, k), dtype=np.int64)
-        bits = None
-        if allow is not None:
-            bits = pack_allow_bits(allow, self.ntotal)
-        if nq:
-            nat.check(nat.lib().css_index_search_masked(self._handle(), a.ctypes.data, nq, k, 1 if normalize else 0,
-                                                        bits.ctypes.data if bits is not None else None,
-                                                        D.ctypes.data, I.ctypes.data))
-        return D, I
+        return self._topk(nat.lib().css_index_search_masked, a, k, (1 if normalize else 0,), allow)
 
     def range_search(self, q, thresh: float, normalize: bool = False, allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``faiss.IndexFlat.range_search``: ``(lims[nq+1] int64, D[total] float32, I[total] int64)``; query ``j``'s
@@ -308,13 +321,10 @@ class IndexFlat:
         a = _as_f32_2d(q, self.d, "range_search")
         nq = a.shape[0]
         h = self._handle()
-        bits = None
-        if allow is not None:
-            bits = pack_allow_bits(allow, self.ntotal)
+        bits, bits_ptr = self._allow_bits(allow)
         res = ctypes.c_void_p()
         nat.check(nat.lib().css_index_range_search(h, a.ctypes.data if nq else None, nq, float(thresh),
-                                                   1 if normalize else 0,
-                                                   bits.ctypes.data if bits is not None else None, ctypes.byref(res)))
+                                                   1 if normalize else 0, bits_ptr, ctypes.byref(res)))
         try:
             lims = np.zeros(nq + 1, dtype=np.int64)
             nat.check(nat.lib().css_range_result_lims(res, lims.ctypes.data))
@@ -363,25 +373,12 @@ class IndexFlat:
         k = int(k)
         if k < 1 or k > MAX_GROUP_K:
             raise ValueError(f"k={k} outside [1, {MAX_GROUP_K}]")
-        nq = a.shape[0]
-        D = np.empty((nq, k), dtype=np.float32)
-        I = np.empty((nq, k), dtype=np.int64)
-        G = np.empty((nq, k), dtype=np.int32)
-        bits = None
-        if allow is not None:
-            bits = pack_allow_bits(allow, self.ntotal)
-        if nq:
-            nat.check(nat.lib().css_index_search_grouped(self._handle(), a.ctypes.data, nq, k, 1 if normalize else 0,
-                                                         bits.ctypes.data if bits is not None else None,
-                                                         D.ctypes.data, I.ctypes.data, G.ctypes.data))
-        return D, I, G
+        return self._topk(nat.lib().css_index_search_grouped, a, k, (1 if normalize else 0,), allow, groups=True)
 
     def last_group_passes(self) -> int:
         """Diagnostics: search passes of the last ``search_grouped`` call (1 when the first pass sufficed for every
         query)."""
-        n = ctypes.c_int64(0)
-        nat.check(nat.lib().css_index_last_group_passes(self._handle(), ctypes.byref(n)))
-        return int(n.value)
+        return self._read_i64(nat.lib().css_index_last_group_passes)
 
     # -- diversified search (MMR) --------------------------------------------
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False,
@@ -394,18 +391,8 @@ class IndexFlat:
         ``fetch = 0`` chooses 32 (``4k <= 32``) or 128.  ``allow`` restricts the pool as in ``search``."""
         a = _as_f32_2d(q, self.d, "search_diverse")
         k, fetch, lam = diverse_args(k, fetch, lam)
-        nq = a.shape[0]
-        D = np.empty((nq, k), dtype=np.float32)
-        I = np.empty((nq, k), dtype=np.int64)
-        h = self._handle()
-        bits = None
-        if allow is not None:
-            bits = pack_allow_bits(allow, self.ntotal)
-        if nq:
-            nat.check(nat.lib().css_index_search_diverse(h, a.ctypes.data, nq, k, fetch, lam, 1 if normalize else 0,
-                                                         bits.ctypes.data if bits is not None else None,
-                                                         D.ctypes.data, I.ctypes.data))
-        return D, I
+        self._handle()   # (a freed index raises even without queries)
+        return self._topk(nat.lib().css_index_search_diverse, a, k, (fetch, lam, 1 if normalize else 0), allow)
 
     def search_diverse_dev(self, q_ptr: int, nq: int, k: int, D_ptr: int, I_ptr: int, stream: int = 0, lam: float = 0.5,
                            fetch: int = 0, normalize: bool = False, allow_bits_ptr: int = 0) -> None:
@@ -441,17 +428,7 @@ class IndexFlat:
         kmax = nat.MAX_K - 1 if exclude_self else nat.MAX_K
         if k < 1 or k > kmax:
             raise ValueError(f"k={k} outside [1, {kmax}]")
-        nq = a.shape[0]
-        D = np.empty((nq, k), dtype=np.float32)
-        I = np.empty((nq, k), dtype=np.int64)
-        bits = None
-        if allow is not None:
-            bits = pack_allow_bits(allow, self.ntotal)
-        if nq:
-            nat.check(nat.lib().css_index_search_rows(self._handle(), a.ctypes.data, nq, k, 1 if exclude_self else 0,
-                                                      bits.ctypes.data if bits is not None else None,
-                                                      D.ctypes.data, I.ctypes.data))
-        return D, I
+        return self._topk(nat.lib().css_index_search_rows, a, k, (1 if exclude_self else 0,), allow)
 
     def search_by_ids_dev(self, ids_ptr: int, nq: int, k: int, D_ptr: int, I_ptr: int, stream: int = 0,
                           exclude_self: bool = True, allow_bits_ptr: int = 0) -> None:
@@ -476,16 +453,12 @@ class IndexFlat:
 
     def last_flagged(self) -> int:
         """Diagnostics: queries of the last candidate-path search whose candidate band or buffer overflowed."""
-        n = ctypes.c_int64(0)
-        nat.check(nat.lib().css_index_last_flagged(self._handle(), ctypes.byref(n)))
-        return int(n.value)
+        return self._read_i64(nat.lib().css_index_last_flagged)
 
     def last_swept(self) -> int:
         """Diagnostics: flagged queries of the last candidate-path search that the second coarse pass could not settle
         and that the exact fp32 sweep re-ran."""
-        n = ctypes.c_int64(0)
-        nat.check(nat.lib().css_index_last_swept(self._handle(), ctypes.byref(n)))
-        return int(n.value)
+        return self._read_i64(nat.lib().css_index_last_swept)
 
     def shadow_info(self) -> dict:
         """Diagnostics: which reduced-precision copies of the rows the index holds (``{"bf16": bool, "int8": bool}``)."""

@@ -141,6 +141,60 @@ class ShardedFlatIndex:
         seg = (torch.bucketize(I, l0, right=True) - 1).clamp_(min=0)
         return torch.where(I >= 0, I - l0[seg] + g0[seg], I)
 
+    def _to_global_np(self, I: np.ndarray) -> np.ndarray:
+        """``_to_global`` for a host array of local row numbers; ``-1`` pads stay ``-1``."""
+        if len(self.segments) <= 1 or I.size == 0:
+            return I
+        l0 = np.array([s[0] for s in self.segments], dtype=np.int64)
+        g0 = np.array([s[1] for s in self.segments], dtype=np.int64)
+        seg = np.clip(np.searchsorted(l0, I, side="right") - 1, 0, None)
+        return np.where(I >= 0, I - l0[seg] + g0[seg], I)
+
+    # -- pieces of the host-side searches ------------------------------------
+    def _queries(self, q) -> np.ndarray:
+        return np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.d)
+
+    def _single(self) -> bool:
+        """One rank and no forced exchange: the local answer is the answer."""
+        return self.world == 1 and not self.exchange_when_single
+
+    def _exchange_device(self) -> str:
+        """Where a host array goes for a collective: gloo moves host memory, RCCL this rank's device."""
+        return "cpu" if self.dist.get_backend(self.group) == "gloo" else f"cuda:{self.device_index or 0}"
+
+    def _all_gather_host(self, send: np.ndarray) -> np.ndarray:
+        """ONE all-gather of a flat host record (the same size on every rank): ``[world, record]``."""
+        import torch
+
+        t = torch.from_numpy(send).to(self._exchange_device())
+        recv = torch.empty(self.world * t.shape[0], dtype=t.dtype, device=t.device)
+        self.dist.all_gather_into_tensor(recv, t, group=self.group)
+        return recv.cpu().numpy().reshape(self.world, t.shape[0])
+
+    def _sum_over_ranks(self, a: np.ndarray) -> np.ndarray:
+        """ONE sum all-reduce of a host array (none with one rank, or for nothing)."""
+        import torch
+
+        if self.world == 1 or a.size == 0:
+            return a
+        t = torch.from_numpy(a).to(self._exchange_device())
+        self.dist.all_reduce(t, group=self.group)
+        return t.cpu().numpy()
+
+    def _owned_rows(self, global_ids: np.ndarray) -> np.ndarray:
+        """The stored rows of ``global_ids`` (any shape; ``-1`` = none) on every rank, ``[..., d]``: the shard that
+        owns an id supplies its row through the segment table, every other shard zeros, then ``_sum_over_ranks``
+        (exact: one non-zero contribution per row)."""
+        rows = np.zeros(global_ids.shape + (self.d,), dtype=np.float32)
+        for l0, g0, m in self.segments:
+            for at in map(tuple, np.argwhere((global_ids >= g0) & (global_ids < g0 + m))):
+                rows[at] = self.local.reconstruct_n(l0 + int(global_ids[at]) - g0, 1)[0]
+        return self._sum_over_ranks(rows)
+
+    def _best_first(self, scores: np.ndarray, ids: np.ndarray, lead: np.ndarray) -> np.ndarray:
+        """Sort order by ``lead`` ascending, then best score first (IP descending, L2 ascending), then ascending id."""
+        return np.lexsort((ids, -scores if self.metric == 0 else scores, lead))
+
     # -- searching ---------------------------------------------------------
     def _merge_packed_hip(self, recv, nq: int, k: int, record: int):
         import torch
@@ -220,15 +274,12 @@ class ShardedFlatIndex:
             if bits is not None:
                 bits.record_stream(torch.cuda.current_stream())
         else:  # CPU doubles (tests)
-            if loc is not None:
-                d_np, i_np = self.local.search(q.numpy(), k, normalize=normalize, allow=loc)
-            else:
-                d_np, i_np = self.local.search(q.numpy(), k, normalize=normalize)
+            d_np, i_np = self.local.search(q.numpy(), k, normalize=normalize, allow=loc)
             D.copy_(torch.from_numpy(d_np))
             I.copy_(torch.from_numpy(i_np))
         if len(self.segments) > 1:
             I.copy_(self._to_global(I))
-        if self.world == 1 and not self.exchange_when_single:
+        if self._single():
             return D, I
         # THE exchange step of the path: one all-gather of nq*k*12 bytes per rank
         recv_flat = torch.empty(self.world * record, dtype=torch.uint8, device=q.device)
@@ -252,49 +303,29 @@ class ShardedFlatIndex:
     def search(self, q: np.ndarray, k: int, normalize: bool = False, allow=None):
         import torch
 
-        qt = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.d))
+        qt = torch.from_numpy(self._queries(q))
         if self.device_index is not None and torch.cuda.is_available():
             qt = qt.to(f"cuda:{self.device_index}")
         D, I = self.search_tensors(qt, k, normalize, allow=allow)
         return D.cpu().numpy(), I.cpu().numpy()
 
     # -- range search ------------------------------------------------------------------------------------------
-    def _to_global_np(self, I: np.ndarray) -> np.ndarray:
-        """``_to_global`` for a host array of local row numbers (no -1 entries)."""
-        if len(self.segments) <= 1 or I.size == 0:
-            return I
-        l0 = np.array([s[0] for s in self.segments], dtype=np.int64)
-        g0 = np.array([s[1] for s in self.segments], dtype=np.int64)
-        seg = np.clip(np.searchsorted(l0, I, side="right") - 1, 0, None)
-        return I - l0[seg] + g0[seg]
-
     def range_search(self, q, thresh: float, normalize: bool = False, allow=None):
         """``IndexFlat.range_search`` over the shards: ``(lims, D, I)`` with global ids on every rank, each query's hits
         best score first and equal scores by ascending id.  Every rank range-searches its shard (local allow-mask as in
         ``search_tensors``); the variable-length lists then take two collective steps -- one all-gather of the
         per-query counts, one of the payload (ids, scores) padded to the largest rank's size -- and every rank merges
         per query.  With one rank there is no exchange.  Results live on the host, as the local call returns them."""
-        import torch
-
-        qa = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.d)
+        qa = self._queries(q)
         nq = qa.shape[0]
-        loc = self._local_allow(allow)
-        if loc is not None:
-            lims, D, I = self.local.range_search(qa, thresh, normalize=normalize, allow=loc)
-        else:
-            lims, D, I = self.local.range_search(qa, thresh, normalize=normalize)
+        lims, D, I = self.local.range_search(qa, thresh, normalize=normalize, allow=self._local_allow(allow))
         lims = np.asarray(lims, dtype=np.int64)
         D = np.asarray(D, dtype=np.float32)
         I = self._to_global_np(np.asarray(I, dtype=np.int64))
-        if (self.world == 1 and not self.exchange_when_single) or nq == 0:   # (nq is the same on every rank)
+        if self._single() or nq == 0:   # (nq is the same on every rank)
             return lims, D, I
-        gloo = self.dist.get_backend(self.group) == "gloo"
-        dev = "cpu" if gloo else f"cuda:{self.device_index or 0}"
         # step 1: the per-query hit counts of every rank
-        counts = torch.from_numpy(np.diff(lims)).to(dev)
-        all_counts = torch.empty(self.world * nq, dtype=torch.int64, device=dev)
-        self.dist.all_gather_into_tensor(all_counts, counts, group=self.group)
-        all_counts = all_counts.cpu().numpy().reshape(self.world, nq)
+        all_counts = self._all_gather_host(np.diff(lims))
         totals = all_counts.sum(axis=1)
         most = int(totals.max())
         if most == 0:
@@ -304,9 +335,7 @@ class ShardedFlatIndex:
         send = np.zeros(record, dtype=np.uint8)
         send[:8 * I.shape[0]] = I.view(np.uint8)
         send[8 * most:8 * most + 4 * D.shape[0]] = D.view(np.uint8)
-        recv = torch.empty(self.world * record, dtype=torch.uint8, device=dev)
-        self.dist.all_gather_into_tensor(recv, torch.from_numpy(send).to(dev), group=self.group)
-        recv = recv.cpu().numpy().reshape(self.world, record)
+        recv = self._all_gather_host(send)
         ids, scores, qid = [], [], []
         for r in range(self.world):
             t = int(totals[r])
@@ -315,7 +344,7 @@ class ShardedFlatIndex:
             qid.append(np.repeat(np.arange(nq, dtype=np.int64), all_counts[r]))
         ids, scores, qid = np.concatenate(ids), np.concatenate(scores), np.concatenate(qid)
         # per-query merge: query, then best score first (IP descending, L2 ascending), then ascending id
-        order = np.lexsort((ids, -scores if self.metric == 0 else scores, qid))
+        order = self._best_first(scores, ids, qid)
         out_lims = np.zeros(nq + 1, dtype=np.int64)
         np.cumsum(all_counts.sum(axis=0), out=out_lims[1:])
         return out_lims, np.ascontiguousarray(scores[order]), np.ascontiguousarray(ids[order])
@@ -343,40 +372,28 @@ class ShardedFlatIndex:
         the host: sort by (score, id), then ``flat_index.collapse_groups``.  Exact: a group of the global top-k is
         among the top-k groups of the shard that holds its best row, because every group ranked above it on that
         shard also ranks above it globally.  With one rank there is no exchange."""
-        import torch
-
         from .flat_index import MAX_GROUP_K, collapse_groups
 
-        qa = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.d)
+        qa = self._queries(q)
         nq, k = qa.shape[0], int(k)
         if k < 1 or k > MAX_GROUP_K:
             raise ValueError(f"k={k} outside [1, {MAX_GROUP_K}]")
-        loc = self._local_allow(allow)
-        if loc is not None:
-            D, I, G = self.local.search_grouped(qa, k, normalize=normalize, allow=loc)
-        else:
-            D, I, G = self.local.search_grouped(qa, k, normalize=normalize)
+        D, I, G = self.local.search_grouped(qa, k, normalize=normalize, allow=self._local_allow(allow))
         D, G = np.ascontiguousarray(D, dtype=np.float32), np.ascontiguousarray(G, dtype=np.int32)
-        I = np.asarray(I, dtype=np.int64)
-        if len(self.segments) > 1:
-            I = np.where(I >= 0, self._to_global_np(np.maximum(I, 0)), -1)
-        I = np.ascontiguousarray(I)
-        if (self.world == 1 and not self.exchange_when_single) or nq == 0:
+        I = np.ascontiguousarray(self._to_global_np(np.asarray(I, dtype=np.int64)))
+        if self._single() or nq == 0:
             return D, I, G
         n = nq * k
         send = np.empty(16 * n, dtype=np.uint8)                      # [n int64 ids][n float32 scores][n int32 labels]
         send[:8 * n] = I.reshape(-1).view(np.uint8)
         send[8 * n:12 * n] = D.reshape(-1).view(np.uint8)
         send[12 * n:] = G.reshape(-1).view(np.uint8)
-        dev = "cpu" if self.dist.get_backend(self.group) == "gloo" else f"cuda:{self.device_index or 0}"
-        recv = torch.empty(self.world * 16 * n, dtype=torch.uint8, device=dev)
-        self.dist.all_gather_into_tensor(recv, torch.from_numpy(send).to(dev), group=self.group)
-        recv = recv.cpu().numpy().reshape(self.world, 16 * n)
+        recv = self._all_gather_host(send)
         Ig = np.concatenate([recv[r, :8 * n].view(np.int64).reshape(nq, k) for r in range(self.world)], axis=1)
         Dg = np.concatenate([recv[r, 8 * n:12 * n].view(np.float32).reshape(nq, k) for r in range(self.world)], axis=1)
         Gg = np.concatenate([recv[r, 12 * n:].view(np.int32).reshape(nq, k) for r in range(self.world)], axis=1)
         for j in range(nq):   # best first by (score, id), pads last
-            order = np.lexsort((Ig[j], -Dg[j] if self.metric == 0 else Dg[j], Ig[j] < 0))
+            order = self._best_first(Dg[j], Ig[j], Ig[j] < 0)
             Ig[j], Dg[j], Gg[j] = Ig[j][order], Dg[j][order], Gg[j][order]
         return collapse_groups(Dg, Ig, Gg, k, self.metric)
 
@@ -391,35 +408,19 @@ class ShardedFlatIndex:
         ``nq * fetch * d * 4`` bytes (393 KB per query at ``fetch = 128``, ``d = 768``), so the call is meant for few
         queries -- the interactive search, not a batch job.  With one rank (and no forced exchange) the whole call is
         the local index's ``search_diverse``, selection on the device included."""
-        import torch
-
         from .flat_index import diverse_args, mmr_select
 
-        qa = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.d)
+        qa = self._queries(q)
         k, fetch, lam = diverse_args(k, fetch, lam)
-        nq = qa.shape[0]
-        if self.world == 1 and not self.exchange_when_single:
-            loc = self._local_allow(allow)
-            kw = {"allow": loc} if loc is not None else {}
-            D, I = self.local.search_diverse(qa, k, lam=lam, fetch=fetch, normalize=normalize, **kw)
-            I = np.asarray(I, dtype=np.int64)
-            if len(self.segments) > 1:
-                I = np.where(I >= 0, self._to_global_np(np.maximum(I, 0)), -1)
+        if self._single():
+            D, I = self.local.search_diverse(qa, k, lam=lam, fetch=fetch, normalize=normalize,
+                                             allow=self._local_allow(allow))
+            I = self._to_global_np(np.asarray(I, dtype=np.int64))
             return np.ascontiguousarray(D, dtype=np.float32), np.ascontiguousarray(I)
-        if nq == 0:
+        if qa.shape[0] == 0:
             return np.empty((0, k), dtype=np.float32), np.empty((0, k), dtype=np.int64)
         S, I = self.search(qa, fetch, normalize=normalize, allow=allow)
-        rows = np.zeros((nq, fetch, self.d), dtype=np.float32)
-        for l0, g0, m in self.segments:
-            for j, c in np.argwhere((I >= g0) & (I < g0 + m)):
-                rows[j, c] = self.local.reconstruct_n(l0 + int(I[j, c]) - g0, 1)[0]
-        if self.world > 1:
-            t = torch.from_numpy(rows)
-            if self.dist.get_backend(self.group) != "gloo":
-                t = t.to(f"cuda:{self.device_index or 0}")
-            self.dist.all_reduce(t, group=self.group)
-            rows = t.cpu().numpy()
-        return mmr_select(S, I, rows, k, lam, self.metric)
+        return mmr_select(S, I, self._owned_rows(I), k, lam, self.metric)
 
     # -- related rows ----------------------------------------------------------------------------------------------
     def search_by_ids(self, ids, k: int, exclude_self: bool = True, allow=None):
@@ -429,8 +430,6 @@ class ShardedFlatIndex:
         Then the usual search runs for ``k + 1`` -- local masked search, one all-gather, merge -- and the anchor's
         global id is dropped after the merge (copies of the anchor on any shard stay).  An id outside
         ``[0, ntotal_global)`` raises ``ValueError`` on every rank, before any collective."""
-        import torch
-
         from .flat_index import MAX_K, drop_self, ids_as_int64
 
         a = ids_as_int64(ids)
@@ -441,20 +440,9 @@ class ShardedFlatIndex:
         bad = a[(a < 0) | (a >= self.ntotal_global)]
         if bad.size:
             raise ValueError(f"search_by_ids: id {int(bad[0])} outside [0, {self.ntotal_global})")
-        nq = a.shape[0]
-        if nq == 0:
+        if a.shape[0] == 0:
             return np.empty((0, k), dtype=np.float32), np.empty((0, k), dtype=np.int64)
-        rows = np.zeros((nq, self.d), dtype=np.float32)
-        for l0, g0, m in self.segments:
-            for j in np.flatnonzero((a >= g0) & (a < g0 + m)):
-                rows[j] = self.local.reconstruct_n(l0 + int(a[j]) - g0, 1)[0]
-        if self.world > 1:
-            t = torch.from_numpy(rows)
-            if self.dist.get_backend(self.group) != "gloo":
-                t = t.to(f"cuda:{self.device_index or 0}")
-            self.dist.all_reduce(t, group=self.group)
-            rows = t.cpu().numpy()
-        D, I = self.search(rows, k + 1 if exclude_self else k, normalize=False, allow=allow)
+        D, I = self.search(self._owned_rows(a), k + 1 if exclude_self else k, normalize=False, allow=allow)
         return drop_self(D, I, a) if exclude_self else (D, I)
 
     # -- rows back out (index files, compaction) ---------------------------------------------------------------
@@ -462,20 +450,12 @@ class ShardedFlatIndex:
         """Rows ``[row0, row0 + n)`` in GLOBAL numbering on every rank (collective).  Each row lives on exactly one
         shard: every rank fills in the rows it owns and ONE sum all-reduce of the zero-filled blocks completes them
         (save / backup / compaction paths only -- never on the search path)."""
-        import torch
-
         out = np.zeros((int(n), self.d), dtype=np.float32)
         for l0, g0, m in self.segments:
             lo, hi = max(g0, row0), min(g0 + m, row0 + n)
             if hi > lo:
                 out[lo - row0:hi - row0] = self.local.reconstruct_n(l0 + (lo - g0), hi - lo)
-        if self.world > 1 and n:
-            t = torch.from_numpy(out)
-            if self.dist.get_backend(self.group) != "gloo":
-                t = t.to(f"cuda:{self.device_index or 0}")
-            self.dist.all_reduce(t, group=self.group)
-            out = t.cpu().numpy()
-        return out
+        return self._sum_over_ranks(out)
 
     def add_file_rows(self, path: str, offset: int, n: int, normalize: bool = False, chunk_rows: int = 1 << 18) -> None:
         """``add_global`` of ``n`` fp32 rows stored row-major at byte ``offset`` of ``path`` (the payload of an index

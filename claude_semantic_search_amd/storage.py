@@ -350,40 +350,59 @@ class HybridStorage:
         self.logger.info(f"Added {len(with_emb)} chunks to storage")
 
     # --------------------------------------------------------------- search
+    def _search_frame(self, config: Optional[SearchConfig], query_embedding=None):
+        """Prologue of every search; the caller holds the lock.  ``None``: no index, or an empty one.  Otherwise
+        ``(cfg, ntotal, q)``, the query as a ``[1, d]`` float32 array (``None`` when the search has none)."""
+        if not self.faiss_index:
+            return None
+        ntotal = self.faiss_index.ntotal
+        if ntotal == 0:
+            return None
+        # accepts ndarray or a plain list (tests/test_integration.py:203-204 of the reference)
+        q = None if query_embedding is None else np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
+        return config or SearchConfig(), ntotal, q
+
+    def _allow_for(self, filters: Optional[Dict[str, Any]], ntotal: int, tombstones_always: bool) -> Optional[np.ndarray]:
+        """The allow mask of a search, ``None`` for every row.  Filters are masked only under ``filter_pushdown``.
+        Tombstones are masked under ``filter_pushdown`` too (``search``, ``search_range``: the host loop skips them
+        otherwise) or, with ``tombstones_always``, in both modes (``search_sessions``, ``search_diverse``: a deleted
+        chunk must not stand for its session or repel other picks)."""
+        pushdown = bool(self.config.filter_pushdown)
+        masked = filters if pushdown and filters else {}
+        tombstones = len(self.faiss_id_to_chunk_id) < ntotal
+        if masked or (tombstones and (pushdown or tombstones_always)):
+            return self._allow_mask(masked, ntotal)
+        return None
+
     def search(self, query_embedding, config: Optional[SearchConfig] = None,
                filters: Optional[Dict[str, Any]] = None) -> List[SearchResult]:
-        cfg = config or SearchConfig()
-        if not self.faiss_index:
-            return []
         with self._lock:
-            ntotal = self.faiss_index.ntotal
-            if ntotal == 0:
+            frame = self._search_frame(config, query_embedding)
+            if frame is None:
                 return []
+            cfg, ntotal, q = frame
             k = min(cfg.max_results, ntotal, fi.MAX_K)   # (fi.MAX_K = 2048: beyond 128 the index takes passes of 128)
             if k <= 0:
                 return []
-            # accepts ndarray or a plain list (tests/test_integration.py:203-204 of the reference)
-            q = np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
-            allow = None
-            if self.config.filter_pushdown and (filters or len(self.faiss_id_to_chunk_id) < ntotal):
-                allow = self._allow_mask(filters or {}, ntotal)
-                k = max(1, min(k, cfg.top_k, fi.MAX_K))
+            allow = self._allow_for(filters, ntotal, tombstones_always=False)
             if allow is not None:
-                sims, ids = self.faiss_index.search(q, k, normalize=self.config.normalize_embeddings, allow=allow)
-            else:
-                sims, ids = self.faiss_index.search(q, k, normalize=self.config.normalize_embeddings)
+                k = max(1, min(k, cfg.top_k, fi.MAX_K))
+            sims, ids = self.faiss_index.search(q, k, normalize=self.config.normalize_embeddings, allow=allow)
             return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
 
     _NO_SESSION = object()   # _results_in_rank_order: no session is left out
 
     def _results_in_rank_order(self, sims, ids, cfg: SearchConfig, filters: Optional[Dict[str, Any]],
-                               skip_session: Any = _NO_SESSION) -> List[SearchResult]:
+                               skip_session: Any = _NO_SESSION, unbounded: bool = False,
+                               limit: Optional[int] = None) -> List[SearchResult]:
         """The hits of one query, best first, through the reference's post-processing (``src/storage.py:438-492``):
         threshold, tombstone skip, SQLite row, filters, stop at ``top_k``.  ``skip_session``: chunks of that session
-        are left out as well (``search_related``)."""
+        are left out as well (``search_related``).  ``unbounded`` (``search_range``: the index applied the threshold):
+        no threshold here, and the stop is at ``limit`` results, or never."""
+        stop = limit if unbounded else cfg.top_k
         out: List[SearchResult] = []
         for score, fid in zip(sims, ids):
-            if score < cfg.similarity_threshold:
+            if not unbounded and score < cfg.similarity_threshold:
                 continue
             chunk_id = self.faiss_id_to_chunk_id.get(fid)
             if not chunk_id:  # tombstone: row deleted from SQLite, vector still in the index
@@ -396,7 +415,7 @@ class HybridStorage:
             if skip_session is not self._NO_SESSION and data["session_id"] == skip_session:
                 continue
             out.append(self._make_result(chunk_id, score, data, cfg))
-            if len(out) >= cfg.top_k:
+            if stop is not None and len(out) >= stop:
                 break
         return out
 
@@ -415,13 +434,11 @@ class HybridStorage:
         ``min(max_results, ntotal - 1, MAX_K - 1)`` rows are fetched and filtered in rank order; with it, filters,
         tombstones and the session rule form the allow mask and ``top_k`` rows are fetched.
         An unknown or deleted ``chunk_id`` raises ``KeyError``; an empty index and one holding only the anchor give ``[]``."""
-        cfg = config or SearchConfig()
-        if not self.faiss_index:
-            return []
         with self._lock:
-            ntotal = self.faiss_index.ntotal
-            if ntotal == 0:
+            frame = self._search_frame(config)
+            if frame is None:
                 return []
+            cfg, ntotal, _ = frame
             fid = self.chunk_id_to_faiss_id.get(chunk_id)
             data = self._get_chunk_data(chunk_id) if fid is not None and fid < ntotal else None
             if not data:
@@ -478,27 +495,18 @@ class HybridStorage:
         then missing even if another of its chunks matches.  Tombstones are masked out in both modes, so a deleted
         chunk never stands for its session.  An index object without ``search_grouped`` raises
         ``NotImplementedError``."""
-        cfg = config or SearchConfig()
-        if not self.faiss_index:
-            return []
-        if not hasattr(self.faiss_index, "search_grouped") or not hasattr(self.faiss_index, "set_groups"):
+        if self.faiss_index and not (hasattr(self.faiss_index, "search_grouped") and hasattr(self.faiss_index, "set_groups")):
             raise NotImplementedError(f"{type(self.faiss_index).__name__} has no grouped search (search_grouped / set_groups)")
         with self._lock:
-            ntotal = self.faiss_index.ntotal
-            if ntotal == 0 or cfg.top_k <= 0:
+            frame = self._search_frame(config, query_embedding)
+            if frame is None or frame[0].top_k <= 0:
                 return []
-            q = np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
-            pushdown = bool(self.config.filter_pushdown)
-            allow = None
-            if (pushdown and filters) or len(self.faiss_id_to_chunk_id) < ntotal:
-                allow = self._allow_mask((filters or {}) if pushdown else {}, ntotal)
-            k = cfg.top_k if (pushdown or not filters) else max(cfg.top_k, cfg.max_results)
+            cfg, ntotal, q = frame
+            allow = self._allow_for(filters, ntotal, tombstones_always=True)
+            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
             k = max(1, min(k, ntotal, fi.MAX_GROUP_K))
             self._sync_session_labels(ntotal)
-            if allow is not None:
-                sims, ids, _ = self.faiss_index.search_grouped(q, k, normalize=self.config.normalize_embeddings, allow=allow)
-            else:
-                sims, ids, _ = self.faiss_index.search_grouped(q, k, normalize=self.config.normalize_embeddings)
+            sims, ids, _ = self.faiss_index.search_grouped(q, k, normalize=self.config.normalize_embeddings, allow=allow)
             return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
 
     def search_diverse(self, query_embedding, config: Optional[SearchConfig] = None,
@@ -517,24 +525,18 @@ class HybridStorage:
         made.  Without it and with filters, ``k = min(max(top_k, max_results), 128)`` picks are made and filtered in
         pick order, as ``search()`` filters rows: a chunk that fails the filter still stood in the way of its
         near-copies.  An index object without ``search_diverse`` raises ``NotImplementedError``."""
-        cfg = config or SearchConfig()
-        if not self.faiss_index:
-            return []
-        if not hasattr(self.faiss_index, "search_diverse"):
+        if self.faiss_index and not hasattr(self.faiss_index, "search_diverse"):
             raise NotImplementedError(f"{type(self.faiss_index).__name__} has no diversified search (search_diverse)")
         with self._lock:
-            ntotal = self.faiss_index.ntotal
-            if ntotal == 0 or cfg.top_k <= 0:
+            frame = self._search_frame(config, query_embedding)
+            if frame is None or frame[0].top_k <= 0:
                 return []
-            q = np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
-            pushdown = bool(self.config.filter_pushdown)
-            allow = None
-            if (pushdown and filters) or len(self.faiss_id_to_chunk_id) < ntotal:
-                allow = self._allow_mask((filters or {}) if pushdown else {}, ntotal)
-            k = cfg.top_k if (pushdown or not filters) else max(cfg.top_k, cfg.max_results)
+            cfg, ntotal, q = frame
+            allow = self._allow_for(filters, ntotal, tombstones_always=True)
+            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
             k = max(1, min(k, fi.MAX_DIVERSE_FETCH))
-            kw = {"allow": allow} if allow is not None else {}
-            sims, ids = self.faiss_index.search_diverse(q, k, lam=lam, normalize=self.config.normalize_embeddings, **kw)
+            sims, ids = self.faiss_index.search_diverse(q, k, lam=lam, normalize=self.config.normalize_embeddings,
+                                                        allow=allow)
             return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
 
     @staticmethod
@@ -563,13 +565,13 @@ class HybridStorage:
         thr = float(cfg.similarity_threshold if threshold is None else threshold)
         if thr != thr:
             raise ValueError("search_range: the threshold is NaN")
-        if not self.faiss_index or (limit is not None and limit <= 0):
+        if limit is not None and limit <= 0:
             return []
         with self._lock:
-            ntotal = self.faiss_index.ntotal
-            if ntotal == 0:
+            frame = self._search_frame(cfg, query_embedding)
+            if frame is None:
                 return []
-            q = np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
+            _, ntotal, q = frame
             with np.errstate(over="ignore"):
                 t32 = np.float32(thr)
             if self.config.normalize_embeddings:
@@ -581,28 +583,10 @@ class HybridStorage:
                 if float(t32) > thr:
                     t32 = np.nextafter(t32, np.float32(-np.inf))
                 radius = np.nextafter(t32, np.float32(np.inf))
-            allow = None
-            if self.config.filter_pushdown and (filters or len(self.faiss_id_to_chunk_id) < ntotal):
-                allow = self._allow_mask(filters or {}, ntotal)
-            if allow is not None:
-                _, sims, ids = self.faiss_index.range_search(q, float(radius), normalize=self.config.normalize_embeddings,
-                                                             allow=allow)
-            else:
-                _, sims, ids = self.faiss_index.range_search(q, float(radius), normalize=self.config.normalize_embeddings)
-            out: List[SearchResult] = []
-            for score, fid in zip(sims.tolist(), ids.tolist()):
-                chunk_id = self.faiss_id_to_chunk_id.get(fid)
-                if not chunk_id:  # tombstone: row deleted from SQLite, vector still in the index
-                    continue
-                data = self._get_chunk_data(chunk_id)
-                if not data:
-                    continue
-                if filters and not self._matches_filters(data, filters):
-                    continue
-                out.append(self._make_result(chunk_id, score, data, cfg))
-                if limit is not None and len(out) >= limit:
-                    break
-            return out
+            allow = self._allow_for(filters, ntotal, tombstones_always=False)
+            _, sims, ids = self.faiss_index.range_search(q, float(radius), normalize=self.config.normalize_embeddings,
+                                                         allow=allow)
+            return self._results_in_rank_order(sims.tolist(), ids.tolist(), cfg, filters, unbounded=True, limit=limit)
 
     def _allow_mask(self, filters: Dict[str, Any], ntotal: int) -> np.ndarray:
         """Boolean mask over index rows: live (not tombstoned) and matching ``filters`` under exactly the

@@ -1213,3 +1213,107 @@ def test_two_host_threads_search_own_and_shared_indexes(tmp_path):
                                 "kernel", "##s", "on", "a", "gpu", "claude", "session", "index", "test"]) + "\n")
     r = subprocess.run([str(csrc / "san" / "cabi_threads"), str(vocab), "gpu"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "cabi_threads: ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+
+
+# ---- the pinned staging of the host entry points (HostCall in css_index.hip): both sides of every boundary ----------
+def _host_stage_bytes():
+    """``css_index::kHostStage`` as the library's source states it."""
+    import re
+
+    src = (Path(__file__).resolve().parents[1] / "claude_semantic_search_amd" / "csrc" / "css_index.hip").read_text()
+    a, b = re.search(r"kHostStage\s*=\s*(\d+)\s*\*\s*(\d+)\s*;", src).groups()
+    return int(a) * int(b)
+
+
+def _grouped_ranking64(x, q, labels, allow, k):
+    """Collapsed float64 ranking of normalised rows (inner product): ``(D32, I, D64)`` ``[nq, k]``, the best allowed
+    row of every group, best group first, ties to the lower id, padded like ``search``."""
+    S = q.astype(np.float64) @ x.astype(np.float64).T
+    S[:, ~allow] = -np.inf
+    pad = -float(np.finfo(np.float32).max)
+    nq = q.shape[0]
+    D64 = np.full((nq, k), pad)
+    I = np.full((nq, k), -1, dtype=np.int64)
+    for j in range(nq):
+        best = {}
+        for r in np.lexsort((np.arange(x.shape[0]), -S[j])):   # best first, ties to the lower id
+            if S[j, r] == -np.inf:
+                break
+            best.setdefault(int(labels[r]), int(r))
+        rows = list(best.values())[:k]
+        I[j, :len(rows)], D64[j, :len(rows)] = rows, S[j, rows]
+    return D64.astype(np.float32), I, D64
+
+
+def test_host_calls_on_both_sides_of_the_pinned_staging_limits():
+    """A host call goes through the pinned staging when its input AND its result record fit ``kHostStage`` each, and
+    through direct copies otherwise; one frame serves every variant, with 12-byte result entries (id, score) or 16-byte
+    ones (``search_grouped``: + label).  Every boundary is taken from both sides: ``search``, ``search_diverse`` and
+    ``search_by_ids`` must return bit for bit what their ``_dev`` twins return, masked and unmasked, and
+    ``search_grouped`` the collapsed masked 128-row list where that holds k groups, else the collapsed float64
+    ranking (``knn_checks.assert_topk_matches``)."""
+    import torch
+
+    from oracle import knn_oracle as ko
+    from claude_semantic_search_amd.flat_index import IndexFlatIP, collapse_groups, pack_allow_bits
+
+    n, d, fetch = 2000, 64, 128
+    stage, qbytes = _host_stage_bytes(), d * 4
+    # (nq, k, side that crosses): the byte arithmetic of the cases, so that another kHostStage fails here
+    plain = [(256, 10, "in"), (257, 10, "in"), (64, 85, "out"), (64, 86, "out")]
+    assert 256 * qbytes <= stage < 257 * qbytes and 257 * 10 * 12 <= stage       # input side, results fit
+    assert 64 * 85 * 12 <= stage < 64 * 86 * 12 and 64 * qbytes <= stage         # 12-byte entries, queries fit
+    assert 64 * 64 * 16 <= stage < 64 * 65 * 16 and 64 * 65 * 12 <= stage        # 16-byte entries: 12 would still stage
+    assert 64 * 8 <= stage                                                       # (the ids of search_by_ids always fit)
+
+    x = ko.normalize_rows(synth.rows(n, d, 301))
+    q = ko.normalize_rows(synth.rows(257, d, 302))
+    labels = (np.arange(n) % 50).astype(np.int32)
+    allow = np.random.default_rng(303).random(n) < 0.5
+    ix = IndexFlatIP(d)
+    ix.add(x)
+    ix.set_groups(labels)
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    bits = torch.from_numpy(pack_allow_bits(allow, n).view(np.int32)).to(dev)
+    q_dev = torch.from_numpy(q).to(dev)
+    anchors = (np.arange(64, dtype=np.int64) * 31 + 7) % n
+    anchors_dev = torch.from_numpy(anchors).to(dev)
+
+    def twin(call, nq, k):
+        D = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        I = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        call(D.data_ptr(), I.data_ptr())
+        torch.cuda.synchronize()
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    for nq, k, side in plain:
+        for mask, mask_ptr in ((None, 0), (allow, bits.data_ptr())):
+            what = f"nq={nq} k={k} masked={mask is not None}"
+            D, I = ix.search(q[:nq], k, allow=mask)
+            Dt, It = twin(lambda Dp, Ip: ix.search_dev(q_dev.data_ptr(), nq, k, Dp, Ip, st, allow_bits_ptr=mask_ptr), nq, k)
+            assert np.array_equal(I, It) and np.array_equal(D, Dt), f"search {what}"
+            D, I = ix.search_diverse(q[:nq], k, fetch=fetch, allow=mask)
+            Dt, It = twin(lambda Dp, Ip: ix.search_diverse_dev(q_dev.data_ptr(), nq, k, Dp, Ip, st, fetch=fetch,
+                                                               allow_bits_ptr=mask_ptr), nq, k)
+            assert np.array_equal(I, It) and np.array_equal(D, Dt), f"search_diverse {what}"
+            if side == "out":   # (its input is 8 bytes per query: only the result side crosses)
+                D, I = ix.search_by_ids(anchors[:nq], k, allow=mask)
+                Dt, It = twin(lambda Dp, Ip: ix.search_by_ids_dev(anchors_dev.data_ptr(), nq, k, Dp, Ip, st,
+                                                                  allow_bits_ptr=mask_ptr), nq, k)
+                assert np.array_equal(I, It) and np.array_equal(D, Dt), f"search_by_ids {what}"
+                assert not (I == anchors[:nq, None]).any() and int(I.min()) >= 0, f"search_by_ids {what}"
+
+    nq = 64
+    D128, I128 = ix.search(q[:nq], 128, allow=allow)
+    G128 = np.where(I128 >= 0, labels[np.maximum(I128, 0)], -1).astype(np.int32)
+    groups_in_list = np.array([np.unique(G128[j][I128[j] >= 0]).size for j in range(nq)])
+    for k in (64, 65):
+        D, I, G = ix.search_grouped(q[:nq], k, allow=allow)
+        assert np.array_equal(G, np.where(I >= 0, labels[np.maximum(I, 0)], -1)), f"search_grouped k={k}: labels"
+        Dc, Ic, Gc = collapse_groups(D128, I128, G128, k, 0)
+        full = groups_in_list >= k
+        assert np.array_equal(D[full], Dc[full]) and np.array_equal(I[full], Ic[full]) and np.array_equal(G[full], Gc[full])
+        De, Ie, D64 = _grouped_ranking64(x, q[:nq], labels, allow, k)
+        assert_topk_matches(D[~full], I[~full], De[~full], Ie[~full], D64[~full], f"search_grouped k={k}")
+    ix.close()
