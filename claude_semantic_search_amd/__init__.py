@@ -18,6 +18,7 @@ _LAZY = {
     "SearchConfig": ".storage",
     "SearchResult": ".storage",
     "HybridStorage": ".storage",
+    "recency_priors": ".storage",
     "EmbeddingConfig": ".embeddings",
     "EmbeddingStats": ".embeddings",
     "EmbeddingGenerator": ".embeddings",

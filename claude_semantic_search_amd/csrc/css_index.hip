@@ -32,6 +32,8 @@
 //   k_drop_self        search for k + 1, and the anchor compacted out of its results behind it (a wave per query)
 //   k_collapse_groups, css_index_search_grouped: a pass's results collapsed to the first row of every group label, and
 //   k_mask_drop_groups the groups already found dropped from the exclusion bitmap of the next pass (css_knn_group.h)
+//   k_scan_prior,      css_index_search_prior: the exact fp32 sweep ranked by score + weight * prior[row], and the raw
+//   k_prior_scores     scores of the k returned rows re-formed behind the merge (css_knn_prior.h).   HBM bound
 //   k_mmr_select       css_index_search_diverse: k of a pool of the best rows picked greedily by maximal marginal
 //                      relevance, similarities from the stored fp32 rows (css_knn_diverse.h)
 //
@@ -41,8 +43,8 @@
 // search's turn at the shared workspaces (wait for the previous stream's event,
 // record at the end); CallScope is the lock and device frame of every search entry point and HostCall the whole frame
 // of the host ones (allow-bitmap and input up, result rows reserved, results back; pinned staging for small calls);
-// prep_queries is the query preparation of every search; sweep_grid is the grid of both exact sweeps.  The sweep body of
-// k_scan_small and k_range_small is deliberately NOT shared (css_knn_range.h says why).
+// prep_queries is the query preparation of every search; sweep_grid is the grid of the exact sweeps.  The sweep body of
+// k_scan_small, k_range_small and k_scan_prior is deliberately NOT shared (css_knn_range.h says why).
 #include "css_common.h"
 #include "css_devbuf.h"
 #include "css_knn_kernels.h"
@@ -86,6 +88,9 @@ struct css_index {
     // group labels of the rows (css_index_set_groups): [cap], -1 = a group of its own; empty until labels are first set.
     // Part of the row storage: it follows the rows through reallocation, ingest, reset and css_index_remove_rows
     DevBuf<int32_t> labels;
+    // per-row priors (css_index_set_priors): [cap] fp32, 0 = no boost; empty until priors are first set.  Part of the row
+    // storage exactly like the labels
+    DevBuf<float> priors;
     hipStream_t stream = nullptr;
     int num_cus = 256;
     // reusable workspaces (DevBuf: grown on demand, freed with the index; guarded by ws_mu)
@@ -167,6 +172,9 @@ struct css_index {
     // css_index_search_diverse: the [nq, fetch] pool lists of the search in front of k_mmr_select
     DevBuf<float> div_d;                // entries
     DevBuf<int64_t> div_i;
+    // css_index_search_prior: the raw scores [nq, k] of the returned rows, the trailing 4-byte column of the call's
+    // results (float bits in HostCall's int32 column)
+    DevBuf<int32_t> pri_s;              // entries
     // rows written by css_index_add_dev / _add_synthetic on the CALLER's stream: searches, reallocation and
     // export wait for this event before touching rows, norms or maxn2
     hipEvent_t ingest_ev = nullptr;
@@ -196,17 +204,20 @@ struct Rows {
     int64_t n, id_base;
     const uint32_t* mask;
     const int32_t* labels;   // group labels, one per row (null: none were ever set)
+    const float* priors;     // per-row priors (null: none were ever set, every prior is 0)
     // rows [row0, row0 + cnt) as rows of their own, with the range's bf16 OR int8 scratch rows as their shadow (the
     // other kind null): search_noshadow_ranges
     Rows range(int64_t row0, int64_t cnt, int dpad, const unsigned short* xh_rows, const unsigned char* x8_rows,
                const float* x8_scales) const {
         return Rows{xb + (size_t)row0 * dpad, xnorm2 + row0, xh_rows, x8_rows, x8_scales, cnt, id_base + row0,
-                    mask ? mask + row0 / 32 : nullptr, labels ? labels + row0 : nullptr};   // (row0 is a multiple of 256)
+                    mask ? mask + row0 / 32 : nullptr, labels ? labels + row0 : nullptr,
+                    priors ? priors + row0 : nullptr};   // (row0 is a multiple of 256)
     }
 };
 // the one place that reads the row fields of the index for a search; caller holds mu (shared is enough)
 Rows rows_of(const css_index* ix, const uint32_t* mask = nullptr) {
-    return Rows{ix->xb.p, ix->xnorm2.p, ix->xh.p, ix->x8.p, ix->x8s.p, ix->ntotal, ix->id_base, mask, ix->labels.p};
+    return Rows{ix->xb.p, ix->xnorm2.p, ix->xh.p, ix->x8.p, ix->x8s.p, ix->ntotal, ix->id_base, mask, ix->labels.p,
+                ix->priors.p};
 }
 // caller holds mu exclusively
 void set_ntotal(css_index* ix, int64_t n) {
@@ -1646,12 +1657,18 @@ int reallocate_rows(css_index* ix, int64_t ncap) {
     DevBuf<unsigned short> nxh;
     DevBuf<unsigned char> nx8;
     DevBuf<int32_t> nlab;
+    DevBuf<float> npri;
     int rc;
     if ((rc = nxb.grow_exact((size_t)ncap * ix->dpad, "hipMalloc(index rows)")) != CSS_OK) return rc;
     // the label column only where labels were set: all -1 (0xFF bytes), then the existing rows' labels
     if (ix->labels.p) {
         if ((rc = nlab.grow_exact((size_t)ncap, "hipMalloc(group labels)")) != CSS_OK) return rc;
         CSS_HIP_TRY(hipMemsetAsync(nlab.p, 0xFF, (size_t)ncap * sizeof(int32_t), ix->stream));
+    }
+    // the prior column likewise: all 0.0f, then the existing rows' priors
+    if (ix->priors.p) {
+        if ((rc = npri.grow_exact((size_t)ncap, "hipMalloc(priors)")) != CSS_OK) return rc;
+        CSS_HIP_TRY(hipMemsetAsync(npri.p, 0, (size_t)ncap * sizeof(float), ix->stream));
     }
     // +256: the coarse scan reads whole tiles of norms
     if ((rc = nn2.grow_exact((size_t)ncap + 256, "hipMalloc(index norms)")) != CSS_OK) return rc;
@@ -1684,9 +1701,13 @@ int reallocate_rows(css_index* ix, int64_t ncap) {
         if (nlab.p)
             CSS_HIP_TRY(hipMemcpyAsync(nlab.p, ix->labels.p, (size_t)ix->ntotal * sizeof(int32_t), hipMemcpyDeviceToDevice,
                                        ix->stream));
+        if (npri.p)
+            CSS_HIP_TRY(hipMemcpyAsync(npri.p, ix->priors.p, (size_t)ix->ntotal * sizeof(float), hipMemcpyDeviceToDevice,
+                                       ix->stream));
     }
-    if (ix->ntotal > 0 || nlab.p) CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    if (ix->ntotal > 0 || nlab.p || npri.p) CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
     ix->labels.swap(nlab);
+    ix->priors.swap(npri);
     ix->xb.swap(nxb);
     ix->xnorm2.swap(nn2);
     ix->xh.swap(nxh);
@@ -1733,6 +1754,8 @@ int ingest(css_index* ix, const float* x_dev, int64_t n, int normalize, bool syn
         float* d8s = ix->x8.p ? ix->x8s.p + r0 : nullptr;
         // appended rows are ungrouped (the slots may hold the labels of rows removed earlier)
         if (ix->labels.p) CSS_HIP_TRY(hipMemsetAsync(ix->labels.p + r0, 0xFF, (size_t)nc * sizeof(int32_t), st));
+        // ... and carry no prior
+        if (ix->priors.p) CSS_HIP_TRY(hipMemsetAsync(ix->priors.p + r0, 0, (size_t)nc * sizeof(float), st));
         if (synth)
             hipLaunchKernelGGL(k_ingest_rows<true>, dim3(blocks), dim3(256), 0, st, nullptr, dst, n2, nc, ix->dim, ix->dpad,
                                normalize, seed, first_row + c0, dh, ix->maxn2.p, (float*)nullptr, d8, d8s);
@@ -2572,7 +2595,7 @@ int launch_scan_coarse(css_index* ix, const Rows& rows, int q0, int nq, int k, f
     return launch_fixup(ix, rows, qpad, nq, k, ix->gthr.p + q0, flag_list, nflag, D_dev, I_dev, sg, st);
 }
 
-// grid of the exact fp32 sweeps (k_scan_small, k_range_small) over the rows in view: enough blocks to fill the chip
+// grid of the exact fp32 sweeps (k_scan_small, k_range_small, k_scan_prior) over the rows in view: enough blocks to fill the chip
 // (8 per CU) but at least ~64 row groups of work each
 void sweep_grid(const css_index* ix, const Rows& rows, int* G, int64_t* gpb) {
     const int64_t ngroups = (rows.n + 3) / 4;
@@ -2649,6 +2672,69 @@ int range_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 // No room: CSS_ERR_OOM, the pool is gone (the next call starts from the initial size) and the index is untouched.
 int range_pool_alloc(css_index* ix, size_t cap) {
     return try_exact_pair(ix->range_s, ix->range_i, kRangeSlots * cap) ? CSS_OK : CSS_ERR_OOM;
+}
+
+// ------------------------------------------------------------------ prior-weighted search (css_knn_prior.h)
+#include "css_knn_prior.h"
+
+// HASP: the index has a prior column (false: every prior is 0, the kernel loads none)
+template <int NQ, int TT, int METRIC, bool HASP>
+int launch_scan_prior_p(css_index* ix, const Rows& rows, const float* qpad, int nq_real, int k, float weight, int* gthr,
+                        const SweepGeom& sg, hipStream_t st) {
+    const size_t lds = (size_t)NQ * ix->dpad * 4 + (size_t)NQ * k * 8 + NQ * 8;   // (k_scan_small's, plain sweep)
+    auto kern = k_scan_prior<NQ, TT, METRIC, HASP>;
+    int rc;
+    if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
+    ProfScope ps("knn_scan_prior", st);
+    hipLaunchKernelGGL(kern, dim3(sg.G), dim3(256), lds, st, (const float4*)rows.xb, qpad, rows.n, ix->dpad / 64, k, sg.gpb,
+                       gthr, ix->part_s.p, ix->part_i.p, nq_real, rows.mask, rows.priors, weight);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+template <int NQ, int TT, int METRIC>
+int launch_scan_prior_t(css_index* ix, const Rows& rows, const float* qpad, int nq_real, int k, float weight, int* gthr,
+                        const SweepGeom& sg, hipStream_t st) {
+    return rows.priors ? launch_scan_prior_p<NQ, TT, METRIC, true>(ix, rows, qpad, nq_real, k, weight, gthr, sg, st)
+                       : launch_scan_prior_p<NQ, TT, METRIC, false>(ix, rows, qpad, nq_real, k, weight, gthr, sg, st);
+}
+
+template <int NQ>
+int launch_scan_prior_nq(css_index* ix, const Rows& rows, const float* qpad, int nq_real, int k, float weight, int* gthr,
+                         const SweepGeom& sg, hipStream_t st) {
+    const bool ip = ix->metric == CSS_METRIC_IP;
+    if (ix->dpad == 768)
+        return ip ? launch_scan_prior_t<NQ, 12, CSS_METRIC_IP>(ix, rows, qpad, nq_real, k, weight, gthr, sg, st)
+                  : launch_scan_prior_t<NQ, 12, CSS_METRIC_L2>(ix, rows, qpad, nq_real, k, weight, gthr, sg, st);
+    return ip ? launch_scan_prior_t<NQ, 0, CSS_METRIC_IP>(ix, rows, qpad, nq_real, k, weight, gthr, sg, st)
+              : launch_scan_prior_t<NQ, 0, CSS_METRIC_L2>(ix, rows, qpad, nq_real, k, weight, gthr, sg, st);
+}
+
+// search_chunk_small with the prior sweep: queries [q0, q0+nqc) (nqc <= sg.nq_sweep) against the rows, fused values
+// and ids to D/I rows q0...  The merge is k_merge_final unchanged (keys are "larger is better" for both metrics).
+int search_chunk_prior(css_index* ix, const Rows& rows, int q0, int nqc, int k, float weight, const SweepGeom& sg,
+                       float* D_dev, int64_t* I_dev, hipStream_t st) {
+    int* gthr = ix->gthr.p + q0;
+    hipLaunchKernelGGL(k_fill_int, dim3(1), dim3(64), 0, st, gthr, nqc, host_f2key(-INFINITY));
+    CSS_LAUNCH_CHECK();
+    const float* qp = ix->qpad.p + (size_t)q0 * ix->dpad;
+    int rc;
+    if (nqc <= 1) rc = launch_scan_prior_nq<1>(ix, rows, qp, nqc, k, weight, gthr, sg, st);
+    else if (nqc <= 2) rc = launch_scan_prior_nq<2>(ix, rows, qp, nqc, k, weight, gthr, sg, st);
+    else if (nqc <= 8) rc = launch_scan_prior_nq<8>(ix, rows, qp, nqc, k, weight, gthr, sg, st);   // (as search_chunk_small)
+    else rc = launch_scan_prior_nq<16>(ix, rows, qp, nqc, k, weight, gthr, sg, st);
+    if (rc != CSS_OK) return rc;
+    ProfScope ps("knn_merge", st);
+    if (ix->metric == CSS_METRIC_IP)
+        hipLaunchKernelGGL(k_merge_final<CSS_METRIC_IP>, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G, k, gthr,
+                           ix->qnorm2.p + q0, rows.id_base, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, 0,
+                           (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
+    else
+        hipLaunchKernelGGL(k_merge_final<CSS_METRIC_L2>, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G, k, gthr,
+                           ix->qnorm2.p + q0, rows.id_base, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, 0,
+                           (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
 }
 
 int merge_parts(const float* Dp, const int64_t* Ip, int nparts, int64_t stride_d, int64_t stride_i, int64_t nq, int k,
@@ -3012,6 +3098,7 @@ int css_index_reset(css_index* ix) {
     CSS_HIP_TRY(hipMemsetAsync(ix->maxn2.p, 0, 3 * sizeof(int), ix->stream));
     CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
     CSS_HIP_TRY(ix->labels.drop());   // the labels go with the rows: the index is again one that never set any
+    CSS_HIP_TRY(ix->priors.drop());   // and so do the priors
     return CSS_OK;
 }
 
@@ -3089,10 +3176,11 @@ int compact_rows(css_index* ix, const uint32_t* keep, int64_t n, int64_t first, 
     return CSS_OK;
 }
 
-// The label column through the same keep bits, OUT OF PLACE into `dst` (all -1 beforehand): a second 4-byte-per-row
+// A 4-byte-per-row column (`src`: the labels, or the priors moved as bits) through the same keep bits, OUT OF PLACE
+// into `dst` (filled with the column's default beforehand): a second 4-byte-per-row
 // buffer has none of the overlap hazards of the row windows above, and the caller swaps it in.  Enqueued behind
 // compact_rows on the index's stream (it reuses compact_bits / compact_pre); `keep` stays valid until the caller waited.
-int compact_labels(css_index* ix, const uint32_t* keep, int64_t n, int32_t* dst) {
+int compact_labels(css_index* ix, const uint32_t* keep, int64_t n, const int32_t* src, int32_t* dst) {
     const hipStream_t st = ix->stream;
     const int64_t words = (n + 31) / 32;
     const uint32_t tail_mask = (n & 31) ? ((1u << (n & 31)) - 1u) : 0xFFFFFFFFu;
@@ -3111,7 +3199,7 @@ int compact_labels(css_index* ix, const uint32_t* keep, int64_t n, int32_t* dst)
             hipLaunchKernelGGL(k_keep_prefix, dim3(1), dim3(1024), 0, st, ix->compact_bits.p, ix->compact_pre.p, (int)nw);
             CSS_LAUNCH_CHECK();
             hipLaunchKernelGGL(k_compact_labels, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, st, ix->compact_bits.p,
-                               ix->compact_pre.p, L, (const int32_t*)ix->labels.p + s0, dst + dnext);
+                               ix->compact_pre.p, L, src + s0, dst + dnext);
             CSS_LAUNCH_CHECK();
         }
         dnext += surv;
@@ -3148,15 +3236,25 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
         if ((rc0 = nlab.grow_exact((size_t)ix->cap, "hipMalloc(group labels)")) != CSS_OK) return rc0;
         CSS_HIP_TRY(hipMemsetAsync(nlab.p, 0xFF, (size_t)ix->cap * sizeof(int32_t), ix->stream));
     }
+    DevBuf<float> npri;     // the compacted prior column (only where priors were set)
+    if (ix->priors.p && kept > 0) {
+        int rc0;
+        if ((rc0 = npri.grow_exact((size_t)ix->cap, "hipMalloc(priors)")) != CSS_OK) return rc0;
+        CSS_HIP_TRY(hipMemsetAsync(npri.p, 0, (size_t)ix->cap * sizeof(float), ix->stream));
+    }
     CSS_HIP_TRY(hipMemsetAsync(ix->maxn2.p, 0, 3 * sizeof(int), ix->stream));
     uint32_t patch = 0;
     int rc = kept > 0 ? compact_rows(ix, keep_bits_host, n, first, &patch) : CSS_OK;
-    if (rc == CSS_OK && nlab.p) rc = compact_labels(ix, keep_bits_host, n, nlab.p);
+    if (rc == CSS_OK && nlab.p) rc = compact_labels(ix, keep_bits_host, n, ix->labels.p, nlab.p);
+    if (rc == CSS_OK && npri.p)   // (a 4-byte column: moved as bits by the label kernel)
+        rc = compact_labels(ix, keep_bits_host, n, reinterpret_cast<const int32_t*>(ix->priors.p),
+                            reinterpret_cast<int32_t*>(npri.p));
     // later adds and searches on any stream are ordered behind the compaction (as css_index_reset)
     const hipError_t e = hipStreamSynchronize(ix->stream);
     if (rc != CSS_OK) return rc;
     if (e != hipSuccess) return css::hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
     if (nlab.p) ix->labels.swap(nlab);
+    if (npri.p) ix->priors.swap(npri);
     set_ntotal(ix, kept);
     if (kept == 0 && !ix->xh.p) ix->shadow = -1;   // emptied: as css_index_reset
     for (css_index::I8Feedback* f : {&ix->fb_batch, &ix->fb_sweep}) {   // (it described other rows; its copy has landed)
@@ -3836,6 +3934,109 @@ int css_index_search_rows(css_index* ix, const int64_t* ids_host, int64_t nq, in
     rc = hc.upload(allow_bits_host, ix->rowq_ids, ids_host, (size_t)nq, (size_t)nq * k);
     if (rc == CSS_OK) rc = search_rows_enqueue(ix, rows, ix->rowq_ids.p, nq, k, exclude_self, hc.d_out, hc.i_out, ix->stream);
     return hc.finish(rc, D_host, I_host);
+}
+
+// ------------------------------------------------------------------ per-row priors and prior-weighted search
+int css_index_set_priors(css_index* ix, int64_t row0, int64_t n, const float* priors_host) {
+    CSS_REQUIRE(ix, "css_index_set_priors: NULL index");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_set_priors: rows [%lld, %lld + %lld) outside [0, %lld)",
+                (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
+    if (n == 0) return CSS_OK;
+    CSS_REQUIRE(priors_host, "css_index_set_priors: priors is NULL");
+    // every value is looked at before anything is written
+    for (int64_t i = 0; i < n; ++i)
+        CSS_REQUIRE(std::isfinite(priors_host[i]), "css_index_set_priors: the prior of row %lld is %s (priors are finite)",
+                    (long long)(row0 + i), std::isnan(priors_host[i]) ? "NaN" : "infinite");
+    DeviceGuard g(ix->device);
+    // rows appended on another stream write their 0.0f there: they must have landed before priors go over them
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
+    int rc;
+    if (!ix->priors.p) {   // first priors of this index: the column, every row 0.0f
+        if ((rc = ix->priors.grow_exact((size_t)ix->cap, "hipMalloc(priors)")) != CSS_OK) return rc;
+        CSS_HIP_TRY(hipMemsetAsync(ix->priors.p, 0, (size_t)ix->cap * sizeof(float), ix->stream));
+    }
+    CSS_HIP_TRY(hipMemcpyAsync(ix->priors.p + row0, priors_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));   // (the copy reads the caller's memory)
+    return CSS_OK;
+}
+
+int css_index_get_priors(css_index* ix, int64_t row0, int64_t n, float* priors_out_host) {
+    CSS_REQUIRE(ix, "css_index_get_priors: NULL index");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    const Rows rows = rows_of(ix);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= rows.n - row0, "css_index_get_priors: rows [%lld, %lld + %lld) outside [0, %lld)",
+                (long long)row0, (long long)row0, (long long)n, (long long)rows.n);
+    if (n == 0) return CSS_OK;
+    CSS_REQUIRE(priors_out_host, "css_index_get_priors: priors_out is NULL");
+    if (!rows.priors) {
+        std::fill(priors_out_host, priors_out_host + n, 0.0f);
+        return CSS_OK;
+    }
+    DeviceGuard g(ix->device);
+    if (ix->ingest_pending) CSS_HIP_TRY(hipEventSynchronize(ix->ingest_ev));
+    CSS_HIP_TRY(hipMemcpy(priors_out_host, rows.priors + row0, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return CSS_OK;
+}
+
+namespace {
+// Query prep, the prior sweeps (sg.nq_sweep queries each, at most 16), and the raw scores of the returned rows behind
+// them.  Everything is enqueued on `st`; nothing waits for the device.  Caller holds ws_mu and a shared lock on mu.
+int search_prior_enqueue(css_index* ix, const Rows& rows, const float* q_dev, int64_t nq, int k, float weight, int normalize_q,
+                         float* D_dev, int64_t* I_dev, float* S_dev, hipStream_t st) {
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    // rows appended on another stream must have landed
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    if ((rc = ix->qpad.grow((size_t)(nq + 256) * ix->dpad)) != CSS_OK) return rc;
+    if ((rc = ix->qnorm2.grow((size_t)nq + 256)) != CSS_OK) return rc;
+    if ((rc = ix->gthr.grow((size_t)nq + 256)) != CSS_OK) return rc;
+    if ((rc = prep_queries(ix, q_dev, nq, normalize_q, nullptr, st)) != CSS_OK) return rc;
+    const int64_t n = nq * k;
+    if (rows.n == 0) {
+        hipLaunchKernelGGL(k_fill_pad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, n, pad_score(ix));
+        CSS_LAUNCH_CHECK();
+    } else {
+        CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "css_index_search_prior: %lld rows exceed the 32-bit row numbers of the lists",
+                    (long long)rows.n);
+        SweepGeom sg;
+        if ((rc = make_sweep_geom(ix, rows, k, &sg)) != CSS_OK) return rc;
+        if ((rc = grow_part(ix, (size_t)sg.nq_sweep * sg.G * k)) != CSS_OK) return rc;
+        for (int64_t q0 = 0; q0 < nq; q0 += sg.nq_sweep) {
+            const int nqc = (int)std::min<int64_t>(sg.nq_sweep, nq - q0);
+            if ((rc = search_chunk_prior(ix, rows, (int)q0, nqc, k, weight, sg, D_dev, I_dev, st)) != CSS_OK) return rc;
+        }
+    }
+    // (an empty index: every slot is padded and no row is read)
+    ProfScope ps("knn_prior_scores", st);
+    const dim3 grid((unsigned)((n + 15) / 16));
+    if (ix->metric == CSS_METRIC_IP)
+        hipLaunchKernelGGL(k_prior_scores<CSS_METRIC_IP>, grid, dim3(256), 0, st, (const float4*)rows.xb, (const float*)ix->qpad.p,
+                           (const int64_t*)I_dev, n, k, ix->dpad / 64, rows.id_base, pad_score(ix), S_dev);
+    else
+        hipLaunchKernelGGL(k_prior_scores<CSS_METRIC_L2>, grid, dim3(256), 0, st, (const float4*)rows.xb, (const float*)ix->qpad.p,
+                           (const int64_t*)I_dev, n, k, ix->dpad / 64, rows.id_base, pad_score(ix), S_dev);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_search_prior(css_index* ix, const float* q_host, int64_t nq, int k, float weight, int normalize_q,
+                           const uint32_t* allow_bits_host, float* D_host, int64_t* I_host, float* S_host) {
+    CSS_REQUIRE(ix, "css_index_search_prior: NULL index");
+    CSS_REQUIRE(nq >= 0 && nq < (1 << 24), "css_index_search_prior: nq=%lld out of range", (long long)nq);
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "css_index_search_prior: k=%d outside [1, %d]", k, CSS_KERNEL_MAX_K);
+    CSS_REQUIRE(std::isfinite(weight), "css_index_search_prior: weight is %s (it must be finite)",
+                std::isnan(weight) ? "NaN" : "infinite");
+    if (nq == 0) return CSS_OK;
+    CSS_REQUIRE(q_host && D_host && I_host, "css_index_search_prior: NULL buffer");
+    HostCall hc(ix);
+    int rc = hc.upload(allow_bits_host, ix->q_raw, q_host, (size_t)nq * ix->dim, (size_t)nq * k, &ix->pri_s);
+    if (rc == CSS_OK)
+        rc = search_prior_enqueue(ix, hc.rows, ix->q_raw.p, nq, k, weight, normalize_q, hc.d_out, hc.i_out,
+                                  reinterpret_cast<float*>(hc.g_out), ix->stream);
+    return hc.finish(rc, D_host, I_host, reinterpret_cast<int32_t*>(S_host));   // (S rides in the 4-byte column)
 }
 
 int css_merge_topk_dev(const float* Dp, const int64_t* Ip, int nparts, int64_t nq, int k, int metric, float* D,

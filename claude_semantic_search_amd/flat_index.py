@@ -135,6 +135,21 @@ def collapse_groups(D, I, G, k: int, metric: int) -> Tuple[np.ndarray, np.ndarra
     return Do, Io, Go
 
 
+MAX_PRIOR_K = nat.MAX_PRIOR_K
+
+
+def priors_as_f32(priors, what: str = "set_priors") -> np.ndarray:
+    """Array-like of real per-row priors -> contiguous 1-D float32 array; anything else (booleans, complex numbers,
+    strings, objects, more than one dimension) raises ``ValueError``.  Values are not looked at here: the library
+    refuses NaN and infinity and names the row."""
+    a = np.asarray(priors)
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+        raise ValueError(f"{what}: priors must be real numbers, got dtype {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"{what}: priors must be one-dimensional, got shape {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
 MAX_DIVERSE_FETCH = nat.MAX_DIVERSE_FETCH
 
 
@@ -238,13 +253,16 @@ class IndexFlat:
         bits = pack_allow_bits(allow, self.ntotal)
         return bits, bits.ctypes.data
 
-    def _topk(self, fn, x, k: int, args, allow, groups: bool = False):
-        """The frame of the top-k searches: ``fn(handle, x, nq, k, *args, allow bits, D, I[, G])`` into fresh
-        ``[nq, k]`` arrays -- scores, ids and, with ``groups``, int32 labels; no query, no call."""
+    def _topk(self, fn, x, k: int, args, allow, groups: bool = False, third=None):
+        """The frame of the top-k searches: ``fn(handle, x, nq, k, *args, allow bits, D, I[, third])`` into fresh
+        ``[nq, k]`` arrays -- scores, ids and an optional third array of dtype ``third`` (``groups``: int32 labels;
+        ``np.float32``: the raw scores of ``search_prior``); no query, no call."""
         nq = x.shape[0]
         out = (np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int64))
         if groups:
-            out += (np.empty((nq, k), dtype=np.int32),)
+            third = np.int32
+        if third is not None:
+            out += (np.empty((nq, k), dtype=third),)
         bits, bits_ptr = self._allow_bits(allow)
         if nq:
             nat.check(fn(self._handle(), x.ctypes.data, nq, k, *args, bits_ptr, *(o.ctypes.data for o in out)))
@@ -379,6 +397,49 @@ class IndexFlat:
         """Diagnostics: search passes of the last ``search_grouped`` call (1 when the first pass sufficed for every
         query)."""
         return self._read_i64(nat.lib().css_index_last_group_passes)
+
+    # -- per-row priors and prior-weighted search -----------------------------
+    def set_priors(self, priors, row0: int = 0) -> None:
+        """Priors of rows ``[row0, row0 + len(priors))`` in LOCAL row numbering (like ``allow``): real numbers, stored as
+        float32.  Rows never given one have ``0.0``.  NaN or infinity raises and writes nothing.  The priors follow
+        the rows through growth, ``remove_ids`` (compacted with them) and ``reset`` (forgotten); rows added later start
+        at ``0.0``."""
+        a = priors_as_f32(priors)
+        row0 = int(row0)
+        n = self.ntotal
+        if row0 < 0 or row0 + a.shape[0] > n:
+            raise ValueError(f"set_priors: rows [{row0}, {row0 + a.shape[0]}) outside [0, {n})")
+        if a.shape[0]:
+            nat.check(nat.lib().css_index_set_priors(self._handle(), row0, a.shape[0], a.ctypes.data))
+
+    def get_priors(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """The priors of rows ``[row0, row0 + n)`` (default: to the end) as float32."""
+        row0 = int(row0)
+        total = self.ntotal
+        n = total - row0 if n is None else int(n)
+        if row0 < 0 or n < 0 or row0 + n > total:
+            raise ValueError(f"get_priors: rows [{row0}, {row0 + n}) outside [0, {total})")
+        out = np.empty(n, dtype=np.float32)
+        if n:
+            nat.check(nat.lib().css_index_get_priors(self._handle(), row0, n, out.ctypes.data))
+        return out
+
+    def search_prior(self, q, k: int, weight: float, normalize: bool = False,
+                     allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The ``k`` best rows per query under ``score + weight * prior`` (``css_index_search_prior``; L2:
+        ``distance - weight * prior``, smaller is better): ``(D[nq,k], I[nq,k], S[nq,k] float32)`` -- the fused value,
+        the global id and the row's RAW score, best fused value first, ties to the lower id, padded like ``search``
+        (``S`` like ``D``).  Exact over ALL allowed rows, not a re-rank of an over-fetched list: scores come from an
+        exact fp32 sweep of the fp32 rows, whatever the search mode.  ``weight`` is any finite float;
+        ``1 <= k <= 128``.  Without priors, or with ``weight = 0``, ``D == S`` is the exact-fp32 ``search``."""
+        a = _as_f32_2d(q, self.d, "search_prior")
+        k, weight = int(k), float(weight)
+        if k < 1 or k > MAX_PRIOR_K:
+            raise ValueError(f"k={k} outside [1, {MAX_PRIOR_K}]")
+        if not np.isfinite(weight):
+            raise ValueError(f"weight={weight} is not finite")
+        self._handle()   # (a freed index raises even without queries)
+        return self._topk(nat.lib().css_index_search_prior, a, k, (weight, 1 if normalize else 0), allow, third=np.float32)
 
     # -- diversified search (MMR) --------------------------------------------
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False,

@@ -397,6 +397,57 @@ class ShardedFlatIndex:
             Ig[j], Dg[j], Gg[j] = Ig[j][order], Dg[j][order], Gg[j][order]
         return collapse_groups(Dg, Ig, Gg, k, self.metric)
 
+    # -- prior-weighted search ---------------------------------------------------------------------------------
+    def set_priors(self, global_priors, row0: int = 0) -> None:
+        """``IndexFlat.set_priors`` in GLOBAL numbering (collective: every rank passes the same priors): priors of the
+        global rows ``[row0, row0 + len(global_priors))``; every rank writes the part its shard holds, through the
+        segment table like ``set_groups``."""
+        from .flat_index import priors_as_f32
+
+        p = priors_as_f32(global_priors)
+        row0 = int(row0)
+        if row0 < 0 or row0 + p.shape[0] > self.ntotal_global:
+            raise ValueError(f"set_priors: rows [{row0}, {row0 + p.shape[0]}) outside [0, {self.ntotal_global})")
+        for l0, g0, n in self.segments:
+            lo, hi = max(g0, row0), min(g0 + n, row0 + p.shape[0])
+            if hi > lo:
+                self.local.set_priors(p[lo - row0:hi - row0], row0=l0 + (lo - g0))
+
+    def search_prior(self, q, k: int, weight: float, normalize: bool = False, allow=None):
+        """``IndexFlat.search_prior`` over the shards: ``(D, I, S)`` with global ids on every rank.  Every rank runs the
+        prior-weighted search of its shard (local allow-mask as in ``search_tensors``), maps its ids to global, and ONE
+        all-gather moves the ``nq * k`` (id, fused value, raw score) records of every rank; every rank then sorts per
+        query by (fused value, id) and keeps the first ``k``.  Exact: a row of the global top-k is in the top-k of its
+        shard.  With one rank there is no exchange."""
+        from .flat_index import MAX_PRIOR_K
+
+        qa = self._queries(q)
+        nq, k, weight = qa.shape[0], int(k), float(weight)
+        if k < 1 or k > MAX_PRIOR_K:
+            raise ValueError(f"k={k} outside [1, {MAX_PRIOR_K}]")
+        if not np.isfinite(weight):
+            raise ValueError(f"weight={weight} is not finite")
+        D, I, S = self.local.search_prior(qa, k, weight, normalize=normalize, allow=self._local_allow(allow))
+        D, S = np.ascontiguousarray(D, dtype=np.float32), np.ascontiguousarray(S, dtype=np.float32)
+        I = np.ascontiguousarray(self._to_global_np(np.asarray(I, dtype=np.int64)))
+        if self._single() or nq == 0:
+            return D, I, S
+        n = nq * k
+        send = np.empty(16 * n, dtype=np.uint8)                      # [n int64 ids][n float32 D][n float32 S]
+        send[:8 * n] = I.reshape(-1).view(np.uint8)
+        send[8 * n:12 * n] = D.reshape(-1).view(np.uint8)
+        send[12 * n:] = S.reshape(-1).view(np.uint8)
+        recv = self._all_gather_host(send)
+        Ig = np.concatenate([recv[r, :8 * n].view(np.int64).reshape(nq, k) for r in range(self.world)], axis=1)
+        Dg = np.concatenate([recv[r, 8 * n:12 * n].view(np.float32).reshape(nq, k) for r in range(self.world)], axis=1)
+        Sg = np.concatenate([recv[r, 12 * n:].view(np.float32).reshape(nq, k) for r in range(self.world)], axis=1)
+        Do, Io, So = (np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int64),
+                      np.empty((nq, k), dtype=np.float32))
+        for j in range(nq):   # best first by (fused value, id), pads last
+            order = self._best_first(Dg[j], Ig[j], Ig[j] < 0)[:k]
+            Do[j], Io[j], So[j] = Dg[j][order], Ig[j][order], Sg[j][order]
+        return Do, Io, So
+
     # -- diversified search ------------------------------------------------------------------------------------
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
         """``IndexFlat.search_diverse`` over the shards (collective: every rank passes the same arguments): ``(D, I)``
@@ -512,6 +563,12 @@ class ShardedIndexFacade:
 
     def search_grouped(self, q, k: int, normalize: bool = False, allow=None):
         return self.sh.search_grouped(np.asarray(q, dtype=np.float32), int(k), normalize=normalize, allow=allow)
+
+    def set_priors(self, priors, row0: int = 0) -> None:
+        self.sh.set_priors(priors, row0=row0)
+
+    def search_prior(self, q, k: int, weight: float, normalize: bool = False, allow=None):
+        return self.sh.search_prior(np.asarray(q, dtype=np.float32), int(k), float(weight), normalize=normalize, allow=allow)
 
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
         return self.sh.search_diverse(np.asarray(q, dtype=np.float32), int(k), lam=lam, fetch=fetch, normalize=normalize,

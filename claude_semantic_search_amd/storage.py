@@ -32,7 +32,7 @@ import sqlite3
 import struct
 import threading
 from dataclasses import dataclass
-from datetime import datetime
+from datetime import datetime, timezone
 from pathlib import Path
 from typing import Any, Dict, List, Optional
 
@@ -154,6 +154,50 @@ class _LiveRows:
         return out
 
 
+# search_recent: the largest exponent of 2 a stored prior or the call's weight factor may carry (fp32 holds 2^127;
+# 60 leaves the fused value far from overflow and the priors far from underflow for every half-life in between)
+RECENCY_MAX_EXPONENT = 60.0
+
+
+def recency_priors(t_days, t_ref_days: float, half_life_days: float) -> np.ndarray:
+    """The stored per-row prior of ``search_recent``: ``p_r = 2^((t_r - t_ref) / h)`` as float32, for timestamps
+    ``t_days`` (days on any common clock; NaN = no timestamp -> prior 0, infinitely old).  The column does not depend
+    on "now": a search at time ``now`` passes ``weight * 2^(-(now - t_ref) / h)`` as the call's weight, and the
+    product is ``weight * 2^(-age / h)``.  Exponents beyond ``RECENCY_MAX_EXPONENT`` raise ``ValueError``: the caller
+    re-references first (``t_ref`` = the newest timestamp, which makes every exponent <= 0)."""
+    h = float(half_life_days)
+    if not (h > 0.0) or not np.isfinite(h):
+        raise ValueError(f"half_life_days={half_life_days} must be a positive finite number")
+    t = np.asarray(t_days, dtype=np.float64).reshape(-1)
+    e = (t - float(t_ref_days)) / h
+    known = ~np.isnan(e)
+    if known.any() and float(e[known].max()) > RECENCY_MAX_EXPONENT:
+        raise ValueError(f"recency_priors: exponent {float(e[known].max()):.1f} beyond {RECENCY_MAX_EXPONENT:.0f}: "
+                         "re-reference t_ref to the newest timestamp")
+    out = np.zeros(t.shape[0], dtype=np.float32)
+    with np.errstate(under="ignore"):
+        out[known] = np.exp2(e[known]).astype(np.float32)
+    return out
+
+
+def timestamp_days(ts) -> float:
+    """A chunk's ``timestamp`` column (ISO string or ``datetime``; naive = UTC) as days since the Unix epoch; NaN for
+    a missing or unparseable one."""
+    if ts is None:
+        return float("nan")
+    try:
+        if not isinstance(ts, datetime):
+            text = str(ts).strip()
+            if text.endswith(("Z", "z")):
+                text = text[:-1] + "+00:00"
+            ts = datetime.fromisoformat(text)
+        if ts.tzinfo is None:
+            ts = ts.replace(tzinfo=timezone.utc)
+        return ts.timestamp() / 86400.0
+    except (ValueError, OverflowError, OSError):
+        return float("nan")
+
+
 class HybridStorage:
     def __init__(self, config: Optional[StorageConfig] = None) -> None:
         self.config: StorageConfig = config or StorageConfig()
@@ -180,6 +224,13 @@ class HybridStorage:
         self._session_labels: Dict[str, int] = {}
         self._labels_index: Optional[Any] = None
         self._labels_synced = 0
+        # search_recent: which rows of WHICH index object carry their recency prior, for which half-life and reference
+        # time (days since the epoch); the newest timestamp seen so far
+        self._priors_index: Optional[Any] = None
+        self._priors_synced = 0
+        self._priors_half_life: Optional[float] = None
+        self._priors_t_ref: Optional[float] = None
+        self._priors_newest: Optional[float] = None
 
         self.total_chunks: int = 0
         self.embedding_dim: int = self.config.embedding_dim
@@ -537,6 +588,83 @@ class HybridStorage:
             k = max(1, min(k, fi.MAX_DIVERSE_FETCH))
             sims, ids = self.faiss_index.search_diverse(q, k, lam=lam, normalize=self.config.normalize_embeddings,
                                                         allow=allow)
+            return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
+
+    def _row_days(self, lo: int, hi: int) -> np.ndarray:
+        """Timestamps of index rows ``[lo, hi)`` in days since the epoch; NaN: no chunk, no or an unparseable timestamp."""
+        t = np.full(hi - lo, np.nan, dtype=np.float64)
+        rows = self.db.cursor().execute(
+            "SELECT faiss_id, timestamp FROM chunks WHERE faiss_id >= ? AND faiss_id < ? AND timestamp IS NOT NULL",
+            (lo, hi)).fetchall()
+        for fid, ts in rows:
+            t[fid - lo] = timestamp_days(ts)
+        return t
+
+    def _sync_recency_priors(self, ntotal: int, half_life_days: float, now_days: float) -> float:
+        """Bring the index's prior column up to date (``recency_priors`` of the rows' timestamps) and return the
+        reference time it is stored against.  The column is never rewritten as time passes: only the tail
+        ``[synced, ntotal)`` is pushed after adds.  Everything is pushed when the index object was replaced or
+        compacted, when ``half_life_days`` changed, and when the newest timestamp or ``now`` lies more than
+        ``RECENCY_MAX_EXPONENT`` half-lives beyond the reference, which then becomes the newest timestamp (a ``now``
+        that far beyond the NEWEST row needs no new column: every boost has underflowed, and the weight factor says so)."""
+        h = float(half_life_days)
+        full = self._priors_index is not self.faiss_index or self._priors_half_life != h or self._priors_t_ref is None
+        lo = 0 if full else self._priors_synced
+        t = self._row_days(lo, ntotal) if lo < ntotal else np.zeros(0)
+        known = t[~np.isnan(t)]
+        newest = None if full else self._priors_newest
+        if known.size:
+            newest = float(known.max()) if newest is None else max(newest, float(known.max()))
+        if not full and newest is not None and newest != self._priors_t_ref:
+            ref = self._priors_t_ref
+            full = (newest - ref) / h > RECENCY_MAX_EXPONENT or (now_days - ref) / h > RECENCY_MAX_EXPONENT
+            if full:
+                lo, t = 0, self._row_days(0, ntotal)
+        if full:
+            self._priors_index, self._priors_half_life = self.faiss_index, h
+            self._priors_t_ref = newest if newest is not None else now_days
+        self._priors_newest = newest
+        if lo < ntotal:
+            self.faiss_index.set_priors(recency_priors(t, self._priors_t_ref, h), row0=lo)
+        self._priors_synced = ntotal
+        return self._priors_t_ref
+
+    def search_recent(self, query_embedding, config: Optional[SearchConfig] = None,
+                      filters: Optional[Dict[str, Any]] = None, half_life_days: float = 30.0, weight: float = 0.1,
+                      now: Optional[datetime] = None) -> List[SearchResult]:
+        """``top_k`` chunks ranked by ``similarity + weight * 2^(-age / half_life_days)`` ("prefer the recent ones"; an
+        L2 storage ranks by ``distance - weight * 2^(-age / half_life_days)``), ``age`` = ``now`` (default: the
+        present) minus the chunk's ``timestamp`` (ISO, naive = UTC; none or unparseable = infinitely old, no boost).
+        The ranking runs inside the index over ALL allowed rows (``IndexFlat.search_prior``), not over an over-fetched
+        list: a recent chunk is found however far down the plain ranking it sits.  Results come in FUSED order, each
+        with its RAW similarity, to which ``similarity_threshold`` applies (as in ``search_diverse``).
+
+        Tombstones always go into the allow mask.  With ``filter_pushdown`` the filters go there too and ``k = top_k``
+        rows are fetched; without it and with filters, ``k = min(max(top_k, max_results), 128)`` rows are fetched and
+        filtered in rank order.  ``half_life_days <= 0`` or NaN and a ``weight`` that is not finite raise
+        ``ValueError``; an index object without ``search_prior`` raises ``NotImplementedError``."""
+        h, w = float(half_life_days), float(weight)
+        if not (h > 0.0) or not np.isfinite(h):
+            raise ValueError(f"search_recent: half_life_days={half_life_days} must be a positive finite number")
+        if not np.isfinite(w):
+            raise ValueError(f"search_recent: weight={weight} is not finite")
+        if self.faiss_index and not (hasattr(self.faiss_index, "search_prior") and hasattr(self.faiss_index, "set_priors")):
+            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no prior-weighted search (search_prior / set_priors)")
+        now_days = timestamp_days(now if now is not None else datetime.now(timezone.utc))
+        if now_days != now_days:
+            raise ValueError(f"search_recent: now={now!r} is not a time")
+        with self._lock:
+            frame = self._search_frame(config, query_embedding)
+            if frame is None or frame[0].top_k <= 0:
+                return []
+            cfg, ntotal, q = frame
+            allow = self._allow_for(filters, ntotal, tombstones_always=True)
+            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
+            k = max(1, min(k, fi.MAX_PRIOR_K))
+            t_ref = self._sync_recency_priors(ntotal, h, now_days)
+            with np.errstate(over="ignore", under="ignore"):
+                w_now = float(np.float32(w * np.exp2(-(now_days - t_ref) / h)))
+            _, ids, sims = self.faiss_index.search_prior(q, k, w_now, normalize=self.config.normalize_embeddings, allow=allow)
             return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
 
     @staticmethod
@@ -957,6 +1085,7 @@ class HybridStorage:
             self.total_chunks = len(live)
             self._mutations += 1
             self._labels_index = None   # (search_sessions pushes every label again: the rows were renumbered)
+            self._priors_index = None   # (and search_recent every prior)
             if not in_place:
                 old.close()
         self.logger.info("Flat index rebuilt")

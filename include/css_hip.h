@@ -244,6 +244,45 @@ int css_index_search_grouped(css_index* ix, const float* q_host, int64_t nq, int
                              int32_t* G_host /* may be NULL */);
 int css_index_last_group_passes(css_index* ix, int64_t* n);   /* diagnostics: search passes of the last grouped call */
 
+/* Per-row priors and prior-weighted search (Elasticsearch "function score", Vespa rank-profile freshness terms, a
+ * document prior): the k best rows under the query score PLUS a per-row additive term -- "prefer the recent ones" is
+ * one use of it.  A re-rank of an over-fetched list cannot do this: a boosted row may sit anywhere below the fetched
+ * rows, so the fused value is the key of the sweep itself.
+ *  - Priors.  Every row has one fp32 prior; a row never given one has 0.0f.  Priors are per index, in LOCAL row
+ *    numbering like allow_bits and the group labels.  css_index_set_priors writes the priors of rows [row0, row0 + n),
+ *    css_index_get_priors reads them back; a range outside [0, ntotal) is CSS_ERR_INVALID.  A NaN or infinite value is
+ *    CSS_ERR_INVALID: the message names the row and NOTHING is written.  Locking and the ordering against pending
+ *    asynchronous adds are those of css_index_set_groups / css_index_get_groups.  The column (4 bytes per row of
+ *    capacity) is allocated by the first css_index_set_priors: an index that never sets one pays nothing, and its
+ *    get_priors returns zeros without touching the device.  It follows the rows: kept through capacity growth, 0.0f for
+ *    appended rows, compacted by css_index_remove_rows with the same keep bits (afterwards get_priors = priors[keep],
+ *    bit for bit), forgotten by css_index_reset.
+ *  - css_index_search_prior.  For every query the k best allowed rows under the FUSED value, with p_r the row's prior:
+ *        inner product   f = fmaf(weight, p_r, s)       larger is better
+ *        squared L2      f = fmaf(-weight, p_r, dist)   smaller is better: a positive prior pulls a row closer, and f
+ *                                                       may be negative
+ *    s / dist is the exact fp32 score of the fp32 rows, in the arithmetic of CSS_SEARCH_EXACT_FP32 for up to 16 queries
+ *    (one fmaf chain per lane over the padded row, the row reduction, L2 from differences).  D = f, best first, ties to
+ *    the lower id; I = global ids; S (may be NULL) = the row's raw s / dist, so that thresholds keep their meaning:
+ *    D[j, t] is exactly the fmaf above applied to S[j, t].  Padding as in css_index_search: I = -1 and D = S = -FLT_MAX
+ *    (inner product) / +FLT_MAX (L2).
+ *  - Limits: 1 <= k <= 128 (the kernels' list size); weight is any finite float (NaN or infinity is CSS_ERR_INVALID,
+ *    the message names it).  nq == 0 is a no-op; an empty index gives fully padded rows.  normalize_q, allow_bits_host,
+ *    rows appended on other streams and the shared workspaces are those of css_index_search_masked.
+ *  - Nothing depends on the reduced-precision row copies (css_index_set_shadow) or on the search mode.  An index without
+ *    priors, or weight == 0, gives f == s bit for bit: the result of css_index_search under CSS_SEARCH_EXACT_FP32 for up
+ *    to 16 queries, with S == D.
+ *  - On the device: one sweep of the fp32 rows serves up to 16 queries (longer batches are walked a sweep at a time: a
+ *    correctness path, the workload is one query); it reads 4 * dpad + 4 bytes per row.  The raw scores of the nq * k
+ *    returned rows are re-formed by one small launch behind the merge, with the sweep's own summation order.  There is
+ *    no candidate path: a certified over-fetch would need a bound on weight * max prior below the score spread of the
+ *    best rows. */
+int css_index_set_priors(css_index* ix, int64_t row0, int64_t n, const float* priors_host);
+int css_index_get_priors(css_index* ix, int64_t row0, int64_t n, float* priors_out_host);
+int css_index_search_prior(css_index* ix, const float* q_host, int64_t nq, int k, float weight, int normalize_q,
+                           const uint32_t* allow_bits_host, float* D_host, int64_t* I_host,
+                           float* S_host /* may be NULL */);
+
 /* Diversified search (maximal marginal relevance, MMR; langchain's max_marginal_relevance_search, the "diversity"
  * option of vector stores): k rows picked greedily from a pool of the best rows, each pick trading its score against
  * its similarity to the rows already picked -- so near-copies of one passage do not fill the answer.  Per query, with
