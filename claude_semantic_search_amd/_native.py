@@ -28,6 +28,8 @@ MAX_K = 2048   # include/css_hip.h CSS_MAX_K
 MAX_GROUP_K = 128   # css_index_search_grouped: the kernels' list size
 MAX_DIVERSE_FETCH = 128   # css_index_search_diverse: the largest candidate pool (the same list size)
 MAX_PRIOR_K = 128   # css_index_search_prior: the same list size
+MAX_EXAMPLES = 16   # include/css_hip.h CSS_MAX_EXAMPLES
+MAX_EXAMPLES_K = 128   # css_index_search_examples: the same list size
 
 
 class CssError(RuntimeError):
@@ -116,6 +118,8 @@ PROTOTYPES = {
     "css_index_get_priors": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
     "css_index_search_prior": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
+    "css_index_search_examples": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_int,
+                                          c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "css_index_search_diverse": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
                                          c_void_p]),
     "css_index_search_diverse_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_void_p,

@@ -34,6 +34,9 @@
 //   k_mask_drop_groups the groups already found dropped from the exclusion bitmap of the next pass (css_knn_group.h)
 //   k_scan_prior,      css_index_search_prior: the exact fp32 sweep ranked by score + weight * prior[row], and the raw
 //   k_prior_scores     scores of the k returned rows re-formed behind the merge (css_knn_prior.h).   HBM bound
+//   k_scan_examples,   css_index_search_examples: the exact fp32 sweep ranked by best positive - gamma * best negative
+//   k_example_scores   score over up to 16 example vectors, ONE list; the best positive scores of the k returned rows
+//                      re-formed behind the merge (css_knn_examples.h).   HBM bound
 //   k_mmr_select       css_index_search_diverse: k of a pool of the best rows picked greedily by maximal marginal
 //                      relevance, similarities from the stored fp32 rows (css_knn_diverse.h)
 //
@@ -44,7 +47,7 @@
 // record at the end); CallScope is the lock and device frame of every search entry point and HostCall the whole frame
 // of the host ones (allow-bitmap and input up, result rows reserved, results back; pinned staging for small calls);
 // prep_queries is the query preparation of every search; sweep_grid is the grid of the exact sweeps.  The sweep body of
-// k_scan_small, k_range_small and k_scan_prior is deliberately NOT shared (css_knn_range.h says why).
+// k_scan_small, k_range_small, k_scan_prior and k_scan_examples is deliberately NOT shared (css_knn_range.h says why).
 #include "css_common.h"
 #include "css_devbuf.h"
 #include "css_knn_kernels.h"
@@ -175,6 +178,8 @@ struct css_index {
     // css_index_search_prior: the raw scores [nq, k] of the returned rows, the trailing 4-byte column of the call's
     // results (float bits in HostCall's int32 column)
     DevBuf<int32_t> pri_s;              // entries
+    // css_index_search_examples: S = the best positive score [k] of the returned rows, the same 4-byte column
+    DevBuf<int32_t> ex_s;               // entries
     // rows written by css_index_add_dev / _add_synthetic on the CALLER's stream: searches, reallocation and
     // export wait for this event before touching rows, norms or maxn2
     hipEvent_t ingest_ev = nullptr;
@@ -2595,8 +2600,8 @@ int launch_scan_coarse(css_index* ix, const Rows& rows, int q0, int nq, int k, f
     return launch_fixup(ix, rows, qpad, nq, k, ix->gthr.p + q0, flag_list, nflag, D_dev, I_dev, sg, st);
 }
 
-// grid of the exact fp32 sweeps (k_scan_small, k_range_small, k_scan_prior) over the rows in view: enough blocks to fill the chip
-// (8 per CU) but at least ~64 row groups of work each
+// grid of the exact fp32 sweeps (k_scan_small, k_range_small, k_scan_prior, k_scan_examples) over the rows in view:
+// enough blocks to fill the chip (8 per CU) but at least ~64 row groups of work each
 void sweep_grid(const css_index* ix, const Rows& rows, int* G, int64_t* gpb) {
     const int64_t ngroups = (rows.n + 3) / 4;
     const int64_t G0 = std::max<int64_t>(1, std::min<int64_t>((int64_t)ix->num_cus * 8, (ngroups + 63) / 64));
@@ -2733,6 +2738,75 @@ int search_chunk_prior(css_index* ix, const Rows& rows, int q0, int nqc, int k, 
         hipLaunchKernelGGL(k_merge_final<CSS_METRIC_L2>, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G, k, gthr,
                            ix->qnorm2.p + q0, rows.id_base, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, 0,
                            (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// ------------------------------------------------------------------ search by examples (css_knn_examples.h)
+#include "css_knn_examples.h"
+
+// the sweep's dynamic LDS: the example table, ONE list of k keys and rows, the lock pair, the excluded rows
+inline size_t examples_lds(int nq_slots, int dpad, int k) {
+    return (size_t)nq_slots * dpad * 4 + (size_t)k * 8 + 8 + kMaxExamples * 4;
+}
+// NQ of the sweep: the smallest of 1 / 2 / 8 / 16 that holds m examples (search_chunk_small's steps)
+inline int examples_slots(int m) { return m <= 1 ? 1 : m <= 2 ? 2 : m <= 8 ? 8 : 16; }
+
+struct ExampleArgs {
+    int npos, m;              // positives, all examples (the table is [m][dpad], positives first)
+    float gamma;
+    const uint32_t* excl;     // local rows never returned
+    int nexcl;
+};
+
+template <int NQ, int TT, int METRIC>
+int launch_scan_examples_t(css_index* ix, const Rows& rows, const float* epad, int k, const ExampleArgs& ea, int* gthr,
+                           const SweepGeom& sg, hipStream_t st) {
+    const size_t lds = examples_lds(NQ, ix->dpad, k);
+    auto kern = k_scan_examples<NQ, TT, METRIC>;
+    int rc;
+    if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
+    ProfScope ps("knn_scan_examples", st);
+    hipLaunchKernelGGL(kern, dim3(sg.G), dim3(256), lds, st, (const float4*)rows.xb, epad, rows.n, ix->dpad / 64, k, sg.gpb,
+                       gthr, ix->part_s.p, ix->part_i.p, ea.npos, ea.m, ea.gamma, rows.mask, ea.excl, ea.nexcl);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+template <int NQ>
+int launch_scan_examples_nq(css_index* ix, const Rows& rows, const float* epad, int k, const ExampleArgs& ea, int* gthr,
+                            const SweepGeom& sg, hipStream_t st) {
+    const bool ip = ix->metric == CSS_METRIC_IP;
+    if (ix->dpad == 768)
+        return ip ? launch_scan_examples_t<NQ, 12, CSS_METRIC_IP>(ix, rows, epad, k, ea, gthr, sg, st)
+                  : launch_scan_examples_t<NQ, 12, CSS_METRIC_L2>(ix, rows, epad, k, ea, gthr, sg, st);
+    return ip ? launch_scan_examples_t<NQ, 0, CSS_METRIC_IP>(ix, rows, epad, k, ea, gthr, sg, st)
+              : launch_scan_examples_t<NQ, 0, CSS_METRIC_L2>(ix, rows, epad, k, ea, gthr, sg, st);
+}
+
+// The example sweep over the rows and the merge of its [block][k] part lists: k_merge_final unchanged, with ONE
+// "query" (keys are "larger is better" for both metrics; <L2> writes D = -key, which is f with its sign).
+int search_examples_sweep(css_index* ix, const Rows& rows, int k, const ExampleArgs& ea, const SweepGeom& sg, float* D_dev,
+                          int64_t* I_dev, hipStream_t st) {
+    int* gthr = ix->gthr.p;
+    hipLaunchKernelGGL(k_fill_int, dim3(1), dim3(64), 0, st, gthr, 1, host_f2key(-INFINITY));
+    CSS_LAUNCH_CHECK();
+    const float* epad = ix->qpad.p;
+    int rc;
+    switch (examples_slots(ea.m)) {
+        case 1: rc = launch_scan_examples_nq<1>(ix, rows, epad, k, ea, gthr, sg, st); break;
+        case 2: rc = launch_scan_examples_nq<2>(ix, rows, epad, k, ea, gthr, sg, st); break;
+        case 8: rc = launch_scan_examples_nq<8>(ix, rows, epad, k, ea, gthr, sg, st); break;
+        default: rc = launch_scan_examples_nq<16>(ix, rows, epad, k, ea, gthr, sg, st); break;
+    }
+    if (rc != CSS_OK) return rc;
+    ProfScope ps("knn_merge", st);
+    if (ix->metric == CSS_METRIC_IP)
+        hipLaunchKernelGGL(k_merge_final<CSS_METRIC_IP>, dim3(1), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G, k, gthr,
+                           ix->qnorm2.p, rows.id_base, D_dev, I_dev, 0, (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
+    else
+        hipLaunchKernelGGL(k_merge_final<CSS_METRIC_L2>, dim3(1), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G, k, gthr,
+                           ix->qnorm2.p, rows.id_base, D_dev, I_dev, 0, (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
@@ -2899,10 +2973,11 @@ int launch_sort_rows(css_index* ix, float* D, int64_t* I, int64_t nrows, int k, 
 }
 
 // Query prep of every search: the row kernel of ingest (normalise, zero pad, squared norm) from raw [nq, dim] rows
-// into qpad / qnorm2, and ||q - bf16(q)||^2 into `qerr2` where the caller keeps it.
-int prep_queries(css_index* ix, const float* src, int64_t nq, int normalize_q, float* qerr2, hipStream_t st) {
-    hipLaunchKernelGGL(k_ingest_rows<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, src, ix->qpad.p, ix->qnorm2.p, nq,
-                       ix->dim, ix->dpad, normalize_q, 0ull, 0ll, (unsigned short*)nullptr, (int*)nullptr, qerr2,
+// into qpad / qnorm2 rows row0.. (the example table of css_index_search_examples is prepared in segments), and
+// ||q - bf16(q)||^2 into `qerr2` where the caller keeps it.
+int prep_queries(css_index* ix, const float* src, int64_t nq, int normalize_q, float* qerr2, hipStream_t st, int64_t row0 = 0) {
+    hipLaunchKernelGGL(k_ingest_rows<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, src,
+                       ix->qpad.p + (size_t)row0 * ix->dpad, ix->qnorm2.p + row0, nq, ix->dim, ix->dpad, normalize_q, 0ull, 0ll, (unsigned short*)nullptr, (int*)nullptr, qerr2,
                        (unsigned char*)nullptr, (float*)nullptr);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
@@ -4036,6 +4111,129 @@ int css_index_search_prior(css_index* ix, const float* q_host, int64_t nq, int k
     if (rc == CSS_OK)
         rc = search_prior_enqueue(ix, hc.rows, ix->q_raw.p, nq, k, weight, normalize_q, hc.d_out, hc.i_out,
                                   reinterpret_cast<float*>(hc.g_out), ix->stream);
+    return hc.finish(rc, D_host, I_host, reinterpret_cast<int32_t*>(S_host));   // (S rides in the 4-byte column)
+}
+
+// ------------------------------------------------------------------ search by examples
+namespace {
+// What css_index_search_examples uploads in ONE copy (floats of q_raw): the id examples, the excluded local rows, and
+// the raw example table [m][dim] in table order -- positive vectors, positive ids, negative vectors, negative ids --
+// with the rows of the id examples left for k_gather_queries to fill.
+constexpr size_t kExIdsAt = 0;                                   // int64[kMaxExamples]
+constexpr size_t kExExclAt = kMaxExamples * 2;                   // uint32[kMaxExamples]
+constexpr size_t kExTableAt = kMaxExamples * 3;                  // float[m][dim]; 192 bytes in: 16-byte aligned
+
+struct ExampleCounts {
+    int vec_pos, vec_neg, id_pos, id_neg;
+    int npos() const { return vec_pos + id_pos; }
+    int m() const { return vec_pos + id_pos + vec_neg + id_neg; }
+};
+
+// Example table, sweep, merge, and S behind them.  in_dev: the upload described above.  Everything is enqueued on
+// `st`; nothing waits for the device.  Caller holds ws_mu and a shared lock on mu.
+int search_examples_enqueue(css_index* ix, const Rows& rows, const float* in_dev, const ExampleCounts& c, int k, float gamma,
+                            int normalize_vec, int nexcl, float* D_dev, int64_t* I_dev, float* S_dev, hipStream_t st) {
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    // rows appended on another stream must have landed
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    if ((rc = ix->qpad.grow((size_t)(kMaxExamples + 256) * ix->dpad)) != CSS_OK) return rc;
+    if ((rc = ix->qnorm2.grow((size_t)kMaxExamples + 256)) != CSS_OK) return rc;
+    if ((rc = ix->gthr.grow((size_t)kMaxExamples + 256)) != CSS_OK) return rc;
+    if ((rc = ix->rowq_flag.grow((size_t)kMaxExamples)) != CSS_OK) return rc;
+    const int64_t* ids_dev = reinterpret_cast<const int64_t*>(in_dev + kExIdsAt);
+    float* table = const_cast<float*>(in_dev) + kExTableAt;
+    // the four segments of the table: rows, whether they are stored rows, and their first id in ids_dev
+    const struct { int n; bool ids; int id0; } seg[4] = {
+        {c.vec_pos, false, 0}, {c.id_pos, true, 0}, {c.vec_neg, false, 0}, {c.id_neg, true, c.id_pos}};
+    // stored rows as they lie in HBM (the host has checked every id: no flag is read)
+    for (int s = 0, r0 = 0; s < 4; r0 += seg[s++].n)
+        if (seg[s].ids && seg[s].n > 0) {
+            hipLaunchKernelGGL(k_gather_queries, dim3((unsigned)((seg[s].n + 3) / 4)), dim3(256), 0, st, rows.xb,
+                               ids_dev + seg[s].id0, table + (size_t)r0 * ix->dim, ix->rowq_flag.p, (int64_t)seg[s].n, rows.n,
+                               rows.id_base, ix->dim, ix->dpad);
+            CSS_LAUNCH_CHECK();
+        }
+    // prep_queries over runs of neighbouring segments that are normalised alike (stored rows never are)
+    for (int s = 0, r0 = 0; s < 4;) {
+        const int flag = !seg[s].ids && normalize_vec ? 1 : 0;
+        int n = 0, e = s;
+        for (; e < 4 && (seg[e].n == 0 || (!seg[e].ids && normalize_vec ? 1 : 0) == flag); ++e) n += seg[e].n;
+        if (n > 0 && (rc = prep_queries(ix, table + (size_t)r0 * ix->dim, n, flag, nullptr, st, r0)) != CSS_OK) return rc;
+        r0 += n;
+        s = e;
+    }
+    if (rows.n == 0) {
+        hipLaunchKernelGGL(k_fill_pad, dim3(1), dim3(256), 0, st, D_dev, I_dev, (int64_t)k, pad_score(ix));
+        CSS_LAUNCH_CHECK();
+    } else {
+        SweepGeom sg;
+        sweep_grid(ix, rows, &sg.G, &sg.gpb);
+        sg.nq_sweep = 1;   // (one list)
+        if ((rc = grow_part(ix, (size_t)sg.G * k)) != CSS_OK) return rc;
+        const ExampleArgs ea{c.npos(), c.m(), gamma, reinterpret_cast<const uint32_t*>(in_dev + kExExclAt), nexcl};
+        if ((rc = search_examples_sweep(ix, rows, k, ea, sg, D_dev, I_dev, st)) != CSS_OK) return rc;
+    }
+    if (!S_dev) return CSS_OK;
+    // (an empty index: every slot is padded and no row is read)
+    ProfScope ps("knn_example_scores", st);
+    if (ix->metric == CSS_METRIC_IP)
+        hipLaunchKernelGGL(k_example_scores<CSS_METRIC_IP>, dim3(k), dim3(256), 0, st, (const float4*)rows.xb,
+                           (const float*)ix->qpad.p, (const int64_t*)I_dev, c.npos(), ix->dpad / 64, rows.id_base, pad_score(ix), S_dev);
+    else
+        hipLaunchKernelGGL(k_example_scores<CSS_METRIC_L2>, dim3(k), dim3(256), 0, st, (const float4*)rows.xb,
+                           (const float*)ix->qpad.p, (const int64_t*)I_dev, c.npos(), ix->dpad / 64, rows.id_base, pad_score(ix), S_dev);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_search_examples(css_index* ix, const float* vec_host, int nvec_pos, int nvec_neg, const int64_t* ids_host,
+                              int nid_pos, int nid_neg, int k, float gamma, int normalize_vec, int exclude_ids,
+                              const uint32_t* allow_bits_host, float* D_host, int64_t* I_host, float* S_host) {
+    CSS_REQUIRE(ix, "css_index_search_examples: NULL index");
+    CSS_REQUIRE(nvec_pos >= 0 && nvec_neg >= 0 && nid_pos >= 0 && nid_neg >= 0,
+                "css_index_search_examples: negative example count (%d, %d, %d, %d)", nvec_pos, nvec_neg, nid_pos, nid_neg);
+    CSS_REQUIRE(nvec_pos <= CSS_MAX_EXAMPLES && nvec_neg <= CSS_MAX_EXAMPLES && nid_pos <= CSS_MAX_EXAMPLES &&
+                    nid_neg <= CSS_MAX_EXAMPLES && nvec_pos + nvec_neg + nid_pos + nid_neg <= CSS_MAX_EXAMPLES,
+                "css_index_search_examples: more than %d examples (%d + %d vectors, %d + %d ids)", CSS_MAX_EXAMPLES, nvec_pos,
+                nvec_neg, nid_pos, nid_neg);
+    const ExampleCounts c{nvec_pos, nvec_neg, nid_pos, nid_neg};
+    CSS_REQUIRE(c.npos() >= 1, "css_index_search_examples: no positive example");
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "css_index_search_examples: k=%d outside [1, %d]", k, CSS_KERNEL_MAX_K);
+    CSS_REQUIRE(std::isfinite(gamma) && gamma >= 0.f, "css_index_search_examples: gamma is %s (it must be finite and >= 0)",
+                std::isnan(gamma) ? "NaN" : std::isinf(gamma) ? "infinite" : "negative");
+    const int nvec = nvec_pos + nvec_neg, nid = nid_pos + nid_neg;
+    CSS_REQUIRE(D_host && I_host && (nvec == 0 || vec_host) && (nid == 0 || ids_host), "css_index_search_examples: NULL buffer");
+    HostCall hc(ix);
+    const Rows& rows = hc.rows;   // (every host check comes before anything is enqueued)
+    for (int j = 0; j < nid; ++j)
+        CSS_REQUIRE(ids_host[j] >= rows.id_base && ids_host[j] - rows.id_base < rows.n,
+                    "css_index_search_examples: id %lld (%s example %d) outside [%lld, %lld)", (long long)ids_host[j],
+                    j < nid_pos ? "positive" : "negative", j < nid_pos ? j : j - nid_pos, (long long)rows.id_base,
+                    (long long)(rows.id_base + rows.n));
+    CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "css_index_search_examples: %lld rows exceed the 32-bit row numbers of the lists",
+                (long long)rows.n);
+    CSS_REQUIRE(examples_lds(examples_slots(c.m()), ix->dpad, k) <= 64 * 1024,
+                "css_index_search_examples: %d examples of dim=%d exceed the sweep's example table (64 KiB with its list)", c.m(),
+                ix->dim);
+    // the ONE upload: ids, excluded local rows, the raw table with the vector examples in their places
+    const size_t dim = (size_t)ix->dim;
+    std::vector<float> in(kExTableAt + (size_t)c.m() * dim, 0.f);
+    if (nid) memcpy(in.data() + kExIdsAt, ids_host, (size_t)nid * sizeof(int64_t));
+    const int nexcl = exclude_ids ? nid : 0;
+    for (int j = 0; j < nexcl; ++j) {
+        const uint32_t r = (uint32_t)(ids_host[j] - rows.id_base);
+        memcpy(in.data() + kExExclAt + j, &r, sizeof r);
+    }
+    if (nvec_pos) memcpy(in.data() + kExTableAt, vec_host, (size_t)nvec_pos * dim * sizeof(float));
+    if (nvec_neg)
+        memcpy(in.data() + kExTableAt + (size_t)c.npos() * dim, vec_host + (size_t)nvec_pos * dim, (size_t)nvec_neg * dim * sizeof(float));
+    int rc = hc.upload(allow_bits_host, ix->q_raw, (const float*)in.data(), in.size(), (size_t)k, S_host ? &ix->ex_s : nullptr);
+    if (rc == CSS_OK)
+        rc = search_examples_enqueue(ix, rows, ix->q_raw.p, c, k, gamma, normalize_vec, nexcl, hc.d_out, hc.i_out,
+                                     reinterpret_cast<float*>(hc.g_out), ix->stream);
     return hc.finish(rc, D_host, I_host, reinterpret_cast<int32_t*>(S_host));   // (S rides in the 4-byte column)
 }
 

@@ -211,6 +211,58 @@ def mmr_select(S, I, X, k: int, lam: float, metric: int) -> Tuple[np.ndarray, np
     return Do, Io
 
 
+MAX_EXAMPLES = nat.MAX_EXAMPLES
+MAX_EXAMPLES_K = nat.MAX_EXAMPLES_K
+
+
+def fuse_example_scores(Spos, Sneg, gamma, metric: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The fusion rule of ``search_examples`` (the library's ``k_scan_examples``), stated in numpy.  ``Spos`` is
+    ``[npos, n]`` and ``Sneg`` ``[nneg, n]`` (``nneg`` may be 0): the float32 scores of ``n`` rows against the positive
+    and the negative examples -- inner products, or squared L2 distances.  Returns ``(F[n], P[n])`` in float32 with
+    ``P = max(Spos)`` and ``N = max(Sneg)`` over the examples (L2: ``min``), and ``F = P`` without negatives, otherwise
+    ``F = fma(-gamma, N, P)`` with ``np.float32`` fma semantics: the product ``gamma * N`` is NOT rounded before the
+    subtraction, so the float64 expression ``P - gamma * N`` (exact for float32 operands up to its own rounding) is
+    rounded ONCE to float32.  Larger ``F`` is better for the inner product, smaller for L2.  (The sharded index and
+    the CPU doubles of the tests fuse with this.)"""
+    Spos = np.asarray(Spos, np.float32)
+    Sneg = np.asarray(Sneg, np.float32)
+    if Spos.ndim != 2 or Spos.shape[0] < 1:
+        raise ValueError(f"fuse_example_scores: Spos must be [npos >= 1, n], got shape {Spos.shape}")
+    ext = np.max if metric == METRIC_INNER_PRODUCT else np.min
+    P = ext(Spos, axis=0).astype(np.float32)
+    if Sneg.size == 0 and (Sneg.ndim < 2 or Sneg.shape[0] == 0):
+        return P.copy(), P
+    if Sneg.ndim != 2 or Sneg.shape[1] != Spos.shape[1]:
+        raise ValueError(f"fuse_example_scores: Sneg must be [nneg, {Spos.shape[1]}], got shape {Sneg.shape}")
+    N = ext(Sneg, axis=0).astype(np.float32)
+    # a float32 product is exact in float64, and the sum of it and a float32 is rounded once more there: double
+    # rounding differs from the fma only on ties of the 53-bit sum, which float32 operands of these sizes do not reach
+    F = (P.astype(np.float64) - np.float64(np.float32(gamma)) * N.astype(np.float64)).astype(np.float32)
+    return F, P
+
+
+def example_vectors(v, d: int, what: str = "search_examples") -> np.ndarray:
+    """Example vectors of ``search_examples`` -> contiguous ``[n, d]`` float32; ``None`` and anything empty are no examples."""
+    if v is None or np.size(v) == 0:
+        return np.zeros((0, d), dtype=np.float32)
+    return _as_f32_2d(v, d, what)
+
+
+def example_args(k, gamma, npos: int, m: int, what: str = "search_examples") -> Tuple[int, float]:
+    """The argument rules of ``search_examples`` (``css_index_search_examples``): ``1 <= k <= 128``, ``gamma`` finite
+    and ``>= 0``, at least one positive, at most 16 examples; anything else raises ``ValueError``."""
+    k, gamma = int(k), float(gamma)
+    if k < 1 or k > MAX_EXAMPLES_K:
+        raise ValueError(f"{what}: k={k} outside [1, {MAX_EXAMPLES_K}]")
+    if not np.isfinite(gamma) or gamma < 0.0:
+        raise ValueError(f"{what}: gamma={gamma} must be finite and >= 0")
+    if npos < 1:
+        raise ValueError(f"{what}: no positive example")
+    if m > MAX_EXAMPLES:
+        raise ValueError(f"{what}: {m} examples, at most {MAX_EXAMPLES}")
+    return k, gamma
+
+
 class IndexFlat:
     """Exact brute-force index in HBM (``faiss.IndexFlat`` semantics)."""
 
@@ -440,6 +492,36 @@ class IndexFlat:
             raise ValueError(f"weight={weight} is not finite")
         self._handle()   # (a freed index raises even without queries)
         return self._topk(nat.lib().css_index_search_prior, a, k, (weight, 1 if normalize else 0), allow, third=np.float32)
+
+    # -- search by examples ---------------------------------------------------
+    def search_examples(self, pos=None, neg=None, pos_ids=(), neg_ids=(), k: int = 10, gamma: float = 0.5,
+                        normalize: bool = False, exclude_ids: bool = True,
+                        allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """"More like these, and not like those" (``css_index_search_examples``): the ``k`` best allowed rows under
+        ``best positive score - gamma * best negative score`` for ONE request of up to 16 examples.  ``pos`` / ``neg``
+        are example vectors (``[n, d]`` or ``[d]``; ``normalize``: ``x / (||x|| + 1e-8)``), ``pos_ids`` / ``neg_ids``
+        stored rows by global id, taken as they lie in HBM.  At least one positive.  Returns
+        ``(D[k], I[k], S[k] float32)``: the fused value (``fuse_example_scores`` states it), the global id and the RAW best
+        positive score, best first, ties to the lower id, padded like ``search`` (``S`` like ``D``).  Exact over ALL
+        allowed rows from an fp32 sweep of the fp32 rows, whatever the search mode -- not a re-rank of a fetched list.
+        ``exclude_ids``: rows named as id examples are never returned (copies under other ids are).  ``allow`` applies to
+        the answer, not to the examples.  ``gamma`` (finite, ``>= 0``) defaults to 0.5 as an interface default, not a
+        measurement; ``1 <= k <= 128``."""
+        what = "search_examples"
+        vp, vn = example_vectors(pos, self.d, what), example_vectors(neg, self.d, what)
+        ip, ineg = ids_as_int64(pos_ids, what), ids_as_int64(neg_ids, what)
+        k, gamma = example_args(k, gamma, vp.shape[0] + ip.shape[0], vp.shape[0] + vn.shape[0] + ip.shape[0] + ineg.shape[0])
+        h = self._handle()
+        # (one kind only is the usual request: no copy then)
+        vec = vp if not vn.shape[0] else vn if not vp.shape[0] else np.concatenate([vp, vn], axis=0)
+        ids = ip if not ineg.shape[0] else ineg if not ip.shape[0] else np.concatenate([ip, ineg])
+        D, I, S = np.empty(k, dtype=np.float32), np.empty(k, dtype=np.int64), np.empty(k, dtype=np.float32)
+        bits, bits_ptr = self._allow_bits(allow)
+        nat.check(nat.lib().css_index_search_examples(
+            h, vec.ctypes.data if vec.shape[0] else None, vp.shape[0], vn.shape[0],
+            ids.ctypes.data if ids.shape[0] else None, ip.shape[0], ineg.shape[0], k, gamma, 1 if normalize else 0,
+            1 if exclude_ids else 0, bits_ptr, D.ctypes.data, I.ctypes.data, S.ctypes.data))
+        return D, I, S
 
     # -- diversified search (MMR) --------------------------------------------
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False,

@@ -448,6 +448,70 @@ class ShardedFlatIndex:
             Do[j], Io[j], So[j] = Dg[j][order], Ig[j][order], Sg[j][order]
         return Do, Io, So
 
+    # -- search by examples ------------------------------------------------------------------------------------
+    def _local_ids(self, global_ids: np.ndarray) -> np.ndarray:
+        """Global ids -> local row numbers through the segment table (one rank: every id is owned)."""
+        out = np.full(global_ids.shape, -1, dtype=np.int64)
+        for l0, g0, n in self.segments:
+            own = (global_ids >= g0) & (global_ids < g0 + n)
+            out[own] = global_ids[own] - g0 + l0
+        return out
+
+    def search_examples(self, pos=None, neg=None, pos_ids=(), neg_ids=(), k: int = 10, gamma: float = 0.5,
+                        normalize: bool = False, exclude_ids: bool = True, allow=None):
+        """``IndexFlat.search_examples`` over the shards (collective: every rank passes the same arguments):
+        ``(D[k], I[k], S[k])`` with global ids on every rank; ``pos_ids`` / ``neg_ids`` are GLOBAL row ids.  The id
+        examples become vectors by the all-reduce of ``search_by_ids`` (the owning shard supplies the stored row), the
+        vector examples are normalised on the host where ``normalize`` is set, and every rank runs the local call for
+        ``k + nids`` rows with EVERY example passed as a vector and nothing excluded.  ONE all-gather moves the 16-byte
+        ``[id | D | S]`` records; every rank sorts by ``(D, id)``, drops the example ids (``exclude_ids``) and keeps
+        ``k``.  Exact: a row of the global answer is among the best ``k + nids`` of its shard.  ``k + nids <= 128``.
+        The host normalisation divides in float32 like the device does but sums the squares in another order, so
+        with ``normalize`` the last bits of ``D`` and ``S`` can differ from the single index.  With one rank the whole
+        call is the local one, ids and exclusion on the device.  An id outside ``[0, ntotal_global)`` raises
+        ``ValueError`` on every rank, before any collective."""
+        from .flat_index import MAX_EXAMPLES_K, example_args, example_vectors, ids_as_int64
+
+        what = "search_examples"
+        vp, vn = example_vectors(pos, self.d, what), example_vectors(neg, self.d, what)
+        ip, ineg = ids_as_int64(pos_ids, what), ids_as_int64(neg_ids, what)
+        nids = ip.shape[0] + ineg.shape[0]
+        k, gamma = example_args(k, gamma, vp.shape[0] + ip.shape[0], vp.shape[0] + vn.shape[0] + nids)
+        ids = np.concatenate([ip, ineg])
+        bad = ids[(ids < 0) | (ids >= self.ntotal_global)]
+        if bad.size:
+            raise ValueError(f"search_examples: id {int(bad[0])} outside [0, {self.ntotal_global})")
+        if self._single():
+            D, I, S = self.local.search_examples(vp, vn, self._local_ids(ip), self._local_ids(ineg), k=k, gamma=gamma,
+                                                 normalize=normalize, exclude_ids=exclude_ids,
+                                                 allow=self._local_allow(allow))
+            return D, np.ascontiguousarray(self._to_global_np(I)), S
+        drop = ids if exclude_ids else ids[:0]
+        kk = k + drop.shape[0]
+        if kk > MAX_EXAMPLES_K:
+            raise ValueError(f"search_examples: k + id examples = {kk} beyond {MAX_EXAMPLES_K}")
+        if normalize:
+            unit = lambda v: (v / (np.sqrt((v * v).sum(axis=1, dtype=np.float32, keepdims=True))
+                                   + np.float32(1e-8))).astype(np.float32)
+            vp, vn = unit(vp), unit(vn)
+        rows = self._owned_rows(ids)
+        D, I, S = self.local.search_examples(np.concatenate([vp, rows[:ip.shape[0]]]), np.concatenate([vn, rows[ip.shape[0]:]]),
+                                             k=kk, gamma=gamma, normalize=False, exclude_ids=False,
+                                             allow=self._local_allow(allow))
+        I = np.ascontiguousarray(self._to_global_np(np.asarray(I, dtype=np.int64)))
+        send = np.empty(16 * kk, dtype=np.uint8)                     # [kk int64 ids][kk float32 D][kk float32 S]
+        send[:8 * kk] = I.view(np.uint8)
+        send[8 * kk:12 * kk] = np.ascontiguousarray(D, dtype=np.float32).view(np.uint8)
+        send[12 * kk:] = np.ascontiguousarray(S, dtype=np.float32).view(np.uint8)
+        recv = self._all_gather_host(send)
+        Ig = np.concatenate([recv[r, :8 * kk].view(np.int64) for r in range(self.world)])
+        Dg = np.concatenate([recv[r, 8 * kk:12 * kk].view(np.float32) for r in range(self.world)])
+        Sg = np.concatenate([recv[r, 12 * kk:].view(np.float32) for r in range(self.world)])
+        keep = ~np.isin(Ig, drop)
+        Ig, Dg, Sg = Ig[keep], Dg[keep], Sg[keep]
+        order = self._best_first(Dg, Ig, Ig < 0)[:k]   # best first by (fused value, id), pads last
+        return Dg[order], Ig[order], Sg[order]
+
     # -- diversified search ------------------------------------------------------------------------------------
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
         """``IndexFlat.search_diverse`` over the shards (collective: every rank passes the same arguments): ``(D, I)``
@@ -569,6 +633,11 @@ class ShardedIndexFacade:
 
     def search_prior(self, q, k: int, weight: float, normalize: bool = False, allow=None):
         return self.sh.search_prior(np.asarray(q, dtype=np.float32), int(k), float(weight), normalize=normalize, allow=allow)
+
+    def search_examples(self, pos=None, neg=None, pos_ids=(), neg_ids=(), k: int = 10, gamma: float = 0.5,
+                        normalize: bool = False, exclude_ids: bool = True, allow=None):
+        return self.sh.search_examples(pos, neg, pos_ids, neg_ids, k=int(k), gamma=float(gamma), normalize=normalize,
+                                       exclude_ids=exclude_ids, allow=allow)
 
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
         return self.sh.search_diverse(np.asarray(q, dtype=np.float32), int(k), lam=lam, fetch=fetch, normalize=normalize,

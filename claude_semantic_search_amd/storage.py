@@ -667,6 +667,48 @@ class HybridStorage:
             _, ids, sims = self.faiss_index.search_prior(q, k, w_now, normalize=self.config.normalize_embeddings, allow=allow)
             return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
 
+    def search_like(self, liked, disliked=(), query_embedding=None, config: Optional[SearchConfig] = None,
+                    filters: Optional[Dict[str, Any]] = None, gamma: float = 0.5) -> List[SearchResult]:
+        """"More like these chunks, and not like those": ``top_k`` chunks ranked by
+        ``best similarity to a liked example - gamma * best similarity to a disliked one`` (an L2 storage: nearest
+        liked distance minus ``gamma`` times nearest disliked distance, smaller first).  ``liked`` / ``disliked`` are
+        chunk ids -- their STORED rows are the examples, read where they lie in HBM -- and ``query_embedding``, if
+        given, is one more positive vector (normalised like the query of ``search()``).  The ranking runs inside the
+        index over ALL allowed rows (``IndexFlat.search_examples``), not over an over-fetched list.  Results come in
+        FUSED order, each with its RAW best-liked similarity, to which ``similarity_threshold`` applies (as in
+        ``search_recent``).  The example chunks are never returned.
+
+        Tombstones always go into the allow mask.  With ``filter_pushdown`` the filters go there too and ``k = top_k``
+        rows are fetched; without it and with filters, ``k = min(max(top_k, max_results), 128)`` rows are fetched and
+        filtered in rank order.  No positive at all (no liked chunk and no query) raises ``ValueError``, as do more
+        than 16 examples and a ``gamma`` that is negative or not finite; an unknown or deleted chunk id raises
+        ``KeyError``; an empty index gives ``[]``; an index object without ``search_examples`` raises
+        ``NotImplementedError``."""
+        liked = [liked] if isinstance(liked, str) else list(liked)
+        disliked = [disliked] if isinstance(disliked, str) else list(disliked)
+        nvec = 0 if query_embedding is None else 1
+        _, g = fi.example_args(1, gamma, len(liked) + nvec, len(liked) + len(disliked) + nvec, "search_like")
+        if self.faiss_index and not hasattr(self.faiss_index, "search_examples"):
+            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no search by examples (search_examples)")
+        with self._lock:
+            frame = self._search_frame(config, query_embedding)
+            if frame is None or frame[0].top_k <= 0:
+                return []
+            cfg, ntotal, q = frame
+            fids = []
+            for chunk_id in liked + disliked:
+                fid = self.chunk_id_to_faiss_id.get(chunk_id)
+                if fid is None or fid >= ntotal or not self._get_chunk_data(chunk_id):
+                    raise KeyError(chunk_id)
+                fids.append(fid)
+            allow = self._allow_for(filters, ntotal, tombstones_always=True)
+            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
+            k = max(1, min(k, fi.MAX_EXAMPLES_K))
+            _, ids, sims = self.faiss_index.search_examples(
+                pos=q, pos_ids=fids[:len(liked)], neg_ids=fids[len(liked):], k=k, gamma=g,
+                normalize=self.config.normalize_embeddings, exclude_ids=True, allow=allow)
+            return self._results_in_rank_order(sims.tolist(), ids.tolist(), cfg, filters)
+
     @staticmethod
     def _make_result(chunk_id: str, score: float, data: Dict[str, Any], cfg: SearchConfig) -> SearchResult:
         res = SearchResult(chunk_id=chunk_id, similarity=float(score))

@@ -283,6 +283,45 @@ int css_index_search_prior(css_index* ix, const float* q_host, int64_t nq, int k
                            const uint32_t* allow_bits_host, float* D_host, int64_t* I_host,
                            float* S_host /* may be NULL */);
 
+/* Search by examples (the "recommend" / "more like these" / positive-negative-examples call of vector stores): the k
+ * best rows for a SET of example vectors, some of them to be avoided -- "more like these three chunks, and not like
+ * that one", "anything that matches any of these phrasings".  One request per call.
+ *  - Examples.  m = npos + nneg of them, 1 <= npos, m <= CSS_MAX_EXAMPLES.  Each is a caller's vector ([d] fp32;
+ *    normalize_vec != 0: x / (||x|| + 1e-8) as in css_index_search) or a stored row named by its GLOBAL id, taken as it
+ *    lies in device memory, never normalised, gathered on the device.  vec_host holds the nvec_pos positive vectors and
+ *    then the nvec_neg negative ones, ids_host the nid_pos positive ids and then the nid_neg negative ones (either may
+ *    be NULL when it holds nothing).  Order of the examples: positive vectors, positive ids, negative vectors, negative
+ *    ids.
+ *  - The value.  With s_j the score of a row against example j (the exact fp32 score of the fp32 rows, in the
+ *    arithmetic of CSS_SEARCH_EXACT_FP32: the inner product, or the squared L2 distance):
+ *        inner product   P = max over positives of s_j, N = max over negatives of s_j     larger f is better
+ *        squared L2      P = min over positives of s_j, N = min over negatives of s_j     smaller f is better; f may be < 0
+ *        f = P when nneg == 0, else f = fmaf(-gamma, N, P)
+ *    The k best ALLOWED rows under f, exact over all rows (the fused value is the key of the sweep: a row's value
+ *    under the negatives can sit anywhere below an over-fetched list, and a maximum of scores is not the score of a
+ *    combined vector).  D = f, best first, ties to the lower id; I = global ids; S (may be NULL) = P, the raw best
+ *    positive score, so that similarity thresholds keep their meaning: D[t] == S[t] bit for bit when nneg == 0, and
+ *    D[t] == fmaf(-gamma, N, S[t]) otherwise.  All three are [k].  Padding as in css_index_search: I = -1 and
+ *    D = S = -FLT_MAX (inner product) / +FLT_MAX (L2).
+ *  - exclude_ids != 0: the rows named as id examples (positive and negative) are never returned.  Copies of them under
+ *    other ids are ordinary results; vector examples exclude nothing.  allow_bits_host applies to the answer, not to
+ *    the examples: an example id need not be allowed itself.
+ *  - CSS_ERR_INVALID, checked on the host before anything is enqueued (the index stays usable): an id outside the index
+ *    (the message names it), no positive, m > CSS_MAX_EXAMPLES, k outside [1, 128], a NaN, infinite or negative gamma,
+ *    more than 2^32 - 2 rows, and an example table beyond the sweep's 64 KiB of LDS (16 examples: d <= 960; 8: d <= 1984).
+ *    An empty index gives fully padded output (and knows no id).
+ *  - Nothing depends on the reduced-precision row copies or on the search mode.  One positive vector and no negative is
+ *    css_index_search under CSS_SEARCH_EXACT_FP32 bit for bit; gamma == 0 is the call without its negatives.
+ *  - On the device: the example table is assembled from one upload (the vectors through the query preparation, the id
+ *    examples gathered row to row), ONE sweep of the fp32 rows forms the m scores of every row and keeps one list, and
+ *    one small launch behind the merge re-forms P of the k returned rows with the sweep's summation order (skipped when
+ *    S_host is NULL).  One wait. */
+#define CSS_MAX_EXAMPLES 16
+int css_index_search_examples(css_index* ix, const float* vec_host, int nvec_pos, int nvec_neg, const int64_t* ids_host,
+                              int nid_pos, int nid_neg, int k, float gamma, int normalize_vec, int exclude_ids,
+                              const uint32_t* allow_bits_host, float* D_host, int64_t* I_host,
+                              float* S_host /* may be NULL */);
+
 /* Diversified search (maximal marginal relevance, MMR; langchain's max_marginal_relevance_search, the "diversity"
  * option of vector stores): k rows picked greedily from a pool of the best rows, each pick trading its score against
  * its similarity to the rows already picked -- so near-copies of one passage do not fill the answer.  Per query, with
