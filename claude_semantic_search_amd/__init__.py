@@ -19,6 +19,7 @@ _LAZY = {
     "SearchResult": ".storage",
     "HybridStorage": ".storage",
     "recency_priors": ".storage",
+    "Topic": ".storage",
     "EmbeddingConfig": ".embeddings",
     "EmbeddingStats": ".embeddings",
     "EmbeddingGenerator": ".embeddings",
@@ -26,6 +27,10 @@ _LAZY = {
     "IndexFlat": ".flat_index",
     "IndexFlatIP": ".flat_index",
     "IndexFlatL2": ".flat_index",
+    "Kmeans": ".flat_index",
+    "KmeansResult": ".flat_index",
+    "KmeansStep": ".flat_index",
+    "run_kmeans": ".flat_index",
     "MpnetEncoder": ".mpnet_encoder",
     "ShardedFlatIndex": ".sharded",
     "GPUCapability": ".gpu_utils",

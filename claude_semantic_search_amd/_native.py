@@ -30,6 +30,7 @@ MAX_DIVERSE_FETCH = 128   # css_index_search_diverse: the largest candidate pool
 MAX_PRIOR_K = 128   # css_index_search_prior: the same list size
 MAX_EXAMPLES = 16   # include/css_hip.h CSS_MAX_EXAMPLES
 MAX_EXAMPLES_K = 128   # css_index_search_examples: the same list size
+MAX_CENTROIDS = 4096   # include/css_hip.h CSS_MAX_CENTROIDS
 
 
 class CssError(RuntimeError):
@@ -120,6 +121,9 @@ PROTOTYPES = {
                                        c_void_p]),
     "css_index_search_examples": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_int,
                                           c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_index_export_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "css_index_kmeans_step": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      POINTER(c_int), POINTER(c_int), c_void_p, c_void_p]),
     "css_index_search_diverse": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
                                          c_void_p]),
     "css_index_search_diverse_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_void_p,

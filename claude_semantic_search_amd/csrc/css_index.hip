@@ -37,6 +37,8 @@
 //   k_scan_examples,   css_index_search_examples: the exact fp32 sweep ranked by best positive - gamma * best negative
 //   k_example_scores   score over up to 16 example vectors, ONE list; the best positive scores of the k returned rows
 //                      re-formed behind the merge (css_knn_examples.h).   HBM bound
+//   k_kmeans_assign,   css_index_kmeans_step: one Lloyd step -- rows x centroids on the fp32-input MFMA, member lists,
+//   k_kmeans_sum       fixed-point int64 sums (css_kmeans.h)
 //   k_mmr_select       css_index_search_diverse: k of a pool of the best rows picked greedily by maximal marginal
 //                      relevance, similarities from the stored fp32 rows (css_knn_diverse.h)
 //
@@ -180,6 +182,13 @@ struct css_index {
     DevBuf<int32_t> pri_s;              // entries
     // css_index_search_examples: S = the best positive score [k] of the returned rows, the same 4-byte column
     DevBuf<int32_t> ex_s;               // entries
+    // css_index_kmeans_step (css_kmeans.h): the uploaded centroids [nc, dim]; their padded table [ncpad][dpad] with the
+    // squared norms [ncpad] behind it; assignment and distance of every row; the member lists [ntotal] with
+    // [nc + 1 offsets | nc + 1 block numbers | nc cursors]; and [KM_HDR words | nc counts | nc * dim sums] of int64
+    DevBuf<float> km_craw, km_ctab, km_dist;
+    DevBuf<int32_t> km_assign;
+    DevBuf<uint32_t> km_members, km_off;
+    DevBuf<long long> km_out;
     // rows written by css_index_add_dev / _add_synthetic on the CALLER's stream: searches, reallocation and
     // export wait for this event before touching rows, norms or maxn2
     hipEvent_t ingest_ev = nullptr;
@@ -2742,6 +2751,9 @@ int search_chunk_prior(css_index* ix, const Rows& rows, int q0, int nqc, int k, 
     return CSS_OK;
 }
 
+// ------------------------------------------------------------------ k-means step (css_kmeans.h)
+#include "css_kmeans.h"
+
 // ------------------------------------------------------------------ search by examples (css_knn_examples.h)
 #include "css_knn_examples.h"
 
@@ -4403,6 +4415,147 @@ int css_range_result_read(const css_range_result* r, float* D_host, int64_t* I_h
 
 int css_range_result_free(css_range_result* r) {
     delete r;
+    return CSS_OK;
+}
+
+// ------------------------------------------------------------------ rows by id, k-means step
+int css_index_export_rows(css_index* ix, const int64_t* ids_host, int64_t n, float* x_out_host) {
+    CSS_REQUIRE(ix, "css_index_export_rows: NULL index");
+    CSS_REQUIRE(n >= 0 && n < (1 << 24), "css_index_export_rows: n=%lld out of range", (long long)n);
+    if (n == 0) return CSS_OK;
+    CSS_REQUIRE(ids_host && x_out_host, "css_index_export_rows: NULL buffer");
+    HostCall hc(ix);
+    const Rows& rows = hc.rows;   // (the id range check comes before anything is enqueued)
+    for (int64_t j = 0; j < n; ++j)
+        CSS_REQUIRE(ids_host[j] >= rows.id_base && ids_host[j] - rows.id_base < rows.n,
+                    "css_index_export_rows: id %lld (entry %lld) outside [%lld, %lld)", (long long)ids_host[j], (long long)j,
+                    (long long)rows.id_base, (long long)(rows.id_base + rows.n));
+    const hipStream_t st = ix->stream;
+    int rc = hc.upload(nullptr, ix->rowq_ids, ids_host, (size_t)n);
+    if (rc == CSS_OK) rc = [&]() -> int {
+        WsTurn turn(ix, st);
+        if (turn.rc != CSS_OK) return turn.rc;
+        if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+        int r;
+        if ((r = ix->rowq.grow((size_t)n * ix->dim)) != CSS_OK) return r;
+        if ((r = ix->rowq_flag.grow((size_t)n)) != CSS_OK) return r;
+        hipLaunchKernelGGL(k_gather_queries, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, rows.xb,
+                           (const int64_t*)ix->rowq_ids.p, ix->rowq.p, ix->rowq_flag.p, n, rows.n, rows.id_base, ix->dim, ix->dpad);
+        CSS_LAUNCH_CHECK();
+        CSS_HIP_TRY(hipMemcpyAsync(x_out_host, ix->rowq.p, (size_t)n * ix->dim * sizeof(float), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipStreamSynchronize(st));
+        return CSS_OK;
+    }();
+    return hc.wait_if_failed(rc);
+}
+
+namespace {
+// The centroid table, the assignment, the member lists and the sums of one Lloyd step (css_kmeans.h).  Everything is
+// enqueued on `st`; nothing waits for the device.  Caller holds ws_mu and a shared lock on mu.
+int kmeans_step_enqueue(css_index* ix, const Rows& rows, const float* craw_dev, int nc, int fx_shift, hipStream_t st) {
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    // rows appended on another stream must have landed (their norms and the running maximum with them)
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    const int nctiles = (nc + MF_BM - 1) / MF_BM, ncpad = nctiles * MF_BM;
+    const size_t n1 = (size_t)std::max<int64_t>(rows.n, 1);
+    if ((rc = ix->km_ctab.grow((size_t)ncpad * ix->dpad + ncpad)) != CSS_OK) return rc;
+    if ((rc = ix->km_out.grow((size_t)KM_HDR + nc + (size_t)nc * ix->dim)) != CSS_OK) return rc;
+    if ((rc = ix->km_off.grow((size_t)3 * nc + 2)) != CSS_OK) return rc;
+    if ((rc = ix->km_assign.grow(n1)) != CSS_OK) return rc;
+    if ((rc = ix->km_dist.grow(n1)) != CSS_OK) return rc;
+    if ((rc = ix->km_members.grow(n1)) != CSS_OK) return rc;
+    long long* hdr = ix->km_out.p;
+    unsigned long long* counts = reinterpret_cast<unsigned long long*>(hdr + KM_HDR);
+    unsigned long long* sums = counts + nc;
+    uint32_t *off = ix->km_off.p, *seg = off + nc + 1, *cursor = seg + nc + 1;
+    CSS_HIP_TRY(hipMemsetAsync(hdr, 0, ((size_t)KM_HDR + nc + (size_t)nc * ix->dim) * sizeof(long long), st));
+    hipLaunchKernelGGL(k_kmeans_params, dim3(1), dim3(64), 0, st, (const int*)ix->maxn2.p, rows.n, fx_shift, hdr);
+    CSS_LAUNCH_CHECK();
+    if (rows.n == 0) return CSS_OK;   // zero sums and counts
+    CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "css_index_kmeans_step: %lld rows exceed the 32-bit row numbers of the member lists",
+                (long long)rows.n);
+    CSS_REQUIRE(ix->dpad % MF_BK == 0, "css_index_kmeans_step: internal: dpad=%d is no multiple of %d", ix->dpad, MF_BK);
+    float* ctab = ix->km_ctab.p;
+    float* cn2 = ctab + (size_t)ncpad * ix->dpad;
+    // the table: the row kernel of ingest pads the centroids and forms ||c||^2 in fp32; pad centroids are zero rows
+    // with ||c||^2 = +inf
+    if (ncpad > nc) {
+        CSS_HIP_TRY(hipMemsetAsync(ctab + (size_t)nc * ix->dpad, 0, (size_t)(ncpad - nc) * ix->dpad * sizeof(float), st));
+        hipLaunchKernelGGL(k_fill_int, dim3(1), dim3(128), 0, st, reinterpret_cast<int*>(cn2 + nc), ncpad - nc, 0x7f800000);
+        CSS_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_ingest_rows<false>, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, st, craw_dev, ctab, cn2, (int64_t)nc,
+                       ix->dim, ix->dpad, 0, 0ull, 0ll, (unsigned short*)nullptr, (int*)nullptr, (float*)nullptr,
+                       (unsigned char*)nullptr, (float*)nullptr);
+    CSS_LAUNCH_CHECK();
+    CSS_HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)nc * sizeof(uint32_t), st));
+    {
+        const int64_t ntiles = (rows.n + MF_BN - 1) / MF_BN;
+        const int64_t want = std::min<int64_t>(ntiles, 2 * (int64_t)ix->num_cus);   // two blocks per CU
+        const int64_t tpb = (ntiles + want - 1) / want;
+        const unsigned grid = (unsigned)((ntiles + tpb - 1) / tpb);
+        const size_t lds = (size_t)(2 * MF_BM * MF_BK + 2 * MF_BN * MF_BK + ncpad + nc) * 4;
+        if ((rc = css::ensure_dynamic_lds((const void*)k_kmeans_assign, lds, ix->device)) != CSS_OK) return rc;
+        ProfScope ps("kmeans_assign", st);
+        hipLaunchKernelGGL(k_kmeans_assign, dim3(grid), dim3(256), lds, st, rows.xb, rows.xnorm2, (const float*)ctab,
+                           (const float*)cn2, nc, nctiles, rows.n, ix->dpad, tpb, rows.mask, (const long long*)hdr,
+                           ix->km_assign.p, ix->km_dist.p, counts, reinterpret_cast<unsigned long long*>(hdr));
+        CSS_LAUNCH_CHECK();
+    }
+    {
+        ProfScope ps("kmeans_lists", st);
+        hipLaunchKernelGGL(k_kmeans_offsets, dim3(1), dim3(1024), 0, st, (const unsigned long long*)counts, nc, off, seg);
+        CSS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_kmeans_members, dim3((unsigned)((rows.n + 255) / 256)), dim3(256), 0, st,
+                           (const int32_t*)ix->km_assign.p, rows.n, (const uint32_t*)off, cursor, ix->km_members.p);
+        CSS_LAUNCH_CHECK();
+    }
+    {
+        ProfScope ps("kmeans_sum", st);
+        const unsigned grid = (unsigned)(nc + (rows.n + KM_SEG - 1) / KM_SEG);
+        hipLaunchKernelGGL(k_kmeans_sum, dim3(grid), dim3(256), 0, st, (const float4*)rows.xb, (const uint32_t*)ix->km_members.p,
+                           (const uint32_t*)off, (const uint32_t*)seg, nc, ix->dim, ix->dpad / 4, (const long long*)hdr, sums);
+        CSS_LAUNCH_CHECK();
+    }
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_kmeans_step(css_index* ix, const float* centroids_host, int nc, int fx_shift, const uint32_t* allow_bits_host,
+                          int64_t* sums_host, int64_t* counts_host, int64_t* obj_host, int* fx_shift_used, int* obj_shift_used,
+                          int32_t* assign_host, float* dist_host) {
+    CSS_REQUIRE(ix, "css_index_kmeans_step: NULL index");
+    CSS_REQUIRE(nc >= 2 && nc <= CSS_MAX_CENTROIDS, "css_index_kmeans_step: nc=%d outside [2, %d]", nc, CSS_MAX_CENTROIDS);
+    CSS_REQUIRE(centroids_host && sums_host && counts_host && obj_host, "css_index_kmeans_step: NULL buffer");
+    CSS_REQUIRE(fx_shift < 1024, "css_index_kmeans_step: fx_shift=%d out of range", fx_shift);
+    for (size_t i = 0, m = (size_t)nc * ix->dim; i < m; ++i)
+        CSS_REQUIRE(std::isfinite(centroids_host[i]), "css_index_kmeans_step: centroid %lld has a %s component (column %lld)",
+                    (long long)(i / ix->dim), std::isnan(centroids_host[i]) ? "NaN" : "infinite", (long long)(i % ix->dim));
+    HostCall hc(ix);
+    const hipStream_t st = ix->stream;
+    const int64_t n = hc.rows.n;
+    long long h[KM_HDR] = {0};
+    int rc = hc.upload(allow_bits_host, ix->km_craw, centroids_host, (size_t)nc * ix->dim);
+    if (rc == CSS_OK) rc = kmeans_step_enqueue(ix, hc.rows, ix->km_craw.p, nc, fx_shift, st);
+    if (rc == CSS_OK) rc = [&]() -> int {   // one wait: header, counts, sums and the per-row arrays the caller asked for
+        const long long* out = ix->km_out.p;
+        CSS_HIP_TRY(hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipMemcpyAsync(counts_host, out + KM_HDR, (size_t)nc * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipMemcpyAsync(sums_host, out + KM_HDR + nc, (size_t)nc * ix->dim * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        if (assign_host && n) CSS_HIP_TRY(hipMemcpyAsync(assign_host, ix->km_assign.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (dist_host && n) CSS_HIP_TRY(hipMemcpyAsync(dist_host, ix->km_dist.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipStreamSynchronize(st));
+        return CSS_OK;
+    }();
+    if (rc != CSS_OK) return hc.wait_if_failed(rc);
+    // an imposed shift that this index's own row count and maximum cannot hold: the sums may have wrapped
+    CSS_REQUIRE(h[3] != 0, "css_index_kmeans_step: fx_shift=%d is too large for %lld rows with this index's largest norm: "
+                "the largest safe value is %lld", fx_shift, (long long)n, h[4]);
+    *obj_host = (int64_t)h[0];
+    if (fx_shift_used) *fx_shift_used = (int)h[1];
+    if (obj_shift_used) *obj_shift_used = (int)h[2];
     return CSS_OK;
 }
 

@@ -12,8 +12,9 @@ The reference touches exactly these faiss members: the classes
 from __future__ import annotations
 
 import ctypes
+import math
 import struct
-from typing import Optional, Tuple
+from typing import Callable, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -261,6 +262,160 @@ def example_args(k, gamma, npos: int, m: int, what: str = "search_examples") -> 
     if m > MAX_EXAMPLES:
         raise ValueError(f"{what}: {m} examples, at most {MAX_EXAMPLES}")
     return k, gamma
+
+MAX_CENTROIDS = nat.MAX_CENTROIDS
+
+
+class KmeansStep(NamedTuple):
+    """What one Lloyd step returns (``css_index_kmeans_step``): the fixed-point sums ``[nc, d]`` and member counts
+    ``[nc]`` (int64), the integer objective, the two shifts ``s`` and ``t``, and -- where asked for -- the assignment
+    (int32, ``-1`` = row not allowed) and squared distance (float32) of every row."""
+    sums: np.ndarray
+    counts: np.ndarray
+    obj: int
+    fx_shift: int
+    obj_shift: int
+    assign: Optional[np.ndarray] = None
+    dist: Optional[np.ndarray] = None
+
+
+class KmeansResult(NamedTuple):
+    """What ``run_kmeans`` returns: the centroids ``[nc, d]`` float32, the final assignment and squared distance of
+    every row (``-1`` / ``0`` for rows not allowed), the cluster sizes, the objective ``obj_int * 2^-t`` of every
+    iteration, the number of iterations run, and per iteration the ``(empty, donor)`` pairs that were split."""
+    centroids: np.ndarray
+    assign: np.ndarray
+    dist: np.ndarray
+    sizes: np.ndarray
+    obj: List[float]
+    iterations: int
+    splits: tuple = ()
+
+
+def kmeans_shift(max_norm2: float, n: int) -> Tuple[int, int, int]:
+    """The shift rule of ``css_index_kmeans_step``, restated: ``(s, e, t)``.  ``ex`` is the exponent ``frexp`` gives the
+    largest squared row norm (0 when that is 0), ``e = ceil(ex / 2)`` so that every ``|x| < 2^e``, ``b`` the bit length
+    of ``max(n, 1) - 1``, ``s = 62 - b - e`` the shift of the sums and ``t = s - e - 2`` that of the objective:
+    ``n * 2^(s + e) <= 2^62``, so no int64 sum can reach ``2^63``."""
+    m = float(np.float32(max_norm2))
+    ex = math.frexp(m)[1] if m > 0.0 else 0
+    e = -((-ex) // 2)
+    b = (max(int(n), 1) - 1).bit_length()
+    s = 62 - b - e
+    return s, e, s - e - 2
+
+
+def _fixed(x, shift: int) -> np.ndarray:
+    """``llrint(x * 2^shift)`` of float32 values as int64: exact scaling in float64, round to nearest even."""
+    return np.rint(np.ldexp(np.asarray(x, dtype=np.float32).astype(np.float64), int(shift))).astype(np.int64)
+
+
+def fixed_point_sums(X, assign, nc: int, s: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The sums of ``css_index_kmeans_step`` stated in numpy: ``sums[c] = sum over assign == c of llrint(X * 2^s)``
+    (int64 ``[nc, d]``) and the member counts (int64 ``[nc]``); rows with ``assign < 0`` count nowhere."""
+    X = np.asarray(X, dtype=np.float32)
+    a = np.asarray(assign).astype(np.int64).reshape(-1)
+    nc = int(nc)
+    sums = np.zeros((nc, X.shape[1] if X.ndim == 2 else 0), dtype=np.int64)
+    live = np.flatnonzero(a >= 0)
+    counts = np.bincount(a[live], minlength=nc).astype(np.int64)
+    if live.size:
+        order = live[np.argsort(a[live], kind="stable")]
+        q = _fixed(X[order], s)
+        starts = np.concatenate(([0], np.cumsum(counts)[:-1]))
+        full = counts > 0
+        sums[full] = np.add.reduceat(q, starts[full], axis=0)
+    return sums, counts
+
+
+def fixed_point_objective(dist, assign, t: int) -> int:
+    """The integer objective of ``css_index_kmeans_step``: ``sum of llrint(dist * 2^t)`` over the assigned rows."""
+    a = np.asarray(assign).reshape(-1)
+    return int(_fixed(np.asarray(dist, dtype=np.float32).reshape(-1)[a >= 0], t).sum(dtype=np.int64))
+
+
+def lloyd_update(sums, counts, s: int, prev, spherical: bool = False) -> Tuple[np.ndarray, List[Tuple[int, int]]]:
+    """The centroid update of ``run_kmeans``: ``(centroids float32 [nc, d], [(empty, donor), ...])``.  ``sums`` goes to
+    float64, times ``2^-s``, divided by the count, and is rounded to float32 ONCE; ``spherical`` divides by the float64
+    norm in front of that rounding (a zero vector stays zero).  An empty cluster is refilled faiss' way, made
+    deterministic: empties in ascending order, the donor is the largest cluster (ties to the lowest index), the empty
+    one takes ``donor * (1 + 1/1024)``, the donor becomes ``donor * (1 - 1/1024)`` (float32 products), and the donor's
+    count is halved between the two.  With no member anywhere the previous centroids are kept."""
+    sums = np.asarray(sums, dtype=np.int64)
+    cw = np.asarray(counts, dtype=np.int64).copy()
+    out = np.array(prev, dtype=np.float32, copy=True).reshape(sums.shape)
+    full = cw > 0
+    mean = np.ldexp(sums[full].astype(np.float64), -int(s)) / cw[full].astype(np.float64)[:, None]
+    if spherical:
+        nrm = np.sqrt((mean * mean).sum(axis=1))
+        mean[nrm > 0] /= nrm[nrm > 0][:, None]
+    out[full] = mean.astype(np.float32)
+    split: List[Tuple[int, int]] = []
+    up, down = np.float32(1.0 + 1.0 / 1024.0), np.float32(1.0 - 1.0 / 1024.0)
+    for c in np.flatnonzero(~full):
+        donor = int(np.argmax(cw))   # (the first maximum: the lowest index)
+        if cw[donor] <= 0:
+            break
+        out[c] = out[donor] * up
+        out[donor] = out[donor] * down
+        cw[c] = cw[donor] // 2
+        cw[donor] -= cw[c]
+        split.append((int(c), donor))
+    return out, split
+
+
+def kmeans_init_ids(allowed_rows, nc: int, seed: int) -> np.ndarray:
+    """The rows the initial centroids are copied from: ``nc`` of ``allowed_rows`` without replacement, by
+    ``np.random.default_rng(seed)``.  Fewer than ``nc`` allowed rows raise ``ValueError``."""
+    rows = np.asarray(allowed_rows, dtype=np.int64).reshape(-1)
+    if rows.shape[0] < int(nc):
+        raise ValueError(f"kmeans: {rows.shape[0]} allowed rows for {int(nc)} centroids")
+    return np.ascontiguousarray(np.random.default_rng(seed).choice(rows, int(nc), replace=False), dtype=np.int64)
+
+
+def run_kmeans(step: Callable, gather_rows: Callable, nc: int, niter: int = 20, seed: int = 0, init=None,
+               spherical: bool = False, init_rows=None, train_allow=None, allow=None) -> KmeansResult:
+    """THE Lloyd loop (the single index, the sharded index and the CPU doubles of the tests all run this one).
+    ``step(centroids, allow, want)`` is one step over the rows -- it returns a ``KmeansStep``, with ``assign`` and
+    ``dist`` when ``want`` -- and ``gather_rows(ids)`` returns stored rows by id.  Initial centroids are ``init``
+    (``[nc, d]``) or the rows ``kmeans_init_ids(init_rows, nc, seed)``.  Then up to ``niter`` times: a step under
+    ``train_allow``, ``lloyd_update``; the loop stops early when the new centroids are bit-equal to the old ones (the
+    arithmetic is deterministic, so that is a fixpoint).  A final step under ``allow`` assigns every allowed row."""
+    nc = int(nc)
+    if nc < 2 or nc > MAX_CENTROIDS:
+        raise ValueError(f"kmeans: nc={nc} outside [2, {MAX_CENTROIDS}]")
+    if init is not None:
+        cent = np.array(init, dtype=np.float32, copy=True)
+        if cent.ndim != 2 or cent.shape[0] != nc:
+            raise ValueError(f"kmeans: init must be [{nc}, d], got shape {cent.shape}")
+    else:
+        cent = np.array(gather_rows(kmeans_init_ids(init_rows, nc, seed)), dtype=np.float32, copy=True)
+    obj: List[float] = []
+    splits = []
+    iterations = 0
+    for _ in range(int(niter)):
+        st = step(cent, train_allow, False)
+        obj.append(math.ldexp(float(st.obj), -st.obj_shift))
+        new, split = lloyd_update(st.sums, st.counts, st.fx_shift, cent, spherical)
+        splits.append(tuple(split))
+        iterations += 1
+        same = new.tobytes() == cent.tobytes()
+        cent = new
+        if same:
+            break
+    last = step(cent, allow, True)
+    return KmeansResult(cent, last.assign, last.dist, np.asarray(last.counts, dtype=np.int64), obj, iterations, tuple(splits))
+
+
+def kmeans_train_mask(allowed_rows: np.ndarray, ntotal: int, nc: int, max_points_per_centroid: int, seed: int):
+    """The training subset of ``kmeans(max_points_per_centroid=...)`` as a boolean mask over ``ntotal`` rows: a seeded
+    random ``nc * max_points_per_centroid`` of the allowed rows; ``None`` when no cut applies."""
+    cap = int(nc) * int(max_points_per_centroid)
+    if max_points_per_centroid <= 0 or allowed_rows.shape[0] <= cap:
+        return None
+    mask = np.zeros(int(ntotal), dtype=np.bool_)
+    mask[np.random.default_rng([int(seed), 1]).choice(allowed_rows, cap, replace=False)] = True
+    return mask
 
 
 class IndexFlat:
@@ -624,6 +779,7 @@ class IndexFlat:
 
     def set_id_base(self, base: int) -> None:
         nat.check(nat.lib().css_index_set_id_base(self._handle(), int(base)))
+        self._id_base = int(base)   # (kmeans names its initial rows by global id)
 
     def reconstruct_n(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
         if n is None:
@@ -636,6 +792,60 @@ class IndexFlat:
     def reconstruct(self, i: int) -> np.ndarray:
         return self.reconstruct_n(int(i), 1)[0]
 
+    def reconstruct_batch(self, ids) -> np.ndarray:
+        """``faiss.IndexFlat.reconstruct_batch``: the stored rows of the GLOBAL ``ids`` (``id_base`` included), gathered
+        on the device, as ``[len(ids), d]`` float32; repeated ids are fine, an id outside the index raises."""
+        a = ids_as_int64(ids, "reconstruct_batch")
+        out = np.empty((a.shape[0], self.d), dtype=np.float32)
+        h = self._handle()
+        if a.shape[0]:
+            nat.check(nat.lib().css_index_export_rows(h, a.ctypes.data, a.shape[0], out.ctypes.data))
+        return out
+
+    # -- k-means ---------------------------------------------------------------
+    def kmeans_step(self, centroids, allow=None, fx_shift: Optional[int] = None, want_assign: bool = False,
+                    want_dist: bool = False) -> KmeansStep:
+        """One Lloyd step on the GPU (``css_index_kmeans_step``): every allowed row goes to its nearest centroid
+        (squared L2 whatever the metric, ties to the lower index) and the members of every centroid are summed in
+        fixed point -- ``fixed_point_sums`` and ``kmeans_shift`` state the integers exactly.  ``fx_shift`` imposes
+        the shift of the sums (the sharded index passes the global one).  ``2 <= nc <= 4096``."""
+        c = _as_f32_2d(centroids, self.d, "kmeans_step")
+        nc = c.shape[0]
+        if nc < 2 or nc > MAX_CENTROIDS:
+            raise ValueError(f"kmeans_step: nc={nc} outside [2, {MAX_CENTROIDS}]")
+        h = self._handle()
+        n = self.ntotal
+        sums, counts = np.zeros((nc, self.d), dtype=np.int64), np.zeros(nc, dtype=np.int64)
+        obj = np.zeros(1, dtype=np.int64)
+        assign = np.empty(n, dtype=np.int32) if want_assign else None
+        dist = np.empty(n, dtype=np.float32) if want_dist else None
+        s, t = ctypes.c_int(0), ctypes.c_int(0)
+        bits, bits_ptr = self._allow_bits(allow)
+        nat.check(nat.lib().css_index_kmeans_step(
+            h, c.ctypes.data, nc, -1 if fx_shift is None else int(fx_shift), bits_ptr, sums.ctypes.data, counts.ctypes.data,
+            obj.ctypes.data, ctypes.byref(s), ctypes.byref(t), assign.ctypes.data if want_assign and n else None,
+            dist.ctypes.data if want_dist and n else None))
+        return KmeansStep(sums, counts, int(obj[0]), int(s.value), int(t.value), assign, dist)
+
+    def kmeans(self, nc: int, niter: int = 20, seed: int = 0, init=None, spherical: Optional[bool] = None, allow=None,
+               max_points_per_centroid: int = 0) -> KmeansResult:
+        """k-means over the stored rows (``run_kmeans`` over ``kmeans_step``): ``nc`` centroids from ``init`` or from
+        seeded random allowed rows, up to ``niter`` Lloyd steps, a final step that assigns every allowed row.
+        ``spherical=None`` means "the metric is the inner product": centroids are renormalised.  ``allow`` restricts
+        the rows as in ``search``.  ``max_points_per_centroid > 0`` trains on a seeded random subset of the allowed
+        rows; the final step still assigns all of them.  The same call gives the same bytes."""
+        n = self.ntotal
+        if allow is not None:
+            pack_allow_bits(allow, n)   # (shape and dtype are checked before anything runs)
+        rows = np.arange(n, dtype=np.int64) if allow is None else np.flatnonzero(np.asarray(allow)).astype(np.int64)
+        sph = self.metric_type == METRIC_INNER_PRODUCT if spherical is None else bool(spherical)
+        train = kmeans_train_mask(rows, n, nc, int(max_points_per_centroid), seed)
+        base = getattr(self, "_id_base", 0)
+        return run_kmeans(lambda c, a, want: self.kmeans_step(c, allow=a, want_assign=want, want_dist=want),
+                          lambda ids: self.reconstruct_batch(np.asarray(ids, dtype=np.int64) + base), nc, niter=niter,
+                          seed=seed, init=init, spherical=sph, init_rows=rows, train_allow=allow if train is None else train,
+                          allow=allow)
+
 
 class IndexFlatIP(IndexFlat):
     def __init__(self, d: int, device: int = 0):
@@ -645,6 +855,40 @@ class IndexFlatIP(IndexFlat):
 class IndexFlatL2(IndexFlat):
     def __init__(self, d: int, device: int = 0):
         super().__init__(d, METRIC_L2, device)
+
+
+class Kmeans:
+    """``faiss.Kmeans`` over the GPU step: ``train(x)`` clusters ``x`` (a temporary ``IndexFlatL2``, ``add``,
+    ``kmeans``) and returns the last objective; afterwards ``centroids`` is ``[k, d]`` float32, ``obj`` the objective
+    of every iteration and ``index`` an ``IndexFlatL2`` of the centroids, which ``assign(x) -> (D, I)`` searches."""
+
+    def __init__(self, d: int, k: int, niter: int = 20, seed: int = 1234, spherical: bool = False, device: int = 0):
+        self.d, self.k, self.niter, self.seed = int(d), int(k), int(niter), int(seed)
+        self.spherical, self.device = bool(spherical), int(device)
+        self.centroids: Optional[np.ndarray] = None
+        self.obj: List[float] = []
+        self.index: Optional[IndexFlat] = None
+
+    def train(self, x, init_centroids=None) -> float:
+        a = _as_f32_2d(x, self.d, "Kmeans.train")
+        tmp = IndexFlatL2(self.d, self.device)
+        try:
+            tmp.add(a)
+            res = tmp.kmeans(self.k, niter=self.niter, seed=self.seed, init=init_centroids, spherical=self.spherical)
+        finally:
+            tmp.close()
+        self.centroids, self.obj = res.centroids, list(res.obj)
+        if self.index is not None:
+            self.index.close()
+        self.index = IndexFlatL2(self.d, self.device)
+        self.index.add(self.centroids)
+        return self.obj[-1] if self.obj else 0.0
+
+    def assign(self, x) -> Tuple[np.ndarray, np.ndarray]:
+        if self.index is None:
+            raise RuntimeError("Kmeans.assign: train() first")
+        D, I = self.index.search(_as_f32_2d(x, self.d, "Kmeans.assign"), 1)
+        return D[:, 0], I[:, 0]
 
 
 # ---------------------------------------------------------------------------

@@ -45,7 +45,7 @@ class ShardedFlatIndex:
     """``IndexFlat`` semantics over ``world`` row shards.
 
     ``local_index`` must offer ``ntotal``, ``add(x, normalize=)``, ``add_synthetic``, ``set_id_base`` and
-    ``search_dev``/``search`` (``range_search`` for ``range_search``, ``reconstruct_n`` for ``search_by_ids`` and ``search_diverse``); ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
+    ``search_dev``/``search`` (``range_search`` for ``range_search``, ``reconstruct_n`` for ``search_by_ids`` and ``search_diverse``; ``kmeans_step``, ``bounds`` and ``reconstruct_batch`` for ``kmeans``); ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
     implementations; tests substitute doubles.
     """
 
@@ -572,6 +572,65 @@ class ShardedFlatIndex:
                 out[lo - row0:hi - row0] = self.local.reconstruct_n(l0 + (lo - g0), hi - lo)
         return self._sum_over_ranks(out)
 
+    def reconstruct_batch(self, ids) -> np.ndarray:
+        """``IndexFlat.reconstruct_batch`` in GLOBAL numbering on every rank (collective): the owner of each row
+        contributes it (gathered on its device), the others zeros, and ONE sum all-reduce completes the block."""
+        from .flat_index import ids_as_int64
+
+        a = ids_as_int64(ids, "reconstruct_batch")
+        bad = a[(a < 0) | (a >= self.ntotal_global)]
+        if bad.size:
+            raise ValueError(f"reconstruct_batch: id {int(bad[0])} outside [0, {self.ntotal_global})")
+        out = np.zeros((a.shape[0], self.d), dtype=np.float32)
+        loc = self._local_ids(a)
+        own = np.flatnonzero(loc >= 0)
+        if own.size:
+            # (one segment: the local index adds id_base itself, so it is asked by global id)
+            ask = a[own] if len(self.segments) == 1 else loc[own]
+            out[own] = self.local.reconstruct_batch(ask)
+        return self._sum_over_ranks(out)
+
+    # -- k-means -----------------------------------------------------------------------------------------------------
+    def kmeans(self, nc: int, niter: int = 20, seed: int = 0, init=None, spherical: Optional[bool] = None, allow=None,
+               max_points_per_centroid: int = 0):
+        """``IndexFlat.kmeans`` over the shards (collective: every rank passes the same arguments; ``allow`` is a mask
+        over the GLOBAL rows).  The loop is ``flat_index.run_kmeans``; a step is the local ``kmeans_step`` under the
+        GLOBAL shift (row counts summed, largest norms reduced with max) followed by ONE sum all-reduce of the int64
+        sums, counts and objective (the objective formed from the step's distances at the global ``t``) -- exact integers, so centroids, sizes and objective are bit-identical to one
+        index over the same rows.  ``assign`` / ``dist`` of the result are those of THIS shard's rows, in local order."""
+        from .flat_index import KmeansStep, fixed_point_objective, kmeans_shift, kmeans_train_mask, run_kmeans
+
+        n = self.ntotal_global
+        g = np.ones(n, dtype=bool) if allow is None else np.asarray(allow, dtype=bool)
+        if g.shape[0] != n:
+            raise ValueError(f"mask has {g.shape[0]} entries, the sharded index {n} rows")
+        if self._dead is not None and self._dead.any():
+            g = g.copy()
+            g[: self._dead.shape[0]] &= ~self._dead
+        rows = np.flatnonzero(g).astype(np.int64)
+        local_max = float(self.local.bounds()["max_norm2"]) if self.local.ntotal else 0.0
+        max_norm2 = local_max if self.world == 1 else float(self._all_gather_host(np.array([local_max], dtype=np.float64)).max())
+        s, _, t = kmeans_shift(max_norm2, n)
+        if s < 0:
+            raise ValueError(f"kmeans: rows too long for the fixed-point sums (shift {s})")
+        sph = self.metric == 0 if spherical is None else bool(spherical)
+        train = kmeans_train_mask(rows, n, nc, int(max_points_per_centroid), seed)
+
+        def step(cent, mask, want):
+            # (the library's objective is scaled by the shard's OWN largest norm, which differs between shards: the
+            # objective is formed here, from the step's distances, at the global t)
+            st = self.local.kmeans_step(cent, allow=self.local_rows_of(g if mask is None else mask), fx_shift=s,
+                                        want_assign=True, want_dist=True)
+            obj = fixed_point_objective(st.dist, st.assign, t)
+            flat = np.concatenate([st.sums.reshape(-1), st.counts, np.array([obj], dtype=np.int64)])
+            flat = self._sum_over_ranks(np.ascontiguousarray(flat, dtype=np.int64))
+            m = st.sums.size
+            return KmeansStep(flat[:m].reshape(st.sums.shape), flat[m:m + st.counts.size], int(flat[-1]), s, t,
+                              st.assign if want else None, st.dist if want else None)
+
+        return run_kmeans(step, self.reconstruct_batch, nc, niter=niter, seed=seed, init=init, spherical=sph,
+                          init_rows=rows, train_allow=train, allow=None)
+
     def add_file_rows(self, path: str, offset: int, n: int, normalize: bool = False, chunk_rows: int = 1 << 18) -> None:
         """``add_global`` of ``n`` fp32 rows stored row-major at byte ``offset`` of ``path`` (the payload of an index
         file): every rank reads only its own block (collective call, no communication)."""
@@ -648,6 +707,23 @@ class ShardedIndexFacade:
 
     def reconstruct(self, i: int) -> np.ndarray:
         return self.reconstruct_n(int(i), 1)[0]
+
+    def reconstruct_batch(self, ids) -> np.ndarray:
+        return self.sh.reconstruct_batch(ids)
+
+    def kmeans(self, nc: int, niter: int = 20, seed: int = 0, init=None, spherical: Optional[bool] = None, allow=None,
+               max_points_per_centroid: int = 0):
+        """``ShardedFlatIndex.kmeans`` with ``assign`` / ``dist`` in GLOBAL numbering on every rank, as one ``IndexFlat``
+        would return them (every shard fills in its rows; one sum all-reduce)."""
+        res = self.sh.kmeans(nc, niter=niter, seed=seed, init=init, spherical=spherical, allow=allow,
+                             max_points_per_centroid=max_points_per_centroid)
+        a = np.zeros(self.ntotal, dtype=np.int64)
+        d = np.zeros(self.ntotal, dtype=np.float32)
+        for l0, g0, n in self.sh.segments:
+            a[g0:g0 + n] = res.assign[l0:l0 + n].astype(np.int64) + 1   # (0 = not this shard's row)
+            d[g0:g0 + n] = res.dist[l0:l0 + n]
+        a, d = self.sh._sum_over_ranks(a), self.sh._sum_over_ranks(d)
+        return res._replace(assign=(a - 1).astype(np.int32), dist=d)
 
     def mark_deleted(self, ids) -> None:
         self.sh.mark_deleted(ids)

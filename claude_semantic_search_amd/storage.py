@@ -91,6 +91,16 @@ class SearchResult:
     text: Optional[str] = None
 
 
+@dataclass
+class Topic:
+    """One cluster of ``HybridStorage.topics``: its number of live chunks, the chunk nearest its centroid, the nearest
+    few chunks (``representative`` is ``examples[0]``; similarities are to the centroid) and the ids of all members."""
+    size: int
+    representative: SearchResult
+    examples: List[SearchResult]
+    chunk_ids: List[str]
+
+
 _CHUNK_COLUMNS = (
     "id", "text", "metadata", "faiss_id", "session_id", "project_name", "file_path", "chunk_type",
     "timestamp", "has_code", "has_tools", "message_count", "char_count", "word_count", "updated_at",
@@ -708,6 +718,52 @@ class HybridStorage:
                 pos=q, pos_ids=fids[:len(liked)], neg_ids=fids[len(liked):], k=k, gamma=g,
                 normalize=self.config.normalize_embeddings, exclude_ids=True, allow=allow)
             return self._results_in_rank_order(sims.tolist(), ids.tolist(), cfg, filters)
+
+    def topics(self, n_topics: int = 20, filters: Optional[Dict[str, Any]] = None, niter: int = 20, seed: int = 0,
+               examples: int = 3) -> List[Topic]:
+        """"What is in here": a k-means of the live chunks that match ``filters`` into ``n_topics`` clusters on the GPU
+        (``IndexFlat.kmeans``), each named by the ``examples`` chunks nearest its centroid.  Tombstones are always left
+        out; ``n_topics`` is cut to the number of live matching chunks (one chunk: one topic, no clustering).  One
+        ``kmeans`` and one ``search(centroids, examples)`` under the same mask.  Largest topic first.  An empty index
+        gives ``[]``; an index object without ``kmeans`` raises ``NotImplementedError``."""
+        if n_topics < 1 or examples < 1:
+            raise ValueError(f"topics: n_topics={n_topics} and examples={examples} must be positive")
+        with self._lock:
+            frame = self._search_frame(SearchConfig())
+            if frame is None:
+                return []
+            cfg, ntotal, _ = frame
+            if not hasattr(self.faiss_index, "kmeans"):
+                raise NotImplementedError(f"{type(self.faiss_index).__name__} has no k-means (kmeans)")
+            allow = self._allow_mask(filters or {}, ntotal)
+            live = int(allow.sum())
+            nc = min(int(n_topics), live, fi.MAX_CENTROIDS)
+            if nc == 0:
+                return []
+            if nc == 1:   # (k-means needs two centroids: the one topic is everything, named by the mean's neighbours)
+                rows = np.flatnonzero(allow)
+                cent = self.faiss_index.reconstruct_batch(rows[: 1 << 16]).astype(np.float64).mean(axis=0, keepdims=True)
+                if self.config.normalize_embeddings:
+                    cent /= max(float(np.linalg.norm(cent)), 1e-30)
+                cent = cent.astype(np.float32)
+                assign = np.where(allow, 0, -1)
+            else:
+                res = self.faiss_index.kmeans(nc, niter=niter, seed=seed, allow=allow)
+                cent, assign = res.centroids, np.asarray(res.assign)
+            k = max(1, min(int(examples), live, fi.MAX_K))
+            sims, ids = self.faiss_index.search(cent, k, normalize=False, allow=allow)
+            out: List[Topic] = []
+            for c in range(nc):
+                members = np.flatnonzero(assign == c)
+                if members.size == 0:
+                    continue
+                near = self._results_in_rank_order(sims[c].tolist(), ids[c].tolist(), cfg, None, unbounded=True, limit=k)
+                if not near:
+                    continue
+                chunk_ids = [self.faiss_id_to_chunk_id[int(f)] for f in members if int(f) in self.faiss_id_to_chunk_id]
+                out.append(Topic(size=int(members.size), representative=near[0], examples=near, chunk_ids=chunk_ids))
+            out.sort(key=lambda t: -t.size)   # (stable: equal sizes stay in centroid order)
+            return out
 
     @staticmethod
     def _make_result(chunk_id: str, score: float, data: Dict[str, Any], cfg: SearchConfig) -> SearchResult:

@@ -322,6 +322,58 @@ int css_index_search_examples(css_index* ix, const float* vec_host, int nvec_pos
                               const uint32_t* allow_bits_host, float* D_host, int64_t* I_host,
                               float* S_host /* may be NULL */);
 
+/* Rows by id (faiss reconstruct_batch): the stored fp32 rows of the n GLOBAL ids (id_base included), gathered on the
+ * device, as [n, dim] floats exactly as they lie in device memory.  Repeated ids are allowed.  An id outside
+ * [id_base, id_base + ntotal) is CSS_ERR_INVALID: the message names it and nothing is enqueued.  n == 0 is a no-op.
+ * Locking and the ordering behind asynchronous adds are those of css_index_search_rows. */
+int css_index_export_rows(css_index* ix, const int64_t* ids_host, int64_t n, float* x_out_host);
+
+/* One Lloyd step of k-means over the rows of the index ("what is in here": topics, a coarse quantiser): every allowed
+ * row is assigned to its nearest centroid and the members of every centroid are summed, on the device.  The loop, the
+ * initialisation and the empty-cluster rule are the caller's (flat_index.run_kmeans); this call is deterministic, so
+ * they are too.
+ *  - Assignment.  The metric is ALWAYS the squared L2 distance to the centroid, whatever the metric of the index (on
+ *    unit rows and unit centroids that is the inner-product order).  Row r whose allow bit is set (allow_bits_host as
+ *    in css_index_search_masked; NULL: every row) gets a(r) = argmax over c of key(r, c) = fmaf(-0.5f, ||c||^2,
+ *    <x_r, c>), ties to the LOWER centroid index.  <x_r, c> is formed on the fp32-input matrix core
+ *    (v_mfma_f32_32x32x2_f32, as the CSS_SEARCH_EXACT_FP32 scan of batches forms its scores): fp32 products, fp32
+ *    accumulation over the padded row.  ||c||^2 is formed once per call in fp32 from the uploaded table.  No
+ *    reduced-precision copy of the rows takes part, and the search mode plays none.
+ *  - Distance.  dist(r) = fmaxf(0, fmaf(-2, key(r, a(r)), xnorm2[r])) with the squared row norms the index keeps.
+ *  - Rows that are not allowed: assign = -1, dist = 0; they count nowhere.
+ *  - Sums are fixed point.  sums[c][j] = sum over a(r) = c of llrint(x_r[j] * 2^s) as int64 (round to nearest even),
+ *    counts[c] = the number of members, obj = sum over allowed r of llrint(dist(r) * 2^t).  They are exact integers:
+ *    identical from run to run and for any grid shape, and shards that use one s add up to the unsharded values.
+ *  - The shift rule (flat_index.kmeans_shift restates it).  ex = frexp(max_norm2) exponent with max_norm2 the running
+ *    maximum of ||row||^2 (css_index_bounds [0]), ex = 0 when that is 0; e = ceil(ex / 2), so every |x| < 2^e;
+ *    b = bit_length(max(ntotal, 1) - 1); s = 62 - b - e; t = s - e - 2.  n * 2^(s + e) <= 2^62: no sum reaches 2^63.
+ *    (obj assumes dist < 2^(2e + 2), i.e. centroids no longer than the longest row, which holds for means of rows; it
+ *    wraps, as int64, for centroids far outside the data.)
+ *  - fx_shift < 0: the library chooses s by the rule.  fx_shift >= 0 imposes s (a sharded index passes the s of the
+ *    global row count and the global maximum); a value above what this index's own ntotal and maximum can hold is
+ *    CSS_ERR_INVALID and the message names the largest safe value.  *fx_shift_used = s, *obj_shift_used = t (either
+ *    may be NULL).
+ *  - 2 <= nc <= CSS_MAX_CENTROIDS, anything else is CSS_ERR_INVALID.  A centroid component that is NaN or infinite is
+ *    CSS_ERR_INVALID: the message names the centroid and nothing is enqueued.  An empty index gives zero sums, counts
+ *    and obj.  Rows are assumed finite: what a NaN or infinite row does to the result is NOT defined (nothing is read or
+ *    written out of bounds).
+ *  - sums_host [nc, dim], counts_host [nc], obj_host [1] are always written; assign_host (int32 [ntotal]) and dist_host
+ *    (float [ntotal]) may be NULL, and are in LOCAL row numbering.
+ *  - Locking, the ordering behind asynchronous adds and the call frame are those of css_index_search_prior; the call
+ *    waits for the device once.  Its workspaces (centroid table, assign / dist, member lists, sums) belong to the index,
+ *    grow on demand and outlive css_index_add, css_index_remove_rows and css_index_reset.
+ *  - On the device: the assignment (128 rows x 128 centroids per tile; a lane holds the scores of one row, so the
+ *    argmax is a register reduction), an exclusive scan of the counts, member lists appended through one cursor per
+ *    centroid, and one block per (centroid, 1024 members) that sums llrint(x * 2^s) in int64 registers and flushes one
+ *    64-bit integer atomic per column.  No float atomics, no sort. */
+#define CSS_MAX_CENTROIDS 4096
+int css_index_kmeans_step(css_index* ix, const float* centroids_host /* [nc, dim] */, int nc,
+                          int fx_shift /* < 0: chosen by the library */, const uint32_t* allow_bits_host,
+                          int64_t* sums_host /* [nc, dim] */, int64_t* counts_host /* [nc] */,
+                          int64_t* obj_host /* [1] */, int* fx_shift_used, int* obj_shift_used,
+                          int32_t* assign_host /* [ntotal], may be NULL */,
+                          float* dist_host /* [ntotal], may be NULL */);
+
 /* Diversified search (maximal marginal relevance, MMR; langchain's max_marginal_relevance_search, the "diversity"
  * option of vector stores): k rows picked greedily from a pool of the best rows, each pick trading its score against
  * its similarity to the rows already picked -- so near-copies of one passage do not fill the answer.  Per query, with
