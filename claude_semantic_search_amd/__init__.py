@@ -31,6 +31,8 @@ _LAZY = {
     "KmeansResult": ".flat_index",
     "KmeansStep": ".flat_index",
     "run_kmeans": ".flat_index",
+    "terms_of": ".lexical",
+    "bm25_weights": ".lexical",
     "MpnetEncoder": ".mpnet_encoder",
     "ShardedFlatIndex": ".sharded",
     "GPUCapability": ".gpu_utils",

@@ -39,6 +39,8 @@
 //                      re-formed behind the merge (css_knn_examples.h).   HBM bound
 //   k_kmeans_assign,   css_index_kmeans_step: one Lloyd step -- rows x centroids on the fp32-input MFMA, member lists,
 //   k_kmeans_sum       fixed-point int64 sums (css_kmeans.h)
+//   k_lex_scores       css_index_search_hybrid: the BM25 column of one query over the per-row term lists, handed to
+//                      k_scan_prior in the place of the priors (css_lexical.h).   HBM bound
 //   k_mmr_select       css_index_search_diverse: k of a pool of the best rows picked greedily by maximal marginal
 //                      relevance, similarities from the stored fp32 rows (css_knn_diverse.h)
 //
@@ -96,6 +98,16 @@ struct css_index {
     // per-row priors (css_index_set_priors): [cap] fp32, 0 = no boost; empty until priors are first set.  Part of the row
     // storage exactly like the labels
     DevBuf<float> priors;
+    // per-row term lists (css_index_set_terms, css_lexical.h): the leading lex_rows rows own entries
+    // [lex_off[r], lex_off[r + 1]) of lex_ent and a length lex_dl[r]; lex_df [CSS_TERM_SPACE] and lex_total [1] are the
+    // statistics.  All empty until terms are first set (lex_df.p tells).  The buffers are sized by the lists, not by
+    // cap, so capacity growth and appended rows leave them alone; reset and css_index_remove_rows follow the rows.
+    // lex_off_h mirrors the offsets on the host (the new offsets of a compaction are a host prefix sum)
+    DevBuf<uint32_t> lex_ent, lex_dl, lex_df;
+    DevBuf<int64_t> lex_off;
+    DevBuf<unsigned long long> lex_total;
+    std::vector<int64_t> lex_off_h;
+    int64_t lex_rows = 0;
     hipStream_t stream = nullptr;
     int num_cus = 256;
     // reusable workspaces (DevBuf: grown on demand, freed with the index; guarded by ws_mu)
@@ -182,6 +194,12 @@ struct css_index {
     DevBuf<int32_t> pri_s;              // entries
     // css_index_search_examples: S = the best positive score [k] of the returned rows, the same 4-byte column
     DevBuf<int32_t> ex_s;               // entries
+    // css_index_search_hybrid: the lexical column [ntotal] of the call's query, and [S | L] of the k returned rows, the
+    // trailing 4-byte columns of the call's results; css_index_term_stats: the asked terms and [m df | total_len]
+    DevBuf<float> lex_col;
+    DevBuf<int32_t> hyb_sl;             // 2 k entries
+    DevBuf<uint32_t> lex_ask;
+    DevBuf<long long> lex_stat;
     // css_index_kmeans_step (css_kmeans.h): the uploaded centroids [nc, dim]; their padded table [ncpad][dpad] with the
     // squared norms [ncpad] behind it; assignment and distance of every row; the member lists [ntotal] with
     // [nc + 1 offsets | nc + 1 block numbers | nc cursors]; and [KM_HDR words | nc counts | nc * dim sums] of int64
@@ -2690,6 +2708,7 @@ int range_pool_alloc(css_index* ix, size_t cap) {
 
 // ------------------------------------------------------------------ prior-weighted search (css_knn_prior.h)
 #include "css_knn_prior.h"
+#include "css_lexical.h"
 
 // HASP: the index has a prior column (false: every prior is 0, the kernel loads none)
 template <int NQ, int TT, int METRIC, bool HASP>
@@ -3174,6 +3193,20 @@ int css_index_free(css_index* ix) {
     return CSS_OK;
 }
 
+namespace {
+// the index is again one that never received terms; caller holds mu exclusively and the stream is idle
+int drop_terms(css_index* ix) {
+    ix->lex_rows = 0;
+    ix->lex_off_h.clear();
+    CSS_HIP_TRY(ix->lex_ent.drop());
+    CSS_HIP_TRY(ix->lex_dl.drop());
+    CSS_HIP_TRY(ix->lex_off.drop());
+    CSS_HIP_TRY(ix->lex_df.drop());
+    CSS_HIP_TRY(ix->lex_total.drop());
+    return CSS_OK;
+}
+}  // namespace
+
 int css_index_reset(css_index* ix) {
     CSS_REQUIRE(ix, "css_index_reset: NULL index");
     std::unique_lock<std::shared_mutex> lk(ix->mu);
@@ -3186,7 +3219,7 @@ int css_index_reset(css_index* ix) {
     CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
     CSS_HIP_TRY(ix->labels.drop());   // the labels go with the rows: the index is again one that never set any
     CSS_HIP_TRY(ix->priors.drop());   // and so do the priors
-    return CSS_OK;
+    return drop_terms(ix);            // and the term lists with their statistics
 }
 
 namespace {
@@ -3293,6 +3326,63 @@ int compact_labels(css_index* ix, const uint32_t* keep, int64_t n, const int32_t
     }
     return CSS_OK;
 }
+
+// a grid for the element-wise list kernels: enough blocks to fill the chip, never more than the elements need
+inline unsigned lex_grid(const css_index* ix, int64_t count) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((count + 255) / 256, (int64_t)ix->num_cus * 16));
+}
+
+// The term lists through the keep bits of css_index_remove_rows, OUT OF PLACE like compact_labels: the new offsets are
+// a host prefix sum over the mirror, k_lex_move moves the lists of the kept rows and takes those of the removed rows
+// out of df and total_len.  Enqueued behind compact_rows on the index's stream; the caller waits, then commits.
+struct TermCompaction {
+    DevBuf<uint32_t> ent, dl, map;
+    DevBuf<int64_t> off;
+    std::vector<int64_t> off_h;   // (read by the copy until the caller has waited)
+    std::vector<uint32_t> map_h;
+    bool built = false;
+    void commit(css_index* ix) {
+        ix->lex_ent.swap(ent);
+        ix->lex_dl.swap(dl);
+        ix->lex_off.swap(off);
+        ix->lex_off_h.swap(off_h);
+        ix->lex_rows = (int64_t)ix->lex_off_h.size() - 1;
+    }
+};
+int compact_terms(css_index* ix, const uint32_t* keep, TermCompaction* tc) {
+    const int64_t T = ix->lex_rows;
+    if (T == 0) return CSS_OK;
+    const hipStream_t st = ix->stream;
+    try {
+        tc->map_h.resize((size_t)T);
+        tc->off_h.assign(1, 0);
+        for (int64_t r = 0; r < T; ++r) {
+            if ((keep[r >> 5] >> (r & 31)) & 1u) {
+                tc->map_h[(size_t)r] = (uint32_t)(tc->off_h.size() - 1);
+                tc->off_h.push_back(tc->off_h.back() + (ix->lex_off_h[(size_t)r + 1] - ix->lex_off_h[(size_t)r]));
+            } else {
+                tc->map_h[(size_t)r] = kLexNoRow;
+            }
+        }
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_index_remove_rows: out of host memory");
+        return CSS_ERR_OOM;
+    }
+    const size_t nT = tc->off_h.size() - 1;
+    int rc;
+    if ((rc = tc->ent.grow_exact(std::max<size_t>((size_t)tc->off_h.back(), 1), "hipMalloc(term lists)")) != CSS_OK) return rc;
+    if ((rc = tc->dl.grow_exact(std::max<size_t>(nT, 1), "hipMalloc(term lists)")) != CSS_OK) return rc;
+    if ((rc = tc->off.grow_exact(nT + 1, "hipMalloc(term lists)")) != CSS_OK) return rc;
+    if ((rc = tc->map.grow_exact((size_t)T, "hipMalloc(term lists)")) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(tc->map.p, tc->map_h.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(tc->off.p, tc->off_h.data(), (nT + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_lex_move, dim3((unsigned)((T + kWaves - 1) / kWaves)), dim3(256), 0, st, (const uint32_t*)ix->lex_ent.p,
+                       (const int64_t*)ix->lex_off.p, (const uint32_t*)ix->lex_dl.p, (const uint32_t*)tc->map.p,
+                       (const int64_t*)tc->off.p, T, tc->ent.p, tc->dl.p, ix->lex_df.p, ix->lex_total.p);
+    CSS_LAUNCH_CHECK();
+    tc->built = true;
+    return CSS_OK;
+}
 }  // namespace
 
 int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t* removed_out) {
@@ -3329,6 +3419,7 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
         if ((rc0 = npri.grow_exact((size_t)ix->cap, "hipMalloc(priors)")) != CSS_OK) return rc0;
         CSS_HIP_TRY(hipMemsetAsync(npri.p, 0, (size_t)ix->cap * sizeof(float), ix->stream));
     }
+    TermCompaction tc;      // the compacted term lists (only where terms were set)
     CSS_HIP_TRY(hipMemsetAsync(ix->maxn2.p, 0, 3 * sizeof(int), ix->stream));
     uint32_t patch = 0;
     int rc = kept > 0 ? compact_rows(ix, keep_bits_host, n, first, &patch) : CSS_OK;
@@ -3336,12 +3427,15 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
     if (rc == CSS_OK && npri.p)   // (a 4-byte column: moved as bits by the label kernel)
         rc = compact_labels(ix, keep_bits_host, n, reinterpret_cast<const int32_t*>(ix->priors.p),
                             reinterpret_cast<int32_t*>(npri.p));
+    if (rc == CSS_OK && ix->lex_df.p && kept > 0) rc = compact_terms(ix, keep_bits_host, &tc);
     // later adds and searches on any stream are ordered behind the compaction (as css_index_reset)
     const hipError_t e = hipStreamSynchronize(ix->stream);
     if (rc != CSS_OK) return rc;
     if (e != hipSuccess) return css::hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
     if (nlab.p) ix->labels.swap(nlab);
     if (npri.p) ix->priors.swap(npri);
+    if (tc.built) tc.commit(ix);
+    if (kept == 0 && (rc = drop_terms(ix)) != CSS_OK) return rc;   // emptied: as css_index_reset
     set_ntotal(ix, kept);
     if (kept == 0 && !ix->xh.p) ix->shadow = -1;   // emptied: as css_index_reset
     for (css_index::I8Feedback* f : {&ix->fb_batch, &ix->fb_sweep}) {   // (it described other rows; its copy has landed)
@@ -3596,9 +3690,10 @@ struct HostCall : CallScope {
     float* d_out = nullptr;
     int64_t* i_out = nullptr;
     int32_t* g_out = nullptr;   // the trailing int32 column of the results, where the call has one
+    int cols = 1;               // ... or `cols` of them, one after the other (set before upload)
     bool staged = false, enqueued = false;
     // the ONE size of a result entry: the staging decision and the offsets of the copy back both use it
-    size_t record() const { return kEntry + (g_out ? sizeof(int32_t) : 0); }
+    size_t record() const { return kEntry + (g_out ? cols * sizeof(int32_t) : 0); }
 
     // `count` elements from `src` into `dst`, the allow-bitmap (null: every row) into the mask of `rows`, and n_out
     // result entries reserved: [ids | scores] in out_i, their int32 column in `column` where the call names one
@@ -3609,7 +3704,7 @@ struct HostCall : CallScope {
         n = n_out;
         if ((rc = dst.grow(count)) != CSS_OK) return rc;
         if (column) {
-            if ((rc = column->grow(n)) != CSS_OK) return rc;
+            if ((rc = column->grow(n * cols)) != CSS_OK) return rc;
             g_out = column->p;
         }
         if (n && (rc = reserve_out(ix, n, &d_out, &i_out)) != CSS_OK) return rc;
@@ -3637,16 +3732,16 @@ struct HostCall : CallScope {
         if (staged) {   // one wait: [ids | scores] in one copy, and the column, into pinned memory
             char* back = ix->h_stage + css_index::kHostStage;
             CSS_HIP_TRY(hipMemcpyAsync(back, i_out, n * kEntry, hipMemcpyDeviceToHost, st));
-            if (G_host) CSS_HIP_TRY(hipMemcpyAsync(back + n * kEntry, g_out, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            if (G_host) CSS_HIP_TRY(hipMemcpyAsync(back + n * kEntry, g_out, n * cols * sizeof(int32_t), hipMemcpyDeviceToHost, st));
             CSS_HIP_TRY(hipStreamSynchronize(st));
             memcpy(I_host, back, n * sizeof(int64_t));
             memcpy(D_host, back + n * sizeof(int64_t), n * sizeof(float));
-            if (G_host) memcpy(G_host, back + n * kEntry, n * sizeof(int32_t));
+            if (G_host) memcpy(G_host, back + n * kEntry, n * cols * sizeof(int32_t));
             return CSS_OK;
         }
         CSS_HIP_TRY(hipMemcpyAsync(D_host, d_out, n * sizeof(float), hipMemcpyDeviceToHost, st));
         CSS_HIP_TRY(hipMemcpyAsync(I_host, i_out, n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        if (G_host) CSS_HIP_TRY(hipMemcpyAsync(G_host, g_out, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (G_host) CSS_HIP_TRY(hipMemcpyAsync(G_host, g_out, n * cols * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         CSS_HIP_TRY(hipStreamSynchronize(st));
         return CSS_OK;
     }
@@ -4247,6 +4342,259 @@ int css_index_search_examples(css_index* ix, const float* vec_host, int nvec_pos
         rc = search_examples_enqueue(ix, rows, ix->q_raw.p, c, k, gamma, normalize_vec, nexcl, hc.d_out, hc.i_out,
                                      reinterpret_cast<float*>(hc.g_out), ix->stream);
     return hc.finish(rc, D_host, I_host, reinterpret_cast<int32_t*>(S_host));   // (S rides in the 4-byte column)
+}
+
+// ------------------------------------------------------------------ per-row term lists and hybrid search
+namespace {
+// `b` grown to `need` elements (at least doubled) with its first `keep` elements kept (an empty `b` has none to keep);
+// the index's stream is drained before the old buffer goes
+extern "C++" template <typename T>
+int grow_keep(css_index* ix, DevBuf<T>& b, size_t keep, size_t need, const char* what) {
+    if (need <= b.cap) return CSS_OK;
+    DevBuf<T> nb;
+    int rc;
+    if ((rc = nb.grow_exact(std::max(need, b.cap * 2), what)) != CSS_OK) return rc;
+    if (keep && b.p) CSS_HIP_TRY(hipMemcpyAsync(nb.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, ix->stream));
+    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    b.swap(nb);
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_set_terms(css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host, const uint32_t* tokens_host) {
+    CSS_REQUIRE(ix, "css_index_set_terms: NULL index");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);   // (ws_pending)
+    const int64_t T0 = ix->lex_rows;
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_set_terms: rows [%lld, %lld + %lld) outside [0, %lld)",
+                (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
+    CSS_REQUIRE(row0 <= T0, "css_index_set_terms: row0=%lld beyond the %lld rows that have lists (lists are append-only)",
+                (long long)row0, (long long)T0);
+    CSS_REQUIRE(n == 0 || offsets_host, "css_index_set_terms: offsets is NULL");
+    // everything is looked at before anything is written
+    if (n > 0) {
+        CSS_REQUIRE(offsets_host[0] == 0, "css_index_set_terms: offsets start at %lld, not 0", (long long)offsets_host[0]);
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t c = offsets_host[i + 1] - offsets_host[i];
+            CSS_REQUIRE(c >= 0, "css_index_set_terms: offsets decrease at row %lld", (long long)(row0 + i));
+            CSS_REQUIRE(c <= CSS_MAX_ROW_TOKENS, "css_index_set_terms: row %lld has %lld tokens (at most %d)", (long long)(row0 + i),
+                        (long long)c, CSS_MAX_ROW_TOKENS);
+        }
+        CSS_REQUIRE(offsets_host[n] == 0 || tokens_host, "css_index_set_terms: tokens is NULL");
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t t = offsets_host[i]; t < offsets_host[i + 1]; ++t)
+                CSS_REQUIRE(tokens_host[t] < CSS_TERM_SPACE, "css_index_set_terms: token %u of row %lld is outside [0, 2^24)",
+                            tokens_host[t], (long long)(row0 + i));
+    }
+    if (n == 0 && row0 == T0) return CSS_OK;
+    // each row sorted and counted on the host: term << 8 | min(tf, 255), ascending by term
+    std::vector<uint32_t> ent, dl, tmp;
+    std::vector<int64_t> off;
+    const int64_t E0 = T0 > 0 ? ix->lex_off_h[(size_t)row0] : 0;
+    try {
+        ent.reserve(n > 0 ? (size_t)offsets_host[n] : 0);
+        dl.resize((size_t)n);
+        off.resize((size_t)n + 1);
+        off[0] = E0;
+        for (int64_t i = 0; i < n; ++i) {
+            tmp.assign(tokens_host + offsets_host[i], tokens_host + offsets_host[i + 1]);
+            std::sort(tmp.begin(), tmp.end());
+            for (size_t a = 0; a < tmp.size();) {
+                size_t e = a;
+                while (e < tmp.size() && tmp[e] == tmp[a]) ++e;
+                ent.push_back(tmp[a] << 8 | (uint32_t)std::min<size_t>(e - a, 255));
+                a = e;
+            }
+            dl[(size_t)i] = (uint32_t)tmp.size();
+            off[(size_t)i + 1] = E0 + (int64_t)ent.size();
+        }
+        ix->lex_off_h.reserve((size_t)(row0 + n) + 1);
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_index_set_terms: out of host memory");
+        return CSS_ERR_OOM;
+    }
+    DeviceGuard g(ix->device);
+    const hipStream_t st = ix->stream;
+    // as css_index_set_groups; and a search on another stream may still read the lists that go or move
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ws_ev, 0));
+    int rc;
+    if (!ix->lex_df.p) {   // first terms of this index: the statistics, all zero
+        if ((rc = ix->lex_total.grow_exact(1, "hipMalloc(term statistics)")) != CSS_OK) return rc;
+        if ((rc = ix->lex_df.grow_exact((size_t)CSS_TERM_SPACE, "hipMalloc(term statistics)")) != CSS_OK) return rc;
+        CSS_HIP_TRY(hipMemsetAsync(ix->lex_df.p, 0, (size_t)CSS_TERM_SPACE * sizeof(uint32_t), st));
+        CSS_HIP_TRY(hipMemsetAsync(ix->lex_total.p, 0, sizeof(unsigned long long), st));
+        ix->lex_off_h.assign(1, 0);
+    }
+    if (row0 < T0) {   // the lists of rows >= row0 go, and leave the statistics
+        const int64_t gone = ix->lex_off_h[(size_t)T0] - E0;
+        if (gone > 0) {
+            hipLaunchKernelGGL(k_lex_df_add, dim3(lex_grid(ix, gone)), dim3(256), 0, st, (const uint32_t*)ix->lex_ent.p + E0, gone,
+                               ix->lex_df.p, 0xFFFFFFFFu);
+            CSS_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(k_lex_len_add, dim3(lex_grid(ix, T0 - row0)), dim3(256), 0, st, (const uint32_t*)ix->lex_dl.p + row0,
+                           T0 - row0, ix->lex_total.p, 1);
+        CSS_LAUNCH_CHECK();
+        ix->lex_off_h.resize((size_t)row0 + 1);
+        ix->lex_rows = row0;
+    }
+    if (n > 0) {
+        const size_t nE = ent.size();
+        if ((rc = grow_keep(ix, ix->lex_ent, (size_t)E0, (size_t)E0 + std::max<size_t>(nE, 1), "hipMalloc(term lists)")) != CSS_OK) return rc;
+        if ((rc = grow_keep(ix, ix->lex_dl, (size_t)row0, (size_t)(row0 + n), "hipMalloc(term lists)")) != CSS_OK) return rc;
+        if ((rc = grow_keep(ix, ix->lex_off, (size_t)row0 + 1, (size_t)(row0 + n) + 1, "hipMalloc(term lists)")) != CSS_OK) return rc;
+        if (nE) CSS_HIP_TRY(hipMemcpyAsync(ix->lex_ent.p + E0, ent.data(), nE * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        CSS_HIP_TRY(hipMemcpyAsync(ix->lex_dl.p + row0, dl.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        CSS_HIP_TRY(hipMemcpyAsync(ix->lex_off.p + row0, off.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        if (nE) {
+            hipLaunchKernelGGL(k_lex_df_add, dim3(lex_grid(ix, (int64_t)nE)), dim3(256), 0, st, (const uint32_t*)ix->lex_ent.p + E0,
+                               (int64_t)nE, ix->lex_df.p, 1u);
+            CSS_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(k_lex_len_add, dim3(lex_grid(ix, n)), dim3(256), 0, st, (const uint32_t*)ix->lex_dl.p + row0, n,
+                           ix->lex_total.p, 0);
+        CSS_LAUNCH_CHECK();
+    }
+    CSS_HIP_TRY(hipStreamSynchronize(st));   // (the copies read this call's vectors)
+    ix->lex_off_h.insert(ix->lex_off_h.end(), off.begin() + 1, off.end());
+    ix->lex_rows = row0 + n;
+    return CSS_OK;
+}
+
+int css_index_get_terms(css_index* ix, int64_t row0, int64_t n, int64_t* offsets_out, uint32_t* entries_out, uint32_t* dl_out) {
+    CSS_REQUIRE(ix, "css_index_get_terms: NULL index");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_get_terms: rows [%lld, %lld + %lld) outside [0, %lld)",
+                (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
+    CSS_REQUIRE(offsets_out, "css_index_get_terms: offsets_out is NULL");
+    const int64_t T = ix->lex_rows;
+    const int64_t a = std::min(row0, T), e = std::min(row0 + n, T);   // the rows of the range that have lists
+    const int64_t E0 = T > 0 ? ix->lex_off_h[(size_t)a] : 0;
+    for (int64_t i = 0; i <= n; ++i) offsets_out[i] = T > 0 ? ix->lex_off_h[(size_t)std::min(row0 + i, T)] - E0 : 0;
+    if (dl_out) std::fill(dl_out, dl_out + n, 0u);
+    if (e <= a) return CSS_OK;
+    DeviceGuard g(ix->device);
+    if (entries_out && offsets_out[n] > 0)
+        CSS_HIP_TRY(hipMemcpy(entries_out, ix->lex_ent.p + E0, (size_t)offsets_out[n] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (dl_out) CSS_HIP_TRY(hipMemcpy(dl_out, ix->lex_dl.p + a, (size_t)(e - a) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return CSS_OK;
+}
+
+int css_index_term_stats(css_index* ix, const uint32_t* terms_host, int m, int64_t* df_out, int64_t* ndocs_out,
+                         int64_t* total_len_out) {
+    CSS_REQUIRE(ix, "css_index_term_stats: NULL index");
+    CSS_REQUIRE(m >= 0 && m <= (1 << 20), "css_index_term_stats: m=%d outside [0, 2^20]", m);
+    CSS_REQUIRE(ndocs_out && total_len_out && (m == 0 || (terms_host && df_out)), "css_index_term_stats: NULL buffer");
+    for (int j = 0; j < m; ++j)
+        CSS_REQUIRE(terms_host[j] < CSS_TERM_SPACE, "css_index_term_stats: term %u (number %d) is outside [0, 2^24)", terms_host[j], j);
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    *ndocs_out = ix->ntotal;
+    *total_len_out = 0;
+    std::fill(df_out, df_out + m, (int64_t)0);
+    if (!ix->lex_df.p) return CSS_OK;
+    DeviceGuard g(ix->device);
+    const hipStream_t st = ix->stream;
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    if ((rc = ix->lex_ask.grow((size_t)m + 1)) != CSS_OK) return rc;
+    if ((rc = ix->lex_stat.grow((size_t)m + 1)) != CSS_OK) return rc;
+    std::vector<long long> out((size_t)m + 1);
+    if (m) CSS_HIP_TRY(hipMemcpyAsync(ix->lex_ask.p, terms_host, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_lex_stats, dim3((unsigned)(m / 256 + 1)), dim3(256), 0, st, (const uint32_t*)ix->lex_ask.p, m,
+                       (const uint32_t*)ix->lex_df.p, (const unsigned long long*)ix->lex_total.p, ix->lex_stat.p);
+    CSS_LAUNCH_CHECK();
+    CSS_HIP_TRY(hipMemcpyAsync(out.data(), ix->lex_stat.p, ((size_t)m + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    for (int j = 0; j < m; ++j) df_out[j] = out[(size_t)j];
+    *total_len_out = out[(size_t)m];
+    return CSS_OK;
+}
+
+namespace {
+// What css_index_search_hybrid uploads in ONE copy (floats of q_raw): the query, then the terms and their weights
+inline size_t hybrid_terms_at(const css_index* ix) { return ((size_t)ix->dim + 3) / 4 * 4; }
+
+struct LexQuery {
+    int m;
+    float alpha, k1, b, avgdl;
+};
+
+// The lexical column (where the call has one), search_prior_enqueue on a COPY of the rows whose priors point at it,
+// and L behind them.  Everything is enqueued on `st`; nothing waits for the device.  Caller holds ws_mu and a shared
+// lock on mu.
+int search_hybrid_enqueue(css_index* ix, const Rows& rows, const float* in_dev, const LexQuery& lq, int k, int normalize_q,
+                          float* D_dev, int64_t* I_dev, float* S_dev, float* L_dev, hipStream_t st) {
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    Rows fused = rows;
+    fused.priors = nullptr;   // (the stored priors play no part in this call)
+    const bool lexical = lq.m > 0 && lq.alpha != 0.f && ix->lex_rows > 0 && rows.n > 0;
+    if (lexical) {
+        if ((rc = ix->lex_col.grow((size_t)rows.n)) != CSS_OK) return rc;
+        const uint32_t* qterms = reinterpret_cast<const uint32_t*>(in_dev + hybrid_terms_at(ix));
+        const float* qweights = in_dev + hybrid_terms_at(ix) + CSS_MAX_QUERY_TERMS;
+        const float c0 = lq.k1 * (1.0f - lq.b), c1 = (lq.k1 * lq.b) / lq.avgdl;
+        ProfScope ps("lex_scores", st);
+        hipLaunchKernelGGL(k_lex_scores, dim3((unsigned)((rows.n + 64 * kWaves - 1) / (64 * kWaves))), dim3(256), 0, st,
+                           (const uint32_t*)ix->lex_ent.p, (const int64_t*)ix->lex_off.p, (const uint32_t*)ix->lex_dl.p,
+                           std::min(ix->lex_rows, rows.n), rows.n, qterms, qweights, lq.m, lq.k1, c0, c1, ix->lex_col.p);
+        CSS_LAUNCH_CHECK();
+        fused.priors = ix->lex_col.p;
+    }
+    if ((rc = search_prior_enqueue(ix, fused, in_dev, 1, k, lexical ? lq.alpha : 0.f, normalize_q, D_dev, I_dev, S_dev, st)) != CSS_OK)
+        return rc;
+    hipLaunchKernelGGL(k_lex_gather, dim3(1), dim3(128), 0, st, (const int64_t*)I_dev, k, rows.id_base, fused.priors, L_dev);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_search_hybrid(css_index* ix, const float* q_host, int k, float alpha, const uint32_t* terms_host,
+                            const float* weights_host, int m, float k1, float b, float avgdl, int normalize_q,
+                            const uint32_t* allow_bits_host, float* D_host, int64_t* I_host, float* S_host, float* L_host) {
+    CSS_REQUIRE(ix, "css_index_search_hybrid: NULL index");
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "css_index_search_hybrid: k=%d outside [1, %d]", k, CSS_KERNEL_MAX_K);
+    CSS_REQUIRE(m >= 0 && m <= CSS_MAX_QUERY_TERMS, "css_index_search_hybrid: m=%d outside [0, %d]", m, CSS_MAX_QUERY_TERMS);
+    CSS_REQUIRE(std::isfinite(alpha), "css_index_search_hybrid: alpha is %s (it must be finite)", std::isnan(alpha) ? "NaN" : "infinite");
+    CSS_REQUIRE(std::isfinite(k1) && k1 >= 0.f, "css_index_search_hybrid: k1 is %s (it must be finite and >= 0)",
+                std::isnan(k1) ? "NaN" : std::isinf(k1) ? "infinite" : "negative");
+    CSS_REQUIRE(std::isfinite(b) && b >= 0.f && b <= 1.f, "css_index_search_hybrid: b is %s (it must lie in [0, 1])",
+                std::isnan(b) ? "NaN" : std::isinf(b) ? "infinite" : "outside [0, 1]");
+    CSS_REQUIRE(std::isfinite(avgdl) && avgdl > 0.f, "css_index_search_hybrid: avgdl is %s (it must be finite and > 0)",
+                std::isnan(avgdl) ? "NaN" : std::isinf(avgdl) ? "infinite" : "not positive");
+    CSS_REQUIRE(q_host && D_host && I_host && (m == 0 || (terms_host && weights_host)), "css_index_search_hybrid: NULL buffer");
+    for (int j = 0; j < m; ++j) {
+        CSS_REQUIRE(terms_host[j] < CSS_TERM_SPACE, "css_index_search_hybrid: term %u (number %d) is outside [0, 2^24)", terms_host[j], j);
+        CSS_REQUIRE(std::isfinite(weights_host[j]), "css_index_search_hybrid: the weight of term %u (number %d) is %s (weights are finite)",
+                    terms_host[j], j, std::isnan(weights_host[j]) ? "NaN" : "infinite");
+        for (int i = 0; i < j; ++i)
+            CSS_REQUIRE(terms_host[i] != terms_host[j], "css_index_search_hybrid: term %u is repeated (numbers %d and %d)",
+                        terms_host[j], i, j);
+    }
+    HostCall hc(ix);
+    // the ONE upload: the query, the terms, the weights
+    const size_t at = hybrid_terms_at(ix);
+    std::vector<float> in(at + 2 * CSS_MAX_QUERY_TERMS, 0.f);
+    memcpy(in.data(), q_host, (size_t)ix->dim * sizeof(float));
+    if (m) memcpy(in.data() + at, terms_host, (size_t)m * sizeof(uint32_t));
+    if (m) memcpy(in.data() + at + CSS_MAX_QUERY_TERMS, weights_host, (size_t)m * sizeof(float));
+    hc.cols = 2;   // [S | L]
+    int rc = hc.upload(allow_bits_host, ix->q_raw, (const float*)in.data(), in.size(), (size_t)k, &ix->hyb_sl);
+    if (rc == CSS_OK) {
+        float* sl = reinterpret_cast<float*>(hc.g_out);
+        rc = search_hybrid_enqueue(ix, hc.rows, ix->q_raw.p, LexQuery{m, alpha, k1, b, avgdl}, k, normalize_q, hc.d_out, hc.i_out,
+                                   sl, sl + k, ix->stream);
+    }
+    float sl_host[2 * CSS_KERNEL_MAX_K];
+    rc = hc.finish(rc, D_host, I_host, reinterpret_cast<int32_t*>(sl_host));
+    if (rc != CSS_OK) return rc;
+    if (S_host) memcpy(S_host, sl_host, (size_t)k * sizeof(float));
+    if (L_host) memcpy(L_host, sl_host + k, (size_t)k * sizeof(float));
+    return CSS_OK;
 }
 
 int css_merge_topk_dev(const float* Dp, const int64_t* Ip, int nparts, int64_t nq, int k, int metric, float* D,

@@ -151,6 +151,42 @@ def priors_as_f32(priors, what: str = "set_priors") -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+MAX_HYBRID_K = nat.MAX_HYBRID_K
+MAX_QUERY_TERMS = nat.MAX_QUERY_TERMS
+
+
+def hybrid_args(terms, weights, k, alpha, k1, b, avgdl, what: str = "search_hybrid"):
+    """The checked arguments of a hybrid search: ``(terms uint32 [m], weights float32 [m], k, alpha, k1, b, avgdl)``;
+    what the library would refuse raises ``ValueError`` here (``avgdl`` may still be ``None``)."""
+    t = np.asarray(terms if terms is not None else (), dtype=np.int64).reshape(-1)
+    w = np.ascontiguousarray(np.asarray(weights if weights is not None else (), dtype=np.float32).reshape(-1))
+    if t.shape[0] != w.shape[0]:
+        raise ValueError(f"{what}: {t.shape[0]} terms but {w.shape[0]} weights")
+    if t.shape[0] > MAX_QUERY_TERMS:
+        raise ValueError(f"{what}: {t.shape[0]} query terms (at most {MAX_QUERY_TERMS})")
+    if t.size and (int(t.min()) < 0 or int(t.max()) >= nat.TERM_SPACE):
+        raise ValueError(f"{what}: a term outside [0, 2^24)")
+    uniq, counts = np.unique(t, return_counts=True)
+    if (counts > 1).any():
+        raise ValueError(f"{what}: term {int(uniq[counts > 1][0])} is repeated")
+    if not np.isfinite(w).all():
+        raise ValueError(f"{what}: the weight of term {int(t[~np.isfinite(w)][0])} is not finite")
+    k, alpha, k1, b = int(k), float(alpha), float(k1), float(b)
+    if k < 1 or k > MAX_HYBRID_K:
+        raise ValueError(f"k={k} outside [1, {MAX_HYBRID_K}]")
+    if not np.isfinite(alpha):
+        raise ValueError(f"{what}: alpha={alpha} is not finite")
+    if not np.isfinite(k1) or k1 < 0.0:
+        raise ValueError(f"{what}: k1={k1} must be finite and >= 0")
+    if not np.isfinite(b) or b < 0.0 or b > 1.0:
+        raise ValueError(f"{what}: b={b} must lie in [0, 1]")
+    if avgdl is not None:
+        avgdl = float(avgdl)
+        if not np.isfinite(avgdl) or avgdl <= 0.0:
+            raise ValueError(f"{what}: avgdl={avgdl} must be finite and > 0")
+    return np.ascontiguousarray(t, dtype=np.uint32), w, k, alpha, k1, b, avgdl
+
+
 MAX_DIVERSE_FETCH = nat.MAX_DIVERSE_FETCH
 
 
@@ -429,6 +465,7 @@ class IndexFlat:
         h = ctypes.c_void_p()
         nat.check(nat.lib().css_index_create(self.d, self.metric_type, self.device, ctypes.byref(h)))
         self._h: Optional[ctypes.c_void_p] = h
+        self._terms_rows = 0   # the leading rows that have term lists (set_terms appends there by default)
 
     # -- lifetime ---------------------------------------------------------
     def close(self) -> None:
@@ -482,6 +519,7 @@ class IndexFlat:
 
     def reset(self) -> None:
         nat.check(nat.lib().css_index_reset(self._handle()))
+        self._terms_rows = 0
 
     def reserve(self, n: int) -> None:
         nat.check(nat.lib().css_index_reserve(self._handle(), int(n)))
@@ -497,6 +535,7 @@ class IndexFlat:
         bits = pack_allow_bits(keep, n)
         removed = ctypes.c_int64(0)
         nat.check(nat.lib().css_index_remove_rows(self._handle(), bits.ctypes.data, ctypes.byref(removed)))
+        self._terms_rows = int(np.count_nonzero(keep[:self._terms_rows]))   # (the lists were compacted with the rows)
         return int(removed.value)
 
     def bounds(self) -> dict:
@@ -677,6 +716,84 @@ class IndexFlat:
             ids.ctypes.data if ids.shape[0] else None, ip.shape[0], ineg.shape[0], k, gamma, 1 if normalize else 0,
             1 if exclude_ids else 0, bits_ptr, D.ctypes.data, I.ctypes.data, S.ctypes.data))
         return D, I, S
+
+    # -- per-row term lists and hybrid search ---------------------------------
+    def set_terms(self, lists, row0: Optional[int] = None) -> None:
+        """Term lists of rows ``[row0, row0 + n)`` in LOCAL row numbering (``css_index_set_terms``).  ``lists`` is a
+        sequence of int sequences (the raw term ids of each row's text, e.g. ``lexical.terms_of``: repeats, any order
+        and empty rows allowed) or an ``(offsets, tokens)`` pair of arrays in CSR form.  Lists are APPEND-ONLY in row
+        order: with ``T`` the leading rows that have lists, ``row0 = None`` or ``T`` appends, ``row0 < T`` first drops
+        the lists of all rows ``>= row0`` (``row0 = 0`` rewrites), ``row0 > T`` raises.  The lists follow the rows
+        through growth, ``remove_ids`` (compacted with them) and ``reset`` (forgotten); rows added later have none."""
+        from .lexical import lists_as_csr
+
+        off, tok = lists_as_csr(lists)
+        row0 = self._terms_rows if row0 is None else int(row0)
+        n = off.shape[0] - 1
+        nat.check(nat.lib().css_index_set_terms(self._handle(), row0, n, off.ctypes.data, tok.ctypes.data if tok.size else None))
+        if n or row0 < self._terms_rows:
+            self._terms_rows = row0 + n
+
+    def get_terms(self, row0: int = 0, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The stored lists of rows ``[row0, row0 + n)`` (default: to the end): ``(offsets int64 [n + 1] from 0, terms
+        uint32, tfs uint8, dl uint32 [n])`` -- per row the distinct terms ascending, their counts saturated at 255, and
+        the number of tokens the row was given.  Rows without a list are empty with ``dl = 0``."""
+        row0 = int(row0)
+        total = self.ntotal
+        n = total - row0 if n is None else int(n)
+        if row0 < 0 or n < 0 or row0 + n > total:
+            raise ValueError(f"get_terms: rows [{row0}, {row0 + n}) outside [0, {total})")
+        off = np.zeros(n + 1, dtype=np.int64)
+        dl = np.zeros(n, dtype=np.uint32)
+        self._handle()
+        if n == 0:
+            return off, np.zeros(0, np.uint32), np.zeros(0, np.uint8), dl
+        nat.check(nat.lib().css_index_get_terms(self._handle(), row0, n, off.ctypes.data, None, None))
+        ent = np.zeros(int(off[-1]), dtype=np.uint32)
+        nat.check(nat.lib().css_index_get_terms(self._handle(), row0, n, off.ctypes.data, ent.ctypes.data if ent.size else None,
+                                                dl.ctypes.data))
+        return off, ent >> np.uint32(8), (ent & np.uint32(255)).astype(np.uint8), dl
+
+    def term_stats(self, terms) -> Tuple[np.ndarray, int, int]:
+        """``(df int64 [m], ndocs, total_len)``: the number of rows that hold each asked term, ``ntotal``, and the sum
+        of the rows' lengths (``css_index_term_stats``).  Zeros on an index without lists."""
+        t = np.asarray(terms, dtype=np.int64).reshape(-1)
+        if t.size and (int(t.min()) < 0 or int(t.max()) >= nat.TERM_SPACE):
+            raise ValueError("term_stats: a term outside [0, 2^24)")
+        t = np.ascontiguousarray(t, dtype=np.uint32)
+        df = np.zeros(t.shape[0], dtype=np.int64)
+        ndocs, total = ctypes.c_int64(0), ctypes.c_int64(0)
+        nat.check(nat.lib().css_index_term_stats(self._handle(), t.ctypes.data if t.size else None, t.shape[0],
+                                                 df.ctypes.data if t.size else None, ctypes.byref(ndocs), ctypes.byref(total)))
+        return df, int(ndocs.value), int(total.value)
+
+    def search_hybrid(self, q, terms, weights, k: int, alpha: float, k1: float = 1.2, b: float = 0.75,
+                      avgdl: Optional[float] = None, normalize: bool = False,
+                      allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The ``k`` best rows for ONE query under ``score + alpha * lex`` (``css_index_search_hybrid``; L2:
+        ``distance - alpha * lex``, smaller is better), ``lex`` = the BM25 score of the query's ``terms`` (distinct ids,
+        at most 32) with the caller's ``weights`` (``lexical.bm25_weights``) against the row's term list, formed on the
+        device in fp32 in query-term order: ``(D, I, S, L)``, each ``[1, k]`` -- the fused value, the global id, the
+        row's RAW score and its ``lex``; best fused value first, ties to the lower id, padded like ``search_prior``
+        (``L = 0``).  Exact over ALL allowed rows: a row that holds a rare query term is found however far down the
+        plain ranking it sits.  ``avgdl=None`` takes ``total_len / ndocs`` from ``term_stats`` (1.0 when that is 0).
+        No terms, ``alpha = 0`` or an index without lists give ``search_prior`` without priors."""
+        a = _as_f32_2d(q, self.d, "search_hybrid")
+        if a.shape[0] != 1:
+            raise ValueError(f"search_hybrid: one query per call, got {a.shape[0]}")
+        t, w, k, alpha, k1, b, avgdl = hybrid_args(terms, weights, k, alpha, k1, b, avgdl)
+        self._handle()
+        if avgdl is None:
+            _, ndocs, total = self.term_stats(())
+            avgdl = total / ndocs if ndocs > 0 and total > 0 else 1.0
+        D, I = np.empty((1, k), dtype=np.float32), np.empty((1, k), dtype=np.int64)
+        S, L = np.empty((1, k), dtype=np.float32), np.empty((1, k), dtype=np.float32)
+        bits, bits_ptr = self._allow_bits(allow)
+        nat.check(nat.lib().css_index_search_hybrid(
+            self._handle(), a.ctypes.data, k, alpha, t.ctypes.data if t.size else None, w.ctypes.data if t.size else None,
+            t.shape[0], k1, b, float(np.float32(avgdl)), 1 if normalize else 0, bits_ptr, D.ctypes.data, I.ctypes.data,
+            S.ctypes.data, L.ctypes.data))
+        return D, I, S, L
 
     # -- diversified search (MMR) --------------------------------------------
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False,

@@ -72,6 +72,7 @@ class ShardedFlatIndex:
         self.segments: List[Tuple[int, int, int]] = []   # (local_row0, global_row0, n) of THIS shard
         self._seg_tensors = None
         self._dead: Optional[np.ndarray] = None          # tombstones in global numbering (replicated; mark_deleted)
+        self._terms_global = 0                           # leading GLOBAL rows that have term lists (replicated; set_terms)
 
     # -- building ----------------------------------------------------------
     def _append_segment(self, n_local: int, global_row0: int) -> None:
@@ -512,6 +513,77 @@ class ShardedFlatIndex:
         order = self._best_first(Dg, Ig, Ig < 0)[:k]   # best first by (fused value, id), pads last
         return Dg[order], Ig[order], Sg[order]
 
+    # -- term lists and hybrid search --------------------------------------------------------------------------
+    def set_terms(self, lists, row0: Optional[int] = None) -> None:
+        """``IndexFlat.set_terms`` in GLOBAL numbering (collective: every rank passes the same lists): the term lists
+        of the global rows ``[row0, row0 + n)``; ``row0 = None`` appends after the global rows that have lists, a lower
+        ``row0`` first drops the lists of all global rows ``>= row0``.  Every rank writes the part its shard holds
+        through the segment table.  Local order is global order within a shard, so the local lists stay append-only:
+        the shard's rows of the call are consecutive local rows that start at its first local row ``>= row0``."""
+        from .lexical import lists_as_csr
+
+        off, tok = lists_as_csr(lists)
+        n = off.shape[0] - 1
+        row0 = self._terms_global if row0 is None else int(row0)
+        if row0 < 0 or row0 + n > self.ntotal_global:
+            raise ValueError(f"set_terms: rows [{row0}, {row0 + n}) outside [0, {self.ntotal_global})")
+        if row0 > self._terms_global:
+            raise ValueError(f"set_terms: row0={row0} beyond the {self._terms_global} rows that have lists (lists are append-only)")
+        if n == 0 and row0 == self._terms_global:
+            return
+        local_row0 = sum(min(max(row0 - g0, 0), m) for _, g0, m in self.segments)   # local rows below global row0
+        parts_off, parts_tok = [np.zeros(1, np.int64)], []
+        for _, g0, m in self.segments:
+            lo, hi = max(g0, row0), min(g0 + m, row0 + n)
+            if hi > lo:
+                a, e = int(off[lo - row0]), int(off[hi - row0])
+                parts_off.append(off[lo - row0 + 1:hi - row0 + 1] - a + sum(t.shape[0] for t in parts_tok))
+                parts_tok.append(tok[a:e])
+        loff = np.concatenate(parts_off).astype(np.int64)
+        ltok = np.concatenate(parts_tok) if parts_tok else np.zeros(0, np.uint32)
+        self.local.set_terms((loff, ltok), row0=local_row0)
+        self._terms_global = row0 + n
+
+    def term_stats(self, terms):
+        """``IndexFlat.term_stats`` over the shards (collective): ``(df, ndocs, total_len)`` of the whole index -- the
+        integer sums of the shards' statistics."""
+        t = np.asarray(terms, dtype=np.int64).reshape(-1)
+        df, _, total = self.local.term_stats(t)
+        both = self._sum_over_ranks(np.concatenate([np.asarray(df, np.int64), np.array([total], np.int64)]))
+        return both[:-1].copy(), int(self.ntotal_global), int(both[-1])
+
+    def search_hybrid(self, q, terms, weights, k: int, alpha: float, k1: float = 1.2, b: float = 0.75,
+                      avgdl: Optional[float] = None, normalize: bool = False, allow=None):
+        """``IndexFlat.search_hybrid`` over the shards (collective): ``(D, I, S, L)`` with global ids on every rank.
+        Every shard scores with the CALLER's weights and constants (``avgdl=None``: the global statistics), so a row's
+        values do not depend on the shard that holds it and the merged result equals the unsharded one bit for bit.
+        The exchange is ``search_prior``'s with 20-byte records (id, D, S, L)."""
+        from .flat_index import hybrid_args
+
+        qa = self._queries(q)
+        if qa.shape[0] != 1:
+            raise ValueError(f"search_hybrid: one query per call, got {qa.shape[0]}")
+        t, w, k, alpha, k1, b, avgdl = hybrid_args(terms, weights, k, alpha, k1, b, avgdl)
+        if avgdl is None:
+            _, ndocs, total = self.term_stats(())
+            avgdl = total / ndocs if ndocs > 0 and total > 0 else 1.0
+        D, I, S, L = self.local.search_hybrid(qa, t, w, k, alpha, k1=k1, b=b, avgdl=avgdl, normalize=normalize,
+                                              allow=self._local_allow(allow))
+        D, S, L = (np.ascontiguousarray(a, dtype=np.float32) for a in (D, S, L))
+        I = np.ascontiguousarray(self._to_global_np(np.asarray(I, dtype=np.int64)))
+        if self._single():
+            return D, I, S, L
+        send = np.empty(20 * k, dtype=np.uint8)                      # [k int64 ids][k float32 D][k float32 S][k float32 L]
+        send[:8 * k] = I.reshape(-1).view(np.uint8)
+        for c, a in enumerate((D, S, L)):
+            send[(8 + 4 * c) * k:(12 + 4 * c) * k] = a.reshape(-1).view(np.uint8)
+        recv = self._all_gather_host(send)
+        Ig = np.concatenate([recv[r, :8 * k].view(np.int64) for r in range(self.world)])
+        Dg, Sg, Lg = (np.concatenate([recv[r, (8 + 4 * c) * k:(12 + 4 * c) * k].view(np.float32) for r in range(self.world)])
+                      for c in range(3))
+        order = self._best_first(Dg, Ig, Ig < 0)[:k]   # best first by (fused value, id), pads last
+        return Dg[order][None, :], Ig[order][None, :], Sg[order][None, :], Lg[order][None, :]
+
     # -- diversified search ------------------------------------------------------------------------------------
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
         """``IndexFlat.search_diverse`` over the shards (collective: every rank passes the same arguments): ``(D, I)``
@@ -697,6 +769,17 @@ class ShardedIndexFacade:
                         normalize: bool = False, exclude_ids: bool = True, allow=None):
         return self.sh.search_examples(pos, neg, pos_ids, neg_ids, k=int(k), gamma=float(gamma), normalize=normalize,
                                        exclude_ids=exclude_ids, allow=allow)
+
+    def set_terms(self, lists, row0: Optional[int] = None) -> None:
+        self.sh.set_terms(lists, row0=row0)
+
+    def term_stats(self, terms):
+        return self.sh.term_stats(terms)
+
+    def search_hybrid(self, q, terms, weights, k: int, alpha: float, k1: float = 1.2, b: float = 0.75,
+                      avgdl: Optional[float] = None, normalize: bool = False, allow=None):
+        return self.sh.search_hybrid(np.asarray(q, dtype=np.float32), terms, weights, int(k), float(alpha), k1=k1, b=b,
+                                     avgdl=avgdl, normalize=normalize, allow=allow)
 
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
         return self.sh.search_diverse(np.asarray(q, dtype=np.float32), int(k), lam=lam, fetch=fetch, normalize=normalize,

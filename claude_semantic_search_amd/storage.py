@@ -241,6 +241,9 @@ class HybridStorage:
         self._priors_half_life: Optional[float] = None
         self._priors_t_ref: Optional[float] = None
         self._priors_newest: Optional[float] = None
+        # search_hybrid: which rows of WHICH index object carry the term list of their chunk's text
+        self._terms_index: Optional[Any] = None
+        self._terms_synced = 0
 
         self.total_chunks: int = 0
         self.embedding_dim: int = self.config.embedding_dim
@@ -765,6 +768,76 @@ class HybridStorage:
             out.sort(key=lambda t: -t.size)   # (stable: equal sizes stay in centroid order)
             return out
 
+    def _sync_terms(self, ntotal: int) -> None:
+        """Bring the index's term lists up to date with SQLite: row = ``faiss_id``, list = ``lexical.terms_of`` of the
+        chunk's stored text; a row without a live chunk gets the empty list.  Only the tail ``[synced, ntotal)`` is
+        pushed after adds (the lists are append-only in row order); everything is pushed again when the index object
+        was replaced or compacted, by the rule of ``_sync_session_labels``."""
+        from .lexical import terms_of
+
+        if self._terms_index is not self.faiss_index:
+            self._terms_index, self._terms_synced = self.faiss_index, 0
+        lo = self._terms_synced
+        if lo >= ntotal:
+            return
+        lists: List[List[int]] = [[] for _ in range(ntotal - lo)]
+        rows = self.db.cursor().execute("SELECT faiss_id, text FROM chunks WHERE faiss_id >= ? AND faiss_id < ?",
+                                        (lo, ntotal)).fetchall()
+        for fid, text in rows:
+            lists[fid - lo] = terms_of(text)
+        self.faiss_index.set_terms(lists, row0=lo)
+        self._terms_synced = ntotal
+
+    def search_hybrid(self, query_text: str, query_embedding, config: Optional[SearchConfig] = None,
+                      filters: Optional[Dict[str, Any]] = None, alpha: float = 0.3, k1: float = 1.2,
+                      b: float = 0.75) -> List[SearchResult]:
+        """``top_k`` chunks ranked by ``similarity + alpha * lex`` (an L2 storage: ``distance - alpha * lex``), ``lex`` =
+        the BM25 score of the words of ``query_text`` against the chunk's stored text, normalised to ``[0, 1)`` by the
+        largest value the query can reach -- the keyword side a sentence encoder blurs: identifiers, error codes, flag
+        and file names.  The ranking runs inside the index over ALL allowed rows (``IndexFlat.search_hybrid``), not
+        over an over-fetched dense list: a chunk that holds a rare query word is found however far down the plain
+        ranking it sits.  Results come in FUSED order, each with its RAW similarity, to which
+        ``similarity_threshold`` applies (as in ``search_recent``).
+
+        Query terms are the distinct ``lexical.terms_of(query_text)`` in first-occurrence order; terms no chunk holds
+        are dropped, and beyond 32 terms the 32 rarest are kept (still in first-occurrence order).  Weights are
+        ``lexical.bm25_weights(..., normalized=True)``.  Without a usable term the ranking is that of ``search()``.
+        Words are matched whole after BERT's word splitting: no stemming, no stop list (the idf handles the latter).
+
+        Tombstones always go into the allow mask.  With ``filter_pushdown`` the filters go there too and ``k = top_k``
+        rows are fetched; without it and with filters, ``k = min(max(top_k, max_results), 128)`` rows are fetched and
+        filtered in rank order.  ``alpha = 0.3`` is a default NOBODY HAS TUNED: there is no relevance data offline.
+        An ``alpha``, ``k1`` or ``b`` the index would refuse raises ``ValueError``; an index object without
+        ``search_hybrid`` raises ``NotImplementedError``."""
+        from .lexical import bm25_weights, terms_of
+
+        a = float(alpha)
+        if not np.isfinite(a):
+            raise ValueError(f"search_hybrid: alpha={alpha} is not finite")
+        if self.faiss_index and not all(hasattr(self.faiss_index, m) for m in ("search_hybrid", "set_terms", "term_stats")):
+            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no hybrid search (search_hybrid / set_terms / term_stats)")
+        with self._lock:
+            frame = self._search_frame(config, query_embedding)
+            if frame is None or frame[0].top_k <= 0:
+                return []
+            cfg, ntotal, q = frame
+            allow = self._allow_for(filters, ntotal, tombstones_always=True)
+            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
+            k = max(1, min(k, fi.MAX_HYBRID_K))
+            self._sync_terms(ntotal)
+            terms = list(dict.fromkeys(terms_of(query_text)))
+            weights = np.zeros(0, np.float32)
+            if terms:
+                df, ndocs, _ = self.faiss_index.term_stats(terms)
+                known = [j for j in range(len(terms)) if df[j] > 0]
+                if len(known) > fi.MAX_QUERY_TERMS:   # the rarest, still in first-occurrence order
+                    known = sorted(sorted(known, key=lambda j: (int(df[j]), j))[:fi.MAX_QUERY_TERMS])
+                terms = [terms[j] for j in known]
+                weights = bm25_weights(np.asarray(df)[known], ndocs, k1=k1, normalized=True)
+            _, ids, sims, _ = self.faiss_index.search_hybrid(q, terms, weights, k, a, k1=k1, b=b,
+                                                             normalize=self.config.normalize_embeddings, allow=allow)
+            return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
+
     @staticmethod
     def _make_result(chunk_id: str, score: float, data: Dict[str, Any], cfg: SearchConfig) -> SearchResult:
         res = SearchResult(chunk_id=chunk_id, similarity=float(score))
@@ -1184,6 +1257,7 @@ class HybridStorage:
             self._mutations += 1
             self._labels_index = None   # (search_sessions pushes every label again: the rows were renumbered)
             self._priors_index = None   # (and search_recent every prior)
+            self._terms_index = None    # (and search_hybrid every term list)
             if not in_place:
                 old.close()
         self.logger.info("Flat index rebuilt")

@@ -322,6 +322,71 @@ int css_index_search_examples(css_index* ix, const float* vec_host, int nvec_pos
                               const uint32_t* allow_bits_host, float* D_host, int64_t* I_host,
                               float* S_host /* may be NULL */);
 
+/* Per-row term lists and hybrid search (the BM25 side that Elasticsearch, Vespa, Qdrant and Milvus pair with their
+ * dense search): the k best rows under the query score PLUS alpha times a BM25 score of the query's terms against the
+ * row's term list -- "which chunks contain hipErrorIllegalAddress" is a question a sentence encoder blurs.  As with the
+ * priors, a re-rank of an over-fetched dense list cannot do this: a row that holds a rare query term may sit anywhere
+ * below the fetched rows, so the fused value is the key of the sweep itself.
+ *  - Term lists.  A term is a uint32 below CSS_TERM_SPACE (2^24); what a term means (a hashed word) is the caller's.
+ *    Every row may carry the distinct terms of its text, each with a term frequency, and its length dl = the number of
+ *    tokens it was given, repeats included (at most CSS_MAX_ROW_TOKENS).  Stored per row: one uint32 per distinct term,
+ *    term << 8 | min(tf, 255), ascending by term, and one uint32 dl.  Lists are per index, in LOCAL row numbering, and
+ *    APPEND-ONLY in row order: with T the number of leading rows that have lists, css_index_set_terms takes the raw
+ *    tokens of rows [row0, row0 + n) as CSR (offsets_host [n + 1] from 0, tokens_host; repeats, any order and empty rows
+ *    are allowed; the library sorts and counts each row on the host).  row0 == T appends; row0 < T first drops the lists
+ *    of ALL rows >= row0, then appends (row0 = 0 is the rewrite); row0 > T and a range outside [0, ntotal) are
+ *    CSS_ERR_INVALID.  Rows >= T have the empty list and dl = 0.  Offsets that do not start at 0 or that decrease, a
+ *    token >= 2^24 (the message names the row) and a row of more than 2^20 tokens are CSS_ERR_INVALID, checked before
+ *    anything is written.  Locking and the ordering against pending asynchronous adds are those of css_index_set_groups.
+ *    css_index_get_terms reads the stored form of rows [row0, row0 + n) back: offsets_out [n + 1] from 0, the packed
+ *    entries and dl (either may be NULL).
+ *  - Storage.  Nothing is allocated before the first css_index_set_terms: an index that never receives terms pays
+ *    nothing.  Then: 4 bytes per entry, 12 per row with a list, and the statistics, a table df[2^24] of uint32 (64 MB:
+ *    the rows that hold a term) and a 64-bit total_len (the sum of dl), kept current by integer atomics, one add per
+ *    entry of the lists that come or go (integer sums do not depend on arrival order).  The lists follow the rows:
+ *    kept through capacity growth, none for appended rows, forgotten by css_index_reset, compacted by
+ *    css_index_remove_rows with the same keep bits -- afterwards css_index_get_terms and css_index_term_stats equal those
+ *    of a fresh index built from the kept rows and their lists (T becomes the kept rows below the old T).  The library
+ *    mirrors the row offsets on the host (8 bytes per row with a list).
+ *  - css_index_term_stats: df of the m asked terms (m <= 2^20), ndocs = ntotal, total_len.  Without lists: zeros, and
+ *    no device is touched.  The BM25 weights (an idf per term) are the caller's: lexical.bm25_weights.
+ *  - css_index_search_hybrid.  One request per call.  With m <= CSS_MAX_QUERY_TERMS distinct terms t_j and finite
+ *    weights w_j, and tf_j the STORED (saturated) count of t_j in row r, all in fp32 and in this order of operations
+ *    (the library is built with -ffp-contract=off; fp32 division is correctly rounded):
+ *        c0 = k1 * (1.0f - b);   c1 = (k1 * b) / avgdl;
+ *        K  = c0 + c1 * (float)dl_r;
+ *        g_j = ((float)tf_j * (k1 + 1.0f)) / ((float)tf_j + K);
+ *        lex_r = 0.0f;  for j = 0 .. m-1 in the caller's order:  if (tf_j > 0) lex_r = lex_r + w_j * g_j;
+ *    The sum runs in QUERY-TERM order, whatever the order of the entries in memory, so a float32 restatement gives the
+ *    same bits and a shard gives the same bits as one index.  The k best allowed rows under
+ *        inner product   f = fmaf(alpha, lex_r, s)        larger is better
+ *        squared L2      f = fmaf(-alpha, lex_r, dist)    smaller is better; f may be negative
+ *    which is css_index_search_prior with the lexical column in the place of the priors (the stored priors play no part
+ *    in this call).  D = f, best first, ties to the lower id; I = global ids; S (may be NULL) = the raw s / dist;
+ *    L (may be NULL) = lex of the returned rows; all [k].  Padding as in css_index_search_prior, with L = 0.
+ *  - Limits: 1 <= k <= 128; 0 <= m <= 32; alpha finite; k1 finite and >= 0; 0 <= b <= 1; avgdl finite and > 0; a NaN or
+ *    infinite value is CSS_ERR_INVALID and the message names which; a repeated query term is CSS_ERR_INVALID and the
+ *    message names it.  An empty index gives fully padded rows.  normalize_q and allow_bits_host are those of
+ *    css_index_search_prior.
+ *  - m == 0, alpha == 0 or an index without lists give css_index_search_prior on an index without priors bit for bit,
+ *    with S == D and L == 0.  Nothing depends on the reduced-precision row copies or on the search mode.
+ *  - On the device: k_lex_scores makes one pass over the lists (4 bytes per entry, 12 per row read, 4 per row written)
+ *    into a workspace column, the prior sweep runs with that column, one small launch gathers L.  A search never edits
+ *    the index.  One wait. */
+#define CSS_TERM_SPACE (1u << 24)
+#define CSS_MAX_ROW_TOKENS (1 << 20)
+#define CSS_MAX_QUERY_TERMS 32
+int css_index_set_terms(css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host /* [n+1] */,
+                        const uint32_t* tokens_host);
+int css_index_get_terms(css_index* ix, int64_t row0, int64_t n, int64_t* offsets_out /* [n+1], from 0 */,
+                        uint32_t* entries_out /* may be NULL */, uint32_t* dl_out /* may be NULL */);
+int css_index_term_stats(css_index* ix, const uint32_t* terms_host, int m, int64_t* df_out /* [m] */, int64_t* ndocs_out,
+                         int64_t* total_len_out);
+int css_index_search_hybrid(css_index* ix, const float* q_host /* [dim] */, int k, float alpha, const uint32_t* terms_host,
+                            const float* weights_host, int m, float k1, float b, float avgdl, int normalize_q,
+                            const uint32_t* allow_bits_host, float* D_host, int64_t* I_host,
+                            float* S_host /* may be NULL */, float* L_host /* may be NULL */);
+
 /* Rows by id (faiss reconstruct_batch): the stored fp32 rows of the n GLOBAL ids (id_base included), gathered on the
  * device, as [n, dim] floats exactly as they lie in device memory.  Repeated ids are allowed.  An id outside
  * [id_base, id_base + ntotal) is CSS_ERR_INVALID: the message names it and nothing is enqueued.  n == 0 is a no-op.
