@@ -50,14 +50,18 @@
 // search's turn at the shared workspaces (wait for the previous stream's event,
 // record at the end); CallScope is the lock and device frame of every search entry point and HostCall the whole frame
 // of the host ones (allow-bitmap and input up, result rows reserved, results back; pinned staging for small calls);
-// prep_queries is the query preparation of every search; sweep_grid is the grid of the exact sweeps.  The sweep body of
-// k_scan_small, k_range_small, k_scan_prior and k_scan_examples is deliberately NOT shared (css_knn_range.h says why).
+// prep_queries is the query preparation of every search; sweep_grid is the grid of the exact sweeps, sweep_variant and
+// sweep_slots the fan-out of their launchers over TT / METRIC and the 1 / 2 / 8 / 16 query slots, launch_merge_final the
+// plain merge behind them; RowColumn is a 4-byte-per-row column (labels, priors) and css_index::columns() the list every
+// row operation walks.  The sweep body of k_scan_small, k_range_small, k_scan_prior and k_scan_examples is deliberately
+// NOT shared (css_knn_range.h says why).
 #include "css_common.h"
 #include "css_devbuf.h"
 #include "css_knn_kernels.h"
 #include "../../include/css_synth.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdlib>
 #include <string>
@@ -71,6 +75,22 @@
 #include <vector>
 
 using namespace css;
+
+// A 4-byte value per row that follows the rows (the group labels, the priors): [cap] words, empty until first set
+// (column_for_write), every row that was never set at the default -- `fill` in every byte.  Its life is stated once:
+// column_alloc (first set, capacity growth, compaction), compact_column, column_check / column_for_write / column_get
+// (the set and get entry points), and one loop over css_index::columns() each in reallocate_rows, ingest,
+// css_index_reset and css_index_remove_rows.
+struct RowColumn {
+    const int fill;            // 0xFF: -1 as int32, 0x00: 0.0f
+    const char* const what;    // in error strings
+    DevBuf<int32_t> words;
+    template <typename T>
+    T* as() const {
+        static_assert(sizeof(T) == sizeof(int32_t), "a column holds 4-byte values");
+        return reinterpret_cast<T*>(words.p);
+    }
+};
 
 struct css_index {
     int dim = 0, dpad = 0, metric = 0, device = 0;
@@ -92,12 +112,12 @@ struct css_index {
     // row; read by the 1..4-query sweep and by the int8 MFMA scan of batches
     DevBuf<unsigned char> x8;      // [cap + 256][dpad]
     DevBuf<float> x8s;             // [cap + 256]
-    // group labels of the rows (css_index_set_groups): [cap], -1 = a group of its own; empty until labels are first set.
-    // Part of the row storage: it follows the rows through reallocation, ingest, reset and css_index_remove_rows
-    DevBuf<int32_t> labels;
-    // per-row priors (css_index_set_priors): [cap] fp32, 0 = no boost; empty until priors are first set.  Part of the row
-    // storage exactly like the labels
-    DevBuf<float> priors;
+    // the per-row columns, part of the row storage: group labels (css_index_set_groups), -1 = a group of its own, and
+    // fp32 priors (css_index_set_priors), 0 = no boost
+    RowColumn labels{0xFF, "hipMalloc(group labels)"};
+    RowColumn priors{0x00, "hipMalloc(priors)"};
+    static constexpr int kColumns = 2;
+    std::array<RowColumn*, kColumns> columns() { return {&labels, &priors}; }
     // per-row term lists (css_index_set_terms, css_lexical.h): the leading lex_rows rows own entries
     // [lex_off[r], lex_off[r + 1]) of lex_ent and a length lex_dl[r]; lex_df [CSS_TERM_SPACE] and lex_total [1] are the
     // statistics.  All empty until terms are first set (lex_df.p tells).  The buffers are sized by the lists, not by
@@ -248,8 +268,8 @@ struct Rows {
 };
 // the one place that reads the row fields of the index for a search; caller holds mu (shared is enough)
 Rows rows_of(const css_index* ix, const uint32_t* mask = nullptr) {
-    return Rows{ix->xb.p, ix->xnorm2.p, ix->xh.p, ix->x8.p, ix->x8s.p, ix->ntotal, ix->id_base, mask, ix->labels.p,
-                ix->priors.p};
+    return Rows{ix->xb.p, ix->xnorm2.p, ix->xh.p, ix->x8.p, ix->x8s.p, ix->ntotal, ix->id_base, mask, ix->labels.words.p,
+                ix->priors.as<float>()};
 }
 // caller holds mu exclusively
 void set_ntotal(css_index* ix, int64_t n) {
@@ -1682,26 +1702,28 @@ bool want_i8_only(css_index* ix, int64_t ncap) {
     return (double)ncap * ix->dpad * 5.0 <= 0.8 * (double)tot;
 }
 
+// `dst` (a column's own buffer, or its successor) with room for `cap` rows, every one at the column's default; on the
+// index's stream
+int column_alloc(css_index* ix, const RowColumn& col, int64_t cap, DevBuf<int32_t>* dst) {
+    const int rc = dst->grow_exact((size_t)cap, col.what);
+    if (rc != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemsetAsync(dst->p, col.fill, (size_t)cap * sizeof(int32_t), ix->stream));
+    return CSS_OK;
+}
+
 // (Re)allocate the row storage for exactly ncap rows, carrying the ntotal existing rows over.  The new arrays are
 // owned here until the swap at the end (whatever returns early frees them), the old ones from there on.
 int reallocate_rows(css_index* ix, int64_t ncap) {
     DevBuf<float> nxb, nn2, nx8s;
     DevBuf<unsigned short> nxh;
     DevBuf<unsigned char> nx8;
-    DevBuf<int32_t> nlab;
-    DevBuf<float> npri;
+    DevBuf<int32_t> ncol[css_index::kColumns];
+    const auto cols = ix->columns();
     int rc;
     if ((rc = nxb.grow_exact((size_t)ncap * ix->dpad, "hipMalloc(index rows)")) != CSS_OK) return rc;
-    // the label column only where labels were set: all -1 (0xFF bytes), then the existing rows' labels
-    if (ix->labels.p) {
-        if ((rc = nlab.grow_exact((size_t)ncap, "hipMalloc(group labels)")) != CSS_OK) return rc;
-        CSS_HIP_TRY(hipMemsetAsync(nlab.p, 0xFF, (size_t)ncap * sizeof(int32_t), ix->stream));
-    }
-    // the prior column likewise: all 0.0f, then the existing rows' priors
-    if (ix->priors.p) {
-        if ((rc = npri.grow_exact((size_t)ncap, "hipMalloc(priors)")) != CSS_OK) return rc;
-        CSS_HIP_TRY(hipMemsetAsync(npri.p, 0, (size_t)ncap * sizeof(float), ix->stream));
-    }
+    // a column only where it was set: all default, then the existing rows' values
+    for (int c = 0; c < css_index::kColumns; ++c)
+        if (cols[c]->words.p && (rc = column_alloc(ix, *cols[c], ncap, &ncol[c])) != CSS_OK) return rc;
     // +256: the coarse scan reads whole tiles of norms
     if ((rc = nn2.grow_exact((size_t)ncap + 256, "hipMalloc(index norms)")) != CSS_OK) return rc;
     // the shadow can only be carried over (or started on an empty index), never rebuilt here
@@ -1730,16 +1752,15 @@ int reallocate_rows(css_index* ix, int64_t ncap) {
         if (nxh.p)
             CSS_HIP_TRY(hipMemcpyAsync(nxh.p, ix->xh.p, (size_t)ix->ntotal * ix->dpad * sizeof(unsigned short),
                                        hipMemcpyDeviceToDevice, ix->stream));
-        if (nlab.p)
-            CSS_HIP_TRY(hipMemcpyAsync(nlab.p, ix->labels.p, (size_t)ix->ntotal * sizeof(int32_t), hipMemcpyDeviceToDevice,
-                                       ix->stream));
-        if (npri.p)
-            CSS_HIP_TRY(hipMemcpyAsync(npri.p, ix->priors.p, (size_t)ix->ntotal * sizeof(float), hipMemcpyDeviceToDevice,
-                                       ix->stream));
+        for (int c = 0; c < css_index::kColumns; ++c)
+            if (ncol[c].p)
+                CSS_HIP_TRY(hipMemcpyAsync(ncol[c].p, cols[c]->words.p, (size_t)ix->ntotal * sizeof(int32_t),
+                                           hipMemcpyDeviceToDevice, ix->stream));
     }
-    if (ix->ntotal > 0 || nlab.p || npri.p) CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
-    ix->labels.swap(nlab);
-    ix->priors.swap(npri);
+    bool filled = false;   // (a column's default fill is the one thing an empty index has in flight)
+    for (const auto& nc : ncol) filled |= nc.p != nullptr;
+    if (ix->ntotal > 0 || filled) CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    for (int c = 0; c < css_index::kColumns; ++c) cols[c]->words.swap(ncol[c]);
     ix->xb.swap(nxb);
     ix->xnorm2.swap(nn2);
     ix->xh.swap(nxh);
@@ -1784,10 +1805,9 @@ int ingest(css_index* ix, const float* x_dev, int64_t n, int normalize, bool syn
         unsigned short* dh = ix->xh.p ? ix->xh.p + (size_t)r0 * ix->dpad : nullptr;
         unsigned char* d8 = ix->x8.p ? ix->x8.p + (size_t)r0 * ix->dpad : nullptr;
         float* d8s = ix->x8.p ? ix->x8s.p + r0 : nullptr;
-        // appended rows are ungrouped (the slots may hold the labels of rows removed earlier)
-        if (ix->labels.p) CSS_HIP_TRY(hipMemsetAsync(ix->labels.p + r0, 0xFF, (size_t)nc * sizeof(int32_t), st));
-        // ... and carry no prior
-        if (ix->priors.p) CSS_HIP_TRY(hipMemsetAsync(ix->priors.p + r0, 0, (size_t)nc * sizeof(float), st));
+        // appended rows are at every column's default (the slots may hold the values of rows removed earlier)
+        for (RowColumn* col : ix->columns())
+            if (col->words.p) CSS_HIP_TRY(hipMemsetAsync(col->words.p + r0, col->fill, (size_t)nc * sizeof(int32_t), st));
         if (synth)
             hipLaunchKernelGGL(k_ingest_rows<true>, dim3(blocks), dim3(256), 0, st, nullptr, dst, n2, nc, ix->dim, ix->dpad,
                                normalize, seed, first_row + c0, dh, ix->maxn2.p, (float*)nullptr, d8, d8s);
@@ -1852,6 +1872,23 @@ struct FixArgs {
     int64_t* I = nullptr;
 };
 
+// The host fan-out of the exact fp32 sweeps (k_scan_small, k_range_small, k_scan_prior, k_scan_examples), once.
+// sweep_variant: f(TT, METRIC) with TT from dpad (12: the unrolled 768-float row, 0: any) and METRIC from the index.
+// sweep_slots: f(NQ) with the smallest NQ of 1 / 2 / 8 / 16 that holds nqc queries (an NQ=4 instantiation spills under
+// hipcc 7.2; 3..8 share NQ=8).  The arguments are std::integral_constants: decltype(X)::value is a template argument.
+template <int V>
+using IntC = std::integral_constant<int, V>;
+template <typename F>
+int sweep_variant(const css_index* ix, F&& f) {
+    const bool ip = ix->metric == CSS_METRIC_IP;
+    if (ix->dpad == 768) return ip ? f(IntC<12>(), IntC<CSS_METRIC_IP>()) : f(IntC<12>(), IntC<CSS_METRIC_L2>());
+    return ip ? f(IntC<0>(), IntC<CSS_METRIC_IP>()) : f(IntC<0>(), IntC<CSS_METRIC_L2>());
+}
+template <typename F>
+int sweep_slots(int nqc, F&& f) {
+    return nqc <= 1 ? f(IntC<1>()) : nqc <= 2 ? f(IntC<2>()) : nqc <= 8 ? f(IntC<8>()) : f(IntC<16>());
+}
+
 template <int NQ, int TT, int METRIC, bool FIX>
 int launch_scan_small_t(css_index* ix, const Rows& rows, const float* qpad, int nq_real, int k, int* gthr, const SweepGeom& sg,
                         hipStream_t st, const FixArgs& fx) {
@@ -1871,12 +1908,9 @@ int launch_scan_small_t(css_index* ix, const Rows& rows, const float* qpad, int 
 template <int NQ, bool FIX>
 int launch_scan_small_nq(css_index* ix, const Rows& rows, const float* qpad, int nq_real, int k, int* gthr, const SweepGeom& sg,
                          hipStream_t st, const FixArgs& fx = FixArgs()) {
-    const bool ip = ix->metric == CSS_METRIC_IP;
-    if (ix->dpad == 768)
-        return ip ? launch_scan_small_t<NQ, 12, CSS_METRIC_IP, FIX>(ix, rows, qpad, nq_real, k, gthr, sg, st, fx)
-                  : launch_scan_small_t<NQ, 12, CSS_METRIC_L2, FIX>(ix, rows, qpad, nq_real, k, gthr, sg, st, fx);
-    return ip ? launch_scan_small_t<NQ, 0, CSS_METRIC_IP, FIX>(ix, rows, qpad, nq_real, k, gthr, sg, st, fx)
-              : launch_scan_small_t<NQ, 0, CSS_METRIC_L2, FIX>(ix, rows, qpad, nq_real, k, gthr, sg, st, fx);
+    return sweep_variant(ix, [&](auto TT, auto M) {
+        return launch_scan_small_t<NQ, decltype(TT)::value, decltype(M)::value, FIX>(ix, rows, qpad, nq_real, k, gthr, sg, st, fx);
+    });
 }
 
 // the per-block top-k lists of the exact scans: [q][block][k] scores and rows
@@ -1891,6 +1925,10 @@ inline int host_f2key(float f) {
     return i >= 0 ? i : i ^ 0x7FFFFFFF;
 }
 
+// (defined behind search_chunk_small, where the merge kernels were first used: the code object keeps its kernel order)
+int launch_merge_final(css_index* ix, const Rows& rows, int q0, int nqc, int k, const SweepGeom& sg, float* D_dev,
+                       int64_t* I_dev, hipStream_t st);
+
 // Queries [q0, q0+nqc) (nqc <= 16) against the whole index, results to D/I rows q0...
 int search_chunk_small(css_index* ix, const Rows& rows, int q0, int nqc, int k, const SweepGeom& sg, float* D_dev,
                        int64_t* I_dev, hipStream_t st) {
@@ -1898,25 +1936,25 @@ int search_chunk_small(css_index* ix, const Rows& rows, int q0, int nqc, int k, 
     hipLaunchKernelGGL(k_fill_int, dim3(1), dim3(64), 0, st, gthr, nqc, host_f2key(-INFINITY));
     CSS_LAUNCH_CHECK();
     const float* qp = ix->qpad.p + (size_t)q0 * ix->dpad;
-    int rc;
-    if (nqc <= 1) rc = launch_scan_small_nq<1, false>(ix, rows, qp, nqc, k, gthr, sg, st);
-    else if (nqc <= 2) rc = launch_scan_small_nq<2, false>(ix, rows, qp, nqc, k, gthr, sg, st);
-    else if (nqc <= 8)  // (an NQ=4 instantiation spills under hipcc 7.2; 3..8 share NQ=8)
-         rc = launch_scan_small_nq<8, false>(ix, rows, qp, nqc, k, gthr, sg, st);
-    else rc = launch_scan_small_nq<16, false>(ix, rows, qp, nqc, k, gthr, sg, st);
-    if (rc != CSS_OK) return rc;
-    {
-        ProfScope ps("knn_merge", st);
-        if (ix->metric == CSS_METRIC_IP)
-            hipLaunchKernelGGL(k_merge_final<CSS_METRIC_IP>, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G,
-                               k, gthr, ix->qnorm2.p + q0, rows.id_base, D_dev + (size_t)q0 * k,
-                               I_dev + (size_t)q0 * k, 0, (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
-        else
-            hipLaunchKernelGGL(k_merge_final<CSS_METRIC_L2>, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G,
-                               k, gthr, ix->qnorm2.p + q0, rows.id_base, D_dev + (size_t)q0 * k,
-                               I_dev + (size_t)q0 * k, 0, (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
-        CSS_LAUNCH_CHECK();
-    }
+    const int rc = sweep_slots(nqc, [&](auto NQ) {
+        return launch_scan_small_nq<decltype(NQ)::value, false>(ix, rows, qp, nqc, k, gthr, sg, st);
+    });
+    return rc != CSS_OK ? rc : launch_merge_final(ix, rows, q0, nqc, k, sg, D_dev, I_dev, st);
+}
+
+// The plain merge behind a sweep: the [block][k] part lists of queries [q0, q0 + nqc) into D/I rows q0... (keys are
+// "larger is better" for both metrics; <L2> writes D = -key)
+int launch_merge_final(css_index* ix, const Rows& rows, int q0, int nqc, int k, const SweepGeom& sg, float* D_dev,
+                       int64_t* I_dev, hipStream_t st) {
+    ProfScope ps("knn_merge", st);
+    const auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G, k, ix->gthr.p + q0,
+                           ix->qnorm2.p + q0, rows.id_base, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, 0, (float*)nullptr,
+                           (uint32_t*)nullptr, (int*)nullptr);
+    };
+    if (ix->metric == CSS_METRIC_IP) go(k_merge_final<CSS_METRIC_IP>);
+    else go(k_merge_final<CSS_METRIC_L2>);
+    CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 
@@ -2667,12 +2705,9 @@ int launch_range_small_t(css_index* ix, const Rows& rows, const float* qpad, int
 template <int NQ>
 int launch_range_small_nq(css_index* ix, const Rows& rows, const float* qpad, int nq_real, float radius, int G,
                           int64_t gpb, hipStream_t st) {
-    const bool ip = ix->metric == CSS_METRIC_IP;
-    if (ix->dpad == 768)
-        return ip ? launch_range_small_t<NQ, 12, CSS_METRIC_IP>(ix, rows, qpad, nq_real, radius, G, gpb, st)
-                  : launch_range_small_t<NQ, 12, CSS_METRIC_L2>(ix, rows, qpad, nq_real, radius, G, gpb, st);
-    return ip ? launch_range_small_t<NQ, 0, CSS_METRIC_IP>(ix, rows, qpad, nq_real, radius, G, gpb, st)
-              : launch_range_small_t<NQ, 0, CSS_METRIC_L2>(ix, rows, qpad, nq_real, radius, G, gpb, st);
+    return sweep_variant(ix, [&](auto TT, auto M) {
+        return launch_range_small_t<NQ, decltype(TT)::value, decltype(M)::value>(ix, rows, qpad, nq_real, radius, G, gpb, st);
+    });
 }
 
 // queries per sweep: the largest instantiated NQ (16, 8, 2) whose query rows fit 64 KiB of LDS (dim <= 8192: at least 2)
@@ -2689,11 +2724,9 @@ int range_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
     int64_t gpb;
     sweep_grid(ix, rows, &G, &gpb);
     CSS_HIP_TRY(hipMemsetAsync(ix->range_cnt.p, 0, kRangeSlots * sizeof(unsigned int), st));
-    int rc;
-    if (nqc <= 1) rc = launch_range_small_nq<1>(ix, rows, qpad, nqc, radius, G, gpb, st);
-    else if (nqc <= 2) rc = launch_range_small_nq<2>(ix, rows, qpad, nqc, radius, G, gpb, st);
-    else if (nqc <= 8) rc = launch_range_small_nq<8>(ix, rows, qpad, nqc, radius, G, gpb, st);
-    else rc = launch_range_small_nq<16>(ix, rows, qpad, nqc, radius, G, gpb, st);
+    const int rc = sweep_slots(nqc, [&](auto NQ) {
+        return launch_range_small_nq<decltype(NQ)::value>(ix, rows, qpad, nqc, radius, G, gpb, st);
+    });
     if (rc != CSS_OK) return rc;
     CSS_HIP_TRY(hipMemcpyAsync(cnt_host, ix->range_cnt.p, kRangeSlots * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     CSS_HIP_TRY(hipStreamSynchronize(st));
@@ -2735,39 +2768,23 @@ int launch_scan_prior_t(css_index* ix, const Rows& rows, const float* qpad, int 
 template <int NQ>
 int launch_scan_prior_nq(css_index* ix, const Rows& rows, const float* qpad, int nq_real, int k, float weight, int* gthr,
                          const SweepGeom& sg, hipStream_t st) {
-    const bool ip = ix->metric == CSS_METRIC_IP;
-    if (ix->dpad == 768)
-        return ip ? launch_scan_prior_t<NQ, 12, CSS_METRIC_IP>(ix, rows, qpad, nq_real, k, weight, gthr, sg, st)
-                  : launch_scan_prior_t<NQ, 12, CSS_METRIC_L2>(ix, rows, qpad, nq_real, k, weight, gthr, sg, st);
-    return ip ? launch_scan_prior_t<NQ, 0, CSS_METRIC_IP>(ix, rows, qpad, nq_real, k, weight, gthr, sg, st)
-              : launch_scan_prior_t<NQ, 0, CSS_METRIC_L2>(ix, rows, qpad, nq_real, k, weight, gthr, sg, st);
+    return sweep_variant(ix, [&](auto TT, auto M) {
+        return launch_scan_prior_t<NQ, decltype(TT)::value, decltype(M)::value>(ix, rows, qpad, nq_real, k, weight, gthr, sg, st);
+    });
 }
 
 // search_chunk_small with the prior sweep: queries [q0, q0+nqc) (nqc <= sg.nq_sweep) against the rows, fused values
-// and ids to D/I rows q0...  The merge is k_merge_final unchanged (keys are "larger is better" for both metrics).
+// and ids to D/I rows q0...
 int search_chunk_prior(css_index* ix, const Rows& rows, int q0, int nqc, int k, float weight, const SweepGeom& sg,
                        float* D_dev, int64_t* I_dev, hipStream_t st) {
     int* gthr = ix->gthr.p + q0;
     hipLaunchKernelGGL(k_fill_int, dim3(1), dim3(64), 0, st, gthr, nqc, host_f2key(-INFINITY));
     CSS_LAUNCH_CHECK();
     const float* qp = ix->qpad.p + (size_t)q0 * ix->dpad;
-    int rc;
-    if (nqc <= 1) rc = launch_scan_prior_nq<1>(ix, rows, qp, nqc, k, weight, gthr, sg, st);
-    else if (nqc <= 2) rc = launch_scan_prior_nq<2>(ix, rows, qp, nqc, k, weight, gthr, sg, st);
-    else if (nqc <= 8) rc = launch_scan_prior_nq<8>(ix, rows, qp, nqc, k, weight, gthr, sg, st);   // (as search_chunk_small)
-    else rc = launch_scan_prior_nq<16>(ix, rows, qp, nqc, k, weight, gthr, sg, st);
-    if (rc != CSS_OK) return rc;
-    ProfScope ps("knn_merge", st);
-    if (ix->metric == CSS_METRIC_IP)
-        hipLaunchKernelGGL(k_merge_final<CSS_METRIC_IP>, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G, k, gthr,
-                           ix->qnorm2.p + q0, rows.id_base, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, 0,
-                           (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
-    else
-        hipLaunchKernelGGL(k_merge_final<CSS_METRIC_L2>, dim3(nqc), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G, k, gthr,
-                           ix->qnorm2.p + q0, rows.id_base, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, 0,
-                           (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
-    CSS_LAUNCH_CHECK();
-    return CSS_OK;
+    const int rc = sweep_slots(nqc, [&](auto NQ) {
+        return launch_scan_prior_nq<decltype(NQ)::value>(ix, rows, qp, nqc, k, weight, gthr, sg, st);
+    });
+    return rc != CSS_OK ? rc : launch_merge_final(ix, rows, q0, nqc, k, sg, D_dev, I_dev, st);
 }
 
 // ------------------------------------------------------------------ k-means step (css_kmeans.h)
@@ -2780,8 +2797,10 @@ int search_chunk_prior(css_index* ix, const Rows& rows, int q0, int nqc, int k, 
 inline size_t examples_lds(int nq_slots, int dpad, int k) {
     return (size_t)nq_slots * dpad * 4 + (size_t)k * 8 + 8 + kMaxExamples * 4;
 }
-// NQ of the sweep: the smallest of 1 / 2 / 8 / 16 that holds m examples (search_chunk_small's steps)
-inline int examples_slots(int m) { return m <= 1 ? 1 : m <= 2 ? 2 : m <= 8 ? 8 : 16; }
+// NQ of the sweep for m examples
+inline int examples_slots(int m) {
+    return sweep_slots(m, [](auto NQ) { return (int)decltype(NQ)::value; });
+}
 
 struct ExampleArgs {
     int npos, m;              // positives, all examples (the table is [m][dpad], positives first)
@@ -2807,39 +2826,23 @@ int launch_scan_examples_t(css_index* ix, const Rows& rows, const float* epad, i
 template <int NQ>
 int launch_scan_examples_nq(css_index* ix, const Rows& rows, const float* epad, int k, const ExampleArgs& ea, int* gthr,
                             const SweepGeom& sg, hipStream_t st) {
-    const bool ip = ix->metric == CSS_METRIC_IP;
-    if (ix->dpad == 768)
-        return ip ? launch_scan_examples_t<NQ, 12, CSS_METRIC_IP>(ix, rows, epad, k, ea, gthr, sg, st)
-                  : launch_scan_examples_t<NQ, 12, CSS_METRIC_L2>(ix, rows, epad, k, ea, gthr, sg, st);
-    return ip ? launch_scan_examples_t<NQ, 0, CSS_METRIC_IP>(ix, rows, epad, k, ea, gthr, sg, st)
-              : launch_scan_examples_t<NQ, 0, CSS_METRIC_L2>(ix, rows, epad, k, ea, gthr, sg, st);
+    return sweep_variant(ix, [&](auto TT, auto M) {
+        return launch_scan_examples_t<NQ, decltype(TT)::value, decltype(M)::value>(ix, rows, epad, k, ea, gthr, sg, st);
+    });
 }
 
-// The example sweep over the rows and the merge of its [block][k] part lists: k_merge_final unchanged, with ONE
-// "query" (keys are "larger is better" for both metrics; <L2> writes D = -key, which is f with its sign).
+// The example sweep over the rows and the merge of its [block][k] part lists: the plain merge with ONE "query" at
+// q0 = 0 (<L2>'s D = -key is f with its sign).
 int search_examples_sweep(css_index* ix, const Rows& rows, int k, const ExampleArgs& ea, const SweepGeom& sg, float* D_dev,
                           int64_t* I_dev, hipStream_t st) {
     int* gthr = ix->gthr.p;
     hipLaunchKernelGGL(k_fill_int, dim3(1), dim3(64), 0, st, gthr, 1, host_f2key(-INFINITY));
     CSS_LAUNCH_CHECK();
     const float* epad = ix->qpad.p;
-    int rc;
-    switch (examples_slots(ea.m)) {
-        case 1: rc = launch_scan_examples_nq<1>(ix, rows, epad, k, ea, gthr, sg, st); break;
-        case 2: rc = launch_scan_examples_nq<2>(ix, rows, epad, k, ea, gthr, sg, st); break;
-        case 8: rc = launch_scan_examples_nq<8>(ix, rows, epad, k, ea, gthr, sg, st); break;
-        default: rc = launch_scan_examples_nq<16>(ix, rows, epad, k, ea, gthr, sg, st); break;
-    }
-    if (rc != CSS_OK) return rc;
-    ProfScope ps("knn_merge", st);
-    if (ix->metric == CSS_METRIC_IP)
-        hipLaunchKernelGGL(k_merge_final<CSS_METRIC_IP>, dim3(1), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G, k, gthr,
-                           ix->qnorm2.p, rows.id_base, D_dev, I_dev, 0, (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
-    else
-        hipLaunchKernelGGL(k_merge_final<CSS_METRIC_L2>, dim3(1), dim3(256), 0, st, ix->part_s.p, ix->part_i.p, sg.G, k, gthr,
-                           ix->qnorm2.p, rows.id_base, D_dev, I_dev, 0, (float*)nullptr, (uint32_t*)nullptr, (int*)nullptr);
-    CSS_LAUNCH_CHECK();
-    return CSS_OK;
+    const int rc = sweep_slots(ea.m, [&](auto NQ) {
+        return launch_scan_examples_nq<decltype(NQ)::value>(ix, rows, epad, k, ea, gthr, sg, st);
+    });
+    return rc != CSS_OK ? rc : launch_merge_final(ix, rows, 0, 1, k, sg, D_dev, I_dev, st);
 }
 
 int merge_parts(const float* Dp, const int64_t* Ip, int nparts, int64_t stride_d, int64_t stride_i, int64_t nq, int k,
@@ -3217,9 +3220,9 @@ int css_index_reset(css_index* ix) {
     if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ws_ev, 0));   // a search enqueued on another stream still reads maxn2
     CSS_HIP_TRY(hipMemsetAsync(ix->maxn2.p, 0, 3 * sizeof(int), ix->stream));
     CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
-    CSS_HIP_TRY(ix->labels.drop());   // the labels go with the rows: the index is again one that never set any
-    CSS_HIP_TRY(ix->priors.drop());   // and so do the priors
-    return drop_terms(ix);            // and the term lists with their statistics
+    // the columns go with the rows: the index is again one that never set any
+    for (RowColumn* col : ix->columns()) CSS_HIP_TRY(col->words.drop());
+    return drop_terms(ix);   // and the term lists with their statistics
 }
 
 namespace {
@@ -3296,11 +3299,13 @@ int compact_rows(css_index* ix, const uint32_t* keep, int64_t n, int64_t first, 
     return CSS_OK;
 }
 
-// A 4-byte-per-row column (`src`: the labels, or the priors moved as bits) through the same keep bits, OUT OF PLACE
-// into `dst` (filled with the column's default beforehand): a second 4-byte-per-row
+// A column (moved as bits, whatever it holds) through the same keep bits, OUT OF PLACE into `dst` (column_alloc: at
+// the column's default beforehand): a second 4-byte-per-row
 // buffer has none of the overlap hazards of the row windows above, and the caller swaps it in.  Enqueued behind
 // compact_rows on the index's stream (it reuses compact_bits / compact_pre); `keep` stays valid until the caller waited.
-int compact_labels(css_index* ix, const uint32_t* keep, int64_t n, const int32_t* src, int32_t* dst) {
+int compact_column(css_index* ix, const uint32_t* keep, int64_t n, const RowColumn& col, const DevBuf<int32_t>& to) {
+    const int32_t* src = col.words.p;
+    int32_t* dst = to.p;
     const hipStream_t st = ix->stream;
     const int64_t words = (n + 31) / 32;
     const uint32_t tail_mask = (n & 31) ? ((1u << (n & 31)) - 1u) : 0xFFFFFFFFu;
@@ -3332,7 +3337,7 @@ inline unsigned lex_grid(const css_index* ix, int64_t count) {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((count + 255) / 256, (int64_t)ix->num_cus * 16));
 }
 
-// The term lists through the keep bits of css_index_remove_rows, OUT OF PLACE like compact_labels: the new offsets are
+// The term lists through the keep bits of css_index_remove_rows, OUT OF PLACE like compact_column: the new offsets are
 // a host prefix sum over the mirror, k_lex_move moves the lists of the kept rows and takes those of the removed rows
 // out of df and total_len.  Enqueued behind compact_rows on the index's stream; the caller waits, then commits.
 struct TermCompaction {
@@ -3407,33 +3412,24 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
     // pending asynchronous adds, and searches on other streams that still read the rows and maxn2
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
     if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ws_ev, 0));
-    DevBuf<int32_t> nlab;   // the compacted label column (only where labels were set)
-    if (ix->labels.p && kept > 0) {
-        int rc0;
-        if ((rc0 = nlab.grow_exact((size_t)ix->cap, "hipMalloc(group labels)")) != CSS_OK) return rc0;
-        CSS_HIP_TRY(hipMemsetAsync(nlab.p, 0xFF, (size_t)ix->cap * sizeof(int32_t), ix->stream));
-    }
-    DevBuf<float> npri;     // the compacted prior column (only where priors were set)
-    if (ix->priors.p && kept > 0) {
-        int rc0;
-        if ((rc0 = npri.grow_exact((size_t)ix->cap, "hipMalloc(priors)")) != CSS_OK) return rc0;
-        CSS_HIP_TRY(hipMemsetAsync(npri.p, 0, (size_t)ix->cap * sizeof(float), ix->stream));
-    }
+    DevBuf<int32_t> ncol[css_index::kColumns];   // the compacted columns (only those that were set)
+    const auto cols = ix->columns();
+    int rc = CSS_OK;
+    for (int c = 0; c < css_index::kColumns; ++c)
+        if (cols[c]->words.p && kept > 0 && (rc = column_alloc(ix, *cols[c], ix->cap, &ncol[c])) != CSS_OK) return rc;
     TermCompaction tc;      // the compacted term lists (only where terms were set)
     CSS_HIP_TRY(hipMemsetAsync(ix->maxn2.p, 0, 3 * sizeof(int), ix->stream));
     uint32_t patch = 0;
-    int rc = kept > 0 ? compact_rows(ix, keep_bits_host, n, first, &patch) : CSS_OK;
-    if (rc == CSS_OK && nlab.p) rc = compact_labels(ix, keep_bits_host, n, ix->labels.p, nlab.p);
-    if (rc == CSS_OK && npri.p)   // (a 4-byte column: moved as bits by the label kernel)
-        rc = compact_labels(ix, keep_bits_host, n, reinterpret_cast<const int32_t*>(ix->priors.p),
-                            reinterpret_cast<int32_t*>(npri.p));
+    if (kept > 0) rc = compact_rows(ix, keep_bits_host, n, first, &patch);
+    for (int c = 0; c < css_index::kColumns; ++c)
+        if (rc == CSS_OK && ncol[c].p) rc = compact_column(ix, keep_bits_host, n, *cols[c], ncol[c]);
     if (rc == CSS_OK && ix->lex_df.p && kept > 0) rc = compact_terms(ix, keep_bits_host, &tc);
     // later adds and searches on any stream are ordered behind the compaction (as css_index_reset)
     const hipError_t e = hipStreamSynchronize(ix->stream);
     if (rc != CSS_OK) return rc;
     if (e != hipSuccess) return css::hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
-    if (nlab.p) ix->labels.swap(nlab);
-    if (npri.p) ix->priors.swap(npri);
+    for (int c = 0; c < css_index::kColumns; ++c)
+        if (ncol[c].p) cols[c]->words.swap(ncol[c]);
     if (tc.built) tc.commit(ix);
     if (kept == 0 && (rc = drop_terms(ix)) != CSS_OK) return rc;   // emptied: as css_index_reset
     set_ntotal(ix, kept);
@@ -3817,21 +3813,45 @@ int css_index_search(css_index* ix, const float* q_host, int64_t nq, int k, int 
 }
 
 // ------------------------------------------------------------------ group labels and grouped search
+namespace {
+// What the set and get entry points of a column share.  The arguments (`fn`, `arg`: the entry point and its host
+// array in error strings); caller holds mu
+int column_check(const char* fn, const char* arg, int64_t row0, int64_t n, int64_t ntotal, const void* host) {
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ntotal - row0, "%s: rows [%lld, %lld + %lld) outside [0, %lld)", fn,
+                (long long)row0, (long long)row0, (long long)n, (long long)ntotal);
+    CSS_REQUIRE(n == 0 || host, "%s: %s is NULL", fn, arg);
+    return CSS_OK;
+}
+// The column ready for a set call's copies on the index's stream.  Rows appended on another stream write their default
+// there: they must have landed before values go over them.  The first values of this index: the column, every row at
+// the default.  Caller holds mu exclusively and the device
+int column_for_write(css_index* ix, RowColumn* col) {
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
+    return col->words.p ? CSS_OK : column_alloc(ix, *col, ix->cap, &col->words);
+}
+// Rows [row0, row0 + n) of the column to the host; a column that was never set answers its default
+int column_get(css_index* ix, const RowColumn& col, const char* fn, const char* arg, int64_t row0, int64_t n, void* out_host) {
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    const int rc = column_check(fn, arg, row0, n, ix->ntotal, out_host);
+    if (rc != CSS_OK || n == 0) return rc;
+    if (!col.words.p) {
+        memset(out_host, col.fill, (size_t)n * sizeof(int32_t));
+        return CSS_OK;
+    }
+    DeviceGuard g(ix->device);
+    if (ix->ingest_pending) CSS_HIP_TRY(hipEventSynchronize(ix->ingest_ev));
+    CSS_HIP_TRY(hipMemcpy(out_host, col.words.p + row0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return CSS_OK;
+}
+}  // namespace
+
 int css_index_set_groups(css_index* ix, int64_t row0, int64_t n, const int32_t* labels_host) {
     CSS_REQUIRE(ix, "css_index_set_groups: NULL index");
     std::unique_lock<std::shared_mutex> lk(ix->mu);
-    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_set_groups: rows [%lld, %lld + %lld) outside [0, %lld)",
-                (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
-    if (n == 0) return CSS_OK;
-    CSS_REQUIRE(labels_host, "css_index_set_groups: labels is NULL");
+    int rc = column_check("css_index_set_groups", "labels", row0, n, ix->ntotal, labels_host);
+    if (rc != CSS_OK || n == 0) return rc;
     DeviceGuard g(ix->device);
-    // rows appended on another stream write their -1 there: they must have landed before labels go over them
-    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
-    int rc;
-    if (!ix->labels.p) {   // first labels of this index: the column, every row ungrouped
-        if ((rc = ix->labels.grow_exact((size_t)ix->cap, "hipMalloc(group labels)")) != CSS_OK) return rc;
-        CSS_HIP_TRY(hipMemsetAsync(ix->labels.p, 0xFF, (size_t)ix->cap * sizeof(int32_t), ix->stream));
-    }
+    if ((rc = column_for_write(ix, &ix->labels)) != CSS_OK) return rc;
     // negative labels are stored as -1: through a bounded host buffer
     const int64_t chunk = 1ll << 20;
     std::vector<int32_t> buf;
@@ -3844,7 +3864,7 @@ int css_index_set_groups(css_index* ix, int64_t row0, int64_t n, const int32_t* 
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t m = std::min(chunk, n - r0);
         for (int64_t i = 0; i < m; ++i) buf[(size_t)i] = std::max<int32_t>(labels_host[r0 + i], -1);
-        CSS_HIP_TRY(hipMemcpyAsync(ix->labels.p + row0 + r0, buf.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice,
+        CSS_HIP_TRY(hipMemcpyAsync(ix->labels.words.p + row0 + r0, buf.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice,
                                    ix->stream));
         CSS_HIP_TRY(hipStreamSynchronize(ix->stream));   // (buf is written again)
     }
@@ -3853,20 +3873,7 @@ int css_index_set_groups(css_index* ix, int64_t row0, int64_t n, const int32_t* 
 
 int css_index_get_groups(css_index* ix, int64_t row0, int64_t n, int32_t* labels_out_host) {
     CSS_REQUIRE(ix, "css_index_get_groups: NULL index");
-    std::shared_lock<std::shared_mutex> lk(ix->mu);
-    const Rows rows = rows_of(ix);
-    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= rows.n - row0, "css_index_get_groups: rows [%lld, %lld + %lld) outside [0, %lld)",
-                (long long)row0, (long long)row0, (long long)n, (long long)rows.n);
-    if (n == 0) return CSS_OK;
-    CSS_REQUIRE(labels_out_host, "css_index_get_groups: labels_out is NULL");
-    if (!rows.labels) {
-        std::fill(labels_out_host, labels_out_host + n, (int32_t)-1);
-        return CSS_OK;
-    }
-    DeviceGuard g(ix->device);
-    if (ix->ingest_pending) CSS_HIP_TRY(hipEventSynchronize(ix->ingest_ev));
-    CSS_HIP_TRY(hipMemcpy(labels_out_host, rows.labels + row0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return CSS_OK;
+    return column_get(ix, ix->labels, "css_index_get_groups", "labels_out", row0, n, labels_out_host);
 }
 
 namespace {
@@ -4122,43 +4129,22 @@ int css_index_search_rows(css_index* ix, const int64_t* ids_host, int64_t nq, in
 int css_index_set_priors(css_index* ix, int64_t row0, int64_t n, const float* priors_host) {
     CSS_REQUIRE(ix, "css_index_set_priors: NULL index");
     std::unique_lock<std::shared_mutex> lk(ix->mu);
-    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_set_priors: rows [%lld, %lld + %lld) outside [0, %lld)",
-                (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
-    if (n == 0) return CSS_OK;
-    CSS_REQUIRE(priors_host, "css_index_set_priors: priors is NULL");
+    int rc = column_check("css_index_set_priors", "priors", row0, n, ix->ntotal, priors_host);
+    if (rc != CSS_OK || n == 0) return rc;
     // every value is looked at before anything is written
     for (int64_t i = 0; i < n; ++i)
         CSS_REQUIRE(std::isfinite(priors_host[i]), "css_index_set_priors: the prior of row %lld is %s (priors are finite)",
                     (long long)(row0 + i), std::isnan(priors_host[i]) ? "NaN" : "infinite");
     DeviceGuard g(ix->device);
-    // rows appended on another stream write their 0.0f there: they must have landed before priors go over them
-    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(ix->stream, ix->ingest_ev, 0));
-    int rc;
-    if (!ix->priors.p) {   // first priors of this index: the column, every row 0.0f
-        if ((rc = ix->priors.grow_exact((size_t)ix->cap, "hipMalloc(priors)")) != CSS_OK) return rc;
-        CSS_HIP_TRY(hipMemsetAsync(ix->priors.p, 0, (size_t)ix->cap * sizeof(float), ix->stream));
-    }
-    CSS_HIP_TRY(hipMemcpyAsync(ix->priors.p + row0, priors_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+    if ((rc = column_for_write(ix, &ix->priors)) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(ix->priors.as<float>() + row0, priors_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ix->stream));
     CSS_HIP_TRY(hipStreamSynchronize(ix->stream));   // (the copy reads the caller's memory)
     return CSS_OK;
 }
 
 int css_index_get_priors(css_index* ix, int64_t row0, int64_t n, float* priors_out_host) {
     CSS_REQUIRE(ix, "css_index_get_priors: NULL index");
-    std::shared_lock<std::shared_mutex> lk(ix->mu);
-    const Rows rows = rows_of(ix);
-    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= rows.n - row0, "css_index_get_priors: rows [%lld, %lld + %lld) outside [0, %lld)",
-                (long long)row0, (long long)row0, (long long)n, (long long)rows.n);
-    if (n == 0) return CSS_OK;
-    CSS_REQUIRE(priors_out_host, "css_index_get_priors: priors_out is NULL");
-    if (!rows.priors) {
-        std::fill(priors_out_host, priors_out_host + n, 0.0f);
-        return CSS_OK;
-    }
-    DeviceGuard g(ix->device);
-    if (ix->ingest_pending) CSS_HIP_TRY(hipEventSynchronize(ix->ingest_ev));
-    CSS_HIP_TRY(hipMemcpy(priors_out_host, rows.priors + row0, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return CSS_OK;
+    return column_get(ix, ix->priors, "css_index_get_priors", "priors_out", row0, n, priors_out_host);
 }
 
 namespace {

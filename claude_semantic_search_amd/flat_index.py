@@ -601,31 +601,40 @@ class IndexFlat:
             nat.lib().css_range_result_free(res)
         return lims, D, I
 
+    # -- per-row columns: the range check, and the setter and getter of a 4-byte column -----
+    def _row_range(self, what: str, row0, n) -> Tuple[int, int]:
+        """``(row0, n)`` as ints, ``n = None`` meaning "to the end"; raises unless ``[row0, row0 + n)`` are rows."""
+        row0 = int(row0)
+        total = self.ntotal
+        n = total - row0 if n is None else int(n)
+        if row0 < 0 or n < 0 or row0 + n > total:
+            raise ValueError(f"{what}: rows [{row0}, {row0 + n}) outside [0, {total})")
+        return row0, n
+
+    def _set_column(self, what: str, convert, values, row0) -> None:
+        a = convert(values)
+        row0, n = self._row_range(what, row0, a.shape[0])
+        if n:
+            nat.check(getattr(nat.lib(), "css_index_" + what)(self._handle(), row0, n, a.ctypes.data))
+
+    def _get_column(self, what: str, dtype, row0, n) -> np.ndarray:
+        row0, n = self._row_range(what, row0, n)
+        out = np.empty(n, dtype=dtype)
+        if n:
+            nat.check(getattr(nat.lib(), "css_index_" + what)(self._handle(), row0, n, out.ctypes.data))
+        return out
+
     # -- group labels and grouped search ------------------------------------
     def set_groups(self, labels, row0: int = 0) -> None:
         """Group labels of rows ``[row0, row0 + len(labels))`` in LOCAL row numbering (like ``allow``): an integer
         array that fits int32.  A negative label means "ungrouped" and is stored as ``-1``; rows never given a label
         are ungrouped too.  The labels follow the rows through growth, ``remove_ids`` (compacted with them) and
         ``reset`` (forgotten); rows added later start ungrouped."""
-        a = labels_as_int32(labels)
-        row0 = int(row0)
-        n = self.ntotal
-        if row0 < 0 or row0 + a.shape[0] > n:
-            raise ValueError(f"set_groups: rows [{row0}, {row0 + a.shape[0]}) outside [0, {n})")
-        if a.shape[0]:
-            nat.check(nat.lib().css_index_set_groups(self._handle(), row0, a.shape[0], a.ctypes.data))
+        self._set_column("set_groups", labels_as_int32, labels, row0)
 
     def get_groups(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """The labels of rows ``[row0, row0 + n)`` (default: to the end) as int32; ``-1`` = ungrouped."""
-        row0 = int(row0)
-        total = self.ntotal
-        n = total - row0 if n is None else int(n)
-        if row0 < 0 or n < 0 or row0 + n > total:
-            raise ValueError(f"get_groups: rows [{row0}, {row0 + n}) outside [0, {total})")
-        out = np.empty(n, dtype=np.int32)
-        if n:
-            nat.check(nat.lib().css_index_get_groups(self._handle(), row0, n, out.ctypes.data))
-        return out
+        return self._get_column("get_groups", np.int32, row0, n)
 
     def search_grouped(self, q, k: int, normalize: bool = False, allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """The ``k`` best GROUPS per query (``css_index_search_grouped``): ``(D[nq,k], I[nq,k], G[nq,k] int32)`` -- score
@@ -650,25 +659,11 @@ class IndexFlat:
         float32.  Rows never given one have ``0.0``.  NaN or infinity raises and writes nothing.  The priors follow
         the rows through growth, ``remove_ids`` (compacted with them) and ``reset`` (forgotten); rows added later start
         at ``0.0``."""
-        a = priors_as_f32(priors)
-        row0 = int(row0)
-        n = self.ntotal
-        if row0 < 0 or row0 + a.shape[0] > n:
-            raise ValueError(f"set_priors: rows [{row0}, {row0 + a.shape[0]}) outside [0, {n})")
-        if a.shape[0]:
-            nat.check(nat.lib().css_index_set_priors(self._handle(), row0, a.shape[0], a.ctypes.data))
+        self._set_column("set_priors", priors_as_f32, priors, row0)
 
     def get_priors(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """The priors of rows ``[row0, row0 + n)`` (default: to the end) as float32."""
-        row0 = int(row0)
-        total = self.ntotal
-        n = total - row0 if n is None else int(n)
-        if row0 < 0 or n < 0 or row0 + n > total:
-            raise ValueError(f"get_priors: rows [{row0}, {row0 + n}) outside [0, {total})")
-        out = np.empty(n, dtype=np.float32)
-        if n:
-            nat.check(nat.lib().css_index_get_priors(self._handle(), row0, n, out.ctypes.data))
-        return out
+        return self._get_column("get_priors", np.float32, row0, n)
 
     def search_prior(self, q, k: int, weight: float, normalize: bool = False,
                      allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -738,11 +733,7 @@ class IndexFlat:
         """The stored lists of rows ``[row0, row0 + n)`` (default: to the end): ``(offsets int64 [n + 1] from 0, terms
         uint32, tfs uint8, dl uint32 [n])`` -- per row the distinct terms ascending, their counts saturated at 255, and
         the number of tokens the row was given.  Rows without a list are empty with ``dl = 0``."""
-        row0 = int(row0)
-        total = self.ntotal
-        n = total - row0 if n is None else int(n)
-        if row0 < 0 or n < 0 or row0 + n > total:
-            raise ValueError(f"get_terms: rows [{row0}, {row0 + n}) outside [0, {total})")
+        row0, n = self._row_range("get_terms", row0, n)
         off = np.zeros(n + 1, dtype=np.int64)
         dl = np.zeros(n, dtype=np.uint32)
         self._handle()

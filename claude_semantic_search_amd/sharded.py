@@ -151,6 +151,23 @@ class ShardedFlatIndex:
         seg = np.clip(np.searchsorted(l0, I, side="right") - 1, 0, None)
         return np.where(I >= 0, I - l0[seg] + g0[seg], I)
 
+    def _overlaps(self, row0: int, n: int):
+        """The walk over the segment table: for every segment of THIS shard that overlaps the GLOBAL rows
+        ``[row0, row0 + n)``, ``(local row, global row, length)`` of the overlap."""
+        for l0, g0, m in self.segments:
+            lo, hi = max(g0, row0), min(g0 + m, row0 + n)
+            if hi > lo:
+                yield l0 + (lo - g0), lo, hi - lo
+
+    def _check_rows(self, what: str, row0: int, n: int) -> None:
+        if row0 < 0 or row0 + n > self.ntotal_global:
+            raise ValueError(f"{what}: rows [{row0}, {row0 + n}) outside [0, {self.ntotal_global})")
+
+    def _check_ids(self, what: str, ids: np.ndarray) -> None:
+        bad = ids[(ids < 0) | (ids >= self.ntotal_global)]
+        if bad.size:
+            raise ValueError(f"{what}: id {int(bad[0])} outside [0, {self.ntotal_global})")
+
     # -- pieces of the host-side searches ------------------------------------
     def _queries(self, q) -> np.ndarray:
         return np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.d)
@@ -196,6 +213,33 @@ class ShardedFlatIndex:
         """Sort order by ``lead`` ascending, then best score first (IP descending, L2 ascending), then ascending id."""
         return np.lexsort((ids, -scores if self.metric == 0 else scores, lead))
 
+    def _columns(self, I, cols, last=np.float32):
+        """The exchange of a local result of fixed-width columns: ``I`` the local ids and ``cols`` the 4-byte columns
+        that ride along (float32; the last one ``last``), ``[nq, k]`` or ``[k]`` each.  Returns ``(I, cols, local)``:
+        contiguous, ids GLOBAL.  One rank, or no query: the local answer is the answer (``local``, shapes as given).
+        Otherwise ONE all-gather of this rank's ``[ids | column ...]`` record, ``8 + 4 * len(cols)`` bytes per entry, and
+        every rank's entries side by side per query, ``[nq, world * k]``, best first by ``(cols[0], id)`` with the
+        pads last."""
+        I = np.ascontiguousarray(self._to_global_np(np.asarray(I, dtype=np.int64)))
+        cols = [np.ascontiguousarray(c, dtype=np.float32 if j + 1 < len(cols) else last) for j, c in enumerate(cols)]
+        if self._single() or I.size == 0:
+            return I, cols, True
+        k, n = I.shape[-1], I.size
+        send = np.empty((8 + 4 * len(cols)) * n, dtype=np.uint8)
+        send[:8 * n] = I.reshape(-1).view(np.uint8)
+        for c, a in enumerate(cols):
+            send[(8 + 4 * c) * n:(12 + 4 * c) * n] = a.reshape(-1).view(np.uint8)
+        recv = self._all_gather_host(send)
+        side_by_side = lambda lo, hi, dt: np.concatenate(
+            [recv[r, lo * n:hi * n].view(dt).reshape(-1, k) for r in range(self.world)], axis=1)
+        Ig = side_by_side(0, 8, np.int64)
+        out = [side_by_side(8 + 4 * c, 12 + 4 * c, a.dtype) for c, a in enumerate(cols)]
+        for j in range(Ig.shape[0]):
+            order = self._best_first(out[0][j], Ig[j], Ig[j] < 0)
+            for a in [Ig] + out:
+                a[j] = a[j][order]
+        return Ig, out, False
+
     # -- searching ---------------------------------------------------------
     def _merge_packed_hip(self, recv, nq: int, k: int, record: int):
         import torch
@@ -219,7 +263,7 @@ class ShardedFlatIndex:
         if g.shape[0] != self.ntotal_global:
             raise ValueError(f"mask has {g.shape[0]} entries, the sharded index {self.ntotal_global} rows")
         out = np.zeros(self.shard_sizes[self.rank], dtype=g.dtype)
-        for l0, g0, n in self.segments:
+        for l0, g0, n in self._overlaps(0, self.ntotal_global):
             out[l0:l0 + n] = g[g0:g0 + n]
         return out
 
@@ -359,12 +403,9 @@ class ShardedFlatIndex:
 
         g = labels_as_int32(global_labels)
         row0 = int(row0)
-        if row0 < 0 or row0 + g.shape[0] > self.ntotal_global:
-            raise ValueError(f"set_groups: rows [{row0}, {row0 + g.shape[0]}) outside [0, {self.ntotal_global})")
-        for l0, g0, n in self.segments:
-            lo, hi = max(g0, row0), min(g0 + n, row0 + g.shape[0])
-            if hi > lo:
-                self.local.set_groups(g[lo - row0:hi - row0], row0=l0 + (lo - g0))
+        self._check_rows("set_groups", row0, g.shape[0])
+        for l0, g0, n in self._overlaps(row0, g.shape[0]):
+            self.local.set_groups(g[g0 - row0:g0 - row0 + n], row0=l0)
 
     def search_grouped(self, q, k: int, normalize: bool = False, allow=None):
         """``IndexFlat.search_grouped`` over the shards: ``(D, I, G)`` with global ids on every rank.  Every rank runs
@@ -375,28 +416,12 @@ class ShardedFlatIndex:
         shard also ranks above it globally.  With one rank there is no exchange."""
         from .flat_index import MAX_GROUP_K, collapse_groups
 
-        qa = self._queries(q)
-        nq, k = qa.shape[0], int(k)
+        qa, k = self._queries(q), int(k)
         if k < 1 or k > MAX_GROUP_K:
             raise ValueError(f"k={k} outside [1, {MAX_GROUP_K}]")
         D, I, G = self.local.search_grouped(qa, k, normalize=normalize, allow=self._local_allow(allow))
-        D, G = np.ascontiguousarray(D, dtype=np.float32), np.ascontiguousarray(G, dtype=np.int32)
-        I = np.ascontiguousarray(self._to_global_np(np.asarray(I, dtype=np.int64)))
-        if self._single() or nq == 0:
-            return D, I, G
-        n = nq * k
-        send = np.empty(16 * n, dtype=np.uint8)                      # [n int64 ids][n float32 scores][n int32 labels]
-        send[:8 * n] = I.reshape(-1).view(np.uint8)
-        send[8 * n:12 * n] = D.reshape(-1).view(np.uint8)
-        send[12 * n:] = G.reshape(-1).view(np.uint8)
-        recv = self._all_gather_host(send)
-        Ig = np.concatenate([recv[r, :8 * n].view(np.int64).reshape(nq, k) for r in range(self.world)], axis=1)
-        Dg = np.concatenate([recv[r, 8 * n:12 * n].view(np.float32).reshape(nq, k) for r in range(self.world)], axis=1)
-        Gg = np.concatenate([recv[r, 12 * n:].view(np.int32).reshape(nq, k) for r in range(self.world)], axis=1)
-        for j in range(nq):   # best first by (score, id), pads last
-            order = self._best_first(Dg[j], Ig[j], Ig[j] < 0)
-            Ig[j], Dg[j], Gg[j] = Ig[j][order], Dg[j][order], Gg[j][order]
-        return collapse_groups(Dg, Ig, Gg, k, self.metric)
+        I, (D, G), local = self._columns(I, (D, G), last=np.int32)   # 16-byte (id, score, label) records
+        return (D, I, G) if local else collapse_groups(D, I, G, k, self.metric)
 
     # -- prior-weighted search ---------------------------------------------------------------------------------
     def set_priors(self, global_priors, row0: int = 0) -> None:
@@ -407,12 +432,9 @@ class ShardedFlatIndex:
 
         p = priors_as_f32(global_priors)
         row0 = int(row0)
-        if row0 < 0 or row0 + p.shape[0] > self.ntotal_global:
-            raise ValueError(f"set_priors: rows [{row0}, {row0 + p.shape[0]}) outside [0, {self.ntotal_global})")
-        for l0, g0, n in self.segments:
-            lo, hi = max(g0, row0), min(g0 + n, row0 + p.shape[0])
-            if hi > lo:
-                self.local.set_priors(p[lo - row0:hi - row0], row0=l0 + (lo - g0))
+        self._check_rows("set_priors", row0, p.shape[0])
+        for l0, g0, n in self._overlaps(row0, p.shape[0]):
+            self.local.set_priors(p[g0 - row0:g0 - row0 + n], row0=l0)
 
     def search_prior(self, q, k: int, weight: float, normalize: bool = False, allow=None):
         """``IndexFlat.search_prior`` over the shards: ``(D, I, S)`` with global ids on every rank.  Every rank runs the
@@ -422,32 +444,14 @@ class ShardedFlatIndex:
         shard.  With one rank there is no exchange."""
         from .flat_index import MAX_PRIOR_K
 
-        qa = self._queries(q)
-        nq, k, weight = qa.shape[0], int(k), float(weight)
+        qa, k, weight = self._queries(q), int(k), float(weight)
         if k < 1 or k > MAX_PRIOR_K:
             raise ValueError(f"k={k} outside [1, {MAX_PRIOR_K}]")
         if not np.isfinite(weight):
             raise ValueError(f"weight={weight} is not finite")
         D, I, S = self.local.search_prior(qa, k, weight, normalize=normalize, allow=self._local_allow(allow))
-        D, S = np.ascontiguousarray(D, dtype=np.float32), np.ascontiguousarray(S, dtype=np.float32)
-        I = np.ascontiguousarray(self._to_global_np(np.asarray(I, dtype=np.int64)))
-        if self._single() or nq == 0:
-            return D, I, S
-        n = nq * k
-        send = np.empty(16 * n, dtype=np.uint8)                      # [n int64 ids][n float32 D][n float32 S]
-        send[:8 * n] = I.reshape(-1).view(np.uint8)
-        send[8 * n:12 * n] = D.reshape(-1).view(np.uint8)
-        send[12 * n:] = S.reshape(-1).view(np.uint8)
-        recv = self._all_gather_host(send)
-        Ig = np.concatenate([recv[r, :8 * n].view(np.int64).reshape(nq, k) for r in range(self.world)], axis=1)
-        Dg = np.concatenate([recv[r, 8 * n:12 * n].view(np.float32).reshape(nq, k) for r in range(self.world)], axis=1)
-        Sg = np.concatenate([recv[r, 12 * n:].view(np.float32).reshape(nq, k) for r in range(self.world)], axis=1)
-        Do, Io, So = (np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int64),
-                      np.empty((nq, k), dtype=np.float32))
-        for j in range(nq):   # best first by (fused value, id), pads last
-            order = self._best_first(Dg[j], Ig[j], Ig[j] < 0)[:k]
-            Do[j], Io[j], So[j] = Dg[j][order], Ig[j][order], Sg[j][order]
-        return Do, Io, So
+        I, (D, S), _ = self._columns(I, (D, S))   # 16-byte (id, fused value, raw score) records
+        return tuple(np.ascontiguousarray(a[..., :k]) for a in (D, I, S))
 
     # -- search by examples ------------------------------------------------------------------------------------
     def _local_ids(self, global_ids: np.ndarray) -> np.ndarray:
@@ -479,9 +483,7 @@ class ShardedFlatIndex:
         nids = ip.shape[0] + ineg.shape[0]
         k, gamma = example_args(k, gamma, vp.shape[0] + ip.shape[0], vp.shape[0] + vn.shape[0] + nids)
         ids = np.concatenate([ip, ineg])
-        bad = ids[(ids < 0) | (ids >= self.ntotal_global)]
-        if bad.size:
-            raise ValueError(f"search_examples: id {int(bad[0])} outside [0, {self.ntotal_global})")
+        self._check_ids(what, ids)
         if self._single():
             D, I, S = self.local.search_examples(vp, vn, self._local_ids(ip), self._local_ids(ineg), k=k, gamma=gamma,
                                                  normalize=normalize, exclude_ids=exclude_ids,
@@ -499,19 +501,9 @@ class ShardedFlatIndex:
         D, I, S = self.local.search_examples(np.concatenate([vp, rows[:ip.shape[0]]]), np.concatenate([vn, rows[ip.shape[0]:]]),
                                              k=kk, gamma=gamma, normalize=False, exclude_ids=False,
                                              allow=self._local_allow(allow))
-        I = np.ascontiguousarray(self._to_global_np(np.asarray(I, dtype=np.int64)))
-        send = np.empty(16 * kk, dtype=np.uint8)                     # [kk int64 ids][kk float32 D][kk float32 S]
-        send[:8 * kk] = I.view(np.uint8)
-        send[8 * kk:12 * kk] = np.ascontiguousarray(D, dtype=np.float32).view(np.uint8)
-        send[12 * kk:] = np.ascontiguousarray(S, dtype=np.float32).view(np.uint8)
-        recv = self._all_gather_host(send)
-        Ig = np.concatenate([recv[r, :8 * kk].view(np.int64) for r in range(self.world)])
-        Dg = np.concatenate([recv[r, 8 * kk:12 * kk].view(np.float32) for r in range(self.world)])
-        Sg = np.concatenate([recv[r, 12 * kk:].view(np.float32) for r in range(self.world)])
-        keep = ~np.isin(Ig, drop)
-        Ig, Dg, Sg = Ig[keep], Dg[keep], Sg[keep]
-        order = self._best_first(Dg, Ig, Ig < 0)[:k]   # best first by (fused value, id), pads last
-        return Dg[order], Ig[order], Sg[order]
+        I, (D, S), _ = self._columns(I, (D, S))   # 16-byte (id, D, S) records
+        keep = np.flatnonzero(~np.isin(I[0], drop))[:k]
+        return D[0][keep], I[0][keep], S[0][keep]
 
     # -- term lists and hybrid search --------------------------------------------------------------------------
     def set_terms(self, lists, row0: Optional[int] = None) -> None:
@@ -525,20 +517,17 @@ class ShardedFlatIndex:
         off, tok = lists_as_csr(lists)
         n = off.shape[0] - 1
         row0 = self._terms_global if row0 is None else int(row0)
-        if row0 < 0 or row0 + n > self.ntotal_global:
-            raise ValueError(f"set_terms: rows [{row0}, {row0 + n}) outside [0, {self.ntotal_global})")
+        self._check_rows("set_terms", row0, n)
         if row0 > self._terms_global:
             raise ValueError(f"set_terms: row0={row0} beyond the {self._terms_global} rows that have lists (lists are append-only)")
         if n == 0 and row0 == self._terms_global:
             return
         local_row0 = sum(min(max(row0 - g0, 0), m) for _, g0, m in self.segments)   # local rows below global row0
         parts_off, parts_tok = [np.zeros(1, np.int64)], []
-        for _, g0, m in self.segments:
-            lo, hi = max(g0, row0), min(g0 + m, row0 + n)
-            if hi > lo:
-                a, e = int(off[lo - row0]), int(off[hi - row0])
-                parts_off.append(off[lo - row0 + 1:hi - row0 + 1] - a + sum(t.shape[0] for t in parts_tok))
-                parts_tok.append(tok[a:e])
+        for _, lo, m in self._overlaps(row0, n):
+            a, e = int(off[lo - row0]), int(off[lo - row0 + m])
+            parts_off.append(off[lo - row0 + 1:lo - row0 + m + 1] - a + sum(t.shape[0] for t in parts_tok))
+            parts_tok.append(tok[a:e])
         loff = np.concatenate(parts_off).astype(np.int64)
         ltok = np.concatenate(parts_tok) if parts_tok else np.zeros(0, np.uint32)
         self.local.set_terms((loff, ltok), row0=local_row0)
@@ -557,7 +546,7 @@ class ShardedFlatIndex:
         """``IndexFlat.search_hybrid`` over the shards (collective): ``(D, I, S, L)`` with global ids on every rank.
         Every shard scores with the CALLER's weights and constants (``avgdl=None``: the global statistics), so a row's
         values do not depend on the shard that holds it and the merged result equals the unsharded one bit for bit.
-        The exchange is ``search_prior``'s with 20-byte records (id, D, S, L)."""
+        The exchange moves 20-byte records (id, D, S, L); every rank keeps the first ``k`` by ``(D, id)``."""
         from .flat_index import hybrid_args
 
         qa = self._queries(q)
@@ -569,20 +558,8 @@ class ShardedFlatIndex:
             avgdl = total / ndocs if ndocs > 0 and total > 0 else 1.0
         D, I, S, L = self.local.search_hybrid(qa, t, w, k, alpha, k1=k1, b=b, avgdl=avgdl, normalize=normalize,
                                               allow=self._local_allow(allow))
-        D, S, L = (np.ascontiguousarray(a, dtype=np.float32) for a in (D, S, L))
-        I = np.ascontiguousarray(self._to_global_np(np.asarray(I, dtype=np.int64)))
-        if self._single():
-            return D, I, S, L
-        send = np.empty(20 * k, dtype=np.uint8)                      # [k int64 ids][k float32 D][k float32 S][k float32 L]
-        send[:8 * k] = I.reshape(-1).view(np.uint8)
-        for c, a in enumerate((D, S, L)):
-            send[(8 + 4 * c) * k:(12 + 4 * c) * k] = a.reshape(-1).view(np.uint8)
-        recv = self._all_gather_host(send)
-        Ig = np.concatenate([recv[r, :8 * k].view(np.int64) for r in range(self.world)])
-        Dg, Sg, Lg = (np.concatenate([recv[r, (8 + 4 * c) * k:(12 + 4 * c) * k].view(np.float32) for r in range(self.world)])
-                      for c in range(3))
-        order = self._best_first(Dg, Ig, Ig < 0)[:k]   # best first by (fused value, id), pads last
-        return Dg[order][None, :], Ig[order][None, :], Sg[order][None, :], Lg[order][None, :]
+        I, (D, S, L), _ = self._columns(I, (D, S, L))
+        return tuple(np.ascontiguousarray(a[..., :k]) for a in (D, I, S, L))
 
     # -- diversified search ------------------------------------------------------------------------------------
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
@@ -624,9 +601,7 @@ class ShardedFlatIndex:
         kmax = MAX_K - 1 if exclude_self else MAX_K
         if k < 1 or k > kmax:
             raise ValueError(f"k={k} outside [1, {kmax}]")
-        bad = a[(a < 0) | (a >= self.ntotal_global)]
-        if bad.size:
-            raise ValueError(f"search_by_ids: id {int(bad[0])} outside [0, {self.ntotal_global})")
+        self._check_ids("search_by_ids", a)
         if a.shape[0] == 0:
             return np.empty((0, k), dtype=np.float32), np.empty((0, k), dtype=np.int64)
         D, I = self.search(self._owned_rows(a), k + 1 if exclude_self else k, normalize=False, allow=allow)
@@ -638,10 +613,8 @@ class ShardedFlatIndex:
         shard: every rank fills in the rows it owns and ONE sum all-reduce of the zero-filled blocks completes them
         (save / backup / compaction paths only -- never on the search path)."""
         out = np.zeros((int(n), self.d), dtype=np.float32)
-        for l0, g0, m in self.segments:
-            lo, hi = max(g0, row0), min(g0 + m, row0 + n)
-            if hi > lo:
-                out[lo - row0:hi - row0] = self.local.reconstruct_n(l0 + (lo - g0), hi - lo)
+        for l0, g0, m in self._overlaps(row0, n):
+            out[g0 - row0:g0 - row0 + m] = self.local.reconstruct_n(l0, m)
         return self._sum_over_ranks(out)
 
     def reconstruct_batch(self, ids) -> np.ndarray:
@@ -650,9 +623,7 @@ class ShardedFlatIndex:
         from .flat_index import ids_as_int64
 
         a = ids_as_int64(ids, "reconstruct_batch")
-        bad = a[(a < 0) | (a >= self.ntotal_global)]
-        if bad.size:
-            raise ValueError(f"reconstruct_batch: id {int(bad[0])} outside [0, {self.ntotal_global})")
+        self._check_ids("reconstruct_batch", a)
         out = np.zeros((a.shape[0], self.d), dtype=np.float32)
         loc = self._local_ids(a)
         own = np.flatnonzero(loc >= 0)
@@ -802,7 +773,7 @@ class ShardedIndexFacade:
                              max_points_per_centroid=max_points_per_centroid)
         a = np.zeros(self.ntotal, dtype=np.int64)
         d = np.zeros(self.ntotal, dtype=np.float32)
-        for l0, g0, n in self.sh.segments:
+        for l0, g0, n in self.sh._overlaps(0, self.ntotal):
             a[g0:g0 + n] = res.assign[l0:l0 + n].astype(np.int64) + 1   # (0 = not this shard's row)
             d[g0:g0 + n] = res.dist[l0:l0 + n]
         a, d = self.sh._sum_over_ranks(a), self.sh._sum_over_ranks(d)

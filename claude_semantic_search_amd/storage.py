@@ -34,7 +34,7 @@ import threading
 from dataclasses import dataclass
 from datetime import datetime, timezone
 from pathlib import Path
-from typing import Any, Dict, List, Optional
+from typing import Any, Callable, Dict, List, Optional
 
 import numpy as np
 
@@ -208,6 +208,20 @@ def timestamp_days(ts) -> float:
         return float("nan")
 
 
+class _Synced:
+    """Which rows of WHICH index object already carry a per-row column that is pushed lazily, in front of the search
+    that reads it (session labels, recency priors, term lists).  A fresh one is synced with no index."""
+
+    index: Optional[Any] = None
+    rows = 0
+
+    def rows_of(self, index) -> int:
+        """Rows of ``index`` that carry the column; another object than last time is adopted with none."""
+        if self.index is not index:
+            self.index, self.rows = index, 0
+        return self.rows
+
+
 class HybridStorage:
     def __init__(self, config: Optional[StorageConfig] = None) -> None:
         self.config: StorageConfig = config or StorageConfig()
@@ -229,21 +243,15 @@ class HybridStorage:
         self._saved_rows = -1  # rows known to be in index_path (-1: unknown)
         self._allow_cache: Dict[str, Any] = {}  # filter key -> (stamp, allow mask); push-down only
         self._mutations = 0  # bumped by every change of the chunk set (part of the allow-cache stamp)
-        # search_sessions: dense group labels per session_id (order of first appearance by faiss_id), and which rows
-        # of WHICH index object already carry theirs (labels are pushed lazily, in front of a grouped search)
+        # the lazily pushed columns of search_sessions (labels), search_recent (priors) and search_hybrid (term lists)
+        self._labels, self._priors, self._terms = _Synced(), _Synced(), _Synced()
+        # search_sessions: dense group labels per session_id (order of first appearance by faiss_id)
         self._session_labels: Dict[str, int] = {}
-        self._labels_index: Optional[Any] = None
-        self._labels_synced = 0
-        # search_recent: which rows of WHICH index object carry their recency prior, for which half-life and reference
-        # time (days since the epoch); the newest timestamp seen so far
-        self._priors_index: Optional[Any] = None
-        self._priors_synced = 0
+        # search_recent: the half-life and reference time (days since the epoch) the priors are stored for; the newest
+        # timestamp seen so far
         self._priors_half_life: Optional[float] = None
         self._priors_t_ref: Optional[float] = None
         self._priors_newest: Optional[float] = None
-        # search_hybrid: which rows of WHICH index object carry the term list of their chunk's text
-        self._terms_index: Optional[Any] = None
-        self._terms_synced = 0
 
         self.total_chunks: int = 0
         self.embedding_dim: int = self.config.embedding_dim
@@ -438,6 +446,28 @@ class HybridStorage:
             return self._allow_mask(masked, ntotal)
         return None
 
+    def _require(self, what: str, *methods: str) -> None:
+        """The capability check of a search variant, in front of the lock (no index at all: the search gives ``[]``)."""
+        if self.faiss_index and not all(hasattr(self.faiss_index, m) for m in methods):
+            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no {what} ({' / '.join(methods)})")
+
+    def _ranked_in_index(self, query_embedding, config: Optional[SearchConfig], filters: Optional[Dict[str, Any]],
+                         cap: int, run: Callable) -> List[SearchResult]:
+        """The frame of the searches whose ranking runs inside the index (``search_sessions``, ``search_diverse``,
+        ``search_recent``, ``search_like``, ``search_hybrid``): tombstones always in the allow mask; ``top_k`` rows are
+        fetched, ``max(top_k, max_results)`` where filters are applied on the host, at most ``cap``.
+        ``run(q, k, allow, ntotal, cfg)`` is the variant, under the lock: the ``(sims, ids)`` of the one query
+        (``[k]`` or ``[1, k]``), to which the post-processing of ``search()`` applies in rank order."""
+        with self._lock:
+            frame = self._search_frame(config, query_embedding)
+            if frame is None or frame[0].top_k <= 0:
+                return []
+            cfg, ntotal, q = frame
+            allow = self._allow_for(filters, ntotal, tombstones_always=True)
+            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
+            sims, ids = run(q, max(1, min(k, cap)), allow, ntotal, cfg)
+            return self._results_in_rank_order(np.ravel(sims).tolist(), np.ravel(ids).tolist(), cfg, filters)
+
     def search(self, query_embedding, config: Optional[SearchConfig] = None,
                filters: Optional[Dict[str, Any]] = None) -> List[SearchResult]:
         with self._lock:
@@ -530,10 +560,9 @@ class HybridStorage:
         ``session_id`` in order of first appearance; rows without a session (or without a chunk) stay ungrouped
         (``-1``).  Only the tail ``[synced, ntotal)`` is pushed after adds; everything is pushed when the index
         object was replaced (load, restore, ``clear_all_data``, a rebuild into a second index) or compacted."""
-        if self._labels_index is not self.faiss_index:
-            self._labels_index, self._labels_synced = self.faiss_index, 0
+        if self._labels.index is not self.faiss_index:
             self._session_labels = {}
-        lo = self._labels_synced
+        lo = self._labels.rows_of(self.faiss_index)
         if lo >= ntotal:
             return
         labels = np.full(ntotal - lo, -1, dtype=np.int32)
@@ -543,7 +572,7 @@ class HybridStorage:
         for fid, session in rows:
             labels[fid - lo] = self._session_labels.setdefault(session, len(self._session_labels))
         self.faiss_index.set_groups(labels, row0=lo)
-        self._labels_synced = ntotal
+        self._labels.rows = ntotal
 
     def search_sessions(self, query_embedding, config: Optional[SearchConfig] = None,
                         filters: Optional[Dict[str, Any]] = None) -> List[SearchResult]:
@@ -559,19 +588,14 @@ class HybridStorage:
         then missing even if another of its chunks matches.  Tombstones are masked out in both modes, so a deleted
         chunk never stands for its session.  An index object without ``search_grouped`` raises
         ``NotImplementedError``."""
-        if self.faiss_index and not (hasattr(self.faiss_index, "search_grouped") and hasattr(self.faiss_index, "set_groups")):
-            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no grouped search (search_grouped / set_groups)")
-        with self._lock:
-            frame = self._search_frame(config, query_embedding)
-            if frame is None or frame[0].top_k <= 0:
-                return []
-            cfg, ntotal, q = frame
-            allow = self._allow_for(filters, ntotal, tombstones_always=True)
-            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
-            k = max(1, min(k, ntotal, fi.MAX_GROUP_K))
+        self._require("grouped search", "search_grouped", "set_groups")
+
+        def run(q, k, allow, ntotal, cfg):
             self._sync_session_labels(ntotal)
-            sims, ids, _ = self.faiss_index.search_grouped(q, k, normalize=self.config.normalize_embeddings, allow=allow)
-            return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
+            sims, ids, _ = self.faiss_index.search_grouped(q, min(k, ntotal), normalize=self.config.normalize_embeddings, allow=allow)
+            return sims, ids
+
+        return self._ranked_in_index(query_embedding, config, filters, fi.MAX_GROUP_K, run)
 
     def search_diverse(self, query_embedding, config: Optional[SearchConfig] = None,
                        filters: Optional[Dict[str, Any]] = None, lam: float = 0.5) -> List[SearchResult]:
@@ -589,19 +613,12 @@ class HybridStorage:
         made.  Without it and with filters, ``k = min(max(top_k, max_results), 128)`` picks are made and filtered in
         pick order, as ``search()`` filters rows: a chunk that fails the filter still stood in the way of its
         near-copies.  An index object without ``search_diverse`` raises ``NotImplementedError``."""
-        if self.faiss_index and not hasattr(self.faiss_index, "search_diverse"):
-            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no diversified search (search_diverse)")
-        with self._lock:
-            frame = self._search_frame(config, query_embedding)
-            if frame is None or frame[0].top_k <= 0:
-                return []
-            cfg, ntotal, q = frame
-            allow = self._allow_for(filters, ntotal, tombstones_always=True)
-            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
-            k = max(1, min(k, fi.MAX_DIVERSE_FETCH))
-            sims, ids = self.faiss_index.search_diverse(q, k, lam=lam, normalize=self.config.normalize_embeddings,
-                                                        allow=allow)
-            return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
+        self._require("diversified search", "search_diverse")
+
+        def run(q, k, allow, ntotal, cfg):
+            return self.faiss_index.search_diverse(q, k, lam=lam, normalize=self.config.normalize_embeddings, allow=allow)
+
+        return self._ranked_in_index(query_embedding, config, filters, fi.MAX_DIVERSE_FETCH, run)
 
     def _row_days(self, lo: int, hi: int) -> np.ndarray:
         """Timestamps of index rows ``[lo, hi)`` in days since the epoch; NaN: no chunk, no or an unparseable timestamp."""
@@ -621,8 +638,8 @@ class HybridStorage:
         ``RECENCY_MAX_EXPONENT`` half-lives beyond the reference, which then becomes the newest timestamp (a ``now``
         that far beyond the NEWEST row needs no new column: every boost has underflowed, and the weight factor says so)."""
         h = float(half_life_days)
-        full = self._priors_index is not self.faiss_index or self._priors_half_life != h or self._priors_t_ref is None
-        lo = 0 if full else self._priors_synced
+        full = self._priors.index is not self.faiss_index or self._priors_half_life != h or self._priors_t_ref is None
+        lo = 0 if full else self._priors.rows
         t = self._row_days(lo, ntotal) if lo < ntotal else np.zeros(0)
         known = t[~np.isnan(t)]
         newest = None if full else self._priors_newest
@@ -634,12 +651,12 @@ class HybridStorage:
             if full:
                 lo, t = 0, self._row_days(0, ntotal)
         if full:
-            self._priors_index, self._priors_half_life = self.faiss_index, h
+            self._priors.index, self._priors_half_life = self.faiss_index, h
             self._priors_t_ref = newest if newest is not None else now_days
         self._priors_newest = newest
         if lo < ntotal:
             self.faiss_index.set_priors(recency_priors(t, self._priors_t_ref, h), row0=lo)
-        self._priors_synced = ntotal
+        self._priors.rows = ntotal
         return self._priors_t_ref
 
     def search_recent(self, query_embedding, config: Optional[SearchConfig] = None,
@@ -661,24 +678,19 @@ class HybridStorage:
             raise ValueError(f"search_recent: half_life_days={half_life_days} must be a positive finite number")
         if not np.isfinite(w):
             raise ValueError(f"search_recent: weight={weight} is not finite")
-        if self.faiss_index and not (hasattr(self.faiss_index, "search_prior") and hasattr(self.faiss_index, "set_priors")):
-            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no prior-weighted search (search_prior / set_priors)")
+        self._require("prior-weighted search", "search_prior", "set_priors")
         now_days = timestamp_days(now if now is not None else datetime.now(timezone.utc))
         if now_days != now_days:
             raise ValueError(f"search_recent: now={now!r} is not a time")
-        with self._lock:
-            frame = self._search_frame(config, query_embedding)
-            if frame is None or frame[0].top_k <= 0:
-                return []
-            cfg, ntotal, q = frame
-            allow = self._allow_for(filters, ntotal, tombstones_always=True)
-            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
-            k = max(1, min(k, fi.MAX_PRIOR_K))
+
+        def run(q, k, allow, ntotal, cfg):
             t_ref = self._sync_recency_priors(ntotal, h, now_days)
             with np.errstate(over="ignore", under="ignore"):
                 w_now = float(np.float32(w * np.exp2(-(now_days - t_ref) / h)))
             _, ids, sims = self.faiss_index.search_prior(q, k, w_now, normalize=self.config.normalize_embeddings, allow=allow)
-            return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
+            return sims, ids
+
+        return self._ranked_in_index(query_embedding, config, filters, fi.MAX_PRIOR_K, run)
 
     def search_like(self, liked, disliked=(), query_embedding=None, config: Optional[SearchConfig] = None,
                     filters: Optional[Dict[str, Any]] = None, gamma: float = 0.5) -> List[SearchResult]:
@@ -701,26 +713,21 @@ class HybridStorage:
         disliked = [disliked] if isinstance(disliked, str) else list(disliked)
         nvec = 0 if query_embedding is None else 1
         _, g = fi.example_args(1, gamma, len(liked) + nvec, len(liked) + len(disliked) + nvec, "search_like")
-        if self.faiss_index and not hasattr(self.faiss_index, "search_examples"):
-            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no search by examples (search_examples)")
-        with self._lock:
-            frame = self._search_frame(config, query_embedding)
-            if frame is None or frame[0].top_k <= 0:
-                return []
-            cfg, ntotal, q = frame
+        self._require("search by examples", "search_examples")
+
+        def run(q, k, allow, ntotal, cfg):
             fids = []
             for chunk_id in liked + disliked:
                 fid = self.chunk_id_to_faiss_id.get(chunk_id)
                 if fid is None or fid >= ntotal or not self._get_chunk_data(chunk_id):
                     raise KeyError(chunk_id)
                 fids.append(fid)
-            allow = self._allow_for(filters, ntotal, tombstones_always=True)
-            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
-            k = max(1, min(k, fi.MAX_EXAMPLES_K))
             _, ids, sims = self.faiss_index.search_examples(
                 pos=q, pos_ids=fids[:len(liked)], neg_ids=fids[len(liked):], k=k, gamma=g,
                 normalize=self.config.normalize_embeddings, exclude_ids=True, allow=allow)
-            return self._results_in_rank_order(sims.tolist(), ids.tolist(), cfg, filters)
+            return sims, ids
+
+        return self._ranked_in_index(query_embedding, config, filters, fi.MAX_EXAMPLES_K, run)
 
     def topics(self, n_topics: int = 20, filters: Optional[Dict[str, Any]] = None, niter: int = 20, seed: int = 0,
                examples: int = 3) -> List[Topic]:
@@ -775,9 +782,7 @@ class HybridStorage:
         was replaced or compacted, by the rule of ``_sync_session_labels``."""
         from .lexical import terms_of
 
-        if self._terms_index is not self.faiss_index:
-            self._terms_index, self._terms_synced = self.faiss_index, 0
-        lo = self._terms_synced
+        lo = self._terms.rows_of(self.faiss_index)
         if lo >= ntotal:
             return
         lists: List[List[int]] = [[] for _ in range(ntotal - lo)]
@@ -786,7 +791,7 @@ class HybridStorage:
         for fid, text in rows:
             lists[fid - lo] = terms_of(text)
         self.faiss_index.set_terms(lists, row0=lo)
-        self._terms_synced = ntotal
+        self._terms.rows = ntotal
 
     def search_hybrid(self, query_text: str, query_embedding, config: Optional[SearchConfig] = None,
                       filters: Optional[Dict[str, Any]] = None, alpha: float = 0.3, k1: float = 1.2,
@@ -814,16 +819,9 @@ class HybridStorage:
         a = float(alpha)
         if not np.isfinite(a):
             raise ValueError(f"search_hybrid: alpha={alpha} is not finite")
-        if self.faiss_index and not all(hasattr(self.faiss_index, m) for m in ("search_hybrid", "set_terms", "term_stats")):
-            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no hybrid search (search_hybrid / set_terms / term_stats)")
-        with self._lock:
-            frame = self._search_frame(config, query_embedding)
-            if frame is None or frame[0].top_k <= 0:
-                return []
-            cfg, ntotal, q = frame
-            allow = self._allow_for(filters, ntotal, tombstones_always=True)
-            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
-            k = max(1, min(k, fi.MAX_HYBRID_K))
+        self._require("hybrid search", "search_hybrid", "set_terms", "term_stats")
+
+        def run(q, k, allow, ntotal, cfg):
             self._sync_terms(ntotal)
             terms = list(dict.fromkeys(terms_of(query_text)))
             weights = np.zeros(0, np.float32)
@@ -836,7 +834,9 @@ class HybridStorage:
                 weights = bm25_weights(np.asarray(df)[known], ndocs, k1=k1, normalized=True)
             _, ids, sims, _ = self.faiss_index.search_hybrid(q, terms, weights, k, a, k1=k1, b=b,
                                                              normalize=self.config.normalize_embeddings, allow=allow)
-            return self._results_in_rank_order(sims[0].tolist(), ids[0].tolist(), cfg, filters)
+            return sims, ids
+
+        return self._ranked_in_index(query_embedding, config, filters, fi.MAX_HYBRID_K, run)
 
     @staticmethod
     def _make_result(chunk_id: str, score: float, data: Dict[str, Any], cfg: SearchConfig) -> SearchResult:
@@ -1255,9 +1255,8 @@ class HybridStorage:
             self._saved_rows = self.faiss_index.ntotal
             self.total_chunks = len(live)
             self._mutations += 1
-            self._labels_index = None   # (search_sessions pushes every label again: the rows were renumbered)
-            self._priors_index = None   # (and search_recent every prior)
-            self._terms_index = None    # (and search_hybrid every term list)
+            # (the rows were renumbered: search_sessions, search_recent and search_hybrid push every row again)
+            self._labels, self._priors, self._terms = _Synced(), _Synced(), _Synced()
             if not in_place:
                 old.close()
         self.logger.info("Flat index rebuilt")

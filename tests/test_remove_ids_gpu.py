@@ -338,3 +338,99 @@ def test_storage_compacts_without_a_second_copy_of_the_index(tmp_path):
         hit = s.search(stored[i])[0]
         assert hit.chunk_id == f"c{i}" and abs(hit.similarity - 1.0) < 1e-5
     s.close()
+
+
+def _stored_terms(lists):
+    """``get_terms`` of rows that were given ``lists``, restated: per row the distinct terms ascending, their counts
+    saturated at 255, and the number of tokens given."""
+    uniq = [np.unique(np.asarray(r, np.int64), return_counts=True) for r in lists]
+    off = np.concatenate([[0], np.cumsum([u.shape[0] for u, _ in uniq])]).astype(np.int64)
+    terms = np.concatenate([u for u, _ in uniq] + [np.zeros(0, np.int64)]).astype(np.uint32)
+    tfs = np.minimum(np.concatenate([c for _, c in uniq] + [np.zeros(0, np.int64)]), 255).astype(np.uint8)
+    return off, terms, tfs, np.array([len(r) for r in lists], np.uint32)
+
+
+def _assert_columns(ix, labels, priors, lists, what):
+    """labels, priors and term lists of EVERY row of ``ix`` against their numpy restatement: ints equal, float bits
+    equal, the defaults (-1, 0.0, the empty list) on rows that were never given a value."""
+    assert ix.ntotal == labels.shape[0] == priors.shape[0] == len(lists), what
+    got_l, got_p = ix.get_groups(), ix.get_priors()
+    assert got_l.dtype == np.int32 and np.array_equal(got_l, labels), f"{what}: labels differ"
+    assert got_p.dtype == np.float32 and np.array_equal(got_p.view(np.uint32), priors.view(np.uint32)), f"{what}: priors differ"
+    for got, want, name in zip(ix.get_terms(), _stored_terms(lists), ("offsets", "terms", "tfs", "dl")):
+        assert got.dtype == want.dtype and np.array_equal(got, want), f"{what}: term list {name} differ"
+
+
+@pytest.mark.parametrize("metric", [0, 1])
+def test_labels_priors_and_terms_follow_the_rows_together(metric):
+    """Labels AND priors (and term lists) on one index: the two columns share their life -- allocation at the default,
+    capacity growth, the default of appended rows, compaction through the same keep-bit workspaces, reset -- so every
+    step is checked against a numpy restatement of all three, and the searches that read the columns after the
+    removal against an index freshly built from the kept rows, labels and priors (bit for bit)."""
+    d, step = 64, 700
+    rng = np.random.default_rng(100 + metric)
+    x = _rows(6 * step + 200, d, 17)
+    ix = _index(d, metric, "auto")
+    labels, priors, lists = np.zeros(0, np.int32), np.zeros(0, np.float32), []
+
+    def add(m, what):
+        nonlocal labels, priors, lists
+        n0 = ix.ntotal
+        ix.add(x[n0:n0 + m])
+        labels = np.concatenate([labels, np.full(m, -1, np.int32)])
+        priors = np.concatenate([priors, np.zeros(m, np.float32)])
+        lists = lists + [[] for _ in range(m)]
+        _assert_columns(ix, labels, priors, lists, what)
+
+    _assert_columns(ix, labels, priors, lists, "empty index")
+    for i in range(3):                                               # 1024 -> 1536 -> 2304 rows of capacity
+        add(step, f"add {i} (no column yet)")
+    # 1. labels on [100, 2100), a few negative (stored as -1)
+    given = rng.integers(0, 40, 2000).astype(np.int32)
+    given[rng.integers(0, 2000, 25)] = -7
+    ix.set_groups(given, row0=100)
+    labels[100:2100] = np.maximum(given, -1)
+    _assert_columns(ix, labels, priors, lists, "labels set")
+    add(step, "growth with labels only")                             # 2304 -> 3456
+    # 2. priors on [500, 2500)
+    given_p = rng.normal(0.0, 0.2, 2000).astype(np.float32)
+    ix.set_priors(given_p, row0=500)
+    priors[500:2500] = given_p
+    _assert_columns(ix, labels, priors, lists, "priors set")
+    # 3. term lists on the leading 1500 rows (repeats, empty rows, one term more than 255 times)
+    given_t = [rng.integers(0, 300, int(rng.integers(0, 12))).tolist() for _ in range(1500)]
+    given_t[7] = [5] * 300 + [2]
+    ix.set_terms(given_t)
+    lists[:1500] = given_t
+    _assert_columns(ix, labels, priors, lists, "terms set")
+    # 4. growth again, with every column set: 3456 -> 5184
+    add(step, "growth with all columns (fits)")
+    add(step, "growth with all columns")
+    n = ix.ntotal
+    assert n == 6 * step
+    # 5. about 10 % of the rows leave: row 0, a row of the last 32-row word, a run longer than 32 rows
+    dead = rng.random(n) < 0.10
+    dead[[0, n - 3]] = True
+    dead[1000:1045] = True
+    keep = np.flatnonzero(~dead)
+    assert ix.remove_ids(np.flatnonzero(dead)) == int(dead.sum())
+    labels, priors, lists = labels[keep], priors[keep], [lists[i] for i in keep]
+    _assert_columns(ix, labels, priors, lists, "removed")
+    fresh = _index(d, metric, "auto", x[keep])
+    fresh.set_groups(labels)
+    fresh.set_priors(priors)
+    q = _rows(3, d, 18)
+    for got, want, name in zip(ix.search_grouped(q, 10), fresh.search_grouped(q, 10), "DIG"):
+        assert np.array_equal(got.view(np.uint32) if name == "D" else got, want.view(np.uint32) if name == "D" else want), \
+            f"search_grouped {name} differs from a freshly built index"
+    for got, want, name in zip(ix.search_prior(q, 10, 0.25), fresh.search_prior(q, 10, 0.25), "DIS"):
+        assert np.array_equal(got.view(np.uint32) if name != "I" else got, want.view(np.uint32) if name != "I" else want), \
+            f"search_prior {name} differs from a freshly built index"
+    fresh.close()
+    # 6. rows appended behind the survivors start at the defaults (the slots held other rows' values)
+    add(100, "add after remove")
+    # 7. reset forgets every column; an index that never set one answers the defaults as well
+    ix.reset()
+    labels, priors, lists = np.zeros(0, np.int32), np.zeros(0, np.float32), []
+    add(step, "add after reset")
+    ix.close()
