@@ -52,12 +52,14 @@
 // of the host ones (allow-bitmap and input up, result rows reserved, results back; pinned staging for small calls);
 // prep_queries is the query preparation of every search; sweep_grid is the grid of the exact sweeps, sweep_variant and
 // sweep_slots the fan-out of their launchers over TT / METRIC and the 1 / 2 / 8 / 16 query slots, launch_merge_final the
-// plain merge behind them; RowColumn is a 4-byte-per-row column (labels, priors) and css_index::columns() the list every
-// row operation walks.  The sweep body of k_scan_small, k_range_small, k_scan_prior and k_scan_examples is deliberately
-// NOT shared (css_knn_range.h says why).
+// plain merge behind them; css_knn_plan.h states the rules of the candidate cascade (kind, growth, schedule, error bound,
+// tickets) and launch_scan_coarse applies them as named steps over one CascadeCall; RowColumn is a 4-byte-per-row
+// column (labels, priors) and css_index::columns() the list every row operation walks.  The sweep body of k_scan_small,
+// k_range_small, k_scan_prior and k_scan_examples is deliberately NOT shared (css_knn_range.h says why).
 #include "css_common.h"
 #include "css_devbuf.h"
 #include "css_knn_kernels.h"
+#include "css_knn_plan.h"
 #include "../../include/css_synth.h"
 
 #include <algorithm>
@@ -67,6 +69,7 @@
 #include <string>
 #include <cfloat>
 #include <cmath>
+#include <map>
 #include <mutex>
 #include <new>
 #include <optional>
@@ -168,6 +171,7 @@ struct css_index {
     DevBuf<uint32_t> cand_i;
     DevBuf<int> cpace;                  // sibling pacing counters [stage][group]
     DevBuf<int> fs_state;               // k_sweep_cascade: ticket / stage counters / threshold key words
+    std::map<const void*, int> fs_occ;  // ... blocks of a k_sweep_cascade instantiation that one CU holds (launch_sweep_cascade_t)
     // device-side exact fix-up of flagged queries (k_scan_small<FIX>): one global list + lock per query
     DevBuf<float> fix_s;  DevBuf<uint32_t> fix_i;     // entries [nq_pad][k]
     DevBuf<int> fix_lock;
@@ -1888,6 +1892,19 @@ template <typename F>
 int sweep_slots(int nqc, F&& f) {
     return nqc <= 1 ? f(IntC<1>()) : nqc <= 2 ? f(IntC<2>()) : nqc <= 8 ? f(IntC<8>()) : f(IntC<16>());
 }
+// The same for the sweeps of the candidate cascade (k_sweep_coarse, k_sweep_coarse_i8, k_sweep_mfma_i8, k_sweep_cascade).
+// sweep_nq_slots: f(NQ) with the smallest NQ of 1 / 2 / 4 that holds nq queries.
+// sweep_unrolled<TT768>: f(TT, MAIN) -- 768 columns get the kernel's unrolled variant (TT768 steps: 6, 3 or 12 by
+// kernel) and the split into main stage or not; every other width TT = 0 and MAIN = false.
+template <typename F>
+int sweep_nq_slots(int nq, F&& f) {
+    return nq <= 1 ? f(IntC<1>()) : nq <= 2 ? f(IntC<2>()) : f(IntC<4>());
+}
+template <int TT768, typename F>
+int sweep_unrolled(const css_index* ix, bool main_stage, F&& f) {
+    if (ix->dpad == 768) return main_stage ? f(IntC<TT768>(), std::true_type()) : f(IntC<TT768>(), std::false_type());
+    return f(IntC<0>(), std::false_type());
+}
 
 template <int NQ, int TT, int METRIC, bool FIX>
 int launch_scan_small_t(css_index* ix, const Rows& rows, const float* qpad, int nq_real, int k, int* gthr, const SweepGeom& sg,
@@ -2241,22 +2258,6 @@ inline bool batch_i8_wanted(css_index* ix, int k, int64_t nrows, int64_t nq) {
     return i8_feedback_allows(ix->fb_batch, 50);
 }
 
-template <int NQ>
-int launch_sweep_coarse_nq(css_index* ix, const Rows& rows, const float* qpad, int nq, int64_t count, int64_t stride,
-                           int gm1, bool stage0, hipStream_t st, bool i8) {
-    const bool main_stage = stride == 1 && !stage0;
-    if (i8) {
-        if (ix->dpad == 768)
-            return main_stage ? launch_sweep_coarse_i8_t<NQ, 3, true>(ix, rows, qpad, nq, count, stride, gm1, stage0, st)
-                              : launch_sweep_coarse_i8_t<NQ, 3, false>(ix, rows, qpad, nq, count, stride, gm1, stage0, st);
-        return launch_sweep_coarse_i8_t<NQ, 0, false>(ix, rows, qpad, nq, count, stride, gm1, stage0, st);
-    }
-    if (ix->dpad == 768)
-        return main_stage ? launch_sweep_coarse_t<NQ, 6, true>(ix, rows, qpad, nq, count, stride, gm1, stage0, st)
-                          : launch_sweep_coarse_t<NQ, 6, false>(ix, rows, qpad, nq, count, stride, gm1, stage0, st);
-    return launch_sweep_coarse_t<NQ, 0, false>(ix, rows, qpad, nq, count, stride, gm1, stage0, st);
-}
-
 // 3..32 queries, inner product, int8 rows in view: does the sweep on the int8 MFMA (k_sweep_mfma_i8) answer sooner than what
 // it replaces -- the VALU sweep (3, 4 queries) or the 256-query tiles of the batch scan?  One
 // session, ms with / without, 3 .. 16 queries: 10 M rows k = 10 1.65 / 1.92-2.07, k = 100 1.83-1.85 / 2.75-3.26; 1 M rows
@@ -2279,30 +2280,17 @@ inline bool mfma_sweep_applies(const css_index* ix, const Rows& rows, int64_t nq
 int launch_sweep_mfma(css_index* ix, const Rows& rows, int nq, int64_t count, int64_t stride, int gm1, bool stage0,
                       hipStream_t st) {
     const int grid = (int)std::min<int64_t>((int64_t)ix->num_cus * 8, count);
-    const bool main_stage = stride == 1 && !stage0;
     const signed char* q8 = reinterpret_cast<const signed char*>(ix->qh.p);
-#define CSS_LAUNCH_SWEEP_MFMA(KS_, MAIN_, NG_)                                                                         \
-    hipLaunchKernelGGL((k_sweep_mfma_i8<KS_, MAIN_, NG_>), dim3(grid), dim3(256), 0, st, rows.x8, rows.x8s, q8, ix->qscale.p, ix->cthr.p,  \
-                       ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, rows.n, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, \
-                       rows.mask)
-    if (nq <= 16) {
-        if (ix->dpad == 768) {
-            if (main_stage) CSS_LAUNCH_SWEEP_MFMA(12, true, 1);
-            else CSS_LAUNCH_SWEEP_MFMA(12, false, 1);
-        } else {
-            CSS_LAUNCH_SWEEP_MFMA(0, false, 1);
-        }
-    } else {   // 17..32 queries: two fragment sets per lane
-        if (ix->dpad == 768) {
-            if (main_stage) CSS_LAUNCH_SWEEP_MFMA(12, true, 2);
-            else CSS_LAUNCH_SWEEP_MFMA(12, false, 2);
-        } else {
-            CSS_LAUNCH_SWEEP_MFMA(0, false, 2);
-        }
-    }
-#undef CSS_LAUNCH_SWEEP_MFMA
-    CSS_LAUNCH_CHECK();
-    return CSS_OK;
+    const auto launch = [&](auto NG) -> int {   // fragment sets per lane
+        return sweep_unrolled<12>(ix, stride == 1 && !stage0, [&](auto KS, auto MAIN) -> int {
+            hipLaunchKernelGGL((k_sweep_mfma_i8<decltype(KS)::value, decltype(MAIN)::value, decltype(NG)::value>), dim3(grid),
+                               dim3(256), 0, st, rows.x8, rows.x8s, q8, ix->qscale.p, ix->cthr.p, ix->cand_s.p, ix->cand_i.p,
+                               ix->cand_n.p, rows.n, ix->dpad, nq, count, stride, gm1, stage0 ? 1 : 0, rows.mask);
+            CSS_LAUNCH_CHECK();
+            return CSS_OK;
+        });
+    };
+    return nq <= 16 ? launch(IntC<1>()) : launch(IntC<2>());   // 17..32 queries: two fragment sets per lane
 }
 
 // one later stage of the int8 batch scan with the queries in registers (k_scan_qreg_i8): two 4-wave blocks per CU
@@ -2330,93 +2318,28 @@ int launch_scan_qreg(css_index* ix, const Rows& rows, int nqt, int64_t count, in
     return launch_scan_qreg_t<4>(ix, rows, nqt, count, stride, gm1, main_stage, st);
 }
 
-// the whole sweep cascade in one launch (k_sweep_cascade); sc: the schedule as tickets
-template <int NQ, int TT, bool I8>
-int launch_sweep_cascade_t(css_index* ix, const Rows& rows, const float* qpad, int nq, const FsSched& sc, int* flags,
-                           const float* qnorm2, float eps_rel, int l2, int k, int measured, hipStream_t st) {
-    const int steps = I8 ? (TT > 0 ? TT : (ix->dpad / 16 + 15) / 16) : 0;
-    const size_t lds = (size_t)cz_fs_lds_floats(NQ, I8 ? 256 * steps : ix->dpad) * sizeof(float);
-    auto kern = k_sweep_cascade<NQ, TT, I8>;
-    int rc;
-    if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
-    // as many blocks as the chip holds at once (a wave leaves only when the tickets run out: more blocks would start at
-    // the very end, load the queries and find nothing to do); nothing depends on the blocks being co-resident
-    static int per_cu_of[64];   // (asked once per device and instantiation: the answer depends on nothing else here)
-    int& per_cu_cached = per_cu_of[ix->device & 63];
-    if (per_cu_cached == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_cached, kern, 256, lds) != hipSuccess || per_cu_cached < 1))
-        per_cu_cached = 1;
-    int per_cu = per_cu_cached;
-    per_cu = std::min(per_cu, 3);   // (12 waves per CU already draw the whole HBM rate: 2 / 3 / 4 blocks 1.305 / 1.302 / 1.316 ms at 10 M rows)
-    const int grid = (int)std::min<int64_t>((int64_t)ix->num_cus * std::min(per_cu, 8), (sc.first[sc.nstage] + 3) / 4);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, I8 ? (const void*)rows.x8 : (const void*)rows.xh,
-                       I8 ? (const float*)rows.x8s : (const float*)nullptr, qpad, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, ix->cthr.p,
-                       flags, rows.n, ix->dpad, nq, sc, ix->fs_state.p, rows.mask,
-                       ix->metric == CSS_METRIC_L2 ? rows.xnorm2 : nullptr, qnorm2, (const int*)ix->maxn2.p, eps_rel, l2, k, measured,
-                       knn_env().fs_spins);
-    CSS_LAUNCH_CHECK();
-    return CSS_OK;
-}
-template <int NQ>
-int launch_sweep_cascade_nq(css_index* ix, const Rows& rows, const float* qpad, int nq, const FsSched& sc, int* flags,
-                            const float* qnorm2, float eps_rel, int l2, int k, int measured, hipStream_t st, bool i8) {
-    if (i8)
-        return ix->dpad == 768 ? launch_sweep_cascade_t<NQ, 3, true>(ix, rows, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st)
-                               : launch_sweep_cascade_t<NQ, 0, true>(ix, rows, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st);
-    return ix->dpad == 768 ? launch_sweep_cascade_t<NQ, 6, false>(ix, rows, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st)
-                           : launch_sweep_cascade_t<NQ, 0, false>(ix, rows, qpad, nq, sc, flags, qnorm2, eps_rel, l2, k, measured, st);
-}
-
 // grid of the persistent k_scan_coarse launches and the largest query chunk it can serve: the nqt blocks
 // that share a row tile must fit the grid / 8 blocks of one XCD group (a CPX partition has few CUs)
 inline int coarse_grid(const css_index* ix) { return std::max(8, ix->num_cus / 8 * 8); }
 inline int coarse_max_chunk(const css_index* ix) { return std::min(4096, coarse_grid(ix) / 8 * CZ_T); }
 
-// sweep = true: 1..4 queries through the HBM-bound bf16 sweep (k_sweep_coarse) instead of the MFMA scan.
-// Everything is enqueued on `st`; nothing waits for the device (flagged queries are fixed up on the device).
-// use_i8: which shadow rows this SEARCH reads, decided once by the caller (search_dev_enqueue / search_noshadow_ranges:
-// the per-index feedback is consulted once per search, not per chunk); record_fb: this is the search's last chunk, whose
-// flagged count is what the feedback sees.
-// q_raw != null (sweep only): the raw query rows, still to be prepared (normalize_q as in search_dev_enqueue) -- the init
-// launch of the cascade does it.
-int launch_scan_coarse(css_index* ix, const Rows& rows, int q0, int nq, int k, float* D_dev, int64_t* I_dev, hipStream_t st,
-                       const SweepGeom& sg, bool sweep, bool use_i8, bool record_fb, const float* q_raw = nullptr,
-                       int normalize_q = 0) {
-    const KnnEnv& env = knn_env();
-    const float* qpad = ix->qpad.p + (size_t)q0 * ix->dpad;
-    const float* qnorm2 = ix->qnorm2.p + q0;
-    D_dev += (size_t)q0 * k;
-    I_dev += (size_t)q0 * k;
-    // 3..32 queries on int8 rows (inner product): the sweep on the int8 MFMA (k_sweep_mfma_i8): int8 queries too
-    const bool sweep_mfma = sweep && use_i8 && mfma_sweep_applies(ix, rows, nq, k);
-    const int nq_pad = sweep ? (sweep_mfma ? (nq <= 16 ? 16 : 32) : nq) : (nq + CZ_T - 1) / CZ_T * CZ_T;
-    const int nqt = sweep ? 1 : nq_pad / CZ_T;
-    // error of one coarse score relative to ||q|| max||x||: both operands bf16 (MFMA scan) or rows only (sweep)
-    // int8 rows: a-priori |x^ - x| <= (s / 2) sqrt(d), s = max|x_i| / 127 <= ||x|| / 127 (the same for int8 queries)
-    const bool i8 = use_i8;
-    int rc_early = CSS_OK;
-    const float i8_rel = sqrtf((float)ix->dpad) / 254.f;
-    const float eps_rel = i8 ? ((sweep && !sweep_mfma) ? i8_rel : 2.f * i8_rel + i8_rel * i8_rel) + 0.00048828125f
-                             : (sweep ? 0.00390625f + 0.00048828125f : 0.0078125f + 0.00048828125f);
-    // ... tightened by the rounding errors actually measured at ingest / query prep (cz_eps).
-    // measured = the word of maxn2 that holds the rows' error: 1 = bf16 rows, 2 = int8 rows
-    const int measured = i8 ? 2 : 1;
-    // (the int8 queries' error norms: sized HERE, before the pointer below is taken -- until round 4 the buffer grew further
-    // down, so the selects of the first int8 search with more queries than any before read the freed, shorter one: zeros on
-    // a fresh device, i.e. a band without the query term; stale bytes otherwise, i.e. everything flagged -- 744 of 1000
-    // queries and 33 ms in the third index of one process, tools/seq_probe.py)
-    if (i8 && (!sweep || sweep_mfma) && (rc_early = ix->qerr2_i8.grow((size_t)q0 + nq_pad)) != CSS_OK) return rc_early;
-    const float* qerr2 = (sweep && !sweep_mfma) ? nullptr : (i8 ? ix->qerr2_i8.p + q0 : ix->qerr2.p + q0);
-    // the second pass over flagged queries reads the bf16 rows with bf16 queries
-    const EpsSet eps_p2{0.0078125f + 0.00048828125f, ix->qerr2.p + q0, 1};
-    const int l2 = ix->metric == CSS_METRIC_L2 ? 1 : 0;
-    const float* xn2 = l2 ? rows.xnorm2 : nullptr;  // L2: coarse score = 2 x.q - ||x||^2
-    int rc;
-    if (!sweep && (rc = ix->qh.grow((size_t)nq_pad * ix->dpad)) != CSS_OK) return rc;
-    if ((rc = grow_candidate_ws(ix, (size_t)nq_pad, k)) != CSS_OK) return rc;
-    int* flags = ix->cflags.p;
-    int* flag_list = ix->cflags.p + nq_pad;
-    int* nflag = ix->cflags.p + 2 * nq_pad;
-    ix->last_nflag = nflag;
+// ---- the candidate cascade of one chunk of queries (launch_scan_coarse).  Its rules -- kind, growth, schedule, error
+// bound, tickets -- are css_knn_plan.h; here they meet the index: the workspace, the launch of a stage, the selects.
+typedef void (*scan_fn)(const unsigned short*, const unsigned short*, const float*, float*, uint32_t*, int*, int64_t, int,
+                        int, int64_t, int64_t, int, int*, const uint32_t*, const float*, const int*, const float*,
+                        const float*);
+constexpr int kPaceGroups = 512, kPaceStages = 20;   // sibling pacing counters of the batch scan (cpace)
+struct CascadeCall {
+    CascadeKind kind;
+    bool i8;          // the scan reads the int8 rows ...
+    bool i8q;         // ... with int8 queries (every kind but the VALU sweep, whose queries stay fp32)
+    int q0, nq, k;    // queries [q0, q0 + nq) of ix->qpad.p; nq <= 4096
+    int nq_pad, nqt;  // query rows the scan sees, and their tiles of CZ_T
+    int l2;
+    int growth;
+    CascadePlan plan;
+    bool fused;       // the VALU sweep's stages and the selects between them as ONE launch (k_sweep_cascade)
+    FsSched tickets;  // ... its schedule
     // Second pass (batches on indexes whose rows can overflow a 4096-slot buffer at all): flagged queries -- band or
     // buffer overflow: dense clusters, duplicate floods -- are scanned once more, together, against the threshold the
     // exact scores of their buffered candidates give (k_coarse_select<true>), into CZ_CAP2-slot buffers; only what
@@ -2424,245 +2347,315 @@ int launch_scan_coarse(css_index* ix, const Rows& rows, int q0, int nq, int k, f
     // per pass over the fp32 rows): 22 flagged of 1000 queries cost 2.9 ms of a 7 ms batch at 1 M clustered rows.
     // (the second pass reads the bf16 rows: a shadow-less range scanned from int8 scratch rows sends its flagged queries
     // straight to the exact sweep -- and, through the feedback of batch_uses_i8, the next searches to bf16 ranges)
-    const bool pass2 = !sweep && ix->dpad % 128 == 0 && rows.n > CZ_CAP && rows.xh != nullptr;
-    const int f2 = pass2 ? std::min(nq_pad, kF2Max) : 0;   // (a multiple of CZ_T)
-    int* flag_listB = nullptr;
-    int* nflagB = nullptr;
-    ix->last_nswept = nflag;
-    if (pass2) {
+    bool pass2;
+    int f2;           // its query slots (a multiple of CZ_T)
+    // one-eps thresholds from exactly scored top-k candidates (k_coarse_select): the int8 scan with int8 queries, whose
+    // band is the widest (the scores are inner products: batch_uses_i8)
+    bool exact_k;
+    EpsSet eps, eps_p2;   // of the scan, and of the second pass (always bf16 rows and queries)
+    scan_fn scan_stage0, scan_mid, scan_main;   // Batch: the kernel of stage 0, of a middle stage, of the main stage
+    float* D;             // result rows of the chunk
+    int64_t* I;
+    // pointers into the index's buffers: null until cascade_workspace has grown them
+    float *qpad, *qnorm2;
+    int *gthr, *flags, *flag_list, *nflag;
+    int *flag_listB, *nflagB;   // pass2: the queries left to the exact sweep
+};
+
+// the whole sweep cascade in one launch (k_sweep_cascade)
+template <int NQ, int TT, bool I8>
+int launch_sweep_cascade_t(css_index* ix, const Rows& rows, const CascadeCall& c, hipStream_t st) {
+    const int steps = I8 ? (TT > 0 ? TT : (ix->dpad / 16 + 15) / 16) : 0;
+    const size_t lds = (size_t)cz_fs_lds_floats(NQ, I8 ? 256 * steps : ix->dpad) * sizeof(float);
+    auto kern = k_sweep_cascade<NQ, TT, I8>;
+    int rc;
+    if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
+    // as many blocks as the chip holds at once (a wave leaves only when the tickets run out: more blocks would start at
+    // the very end, load the queries and find nothing to do); nothing depends on the blocks being co-resident, and no
+    // result on the grid: tickets are drawn from a counter
+    int& per_cu_cached = ix->fs_occ[(const void*)kern];   // (asked once per index -- one device, one row width -- and kernel; caller holds ws_mu)
+    if (per_cu_cached == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_cached, kern, 256, lds) != hipSuccess || per_cu_cached < 1))
+        per_cu_cached = 1;
+    const int per_cu = std::min(per_cu_cached, 3);   // (12 waves per CU already draw the whole HBM rate: 2 / 3 / 4 blocks 1.305 / 1.302 / 1.316 ms at 10 M rows)
+    const FsSched& sc = c.tickets;
+    const int grid = (int)std::min<int64_t>((int64_t)ix->num_cus * std::min(per_cu, 8), (sc.first[sc.nstage] + 3) / 4);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, I8 ? (const void*)rows.x8 : (const void*)rows.xh,
+                       I8 ? (const float*)rows.x8s : (const float*)nullptr, (const float*)c.qpad, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, ix->cthr.p,
+                       c.flags, rows.n, ix->dpad, c.nq, sc, ix->fs_state.p, rows.mask,
+                       ix->metric == CSS_METRIC_L2 ? rows.xnorm2 : nullptr, (const float*)c.qnorm2, (const int*)ix->maxn2.p, c.eps.eps_rel, c.l2, c.k,
+                       c.eps.measured, knn_env().fs_spins);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// What one chunk's cascade is, decided once.  use_i8: which shadow rows this SEARCH reads (the caller's decision: the
+// per-index feedback is consulted once per search, not per chunk).
+CascadeCall cascade_call(const css_index* ix, const Rows& rows, CascadeKind kind, bool use_i8, int q0, int nq, int k,
+                         float* D_dev, int64_t* I_dev) {
+    const KnnEnv& env = knn_env();
+    const bool batch = kind == CascadeKind::Batch;
+    CascadeCall c{};
+    c.kind = kind;
+    c.i8 = use_i8;
+    c.i8q = use_i8 && kind != CascadeKind::SweepValu;
+    c.q0 = q0, c.nq = nq, c.k = k;
+    // (the int8 MFMA sweep: 16 or 32 int8 query rows, zero padded)
+    c.nq_pad = batch ? (nq + CZ_T - 1) / CZ_T * CZ_T : (kind == CascadeKind::SweepMfma ? (nq <= 16 ? 16 : 32) : nq);
+    c.nqt = batch ? c.nq_pad / CZ_T : 1;
+    c.l2 = ix->metric == CSS_METRIC_L2 ? 1 : 0;
+    c.growth = cascade_growth(kind, use_i8, k, rows.n, env.growth, env.growth_sweep);
+    c.plan = cascade_plan((rows.n + CZ_T - 1) / CZ_T, c.growth, cascade_fills_stage0(kind), cascade_splits_last(kind, use_i8));
+    // 1..4 queries: one launch, quarter tiles as tickets in stage order (measured, ms one launch / one per stage: 10 M rows,
+    // 1 query k = 10 1.35 / 1.41, k = 100 1.40 / 1.56, 2 queries 1.40 / 1.47, 4 queries 2.68 / 2.69; 100 k rows: 0.085 /
+    // 0.095, 0.118 / 0.125, but 2 queries 0.117 / 0.111, 4: 0.186 / 0.155) -- where the tickets can state the plan
+    c.fused = kind == CascadeKind::SweepValu && env.sweep_fused && (env.sweep_fused == 2 || nq == 1 || rows.n >= 1000000) &&
+              cascade_tickets(c.plan, c.growth, c.tickets.first, c.tickets.stride, c.tickets.gm1);
+    if (c.fused) c.tickets.nstage = c.plan.n;
+    c.pass2 = batch && ix->dpad % 128 == 0 && rows.n > CZ_CAP && rows.xh != nullptr;
+    c.f2 = c.pass2 ? std::min(c.nq_pad, kF2Max) : 0;
+    c.exact_k = c.i8q && k * 2 <= CZ_EXK;
+    // measured = the word of maxn2 that holds the rows' error: 1 = bf16 rows, 2 = int8 rows
+    c.eps = EpsSet{cascade_eps_rel(kind, use_i8, ix->dpad), nullptr, use_i8 ? 2 : 1};
+    c.eps_p2 = EpsSet{cascade_eps_rel(CascadeKind::Batch, false, ix->dpad), nullptr, 1};
+    if (batch) {
+        // the 8-phase ping-pong loop (k_scan_coarse8) wherever its shape constraints hold (batch_uses_i8 implies it)
+        const bool loop8 = ix->dpad % 128 == 0;
+        const bool i8b = use_i8;
+        c.scan_stage0 = i8b ? k_scan_coarse8<true, false, CZ_CAP, true>
+                            : (loop8 ? k_scan_coarse8<true, false> : k_scan_coarse<true, false>);
+        c.scan_mid = i8b ? k_scan_coarse8<false, false, CZ_CAP, true>
+                         : (loop8 ? k_scan_coarse8<false, false> : k_scan_coarse<false, false>);
+        c.scan_main = i8b ? k_scan_coarse8<false, true, CZ_CAP, true>
+                          : (loop8 ? k_scan_coarse8<false, true> : k_scan_coarse<false, true>);
+    }
+    c.D = D_dev + (size_t)q0 * k;
+    c.I = I_dev + (size_t)q0 * k;
+    return c;
+}
+
+// Every growth of the chunk's buffers, and only then the pointers into them.  A DevBuf that grows frees its old memory,
+// so NO pointer into one of these buffers is formed above the last growth: the steps of the cascade take theirs from the
+// call, which gets them at the end of this function, or from the index after it has run.  (Until round 4 the int8 queries'
+// error norms grew below the point where their pointer was taken, so the selects of the first int8 search with more
+// queries than any before read the freed, shorter buffer: zeros on a fresh device, i.e. a band without the query term;
+// stale bytes otherwise, i.e. everything flagged -- 744 of 1000 queries and 33 ms in the third index of one process,
+// tools/seq_probe.py.)
+int cascade_workspace(css_index* ix, CascadeCall& c, hipStream_t st) {
+    const size_t nq_pad = (size_t)c.nq_pad;
+    int rc;
+    // rounded query rows: bf16, or int8 (into the same buffer: half its bytes) with their scales and error norms
+    if (c.kind != CascadeKind::SweepValu && (rc = ix->qh.grow(nq_pad * ix->dpad)) != CSS_OK) return rc;
+    if (c.i8q && (rc = ix->qscale.grow(nq_pad)) != CSS_OK) return rc;
+    if (c.i8q && (rc = ix->qerr2_i8.grow((size_t)c.q0 + nq_pad)) != CSS_OK) return rc;
+    if ((rc = grow_candidate_ws(ix, nq_pad, c.k)) != CSS_OK) return rc;
+    if (c.pass2) {
         const size_t qh2_before = ix->qh2.cap;
-        if ((rc = ix->qh2.grow((size_t)f2 * ix->dpad)) != CSS_OK) return rc;
+        if ((rc = ix->qh2.grow((size_t)c.f2 * ix->dpad)) != CSS_OK) return rc;
         // slots beyond the flagged count are scanned with a +inf threshold; their rows must still be finite numbers
         if (ix->qh2.cap != qh2_before) CSS_HIP_TRY(hipMemsetAsync(ix->qh2.p, 0, ix->qh2.cap * sizeof(unsigned short), st));
-        if ((rc = ix->thr2.grow((size_t)f2)) != CSS_OK) return rc;
-        if ((rc = ix->cand_n2.grow((size_t)f2 * CZ_NS)) != CSS_OK) return rc;
-        if ((rc = ix->cand_s2.grow((size_t)f2 * CZ_CAP2)) != CSS_OK) return rc;
-        if ((rc = ix->cand_i2.grow((size_t)f2 * CZ_CAP2)) != CSS_OK) return rc;
-        if ((rc = ix->flagB.grow((size_t)nq_pad + 2)) != CSS_OK) return rc;
-        flag_listB = ix->flagB.p;
-        nflagB = ix->flagB.p + nq_pad;
-        ix->last_nswept = nflagB;
+        if ((rc = ix->thr2.grow((size_t)c.f2)) != CSS_OK) return rc;
+        if ((rc = ix->cand_n2.grow((size_t)c.f2 * CZ_NS)) != CSS_OK) return rc;
+        if ((rc = ix->cand_s2.grow((size_t)c.f2 * CZ_CAP2)) != CSS_OK) return rc;
+        if ((rc = ix->cand_i2.grow((size_t)c.f2 * CZ_CAP2)) != CSS_OK) return rc;
+        if ((rc = ix->flagB.grow(nq_pad + 2)) != CSS_OK) return rc;
     }
+    if (c.fused && (rc = ix->fs_state.grow((size_t)CZ_FS_WORDS)) != CSS_OK) return rc;
+    if (c.kind == CascadeKind::Batch && (rc = ix->cpace.grow((size_t)kPaceGroups * kPaceStages)) != CSS_OK) return rc;
+    // ---- the last growth is above this line
+    c.qpad = ix->qpad.p + (size_t)c.q0 * ix->dpad;
+    c.qnorm2 = ix->qnorm2.p + c.q0;
+    c.gthr = ix->gthr.p + c.q0;
+    c.flags = ix->cflags.p;
+    c.flag_list = ix->cflags.p + nq_pad;
+    c.nflag = ix->cflags.p + 2 * nq_pad;
+    if (c.pass2) {
+        c.flag_listB = ix->flagB.p;
+        c.nflagB = ix->flagB.p + nq_pad;
+    }
+    // the queries' own rounding error (cz_eps): none for the fp32 queries of the VALU sweep
+    if (c.kind != CascadeKind::SweepValu) c.eps.qerr2 = c.i8q ? ix->qerr2_i8.p + c.q0 : ix->qerr2.p + c.q0;
+    c.eps_p2.qerr2 = ix->qerr2.p + c.q0;
+    return CSS_OK;
+}
 
-    // cascade schedule: a nested, uniformly strided sample of row tiles.  Stage 0 reads every s-th tile (at most 15
-    // tiles: it keeps every score, 3840 of the 4096 slots), every later stage the tiles at a stride `ratio` times
-    // smaller that were not read before; the last stage has stride 1.
-    // Growth factor g: every stage reads g-1 times the tiles read before it.  Batches (MFMA scan): g = 8 for k <= 32
-    // (4 stages at 1.25 M rows instead of 6; the last stage is 7/8 of the rows and appends ~7k + band candidates per
-    // query, cheap since the tile epilogue walks hits per lane: 10 M x 1000, k = 10: 12.25 ms vs 12.47 at g = 4, 100 k
-    // rows 0.32 vs 0.34 ms; g = 16: 12.4 ms), g = 4 above (k = 100: 13.55 vs 13.79 ms; k = 32..64 equal).  Round 2's
-    // epilogue made g = 8 2 % slower.  1..4 queries (sweep): g = 4.  Fewer, larger stages do not help
-    // there -- measured at 10 M rows, k = 10: g = 4 / 8 / 16 (7 / 5 / 4 stages) all take 2.71-2.72 ms, the call is the
-    // 15.36 GB of shadow rows at the sweep's bandwidth plus ~0.25 ms -- and with k = 100 (the reference's call shape)
-    // g = 16 overflows the 4096-slot buffers (~k g candidates per stage) and lands in the exact fix-up: 10 ms.
-    const int64_t ntiles = (rows.n + CZ_T - 1) / CZ_T;
-    // (int8 scan: its band is ~4 x wider, growth 8 would append ~2500 rows per query in the main stage)
-    // (3..32 queries on the int8 MFMA: one launch per stage, so below ~4 M rows fewer, larger stages win -- ms at growth 4 / 8,
-    // k = 10: 1 M rows 0.33 / 0.27, 100 k rows 0.13 / 0.10, 10 M rows 1.59 / 1.55-1.67; k = 100 overflows the buffers at
-    // growth 8 and 10 M rows, as the VALU sweep did)
-    const int g_sweep = env.growth_sweep ? env.growth_sweep : ((sweep_mfma && k <= 32 && rows.n < 4000000) ? 8 : 4);
-    const int g = sweep ? g_sweep : (env.growth ? env.growth : ((k <= 32 && !i8) ? 8 : 4));
-    struct Stage {
-        int64_t stride;
-        int ratio;   // stride of the previous stage / this stride (stage 0: unused)
-    };
-    std::vector<Stage> sched;
-    {
-        int64_t s0 = 1;
-        while (ntiles / (s0 * g) >= 2) s0 *= g;
-#ifndef CZ_S0_FILL
-#define CZ_S0_FILL 1
-#endif
-        // (2 .. 2g-1 tiles so far; stage 0 holds 15: where the next finer stride still fits, the cascade is one stage shorter --
-        // batches 152.5 k -> 153.7 k queries/s, 4 / 16 queries on the int8 MFMA 1.67 / 1.72 -> 1.59 ms at 10 M rows; not for the
-        // one-launch cascade of 1..2 queries, whose first select is one wave's work: 1.29 -> 1.32 ms)
-        if (CZ_S0_FILL && (!sweep || sweep_mfma) && s0 >= g && (ntiles + s0 / g - 1) / (s0 / g) <= 15) s0 /= g;
-        const int64_t w0 = (ntiles + s0 - 1) / s0;          // tiles at stride s0
-        const int g0 = (int)((w0 + 14) / 15);                // > 1: one coarser first stage in front
-        if (g0 > 1) sched.push_back({s0 * g0, 0});
-        sched.push_back({s0, g0});
-        for (int64_t s = s0 / g; s >= 1; s /= g) sched.push_back({s, g});
-        // int8 scan (band ~4 x wider): the last step of 4 is taken as two steps of 2 -- the main stage is then half of
-        // the rows under the threshold of the other half (~3 x fewer appends than 3/4 of the rows under a quarter's)
-        if (i8 && (!sweep || sweep_mfma) && g == 4 && sched.size() >= 2 && sched.back().stride == 1 && ntiles >= 64) {
-            sched.back() = {2, 2};
-            sched.push_back({1, 2});
-        }
-    }
-    const int64_t n0 = (ntiles + sched[0].stride - 1) / sched[0].stride;
-    // 1..4 queries: the stages and the selects between them as ONE launch (k_sweep_cascade), quarter tiles as tickets in stage order
-    // (measured, ms one launch / one per stage: 10 M rows, 1 query k = 10 1.35 / 1.41, k = 100 1.40 / 1.56, 2 queries 1.40 /
-    // 1.47, 4 queries 2.68 / 2.69; 100 k rows: 0.085 / 0.095, 0.118 / 0.125, but 2 queries 0.117 / 0.111, 4: 0.186 / 0.155)
-    bool fused = sweep && !sweep_mfma && env.sweep_fused && (env.sweep_fused == 2 || nq == 1 || rows.n >= 1000000) &&
-                 (int)sched.size() <= CZ_FS_MAXST && ntiles < (int64_t)1 << 28;
-    FsSched fsched{};
-    if (fused) {
-        fsched.nstage = (int)sched.size();
-        int64_t first = 0;
-        for (size_t si = 0; si < sched.size(); ++si) {
-            const int64_t W = (ntiles + sched[si].stride - 1) / sched[si].stride;
-            const int gr = si == 0 ? g : sched[si].ratio;
-            const int64_t count = si == 0 ? W : (W - 1) - (W - 1) / gr;
-            if (count <= 0) fused = false;   // (a stage without tiles would leave nobody to run its select; not seen with these schedules)
-            fsched.first[si] = (int)first;
-            fsched.stride[si] = (int)sched[si].stride;
-            fsched.gm1[si] = std::max(1, gr - 1);
-            first += 4 * count;   // tickets are quarter tiles
-        }
-        fsched.first[sched.size()] = (int)first;
-        if (fused && (rc = ix->fs_state.grow((size_t)CZ_FS_WORDS)) != CSS_OK) return rc;
-    }
-    constexpr int kPaceGroups = 512, kPaceStages = 20;
-    const bool use_pace = !sweep;
-    if (use_pace && (rc = ix->cpace.grow((size_t)kPaceGroups * kPaceStages)) != CSS_OK) return rc;
+// int8 query rows, their scales and error norms
+int launch_queries_to_i8(css_index* ix, const CascadeCall& c, hipStream_t st) {
+    hipLaunchKernelGGL(k_rows_to_i8, dim3((unsigned)((c.nq_pad + 3) / 4)), dim3(256), 0, st, (const float*)c.qpad,
+                       reinterpret_cast<signed char*>(ix->qh.p), ix->qscale.p, ix->qerr2_i8.p + c.q0, c.nq, c.nq_pad, ix->dpad);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
 
-    {
-        if (!sweep && i8) {   // int8 query rows (into the same buffer: half its bytes), their scales and error norms
-            if ((rc = ix->qscale.grow((size_t)nq_pad)) != CSS_OK) return rc;
-            if ((rc = ix->qerr2_i8.grow((size_t)q0 + nq_pad)) != CSS_OK) return rc;
-            hipLaunchKernelGGL(k_rows_to_i8, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, st, qpad,
-                               reinterpret_cast<signed char*>(ix->qh.p), ix->qscale.p, ix->qerr2_i8.p + q0, nq, nq_pad, ix->dpad);
-            CSS_LAUNCH_CHECK();
-        } else if (!sweep) {
-            const int64_t ne = (int64_t)nq_pad * ix->dpad;
-            hipLaunchKernelGGL(k_rows_to_bf16, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, qpad, ix->qh.p,
-                               (int64_t)nq, (int64_t)nq_pad, ix->dpad);
-            CSS_LAUNCH_CHECK();
-        }
-        const int npace = use_pace ? kPaceGroups * kPaceStages : 0;
-        const int ninit = std::max(std::max(std::max(std::max(nq_pad, npace), f2), fused ? CZ_FS_KEYWORDS : 0),
-                                   q_raw != nullptr ? nq * 64 : 0);   // (query prep: one wave per query)
-        hipLaunchKernelGGL(k_coarse_init, dim3((ninit + 255) / 256), dim3(256), 0, st, ix->cthr.p, ix->cand_n.p, flags,
-                           nflag, nq, nq_pad, (int)(n0 * CZ_T), use_pace ? ix->cpace.p : (int*)nullptr, npace,
-                           pass2 ? ix->cand_n2.p : (int*)nullptr, pass2 ? ix->thr2.p : (float*)nullptr, nflagB, f2,
-                           fused ? ix->fs_state.p : (int*)nullptr, q_raw, ix->qpad.p + (size_t)q0 * ix->dpad, ix->qnorm2.p + q0,
-                           ix->qerr2.p + q0, ix->dim, ix->dpad, normalize_q);
+// Thresholds, counters and flags of the chunk cleared in one launch (k_coarse_init), the rounded query rows around it.
+// q_raw != null (sweeps only): the raw query rows, still to be prepared (normalize_q as in search_dev_enqueue) -- the
+// init launch does it, so the int8 queries of the MFMA sweep are made behind it; a batch's queries come prepared.
+int cascade_init(css_index* ix, const CascadeCall& c, const float* q_raw, int normalize_q, hipStream_t st) {
+    const bool batch = c.kind == CascadeKind::Batch;
+    int rc;
+    if (batch && c.i8) {
+        if ((rc = launch_queries_to_i8(ix, c, st)) != CSS_OK) return rc;
+    } else if (batch) {
+        const int64_t ne = (int64_t)c.nq_pad * ix->dpad;
+        hipLaunchKernelGGL(k_rows_to_bf16, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, (const float*)c.qpad, ix->qh.p,
+                           (int64_t)c.nq, (int64_t)c.nq_pad, ix->dpad);
         CSS_LAUNCH_CHECK();
-        if (sweep_mfma) {   // int8 query rows (16, zero padded), their scales and error norms -- behind the init launch, which may have prepared qpad
-            if ((rc = ix->qh.grow((size_t)nq_pad * ix->dpad)) != CSS_OK) return rc;
-            if ((rc = ix->qscale.grow((size_t)nq_pad)) != CSS_OK) return rc;
-            if ((rc = ix->qerr2_i8.grow((size_t)q0 + nq_pad)) != CSS_OK) return rc;
-            hipLaunchKernelGGL(k_rows_to_i8, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, st, qpad,
-                               reinterpret_cast<signed char*>(ix->qh.p), ix->qscale.p, ix->qerr2_i8.p + q0, nq, nq_pad, ix->dpad);
-            CSS_LAUNCH_CHECK();
-        }
     }
-    const size_t lds = (size_t)CZ_NST * CZ_STAGE;
-    typedef void (*scan_fn)(const unsigned short*, const unsigned short*, const float*, float*, uint32_t*, int*, int64_t, int,
-                            int, int64_t, int64_t, int, int*, const uint32_t*, const float*, const int*, const float*,
-                            const float*);
-    // the 8-phase ping-pong loop (k_scan_coarse8) wherever its shape constraints hold
-    const bool loop8 = ix->dpad % 128 == 0;
-    const bool i8b = i8 && !sweep;   // (batch_uses_i8 implies the 8-phase loop)
-    // one-eps thresholds from exactly scored top-k candidates (k_coarse_select): the int8 scan, whose band is wide
-    // (the scores are inner products: batch_uses_i8)
-    const bool exact_k = (i8b || sweep_mfma) && k * 2 <= CZ_EXK;   // (both operands int8: the widest band)
-    const scan_fn f_stage0 = i8b ? k_scan_coarse8<true, false, CZ_CAP, true>
-                                 : (loop8 ? k_scan_coarse8<true, false> : k_scan_coarse<true, false>);
-    const scan_fn f_mid = i8b ? k_scan_coarse8<false, false, CZ_CAP, true>
-                              : (loop8 ? k_scan_coarse8<false, false> : k_scan_coarse<false, false>);
-    const scan_fn f_main = i8b ? k_scan_coarse8<false, true, CZ_CAP, true>
-                               : (loop8 ? k_scan_coarse8<false, true> : k_scan_coarse<false, true>);
-    const unsigned short* scan_rows = i8b ? reinterpret_cast<const unsigned short*>(rows.x8) : rows.xh;
-    const float* scan_xsc = i8b ? rows.x8s : nullptr;
-    const float* scan_qsc = i8b ? ix->qscale.p : nullptr;
-    if (!sweep)
-        for (scan_fn f : {f_stage0, f_mid, f_main})
-            if ((rc = css::ensure_dynamic_lds((const void*)f, lds, ix->device)) != CSS_OK) return rc;
-    const int grid = coarse_grid(ix);
-    CSS_REQUIRE(sweep || (grid / 8) / nqt >= 1, "css_index_search: %d query tiles do not fit a grid of %d blocks", nqt, grid);
+    const int npace = batch ? kPaceGroups * kPaceStages : 0;
+    const int ninit = std::max(std::max(std::max(std::max(c.nq_pad, npace), c.f2), c.fused ? CZ_FS_KEYWORDS : 0),
+                               q_raw != nullptr ? c.nq * 64 : 0);   // (query prep: one wave per query)
+    hipLaunchKernelGGL(k_coarse_init, dim3((ninit + 255) / 256), dim3(256), 0, st, ix->cthr.p, ix->cand_n.p, c.flags,
+                       c.nflag, c.nq, c.nq_pad, (int)(c.plan.st[0].count * CZ_T), batch ? ix->cpace.p : (int*)nullptr, npace,
+                       c.pass2 ? ix->cand_n2.p : (int*)nullptr, c.pass2 ? ix->thr2.p : (float*)nullptr, c.nflagB, c.f2,
+                       c.fused ? ix->fs_state.p : (int*)nullptr, q_raw, c.qpad, c.qnorm2, ix->qerr2.p + c.q0, ix->dim, ix->dpad,
+                       normalize_q);
+    CSS_LAUNCH_CHECK();
+    return c.kind == CascadeKind::SweepMfma ? launch_queries_to_i8(ix, c, st) : CSS_OK;
+}
 
-    int stage_idx = 0;
-    if (fused) {
-        ProfScope all("knn_sweep_cascade", st);
-        {
-            ProfScope ps("knn_sweep_fused", st);
-            if (nq <= 1) rc = launch_sweep_cascade_nq<1>(ix, rows, qpad, nq, fsched, flags, qnorm2, eps_rel, l2, k, measured, st, i8);
-            else if (nq <= 2) rc = launch_sweep_cascade_nq<2>(ix, rows, qpad, nq, fsched, flags, qnorm2, eps_rel, l2, k, measured, st, i8);
-            else rc = launch_sweep_cascade_nq<4>(ix, rows, qpad, nq, fsched, flags, qnorm2, eps_rel, l2, k, measured, st, i8);
-            if (rc != CSS_OK) return rc;
-        }
-        if ((rc = launch_final_select(ix, rows, nq, k, EpsSet{eps_rel, qerr2, measured}, eps_p2, exact_k, l2, 0, qpad, qnorm2, ix->gthr.p + q0, flags, nflag, flag_list, D_dev,
-                                      I_dev, pass2 ? ix->thr2.p : nullptr, pass2 ? ix->qh2.p : nullptr, f2, st)) != CSS_OK)
-            return rc;
-    } else {
-    ProfScope all(sweep ? "knn_sweep_cascade" : "knn_coarse_cascade", st);
-    for (size_t si = 0; si < sched.size(); ++si) {
-        const int64_t s = sched[si].stride;
-        const int gr = si == 0 ? g : sched[si].ratio;   // (stage 0 does not use the ratio)
-        const bool stage0 = si == 0;
-        const int64_t W = (ntiles + s - 1) / s;
-        const int64_t count = stage0 ? W : (W - 1) - (W - 1) / gr;
-        if (count > 0 && sweep_mfma) {
-            ProfScope ps(s == 1 && !stage0 ? "knn_sweep_mfma_main" : "knn_sweep_mfma_stage", st);
-            if ((rc = launch_sweep_mfma(ix, rows, nq, count, s, std::max(1, gr - 1), stage0, st)) != CSS_OK) return rc;
-        } else if (count > 0 && sweep) {
-            ProfScope ps(s == 1 && !stage0 ? "knn_sweep_coarse_main" : "knn_sweep_coarse_stage", st);
-            if (nq <= 1) rc = launch_sweep_coarse_nq<1>(ix, rows, qpad, nq, count, s, gr - 1, stage0, st, i8);
-            else if (nq <= 2) rc = launch_sweep_coarse_nq<2>(ix, rows, qpad, nq, count, s, gr - 1, stage0, st, i8);
-            else rc = launch_sweep_coarse_nq<4>(ix, rows, qpad, nq, count, s, gr - 1, stage0, st, i8);
-            if (rc != CSS_OK) return rc;
-        } else if (count > 0) {
-            const scan_fn f = stage0 ? f_stage0 : (s == 1 ? f_main : f_mid);
-            ProfScope ps(s == 1 && !stage0 ? "knn_scan_coarse_main" : "knn_scan_coarse_stage", st);
-            // int8 rows, later stages: the queries stay in registers (k_scan_qreg_i8) -- from two (row tile, query tile) pairs
-            // per block on: a block first loads its 256 queries.  ms per search, k = 10, 64 / 256 / 1000 queries, minimum
-            // 0 / 1024 / 4096 / never: 300 k rows 0.31, 0.35, 0.56 / 0.26, 0.31, 0.53 / 0.26, 0.31, 0.56 / 0.25, 0.31, 0.56;
-            // 3 M rows (1024 / 4096 / never) 0.70, 0.79, 2.25 / 0.73, 0.84, 2.28 / 0.78, 0.90, 2.56; 10 M rows 1.88, 1.99,
-            // 6.45 / 1.88, 2.01, 6.52 / 2.05, 2.27, 7.36.
-            if (i8b && !stage0 && qreg_applies(ix, nqt) && count * nqt >= env.qreg_min) {
-                if ((rc = launch_scan_qreg(ix, rows, nqt, count, s, gr - 1, s == 1, st)) != CSS_OK) return rc;
-            } else {
-                // (int8 rows: no sibling pacing -- a row tile fetched by every query-tile block on its own is still only
-                // ~3.5 TB/s worst case at this scan's speed, and the coupling costs more than the HBM traffic it saves:
-                // 9.65 vs 9.02 ms per batch; the bf16 scan reads twice the bytes per row and needs it)
-                int* pace = (!i8b && grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace.p + (size_t)stage_idx * kPaceGroups : nullptr;
-                hipLaunchKernelGGL(f, dim3(grid), dim3(512), lds, st, scan_rows, ix->qh.p, ix->cthr.p, ix->cand_s.p, ix->cand_i.p,
-                                   ix->cand_n.p, rows.n, ix->dpad, nqt, count, s, gr - 1, pace, rows.mask, xn2,
-                                   (const int*)nullptr, scan_xsc, scan_qsc);
-                CSS_LAUNCH_CHECK();
+// the VALU sweep: all stages in one launch, or stage by stage
+int launch_sweep_cascade(css_index* ix, const Rows& rows, const CascadeCall& c, hipStream_t st) {
+    return sweep_nq_slots(c.nq, [&](auto NQ) -> int {
+        if (c.i8)
+            return sweep_unrolled<3>(ix, false, [&](auto TT, auto) -> int {
+                return launch_sweep_cascade_t<decltype(NQ)::value, decltype(TT)::value, true>(ix, rows, c, st);
+            });
+        return sweep_unrolled<6>(ix, false, [&](auto TT, auto) -> int {
+            return launch_sweep_cascade_t<decltype(NQ)::value, decltype(TT)::value, false>(ix, rows, c, st);
+        });
+    });
+}
+int launch_sweep_coarse(css_index* ix, const Rows& rows, const CascadeCall& c, int64_t count, int64_t stride, int gm1,
+                        bool stage0, hipStream_t st) {
+    return sweep_nq_slots(c.nq, [&](auto NQ) -> int {
+        if (c.i8)
+            return sweep_unrolled<3>(ix, stride == 1 && !stage0, [&](auto TT, auto MAIN) -> int {
+                return launch_sweep_coarse_i8_t<decltype(NQ)::value, decltype(TT)::value, decltype(MAIN)::value>(
+                    ix, rows, c.qpad, c.nq, count, stride, gm1, stage0, st);
+            });
+        return sweep_unrolled<6>(ix, stride == 1 && !stage0, [&](auto TT, auto MAIN) -> int {
+            return launch_sweep_coarse_t<decltype(NQ)::value, decltype(TT)::value, decltype(MAIN)::value>(
+                ix, rows, c.qpad, c.nq, count, stride, gm1, stage0, st);
+        });
+    });
+}
+
+// stage si of the plan on the kernel of the call's kind
+int cascade_stage(css_index* ix, const Rows& rows, const CascadeCall& c, int si, hipStream_t st) {
+    const CascadeStage& s = c.plan.st[si];
+    if (s.count <= 0) return CSS_OK;
+    const bool stage0 = si == 0, main_stage = s.stride == 1 && !stage0;
+    const int gm1 = cascade_gm1(c.plan, c.growth, si);
+    if (c.kind == CascadeKind::SweepMfma) {
+        ProfScope ps(main_stage ? "knn_sweep_mfma_main" : "knn_sweep_mfma_stage", st);
+        return launch_sweep_mfma(ix, rows, c.nq, s.count, s.stride, gm1, stage0, st);
+    }
+    if (c.kind == CascadeKind::SweepValu) {
+        ProfScope ps(main_stage ? "knn_sweep_coarse_main" : "knn_sweep_coarse_stage", st);
+        return launch_sweep_coarse(ix, rows, c, s.count, s.stride, gm1, stage0, st);
+    }
+    ProfScope ps(main_stage ? "knn_scan_coarse_main" : "knn_scan_coarse_stage", st);
+    // int8 rows, later stages: the queries stay in registers (k_scan_qreg_i8) -- from two (row tile, query tile) pairs
+    // per block on: a block first loads its 256 queries.  ms per search, k = 10, 64 / 256 / 1000 queries, minimum
+    // 0 / 1024 / 4096 / never: 300 k rows 0.31, 0.35, 0.56 / 0.26, 0.31, 0.53 / 0.26, 0.31, 0.56 / 0.25, 0.31, 0.56;
+    // 3 M rows (1024 / 4096 / never) 0.70, 0.79, 2.25 / 0.73, 0.84, 2.28 / 0.78, 0.90, 2.56; 10 M rows 1.88, 1.99,
+    // 6.45 / 1.88, 2.01, 6.52 / 2.05, 2.27, 7.36.
+    if (c.i8 && !stage0 && qreg_applies(ix, c.nqt) && s.count * c.nqt >= knn_env().qreg_min)
+        return launch_scan_qreg(ix, rows, c.nqt, s.count, s.stride, gm1, main_stage, st);
+    // (int8 rows: no sibling pacing -- a row tile fetched by every query-tile block on its own is still only
+    // ~3.5 TB/s worst case at this scan's speed, and the coupling costs more than the HBM traffic it saves:
+    // 9.65 vs 9.02 ms per batch; the bf16 scan reads twice the bytes per row and needs it)
+    const int grid = coarse_grid(ix);
+    int* pace = (!c.i8 && grid / 8 <= kPaceGroups / 8 && si < kPaceStages) ? ix->cpace.p + (size_t)si * kPaceGroups : nullptr;
+    hipLaunchKernelGGL(stage0 ? c.scan_stage0 : (main_stage ? c.scan_main : c.scan_mid), dim3(grid), dim3(512),
+                       (size_t)CZ_NST * CZ_STAGE, st, c.i8 ? reinterpret_cast<const unsigned short*>(rows.x8) : rows.xh, ix->qh.p,
+                       ix->cthr.p, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p, rows.n, ix->dpad, c.nqt, s.count, s.stride, gm1, pace,
+                       rows.mask, c.l2 ? rows.xnorm2 : nullptr,   // L2: coarse score = 2 x.q - ||x||^2
+                       (const int*)nullptr, c.i8 ? rows.x8s : nullptr, c.i8 ? ix->qscale.p : nullptr);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// the select between two stages (the next threshold), and the one behind the last: band, exact rescoring, results
+int cascade_select(css_index* ix, const Rows& rows, const CascadeCall& c, bool final, hipStream_t st) {
+    if (final)
+        return launch_final_select(ix, rows, c.nq, c.k, c.eps, c.eps_p2, c.exact_k, c.l2, 0, c.qpad, c.qnorm2, c.gthr, c.flags,
+                                   c.nflag, c.flag_list, c.D, c.I, c.pass2 ? ix->thr2.p : nullptr,
+                                   c.pass2 ? ix->qh2.p : nullptr, c.f2, st);
+    hipLaunchKernelGGL(k_coarse_select<false>, dim3(c.nq), dim3(256), 0, st, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p,
+                       ix->cthr.p, c.flags, c.nflag, c.flag_list, (const float*)c.qnorm2, ix->maxn2.p, c.eps.eps_rel, c.l2, c.k, 0, c.gthr,
+                       c.eps.qerr2, c.eps.measured, ix->fix_s.p, ix->fix_i.p, ix->fix_lock.p,
+                       c.exact_k ? (const float*)c.qpad : (const float*)nullptr,
+                       c.exact_k ? (const float*)rows.xb : (const float*)nullptr, ix->dpad);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// the second pass over the flagged queries of a batch (CascadeCall::pass2); every launch reads the flagged count from
+// device memory and returns at once when there is nothing to do
+int cascade_pass2(css_index* ix, const Rows& rows, const CascadeCall& c, hipStream_t st) {
+    ProfScope ps("knn_coarse_pass2", st);
+    const size_t lds = (size_t)CZ_NST * CZ_STAGE;
+    const scan_fn f_all = k_scan_coarse8<false, true, CZ_CAP2>;   // every row tile against thr2 (the gate also makes tile = ordinal)
+    int rc;
+    if ((rc = css::ensure_dynamic_lds((const void*)f_all, lds, ix->device)) != CSS_OK) return rc;
+    const int grid = coarse_grid(ix);
+    const int stage_idx = c.plan.n;   // (its pacing counters: behind the stages')
+    int* pace = (grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace.p + (size_t)stage_idx * kPaceGroups : nullptr;
+    hipLaunchKernelGGL(f_all, dim3(grid), dim3(512), lds, st, rows.xh, ix->qh2.p, ix->thr2.p, ix->cand_s2.p, ix->cand_i2.p,
+                       ix->cand_n2.p, rows.n, ix->dpad, c.f2 / CZ_T, c.plan.ntiles, (int64_t)1, 1 << 30, pace, rows.mask,
+                       c.l2 ? rows.xnorm2 : nullptr, (const int*)c.nflag, (const float*)nullptr, (const float*)nullptr);
+    hipLaunchKernelGGL(k_rescore_parts<true>, dim3(kRescoreGrid), dim3(256), 0, st, ix->cand_s2.p, ix->cand_i2.p, ix->cand_n2.p,
+                       CZ_CAP2, c.f2, c.nflag, c.flag_list, ix->thr2.p, c.l2, (const float*)c.qpad, rows.xb, ix->dpad, (const int*)nullptr,
+                       (const int*)nullptr);
+    hipLaunchKernelGGL(k_coarse_select2<CZ_CAP2>, dim3(c.f2), dim3(256), 0, st, ix->cand_s2.p, ix->cand_i2.p, ix->cand_n2.p, c.nflag,
+                       c.flag_list, c.f2, c.nflagB, c.flag_listB, c.l2, c.k, rows.id_base, c.D, c.I);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// Coarse scan + exact rescoring (css_knn_coarse.h) for queries [q0, q0 + nq) of ix->qpad.p; nq <= 4096.
+// Everything is enqueued on `st`; nothing waits for the device (flagged queries are fixed up on the device).
+// kind, use_i8: decided once per search by the caller (search_dev_enqueue / search_noshadow_ranges); record_fb: this is
+// the search's last chunk, whose flagged count is what the int8 feedback sees.  q_raw, normalize_q: cascade_init.
+int launch_scan_coarse(css_index* ix, const Rows& rows, int q0, int nq, int k, float* D_dev, int64_t* I_dev, hipStream_t st,
+                       const SweepGeom& sg, CascadeKind kind, bool use_i8, bool record_fb, const float* q_raw = nullptr,
+                       int normalize_q = 0) {
+    const bool batch = kind == CascadeKind::Batch;
+    CascadeCall c = cascade_call(ix, rows, kind, use_i8, q0, nq, k, D_dev, I_dev);
+    int rc;
+    if ((rc = cascade_workspace(ix, c, st)) != CSS_OK) return rc;
+    ix->last_nflag = c.nflag;
+    ix->last_nswept = c.pass2 ? c.nflagB : c.nflag;
+    if ((rc = cascade_init(ix, c, q_raw, normalize_q, st)) != CSS_OK) return rc;
+    if (batch)
+        for (scan_fn f : {c.scan_stage0, c.scan_mid, c.scan_main})
+            if ((rc = css::ensure_dynamic_lds((const void*)f, (size_t)CZ_NST * CZ_STAGE, ix->device)) != CSS_OK) return rc;
+    CSS_REQUIRE(!batch || (coarse_grid(ix) / 8) / c.nqt >= 1, "css_index_search: %d query tiles do not fit a grid of %d blocks",
+                c.nqt, coarse_grid(ix));
+    {
+        ProfScope all(batch ? "knn_coarse_cascade" : "knn_sweep_cascade", st);
+        if (c.fused) {
+            {
+                ProfScope ps("knn_sweep_fused", st);
+                if ((rc = launch_sweep_cascade(ix, rows, c, st)) != CSS_OK) return rc;
+            }
+            if ((rc = cascade_select(ix, rows, c, true, st)) != CSS_OK) return rc;
+        } else {
+            for (int si = 0; si < c.plan.n; ++si) {
+                if ((rc = cascade_stage(ix, rows, c, si, st)) != CSS_OK) return rc;
+                if ((rc = cascade_select(ix, rows, c, si == c.plan.n - 1, st)) != CSS_OK) return rc;
             }
         }
-        ++stage_idx;
-        if (s == 1) {
-            if ((rc = launch_final_select(ix, rows, nq, k, EpsSet{eps_rel, qerr2, measured}, eps_p2, exact_k, l2, 0, qpad, qnorm2, ix->gthr.p + q0, flags, nflag, flag_list, D_dev,
-                                          I_dev, pass2 ? ix->thr2.p : nullptr, pass2 ? ix->qh2.p : nullptr, f2, st)) != CSS_OK)
-                return rc;
-            break;
-        }
-        hipLaunchKernelGGL(k_coarse_select<false>, dim3(nq), dim3(256), 0, st, ix->cand_s.p, ix->cand_i.p, ix->cand_n.p,
-                           ix->cthr.p, flags, nflag, flag_list, qnorm2, ix->maxn2.p, eps_rel, l2, k, 0, ix->gthr.p + q0, qerr2, measured, ix->fix_s.p,
-                           ix->fix_i.p, ix->fix_lock.p, exact_k ? qpad : (const float*)nullptr,
-                           exact_k ? (const float*)rows.xb : (const float*)nullptr, ix->dpad);
-        CSS_LAUNCH_CHECK();
-    }
     }
     // feedback for batch_i8_wanted / sweep_uses_i8: the last chunk of a search speaks for it
-    if (record_fb && i8b && env.batch_i8 == 1 && (rc = i8_feedback_record(ix->fb_batch, nflag, nq, st)) != CSS_OK) return rc;
-    if (record_fb && i8 && sweep && (rc = i8_feedback_record(ix->fb_sweep, nflag, nq, st)) != CSS_OK) return rc;
-    if (pass2) {
-        // every launch below reads the flagged count from device memory and returns at once when there is nothing to do
-        ProfScope ps("knn_coarse_pass2", st);
-        const scan_fn f_all = k_scan_coarse8<false, true, CZ_CAP2>;   // every row tile against thr2 (the gate also makes tile = ordinal)
-        if ((rc = css::ensure_dynamic_lds((const void*)f_all, lds, ix->device)) != CSS_OK) return rc;
-        const int nqt2 = f2 / CZ_T;
-        {
-            int* pace = (grid / 8 <= kPaceGroups / 8 && stage_idx < kPaceStages) ? ix->cpace.p + (size_t)stage_idx * kPaceGroups : nullptr;
-            hipLaunchKernelGGL(f_all, dim3(grid), dim3(512), lds, st, rows.xh, ix->qh2.p, ix->thr2.p, ix->cand_s2.p, ix->cand_i2.p,
-                               ix->cand_n2.p, rows.n, ix->dpad, nqt2, ntiles, (int64_t)1, 1 << 30, pace, rows.mask, xn2,
-                               (const int*)nflag, (const float*)nullptr, (const float*)nullptr);
-        }
-        hipLaunchKernelGGL(k_rescore_parts<true>, dim3(kRescoreGrid), dim3(256), 0, st, ix->cand_s2.p, ix->cand_i2.p, ix->cand_n2.p,
-                           CZ_CAP2, f2, nflag, flag_list, ix->thr2.p, l2, qpad, rows.xb, ix->dpad, (const int*)nullptr, (const int*)nullptr);
-        hipLaunchKernelGGL(k_coarse_select2<CZ_CAP2>, dim3(f2), dim3(256), 0, st, ix->cand_s2.p, ix->cand_i2.p, ix->cand_n2.p, nflag,
-                           flag_list, f2, nflagB, flag_listB, l2, k, rows.id_base, D_dev, I_dev);
-        CSS_LAUNCH_CHECK();
-        // what overflowed the second pass too (tens of thousands of rows inside one band): exact fp32 sweep
-        return launch_fixup(ix, rows, qpad, nq, k, ix->gthr.p + q0, flag_listB, nflagB, D_dev, I_dev, sg, st);
-    }
-    // queries whose candidate buffer or band overflowed (thousands of duplicate rows, a zero query): exact
-    // fp32 sweep on the device, two launches that return at once when the flag count is zero
-    return launch_fixup(ix, rows, qpad, nq, k, ix->gthr.p + q0, flag_list, nflag, D_dev, I_dev, sg, st);
+    if (record_fb && use_i8 && batch && knn_env().batch_i8 == 1 && (rc = i8_feedback_record(ix->fb_batch, c.nflag, nq, st)) != CSS_OK) return rc;
+    if (record_fb && use_i8 && !batch && (rc = i8_feedback_record(ix->fb_sweep, c.nflag, nq, st)) != CSS_OK) return rc;
+    if (c.pass2 && (rc = cascade_pass2(ix, rows, c, st)) != CSS_OK) return rc;
+    // queries whose candidate buffer or band overflowed (thousands of duplicate rows, a zero query) -- and, behind a second
+    // pass, its buffers too (tens of thousands of rows inside one band): exact fp32 sweep on the device, two launches that
+    // return at once when the flag count is zero
+    return launch_fixup(ix, rows, c.qpad, nq, k, c.gthr, c.pass2 ? c.flag_listB : c.flag_list, c.pass2 ? c.nflagB : c.nflag, c.D,
+                        c.I, sg, st);
 }
 
 // grid of the exact fp32 sweeps (k_scan_small, k_range_small, k_scan_prior, k_scan_examples) over the rows in view:
@@ -2943,7 +2936,7 @@ int search_noshadow_ranges(css_index* ix, const Rows& rows, int64_t nq, int k, f
         const int chunk = coarse_max_chunk(ix);
         for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
             const int nqc = (int)std::min<int64_t>(chunk, nq - q0);
-            if ((rc = launch_scan_coarse(ix, sub, (int)q0, nqc, k, Dp, Ip, st, sg, false, use_i8,
+            if ((rc = launch_scan_coarse(ix, sub, (int)q0, nqc, k, Dp, Ip, st, sg, CascadeKind::Batch, use_i8,
                                          r == nranges - 1 && q0 + nqc == nq)) != CSS_OK) return rc;
         }
     }
@@ -3085,11 +3078,13 @@ int search_dev_enqueue(css_index* ix, const Rows& rows, const float* q_dev, int6
         const bool sweep = sweep_path;
         const bool use_i8 = rows.x8 != nullptr && (sweep ? sweep_i8 : batch_i8_wanted(ix, k, rows.n, nq));
         if (use_i8 || rows.xh != nullptr) {
-            if (sweep) return launch_scan_coarse(ix, rows, 0, (int)nq, k, D_dev, I_dev, st, sg, true, use_i8, true, q_dev, normalize_q);
+            // (3..32 queries on int8 rows where mfma_sweep_applies: the sweep on the int8 MFMA, int8 queries too)
+            const CascadeKind kind = !sweep ? CascadeKind::Batch : ((use_i8 && mfma_sweep_ok) ? CascadeKind::SweepMfma : CascadeKind::SweepValu);
+            if (sweep) return launch_scan_coarse(ix, rows, 0, (int)nq, k, D_dev, I_dev, st, sg, kind, use_i8, true, q_dev, normalize_q);
             const int chunk = coarse_max_chunk(ix);
             for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
                 const int nqc = (int)std::min<int64_t>(chunk, nq - q0);
-                if ((rc = launch_scan_coarse(ix, rows, (int)q0, nqc, k, D_dev, I_dev, st, sg, false, use_i8, q0 + nqc == nq)) != CSS_OK)
+                if ((rc = launch_scan_coarse(ix, rows, (int)q0, nqc, k, D_dev, I_dev, st, sg, kind, use_i8, q0 + nqc == nq)) != CSS_OK)
                     return rc;
             }
             return CSS_OK;

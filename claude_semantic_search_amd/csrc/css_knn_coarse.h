@@ -147,7 +147,7 @@ constexpr int CZ_PARTS = 16;
 #endif
 constexpr int CZ_NS = CZ_NS_STRIDE;
 // k_sweep_cascade (the 1..4-query cascade in one launch, below): its limits and its state words
-constexpr int CZ_FS_MAXST = 16;            // stages (growth 4: 4^15 tiles)
+// (CZ_FS_MAXST, its stages: css_knn_plan.h, where the host plans them)
 constexpr int CZ_FS_RING = 16;             // pending quarter tiles per wave
 constexpr int CZ_FS_SENT = 0x7FFFFFFF;     // key word "not published yet" (a NaN's key: a published threshold never is one)
 // state words (k_coarse_init).  Agent-scope atomics AND sc1 loads of one 128-byte line complete at only ~30 per microsecond
