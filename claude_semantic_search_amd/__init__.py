@@ -20,6 +20,7 @@ _LAZY = {
     "HybridStorage": ".storage",
     "recency_priors": ".storage",
     "Topic": ".storage",
+    "MapPoint": ".storage",
     "EmbeddingConfig": ".embeddings",
     "EmbeddingStats": ".embeddings",
     "EmbeddingGenerator": ".embeddings",
@@ -31,6 +32,10 @@ _LAZY = {
     "KmeansResult": ".flat_index",
     "KmeansStep": ".flat_index",
     "run_kmeans": ".flat_index",
+    "PCAMatrix": ".flat_index",
+    "PcaResult": ".flat_index",
+    "GramResult": ".flat_index",
+    "pca_from_gram": ".flat_index",
     "terms_of": ".lexical",
     "bm25_weights": ".lexical",
     "MpnetEncoder": ".mpnet_encoder",

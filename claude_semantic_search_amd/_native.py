@@ -34,6 +34,7 @@ TERM_SPACE = 1 << 24   # include/css_hip.h CSS_TERM_SPACE
 MAX_EXAMPLES = 16   # include/css_hip.h CSS_MAX_EXAMPLES
 MAX_EXAMPLES_K = 128   # css_index_search_examples: the same list size
 MAX_CENTROIDS = 4096   # include/css_hip.h CSS_MAX_CENTROIDS
+MAX_TRANSFORM_ROWS = 256   # include/css_hip.h CSS_MAX_TRANSFORM_ROWS
 
 
 class CssError(RuntimeError):
@@ -127,6 +128,9 @@ PROTOTYPES = {
     "css_index_export_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "css_index_kmeans_step": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       POINTER(c_int), POINTER(c_int), c_void_p, c_void_p]),
+    "css_index_set_gram_rows": (c_int, [c_void_p, c_int64]),
+    "css_index_gram": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
+    "css_index_transform": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "css_index_set_terms": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "css_index_get_terms": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "css_index_term_stats": (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(c_int64), POINTER(c_int64)]),

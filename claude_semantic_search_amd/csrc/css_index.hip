@@ -39,6 +39,8 @@
 //                      re-formed behind the merge (css_knn_examples.h).   HBM bound
 //   k_kmeans_assign,   css_index_kmeans_step: one Lloyd step -- rows x centroids on the fp32-input MFMA, member lists,
 //   k_kmeans_sum       fixed-point int64 sums (css_kmeans.h)
+//   k_gram_fx,         css_index_gram: the fixed-point Gram matrix of the rows on the fp64 matrix core;
+//   k_transform_rows   css_index_transform: y = A x + b over stored rows, the K loop of k_kmeans_assign (css_pca.h)
 //   k_lex_scores       css_index_search_hybrid: the BM25 column of one query over the per-row term lists, handed to
 //                      k_scan_prior in the place of the priors (css_lexical.h).   HBM bound
 //   k_mmr_select       css_index_search_diverse: k of a pool of the best rows picked greedily by maximal marginal
@@ -71,6 +73,7 @@
 #include <cmath>
 #include <map>
 #include <mutex>
+#include <memory>
 #include <new>
 #include <optional>
 #include <shared_mutex>
@@ -231,6 +234,12 @@ struct css_index {
     DevBuf<int32_t> km_assign;
     DevBuf<uint32_t> km_members, km_off;
     DevBuf<long long> km_out;
+    // css_index_gram (css_pca.h): [GR_HDR words | gp column sums | gp * gp matrix] of int64, gp = dpad rounded up to 128.
+    // css_index_transform: the uploaded [A | b] ([m, dim] then [m]); the padded table [mpad][dpad] with its squared
+    // norms [mpad] (unused) and the padded bias [mpad] behind it; and one batch of results [rows, m]
+    DevBuf<long long> gr_out;
+    int64_t gram_rows = 0;   // css_index_set_gram_rows: rows per block of k_gram_fx (0: the rule of gram_enqueue)
+    DevBuf<float> tr_raw, tr_tab, tr_y;
     // rows written by css_index_add_dev / _add_synthetic on the CALLER's stream: searches, reallocation and
     // export wait for this event before touching rows, norms or maxn2
     hipEvent_t ingest_ev = nullptr;
@@ -2782,6 +2791,8 @@ int search_chunk_prior(css_index* ix, const Rows& rows, int q0, int nqc, int k, 
 
 // ------------------------------------------------------------------ k-means step (css_kmeans.h)
 #include "css_kmeans.h"
+// ------------------------------------------------------------------ Gram matrix and linear transform (css_pca.h)
+#include "css_pca.h"
 
 // ------------------------------------------------------------------ search by examples (css_knn_examples.h)
 #include "css_knn_examples.h"
@@ -3508,6 +3519,14 @@ int css_index_set_range_rows(css_index* ix, int64_t rows) {
     CSS_REQUIRE(rows >= 0, "css_index_set_range_rows: rows < 0");
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     ix->range_rows = rows;
+    return CSS_OK;
+}
+
+int css_index_set_gram_rows(css_index* ix, int64_t rows) {
+    CSS_REQUIRE(ix, "css_index_set_gram_rows: NULL index");
+    CSS_REQUIRE(rows >= 0, "css_index_set_gram_rows: rows < 0");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    ix->gram_rows = rows;
     return CSS_OK;
 }
 
@@ -4886,6 +4905,165 @@ int css_index_kmeans_step(css_index* ix, const float* centroids_host, int nc, in
     if (fx_shift_used) *fx_shift_used = (int)h[1];
     if (obj_shift_used) *obj_shift_used = (int)h[2];
     return CSS_OK;
+}
+
+namespace {
+// The Gram matrix and column sums of the call's rows into gr_out.  Everything is enqueued on `st`; nothing waits for
+// the device.  Caller holds ws_mu and a shared lock on mu.
+int gram_enqueue(css_index* ix, const Rows& rows, int fx_shift, int gp, hipStream_t st) {
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    // rows appended on another stream must have landed (the running maximum with them)
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    const size_t words = (size_t)GR_HDR + gp + (size_t)gp * gp;
+    if ((rc = ix->gr_out.grow(words)) != CSS_OK) return rc;
+    long long* hdr = ix->gr_out.p;
+    unsigned long long* colsum = reinterpret_cast<unsigned long long*>(hdr + GR_HDR);
+    unsigned long long* G = colsum + gp;
+    CSS_HIP_TRY(hipMemsetAsync(hdr, 0, words * sizeof(long long), st));
+    hipLaunchKernelGGL(k_gram_params, dim3(1), dim3(64), 0, st, (const int*)ix->maxn2.p, rows.n, fx_shift, hdr);
+    CSS_LAUNCH_CHECK();
+    if (rows.n == 0) return CSS_OK;   // zeros
+    const int T = gp / GR_T, ntile = T * (T + 1) / 2;
+    // strips: about four blocks per CU over the tiles, at least 512 rows each (a block ends in 16384 atomics), a
+    // multiple of the staged chunk; the integers do not depend on this choice
+    const int64_t want = std::max<int64_t>(1, (4 * (int64_t)ix->num_cus + ntile - 1) / ntile);
+    int64_t rpb = std::max<int64_t>(512, (rows.n + want - 1) / want);
+    if (ix->gram_rows > 0) rpb = ix->gram_rows;   // css_index_set_gram_rows: another grid, the same integers
+    rpb = (rpb + GR_KC - 1) / GR_KC * GR_KC;
+    const int64_t strips = (rows.n + rpb - 1) / rpb;
+    CSS_REQUIRE(strips <= 65535, "css_index_gram: internal: %lld strips", (long long)strips);
+    ProfScope ps("gram_fx", st);
+    hipLaunchKernelGGL(k_gram_fx, dim3((unsigned)ntile, (unsigned)strips), dim3(256), 0, st, rows.xb, rows.n, ix->dpad, gp, rpb,
+                       rows.mask, (const long long*)hdr, G, colsum);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// y = A x + b for rows [row0, row0 + n) into y_out_host, in batches of rows through tr_y.  a_dev: the uploaded
+// [A | b].  Everything is enqueued on `st`; nothing waits for the device.  Caller holds ws_mu and a shared lock on mu.
+int transform_enqueue(css_index* ix, const Rows& rows, const float* a_dev, int m, int64_t row0, int64_t n, float* y_out_host,
+                      hipStream_t st) {
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    CSS_REQUIRE(ix->dpad % MF_BK == 0, "css_index_transform: internal: dpad=%d is no multiple of %d", ix->dpad, MF_BK);
+    const int mtiles = (m + MF_BM - 1) / MF_BM, mpad = mtiles * MF_BM;
+    if ((rc = ix->tr_tab.grow((size_t)mpad * ix->dpad + 2 * (size_t)mpad)) != CSS_OK) return rc;
+    float* atab = ix->tr_tab.p;
+    float* an2 = atab + (size_t)mpad * ix->dpad;
+    float* bias = an2 + mpad;
+    // the table: the row kernel of ingest pads the rows of A (its squared norms go unused); pad rows and pad bias are zero
+    CSS_HIP_TRY(hipMemsetAsync(atab + (size_t)m * ix->dpad, 0, ((size_t)(mpad - m) * ix->dpad + 2 * (size_t)mpad) * sizeof(float), st));
+    hipLaunchKernelGGL(k_ingest_rows<false>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, a_dev, atab, an2, (int64_t)m,
+                       ix->dim, ix->dpad, 0, 0ull, 0ll, (unsigned short*)nullptr, (int*)nullptr, (float*)nullptr,
+                       (unsigned char*)nullptr, (float*)nullptr);
+    CSS_LAUNCH_CHECK();
+    CSS_HIP_TRY(hipMemcpyAsync(bias, a_dev + (size_t)m * ix->dim, (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, st));
+    const int64_t batch = std::min<int64_t>(n, std::max<int64_t>(MF_BN, ((int64_t)1 << 24) / m / MF_BN * MF_BN));
+    if ((rc = ix->tr_y.grow((size_t)batch * m)) != CSS_OK) return rc;
+    const size_t lds = (size_t)(2 * MF_BM * MF_BK + 2 * MF_BN * MF_BK + mpad) * 4;
+    if ((rc = css::ensure_dynamic_lds((const void*)k_transform_rows, lds, ix->device)) != CSS_OK) return rc;
+    for (int64_t r = 0; r < n; r += batch) {
+        const int64_t nb = std::min(batch, n - r);
+        const int64_t ntiles = (nb + MF_BN - 1) / MF_BN;
+        const int64_t want = std::min<int64_t>(ntiles, 2 * (int64_t)ix->num_cus);   // two blocks per CU
+        const int64_t tpb = (ntiles + want - 1) / want;
+        const unsigned grid = (unsigned)((ntiles + tpb - 1) / tpb);
+        {
+            ProfScope ps("transform_rows", st);
+            hipLaunchKernelGGL(k_transform_rows, dim3(grid), dim3(256), lds, st, rows.xb + (size_t)(row0 + r) * ix->dpad,
+                               (const float*)atab, (const float*)bias, m, mtiles, nb, ix->dpad, tpb, ix->tr_y.p);
+            CSS_LAUNCH_CHECK();
+        }
+        CSS_HIP_TRY(hipMemcpyAsync(y_out_host + (size_t)r * m, ix->tr_y.p, (size_t)nb * m * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_gram(css_index* ix, int fx_shift, const uint32_t* allow_bits_host, int64_t* gram_host, int64_t* colsum_host,
+                   int64_t* count_host, int* fx_shift_used) {
+    CSS_REQUIRE(ix, "css_index_gram: NULL index");
+    CSS_REQUIRE(gram_host && colsum_host && count_host, "css_index_gram: NULL buffer");
+    CSS_REQUIRE(fx_shift < 1024, "css_index_gram: fx_shift=%d out of range", fx_shift);
+    HostCall hc(ix);
+    const hipStream_t st = ix->stream;
+    const int64_t n = hc.rows.n;
+    const int dim = ix->dim, gp = (ix->dpad + GR_T - 1) / GR_T * GR_T;
+    const size_t words = (size_t)GR_HDR + gp + (size_t)gp * gp;
+    const std::unique_ptr<long long[]> h(new (std::nothrow) long long[words]);
+    if (!h) {
+        css::set_error("css_index_gram: no host memory for %zu bytes of results", words * sizeof(long long));
+        return CSS_ERR_OOM;
+    }
+    hc.enqueued = true;
+    int rc = upload_allow_bits(ix, allow_bits_host, &hc.rows);
+    if (rc == CSS_OK) rc = gram_enqueue(ix, hc.rows, fx_shift, gp, st);
+    if (rc == CSS_OK) rc = [&]() -> int {   // one wait
+        CSS_HIP_TRY(hipMemcpyAsync(h.get(), ix->gr_out.p, words * sizeof(long long), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipStreamSynchronize(st));
+        return CSS_OK;
+    }();
+    if (rc != CSS_OK) return hc.wait_if_failed(rc);
+    // an imposed shift that this index's own row count and maximum cannot hold: the sums may have wrapped
+    CSS_REQUIRE(h[1] != 0, "css_index_gram: fx_shift=%d is too large for %lld rows with this index's largest norm: "
+                "the largest safe value is %lld", fx_shift, (long long)n, h[2]);
+    // the device fills the upper TILE triangle; the rest is its mirror image.  Pad columns stay behind.
+    const long long* cs = h.get() + GR_HDR;
+    const long long* G = cs + gp;
+    for (int i = 0; i < dim; ++i) {
+        colsum_host[i] = (int64_t)cs[i];
+        for (int j = 0; j < dim; ++j)
+            gram_host[(size_t)i * dim + j] = (int64_t)(i / GR_T <= j / GR_T ? G[(size_t)i * gp + j] : G[(size_t)j * gp + i]);
+    }
+    int64_t count = n;
+    if (allow_bits_host && n > 0) {
+        count = 0;
+        for (int64_t w = 0, words = (n + 31) / 32; w < words; ++w) {
+            uint32_t bits = allow_bits_host[w];
+            if (w == words - 1 && (n & 31)) bits &= (1u << (n & 31)) - 1u;
+            count += __builtin_popcount(bits);
+        }
+    }
+    *count_host = count;
+    if (fx_shift_used) *fx_shift_used = (int)h[0];
+    return CSS_OK;
+}
+
+int css_index_transform(css_index* ix, const float* A_host, const float* b_host, int m, int64_t row0, int64_t n,
+                        float* y_out_host) {
+    CSS_REQUIRE(ix, "css_index_transform: NULL index");
+    CSS_REQUIRE(m >= 1 && m <= CSS_MAX_TRANSFORM_ROWS, "css_index_transform: m=%d outside [1, %d]", m, CSS_MAX_TRANSFORM_ROWS);
+    CSS_REQUIRE(A_host, "css_index_transform: NULL matrix");
+    for (size_t i = 0, e = (size_t)m * ix->dim; i < e; ++i)
+        CSS_REQUIRE(std::isfinite(A_host[i]), "css_index_transform: row %lld of A has a %s component (column %lld)",
+                    (long long)(i / ix->dim), std::isnan(A_host[i]) ? "NaN" : "infinite", (long long)(i % ix->dim));
+    for (int c = 0; b_host && c < m; ++c)
+        CSS_REQUIRE(std::isfinite(b_host[c]), "css_index_transform: entry %d of b is %s", c, std::isnan(b_host[c]) ? "NaN" : "infinite");
+    HostCall hc(ix);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && row0 + n <= hc.rows.n, "css_index_transform: rows [%lld, %lld) outside [0, %lld)",
+                (long long)row0, (long long)(row0 + n), (long long)hc.rows.n);
+    if (n == 0) return CSS_OK;
+    CSS_REQUIRE(y_out_host, "css_index_transform: NULL buffer");
+    const size_t nab = (size_t)m * ix->dim + m;   // [A | b], b = 0 without one: one upload
+    const std::unique_ptr<float[]> ab(new (std::nothrow) float[nab]);
+    if (!ab) {
+        css::set_error("css_index_transform: no host memory for %zu bytes of [A | b]", nab * sizeof(float));
+        return CSS_ERR_OOM;
+    }
+    memcpy(ab.get(), A_host, (size_t)m * ix->dim * sizeof(float));
+    if (b_host) memcpy(ab.get() + (size_t)m * ix->dim, b_host, (size_t)m * sizeof(float));
+    else memset(ab.get() + (size_t)m * ix->dim, 0, (size_t)m * sizeof(float));
+    int rc = hc.upload(nullptr, ix->tr_raw, (const float*)ab.get(), nab);
+    if (rc == CSS_OK) rc = transform_enqueue(ix, hc.rows, ix->tr_raw.p, m, row0, n, y_out_host, ix->stream);
+    if (rc == CSS_OK) rc = [&]() -> int {
+        CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+        return CSS_OK;
+    }();
+    return hc.wait_if_failed(rc);
 }
 
 }  // extern "C"

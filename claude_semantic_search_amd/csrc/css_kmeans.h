@@ -59,28 +59,26 @@ __global__ void k_kmeans_params(const int* __restrict__ maxn2, int64_t n, int fx
     hdr[7] = 0;
 }
 
-// LDS: As [2][128][32] centroids | Bs [2][128][32] rows | cn2s [ncpad] | cnt [nc]
-__global__ __launch_bounds__(256, 2) void k_kmeans_assign(const float* __restrict__ xb, const float* __restrict__ xnorm2,
-                                                          const float* __restrict__ ctab, const float* __restrict__ cn2,
-                                                          int nc, int nctiles, int64_t ntotal, int dpad,
-                                                          int64_t tiles_per_block, const uint32_t* __restrict__ mask,
-                                                          const long long* __restrict__ hdr, int32_t* __restrict__ assign,
-                                                          float* __restrict__ dist, unsigned long long* __restrict__ counts,
-                                                          unsigned long long* __restrict__ obj) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+// The K loop of k_kmeans_assign and k_transform_rows (css_pca.h): a block walks its strip of 128-row tiles, and for each
+// of them every 128-row tile of the table `ctab` ([nctiles * 128][dpad]: the A operand), accumulating the 128 x 128
+// scores on the fp32-input matrix core.  What happens to the scores is the epilogue's:
+//     epi.init(lds, tid)            once, in front of the first barrier; `lds` is the dynamic LDS behind As / Bs
+//     epi.tile(acc, ct, row, fh)    after the last K-step of table tile ct: acc[m][r] is the score of THIS lane's row
+//                                   `row` (it may be >= ntotal) against table row ct * 128 + 32 m + (r & 3) + 8 (r >> 2)
+//                                   + 4 fh; the epilogue leaves acc zeroed
+// Returns false, having touched nothing, when the block has no tile.
+template <class Epi>
+__device__ __forceinline__ bool km_sweep(const float* __restrict__ xb, const float* __restrict__ ctab, int nctiles,
+                                         int64_t ntotal, int dpad, int64_t tiles_per_block, char* smem, Epi& epi) {
     float* As = reinterpret_cast<float*>(smem);
     float* Bs = As + 2 * MF_BM * MF_BK;
-    float* cn2s = Bs + 2 * MF_BN * MF_BK;
-    unsigned int* cnt = reinterpret_cast<unsigned int*>(cn2s + nctiles * MF_BM);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t ntiles = (ntotal + MF_BN - 1) / MF_BN;
     const int64_t t_begin = (int64_t)blockIdx.x * tiles_per_block;
     const int64_t t_end = min(t_begin + tiles_per_block, ntiles);
-    if (t_begin >= t_end) return;
-    for (int i = tid; i < nctiles * MF_BM; i += 256) cn2s[i] = cn2[i];
-    for (int i = tid; i < nc; i += 256) cnt[i] = 0u;
-    const double scale_t = __longlong_as_double(hdr[6]);
+    if (t_begin >= t_end) return false;
+    epi.init(Bs + 2 * MF_BN * MF_BK, tid);
 
     const int KT = dpad / MF_BK;
     const int64_t n_it = (t_end - t_begin) * nctiles * KT;
@@ -109,13 +107,10 @@ __global__ __launch_bounds__(256, 2) void k_kmeans_assign(const float* __restric
 
     const int fr = lane & 31, fh = lane >> 5;
     const int jr = wave * 32 + fr;   // this lane's row inside the row tile
-    float bkey = -INFINITY;
-    int bc = 0;
-    long long objw = 0;
 
     KM_GLOAD(t_begin, 0, 0)
     KM_SSTORE(0)
-    __syncthreads();   // (also orders cn2s / cnt)
+    __syncthreads();   // (also orders what epi.init wrote)
     int cur = 0;
     int64_t rt = t_begin;
     int ct = 0, kt = 0;
@@ -148,47 +143,7 @@ __global__ __launch_bounds__(256, 2) void k_kmeans_assign(const float* __restric
                 acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].w, b.w, acc[m], 0, 0, 0);
             }
         }
-        if (kt == KT - 1) {
-            // ---------------- the 64 keys of this lane's row against centroid tile ct, ascending centroid number
-            const int cbase = ct * MF_BM;
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int c = cbase + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                    const float key = fmaf(-0.5f, cn2s[c], acc[m][r]);
-                    if (key > bkey) {
-                        bkey = key;
-                        bc = c;
-                    }
-                    acc[m][r] = 0.f;
-                }
-            if (ct == nctiles - 1) {
-                // ---------------- the row is done: the two lane halves meet, lane fr of half 0 writes it
-                const float okey = __shfl_xor(bkey, 32);
-                const int oc = __shfl_xor(bc, 32);
-                if (okey > bkey || (okey == bkey && oc < bc)) {
-                    bkey = okey;
-                    bc = oc;
-                }
-                const int64_t row = rt * MF_BN + jr;
-                if (fh == 0 && row < ntotal) {
-                    const bool ok = mask == nullptr || ((mask[row >> 5] >> (row & 31)) & 1u);
-                    int a_r = -1;
-                    float d_r = 0.f;
-                    if (ok) {
-                        a_r = bc;
-                        d_r = fmaxf(0.f, fmaf(-2.f, bkey, xnorm2[row]));
-                        atomicAdd(&cnt[bc], 1u);
-                        objw += (long long)rint((double)d_r * scale_t);
-                    }
-                    assign[row] = a_r;
-                    dist[row] = d_r;
-                }
-                bkey = -INFINITY;
-                bc = 0;
-            }
-        }
+        if (kt == KT - 1) epi.tile(acc, ct, rt * MF_BN + jr, fh);
         if (it + 1 < n_it) {
             KM_SSTORE(cur ^ 1)
         }
@@ -204,12 +159,92 @@ __global__ __launch_bounds__(256, 2) void k_kmeans_assign(const float* __restric
     }
 #undef KM_GLOAD
 #undef KM_SSTORE
+    return true;
+}
+
+// The epilogue of k_kmeans_assign: the running argmax of this lane's row over the table tiles, and at the last tile
+// the row's assignment, distance, LDS member count and objective term.
+struct KmAssignEpi {
+    const float* __restrict__ xnorm2;
+    const float* __restrict__ cn2;
+    int nc, nctiles;
+    int64_t ntotal;
+    const uint32_t* __restrict__ mask;
+    double scale_t;
+    int32_t* __restrict__ assign;
+    float* __restrict__ dist;
+    float* cn2s;
+    unsigned int* cnt;
+    float bkey;
+    int bc;
+    long long objw;
+    __device__ __forceinline__ void init(float* lds, int tid) {
+        cn2s = lds;
+        cnt = reinterpret_cast<unsigned int*>(cn2s + nctiles * MF_BM);
+        for (int i = tid; i < nctiles * MF_BM; i += 256) cn2s[i] = cn2[i];
+        for (int i = tid; i < nc; i += 256) cnt[i] = 0u;
+    }
+    __device__ __forceinline__ void tile(f32x16 (&acc)[4], int ct, int64_t row, int fh) {
+        // ---------------- the 64 keys of this lane's row against centroid tile ct, ascending centroid number
+        const int cbase = ct * MF_BM;
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int c = cbase + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const float key = fmaf(-0.5f, cn2s[c], acc[m][r]);
+                if (key > bkey) {
+                    bkey = key;
+                    bc = c;
+                }
+                acc[m][r] = 0.f;
+            }
+        if (ct != nctiles - 1) return;
+        // ---------------- the row is done: the two lane halves meet, lane fr of half 0 writes it
+        const float okey = __shfl_xor(bkey, 32);
+        const int oc = __shfl_xor(bc, 32);
+        if (okey > bkey || (okey == bkey && oc < bc)) {
+            bkey = okey;
+            bc = oc;
+        }
+        if (fh == 0 && row < ntotal) {
+            const bool ok = mask == nullptr || ((mask[row >> 5] >> (row & 31)) & 1u);
+            int a_r = -1;
+            float d_r = 0.f;
+            if (ok) {
+                a_r = bc;
+                d_r = fmaxf(0.f, fmaf(-2.f, bkey, xnorm2[row]));
+                atomicAdd(&cnt[bc], 1u);
+                objw += (long long)rint((double)d_r * scale_t);
+            }
+            assign[row] = a_r;
+            dist[row] = d_r;
+        }
+        bkey = -INFINITY;
+        bc = 0;
+    }
+};
+
+// LDS: As [2][128][32] centroids | Bs [2][128][32] rows | cn2s [ncpad] | cnt [nc]
+__global__ __launch_bounds__(256, 2) void k_kmeans_assign(const float* __restrict__ xb, const float* __restrict__ xnorm2,
+                                                          const float* __restrict__ ctab, const float* __restrict__ cn2,
+                                                          int nc, int nctiles, int64_t ntotal, int dpad,
+                                                          int64_t tiles_per_block, const uint32_t* __restrict__ mask,
+                                                          const long long* __restrict__ hdr, int32_t* __restrict__ assign,
+                                                          float* __restrict__ dist, unsigned long long* __restrict__ counts,
+                                                          unsigned long long* __restrict__ obj) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    KmAssignEpi epi{xnorm2, cn2, nc, nctiles, ntotal, mask, __longlong_as_double(hdr[6]), assign, dist,
+                    nullptr, nullptr, -INFINITY, 0, 0};
+    if (!km_sweep(xb, ctab, nctiles, ntotal, dpad, tiles_per_block, smem, epi)) return;
+    long long objw = epi.objw;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) objw += __shfl_xor(objw, off);
     if (lane == 0 && objw != 0) atomicAdd(obj, (unsigned long long)objw);
     // (the barrier that closed the last K-step is behind every LDS count)
     for (int i = tid; i < nc; i += 256)
-        if (cnt[i]) atomicAdd(counts + i, (unsigned long long)cnt[i]);
+        if (epi.cnt[i]) atomicAdd(counts + i, (unsigned long long)epi.cnt[i]);
 }
 
 // One block: counts -> exclusive offsets off[0..nc] into the member lists and seg[0..nc], the exclusive prefix of

@@ -454,6 +454,115 @@ def kmeans_train_mask(allowed_rows: np.ndarray, ntotal: int, nc: int, max_points
     return mask
 
 
+MAX_TRANSFORM_ROWS = nat.MAX_TRANSFORM_ROWS
+
+
+class GramResult(NamedTuple):
+    """What ``css_index_gram`` returns: ``gram[i, j] = sum_r q_r[i] q_r[j]`` (int64 ``[d, d]``, symmetric) and
+    ``colsum[j] = sum_r q_r[j]`` (int64 ``[d]``) over the allowed rows with ``q = llrint(x * 2^shift)``, the number of
+    allowed rows, and the shift ``p``."""
+    gram: np.ndarray
+    colsum: np.ndarray
+    count: int
+    shift: int
+
+
+class PcaResult(NamedTuple):
+    """What ``pca_from_gram`` returns: the mean ``[d]`` float32, the components ``[m, d]`` float32 (rows; scaled by
+    ``1 / sqrt(eigenvalue)`` under ``whiten``), their eigenvalues (float64, descending, clipped at 0), the trace of the
+    covariance, the number of rows and the shift of the integers it was formed from."""
+    mean: np.ndarray
+    components: np.ndarray
+    eigenvalues: np.ndarray
+    total_variance: float
+    count: int
+    shift: int
+
+
+def pca_shift(max_norm2: float, n: int) -> Tuple[int, int]:
+    """The shift rule of ``css_index_gram``, restated: ``(p, e)``.  ``ex``, ``e`` and ``b`` are those of ``kmeans_shift``
+    (``|x| < 2^e`` for every entry, ``b`` the bit length of ``max(n, 1) - 1``); ``p = min(20, (62 - b) >> 1) - e``.  So
+    ``|q| <= 2^(p + e) <= 2^20``, a product is at most ``2^40`` -- 8192 of them sum exactly in float64 -- and
+    ``n * 2^(2 (p + e)) <= 2^62``: no int64 sum can reach ``2^63``."""
+    m = float(np.float32(max_norm2))
+    ex = math.frexp(m)[1] if m > 0.0 else 0
+    e = -((-ex) // 2)
+    b = (max(int(n), 1) - 1).bit_length()
+    return min(20, (62 - b) >> 1) - e, e
+
+
+def fixed_point_gram(X, allow, p: int) -> Tuple[np.ndarray, np.ndarray, int]:
+    """``css_index_gram`` stated in numpy: ``(gram int64 [d, d], colsum int64 [d], count)`` of the allowed rows of ``X``
+    (``allow`` a boolean mask or ``None``) under ``q = llrint(X * 2^p)``.  Exact int64 (which wraps silently: the
+    caller keeps to ``pca_shift``).  Not by the kernel's argument: ``q`` is split into ``hi * 2^13 + lo`` with
+    ``0 <= lo < 2^13``, so for ``|q| < 2^26`` the limb products stay below ``2^26`` and their sums over 4096 rows below
+    ``2^38`` -- far inside what float64 holds exactly -- and three BLAS products per chunk give the integers; longer
+    ``q`` go through numpy's (slow) integer matmul."""
+    X = np.asarray(X, dtype=np.float32)
+    X = X.reshape(-1, X.shape[-1] if X.ndim else 0)
+    if allow is not None:
+        X = X[np.asarray(allow, dtype=bool)]
+    d = X.shape[1]
+    gram, colsum = np.zeros((d, d), dtype=np.int64), np.zeros(d, dtype=np.int64)
+    for at in range(0, X.shape[0], 4096):
+        q = _fixed(X[at:at + 4096], p)
+        colsum += q.sum(axis=0, dtype=np.int64)
+        if int(np.abs(q).max()) >= 1 << 26:
+            gram += q.T @ q
+            continue
+        hi = q >> 13                                             # (floor: lo is never negative)
+        H, L = hi.astype(np.float64), (q - (hi << 13)).astype(np.float64)
+        HL = H.T @ L
+        gram += ((H.T @ H).astype(np.int64) << 26) + ((HL + HL.T).astype(np.int64) << 13) + (L.T @ L).astype(np.int64)
+    return gram, colsum, int(X.shape[0])
+
+
+def pca_from_gram(gram, colsum, count: int, p: int, n_components: int, whiten: bool = False) -> PcaResult:
+    """Mean, principal components and eigenvalues from the integers of ``css_index_gram`` (the single index, the
+    sharded index and the CPU doubles all run this one, so the same integers give the same bytes).  In float64: the
+    BIASED covariance ``C = (G - outer(s, s) / count) / count * 2^(-2p)``, ``numpy.linalg.eigh``, eigenvalues descending
+    and clipped at 0, each component's sign chosen so that its entry of largest magnitude is positive (ties to the
+    lowest index); ``whiten`` scales component ``i`` by ``1 / sqrt(max(eigenvalue_i, tiny))`` (``tiny`` the smallest normal float32, so
+    the result stays finite in float32); ONE rounding to float32.
+    ``count == 0`` raises ``ValueError``."""
+    G = np.asarray(gram, dtype=np.int64)
+    s = np.asarray(colsum, dtype=np.int64).astype(np.float64)
+    d = G.shape[0]
+    m, count = int(n_components), int(count)
+    if count <= 0:
+        raise ValueError("pca: no rows")
+    if m < 1 or m > d:
+        raise ValueError(f"pca: n_components={m} outside [1, {d}]")
+    C = np.ldexp((G.astype(np.float64) - np.outer(s, s) / count) / count, -2 * int(p))
+    w, V = np.linalg.eigh(C)
+    order = np.argsort(-w, kind="stable")[:m]
+    w, V = np.maximum(w[order], 0.0), V[:, order].T.copy()
+    lead = np.abs(V).argmax(axis=1)                      # (the first maximum: the lowest index)
+    V[V[np.arange(m), lead] < 0] *= -1.0
+    if whiten:
+        V /= np.sqrt(np.maximum(w, np.finfo(np.float32).tiny))[:, None]
+    mean = np.ldexp(s / count, -int(p))
+    return PcaResult(mean.astype(np.float32), np.ascontiguousarray(V, dtype=np.float32), w, float(np.trace(C)), count, int(p))
+
+
+def pca_offset(components, mean) -> np.ndarray:
+    """``b = -A mean`` of the transform ``y = A x + b`` that centres the rows: formed in float64, ONE rounding to float32."""
+    return (-(np.asarray(components, dtype=np.float32).astype(np.float64) @ np.asarray(mean, dtype=np.float32).astype(np.float64))).astype(np.float32)
+
+
+def transform_args(A, b, d: int, what: str = "transform") -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """``A`` as float32 ``[m, d]`` with ``1 <= m <= 256`` and ``b`` as float32 ``[m]`` (or ``None``), or ``ValueError``."""
+    A = _as_f32_2d(A, d, what)
+    m = A.shape[0]
+    if m < 1 or m > MAX_TRANSFORM_ROWS:
+        raise ValueError(f"{what}: m={m} outside [1, {MAX_TRANSFORM_ROWS}]")
+    if b is not None:
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        if b.shape[0] != m:
+            raise ValueError(f"{what}: b must have {m} entries, got {b.shape[0]}")
+    return A, b
+
+
 class IndexFlat:
     """Exact brute-force index in HBM (``faiss.IndexFlat`` semantics)."""
 
@@ -954,6 +1063,40 @@ class IndexFlat:
                           seed=seed, init=init, spherical=sph, init_rows=rows, train_allow=allow if train is None else train,
                           allow=allow)
 
+    # -- PCA -------------------------------------------------------------------
+    def gram(self, allow=None, fx_shift: Optional[int] = None) -> GramResult:
+        """The fixed-point Gram matrix and column sums of the allowed rows on the GPU (``css_index_gram``);
+        ``fixed_point_gram`` and ``pca_shift`` state the integers exactly.  ``fx_shift`` imposes the shift (the sharded
+        index passes the global one)."""
+        h = self._handle()
+        gram, colsum = np.zeros((self.d, self.d), dtype=np.int64), np.zeros(self.d, dtype=np.int64)
+        count = np.zeros(1, dtype=np.int64)
+        p = ctypes.c_int(0)
+        bits, bits_ptr = self._allow_bits(allow)
+        nat.check(nat.lib().css_index_gram(h, -1 if fx_shift is None else int(fx_shift), bits_ptr, gram.ctypes.data,
+                                           colsum.ctypes.data, count.ctypes.data, ctypes.byref(p)))
+        return GramResult(gram, colsum, int(count[0]), int(p.value))
+
+    def set_gram_rows(self, rows: int) -> None:
+        """Rows per block of the Gram kernel (0 = the library's rule); the integers of ``gram`` do not depend on it."""
+        nat.check(nat.lib().css_index_set_gram_rows(self._handle(), int(rows)))
+
+    def pca(self, n_components: int, allow=None, whiten: bool = False) -> PcaResult:
+        """PCA of the allowed stored rows: one ``gram`` on the GPU, ``pca_from_gram`` on the host."""
+        g = self.gram(allow=allow)
+        return pca_from_gram(g.gram, g.colsum, g.count, g.shift, n_components, whiten=whiten)
+
+    def transform(self, A, b=None, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """``y = A x + b`` for the stored rows ``[row0, row0 + n)`` on the GPU (``css_index_transform``): ``A`` is
+        ``[m, d]`` with ``m <= 256``, ``b`` ``[m]`` or ``None``; float32 ``[n, m]`` comes back.  fp32 products and
+        accumulation; tombstoned rows are transformed like any other."""
+        A, b = transform_args(A, b, self.d)
+        row0, n = self._row_range("transform", row0, n)
+        out = np.empty((n, A.shape[0]), dtype=np.float32)
+        nat.check(nat.lib().css_index_transform(self._handle(), A.ctypes.data, None if b is None else b.ctypes.data,
+                                                A.shape[0], row0, n, out.ctypes.data if n else None))
+        return out
+
 
 class IndexFlatIP(IndexFlat):
     def __init__(self, d: int, device: int = 0):
@@ -997,6 +1140,64 @@ class Kmeans:
             raise RuntimeError("Kmeans.assign: train() first")
         D, I = self.index.search(_as_f32_2d(x, self.d, "Kmeans.assign"), 1)
         return D[:, 0], I[:, 0]
+
+
+class PCAMatrix:
+    """``faiss.PCAMatrix`` over the GPU primitives: ``train(x)`` puts ``x`` into a temporary ``IndexFlatL2`` and runs
+    ``pca``; afterwards ``A`` is ``[d_out, d_in]`` float32, ``b = -A mean`` (formed in float64, one rounding), ``mean``
+    and ``eigenvalues`` as ``pca_from_gram`` gives them.  ``eigen_power`` is 0 or -0.5 (whitening).  ``apply(x)`` is
+    ``x A^T + b`` through a temporary index (``transform``); ``reverse_transform(y)`` runs on the host."""
+
+    def __init__(self, d_in: int, d_out: int, eigen_power: float = 0.0, device: int = 0):
+        self.d_in, self.d_out, self.device = int(d_in), int(d_out), int(device)
+        if float(eigen_power) not in (0.0, -0.5):
+            raise ValueError(f"PCAMatrix: eigen_power={eigen_power} is neither 0 nor -0.5")
+        if self.d_out < 1 or self.d_out > min(self.d_in, MAX_TRANSFORM_ROWS):
+            raise ValueError(f"PCAMatrix: d_out={d_out} outside [1, {min(self.d_in, MAX_TRANSFORM_ROWS)}]")
+        self.eigen_power = float(eigen_power)
+        self.is_trained = False
+        self.A: Optional[np.ndarray] = None
+        self.b: Optional[np.ndarray] = None
+        self.mean: Optional[np.ndarray] = None
+        self.eigenvalues: Optional[np.ndarray] = None
+
+    def set_result(self, res: PcaResult) -> None:
+        self.A, self.mean, self.eigenvalues = res.components, res.mean, res.eigenvalues
+        self.b = pca_offset(self.A, self.mean)
+        self.is_trained = True
+
+    def train(self, x) -> None:
+        a = _as_f32_2d(x, self.d_in, "PCAMatrix.train")
+        tmp = IndexFlatL2(self.d_in, self.device)
+        try:
+            tmp.add(a)
+            self.set_result(tmp.pca(self.d_out, whiten=self.eigen_power != 0.0))
+        finally:
+            tmp.close()
+
+    def apply(self, x) -> np.ndarray:
+        if not self.is_trained:
+            raise RuntimeError("PCAMatrix.apply: train() first")
+        a = _as_f32_2d(x, self.d_in, "PCAMatrix.apply")
+        tmp = IndexFlatL2(self.d_in, self.device)
+        try:
+            tmp.add(a)
+            return tmp.transform(self.A, self.b)
+        finally:
+            tmp.close()
+
+    apply_py = apply
+
+    def reverse_transform(self, y) -> np.ndarray:
+        """The rows whose transform is ``y``, up to the discarded components: ``mean + y W`` with ``W`` the components
+        (a whitened matrix first takes its scaling back), in float64, one rounding."""
+        if not self.is_trained:
+            raise RuntimeError("PCAMatrix.reverse_transform: train() first")
+        y = _as_f32_2d(y, self.d_out, "PCAMatrix.reverse_transform").astype(np.float64)
+        W = self.A.astype(np.float64)
+        if self.eigen_power != 0.0:
+            W = W * np.maximum(self.eigenvalues, np.finfo(np.float32).tiny)[:, None]
+        return (self.mean.astype(np.float64) + y @ W).astype(np.float32)
 
 
 # ---------------------------------------------------------------------------

@@ -674,6 +674,51 @@ class ShardedFlatIndex:
         return run_kmeans(step, self.reconstruct_batch, nc, niter=niter, seed=seed, init=init, spherical=sph,
                           init_rows=rows, train_allow=train, allow=None)
 
+    # -- PCA ---------------------------------------------------------------------------------------------------------
+    def gram(self, allow=None, fx_shift: Optional[int] = None):
+        """``IndexFlat.gram`` over the shards (collective; ``allow`` is a mask over the GLOBAL rows, tombstones are left
+        out): the local Gram matrix under the GLOBAL shift (row counts summed, largest norms reduced with max) and ONE
+        sum all-reduce of matrix, column sums and count -- exact integers, bit-identical to one index over the rows.
+        One index accepts rows longer than 2^20 (its own shift is then negative); the shards cannot, because
+        ``css_index_gram`` reads a negative ``fx_shift`` as "choose": a negative global shift raises ``ValueError``."""
+        from .flat_index import GramResult, pca_shift
+
+        n = self.ntotal_global
+        local_max = float(self.local.bounds()["max_norm2"]) if self.local.ntotal else 0.0
+        max_norm2 = local_max if self.world == 1 else float(self._all_gather_host(np.array([local_max], dtype=np.float64)).max())
+        p = pca_shift(max_norm2, n)[0] if fx_shift is None else int(fx_shift)
+        if p < 0:
+            raise ValueError(f"gram: rows too long for the fixed-point sums (shift {p})")
+        g = self.local.gram(allow=self._local_allow(allow), fx_shift=p)
+        flat = np.concatenate([g.gram.reshape(-1), g.colsum, np.array([g.count], dtype=np.int64)])
+        flat = self._sum_over_ranks(np.ascontiguousarray(flat, dtype=np.int64))
+        m = g.gram.size
+        return GramResult(flat[:m].reshape(g.gram.shape), flat[m:m + g.colsum.size], int(flat[-1]), p)
+
+    def pca(self, n_components: int, allow=None, whiten: bool = False):
+        """``IndexFlat.pca`` over the shards: ``gram`` and ``flat_index.pca_from_gram``, the same bytes on every rank."""
+        from .flat_index import pca_from_gram
+
+        g = self.gram(allow=allow)
+        return pca_from_gram(g.gram, g.colsum, g.count, g.shift, n_components, whiten=whiten)
+
+    def transform(self, A, b=None, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """``IndexFlat.transform`` of the GLOBAL rows ``[row0, row0 + n)`` on every rank (collective), following
+        ``reconstruct_n``: every shard transforms the rows it owns and ONE sum all-reduce of the zero-filled blocks
+        completes them (exact: one non-zero contribution per row)."""
+        from .flat_index import transform_args
+
+        A, b = transform_args(A, b, self.d)
+        row0 = int(row0)
+        n = self.ntotal_global - row0 if n is None else int(n)
+        if n < 0:
+            raise ValueError(f"transform: n={n} is negative")
+        self._check_rows("transform", row0, n)
+        out = np.zeros((n, A.shape[0]), dtype=np.float32)
+        for l0, g0, m in self._overlaps(row0, n):
+            out[g0 - row0:g0 - row0 + m] = self.local.transform(A, b, l0, m)
+        return self._sum_over_ranks(out)
+
     def add_file_rows(self, path: str, offset: int, n: int, normalize: bool = False, chunk_rows: int = 1 << 18) -> None:
         """``add_global`` of ``n`` fp32 rows stored row-major at byte ``offset`` of ``path`` (the payload of an index
         file): every rank reads only its own block (collective call, no communication)."""
@@ -778,6 +823,15 @@ class ShardedIndexFacade:
             d[g0:g0 + n] = res.dist[l0:l0 + n]
         a, d = self.sh._sum_over_ranks(a), self.sh._sum_over_ranks(d)
         return res._replace(assign=(a - 1).astype(np.int32), dist=d)
+
+    def gram(self, allow=None, fx_shift: Optional[int] = None):
+        return self.sh.gram(allow=allow, fx_shift=fx_shift)
+
+    def pca(self, n_components: int, allow=None, whiten: bool = False):
+        return self.sh.pca(int(n_components), allow=allow, whiten=whiten)
+
+    def transform(self, A, b=None, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        return self.sh.transform(A, b, row0=row0, n=n)
 
     def mark_deleted(self, ids) -> None:
         self.sh.mark_deleted(ids)

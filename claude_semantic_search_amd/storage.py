@@ -101,6 +101,16 @@ class Topic:
     chunk_ids: List[str]
 
 
+@dataclass
+class MapPoint:
+    """One chunk of ``HybridStorage.map``: its coordinates on the first two principal components of the selection, and
+    its k-means topic under the same selection (``None`` when no topics were asked for)."""
+    chunk_id: str
+    x: float
+    y: float
+    topic: Optional[int] = None
+
+
 _CHUNK_COLUMNS = (
     "id", "text", "metadata", "faiss_id", "session_id", "project_name", "file_path", "chunk_type",
     "timestamp", "has_code", "has_tools", "message_count", "char_count", "word_count", "updated_at",
@@ -773,6 +783,52 @@ class HybridStorage:
                 chunk_ids = [self.faiss_id_to_chunk_id[int(f)] for f in members if int(f) in self.faiss_id_to_chunk_id]
                 out.append(Topic(size=int(members.size), representative=near[0], examples=near, chunk_ids=chunk_ids))
             out.sort(key=lambda t: -t.size)   # (stable: equal sizes stay in centroid order)
+            return out
+
+    def map(self, filters: Optional[Dict[str, Any]] = None, n_topics: int = 0, seed: int = 0,
+            niter: int = 20) -> List[MapPoint]:
+        """A 2-D map of the live chunks that match ``filters``: each chunk at its coordinates on the first two principal
+        components of the selection, computed on the GPU (one ``IndexFlat.pca(2, allow=mask)``, then ``transform`` over
+        the rows in ranges of at most 2^20, of which the allowed rows are kept).  Tombstones are always left out.
+        ``n_topics >= 2`` adds as ``topic`` the ``kmeans`` assignment under the same mask, ``seed`` and ``niter``: the
+        clusters of ``topics`` called with the same ``n_topics``, ``filters``, ``seed`` and ``niter``; else ``topic`` is
+        ``None``.  An empty selection gives ``[]``; a single chunk lies at ``(0, 0)``; an
+        index object without ``pca`` raises ``NotImplementedError``."""
+        with self._lock:
+            frame = self._search_frame(SearchConfig())
+            if frame is None:
+                return []
+            _, ntotal, _ = frame
+            if not (hasattr(self.faiss_index, "pca") and hasattr(self.faiss_index, "transform")):
+                raise NotImplementedError(f"{type(self.faiss_index).__name__} has no PCA (pca / transform)")
+            allow = self._allow_mask(filters or {}, ntotal)
+            rows = np.flatnonzero(allow)
+            if rows.size == 0:
+                return []
+            topic = None
+            if n_topics >= 2:
+                nc = min(int(n_topics), int(rows.size), fi.MAX_CENTROIDS)
+                if nc >= 2:
+                    topic = np.asarray(self.faiss_index.kmeans(nc, niter=niter, seed=seed, allow=allow).assign)[rows]
+                else:
+                    topic = np.zeros(rows.size, dtype=np.int64)
+            xy = np.zeros((rows.size, 2), dtype=np.float32)
+            if rows.size > 1:
+                res = self.faiss_index.pca(2, allow=allow)
+                b = fi.pca_offset(res.components, res.mean)
+                step = 1 << 20
+                for lo in range(0, ntotal, step):
+                    n = min(step, ntotal - lo)
+                    keep = allow[lo:lo + n]
+                    if keep.any():
+                        at = np.searchsorted(rows, lo)
+                        part = self.faiss_index.transform(res.components, b, lo, n)[keep]
+                        xy[at:at + part.shape[0]] = part
+            out: List[MapPoint] = []
+            for j, f in enumerate(rows.tolist()):
+                cid = self.faiss_id_to_chunk_id.get(f)
+                if cid is not None:
+                    out.append(MapPoint(cid, float(xy[j, 0]), float(xy[j, 1]), None if topic is None else int(topic[j])))
             return out
 
     def _sync_terms(self, ntotal: int) -> None:

@@ -439,6 +439,55 @@ int css_index_kmeans_step(css_index* ix, const float* centroids_host /* [nc, dim
                           int32_t* assign_host /* [ntotal], may be NULL */,
                           float* dist_host /* [ntotal], may be NULL */);
 
+/* The second-moment (Gram) matrix X^T X of the stored rows with their column sums, in fixed point, on the device: the
+ * reduction PCA needs (flat_index.pca_from_gram turns it into mean, covariance and components on the host), without
+ * the rows leaving HBM.  k-means' sibling: one deterministic primitive here, the eigen-solve and the policy in Python.
+ *  - Quantisation.  For every allowed row r (allow_bits_host as in css_index_search_masked; NULL: every row)
+ *    q_r[j] = llrint((double)x_r[j] * 2^p): an exact float64 scaling, then round to nearest even.
+ *  - Outputs.  gram[i][j] = sum over r of q_r[i] * q_r[j] (the full symmetric [dim, dim] matrix; pad columns never
+ *    appear), colsum[j] = sum over r of q_r[j], count = the number of allowed rows.  They are exact integers: the same
+ *    bytes on every run and for any grid shape, and shards that use one p add up to the unsharded values.
+ *  - The shift rule (flat_index.pca_shift restates it).  ex, e and b exactly as in css_index_kmeans_step: ex = frexp
+ *    exponent of the running maximum of ||row||^2 (0 when that is 0), e = ceil(ex / 2) so that every |x| < 2^e,
+ *    b = bit_length(max(ntotal, 1) - 1).  p = min(20, (62 - b) >> 1) - e.  Hence |q| <= 2^(p + e) <= 2^20, a product is
+ *    at most 2^40 and ntotal * 2^(2 (p + e)) <= 2^62: no sum reaches 2^63.  b uses ntotal, not the allowed count, so the
+ *    rule does not depend on the mask.  Unit rows have e = 1: up to 2^22 of them give p = 19, 10 M give p = 18.
+ *  - fx_shift < 0: the library chooses p by the rule.  fx_shift >= 0 imposes p (a sharded index passes the p of the
+ *    global row count and the global maximum); a value above what this index's own ntotal and maximum can hold is
+ *    CSS_ERR_INVALID and the message names the largest safe value.  *fx_shift_used = p (may be NULL).  The rule is
+ *    evaluated on the device; the call waits for the device once.  The rule's own p is negative for rows longer
+ *    than 2^20; a NEGATIVE p cannot be imposed (the sign means "choose"), so shards of such rows cannot be combined.
+ *  - An empty index, or a mask that allows nothing, gives zeros.  Rows are assumed finite: what a NaN or infinite row
+ *    does to the result is NOT defined (nothing is read or written out of bounds).
+ *  - Locking, the ordering behind asynchronous adds and the call frame are those of css_index_kmeans_step.  The
+ *    workspace belongs to the index, grows on demand and outlives css_index_add, css_index_remove_rows and
+ *    css_index_reset.
+ *  - On the device: the fp64 matrix core (v_mfma_f64_16x16x4_f64) with the rows as the K dimension, one 128 x 128 tile
+ *    of the upper triangle and one strip of rows per block.  |q| <= 2^20 makes a partial sum over at most 8192 rows an
+ *    integer of at most 2^53, which fp64 accumulates exactly in any order; every 8192 rows the accumulators are folded
+ *    into int64 registers, and a block flushes once with 64-bit integer atomics.  No float atomics. */
+/* Rows per block of the Gram kernel (0 = the library's rule: about four blocks per CU, at least 512 rows).  A
+ * verification knob like css_index_set_range_rows: the integers of css_index_gram do not depend on it.  Values above
+ * 8192 make a block fold its fp64 accumulators into int64 more than once. */
+int css_index_set_gram_rows(css_index* ix, int64_t rows);
+int css_index_gram(css_index* ix, int fx_shift /* < 0: chosen by the library */, const uint32_t* allow_bits_host,
+                   int64_t* gram_host /* [dim, dim] */, int64_t* colsum_host /* [dim] */, int64_t* count_host /* [1] */,
+                   int* fx_shift_used);
+
+/* A linear transform of stored rows (faiss' LinearTransform / PCAMatrix apply, a 2-D map, a reduced copy, whitening):
+ * y[r][c] = (sum over j of x_r[j] * A[c][j]) + b[c] for the rows r in [row0, row0 + n), LOCAL row numbering, range-checked
+ * like css_index_export; n == 0 is a no-op.  1 <= m <= CSS_MAX_TRANSFORM_ROWS, anything else is CSS_ERR_INVALID.  A
+ * non-finite entry of A or b is CSS_ERR_INVALID: the message names it and nothing is enqueued.  b_host NULL means b = 0.
+ *  - Products and accumulation run in fp32 on the fp32-input matrix core (v_mfma_f32_32x32x2_f32) over the padded row,
+ *    as css_index_kmeans_step forms its scores, with A in the place of the centroid table; b[c] is added once, in
+ *    fp32.  No reduced-precision copy of the rows takes part, and the search mode plays none.
+ *  - Tombstoned rows are transformed like any other: the caller selects.
+ *  - Locking, the ordering behind asynchronous adds and the call frame are those of css_index_kmeans_step; the call
+ *    waits for the device once.  Results come back in batches of rows through a workspace of the index. */
+#define CSS_MAX_TRANSFORM_ROWS 256
+int css_index_transform(css_index* ix, const float* A_host /* [m, dim] */, const float* b_host /* [m] or NULL */, int m,
+                        int64_t row0, int64_t n, float* y_out_host /* [n, m] */);
+
 /* Diversified search (maximal marginal relevance, MMR; langchain's max_marginal_relevance_search, the "diversity"
  * option of vector stores): k rows picked greedily from a pool of the best rows, each pick trading its score against
  * its similarity to the rows already picked -- so near-copies of one passage do not fill the answer.  Per query, with
