@@ -21,6 +21,7 @@ _LAZY = {
     "recency_priors": ".storage",
     "Topic": ".storage",
     "MapPoint": ".storage",
+    "Keyword": ".storage",
     "EmbeddingConfig": ".embeddings",
     "EmbeddingStats": ".embeddings",
     "EmbeddingGenerator": ".embeddings",
@@ -38,6 +39,10 @@ _LAZY = {
     "pca_from_gram": ".flat_index",
     "terms_of": ".lexical",
     "bm25_weights": ".lexical",
+    "jlh": ".lexical",
+    "significant_from_counts": ".lexical",
+    "SignificantTerms": ".lexical",
+    "words_of_terms": ".lexical",
     "MpnetEncoder": ".mpnet_encoder",
     "ShardedFlatIndex": ".sharded",
     "GPUCapability": ".gpu_utils",

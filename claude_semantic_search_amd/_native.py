@@ -31,6 +31,7 @@ MAX_PRIOR_K = 128   # css_index_search_prior: the same list size
 MAX_HYBRID_K = 128   # css_index_search_hybrid: the same list size
 MAX_QUERY_TERMS = 32   # include/css_hip.h CSS_MAX_QUERY_TERMS
 TERM_SPACE = 1 << 24   # include/css_hip.h CSS_TERM_SPACE
+MAX_SIG_TERMS = 256   # include/css_hip.h CSS_MAX_SIG_TERMS
 MAX_EXAMPLES = 16   # include/css_hip.h CSS_MAX_EXAMPLES
 MAX_EXAMPLES_K = 128   # css_index_search_examples: the same list size
 MAX_CENTROIDS = 4096   # include/css_hip.h CSS_MAX_CENTROIDS
@@ -134,6 +135,10 @@ PROTOTYPES = {
     "css_index_set_terms": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "css_index_get_terms": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "css_index_term_stats": (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    "css_index_set_sigterm_slots": (c_int, [c_void_p, c_int]),
+    "css_index_subset_terms": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    "css_index_significant_terms": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, POINTER(c_int), POINTER(c_int64), POINTER(c_int64)]),
     "css_index_search_hybrid": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_float, c_float,
                                         c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "css_index_search_diverse": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_void_p,

@@ -43,6 +43,9 @@
 //   k_transform_rows   css_index_transform: y = A x + b over stored rows, the K loop of k_kmeans_assign (css_pca.h)
 //   k_lex_scores       css_index_search_hybrid: the BM25 column of one query over the per-row term lists, handed to
 //                      k_scan_prior in the place of the priors (css_lexical.h).   HBM bound
+//   k_sig_count        css_index_subset_terms / _significant_terms: +1 per list entry of the selected rows into a
+//                      uint32 table [2^24], repeats merged in a per-block LDS table first; k_sig_score and the radix
+//                      select rank the terms (css_sigterms.h)
 //   k_mmr_select       css_index_search_diverse: k of a pool of the best rows picked greedily by maximal marginal
 //                      relevance, similarities from the stored fp32 rows (css_knn_diverse.h)
 //
@@ -240,6 +243,13 @@ struct css_index {
     DevBuf<long long> gr_out;
     int64_t gram_rows = 0;   // css_index_set_gram_rows: rows per block of k_gram_fx (0: the rule of gram_enqueue)
     DevBuf<float> tr_raw, tr_tab, tr_y;
+    // css_index_subset_terms / css_index_significant_terms (css_sigterms.h): the count tables [CSS_TERM_SPACE] of the
+    // selection and of a background mask (64 MB each, allocated on first use; workspaces, not index state), the device
+    // copy of the background bitmap, the candidate list (score bits, term) of the select -- also the (term, count)
+    // pairs of the compaction --, the SigState and the packed results
+    DevBuf<uint32_t> sig_fg, sig_bg, sig_mask2, sig_term, sig_cnt;
+    DevBuf<unsigned long long> sig_key, sig_st, sig_out;
+    int sig_slots = -1;   // css_index_set_sigterm_slots: LDS slots per block of k_sig_count (-1: the library's rule)
     // rows written by css_index_add_dev / _add_synthetic on the CALLER's stream: searches, reallocation and
     // export wait for this event before touching rows, norms or maxn2
     hipEvent_t ingest_ev = nullptr;
@@ -2744,6 +2754,7 @@ int range_pool_alloc(css_index* ix, size_t cap) {
 // ------------------------------------------------------------------ prior-weighted search (css_knn_prior.h)
 #include "css_knn_prior.h"
 #include "css_lexical.h"
+#include "css_sigterms.h"
 
 // HASP: the index has a prior column (false: every prior is 0, the kernel loads none)
 template <int NQ, int TT, int METRIC, bool HASP>
@@ -3527,6 +3538,15 @@ int css_index_set_gram_rows(css_index* ix, int64_t rows) {
     CSS_REQUIRE(rows >= 0, "css_index_set_gram_rows: rows < 0");
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     ix->gram_rows = rows;
+    return CSS_OK;
+}
+
+int css_index_set_sigterm_slots(css_index* ix, int slots) {
+    CSS_REQUIRE(ix, "css_index_set_sigterm_slots: NULL index");
+    CSS_REQUIRE(slots == -1 || slots == 0 || (slots >= 16 && slots <= kSigMaxSlots && (slots & (slots - 1)) == 0),
+                "css_index_set_sigterm_slots: slots=%d is not -1, 0 or a power of two in [16, %d]", slots, kSigMaxSlots);
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    ix->sig_slots = slots;
     return CSS_OK;
 }
 
@@ -4510,6 +4530,206 @@ int css_index_term_stats(css_index* ix, const uint32_t* terms_host, int m, int64
     CSS_HIP_TRY(hipStreamSynchronize(st));
     for (int j = 0; j < m; ++j) df_out[j] = out[(size_t)j];
     *total_len_out = out[(size_t)m];
+    return CSS_OK;
+}
+
+namespace {
+// word w of a host bitmap cut to the rows [0, T) (null: every row)
+inline uint32_t sig_word(const uint32_t* bits, int64_t w, int64_t T) {
+    uint32_t v = bits ? bits[w] : 0xFFFFFFFFu;
+    if ((w + 1) * 32 > T) v &= (uint32_t)((1ull << (T - w * 32)) - 1ull);
+    return v;
+}
+inline int64_t sig_popcount(const uint32_t* bits, int64_t T) {
+    if (!bits) return T;
+    int64_t n = 0;
+    for (int64_t w = 0, words = (T + 31) / 32; w < words; ++w) n += __builtin_popcount(sig_word(bits, w, T));
+    return n;
+}
+// the first row below T that `a` selects and `b` does not (-1: none)
+inline int64_t sig_first_outside(const uint32_t* a, const uint32_t* b, int64_t T) {
+    if (!b) return -1;
+    for (int64_t w = 0, words = (T + 31) / 32; w < words; ++w) {
+        const uint32_t bad = sig_word(a, w, T) & ~b[w];
+        if (bad) return w * 32 + __builtin_ctz(bad);
+    }
+    return -1;
+}
+
+// table[t] = the rows r < T with mask bit r (null: every row) whose list holds t.  Enqueued on `st`.
+int sig_count_enqueue(css_index* ix, const uint32_t* mask_dev, int64_t T, int64_t ntotal, uint32_t* table, hipStream_t st) {
+    {
+        ProfScope pz("sig_zero", st);
+        CSS_HIP_TRY(hipMemsetAsync(table, 0, (size_t)CSS_TERM_SPACE * sizeof(uint32_t), st));
+    }
+    const int slots = ix->sig_slots < 0 ? kSigMaxSlots : ix->sig_slots;
+    int shift = 32;
+    for (int s = slots; s > 1; s >>= 1) --shift;
+    // one block of 16 waves per CU that strides over the 1024-row groups: the fewer blocks, the more repeats one LDS
+    // table merges and the fewer adds the flushes send to the addresses of the frequent terms
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((T + 64 * kSigWaves - 1) / (64 * kSigWaves), (int64_t)ix->num_cus));
+    ProfScope ps("sig_count", st);
+    hipLaunchKernelGGL(k_sig_count, dim3((unsigned)blocks), dim3(64 * kSigWaves), (size_t)slots * 2 * sizeof(uint32_t), st,
+                       (const uint32_t*)ix->lex_ent.p, (const int64_t*)ix->lex_off.p, T, ntotal, mask_dev, slots, shift, table);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+int sig_state_reset(css_index* ix, hipStream_t st) {
+    const size_t words = (sizeof(SigState) + 7) / 8;
+    int rc;
+    if ((rc = ix->sig_st.grow_exact(words, "hipMalloc(significant terms)")) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemsetAsync(ix->sig_st.p, 0, words * 8, st));
+    return CSS_OK;
+}
+
+// css_index_subset_terms under the call's frame; T rows have lists and at least one of them is selected
+int subset_terms_locked(css_index* ix, HostCall& hc, const uint32_t* allow_bits_host, int64_t T, int64_t cap,
+                        uint32_t* terms_out, int64_t* fg_out, int64_t* n_out) {
+    const hipStream_t st = ix->stream;
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    if ((rc = ix->sig_fg.grow_exact((size_t)CSS_TERM_SPACE, "hipMalloc(significant terms)")) != CSS_OK) return rc;
+    hc.enqueued = true;
+    if ((rc = upload_allow_bits(ix, allow_bits_host, &hc.rows)) != CSS_OK) return rc;
+    if ((rc = sig_count_enqueue(ix, hc.rows.mask, T, hc.rows.n, ix->sig_fg.p, st)) != CSS_OK) return rc;
+    if ((rc = sig_state_reset(ix, st)) != CSS_OK) return rc;
+    SigState* ss = reinterpret_cast<SigState*>(ix->sig_st.p);
+    hipLaunchKernelGGL(k_sig_nz_count, dim3(kSigBlocks), dim3(256), 0, st, (const uint32_t*)ix->sig_fg.p, ss);
+    CSS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sig_nz_scan, dim3(1), dim3(256), 0, st, ss);
+    CSS_LAUNCH_CHECK();
+    uint32_t total = 0;
+    CSS_HIP_TRY(hipMemcpyAsync(&total, &ss->total, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    *n_out = (int64_t)total;
+    if (total == 0 || cap < (int64_t)total) return CSS_OK;   // (sizing call, or a buffer too small: nothing is written)
+    if ((rc = ix->sig_term.grow((size_t)total)) != CSS_OK) return rc;
+    if ((rc = ix->sig_cnt.grow((size_t)total)) != CSS_OK) return rc;
+    hipLaunchKernelGGL(k_sig_compact, dim3(kSigBlocks), dim3(256), 0, st, (const uint32_t*)ix->sig_fg.p, (const SigState*)ss, total,
+                       ix->sig_term.p, ix->sig_cnt.p);
+    CSS_LAUNCH_CHECK();
+    std::vector<uint32_t> cnt((size_t)total);
+    CSS_HIP_TRY(hipMemcpyAsync(terms_out, ix->sig_term.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipMemcpyAsync(cnt.data(), ix->sig_cnt.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < total; ++i) fg_out[i] = (int64_t)cnt[i];
+    return CSS_OK;
+}
+
+// css_index_significant_terms under the call's frame; FG >= 1 rows are selected, BG >= FG form the background
+int significant_terms_locked(css_index* ix, HostCall& hc, const uint32_t* allow_bits_host, const uint32_t* background_bits_host,
+                             int64_t T, int64_t FG, int64_t BG, int m, uint32_t min_count, unsigned long long* packed) {
+    const hipStream_t st = ix->stream;
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    if ((rc = ix->sig_fg.grow_exact((size_t)CSS_TERM_SPACE, "hipMalloc(significant terms)")) != CSS_OK) return rc;
+    const uint32_t* bg = ix->lex_df.p;   // no background mask: every row below T, which is what df counts
+    if (background_bits_host) {
+        const size_t words = (size_t)((hc.rows.n + 31) / 32);
+        if ((rc = ix->sig_bg.grow_exact((size_t)CSS_TERM_SPACE, "hipMalloc(significant terms)")) != CSS_OK) return rc;
+        if ((rc = ix->sig_mask2.grow(words)) != CSS_OK) return rc;
+        bg = ix->sig_bg.p;
+    }
+    // the candidates: at most one per distinct term of the lists
+    const uint32_t cap = (uint32_t)std::min<int64_t>((int64_t)CSS_TERM_SPACE, std::max<int64_t>(ix->lex_off_h[(size_t)T], 1));
+    if ((rc = ix->sig_key.grow((size_t)cap)) != CSS_OK) return rc;
+    if ((rc = ix->sig_term.grow((size_t)cap)) != CSS_OK) return rc;
+    constexpr size_t out_words = CSS_MAX_SIG_TERMS + 3 * CSS_MAX_SIG_TERMS / 2 + 1;
+    if ((rc = ix->sig_out.grow_exact(out_words, "hipMalloc(significant terms)")) != CSS_OK) return rc;
+    hc.enqueued = true;
+    if ((rc = upload_allow_bits(ix, allow_bits_host, &hc.rows)) != CSS_OK) return rc;
+    if ((rc = sig_count_enqueue(ix, hc.rows.mask, T, hc.rows.n, ix->sig_fg.p, st)) != CSS_OK) return rc;
+    if (background_bits_host) {
+        CSS_HIP_TRY(hipMemcpyAsync(ix->sig_mask2.p, background_bits_host, (size_t)((hc.rows.n + 31) / 32) * sizeof(uint32_t),
+                                   hipMemcpyHostToDevice, st));
+        if ((rc = sig_count_enqueue(ix, ix->sig_mask2.p, T, hc.rows.n, ix->sig_bg.p, st)) != CSS_OK) return rc;
+    }
+    if ((rc = sig_state_reset(ix, st)) != CSS_OK) return rc;
+    SigState* ss = reinterpret_cast<SigState*>(ix->sig_st.p);
+    const unsigned grid = (unsigned)std::max(1, ix->num_cus * 8);
+    {
+        ProfScope ps("sig_select", st);
+        hipLaunchKernelGGL(k_sig_score, dim3(grid), dim3(256), 0, st, (const uint32_t*)ix->sig_fg.p, bg, (unsigned long long)FG,
+                           (unsigned long long)BG, min_count, cap, ix->sig_key.p, ix->sig_term.p, ss);
+        CSS_LAUNCH_CHECK();
+        const unsigned sgrid = (unsigned)std::max(1, ix->num_cus * 2);
+        for (int d = 0; d < kSigDigits; ++d) {
+            hipLaunchKernelGGL(k_sig_hist, dim3(sgrid), dim3(256), 0, st, (const unsigned long long*)ix->sig_key.p,
+                               (const uint32_t*)ix->sig_term.p, cap, d, ss);
+            CSS_LAUNCH_CHECK();
+            hipLaunchKernelGGL(k_sig_pick, dim3(1), dim3(64), 0, st, d, (uint32_t)m, cap, ss);
+            CSS_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(k_sig_gather, dim3(sgrid), dim3(256), 0, st, (const unsigned long long*)ix->sig_key.p,
+                           (const uint32_t*)ix->sig_term.p, cap, ss);
+        CSS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_sig_final, dim3(1), dim3(CSS_MAX_SIG_TERMS), 0, st, (const uint32_t*)ix->sig_fg.p, bg, (const SigState*)ss,
+                           ix->sig_out.p);
+        CSS_LAUNCH_CHECK();
+    }
+    CSS_HIP_TRY(hipMemcpyAsync(packed, ix->sig_out.p, out_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));   // one wait
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_subset_terms(css_index* ix, const uint32_t* allow_bits_host, int64_t cap, uint32_t* terms_out, int64_t* fg_out,
+                           int64_t* n_out, int64_t* rows_out) {
+    CSS_REQUIRE(ix, "css_index_subset_terms: NULL index");
+    CSS_REQUIRE(n_out && rows_out, "css_index_subset_terms: NULL buffer");
+    CSS_REQUIRE(cap >= 0 && (cap == 0 || (terms_out && fg_out)), "css_index_subset_terms: cap=%lld without buffers", (long long)cap);
+    HostCall hc(ix, nullptr, false);
+    *n_out = 0;
+    *rows_out = 0;
+    const int64_t T = std::min(ix->lex_rows, hc.rows.n);
+    if (T == 0) return CSS_OK;
+    const int64_t FG = sig_popcount(allow_bits_host, T);
+    *rows_out = FG;
+    if (FG == 0) return CSS_OK;
+    return hc.wait_if_failed(subset_terms_locked(ix, hc, allow_bits_host, T, cap, terms_out, fg_out, n_out));
+}
+
+int css_index_significant_terms(css_index* ix, const uint32_t* allow_bits_host, const uint32_t* background_bits_host, int m,
+                                int64_t min_count, uint32_t* terms_out, int64_t* fg_out, int64_t* bg_out, double* score_out,
+                                int* n_out, int64_t* fg_rows_out, int64_t* bg_rows_out) {
+    CSS_REQUIRE(ix, "css_index_significant_terms: NULL index");
+    CSS_REQUIRE(m >= 1 && m <= CSS_MAX_SIG_TERMS, "css_index_significant_terms: m=%d outside [1, %d]", m, CSS_MAX_SIG_TERMS);
+    CSS_REQUIRE(min_count >= 1, "css_index_significant_terms: min_count=%lld is below 1", (long long)min_count);
+    CSS_REQUIRE(terms_out && fg_out && bg_out && score_out && n_out && fg_rows_out && bg_rows_out,
+                "css_index_significant_terms: NULL buffer");
+    HostCall hc(ix, nullptr, false);
+    const int64_t T = std::min(ix->lex_rows, hc.rows.n);
+    const int64_t outside = sig_first_outside(allow_bits_host, background_bits_host, T);
+    CSS_REQUIRE(outside < 0, "css_index_significant_terms: row %lld is selected but not in the background", (long long)outside);
+    for (int i = 0; i < m; ++i) {
+        terms_out[i] = kSigEmpty;
+        fg_out[i] = bg_out[i] = 0;
+        score_out[i] = 0.0;
+    }
+    *n_out = 0;
+    *fg_rows_out = *bg_rows_out = 0;
+    if (T == 0) return CSS_OK;
+    const int64_t FG = sig_popcount(allow_bits_host, T), BG = sig_popcount(background_bits_host, T);
+    if (FG == 0) return CSS_OK;
+    *fg_rows_out = FG;
+    *bg_rows_out = BG;
+    constexpr int N = CSS_MAX_SIG_TERMS;
+    unsigned long long packed[N + 3 * N / 2 + 1];
+    const uint32_t mc = (uint32_t)std::min<int64_t>(min_count, 0xFFFFFFFFll);
+    const int rc = significant_terms_locked(ix, hc, allow_bits_host, background_bits_host, T, FG, BG, m, mc, packed);
+    if (rc != CSS_OK) return hc.wait_if_failed(rc);
+    const uint32_t* terms = reinterpret_cast<const uint32_t*>(packed + N);
+    const int n = (int)packed[N + 3 * N / 2];
+    for (int i = 0; i < n; ++i) {
+        terms_out[i] = terms[i];
+        fg_out[i] = (int64_t)terms[N + i];
+        bg_out[i] = (int64_t)terms[2 * N + i];
+        memcpy(&score_out[i], &packed[i], sizeof(double));
+    }
+    *n_out = n;
     return CSS_OK;
 }
 

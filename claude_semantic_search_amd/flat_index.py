@@ -867,6 +867,61 @@ class IndexFlat:
                                                  df.ctypes.data if t.size else None, ctypes.byref(ndocs), ctypes.byref(total)))
         return df, int(ndocs.value), int(total.value)
 
+    # -- significant terms -------------------------------------------------------
+    def subset_terms(self, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``(terms uint32 ascending, fg int64)``: every term that a selected row's list holds, with the number of
+        selected rows that hold it (``css_index_subset_terms``; ``allow=None``: every row that has a list).  Counted on
+        the GPU over the lists of the selected rows only; the form the sharded index exchanges."""
+        return self._subset_terms(allow)[:2]
+
+    def _subset_terms(self, allow) -> Tuple[np.ndarray, np.ndarray, int]:
+        """``subset_terms`` and the number of selected rows that have a list."""
+        h = self._handle()
+        bits, bits_ptr = self._allow_bits(allow)
+        n, rows = ctypes.c_int64(0), ctypes.c_int64(0)
+        cap = 1 << 16   # (one call answers a small selection; a larger one is sized by the first)
+        while True:
+            terms, fg = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.int64)
+            nat.check(nat.lib().css_index_subset_terms(h, bits_ptr, cap, terms.ctypes.data, fg.ctypes.data, ctypes.byref(n),
+                                                       ctypes.byref(rows)))
+            if n.value <= cap:
+                return terms[:n.value].copy(), fg[:n.value].copy(), int(rows.value)
+            cap = int(n.value)
+
+    def significant_terms(self, allow=None, m: int = 20, min_count: int = 2, background=None):
+        """The ``m`` terms that set the selected rows apart from the background (``css_index_significant_terms``): a
+        ``lexical.SignificantTerms`` ``(terms, fg, bg, score float64, n_fg, n_bg)``, best first, cut to the terms that
+        qualified.  ``allow`` selects the rows (``None``: every row with a list), ``background`` the rows they are
+        compared with (``None``: every row with a list, counted by the standing df table); the selection must lie within
+        the background, else ``ValueError``.  A term qualifies iff at least ``min_count`` selected rows hold it and it
+        is more frequent in the selection than in the background; the score is JLH in float64
+        (``lexical.significant_from_counts`` states the same bits).  ``1 <= m <= 256``."""
+        from .lexical import SignificantTerms, significant_args
+
+        m, min_count = significant_args(m, min_count)
+        h = self._handle()
+        bits, bits_ptr = self._allow_bits(allow)
+        bg_bits, bg_ptr = self._allow_bits(background)
+        if background is not None:
+            T = self._terms_rows
+            sel = np.ones(T, dtype=bool) if allow is None else np.asarray(allow)[:T]
+            bad = np.flatnonzero(sel & ~np.asarray(background)[:T])
+            if bad.size:
+                raise ValueError(f"significant_terms: row {int(bad[0])} is selected but not in the background")
+        terms, score = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.float64)
+        fg, bg = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+        n, n_fg, n_bg = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        nat.check(nat.lib().css_index_significant_terms(h, bits_ptr, bg_ptr, m, min_count, terms.ctypes.data, fg.ctypes.data,
+                                                        bg.ctypes.data, score.ctypes.data, ctypes.byref(n), ctypes.byref(n_fg),
+                                                        ctypes.byref(n_bg)))
+        k = int(n.value)
+        return SignificantTerms(terms[:k].copy(), fg[:k].copy(), bg[:k].copy(), score[:k].copy(), int(n_fg.value), int(n_bg.value))
+
+    def set_sigterm_slots(self, slots: int) -> None:
+        """LDS slots per block in which the counting pass of ``subset_terms`` / ``significant_terms`` merges repeated
+        terms (-1 = the library's rule, 0 = none: every entry is one global add); the integers do not depend on it."""
+        nat.check(nat.lib().css_index_set_sigterm_slots(self._handle(), int(slots)))
+
     def search_hybrid(self, q, terms, weights, k: int, alpha: float, k1: float = 1.2, b: float = 0.75,
                       avgdl: Optional[float] = None, normalize: bool = False,
                       allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:

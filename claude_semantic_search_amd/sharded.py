@@ -45,7 +45,7 @@ class ShardedFlatIndex:
     """``IndexFlat`` semantics over ``world`` row shards.
 
     ``local_index`` must offer ``ntotal``, ``add(x, normalize=)``, ``add_synthetic``, ``set_id_base`` and
-    ``search_dev``/``search`` (``range_search`` for ``range_search``, ``reconstruct_n`` for ``search_by_ids`` and ``search_diverse``; ``kmeans_step``, ``bounds`` and ``reconstruct_batch`` for ``kmeans``); ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
+    ``search_dev``/``search`` (``range_search`` for ``range_search``, ``reconstruct_n`` for ``search_by_ids`` and ``search_diverse``; ``kmeans_step``, ``bounds`` and ``reconstruct_batch`` for ``kmeans``; ``subset_terms`` and ``term_stats`` for ``significant_terms``); ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
     implementations; tests substitute doubles.
     """
 
@@ -561,6 +561,64 @@ class ShardedFlatIndex:
         I, (D, S, L), _ = self._columns(I, (D, S, L))
         return tuple(np.ascontiguousarray(a[..., :k]) for a in (D, I, S, L))
 
+    # -- significant terms -------------------------------------------------------------------------------------
+    def _exchange_counts(self, local_mask):
+        """``(terms ascending, counts, rows)`` of the whole index for a mask over THIS shard's rows (``None``: every
+        row): every shard's ``subset_terms`` added up by term, and the number of masked rows that have lists.  The
+        variable-length pairs move the way ``range_search`` moves its hits: one all-gather of the sizes, one of the
+        pairs padded to the largest shard's."""
+        t_local = sum(min(max(self._terms_global - g0, 0), m) for _, g0, m in self.segments)   # local rows with lists
+        rows = t_local if local_mask is None else int(np.count_nonzero(np.asarray(local_mask)[:t_local]))
+        t, f = self.local.subset_terms(local_mask)
+        t, f = np.ascontiguousarray(t, dtype=np.uint32), np.ascontiguousarray(f, dtype=np.int64)
+        if self._single():
+            return t, f, rows
+        sizes = self._all_gather_host(np.array([t.shape[0], rows], dtype=np.int64))
+        most, rows = int(sizes[:, 0].max()), int(sizes[:, 1].sum())
+        if most == 0:
+            return np.zeros(0, np.uint32), np.zeros(0, np.int64), rows
+        record = (12 * most + 15) // 16 * 16   # [most int64 counts][most uint32 terms]
+        send = np.zeros(record, dtype=np.uint8)
+        send[:8 * f.shape[0]] = f.view(np.uint8)
+        send[8 * most:8 * most + 4 * t.shape[0]] = t.view(np.uint8)
+        recv = self._all_gather_host(send)
+        ts = np.concatenate([recv[r, 8 * most:8 * most + 4 * int(sizes[r, 0])].view(np.uint32) for r in range(self.world)])
+        fs = np.concatenate([recv[r, :8 * int(sizes[r, 0])].view(np.int64) for r in range(self.world)])
+        order = np.argsort(ts, kind="stable")
+        ts, fs = ts[order], fs[order]
+        first = np.flatnonzero(np.concatenate([[True], ts[1:] != ts[:-1]]))
+        return np.ascontiguousarray(ts[first]), np.add.reduceat(fs, first).astype(np.int64), rows
+
+    def subset_terms(self, allow=None):
+        """``IndexFlat.subset_terms`` over the shards (collective; ``allow`` is a mask over the GLOBAL rows, tombstones
+        are left out): the integer sums of the shards' counts, the same on every rank."""
+        return self._exchange_counts(self._local_allow(allow))[:2]
+
+    def significant_terms(self, allow=None, m: int = 20, min_count: int = 2, background=None):
+        """``IndexFlat.significant_terms`` over the shards (collective; masks over the GLOBAL rows): the shards'
+        ``subset_terms`` are exchanged and added by term, the background counts come from the sharded ``term_stats`` (or
+        from a second exchange under a ``background`` mask), and ``lexical.significant_from_counts`` ranks -- integers
+        in, so the result equals the unsharded one byte for byte."""
+        from .lexical import significant_args, significant_from_counts
+
+        m, min_count = significant_args(m, min_count)
+        T = self._terms_global
+        for mask in (allow, background):
+            if mask is not None and np.asarray(mask).shape != (self.ntotal_global,):
+                raise ValueError(f"mask has {np.asarray(mask).shape} entries, the sharded index {self.ntotal_global} rows")
+        if background is not None:
+            sel = np.ones(T, dtype=bool) if allow is None else np.asarray(allow, dtype=bool)[:T]
+            bad = np.flatnonzero(sel & ~np.asarray(background, dtype=bool)[:T])
+            if bad.size:
+                raise ValueError(f"significant_terms: row {int(bad[0])} is selected but not in the background")
+        t, f, FG = self._exchange_counts(self._local_allow(allow))
+        if background is None:
+            b, BG = np.asarray(self.term_stats(t)[0], dtype=np.int64), T
+        else:
+            bt, bc, BG = self._exchange_counts(self._local_allow(background))
+            b = bc[np.searchsorted(bt, t)]   # (the selection lies within the background: every term is there)
+        return significant_from_counts(t, f, b, FG, BG, m, min_count)
+
     # -- diversified search ------------------------------------------------------------------------------------
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
         """``IndexFlat.search_diverse`` over the shards (collective: every rank passes the same arguments): ``(D, I)``
@@ -791,6 +849,12 @@ class ShardedIndexFacade:
 
     def term_stats(self, terms):
         return self.sh.term_stats(terms)
+
+    def subset_terms(self, allow=None):
+        return self.sh.subset_terms(allow=allow)
+
+    def significant_terms(self, allow=None, m: int = 20, min_count: int = 2, background=None):
+        return self.sh.significant_terms(allow=allow, m=m, min_count=min_count, background=background)
 
     def search_hybrid(self, q, terms, weights, k: int, alpha: float, k1: float = 1.2, b: float = 0.75,
                       avgdl: Optional[float] = None, normalize: bool = False, allow=None):

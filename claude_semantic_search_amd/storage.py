@@ -102,6 +102,17 @@ class Topic:
 
 
 @dataclass
+class Keyword:
+    """One term of ``HybridStorage.keywords``: the word, its hashed term id, the number of selected chunks and of live
+    chunks that hold it, and its JLH score."""
+    word: str
+    term: int
+    count: int
+    background_count: int
+    score: float
+
+
+@dataclass
 class MapPoint:
     """One chunk of ``HybridStorage.map``: its coordinates on the first two principal components of the selection, and
     its k-means topic under the same selection (``None`` when no topics were asked for)."""
@@ -848,6 +859,50 @@ class HybridStorage:
             lists[fid - lo] = terms_of(text)
         self.faiss_index.set_terms(lists, row0=lo)
         self._terms.rows = ntotal
+
+    def keywords(self, chunk_ids: Optional[List[str]] = None, filters: Optional[Dict[str, Any]] = None, n: int = 10,
+                 min_count: int = 2) -> List[Keyword]:
+        """"Which words set these chunks apart": the ``n`` terms most over-represented in a selection of chunks against
+        all live chunks, counted and ranked on the GPU (``IndexFlat.significant_terms``, JLH score; Elasticsearch's
+        ``significant_terms``).  The selection is the live chunks that match ``filters`` and, where given, are named by
+        ``chunk_ids`` (unknown and deleted ids are ignored) -- ``keywords(chunk_ids=topic.chunk_ids)`` names a topic,
+        ``keywords(chunk_ids=[r.chunk_id for r in hits])`` says why these hits.  A word counts once per chunk and must
+        be in at least ``min_count`` selected chunks.  Each ``Keyword`` carries the word as it first appears (after BERT's
+        word splitting) in the selected chunks' stored text in ``faiss_id`` order, its term id, the chunks of the
+        selection and of the background that hold it, and the score; best first.  An empty selection gives ``[]``; an
+        index object without ``significant_terms`` raises ``NotImplementedError``."""
+        from .lexical import significant_args, words_of_terms
+
+        n, min_count = significant_args(n, min_count, "keywords")
+        self._require("significant terms", "significant_terms", "set_terms")
+        with self._lock:
+            frame = self._search_frame(SearchConfig())
+            if frame is None:
+                return []
+            _, ntotal, _ = frame
+            self._sync_terms(ntotal)
+            live = self._allow_mask({}, ntotal)
+            sel = self._allow_mask(filters or {}, ntotal)
+            if chunk_ids is not None:
+                named = np.zeros(ntotal, dtype=bool)
+                for cid in chunk_ids:
+                    fid = self.chunk_id_to_faiss_id.get(cid)
+                    if fid is not None and fid < ntotal:
+                        named[fid] = True
+                sel = sel & named
+            rows = np.flatnonzero(sel)
+            if rows.size == 0:
+                return []
+            res = self.faiss_index.significant_terms(allow=sel, m=n, min_count=min_count, background=live)
+            if len(res.terms) == 0:
+                return []
+            cur = self.db.cursor().execute(
+                "SELECT faiss_id, id, text FROM chunks WHERE faiss_id >= ? AND faiss_id <= ? ORDER BY faiss_id",
+                (int(rows[0]), int(rows[-1])))
+            texts = (text for fid, cid, text in cur if sel[fid] and self.faiss_id_to_chunk_id.get(fid) == cid)
+            words = words_of_terms(texts, res.terms)
+            return [Keyword(words.get(int(t), ""), int(t), int(f), int(b), float(s))
+                    for t, f, b, s in zip(res.terms, res.fg, res.bg, res.score)]
 
     def search_hybrid(self, query_text: str, query_embedding, config: Optional[SearchConfig] = None,
                       filters: Optional[Dict[str, Any]] = None, alpha: float = 0.3, k1: float = 1.2,

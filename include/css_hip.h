@@ -387,6 +387,46 @@ int css_index_search_hybrid(css_index* ix, const float* q_host /* [dim] */, int 
                             const uint32_t* allow_bits_host, float* D_host, int64_t* I_host,
                             float* S_host /* may be NULL */, float* L_host /* may be NULL */);
 
+/* Significant terms (Elasticsearch's significant_terms aggregation, the keyword side of BERTopic): which terms set a
+ * selection of rows apart from a background -- "what is in this cluster / this project / these hits".  Everything is
+ * read from the term lists above; the rows' values play no part.  T = the leading rows that have lists.
+ *  - Sets.  The selection S = {r < T : bit r of allow_bits_host} and the background B = {r < T : bit r of
+ *    background_bits_host}, bitmaps as in css_index_search_masked over LOCAL rows; NULL means every row below T.  S must
+ *    lie within B: otherwise CSS_ERR_INVALID, the message names the first offending row and nothing is written.
+ *  - Counts.  fg[t] = the rows of S whose list holds term t, bg[t] the same for B (without a background mask that is
+ *    the standing df table), FG = |S|, BG = |B|; rows with an empty list count in FG and BG.  Exact integers.
+ *  - css_index_subset_terms: every term with fg >= 1, ascending by term, with its fg -- the form that shards exchange.
+ *    Two-call sizing: *n_out = the number of such terms and *rows_out = FG always; the pairs are written when
+ *    cap >= *n_out (terms_out, fg_out: cap entries each) and nothing is written when it is not (cap = 0: sizing).
+ *  - css_index_significant_terms.  A term qualifies iff fg >= min_count (min_count >= 1) and fg * BG > bg * FG, compared
+ *    in exact unsigned 64-bit integers.  Its score is JLH in float64, one IEEE rounding per operation, no contraction:
+ *        p = (double)fg / (double)FG;   q = (double)bg / (double)BG;   score = (p - q) * (p / q);
+ *    so a float64 restatement (lexical.significant_from_counts) gives the same bits.  The answer is the best m
+ *    qualifying terms, 1 <= m <= CSS_MAX_SIG_TERMS, score descending, ties to the smaller term; *n_out <= m says how
+ *    many qualified.  All m slots of terms_out / fg_out / bg_out / score_out are written: unused slots hold term
+ *    0xFFFFFFFF, counts 0 and score 0.0.  *fg_rows_out = FG, *bg_rows_out = BG.
+ *  - An index without lists, or an empty selection: *n_out = 0 and FG = BG = 0; no device is touched.
+ *  - On the device (css_sigterms.h): one scatter-count over the lists of the selected rows into a zeroed uint32 table
+ *    [2^24] (a second one under a background mask) with integer atomics only, a wave passing over 64 unselected rows
+ *    for the price of their two mask words; one pass over the 2^24 slots qualifies and scores; an exact radix select on
+ *    the 88-bit key (score bits, term) and a sort of the m winners.  The tables (64 MB each) and the candidate list are
+ *    workspaces of the index, allocated on first use; they are not index state and outlive css_index_reset.  Locking
+ *    and the call frame are those of css_index_term_stats; css_index_significant_terms waits for the device once,
+ *    css_index_subset_terms twice when it writes.  Neither edits the index: df, the lists and every search are
+ *    unchanged by them.
+ *  - css_index_set_sigterm_slots: the (term, count) slots of the per-block LDS table in which the counting pass merges
+ *    repeats of a term before it touches the global table (a term present in most rows would otherwise send one global
+ *    add per row to one address).  -1 = the library's rule (4096), 0 = no table: every entry is one global add; else a
+ *    power of two in [16, 4096].  A verification knob like css_index_set_gram_rows: the integers do not depend on it. */
+#define CSS_MAX_SIG_TERMS 256
+int css_index_set_sigterm_slots(css_index* ix, int slots);
+int css_index_subset_terms(css_index* ix, const uint32_t* allow_bits_host, int64_t cap, uint32_t* terms_out /* [cap] */,
+                           int64_t* fg_out /* [cap] */, int64_t* n_out, int64_t* rows_out);
+int css_index_significant_terms(css_index* ix, const uint32_t* allow_bits_host,
+                                const uint32_t* background_bits_host /* or NULL */, int m, int64_t min_count,
+                                uint32_t* terms_out /* [m] */, int64_t* fg_out /* [m] */, int64_t* bg_out /* [m] */,
+                                double* score_out /* [m] */, int* n_out, int64_t* fg_rows_out, int64_t* bg_rows_out);
+
 /* Rows by id (faiss reconstruct_batch): the stored fp32 rows of the n GLOBAL ids (id_base included), gathered on the
  * device, as [n, dim] floats exactly as they lie in device memory.  Repeated ids are allowed.  An id outside
  * [id_base, id_base + ntotal) is CSS_ERR_INVALID: the message names it and nothing is enqueued.  n == 0 is a no-op.
