@@ -22,6 +22,8 @@ _LAZY = {
     "Topic": ".storage",
     "MapPoint": ".storage",
     "Keyword": ".storage",
+    "Facet": ".storage",
+    "Facets": ".storage",
     "EmbeddingConfig": ".embeddings",
     "EmbeddingStats": ".embeddings",
     "EmbeddingGenerator": ".embeddings",
@@ -36,6 +38,7 @@ _LAZY = {
     "PCAMatrix": ".flat_index",
     "PcaResult": ".flat_index",
     "GramResult": ".flat_index",
+    "FacetCounts": ".flat_index",
     "pca_from_gram": ".flat_index",
     "terms_of": ".lexical",
     "bm25_weights": ".lexical",

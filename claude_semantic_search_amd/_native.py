@@ -32,6 +32,7 @@ MAX_HYBRID_K = 128   # css_index_search_hybrid: the same list size
 MAX_QUERY_TERMS = 32   # include/css_hip.h CSS_MAX_QUERY_TERMS
 TERM_SPACE = 1 << 24   # include/css_hip.h CSS_TERM_SPACE
 MAX_SIG_TERMS = 256   # include/css_hip.h CSS_MAX_SIG_TERMS
+MAX_FACET_BUCKETS = 1 << 20   # include/css_hip.h CSS_MAX_FACET_BUCKETS
 MAX_EXAMPLES = 16   # include/css_hip.h CSS_MAX_EXAMPLES
 MAX_EXAMPLES_K = 128   # css_index_search_examples: the same list size
 MAX_CENTROIDS = 4096   # include/css_hip.h CSS_MAX_CENTROIDS
@@ -149,6 +150,10 @@ PROTOTYPES = {
     "css_range_result_lims": (c_int, [c_void_p, c_void_p]),
     "css_range_result_read": (c_int, [c_void_p, c_void_p, c_void_p]),
     "css_range_result_free": (c_int, [c_void_p]),
+    "css_index_facets": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "css_index_last_facet_sweeps": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    "css_index_set_facet_lds_entries": (c_int, [c_void_p, c_int64]),
     "css_merge_topk_dev": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "css_merge_topk_packed_dev": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int,
                                           c_void_p]),

@@ -28,6 +28,9 @@
 //   k_merge_final      per query: merge the per-block lists into the final top-k.
 //   k_range_small      css_index_range_search: the exact fp32 sweep with a radius test and a variable-length
 //                      hit list instead of top-k lists (css_knn_range.h).   HBM bound
+//   k_facet_small      css_index_facets: the same sweep with a per-(query, bucket) table of hit counts and best-row
+//                      keys instead of the hit list, in LDS per block or in global memory, integer atomics only
+//                      (css_knn_facets.h).   HBM bound
 //   k_gather_queries,  css_index_search_rows: stored rows copied into a query buffer in front of the ordinary
 //   k_drop_self        search for k + 1, and the anchor compacted out of its results behind it (a wave per query)
 //   k_collapse_groups, css_index_search_grouped: a pass's results collapsed to the first row of every group label, and
@@ -60,7 +63,7 @@
 // plain merge behind them; css_knn_plan.h states the rules of the candidate cascade (kind, growth, schedule, error bound,
 // tickets) and launch_scan_coarse applies them as named steps over one CascadeCall; RowColumn is a 4-byte-per-row
 // column (labels, priors) and css_index::columns() the list every row operation walks.  The sweep body of k_scan_small,
-// k_range_small, k_scan_prior and k_scan_examples is deliberately NOT shared (css_knn_range.h says why).
+// k_range_small, k_scan_prior, k_scan_examples and k_facet_small is deliberately NOT shared (css_knn_range.h says why).
 #include "css_common.h"
 #include "css_devbuf.h"
 #include "css_knn_kernels.h"
@@ -201,6 +204,13 @@ struct css_index {
     DevBuf<float> range_s;  DevBuf<uint32_t> range_i;
     static constexpr int kRangeSlots = 16;   // query slots of one sweep (counters, pool segments)
     size_t range_cap() const { return range_s.cap / kRangeSlots; }
+    // css_index_facets (css_knn_facets.h): the table of ONE sweep, at most 2^20 entries -- [E uint64 keys | 16 totals |
+    // 16 unbucketed | E uint32 counts] in 8-byte words, zeroed before and copied back after every sweep -- and the
+    // device copy of a per-call bucket column [ntotal] (a workspace: uploaded on every call, never index state)
+    DevBuf<unsigned long long> facet_tab;
+    DevBuf<int32_t> facet_col;
+    int64_t facet_lds_entries = -1;     // css_index_set_facet_lds_entries: -1 = the library's rule (facet_lds_fits)
+    int64_t last_facet_sweeps = 0, last_facet_lds_sweeps = 0;   // of the last css_index_facets (css_index_last_facet_sweeps)
     // css_index_search_rows: the gathered query rows [nq, dim] (not q_raw: the host search copies into that before it
     // has waited for ws_ev), one invalid-id flag per query, the search's own [nq, k + 1] results in front of
     // k_drop_self, and the device copy of a host id list
@@ -1895,7 +1905,7 @@ struct FixArgs {
     int64_t* I = nullptr;
 };
 
-// The host fan-out of the exact fp32 sweeps (k_scan_small, k_range_small, k_scan_prior, k_scan_examples), once.
+// The host fan-out of the exact fp32 sweeps (k_scan_small, k_range_small, k_scan_prior, k_scan_examples, k_facet_small), once.
 // sweep_variant: f(TT, METRIC) with TT from dpad (12: the unrolled 768-float row, 0: any) and METRIC from the index.
 // sweep_slots: f(NQ) with the smallest NQ of 1 / 2 / 8 / 16 that holds nqc queries (an NQ=4 instantiation spills under
 // hipcc 7.2; 3..8 share NQ=8).  The arguments are std::integral_constants: decltype(X)::value is a template argument.
@@ -2677,7 +2687,7 @@ int launch_scan_coarse(css_index* ix, const Rows& rows, int q0, int nq, int k, f
                         c.I, sg, st);
 }
 
-// grid of the exact fp32 sweeps (k_scan_small, k_range_small, k_scan_prior, k_scan_examples) over the rows in view:
+// grid of the exact fp32 sweeps (k_scan_small, k_range_small, k_scan_prior, k_scan_examples, k_facet_small) over the rows in view:
 // enough blocks to fill the chip (8 per CU) but at least ~64 row groups of work each
 void sweep_grid(const css_index* ix, const Rows& rows, int* G, int64_t* gpb) {
     const int64_t ngroups = (rows.n + 3) / 4;
@@ -2749,6 +2759,75 @@ int range_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 // No room: CSS_ERR_OOM, the pool is gone (the next call starts from the initial size) and the index is untouched.
 int range_pool_alloc(css_index* ix, size_t cap) {
     return try_exact_pair(ix->range_s, ix->range_i, kRangeSlots * cap) ? CSS_OK : CSS_ERR_OOM;
+}
+
+// ------------------------------------------------------------------ facet counts (css_knn_facets.h)
+#include "css_knn_facets.h"
+
+constexpr int64_t kFacetMaxEntries = (int64_t)CSS_MAX_FACET_BUCKETS;   // table entries of one sweep
+constexpr size_t kFacetEntryBytes = sizeof(unsigned long long) + sizeof(unsigned int);   // key + count
+constexpr size_t kLdsPerCu = 160 * 1024;      // gfx950
+
+// Does the [nqc][nbuckets] table of a sweep go to LDS?  The library's rule is a number of blocks that must still fit
+// one CU (160 KB) with the NQ query rows and the table each: ONE block for NQ <= 2, TWO for NQ = 8 / 16.  Measured at
+// 10 M x 768 (profiles/facets_10M.json): the one- and two-query sweeps are HBM bound and the LDS table
+// never lost to the global one, down to a single block per CU; the 8- and 16-query sweeps are VALU / LDS bound: with
+// rare hits the LDS table costs up to 3 % (8 queries) and 9 % (16 queries) while two blocks fit and 37-51 % at one, and
+// with half the rows hitting it wins 2x to 11x at two blocks or more and barely at one.  (Keeping k_range_small's own occupancy, three to four blocks, was the first rule: it sent 16 queries x 64
+// buckets to global memory, 2.2x slower with half the rows hitting.)  css_index_set_facet_lds_entries replaces the rule
+// by a fixed entry count (0: never), still inside the 160 KB one block can have.
+bool facet_lds_fits(const css_index* ix, int NQ, int64_t entries) {
+    const size_t qbytes = (size_t)NQ * ix->dpad * 4, tbytes = (size_t)entries * kFacetEntryBytes;
+    if (qbytes + tbytes > kLdsPerCu) return false;
+    if (ix->facet_lds_entries >= 0) return entries <= ix->facet_lds_entries;
+    return qbytes + tbytes <= kLdsPerCu / (NQ <= 2 ? 1 : 2);
+}
+
+template <int NQ, int TT, int METRIC, bool LDS_TABLE>
+int launch_facet_small_t(css_index* ix, const Rows& rows, const float* qpad, int nq_real, float radius, const int32_t* bucket,
+                         int nbuckets, int G, int64_t gpb, hipStream_t st) {
+    const size_t E = (size_t)nq_real * nbuckets;
+    const size_t lds = (size_t)NQ * ix->dpad * 4 + (LDS_TABLE ? E * kFacetEntryBytes : 0);
+    auto kern = k_facet_small<NQ, TT, METRIC, LDS_TABLE>;
+    int rc;
+    if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)kern, lds, ix->device)) != CSS_OK) return rc;
+    unsigned int* words = reinterpret_cast<unsigned int*>(ix->facet_tab.p + E);   // [16 | 16 | E counts]
+    ProfScope ps("knn_facet_small", st);
+    hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, st, (const float4*)rows.xb, qpad, rows.n, ix->dpad / 64, gpb, nq_real,
+                       rows.mask, radius, bucket, nbuckets, words, words + 32, ix->facet_tab.p);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+template <int NQ>
+int launch_facet_small_nq(css_index* ix, const Rows& rows, const float* qpad, int nq_real, float radius, const int32_t* bucket,
+                          int nbuckets, bool lds_table, int G, int64_t gpb, hipStream_t st) {
+    return sweep_variant(ix, [&](auto TT, auto M) {
+        return lds_table ? launch_facet_small_t<NQ, decltype(TT)::value, decltype(M)::value, true>(ix, rows, qpad, nq_real, radius, bucket, nbuckets, G, gpb, st)
+                         : launch_facet_small_t<NQ, decltype(TT)::value, decltype(M)::value, false>(ix, rows, qpad, nq_real, radius, bucket, nbuckets, G, gpb, st);
+    });
+}
+
+// 8-byte words of the table of a sweep with E entries: [E keys | 32 + E uint32]
+inline size_t facet_tab_words(size_t E) { return E + (32 + E + 1) / 2; }
+
+// One sweep of all rows for queries qpad[0 .. nqc): table zeroed, kernel, table back in `tab_host` (waits for the
+// stream).  *lds: the placement that ran.
+int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, float radius, const int32_t* bucket, int nbuckets,
+                unsigned long long* tab_host, bool* lds, hipStream_t st) {
+    int G;
+    int64_t gpb;
+    sweep_grid(ix, rows, &G, &gpb);
+    const size_t words = facet_tab_words((size_t)nqc * nbuckets);
+    CSS_HIP_TRY(hipMemsetAsync(ix->facet_tab.p, 0, words * sizeof(unsigned long long), st));
+    const int rc = sweep_slots(nqc, [&](auto NQ) {
+        *lds = facet_lds_fits(ix, decltype(NQ)::value, (int64_t)nqc * nbuckets);
+        return launch_facet_small_nq<decltype(NQ)::value>(ix, rows, qpad, nqc, radius, bucket, nbuckets, *lds, G, gpb, st);
+    });
+    if (rc != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(tab_host, ix->facet_tab.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    return CSS_OK;
 }
 
 // ------------------------------------------------------------------ prior-weighted search (css_knn_prior.h)
@@ -4963,6 +5042,121 @@ int css_index_range_search(css_index* ix, const float* q_host, int64_t nq, float
         return rc;
     }
     *out = res;
+    return CSS_OK;
+}
+
+// ------------------------------------------------------------------ facet counts
+namespace {
+// nq > 0 queries over hc.rows.n > 0 rows inside the caller's host frame, the outputs already at their empty values:
+// the turn at the workspaces, the frame's upload of bitmap and queries, the bucket column, then one table per sweep
+// decoded into the caller's arrays.  Everything has finished on the index's own stream when this returns CSS_OK.
+int facets_locked(css_index* ix, HostCall& hc, const float* q_host, const uint32_t* allow_bits_host, int64_t nq, float radius,
+                  int normalize_q, const int32_t* buckets_host, int64_t nbuckets, int64_t* count_out, float* best_score_out,
+                  int64_t* best_id_out, int64_t* total_out, int64_t* unbucketed_out) {
+    hipStream_t st = ix->stream;
+    int rc;
+    CSS_REQUIRE(hc.rows.n < 0xFFFFFFFFll, "css_index_facets: %lld rows exceed the 32-bit row numbers of the table keys",
+                (long long)hc.rows.n);
+    const int nq_sweep = (int)std::min<int64_t>(range_nq_sweep(ix), std::max<int64_t>(1, kFacetMaxEntries / nbuckets));
+    const size_t words = facet_tab_words((size_t)std::min<int64_t>(nq_sweep, nq) * (size_t)nbuckets);
+    std::vector<unsigned long long> tab;
+    try {
+        tab.resize(words);
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_index_facets: no host memory for a table of %lld buckets", (long long)nbuckets);
+        return CSS_ERR_OOM;
+    }
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    if ((rc = hc.upload(allow_bits_host, ix->q_raw, q_host, (size_t)nq * ix->dim)) != CSS_OK) return rc;
+    const Rows& rows = hc.rows;
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    if ((rc = ix->qpad.grow((size_t)(nq + 256) * ix->dpad)) != CSS_OK) return rc;
+    if ((rc = ix->qnorm2.grow((size_t)nq + 256)) != CSS_OK) return rc;
+    if (!ix->facet_tab.try_exact(words)) {
+        css::set_error("css_index_facets: no device memory for a table of %lld queries x %lld buckets",
+                       (long long)std::min<int64_t>(nq_sweep, nq), (long long)nbuckets);
+        return CSS_ERR_OOM;
+    }
+    const int32_t* bucket = rows.labels;   // (null: no label was ever set, every hit is unbucketed)
+    if (buckets_host) {
+        if (!ix->facet_col.try_exact((size_t)rows.n)) {
+            css::set_error("css_index_facets: no device memory for the bucket column of %lld rows", (long long)rows.n);
+            return CSS_ERR_OOM;
+        }
+        CSS_HIP_TRY(hipMemcpyAsync(ix->facet_col.p, buckets_host, (size_t)rows.n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        bucket = ix->facet_col.p;
+    }
+    if ((rc = prep_queries(ix, ix->q_raw.p, nq, normalize_q, nullptr, st)) != CSS_OK) return rc;
+    const bool ip = ix->metric == CSS_METRIC_IP;
+    for (int64_t q0 = 0; q0 < nq; q0 += nq_sweep) {
+        const int nqc = (int)std::min<int64_t>(nq_sweep, nq - q0);
+        const size_t E = (size_t)nqc * (size_t)nbuckets;
+        bool lds = false;
+        if ((rc = facet_sweep(ix, rows, ix->qpad.p + (size_t)q0 * ix->dpad, nqc, radius, bucket, (int)nbuckets, tab.data(), &lds,
+                              st)) != CSS_OK)
+            return rc;
+        ++ix->last_facet_sweeps;
+        ix->last_facet_lds_sweeps += lds ? 1 : 0;
+        const unsigned int* w = reinterpret_cast<const unsigned int*>(tab.data() + E);
+        for (int j = 0; j < nqc; ++j) {
+            total_out[q0 + j] = (int64_t)w[j];
+            unbucketed_out[q0 + j] = (int64_t)w[16 + j];
+        }
+        const size_t o0 = (size_t)q0 * (size_t)nbuckets;
+        for (size_t e = 0; e < E; ++e) {
+            const unsigned int c = w[32 + e];
+            count_out[o0 + e] = (int64_t)c;
+            if (c == 0) continue;
+            const unsigned long long key = tab[e];
+            uint32_t u = (uint32_t)(key >> 32);
+            if (!ip) u = ~u;
+            u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+            if (best_score_out) memcpy(best_score_out + o0 + e, &u, sizeof(float));
+            if (best_id_out) best_id_out[o0 + e] = rows.id_base + (int64_t)(uint32_t)~(uint32_t)key;
+        }
+    }
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_facets(css_index* ix, const float* q_host, int64_t nq, float radius, int normalize_q,
+                     const uint32_t* allow_bits_host, const int32_t* buckets_host, int64_t nbuckets, int64_t* count_out,
+                     float* best_score_out, int64_t* best_id_out, int64_t* total_out, int64_t* unbucketed_out) {
+    CSS_REQUIRE(ix, "css_index_facets: NULL index");
+    CSS_REQUIRE(nq >= 0 && nq < (1 << 24), "css_index_facets: nq=%lld out of range", (long long)nq);
+    CSS_REQUIRE(!std::isnan(radius), "css_index_facets: the radius is NaN");
+    CSS_REQUIRE(nbuckets >= 1 && nbuckets <= CSS_MAX_FACET_BUCKETS, "css_index_facets: nbuckets=%lld outside [1, %d]",
+                (long long)nbuckets, CSS_MAX_FACET_BUCKETS);
+    CSS_REQUIRE(nq == 0 || (q_host && count_out && total_out && unbucketed_out), "css_index_facets: NULL buffer");
+    if (nq == 0) return CSS_OK;   // (no query touches no device)
+    HostCall hc(ix, nullptr, false);
+    ix->last_facet_sweeps = ix->last_facet_lds_sweeps = 0;
+    // the answer of an empty index, and the empty slots of any other
+    const size_t n = (size_t)nq * (size_t)nbuckets;
+    std::fill(count_out, count_out + n, (int64_t)0);
+    if (best_score_out) std::fill(best_score_out, best_score_out + n, pad_score(ix));
+    if (best_id_out) std::fill(best_id_out, best_id_out + n, (int64_t)-1);
+    std::fill(total_out, total_out + nq, (int64_t)0);
+    std::fill(unbucketed_out, unbucketed_out + nq, (int64_t)0);
+    if (hc.rows.n == 0) return CSS_OK;
+    return hc.wait_if_failed(facets_locked(ix, hc, q_host, allow_bits_host, nq, radius, normalize_q, buckets_host, nbuckets,
+                                           count_out, best_score_out, best_id_out, total_out, unbucketed_out));
+}
+
+int css_index_last_facet_sweeps(css_index* ix, int64_t* sweeps, int64_t* lds_sweeps) {
+    CSS_REQUIRE(ix && sweeps && lds_sweeps, "css_index_last_facet_sweeps: NULL argument");
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    *sweeps = ix->last_facet_sweeps;
+    *lds_sweeps = ix->last_facet_lds_sweeps;
+    return CSS_OK;
+}
+
+int css_index_set_facet_lds_entries(css_index* ix, int64_t entries) {
+    CSS_REQUIRE(ix, "css_index_set_facet_lds_entries: NULL index");
+    CSS_REQUIRE(entries >= -1, "css_index_set_facet_lds_entries: entries=%lld below -1", (long long)entries);
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    ix->facet_lds_entries = entries;
     return CSS_OK;
 }
 

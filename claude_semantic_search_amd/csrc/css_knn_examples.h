@@ -29,9 +29,10 @@
 // numbers in LDS.  They are tested only on the slow path, in `pass`, before wave_insert: an excluded row is a near-best
 // row by construction, so it reaches the slow path anyway, and the fast path pays nothing.
 //
-// The sweep body (row addressing, mask test, fmaf blocks) now exists FOUR times on purpose: k_scan_small,
-// k_range_small, k_scan_prior and here (css_knn_range.h and profiles/flat_index_refactor_shared_sweep_attempts.txt say
-// why it is not one function); a change to one is made to all four.
+// The sweep body (row addressing, mask test, fmaf blocks) now exists FIVE times on purpose: k_scan_small,
+// k_range_small, k_scan_prior, here and k_facet_small (css_knn_facets.h); css_knn_range.h and
+// profiles/flat_index_refactor_shared_sweep_attempts.txt say why it is not one function.  A change to one is made to
+// all five.
 //
 // The raw score.  The call also returns S = P, the best positive score of a returned row, so that similarity
 // thresholds keep their meaning.  As in css_knn_prior.h it is not carried through the lists: k_example_scores runs ONCE

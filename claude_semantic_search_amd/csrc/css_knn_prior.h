@@ -19,10 +19,10 @@
 // (k_merge_final<L2> writes D = -key, which is f with its sign).  weight == 0 or no column give key == s bit for
 // bit: fmaf(0, p, s) and fmaf(w, 0, s) are s for finite p and w (a chain that starts at +0 never ends at -0).
 //
-// The sweep body (row addressing, mask test, fmaf blocks) exists FOUR times on purpose: k_scan_small, k_range_small,
-// here and k_scan_examples (css_knn_examples.h); css_knn_range.h and
+// The sweep body (row addressing, mask test, fmaf blocks) exists FIVE times on purpose: k_scan_small, k_range_small,
+// here, k_scan_examples (css_knn_examples.h) and k_facet_small (css_knn_facets.h); css_knn_range.h and
 // profiles/flat_index_refactor_shared_sweep_attempts.txt say why it is not one function.  A change to one is made to
-// all four.
+// all five.
 //
 // The raw score.  The call also returns S, the row's own s / dist, so that thresholds keep their meaning.  A third
 // LDS list beside keys and ids would cost NQ * k * 4 bytes of LDS per block and a third shifted array in every

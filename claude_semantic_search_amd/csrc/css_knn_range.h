@@ -12,9 +12,10 @@
 // row, IP = dot, L2 = sum of squared differences, which cannot go negative).  It reads the fp32 rows only, so the
 // answer does not depend on which reduced-precision copies the index keeps.  The fp32 score the kernel formed is the
 // value compared with the radius AND the value returned.  The sweep body (row addressing, mask test, fmaf blocks) is
-// kept FOUR times on purpose, here, in k_scan_small, in k_scan_prior (css_knn_prior.h) and in k_scan_examples
-// (css_knn_examples.h): moved into one __forceinline__ function it changed the register allocation of the kernels that
-// shared it (profiles/flat_index_refactor_shared_sweep_attempts.txt), so a change to one is made to all four.
+// kept FIVE times on purpose, here, in k_scan_small, in k_scan_prior (css_knn_prior.h), in k_scan_examples
+// (css_knn_examples.h) and in k_facet_small (css_knn_facets.h): moved into one __forceinline__ function it changed the
+// register allocation of the kernels that shared it (profiles/flat_index_refactor_shared_sweep_attempts.txt), so a
+// change to one is made to all five.
 //
 // Appending.  Query slot j owns pool entries [j * cap, (j + 1) * cap) and the counter cnt[j].  Per wave instruction
 // and query with at least one hit among the 4 rows: ballot, popcount, ONE returning agent-scope integer atomicAdd by

@@ -136,6 +136,46 @@ def collapse_groups(D, I, G, k: int, metric: int) -> Tuple[np.ndarray, np.ndarra
     return Do, Io, Go
 
 
+MAX_FACET_BUCKETS = nat.MAX_FACET_BUCKETS
+
+
+class FacetCounts(NamedTuple):
+    """What ``facets`` returns: per query and bucket the number of hits (``counts`` int64 ``[nq, nb]``) and the best
+    hit (``best_score`` float32, ``best_id`` int64 ``[nq, nb]``; an empty bucket has count 0, id ``-1`` and the score
+    ``search`` pads with), and per query all hits (``total``) and those outside every bucket (``unbucketed``), int64
+    ``[nq]``: ``total == counts.sum(1) + unbucketed``."""
+    counts: np.ndarray
+    best_score: np.ndarray
+    best_id: np.ndarray
+    total: np.ndarray
+    unbucketed: np.ndarray
+
+
+def facet_args(thresh, buckets, nbuckets, ntotal: int, what: str = "facets") -> Tuple[float, Optional[np.ndarray], int]:
+    """The argument rules of ``facets``, stated once: ``(thresh, buckets as int32 or None, nbuckets)``.  ``thresh`` is a
+    number, not NaN.  ``buckets`` is ``None`` (the ``set_groups`` labels; ``nbuckets`` is then required) or an integer
+    array of ``ntotal`` entries that fit int32; ``nbuckets=None`` then means ``max(buckets) + 1``, at least 1.
+    ``1 <= nbuckets <= MAX_FACET_BUCKETS``.  Anything else raises ``ValueError``."""
+    thresh = float(thresh)
+    if math.isnan(thresh):
+        raise ValueError(f"{what}: the threshold is NaN")
+    b = None
+    if buckets is not None:
+        b = labels_as_int32(buckets, what)
+        if b.shape[0] != ntotal:
+            raise ValueError(f"{what}: buckets must have ntotal={ntotal} entries, got {b.shape[0]}")
+        if nbuckets is None:
+            nbuckets = max(int(b.max()) + 1, 1) if b.size else 1
+    elif nbuckets is None:
+        raise ValueError(f"{what}: nbuckets is required when the buckets are the set_groups labels")
+    if isinstance(nbuckets, (bool, np.bool_)) or not isinstance(nbuckets, (int, np.integer)):
+        raise ValueError(f"{what}: nbuckets must be an integer, got {type(nbuckets).__name__}")
+    nbuckets = int(nbuckets)
+    if nbuckets < 1 or nbuckets > MAX_FACET_BUCKETS:
+        raise ValueError(f"{what}: nbuckets={nbuckets} outside [1, {MAX_FACET_BUCKETS}]")
+    return thresh, b, nbuckets
+
+
 MAX_PRIOR_K = nat.MAX_PRIOR_K
 
 
@@ -709,6 +749,42 @@ class IndexFlat:
         finally:
             nat.lib().css_range_result_free(res)
         return lims, D, I
+
+    def facets(self, q, thresh: float, buckets=None, nbuckets: Optional[int] = None, normalize: bool = False,
+               allow=None) -> FacetCounts:
+        """Where the matches lie (``css_index_facets``): for every query the number of rows with ``score > thresh``
+        (inner product) or squared distance ``< thresh`` (L2) -- strict, the hits of ``range_search`` -- in each of
+        ``nbuckets`` buckets, and the best such row per bucket (best score, ties to the smallest id), as a
+        ``FacetCounts``.  ``buckets`` is an integer array of ``ntotal`` entries that fit int32, in LOCAL row numbering
+        like ``allow``, uploaded for this call only; ``None`` means the ``set_groups`` labels (nothing is uploaded) and
+        ``nbuckets`` is then required.  ``nbuckets=None`` with ``buckets`` given means ``max(buckets) + 1``.  A hit whose
+        bucket is negative or ``>= nbuckets`` counts in ``unbucketed`` only.  Counts are integers and scores come from
+        the exact fp32 sweep of ``range_search``: the result is the same bytes on every call."""
+        a = _as_f32_2d(q, self.d, "facets")
+        nq = a.shape[0]
+        thresh, b, nb = facet_args(thresh, buckets, nbuckets, self.ntotal)
+        bits, bits_ptr = self._allow_bits(allow)
+        pad = -np.finfo(np.float32).max if self.metric_type == METRIC_INNER_PRODUCT else np.finfo(np.float32).max
+        out = FacetCounts(np.zeros((nq, nb), dtype=np.int64), np.full((nq, nb), pad, dtype=np.float32),
+                          np.full((nq, nb), -1, dtype=np.int64), np.zeros(nq, dtype=np.int64), np.zeros(nq, dtype=np.int64))
+        if nq:
+            nat.check(nat.lib().css_index_facets(self._handle(), a.ctypes.data, nq, thresh, 1 if normalize else 0, bits_ptr,
+                                                 None if b is None else b.ctypes.data, nb, out.counts.ctypes.data,
+                                                 out.best_score.ctypes.data, out.best_id.ctypes.data, out.total.ctypes.data,
+                                                 out.unbucketed.ctypes.data))
+        return out
+
+    def last_facet_sweeps(self) -> Tuple[int, int]:
+        """Diagnostics: ``(sweeps, lds_sweeps)`` of the last ``facets`` call -- the sweeps of the rows it ran and how many
+        of them kept their table in LDS."""
+        n, m = ctypes.c_int64(0), ctypes.c_int64(0)
+        nat.check(nat.lib().css_index_last_facet_sweeps(self._handle(), ctypes.byref(n), ctypes.byref(m)))
+        return int(n.value), int(m.value)
+
+    def set_facet_lds_entries(self, entries: int) -> None:
+        """The largest table (queries x buckets of one sweep) that ``facets`` keeps in LDS (-1 = the library's rule,
+        0 = never); the result does not depend on it."""
+        nat.check(nat.lib().css_index_set_facet_lds_entries(self._handle(), int(entries)))
 
     # -- per-row columns: the range check, and the setter and getter of a 4-byte column -----
     def _row_range(self, what: str, row0, n) -> Tuple[int, int]:

@@ -45,7 +45,7 @@ class ShardedFlatIndex:
     """``IndexFlat`` semantics over ``world`` row shards.
 
     ``local_index`` must offer ``ntotal``, ``add(x, normalize=)``, ``add_synthetic``, ``set_id_base`` and
-    ``search_dev``/``search`` (``range_search`` for ``range_search``, ``reconstruct_n`` for ``search_by_ids`` and ``search_diverse``; ``kmeans_step``, ``bounds`` and ``reconstruct_batch`` for ``kmeans``; ``subset_terms`` and ``term_stats`` for ``significant_terms``); ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
+    ``search_dev``/``search`` (``range_search`` for ``range_search``, ``reconstruct_n`` for ``search_by_ids`` and ``search_diverse``; ``kmeans_step``, ``bounds`` and ``reconstruct_batch`` for ``kmeans``; ``subset_terms`` and ``term_stats`` for ``significant_terms``; ``facets`` for ``facets``); ``merge`` merges ``[world, nq, k]`` candidate tensors.  Defaults are the HIP
     implementations; tests substitute doubles.
     """
 
@@ -393,6 +393,42 @@ class ShardedFlatIndex:
         out_lims = np.zeros(nq + 1, dtype=np.int64)
         np.cumsum(all_counts.sum(axis=0), out=out_lims[1:])
         return out_lims, np.ascontiguousarray(scores[order]), np.ascontiguousarray(ids[order])
+
+    # -- facet counts ------------------------------------------------------------------------------------------
+    def facets(self, q, thresh: float, buckets=None, nbuckets: Optional[int] = None, normalize: bool = False, allow=None):
+        """``IndexFlat.facets`` over the shards (collective: every rank passes the same arguments): a ``FacetCounts``
+        with global ids on every rank.  ``buckets`` and ``allow`` are in GLOBAL numbering and are cut per shard through
+        the segment table, as ``set_groups`` and ``_local_allow`` do (``buckets=None``: the labels ``set_groups``
+        stored); tombstones are left out.  Every rank counts its shard, then ONE sum all-reduce adds
+        ``counts | total | unbucketed`` (int64) and ONE all-gather moves every rank's ``(best_score, best global id)``
+        per entry, merged by best score, then smaller global id.  A row's score is its own fp32 chain wherever it lies
+        and counts are integers, so the result equals the unsharded one byte for byte.  With one rank there is no
+        exchange."""
+        from .flat_index import FacetCounts, facet_args
+
+        qa = self._queries(q)
+        thresh, b, nb = facet_args(thresh, buckets, nbuckets, self.ntotal_global)
+        loc = self.local.facets(qa, thresh, buckets=None if b is None else self.local_rows_of(b), nbuckets=nb,
+                                normalize=normalize, allow=self._local_allow(allow))
+        counts, total, unb = (np.ascontiguousarray(a, dtype=np.int64) for a in (loc.counts, loc.total, loc.unbucketed))
+        S = np.ascontiguousarray(loc.best_score, dtype=np.float32)
+        I = np.ascontiguousarray(self._to_global_np(np.asarray(loc.best_id, dtype=np.int64)))
+        if self._single() or qa.shape[0] == 0:
+            return FacetCounts(counts, S, I, total, unb)
+        n, nq = counts.size, qa.shape[0]
+        sums = self._sum_over_ranks(np.concatenate([counts.reshape(-1), total, unb]))
+        send = np.empty(12 * n, dtype=np.uint8)   # [n int64 ids][n float32 scores]
+        send[:8 * n] = I.reshape(-1).view(np.uint8)
+        send[8 * n:] = S.reshape(-1).view(np.uint8)
+        recv = self._all_gather_host(send)
+        Ig = np.stack([recv[r, :8 * n].view(np.int64) for r in range(self.world)], axis=1)      # [n, world]
+        Sg = np.stack([recv[r, 8 * n:].view(np.float32) for r in range(self.world)], axis=1)
+        # per entry: the shards that have a hit first, then best score (IP descending, L2 ascending), then smaller id
+        first = np.lexsort((Ig, -Sg if self.metric == 0 else Sg, Ig < 0), axis=1)[:, :1]
+        return FacetCounts(np.ascontiguousarray(sums[:n].reshape(nq, nb)),
+                           np.ascontiguousarray(np.take_along_axis(Sg, first, axis=1).reshape(nq, nb)),
+                           np.ascontiguousarray(np.take_along_axis(Ig, first, axis=1).reshape(nq, nb)),
+                           np.ascontiguousarray(sums[n:n + nq]), np.ascontiguousarray(sums[n + nq:]))
 
     # -- grouped search ----------------------------------------------------------------------------------------
     def set_groups(self, global_labels, row0: int = 0) -> None:
@@ -855,6 +891,10 @@ class ShardedIndexFacade:
 
     def significant_terms(self, allow=None, m: int = 20, min_count: int = 2, background=None):
         return self.sh.significant_terms(allow=allow, m=m, min_count=min_count, background=background)
+
+    def facets(self, q, thresh: float, buckets=None, nbuckets=None, normalize: bool = False, allow=None):
+        return self.sh.facets(np.asarray(q, dtype=np.float32), float(thresh), buckets=buckets, nbuckets=nbuckets,
+                              normalize=normalize, allow=allow)
 
     def search_hybrid(self, q, terms, weights, k: int, alpha: float, k1: float = 1.2, b: float = 0.75,
                       avgdl: Optional[float] = None, normalize: bool = False, allow=None):

@@ -113,6 +113,24 @@ class Keyword:
 
 
 @dataclass
+class Facet:
+    """One bucket of ``HybridStorage.facets``: the value the chunks share (a column value, or the ISO date of the first
+    day of a day / week / month), the number of matching chunks, and the best of them."""
+    value: Any
+    count: int
+    best: SearchResult
+
+
+@dataclass
+class Facets:
+    """What ``HybridStorage.facets`` returns: all matching chunks, those among them without a value for the facet
+    (``missing``), and the non-empty buckets, largest first."""
+    total: int
+    missing: int
+    buckets: List[Facet]
+
+
+@dataclass
 class MapPoint:
     """One chunk of ``HybridStorage.map``: its coordinates on the first two principal components of the selection, and
     its k-means topic under the same selection (``None`` when no topics were asked for)."""
@@ -229,6 +247,55 @@ def timestamp_days(ts) -> float:
         return float("nan")
 
 
+def strict_radius(threshold: float, similarity: bool) -> np.float32:
+    """The float32 radius that makes the index's STRICT comparison mean ``>= threshold`` (``similarity``: inner
+    product, ``score > radius``) or ``<= threshold`` (squared L2, ``dist < radius``) for every float32 score: the
+    float32 next to the threshold on the far side.  ``search_range`` and ``facets`` share it."""
+    thr = float(threshold)
+    with np.errstate(over="ignore"):   # (a threshold beyond float32 ends at +-inf, which is the right radius)
+        t32 = np.float32(thr)
+        if similarity:
+            # score >= thr  <=>  score >= (smallest float32 >= thr)  <=>  score > the float32 below that one
+            if float(t32) < thr:
+                t32 = np.nextafter(t32, np.float32(np.inf))
+            return np.nextafter(t32, np.float32(-np.inf))
+        if float(t32) > thr:
+            t32 = np.nextafter(t32, np.float32(-np.inf))
+        return np.nextafter(t32, np.float32(np.inf))
+
+
+FACET_COLUMNS = ("project_name", "session_id", "chunk_type", "has_code", "has_tools")
+FACET_DATES = ("day", "week", "month")
+
+
+def facet_date_key(days: float, by: str) -> Optional[int]:
+    """The bucket of a timestamp (``timestamp_days``; NaN: ``None``) under ``by`` = day / week / month, as an integer:
+    the floored day number, the day number of the week's Monday, or ``year * 12 + month - 1`` (all UTC)."""
+    if days != days:
+        return None
+    day = int(np.floor(days))
+    if by == "day":
+        return day
+    if by == "week":
+        return (day + 3) // 7 * 7 - 3   # (day 0, 1970-01-01, was a Thursday)
+    d = datetime.fromtimestamp(day * 86400.0, tz=timezone.utc)
+    return d.year * 12 + d.month - 1
+
+
+def facet_date_value(key: int, by: str) -> str:
+    """The ISO date of the first day of the bucket ``facet_date_key`` named."""
+    if by == "month":
+        return f"{key // 12:04d}-{key % 12 + 1:02d}-01"
+    return datetime.fromtimestamp(key * 86400.0, tz=timezone.utc).date().isoformat()
+
+
+def order_facets(buckets: List[Facet], similarity: bool, top: Optional[int] = None) -> List[Facet]:
+    """The order of ``HybridStorage.facets``: count descending, then the better best hit (``similarity``: larger;
+    squared distance: smaller), then the value; cut to ``top`` when given."""
+    out = sorted(buckets, key=lambda f: (-f.count, -f.best.similarity if similarity else f.best.similarity, f.value))
+    return out if top is None else out[:max(int(top), 0)]
+
+
 class _Synced:
     """Which rows of WHICH index object already carry a per-row column that is pushed lazily, in front of the search
     that reads it (session labels, recency priors, term lists).  A fresh one is synced with no index."""
@@ -263,6 +330,7 @@ class HybridStorage:
         self._lock = threading.RLock()
         self._saved_rows = -1  # rows known to be in index_path (-1: unknown)
         self._allow_cache: Dict[str, Any] = {}  # filter key -> (stamp, allow mask); push-down only
+        self._facet_cache: Dict[str, Any] = {}  # facets: by -> (stamp, bucket ids, values)
         self._mutations = 0  # bumped by every change of the chunk set (part of the allow-cache stamp)
         # the lazily pushed columns of search_sessions (labels), search_recent (priors) and search_hybrid (term lists)
         self._labels, self._priors, self._terms = _Synced(), _Synced(), _Synced()
@@ -982,21 +1050,94 @@ class HybridStorage:
             if frame is None:
                 return []
             _, ntotal, q = frame
-            with np.errstate(over="ignore"):
-                t32 = np.float32(thr)
-            if self.config.normalize_embeddings:
-                # score >= thr  <=>  score >= (smallest float32 >= thr)  <=>  score > the float32 below that one
-                if float(t32) < thr:
-                    t32 = np.nextafter(t32, np.float32(np.inf))
-                radius = np.nextafter(t32, np.float32(-np.inf))
-            else:
-                if float(t32) > thr:
-                    t32 = np.nextafter(t32, np.float32(-np.inf))
-                radius = np.nextafter(t32, np.float32(np.inf))
+            radius = strict_radius(thr, bool(self.config.normalize_embeddings))
             allow = self._allow_for(filters, ntotal, tombstones_always=False)
             _, sims, ids = self.faiss_index.range_search(q, float(radius), normalize=self.config.normalize_embeddings,
                                                          allow=allow)
             return self._results_in_rank_order(sims.tolist(), ids.tolist(), cfg, filters, unbounded=True, limit=limit)
+
+    def _facet_buckets(self, by: str, ntotal: int):
+        """``(ids, values)`` of a facet over a column or a date unit: ``ids`` int32 ``[ntotal]``, the dense bucket of
+        every index row in order of first appearance, ``-1`` for a row whose value is NULL (or whose timestamp does not
+        parse) and for a row without a live chunk; ``values[b]`` what bucket ``b`` stands for.  One pass over the
+        chunks table, cached per ``by`` under the stamp of ``_allow_mask``."""
+        stamp = (self._mutations, len(self.faiss_id_to_chunk_id), ntotal, self.total_chunks)
+        hit = self._facet_cache.get(by)
+        if hit is not None and hit[0] == stamp:
+            return hit[1], hit[2]
+        if not self.db:
+            raise RuntimeError("Database not initialized")
+        ids = np.full(ntotal, -1, dtype=np.int32)
+        dense: Dict[Any, int] = {}
+        column = "timestamp" if by in FACET_DATES else by
+        for cid, value in self.db.cursor().execute(f"SELECT id, {column} FROM chunks"):
+            fid = self.chunk_id_to_faiss_id.get(cid)
+            if fid is None or fid >= ntotal or self.faiss_id_to_chunk_id.get(fid) != cid:
+                continue
+            if by in FACET_DATES:
+                value = facet_date_key(timestamp_days(value), by)
+            elif value is not None and by in ("has_code", "has_tools"):
+                value = bool(value)
+            if value is not None:
+                ids[fid] = dense.setdefault(value, len(dense))
+        values = [facet_date_value(v, by) for v in dense] if by in FACET_DATES else list(dense)
+        self._facet_cache[by] = (stamp, ids, values)
+        return ids, values
+
+    def facets(self, query_embedding, by: str = "project_name", threshold: Optional[float] = None,
+               filters: Optional[Dict[str, Any]] = None, config: Optional[SearchConfig] = None,
+               top: Optional[int] = None) -> Facets:
+        """Where the matches of a query lie: the live chunks with ``similarity >= threshold`` (default
+        ``config.similarity_threshold``; an L2 storage: ``distance <= threshold``, as in ``search_range``, made exact
+        through the neighbouring float32) that match ``filters``, COUNTED per value of ``by`` inside the index
+        (``IndexFlat.facets``: a histogram, no hit list) -- the distribution behind the ``project`` / ``session`` /
+        date filters.  ``by`` is a column (``project_name``, ``session_id``, ``chunk_type``, ``has_code``,
+        ``has_tools``) or a date unit (``day``, ``week`` starting Monday, ``month``; the chunk's ``timestamp`` in UTC,
+        reported as the ISO date of the bucket's first day); anything else raises ``ValueError``.
+
+        Returns ``Facets(total, missing, buckets)``: all matching chunks, those without a value (NULL column, no or
+        unparseable timestamp), and one ``Facet(value, count, best)`` per non-empty bucket -- ``best`` the best matching
+        chunk of the bucket as ``search()`` would report it under ``config`` -- ordered by count descending, then the
+        better best hit, then value, cut to ``top`` when given.
+
+        Tombstones are always masked, and ``filters`` ALWAYS go into the allow mask, whatever ``filter_pushdown`` says:
+        a count cannot be filtered afterwards.  ``session_id`` counts over the stored session labels of
+        ``search_sessions`` and uploads nothing; every other ``by`` uploads its bucket column (4 bytes per row) with
+        the call.  More than ``MAX_FACET_BUCKETS`` distinct values raise ``ValueError``; an index object without
+        ``facets`` raises ``NotImplementedError``."""
+        if by not in FACET_COLUMNS + FACET_DATES:
+            raise ValueError(f"facets: by={by!r} is not one of {', '.join(FACET_COLUMNS + FACET_DATES)}")
+        cfg = config or SearchConfig()
+        thr = float(cfg.similarity_threshold if threshold is None else threshold)
+        if thr != thr:
+            raise ValueError("facets: the threshold is NaN")
+        self._require("facet counts", "facets", *(("set_groups",) if by == "session_id" else ()))
+        with self._lock:
+            frame = self._search_frame(cfg, query_embedding)
+            if frame is None:
+                return Facets(0, 0, [])
+            _, ntotal, q = frame
+            similarity = bool(self.config.normalize_embeddings)
+            radius = strict_radius(thr, similarity)
+            if by == "session_id":
+                self._sync_session_labels(ntotal)
+                ids, values = None, list(self._session_labels)   # (label = position: dense in order of first appearance)
+            else:
+                ids, values = self._facet_buckets(by, ntotal)
+            if len(values) > fi.MAX_FACET_BUCKETS:
+                raise ValueError(f"facets: by={by!r} has {len(values)} distinct values, more than {fi.MAX_FACET_BUCKETS}")
+            allow = self._allow_mask(filters or {}, ntotal)
+            res = self.faiss_index.facets(q, float(radius), buckets=ids, nbuckets=max(len(values), 1),
+                                          normalize=self.config.normalize_embeddings,
+                                          allow=None if bool(allow.all()) else allow)
+            out = []
+            for b in np.flatnonzero(res.counts[0] > 0).tolist():
+                chunk_id = self.faiss_id_to_chunk_id.get(int(res.best_id[0, b]))
+                data = self._get_chunk_data(chunk_id) if chunk_id else None
+                if data:
+                    out.append(Facet(values[b], int(res.counts[0, b]),
+                                     self._make_result(chunk_id, float(res.best_score[0, b]), data, cfg)))
+            return Facets(int(res.total[0]), int(res.unbucketed[0]), order_facets(out, similarity, top))
 
     def _allow_mask(self, filters: Dict[str, Any], ntotal: int) -> np.ndarray:
         """Boolean mask over index rows: live (not tombstoned) and matching ``filters`` under exactly the

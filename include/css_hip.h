@@ -13,6 +13,7 @@
  *   q / (norm + 1e-8), reshape(1,-1)         src/storage.py:424-429  -> css_index_search(normalize_q=1)
  *   faiss_index.search(q, k) -> (D, I)       src/storage.py:436      -> css_index_search
  *   faiss_index.range_search(q, r)           (not called by the reference) -> css_index_range_search
+ *   (no faiss call: facet counts per query)  (not called by the reference) -> css_index_facets
  *   faiss.write_index / read_index payload   src/storage.py:306,879  -> css_index_export / css_index_add
  *   faiss.index_cpu_to_gpu / get_num_gpus    src/storage.py:283, src/gpu_utils.py:117-118
  *                                                                    -> css_device_count / css_device_info
@@ -590,6 +591,43 @@ int css_index_range_search(css_index* ix, const float* q_host, int64_t nq, float
 int css_range_result_lims(const css_range_result* r, int64_t* lims_host);
 int css_range_result_read(const css_range_result* r, float* D_host, int64_t* I_host);
 int css_range_result_free(css_range_result* r);
+
+/* Facet counts (Elasticsearch's terms / date_histogram aggregations, Qdrant's facet API, Vespa grouping): per query,
+ * how many rows within the radius fall into each bucket of a per-row int32 column, and the best such row per bucket.
+ * The reference answers "which projects / sessions exist" only without a query (get_stats, src/storage.py:654;
+ * get_all_projects, :721), yet its search filters --project / --after / --before / --session (src/cli.py:338-342) can
+ * only be set well after seeing where the matches of a query lie; this call is that distribution.
+ *  - A row hits query j when score > radius (inner product) / squared distance < radius (L2): strict, NaN never, the
+ *    predicate and the fp32 sweep of css_index_range_search -- a row hits here exactly when it hits there, with the
+ *    same float.  Nothing depends on the reduced-precision row copies or on the search mode.
+ *  - The bucket of row r is buckets_host[r] (a per-call column in LOCAL row numbering, uploaded on every call into a
+ *    kept workspace, never stored) or, with buckets_host == NULL, the row's group label (css_index_set_groups; no
+ *    upload).  A hit with bucket b in [0, nbuckets) counts in count_out[j * nbuckets + b]; every other hit (negative
+ *    label, b >= nbuckets, or labels that were never set) counts in unbucketed_out[j] only; total_out[j] counts all
+ *    hits: total = sum_b count + unbucketed.
+ *  - best_score_out / best_id_out (either may be NULL): the best hit of the bucket -- best score, equal scores to the
+ *    smallest id; ids are global (id_base added) as css_index_range_search's.  An empty bucket has count 0, id -1 and
+ *    the score css_index_search pads with (-FLT_MAX inner product, +FLT_MAX L2).
+ *  - Counts and keys are integers combined by atomic add and max only, so the answer is the same bytes on every run
+ *    and whatever the placement of the table.  No hit list exists at any point: no pool, no second sweep, no sort.
+ *  - One sweep of the rows serves min(16, the queries whose rows fit 64 KiB of LDS, 2^20 / nbuckets) queries; its
+ *    table (at most 2^20 entries of 12 bytes) lives in a workspace of the index, is zeroed before and copied back
+ *    after the sweep, and is decoded on the host side of the library.
+ *  - nq in [0, 2^24); 1 <= nbuckets <= CSS_MAX_FACET_BUCKETS; a NaN radius is CSS_ERR_INVALID, +-inf is legal (IP
+ *    radius -inf counts every allowed row); fewer than 2^32 - 1 rows.  nq == 0 writes nothing; an empty index answers
+ *    zero counts and empty slots without a launch.  normalize_q, allow_bits_host (may be NULL), rows appended on other
+ *    streams and the shared workspaces behave as for css_index_search_masked.  A failed allocation (table, column or
+ *    host memory) is CSS_ERR_OOM and leaves the index as it was.
+ *  - css_index_last_facet_sweeps: sweeps of the last call, and how many of them kept their table in LDS.
+ *  - css_index_set_facet_lds_entries: the largest table (queries x buckets of one sweep) that goes to LDS; -1 (default)
+ *    the library's rule, 0 never.  A table that does not fit the 160 KB of a CU beside the query rows
+ *    goes to global memory whatever is set.  For measurements and tests; the answer does not depend on it. */
+#define CSS_MAX_FACET_BUCKETS (1 << 20)
+int css_index_facets(css_index* ix, const float* q_host, int64_t nq, float radius, int normalize_q,
+                     const uint32_t* allow_bits_host, const int32_t* buckets_host, int64_t nbuckets, int64_t* count_out,
+                     float* best_score_out, int64_t* best_id_out, int64_t* total_out, int64_t* unbucketed_out);
+int css_index_last_facet_sweeps(css_index* ix, int64_t* sweeps, int64_t* lds_sweeps);
+int css_index_set_facet_lds_entries(css_index* ix, int64_t entries);
 
 /* Merge `nparts` per-shard results ([nparts, nq, k] each) into the global
  * top-k by (score, id); used after the RCCL all-gather of per-shard top-k. */
