@@ -47,6 +47,9 @@ _LAZY = {
     "SignificantTerms": ".lexical",
     "words_of_terms": ".lexical",
     "MpnetEncoder": ".mpnet_encoder",
+    "Passage": ".passages",
+    "split_passages": ".passages",
+    "pack_passages": ".passages",
     "ShardedFlatIndex": ".sharded",
     "GPUCapability": ".gpu_utils",
     "assess_gpu_capability": ".gpu_utils",

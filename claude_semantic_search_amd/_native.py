@@ -164,6 +164,10 @@ PROTOTYPES = {
     "css_encoder_export_weight": (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),
     "css_encoder_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "css_encoder_forward_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "css_encoder_forward_spans": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                          c_void_p, c_void_p]),
+    "css_encoder_forward_spans_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                              c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "css_encoder_debug_read": (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),
     "css_encoder_set_attention_range": (c_int, [c_void_p, c_float]),
     "css_mpnet_rel_bucket": (c_int, [c_int, c_int, c_int]),

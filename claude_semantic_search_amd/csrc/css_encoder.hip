@@ -120,6 +120,11 @@ struct css_encoder {
     float att_range = 1.2676506e30f;                 // 2^100: row-sum range of the reference-free softmax pass (attn_pass); 0 = always the SAFE pass
     int32_t *ids_dev = nullptr, *cu_dev = nullptr;
     float* out_dev = nullptr;
+    // css_encoder_forward_spans: span table [S][3], span rows [S, H], scores [S], query [H].  Grow-only and apart from
+    // the buffers above: no captured graph holds one of these pointers, so growing them leaves the graphs alone.
+    int cap_spans = 0;
+    int32_t* spans_dev = nullptr;
+    float *span_out_dev = nullptr, *span_scores_dev = nullptr, *span_q_dev = nullptr;
     // hipGraph cache for the launch-bound tiny-batch path (generate_single_embedding): key =
     // (B, T, max_len, normalize); a key is run eagerly once, captured on its second use, replayed after
     struct GraphEntry {
@@ -337,6 +342,26 @@ int ensure_acts(css_encoder* e, int T, int B) {
         CSS_HIP_TRY(hipMalloc((void**)&e->out_dev, cap * H * 4));
         e->cap_seqs = (int)cap;
     }
+    return CSS_OK;
+}
+
+// Buffers of css_encoder_forward_spans (host entry point).  The stream is idle between calls (every host entry point
+// ends with a synchronise), so the old buffers can be freed at once.
+int ensure_spans(css_encoder* e, int S) {
+    const size_t H = e->cfg.hidden;
+    if (!e->span_q_dev) CSS_HIP_TRY(hipMalloc((void**)&e->span_q_dev, H * 4));
+    if (S <= e->cap_spans) return CSS_OK;
+    void* ptrs[] = {e->spans_dev, e->span_out_dev, e->span_scores_dev};
+    for (void* p : ptrs)
+        if (p) CSS_HIP_TRY(hipFree(p));
+    e->spans_dev = nullptr;
+    e->span_out_dev = e->span_scores_dev = nullptr;
+    e->cap_spans = 0;
+    const size_t cap = (size_t)S + (size_t)S / 2 + 64;
+    CSS_HIP_TRY(hipMalloc((void**)&e->spans_dev, cap * 3 * sizeof(int32_t)));
+    CSS_HIP_TRY(hipMalloc((void**)&e->span_out_dev, cap * H * 4));
+    CSS_HIP_TRY(hipMalloc((void**)&e->span_scores_dev, cap * 4));
+    e->cap_spans = (int)cap;
     return CSS_OK;
 }
 
@@ -637,6 +662,47 @@ int forward_any(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, in
                                : forward_typed<float, 768>(e, ids, cu, B, T, max_len, normalize, out, st);
 }
 
+// One pooled row per span over the token rows that the forward just enqueued on `st` left behind: x32 on the unfolded
+// paths, the last pre tensor + its row statistics on the LayerNorm-folded one (pre[0] = x16, stats[0]: the pooling
+// kernels only read them).  One launch.
+int pool_spans(css_encoder* e, const int32_t* cu, int B, const int32_t* spans, int S, const float* q, int normalize,
+               float* span_out, float* scores, hipStream_t st) {
+    if (S == 0 || (!span_out && !scores)) return CSS_OK;
+    const css_encoder_cfg& c = e->cfg;
+    if (!scores) q = nullptr;
+    ProfScope ps("enc_span_pool", st);
+    if (!e->x32_valid) {
+        const LayerW& L = e->layers.back();
+        hipLaunchKernelGGL(k_span_pool_ln<768>, dim3(S), dim3(256), 0, st, (const bf16_t*)e->x16, e->stats[0], L.ln2g, L.ln2b,
+                           1.0f / c.hidden, c.ln_eps, cu, B, spans, normalize, q, span_out, scores);
+    } else if (c.hidden == 384) {
+        hipLaunchKernelGGL(k_span_pool<384>, dim3(S), dim3(256), 0, st, e->x32, cu, B, spans, normalize, q, span_out, scores);
+    } else {
+        hipLaunchKernelGGL(k_span_pool<768>, dim3(S), dim3(256), 0, st, e->x32, cu, B, spans, normalize, q, span_out, scores);
+    }
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// Shape checks of a packed host batch (css_encoder_forward, css_encoder_forward_spans); *max_len = the longest sequence.
+int check_batch(const css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int* max_len) {
+    CSS_REQUIRE(B >= 1, "css_encoder_forward: B < 1");
+    CSS_REQUIRE(cu[0] == 0, "css_encoder_forward: cu_seqlens[0] must be 0");
+    int ml = 0;
+    for (int b = 0; b < B; ++b) {
+        const int len = cu[b + 1] - cu[b];
+        CSS_REQUIRE(len >= 1 && len <= e->cfg.max_seq_len, "css_encoder_forward: sequence %d has length %d outside [1, %d]", b,
+                    len, e->cfg.max_seq_len);
+        ml = len > ml ? len : ml;
+    }
+    const int T = cu[B];
+    for (int t = 0; t < T; ++t)
+        CSS_REQUIRE(ids[t] >= 0 && ids[t] < e->cfg.vocab && ids[t] != e->cfg.pad_id,
+                    "css_encoder_forward: token %d has id %d (outside the vocabulary or the pad id)", t, ids[t]);
+    *max_len = ml;
+    return CSS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -710,7 +776,8 @@ int css_encoder_free(css_encoder* e) {
             if (p) (void)hipFree(p);
     }
     void* ptrs[] = {e->bias_tab, e->bucket_dev, e->x32, e->pre32, e->x16, e->qkv, e->ctx, e->ffn, e->ids_dev,
-                    e->cu_dev, e->out_dev, e->stats[0], e->stats[1]};
+                    e->cu_dev, e->out_dev, e->stats[0], e->stats[1], e->spans_dev, e->span_out_dev, e->span_scores_dev,
+                    e->span_q_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -844,22 +911,13 @@ int css_encoder_debug_read(css_encoder* e, const char* what, float* out_host, in
 
 int css_encoder_forward(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int normalize, float* out) {
     CSS_REQUIRE(e && ids && cu && out, "css_encoder_forward: NULL argument");
-    CSS_REQUIRE(B >= 1, "css_encoder_forward: B < 1");
-    CSS_REQUIRE(cu[0] == 0, "css_encoder_forward: cu_seqlens[0] must be 0");
     int max_len = 0;
-    for (int b = 0; b < B; ++b) {
-        const int len = cu[b + 1] - cu[b];
-        CSS_REQUIRE(len >= 1 && len <= e->cfg.max_seq_len, "css_encoder_forward: sequence %d has length %d outside [1, %d]", b,
-                    len, e->cfg.max_seq_len);
-        max_len = len > max_len ? len : max_len;
-    }
+    int rc = check_batch(e, ids, cu, B, &max_len);
+    if (rc != CSS_OK) return rc;
     const int T = cu[B];
-    for (int t = 0; t < T; ++t)
-        CSS_REQUIRE(ids[t] >= 0 && ids[t] < e->cfg.vocab && ids[t] != e->cfg.pad_id,
-                    "css_encoder_forward: token %d has id %d (outside the vocabulary or the pad id)", t, ids[t]);
     std::lock_guard<std::mutex> lk(e->mu);
     DeviceGuard g(e->device);
-    int rc = ensure_acts(e, T, B);
+    rc = ensure_acts(e, T, B);
     if (rc != CSS_OK) return rc;
     CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, e->stream));
     CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, e->stream));
@@ -908,6 +966,60 @@ int css_encoder_forward_dev(css_encoder* e, const int32_t* ids_dev, const int32_
     int rc = ensure_acts(e, total_tokens, B);
     if (rc != CSS_OK) return rc;
     return forward_any(e, ids_dev, cu_dev, B, total_tokens, max_len, normalize, out_dev, (hipStream_t)stream);
+}
+
+int css_encoder_forward_spans(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, const int32_t* spans, int S,
+                              const float* q, int normalize, float* seq_out, float* span_out, float* scores_out) {
+    CSS_REQUIRE(e && ids && cu, "css_encoder_forward_spans: NULL argument");
+    CSS_REQUIRE(S >= 0 && (S == 0 || spans), "css_encoder_forward_spans: S=%d is negative, or spans is NULL", S);
+    CSS_REQUIRE((q != nullptr) == (scores_out != nullptr), "css_encoder_forward_spans: q and scores_out go together");
+    int max_len = 0;
+    int rc = check_batch(e, ids, cu, B, &max_len);
+    if (rc != CSS_OK) return rc;
+    for (int s = 0; s < S; ++s) {
+        const int b = spans[3 * s], lo = spans[3 * s + 1], hi = spans[3 * s + 2];
+        CSS_REQUIRE(b >= 0 && b < B, "css_encoder_forward_spans: span %d names sequence %d outside [0, %d)", s, b, B);
+        const int len = cu[b + 1] - cu[b];
+        CSS_REQUIRE(lo >= 0 && lo < hi && hi <= len,
+                    "css_encoder_forward_spans: span %d is [%d, %d) of sequence %d: need 0 <= begin < end <= %d", s, lo, hi, b, len);
+    }
+    const int T = cu[B];
+    const size_t H = e->cfg.hidden;
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard g(e->device);
+    if ((rc = ensure_acts(e, T, B)) != CSS_OK || (rc = ensure_spans(e, S)) != CSS_OK) return rc;
+    hipStream_t st = e->stream;
+    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
+    if (S) CSS_HIP_TRY(hipMemcpyAsync(e->spans_dev, spans, (size_t)S * 12, hipMemcpyHostToDevice, st));
+    if (q) CSS_HIP_TRY(hipMemcpyAsync(e->span_q_dev, q, H * 4, hipMemcpyHostToDevice, st));
+    // eager launches (the tiny-batch graphs replay css_encoder_forward only)
+    if ((rc = forward_any(e, e->ids_dev, e->cu_dev, B, T, max_len, normalize, e->out_dev, st)) != CSS_OK) return rc;
+    if ((rc = pool_spans(e, e->cu_dev, B, e->spans_dev, S, q ? e->span_q_dev : nullptr, normalize,
+                         span_out ? e->span_out_dev : nullptr, scores_out ? e->span_scores_dev : nullptr, st)) != CSS_OK)
+        return rc;
+    if (seq_out) CSS_HIP_TRY(hipMemcpyAsync(seq_out, e->out_dev, (size_t)B * H * 4, hipMemcpyDeviceToHost, st));
+    if (span_out && S) CSS_HIP_TRY(hipMemcpyAsync(span_out, e->span_out_dev, (size_t)S * H * 4, hipMemcpyDeviceToHost, st));
+    if (scores_out && S) CSS_HIP_TRY(hipMemcpyAsync(scores_out, e->span_scores_dev, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    return CSS_OK;
+}
+
+int css_encoder_forward_spans_dev(css_encoder* e, const int32_t* ids_dev, const int32_t* cu_dev, int B, int total_tokens,
+                                  int max_len, const int32_t* spans_dev, int S, const float* q_dev, int normalize,
+                                  float* seq_out_dev, float* span_out_dev, float* scores_out_dev, void* stream) {
+    CSS_REQUIRE(e && ids_dev && cu_dev, "css_encoder_forward_spans_dev: NULL argument");
+    CSS_REQUIRE(S >= 0 && (S == 0 || spans_dev), "css_encoder_forward_spans_dev: S=%d is negative, or spans is NULL", S);
+    CSS_REQUIRE((q_dev != nullptr) == (scores_out_dev != nullptr), "css_encoder_forward_spans_dev: q and scores_out go together");
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard g(e->device);
+    int rc = ensure_acts(e, total_tokens, B);
+    if (rc != CSS_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // (seq_out NULL: the sequence rows go to the encoder's own buffer)
+    if ((rc = forward_any(e, ids_dev, cu_dev, B, total_tokens, max_len, normalize, seq_out_dev ? seq_out_dev : e->out_dev, st)) != CSS_OK)
+        return rc;
+    return pool_spans(e, cu_dev, B, spans_dev, S, q_dev, normalize, span_out_dev, scores_out_dev, st);
 }
 
 }  // extern "C"

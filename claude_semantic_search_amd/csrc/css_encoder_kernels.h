@@ -1855,28 +1855,24 @@ __global__ __launch_bounds__(256) void k_pool_partial(const float* __restrict__ 
 
 // LayerNorm-folded path: the rows are the last pre tensor (bf16) + its row statistics; the last LayerNorm is applied
 // on the way:  sum_t LN(p_t)[c] = gamma[c] * sum_t (p_t[c] rs_t - mu_t rs_t) + n beta[c].
+//
+// pool_ln_rows: the blocked read of that sum, shared by k_pool_partial_ln and k_span_pool_ln.  For the GLOBAL token
+// numbers [tb, te) it leaves red[q][c] = sum over the tokens t with t % 16 == q of (p_t[c] rs_t - mu_t rs_t), tokens in
+// ascending order, and ends with a block barrier; pool_ln_col adds the 16 classes of a column in a fixed order.
+// Blocked layout (preblk_elem): thread (lq = tid & 15, g = tid >> 4) reads the 16-byte pieces g, g + 16, ... of the
+// tokens t with t % 16 == lq, so 16 consecutive lanes read 256 contiguous bytes.  256 threads.
 template <int H>
-__global__ __launch_bounds__(256) void k_pool_partial_ln(const bf16_t* __restrict__ pre, const long long* __restrict__ stats,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         float inv_h, float eps, const int32_t* __restrict__ cu, int S,
-                                                         float* __restrict__ part) {
-    // Blocked layout (preblk_elem): thread (lq = tid & 15, g = tid >> 4) reads the 16-byte pieces g, g + 16, ... of the
-    // tokens t with t % 16 == lq, so 16 consecutive lanes read 256 contiguous bytes; the 16 token classes are summed in a
-    // fixed order at the end.
+__device__ __forceinline__ void pool_ln_rows(const bf16_t* __restrict__ pre, const long long* __restrict__ stats, float inv_h,
+                                             float eps, int tb, int te, float (&red)[16][H + 8]) {
     static_assert(H % 128 == 0, "6 pieces per thread");
     constexpr int NP = H / 8, PT = NP / 16;   // pieces per token row / per thread
-    __shared__ float red[16][H + 8];
-    const int b = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int lq = tid & 15, g = tid >> 4;
-    const int t0 = cu[b], L = cu[b + 1] - t0;
-    const int per = (L + S - 1) / S;
-    const int lo = min(L, sl * per), hi = min(L, lo + per);
     float acc[PT][8];
 #pragma unroll
     for (int i = 0; i < PT; ++i)
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[i][e] = 0.f;
-    const int tb = t0 + lo, te = t0 + hi;
     for (int t = (tb & ~15) + lq; t < te; t += 16) {
         if (t < tb) continue;
         const v4u32 raw = *reinterpret_cast<const v4u32*>(stats + (size_t)t * 2);
@@ -1907,12 +1903,28 @@ __global__ __launch_bounds__(256) void k_pool_partial_ln(const bf16_t* __restric
         }
     }
     __syncthreads();
-    for (int c = tid; c < H; c += 256) {
-        float a = 0.f;
+}
+template <int H>
+__device__ __forceinline__ float pool_ln_col(const float (&red)[16][H + 8], int c) {
+    float a = 0.f;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) a += red[i][c];
-        part[((size_t)b * S + sl) * H + c] = fmaf(a, gamma[c], (float)(hi - lo) * beta[c]);
-    }
+    for (int i = 0; i < 16; ++i) a += red[i][c];
+    return a;
+}
+
+template <int H>
+__global__ __launch_bounds__(256) void k_pool_partial_ln(const bf16_t* __restrict__ pre, const long long* __restrict__ stats,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                         float inv_h, float eps, const int32_t* __restrict__ cu, int S,
+                                                         float* __restrict__ part) {
+    __shared__ float red[16][H + 8];
+    const int b = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    const int t0 = cu[b], L = cu[b + 1] - t0;
+    const int per = (L + S - 1) / S;
+    const int lo = min(L, sl * per), hi = min(L, lo + per);
+    pool_ln_rows<H>(pre, stats, inv_h, eps, t0 + lo, t0 + hi, red);
+    for (int c = tid; c < H; c += 256)
+        part[((size_t)b * S + sl) * H + c] = fmaf(pool_ln_col<H>(red, c), gamma[c], (float)(hi - lo) * beta[c]);
 }
 
 template <int H>
@@ -1999,6 +2011,119 @@ __global__ __launch_bounds__(256) void k_pool_cls_ln(const bf16_t* __restrict__ 
         v[i] = c < H ? fmaf(gamma[c], fmaf(bf2f(pre[preblk_elem(t, c, H)]), rs, -mrs), beta[c]) : 0.f;
     }
     cls_pool_write<H>(v, normalize, out + (size_t)b * H);
+}
+
+// ---------------------------------------------------------------- span pooling
+// css_encoder_forward_spans: one pooled row per SPAN (sequence b, begin, end) of token rows -- always the masked MEAN of
+// the final hidden states of tokens begin..end-1, also for a CLS-pooling model.  One block per span, 256 threads, thread
+// tid owns columns tid + 256 i; every sum has a fixed order, so the same call gives the same bits.
+//
+// span_range: global token numbers [tb, te) of span s.  The host entry point validates its table before anything is
+// enqueued; the clamps keep the reads of a table that the caller of the _dev entry point did not validate inside the batch.
+__device__ __forceinline__ void span_range(const int32_t* __restrict__ spans, const int32_t* __restrict__ cu, int B, int s,
+                                           int& tb, int& te) {
+    const int b = min(max(spans[3 * s], 0), B - 1);
+    const int t0 = cu[b], L = cu[b + 1] - t0;
+    const int lo = min(max(spans[3 * s + 1], 0), L), hi = min(max(spans[3 * s + 2], lo), L);
+    tb = t0 + lo;
+    te = t0 + hi;
+}
+
+// sum[i] = sum over the span's n tokens of column tid + 256 i (0 for columns >= H).  e = sum / max(n, 1e-9), then
+// e / max(||e||, 1e-12) when normalize (the norm as k_pool_final forms it: wave sum + four LDS partials); orow (may be
+// NULL) gets the row, *score (q != NULL) the dot of q with the row as written.
+template <int H>
+__device__ __forceinline__ void span_write(const float (&sum)[(H + 255) / 256], int n, int normalize, const float* __restrict__ q,
+                                           float* __restrict__ orow, float* __restrict__ score) {
+    __shared__ float red[2][4];
+    constexpr int PER = (H + 255) / 256;
+    const int tid = threadIdx.x;
+    const float denom = fmaxf((float)n, 1e-9f);
+    float v[PER];
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        v[i] = sum[i] / denom;
+        ss += v[i] * v[i];
+    }
+    ss = wave_allsum(ss);
+    if ((tid & 63) == 0) red[0][tid >> 6] = ss;
+    __syncthreads();
+    const float nrm = fmaxf(sqrtf(red[0][0] + red[0][1] + red[0][2] + red[0][3]), 1e-12f);
+    float d = 0.f;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int c = tid + 256 * i;
+        if (normalize) v[i] = v[i] / nrm;
+        if (c < H) {
+            if (orow) orow[c] = v[i];
+            if (q) d += q[c] * v[i];
+        }
+    }
+    if (q == nullptr) return;   // (uniform over the block)
+    d = wave_allsum(d);
+    if ((tid & 63) == 0) red[1][tid >> 6] = d;
+    __syncthreads();
+    if (tid == 0) *score = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+}
+
+// Unfolded paths: y [T][H] fp32 token rows (x32).  A thread walks the span's rows in ascending order: a block reads
+// whole rows, coalesced.
+template <int H>
+__global__ __launch_bounds__(256) void k_span_pool(const float* __restrict__ y, const int32_t* __restrict__ cu, int B,
+                                                   const int32_t* __restrict__ spans, int normalize,
+                                                   const float* __restrict__ q, float* __restrict__ out,
+                                                   float* __restrict__ scores) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    int tb, te;
+    span_range(spans, cu, B, s, tb, te);
+    constexpr int PER = (H + 255) / 256;
+    float acc[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) acc[i] = 0.f;
+    // rows in ascending order, the loads of RB rows in flight at once (a row at a time costs one memory round trip per
+    // row); rows past the end add +0, which leaves every bit of the sum alone
+    constexpr int RB = 8;
+    for (int t = tb; t < te; t += RB) {
+        float r[RB][PER];
+#pragma unroll
+        for (int j = 0; j < RB; ++j)
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {
+                const int c = tid + 256 * i;
+                r[j][i] = (c < H && t + j < te) ? y[(size_t)(t + j) * H + c] : 0.f;
+            }
+#pragma unroll
+        for (int j = 0; j < RB; ++j)
+#pragma unroll
+            for (int i = 0; i < PER; ++i) acc[i] += r[j][i];
+    }
+    span_write<H>(acc, te - tb, normalize, q, out ? out + (size_t)s * H : nullptr, scores ? scores + s : nullptr);
+}
+
+// LayerNorm-folded path: the rows are the last pre tensor (bf16, blocked layout) + its row statistics, read through
+// pool_ln_rows (token classes t % 16 over GLOBAL token numbers) with the last LayerNorm applied on the way, exactly as
+// k_pool_partial_ln does it: sum = gamma[c] * sum_t (p_t[c] rs_t - mu_t rs_t) + n beta[c].
+template <int H>
+__global__ __launch_bounds__(256) void k_span_pool_ln(const bf16_t* __restrict__ pre, const long long* __restrict__ stats,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      float inv_h, float eps, const int32_t* __restrict__ cu, int B,
+                                                      const int32_t* __restrict__ spans, int normalize,
+                                                      const float* __restrict__ q, float* __restrict__ out,
+                                                      float* __restrict__ scores) {
+    static_assert(H % 256 == 0, "thread tid owns columns tid + 256 i");
+    __shared__ float red[16][H + 8];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    int tb, te;
+    span_range(spans, cu, B, s, tb, te);
+    pool_ln_rows<H>(pre, stats, inv_h, eps, tb, te, red);
+    float acc[H / 256];
+#pragma unroll
+    for (int i = 0; i < H / 256; ++i) {
+        const int c = tid + 256 * i;
+        acc[i] = fmaf(pool_ln_col<H>(red, c), gamma[c], (float)(te - tb) * beta[c]);
+    }
+    span_write<H>(acc, te - tb, normalize, q, out ? out + (size_t)s * H : nullptr, scores ? scores + s : nullptr);
 }
 
 // ---------------------------------------------------------------- weights

@@ -225,6 +225,20 @@ class EmbeddingGenerator:
             self.load_model()
         return self.model.encode(text, normalize_embeddings=self.config.normalize_embeddings, show_progress_bar=False)
 
+    def best_passages(self, query, texts_or_results, n: int = 1):
+        """Where in each text the answer is: per text (a string, or a ``SearchResult`` whose chunk text is read) its
+        ``n`` best ``Passage(start, end, text, score)`` against ``query`` -- a string (encoded once) or a query vector --
+        best first.  One encoder forward pass pools every passage of every text over its token span
+        (``MpnetEncoder.best_passages``); the reference prints a chunk's first characters instead
+        (INTEGRATION.md)."""
+        from .passages import texts_of
+
+        if not self.model:
+            self.load_model()
+        texts = texts_of(texts_or_results)
+        qv = self.generate_single_embedding(query) if isinstance(query, str) else np.asarray(query, dtype=np.float32)
+        return self.model.best_passages(qv, texts, n=n)
+
     def _generate_embeddings_batch(self, texts: List[str]):
         t0 = time.time()
         clean: List[str] = []

@@ -345,6 +345,51 @@ class MpnetEncoder:
                                                 out.ctypes.data))
         return out
 
+    def encode_spans_ids(self, batch: Sequence[Sequence[int]], spans, normalize: bool = True, query=None,
+                         span_rows: bool = True):
+        """One packed var-len batch through ``css_encoder_forward_spans``: the forward pass of ``encode_ids`` plus one
+        pooled row per span ``(sequence, begin, end)`` (token positions relative to the sequence) -- the masked MEAN of
+        the final hidden states of tokens ``begin..end-1``, also for a CLS-pooling model.  Returns
+        ``(seq_emb [B, hidden], span_emb [S, hidden], scores [S] | None)``; ``scores`` (with ``query`` [hidden]) are
+        ``dot(query, span row)`` formed on the device.  ``seq_emb`` is exactly what ``encode_ids`` returns.
+        ``span_rows=False`` (scores only) leaves the span rows on the device and returns ``None`` for them."""
+        B = len(batch)
+        H = int(self.cfg["hidden"])
+        lens = np.fromiter((len(s) for s in batch), dtype=np.int32, count=B)
+        cu = np.zeros(B + 1, dtype=np.int32)
+        np.cumsum(lens, out=cu[1:])
+        ids = np.concatenate([np.asarray(s, dtype=np.int32) for s in batch]) if B else np.zeros(0, np.int32)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        sp = np.ascontiguousarray(np.asarray(spans if len(spans) else np.zeros((0, 3)), dtype=np.int64))
+        if sp.ndim != 2 or sp.shape[1] != 3:
+            raise ValueError(f"encode_spans_ids: spans must be [S, 3] = (sequence, begin, end) (got shape {sp.shape})")
+        if sp.size and np.abs(sp).max() >= 2 ** 31:
+            raise ValueError("encode_spans_ids: span entries must fit int32")
+        sp = np.ascontiguousarray(sp, dtype=np.int32)
+        S = int(sp.shape[0])
+        q = None
+        if query is not None:
+            q = np.ascontiguousarray(query, dtype=np.float32).reshape(-1)
+            if q.size != H:
+                raise ValueError(f"encode_spans_ids: query has {q.size} elements, the model's hidden size is {H}")
+        seq = np.empty((B, H), dtype=np.float32)
+        out = np.empty((S, H), dtype=np.float32) if span_rows else None
+        scores = np.empty(S, dtype=np.float32) if q is not None else None
+        nat.check(nat.lib().css_encoder_forward_spans(
+            self._h, ids.ctypes.data, cu.ctypes.data, B, sp.ctypes.data if S else None, S,
+            q.ctypes.data if q is not None else None, 1 if normalize else 0, seq.ctypes.data,
+            out.ctypes.data if out is not None else None,
+            scores.ctypes.data if scores is not None else None))
+        return seq, out, scores
+
+    def best_passages(self, query_vec, texts: Sequence[str], n: int = 1, min_tokens: int = 8, max_tokens: int = 64,
+                      normalize: bool = True):
+        """``List[List[Passage]]``: per text its ``n`` best passages against ``query_vec``, best first, ties by position
+        (``passages.best_passages``: split at sentence and line ends, packed, one ``encode_spans_ids`` call)."""
+        from .passages import best_passages
+
+        return best_passages(self, query_vec, texts, n=n, min_tokens=min_tokens, max_tokens=max_tokens, normalize=normalize)
+
     def encode(self, sentences: Union[str, Sequence[str]], batch_size: int = 32, normalize_embeddings: bool = False,
                show_progress_bar: bool = False, convert_to_numpy: bool = True, **_ignored) -> np.ndarray:
         single = isinstance(sentences, str)

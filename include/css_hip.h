@@ -690,6 +690,28 @@ int css_encoder_forward(css_encoder* enc, const int32_t* input_ids_host, const i
 int css_encoder_forward_dev(css_encoder* enc, const int32_t* input_ids_dev, const int32_t* cu_seqlens_dev,
                             int B, int total_tokens, int max_len, int normalize, float* out_dev, void* stream);
 
+/* The forward pass of css_encoder_forward, plus one pooled row per SPAN of token rows (best passages of a search hit:
+ * sentence vectors that have seen the whole chunk as context, from one forward pass).
+ * spans: [S][3] int32 = (sequence b, begin, end), token positions relative to the sequence,
+ * 0 <= begin < end <= len_b.  Spans may overlap, repeat, come in any order, and leave sequences uncovered.
+ * span_out [S, hidden] (may be NULL): masked MEAN of the final hidden states of tokens begin..end-1
+ *   (always the mean, also for a CLS-pooling model), then e / max(||e||, 1e-12) when normalize != 0.
+ * q [hidden] (may be NULL) with scores_out [S] (NULL exactly when q is): dot(q, span row as written to span_out),
+ *   formed on the device.
+ * seq_out [B, hidden] (may be NULL): exactly what css_encoder_forward writes.
+ * S == 0 is allowed.  A bad span fails before anything is enqueued, naming the span.  The same call gives the same
+ * bits on every run (one block per span, fixed summation order).  The tiny-batch graphs of css_encoder_forward are
+ * not used by this call, and growing its span buffers does not drop them.
+ * _dev: device pointers, enqueued on `stream` without a synchronise.  The span table cannot be checked there: the
+ * kernels clamp (b, begin, end) into the batch, so a bad span yields a meaningless row, never a read outside it. */
+int css_encoder_forward_spans(css_encoder* enc, const int32_t* input_ids_host, const int32_t* cu_seqlens_host, int B,
+                              const int32_t* spans_host, int S, const float* q_host, int normalize,
+                              float* seq_out_host, float* span_out_host, float* scores_out_host);
+int css_encoder_forward_spans_dev(css_encoder* enc, const int32_t* input_ids_dev, const int32_t* cu_seqlens_dev, int B,
+                                  int total_tokens, int max_len, const int32_t* spans_dev, int S, const float* q_dev,
+                                  int normalize, float* seq_out_dev, float* span_out_dev, float* scores_out_dev,
+                                  void* stream);
+
 /* bf16 attention computes softmax rows as exp2(score) / sum WITHOUT a running maximum while every row sum of a
  * block stays in (1 / range, range) and repeats the block with the running-maximum (online) softmax otherwise --
  * same result, the guard only protects the fp32 range.  Default 2^100 (|logit| < 69); range = 0 always takes the
