@@ -15,6 +15,9 @@ def assert_topk_matches(D, I, D_ref, I_ref, D64_ref, what="", D64_next=None, tie
     assert D.shape == D_ref.shape and I.shape == I_ref.shape, what
     valid = I_ref >= 0
     assert ((I >= 0) == valid).all(), f"{what}: padding differs"
+    for r in range(I.shape[0]):   # (the set comparison below would let a repeated id through)
+        ids = I[r][I[r] >= 0]
+        assert np.unique(ids).size == ids.size, f"{what}: row {r} repeats an id"
     assert np.allclose(D[valid], D_ref[valid], atol=SCORE_TOL, rtol=0), \
         f"{what}: max score diff {np.abs(D[valid] - D_ref[valid]).max()}"
     gaps = np.abs(np.diff(D64_ref, axis=1))

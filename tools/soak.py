@@ -30,6 +30,7 @@ cx.add(np.repeat(cent, 6000, axis=0) + 0.01 * synth.rows(240_000, 768, 12), norm
 cx.set_search_mode("coarse")
 cq = cent[:24] + 0.005 * synth.rows(24, 768, 13)
 cref = cx.search(cq, 10, normalize=True)
+cqn = (cq / (np.linalg.norm(cq, axis=1, keepdims=True) + 1e-8)).astype(np.float32).astype(np.float64)   # the queries as searched
 assert cx.last_flagged() > 0
 free0 = torch.cuda.mem_get_info()[0]
 t0 = time.time(); it = 0
@@ -47,6 +48,14 @@ while time.time() - t0 < secs:
     # int8-MFMA sweep + exact fix-up and, for the 16 searches after it flagged, the bf16 batch scan + second pass, whose
     # exact scores are summed in another order: equal within 1e-6, ids may swap inside ties -- tools/cx_probe.py)
     assert np.allclose(D, cref[0], atol=1e-6, rtol=0), f"fix-up search changed at iteration {it}"
+    # ids that tolerate those ties and nothing else: an id may differ from the reference's only in a slot whose score
+    # equals the reference's within 1e-6 (asserted above for every slot, restated per slot here), no query repeats an id
+    # or returns a pad, and every returned id really HAS the score beside it (fp64 re-score of the stored row)
+    moved = I != cref[1]
+    assert (np.abs(D - cref[0])[moved] <= 1e-6).all(), f"fix-up search: ids moved outside ties at iteration {it}"
+    assert (I >= 0).all() and all(np.unique(r).size == r.size for r in I), f"fix-up search: repeated or padded ids at iteration {it}"
+    assert np.abs((cx.reconstruct_batch(I.reshape(-1)).astype(np.float64).reshape(I.shape + (768,)) * cqn[:, None, :]).sum(-1) - D).max() <= 1e-5, \
+        f"fix-up search: a returned id does not have its score at iteration {it}"
     it += 1
     if it % 50 == 0:
         print(f"iteration {it}, {time.time() - t0:.0f}s, free HBM delta {(free0 - torch.cuda.mem_get_info()[0]) / 1e6:.1f} MB", flush=True)
