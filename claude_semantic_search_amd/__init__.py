@@ -47,6 +47,8 @@ _LAZY = {
     "SignificantTerms": ".lexical",
     "words_of_terms": ".lexical",
     "MpnetEncoder": ".mpnet_encoder",
+    "CrossEncoder": ".cross_encoder",
+    "Reranked": ".storage",
     "Passage": ".passages",
     "split_passages": ".passages",
     "pack_passages": ".passages",

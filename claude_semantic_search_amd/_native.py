@@ -168,6 +168,10 @@ PROTOTYPES = {
                                           c_void_p, c_void_p]),
     "css_encoder_forward_spans_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                               c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_encoder_set_head": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_encoder_forward_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "css_encoder_forward_pairs_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                              c_void_p]),
     "css_encoder_debug_read": (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),
     "css_encoder_set_attention_range": (c_int, [c_void_p, c_float]),
     "css_mpnet_rel_bucket": (c_int, [c_int, c_int, c_int]),

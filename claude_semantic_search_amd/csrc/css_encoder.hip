@@ -12,6 +12,8 @@
 //                        -> k_gemm<GELU> -> k_gemm<RESID> -> k_layernorm ] -> k_pool_norm
 // BERT is the same post-LN stack with absolute positions (+ token-type row 0, folded into the position table when the
 // weights are finalised), no relative position bias, and mean or CLS pooling (css_encoder_cfg.arch / .pooling).
+// css_encoder_forward_pairs (BERT cross-encoders) runs the same stack with a per-sequence segment start (type-1 tokens
+// take `tdelta` in the embedding kernels), CLS rows without normalisation, then k_ce_head.
 // Residual stream / LayerNorm / softmax / pooling are fp32; GEMM and attention
 // operands are bf16 (MFMA) in the product mode, fp32 in the verification mode.
 #include "css_common.h"
@@ -78,6 +80,12 @@ __global__ void k_add_row(const float* __restrict__ pemb, const float* __restric
     if (i < (size_t)rows * H) out[i] = pemb[i] + row[i % H];
 }
 
+// BERT: tdelta[c] = tte[1][c] - tte[0][c] (what a type-1 token adds on top of the folded position table)
+__global__ void k_type_delta(const float* __restrict__ tte, float* __restrict__ out, int H) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < H) out[i] = tte[H + i] - tte[i];
+}
+
 }  // namespace
 
 // Bucket of a relative position (rel = key - query), transformers'
@@ -106,6 +114,7 @@ struct css_encoder {
     float *wemb = nullptr, *pemb = nullptr, *embg = nullptr, *embb = nullptr, *relw = nullptr;
     float *tte = nullptr;        // BERT token_type_embeddings [2][H]
     float *pemb_eff = nullptr;   // position table the embedding kernels read: pemb (MPNet), pemb + tte[0] (BERT)
+    float *tdelta = nullptr;     // BERT: tte[1] - tte[0] [H], added to the type-1 tokens of a pair batch
     std::vector<void*> extra;    // device buffers owned outside `params` (BERT fused QKV, pemb_eff)
     std::vector<LayerW> layers;
     float* bias_tab = nullptr;  // [heads][2*maxL-1]
@@ -125,6 +134,13 @@ struct css_encoder {
     int cap_spans = 0;
     int32_t* spans_dev = nullptr;
     float *span_out_dev = nullptr, *span_scores_dev = nullptr, *span_q_dev = nullptr;
+    // css_encoder_set_head / css_encoder_forward_pairs: head weights [H*H + H + H + 1] (Wp, bp, wc, bc), segment starts
+    // [B], logits [B].  Grow-only and apart from the activations, like the span buffers: no graph holds them.
+    float* head_dev = nullptr;
+    bool head_set = false;
+    int cap_pairs = 0;
+    int32_t* seg_dev = nullptr;
+    float* logits_dev = nullptr;
     // hipGraph cache for the launch-bound tiny-batch path (generate_single_embedding): key =
     // (B, T, max_len, normalize); a key is run eagerly once, captured on its second use, replayed after
     struct GraphEntry {
@@ -177,6 +193,8 @@ int build_params(css_encoder* e) {
         AP("embeddings.token_type_embeddings.weight", 2 * H, 5, 0.f, 0.02f, &e->tte);
         CSS_HIP_TRY(hipMalloc((void**)&e->pemb_eff, (size_t)c.max_pos * H * 4));
         e->extra.push_back(e->pemb_eff);
+        CSS_HIP_TRY(hipMalloc((void**)&e->tdelta, (size_t)H * 4));
+        e->extra.push_back(e->tdelta);
     } else {
         AP("encoder.relative_attention_bias.weight", (int64_t)c.rel_buckets * c.heads, 4, 0.f, 0.1f, &e->relw);
         e->pemb_eff = e->pemb;
@@ -286,6 +304,7 @@ int finalize_weights(css_encoder* e) {
         const size_t n = (size_t)c.max_pos * H;
         hipLaunchKernelGGL(k_add_row, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, e->pemb, e->tte, e->pemb_eff,
                            c.max_pos, (int)H);
+        hipLaunchKernelGGL(k_type_delta, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, st, e->tte, e->tdelta, (int)H);
     } else {
         const int n = c.heads * (2 * c.max_seq_len - 1);
         hipLaunchKernelGGL(k_build_bias_tab, dim3((n + 255) / 256), dim3(256), 0, st, e->relw, e->bucket_dev, c.heads,
@@ -494,7 +513,7 @@ void launch_attention_bf16(css_encoder* e, const int32_t* cu, int B, int max_len
 
 template <typename TIn, int H>
 int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int T, int max_len, int normalize,
-                  float* out, hipStream_t st) {
+                  float* out, hipStream_t st, const int32_t* seg, int pooling) {
     const css_encoder_cfg& c = e->cfg;
     const int F = c.ffn;
     constexpr bool BF = sizeof(TIn) == 2;
@@ -503,7 +522,7 @@ int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, 
         ProfScope ps("enc_embed_ln", st);
         hipLaunchKernelGGL(k_embed_ln<H>, dim3((T + 3) / 4), dim3(256), 0, st, ids, cu, B, e->wemb, e->pemb_eff,
                            e->embg, e->embb, c.ln_eps, c.vocab, c.max_pos, pos_offset(c), e->x32,
-                           BF ? (bf16_t*)e->x16 : nullptr, T);
+                           BF ? (bf16_t*)e->x16 : nullptr, T, seg, e->tdelta);
         CSS_LAUNCH_CHECK();
     }
     const int maxL = c.max_seq_len;
@@ -560,7 +579,7 @@ int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, 
     {
         ProfScope ps("enc_pool", st);
         constexpr int kPoolSlices = 8;
-        if (c.pooling == CSS_ENCODER_POOL_CLS) {
+        if (pooling == CSS_ENCODER_POOL_CLS) {
             hipLaunchKernelGGL(k_pool_cls<H>, dim3(B), dim3(256), 0, st, e->x32, cu, normalize, out);
         } else {
             // partial sums live in pre32 (free after the last LayerNorm): [B][8][H] floats
@@ -576,7 +595,7 @@ int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, 
 // "LayerNorm without LayerNorm kernels").  Launches per layer: QKV GEMM, attention, O GEMM, FFN1 GEMM, FFN2 GEMM.
 // The two pre tensors alternate between x16 and pre32 (both hold bf16 rows here).
 int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int T, int max_len, int normalize,
-                        float* out, hipStream_t st) {
+                        float* out, hipStream_t st, const int32_t* seg, int pooling) {
     const css_encoder_cfg& c = e->cfg;
     const int H = c.hidden, F = c.ffn;
     int rc;
@@ -584,7 +603,7 @@ int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, i
     {
         ProfScope ps("enc_embed_ln", st);
         hipLaunchKernelGGL(k_embed_pre<768>, dim3((T + 15) / 16), dim3(256), 0, st, ids, cu, B, e->wemb, e->pemb_eff, c.vocab,
-                           c.max_pos, pos_offset(c), pre[0], e->stats[0], T, kStatScale1, kStatScale2);
+                           c.max_pos, pos_offset(c), pre[0], e->stats[0], T, kStatScale1, kStatScale2, seg, e->tdelta);
         CSS_LAUNCH_CHECK();
     }
     const float *g_in = e->embg, *b_in = e->embb;  // the LayerNorm that turns pre[0] into the layer input
@@ -627,7 +646,7 @@ int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, i
         constexpr int kPoolSlices = 8;
         // partial sums live in ffn (free after the last FFN2; capacity >= 8 B rows of 8 H bytes): [B][8][H] floats
         float* part = (float*)e->ffn;
-        if (c.pooling == CSS_ENCODER_POOL_CLS) {
+        if (pooling == CSS_ENCODER_POOL_CLS) {
             hipLaunchKernelGGL(k_pool_cls_ln<768>, dim3(B), dim3(256), 0, st, (const bf16_t*)pre[0], e->stats[0], g_in, b_in,
                                1.0f / H, c.ln_eps, cu, normalize, out);
         } else {
@@ -641,8 +660,11 @@ int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, i
     return CSS_OK;
 }
 
+// seg (pair batches: per-sequence segment start, else NULL) and pooling (cfg.pooling, or CLS for the pair head) are the
+// only things a pair forward changes; with seg == NULL every kernel does what it does for css_encoder_forward.
 int forward_any(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int T, int max_len, int normalize,
-                float* out, hipStream_t st) {
+                float* out, hipStream_t st, const int32_t* seg = nullptr, int pooling = -1) {
+    if (pooling < 0) pooling = e->cfg.pooling;
     if (!e->weights_ready) {
         css::set_error("css_encoder_forward: weights not loaded (call css_encoder_load_weights or css_encoder_init_synthetic)");
         return CSS_ERR_STATE;
@@ -653,13 +675,13 @@ int forward_any(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, in
     // Hidden 384 (BERT small: GEMM N in {384, 1152, 1536}, K in {384, 1536}) always takes the unfolded path: its GEMMs
     // run on the 128x128 k_gemm tile (k_gemm8p for N = 1536) and k_gemm_skinny for <= 64 tokens.
     if (folded_shape(e->cfg) && T >= 1024 && (size_t)T * e->cfg.ffn * 2 < ((size_t)1 << 32))
-        return forward_folded_bf16(e, ids, cu, B, T, max_len, normalize, out, st);
+        return forward_folded_bf16(e, ids, cu, B, T, max_len, normalize, out, st, seg, pooling);
     e->x32_valid = true;
     if (e->cfg.hidden == 384)
-        return e->cfg.compute == 0 ? forward_typed<bf16_t, 384>(e, ids, cu, B, T, max_len, normalize, out, st)
-                                   : forward_typed<float, 384>(e, ids, cu, B, T, max_len, normalize, out, st);
-    return e->cfg.compute == 0 ? forward_typed<bf16_t, 768>(e, ids, cu, B, T, max_len, normalize, out, st)
-                               : forward_typed<float, 768>(e, ids, cu, B, T, max_len, normalize, out, st);
+        return e->cfg.compute == 0 ? forward_typed<bf16_t, 384>(e, ids, cu, B, T, max_len, normalize, out, st, seg, pooling)
+                                   : forward_typed<float, 384>(e, ids, cu, B, T, max_len, normalize, out, st, seg, pooling);
+    return e->cfg.compute == 0 ? forward_typed<bf16_t, 768>(e, ids, cu, B, T, max_len, normalize, out, st, seg, pooling)
+                               : forward_typed<float, 768>(e, ids, cu, B, T, max_len, normalize, out, st, seg, pooling);
 }
 
 // One pooled row per span over the token rows that the forward just enqueued on `st` left behind: x32 on the unfolded
@@ -680,6 +702,53 @@ int pool_spans(css_encoder* e, const int32_t* cu, int B, const int32_t* spans, i
     } else {
         hipLaunchKernelGGL(k_span_pool<768>, dim3(S), dim3(256), 0, st, e->x32, cu, B, spans, normalize, q, span_out, scores);
     }
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// Buffers of css_encoder_forward_pairs (host entry point); the stream is idle between calls, as for ensure_spans.
+int ensure_pairs(css_encoder* e, int B) {
+    if (B <= e->cap_pairs) return CSS_OK;
+    if (e->seg_dev) CSS_HIP_TRY(hipFree(e->seg_dev));
+    if (e->logits_dev) CSS_HIP_TRY(hipFree(e->logits_dev));
+    e->seg_dev = nullptr;
+    e->logits_dev = nullptr;
+    e->cap_pairs = 0;
+    const size_t cap = (size_t)B + (size_t)B / 2 + 64;
+    CSS_HIP_TRY(hipMalloc((void**)&e->seg_dev, cap * sizeof(int32_t)));
+    CSS_HIP_TRY(hipMalloc((void**)&e->logits_dev, cap * 4));
+    e->cap_pairs = (int)cap;
+    return CSS_OK;
+}
+
+// What a pair forward needs of the encoder: BERT, weights and a head.
+int check_pairs_state(const css_encoder* e, const char* fn) {
+    CSS_REQUIRE(e->cfg.arch == CSS_ENCODER_ARCH_BERT, "%s: the encoder is not a BERT model (token types and the "
+                "classification head exist for arch = BERT only)", fn);
+    if (!e->head_set) {
+        css::set_error("%s: no classification head (call css_encoder_set_head first)", fn);
+        return CSS_ERR_STATE;
+    }
+    return CSS_OK;
+}
+
+// The pair forward on `st`: segment-aware forward, CLS rows without normalisation into out_dev [B][H], then the head
+// (k_ce_head: partial logits per slab of pooler rows; k_ce_head_sum: their sum + bc).
+int forward_pairs_any(css_encoder* e, const int32_t* ids, const int32_t* cu, const int32_t* seg, int B, int T, int max_len,
+                      float* logits, hipStream_t st) {
+    int rc = forward_any(e, ids, cu, B, T, max_len, 0, e->out_dev, st, seg, CSS_ENCODER_POOL_CLS);
+    if (rc != CSS_OK) return rc;
+    const size_t H = e->cfg.hidden;
+    const float *wp = e->head_dev, *bp = wp + H * H, *wc = bp + H, *bc = wc + H;
+    // partials [tiles][H / kCeSlab][kCeTile] live in pre32 (free after the last LayerNorm / the last FFN2 GEMM;
+    // capacity >= 8 B rows of H floats, ensure_acts)
+    float* part = e->pre32;
+    ProfScope ps("enc_ce_head", st);
+    const int nslab = (int)H / kCeSlab;
+    const dim3 grid((B + kCeTile - 1) / kCeTile, nslab), blk(256);
+    if (H == 384) hipLaunchKernelGGL(k_ce_head<384>, grid, blk, 0, st, e->out_dev, wp, bp, wc, B, part);
+    else hipLaunchKernelGGL(k_ce_head<768>, grid, blk, 0, st, e->out_dev, wp, bp, wc, B, part);
+    hipLaunchKernelGGL(k_ce_head_sum, dim3((B + 255) / 256), dim3(256), 0, st, part, bc, B, nslab, logits);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
@@ -777,7 +846,7 @@ int css_encoder_free(css_encoder* e) {
     }
     void* ptrs[] = {e->bias_tab, e->bucket_dev, e->x32, e->pre32, e->x16, e->qkv, e->ctx, e->ffn, e->ids_dev,
                     e->cu_dev, e->out_dev, e->stats[0], e->stats[1], e->spans_dev, e->span_out_dev, e->span_scores_dev,
-                    e->span_q_dev};
+                    e->span_q_dev, e->head_dev, e->seg_dev, e->logits_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -1020,6 +1089,62 @@ int css_encoder_forward_spans_dev(css_encoder* e, const int32_t* ids_dev, const 
     if ((rc = forward_any(e, ids_dev, cu_dev, B, total_tokens, max_len, normalize, seq_out_dev ? seq_out_dev : e->out_dev, st)) != CSS_OK)
         return rc;
     return pool_spans(e, cu_dev, B, spans_dev, S, q_dev, normalize, span_out_dev, scores_out_dev, st);
+}
+
+int css_encoder_set_head(css_encoder* e, const float* pooler_w, const float* pooler_b, const float* cls_w, const float* cls_b) {
+    CSS_REQUIRE(e && pooler_w && pooler_b && cls_w && cls_b, "css_encoder_set_head: NULL argument");
+    CSS_REQUIRE(e->cfg.arch == CSS_ENCODER_ARCH_BERT, "css_encoder_set_head: the encoder is not a BERT model (the "
+                "classification head exists for arch = BERT only)");
+    const size_t H = e->cfg.hidden;
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard g(e->device);
+    if (!e->head_dev) CSS_HIP_TRY(hipMalloc((void**)&e->head_dev, (H * H + 2 * H + 1) * 4));
+    e->head_set = false;   // (a failed copy leaves no half-replaced head in use)
+    // the stream is idle between calls (every host entry point ends with a synchronise)
+    CSS_HIP_TRY(hipMemcpy(e->head_dev, pooler_w, H * H * 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(e->head_dev + H * H, pooler_b, H * 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(e->head_dev + H * H + H, cls_w, H * 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(e->head_dev + H * H + 2 * H, cls_b, 4, hipMemcpyHostToDevice));
+    e->head_set = true;
+    return CSS_OK;
+}
+
+int css_encoder_forward_pairs(css_encoder* e, const int32_t* ids, const int32_t* cu, const int32_t* seg_starts, int B,
+                              float* logits_out) {
+    CSS_REQUIRE(e && ids && cu && seg_starts && logits_out, "css_encoder_forward_pairs: NULL argument");
+    int max_len = 0;
+    int rc = check_batch(e, ids, cu, B, &max_len);
+    if (rc != CSS_OK) return rc;
+    for (int b = 0; b < B; ++b) {
+        const int len = cu[b + 1] - cu[b];
+        CSS_REQUIRE(seg_starts[b] >= 1 && seg_starts[b] <= len,
+                    "css_encoder_forward_pairs: sequence %d has seg_start %d outside [1, %d]", b, seg_starts[b], len);
+    }
+    const int T = cu[B];
+    std::lock_guard<std::mutex> lk(e->mu);
+    if ((rc = check_pairs_state(e, "css_encoder_forward_pairs")) != CSS_OK) return rc;
+    DeviceGuard g(e->device);
+    if ((rc = ensure_acts(e, T, B)) != CSS_OK || (rc = ensure_pairs(e, B)) != CSS_OK) return rc;
+    hipStream_t st = e->stream;
+    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(e->seg_dev, seg_starts, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    // eager launches (the tiny-batch graphs replay css_encoder_forward only)
+    if ((rc = forward_pairs_any(e, e->ids_dev, e->cu_dev, e->seg_dev, B, T, max_len, e->logits_dev, st)) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(logits_out, e->logits_dev, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    return CSS_OK;
+}
+
+int css_encoder_forward_pairs_dev(css_encoder* e, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* seg_starts_dev,
+                                  int B, int total_tokens, int max_len, float* logits_out_dev, void* stream) {
+    CSS_REQUIRE(e && ids_dev && cu_dev && seg_starts_dev && logits_out_dev, "css_encoder_forward_pairs_dev: NULL argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = check_pairs_state(e, "css_encoder_forward_pairs_dev");
+    if (rc != CSS_OK) return rc;
+    DeviceGuard g(e->device);
+    if ((rc = ensure_acts(e, total_tokens, B)) != CSS_OK) return rc;
+    return forward_pairs_any(e, ids_dev, cu_dev, seg_starts_dev, B, total_tokens, max_len, logits_out_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

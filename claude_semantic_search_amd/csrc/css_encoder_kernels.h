@@ -47,12 +47,20 @@ template <int H>
 __device__ __forceinline__ bool ln_col_ok(int idx) {   // float4 column idx of a row exists
     return H % 256 == 0 || idx < H / 4;
 }
+// Token type of position `rel` of a sequence of `len` tokens in a cross-encoder pair batch (css_encoder_forward_pairs):
+// 0 before seg_start, 1 from there on.  seg_start is clamped into [1, len]: the _dev entry point cannot check it.
+__device__ __forceinline__ bool seg_type1(const int32_t* __restrict__ seg, int b, int rel, int len) {
+    return seg != nullptr && rel >= min(max(seg[b], 1), len);
+}
+// seg (per sequence, may be NULL) / tdelta [H] = token_type_embeddings[1] - [0]: a type-1 token's row is
+// (word + pemb[pos]) + tdelta before the statistics.  seg == NULL: the additions below are those of a plain forward.
 template <int H>
 __global__ __launch_bounds__(256) void k_embed_ln(const int32_t* __restrict__ ids, const int32_t* __restrict__ cu,
                                                   int B, const float* __restrict__ wemb,
                                                   const float* __restrict__ pemb, const float* __restrict__ gamma,
                                                   const float* __restrict__ beta, float eps, int vocab, int max_pos,
-                                                  int pos_off, float* __restrict__ out32, bf16_t* __restrict__ out16, int T) {
+                                                  int pos_off, float* __restrict__ out32, bf16_t* __restrict__ out16, int T,
+                                                  const int32_t* __restrict__ seg, const float* __restrict__ tdelta) {
     static_assert(H % 128 == 0, "float4 columns of a row cover whole 32-lane halves");
     constexpr int NV = (H / 4 + 63) / 64;  // float4 per lane
     const int lane = threadIdx.x & 63;
@@ -70,6 +78,7 @@ __global__ __launch_bounds__(256) void k_embed_ln(const int32_t* __restrict__ id
     pos = pos < max_pos ? pos : max_pos - 1;
     const float4* w4 = reinterpret_cast<const float4*>(wemb + (size_t)id * H);
     const float4* p4 = reinterpret_cast<const float4*>(pemb + (size_t)pos * H);
+    const bool ty1 = seg_type1(seg, lo, t - cu[lo], cu[lo + 1] - cu[lo]);   // (wave-uniform: one token per wave)
     float4 v[NV];
     float s = 0.f;
 #pragma unroll
@@ -78,6 +87,10 @@ __global__ __launch_bounds__(256) void k_embed_ln(const int32_t* __restrict__ id
         if (!ln_col_ok<H>(lane + 64 * i)) continue;
         const float4 a = w4[lane + 64 * i], b = p4[lane + 64 * i];
         v[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+        if (ty1) {
+            const float4 d = reinterpret_cast<const float4*>(tdelta)[lane + 64 * i];
+            v[i] = make_float4(v[i].x + d.x, v[i].y + d.y, v[i].z + d.z, v[i].w + d.w);
+        }
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
     const float mean = wave_allsum(s) * (1.0f / H);
@@ -143,7 +156,8 @@ __global__ __launch_bounds__(256) void k_embed_pre(const int32_t* __restrict__ i
                                                    int B, const float* __restrict__ wemb,
                                                    const float* __restrict__ pemb, int vocab, int max_pos, int pos_off,
                                                    bf16_t* __restrict__ pre, long long* __restrict__ stats, int T,
-                                                   float scale1, float scale2) {
+                                                   float scale1, float scale2, const int32_t* __restrict__ seg,
+                                                   const float* __restrict__ tdelta) {
     // One block = one 16-token block row of the blocked layout: thread (lq = tid & 15, g = tid >> 4) writes the 16-byte
     // pieces g, g + 16, ... of token lq, so 16 consecutive lanes store 256 contiguous bytes (one piece row of a block).
     static_assert(H % 64 == 0, "blocked layout");
@@ -164,6 +178,9 @@ __global__ __launch_bounds__(256) void k_embed_pre(const int32_t* __restrict__ i
         pos = pos < max_pos ? pos : max_pos - 1;
         const float* wr_ = wemb + (size_t)id * H;
         const float* pr_ = pemb + (size_t)pos * H;
+        // seg / tdelta as in k_embed_ln: the type-1 add comes before the bf16 rounding, so the sums stay those of the
+        // stored values
+        const bool ty1 = seg_type1(seg, lo, t - cu[lo], cu[lo + 1] - cu[lo]);
         char* orow = reinterpret_cast<char*>(pre) + (size_t)(t >> 4) * preblk_rowstride(H) + lq * 16;
 #pragma unroll
         for (int pi = g; pi < NP; pi += 16) {
@@ -171,7 +188,12 @@ __global__ __launch_bounds__(256) void k_embed_pre(const int32_t* __restrict__ i
             const int c0 = 64 * cb + 32 * j + 4 * lg;
             const float4 a0 = *reinterpret_cast<const float4*>(wr_ + c0), a1 = *reinterpret_cast<const float4*>(wr_ + c0 + 16);
             const float4 b0 = *reinterpret_cast<const float4*>(pr_ + c0), b1 = *reinterpret_cast<const float4*>(pr_ + c0 + 16);
-            const float v[8] = {a0.x + b0.x, a0.y + b0.y, a0.z + b0.z, a0.w + b0.w, a1.x + b1.x, a1.y + b1.y, a1.z + b1.z, a1.w + b1.w};
+            float v[8] = {a0.x + b0.x, a0.y + b0.y, a0.z + b0.z, a0.w + b0.w, a1.x + b1.x, a1.y + b1.y, a1.z + b1.z, a1.w + b1.w};
+            if (ty1) {
+                const float4 d0 = *reinterpret_cast<const float4*>(tdelta + c0), d1 = *reinterpret_cast<const float4*>(tdelta + c0 + 16);
+                v[0] += d0.x; v[1] += d0.y; v[2] += d0.z; v[3] += d0.w;
+                v[4] += d1.x; v[5] += d1.y; v[6] += d1.z; v[7] += d1.w;
+            }
             unsigned o[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -2011,6 +2033,95 @@ __global__ __launch_bounds__(256) void k_pool_cls_ln(const bf16_t* __restrict__ 
         v[i] = c < H ? fmaf(gamma[c], fmaf(bf2f(pre[preblk_elem(t, c, H)]), rs, -mrs), beta[c]) : 0.f;
     }
     cls_pool_write<H>(v, normalize, out + (size_t)b * H);
+}
+
+// ---------------------------------------------------------------- cross-encoder head
+// css_encoder_forward_pairs: logit[b] = dot(wc, tanh(Wp h_b + bp)) + bc over the CLS rows h [B][H] (fp32, from
+// k_pool_cls / k_pool_cls_ln with normalize = 0).  fp32 in both compute modes, no atomics, every sum in a fixed order:
+// the same batch gives the same bits.
+//
+// k_ce_head<H>: grid (tiles of kCeTile = 8 pairs, H / kCeSlab slabs of output rows), 256 threads.  The tile's CLS rows
+// sit in LDS (8 x 768 x 4 B = 24 KiB), so Wp is read once per 8 pairs.  Wave w takes rows j = slab + w + 4 r of Wp,
+// kCeRows at a time (their coalesced float4 loads are in flight together and one LDS read serves all of them), forms the
+// 8 dot products per row against the LDS rows, reduces each across the lanes (wave_allsum), and accumulates
+// wc[j] * tanhf(. + bp[j]) per pair in a register.  The four waves' partials are summed in a fixed order through LDS
+// into part[tile][slab][pair].  The slabs exist because one block per tile walking all H rows measured 0.13 ms (H = 384)
+// / 0.30 ms (H = 768) for 64 pairs -- 8 blocks on 256 CUs, each wave bound by its own 8 reductions and tanhf per row
+// (DESIGN.md 3.3c).
+// k_ce_head_sum: logit[b] = (part[..][0][..] + part[..][1][..] + ...) + bc, slabs in ascending order, bc last.
+constexpr int kCeTile = 8;
+constexpr int kCeRows = 4;              // output rows per wave and step
+constexpr int kCeSlab = 3 * 4 * kCeRows;   // output rows per block: three steps of 4 waves x kCeRows (divides 384 and 768)
+template <int H>
+__global__ __launch_bounds__(256) void k_ce_head(const float* __restrict__ cls, const float* __restrict__ wp,
+                                                 const float* __restrict__ bp, const float* __restrict__ wc, int B,
+                                                 float* __restrict__ part_out) {
+    static_assert(H % 128 == 0, "float4 columns of a row cover whole 32-lane halves");
+    static_assert(H % kCeSlab == 0, "whole slabs of output rows");
+    constexpr int NV = (H / 4 + 63) / 64;   // float4 per lane (k_embed_ln's column split)
+    __shared__ float4 rows[kCeTile][H / 4];
+    __shared__ float part[4][kCeTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b0 = blockIdx.x * kCeTile, jb = blockIdx.y * kCeSlab;
+    for (int i = tid; i < kCeTile * (H / 4); i += 256) {
+        const int p = i / (H / 4), c = i - p * (H / 4);
+        rows[p][c] = b0 + p < B ? reinterpret_cast<const float4*>(cls + (size_t)(b0 + p) * H)[c]
+                                : make_float4(0.f, 0.f, 0.f, 0.f);   // (pairs beyond the batch: zero rows, never read back)
+    }
+    __syncthreads();
+    float acc[kCeTile];
+#pragma unroll
+    for (int p = 0; p < kCeTile; ++p) acc[p] = 0.f;
+    for (int j0 = jb + wave; j0 < jb + kCeSlab; j0 += 4 * kCeRows) {   // rows j0 + 4 r < jb + kCeSlab <= H
+        float4 w[kCeRows][NV];
+#pragma unroll
+        for (int r = 0; r < kCeRows; ++r)
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+                w[r][i] = ln_col_ok<H>(lane + 64 * i)
+                              ? reinterpret_cast<const float4*>(wp + (size_t)(j0 + 4 * r) * H)[lane + 64 * i]
+                              : make_float4(0.f, 0.f, 0.f, 0.f);
+        float d[kCeRows][kCeTile];
+#pragma unroll
+        for (int r = 0; r < kCeRows; ++r)
+#pragma unroll
+            for (int p = 0; p < kCeTile; ++p) d[r][p] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            if (!ln_col_ok<H>(lane + 64 * i)) continue;
+#pragma unroll
+            for (int p = 0; p < kCeTile; ++p) {
+                const float4 x = rows[p][lane + 64 * i];
+#pragma unroll
+                for (int r = 0; r < kCeRows; ++r)
+                    d[r][p] = fmaf(w[r][i].w, x.w, fmaf(w[r][i].z, x.z, fmaf(w[r][i].y, x.y, fmaf(w[r][i].x, x.x, d[r][p]))));
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kCeRows; ++r) {   // rows in ascending order
+            const float bj = bp[j0 + 4 * r], wj = wc[j0 + 4 * r];
+#pragma unroll
+            for (int p = 0; p < kCeTile; ++p) acc[p] = fmaf(wj, tanhf(wave_allsum(d[r][p]) + bj), acc[p]);
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int p = 0; p < kCeTile; ++p) part[wave][p] = acc[p];
+    }
+    __syncthreads();
+    if (tid < kCeTile)
+        part_out[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * kCeTile + tid] =
+            ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+}
+
+__global__ void k_ce_head_sum(const float* __restrict__ part, const float* __restrict__ bc, int B, int nslab,
+                              float* __restrict__ logits) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float* p = part + (size_t)(b / kCeTile) * nslab * kCeTile + (b % kCeTile);
+    float s = p[0];
+    for (int k = 1; k < nslab; ++k) s += p[(size_t)k * kCeTile];
+    logits[b] = s + bc[0];
 }
 
 // ---------------------------------------------------------------- span pooling

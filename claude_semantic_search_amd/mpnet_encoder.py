@@ -228,7 +228,9 @@ def _load_state_dict(model_dir: Path) -> Dict[str, np.ndarray]:
 class MpnetEncoder:
     def __init__(self, model_name_or_path: Optional[str] = "all-mpnet-base-v2", cache_folder: Optional[str] = None,
                  device: int = 0, compute: str = "bf16", synthetic_seed: Optional[int] = None,
-                 cfg_overrides: Optional[dict] = None):
+                 cfg_overrides: Optional[dict] = None, weights: Optional[Dict[str, np.ndarray]] = None):
+        # weights: a state dict to load in place of the checkpoint's own file (CrossEncoder passes the body of a
+        # sequence-classification checkpoint, whose head tensors the strict loader does not know)
         cfg = dict(DEFAULT_CFG)
         model_dir = None
         if synthetic_seed is None:
@@ -260,7 +262,7 @@ class MpnetEncoder:
             nat.check(nat.lib().css_encoder_init_synthetic(self._h, ctypes.c_uint64(synthetic_seed)))
             self.tokenizer = HashTokenizer(cfg["vocab"])   # synthetic weights: any deterministic text -> ids map will do
         else:
-            self.load_state_dict(_load_state_dict(model_dir))
+            self.load_state_dict(_load_state_dict(model_dir) if weights is None else weights)
             tk = _tokenizer_files(model_dir)
             if tk["max_seq_length"]:
                 self.max_seq_length = min(int(tk["max_seq_length"]), cfg["max_seq_len"])
@@ -381,6 +383,41 @@ class MpnetEncoder:
             out.ctypes.data if out is not None else None,
             scores.ctypes.data if scores is not None else None))
         return seq, out, scores
+
+    # -- cross-encoder head ----------------------------------------------------
+    def set_head(self, pooler_w, pooler_b, cls_w, cls_b) -> None:
+        """The sequence-classification head of a BERT cross-encoder (``css_encoder_set_head``): ``pooler_w`` [H, H],
+        ``pooler_b`` [H], ``cls_w`` [H] or [1, H], ``cls_b`` [1].  May be called again to replace the head."""
+        H = int(self.cfg["hidden"])
+        arrs = []
+        for name, a, shapes in (("pooler_w", pooler_w, ((H, H),)), ("pooler_b", pooler_b, ((H,),)),
+                                ("cls_w", cls_w, ((H,), (1, H))), ("cls_b", cls_b, ((1,), ()))):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape not in shapes:
+                raise ValueError(f"set_head: {name} has shape {a.shape}, expected {' or '.join(map(str, shapes))}")
+            arrs.append(a.reshape(-1))
+        nat.check(nat.lib().css_encoder_set_head(self._h, *(a.ctypes.data for a in arrs)))
+
+    def score_pair_ids(self, batch: Sequence[Sequence[int]], seg_starts: Sequence[int]) -> np.ndarray:
+        """One packed var-len batch of ``[CLS] a [SEP] b [SEP]`` sequences through ``css_encoder_forward_pairs``:
+        tokens at positions ``< seg_starts[b]`` take token type 0, the others type 1.  Returns the float32 logits [B]."""
+        B = len(batch)
+        seg = np.asarray(seg_starts, dtype=np.int64).reshape(-1)
+        if seg.size != B:
+            raise ValueError(f"score_pair_ids: {seg.size} seg_starts for {B} sequences")
+        if B == 0:
+            return np.zeros(0, dtype=np.float32)
+        if np.abs(seg).max() >= 2 ** 31:
+            raise ValueError("score_pair_ids: seg_starts must fit int32")
+        seg = np.ascontiguousarray(seg, dtype=np.int32)
+        lens = np.fromiter((len(s) for s in batch), dtype=np.int32, count=B)
+        cu = np.zeros(B + 1, dtype=np.int32)
+        np.cumsum(lens, out=cu[1:])
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int32) for s in batch]), dtype=np.int32)
+        out = np.empty(B, dtype=np.float32)
+        nat.check(nat.lib().css_encoder_forward_pairs(self._h, ids.ctypes.data, cu.ctypes.data, seg.ctypes.data, B,
+                                                      out.ctypes.data))
+        return out
 
     def best_passages(self, query_vec, texts: Sequence[str], n: int = 1, min_tokens: int = 8, max_tokens: int = 64,
                       normalize: bool = True):

@@ -34,7 +34,7 @@ import threading
 from dataclasses import dataclass
 from datetime import datetime, timezone
 from pathlib import Path
-from typing import Any, Callable, Dict, List, Optional
+from typing import Any, Callable, Dict, List, NamedTuple, Optional
 
 import numpy as np
 
@@ -89,6 +89,14 @@ class SearchResult:
     chunk: Optional[Chunk] = None
     metadata: Optional[Dict[str, Any]] = None
     text: Optional[str] = None
+
+
+class Reranked(NamedTuple):
+    """One hit of ``HybridStorage.search_reranked``: the plain search result, the cross-encoder logit of
+    ``(query_text, chunk text)`` and the chunk's position in the plain search's ranking (0 = its best hit)."""
+    result: SearchResult
+    score: float
+    rank_before: int
 
 
 @dataclass
@@ -1016,6 +1024,35 @@ class HybridStorage:
             return sims, ids
 
         return self._ranked_in_index(query_embedding, config, filters, fi.MAX_HYBRID_K, run)
+
+    def search_reranked(self, query_text: str, query_embedding, reranker, config: Optional[SearchConfig] = None,
+                        filters: Optional[Dict[str, Any]] = None, fetch: int = 50) -> List[Reranked]:
+        """Retrieve, then re-read: the ordinary ``search`` for ``max(fetch, top_k)`` hits, each ``(query_text, chunk
+        text)`` pair scored by ``reranker.predict`` (a ``CrossEncoder``: one forward pass over ``[CLS] query [SEP] text
+        [SEP]`` per hit), and the ``top_k`` best by that score, best first; ties keep the plain search's order.  Each
+        ``Reranked`` carries the plain ``SearchResult`` (its bi-encoder ``similarity`` untouched), the reranker's
+        ``score`` and ``rank_before``, the hit's position in the plain ranking.  Tombstones, filters and
+        ``similarity_threshold`` behave as in ``search``; the reranker's hidden size need not match the index.  A chunk
+        the plain search ranks below ``fetch`` is never seen: re-ranking reorders, it does not retrieve."""
+        cfg = config or SearchConfig()
+        if cfg.top_k <= 0:
+            return []
+        n = max(int(fetch), cfg.top_k)
+        wide = SearchConfig(top_k=n, similarity_threshold=cfg.similarity_threshold, include_metadata=cfg.include_metadata,
+                            include_text=True, max_results=max(cfg.max_results, n))
+        hits = self.search(query_embedding, wide, filters)
+        if not hits:
+            return []
+        scores = np.asarray(reranker.predict([(query_text, h.text or "") for h in hits]), dtype=np.float32).reshape(-1)
+        if scores.size != len(hits):
+            raise ValueError(f"search_reranked: the reranker returned {scores.size} scores for {len(hits)} pairs")
+        out = []
+        for i in np.argsort(-scores, kind="stable")[:cfg.top_k]:
+            h = hits[int(i)]
+            if not cfg.include_text:
+                h.text, h.chunk = None, None
+            out.append(Reranked(h, float(scores[i]), int(i)))
+        return out
 
     @staticmethod
     def _make_result(chunk_id: str, score: float, data: Dict[str, Any], cfg: SearchConfig) -> SearchResult:

@@ -712,6 +712,28 @@ int css_encoder_forward_spans_dev(css_encoder* enc, const int32_t* input_ids_dev
                                   int normalize, float* seq_out_dev, float* span_out_dev, float* scores_out_dev,
                                   void* stream);
 
+/* ---- cross-encoder re-ranking: one relevance logit per (query, text) pair ----
+ * Sequence-classification head of a BERT cross-encoder (transformers' BertForSequenceClassification, num_labels = 1):
+ * pooled = tanh(Wp h_CLS + bp), logit = dot(wc, pooled) + bc.  Host fp32; copies are kept on the device.
+ * Separate from css_encoder_load_weights (which still skips pooler.* and does not know classifier.*).  BERT
+ * architecture only (anything else: CSS_ERR_INVALID).  May be called again to replace the head. */
+int css_encoder_set_head(css_encoder* enc, const float* pooler_w /* [H,H] */, const float* pooler_b /* [H] */,
+                         const float* cls_w /* [H] */, const float* cls_b /* [1] */);
+/* Packed var-len batch as css_encoder_forward, plus seg_starts[b] in [1, len_b]: tokens at positions < seg_starts[b]
+ * of sequence b take token type 0, the others type 1 (seg_starts[b] == len_b: a single-segment input).
+ * logits_out [B] fp32: the head applied to the final hidden state of token 0 of every sequence (whatever cfg.pooling is).
+ * The head is fp32 in both compute modes and uses no atomics: the same batch gives the same bits on every run.
+ * A seg_start outside [1, len_b] fails before anything is enqueued, naming the sequence.  An MPNet encoder is
+ * CSS_ERR_INVALID, an encoder without a head CSS_ERR_STATE.  The tiny-batch graphs of css_encoder_forward are not
+ * used, created or dropped by this call (as for css_encoder_forward_spans).
+ * _dev: device pointers, enqueued on `stream` without a synchronise.  seg_starts cannot be checked there: the kernels
+ * clamp it into [1, len_b], so a bad value yields a meaningless logit, never a read outside the batch. */
+int css_encoder_forward_pairs(css_encoder* enc, const int32_t* input_ids_host, const int32_t* cu_seqlens_host,
+                              const int32_t* seg_starts_host, int B, float* logits_out_host);
+int css_encoder_forward_pairs_dev(css_encoder* enc, const int32_t* input_ids_dev, const int32_t* cu_seqlens_dev,
+                                  const int32_t* seg_starts_dev, int B, int total_tokens, int max_len,
+                                  float* logits_out_dev, void* stream);
+
 /* bf16 attention computes softmax rows as exp2(score) / sum WITHOUT a running maximum while every row sum of a
  * block stays in (1 / range, range) and repeats the block with the running-maximum (online) softmax otherwise --
  * same result, the guard only protects the fp32 range.  Default 2^100 (|logit| < 69); range = 0 always takes the
