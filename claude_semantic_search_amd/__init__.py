@@ -48,6 +48,7 @@ _LAZY = {
     "words_of_terms": ".lexical",
     "MpnetEncoder": ".mpnet_encoder",
     "CrossEncoder": ".cross_encoder",
+    "LateInteraction": ".late_interaction",
     "Reranked": ".storage",
     "Passage": ".passages",
     "split_passages": ".passages",

@@ -172,6 +172,19 @@ PROTOTYPES = {
     "css_encoder_forward_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "css_encoder_forward_pairs_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                               c_void_p]),
+    "css_encoder_set_token_projection": (c_int, [c_void_p, c_void_p, c_int]),
+    "css_encoder_token_dim": (c_int, [c_void_p]),
+    "css_encoder_forward_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "css_encoder_forward_tokens_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                               c_void_p]),
+    "css_encoder_maxsim": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                   c_int, c_void_p]),
+    "css_encoder_maxsim_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                       c_int, c_int, c_void_p, c_void_p]),
+    "css_encoder_forward_maxsim": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_int, c_void_p, c_void_p]),
+    "css_encoder_forward_maxsim_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                               c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "css_encoder_debug_read": (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),
     "css_encoder_set_attention_range": (c_int, [c_void_p, c_float]),
     "css_mpnet_rel_bucket": (c_int, [c_int, c_int, c_int]),

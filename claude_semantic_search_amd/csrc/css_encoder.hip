@@ -17,6 +17,7 @@
 // Residual stream / LayerNorm / softmax / pooling are fp32; GEMM and attention
 // operands are bf16 (MFMA) in the product mode, fp32 in the verification mode.
 #include "css_common.h"
+#include "css_devbuf.h"
 #include "css_encoder_kernels.h"
 #include "../../include/css_synth.h"
 
@@ -141,6 +142,16 @@ struct css_encoder {
     int cap_pairs = 0;
     int32_t* seg_dev = nullptr;
     float* logits_dev = nullptr;
+    // css_encoder_set_token_projection / css_encoder_forward_tokens / css_encoder_maxsim: projection [P][H] fp32
+    // (tok_p == 0: none, the token vectors are the hidden states), and the host entry points' device copies: token
+    // rows, query rows, both offset tables, keep flags, pairs, scores.  Grow-only and apart from the activations, like
+    // the span buffers: no graph holds them.
+    float* tokw_dev = nullptr;
+    int tok_p = 0;
+    css::DevBuf<bf16_t> li_tok, li_q;
+    css::DevBuf<int32_t> li_cuq, li_cud, li_pairs;
+    css::DevBuf<uint8_t> li_keep;
+    css::DevBuf<float> li_scores, li_part;   // li_part: partial maxima [np][nsplit][64] of a split MaxSim launch
     // hipGraph cache for the launch-bound tiny-batch path (generate_single_embedding): key =
     // (B, T, max_len, normalize); a key is run eagerly once, captured on its second use, replayed after
     struct GraphEntry {
@@ -772,6 +783,114 @@ int check_batch(const css_encoder* e, const int32_t* ids, const int32_t* cu, int
     return CSS_OK;
 }
 
+// Width of a token vector: the projection's P, or the hidden size without one.
+int token_dim(const css_encoder* e) { return e->tok_p ? e->tok_p : e->cfg.hidden; }
+
+// One bf16 row per token over the rows that the forward just enqueued on `st` left behind (the two layouts of
+// pool_spans).  One launch.
+int write_tokens(css_encoder* e, int T, int normalize, bf16_t* tok_out, hipStream_t st) {
+    const css_encoder_cfg& c = e->cfg;
+    const int P = token_dim(e);
+    const float* W = e->tok_p ? e->tokw_dev : nullptr;
+    ProfScope ps("enc_tok_vec", st);
+    const dim3 grid((T + 15) / 16), blk(256);
+    if (!e->x32_valid) {
+        const LayerW& L = e->layers.back();
+        hipLaunchKernelGGL(k_tok_vec_ln<768>, grid, blk, 0, st, (const bf16_t*)e->x16, e->stats[0], L.ln2g, L.ln2b,
+                           1.0f / c.hidden, c.ln_eps, T, W, P, normalize, tok_out);
+    } else if (c.hidden == 384) {
+        hipLaunchKernelGGL(k_tok_vec<384>, grid, blk, 0, st, e->x32, T, W, P, normalize, tok_out);
+    } else {
+        hipLaunchKernelGGL(k_tok_vec<768>, grid, blk, 0, st, e->x32, T, W, P, normalize, tok_out);
+    }
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+bool maxsim_width_ok(int P) { return (P % 32 == 0 && P >= 32 && P <= 128) || P == 384 || P == 768; }
+
+template <int P>
+int launch_maxsim_p(const css_encoder* e, const bf16_t* q, const int32_t* cuq, int nq, const bf16_t* d, const int32_t* cud,
+                    int nd, const uint8_t* keep, const int32_t* pairs, int np, int nsplit, float* scores, float* part,
+                    hipStream_t st) {
+    constexpr size_t lds = maxsim_lds_bytes<P>();
+    const int rc = css::ensure_dynamic_lds((const void*)k_maxsim<P>, lds, e->device);
+    if (rc != CSS_OK) return rc;
+    hipLaunchKernelGGL(k_maxsim<P>, dim3(np, nsplit), dim3(256), lds, st, q, cuq, nq, d, cud, nd, keep, pairs, scores, part);
+    if (nsplit > 1) hipLaunchKernelGGL(k_maxsim_sum, dim3(np), dim3(64), 0, st, part, nsplit, cuq, nq, pairs, scores);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// Blocks per doc: one while the pairs alone give every CU CSS_MAXSIM_BLOCKS_PER_CU blocks, else as many as that takes,
+// 8 at the most (a 64-pair re-rank batch would otherwise run on 64 of the CUs).  The partial maxima of a split launch
+// live in a buffer of the encoder's that only grows; growing frees the old one, so work that an earlier call enqueued
+// on another stream must have finished, as for the activations.  DESIGN.md 3.3d has the measurements.
+#ifndef CSS_MAXSIM_BLOCKS_PER_CU
+#define CSS_MAXSIM_BLOCKS_PER_CU 2
+#endif
+constexpr int kMaxsimSplitMax = 8;
+int launch_maxsim(css_encoder* e, const bf16_t* q, const int32_t* cuq, int nq, const bf16_t* d, const int32_t* cud,
+                  int nd, const uint8_t* keep, const int32_t* pairs, int np, int P, float* scores, hipStream_t st) {
+    if (np == 0) return CSS_OK;
+    const int want = CSS_MAXSIM_BLOCKS_PER_CU * e->num_cus;
+    const int nsplit = std::min(kMaxsimSplitMax, std::max(1, (want + np - 1) / np));
+    if (nsplit > 1) {
+        const int rc = e->li_part.grow((size_t)np * nsplit * kMaxsimQ);
+        if (rc != CSS_OK) return rc;
+    }
+    ProfScope ps("enc_maxsim", st);
+    switch (P) {
+#define MS(W_) case W_: return launch_maxsim_p<W_>(e, q, cuq, nq, d, cud, nd, keep, pairs, np, nsplit, scores, e->li_part.p, st)
+        MS(32); MS(64); MS(96); MS(128); MS(384); MS(768);
+#undef MS
+    }
+    css::set_error("css_encoder_maxsim: P=%d must be a multiple of 32 in [32, 128], or 384, or 768", P);
+    return CSS_ERR_INVALID;
+}
+
+// Host tables of a MaxSim call, checked before anything is enqueued: every query has 1..64 tokens, every doc at least
+// one token and one kept token, every pair names a query and a doc.
+int check_maxsim(const char* fn, const int32_t* cuq, int nq, const int32_t* cud, int nd, const uint8_t* keep,
+                 const int32_t* pairs, int np) {
+    CSS_REQUIRE(nq >= 1 && nd >= 1 && np >= 0, "%s: need nq >= 1, nd >= 1, np >= 0 (got %d, %d, %d)", fn, nq, nd, np);
+    CSS_REQUIRE(np == 0 || pairs, "%s: pairs is NULL", fn);
+    CSS_REQUIRE(cuq[0] == 0 && cud[0] == 0, "%s: cu_q[0] and cu_d[0] must be 0", fn);
+    for (int i = 0; i < nq; ++i) {
+        const int m = cuq[i + 1] - cuq[i];
+        CSS_REQUIRE(m >= 1 && m <= kMaxsimQ, "%s: query %d has %d tokens, outside [1, %d]", fn, i, m, kMaxsimQ);
+    }
+    for (int j = 0; j < nd; ++j) {
+        const int m = cud[j + 1] - cud[j];
+        CSS_REQUIRE(m >= 1, "%s: doc %d has %d tokens (need at least 1)", fn, j, m);
+        if (!keep) continue;
+        bool any = false;
+        for (int t = cud[j]; t < cud[j + 1] && !any; ++t) any = keep[t] != 0;
+        CSS_REQUIRE(any, "%s: doc %d has no kept token (d_keep is 0 for all of its %d tokens)", fn, j, m);
+    }
+    for (int p = 0; p < np; ++p)
+        CSS_REQUIRE(pairs[2 * p] >= 0 && pairs[2 * p] < nq && pairs[2 * p + 1] >= 0 && pairs[2 * p + 1] < nd,
+                    "%s: pair %d is (query %d, doc %d), outside [0, %d) x [0, %d)", fn, p, pairs[2 * p], pairs[2 * p + 1], nq, nd);
+    return CSS_OK;
+}
+
+// Device copies of the query side of a host MaxSim call (query rows, their offsets, keep flags over `nkeep` doc tokens,
+// pairs) and room for the scores.  The stream is idle between calls, as for ensure_spans.
+int upload_maxsim(css_encoder* e, const uint16_t* q_tok, const int32_t* cuq, int nq, const uint8_t* keep, size_t nkeep,
+                  const int32_t* pairs, int np, int P, hipStream_t st) {
+    const size_t nqt = (size_t)cuq[nq] * P;
+    int rc;
+    if ((rc = e->li_q.grow(nqt)) != CSS_OK || (rc = e->li_cuq.grow((size_t)nq + 1)) != CSS_OK ||
+        (rc = e->li_pairs.grow((size_t)2 * std::max(np, 1))) != CSS_OK || (rc = e->li_scores.grow(std::max(np, 1))) != CSS_OK ||
+        (keep && (rc = e->li_keep.grow(nkeep)) != CSS_OK))
+        return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(e->li_q.p, q_tok, nqt * 2, hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(e->li_cuq.p, cuq, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, st));
+    if (np) CSS_HIP_TRY(hipMemcpyAsync(e->li_pairs.p, pairs, (size_t)np * 8, hipMemcpyHostToDevice, st));
+    if (keep) CSS_HIP_TRY(hipMemcpyAsync(e->li_keep.p, keep, nkeep, hipMemcpyHostToDevice, st));
+    return CSS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -846,7 +965,7 @@ int css_encoder_free(css_encoder* e) {
     }
     void* ptrs[] = {e->bias_tab, e->bucket_dev, e->x32, e->pre32, e->x16, e->qkv, e->ctx, e->ffn, e->ids_dev,
                     e->cu_dev, e->out_dev, e->stats[0], e->stats[1], e->spans_dev, e->span_out_dev, e->span_scores_dev,
-                    e->span_q_dev, e->head_dev, e->seg_dev, e->logits_dev};
+                    e->span_q_dev, e->head_dev, e->seg_dev, e->logits_dev, e->tokw_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -1145,6 +1264,159 @@ int css_encoder_forward_pairs_dev(css_encoder* e, const int32_t* ids_dev, const 
     DeviceGuard g(e->device);
     if ((rc = ensure_acts(e, total_tokens, B)) != CSS_OK) return rc;
     return forward_pairs_any(e, ids_dev, cu_dev, seg_starts_dev, B, total_tokens, max_len, logits_out_dev, (hipStream_t)stream);
+}
+
+int css_encoder_set_token_projection(css_encoder* e, const float* W, int P) {
+    CSS_REQUIRE(e, "css_encoder_set_token_projection: NULL argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!W) {
+        e->tok_p = 0;
+        return CSS_OK;
+    }
+    CSS_REQUIRE(P % 32 == 0 && P >= 32 && P <= kTokMaxP,
+                "css_encoder_set_token_projection: P=%d must be a multiple of 32 in [32, %d]", P, kTokMaxP);
+    const size_t H = e->cfg.hidden;
+    DeviceGuard g(e->device);
+    if (!e->tokw_dev) CSS_HIP_TRY(hipMalloc((void**)&e->tokw_dev, (size_t)kTokMaxP * H * 4));
+    e->tok_p = 0;   // (a failed copy leaves no half-replaced projection in use)
+    // the stream is idle between calls (every host entry point ends with a synchronise)
+    CSS_HIP_TRY(hipMemcpy(e->tokw_dev, W, (size_t)P * H * 4, hipMemcpyHostToDevice));
+    e->tok_p = P;
+    return CSS_OK;
+}
+
+int css_encoder_token_dim(css_encoder* e) {
+    if (!e) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return token_dim(e);
+}
+
+int css_encoder_forward_tokens(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int normalize, uint16_t* tok_out,
+                               float* seq_out) {
+    CSS_REQUIRE(e && ids && cu && tok_out, "css_encoder_forward_tokens: NULL argument");
+    int max_len = 0;
+    int rc = check_batch(e, ids, cu, B, &max_len);
+    if (rc != CSS_OK) return rc;
+    const int T = cu[B];
+    const size_t H = e->cfg.hidden;
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard g(e->device);
+    const size_t P = token_dim(e);
+    if ((rc = ensure_acts(e, T, B)) != CSS_OK || (rc = e->li_tok.grow((size_t)T * P)) != CSS_OK) return rc;
+    hipStream_t st = e->stream;
+    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
+    // eager launches (the tiny-batch graphs replay css_encoder_forward only)
+    if ((rc = forward_any(e, e->ids_dev, e->cu_dev, B, T, max_len, normalize, e->out_dev, st)) != CSS_OK) return rc;
+    if ((rc = write_tokens(e, T, normalize, e->li_tok.p, st)) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(tok_out, e->li_tok.p, (size_t)T * P * 2, hipMemcpyDeviceToHost, st));
+    if (seq_out) CSS_HIP_TRY(hipMemcpyAsync(seq_out, e->out_dev, (size_t)B * H * 4, hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    return CSS_OK;
+}
+
+int css_encoder_forward_tokens_dev(css_encoder* e, const int32_t* ids_dev, const int32_t* cu_dev, int B, int total_tokens,
+                                   int max_len, int normalize, uint16_t* tok_out_dev, float* seq_out_dev, void* stream) {
+    CSS_REQUIRE(e && ids_dev && cu_dev && tok_out_dev, "css_encoder_forward_tokens_dev: NULL argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard g(e->device);
+    int rc = ensure_acts(e, total_tokens, B);
+    if (rc != CSS_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // (seq_out NULL: the sequence rows go to the encoder's own buffer)
+    if ((rc = forward_any(e, ids_dev, cu_dev, B, total_tokens, max_len, normalize, seq_out_dev ? seq_out_dev : e->out_dev, st)) != CSS_OK)
+        return rc;
+    return write_tokens(e, total_tokens, normalize, tok_out_dev, st);
+}
+
+int css_encoder_maxsim(css_encoder* e, const uint16_t* q_tok, const int32_t* cu_q, int nq, const uint16_t* d_tok,
+                       const int32_t* cu_d, int nd, const uint8_t* d_keep, const int32_t* pairs, int np, int P,
+                       float* scores_out) {
+    CSS_REQUIRE(e && q_tok && cu_q && d_tok && cu_d && (scores_out || np == 0), "css_encoder_maxsim: NULL argument");
+    CSS_REQUIRE(maxsim_width_ok(P), "css_encoder_maxsim: P=%d must be a multiple of 32 in [32, 128], or 384, or 768", P);
+    int rc = check_maxsim("css_encoder_maxsim", cu_q, nq, cu_d, nd, d_keep, pairs, np);
+    if (rc != CSS_OK) return rc;
+    if (np == 0) return CSS_OK;
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard g(e->device);
+    hipStream_t st = e->stream;
+    const size_t ndt = (size_t)cu_d[nd];
+    if ((rc = e->li_tok.grow(ndt * P)) != CSS_OK || (rc = e->li_cud.grow((size_t)nd + 1)) != CSS_OK ||
+        (rc = upload_maxsim(e, q_tok, cu_q, nq, d_keep, ndt, pairs, np, P, st)) != CSS_OK)
+        return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(e->li_tok.p, d_tok, ndt * P * 2, hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(e->li_cud.p, cu_d, ((size_t)nd + 1) * 4, hipMemcpyHostToDevice, st));
+    if ((rc = launch_maxsim(e, e->li_q.p, e->li_cuq.p, nq, e->li_tok.p, e->li_cud.p, nd, d_keep ? e->li_keep.p : nullptr,
+                            e->li_pairs.p, np, P, e->li_scores.p, st)) != CSS_OK)
+        return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(scores_out, e->li_scores.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    return CSS_OK;
+}
+
+int css_encoder_maxsim_dev(css_encoder* e, const uint16_t* q_tok_dev, const int32_t* cu_q_dev, int nq, const uint16_t* d_tok_dev,
+                           const int32_t* cu_d_dev, int nd, const uint8_t* d_keep_dev, const int32_t* pairs_dev, int np, int P,
+                           float* scores_out_dev, void* stream) {
+    CSS_REQUIRE(e && q_tok_dev && cu_q_dev && d_tok_dev && cu_d_dev && (np == 0 || (pairs_dev && scores_out_dev)),
+                "css_encoder_maxsim_dev: NULL argument");
+    CSS_REQUIRE(maxsim_width_ok(P), "css_encoder_maxsim_dev: P=%d must be a multiple of 32 in [32, 128], or 384, or 768", P);
+    CSS_REQUIRE(nq >= 1 && nd >= 1 && np >= 0, "css_encoder_maxsim_dev: need nq >= 1, nd >= 1, np >= 0 (got %d, %d, %d)", nq, nd, np);
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard g(e->device);
+    return launch_maxsim(e, q_tok_dev, cu_q_dev, nq, d_tok_dev, cu_d_dev, nd, d_keep_dev, pairs_dev, np, P, scores_out_dev,
+                         (hipStream_t)stream);
+}
+
+int css_encoder_forward_maxsim(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, const uint16_t* q_tok,
+                               const int32_t* cu_q, int nq, const uint8_t* d_keep, const int32_t* pairs, int np,
+                               float* scores_out, uint16_t* tok_out) {
+    CSS_REQUIRE(e && ids && cu && q_tok && cu_q && (scores_out || np == 0), "css_encoder_forward_maxsim: NULL argument");
+    int max_len = 0;
+    int rc = check_batch(e, ids, cu, B, &max_len);
+    if (rc != CSS_OK) return rc;
+    if ((rc = check_maxsim("css_encoder_forward_maxsim", cu_q, nq, cu, B, d_keep, pairs, np)) != CSS_OK) return rc;
+    const int T = cu[B];
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard g(e->device);
+    const int P = token_dim(e);
+    hipStream_t st = e->stream;
+    if ((rc = ensure_acts(e, T, B)) != CSS_OK || (rc = e->li_tok.grow((size_t)T * P)) != CSS_OK ||
+        (rc = upload_maxsim(e, q_tok, cu_q, nq, d_keep, (size_t)T, pairs, np, P, st)) != CSS_OK)
+        return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
+    // eager launches (the tiny-batch graphs replay css_encoder_forward only)
+    if ((rc = forward_any(e, e->ids_dev, e->cu_dev, B, T, max_len, 1, e->out_dev, st)) != CSS_OK) return rc;
+    if ((rc = write_tokens(e, T, 1, e->li_tok.p, st)) != CSS_OK) return rc;
+    if ((rc = launch_maxsim(e, e->li_q.p, e->li_cuq.p, nq, e->li_tok.p, e->cu_dev, B, d_keep ? e->li_keep.p : nullptr,
+                            e->li_pairs.p, np, P, e->li_scores.p, st)) != CSS_OK)
+        return rc;
+    if (np) CSS_HIP_TRY(hipMemcpyAsync(scores_out, e->li_scores.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+    if (tok_out) CSS_HIP_TRY(hipMemcpyAsync(tok_out, e->li_tok.p, (size_t)T * P * 2, hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    return CSS_OK;
+}
+
+int css_encoder_forward_maxsim_dev(css_encoder* e, const int32_t* ids_dev, const int32_t* cu_dev, int B, int total_tokens,
+                                   int max_len, const uint16_t* q_tok_dev, const int32_t* cu_q_dev, int nq,
+                                   const uint8_t* d_keep_dev, const int32_t* pairs_dev, int np, float* scores_out_dev,
+                                   uint16_t* tok_out_dev, void* stream) {
+    CSS_REQUIRE(e && ids_dev && cu_dev && q_tok_dev && cu_q_dev && (np == 0 || (pairs_dev && scores_out_dev)),
+                "css_encoder_forward_maxsim_dev: NULL argument");
+    CSS_REQUIRE(nq >= 1 && np >= 0, "css_encoder_forward_maxsim_dev: need nq >= 1, np >= 0 (got %d, %d)", nq, np);
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard g(e->device);
+    const int P = token_dim(e);
+    int rc = ensure_acts(e, total_tokens, B);
+    // (tok_out NULL: the token rows stay in the encoder's own buffer; growing it frees the old one, so work that an
+    // earlier call enqueued on another stream must have finished, as for the activations)
+    if (rc == CSS_OK && !tok_out_dev) rc = e->li_tok.grow((size_t)total_tokens * P);
+    if (rc != CSS_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    bf16_t* tok = tok_out_dev ? tok_out_dev : e->li_tok.p;
+    if ((rc = forward_any(e, ids_dev, cu_dev, B, total_tokens, max_len, 1, e->out_dev, st)) != CSS_OK) return rc;
+    if ((rc = write_tokens(e, total_tokens, 1, tok, st)) != CSS_OK) return rc;
+    return launch_maxsim(e, q_tok_dev, cu_q_dev, nq, tok, cu_dev, B, d_keep_dev, pairs_dev, np, P, scores_out_dev, st);
 }
 
 }  // extern "C"

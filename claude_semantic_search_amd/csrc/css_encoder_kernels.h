@@ -2237,6 +2237,240 @@ __global__ __launch_bounds__(256) void k_span_pool_ln(const bf16_t* __restrict__
     span_write<H>(acc, te - tb, normalize, q, out ? out + (size_t)s * H : nullptr, scores ? scores + s : nullptr);
 }
 
+// ---------------------------------------------------------------- token vectors (late interaction)
+// css_encoder_forward_tokens: one bf16 row per TOKEN, tok[t] = W h_t (W [P][H] fp32, the ColBERT `linear.weight`) or
+// h_t itself (W == NULL, P = H), then v / max(||v||, 1e-12) when normalize, rounded to bf16 once.  One block of 256
+// threads per 16 consecutive GLOBAL tokens -- one block row of the blocked layout, so the folded path reads it through
+// pool_ln_rows, where every class t % 16 then holds exactly one token.  No atomics, every sum in a fixed order.
+//
+// tok_write, the epilogue both kernels share: rows[q][c] = the fp32 LayerNorm output of token t0 + q (barrier done).
+// Projection on v_mfma_f32_16x16x4_f32 (exact fp32 fma chains; DESIGN.md 3.3d has the measurement): tokens are the rows
+// of A, 16 rows of W the columns of B, wave w takes the column tiles w, w + 4.  A lane reads float4 at k0 + 4 (lane >> 4)
+// from its token row (LDS) and its W row (global, L2 resident) and feeds the four elements to four MFMAs: the k
+// assignment only has to agree between A and B.  Two accumulators alternate (the dependent latency of this MFMA is
+// longer than its issue interval) and are added at the end.
+constexpr int kTokMaxP = 128;   // widest projection
+template <int H>
+__device__ __forceinline__ void tok_write(const float (&rows)[16][H + 8], int t0, int T, const float* __restrict__ W, int P,
+                                          int normalize, bf16_t* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float proj[16][kTokMaxP + 4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (W != nullptr) {   // (uniform over the grid)
+        const int r = lane & 15, g = lane >> 4;
+        for (int n = wave; n < P / 16; n += 4) {
+            v4f acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            const float* wrow = W + (size_t)(n * 16 + r) * H + 4 * g;
+#pragma unroll 4
+            for (int k0 = 0; k0 < H; k0 += 16) {
+                const float4 a = *reinterpret_cast<const float4*>(&rows[r][k0 + 4 * g]);
+                const float4 w = *reinterpret_cast<const float4*>(wrow + k0);
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w.x, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w.y, acc1, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w.z, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w.w, acc1, 0, 0, 0);
+            }
+            // C/D: column (output) lane & 15, row (token) 4 (lane >> 4) + i
+#pragma unroll
+            for (int i = 0; i < 4; ++i) proj[4 * g + i][n * 16 + r] = acc0[i] + acc1[i];
+        }
+        __syncthreads();
+    }
+    // thread (token tid >> 4, sub = tid & 15) owns the column pairs 2 sub + 32 i of its token
+    const int tok = tid >> 4, sub = tid & 15;
+    const float* src = W != nullptr ? &proj[tok][0] : &rows[tok][0];
+    float ss = 0.f;
+    for (int c = 2 * sub; c < P; c += 32) ss += src[c] * src[c] + src[c + 1] * src[c + 1];
+    ss = row16_allsum(ss);
+    const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+    if (t0 + tok >= T) return;
+    unsigned* orow = reinterpret_cast<unsigned*>(out + (size_t)(t0 + tok) * P);
+    for (int c = 2 * sub; c < P; c += 32) {
+        const float a = normalize ? src[c] / nrm : src[c], b = normalize ? src[c + 1] / nrm : src[c + 1];
+        orow[c >> 1] = (unsigned)f2bf(a) | ((unsigned)f2bf(b) << 16);
+    }
+}
+
+// Unfolded paths: y [T][H] fp32 token rows (x32).
+template <int H>
+__global__ __launch_bounds__(256) void k_tok_vec(const float* __restrict__ y, int T, const float* __restrict__ W, int P,
+                                                 int normalize, bf16_t* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float rows[16][H + 8];
+    const int t0 = blockIdx.x * 16, tid = threadIdx.x;
+    for (int i = tid; i < 16 * (H / 4); i += 256) {
+        const int r = i / (H / 4), c = i - r * (H / 4);
+        // (tokens beyond the batch: zero rows, never written back)
+        *reinterpret_cast<float4*>(&rows[r][4 * c]) =
+            t0 + r < T ? reinterpret_cast<const float4*>(y + (size_t)(t0 + r) * H)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+    tok_write<H>(rows, t0, T, W, P, normalize, out);
+}
+
+// LayerNorm-folded path: the last pre tensor (bf16, blocked layout) + its row statistics through pool_ln_rows over the
+// tokens [t0, t0 + 16): class q holds token t0 + q alone (0 + x is x), and the last LayerNorm is finished as
+// k_pool_cls_ln does it: gamma[c] (p[c] rs - mu rs) + beta[c].
+template <int H>
+__global__ __launch_bounds__(256) void k_tok_vec_ln(const bf16_t* __restrict__ pre, const long long* __restrict__ stats,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                    float inv_h, float eps, int T, const float* __restrict__ W, int P,
+                                                    int normalize, bf16_t* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float rows[16][H + 8];
+    const int t0 = blockIdx.x * 16, tid = threadIdx.x;
+    pool_ln_rows<H>(pre, stats, inv_h, eps, t0, min(t0 + 16, T), rows);
+    for (int i = tid; i < 16 * H; i += 256) {
+        const int r = i / H, c = i - r * H;
+        rows[r][c] = fmaf(gamma[c], rows[r][c], beta[c]);
+    }
+    __syncthreads();
+    tok_write<H>(rows, t0, T, W, P, normalize, out);
+}
+
+// ---------------------------------------------------------------- MaxSim (late interaction)
+// css_encoder_maxsim: score(pair) = sum over the query's tokens s (ascending, fp32) of the maximum over the doc's kept
+// tokens t of dot(q_s, d_t); bf16 rows of P elements, fp32 accumulation on v_mfma_f32_16x16x32_bf16.
+//
+// Grid (pairs, nsplit), blocks of four waves: block y of a pair takes the doc's tiles of 16 tokens 4 y + w,
+// 4 (y + nsplit) + w, ... (w = its wave).  The host picks nsplit so that few pairs still fill the device (launch_maxsim).
+// The query's rows (<= 64) sit in LDS, rows padded by 16 bytes so that the 16 lanes of a ds_read_b128 group fall into
+// different banks; the doc's rows stream through from global memory.  A = query tokens (rows), B = doc tokens (columns): lane l reads 16 bytes at k = 32 s + 8 (l >> 4)
+// of query row 16 mt + (l & 15) and of doc row 16 tile + (l & 15), and holds C/D of doc column l & 15 for the query rows
+// 16 mt + 4 (l >> 4) + i.  Doc rows past the end are read from the doc's last row and, like the rows with keep == 0,
+// enter the running maximum as -inf.  The maximum is reduced over the 16 lanes of a row group with DPP (row16_allmax),
+// over the waves through LDS.  nsplit == 1: thread 0 adds the maxima in ascending s.  nsplit > 1: the block leaves its
+// 64 maxima in part[pair][y][64] and k_maxsim_sum takes the maximum over y and adds in ascending s.  A maximum is
+// order-free and the sum has one order, so the bits do not depend on the split.  Indices are clamped into range (the _dev entry point cannot check
+// them); a doc without a kept token, or an empty query or doc, scores 0.
+constexpr int kMaxsimQ = 64;   // query tokens at most
+template <int P>
+constexpr int maxsim_lds_bytes() { return kMaxsimQ * (P * 2 + 16) + 4 * kMaxsimQ * 4; }
+__device__ __forceinline__ float row16_allmax(float v) {   // the DPP steps of row16_allsum
+    v = fmaxf(v, dpp_f32<0xB1>(v));
+    v = fmaxf(v, dpp_f32<0x4E>(v));
+    v = fmaxf(v, dpp_f32<0x141>(v));
+    v = fmaxf(v, dpp_f32<0x140>(v));
+    return v;
+}
+template <int P>
+__global__ __launch_bounds__(256) void k_maxsim(const bf16_t* __restrict__ q_tok, const int32_t* __restrict__ cu_q, int nq,
+                                                const bf16_t* __restrict__ d_tok, const int32_t* __restrict__ cu_d, int nd,
+                                                const uint8_t* __restrict__ keep, const int32_t* __restrict__ pairs,
+                                                float* __restrict__ scores, float* __restrict__ part) {
+    static_assert(P % 32 == 0, "whole K steps of the MFMA");
+    constexpr int QS = P * 2 + 16;   // bytes per query row in LDS
+    extern __shared__ __attribute__((aligned(16))) char maxsim_smem[];
+    char* qs = maxsim_smem;
+    float* wmax = reinterpret_cast<float*>(maxsim_smem + kMaxsimQ * QS);   // [4][kMaxsimQ]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int pair = blockIdx.x, y = blockIdx.y, nsplit = gridDim.y;
+    const int qi = min(max(pairs[2 * pair], 0), nq - 1), dj = min(max(pairs[2 * pair + 1], 0), nd - 1);
+    const int q0 = cu_q[qi], mq = min(cu_q[qi + 1] - q0, kMaxsimQ);
+    const int d0 = cu_d[dj], md = cu_d[dj + 1] - d0;
+    if (mq <= 0 || md <= 0) {   // (uniform over the block; nsplit > 1: -inf maxima, which k_maxsim_sum scores 0)
+        if (nsplit == 1 && tid == 0) scores[pair] = 0.f;
+        if (nsplit > 1 && tid < kMaxsimQ) part[((size_t)pair * nsplit + y) * kMaxsimQ + tid] = -__builtin_inff();
+        return;
+    }
+    const int MT = (mq + 15) >> 4;
+    for (int i = tid; i < MT * 16 * (P / 8); i += 256) {
+        const int r = i / (P / 8), c = i - r * (P / 8);
+        // (rows beyond the query inside its last tile: zeros; their results are never read)
+        *reinterpret_cast<uint4*>(qs + r * QS + 16 * c) =
+            r < mq ? *reinterpret_cast<const uint4*>(q_tok + (size_t)(q0 + r) * P + 8 * c) : make_uint4(0u, 0u, 0u, 0u);
+    }
+    __syncthreads();
+    const float ninf = -__builtin_inff();
+    const int lr = lane & 15, g = lane >> 4;
+    v4f run[4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) run[mt] = v4f{ninf, ninf, ninf, ninf};
+    // This wave's tiles are first, first + stride, ...; a tile's K steps go in chunks of CH.  The doc fragments of chunk
+    // it + 1 (of the same tile or the next) are loaded before the MFMAs of chunk it, so a wave never waits for one
+    // tile's loads with nothing else in flight.
+    constexpr int KS = P / 32, CH = KS < 4 ? KS : 4, NCH = KS / CH;
+    static_assert(KS % CH == 0, "whole chunks");
+    const int ntiles = (md + 15) >> 4;
+    const int first = 4 * y + wave, stride = 4 * nsplit;
+    const int total = ntiles > first ? (ntiles - first + stride - 1) / stride * NCH : 0;
+    const char* qrow = qs + lr * QS + 16 * g;
+    auto load_chunk = [&](int it, v8s(&b)[CH]) {
+        const int tile = first + stride * (it / NCH), c = it % NCH;
+        const bf16_t* drow = d_tok + ((size_t)d0 + min(tile * 16 + lr, md - 1)) * P + 8 * g + 32 * CH * c;
+#pragma unroll
+        for (int j = 0; j < CH; ++j) b[j] = *reinterpret_cast<const v8s*>(drow + 32 * j);
+    };
+    v8s cur[CH], nxt[CH];
+    if (total > 0) load_chunk(0, cur);
+    v4f acc[4];
+    for (int it = 0; it < total; ++it) {
+        if (it + 1 < total) load_chunk(it + 1, nxt);
+        const int tile = first + stride * (it / NCH), c = it % NCH;
+        if (c == 0) {
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) acc[mt] = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                if (mt < MT) {   // (uniform over the block)
+                    const v8s a = *reinterpret_cast<const v8s*>(qrow + mt * 16 * QS + 64 * (CH * c + j));
+                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, cur[j]),
+                                                                      acc[mt], 0, 0, 0);
+                }
+            }
+        }
+        if (c == NCH - 1) {
+            const int tok = tile * 16 + lr;
+            const bool ok = tok < md && (keep == nullptr || keep[(size_t)d0 + tok] != 0);
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) run[mt][i] = fmaxf(run[mt][i], ok ? acc[mt][i] : ninf);
+        }
+#pragma unroll
+        for (int j = 0; j < CH; ++j) cur[j] = nxt[j];
+    }
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float m = row16_allmax(run[mt][i]);
+            if (lr == 0) wmax[wave * kMaxsimQ + mt * 16 + 4 * g + i] = m;
+        }
+    __syncthreads();
+    if (tid < kMaxsimQ)
+        wmax[tid] = fmaxf(fmaxf(wmax[tid], wmax[kMaxsimQ + tid]), fmaxf(wmax[2 * kMaxsimQ + tid], wmax[3 * kMaxsimQ + tid]));
+    if (nsplit > 1) {   // (uniform over the grid)
+        if (tid < kMaxsimQ) part[((size_t)pair * nsplit + y) * kMaxsimQ + tid] = wmax[tid];
+        return;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float s = 0.f;
+        for (int i = 0; i < mq; ++i) s += wmax[i];
+        scores[pair] = wmax[0] == ninf ? 0.f : s;
+    }
+}
+
+// The second step of a split MaxSim: one block of 64 threads per pair; thread s takes the maximum of query token s over
+// the nsplit partial rows, thread 0 adds the maxima in ascending s as k_maxsim does.
+__global__ __launch_bounds__(64) void k_maxsim_sum(const float* __restrict__ part, int nsplit, const int32_t* __restrict__ cu_q,
+                                                   int nq, const int32_t* __restrict__ pairs, float* __restrict__ scores) {
+    __shared__ float mx[kMaxsimQ];
+    const int pair = blockIdx.x, tid = threadIdx.x;
+    const int qi = min(max(pairs[2 * pair], 0), nq - 1);
+    const int mq = min(cu_q[qi + 1] - cu_q[qi], kMaxsimQ);
+    float m = -__builtin_inff();
+    for (int y = 0; y < nsplit; ++y) m = fmaxf(m, part[((size_t)pair * nsplit + y) * kMaxsimQ + tid]);
+    mx[tid] = m;
+    __syncthreads();
+    if (tid == 0) {
+        float s = 0.f;
+        for (int i = 0; i < mq; ++i) s += mx[i];
+        scores[pair] = (mq <= 0 || mx[0] == -__builtin_inff()) ? 0.f : s;
+    }
+}
+
 // ---------------------------------------------------------------- weights
 // [N][K] fp32 -> bf16 with the K order of the blocked activation layout (preblk_kpos): the weights of a GEMM whose A
 // operand is a blocked tensor (FFN2 reading the blocked FFN1 output).

@@ -419,6 +419,118 @@ class MpnetEncoder:
                                                       out.ctypes.data))
         return out
 
+    # -- late interaction: token vectors and MaxSim ------------------------------
+    def set_token_projection(self, W) -> None:
+        """The bias-free token projection of a ColBERT checkpoint (``css_encoder_set_token_projection``): ``W`` [P, H]
+        with P a multiple of 32 in [32, 128]; ``None`` clears it (the token vectors are then the hidden states)."""
+        if W is None:
+            nat.check(nat.lib().css_encoder_set_token_projection(self._h, None, 0))
+            return
+        H = int(self.cfg["hidden"])
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        if W.ndim != 2 or W.shape[1] != H:
+            raise ValueError(f"set_token_projection: W has shape {W.shape}, expected [P, {H}]")
+        nat.check(nat.lib().css_encoder_set_token_projection(self._h, W.ctypes.data, int(W.shape[0])))
+
+    @property
+    def token_dim(self) -> int:
+        """Columns of a token vector: the projection's P, or the hidden size without one."""
+        return int(nat.lib().css_encoder_token_dim(self._h))
+
+    @staticmethod
+    def _pack_ids(batch: Sequence[Sequence[int]]):
+        B = len(batch)
+        lens = np.fromiter((len(s) for s in batch), dtype=np.int32, count=B)
+        cu = np.zeros(B + 1, dtype=np.int32)
+        np.cumsum(lens, out=cu[1:])
+        ids = np.concatenate([np.asarray(s, dtype=np.int32) for s in batch]) if B else np.zeros(0, np.int32)
+        return np.ascontiguousarray(ids, dtype=np.int32), cu
+
+    @staticmethod
+    def _pack_mats(name: str, mats, P: Optional[int] = None):
+        """``(rows [sum m, P] uint16, cu [n + 1] int32, P)`` of a list of bf16 token matrices (uint16 bit patterns)."""
+        mats = [np.asarray(m) for m in mats]
+        for i, m in enumerate(mats):
+            if m.dtype != np.uint16 or m.ndim != 2:
+                raise ValueError(f"{name}[{i}] must be a uint16 [tokens, P] matrix of bf16 bit patterns "
+                                 f"(got dtype {m.dtype}, shape {m.shape})")
+            if P is None:
+                P = int(m.shape[1])
+            if m.shape[1] != P:
+                raise ValueError(f"{name}[{i}] has P={m.shape[1]} columns, expected P={P}")
+        cu = np.zeros(len(mats) + 1, dtype=np.int32)
+        np.cumsum([m.shape[0] for m in mats], out=cu[1:])
+        rows = np.ascontiguousarray(np.concatenate(mats, axis=0)) if mats else np.zeros((0, P or 0), np.uint16)
+        return rows, cu, P
+
+    @staticmethod
+    def _pack_pairs(pairs, nq: int, nd: int) -> np.ndarray:
+        if pairs is None:   # every query against every doc, query-major
+            pairs = [(i, j) for i in range(nq) for j in range(nd)]
+        pr = np.asarray(pairs if len(pairs) else np.zeros((0, 2)), dtype=np.int64)
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise ValueError(f"pairs must be [np, 2] = (query, doc) (got shape {pr.shape})")
+        if pr.size and np.abs(pr).max() >= 2 ** 31:
+            raise ValueError("pair entries must fit int32")
+        return np.ascontiguousarray(pr, dtype=np.int32)
+
+    @staticmethod
+    def _pack_keep(keep, cu_d: np.ndarray) -> Optional[np.ndarray]:
+        if keep is None:
+            return None
+        flat = np.concatenate([np.asarray(k).reshape(-1) != 0 for k in keep]) if len(keep) else np.zeros(0, bool)
+        lens = [int(np.asarray(k).size) for k in keep]
+        if lens != list(np.diff(cu_d)):
+            raise ValueError("keep must hold one flag per doc token (lengths differ from the docs')")
+        return np.ascontiguousarray(flat, dtype=np.uint8)
+
+    def encode_tokens_ids(self, batch: Sequence[Sequence[int]], normalize: bool = True, return_seq: bool = False):
+        """One packed var-len batch through ``css_encoder_forward_tokens``: per sequence its token matrix, uint16
+        [len_b, P] of bf16 bit patterns (``W h_t`` or ``h_t``, unit rows when ``normalize``).  ``return_seq=True`` also
+        returns what ``encode_ids`` returns for the batch."""
+        ids, cu = self._pack_ids(batch)
+        B, P = len(batch), self.token_dim
+        tok = np.empty((int(cu[-1]), P), dtype=np.uint16)
+        seq = np.empty((B, int(self.cfg["hidden"])), dtype=np.float32) if return_seq else None
+        nat.check(nat.lib().css_encoder_forward_tokens(self._h, ids.ctypes.data, cu.ctypes.data, B, 1 if normalize else 0,
+                                                       tok.ctypes.data, seq.ctypes.data if seq is not None else None))
+        mats = [tok[cu[b]:cu[b + 1]] for b in range(B)]
+        return (mats, seq) if return_seq else mats
+
+    def maxsim(self, q_mats, d_mats, pairs=None, keep=None) -> np.ndarray:
+        """``css_encoder_maxsim`` over kept token matrices (no forward pass): float32 scores, one per ``(query, doc)``
+        pair (``pairs=None``: every query against every doc, query-major).  ``keep``: per doc one flag per token, or
+        ``None``."""
+        q, cu_q, P = self._pack_mats("q_mats", q_mats)
+        d, cu_d, P = self._pack_mats("d_mats", d_mats, P)
+        pr = self._pack_pairs(pairs, len(q_mats), len(d_mats))
+        kp = self._pack_keep(keep, cu_d)
+        out = np.empty(pr.shape[0], dtype=np.float32)
+        nat.check(nat.lib().css_encoder_maxsim(self._h, q.ctypes.data, cu_q.ctypes.data, len(q_mats), d.ctypes.data,
+                                               cu_d.ctypes.data, len(d_mats), kp.ctypes.data if kp is not None else None,
+                                               pr.ctypes.data, int(pr.shape[0]), int(P or 0), out.ctypes.data))
+        return out
+
+    def score_late_ids(self, batch: Sequence[Sequence[int]], q_mats, pairs=None, keep=None, return_tokens: bool = False):
+        """One packed var-len batch of documents through ``css_encoder_forward_maxsim``: unit token vectors of the
+        batch, then MaxSim of ``q_mats`` against the batch's sequences, in one call.  Returns the float32 scores (with
+        ``return_tokens=True`` also the token matrices)."""
+        ids, cu = self._pack_ids(batch)
+        B, P = len(batch), self.token_dim
+        q, cu_q, _ = self._pack_mats("q_mats", q_mats, P)
+        pr = self._pack_pairs(pairs, len(q_mats), B)
+        kp = self._pack_keep(keep, cu)
+        out = np.empty(pr.shape[0], dtype=np.float32)
+        tok = np.empty((int(cu[-1]), P), dtype=np.uint16) if return_tokens else None
+        nat.check(nat.lib().css_encoder_forward_maxsim(self._h, ids.ctypes.data, cu.ctypes.data, B, q.ctypes.data,
+                                                       cu_q.ctypes.data, len(q_mats),
+                                                       kp.ctypes.data if kp is not None else None, pr.ctypes.data,
+                                                       int(pr.shape[0]), out.ctypes.data,
+                                                       tok.ctypes.data if tok is not None else None))
+        if return_tokens:
+            return out, [tok[cu[b]:cu[b + 1]] for b in range(B)]
+        return out
+
     def best_passages(self, query_vec, texts: Sequence[str], n: int = 1, min_tokens: int = 8, max_tokens: int = 64,
                       normalize: bool = True):
         """``List[List[Passage]]``: per text its ``n`` best passages against ``query_vec``, best first, ties by position

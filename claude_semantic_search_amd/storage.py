@@ -1033,7 +1033,9 @@ class HybridStorage:
         ``Reranked`` carries the plain ``SearchResult`` (its bi-encoder ``similarity`` untouched), the reranker's
         ``score`` and ``rank_before``, the hit's position in the plain ranking.  Tombstones, filters and
         ``similarity_threshold`` behave as in ``search``; the reranker's hidden size need not match the index.  A chunk
-        the plain search ranks below ``fetch`` is never seen: re-ranking reorders, it does not retrieve."""
+        the plain search ranks below ``fetch`` is never seen: re-ranking reorders, it does not retrieve.
+        ``reranker`` is any object with ``predict(pairs)``: a ``LateInteraction`` serves as well (the query is encoded
+        once, every hit gets one text-only forward pass and a MaxSim score)."""
         cfg = config or SearchConfig()
         if cfg.top_k <= 0:
             return []

@@ -734,6 +734,56 @@ int css_encoder_forward_pairs_dev(css_encoder* enc, const int32_t* input_ids_dev
                                   const int32_t* seg_starts_dev, int B, int total_tokens, int max_len,
                                   float* logits_out_dev, void* stream);
 
+/* ---- late-interaction re-ranking (ColBERT-style MaxSim): one vector per token ----
+ * score(query, doc) = sum over the query's tokens s of max over the doc's kept tokens t of dot(q_s, d_t).  The doc side
+ * does not depend on the query: token matrices can be formed once (css_encoder_forward_tokens), kept by the caller and
+ * scored later without a forward pass (css_encoder_maxsim).
+ *
+ * Token projection W [P, H] row-major, host fp32 (the bias-free `linear.weight` of a ColBERT checkpoint); P a multiple
+ * of 32 in [32, 128].  W == NULL clears it: the token vectors are then the hidden states themselves (P = H).  Separate
+ * from css_encoder_load_weights, both architectures.  May be called again.  css_encoder_token_dim: the current P. */
+int css_encoder_set_token_projection(css_encoder* enc, const float* W_host /* [P,H]; NULL clears */, int P);
+int css_encoder_token_dim(css_encoder* enc);
+/* Packed var-len batch as css_encoder_forward.  tok_out [total_tokens, P] bf16: row t is W h_t (h_t without a
+ * projection) of the final hidden state of token t, formed with fp32 accumulation from the fp32 LayerNorm output,
+ * scaled to v / max(||v||, 1e-12) when normalize != 0, then rounded to bf16 once (round to nearest even).
+ * seq_out [B, hidden] (may be NULL): exactly what css_encoder_forward writes.  No atomics: the same call gives the
+ * same bits.  The tiny-batch graphs of css_encoder_forward are not used, created or dropped by this call.
+ * _dev: device pointers (tok_out 16-byte aligned), enqueued on `stream` without a synchronise. */
+int css_encoder_forward_tokens(css_encoder* enc, const int32_t* input_ids_host, const int32_t* cu_seqlens_host, int B,
+                               int normalize, uint16_t* tok_out_host, float* seq_out_host);
+int css_encoder_forward_tokens_dev(css_encoder* enc, const int32_t* input_ids_dev, const int32_t* cu_seqlens_dev, int B,
+                                   int total_tokens, int max_len, int normalize, uint16_t* tok_out_dev, float* seq_out_dev,
+                                   void* stream);
+/* MaxSim over token matrices that the caller kept: no forward pass.  q_tok [sum mq, P] / d_tok [sum md, P] bf16 rows,
+ * cu_q [nq + 1] / cu_d [nd + 1] their offsets (cu[0] = 0), d_keep [sum md] (may be NULL: all kept) the doc tokens that
+ * take part (ColBERT's punctuation skiplist), pairs [np][2] int32 = (query, doc), scores_out [np] fp32.
+ * bf16 operands, fp32 accumulation, the per-query-token maxima added in ascending s in fp32; bit reproducible.
+ * P is a multiple of 32 in [32, 128], or 384, or 768 (any encoder handle serves any such P).  Every query has 1..64
+ * tokens, every doc at least one kept token.  Pairs may repeat, come in any order and leave queries or docs unused;
+ * np == 0 is allowed.  The host form checks all of that before anything is enqueued and names the bad query, doc or
+ * pair.  _dev: device pointers (token rows 16-byte aligned), enqueued on `stream` without a synchronise; indices are
+ * clamped into range, a query's tokens beyond 64 are ignored, and a doc with no kept token scores 0.
+ * With few pairs a doc is spread over several blocks, whose partial maxima live in a buffer of the encoder's that only
+ * grows; growing frees the old one, so work that an earlier _dev call enqueued on another stream must have finished
+ * (as for the activations of css_encoder_forward_dev).  The result does not depend on the spread, bit for bit. */
+int css_encoder_maxsim(css_encoder* enc, const uint16_t* q_tok_host, const int32_t* cu_q_host, int nq,
+                       const uint16_t* d_tok_host, const int32_t* cu_d_host, int nd, const uint8_t* d_keep_host,
+                       const int32_t* pairs_host, int np, int P, float* scores_out_host);
+int css_encoder_maxsim_dev(css_encoder* enc, const uint16_t* q_tok_dev, const int32_t* cu_q_dev, int nq,
+                           const uint16_t* d_tok_dev, const int32_t* cu_d_dev, int nd, const uint8_t* d_keep_dev,
+                           const int32_t* pairs_dev, int np, int P, float* scores_out_dev, void* stream);
+/* css_encoder_forward_tokens with normalize = 1 over the batch, then css_encoder_maxsim with the batch's sequences as
+ * the docs (cu_d = cu_seqlens, nd = B; q_tok has the encoder's P columns), in one host call: nothing per token leaves
+ * the device unless tok_out [total_tokens, P] is given.  Returns the bits that the two calls return. */
+int css_encoder_forward_maxsim(css_encoder* enc, const int32_t* input_ids_host, const int32_t* cu_seqlens_host, int B,
+                               const uint16_t* q_tok_host, const int32_t* cu_q_host, int nq, const uint8_t* d_keep_host,
+                               const int32_t* pairs_host, int np, float* scores_out_host, uint16_t* tok_out_host);
+int css_encoder_forward_maxsim_dev(css_encoder* enc, const int32_t* input_ids_dev, const int32_t* cu_seqlens_dev, int B,
+                                   int total_tokens, int max_len, const uint16_t* q_tok_dev, const int32_t* cu_q_dev, int nq,
+                                   const uint8_t* d_keep_dev, const int32_t* pairs_dev, int np, float* scores_out_dev,
+                                   uint16_t* tok_out_dev, void* stream);
+
 /* bf16 attention computes softmax rows as exp2(score) / sum WITHOUT a running maximum while every row sum of a
  * block stays in (1 / range, range) and repeats the block with the running-maximum (online) softmax otherwise --
  * same result, the guard only protects the fp32 range.  Default 2^100 (|logit| < 69); range = 0 always takes the
