@@ -49,6 +49,9 @@ _LAZY = {
     "MpnetEncoder": ".mpnet_encoder",
     "CrossEncoder": ".cross_encoder",
     "LateInteraction": ".late_interaction",
+    "SparseEncoder": ".sparse_encoder",
+    "SparseVector": ".sparse_encoder",
+    "sparse_dot_numpy": ".sparse_encoder",
     "Reranked": ".storage",
     "Passage": ".passages",
     "split_passages": ".passages",

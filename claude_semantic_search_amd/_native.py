@@ -185,6 +185,13 @@ PROTOTYPES = {
                                            c_int, c_void_p, c_void_p]),
     "css_encoder_forward_maxsim_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                                c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "css_encoder_set_mlm_head": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_encoder_vocab_max": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "css_encoder_vocab_max_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "css_encoder_forward_sparse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
+    "css_encoder_forward_sparse_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "css_encoder_debug_read": (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),
     "css_encoder_set_attention_range": (c_int, [c_void_p, c_float]),
     "css_mpnet_rel_bucket": (c_int, [c_int, c_int, c_int]),

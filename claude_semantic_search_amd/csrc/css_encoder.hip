@@ -14,6 +14,8 @@
 // weights are finalised), no relative position bias, and mean or CLS pooling (css_encoder_cfg.arch / .pooling).
 // css_encoder_forward_pairs (BERT cross-encoders) runs the same stack with a per-sequence segment start (type-1 tokens
 // take `tdelta` in the embedding kernels), CLS rows without normalisation, then k_ce_head.
+// css_encoder_forward_sparse (BERT masked-LM checkpoints) follows the stack with the head's transform (GEMM + GELU,
+// k_mlm_ln), k_vocab_max (decoder GEMM with the maximum over each sequence's tokens in its epilogue) and k_vocab_topm.
 // Residual stream / LayerNorm / softmax / pooling are fp32; GEMM and attention
 // operands are bf16 (MFMA) in the product mode, fp32 in the verification mode.
 #include "css_common.h"
@@ -152,6 +154,20 @@ struct css_encoder {
     css::DevBuf<int32_t> li_cuq, li_cud, li_pairs;
     css::DevBuf<uint8_t> li_keep;
     css::DevBuf<float> li_scores, li_part;   // li_part: partial maxima [np][nsplit][64] of a split MaxSim launch
+    // css_encoder_set_mlm_head / css_encoder_forward_sparse / css_encoder_vocab_max: the head's transform
+    // [H*H + 3H] fp32 (Wd, bd, LayerNorm gamma, beta) with Wd's bf16 copy for the LayerNorm-folded path, the decoder
+    // bias c [V], and the decoder E [V][H] in the operand type of the compute mode (mlm_e32 == wemb: tied, fp32 mode;
+    // mlm_e32_own holds an untied fp32 decoder).  sp_*: the host entry points' device copies (token rows, their bf16
+    // rounding, offsets) and the results (zmax bit patterns [B][V], terms / weights [B][m], nnz [B]).  Grow-only and
+    // apart from the activations, like li_*: no graph holds them.
+    css::DevBuf<float> mlm_w, mlm_c, mlm_e32_own;
+    css::DevBuf<bf16_t> mlm_wd16, mlm_e16;
+    const float* mlm_e32 = nullptr;
+    bool mlm_set = false;
+    css::DevBuf<float> sp_rows, sp_w;
+    css::DevBuf<bf16_t> sp_g16;
+    css::DevBuf<int32_t> sp_cu, sp_terms, sp_nnz;
+    css::DevBuf<unsigned> sp_z;
     // hipGraph cache for the launch-bound tiny-batch path (generate_single_embedding): key =
     // (B, T, max_len, normalize); a key is run eagerly once, captured on its second use, replayed after
     struct GraphEntry {
@@ -891,6 +907,84 @@ int upload_maxsim(css_encoder* e, const uint16_t* q_tok, const int32_t* cuq, int
     return CSS_OK;
 }
 
+// What the sparse entry points need of the encoder: BERT and a masked-LM head.
+int check_sparse_state(const css_encoder* e, const char* fn) {
+    CSS_REQUIRE(e->cfg.arch == CSS_ENCODER_ARCH_BERT, "%s: the encoder is not a BERT model (the masked-LM head exists for "
+                "arch = BERT only)", fn);
+    if (!e->mlm_set) {
+        css::set_error("%s: no masked-LM head (call css_encoder_set_mlm_head first)", fn);
+        return CSS_ERR_STATE;
+    }
+    return CSS_OK;
+}
+
+// g_t = LayerNorm(gelu(Wd h_t + bd)) over the rows that the forward just enqueued on `st` left behind: fp32 rows into
+// g32 and, in bf16 mode, their one rounding into g16.  Unfolded paths: the fp32 GEMM over x32 (both modes; u in qkv).
+// LayerNorm-folded path: x32 does not exist, so k_tok_vec_ln finishes the last LayerNorm into bf16 rows (ctx), the bf16
+// GEMM forms u (qkv), and g16 may be ctx again (the GEMM has read it by then).
+int mlm_rows(css_encoder* e, int T, float* g32, bf16_t* g16, hipStream_t st) {
+    const css_encoder_cfg& c = e->cfg;
+    const int H = c.hidden;
+    const float *W = e->mlm_w.p, *bd = W + (size_t)H * H, *lg = bd + H, *lb = lg + H;
+    int rc;
+    const dim3 grid((T + 3) / 4), blk(256);
+    if (!e->x32_valid) {
+        const LayerW& L = e->layers.back();
+        {
+            ProfScope ps("enc_mlm_rows", st);
+            hipLaunchKernelGGL(k_tok_vec_ln<768>, dim3((T + 15) / 16), blk, 0, st, (const bf16_t*)e->x16, e->stats[0], L.ln2g,
+                               L.ln2b, 1.0f / H, c.ln_eps, T, (const float*)nullptr, H, 0, (bf16_t*)e->ctx);
+            CSS_LAUNCH_CHECK();
+        }
+        if ((rc = launch_gemm<bf16_t, EPI_GELU>(e->ctx, e->mlm_wd16.p, bd, e->qkv, T, H, H, 0, 1.0f, e->num_cus, st,
+                                                "enc_mlm_dense")) != CSS_OK)
+            return rc;
+        ProfScope ps("enc_mlm_ln", st);
+        hipLaunchKernelGGL((k_mlm_ln<768, bf16_t>), grid, blk, 0, st, (const bf16_t*)e->qkv, lg, lb, c.ln_eps, g32, g16, T);
+        CSS_LAUNCH_CHECK();
+        return CSS_OK;
+    }
+    if ((rc = launch_gemm<float, EPI_GELU>(e->x32, W, bd, e->qkv, T, H, H, 0, 1.0f, e->num_cus, st, "enc_mlm_dense")) != CSS_OK)
+        return rc;
+    ProfScope ps("enc_mlm_ln", st);
+    if (H == 384) hipLaunchKernelGGL((k_mlm_ln<384, float>), grid, blk, 0, st, (const float*)e->qkv, lg, lb, c.ln_eps, g32, g16, T);
+    else hipLaunchKernelGGL((k_mlm_ln<768, float>), grid, blk, 0, st, (const float*)e->qkv, lg, lb, c.ln_eps, g32, g16, T);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// zmax [B][V] (bit patterns) of the token rows `rows` ([T][H], bf16 in bf16 mode, fp32 in fp32 mode): zero fill, then
+// k_vocab_max.  The fill makes every call start from nothing, whatever an earlier call left in the buffer.
+int launch_vocab_max(css_encoder* e, const void* rows, const int32_t* cu, int B, int T, unsigned* zmax, hipStream_t st) {
+    const css_encoder_cfg& c = e->cfg;
+    CSS_HIP_TRY(hipMemsetAsync(zmax, 0, (size_t)B * c.vocab * 4, st));
+    ProfScope ps("enc_vocab_max", st);
+    const dim3 grid((c.vocab + 127) / 128, (T + 127) / 128), blk(256);
+    if (c.compute == 0)
+        hipLaunchKernelGGL(k_vocab_max<bf16_t>, grid, blk, 0, st, (const bf16_t*)rows, cu, B, T, (const bf16_t*)e->mlm_e16.p,
+                           (const float*)e->mlm_c.p, c.vocab, c.hidden, zmax);
+    else
+        hipLaunchKernelGGL(k_vocab_max<float>, grid, blk, 0, st, (const float*)rows, cu, B, T, e->mlm_e32, (const float*)e->mlm_c.p,
+                           c.vocab, c.hidden, zmax);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// Forward, head, vocabulary maximum and top-m on `st`.  g32: where the fp32 rows g go (the caller's rows_out, or
+// pre32, which is free after the forward); zmax: the caller's dense_out or sp_z.
+int forward_sparse_any(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int T, int max_len, int m, int32_t* terms,
+                       float* weights, int32_t* nnz, unsigned* zmax, float* g32, hipStream_t st) {
+    int rc = forward_any(e, ids, cu, B, T, max_len, 0, e->out_dev, st);
+    if (rc != CSS_OK) return rc;
+    const bool bf = e->cfg.compute == 0;
+    if ((rc = mlm_rows(e, T, g32, bf ? (bf16_t*)e->ctx : nullptr, st)) != CSS_OK) return rc;
+    if ((rc = launch_vocab_max(e, bf ? (const void*)e->ctx : (const void*)g32, cu, B, T, zmax, st)) != CSS_OK) return rc;
+    ProfScope ps("enc_vocab_topm", st);
+    hipLaunchKernelGGL(k_vocab_topm, dim3(B), dim3(256), 0, st, (const unsigned*)zmax, e->cfg.vocab, m, terms, weights, nnz);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -916,7 +1010,8 @@ int css_encoder_create(const css_encoder_cfg* cfg, int device, css_encoder** out
     CSS_REQUIRE(cfg->max_seq_len >= 1 && cfg->max_seq_len <= 512, "css_encoder_create: max_seq_len outside [1, 512]");
     CSS_REQUIRE(cfg->max_pos >= cfg->max_seq_len + pos_offset(*cfg), "css_encoder_create: max_pos must be >= max_seq_len + %d",
                 pos_offset(*cfg));
-    CSS_REQUIRE(cfg->vocab >= 4 && (bert || (cfg->rel_buckets >= 4 && cfg->rel_buckets % 4 == 0)),
+    // (a vocabulary of one row, the pad id, runs no forward pass, and css_encoder_vocab_max needs none)
+    CSS_REQUIRE(cfg->vocab >= 1 && (bert || (cfg->rel_buckets >= 4 && cfg->rel_buckets % 4 == 0)),
                 "css_encoder_create: bad vocab / rel_buckets");
     CSS_REQUIRE(cfg->pad_id >= 0 && cfg->pad_id < cfg->vocab, "css_encoder_create: pad_id outside the vocabulary");
     CSS_REQUIRE(cfg->compute == 0 || cfg->compute == 1, "css_encoder_create: compute must be 0 (bf16) or 1 (fp32)");
@@ -1417,6 +1512,162 @@ int css_encoder_forward_maxsim_dev(css_encoder* e, const int32_t* ids_dev, const
     if ((rc = forward_any(e, ids_dev, cu_dev, B, total_tokens, max_len, 1, e->out_dev, st)) != CSS_OK) return rc;
     if ((rc = write_tokens(e, total_tokens, 1, tok, st)) != CSS_OK) return rc;
     return launch_maxsim(e, q_tok_dev, cu_q_dev, nq, tok, cu_dev, B, d_keep_dev, pairs_dev, np, P, scores_out_dev, st);
+}
+
+int css_encoder_set_mlm_head(css_encoder* e, const float* dense_w, const float* dense_b, const float* ln_g, const float* ln_b,
+                             const float* decoder_w, const float* decoder_b) {
+    CSS_REQUIRE(e && dense_w && dense_b && ln_g && ln_b && decoder_b, "css_encoder_set_mlm_head: NULL argument");
+    CSS_REQUIRE(e->cfg.arch == CSS_ENCODER_ARCH_BERT, "css_encoder_set_mlm_head: the encoder is not a BERT model (the "
+                "masked-LM head exists for arch = BERT only)");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!decoder_w && !e->weights_ready) {
+        css::set_error("css_encoder_set_mlm_head: a tied decoder (decoder_w == NULL) needs the word embeddings: load the "
+                       "weights first");
+        return CSS_ERR_STATE;
+    }
+    DeviceGuard g(e->device);
+    const size_t H = e->cfg.hidden, V = e->cfg.vocab;
+    const bool bf = e->cfg.compute == 0;
+    int rc;
+    css::DevBuf<float> tmp;       // bf16 mode, untied: the fp32 decoder lives until its bf16 copy is made
+    css::DevBuf<float>& own = bf ? tmp : e->mlm_e32_own;   // where an untied fp32 decoder goes
+    // every allocation first: a refusal here leaves the current head in place (the buffers have one size per encoder, so
+    // a head that is in use is never reallocated)
+    if ((rc = e->mlm_w.grow_exact(H * H + 3 * H, "hipMalloc(mlm head)")) != CSS_OK ||
+        (rc = e->mlm_c.grow_exact(V, "hipMalloc(mlm head)")) != CSS_OK ||
+        (bf && ((rc = e->mlm_wd16.grow_exact(H * H, "hipMalloc(mlm head)")) != CSS_OK ||
+                (rc = e->mlm_e16.grow_exact(V * H, "hipMalloc(mlm decoder)")) != CSS_OK)) ||
+        (decoder_w && (rc = own.grow_exact(V * H, "hipMalloc(mlm decoder)")) != CSS_OK))
+        return rc;
+    // nothing was refused: from here on the old head is being replaced (a failed copy leaves no head in use).  The
+    // stream is idle between calls (every host entry point ends with a synchronise).
+    e->mlm_set = false;
+    float* w = e->mlm_w.p;
+    CSS_HIP_TRY(hipMemcpy(w, dense_w, H * H * 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(w + H * H, dense_b, H * 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(w + H * H + H, ln_g, H * 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(w + H * H + 2 * H, ln_b, H * 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(e->mlm_c.p, decoder_b, V * 4, hipMemcpyHostToDevice));
+    const float* e32 = e->wemb;   // tied: the word embeddings as they are now
+    if (decoder_w) {
+        CSS_HIP_TRY(hipMemcpy(own.p, decoder_w, V * H * 4, hipMemcpyHostToDevice));
+        e32 = own.p;
+    }
+    if (bf) {
+        hipLaunchKernelGGL(k_f32_to_bf16, dim3(1024), dim3(256), 0, e->stream, w, e->mlm_wd16.p, H * H);
+        hipLaunchKernelGGL(k_f32_to_bf16, dim3(1024), dim3(256), 0, e->stream, e32, e->mlm_e16.p, V * H);
+        CSS_LAUNCH_CHECK();
+        CSS_HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    e->mlm_e32 = bf ? nullptr : e32;
+    e->mlm_set = true;
+    return CSS_OK;
+}
+
+int css_encoder_vocab_max(css_encoder* e, const float* rows, const int32_t* cu, int B, float* zmax_out) {
+    CSS_REQUIRE(e && rows && cu && zmax_out, "css_encoder_vocab_max: NULL argument");
+    CSS_REQUIRE(B >= 1, "css_encoder_vocab_max: B < 1");
+    CSS_REQUIRE(cu[0] == 0, "css_encoder_vocab_max: cu_seqlens[0] must be 0");
+    for (int b = 0; b < B; ++b)
+        CSS_REQUIRE(cu[b + 1] - cu[b] >= 1, "css_encoder_vocab_max: sequence %d has length %d (need at least 1)", b,
+                    cu[b + 1] - cu[b]);
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = check_sparse_state(e, "css_encoder_vocab_max");
+    if (rc != CSS_OK) return rc;
+    DeviceGuard g(e->device);
+    const size_t T = (size_t)cu[B], H = e->cfg.hidden, V = e->cfg.vocab;
+    const bool bf = e->cfg.compute == 0;
+    if ((rc = e->sp_rows.grow(T * H)) != CSS_OK || (rc = e->sp_cu.grow((size_t)B + 1)) != CSS_OK ||
+        (rc = e->sp_z.grow((size_t)B * V)) != CSS_OK || (bf && (rc = e->sp_g16.grow(T * H)) != CSS_OK))
+        return rc;
+    hipStream_t st = e->stream;
+    CSS_HIP_TRY(hipMemcpyAsync(e->sp_rows.p, rows, T * H * 4, hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(e->sp_cu.p, cu, ((size_t)B + 1) * 4, hipMemcpyHostToDevice, st));
+    if (bf) {
+        hipLaunchKernelGGL(k_f32_to_bf16, dim3(1024), dim3(256), 0, st, (const float*)e->sp_rows.p, e->sp_g16.p, T * H);
+        CSS_LAUNCH_CHECK();
+    }
+    if ((rc = launch_vocab_max(e, bf ? (const void*)e->sp_g16.p : (const void*)e->sp_rows.p, e->sp_cu.p, B, (int)T, e->sp_z.p,
+                               st)) != CSS_OK)
+        return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(zmax_out, e->sp_z.p, (size_t)B * V * 4, hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    return CSS_OK;
+}
+
+int css_encoder_vocab_max_dev(css_encoder* e, const float* rows_dev, const int32_t* cu_dev, int B, int total_tokens,
+                              float* zmax_out_dev, void* stream) {
+    CSS_REQUIRE(e && rows_dev && cu_dev && zmax_out_dev, "css_encoder_vocab_max_dev: NULL argument");
+    CSS_REQUIRE(B >= 1 && total_tokens >= B, "css_encoder_vocab_max_dev: bad batch (B=%d, tokens=%d)", B, total_tokens);
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = check_sparse_state(e, "css_encoder_vocab_max_dev");
+    if (rc != CSS_OK) return rc;
+    DeviceGuard g(e->device);
+    hipStream_t st = (hipStream_t)stream;
+    const void* rows = rows_dev;
+    if (e->cfg.compute == 0) {
+        // (the bf16 rounding of the rows lives in a buffer of the encoder's that only grows; growing frees the old one,
+        // so work that an earlier call enqueued on another stream must have finished, as for the activations)
+        const size_t n = (size_t)total_tokens * e->cfg.hidden;
+        if ((rc = e->sp_g16.grow(n)) != CSS_OK) return rc;
+        hipLaunchKernelGGL(k_f32_to_bf16, dim3(1024), dim3(256), 0, st, rows_dev, e->sp_g16.p, n);
+        CSS_LAUNCH_CHECK();
+        rows = e->sp_g16.p;
+    }
+    return launch_vocab_max(e, rows, cu_dev, B, total_tokens, reinterpret_cast<unsigned*>(zmax_out_dev), st);
+}
+
+int css_encoder_forward_sparse(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int m, int32_t* terms_out,
+                               float* weights_out, int32_t* nnz_out, float* dense_out, float* rows_out) {
+    CSS_REQUIRE(e && ids && cu && terms_out && weights_out && nnz_out, "css_encoder_forward_sparse: NULL argument");
+    CSS_REQUIRE(m >= 1 && m <= kSparseMaxM, "css_encoder_forward_sparse: m=%d outside [1, %d]", m, kSparseMaxM);
+    int max_len = 0;
+    int rc = check_batch(e, ids, cu, B, &max_len);
+    if (rc != CSS_OK) return rc;
+    const int T = cu[B];
+    const size_t H = e->cfg.hidden, V = e->cfg.vocab;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if ((rc = check_sparse_state(e, "css_encoder_forward_sparse")) != CSS_OK) return rc;
+    DeviceGuard g(e->device);
+    const size_t bm = (size_t)B * m;
+    if ((rc = ensure_acts(e, T, B)) != CSS_OK || (rc = e->sp_z.grow((size_t)B * V)) != CSS_OK ||
+        (rc = e->sp_terms.grow(bm)) != CSS_OK || (rc = e->sp_w.grow(bm)) != CSS_OK || (rc = e->sp_nnz.grow(B)) != CSS_OK)
+        return rc;
+    hipStream_t st = e->stream;
+    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
+    // eager launches (the tiny-batch graphs replay css_encoder_forward only)
+    if ((rc = forward_sparse_any(e, e->ids_dev, e->cu_dev, B, T, max_len, m, e->sp_terms.p, e->sp_w.p, e->sp_nnz.p, e->sp_z.p,
+                                 e->pre32, st)) != CSS_OK)
+        return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(terms_out, e->sp_terms.p, bm * 4, hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipMemcpyAsync(weights_out, e->sp_w.p, bm * 4, hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipMemcpyAsync(nnz_out, e->sp_nnz.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    if (dense_out) CSS_HIP_TRY(hipMemcpyAsync(dense_out, e->sp_z.p, (size_t)B * V * 4, hipMemcpyDeviceToHost, st));
+    if (rows_out) CSS_HIP_TRY(hipMemcpyAsync(rows_out, e->pre32, (size_t)T * H * 4, hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));
+    return CSS_OK;
+}
+
+int css_encoder_forward_sparse_dev(css_encoder* e, const int32_t* ids_dev, const int32_t* cu_dev, int B, int total_tokens,
+                                   int max_len, int m, int32_t* terms_out_dev, float* weights_out_dev, int32_t* nnz_out_dev,
+                                   float* dense_out_dev, float* rows_out_dev, void* stream) {
+    CSS_REQUIRE(e && ids_dev && cu_dev && terms_out_dev && weights_out_dev && nnz_out_dev,
+                "css_encoder_forward_sparse_dev: NULL argument");
+    CSS_REQUIRE(m >= 1 && m <= kSparseMaxM, "css_encoder_forward_sparse_dev: m=%d outside [1, %d]", m, kSparseMaxM);
+    CSS_REQUIRE(B >= 1 && total_tokens >= B, "css_encoder_forward_sparse_dev: bad batch (B=%d, tokens=%d)", B, total_tokens);
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = check_sparse_state(e, "css_encoder_forward_sparse_dev");
+    if (rc != CSS_OK) return rc;
+    DeviceGuard g(e->device);
+    rc = ensure_acts(e, total_tokens, B);
+    // (dense_out NULL: the maxima stay in the encoder's own buffer; growing it frees the old one, so work that an
+    // earlier call enqueued on another stream must have finished, as for the activations)
+    if (rc == CSS_OK && !dense_out_dev) rc = e->sp_z.grow((size_t)B * e->cfg.vocab);
+    if (rc != CSS_OK) return rc;
+    unsigned* z = dense_out_dev ? reinterpret_cast<unsigned*>(dense_out_dev) : e->sp_z.p;
+    return forward_sparse_any(e, ids_dev, cu_dev, B, total_tokens, max_len, m, terms_out_dev, weights_out_dev, nnz_out_dev, z,
+                              rows_out_dev ? rows_out_dev : e->pre32, (hipStream_t)stream);
 }
 
 }  // extern "C"

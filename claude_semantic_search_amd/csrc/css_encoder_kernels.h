@@ -2471,6 +2471,310 @@ __global__ __launch_bounds__(64) void k_maxsim_sum(const float* __restrict__ par
     }
 }
 
+// ---------------------------------------------------------------- learned sparse encoding (masked-LM head)
+// css_encoder_forward_sparse: u_t = gelu(Wd h_t + bd) comes from the encoder's GEMMs; k_mlm_ln is the head's LayerNorm,
+// k_layernorm without a residual: g_t = LayerNorm(u_t) as fp32 rows (out32) and / or rounded to bf16 once (out16).
+template <int H, typename TIn>
+__global__ __launch_bounds__(256) void k_mlm_ln(const TIn* __restrict__ in, const float* __restrict__ gamma,
+                                                const float* __restrict__ beta, float eps, float* __restrict__ out32,
+                                                bf16_t* __restrict__ out16, int T) {
+    static_assert(H % 128 == 0, "float4 columns of a row cover whole 32-lane halves");
+    constexpr int NV = (H / 4 + 63) / 64;
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= T) return;
+    const TIn* xrow = in + (size_t)t * H;
+    float4 v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!ln_col_ok<H>(lane + 64 * i)) continue;
+        v[i] = ln_load4<TIn>(xrow, lane + 64 * i);
+        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    }
+    const float mean = wave_allsum(s) * (1.0f / H);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        if (!ln_col_ok<H>(lane + 64 * i)) continue;
+        const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
+        q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+    }
+    const float rstd = rsqrtf(wave_allsum(q) * (1.0f / H) + eps);
+    const float4* g4 = reinterpret_cast<const float4*>(gamma);
+    const float4* b4 = reinterpret_cast<const float4*>(beta);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        if (!ln_col_ok<H>(lane + 64 * i)) continue;
+        const float4 g = g4[lane + 64 * i], b = b4[lane + 64 * i];
+        float4 o;
+        o.x = (v[i].x - mean) * rstd * g.x + b.x;
+        o.y = (v[i].y - mean) * rstd * g.y + b.y;
+        o.z = (v[i].z - mean) * rstd * g.z + b.z;
+        o.w = (v[i].w - mean) * rstd * g.w + b.w;
+        if (out32) reinterpret_cast<float4*>(out32 + (size_t)t * H)[lane + 64 * i] = o;
+        if (out16) {
+            ushort4 h;
+            h.x = f2bf(o.x); h.y = f2bf(o.y); h.z = f2bf(o.z); h.w = f2bf(o.w);
+            reinterpret_cast<ushort4*>(out16 + (size_t)t * H)[lane + 64 * i] = h;
+        }
+    }
+}
+
+// Vocabulary maximum: zmax[b][v] = max over the tokens t of sequence b of relu(dot(E_v, g_t) + c_v), the [T, V] logits
+// never leaving the registers.  zmax holds the BIT PATTERNS of non-negative floats (zero-filled by the launcher): they
+// order like unsigned integers, so the maximum across waves and blocks is one unsigned atomic maximum, which is
+// order-free: the same call gives the same bits.  Only logits > 0 are sent.
+//
+// Grid (ceil(V / 128), ceil(T / 128)), four waves, wave w the 64 tokens x 64 terms at (64 (w >> 1), 64 (w & 1)) of the
+// block's tile: A = token rows, B = rows of E, both K-contiguous and read from global memory (L1 / L2) one K step ahead
+// of the MFMAs; a lane reads VmOp::KL elements at k0 + KL (lane >> 4) of token row 16 mt + (lane & 15) and of term row
+// 16 nt + (lane & 15) and holds C/D of term lane & 15 for the tokens 16 mt + 4 (lane >> 4) + i.  Rows past T and terms
+// past V are read from the last row (never out of bounds) and never written.
+// Epilogue.  The wave's 64 tokens lie in one sequence (the usual case): the maximum over the 16 registers of a term,
+// then over the four lane groups (two shuffles), c_v added after it (x + c is monotone in x, so the maximum commutes),
+// and ONE atomic wave instruction over 64 consecutive terms.  A sequence boundary inside the 64 tokens: every lane
+// finds the sequence of each of its tokens by bisection of cu_seqlens and sends its positive logits one by one --
+// slow for many very short sequences, and exact.  Sequence numbers are clamped into [0, B), so a bad cu_seqlens on
+// the _dev path cannot write outside zmax.
+template <typename TIn>
+struct VmOp;
+template <>
+struct VmOp<bf16_t> {   // v_mfma_f32_16x16x32_bf16
+    typedef v8s frag;
+    static constexpr int KS = 32, KL = 8;
+    static __device__ __forceinline__ void mma(const frag& a, const frag& b, v4f& acc) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, b), acc, 0, 0, 0);
+    }
+};
+template <>
+struct VmOp<float> {   // four v_mfma_f32_16x16x4_f32 per float4 (the k assignment only has to agree between A and B)
+    typedef float4 frag;
+    static constexpr int KS = 16, KL = 4;
+    static __device__ __forceinline__ void mma(const frag& a, const frag& b, v4f& acc) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+    }
+};
+
+// the sequence b with cu[b] <= row < cu[b + 1] (lengths >= 1: cu is strictly increasing), clamped into [0, B)
+__device__ __forceinline__ int vm_seq_of(const int32_t* __restrict__ cu, int B, int row) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (cu[mid] <= row) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+template <typename TIn>
+__global__ __launch_bounds__(256) void k_vocab_max(const TIn* __restrict__ g, const int32_t* __restrict__ cu, int B, int T,
+                                                   const TIn* __restrict__ E, const float* __restrict__ cvec, int V, int H,
+                                                   unsigned* __restrict__ zmax) {
+    typedef typename VmOp<TIn>::frag frag;
+    constexpr int KS = VmOp<TIn>::KS, KL = VmOp<TIn>::KL;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lr = lane & 15, lg = lane >> 4;
+    const int r0 = blockIdx.y * 128 + 64 * (wave >> 1), c0 = blockIdx.x * 128 + 64 * (wave & 1);
+    if (r0 >= T || c0 >= V) return;   // (uniform over the wave; no barrier follows)
+    const TIn* arow[4];
+    const TIn* brow[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        arow[j] = g + (size_t)min(r0 + 16 * j + lr, T - 1) * H + KL * lg;
+        brow[j] = E + (size_t)min(c0 + 16 * j + lr, V - 1) * H + KL * lg;
+    }
+    v4f acc[4][4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = v4f{0.f, 0.f, 0.f, 0.f};
+    frag a[4], b[4], an[4], bn[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        a[j] = *reinterpret_cast<const frag*>(arow[j]);
+        b[j] = *reinterpret_cast<const frag*>(brow[j]);
+    }
+    for (int k0 = 0; k0 < H; k0 += KS) {   // H is a multiple of KS (384, 768)
+        const int kn = k0 + KS < H ? k0 + KS : k0;   // (the last step reloads its own fragments: no read past a row)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            an[j] = *reinterpret_cast<const frag*>(arow[j] + kn);
+            bn[j] = *reinterpret_cast<const frag*>(brow[j] + kn);
+        }
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) VmOp<TIn>::mma(a[mt], b[nt], acc[mt][nt]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            a[j] = an[j];
+            b[j] = bn[j];
+        }
+    }
+    const int rlast = min(r0 + 64, T) - 1;
+    const int b_lo = vm_seq_of(cu, B, r0), b_hi = vm_seq_of(cu, B, rlast);
+    if (b_lo == b_hi) {
+        // (rows past T repeat row T - 1, a token of this same sequence: they need no mask)
+        float red[4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            float m = acc[0][nt][0];
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) m = fmaxf(m, acc[mt][nt][i]);
+            m = fmaxf(m, __shfl_xor(m, 16));
+            m = fmaxf(m, __shfl_xor(m, 32));
+            red[nt] = m;
+        }
+        // lane l takes term c0 + l: the column group lane >> 4 of the value that lane (l & 15) of every group holds
+        const float m = lg == 0 ? red[0] : lg == 1 ? red[1] : lg == 2 ? red[2] : red[3];
+        const int col = c0 + lane;
+        if (col < V) {
+            const float z = m + cvec[col];
+            if (z > 0.f) atomicMax(zmax + (size_t)b_lo * V + col, __float_as_uint(z));
+        }
+        return;
+    }
+    int seq[4][4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = r0 + 16 * mt + 4 * lg + i;
+            seq[mt][i] = row < T ? vm_seq_of(cu, B, row) : -1;
+        }
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const int col = c0 + 16 * nt + lr;
+        if (col >= V) continue;
+        const float cv = cvec[col];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float z = acc[mt][nt][i] + cv;
+                if (seq[mt][i] >= 0 && z > 0.f) atomicMax(zmax + (size_t)seq[mt][i] * V + col, __float_as_uint(z));
+            }
+    }
+}
+
+// Top-m of one sequence's row of zmax, one block per sequence: the m largest z > 0, best first, ties to the lower term
+// id; terms padded with -1 and weights with 0; nnz = the number of z > 0 before the cut.  Exact selection on the bit
+// patterns: a radix select (four 8-bit passes over the row, which is L2 resident) finds the value of rank
+// min(m, nnz); everything above it is taken, and of its equals the lowest ids.  Where every equal is taken (the last
+// pass counted them; the usual case, values being distinct) no order among them is needed and the row is read strided,
+// as in the passes before; otherwise every thread owns a contiguous id range and a prefix sum over the threads' counts
+// gives each equal its rank (uncoalesced and serial, for ties at the cut only).  The <= 512 survivors are sorted in LDS as
+// (bits << 32 | ~id), a bitonic network over 512 slots.  w = (float) log1p((double) z), on the returned entries only.
+constexpr int kSparseMaxM = 512;
+__global__ __launch_bounds__(256) void k_vocab_topm(const unsigned* __restrict__ zmax, int V, int m, int32_t* __restrict__ terms,
+                                                    float* __restrict__ weights, int32_t* __restrict__ nnz_out) {
+    __shared__ unsigned hist[256], scan[256];
+    __shared__ unsigned long long sel[kSparseMaxM];
+    __shared__ unsigned sh_prefix, sh_remain, sh_cnt, sh_eq;
+    const int tid = threadIdx.x;
+    const unsigned* z = zmax + (size_t)blockIdx.x * V;
+    if (tid == 0) sh_cnt = 0;
+    for (int j = tid; j < kSparseMaxM; j += 256) sel[j] = 0ull;
+    __syncthreads();
+    unsigned cnt = 0;
+    for (int i = tid; i < V; i += 256) cnt += z[i] != 0u;
+    atomicAdd(&sh_cnt, cnt);
+    __syncthreads();
+    const int nnz = (int)sh_cnt;
+    const int want = min(m, nnz);
+    __syncthreads();
+    if (want > 0) {   // (uniform over the block)
+        unsigned prefix = 0, mask = 0, remain = (unsigned)want;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hist[tid] = 0;
+            __syncthreads();
+            for (int i = tid; i < V; i += 256) {
+                const unsigned k = z[i];
+                if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned cum = 0;
+                for (int bin = 255; bin >= 0; --bin) {
+                    const unsigned h = hist[bin];
+                    if (cum + h >= remain) {
+                        sh_prefix = prefix | ((unsigned)bin << shift);
+                        sh_remain = remain - cum;
+                        sh_eq = h;   // (after the last pass: the entries equal to the threshold)
+                        break;
+                    }
+                    cum += h;
+                }
+                sh_cnt = 0;
+            }
+            __syncthreads();
+            prefix = sh_prefix;
+            remain = sh_remain;
+            mask |= 255u << shift;
+            __syncthreads();
+        }
+        const unsigned thr = prefix;              // the value of rank `want` (> 0, since want <= nnz)
+        const unsigned ngt = (unsigned)want - remain;   // entries above it; `remain` of its equals are taken
+        if (sh_eq == remain) {   // (uniform) every equal is taken: ngt + remain = want <= 512 entries, in any order
+            for (int i = tid; i < V; i += 256) {
+                const unsigned k = z[i];
+                if (k >= thr) {
+                    const unsigned pos = atomicAdd(&sh_cnt, 1u);
+                    if (pos < (unsigned)kSparseMaxM) sel[pos] = ((unsigned long long)k << 32) | (0xFFFFFFFFu - (unsigned)i);
+                }
+            }
+        } else {
+            const int seg = (V + 255) / 256, lo = tid * seg, hi = min(lo + seg, V);
+            unsigned eq = 0;
+            for (int i = lo; i < hi; ++i) {
+                const unsigned k = z[i];
+                if (k > thr) {
+                    const unsigned pos = atomicAdd(&sh_cnt, 1u);
+                    if (pos < (unsigned)kSparseMaxM) sel[pos] = ((unsigned long long)k << 32) | (0xFFFFFFFFu - (unsigned)i);
+                } else if (k == thr) {
+                    ++eq;
+                }
+            }
+            scan[tid] = eq;
+            __syncthreads();
+            unsigned rank = 0;
+            for (int j = 0; j < tid; ++j) rank += scan[j];
+            for (int i = lo; i < hi && rank < remain; ++i) {
+                if (z[i] != thr) continue;
+                sel[ngt + rank] = ((unsigned long long)thr << 32) | (0xFFFFFFFFu - (unsigned)i);
+                ++rank;
+            }
+        }
+        __syncthreads();
+        for (int k = 2; k <= kSparseMaxM; k <<= 1) {
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), p = i | j;
+                const unsigned long long x = sel[i], y = sel[p];
+                const bool down = (i & k) == 0;   // this run is sorted largest first
+                if (down ? x < y : x > y) {
+                    sel[i] = y;
+                    sel[p] = x;
+                }
+                __syncthreads();
+            }
+        }
+    }
+    for (int j = tid; j < m; j += 256) {
+        const unsigned long long s = sel[j];
+        const bool ok = j < want;
+        terms[(size_t)blockIdx.x * m + j] = ok ? (int32_t)(0xFFFFFFFFu - (unsigned)(s & 0xFFFFFFFFull)) : -1;
+        weights[(size_t)blockIdx.x * m + j] = ok ? (float)log1p((double)__uint_as_float((unsigned)(s >> 32))) : 0.f;
+    }
+    if (tid == 0) nnz_out[blockIdx.x] = nnz;
+}
+
 // ---------------------------------------------------------------- weights
 // [N][K] fp32 -> bf16 with the K order of the blocked activation layout (preblk_kpos): the weights of a GEMM whose A
 // operand is a blocked tensor (FFN2 reading the blocked FFN1 output).

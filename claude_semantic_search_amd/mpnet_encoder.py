@@ -531,6 +531,63 @@ class MpnetEncoder:
             return out, [tok[cu[b]:cu[b + 1]] for b in range(B)]
         return out
 
+    # -- learned sparse encoding: masked-LM head and vocabulary maximum -------------
+    def set_mlm_head(self, dense_w, dense_b, ln_g, ln_b, decoder_w, decoder_b) -> None:
+        """The masked-LM head of a ``BertForMaskedLM`` (``css_encoder_set_mlm_head``): ``dense_w`` [H, H], ``dense_b``
+        [H], ``ln_g`` / ``ln_b`` [H], ``decoder_w`` [V, H] or ``None`` (tied to the word embeddings as loaded),
+        ``decoder_b`` [V].  May be called again to replace the head."""
+        H, V = int(self.cfg["hidden"]), int(self.cfg["vocab"])
+        arrs = []
+        for name, a, shape in (("dense_w", dense_w, (H, H)), ("dense_b", dense_b, (H,)), ("ln_g", ln_g, (H,)),
+                               ("ln_b", ln_b, (H,)), ("decoder_w", decoder_w, (V, H)), ("decoder_b", decoder_b, (V,))):
+            if a is None and name == "decoder_w":
+                arrs.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"set_mlm_head: {name} has shape {a.shape}, expected {shape}")
+            arrs.append(a)
+        nat.check(nat.lib().css_encoder_set_mlm_head(self._h, *(a.ctypes.data if a is not None else None for a in arrs)))
+
+    def encode_sparse_ids(self, batch: Sequence[Sequence[int]], m: int, return_dense: bool = False,
+                          return_rows: bool = False):
+        """One packed var-len batch through ``css_encoder_forward_sparse``: ``(terms int32 [B, m], weights float32
+        [B, m], nnz int32 [B])`` -- per sequence its ``m`` heaviest vocabulary terms, best first, padded with -1 / 0, and
+        the number of positive terms before the cut.  ``return_dense=True`` appends ``z`` [B, V] (the maxima before
+        ``log1p``), ``return_rows=True`` the head's token rows ``g`` [tokens, H] (fp32, before the bf16 rounding)."""
+        ids, cu = self._pack_ids(batch)
+        B, m = len(batch), int(m)
+        terms = np.empty((B, m), dtype=np.int32)
+        weights = np.empty((B, m), dtype=np.float32)
+        nnz = np.empty(B, dtype=np.int32)
+        dense = np.empty((B, int(self.cfg["vocab"])), dtype=np.float32) if return_dense else None
+        rows = np.empty((int(cu[-1]), int(self.cfg["hidden"])), dtype=np.float32) if return_rows else None
+        nat.check(nat.lib().css_encoder_forward_sparse(self._h, ids.ctypes.data, cu.ctypes.data, B, m, terms.ctypes.data,
+                                                       weights.ctypes.data, nnz.ctypes.data,
+                                                       dense.ctypes.data if dense is not None else None,
+                                                       rows.ctypes.data if rows is not None else None))
+        out = (terms, weights, nnz)
+        if return_dense:
+            out += (dense,)
+        if return_rows:
+            out += (rows,)
+        return out
+
+    def vocab_max(self, rows, cu) -> np.ndarray:
+        """``css_encoder_vocab_max`` (no forward pass): ``z`` [B, V] of the token rows ``rows`` [tokens, H] (taken as the
+        head's ``g``) split into sequences by the offsets ``cu`` [B + 1]."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        cu = np.ascontiguousarray(cu, dtype=np.int32).reshape(-1)
+        H = int(self.cfg["hidden"])
+        if rows.ndim != 2 or rows.shape[1] != H:
+            raise ValueError(f"vocab_max: rows has shape {rows.shape}, expected [tokens, {H}]")
+        if cu.size < 2 or int(cu[-1]) != rows.shape[0]:
+            raise ValueError(f"vocab_max: cu must hold B + 1 >= 2 offsets ending at the row count {rows.shape[0]}")
+        B = cu.size - 1
+        out = np.empty((B, int(self.cfg["vocab"])), dtype=np.float32)
+        nat.check(nat.lib().css_encoder_vocab_max(self._h, rows.ctypes.data, cu.ctypes.data, B, out.ctypes.data))
+        return out
+
     def best_passages(self, query_vec, texts: Sequence[str], n: int = 1, min_tokens: int = 8, max_tokens: int = 64,
                       normalize: bool = True):
         """``List[List[Passage]]``: per text its ``n`` best passages against ``query_vec``, best first, ties by position

@@ -672,6 +672,11 @@ typedef struct css_tensor {
     int64_t numel;
 } css_tensor;
 
+/* css_encoder_create refuses (CSS_ERR_INVALID) a geometry the kernels are not built for: hidden / heads (comments
+ * above), ffn no multiple of 128, num_layers outside [1, 64], max_seq_len outside [1, 512], max_pos too small for
+ * max_seq_len, vocab < 1, pad_id outside the vocabulary, MPNet rel_buckets no positive multiple of 4, compute not 0 / 1.
+ * vocab may be as small as 1 (the masked-LM head's vocabulary maximum is defined for any V >= 1); ids are checked
+ * against it on every call. */
 int css_encoder_create(const css_encoder_cfg* cfg, int device, css_encoder** out);
 int css_encoder_free(css_encoder* enc);
 int css_encoder_load_weights(css_encoder* enc, const css_tensor* tensors, int n);
@@ -783,6 +788,61 @@ int css_encoder_forward_maxsim_dev(css_encoder* enc, const int32_t* input_ids_de
                                    int total_tokens, int max_len, const uint16_t* q_tok_dev, const int32_t* cu_q_dev, int nq,
                                    const uint8_t* d_keep_dev, const int32_t* pairs_dev, int np, float* scores_out_dev,
                                    uint16_t* tok_out_dev, void* stream);
+
+/* ---- learned sparse encoding (SPLADE-style): masked-LM head and a maximum over each sequence's tokens ----
+ * For the final hidden state h_t of token t (the output of the last LayerNorm), with V = cfg.vocab:
+ *   u_t    = gelu(Wd h_t + bd)                          erf GELU, Wd [H, H]
+ *   g_t    = LayerNorm(u_t; gamma, beta, cfg.ln_eps)
+ *   z[b,v] = max over the tokens t of sequence b of relu(dot(E_v, g_t) + c_v)        E [V, H], c [V]
+ *   w[b,v] = (float) log1p((double) z[b,v])
+ * log1p o relu is monotone, so this is SPLADE's max_t log(1 + relu(logit)) with one log1p per kept entry.  Every token
+ * of the packed sequence takes part ([CLS] and [SEP] included).  z >= 0 is kept as a bit pattern in a zero-filled
+ * [B, V] table under an unsigned integer atomic maximum: order-free, so the same call gives the same bits on every
+ * run.  The [total_tokens, V] logits never exist in memory.  log1p is evaluated in fp64 and rounded to fp32 once, on
+ * the returned entries only.
+ * bf16 compute mode: g_t is rounded to bf16 once (nearest even), E is held as a bf16 copy, the products run on
+ * v_mfma_f32_16x16x32_bf16 with fp32 accumulation and c_v is added in fp32 after the accumulation.  The transform is
+ * the fp32 GEMM over the fp32 hidden states on the unfolded paths; on the LayerNorm-folded path (hidden 768, >= 1024
+ * tokens, which never materialises the fp32 hidden states) h_t and u_t are bf16 rows and the GEMM is the bf16 one.
+ * fp32 compute mode (verification): fp32 throughout, products on v_mfma_f32_16x16x4_f32.
+ *
+ * css_encoder_set_mlm_head: host fp32 arguments, the `cls.predictions` tensors of a BertForMaskedLM: dense_w [H, H],
+ * dense_b [H], ln_g / ln_b [H], decoder_w [V, H] and decoder_b [V].  decoder_w == NULL ties the decoder to the word
+ * embeddings (CSS_ERR_STATE without weights): bf16 mode takes its bf16 copy of them as they are loaded NOW, fp32 mode
+ * reads the encoder's own fp32 table in place, so there a later css_encoder_load_weights changes the decoder with it.
+ * In either mode call this again after loading other weights.  BERT only (an MPNet encoder is CSS_ERR_INVALID).  May be
+ * called again; a refused call (bad argument, wrong state, failed allocation) leaves the current head in place; a copy
+ * that fails after that leaves the encoder without a head. */
+int css_encoder_set_mlm_head(css_encoder* enc, const float* dense_w_host, const float* dense_b_host, const float* ln_g_host,
+                             const float* ln_b_host, const float* decoder_w_host /* NULL: tied */,
+                             const float* decoder_b_host);
+/* The vocabulary maximum alone, no forward pass: rows [total_tokens, H] fp32 are taken as g (bf16 mode: rounded to bf16
+ * on the device, then the bf16 kernel; fp32 mode: the fp32 kernel), cu_seqlens [B + 1] with cu[0] = 0 and every length
+ * >= 1 (any length: max_seq_len does not apply), zmax_out [B, V] fp32 = z.  The host form checks the offsets before
+ * anything is enqueued and names the bad sequence.  An MPNet encoder is CSS_ERR_INVALID, an encoder without a head
+ * CSS_ERR_STATE.  _dev: device pointers, enqueued on `stream` without a synchronise; a sequence number is clamped into
+ * [0, B).  In bf16 mode the rounded rows live in a buffer of the encoder's that only grows; growing frees the old one,
+ * so work that an earlier _dev call enqueued on another stream must have finished (as for the activations of
+ * css_encoder_forward_dev). */
+int css_encoder_vocab_max(css_encoder* enc, const float* rows_host, const int32_t* cu_seqlens_host, int B,
+                          float* zmax_out_host);
+int css_encoder_vocab_max_dev(css_encoder* enc, const float* rows_dev, const int32_t* cu_seqlens_dev, int B, int total_tokens,
+                              float* zmax_out_dev, void* stream);
+/* Packed var-len batch as css_encoder_forward, then the head, the vocabulary maximum and the top-m per sequence:
+ * terms_out [B, m] int32 the m largest z > 0, best first, ties to the lower term id, padded with -1; weights_out [B, m]
+ * fp32 = w of those terms, padded with 0; nnz_out [B] the number of z > 0 before the cut; 1 <= m <= 512.  The
+ * selection is on z and exact.  dense_out [B, V] fp32 (may be NULL) is z; rows_out [total_tokens, H] fp32 (may be
+ * NULL) is g before the bf16 rounding.  The tiny-batch graphs of css_encoder_forward are not used, created or dropped
+ * by this call.  Errors as css_encoder_forward, checked before anything is enqueued; an MPNet encoder is
+ * CSS_ERR_INVALID, an encoder without a head CSS_ERR_STATE.  _dev: device pointers, enqueued on `stream` without a
+ * synchronise; with dense_out NULL the maxima stay in a buffer of the encoder's that only grows (growth caveat as
+ * above). */
+int css_encoder_forward_sparse(css_encoder* enc, const int32_t* input_ids_host, const int32_t* cu_seqlens_host, int B, int m,
+                               int32_t* terms_out_host, float* weights_out_host, int32_t* nnz_out_host,
+                               float* dense_out_host, float* rows_out_host);
+int css_encoder_forward_sparse_dev(css_encoder* enc, const int32_t* input_ids_dev, const int32_t* cu_seqlens_dev, int B,
+                                   int total_tokens, int max_len, int m, int32_t* terms_out_dev, float* weights_out_dev,
+                                   int32_t* nnz_out_dev, float* dense_out_dev, float* rows_out_dev, void* stream);
 
 /* bf16 attention computes softmax rows as exp2(score) / sum WITHOUT a running maximum while every row sum of a
  * block stays in (1 / range, range) and repeats the block with the running-maximum (online) softmax otherwise --
