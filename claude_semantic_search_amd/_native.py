@@ -31,6 +31,11 @@ MAX_PRIOR_K = 128   # css_index_search_prior: the same list size
 MAX_HYBRID_K = 128   # css_index_search_hybrid: the same list size
 MAX_QUERY_TERMS = 32   # include/css_hip.h CSS_MAX_QUERY_TERMS
 TERM_SPACE = 1 << 24   # include/css_hip.h CSS_TERM_SPACE
+MAX_SPARSE_QUERY_TERMS = 64   # include/css_hip.h CSS_MAX_SPARSE_QUERY_TERMS
+MAX_SPARSE_ROW_ENTRIES = 65536   # include/css_hip.h CSS_MAX_SPARSE_ROW_ENTRIES
+MAX_SPARSE_WEIGHT = 65536.0   # include/css_hip.h CSS_MAX_SPARSE_WEIGHT
+SPARSE_TOPK_MIN_SLICE = 4096   # csrc/css_sparse.h kSparseTopkMinSlice: rows per block of the column top-k at least ...
+SPARSE_TOPK_MAX_PARTS = 32   # ... kSparseTopkMaxParts: and at most this many blocks
 MAX_SIG_TERMS = 256   # include/css_hip.h CSS_MAX_SIG_TERMS
 MAX_FACET_BUCKETS = 1 << 20   # include/css_hip.h CSS_MAX_FACET_BUCKETS
 MAX_EXAMPLES = 16   # include/css_hip.h CSS_MAX_EXAMPLES
@@ -142,6 +147,12 @@ PROTOTYPES = {
                                             c_void_p, POINTER(c_int), POINTER(c_int64), POINTER(c_int64)]),
     "css_index_search_hybrid": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_float, c_float,
                                         c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_index_set_sparse": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "css_index_get_sparse": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "css_index_sparse_rows": (c_int, [c_void_p, POINTER(c_int64)]),
+    "css_index_search_sparse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "css_index_search_hybrid_sparse": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "css_index_search_diverse": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
                                          c_void_p]),
     "css_index_search_diverse_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_void_p,

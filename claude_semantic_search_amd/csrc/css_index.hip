@@ -46,6 +46,9 @@
 //   k_transform_rows   css_index_transform: y = A x + b over stored rows, the K loop of k_kmeans_assign (css_pca.h)
 //   k_lex_scores       css_index_search_hybrid: the BM25 column of one query over the per-row term lists, handed to
 //                      k_scan_prior in the place of the priors (css_lexical.h).   HBM bound
+//   k_sparse_scores,   css_index_search_sparse / _hybrid_sparse: the dot column of one sparse query over the per-row
+//   k_sparse_topk      sparse vectors; ranked alone by slices of the column and the part merge, or handed to
+//                      k_scan_prior like the BM25 column (css_sparse.h).   HBM bound up to 32 terms
 //   k_sig_count        css_index_subset_terms / _significant_terms: +1 per list entry of the selected rows into a
 //                      uint32 table [2^24], repeats merged in a per-block LDS table first; k_sig_score and the radix
 //                      select rank the terms (css_sigterms.h)
@@ -140,6 +143,13 @@ struct css_index {
     DevBuf<unsigned long long> lex_total;
     std::vector<int64_t> lex_off_h;
     int64_t lex_rows = 0;
+    // per-row sparse vectors (css_index_set_sparse, css_sparse.h), independent of the term lists: the leading sp_rows
+    // rows own entries [sp_off[r], sp_off[r + 1]) of sp_ent, 8 bytes each (term | weight bits << 32).  No statistics.
+    // All empty until vectors are first set (sp_off_h.empty() tells); sp_off_h mirrors the offsets on the host
+    DevBuf<unsigned long long> sp_ent;
+    DevBuf<int64_t> sp_off;
+    std::vector<int64_t> sp_off_h;
+    int64_t sp_rows = 0;
     hipStream_t stream = nullptr;
     int num_cus = 256;
     // reusable workspaces (DevBuf: grown on demand, freed with the index; guarded by ws_mu)
@@ -240,6 +250,11 @@ struct css_index {
     DevBuf<int32_t> hyb_sl;             // 2 k entries
     DevBuf<uint32_t> lex_ask;
     DevBuf<long long> lex_stat;
+    // css_index_search_sparse: the query's [terms | weights], and the part lists [blocks, k] of k_sparse_topk (the
+    // column itself is lex_col, as in the hybrid search)
+    DevBuf<float> sp_q;
+    DevBuf<float> sp_pd;
+    DevBuf<int64_t> sp_pi;
     // css_index_kmeans_step (css_kmeans.h): the uploaded centroids [nc, dim]; their padded table [ncpad][dpad] with the
     // squared norms [ncpad] behind it; assignment and distance of every row; the member lists [ntotal] with
     // [nc + 1 offsets | nc + 1 block numbers | nc cursors]; and [KM_HDR words | nc counts | nc * dim sums] of int64
@@ -2833,6 +2848,7 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 // ------------------------------------------------------------------ prior-weighted search (css_knn_prior.h)
 #include "css_knn_prior.h"
 #include "css_lexical.h"
+#include "css_sparse.h"
 #include "css_sigterms.h"
 
 // HASP: the index has a prior column (false: every prior is 0, the kernel loads none)
@@ -3304,6 +3320,14 @@ int drop_terms(css_index* ix) {
     CSS_HIP_TRY(ix->lex_total.drop());
     return CSS_OK;
 }
+// ... and one that never received sparse vectors
+int drop_sparse(css_index* ix) {
+    ix->sp_rows = 0;
+    ix->sp_off_h.clear();
+    CSS_HIP_TRY(ix->sp_ent.drop());
+    CSS_HIP_TRY(ix->sp_off.drop());
+    return CSS_OK;
+}
 }  // namespace
 
 int css_index_reset(css_index* ix) {
@@ -3318,7 +3342,8 @@ int css_index_reset(css_index* ix) {
     CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
     // the columns go with the rows: the index is again one that never set any
     for (RowColumn* col : ix->columns()) CSS_HIP_TRY(col->words.drop());
-    return drop_terms(ix);   // and the term lists with their statistics
+    const int rc = drop_terms(ix);   // and the term lists with their statistics, and the sparse vectors
+    return rc != CSS_OK ? rc : drop_sparse(ix);
 }
 
 namespace {
@@ -3484,6 +3509,56 @@ int compact_terms(css_index* ix, const uint32_t* keep, TermCompaction* tc) {
     tc->built = true;
     return CSS_OK;
 }
+
+// The sparse vectors through the same keep bits, OUT OF PLACE like compact_terms: a host prefix sum over the mirror, and
+// k_sparse_move moves the vectors of the kept rows.  Enqueued on the index's stream; the caller waits, then commits.
+struct SparseCompaction {
+    DevBuf<unsigned long long> ent;
+    DevBuf<uint32_t> map;
+    DevBuf<int64_t> off;
+    std::vector<int64_t> off_h;   // (read by the copy until the caller has waited)
+    std::vector<uint32_t> map_h;
+    bool built = false;
+    void commit(css_index* ix) {
+        ix->sp_ent.swap(ent);
+        ix->sp_off.swap(off);
+        ix->sp_off_h.swap(off_h);
+        ix->sp_rows = (int64_t)ix->sp_off_h.size() - 1;
+    }
+};
+int compact_sparse(css_index* ix, const uint32_t* keep, SparseCompaction* sc) {
+    const int64_t T = ix->sp_rows;
+    if (T == 0) return CSS_OK;
+    const hipStream_t st = ix->stream;
+    try {
+        sc->map_h.resize((size_t)T);
+        sc->off_h.assign(1, 0);
+        for (int64_t r = 0; r < T; ++r) {
+            if ((keep[r >> 5] >> (r & 31)) & 1u) {
+                sc->map_h[(size_t)r] = (uint32_t)(sc->off_h.size() - 1);
+                sc->off_h.push_back(sc->off_h.back() + (ix->sp_off_h[(size_t)r + 1] - ix->sp_off_h[(size_t)r]));
+            } else {
+                sc->map_h[(size_t)r] = kLexNoRow;
+            }
+        }
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_index_remove_rows: out of host memory");
+        return CSS_ERR_OOM;
+    }
+    const size_t nT = sc->off_h.size() - 1;
+    int rc;
+    if ((rc = sc->ent.grow_exact(std::max<size_t>((size_t)sc->off_h.back(), 1), "hipMalloc(sparse vectors)")) != CSS_OK) return rc;
+    if ((rc = sc->off.grow_exact(nT + 1, "hipMalloc(sparse vectors)")) != CSS_OK) return rc;
+    if ((rc = sc->map.grow_exact((size_t)T, "hipMalloc(sparse vectors)")) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(sc->map.p, sc->map_h.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(sc->off.p, sc->off_h.data(), (nT + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_sparse_move, dim3((unsigned)((T + kWaves - 1) / kWaves)), dim3(256), 0, st,
+                       (const unsigned long long*)ix->sp_ent.p, (const int64_t*)ix->sp_off.p, (const uint32_t*)sc->map.p,
+                       (const int64_t*)sc->off.p, T, sc->ent.p);
+    CSS_LAUNCH_CHECK();
+    sc->built = true;
+    return CSS_OK;
+}
 }  // namespace
 
 int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t* removed_out) {
@@ -3514,12 +3589,14 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
     for (int c = 0; c < css_index::kColumns; ++c)
         if (cols[c]->words.p && kept > 0 && (rc = column_alloc(ix, *cols[c], ix->cap, &ncol[c])) != CSS_OK) return rc;
     TermCompaction tc;      // the compacted term lists (only where terms were set)
+    SparseCompaction sc;    // the compacted sparse vectors (only where vectors were set)
     CSS_HIP_TRY(hipMemsetAsync(ix->maxn2.p, 0, 3 * sizeof(int), ix->stream));
     uint32_t patch = 0;
     if (kept > 0) rc = compact_rows(ix, keep_bits_host, n, first, &patch);
     for (int c = 0; c < css_index::kColumns; ++c)
         if (rc == CSS_OK && ncol[c].p) rc = compact_column(ix, keep_bits_host, n, *cols[c], ncol[c]);
     if (rc == CSS_OK && ix->lex_df.p && kept > 0) rc = compact_terms(ix, keep_bits_host, &tc);
+    if (rc == CSS_OK && !ix->sp_off_h.empty() && kept > 0) rc = compact_sparse(ix, keep_bits_host, &sc);
     // later adds and searches on any stream are ordered behind the compaction (as css_index_reset)
     const hipError_t e = hipStreamSynchronize(ix->stream);
     if (rc != CSS_OK) return rc;
@@ -3527,7 +3604,9 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
     for (int c = 0; c < css_index::kColumns; ++c)
         if (ncol[c].p) cols[c]->words.swap(ncol[c]);
     if (tc.built) tc.commit(ix);
+    if (sc.built) sc.commit(ix);
     if (kept == 0 && (rc = drop_terms(ix)) != CSS_OK) return rc;   // emptied: as css_index_reset
+    if (kept == 0 && (rc = drop_sparse(ix)) != CSS_OK) return rc;
     set_ntotal(ix, kept);
     if (kept == 0 && !ix->xh.p) ix->shadow = -1;   // emptied: as css_index_reset
     for (css_index::I8Feedback* f : {&ix->fb_batch, &ix->fb_sweep}) {   // (it described other rows; its copy has landed)
@@ -4816,12 +4895,35 @@ namespace {
 // What css_index_search_hybrid uploads in ONE copy (floats of q_raw): the query, then the terms and their weights
 inline size_t hybrid_terms_at(const css_index* ix) { return ((size_t)ix->dim + 3) / 4 * 4; }
 
+// The column of a hybrid call: BM25 over the term lists (k1, b, avgdl) or the dot product with the sparse vectors
+enum class ColumnKind { Bm25, Sparse };
 struct LexQuery {
     int m;
     float alpha, k1, b, avgdl;
+    ColumnKind kind = ColumnKind::Bm25;
+    int max_terms() const { return kind == ColumnKind::Sparse ? CSS_MAX_SPARSE_QUERY_TERMS : CSS_MAX_QUERY_TERMS; }
+    int64_t list_rows(const css_index* ix) const { return kind == ColumnKind::Sparse ? ix->sp_rows : ix->lex_rows; }
 };
 
-// The lexical column (where the call has one), search_prior_enqueue on a COPY of the rows whose priors point at it,
+// The dot column of one query (m >= 1 terms and weights on the device) over the sparse vectors of rows.n > 0 rows into
+// `col`; rows without a common term, and rows beyond the vectors, get `miss`.  Enqueued on `st`.
+int sparse_scores_enqueue(css_index* ix, const Rows& rows, const uint32_t* qterms, const float* qweights, int m, float miss,
+                          float* col, hipStream_t st) {
+    const int64_t T = std::min(ix->sp_rows, rows.n);
+    const unsigned long long* ent = ix->sp_ent.p;
+    const int64_t* off = ix->sp_off.p;
+    ProfScope ps("sparse_scores", st);
+    if (m <= 32)
+        hipLaunchKernelGGL((k_sparse_scores<32, 4, 64, 4>), dim3((unsigned)((rows.n + 255) / 256)), dim3(256), 0, st, ent, off, T, rows.n,
+                           qterms, qweights, m, miss, col);
+    else
+        hipLaunchKernelGGL((k_sparse_scores<64, 4, 32, 4>), dim3((unsigned)((rows.n + 127) / 128)), dim3(256), 0, st, ent, off, T, rows.n,
+                           qterms, qweights, m, miss, col);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// The call's column (where it has one), search_prior_enqueue on a COPY of the rows whose priors point at it,
 // and L behind them.  Everything is enqueued on `st`; nothing waits for the device.  Caller holds ws_mu and a shared
 // lock on mu.
 int search_hybrid_enqueue(css_index* ix, const Rows& rows, const float* in_dev, const LexQuery& lq, int k, int normalize_q,
@@ -4831,17 +4933,21 @@ int search_hybrid_enqueue(css_index* ix, const Rows& rows, const float* in_dev, 
     if (turn.rc != CSS_OK) return turn.rc;
     Rows fused = rows;
     fused.priors = nullptr;   // (the stored priors play no part in this call)
-    const bool lexical = lq.m > 0 && lq.alpha != 0.f && ix->lex_rows > 0 && rows.n > 0;
+    const bool lexical = lq.m > 0 && lq.alpha != 0.f && lq.list_rows(ix) > 0 && rows.n > 0;
     if (lexical) {
         if ((rc = ix->lex_col.grow((size_t)rows.n)) != CSS_OK) return rc;
         const uint32_t* qterms = reinterpret_cast<const uint32_t*>(in_dev + hybrid_terms_at(ix));
-        const float* qweights = in_dev + hybrid_terms_at(ix) + CSS_MAX_QUERY_TERMS;
-        const float c0 = lq.k1 * (1.0f - lq.b), c1 = (lq.k1 * lq.b) / lq.avgdl;
-        ProfScope ps("lex_scores", st);
-        hipLaunchKernelGGL(k_lex_scores, dim3((unsigned)((rows.n + 64 * kWaves - 1) / (64 * kWaves))), dim3(256), 0, st,
-                           (const uint32_t*)ix->lex_ent.p, (const int64_t*)ix->lex_off.p, (const uint32_t*)ix->lex_dl.p,
-                           std::min(ix->lex_rows, rows.n), rows.n, qterms, qweights, lq.m, lq.k1, c0, c1, ix->lex_col.p);
-        CSS_LAUNCH_CHECK();
+        const float* qweights = in_dev + hybrid_terms_at(ix) + lq.max_terms();
+        if (lq.kind == ColumnKind::Sparse) {
+            if ((rc = sparse_scores_enqueue(ix, rows, qterms, qweights, lq.m, 0.0f, ix->lex_col.p, st)) != CSS_OK) return rc;
+        } else {
+            const float c0 = lq.k1 * (1.0f - lq.b), c1 = (lq.k1 * lq.b) / lq.avgdl;
+            ProfScope ps("lex_scores", st);
+            hipLaunchKernelGGL(k_lex_scores, dim3((unsigned)((rows.n + 64 * kWaves - 1) / (64 * kWaves))), dim3(256), 0, st,
+                               (const uint32_t*)ix->lex_ent.p, (const int64_t*)ix->lex_off.p, (const uint32_t*)ix->lex_dl.p,
+                               std::min(ix->lex_rows, rows.n), rows.n, qterms, qweights, lq.m, lq.k1, c0, c1, ix->lex_col.p);
+            CSS_LAUNCH_CHECK();
+        }
         fused.priors = ix->lex_col.p;
     }
     if ((rc = search_prior_enqueue(ix, fused, in_dev, 1, k, lexical ? lq.alpha : 0.f, normalize_q, D_dev, I_dev, S_dev, st)) != CSS_OK)
@@ -4887,6 +4993,236 @@ int css_index_search_hybrid(css_index* ix, const float* q_host, int k, float alp
         float* sl = reinterpret_cast<float*>(hc.g_out);
         rc = search_hybrid_enqueue(ix, hc.rows, ix->q_raw.p, LexQuery{m, alpha, k1, b, avgdl}, k, normalize_q, hc.d_out, hc.i_out,
                                    sl, sl + k, ix->stream);
+    }
+    float sl_host[2 * CSS_KERNEL_MAX_K];
+    rc = hc.finish(rc, D_host, I_host, reinterpret_cast<int32_t*>(sl_host));
+    if (rc != CSS_OK) return rc;
+    if (S_host) memcpy(S_host, sl_host, (size_t)k * sizeof(float));
+    if (L_host) memcpy(L_host, sl_host + k, (size_t)k * sizeof(float));
+    return CSS_OK;
+}
+
+// ------------------------------------------------------------------ per-row sparse vectors and sparse search
+int css_index_set_sparse(css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host, const uint32_t* terms_host,
+                         const float* weights_host) {
+    CSS_REQUIRE(ix, "css_index_set_sparse: NULL index");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);   // (ws_pending)
+    const int64_t T0 = ix->sp_rows;
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_set_sparse: rows [%lld, %lld + %lld) outside [0, %lld)",
+                (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
+    CSS_REQUIRE(row0 <= T0, "css_index_set_sparse: row0=%lld beyond the %lld rows that have vectors (vectors are append-only)",
+                (long long)row0, (long long)T0);
+    CSS_REQUIRE(n == 0 || offsets_host, "css_index_set_sparse: offsets is NULL");
+    // everything is looked at before anything is written
+    if (n > 0) {
+        CSS_REQUIRE(offsets_host[0] == 0, "css_index_set_sparse: offsets start at %lld, not 0", (long long)offsets_host[0]);
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t c = offsets_host[i + 1] - offsets_host[i];
+            CSS_REQUIRE(c >= 0, "css_index_set_sparse: offsets decrease at row %lld", (long long)(row0 + i));
+            CSS_REQUIRE(c <= CSS_MAX_SPARSE_ROW_ENTRIES, "css_index_set_sparse: row %lld has %lld entries (at most %d)",
+                        (long long)(row0 + i), (long long)c, CSS_MAX_SPARSE_ROW_ENTRIES);
+        }
+        CSS_REQUIRE(offsets_host[n] == 0 || (terms_host && weights_host), "css_index_set_sparse: terms or weights is NULL");
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t t = offsets_host[i]; t < offsets_host[i + 1]; ++t) {
+                CSS_REQUIRE(terms_host[t] < CSS_TERM_SPACE, "css_index_set_sparse: term %u of row %lld is outside [0, 2^24)",
+                            terms_host[t], (long long)(row0 + i));
+                const float w = weights_host[t];
+                CSS_REQUIRE(std::isfinite(w) && w > 0.f && w <= CSS_MAX_SPARSE_WEIGHT,
+                            "css_index_set_sparse: the weight of term %u of row %lld is %s (weights are finite, > 0 and <= 65536)",
+                            terms_host[t], (long long)(row0 + i),
+                            std::isnan(w) ? "NaN" : std::isinf(w) ? "infinite" : w > 0.f ? "too large" : w == 0.f ? "zero" : "negative");
+            }
+    }
+    if (n == 0 && row0 == T0) return CSS_OK;
+    // each row sorted on the host: term | weight bits << 32, ascending by term (a repeated term shows as neighbours)
+    std::vector<unsigned long long> ent;
+    std::vector<int64_t> off;
+    const int64_t E0 = T0 > 0 ? ix->sp_off_h[(size_t)row0] : 0;
+    try {
+        ent.reserve(n > 0 ? (size_t)offsets_host[n] : 0);
+        off.resize((size_t)n + 1);
+        off[0] = E0;
+        for (int64_t i = 0; i < n; ++i) {
+            const size_t a = ent.size();
+            for (int64_t t = offsets_host[i]; t < offsets_host[i + 1]; ++t) {
+                uint32_t bits;
+                memcpy(&bits, &weights_host[t], sizeof bits);
+                ent.push_back((unsigned long long)bits << 32 | terms_host[t]);
+            }
+            std::sort(ent.begin() + (ptrdiff_t)a, ent.end(),
+                      [](unsigned long long x, unsigned long long y) { return (uint32_t)x < (uint32_t)y; });
+            for (size_t e = a + 1; e < ent.size(); ++e)
+                CSS_REQUIRE((uint32_t)ent[e] != (uint32_t)ent[e - 1], "css_index_set_sparse: term %u is repeated in row %lld",
+                            (uint32_t)ent[e], (long long)(row0 + i));
+            off[(size_t)i + 1] = E0 + (int64_t)ent.size();
+        }
+        ix->sp_off_h.reserve((size_t)(row0 + n) + 1);
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_index_set_sparse: out of host memory");
+        return CSS_ERR_OOM;
+    }
+    DeviceGuard g(ix->device);
+    const hipStream_t st = ix->stream;
+    // as css_index_set_terms: a search on another stream may still read the vectors that go or move
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ws_ev, 0));
+    int rc;
+    if (ix->sp_off_h.empty()) ix->sp_off_h.assign(1, 0);   // first vectors of this index
+    if (row0 < T0) {   // the vectors of rows >= row0 go
+        ix->sp_off_h.resize((size_t)row0 + 1);
+        ix->sp_rows = row0;
+    }
+    if (n > 0) {
+        const size_t nE = ent.size();
+        if ((rc = grow_keep(ix, ix->sp_ent, (size_t)E0, (size_t)E0 + std::max<size_t>(nE, 1), "hipMalloc(sparse vectors)")) != CSS_OK) return rc;
+        if ((rc = grow_keep(ix, ix->sp_off, (size_t)row0 + 1, (size_t)(row0 + n) + 1, "hipMalloc(sparse vectors)")) != CSS_OK) return rc;
+        if (nE) CSS_HIP_TRY(hipMemcpyAsync(ix->sp_ent.p + E0, ent.data(), nE * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+        CSS_HIP_TRY(hipMemcpyAsync(ix->sp_off.p + row0, off.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    }
+    CSS_HIP_TRY(hipStreamSynchronize(st));   // (the copies read this call's vectors)
+    ix->sp_off_h.insert(ix->sp_off_h.end(), off.begin() + 1, off.end());
+    ix->sp_rows = row0 + n;
+    return CSS_OK;
+}
+
+int css_index_get_sparse(css_index* ix, int64_t row0, int64_t n, int64_t* offsets_out, uint32_t* terms_out, float* weights_out) {
+    CSS_REQUIRE(ix, "css_index_get_sparse: NULL index");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_get_sparse: rows [%lld, %lld + %lld) outside [0, %lld)",
+                (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
+    CSS_REQUIRE(offsets_out, "css_index_get_sparse: offsets_out is NULL");
+    const int64_t T = ix->sp_rows;
+    const int64_t a = std::min(row0, T), e = std::min(row0 + n, T);   // the rows of the range that have vectors
+    const int64_t E0 = T > 0 ? ix->sp_off_h[(size_t)a] : 0;
+    for (int64_t i = 0; i <= n; ++i) offsets_out[i] = T > 0 ? ix->sp_off_h[(size_t)std::min(row0 + i, T)] - E0 : 0;
+    const int64_t nE = offsets_out[n];
+    if (e <= a || nE == 0 || !(terms_out || weights_out)) return CSS_OK;
+    std::vector<unsigned long long> ent;
+    try {
+        ent.resize((size_t)nE);
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_index_get_sparse: out of host memory");
+        return CSS_ERR_OOM;
+    }
+    DeviceGuard g(ix->device);
+    CSS_HIP_TRY(hipMemcpy(ent.data(), ix->sp_ent.p + E0, (size_t)nE * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < nE; ++i) {
+        if (terms_out) terms_out[i] = (uint32_t)ent[(size_t)i];
+        const uint32_t bits = (uint32_t)(ent[(size_t)i] >> 32);
+        if (weights_out) memcpy(&weights_out[i], &bits, sizeof bits);
+    }
+    return CSS_OK;
+}
+
+int css_index_sparse_rows(css_index* ix, int64_t* rows_out) {
+    CSS_REQUIRE(ix && rows_out, "css_index_sparse_rows: NULL argument");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    *rows_out = ix->sp_rows;
+    return CSS_OK;
+}
+
+namespace {
+// the checks that css_index_search_sparse and css_index_search_hybrid_sparse make of a sparse query
+int sparse_query_check(const char* fn, const uint32_t* terms_host, const float* weights_host, int m) {
+    CSS_REQUIRE(m >= 0 && m <= CSS_MAX_SPARSE_QUERY_TERMS, "%s: m=%d outside [0, %d]", fn, m, CSS_MAX_SPARSE_QUERY_TERMS);
+    CSS_REQUIRE(m == 0 || (terms_host && weights_host), "%s: NULL buffer", fn);
+    for (int j = 0; j < m; ++j) {
+        const float w = weights_host[j];
+        CSS_REQUIRE(terms_host[j] < CSS_TERM_SPACE, "%s: term %u (number %d) is outside [0, 2^24)", fn, terms_host[j], j);
+        CSS_REQUIRE(std::isfinite(w) && w != 0.f && fabsf(w) <= CSS_MAX_SPARSE_WEIGHT,
+                    "%s: the weight of term %u (number %d) is %s (weights are finite, nonzero and at most 65536 in size)", fn,
+                    terms_host[j], j, std::isnan(w) ? "NaN" : std::isinf(w) ? "infinite" : w == 0.f ? "zero" : "too large");
+        for (int i = 0; i < j; ++i)
+            CSS_REQUIRE(terms_host[i] != terms_host[j], "%s: term %u is repeated (numbers %d and %d)", fn, terms_host[j], i, j);
+    }
+    return CSS_OK;
+}
+
+// rows per block of k_sparse_topk over n > 0 rows: at least kSparseTopkMinSlice, a multiple of 256, at most
+// kSparseTopkMaxParts blocks
+inline int64_t sparse_topk_slice(int64_t n) {
+    const int64_t per = (n + kSparseTopkMaxParts - 1) / kSparseTopkMaxParts;
+    return std::max<int64_t>(kSparseTopkMinSlice, (per + 255) / 256 * 256);
+}
+
+// The dot column with miss = -inf, its top-k by slices, and the part merge.  `in_dev`: [64 terms | 64 weights].
+// Everything is enqueued on `st`; nothing waits for the device.  Caller holds ws_mu and a shared lock on mu.
+int search_sparse_enqueue(css_index* ix, const Rows& rows, const float* in_dev, int m, int k, float* D_dev, int64_t* I_dev,
+                          hipStream_t st) {
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    if (m == 0 || ix->sp_rows == 0 || rows.n == 0) {
+        hipLaunchKernelGGL(k_sparse_pad, dim3(1), dim3(128), 0, st, D_dev, I_dev, k);
+        CSS_LAUNCH_CHECK();
+        return CSS_OK;
+    }
+    CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "css_index_search_sparse: %lld rows exceed the 32-bit row numbers of the lists",
+                (long long)rows.n);
+    // rows appended on another stream must have landed (the mask and the row count speak of them)
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    const int64_t slice = sparse_topk_slice(rows.n);
+    const int parts = (int)((rows.n + slice - 1) / slice);
+    if ((rc = ix->lex_col.grow((size_t)rows.n)) != CSS_OK) return rc;
+    if ((rc = ix->sp_pd.grow((size_t)parts * k)) != CSS_OK) return rc;
+    if ((rc = ix->sp_pi.grow((size_t)parts * k)) != CSS_OK) return rc;
+    if ((rc = sparse_scores_enqueue(ix, rows, reinterpret_cast<const uint32_t*>(in_dev), in_dev + CSS_MAX_SPARSE_QUERY_TERMS, m,
+                                    -INFINITY, ix->lex_col.p, st)) != CSS_OK)
+        return rc;
+    {
+        ProfScope ps("sparse_topk", st);
+        hipLaunchKernelGGL(k_sparse_topk, dim3((unsigned)parts), dim3(256), 0, st, (const float*)ix->lex_col.p, rows.n, slice,
+                           rows.mask, k, rows.id_base, ix->sp_pd.p, ix->sp_pi.p);
+        CSS_LAUNCH_CHECK();
+    }
+    // (larger is better whatever the index's metric: the parts merge as inner-product lists)
+    return merge_parts(ix->sp_pd.p, ix->sp_pi.p, parts, k, k, 1, k, CSS_METRIC_IP, D_dev, I_dev, ix->device, st,
+                       "css_index_search_sparse");
+}
+}  // namespace
+
+int css_index_search_sparse(css_index* ix, const uint32_t* terms_host, const float* weights_host, int m, int k,
+                            const uint32_t* allow_bits_host, float* D_host, int64_t* I_host) {
+    CSS_REQUIRE(ix, "css_index_search_sparse: NULL index");
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "css_index_search_sparse: k=%d outside [1, %d]", k, CSS_KERNEL_MAX_K);
+    CSS_REQUIRE(D_host && I_host, "css_index_search_sparse: NULL buffer");
+    int rc = sparse_query_check("css_index_search_sparse", terms_host, weights_host, m);
+    if (rc != CSS_OK) return rc;
+    HostCall hc(ix);
+    // the ONE upload: the terms, the weights
+    float in[2 * CSS_MAX_SPARSE_QUERY_TERMS] = {};
+    if (m) memcpy(in, terms_host, (size_t)m * sizeof(uint32_t));
+    if (m) memcpy(in + CSS_MAX_SPARSE_QUERY_TERMS, weights_host, (size_t)m * sizeof(float));
+    rc = hc.upload(allow_bits_host, ix->sp_q, (const float*)in, (size_t)2 * CSS_MAX_SPARSE_QUERY_TERMS, (size_t)k);
+    if (rc == CSS_OK) rc = search_sparse_enqueue(ix, hc.rows, ix->sp_q.p, m, k, hc.d_out, hc.i_out, ix->stream);
+    return hc.finish(rc, D_host, I_host);
+}
+
+int css_index_search_hybrid_sparse(css_index* ix, const float* q_host, int k, float alpha, const uint32_t* terms_host,
+                                   const float* weights_host, int m, int normalize_q, const uint32_t* allow_bits_host,
+                                   float* D_host, int64_t* I_host, float* S_host, float* L_host) {
+    CSS_REQUIRE(ix, "css_index_search_hybrid_sparse: NULL index");
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "css_index_search_hybrid_sparse: k=%d outside [1, %d]", k, CSS_KERNEL_MAX_K);
+    CSS_REQUIRE(std::isfinite(alpha), "css_index_search_hybrid_sparse: alpha is %s (it must be finite)",
+                std::isnan(alpha) ? "NaN" : "infinite");
+    CSS_REQUIRE(q_host && D_host && I_host, "css_index_search_hybrid_sparse: NULL buffer");
+    int rc = sparse_query_check("css_index_search_hybrid_sparse", terms_host, weights_host, m);
+    if (rc != CSS_OK) return rc;
+    HostCall hc(ix);
+    // the ONE upload: the query, the terms, the weights
+    const size_t at = hybrid_terms_at(ix);
+    std::vector<float> in(at + 2 * CSS_MAX_SPARSE_QUERY_TERMS, 0.f);
+    memcpy(in.data(), q_host, (size_t)ix->dim * sizeof(float));
+    if (m) memcpy(in.data() + at, terms_host, (size_t)m * sizeof(uint32_t));
+    if (m) memcpy(in.data() + at + CSS_MAX_SPARSE_QUERY_TERMS, weights_host, (size_t)m * sizeof(float));
+    hc.cols = 2;   // [S | L]
+    rc = hc.upload(allow_bits_host, ix->q_raw, (const float*)in.data(), in.size(), (size_t)k, &ix->hyb_sl);
+    if (rc == CSS_OK) {
+        float* sl = reinterpret_cast<float*>(hc.g_out);
+        rc = search_hybrid_enqueue(ix, hc.rows, ix->q_raw.p, LexQuery{m, alpha, 0.f, 0.f, 1.f, ColumnKind::Sparse}, k, normalize_q,
+                                   hc.d_out, hc.i_out, sl, sl + k, ix->stream);
     }
     float sl_host[2 * CSS_KERNEL_MAX_K];
     rc = hc.finish(rc, D_host, I_host, reinterpret_cast<int32_t*>(sl_host));

@@ -227,6 +227,97 @@ def hybrid_args(terms, weights, k, alpha, k1, b, avgdl, what: str = "search_hybr
     return np.ascontiguousarray(t, dtype=np.uint32), w, k, alpha, k1, b, avgdl
 
 
+MAX_SPARSE_QUERY_TERMS = nat.MAX_SPARSE_QUERY_TERMS
+MAX_SPARSE_WEIGHT = nat.MAX_SPARSE_WEIGHT
+
+
+def sparse_args(terms, weights, k, alpha=None, what: str = "search_sparse"):
+    """The checked arguments of a sparse search: ``(terms uint32 [m], weights float32 [m], k, alpha)``; what the library
+    would refuse raises ``ValueError`` here.  ``terms`` may be a ``SparseVector`` (``weights=None``).  At most 64 distinct
+    terms below 2^24; weights finite, nonzero and at most 65536 in size (negative ones are allowed); ``1 <= k <= 128``;
+    ``alpha`` (hybrid only) finite."""
+    if weights is None and isinstance(terms, tuple) and len(terms) == 2:
+        terms, weights = terms
+    t = np.asarray(terms if terms is not None else (), dtype=np.int64)
+    w = np.asarray(weights if weights is not None else (), dtype=np.float32)
+    if t.ndim > 1 or w.ndim > 1:
+        raise ValueError(f"{what}: one query per call, got terms of shape {t.shape} and weights of shape {w.shape}")
+    t, w = t.reshape(-1), np.ascontiguousarray(w.reshape(-1))
+    if t.shape[0] != w.shape[0]:
+        raise ValueError(f"{what}: {t.shape[0]} terms but {w.shape[0]} weights")
+    if t.shape[0] > MAX_SPARSE_QUERY_TERMS:
+        raise ValueError(f"{what}: {t.shape[0]} query terms (at most {MAX_SPARSE_QUERY_TERMS})")
+    if t.size and (int(t.min()) < 0 or int(t.max()) >= nat.TERM_SPACE):
+        raise ValueError(f"{what}: a term outside [0, 2^24)")
+    uniq, counts = np.unique(t, return_counts=True)
+    if (counts > 1).any():
+        raise ValueError(f"{what}: term {int(uniq[counts > 1][0])} is repeated")
+    bad = ~np.isfinite(w) | (w == 0.0) | (np.abs(w) > MAX_SPARSE_WEIGHT)
+    if bad.any():
+        raise ValueError(f"{what}: the weight {float(w[bad][0])} of term {int(t[bad][0])} must be finite, nonzero and at most "
+                         f"{MAX_SPARSE_WEIGHT:g} in size")
+    k = int(k)
+    if k < 1 or k > MAX_HYBRID_K:
+        raise ValueError(f"k={k} outside [1, {MAX_HYBRID_K}]")
+    if alpha is not None:
+        alpha = float(alpha)
+        if not np.isfinite(alpha):
+            raise ValueError(f"{what}: alpha={alpha} is not finite")
+    return np.ascontiguousarray(t, dtype=np.uint32), w, k, alpha
+
+
+def sparse_as_csr(vectors, what: str = "set_sparse") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Sparse vectors as CSR ``(offsets int64 [n + 1] from 0, terms uint32, weights float32)``.  ``vectors`` is a
+    sequence of ``SparseVector`` or ``(terms, weights)`` pairs (one per row, any order within a row, empty allowed) or
+    an ``(offsets, terms, weights)`` triple of arrays.  What the library would refuse in the entries raises
+    ``ValueError`` here and names the row (of this call): a term outside ``[0, 2^24)`` or repeated within a row, a
+    weight that is not finite, not ``> 0`` or above 65536, a row of more than 65536 entries.  The shape of the offsets
+    is the library's to check."""
+    if isinstance(vectors, tuple) and len(vectors) == 3 and isinstance(vectors[0], np.ndarray):
+        off = np.ascontiguousarray(vectors[0], dtype=np.int64).reshape(-1)
+        t, w = np.asarray(vectors[1]).reshape(-1), np.asarray(vectors[2]).reshape(-1)
+        if off.shape[0] < 1:
+            raise ValueError(f"{what}: offsets must hold n + 1 values")
+    else:
+        rows = [(np.asarray(v[0]).reshape(-1), np.asarray(v[1]).reshape(-1)) for v in vectors]
+        for r, (a, b) in enumerate(rows):
+            if a.shape[0] != b.shape[0]:
+                raise ValueError(f"{what}: row {r} (of this call) has {a.shape[0]} terms but {b.shape[0]} weights")
+            if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
+                raise ValueError(f"{what}: the terms of row {r} (of this call) must be integers, got dtype {a.dtype}")
+        off = np.zeros(len(rows) + 1, dtype=np.int64)
+        if rows:
+            np.cumsum([a.shape[0] for a, _ in rows], out=off[1:])
+        t = np.concatenate([a.astype(np.int64) for a, _ in rows]) if rows else np.zeros(0, np.int64)
+        w = np.concatenate([b.astype(np.float32) for _, b in rows]) if rows else np.zeros(0, np.float32)
+    if t.shape[0] != w.shape[0]:
+        raise ValueError(f"{what}: {t.shape[0]} terms but {w.shape[0]} weights")
+    if t.size and (t.dtype == np.bool_ or not np.issubdtype(t.dtype, np.integer)):
+        raise ValueError(f"{what}: terms must be integers, got dtype {t.dtype}")
+    t = t.astype(np.int64)
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    well_formed = off[0] == 0 and off[-1] == t.shape[0] and (np.diff(off) >= 0).all()
+    row_of = (lambda e: int(np.searchsorted(off, e, side="right")) - 1) if well_formed else (lambda e: -1)
+    bad = np.flatnonzero((t < 0) | (t >= nat.TERM_SPACE))
+    if bad.size:
+        raise ValueError(f"{what}: term {int(t[bad[0]])} of row {row_of(bad[0])} (of this call) is outside [0, 2^24)")
+    bad = np.flatnonzero(~np.isfinite(w) | ~(w > 0.0) | (w > MAX_SPARSE_WEIGHT))
+    if bad.size:
+        raise ValueError(f"{what}: the weight {float(w[bad[0]])} of term {int(t[bad[0]])} of row {row_of(bad[0])} (of this call) "
+                         f"must be finite, > 0 and <= {MAX_SPARSE_WEIGHT:g}")
+    if well_formed:
+        lens = np.diff(off)
+        if lens.size and int(lens.max()) > nat.MAX_SPARSE_ROW_ENTRIES:
+            raise ValueError(f"{what}: row {int(lens.argmax())} (of this call) has {int(lens.max())} entries "
+                             f"(at most {nat.MAX_SPARSE_ROW_ENTRIES})")
+        key = np.repeat(np.arange(lens.shape[0], dtype=np.int64), lens) << 24 | t
+        uniq, counts = np.unique(key, return_counts=True)
+        if (counts > 1).any():
+            rep = int(uniq[counts > 1][0])
+            raise ValueError(f"{what}: term {rep & (nat.TERM_SPACE - 1)} is repeated in row {rep >> 24} (of this call)")
+    return off, np.ascontiguousarray(t, dtype=np.uint32), w
+
+
 MAX_DIVERSE_FETCH = nat.MAX_DIVERSE_FETCH
 
 
@@ -1024,6 +1115,76 @@ class IndexFlat:
             self._handle(), a.ctypes.data, k, alpha, t.ctypes.data if t.size else None, w.ctypes.data if t.size else None,
             t.shape[0], k1, b, float(np.float32(avgdl)), 1 if normalize else 0, bits_ptr, D.ctypes.data, I.ctypes.data,
             S.ctypes.data, L.ctypes.data))
+        return D, I, S, L
+
+    # -- per-row sparse vectors and sparse search ------------------------------
+    def set_sparse(self, vectors, row0: Optional[int] = None) -> None:
+        """Sparse vectors of rows ``[row0, row0 + n)`` in LOCAL row numbering (``css_index_set_sparse``).  ``vectors`` is
+        a sequence of ``SparseVector`` or ``(terms, weights)`` pairs (e.g. ``SparseEncoder.encode``: any order within a
+        row, empty rows allowed) or an ``(offsets, terms, weights)`` triple of arrays in CSR form.  Terms are distinct
+        within a row and below 2^24; weights are finite, ``> 0`` and ``<= 65536``; at most 65536 entries per row.
+        APPEND-ONLY in row order like ``set_terms`` and independent of it: with ``T = sparse_rows``, ``row0 = None`` or
+        ``T`` appends, ``row0 < T`` first drops the vectors of all rows ``>= row0``, ``row0 > T`` raises.  The vectors
+        follow the rows through growth, ``remove_ids`` (compacted with them) and ``reset`` (forgotten); rows added
+        later have none."""
+        off, t, w = sparse_as_csr(vectors)
+        row0 = self.sparse_rows if row0 is None else int(row0)
+        nat.check(nat.lib().css_index_set_sparse(self._handle(), row0, off.shape[0] - 1, off.ctypes.data,
+                                                 t.ctypes.data if t.size else None, w.ctypes.data if w.size else None))
+
+    def get_sparse(self, row0: int = 0, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The stored vectors of rows ``[row0, row0 + n)`` (default: to the end): ``(offsets int64 [n + 1] from 0, terms
+        uint32, weights float32)``, per row ascending by term.  Rows without a vector are empty."""
+        row0, n = self._row_range("get_sparse", row0, n)
+        off = np.zeros(n + 1, dtype=np.int64)
+        self._handle()
+        if n == 0:
+            return off, np.zeros(0, np.uint32), np.zeros(0, np.float32)
+        nat.check(nat.lib().css_index_get_sparse(self._handle(), row0, n, off.ctypes.data, None, None))
+        t, w = np.zeros(int(off[-1]), dtype=np.uint32), np.zeros(int(off[-1]), dtype=np.float32)
+        if t.size:
+            nat.check(nat.lib().css_index_get_sparse(self._handle(), row0, n, off.ctypes.data, t.ctypes.data, w.ctypes.data))
+        return off, t, w
+
+    @property
+    def sparse_rows(self) -> int:
+        """The number of leading rows that have sparse vectors."""
+        return self._read_i64(nat.lib().css_index_sparse_rows)
+
+    def search_sparse(self, terms, weights, k: int, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The ``k`` best rows for ONE sparse query by the dot product with the rows' sparse vectors ALONE
+        (``css_index_search_sparse``): ``(D, I)``, each ``[1, k]`` -- the dot product, formed on the device in fp32 in
+        query-term order, and the global id; larger first on an index of either metric, ties to the lower id.  Only
+        HIT rows are returned, rows that share at least one term with the query; fewer than ``k`` of them, no terms or
+        an index without vectors pad with ``I = -1``, ``D = -FLT_MAX``.  No dense row is read.  ``terms`` are distinct
+        ids (at most 64; or a ``SparseVector`` with ``weights=None``), ``weights`` finite, nonzero, at most 65536 in
+        size; negative ones are allowed."""
+        t, w, k, _ = sparse_args(terms, weights, k)
+        D, I = np.empty((1, k), dtype=np.float32), np.empty((1, k), dtype=np.int64)
+        h = self._handle()
+        bits, bits_ptr = self._allow_bits(allow)
+        nat.check(nat.lib().css_index_search_sparse(h, t.ctypes.data if t.size else None, w.ctypes.data if t.size else None,
+                                                    t.shape[0], k, bits_ptr, D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    def search_hybrid_sparse(self, q, terms, weights, k: int, alpha: float, normalize: bool = False,
+                             allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """``search_hybrid`` with the sparse dot product ``sp`` in the place of the BM25 score
+        (``css_index_search_hybrid_sparse``): the ``k`` best rows for ONE query under ``score + alpha * sp`` (L2:
+        ``distance - alpha * sp``), exact over ALL allowed rows: ``(D, I, S, L)``, each ``[1, k]``, ``L = sp`` of the
+        returned rows (0 for a row that shares no term).  The query's sparse side is that of ``search_sparse``.  No
+        terms, ``alpha = 0`` or an index without vectors give ``search_prior`` without priors."""
+        a = _as_f32_2d(q, self.d, "search_hybrid_sparse")
+        if a.shape[0] != 1:
+            raise ValueError(f"search_hybrid_sparse: one query per call, got {a.shape[0]}")
+        t, w, k, alpha = sparse_args(terms, weights, k, alpha, what="search_hybrid_sparse")
+        D, I = np.empty((1, k), dtype=np.float32), np.empty((1, k), dtype=np.int64)
+        S, L = np.empty((1, k), dtype=np.float32), np.empty((1, k), dtype=np.float32)
+        h = self._handle()
+        bits, bits_ptr = self._allow_bits(allow)
+        nat.check(nat.lib().css_index_search_hybrid_sparse(
+            h, a.ctypes.data, k, alpha, t.ctypes.data if t.size else None, w.ctypes.data if t.size else None, t.shape[0],
+            1 if normalize else 0, bits_ptr, D.ctypes.data, I.ctypes.data, S.ctypes.data, L.ctypes.data))
         return D, I, S, L
 
     # -- diversified search (MMR) --------------------------------------------

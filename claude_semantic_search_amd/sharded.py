@@ -73,6 +73,7 @@ class ShardedFlatIndex:
         self._seg_tensors = None
         self._dead: Optional[np.ndarray] = None          # tombstones in global numbering (replicated; mark_deleted)
         self._terms_global = 0                           # leading GLOBAL rows that have term lists (replicated; set_terms)
+        self._sparse_global = 0                          # ... that have sparse vectors (replicated; set_sparse)
 
     # -- building ----------------------------------------------------------
     def _append_segment(self, n_local: int, global_row0: int) -> None:
@@ -209,11 +210,12 @@ class ShardedFlatIndex:
                 rows[at] = self.local.reconstruct_n(l0 + int(global_ids[at]) - g0, 1)[0]
         return self._sum_over_ranks(rows)
 
-    def _best_first(self, scores: np.ndarray, ids: np.ndarray, lead: np.ndarray) -> np.ndarray:
-        """Sort order by ``lead`` ascending, then best score first (IP descending, L2 ascending), then ascending id."""
-        return np.lexsort((ids, -scores if self.metric == 0 else scores, lead))
+    def _best_first(self, scores: np.ndarray, ids: np.ndarray, lead: np.ndarray, metric: Optional[int] = None) -> np.ndarray:
+        """Sort order by ``lead`` ascending, then best score first (IP descending, L2 ascending; ``metric``: that of the
+        scores where it is not the index's), then ascending id."""
+        return np.lexsort((ids, -scores if (self.metric if metric is None else metric) == 0 else scores, lead))
 
-    def _columns(self, I, cols, last=np.float32):
+    def _columns(self, I, cols, last=np.float32, metric: Optional[int] = None):
         """The exchange of a local result of fixed-width columns: ``I`` the local ids and ``cols`` the 4-byte columns
         that ride along (float32; the last one ``last``), ``[nq, k]`` or ``[k]`` each.  Returns ``(I, cols, local)``:
         contiguous, ids GLOBAL.  One rank, or no query: the local answer is the answer (``local``, shapes as given).
@@ -235,7 +237,7 @@ class ShardedFlatIndex:
         Ig = side_by_side(0, 8, np.int64)
         out = [side_by_side(8 + 4 * c, 12 + 4 * c, a.dtype) for c, a in enumerate(cols)]
         for j in range(Ig.shape[0]):
-            order = self._best_first(out[0][j], Ig[j], Ig[j] < 0)
+            order = self._best_first(out[0][j], Ig[j], Ig[j] < 0, metric)
             for a in [Ig] + out:
                 a[j] = a[j][order]
         return Ig, out, False
@@ -558,16 +560,24 @@ class ShardedFlatIndex:
             raise ValueError(f"set_terms: row0={row0} beyond the {self._terms_global} rows that have lists (lists are append-only)")
         if n == 0 and row0 == self._terms_global:
             return
-        local_row0 = sum(min(max(row0 - g0, 0), m) for _, g0, m in self.segments)   # local rows below global row0
-        parts_off, parts_tok = [np.zeros(1, np.int64)], []
-        for _, lo, m in self._overlaps(row0, n):
-            a, e = int(off[lo - row0]), int(off[lo - row0 + m])
-            parts_off.append(off[lo - row0 + 1:lo - row0 + m + 1] - a + sum(t.shape[0] for t in parts_tok))
-            parts_tok.append(tok[a:e])
-        loff = np.concatenate(parts_off).astype(np.int64)
-        ltok = np.concatenate(parts_tok) if parts_tok else np.zeros(0, np.uint32)
+        local_row0, loff, (ltok,) = self._local_csr(row0, off, (tok,))
         self.local.set_terms((loff, ltok), row0=local_row0)
         self._terms_global = row0 + n
+
+    def _local_csr(self, row0: int, off: np.ndarray, values):
+        """This shard's part of per-row lists in CSR form over the GLOBAL rows ``[row0, row0 + n)``: ``(the first local
+        row >= global row0, local offsets from 0, the entries of each array of values)``, through the segment table."""
+        n = off.shape[0] - 1
+        local_row0 = sum(min(max(row0 - g0, 0), m) for _, g0, m in self.segments)   # local rows below global row0
+        parts_off, parts, count = [np.zeros(1, np.int64)], [[] for _ in values], 0
+        for _, lo, m in self._overlaps(row0, n):
+            a, e = int(off[lo - row0]), int(off[lo - row0 + m])
+            parts_off.append(off[lo - row0 + 1:lo - row0 + m + 1] - a + count)
+            count += e - a
+            for p, v in zip(parts, values):
+                p.append(v[a:e])
+        loff = np.concatenate(parts_off).astype(np.int64)
+        return local_row0, loff, tuple(np.concatenate(p) if p else v[:0] for p, v in zip(parts, values))
 
     def term_stats(self, terms):
         """``IndexFlat.term_stats`` over the shards (collective): ``(df, ndocs, total_len)`` of the whole index -- the
@@ -594,6 +604,55 @@ class ShardedFlatIndex:
             avgdl = total / ndocs if ndocs > 0 and total > 0 else 1.0
         D, I, S, L = self.local.search_hybrid(qa, t, w, k, alpha, k1=k1, b=b, avgdl=avgdl, normalize=normalize,
                                               allow=self._local_allow(allow))
+        I, (D, S, L), _ = self._columns(I, (D, S, L))
+        return tuple(np.ascontiguousarray(a[..., :k]) for a in (D, I, S, L))
+
+    # -- sparse vectors and sparse search ----------------------------------------------------------------------
+    def set_sparse(self, vectors, row0: Optional[int] = None) -> None:
+        """``IndexFlat.set_sparse`` in GLOBAL numbering (collective: every rank passes the same vectors; no
+        communication): the sparse vectors of the global rows ``[row0, row0 + n)``, append-only like ``set_terms`` and
+        routed through the segment table the same way."""
+        from .flat_index import sparse_as_csr
+
+        off, t, w = sparse_as_csr(vectors)
+        n = off.shape[0] - 1
+        row0 = self._sparse_global if row0 is None else int(row0)
+        self._check_rows("set_sparse", row0, n)
+        if row0 > self._sparse_global:
+            raise ValueError(f"set_sparse: row0={row0} beyond the {self._sparse_global} rows that have vectors (vectors are append-only)")
+        if n == 0 and row0 == self._sparse_global:
+            return
+        local_row0, loff, (lt, lw) = self._local_csr(row0, off, (t, w))
+        self.local.set_sparse((loff, lt, lw), row0=local_row0)
+        self._sparse_global = row0 + n
+
+    @property
+    def sparse_rows(self) -> int:
+        """The leading GLOBAL rows that have sparse vectors."""
+        return self._sparse_global
+
+    def search_sparse(self, terms, weights, k: int, allow=None):
+        """``IndexFlat.search_sparse`` over the shards (collective): ``(D, I)`` with global ids on every rank.  A row's
+        dot product is a function of its own vector and the query, with no corpus statistics, so the merged result
+        equals the single index's in bytes.  The exchange moves 12-byte records (id, D); every rank keeps the first
+        ``k`` by ``(D descending, id)`` on an index of either metric."""
+        from .flat_index import sparse_args
+
+        t, w, k, _ = sparse_args(terms, weights, k)
+        D, I = self.local.search_sparse(t, w, k, allow=self._local_allow(allow))
+        I, (D,), _ = self._columns(I, (D,), metric=0)
+        return tuple(np.ascontiguousarray(a[..., :k]) for a in (D, I))
+
+    def search_hybrid_sparse(self, q, terms, weights, k: int, alpha: float, normalize: bool = False, allow=None):
+        """``IndexFlat.search_hybrid_sparse`` over the shards (collective): ``(D, I, S, L)`` with global ids on every
+        rank, the exchange and the merge of ``search_hybrid``."""
+        from .flat_index import sparse_args
+
+        qa = self._queries(q)
+        if qa.shape[0] != 1:
+            raise ValueError(f"search_hybrid_sparse: one query per call, got {qa.shape[0]}")
+        t, w, k, alpha = sparse_args(terms, weights, k, alpha, what="search_hybrid_sparse")
+        D, I, S, L = self.local.search_hybrid_sparse(qa, t, w, k, alpha, normalize=normalize, allow=self._local_allow(allow))
         I, (D, S, L), _ = self._columns(I, (D, S, L))
         return tuple(np.ascontiguousarray(a[..., :k]) for a in (D, I, S, L))
 
@@ -900,6 +959,20 @@ class ShardedIndexFacade:
                       avgdl: Optional[float] = None, normalize: bool = False, allow=None):
         return self.sh.search_hybrid(np.asarray(q, dtype=np.float32), terms, weights, int(k), float(alpha), k1=k1, b=b,
                                      avgdl=avgdl, normalize=normalize, allow=allow)
+
+    def set_sparse(self, vectors, row0: Optional[int] = None) -> None:
+        self.sh.set_sparse(vectors, row0=row0)
+
+    @property
+    def sparse_rows(self) -> int:
+        return self.sh.sparse_rows
+
+    def search_sparse(self, terms, weights, k: int, allow=None):
+        return self.sh.search_sparse(terms, weights, int(k), allow=allow)
+
+    def search_hybrid_sparse(self, q, terms, weights, k: int, alpha: float, normalize: bool = False, allow=None):
+        return self.sh.search_hybrid_sparse(np.asarray(q, dtype=np.float32), terms, weights, int(k), float(alpha),
+                                            normalize=normalize, allow=allow)
 
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
         return self.sh.search_diverse(np.asarray(q, dtype=np.float32), int(k), lam=lam, fetch=fetch, normalize=normalize,

@@ -34,7 +34,7 @@ import threading
 from dataclasses import dataclass
 from datetime import datetime, timezone
 from pathlib import Path
-from typing import Any, Callable, Dict, List, NamedTuple, Optional
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -342,6 +342,11 @@ class HybridStorage:
         self._mutations = 0  # bumped by every change of the chunk set (part of the allow-cache stamp)
         # the lazily pushed columns of search_sessions (labels), search_recent (priors) and search_hybrid (term lists)
         self._labels, self._priors, self._terms = _Synced(), _Synced(), _Synced()
+        # index_sparse / search_sparse: the rows that carry a sparse vector, the model that made the vectors, and what
+        # of them the file beside the index holds as (model, rows with a vector, rows of the index)
+        self._sparse = _Synced()
+        self._sparse_model: Optional[str] = None
+        self._sparse_saved: Optional[Tuple[Optional[str], int, int]] = None
         # search_sessions: dense group labels per session_id (order of first appearance by faiss_id)
         self._session_labels: Dict[str, int] = {}
         # search_recent: the half-life and reference time (days since the epoch) the priors are stored for; the newest
@@ -430,6 +435,7 @@ class HybridStorage:
         compact = Path(str(self.index_path) + ".compact")
         row = self.db.execute("SELECT value FROM storage_meta WHERE key = 'pending_compact'").fetchone()
         if row is not None:
+            self._drop_sparse_file()   # (the sparse vectors beside the index speak the old numbering)
             if compact.exists():
                 os.replace(str(compact), str(self.index_path))
                 _fsync_dir(self.index_path.parent)
@@ -452,6 +458,7 @@ class HybridStorage:
             self._saved_rows = loaded.ntotal
             self.logger.info(f"Loaded flat index with {loaded.ntotal} vectors")
             self._rebuild_id_mappings()
+            self._load_sparse()
             bad = [i for i in self.faiss_id_to_chunk_id if i >= loaded.ntotal]
             if bad:   # e.g. a crash before the last save with auto_save off: those chunks have no vector on file
                 self.logger.warning(f"{len(bad)} chunks refer to rows beyond the {loaded.ntotal} rows of the index file; "
@@ -1025,6 +1032,150 @@ class HybridStorage:
 
         return self._ranked_in_index(query_embedding, config, filters, fi.MAX_HYBRID_K, run)
 
+    # ------------------------------------------------------- sparse vectors
+    @property
+    def sparse_path(self) -> Path:
+        """The file beside the index file that holds the chunks' sparse vectors."""
+        return Path(str(self.index_path) + ".sparse.npz")
+
+    @staticmethod
+    def _sparse_model_name(sparse_encoder) -> str:
+        name = getattr(sparse_encoder, "model_name", None) or getattr(sparse_encoder, "model_dir", None)
+        return str(name) if name else type(sparse_encoder).__name__
+
+    def _drop_sparse_file(self) -> None:
+        self._sparse_saved = None
+        if self.sparse_path.exists():
+            self.sparse_path.unlink()
+
+    def _save_sparse(self, ntotal: int) -> None:
+        """``save_index``'s second file: ``offsets``, ``terms``, ``weights`` of all ``ntotal`` rows, the rows that have a
+        vector and the model's name, as one ``.npz``, written whole through a temporary sibling.  Skipped while the
+        file already says the same; nothing is written for an index that carries no vectors."""
+        ix = self.faiss_index
+        rows = self._sparse.rows if self._sparse.index is ix else 0
+        if rows <= 0 or not hasattr(ix, "get_sparse"):
+            return
+        state = (self._sparse_model, rows, ntotal)
+        if state == self._sparse_saved and self.sparse_path.exists():
+            return
+        off, terms, weights = ix.get_sparse(0, ntotal)
+        tmp = str(self.sparse_path) + ".tmp.npz"
+        np.savez(tmp, offsets=off, terms=terms, weights=weights, rows=np.int64(rows), model=np.array(self._sparse_model or ""))
+        os.replace(tmp, str(self.sparse_path))
+        _fsync_dir(self.sparse_path.parent)
+        self._sparse_saved = state
+
+    def _load_sparse(self) -> None:
+        """The vectors of ``_save_sparse`` back into a freshly loaded index, when the file is there and speaks of as many
+        rows as the index has; otherwise nothing, and ``index_sparse`` encodes lazily."""
+        ix = self.faiss_index
+        if not self.sparse_path.exists() or not hasattr(ix, "set_sparse"):
+            return
+        try:
+            with np.load(str(self.sparse_path)) as z:
+                off, terms, weights = z["offsets"], z["terms"], z["weights"]
+                rows, model = int(z["rows"]), str(z["model"])
+            if off.shape[0] - 1 != ix.ntotal or not 0 < rows <= ix.ntotal:
+                self.logger.warning(f"{self.sparse_path.name} speaks of {off.shape[0] - 1} rows, the index has {ix.ntotal}: ignored")
+                return
+            e = int(off[rows])
+            ix.set_sparse((np.ascontiguousarray(off[:rows + 1]), terms[:e], weights[:e]), row0=0)
+        except Exception as e:  # a corrupt or foreign file: the lazy sync encodes again
+            self.logger.warning(f"Could not load the sparse vectors: {e}")
+            return
+        self._sparse.index, self._sparse.rows = ix, rows
+        self._sparse_model = model or None
+        self._sparse_saved = (self._sparse_model, rows, ix.ntotal)
+        self.logger.info(f"Loaded the sparse vectors of {rows} rows")
+
+    def _sync_sparse(self, ntotal: int, sparse_encoder, batch_size: int = 32) -> int:
+        """Bring the index's sparse vectors up to date with SQLite, in the shape of ``_sync_terms``: row = ``faiss_id``,
+        vector = ``sparse_encoder.encode_documents`` of the chunk's stored text; a row without a live chunk gets the
+        empty vector.  Only the tail ``[synced, ntotal)`` is encoded after adds; everything again when the index
+        object was replaced or the vectors came from another model.  Returns the number of texts encoded."""
+        name = self._sparse_model_name(sparse_encoder)
+        lo = self._sparse.rows_of(self.faiss_index)
+        if lo > 0 and self._sparse_model != name:
+            lo = 0
+        if lo >= ntotal:
+            return 0
+        rows = self.db.cursor().execute("SELECT faiss_id, text FROM chunks WHERE faiss_id >= ? AND faiss_id < ? ORDER BY faiss_id",
+                                        (lo, ntotal)).fetchall()
+        rows = [(fid, text) for fid, text in rows if self.faiss_id_to_chunk_id.get(fid) is not None]
+        empty = (np.zeros(0, np.int64), np.zeros(0, np.float32))
+        vectors = [empty] * (ntotal - lo)
+        if rows:
+            encoded = sparse_encoder.encode_documents([text or "" for _, text in rows], batch_size=batch_size)
+            for (fid, _), v in zip(rows, encoded):
+                t, w = np.asarray(v[0], np.int64), np.asarray(v[1], np.float32)
+                keep = w > 0.0                   # (a zero weight means "not in the vector")
+                vectors[fid - lo] = (t[keep], w[keep])
+        self.faiss_index.set_sparse(vectors, row0=lo)
+        self._sparse.rows, self._sparse_model = ntotal, name
+        return len(rows)
+
+    def index_sparse(self, sparse_encoder, batch_size: int = 32) -> int:
+        """Give every live chunk that has none yet a learned sparse vector (``SparseEncoder.encode_documents`` of its
+        stored text, stored in the index by ``IndexFlat.set_sparse``); tombstones get the empty vector.  Lazy: only
+        rows added since the last call are encoded, and ``search_sparse`` / ``search_hybrid_sparse`` call it
+        themselves.  ``save_index`` writes the vectors beside the index file and ``initialize`` loads them again, so a
+        corpus is not encoded on every load.  Returns the number of texts encoded."""
+        self._require("sparse vectors", "set_sparse", "search_sparse")
+        with self._lock:
+            frame = self._search_frame(SearchConfig())
+            if frame is None:
+                return 0
+            done = self._sync_sparse(frame[1], sparse_encoder, batch_size)
+            if done and self.config.auto_save:
+                self._save_sparse(frame[1])
+            return done
+
+    def _sparse_query(self, query_text: str, sparse_encoder):
+        v = sparse_encoder.encode_queries([query_text or ""], max_terms=fi.MAX_SPARSE_QUERY_TERMS)[0]
+        t, w = np.asarray(v[0], np.int64), np.asarray(v[1], np.float32)
+        keep = w != 0.0
+        return t[keep], w[keep]
+
+    def search_sparse(self, query_text: str, sparse_encoder, config: Optional[SearchConfig] = None,
+                      filters: Optional[Dict[str, Any]] = None) -> List[SearchResult]:
+        """Learned sparse retrieval as a FIRST stage: ``top_k`` chunks ranked by the dot product of the query's sparse
+        vector (``sparse_encoder.encode_queries``, at most 64 terms) with the chunks' sparse vectors, over ALL allowed
+        rows inside the index (``IndexFlat.search_sparse``); no dense row is read and no query embedding is needed.
+        Only chunks that share a term with the query are returned.  Each result's ``similarity`` is the dot product,
+        to which ``similarity_threshold`` applies.  Tombstones and filters as in ``search_hybrid``."""
+        self._require("sparse search", "set_sparse", "search_sparse")
+
+        def run(q, k, allow, ntotal, cfg):
+            self._sync_sparse(ntotal, sparse_encoder)
+            t, w = self._sparse_query(query_text, sparse_encoder)
+            sims, ids = self.faiss_index.search_sparse(t, w, k, allow=allow)
+            return sims, ids
+
+        return self._ranked_in_index(None, config, filters, fi.MAX_HYBRID_K, run)
+
+    def search_hybrid_sparse(self, query_text: str, query_embedding, sparse_encoder, alpha: float = 0.3,
+                             config: Optional[SearchConfig] = None,
+                             filters: Optional[Dict[str, Any]] = None) -> List[SearchResult]:
+        """``search_hybrid`` with the learned sparse dot product in the place of BM25: ``top_k`` chunks ranked by
+        ``similarity + alpha * sp`` (an L2 storage: ``distance - alpha * sp``) over ALL allowed rows inside the index
+        (``IndexFlat.search_hybrid_sparse``).  Results come in FUSED order, each with its RAW similarity, to which
+        ``similarity_threshold`` applies.  ``sp`` is not normalised: it grows with the number and weight of the shared
+        terms.  ``alpha = 0.3`` is a default NOBODY HAS TUNED, as it is for BM25: there is no relevance data offline."""
+        a = float(alpha)
+        if not np.isfinite(a):
+            raise ValueError(f"search_hybrid_sparse: alpha={alpha} is not finite")
+        self._require("sparse hybrid search", "set_sparse", "search_hybrid_sparse")
+
+        def run(q, k, allow, ntotal, cfg):
+            self._sync_sparse(ntotal, sparse_encoder)
+            t, w = self._sparse_query(query_text, sparse_encoder)
+            _, ids, sims, _ = self.faiss_index.search_hybrid_sparse(q, t, w, k, a, normalize=self.config.normalize_embeddings,
+                                                                    allow=allow)
+            return sims, ids
+
+        return self._ranked_in_index(query_embedding, config, filters, fi.MAX_HYBRID_K, run)
+
     def search_reranked(self, query_text: str, query_embedding, reranker, config: Optional[SearchConfig] = None,
                         filters: Optional[Dict[str, Any]] = None, fetch: int = 50) -> List[Reranked]:
         """Retrieve, then re-read: the ordinary ``search`` for ``max(fetch, top_k)`` hits, each ``(query_text, chunk
@@ -1392,6 +1543,7 @@ class HybridStorage:
             self.chunk_id_to_faiss_id.clear()
             self.faiss_id_to_chunk_id.clear()
             self.total_chunks = 0
+            self._drop_sparse_file()
             if self.config.auto_save:
                 self.save_index()
         self.logger.info("Cleared all data from storage")
@@ -1429,6 +1581,7 @@ class HybridStorage:
             else:
                 self._write_index_atomically(ix, path)
             self._saved_rows = n
+            self._save_sparse(n)
         self.logger.info(f"Saved flat index ({n} vectors) to {self.index_path}")
 
     def _crash_point(self, where: str) -> None:
@@ -1531,6 +1684,7 @@ class HybridStorage:
             cur.execute("INSERT OR REPLACE INTO storage_meta (key, value) VALUES ('pending_compact', ?)", (str(len(live)),))
             self.db.commit()
             self._crash_point("compaction committed, file not yet moved")
+            self._drop_sparse_file()            # (it speaks the old numbering)
             os.replace(compact, str(self.index_path))
             _fsync_dir(self.index_path.parent)
             cur.execute("DELETE FROM storage_meta WHERE key = 'pending_compact'")
@@ -1548,6 +1702,13 @@ class HybridStorage:
             self._mutations += 1
             # (the rows were renumbered: search_sessions, search_recent and search_hybrid push every row again)
             self._labels, self._priors, self._terms = _Synced(), _Synced(), _Synced()
+            # ... but no text is encoded again: an index compacted in place has compacted its sparse vectors with the rows
+            if in_place and self._sparse.index is old and hasattr(old, "sparse_rows"):
+                self._sparse.rows = int(old.sparse_rows)
+            else:
+                self._sparse = _Synced()
+            if self.config.auto_save:
+                self._save_sparse(self.faiss_index.ntotal)
             if not in_place:
                 old.close()
         self.logger.info("Flat index rebuilt")

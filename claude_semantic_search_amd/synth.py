@@ -85,6 +85,26 @@ def term_lists(n: int, seed: int, vocab: int = TERM_VOCAB):
     return off, np.ascontiguousarray(tok[keep])
 
 
+def sparse_vectors(n: int, seed: int, vocab: int = TERM_VOCAB, lattice: bool = False):
+    """Synthetic per-row sparse vectors, as CSR ``(offsets int64 [n + 1], terms uint32, weights float32)``: the row
+    sizes and the ``u^3`` term skew of ``term_lists`` (same draws from ``numpy.random.default_rng(seed)``), the terms
+    de-duplicated per row and ascending, then one weight per kept entry, ``log1p`` of a standard exponential draw (a
+    draw that rounds to 0 becomes the smallest positive normal float32).  ``lattice=True``: the weights are multiples of 1/8
+    in ``(0, 4]`` instead, so that sums of products with lattice query weights are exact in fp32."""
+    rng = np.random.default_rng(seed)
+    dl = 16 + rng.integers(0, 240, size=n)
+    tok = np.floor(vocab * rng.random((n, 255)) ** 3).astype(np.int64)
+    keep = np.arange(255)[None, :] < dl[:, None]
+    key = np.unique((np.arange(n, dtype=np.int64)[:, None] << 32 | tok)[keep])
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key >> 32, minlength=n), out=off[1:])
+    if lattice:
+        w = (rng.integers(1, 33, size=key.shape[0]) / 8.0).astype(np.float32)
+    else:
+        w = np.maximum(np.log1p(rng.standard_exponential(key.shape[0])).astype(np.float32), np.finfo(np.float32).tiny)
+    return off, (key & 0xFFFFFFFF).astype(np.uint32), w
+
+
 def query_terms(j: int, count: int = 4, vocab: int = TERM_VOCAB) -> np.ndarray:
     """The distinct values, in order of first occurrence, of ``floor(vocab * default_rng(500 + j).random(count)^3)``."""
     t = np.floor(vocab * np.random.default_rng(500 + j).random(count) ** 3).astype(np.int64)

@@ -388,6 +388,64 @@ int css_index_search_hybrid(css_index* ix, const float* q_host /* [dim] */, int 
                             const uint32_t* allow_bits_host, float* D_host, int64_t* I_host,
                             float* S_host /* may be NULL */, float* L_host /* may be NULL */);
 
+/* Per-row sparse vectors and sparse search (learned sparse retrieval as a FIRST stage and as the sparse leg of hybrid
+ * search: OpenSearch neural sparse, Qdrant and Milvus sparse vectors, Vespa, ELSER).  A row may carry a sparse vector,
+ * (term, weight) pairs such as SparseEncoder.encode produces; a query is a sparse vector too, and a row's value is the
+ * dot product of the two.  A second per-row list kind, independent of the term lists above: an index may carry both,
+ * either or neither.
+ *  - Vectors.  A term is a uint32 below CSS_TERM_SPACE; a stored weight is finite, > 0 and <= CSS_MAX_SPARSE_WEIGHT (a
+ *    zero weight means "not in the vector" and is refused, not stored); at most CSS_MAX_SPARSE_ROW_ENTRIES entries per
+ *    row, terms distinct within a row.  Stored per entry: 8 bytes, (uint32 term, float weight), ascending by term.
+ *    css_index_set_sparse takes rows [row0, row0 + n) as CSR (offsets_host [n + 1] from 0, terms_host, weights_host;
+ *    any order within a row, empty rows allowed; the library sorts each row on the host) under the APPEND-ONLY rules of
+ *    css_index_set_terms: with T the leading rows that have vectors, row0 == T appends, row0 < T first drops the vectors
+ *    of ALL rows >= row0, row0 > T and a range outside [0, ntotal) are CSS_ERR_INVALID.  Offsets that do not start at 0
+ *    or that decrease, a row of too many entries, a term >= 2^24, a weight that is NaN, infinite, zero, negative or too
+ *    large, and a term repeated within a row are CSS_ERR_INVALID; the message names the row; all of it is checked before
+ *    anything is written.  css_index_get_sparse reads the stored form of rows [row0, row0 + n) back: offsets_out
+ *    [n + 1] from 0, then terms and weights (either may be NULL: a first call sizes the second).  css_index_sparse_rows
+ *    gives T.
+ *  - Storage.  Nothing is allocated before the first css_index_set_sparse.  Then 8 bytes per entry and 8 per row with
+ *    a vector, the row offsets mirrored on the host.  NO df table and NO lengths: a dot product needs no corpus
+ *    statistics, which also makes a shard's column equal to the single index's by construction.  The vectors follow
+ *    the rows: kept through capacity growth, none for appended rows, forgotten by css_index_reset, compacted by
+ *    css_index_remove_rows with the same keep bits -- afterwards css_index_get_sparse equals that of a fresh index built
+ *    from the kept rows.
+ *  - The column.  With the query's m <= CSS_MAX_SPARSE_QUERY_TERMS distinct terms t_j and weights w_j (finite, nonzero,
+ *    |w_j| <= CSS_MAX_SPARSE_WEIGHT; negative weights are allowed), in fp32 and in this order (-ffp-contract=off):
+ *        sp_r = 0.0f;  hit_r = false;
+ *        for j = 0 .. m-1 in the caller's order:
+ *            if row r stores t_j with weight d:  sp_r = sp_r + w_j * d;  hit_r = true;
+ *        col[r] = hit_r ? sp_r : miss          // miss = 0.0f (hybrid) or -inf (pure sparse search); rows >= T: miss
+ *    The sum runs in QUERY-TERM order, whatever the order of the entries in memory, so a float32 restatement gives the
+ *    same bits and a shard gives the same bits as one index.
+ *  - css_index_search_sparse.  One request per call, 1 <= k <= 128.  The k best HIT rows -- rows that share at least one
+ *    term with the query -- among the allowed rows (allow_bits_host as in css_index_search_masked), ranked by the
+ *    column ALONE: larger sp is better on an index of either metric, ties to the lower id (a hit row whose products
+ *    cancel to 0.0 is still a hit).  D = sp, I = global ids.  Fewer than k hits, m == 0, an index without vectors or
+ *    an empty index give padding: I = -1, D = -FLT_MAX.  On the device: k_sparse_scores with miss = -inf (8 bytes per
+ *    entry and 8 per row read, 4 per row written), k_sparse_topk over slices of the column, the part merge.  No dense
+ *    row is read.  One upload, one wait; a search never edits the index.
+ *  - css_index_search_hybrid_sparse is css_index_search_hybrid with sp in the place of the BM25 column (miss = 0.0f):
+ *        inner product   f = fmaf(alpha, sp_r, s)        larger is better
+ *        squared L2      f = fmaf(-alpha, sp_r, dist)    smaller is better
+ *    D, I, S, L (= sp of the returned rows) and the padding as there.  m == 0, alpha == 0 or an index without vectors
+ *    give css_index_search_prior on an index without priors bit for bit. */
+#define CSS_MAX_SPARSE_QUERY_TERMS 64
+#define CSS_MAX_SPARSE_ROW_ENTRIES 65536
+#define CSS_MAX_SPARSE_WEIGHT 65536.0f
+int css_index_set_sparse(css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host /* [n+1] */,
+                         const uint32_t* terms_host, const float* weights_host);
+int css_index_get_sparse(css_index* ix, int64_t row0, int64_t n, int64_t* offsets_out /* [n+1], from 0 */,
+                         uint32_t* terms_out /* may be NULL */, float* weights_out /* may be NULL */);
+int css_index_sparse_rows(css_index* ix, int64_t* rows_out);
+int css_index_search_sparse(css_index* ix, const uint32_t* terms_host, const float* weights_host, int m, int k,
+                            const uint32_t* allow_bits_host, float* D_host /* [k] */, int64_t* I_host /* [k] */);
+int css_index_search_hybrid_sparse(css_index* ix, const float* q_host /* [dim] */, int k, float alpha,
+                                   const uint32_t* terms_host, const float* weights_host, int m, int normalize_q,
+                                   const uint32_t* allow_bits_host, float* D_host, int64_t* I_host,
+                                   float* S_host /* may be NULL */, float* L_host /* may be NULL */);
+
 /* Significant terms (Elasticsearch's significant_terms aggregation, the keyword side of BERTopic): which terms set a
  * selection of rows apart from a background -- "what is in this cluster / this project / these hits".  Everything is
  * read from the term lists above; the rows' values play no part.  T = the leading rows that have lists.
