@@ -42,6 +42,13 @@ MAX_EXAMPLES = 16   # include/css_hip.h CSS_MAX_EXAMPLES
 MAX_EXAMPLES_K = 128   # css_index_search_examples: the same list size
 MAX_CENTROIDS = 4096   # include/css_hip.h CSS_MAX_CENTROIDS
 MAX_TRANSFORM_ROWS = 256   # include/css_hip.h CSS_MAX_TRANSFORM_ROWS
+MAX_ATTRS = 16   # include/css_hip.h CSS_MAX_ATTRS
+MAX_CLAUSES = 16   # include/css_hip.h CSS_MAX_CLAUSES
+MAX_TABLE_BITS = 1 << 27   # include/css_hip.h CSS_MAX_TABLE_BITS
+ATTR_I32, ATTR_F32 = 0, 1   # include/css_hip.h CSS_ATTR_*
+WHERE_OPS = ("==", "!=", "<", "<=", ">", ">=", "in", "not in")   # include/css_hip.h CSS_WHERE_*: the index is the code
+WHERE_TILE_ROWS = 1024   # csrc/css_where.h kWhereTileRows: rows of one tile of k_where
+WHERE_LDS_WORDS = 8192   # csrc/css_where.h kWhereLdsWords: table words of a call that still go to LDS
 
 
 class CssError(RuntimeError):
@@ -60,6 +67,18 @@ class DevInfo(ctypes.Structure):
         ("hbm_free_bytes", c_int64),
         ("lds_bytes_per_cu", c_int),
         ("clock_mhz", c_int),
+    ]
+
+
+class Clause(ctypes.Structure):
+    """include/css_hip.h css_clause."""
+    _fields_ = [
+        ("slot", ctypes.c_int32),
+        ("op", ctypes.c_int32),
+        ("value", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("table_off", c_int64),
+        ("table_bits", c_int64),
     ]
 
 
@@ -165,6 +184,13 @@ PROTOTYPES = {
                                  c_void_p, c_void_p, c_void_p]),
     "css_index_last_facet_sweeps": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     "css_index_set_facet_lds_entries": (c_int, [c_void_p, c_int64]),
+    "css_index_set_attr": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p]),
+    "css_index_get_attr": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p]),
+    "css_index_attr_type": (c_int, [c_void_p, c_int, POINTER(c_int)]),
+    "css_index_drop_attr": (c_int, [c_void_p, c_int]),
+    "css_index_where": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
+    "css_index_facets_attr": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p, c_int, c_int64, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "css_merge_topk_dev": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "css_merge_topk_packed_dev": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int,
                                           c_void_p]),

@@ -65,8 +65,9 @@
 // sweep_slots the fan-out of their launchers over TT / METRIC and the 1 / 2 / 8 / 16 query slots, launch_merge_final the
 // plain merge behind them; css_knn_plan.h states the rules of the candidate cascade (kind, growth, schedule, error bound,
 // tickets) and launch_scan_coarse applies them as named steps over one CascadeCall; RowColumn is a 4-byte-per-row
-// column (labels, priors) and css_index::columns() the list every row operation walks.  The sweep body of k_scan_small,
-// k_range_small, k_scan_prior, k_scan_examples and k_facet_small is deliberately NOT shared (css_knn_range.h says why).
+// column (labels, priors, the attribute slots) and css_index::columns() the list every row operation walks.  The sweep
+// body of k_scan_small, k_range_small, k_scan_prior, k_scan_examples and k_facet_small is deliberately NOT shared
+// (css_knn_range.h says why).
 #include "css_common.h"
 #include "css_devbuf.h"
 #include "css_knn_kernels.h"
@@ -91,8 +92,9 @@
 
 using namespace css;
 
-// A 4-byte value per row that follows the rows (the group labels, the priors): [cap] words, empty until first set
-// (column_for_write), every row that was never set at the default -- `fill` in every byte.  Its life is stated once:
+// A 4-byte value per row that follows the rows (the group labels, the priors, an attribute): [cap] words, empty until
+// first set (column_for_write), every row that was never set at the default -- `fill` in every byte.  Its life is
+// stated once:
 // column_alloc (first set, capacity growth, compaction), compact_column, column_check / column_for_write / column_get
 // (the set and get entry points), and one loop over css_index::columns() each in reallocate_rows, ingest,
 // css_index_reset and css_index_remove_rows.
@@ -105,6 +107,11 @@ struct RowColumn {
         static_assert(sizeof(T) == sizeof(int32_t), "a column holds 4-byte values");
         return reinterpret_cast<T*>(words.p);
     }
+};
+// An attribute slot (css_index_set_attr): a column with the default -1 / NaN, typed by its first set
+struct AttrColumn : RowColumn {
+    int type = -1;   // CSS_ATTR_I32 / CSS_ATTR_F32; -1: never set (no memory)
+    AttrColumn() : RowColumn{0xFF, "hipMalloc(attribute column)"} {}
 };
 
 struct css_index {
@@ -131,8 +138,15 @@ struct css_index {
     // fp32 priors (css_index_set_priors), 0 = no boost
     RowColumn labels{0xFF, "hipMalloc(group labels)"};
     RowColumn priors{0x00, "hipMalloc(priors)"};
-    static constexpr int kColumns = 2;
-    std::array<RowColumn*, kColumns> columns() { return {&labels, &priors}; }
+    // ... and the attribute slots that css_index_where and css_index_facets_attr read; a slot that was never set is a
+    // null pointer to every loop over columns()
+    AttrColumn attrs[CSS_MAX_ATTRS];
+    static constexpr int kColumns = 2 + CSS_MAX_ATTRS;
+    std::array<RowColumn*, kColumns> columns() {
+        std::array<RowColumn*, kColumns> all{&labels, &priors};
+        for (int s = 0; s < CSS_MAX_ATTRS; ++s) all[2 + s] = &attrs[s];
+        return all;
+    }
     // per-row term lists (css_index_set_terms, css_lexical.h): the leading lex_rows rows own entries
     // [lex_off[r], lex_off[r + 1]) of lex_ent and a length lex_dl[r]; lex_df [CSS_TERM_SPACE] and lex_total [1] are the
     // statistics.  All empty until terms are first set (lex_df.p tells).  The buffers are sized by the lists, not by
@@ -221,6 +235,8 @@ struct css_index {
     DevBuf<int32_t> facet_col;
     int64_t facet_lds_entries = -1;     // css_index_set_facet_lds_entries: -1 = the library's rule (facet_lds_fits)
     int64_t last_facet_sweeps = 0, last_facet_lds_sweeps = 0;   // of the last css_index_facets (css_index_last_facet_sweeps)
+    // css_index_where (css_where.h): the call's table words, and [2 words of count | ceil(ntotal / 32) result words]
+    DevBuf<uint32_t> where_tab, where_out;
     // css_index_search_rows: the gathered query rows [nq, dim] (not q_raw: the host search copies into that before it
     // has waited for ws_ev), one invalid-id flag per query, the search's own [nq, k + 1] results in front of
     // k_drop_self, and the device copy of a host id list
@@ -2849,6 +2865,7 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 #include "css_knn_prior.h"
 #include "css_lexical.h"
 #include "css_sparse.h"
+#include "css_where.h"
 #include "css_sigterms.h"
 
 // HASP: the index has a prior column (false: every prior is 0, the kernel loads none)
@@ -3342,6 +3359,7 @@ int css_index_reset(css_index* ix) {
     CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
     // the columns go with the rows: the index is again one that never set any
     for (RowColumn* col : ix->columns()) CSS_HIP_TRY(col->words.drop());
+    for (AttrColumn& a : ix->attrs) a.type = -1;
     const int rc = drop_terms(ix);   // and the term lists with their statistics, and the sparse vectors
     return rc != CSS_OK ? rc : drop_sparse(ix);
 }
@@ -4066,6 +4084,166 @@ int css_index_set_groups(css_index* ix, int64_t row0, int64_t n, const int32_t* 
 int css_index_get_groups(css_index* ix, int64_t row0, int64_t n, int32_t* labels_out_host) {
     CSS_REQUIRE(ix, "css_index_get_groups: NULL index");
     return column_get(ix, ix->labels, "css_index_get_groups", "labels_out", row0, n, labels_out_host);
+}
+
+// ------------------------------------------------------------------ attribute columns and css_index_where (css_where.h)
+#define CSS_REQUIRE_SLOT(fn, slot) \
+    CSS_REQUIRE((slot) >= 0 && (slot) < CSS_MAX_ATTRS, "%s: attribute slot %d outside [0, %d)", fn, (int)(slot), CSS_MAX_ATTRS)
+
+int css_index_set_attr(css_index* ix, int slot, int type, int64_t row0, int64_t n, const void* values_host) {
+    CSS_REQUIRE(ix, "css_index_set_attr: NULL index");
+    CSS_REQUIRE_SLOT("css_index_set_attr", slot);
+    CSS_REQUIRE(type == CSS_ATTR_I32 || type == CSS_ATTR_F32, "css_index_set_attr: type=%d is neither CSS_ATTR_I32 nor CSS_ATTR_F32", type);
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    AttrColumn& col = ix->attrs[slot];
+    CSS_REQUIRE(col.type < 0 || col.type == type, "css_index_set_attr: attribute slot %d holds %s values, not %s", slot,
+                col.type == CSS_ATTR_I32 ? "int32" : "float32", type == CSS_ATTR_I32 ? "int32" : "float32");
+    int rc = column_check("css_index_set_attr", "values", row0, n, ix->ntotal, values_host);
+    if (rc != CSS_OK || n == 0) return rc;   // (no row, no type: a typed slot always has its column)
+    DeviceGuard g(ix->device);
+    if ((rc = column_for_write(ix, &col)) != CSS_OK) return rc;
+    col.type = type;
+    CSS_HIP_TRY(hipMemcpyAsync(col.words.p + row0, values_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ix->stream));
+    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));   // (the caller's array is free again)
+    return CSS_OK;
+}
+
+int css_index_get_attr(css_index* ix, int slot, int64_t row0, int64_t n, void* out_host) {
+    CSS_REQUIRE(ix, "css_index_get_attr: NULL index");
+    CSS_REQUIRE_SLOT("css_index_get_attr", slot);
+    return column_get(ix, ix->attrs[slot], "css_index_get_attr", "out", row0, n, out_host);
+}
+
+int css_index_attr_type(css_index* ix, int slot, int* type) {
+    CSS_REQUIRE(ix && type, "css_index_attr_type: NULL argument");
+    CSS_REQUIRE_SLOT("css_index_attr_type", slot);
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    *type = ix->attrs[slot].type;
+    return CSS_OK;
+}
+
+int css_index_drop_attr(css_index* ix, int slot) {
+    CSS_REQUIRE(ix, "css_index_drop_attr: NULL index");
+    CSS_REQUIRE_SLOT("css_index_drop_attr", slot);
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    AttrColumn& col = ix->attrs[slot];
+    if (!col.words.p) return CSS_OK;
+    DeviceGuard g(ix->device);
+    // rows appended on another stream still write their default into the column
+    if (ix->ingest_pending) CSS_HIP_TRY(hipEventSynchronize(ix->ingest_ev));
+    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    col.type = -1;
+    CSS_HIP_TRY(col.words.drop());
+    return CSS_OK;
+}
+
+namespace {
+// The clauses of a call checked against the slots and turned into what k_where reads; nothing is enqueued.  Caller
+// holds mu (shared is enough: set and drop take it exclusively)
+int where_args_of(css_index* ix, const css_clause* clauses, int nclauses, int64_t table_words, WhereArgs* out) {
+    WhereArgs& a = *out;
+    a.n = nclauses;
+    for (int c = 0; c < nclauses; ++c) {
+        const css_clause& cl = clauses[c];
+        CSS_REQUIRE(cl.slot >= 0 && cl.slot < CSS_MAX_ATTRS, "css_index_where: clause %d: attribute slot %d outside [0, %d)", c,
+                    (int)cl.slot, CSS_MAX_ATTRS);
+        const AttrColumn& col = ix->attrs[cl.slot];
+        CSS_REQUIRE(col.type >= 0 && col.words.p, "css_index_where: clause %d: attribute slot %d was never set", c, (int)cl.slot);
+        CSS_REQUIRE(cl.op >= CSS_WHERE_EQ && cl.op <= CSS_WHERE_NOT_IN, "css_index_where: clause %d: unknown op %d", c, (int)cl.op);
+        const bool f32 = col.type == CSS_ATTR_F32, in = cl.op >= CSS_WHERE_IN;
+        CSS_REQUIRE(!(f32 && in), "css_index_where: clause %d: IN / NOT_IN on attribute slot %d, which holds float32 values", c,
+                    (int)cl.slot);
+        a.col[c] = col.as<const uint32_t>();
+        a.key[c] = a.toff[c] = a.tbits[c] = 0u;
+        int op = cl.op;
+        if (in) {
+            CSS_REQUIRE(cl.table_bits >= 0 && cl.table_bits <= CSS_MAX_TABLE_BITS, "css_index_where: clause %d: table_bits=%lld outside [0, %d]",
+                        c, (long long)cl.table_bits, CSS_MAX_TABLE_BITS);
+            CSS_REQUIRE(cl.table_off >= 0 && cl.table_off <= table_words && (cl.table_bits + 31) / 32 <= table_words - cl.table_off,
+                        "css_index_where: clause %d: the table of %lld bits at word %lld does not lie inside the %lld table words", c,
+                        (long long)cl.table_bits, (long long)cl.table_off, (long long)table_words);
+            a.toff[c] = (uint32_t)cl.table_off;
+            a.tbits[c] = (uint32_t)cl.table_bits;
+        } else if (f32) {
+            const uint32_t b = (uint32_t)cl.value;
+            if (where_is_nan(b)) op = cl.op == CSS_WHERE_NE ? kWhereAlways : kWhereNever;
+            a.key[c] = where_key_f32(b);
+        } else {
+            a.key[c] = where_key_i32((uint32_t)cl.value);
+        }
+        a.kind[c] = (uint32_t)op | (f32 ? 0x100u : 0u);
+    }
+    return CSS_OK;
+}
+
+// nrows > 0 rows inside the caller's host frame: tables and allow bitmap up, k_where, [count | bits] back.  Everything
+// has finished on the index's own stream when this returns CSS_OK.
+int where_locked(css_index* ix, HostCall& hc, const WhereArgs& a, const uint32_t* tables_host, int64_t table_words,
+                 const uint32_t* allow_bits_host, uint32_t* bits_out_host, int64_t* count_out) {
+    const hipStream_t st = ix->stream;
+    const int64_t n = hc.rows.n, nwords = (n + 31) / 32, tiles = (n + kWhereTileRows - 1) / kWhereTileRows;
+    int rc;
+    WsTurn turn(ix, st);   // mask_ws, where_tab and where_out are shared workspaces
+    if (turn.rc != CSS_OK) return turn.rc;
+    if (table_words > 0) {
+        if ((rc = hc.upload(allow_bits_host, ix->where_tab, tables_host, (size_t)table_words)) != CSS_OK) return rc;
+    } else {
+        hc.enqueued = true;
+        if ((rc = upload_allow_bits(ix, allow_bits_host, &hc.rows)) != CSS_OK) return rc;
+    }
+    if ((rc = ix->where_out.grow((size_t)nwords + 2)) != CSS_OK) return rc;
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    unsigned long long* count = reinterpret_cast<unsigned long long*>(ix->where_out.p);
+    uint32_t* bits = ix->where_out.p + 2;
+    CSS_HIP_TRY(hipMemsetAsync(count, 0, sizeof(unsigned long long), st));
+    // a block takes tiles in turn: enough blocks to fill the CUs, few enough that the LDS copy of the tables is rare
+    const unsigned blocks = (unsigned)std::min<int64_t>(tiles, (int64_t)ix->num_cus * 8);
+    const bool lds = table_words <= kWhereLdsWords;
+    {
+        ProfScope ps("where", st);
+        if (lds)
+            hipLaunchKernelGGL(k_where<true>, dim3(blocks), dim3(256), (size_t)table_words * sizeof(uint32_t), st, a, (const uint32_t*)ix->where_tab.p, (int)table_words,
+                               hc.rows.mask, n, tiles, bits, count);
+        else
+            hipLaunchKernelGGL(k_where<false>, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)ix->where_tab.p, (int)table_words,
+                               hc.rows.mask, n, tiles, bits, count);
+        CSS_LAUNCH_CHECK();
+    }
+    const size_t bytes = ((size_t)nwords + 2) * sizeof(uint32_t);
+    unsigned long long cnt = 0;
+    if (ix->h_stage != nullptr && css_index::fits_host_stage(bytes)) {   // one copy, one wait (as read_ints)
+        char* back = ix->h_stage + css_index::kHostStage;
+        CSS_HIP_TRY(hipMemcpyAsync(back, ix->where_out.p, bytes, hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipStreamSynchronize(st));
+        memcpy(&cnt, back, sizeof(cnt));
+        memcpy(bits_out_host, back + 2 * sizeof(uint32_t), (size_t)nwords * sizeof(uint32_t));
+    } else {
+        CSS_HIP_TRY(hipMemcpyAsync(bits_out_host, bits, (size_t)nwords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipMemcpyAsync(&cnt, count, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipStreamSynchronize(st));
+    }
+    *count_out = (int64_t)cnt;
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_where(css_index* ix, const css_clause* clauses, int nclauses, const uint32_t* tables_host, int64_t table_words,
+                    const uint32_t* allow_bits_host, uint32_t* bits_out_host, int64_t* count_out) {
+    CSS_REQUIRE(ix, "css_index_where: NULL index");
+    CSS_REQUIRE(nclauses >= 0 && nclauses <= CSS_MAX_CLAUSES, "css_index_where: nclauses=%d outside [0, %d]", nclauses, CSS_MAX_CLAUSES);
+    CSS_REQUIRE(nclauses == 0 || clauses, "css_index_where: clauses is NULL");
+    CSS_REQUIRE(table_words >= 0 && table_words <= (int64_t)CSS_MAX_CLAUSES * (CSS_MAX_TABLE_BITS / 32),
+                "css_index_where: table_words=%lld out of range", (long long)table_words);
+    CSS_REQUIRE(table_words == 0 || tables_host, "css_index_where: tables is NULL");
+    CSS_REQUIRE(count_out, "css_index_where: count_out is NULL");
+    HostCall hc(ix, nullptr, false);
+    WhereArgs a;
+    const int rc = where_args_of(ix, clauses, nclauses, table_words, &a);
+    if (rc != CSS_OK) return rc;
+    *count_out = 0;
+    if (hc.rows.n == 0) return CSS_OK;
+    CSS_REQUIRE(bits_out_host, "css_index_where: bits_out is NULL");
+    return hc.wait_if_failed(where_locked(ix, hc, a, tables_host, table_words, allow_bits_host, bits_out_host, count_out));
 }
 
 namespace {
@@ -5386,9 +5564,10 @@ namespace {
 // nq > 0 queries over hc.rows.n > 0 rows inside the caller's host frame, the outputs already at their empty values:
 // the turn at the workspaces, the frame's upload of bitmap and queries, the bucket column, then one table per sweep
 // decoded into the caller's arrays.  Everything has finished on the index's own stream when this returns CSS_OK.
+// bucket_col: a device column of the index in the place of buckets_host / the labels (css_index_facets_attr).
 int facets_locked(css_index* ix, HostCall& hc, const float* q_host, const uint32_t* allow_bits_host, int64_t nq, float radius,
                   int normalize_q, const int32_t* buckets_host, int64_t nbuckets, int64_t* count_out, float* best_score_out,
-                  int64_t* best_id_out, int64_t* total_out, int64_t* unbucketed_out) {
+                  int64_t* best_id_out, int64_t* total_out, int64_t* unbucketed_out, const int32_t* bucket_col = nullptr) {
     hipStream_t st = ix->stream;
     int rc;
     CSS_REQUIRE(hc.rows.n < 0xFFFFFFFFll, "css_index_facets: %lld rows exceed the 32-bit row numbers of the table keys",
@@ -5414,7 +5593,8 @@ int facets_locked(css_index* ix, HostCall& hc, const float* q_host, const uint32
                        (long long)std::min<int64_t>(nq_sweep, nq), (long long)nbuckets);
         return CSS_ERR_OOM;
     }
-    const int32_t* bucket = rows.labels;   // (null: no label was ever set, every hit is unbucketed)
+    // (null: no label was ever set, every hit is unbucketed; bucket_col: the attribute column of css_index_facets_attr)
+    const int32_t* bucket = bucket_col ? bucket_col : rows.labels;
     if (buckets_host) {
         if (!ix->facet_col.try_exact((size_t)rows.n)) {
             css::set_error("css_index_facets: no device memory for the bucket column of %lld rows", (long long)rows.n);
@@ -5454,19 +5634,25 @@ int facets_locked(css_index* ix, HostCall& hc, const float* q_host, const uint32
     }
     return CSS_OK;
 }
-}  // namespace
 
-int css_index_facets(css_index* ix, const float* q_host, int64_t nq, float radius, int normalize_q,
-                     const uint32_t* allow_bits_host, const int32_t* buckets_host, int64_t nbuckets, int64_t* count_out,
-                     float* best_score_out, int64_t* best_id_out, int64_t* total_out, int64_t* unbucketed_out) {
-    CSS_REQUIRE(ix, "css_index_facets: NULL index");
-    CSS_REQUIRE(nq >= 0 && nq < (1 << 24), "css_index_facets: nq=%lld out of range", (long long)nq);
-    CSS_REQUIRE(!std::isnan(radius), "css_index_facets: the radius is NaN");
-    CSS_REQUIRE(nbuckets >= 1 && nbuckets <= CSS_MAX_FACET_BUCKETS, "css_index_facets: nbuckets=%lld outside [1, %d]",
+// The two entry points: the buckets are buckets_host / the labels (slot < 0), or the int32 attribute column `slot`
+int facets_call(const char* fn, css_index* ix, const float* q_host, int64_t nq, float radius, int normalize_q, const uint32_t* allow_bits_host,
+                const int32_t* buckets_host, int slot, int64_t nbuckets, int64_t* count_out, float* best_score_out,
+                int64_t* best_id_out, int64_t* total_out, int64_t* unbucketed_out) {
+    CSS_REQUIRE(ix, "%s: NULL index", fn);
+    CSS_REQUIRE(nq >= 0 && nq < (1 << 24), "%s: nq=%lld out of range", fn, (long long)nq);
+    CSS_REQUIRE(!std::isnan(radius), "%s: the radius is NaN", fn);
+    CSS_REQUIRE(nbuckets >= 1 && nbuckets <= CSS_MAX_FACET_BUCKETS, "%s: nbuckets=%lld outside [1, %d]", fn,
                 (long long)nbuckets, CSS_MAX_FACET_BUCKETS);
-    CSS_REQUIRE(nq == 0 || (q_host && count_out && total_out && unbucketed_out), "css_index_facets: NULL buffer");
+    CSS_REQUIRE(nq == 0 || (q_host && count_out && total_out && unbucketed_out), "%s: NULL buffer", fn);
     if (nq == 0) return CSS_OK;   // (no query touches no device)
     HostCall hc(ix, nullptr, false);
+    const int32_t* bucket_col = nullptr;
+    if (slot >= 0) {   // (under the shared lock: the slot cannot change before the sweep has read it)
+        CSS_REQUIRE(ix->attrs[slot].type == CSS_ATTR_I32, "css_index_facets_attr: attribute slot %d %s", slot,
+                    ix->attrs[slot].type < 0 ? "was never set" : "is float32 (buckets are an int32 column)");
+        bucket_col = ix->attrs[slot].words.p;
+    }
     ix->last_facet_sweeps = ix->last_facet_lds_sweeps = 0;
     // the answer of an empty index, and the empty slots of any other
     const size_t n = (size_t)nq * (size_t)nbuckets;
@@ -5477,7 +5663,24 @@ int css_index_facets(css_index* ix, const float* q_host, int64_t nq, float radiu
     std::fill(unbucketed_out, unbucketed_out + nq, (int64_t)0);
     if (hc.rows.n == 0) return CSS_OK;
     return hc.wait_if_failed(facets_locked(ix, hc, q_host, allow_bits_host, nq, radius, normalize_q, buckets_host, nbuckets,
-                                           count_out, best_score_out, best_id_out, total_out, unbucketed_out));
+                                           count_out, best_score_out, best_id_out, total_out, unbucketed_out, bucket_col));
+}
+}  // namespace
+
+int css_index_facets(css_index* ix, const float* q_host, int64_t nq, float radius, int normalize_q,
+                     const uint32_t* allow_bits_host, const int32_t* buckets_host, int64_t nbuckets, int64_t* count_out,
+                     float* best_score_out, int64_t* best_id_out, int64_t* total_out, int64_t* unbucketed_out) {
+    return facets_call("css_index_facets", ix, q_host, nq, radius, normalize_q, allow_bits_host, buckets_host, -1, nbuckets, count_out,
+                       best_score_out, best_id_out, total_out, unbucketed_out);
+}
+
+int css_index_facets_attr(css_index* ix, const float* q_host, int64_t nq, float radius, int normalize_q,
+                          const uint32_t* allow_bits_host, int slot, int64_t nbuckets, int64_t* count_out,
+                          float* best_score_out, int64_t* best_id_out, int64_t* total_out, int64_t* unbucketed_out) {
+    CSS_REQUIRE(slot >= 0 && slot < CSS_MAX_ATTRS, "css_index_facets_attr: attribute slot %d outside [0, %d)", slot,
+                CSS_MAX_ATTRS);
+    return facets_call("css_index_facets_attr", ix, q_host, nq, radius, normalize_q, allow_bits_host, nullptr, slot, nbuckets, count_out,
+                       best_score_out, best_id_out, total_out, unbucketed_out);
 }
 
 int css_index_last_facet_sweeps(css_index* ix, int64_t* sweeps, int64_t* lds_sweeps) {

@@ -176,6 +176,138 @@ def facet_args(thresh, buckets, nbuckets, ntotal: int, what: str = "facets") -> 
     return thresh, b, nbuckets
 
 
+MAX_ATTRS = nat.MAX_ATTRS
+MAX_CLAUSES = nat.MAX_CLAUSES
+MAX_TABLE_BITS = nat.MAX_TABLE_BITS
+ATTR_I32, ATTR_F32 = nat.ATTR_I32, nat.ATTR_F32
+WHERE_OPS = nat.WHERE_OPS
+_WHERE_IN = WHERE_OPS.index("in")
+
+
+def attr_slot(slot, what: str = "set_attribute") -> int:
+    """An attribute slot number as int; anything but an integer in ``[0, MAX_ATTRS)`` raises ``ValueError``."""
+    if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)):
+        raise ValueError(f"{what}: the slot must be an integer, got {type(slot).__name__}")
+    if slot < 0 or slot >= MAX_ATTRS:
+        raise ValueError(f"{what}: attribute slot {int(slot)} outside [0, {MAX_ATTRS})")
+    return int(slot)
+
+
+def attr_values(values, what: str = "set_attribute") -> Tuple[np.ndarray, int]:
+    """Array-like of per-row attribute values -> ``(contiguous 1-D array, ATTR_I32 | ATTR_F32)``: an integer (or
+    boolean) dtype gives int32 and is range-checked, a floating dtype gives float32 (rounded; NaN and infinity are
+    values like any other).  Anything else (strings, objects, complex, more than one dimension) raises ``ValueError``."""
+    a = np.asarray(values)
+    if a.ndim != 1:
+        raise ValueError(f"{what}: values must be one-dimensional, got shape {a.shape}")
+    if a.dtype == np.bool_ or np.issubdtype(a.dtype, np.integer):
+        if a.size and (int(a.min()) < np.iinfo(np.int32).min or int(a.max()) > np.iinfo(np.int32).max):
+            raise ValueError(f"{what}: value beyond int32")
+        return np.ascontiguousarray(a, dtype=np.int32), ATTR_I32
+    if np.issubdtype(a.dtype, np.floating):
+        with np.errstate(over="ignore"):
+            return np.ascontiguousarray(a, dtype=np.float32), ATTR_F32
+    raise ValueError(f"{what}: values must be integers or real numbers, got dtype {a.dtype}")
+
+
+class WhereArgs(NamedTuple):
+    """What ``where_args`` returns: per clause ``(slot, op code, value bits as int32, table_off, table_bits)`` and the
+    table words of the call (uint32; empty without ``in`` clauses)."""
+    clauses: List[Tuple[int, int, int, int, int]]
+    tables: np.ndarray
+
+
+def where_args(clauses, type_of: Callable[[int], int], what: str = "where") -> WhereArgs:
+    """The argument rules of ``where``, stated once, and the packing of the ``in`` tables.  ``clauses`` is a sequence
+    of at most ``MAX_CLAUSES`` triples ``(slot, op, operand)`` with ``op`` one of ``WHERE_OPS``; ``type_of(slot)`` gives
+    the slot's type (``ATTR_I32``, ``ATTR_F32`` or ``-1`` for a slot that was never set).  On an int32 slot the operand
+    of a comparison is an integer that fits int32; on a float32 slot any real number, rounded to float32 (NaN and
+    infinity included).  ``in`` / ``not in`` exist on int32 slots only; their operand is an iterable of non-negative
+    integers below ``MAX_TABLE_BITS`` and becomes a bit table of ``max + 1`` bits (an empty iterable: no bits, nothing
+    is in).  Anything else raises ``ValueError``."""
+    try:
+        clauses = list(clauses)
+    except TypeError:
+        raise ValueError(f"{what}: clauses must be a sequence of (slot, op, operand)") from None
+    if len(clauses) > MAX_CLAUSES:
+        raise ValueError(f"{what}: {len(clauses)} clauses, at most {MAX_CLAUSES}")
+    out: List[Tuple[int, int, int, int, int]] = []
+    tables: List[np.ndarray] = []
+    words = 0
+    for c, cl in enumerate(clauses):
+        if not isinstance(cl, (tuple, list)) or len(cl) != 3:
+            raise ValueError(f"{what}: clause {c} is not (slot, op, operand)")
+        slot, op, operand = cl
+        slot = attr_slot(slot, f"{what}: clause {c}")
+        if not isinstance(op, str) or op not in WHERE_OPS:
+            raise ValueError(f"{what}: clause {c}: unknown op {op!r} (one of {', '.join(WHERE_OPS)})")
+        code = WHERE_OPS.index(op)
+        typ = int(type_of(slot))
+        if typ < 0:
+            raise ValueError(f"{what}: clause {c}: attribute slot {slot} was never set")
+        if code >= _WHERE_IN:
+            if typ != ATTR_I32:
+                raise ValueError(f"{what}: clause {c}: {op!r} on attribute slot {slot}, which holds float32 values")
+            try:
+                vals = np.asarray(list(operand))
+            except TypeError:
+                raise ValueError(f"{what}: clause {c}: the operand of {op!r} must be an iterable of integers") from None
+            if vals.size and (vals.dtype == np.bool_ or not np.issubdtype(vals.dtype, np.integer)):
+                raise ValueError(f"{what}: clause {c}: the operand of {op!r} must hold integers, got dtype {vals.dtype}")
+            vals = vals.reshape(-1)
+            if vals.size and (int(vals.min()) < 0 or int(vals.max()) >= MAX_TABLE_BITS):
+                raise ValueError(f"{what}: clause {c}: the operand of {op!r} must lie in [0, {MAX_TABLE_BITS})")
+            nbits = int(vals.max()) + 1 if vals.size else 0
+            member = np.zeros(nbits, dtype=np.bool_)
+            member[vals.astype(np.int64)] = True
+            tab = pack_allow_bits(member, nbits)
+            out.append((slot, code, 0, words, nbits))
+            tables.append(tab)
+            words += tab.shape[0]
+            continue
+        if isinstance(operand, (bool, np.bool_)):
+            operand = int(operand)
+        if typ == ATTR_I32:
+            if not isinstance(operand, (int, np.integer)):
+                raise ValueError(f"{what}: clause {c}: attribute slot {slot} holds int32 values; the operand of {op!r} must "
+                                 f"be an integer, got {type(operand).__name__}")
+            if operand < np.iinfo(np.int32).min or operand > np.iinfo(np.int32).max:
+                raise ValueError(f"{what}: clause {c}: operand {int(operand)} beyond int32")
+            out.append((slot, code, int(operand), 0, 0))
+        else:
+            if not isinstance(operand, (int, float, np.integer, np.floating)):
+                raise ValueError(f"{what}: clause {c}: the operand of {op!r} must be a real number, got "
+                                 f"{type(operand).__name__}")
+            with np.errstate(over="ignore"):
+                bits = int(np.asarray(operand, dtype=np.float32).reshape(1).view(np.int32)[0])
+            out.append((slot, code, bits, 0, 0))
+    tabs = np.concatenate(tables).astype("<u4") if tables else np.zeros(0, dtype="<u4")
+    return WhereArgs(out, np.ascontiguousarray(tabs))
+
+
+def where_numpy(columns, clauses, ntotal: int, allow=None) -> np.ndarray:
+    """What ``where`` computes, stated in numpy (the tests compare the device with this): the boolean mask of the rows
+    that pass every clause and ``allow``.  ``columns`` maps a slot to its int32 or float32 array of ``ntotal`` values;
+    the comparisons are numpy's own on those dtypes (a NaN fails everything but ``!=``, ``-0.0 == 0.0``); a value is
+    ``in`` when it equals one of the operand's members -- those are non-negative, so a negative value never is."""
+    mask = np.ones(ntotal, dtype=np.bool_) if allow is None else np.array(allow, dtype=np.bool_, copy=True)
+    typed = where_args(clauses, lambda s: ATTR_F32 if np.asarray(columns[s]).dtype == np.float32 else ATTR_I32, "where_numpy")
+    for (slot, op, operand), (_, code, bits, _, _) in zip(clauses, typed.clauses):
+        col = np.asarray(columns[slot])
+        if col.shape != (ntotal,) or col.dtype not in (np.int32, np.float32):
+            raise ValueError(f"where_numpy: column {slot} must be an int32 or float32 array of {ntotal} entries")
+        if code >= _WHERE_IN:
+            members = np.asarray(list(operand), dtype=np.int64).reshape(-1)
+            ok = np.isin(col.astype(np.int64), members)
+            ok = ok if code == _WHERE_IN else ~ok
+        else:
+            x = np.array([bits], dtype=np.int32).view(col.dtype)[0]   # the operand in the column's own dtype
+            with np.errstate(invalid="ignore"):
+                ok = (col == x, col != x, col < x, col <= x, col > x, col >= x)[code]
+        mask &= ok
+    return mask
+
+
 MAX_PRIOR_K = nat.MAX_PRIOR_K
 
 
@@ -842,7 +974,7 @@ class IndexFlat:
         return lims, D, I
 
     def facets(self, q, thresh: float, buckets=None, nbuckets: Optional[int] = None, normalize: bool = False,
-               allow=None) -> FacetCounts:
+               allow=None, by_attribute: Optional[int] = None) -> FacetCounts:
         """Where the matches lie (``css_index_facets``): for every query the number of rows with ``score > thresh``
         (inner product) or squared distance ``< thresh`` (L2) -- strict, the hits of ``range_search`` -- in each of
         ``nbuckets`` buckets, and the best such row per bucket (best score, ties to the smallest id), as a
@@ -850,15 +982,31 @@ class IndexFlat:
         like ``allow``, uploaded for this call only; ``None`` means the ``set_groups`` labels (nothing is uploaded) and
         ``nbuckets`` is then required.  ``nbuckets=None`` with ``buckets`` given means ``max(buckets) + 1``.  A hit whose
         bucket is negative or ``>= nbuckets`` counts in ``unbucketed`` only.  Counts are integers and scores come from
-        the exact fp32 sweep of ``range_search``: the result is the same bytes on every call."""
+        the exact fp32 sweep of ``range_search``: the result is the same bytes on every call.  ``by_attribute=slot``
+        takes the int32 attribute column ``slot`` (``set_attribute``) as the buckets -- what ``buckets=get_attribute(slot)``
+        answers, without the upload; ``nbuckets`` is then required and ``buckets`` must be ``None``."""
         a = _as_f32_2d(q, self.d, "facets")
         nq = a.shape[0]
+        if by_attribute is not None:
+            slot = attr_slot(by_attribute, "facets")
+            if buckets is not None:
+                raise ValueError("facets: give buckets or by_attribute, not both")
+            if nbuckets is None:
+                raise ValueError("facets: nbuckets is required with by_attribute")
+            typ = self.attribute_type(slot)
+            if typ != ATTR_I32:
+                raise ValueError(f"facets: attribute slot {slot} " + ("was never set" if typ < 0 else "holds float32 values"))
         thresh, b, nb = facet_args(thresh, buckets, nbuckets, self.ntotal)
         bits, bits_ptr = self._allow_bits(allow)
         pad = -np.finfo(np.float32).max if self.metric_type == METRIC_INNER_PRODUCT else np.finfo(np.float32).max
         out = FacetCounts(np.zeros((nq, nb), dtype=np.int64), np.full((nq, nb), pad, dtype=np.float32),
                           np.full((nq, nb), -1, dtype=np.int64), np.zeros(nq, dtype=np.int64), np.zeros(nq, dtype=np.int64))
-        if nq:
+        if nq and by_attribute is not None:
+            nat.check(nat.lib().css_index_facets_attr(self._handle(), a.ctypes.data, nq, thresh, 1 if normalize else 0,
+                                                      bits_ptr, slot, nb, out.counts.ctypes.data,
+                                                      out.best_score.ctypes.data, out.best_id.ctypes.data,
+                                                      out.total.ctypes.data, out.unbucketed.ctypes.data))
+        elif nq:
             nat.check(nat.lib().css_index_facets(self._handle(), a.ctypes.data, nq, thresh, 1 if normalize else 0, bits_ptr,
                                                  None if b is None else b.ctypes.data, nb, out.counts.ctypes.data,
                                                  out.best_score.ctypes.data, out.best_id.ctypes.data, out.total.ctypes.data,
@@ -899,6 +1047,71 @@ class IndexFlat:
         if n:
             nat.check(getattr(nat.lib(), "css_index_" + what)(self._handle(), row0, n, out.ctypes.data))
         return out
+
+    # -- attribute columns and filters on the device ---------------------------
+    def set_attribute(self, slot: int, values, row0: int = 0) -> None:
+        """Values of attribute ``slot`` (``0 <= slot < MAX_ATTRS``) for rows ``[row0, row0 + len(values))`` in LOCAL row
+        numbering: an integer (or boolean) array gives an int32 column and is range-checked, a floating array a float32
+        column; the first set types the slot and a later set of the other kind raises.  Rows never given a value, and
+        rows added later, hold ``-1`` / NaN.  The columns follow the rows through growth, ``remove_ids`` (compacted with
+        them) and ``reset`` (values and types forgotten)."""
+        slot = attr_slot(slot)
+        a, typ = attr_values(values)
+        row0, n = self._row_range("set_attribute", row0, a.shape[0])
+        if n:
+            nat.check(nat.lib().css_index_set_attr(self._handle(), slot, typ, row0, n, a.ctypes.data))
+
+    def get_attribute(self, slot: int, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """The values of attribute ``slot`` for rows ``[row0, row0 + n)`` (default: to the end), int32 or float32 by the
+        slot's type; a slot that was never set answers int32 ``-1``."""
+        slot = attr_slot(slot, "get_attribute")
+        row0, n = self._row_range("get_attribute", row0, n)
+        out = np.empty(n, dtype=np.float32 if self.attribute_type(slot) == ATTR_F32 else np.int32)
+        if n:
+            nat.check(nat.lib().css_index_get_attr(self._handle(), slot, row0, n, out.ctypes.data))
+        return out
+
+    def attribute_type(self, slot: int) -> int:
+        """``ATTR_I32``, ``ATTR_F32``, or ``-1`` for a slot that was never set."""
+        t = ctypes.c_int(-1)
+        nat.check(nat.lib().css_index_attr_type(self._handle(), attr_slot(slot, "attribute_type"), ctypes.byref(t)))
+        return int(t.value)
+
+    def drop_attribute(self, slot: int) -> None:
+        """Free attribute ``slot`` and forget its type."""
+        nat.check(nat.lib().css_index_drop_attr(self._handle(), attr_slot(slot, "drop_attribute")))
+
+    def where_bits(self, clauses, allow=None, out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, int]:
+        """``where`` in the form the library answers: ``(uint32 bitmap of ceil(ntotal / 32) words, number of set bits)``.
+        ``out`` (optional) is a contiguous uint32 array of exactly that many words to write into."""
+        args = where_args(clauses, self.attribute_type)
+        ntotal = self.ntotal
+        words = (ntotal + 31) // 32
+        if out is None:
+            out = np.zeros(words, dtype="<u4")
+        elif out.dtype != np.dtype("<u4") or out.ndim != 1 or out.shape[0] != words or not out.flags.c_contiguous:
+            raise ValueError(f"where: out must be a contiguous uint32 array of {words} words")
+        cl = (nat.Clause * max(len(args.clauses), 1))()
+        for c, (slot, code, value, off, nbits) in enumerate(args.clauses):
+            cl[c] = nat.Clause(slot, code, value, 0, off, nbits)
+        bits, bits_ptr = self._allow_bits(allow)
+        count = ctypes.c_int64(0)
+        nat.check(nat.lib().css_index_where(self._handle(), cl, len(args.clauses),
+                                            args.tables.ctypes.data if args.tables.size else None, args.tables.shape[0],
+                                            bits_ptr, out.ctypes.data if words else None, ctypes.byref(count)))
+        return out, int(count.value)
+
+    def where(self, clauses, allow=None, return_count: bool = False):
+        """The rows that pass a filter, evaluated on the device (``css_index_where``): the boolean mask of ``ntotal``
+        entries that every search method accepts as ``allow``.  ``clauses`` is a sequence of at most ``MAX_CLAUSES``
+        triples ``(slot, op, operand)``, all of which must hold (AND); ``op`` is one of ``== != < <= > >= in "not in"``,
+        compared as numpy compares int32 / float32 arrays (``where_numpy``); the operand of ``in`` / ``not in`` (int32
+        slots only) is an iterable of non-negative integers.  ``allow`` is ANDed in; no clause answers ``allow`` (or
+        every row).  ``return_count=True`` returns ``(mask, number of rows that pass)``."""
+        bits, count = self.where_bits(clauses, allow)
+        ntotal = self.ntotal
+        mask = np.unpackbits(bits.view(np.uint8), bitorder="little")[:ntotal].astype(np.bool_)
+        return (mask, count) if return_count else mask
 
     # -- group labels and grouped search ------------------------------------
     def set_groups(self, labels, row0: int = 0) -> None:

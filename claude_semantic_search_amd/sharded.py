@@ -74,6 +74,7 @@ class ShardedFlatIndex:
         self._dead: Optional[np.ndarray] = None          # tombstones in global numbering (replicated; mark_deleted)
         self._terms_global = 0                           # leading GLOBAL rows that have term lists (replicated; set_terms)
         self._sparse_global = 0                          # ... that have sparse vectors (replicated; set_sparse)
+        self._attr_types: dict = {}                      # slot -> type of the attribute columns (replicated; set_attribute)
 
     # -- building ----------------------------------------------------------
     def _append_segment(self, n_local: int, global_row0: int) -> None:
@@ -397,7 +398,8 @@ class ShardedFlatIndex:
         return out_lims, np.ascontiguousarray(scores[order]), np.ascontiguousarray(ids[order])
 
     # -- facet counts ------------------------------------------------------------------------------------------
-    def facets(self, q, thresh: float, buckets=None, nbuckets: Optional[int] = None, normalize: bool = False, allow=None):
+    def facets(self, q, thresh: float, buckets=None, nbuckets: Optional[int] = None, normalize: bool = False, allow=None,
+               by_attribute: Optional[int] = None):
         """``IndexFlat.facets`` over the shards (collective: every rank passes the same arguments): a ``FacetCounts``
         with global ids on every rank.  ``buckets`` and ``allow`` are in GLOBAL numbering and are cut per shard through
         the segment table, as ``set_groups`` and ``_local_allow`` do (``buckets=None``: the labels ``set_groups``
@@ -405,13 +407,26 @@ class ShardedFlatIndex:
         ``counts | total | unbucketed`` (int64) and ONE all-gather moves every rank's ``(best_score, best global id)``
         per entry, merged by best score, then smaller global id.  A row's score is its own fp32 chain wherever it lies
         and counts are integers, so the result equals the unsharded one byte for byte.  With one rank there is no
-        exchange."""
-        from .flat_index import FacetCounts, facet_args
+        exchange.  ``by_attribute=slot``: the buckets are the int32 attribute column ``set_attribute`` stored on every
+        shard (``nbuckets`` required, ``buckets`` must be ``None``)."""
+        from .flat_index import ATTR_I32, FacetCounts, attr_slot, facet_args
 
         qa = self._queries(q)
+        more = {}
+        if by_attribute is not None:
+            slot = attr_slot(by_attribute, "facets")
+            if buckets is not None:
+                raise ValueError("facets: give buckets or by_attribute, not both")
+            if nbuckets is None:
+                raise ValueError("facets: nbuckets is required with by_attribute")
+            typ = self._attr_types.get(slot, -1)
+            if typ != ATTR_I32:
+                raise ValueError(f"facets: attribute slot {slot} " + ("was never set" if typ < 0 else "holds float32 values"))
+            if self.shard_sizes[self.rank]:   # (a shard without rows has no column, and no hit either)
+                more["by_attribute"] = slot
         thresh, b, nb = facet_args(thresh, buckets, nbuckets, self.ntotal_global)
         loc = self.local.facets(qa, thresh, buckets=None if b is None else self.local_rows_of(b), nbuckets=nb,
-                                normalize=normalize, allow=self._local_allow(allow))
+                                normalize=normalize, allow=self._local_allow(allow), **more)
         counts, total, unb = (np.ascontiguousarray(a, dtype=np.int64) for a in (loc.counts, loc.total, loc.unbucketed))
         S = np.ascontiguousarray(loc.best_score, dtype=np.float32)
         I = np.ascontiguousarray(self._to_global_np(np.asarray(loc.best_id, dtype=np.int64)))
@@ -431,6 +446,61 @@ class ShardedFlatIndex:
                            np.ascontiguousarray(np.take_along_axis(Sg, first, axis=1).reshape(nq, nb)),
                            np.ascontiguousarray(np.take_along_axis(Ig, first, axis=1).reshape(nq, nb)),
                            np.ascontiguousarray(sums[n:n + nq]), np.ascontiguousarray(sums[n + nq:]))
+
+    # -- attribute columns and filters -------------------------------------------------------------------------
+    def set_attribute(self, slot: int, global_values, row0: int = 0) -> None:
+        """``IndexFlat.set_attribute`` in GLOBAL numbering (collective: every rank passes the same values): values of the
+        global rows ``[row0, row0 + len(global_values))``; every rank writes the part its shard holds, through the
+        segment table like ``set_groups``.  The slot has ONE type on all shards: a shard none of whose rows were in the
+        range still gets the (all-default) column, so that a later ``where`` finds the slot on every rank."""
+        from .flat_index import ATTR_F32, attr_slot, attr_values
+
+        slot = attr_slot(slot)
+        v, typ = attr_values(global_values)
+        row0 = int(row0)
+        self._check_rows("set_attribute", row0, v.shape[0])
+        have = self._attr_types.get(slot, -1)
+        if have >= 0 and have != typ:
+            raise ValueError(f"set_attribute: attribute slot {slot} holds {'float32' if have == ATTR_F32 else 'int32'} values")
+        if v.shape[0] == 0:
+            return
+        self._attr_types[slot] = typ
+        for l0, g0, n in self._overlaps(row0, v.shape[0]):
+            self.local.set_attribute(slot, v[g0 - row0:g0 - row0 + n], row0=l0)
+        if self.shard_sizes[self.rank] and self.local.attribute_type(slot) < 0:
+            self.local.set_attribute(slot, np.full(1, np.nan, np.float32) if typ == ATTR_F32 else np.full(1, -1, np.int32))
+
+    def get_attribute(self, slot: int) -> np.ndarray:
+        """This shard's values of attribute ``slot`` in LOCAL row order (``local_rows_of`` of the global column)."""
+        return self.local.get_attribute(slot)
+
+    def attribute_type(self, slot: int) -> int:
+        from .flat_index import attr_slot
+
+        return self._attr_types.get(attr_slot(slot, "attribute_type"), -1)
+
+    def drop_attribute(self, slot: int) -> None:
+        from .flat_index import attr_slot
+
+        if self._attr_types.pop(attr_slot(slot, "drop_attribute"), None) is not None:
+            self.local.drop_attribute(slot)
+
+    def where(self, clauses, allow=None, return_count: bool = False):
+        """``IndexFlat.where`` over the shards (collective with ``return_count``): the boolean mask over THIS shard's
+        rows in local order -- ``local_rows_of`` of the mask one index holding all rows would answer; ``allow`` is in
+        GLOBAL numbering and the tombstones are left out, as in every search.  ``return_count=True`` returns
+        ``(local mask, number of rows that pass on ALL shards)``: ONE sum all-reduce of an int64."""
+        from .flat_index import where_args
+
+        where_args(clauses, self.attribute_type)   # the same refusal on every rank, before any shard is asked
+        la = self._local_allow(allow)
+        if self.shard_sizes[self.rank]:
+            mask, count = self.local.where(clauses, allow=la, return_count=True)
+        else:
+            mask, count = np.zeros(0, dtype=np.bool_), 0
+        if not return_count:
+            return mask
+        return mask, int(self._sum_over_ranks(np.array([count], dtype=np.int64))[0])
 
     # -- grouped search ----------------------------------------------------------------------------------------
     def set_groups(self, global_labels, row0: int = 0) -> None:
@@ -951,9 +1021,24 @@ class ShardedIndexFacade:
     def significant_terms(self, allow=None, m: int = 20, min_count: int = 2, background=None):
         return self.sh.significant_terms(allow=allow, m=m, min_count=min_count, background=background)
 
-    def facets(self, q, thresh: float, buckets=None, nbuckets=None, normalize: bool = False, allow=None):
+    def facets(self, q, thresh: float, buckets=None, nbuckets=None, normalize: bool = False, allow=None, by_attribute=None):
         return self.sh.facets(np.asarray(q, dtype=np.float32), float(thresh), buckets=buckets, nbuckets=nbuckets,
-                              normalize=normalize, allow=allow)
+                              normalize=normalize, allow=allow, by_attribute=by_attribute)
+
+    def set_attribute(self, slot: int, values, row0: int = 0) -> None:
+        self.sh.set_attribute(slot, values, row0=row0)
+
+    def get_attribute(self, slot: int) -> np.ndarray:
+        return self.sh.get_attribute(slot)
+
+    def attribute_type(self, slot: int) -> int:
+        return self.sh.attribute_type(slot)
+
+    def drop_attribute(self, slot: int) -> None:
+        self.sh.drop_attribute(slot)
+
+    def where(self, clauses, allow=None, return_count: bool = False):
+        return self.sh.where(clauses, allow=allow, return_count=return_count)
 
     def search_hybrid(self, q, terms, weights, k: int, alpha: float, k1: float = 1.2, b: float = 0.75,
                       avgdl: Optional[float] = None, normalize: bool = False, allow=None):

@@ -40,6 +40,7 @@ import numpy as np
 
 from . import flat_index as fi
 from .chunk import Chunk
+from .filters import ATTR_COLUMNS, DICT_COLUMNS, FLAG_COLUMNS, AttrCatalog, compile_filters
 from .gpu_utils import GPUCapability, assess_gpu_capability, log_gpu_status
 
 # bytes in front of the row data of faiss' IndexFlat file: fourcc, d, ntotal, 2 dummies, is_trained, metric, n_floats
@@ -71,6 +72,11 @@ class StorageConfig:
     # with the same arguments; search() is then the local masked search of every shard + ONE all-gather + merge.
     # CSS_STORAGE_SHARDED=1 switches it on for an unmodified caller (the reference's CLI under torch.distributed.run).
     sharded: bool = False
+    # extension: evaluate filters on the GPU.  The filterable chunk columns are kept as attribute columns of the index
+    # (``IndexFlat.set_attribute``) and a filter dict is compiled into ``IndexFlat.where`` clauses (``filters.py``); a
+    # filter that cannot be compiled with exactly the host's semantics falls back to the host loop.  It changes where
+    # the allow mask of a search is computed, never what a search returns.  Off by default.
+    attribute_filters: bool = False
 
 
 @dataclass
@@ -345,6 +351,10 @@ class HybridStorage:
         # index_sparse / search_sparse: the rows that carry a sparse vector, the model that made the vectors, and what
         # of them the file beside the index holds as (model, rows with a vector, rows of the index)
         self._sparse = _Synced()
+        # attribute_filters: the chunk columns pushed into attribute slots, and what their codes mean
+        self._attrs = _Synced()
+        self._catalog = AttrCatalog()
+        self._live_cache: Optional[Tuple[Any, np.ndarray]] = None
         self._sparse_model: Optional[str] = None
         self._sparse_saved: Optional[Tuple[Optional[str], int, int]] = None
         # search_sessions: dense group labels per session_id (order of first appearance by faiss_id)
@@ -547,8 +557,63 @@ class HybridStorage:
         masked = filters if pushdown and filters else {}
         tombstones = len(self.faiss_id_to_chunk_id) < ntotal
         if masked or (tombstones and (pushdown or tombstones_always)):
-            return self._allow_mask(masked, ntotal)
+            return self._mask_of(masked, ntotal)
         return None
+
+    # ------------------------------------------------- attribute filters (StorageConfig.attribute_filters, filters.py)
+    def _sync_attributes(self, ntotal: int) -> None:
+        """Bring the index's attribute columns up to date with SQLite, by the rule of ``_sync_session_labels``: only
+        the tail ``[synced, ntotal)`` is read and pushed after adds (a timestamp that sorts in front of a stored one
+        moves earlier ranks, and that column is pushed whole); everything when the index object was replaced (load,
+        restore, ``clear_all_data``, a rebuild) or compacted."""
+        if self._attrs.index is not self.faiss_index:
+            self._catalog = AttrCatalog()
+        lo = self._attrs.rows_of(self.faiss_index)
+        if lo >= ntotal:
+            return
+        chunks: List[Optional[Dict[str, Any]]] = [None] * (ntotal - lo)
+        cols = ", ".join(ATTR_COLUMNS)
+        for row in self.db.cursor().execute(f"SELECT id, faiss_id, {cols} FROM chunks WHERE faiss_id >= ? AND faiss_id < ?",
+                                            (lo, ntotal)):
+            if self.faiss_id_to_chunk_id.get(row["faiss_id"]) == row["id"]:
+                chunks[row["faiss_id"] - lo] = {c: row[c] for c in ATTR_COLUMNS}
+        try:
+            first = self._catalog.extend(chunks)
+            for col, row0 in first.items():
+                self.faiss_index.set_attribute(self._catalog.slot(col), self._catalog.codes[col][row0:ntotal], row0=row0)
+        except BaseException:
+            # the catalog may be ahead of the columns: forget both, the next sync pushes everything again
+            self._attrs, self._catalog = _Synced(), AttrCatalog()
+            raise
+        self._attrs.rows = ntotal
+
+    def _attribute_path(self) -> bool:
+        """Filters go to the GPU: the option is on and the index answers ``where`` with a mask over ALL its rows (the
+        sharded facade answers each rank's local part, which no search of the facade takes: it stays on the host loop)."""
+        return bool(self.config.attribute_filters) and not self._sharded() and all(
+            hasattr(self.faiss_index, m) for m in ("where", "set_attribute"))
+
+    def _live_mask(self, ntotal: int) -> np.ndarray:
+        """The rows that hold a live chunk (the tombstone part of ``_allow_mask``), cached under its stamp."""
+        stamp = (self._mutations, len(self.faiss_id_to_chunk_id), ntotal, self.total_chunks)
+        if self._live_cache is None or self._live_cache[0] != stamp:
+            live = np.zeros(ntotal, dtype=bool)
+            ids = np.fromiter((fid for fid, cid in self.faiss_id_to_chunk_id.items()
+                               if fid < ntotal and self.chunk_id_to_faiss_id.get(cid) == fid), dtype=np.int64)
+            live[ids] = True
+            self._live_cache = (stamp, live)
+        return self._live_cache[1]
+
+    def _mask_of(self, filters: Dict[str, Any], ntotal: int) -> np.ndarray:
+        """``_allow_mask(filters, ntotal)``, computed on the GPU where ``attribute_filters`` is on, the index has
+        ``where`` and ``compile_filters`` takes the filter; by the host loop otherwise."""
+        if self._attribute_path():
+            self._sync_attributes(ntotal)
+            clauses = compile_filters(filters, self._catalog)
+            if clauses is not None:
+                live = self._live_mask(ntotal)
+                return self.faiss_index.where(clauses, allow=None if bool(live.all()) else live)
+        return self._allow_mask(filters, ntotal)
 
     def _require(self, what: str, *methods: str) -> None:
         """The capability check of a search variant, in front of the lock (no index at all: the search gives ``[]``)."""
@@ -648,7 +713,7 @@ class HybridStorage:
             skip = self._NO_SESSION if same_session or session is None else session
             allow = None
             if self.config.filter_pushdown:
-                allow = self._allow_mask(filters or {}, ntotal)
+                allow = self._mask_of(filters or {}, ntotal)
                 if skip is not self._NO_SESSION:
                     allow = allow.copy()   # (the cached mask stays as it is)
                     mates = self.db.cursor().execute("SELECT faiss_id FROM chunks WHERE session_id = ? AND faiss_id IS NOT NULL",
@@ -849,7 +914,7 @@ class HybridStorage:
             cfg, ntotal, _ = frame
             if not hasattr(self.faiss_index, "kmeans"):
                 raise NotImplementedError(f"{type(self.faiss_index).__name__} has no k-means (kmeans)")
-            allow = self._allow_mask(filters or {}, ntotal)
+            allow = self._mask_of(filters or {}, ntotal)
             live = int(allow.sum())
             nc = min(int(n_topics), live, fi.MAX_CENTROIDS)
             if nc == 0:
@@ -895,7 +960,7 @@ class HybridStorage:
             _, ntotal, _ = frame
             if not (hasattr(self.faiss_index, "pca") and hasattr(self.faiss_index, "transform")):
                 raise NotImplementedError(f"{type(self.faiss_index).__name__} has no PCA (pca / transform)")
-            allow = self._allow_mask(filters or {}, ntotal)
+            allow = self._mask_of(filters or {}, ntotal)
             rows = np.flatnonzero(allow)
             if rows.size == 0:
                 return []
@@ -964,8 +1029,8 @@ class HybridStorage:
                 return []
             _, ntotal, _ = frame
             self._sync_terms(ntotal)
-            live = self._allow_mask({}, ntotal)
-            sel = self._allow_mask(filters or {}, ntotal)
+            live = self._mask_of({}, ntotal)
+            sel = self._mask_of(filters or {}, ntotal)
             if chunk_ids is not None:
                 named = np.zeros(ntotal, dtype=bool)
                 for cid in chunk_ids:
@@ -1309,17 +1374,28 @@ class HybridStorage:
             _, ntotal, q = frame
             similarity = bool(self.config.normalize_embeddings)
             radius = strict_radius(thr, similarity)
-            if by == "session_id":
+            by_attribute = None
+            if by in DICT_COLUMNS + FLAG_COLUMNS and self._attribute_path():
+                self._sync_attributes(ntotal)
+                # the codes ARE dense bucket ids, NULL = -1 = unbucketed.  The dictionary keeps the values of deleted
+                # chunks until the next compaction: where it is larger than the index takes, the upload path below
+                # decides over the live values alone, as with the option off
+                if not self._catalog.mixed[by] and len(self._catalog.values(by)) <= fi.MAX_FACET_BUCKETS:
+                    by_attribute = self._catalog.slot(by)
+            if by_attribute is not None:
+                ids, values = None, self._catalog.values(by)
+            elif by == "session_id":
                 self._sync_session_labels(ntotal)
                 ids, values = None, list(self._session_labels)   # (label = position: dense in order of first appearance)
             else:
                 ids, values = self._facet_buckets(by, ntotal)
             if len(values) > fi.MAX_FACET_BUCKETS:
                 raise ValueError(f"facets: by={by!r} has {len(values)} distinct values, more than {fi.MAX_FACET_BUCKETS}")
-            allow = self._allow_mask(filters or {}, ntotal)
+            allow = self._mask_of(filters or {}, ntotal)
+            more = {} if by_attribute is None else {"by_attribute": by_attribute}
             res = self.faiss_index.facets(q, float(radius), buckets=ids, nbuckets=max(len(values), 1),
                                           normalize=self.config.normalize_embeddings,
-                                          allow=None if bool(allow.all()) else allow)
+                                          allow=None if bool(allow.all()) else allow, **more)
             out = []
             for b in np.flatnonzero(res.counts[0] > 0).tolist():
                 chunk_id = self.faiss_id_to_chunk_id.get(int(res.best_id[0, b]))
@@ -1702,6 +1778,7 @@ class HybridStorage:
             self._mutations += 1
             # (the rows were renumbered: search_sessions, search_recent and search_hybrid push every row again)
             self._labels, self._priors, self._terms = _Synced(), _Synced(), _Synced()
+            self._attrs = _Synced()
             # ... but no text is encoded again: an index compacted in place has compacted its sparse vectors with the rows
             if in_place and self._sparse.index is old and hasattr(old, "sparse_rows"):
                 self._sparse.rows = int(old.sparse_rows)

@@ -14,6 +14,7 @@
  *   faiss_index.search(q, k) -> (D, I)       src/storage.py:436      -> css_index_search
  *   faiss_index.range_search(q, r)           (not called by the reference) -> css_index_range_search
  *   (no faiss call: facet counts per query)  (not called by the reference) -> css_index_facets
+ *   _matches_filters(chunk, filters) per row src/storage.py:508-543  -> css_index_set_attr + css_index_where
  *   faiss.write_index / read_index payload   src/storage.py:306,879  -> css_index_export / css_index_add
  *   faiss.index_cpu_to_gpu / get_num_gpus    src/storage.py:283, src/gpu_utils.py:117-118
  *                                                                    -> css_device_count / css_device_info
@@ -686,6 +687,66 @@ int css_index_facets(css_index* ix, const float* q_host, int64_t nq, float radiu
                      float* best_score_out, int64_t* best_id_out, int64_t* total_out, int64_t* unbucketed_out);
 int css_index_last_facet_sweeps(css_index* ix, int64_t* sweeps, int64_t* lds_sweeps);
 int css_index_set_facet_lds_entries(css_index* ix, int64_t entries);
+
+/* Attribute columns and filters on the device (Qdrant payload indexes, Milvus scalar filtering, Vespa attributes,
+ * Elasticsearch filter context).  The reference filters AFTER the search, one chunk at a time in Python
+ * (_matches_filters, src/storage.py:508-543: project_name, has_code, session_id, a timestamp range); every search
+ * here takes an allow bitmap instead, and these calls produce that bitmap from values kept beside the rows.
+ *  - Columns.  CSS_MAX_ATTRS numbered slots, each one 4-byte value per row in LOCAL row numbering, typed
+ *    CSS_ATTR_I32 or CSS_ATTR_F32 by its first css_index_set_attr with n > 0; a later set with the other type is
+ *    CSS_ERR_INVALID and names the slot.  A slot that was never set holds no memory.  Rows never given a value, and rows
+ *    appended after a set, hold the default: every byte 0xFF, i.e. -1 (int32) / a NaN (float32).  The columns follow
+ *    the rows like the group labels: kept through capacity growth, compacted by css_index_remove_rows with the same
+ *    keep bits, forgotten (values AND types) by css_index_reset.  css_index_get_attr reads rows [row0, row0 + n) back
+ *    as stored (an unset slot answers the default bytes); css_index_attr_type gives the type, -1 for an unset slot;
+ *    css_index_drop_attr frees a slot and forgets its type (an unset slot: nothing happens).  Locking and the wait on
+ *    pending asynchronous adds are those of css_index_set_groups / css_index_get_groups.  Values are stored as given:
+ *    no range or NaN check.
+ *  - css_index_where.  bits_out_host [ceil(ntotal / 32)] receives bit r & 31 of word r >> 5 = 1 exactly when row r
+ *    passes ALL nclauses clauses and, with allow_bits_host given, its allow bit is set; the bits of the last word past
+ *    ntotal are zero and nothing past the last word is written.  *count_out is the number of set bits.  nclauses == 0
+ *    answers the allow bits (or all rows) cut to ntotal.  An empty index writes nothing and counts 0.
+ *  - A css_clause compares the value of row r in `slot` with the operand: EQ NE LT LE GT GE compare with `value`
+ *    (an int32, or the BITS of a float32 for a float slot) exactly as numpy compares int32 / float32 arrays: a NaN, stored
+ *    or as operand, fails every op except NE; -0.0 == 0.0; denormals compare as themselves (the device compares
+ *    ordered integer keys, so the denormal mode of the build does not matter).  IN / NOT_IN are for int32 slots only:
+ *    the operand is a bit table over [0, table_bits), table_bits <= CSS_MAX_TABLE_BITS, that starts at WORD table_off of
+ *    tables_host [table_words]; bit v & 31 of word table_off + (v >> 5) says whether v is in.  A stored value that is
+ *    negative or >= table_bits is "not in" (so the default -1 passes NOT_IN and fails IN).  Tables of several clauses may
+ *    overlap.  All tables of a call go to LDS when table_words <= 8192 (32 KiB) and are read from global memory (L2)
+ *    otherwise; the answer does not depend on it.
+ *  - CSS_ERR_INVALID, with nothing enqueued and nothing written: nclauses outside [0, CSS_MAX_CLAUSES]; a slot outside
+ *    [0, CSS_MAX_ATTRS); a clause on a slot that was never set (the message names the slot); an unknown op; IN / NOT_IN
+ *    on a float slot; a table that does not lie inside tables_host or has more than CSS_MAX_TABLE_BITS bits.
+ *  - The count is a sum of integers (one atomic add per block), so the answer is the same bytes on every call.  The
+ *    call runs on the index's own stream inside the frame of the host searches (allow bitmap up, result through
+ *    pinned staging when it is small); rows appended on other streams have landed before it reads.  There is no _dev
+ *    form: the bitmap goes back to the host and into the allow argument of any search.
+ *  - css_index_facets_attr is css_index_facets with the int32 attribute column `slot` as the bucket column: nothing
+ *    is uploaded.  A float or unset slot is CSS_ERR_INVALID. */
+#define CSS_MAX_ATTRS 16
+#define CSS_MAX_CLAUSES 16
+#define CSS_MAX_TABLE_BITS (1 << 27)
+enum { CSS_ATTR_I32 = 0, CSS_ATTR_F32 = 1 };
+enum { CSS_WHERE_EQ = 0, CSS_WHERE_NE = 1, CSS_WHERE_LT = 2, CSS_WHERE_LE = 3, CSS_WHERE_GT = 4, CSS_WHERE_GE = 5,
+       CSS_WHERE_IN = 6, CSS_WHERE_NOT_IN = 7 };
+typedef struct css_clause {
+    int32_t slot;
+    int32_t op;
+    int32_t value;        /* EQ .. GE: the int32 operand, or the bits of the float32 operand */
+    int32_t reserved;     /* 0 */
+    int64_t table_off;    /* IN / NOT_IN: first word of the table in tables_host */
+    int64_t table_bits;   /* IN / NOT_IN: bits of the table */
+} css_clause;
+int css_index_set_attr(css_index* ix, int slot, int type, int64_t row0, int64_t n, const void* values_host);
+int css_index_get_attr(css_index* ix, int slot, int64_t row0, int64_t n, void* out_host);
+int css_index_attr_type(css_index* ix, int slot, int* type);
+int css_index_drop_attr(css_index* ix, int slot);
+int css_index_where(css_index* ix, const css_clause* clauses, int nclauses, const uint32_t* tables_host,
+                    int64_t table_words, const uint32_t* allow_bits_host, uint32_t* bits_out_host, int64_t* count_out);
+int css_index_facets_attr(css_index* ix, const float* q_host, int64_t nq, float radius, int normalize_q,
+                          const uint32_t* allow_bits_host, int slot, int64_t nbuckets, int64_t* count_out,
+                          float* best_score_out, int64_t* best_id_out, int64_t* total_out, int64_t* unbucketed_out);
 
 /* Merge `nparts` per-shard results ([nparts, nq, k] each) into the global
  * top-k by (score, id); used after the RCCL all-gather of per-shard top-k. */
