@@ -36,6 +36,10 @@ MAX_SPARSE_ROW_ENTRIES = 65536   # include/css_hip.h CSS_MAX_SPARSE_ROW_ENTRIES
 MAX_SPARSE_WEIGHT = 65536.0   # include/css_hip.h CSS_MAX_SPARSE_WEIGHT
 SPARSE_TOPK_MIN_SLICE = 4096   # csrc/css_sparse.h kSparseTopkMinSlice: rows per block of the column top-k at least ...
 SPARSE_TOPK_MAX_PARTS = 32   # ... kSparseTopkMaxParts: and at most this many blocks
+MAX_TOKEN_DIM = 128   # include/css_hip.h CSS_MAX_TOKEN_DIM
+MAX_ROW_TOKEN_VECTORS = 512   # include/css_hip.h CSS_MAX_ROW_TOKEN_VECTORS
+MAX_QUERY_TOKENS = 64   # include/css_hip.h CSS_MAX_QUERY_TOKENS
+MAX_MAXSIM_ROWS = 65536   # include/css_hip.h CSS_MAX_MAXSIM_ROWS
 MAX_SIG_TERMS = 256   # include/css_hip.h CSS_MAX_SIG_TERMS
 MAX_FACET_BUCKETS = 1 << 20   # include/css_hip.h CSS_MAX_FACET_BUCKETS
 MAX_EXAMPLES = 16   # include/css_hip.h CSS_MAX_EXAMPLES
@@ -172,6 +176,14 @@ PROTOTYPES = {
     "css_index_search_sparse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "css_index_search_hybrid_sparse": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_index_set_tokens": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int]),
+    "css_index_get_tokens": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "css_index_token_rows": (c_int, [c_void_p, POINTER(c_int64)]),
+    "css_index_token_dim": (c_int, [c_void_p, POINTER(c_int)]),
+    "css_index_drop_tokens": (c_int, [c_void_p]),
+    "css_index_set_token_blocks": (c_int, [c_void_p, c_int]),
+    "css_index_search_maxsim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "css_index_maxsim_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "css_index_search_diverse": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
                                          c_void_p]),
     "css_index_search_diverse_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_void_p,

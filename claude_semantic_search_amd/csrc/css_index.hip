@@ -49,6 +49,9 @@
 //   k_sparse_scores,   css_index_search_sparse / _hybrid_sparse: the dot column of one sparse query over the per-row
 //   k_sparse_topk      sparse vectors; ranked alone by slices of the column and the part merge, or handed to
 //                      k_scan_prior like the BM25 column (css_sparse.h).   HBM bound up to 32 terms
+//   k_tok_scores       css_index_search_maxsim / css_index_maxsim_rows: the MaxSim column of one query matrix over the
+//                      per-row token matrices, bf16 MFMA with the query in registers, a persistent grid; ranked by
+//                      k_sparse_topk and the part merge (css_tokens.h).   HBM bound
 //   k_sig_count        css_index_subset_terms / _significant_terms: +1 per list entry of the selected rows into a
 //                      uint32 table [2^24], repeats merged in a per-block LDS table first; k_sig_score and the radix
 //                      select rank the terms (css_sigterms.h)
@@ -164,6 +167,15 @@ struct css_index {
     DevBuf<int64_t> sp_off;
     std::vector<int64_t> sp_off_h;
     int64_t sp_rows = 0;
+    // per-row token matrices (css_index_set_tokens, css_tokens.h), a third list kind: the leading tk_rows rows own
+    // tokens [tk_off[r], tk_off[r + 1]) of tk_tok, tk_dim bf16 each.  All empty until matrices are first set
+    // (tk_off_h.empty() tells); tk_off_h mirrors the offsets on the host.  tk_blocks: css_index_set_token_blocks
+    DevBuf<unsigned short> tk_tok;
+    DevBuf<int64_t> tk_off;
+    std::vector<int64_t> tk_off_h;
+    int64_t tk_rows = 0;
+    int tk_dim = 0;
+    int tk_blocks = 0;
     hipStream_t stream = nullptr;
     int num_cus = 256;
     // reusable workspaces (DevBuf: grown on demand, freed with the index; guarded by ws_mu)
@@ -271,6 +283,11 @@ struct css_index {
     DevBuf<float> sp_q;
     DevBuf<float> sp_pd;
     DevBuf<int64_t> sp_pi;
+    // css_index_search_maxsim / css_index_maxsim_rows: the query matrix [mq, P] bf16, the row numbers and the column
+    // of a row list (a search's column is lex_col, its part lists sp_pd / sp_pi)
+    DevBuf<unsigned short> tk_q;
+    DevBuf<uint32_t> tk_ids;
+    DevBuf<float> tk_col;
     // css_index_kmeans_step (css_kmeans.h): the uploaded centroids [nc, dim]; their padded table [ncpad][dpad] with the
     // squared norms [ncpad] behind it; assignment and distance of every row; the member lists [ntotal] with
     // [nc + 1 offsets | nc + 1 block numbers | nc cursors]; and [KM_HDR words | nc counts | nc * dim sums] of int64
@@ -2865,6 +2882,7 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 #include "css_knn_prior.h"
 #include "css_lexical.h"
 #include "css_sparse.h"
+#include "css_tokens.h"
 #include "css_where.h"
 #include "css_sigterms.h"
 
@@ -3345,6 +3363,15 @@ int drop_sparse(css_index* ix) {
     CSS_HIP_TRY(ix->sp_off.drop());
     return CSS_OK;
 }
+// ... and one that never received token matrices
+int drop_tokens(css_index* ix) {
+    ix->tk_rows = 0;
+    ix->tk_dim = 0;
+    ix->tk_off_h.clear();
+    CSS_HIP_TRY(ix->tk_tok.drop());
+    CSS_HIP_TRY(ix->tk_off.drop());
+    return CSS_OK;
+}
 }  // namespace
 
 int css_index_reset(css_index* ix) {
@@ -3360,8 +3387,9 @@ int css_index_reset(css_index* ix) {
     // the columns go with the rows: the index is again one that never set any
     for (RowColumn* col : ix->columns()) CSS_HIP_TRY(col->words.drop());
     for (AttrColumn& a : ix->attrs) a.type = -1;
-    const int rc = drop_terms(ix);   // and the term lists with their statistics, and the sparse vectors
-    return rc != CSS_OK ? rc : drop_sparse(ix);
+    int rc = drop_terms(ix);   // and the term lists with their statistics, the sparse vectors and the token matrices
+    if (rc == CSS_OK) rc = drop_sparse(ix);
+    return rc != CSS_OK ? rc : drop_tokens(ix);
 }
 
 namespace {
@@ -3577,6 +3605,55 @@ int compact_sparse(css_index* ix, const uint32_t* keep, SparseCompaction* sc) {
     sc->built = true;
     return CSS_OK;
 }
+
+// The token matrices through the same keep bits, OUT OF PLACE like compact_sparse, with k_tok_move.
+struct TokenCompaction {
+    DevBuf<unsigned short> tok;
+    DevBuf<uint32_t> map;
+    DevBuf<int64_t> off;
+    std::vector<int64_t> off_h;   // (read by the copy until the caller has waited)
+    std::vector<uint32_t> map_h;
+    bool built = false;
+    void commit(css_index* ix) {
+        ix->tk_tok.swap(tok);
+        ix->tk_off.swap(off);
+        ix->tk_off_h.swap(off_h);
+        ix->tk_rows = (int64_t)ix->tk_off_h.size() - 1;
+    }
+};
+int compact_tokens(css_index* ix, const uint32_t* keep, TokenCompaction* tc) {
+    const int64_t T = ix->tk_rows;
+    if (T == 0) return CSS_OK;
+    const hipStream_t st = ix->stream;
+    try {
+        tc->map_h.resize((size_t)T);
+        tc->off_h.assign(1, 0);
+        for (int64_t r = 0; r < T; ++r) {
+            if ((keep[r >> 5] >> (r & 31)) & 1u) {
+                tc->map_h[(size_t)r] = (uint32_t)(tc->off_h.size() - 1);
+                tc->off_h.push_back(tc->off_h.back() + (ix->tk_off_h[(size_t)r + 1] - ix->tk_off_h[(size_t)r]));
+            } else {
+                tc->map_h[(size_t)r] = kLexNoRow;
+            }
+        }
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_index_remove_rows: out of host memory");
+        return CSS_ERR_OOM;
+    }
+    const size_t nT = tc->off_h.size() - 1, P = (size_t)ix->tk_dim;
+    int rc;
+    if ((rc = tc->tok.grow_exact(std::max<size_t>((size_t)tc->off_h.back(), 1) * P, "hipMalloc(token matrices)")) != CSS_OK) return rc;
+    if ((rc = tc->off.grow_exact(nT + 1, "hipMalloc(token matrices)")) != CSS_OK) return rc;
+    if ((rc = tc->map.grow_exact((size_t)T, "hipMalloc(token matrices)")) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(tc->map.p, tc->map_h.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    CSS_HIP_TRY(hipMemcpyAsync(tc->off.p, tc->off_h.data(), (nT + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_tok_move, dim3((unsigned)((T + kWaves - 1) / kWaves)), dim3(256), 0, st,
+                       reinterpret_cast<const uint4*>(ix->tk_tok.p), (const int64_t*)ix->tk_off.p, (const uint32_t*)tc->map.p,
+                       (const int64_t*)tc->off.p, T, (int)(P / 8), reinterpret_cast<uint4*>(tc->tok.p));
+    CSS_LAUNCH_CHECK();
+    tc->built = true;
+    return CSS_OK;
+}
 }  // namespace
 
 int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t* removed_out) {
@@ -3608,6 +3685,7 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
         if (cols[c]->words.p && kept > 0 && (rc = column_alloc(ix, *cols[c], ix->cap, &ncol[c])) != CSS_OK) return rc;
     TermCompaction tc;      // the compacted term lists (only where terms were set)
     SparseCompaction sc;    // the compacted sparse vectors (only where vectors were set)
+    TokenCompaction kc;     // the compacted token matrices (only where matrices were set)
     CSS_HIP_TRY(hipMemsetAsync(ix->maxn2.p, 0, 3 * sizeof(int), ix->stream));
     uint32_t patch = 0;
     if (kept > 0) rc = compact_rows(ix, keep_bits_host, n, first, &patch);
@@ -3615,6 +3693,7 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
         if (rc == CSS_OK && ncol[c].p) rc = compact_column(ix, keep_bits_host, n, *cols[c], ncol[c]);
     if (rc == CSS_OK && ix->lex_df.p && kept > 0) rc = compact_terms(ix, keep_bits_host, &tc);
     if (rc == CSS_OK && !ix->sp_off_h.empty() && kept > 0) rc = compact_sparse(ix, keep_bits_host, &sc);
+    if (rc == CSS_OK && !ix->tk_off_h.empty() && kept > 0) rc = compact_tokens(ix, keep_bits_host, &kc);
     // later adds and searches on any stream are ordered behind the compaction (as css_index_reset)
     const hipError_t e = hipStreamSynchronize(ix->stream);
     if (rc != CSS_OK) return rc;
@@ -3623,8 +3702,10 @@ int css_index_remove_rows(css_index* ix, const uint32_t* keep_bits_host, int64_t
         if (ncol[c].p) cols[c]->words.swap(ncol[c]);
     if (tc.built) tc.commit(ix);
     if (sc.built) sc.commit(ix);
+    if (kc.built) kc.commit(ix);
     if (kept == 0 && (rc = drop_terms(ix)) != CSS_OK) return rc;   // emptied: as css_index_reset
     if (kept == 0 && (rc = drop_sparse(ix)) != CSS_OK) return rc;
+    if (kept == 0 && (rc = drop_tokens(ix)) != CSS_OK) return rc;
     set_ntotal(ix, kept);
     if (kept == 0 && !ix->xh.p) ix->shadow = -1;   // emptied: as css_index_reset
     for (css_index::I8Feedback* f : {&ix->fb_batch, &ix->fb_sweep}) {   // (it described other rows; its copy has landed)
@@ -5407,6 +5488,289 @@ int css_index_search_hybrid_sparse(css_index* ix, const float* q_host, int k, fl
     if (rc != CSS_OK) return rc;
     if (S_host) memcpy(S_host, sl_host, (size_t)k * sizeof(float));
     if (L_host) memcpy(L_host, sl_host + k, (size_t)k * sizeof(float));
+    return CSS_OK;
+}
+
+// ------------------------------------------------------------------ per-row token matrices and MaxSim search
+namespace {
+inline bool bf16_finite(uint16_t v) { return (v & 0x7F80u) != 0x7F80u; }
+inline bool token_dim_ok(int P) { return P >= 32 && P <= CSS_MAX_TOKEN_DIM && P % 32 == 0; }
+}  // namespace
+
+int css_index_set_tokens(css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host, const uint16_t* tok_host, int P) {
+    CSS_REQUIRE(ix, "css_index_set_tokens: NULL index");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);   // (ws_pending)
+    const int64_t T0 = ix->tk_rows;
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_set_tokens: rows [%lld, %lld + %lld) outside [0, %lld)",
+                (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
+    CSS_REQUIRE(row0 <= T0, "css_index_set_tokens: row0=%lld beyond the %lld rows that have matrices (matrices are append-only)",
+                (long long)row0, (long long)T0);
+    CSS_REQUIRE(token_dim_ok(P), "css_index_set_tokens: P=%d must be a multiple of 32 in [32, %d]", P, CSS_MAX_TOKEN_DIM);
+    CSS_REQUIRE(T0 == 0 || n == 0 || P == ix->tk_dim || row0 == 0,
+                "css_index_set_tokens: P=%d, but the stored matrices have P=%d (only a rewrite from row 0 changes it)", P, ix->tk_dim);
+    CSS_REQUIRE(n == 0 || offsets_host, "css_index_set_tokens: offsets is NULL");
+    // everything is looked at before anything is written
+    if (n > 0) {
+        CSS_REQUIRE(offsets_host[0] == 0, "css_index_set_tokens: offsets start at %lld, not 0", (long long)offsets_host[0]);
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t c = offsets_host[i + 1] - offsets_host[i];
+            CSS_REQUIRE(c >= 0, "css_index_set_tokens: offsets decrease at row %lld", (long long)(row0 + i));
+            CSS_REQUIRE(c <= CSS_MAX_ROW_TOKEN_VECTORS, "css_index_set_tokens: row %lld has %lld tokens (at most %d)", (long long)(row0 + i),
+                        (long long)c, CSS_MAX_ROW_TOKEN_VECTORS);
+        }
+        CSS_REQUIRE(offsets_host[n] == 0 || tok_host, "css_index_set_tokens: tokens is NULL");
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t e = offsets_host[i] * P; e < offsets_host[i + 1] * P; ++e)
+                CSS_REQUIRE(bf16_finite(tok_host[e]), "css_index_set_tokens: component %lld of token %lld of row %lld is %s",
+                            (long long)(e % P), (long long)(e / P - offsets_host[i]), (long long)(row0 + i),
+                            (tok_host[e] & 0x7Fu) ? "NaN" : "infinite");
+    }
+    if (n == 0 && row0 == T0) return CSS_OK;
+    const int64_t E0 = T0 > 0 ? ix->tk_off_h[(size_t)row0] : 0;
+    const int64_t nE = n > 0 ? offsets_host[n] : 0;
+    std::vector<int64_t> off;
+    try {
+        off.resize((size_t)n + 1);
+        for (int64_t i = 0; i <= n; ++i) off[(size_t)i] = E0 + (n > 0 ? offsets_host[i] : 0);
+        ix->tk_off_h.reserve((size_t)(row0 + n) + 1);
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_index_set_tokens: out of host memory");
+        return CSS_ERR_OOM;
+    }
+    DeviceGuard g(ix->device);
+    const hipStream_t st = ix->stream;
+    // as css_index_set_sparse: a search on another stream may still read the matrices that go or move
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    if (ix->ws_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ws_ev, 0));
+    int rc;
+    if (ix->tk_off_h.empty()) ix->tk_off_h.assign(1, 0);   // first matrices of this index
+    if (row0 < T0) {   // the matrices of rows >= row0 go
+        ix->tk_off_h.resize((size_t)row0 + 1);
+        ix->tk_rows = row0;
+    }
+    if (n > 0) {
+        ix->tk_dim = P;   // (another P only from row 0: nothing of the old width is left)
+        const size_t sP = (size_t)P;
+        if ((rc = grow_keep(ix, ix->tk_tok, (size_t)E0 * sP, ((size_t)E0 + std::max<size_t>((size_t)nE, 1)) * sP, "hipMalloc(token matrices)")) != CSS_OK) return rc;
+        if ((rc = grow_keep(ix, ix->tk_off, (size_t)row0 + 1, (size_t)(row0 + n) + 1, "hipMalloc(token matrices)")) != CSS_OK) return rc;
+        if (nE) CSS_HIP_TRY(hipMemcpyAsync(ix->tk_tok.p + (size_t)E0 * sP, tok_host, (size_t)nE * sP * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        CSS_HIP_TRY(hipMemcpyAsync(ix->tk_off.p + row0, off.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    }
+    CSS_HIP_TRY(hipStreamSynchronize(st));   // (the copies read this call's matrices)
+    ix->tk_off_h.insert(ix->tk_off_h.end(), off.begin() + 1, off.end());
+    ix->tk_rows = row0 + n;
+    return CSS_OK;
+}
+
+int css_index_get_tokens(css_index* ix, int64_t row0, int64_t n, int64_t* offsets_out, uint16_t* tok_out) {
+    CSS_REQUIRE(ix, "css_index_get_tokens: NULL index");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_get_tokens: rows [%lld, %lld + %lld) outside [0, %lld)",
+                (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
+    CSS_REQUIRE(offsets_out, "css_index_get_tokens: offsets_out is NULL");
+    const int64_t T = ix->tk_rows;
+    const int64_t a = std::min(row0, T), e = std::min(row0 + n, T);   // the rows of the range that have matrices
+    const int64_t E0 = T > 0 ? ix->tk_off_h[(size_t)a] : 0;
+    for (int64_t i = 0; i <= n; ++i) offsets_out[i] = T > 0 ? ix->tk_off_h[(size_t)std::min(row0 + i, T)] - E0 : 0;
+    const int64_t nE = offsets_out[n];
+    if (e <= a || nE == 0 || !tok_out) return CSS_OK;
+    DeviceGuard g(ix->device);
+    const size_t P = (size_t)ix->tk_dim;
+    CSS_HIP_TRY(hipMemcpy(tok_out, ix->tk_tok.p + (size_t)E0 * P, (size_t)nE * P * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return CSS_OK;
+}
+
+int css_index_token_rows(css_index* ix, int64_t* rows_out) {
+    CSS_REQUIRE(ix && rows_out, "css_index_token_rows: NULL argument");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    *rows_out = ix->tk_rows;
+    return CSS_OK;
+}
+
+int css_index_token_dim(css_index* ix, int* dim_out) {
+    CSS_REQUIRE(ix && dim_out, "css_index_token_dim: NULL argument");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    *dim_out = ix->tk_rows == 0 ? 0 : ix->tk_dim;
+    return CSS_OK;
+}
+
+int css_index_drop_tokens(css_index* ix) {
+    CSS_REQUIRE(ix, "css_index_drop_tokens: NULL index");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    if (ix->tk_off_h.empty()) return CSS_OK;
+    DeviceGuard g(ix->device);
+    // a search on another stream may still read the matrices
+    if (ix->ws_pending) CSS_HIP_TRY(hipEventSynchronize(ix->ws_ev));
+    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    return drop_tokens(ix);
+}
+
+int css_index_set_token_blocks(css_index* ix, int blocks) {
+    CSS_REQUIRE(ix, "css_index_set_token_blocks: NULL index");
+    CSS_REQUIRE(blocks >= 0 && blocks <= 65536, "css_index_set_token_blocks: blocks=%d outside [0, 65536]", blocks);
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    ix->tk_blocks = blocks;
+    return CSS_OK;
+}
+
+namespace {
+// the checks that css_index_search_maxsim and css_index_maxsim_rows make of a query matrix
+int token_query_check(const char* fn, const uint16_t* q_tok_host, int mq, int P) {
+    CSS_REQUIRE(mq >= 1 && mq <= CSS_MAX_QUERY_TOKENS, "%s: mq=%d outside [1, %d]", fn, mq, CSS_MAX_QUERY_TOKENS);
+    CSS_REQUIRE(token_dim_ok(P), "%s: P=%d must be a multiple of 32 in [32, %d]", fn, P, CSS_MAX_TOKEN_DIM);
+    CSS_REQUIRE(q_tok_host, "%s: NULL buffer", fn);
+    for (int i = 0; i < mq * P; ++i)
+        CSS_REQUIRE(bf16_finite(q_tok_host[i]), "%s: component %d of query token %d is %s", fn, i % P, i / P,
+                    (q_tok_host[i] & 0x7Fu) ? "NaN" : "infinite");
+    return CSS_OK;
+}
+
+extern "C++" template <int P>
+const void* tok_scores_kernel(int MT) {
+    switch (MT) {
+        case 1: return (const void*)k_tok_scores<P, 1>;
+        case 2: return (const void*)k_tok_scores<P, 2>;
+        case 3: return (const void*)k_tok_scores<P, 3>;
+        default: return (const void*)k_tok_scores<P, 4>;
+    }
+}
+
+// The MaxSim column of the query (mq tokens of the index's P on the device) over positions [0, n) into `col`: the rows
+// 0 .. n - 1 (rows == null; `mask` as in the searches) or the n rows of the list; -inf where the row is a miss.
+// n > 0 and the index has matrices.  Enqueued on `st`.
+int tok_scores_enqueue(css_index* ix, const uint32_t* rows, int64_t n, const uint32_t* mask, const unsigned short* q, int mq,
+                       float* col, hipStream_t st) {
+    const int P = ix->tk_dim, MT = (mq + 15) / 16;
+    const void* fn = P == 32 ? tok_scores_kernel<32>(MT) : P == 64 ? tok_scores_kernel<64>(MT) : P == 96 ? tok_scores_kernel<96>(MT)
+                                                                                                        : tok_scores_kernel<128>(MT);
+    // The grid: as many blocks as stay resident (no block waits for another, so the figure only sets the speed), and
+    // the rows of a wave's turn: 16 for a scan, fewer where that would leave waves idle.  css_index_set_token_blocks
+    // fixes the grid and with it 16 rows per turn
+    int64_t blocks = ix->tk_blocks;
+    int per = kTokTurn;
+    if (blocks == 0) {
+        int per_cu = 0;
+        CSS_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * kWaves, 0));
+        blocks = (int64_t)std::max(per_cu, 1) * ix->num_cus;
+        per = (int)std::min<int64_t>(kTokTurn, (n + blocks * kWaves - 1) / (blocks * kWaves));
+    }
+    blocks = std::min<int64_t>(blocks, (n + (int64_t)per * kWaves - 1) / ((int64_t)per * kWaves));
+    const unsigned short* tok = ix->tk_tok.p;
+    const int64_t* off = ix->tk_off.p;
+    int64_t nlist = ix->tk_rows;
+    void* args[] = {&tok, &off, &nlist, &rows, &n, &mask, &q, &mq, &per, &col};
+    ProfScope ps("tok_scores", st);
+    CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * kWaves), args, 0, st));
+    return CSS_OK;
+}
+
+// The MaxSim column, its top-k by slices, and the part merge.  Everything is enqueued on `st`; nothing waits for the
+// device.  Caller holds ws_mu and a shared lock on mu.
+int search_maxsim_enqueue(css_index* ix, const Rows& rows, const unsigned short* q_dev, int mq, int k, float* D_dev,
+                          int64_t* I_dev, hipStream_t st) {
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    if (ix->tk_rows == 0 || rows.n == 0) {
+        hipLaunchKernelGGL(k_sparse_pad, dim3(1), dim3(128), 0, st, D_dev, I_dev, k);
+        CSS_LAUNCH_CHECK();
+        return CSS_OK;
+    }
+    CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "css_index_search_maxsim: %lld rows exceed the 32-bit row numbers of the lists",
+                (long long)rows.n);
+    // rows appended on another stream must have landed (the mask and the row count speak of them)
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    const int64_t slice = sparse_topk_slice(rows.n);
+    const int parts = (int)((rows.n + slice - 1) / slice);
+    if ((rc = ix->lex_col.grow((size_t)rows.n)) != CSS_OK) return rc;
+    if ((rc = ix->sp_pd.grow((size_t)parts * k)) != CSS_OK) return rc;
+    if ((rc = ix->sp_pi.grow((size_t)parts * k)) != CSS_OK) return rc;
+    if ((rc = tok_scores_enqueue(ix, nullptr, rows.n, rows.mask, q_dev, mq, ix->lex_col.p, st)) != CSS_OK) return rc;
+    {
+        ProfScope ps("sparse_topk", st);
+        hipLaunchKernelGGL(k_sparse_topk, dim3((unsigned)parts), dim3(256), 0, st, (const float*)ix->lex_col.p, rows.n, slice,
+                           rows.mask, k, rows.id_base, ix->sp_pd.p, ix->sp_pi.p);
+        CSS_LAUNCH_CHECK();
+    }
+    // (larger is better whatever the index's metric: the parts merge as inner-product lists)
+    return merge_parts(ix->sp_pd.p, ix->sp_pi.p, parts, k, k, 1, k, CSS_METRIC_IP, D_dev, I_dev, ix->device, st,
+                       "css_index_search_maxsim");
+}
+}  // namespace
+
+int css_index_search_maxsim(css_index* ix, const uint16_t* q_tok_host, int mq, int P, int k, const uint32_t* allow_bits_host,
+                            float* D_host, int64_t* I_host) {
+    CSS_REQUIRE(ix, "css_index_search_maxsim: NULL index");
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "css_index_search_maxsim: k=%d outside [1, %d]", k, CSS_KERNEL_MAX_K);
+    CSS_REQUIRE(D_host && I_host, "css_index_search_maxsim: NULL buffer");
+    int rc = token_query_check("css_index_search_maxsim", q_tok_host, mq, P);
+    if (rc != CSS_OK) return rc;
+    HostCall hc(ix);
+    CSS_REQUIRE(ix->tk_rows == 0 || P == ix->tk_dim, "css_index_search_maxsim: the query has P=%d, the stored matrices P=%d", P,
+                ix->tk_dim);
+    // the ONE upload: the query matrix
+    rc = hc.upload(allow_bits_host, ix->tk_q, (const unsigned short*)q_tok_host, (size_t)mq * P, (size_t)k);
+    if (rc == CSS_OK) rc = search_maxsim_enqueue(ix, hc.rows, ix->tk_q.p, mq, k, hc.d_out, hc.i_out, ix->stream);
+    return hc.finish(rc, D_host, I_host);
+}
+
+int css_index_maxsim_rows(css_index* ix, const uint16_t* q_tok_host, int mq, int P, const int64_t* ids_host, int64_t n,
+                          float* scores_out) {
+    CSS_REQUIRE(ix, "css_index_maxsim_rows: NULL index");
+    CSS_REQUIRE(n >= 0 && n <= CSS_MAX_MAXSIM_ROWS, "css_index_maxsim_rows: n=%lld outside [0, %d]", (long long)n, CSS_MAX_MAXSIM_ROWS);
+    CSS_REQUIRE(n == 0 || (ids_host && scores_out), "css_index_maxsim_rows: NULL buffer");
+    int rc = token_query_check("css_index_maxsim_rows", q_tok_host, mq, P);
+    if (rc != CSS_OK) return rc;
+    CallScope cs(ix);
+    CSS_REQUIRE(ix->tk_rows == 0 || P == ix->tk_dim, "css_index_maxsim_rows: the query has P=%d, the stored matrices P=%d", P,
+                ix->tk_dim);
+    for (int64_t i = 0; i < n; ++i)
+        CSS_REQUIRE(ids_host[i] >= cs.rows.id_base && ids_host[i] - cs.rows.id_base < cs.rows.n,
+                    "css_index_maxsim_rows: id %lld (position %lld) is outside the index's [%lld, %lld)", (long long)ids_host[i],
+                    (long long)i, (long long)cs.rows.id_base, (long long)(cs.rows.id_base + cs.rows.n));
+    if (n == 0) return CSS_OK;
+    if (ix->tk_rows == 0) {   // no matrices: every row is a miss
+        for (int64_t i = 0; i < n; ++i) scores_out[i] = -INFINITY;
+        return CSS_OK;
+    }
+    // the ONE upload: [row numbers | the query matrix] (the matrix behind the 4-byte numbers: 16-byte aligned rows)
+    const size_t nq_words = ((size_t)mq * P + 1) / 2, at = ((size_t)n + 3) / 4 * 4;
+    std::vector<uint32_t> in;
+    try {
+        in.assign(at + nq_words, 0u);
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_index_maxsim_rows: out of host memory");
+        return CSS_ERR_OOM;
+    }
+    for (int64_t i = 0; i < n; ++i) in[(size_t)i] = (uint32_t)(ids_host[i] - cs.rows.id_base);
+    memcpy(in.data() + at, q_tok_host, (size_t)mq * P * sizeof(uint16_t));
+    const hipStream_t st = ix->stream;
+    if ((rc = ix->tk_ids.grow(in.size())) != CSS_OK) return rc;
+    if ((rc = ix->tk_col.grow((size_t)n)) != CSS_OK) return rc;
+    {
+        WsTurn turn(ix, st);
+        rc = turn.rc;
+        if (rc == CSS_OK) {
+            const hipError_t e = hipMemcpyAsync(ix->tk_ids.p, in.data(), in.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) rc = css::hip_fail(e, "hipMemcpyAsync(row numbers)", __FILE__, __LINE__);
+        }
+        if (rc == CSS_OK && ix->ingest_pending) {
+            const hipError_t e = hipStreamWaitEvent(st, ix->ingest_ev, 0);
+            if (e != hipSuccess) rc = css::hip_fail(e, "hipStreamWaitEvent(ingest)", __FILE__, __LINE__);
+        }
+        if (rc == CSS_OK)
+            rc = tok_scores_enqueue(ix, ix->tk_ids.p, n, nullptr, reinterpret_cast<const unsigned short*>(ix->tk_ids.p + at), mq,
+                                    ix->tk_col.p, st);
+        if (rc == CSS_OK) {
+            const hipError_t e = hipMemcpyAsync(scores_out, ix->tk_col.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st);
+            if (e != hipSuccess) rc = css::hip_fail(e, "hipMemcpyAsync(scores)", __FILE__, __LINE__);
+        }
+    }
+    const hipError_t e = hipStreamSynchronize(st);   // (also after a failure: the copies read this call's memory)
+    if (rc != CSS_OK) return rc;
+    CSS_HIP_TRY(e);
     return CSS_OK;
 }
 

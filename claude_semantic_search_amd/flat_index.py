@@ -450,6 +450,116 @@ def sparse_as_csr(vectors, what: str = "set_sparse") -> Tuple[np.ndarray, np.nda
     return off, np.ascontiguousarray(t, dtype=np.uint32), w
 
 
+MAX_QUERY_TOKENS = nat.MAX_QUERY_TOKENS
+MAX_ROW_TOKEN_VECTORS = nat.MAX_ROW_TOKEN_VECTORS
+MAX_MAXSIM_ROWS = nat.MAX_MAXSIM_ROWS
+
+
+def _bf16_bits(m, what: str, name: str) -> np.ndarray:
+    """uint16 bf16 bit patterns of a token matrix: uint16 as it is, float32 only where every value IS a bf16 value (the
+    low 16 bits are zero) -- rounding is the caller's decision, never a silent one.  ``name`` says whose matrix it is."""
+    a = np.asarray(m)
+    if a.dtype == np.uint16:
+        return a
+    if a.dtype != np.float32:
+        raise ValueError(f"{what}: {name} must be uint16 (bf16 bits) or bf16-exact float32, got dtype {a.dtype}")
+    u = np.ascontiguousarray(a).view(np.uint32)
+    if (u & 0xFFFF).any():
+        raise ValueError(f"{what}: {name} holds float32 values that are not bf16 values (round them first)")
+    return (u >> 16).astype(np.uint16)
+
+
+def _token_dim_ok(P: int) -> bool:
+    return 32 <= P <= nat.MAX_TOKEN_DIM and P % 32 == 0
+
+
+def tokens_as_csr(mats, keep=None, what: str = "set_tokens") -> Tuple[np.ndarray, np.ndarray, int]:
+    """Token matrices as CSR ``(offsets int64 [n + 1] from 0 in tokens, tokens uint16 [offsets[n], P], P)``.  ``mats`` is
+    a sequence of ``[m_i, P]`` matrices, uint16 bf16 bits or bf16-exact float32 (one per row, empty allowed), or an
+    ``(offsets, tokens [E, P], P)`` triple.  ``keep`` (sequence form only; per row one flag per token, or ``None``) is
+    ColBERT's skiplist as in ``LateInteraction.score``: a token whose flag is 0 is DROPPED here and not stored.  What
+    the library would refuse raises ``ValueError`` here and names the row (of this call): a width that is not a
+    multiple of 32 in [32, 128] or differs between rows, a NaN or infinite component, more than 512 tokens."""
+    if isinstance(mats, tuple) and len(mats) == 3 and isinstance(mats[0], np.ndarray) and np.ndim(mats[2]) == 0:
+        if keep is not None:
+            raise ValueError(f"{what}: keep flags go with a sequence of matrices, not with the CSR form")
+        off = np.ascontiguousarray(mats[0], dtype=np.int64).reshape(-1)
+        P = int(mats[2])
+        if off.shape[0] < 1:
+            raise ValueError(f"{what}: offsets must hold n + 1 values")
+        if not _token_dim_ok(P):
+            raise ValueError(f"{what}: P={P} must be a multiple of 32 in [32, {nat.MAX_TOKEN_DIM}]")
+        tok = _bf16_bits(mats[1], what, "the tokens")
+        if tok.size % P:
+            raise ValueError(f"{what}: {tok.size} components are no whole tokens of P={P}")
+        tok = tok.reshape(-1, P)
+    else:
+        mats = list(mats)
+        if keep is not None and len(keep) != len(mats):
+            raise ValueError(f"{what}: {len(keep)} keep arrays for {len(mats)} matrices")
+        rows, P = [], 0
+        for r, m in enumerate(mats):
+            a = _bf16_bits(m, what, f"the matrix of row {r} (of this call)")
+            if a.ndim != 2:
+                raise ValueError(f"{what}: the matrix of row {r} (of this call) has shape {a.shape}, not [m, P]")
+            if not _token_dim_ok(a.shape[1]):
+                raise ValueError(f"{what}: row {r} (of this call) has P={a.shape[1]}, not a multiple of 32 in "
+                                 f"[32, {nat.MAX_TOKEN_DIM}]")
+            if P and a.shape[1] != P:
+                raise ValueError(f"{what}: row {r} (of this call) has P={a.shape[1]}, the rows before it P={P}")
+            P = a.shape[1]
+            if keep is not None and keep[r] is not None:
+                f = np.asarray(keep[r]).reshape(-1) != 0
+                if f.shape[0] != a.shape[0]:
+                    raise ValueError(f"{what}: {f.shape[0]} keep flags for the {a.shape[0]} tokens of row {r} (of this call)")
+                a = a[f]
+            rows.append(a)
+        P = P or 32   # (no row: nothing is stored, any width serves)
+        off = np.zeros(len(rows) + 1, dtype=np.int64)
+        if rows:
+            np.cumsum([a.shape[0] for a in rows], out=off[1:])
+        tok = np.concatenate(rows) if rows else np.zeros((0, P), np.uint16)
+    tok = np.ascontiguousarray(tok, dtype=np.uint16)
+    well_formed = off[0] == 0 and off[-1] == tok.shape[0] and (np.diff(off) >= 0).all()
+    bad = np.flatnonzero(((tok & 0x7F80) == 0x7F80).any(axis=1))
+    if bad.size:
+        row = int(np.searchsorted(off, bad[0], side="right")) - 1 if well_formed else -1
+        raise ValueError(f"{what}: token {int(bad[0] - off[row]) if well_formed else int(bad[0])} of row {row} (of this call) "
+                         "has a NaN or infinite component")
+    if well_formed:
+        lens = np.diff(off)
+        if lens.size and int(lens.max()) > MAX_ROW_TOKEN_VECTORS:
+            raise ValueError(f"{what}: row {int(lens.argmax())} (of this call) has {int(lens.max())} tokens "
+                             f"(at most {MAX_ROW_TOKEN_VECTORS})")
+    return off, tok, P
+
+
+def maxsim_args(q_mat, k=None, ids=None, what: str = "search_maxsim"):
+    """The checked arguments of a MaxSim call: ``(q uint16 [mq, P], k or None, ids int64 [n] or None)``; what the library
+    would refuse raises ``ValueError`` here.  ``q_mat`` is ONE ``[mq, P]`` matrix, uint16 bf16 bits or bf16-exact
+    float32, ``1 <= mq <= 64``, P a multiple of 32 in [32, 128], finite; ``1 <= k <= 128``; at most 65536 ``ids``."""
+    q = _bf16_bits(q_mat, what, "the query matrix")
+    if q.ndim != 2:
+        raise ValueError(f"{what}: one query matrix [mq, P] per call, got shape {q.shape}")
+    if not 1 <= q.shape[0] <= MAX_QUERY_TOKENS:
+        raise ValueError(f"{what}: {q.shape[0]} query tokens outside [1, {MAX_QUERY_TOKENS}]")
+    if not _token_dim_ok(q.shape[1]):
+        raise ValueError(f"{what}: P={q.shape[1]} must be a multiple of 32 in [32, {nat.MAX_TOKEN_DIM}]")
+    q = np.ascontiguousarray(q, dtype=np.uint16)
+    bad = np.flatnonzero(((q & 0x7F80) == 0x7F80).any(axis=1))
+    if bad.size:
+        raise ValueError(f"{what}: query token {int(bad[0])} has a NaN or infinite component")
+    if k is not None:
+        k = int(k)
+        if k < 1 or k > MAX_HYBRID_K:
+            raise ValueError(f"k={k} outside [1, {MAX_HYBRID_K}]")
+    if ids is not None:
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        if ids.shape[0] > MAX_MAXSIM_ROWS:
+            raise ValueError(f"{what}: {ids.shape[0]} ids (at most {MAX_MAXSIM_ROWS})")
+    return q, k, ids
+
+
 MAX_DIVERSE_FETCH = nat.MAX_DIVERSE_FETCH
 
 
@@ -1399,6 +1509,81 @@ class IndexFlat:
             h, a.ctypes.data, k, alpha, t.ctypes.data if t.size else None, w.ctypes.data if t.size else None, t.shape[0],
             1 if normalize else 0, bits_ptr, D.ctypes.data, I.ctypes.data, S.ctypes.data, L.ctypes.data))
         return D, I, S, L
+
+    # -- per-row token matrices and MaxSim search ------------------------------
+    def set_tokens(self, mats, keep=None, row0: Optional[int] = None) -> None:
+        """Token matrices of rows ``[row0, row0 + n)`` in LOCAL row numbering (``css_index_set_tokens``).  ``mats`` is a
+        sequence of ``[m_i, P]`` matrices of bf16 values (uint16 bits as ``LateInteraction.encode_documents`` gives them,
+        or bf16-exact float32; empty rows allowed) or an ``(offsets, tokens, P)`` triple in CSR form.  ``keep`` per row
+        is ColBERT's skiplist as in ``LateInteraction.score``: a dropped token is NOT STORED.  P is a multiple of 32 in
+        [32, 128], fixed by the first call (only a rewrite from row 0 changes it); at most 512 tokens per row; finite
+        components.  APPEND-ONLY in row order like ``set_sparse`` and independent of it: with ``T = token_rows``,
+        ``row0 = None`` or ``T`` appends, ``row0 < T`` first drops the matrices of all rows ``>= row0``, ``row0 > T``
+        raises.  The matrices follow the rows through growth, ``remove_ids`` (compacted with them) and ``reset``
+        (forgotten); rows added later have none."""
+        off, tok, P = tokens_as_csr(mats, keep)
+        row0 = self.token_rows if row0 is None else int(row0)
+        nat.check(nat.lib().css_index_set_tokens(self._handle(), row0, off.shape[0] - 1, off.ctypes.data,
+                                                 tok.ctypes.data if tok.size else None, P))
+
+    def get_tokens(self, row0: int = 0, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """The stored matrices of rows ``[row0, row0 + n)`` (default: to the end): ``(offsets int64 [n + 1] from 0,
+        tokens uint16 [offsets[n], P])``.  Rows without a matrix are empty."""
+        row0, n = self._row_range("get_tokens", row0, n)
+        off = np.zeros(n + 1, dtype=np.int64)
+        P = self.token_dim
+        if n == 0 or P == 0:
+            return off, np.zeros((0, P), np.uint16)
+        nat.check(nat.lib().css_index_get_tokens(self._handle(), row0, n, off.ctypes.data, None))
+        tok = np.zeros((int(off[-1]), P), dtype=np.uint16)
+        if tok.size:
+            nat.check(nat.lib().css_index_get_tokens(self._handle(), row0, n, off.ctypes.data, tok.ctypes.data))
+        return off, tok
+
+    @property
+    def token_rows(self) -> int:
+        """The number of leading rows that have token matrices."""
+        return self._read_i64(nat.lib().css_index_token_rows)
+
+    @property
+    def token_dim(self) -> int:
+        """The width P of the stored token vectors (0: no row has a matrix)."""
+        p = ctypes.c_int(0)
+        nat.check(nat.lib().css_index_token_dim(self._handle(), ctypes.byref(p)))
+        return int(p.value)
+
+    def drop_tokens(self) -> None:
+        """Forget every token matrix and free their memory (``css_index_drop_tokens``)."""
+        nat.check(nat.lib().css_index_drop_tokens(self._handle()))
+
+    def set_token_blocks(self, blocks: int) -> None:
+        """The grid of the MaxSim kernel (0 = the library's choice); the result does not depend on it."""
+        nat.check(nat.lib().css_index_set_token_blocks(self._handle(), int(blocks)))
+
+    def search_maxsim(self, q_mat, k: int, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The ``k`` best rows for ONE query matrix ``[mq, P]`` by MaxSim with the rows' token matrices ALONE
+        (``css_index_search_maxsim``): ``(D, I)``, each ``[1, k]`` -- the score ``sum_s max_t dot(q_s, d_t)``, bit for
+        bit what ``MpnetEncoder.maxsim`` gives for the same matrices, and the global id; larger first on an index of
+        either metric, ties to the lower id.  Rows without tokens are never returned; fewer than ``k`` hits or an
+        index without matrices pad with ``I = -1``, ``D = -FLT_MAX``.  No dense row is read."""
+        q, k, _ = maxsim_args(q_mat, k)
+        D, I = np.empty((1, k), dtype=np.float32), np.empty((1, k), dtype=np.int64)
+        h = self._handle()
+        bits, bits_ptr = self._allow_bits(allow)
+        nat.check(nat.lib().css_index_search_maxsim(h, q.ctypes.data, q.shape[0], q.shape[1], k, bits_ptr, D.ctypes.data,
+                                                    I.ctypes.data))
+        return D, I
+
+    def maxsim_ids(self, q_mat, ids) -> np.ndarray:
+        """The MaxSim scores of the rows named by GLOBAL ``ids`` (any order, repeats allowed, at most 65536) for ONE
+        query matrix (``css_index_maxsim_rows``): float32 ``[n]``, ``-inf`` for a row without tokens.  The re-rank
+        stage without a forward pass; an id outside the index raises and names its position."""
+        q, _, ids = maxsim_args(q_mat, ids=ids, what="maxsim_ids")
+        out = np.empty(ids.shape[0], dtype=np.float32)
+        nat.check(nat.lib().css_index_maxsim_rows(self._handle(), q.ctypes.data, q.shape[0], q.shape[1],
+                                                  ids.ctypes.data if ids.size else None, ids.shape[0],
+                                                  out.ctypes.data if ids.size else None))
+        return out
 
     # -- diversified search (MMR) --------------------------------------------
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False,

@@ -74,6 +74,8 @@ class ShardedFlatIndex:
         self._dead: Optional[np.ndarray] = None          # tombstones in global numbering (replicated; mark_deleted)
         self._terms_global = 0                           # leading GLOBAL rows that have term lists (replicated; set_terms)
         self._sparse_global = 0                          # ... that have sparse vectors (replicated; set_sparse)
+        self._tokens_global = 0                          # ... that have token matrices, and their width (set_tokens)
+        self._token_dim = 0
         self._attr_types: dict = {}                      # slot -> type of the attribute columns (replicated; set_attribute)
 
     # -- building ----------------------------------------------------------
@@ -726,6 +728,90 @@ class ShardedFlatIndex:
         I, (D, S, L), _ = self._columns(I, (D, S, L))
         return tuple(np.ascontiguousarray(a[..., :k]) for a in (D, I, S, L))
 
+    # -- token matrices and MaxSim search ------------------------------------------------------------------------
+    def set_tokens(self, mats, keep=None, row0: Optional[int] = None) -> None:
+        """``IndexFlat.set_tokens`` in GLOBAL numbering (collective: every rank passes the same matrices; no
+        communication): the token matrices of the global rows ``[row0, row0 + n)``, append-only like ``set_sparse`` and
+        routed through the segment table the same way."""
+        from .flat_index import tokens_as_csr
+
+        off, tok, P = tokens_as_csr(mats, keep)
+        n = off.shape[0] - 1
+        row0 = self._tokens_global if row0 is None else int(row0)
+        self._check_rows("set_tokens", row0, n)
+        if row0 > self._tokens_global:
+            raise ValueError(f"set_tokens: row0={row0} beyond the {self._tokens_global} rows that have matrices (matrices are append-only)")
+        if self._tokens_global and row0 and n and P != self._token_dim:
+            raise ValueError(f"set_tokens: P={P}, but the stored matrices have P={self._token_dim} (only a rewrite from row 0 changes it)")
+        if n == 0 and row0 == self._tokens_global:
+            return
+        local_row0, loff, (ltok,) = self._local_csr(row0, off, (tok,))
+        self.local.set_tokens((loff, ltok, P), row0=local_row0)
+        self._tokens_global, self._token_dim = row0 + n, P if n else self._token_dim
+
+    @property
+    def token_rows(self) -> int:
+        """The leading GLOBAL rows that have token matrices."""
+        return self._tokens_global
+
+    @property
+    def token_dim(self) -> int:
+        """The width P of the stored token vectors (0: no row has a matrix)."""
+        return self._token_dim if self._tokens_global else 0
+
+    def drop_tokens(self) -> None:
+        """``IndexFlat.drop_tokens`` on every shard (collective; no communication)."""
+        self.local.drop_tokens()
+        self._tokens_global, self._token_dim = 0, 0
+
+    def get_tokens(self, row0: int = 0, n: Optional[int] = None):
+        """``IndexFlat.get_tokens`` of the GLOBAL rows ``[row0, row0 + n)`` on every rank (collective): the shard that
+        owns a row supplies its length and its tokens, every other shard zeros, in two ``_sum_over_ranks`` (exact: one
+        contribution per entry)."""
+        row0 = int(row0)
+        n = self.ntotal_global - row0 if n is None else int(n)
+        self._check_rows("get_tokens", row0, n)
+        P = self.token_dim
+        parts = [(lo - row0, m) + tuple(self.local.get_tokens(l0, m)) for l0, lo, m in self._overlaps(row0, n)] if P else []
+        lens = np.zeros(n, dtype=np.int64)
+        for at, m, loff, _ in parts:
+            lens[at:at + m] = np.diff(loff)
+        lens = self._sum_over_ranks(lens)
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        tok = np.zeros((int(off[-1]), max(P, 1)), dtype=np.int32)
+        for at, m, _, ltok in parts:
+            tok[off[at]:off[at + m]] = np.asarray(ltok).reshape(-1, P)   # (a shard without matrices gives [0, 0])
+        return off, self._sum_over_ranks(tok).astype(np.uint16).reshape(int(off[-1]), P)
+
+    def search_maxsim(self, q_mat, k: int, allow=None):
+        """``IndexFlat.search_maxsim`` over the shards (collective): ``(D, I)`` with global ids on every rank.  A row's
+        score is a function of its own matrix and the query, so the merged result equals the single index's in bytes.
+        The exchange moves 12-byte records (id, D); every rank keeps the first ``k`` by ``(D descending, id)`` on an
+        index of either metric."""
+        from .flat_index import maxsim_args
+
+        q, k, _ = maxsim_args(q_mat, k)
+        D, I = self.local.search_maxsim(q, k, allow=self._local_allow(allow))
+        I, (D,), _ = self._columns(I, (D,), metric=0)
+        return tuple(np.ascontiguousarray(a[..., :k]) for a in (D, I))
+
+    def maxsim_ids(self, q_mat, ids) -> np.ndarray:
+        """``IndexFlat.maxsim_ids`` of GLOBAL ``ids`` on every rank (collective): every id is routed to the shard that
+        owns it through the segment table, the other shards contribute zero bits, then ONE ``_sum_over_ranks`` of the
+        float32 bit patterns (exact: one contribution per id)."""
+        from .flat_index import maxsim_args
+
+        q, _, ids = maxsim_args(q_mat, ids=ids, what="maxsim_ids")
+        self._check_ids("maxsim_ids", ids)
+        out = np.zeros(ids.shape[0], dtype=np.float32)
+        loc = self._local_ids(ids)
+        own = np.flatnonzero(loc >= 0)
+        if own.size:
+            # (one segment: the local index adds id_base itself, so it is asked by global id)
+            out[own] = self.local.maxsim_ids(q, ids[own] if len(self.segments) == 1 else loc[own])
+        return self._sum_over_ranks(out.view(np.int32)).view(np.float32)
+
     # -- significant terms -------------------------------------------------------------------------------------
     def _exchange_counts(self, local_mask):
         """``(terms ascending, counts, rows)`` of the whole index for a mask over THIS shard's rows (``None``: every
@@ -1058,6 +1144,29 @@ class ShardedIndexFacade:
     def search_hybrid_sparse(self, q, terms, weights, k: int, alpha: float, normalize: bool = False, allow=None):
         return self.sh.search_hybrid_sparse(np.asarray(q, dtype=np.float32), terms, weights, int(k), float(alpha),
                                             normalize=normalize, allow=allow)
+
+    def set_tokens(self, mats, keep=None, row0: Optional[int] = None) -> None:
+        self.sh.set_tokens(mats, keep=keep, row0=row0)
+
+    def get_tokens(self, row0: int = 0, n: Optional[int] = None):
+        return self.sh.get_tokens(row0, n)
+
+    @property
+    def token_rows(self) -> int:
+        return self.sh.token_rows
+
+    @property
+    def token_dim(self) -> int:
+        return self.sh.token_dim
+
+    def drop_tokens(self) -> None:
+        self.sh.drop_tokens()
+
+    def search_maxsim(self, q_mat, k: int, allow=None):
+        return self.sh.search_maxsim(q_mat, int(k), allow=allow)
+
+    def maxsim_ids(self, q_mat, ids) -> np.ndarray:
+        return self.sh.maxsim_ids(q_mat, ids)
 
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
         return self.sh.search_diverse(np.asarray(q, dtype=np.float32), int(k), lam=lam, fetch=fetch, normalize=normalize,

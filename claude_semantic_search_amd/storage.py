@@ -357,6 +357,10 @@ class HybridStorage:
         self._live_cache: Optional[Tuple[Any, np.ndarray]] = None
         self._sparse_model: Optional[str] = None
         self._sparse_saved: Optional[Tuple[Optional[str], int, int]] = None
+        # index_tokens / search_late: the same three for the chunks' token matrices (late interaction)
+        self._tokens = _Synced()
+        self._tokens_model: Optional[str] = None
+        self._tokens_saved: Optional[Tuple[Optional[str], int, int]] = None
         # search_sessions: dense group labels per session_id (order of first appearance by faiss_id)
         self._session_labels: Dict[str, int] = {}
         # search_recent: the half-life and reference time (days since the epoch) the priors are stored for; the newest
@@ -446,6 +450,7 @@ class HybridStorage:
         row = self.db.execute("SELECT value FROM storage_meta WHERE key = 'pending_compact'").fetchone()
         if row is not None:
             self._drop_sparse_file()   # (the sparse vectors beside the index speak the old numbering)
+            self._drop_tokens_file()   # (and so do the token matrices)
             if compact.exists():
                 os.replace(str(compact), str(self.index_path))
                 _fsync_dir(self.index_path.parent)
@@ -469,6 +474,7 @@ class HybridStorage:
             self.logger.info(f"Loaded flat index with {loaded.ntotal} vectors")
             self._rebuild_id_mappings()
             self._load_sparse()
+            self._load_tokens()
             bad = [i for i in self.faiss_id_to_chunk_id if i >= loaded.ntotal]
             if bad:   # e.g. a crash before the last save with auto_save off: those chunks have no vector on file
                 self.logger.warning(f"{len(bad)} chunks refer to rows beyond the {loaded.ntotal} rows of the index file; "
@@ -1241,6 +1247,119 @@ class HybridStorage:
 
         return self._ranked_in_index(query_embedding, config, filters, fi.MAX_HYBRID_K, run)
 
+    # ------------------------------------------------------- token matrices (late interaction)
+    @property
+    def tokens_path(self) -> Path:
+        """The file beside the index file that holds the chunks' token matrices."""
+        return Path(str(self.index_path) + ".tokens.npz")
+
+    def _drop_tokens_file(self) -> None:
+        self._tokens_saved = None
+        if self.tokens_path.exists():
+            self.tokens_path.unlink()
+
+    def _save_tokens(self, ntotal: int) -> None:
+        """``save_index``'s third file, in the shape of ``_save_sparse``: ``offsets``, the uint16 ``tokens``, ``P``, the
+        rows that have a matrix and the model's name, as one ``.npz``, written whole through a temporary sibling.
+        Skipped while the file already says the same; nothing is written for an index that carries no matrices."""
+        ix = self.faiss_index
+        rows = self._tokens.rows if self._tokens.index is ix else 0
+        if rows <= 0 or not hasattr(ix, "get_tokens"):
+            return
+        state = (self._tokens_model, rows, ntotal)
+        if state == self._tokens_saved and self.tokens_path.exists():
+            return
+        off, tok = ix.get_tokens(0, ntotal)
+        tmp = str(self.tokens_path) + ".tmp.npz"
+        np.savez(tmp, offsets=off, tokens=tok, P=np.int64(tok.shape[1]), rows=np.int64(rows), model=np.array(self._tokens_model or ""))
+        os.replace(tmp, str(self.tokens_path))
+        _fsync_dir(self.tokens_path.parent)
+        self._tokens_saved = state
+
+    def _load_tokens(self) -> None:
+        """The matrices of ``_save_tokens`` back into a freshly loaded index, when the file is there and speaks of as
+        many rows as the index has; otherwise nothing, and ``index_tokens`` encodes lazily."""
+        ix = self.faiss_index
+        if not self.tokens_path.exists() or not hasattr(ix, "set_tokens"):
+            return
+        try:
+            with np.load(str(self.tokens_path)) as z:
+                off, tok = z["offsets"], z["tokens"]
+                P, rows, model = int(z["P"]), int(z["rows"]), str(z["model"])
+            if off.shape[0] - 1 != ix.ntotal or not 0 < rows <= ix.ntotal:
+                self.logger.warning(f"{self.tokens_path.name} speaks of {off.shape[0] - 1} rows, the index has {ix.ntotal}: ignored")
+                return
+            ix.set_tokens((np.ascontiguousarray(off[:rows + 1]), tok[:int(off[rows])], P), row0=0)
+        except Exception as e:  # a corrupt or foreign file: the lazy sync encodes again
+            self.logger.warning(f"Could not load the token matrices: {e}")
+            return
+        self._tokens.index, self._tokens.rows = ix, rows
+        self._tokens_model = model or None
+        self._tokens_saved = (self._tokens_model, rows, ix.ntotal)
+        self.logger.info(f"Loaded the token matrices of {rows} rows")
+
+    def _sync_tokens(self, ntotal: int, late, batch_size: int = 32) -> int:
+        """Bring the index's token matrices up to date with SQLite, in the shape of ``_sync_sparse``: row =
+        ``faiss_id``, matrix = ``late.encode_documents`` of the chunk's stored text with the skiplist's tokens dropped;
+        a row without a live chunk gets the empty matrix.  Only the tail ``[synced, ntotal)`` is encoded after adds;
+        everything again when the index object was replaced or the matrices came from another model.  Returns the
+        number of texts encoded."""
+        P = int(late.token_dim)
+        if P % 32 or not 32 <= P <= 128:
+            raise ValueError(f"index_tokens: the model's token vectors have P={P}; the index stores a multiple of 32 in "
+                             "[32, 128] (a checkpoint with a token projection)")
+        name = self._sparse_model_name(late)
+        lo = self._tokens.rows_of(self.faiss_index)
+        if lo > 0 and self._tokens_model != name:
+            lo = 0
+        if lo >= ntotal:
+            return 0
+        rows = self.db.cursor().execute("SELECT faiss_id, text FROM chunks WHERE faiss_id >= ? AND faiss_id < ? ORDER BY faiss_id",
+                                        (lo, ntotal)).fetchall()
+        rows = [(fid, text) for fid, text in rows if self.faiss_id_to_chunk_id.get(fid) is not None]
+        mats: List[Any] = [np.zeros((0, P), np.uint16)] * (ntotal - lo)
+        keep: List[Any] = [None] * (ntotal - lo)
+        if rows:
+            encoded, flags = late.encode_documents([text or "" for _, text in rows], batch_size=batch_size)
+            for n, (fid, _) in enumerate(rows):
+                mats[fid - lo] = encoded[n]
+                keep[fid - lo] = flags[n] if flags is not None else None
+        self.faiss_index.set_tokens(mats, keep=keep, row0=lo)
+        self._tokens.rows, self._tokens_model = ntotal, name
+        return len(rows)
+
+    def index_tokens(self, late, batch_size: int = 32) -> int:
+        """Give every live chunk that has none yet a token matrix (``LateInteraction.encode_documents`` of its stored
+        text, kept tokens only, stored in the index by ``IndexFlat.set_tokens``); tombstones get the empty matrix.
+        Lazy: only rows added since the last call are encoded, and ``search_late`` / ``search_late_reranked`` call it
+        themselves.  ``save_index`` writes the matrices beside the index file and ``initialize`` loads them again, so a
+        corpus is not encoded on every load.  Returns the number of texts encoded."""
+        self._require("token matrices", "set_tokens", "search_maxsim")
+        with self._lock:
+            frame = self._search_frame(SearchConfig())
+            if frame is None:
+                return 0
+            done = self._sync_tokens(frame[1], late, batch_size)
+            if done and self.config.auto_save:
+                self._save_tokens(frame[1])
+            return done
+
+    def search_late(self, query_text: str, late, config: Optional[SearchConfig] = None,
+                    filters: Optional[Dict[str, Any]] = None) -> List[SearchResult]:
+        """Late interaction as a FIRST stage: ``top_k`` chunks ranked by MaxSim of the query's token matrix
+        (``late.encode_queries``) with the chunks' stored matrices, over ALL allowed rows inside the index
+        (``IndexFlat.search_maxsim``); no dense row is read, no query embedding is needed and no text goes through the
+        encoder again.  Each result's ``similarity`` is the MaxSim score, to which ``similarity_threshold`` applies.
+        Tombstones and filters as in ``search_sparse``."""
+        self._require("late-interaction search", "set_tokens", "search_maxsim")
+
+        def run(q, k, allow, ntotal, cfg):
+            self._sync_tokens(ntotal, late)
+            q_mat = late.encode_queries([query_text or ""])[0][0]
+            return self.faiss_index.search_maxsim(q_mat, k, allow=allow)
+
+        return self._ranked_in_index(None, config, filters, fi.MAX_HYBRID_K, run)
+
     def search_reranked(self, query_text: str, query_embedding, reranker, config: Optional[SearchConfig] = None,
                         filters: Optional[Dict[str, Any]] = None, fetch: int = 50) -> List[Reranked]:
         """Retrieve, then re-read: the ordinary ``search`` for ``max(fetch, top_k)`` hits, each ``(query_text, chunk
@@ -1271,6 +1390,30 @@ class HybridStorage:
                 h.text, h.chunk = None, None
             out.append(Reranked(h, float(scores[i]), int(i)))
         return out
+
+    def search_late_reranked(self, query_text: str, query_embedding, late, config: Optional[SearchConfig] = None,
+                             filters: Optional[Dict[str, Any]] = None, fetch: int = 50) -> List[Reranked]:
+        """``search_reranked(reranker=late)`` WITHOUT a text forward pass: the ordinary ``search`` for ``max(fetch,
+        top_k)`` hits, then the MaxSim of the query's token matrix with the hits' STORED matrices
+        (``IndexFlat.maxsim_ids``), and the ``top_k`` best by that score, best first; ties keep the plain search's
+        order.  The result is that of ``search_reranked`` with a ``LateInteraction``, order and score bits, because the
+        stored matrices are the ones the forward pass would form again.  A hit without a kept token scores ``-inf``."""
+        self._require("late-interaction re-ranking", "set_tokens", "maxsim_ids")
+        cfg = config or SearchConfig()
+        if cfg.top_k <= 0:
+            return []
+        n = max(int(fetch), cfg.top_k)
+        wide = SearchConfig(top_k=n, similarity_threshold=cfg.similarity_threshold, include_metadata=cfg.include_metadata,
+                            include_text=cfg.include_text, max_results=max(cfg.max_results, n))
+        with self._lock:
+            hits = self.search(query_embedding, wide, filters)
+            if not hits:
+                return []
+            self._sync_tokens(self.faiss_index.ntotal, late)
+            q_mat = late.encode_queries([query_text or ""])[0][0]
+            ids = np.asarray([self.chunk_id_to_faiss_id[h.chunk_id] for h in hits], dtype=np.int64)
+            scores = np.asarray(self.faiss_index.maxsim_ids(q_mat, ids), dtype=np.float32).reshape(-1)
+        return [Reranked(hits[int(i)], float(scores[i]), int(i)) for i in np.argsort(-scores, kind="stable")[:cfg.top_k]]
 
     @staticmethod
     def _make_result(chunk_id: str, score: float, data: Dict[str, Any], cfg: SearchConfig) -> SearchResult:
@@ -1620,6 +1763,7 @@ class HybridStorage:
             self.faiss_id_to_chunk_id.clear()
             self.total_chunks = 0
             self._drop_sparse_file()
+            self._drop_tokens_file()
             if self.config.auto_save:
                 self.save_index()
         self.logger.info("Cleared all data from storage")
@@ -1658,6 +1802,7 @@ class HybridStorage:
                 self._write_index_atomically(ix, path)
             self._saved_rows = n
             self._save_sparse(n)
+            self._save_tokens(n)
         self.logger.info(f"Saved flat index ({n} vectors) to {self.index_path}")
 
     def _crash_point(self, where: str) -> None:
@@ -1761,6 +1906,7 @@ class HybridStorage:
             self.db.commit()
             self._crash_point("compaction committed, file not yet moved")
             self._drop_sparse_file()            # (it speaks the old numbering)
+            self._drop_tokens_file()
             os.replace(compact, str(self.index_path))
             _fsync_dir(self.index_path.parent)
             cur.execute("DELETE FROM storage_meta WHERE key = 'pending_compact'")
@@ -1784,8 +1930,13 @@ class HybridStorage:
                 self._sparse.rows = int(old.sparse_rows)
             else:
                 self._sparse = _Synced()
+            if in_place and self._tokens.index is old and hasattr(old, "token_rows"):   # (and its token matrices)
+                self._tokens.rows = int(old.token_rows)
+            else:
+                self._tokens = _Synced()
             if self.config.auto_save:
                 self._save_sparse(self.faiss_index.ntotal)
+                self._save_tokens(self.faiss_index.ntotal)
             if not in_place:
                 old.close()
         self.logger.info("Flat index rebuilt")

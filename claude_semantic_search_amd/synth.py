@@ -105,6 +105,34 @@ def sparse_vectors(n: int, seed: int, vocab: int = TERM_VOCAB, lattice: bool = F
     return off, (key & 0xFFFFFFFF).astype(np.uint32), w
 
 
+TOKEN_EDGE_LENGTHS = (0, 1, 15, 16, 17, 63, 64, 65, 512)
+
+
+def token_matrices(n: int, P: int, seed: int, lattice=False, max_len: int = 40):
+    """Synthetic per-row token matrices, as CSR ``(offsets int64 [n + 1] in tokens, tokens uint16 [E, P] of bf16 bits,
+    P)``: row lengths ``integers(0, max_len + 1)`` from ``numpy.random.default_rng(seed)`` with the first rows forced
+    to ``TOKEN_EDGE_LENGTHS`` (empty, one token, around the 16-token tile and its multiples, the longest row the index
+    takes), then Gaussian rows scaled to unit length and rounded to bf16.  ``lattice``: the components are ``{-8 .. 8}
+    / 8`` instead (``True`` or ``"E"``) or ``{-1, 0, 1}`` (``"T"``), exact in bf16, so that every dot product and every
+    MaxSim sum is exact in fp32."""
+    rng = np.random.default_rng(seed)
+    lens = rng.integers(0, max_len + 1, size=n)
+    edge = np.asarray(TOKEN_EDGE_LENGTHS[:n], dtype=lens.dtype)
+    lens[:edge.shape[0]] = edge
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    E = int(off[-1])
+    if lattice == "T":
+        x = rng.integers(-1, 2, size=(E, P)).astype(np.float32)
+    elif lattice:
+        x = (rng.integers(-8, 9, size=(E, P)) / 8.0).astype(np.float32)
+    else:
+        x = rng.standard_normal((E, P))
+        x = (x / np.maximum(np.linalg.norm(x, axis=1, keepdims=True), 1e-30)).astype(np.float32)
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    return off, ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16), int(P)
+
+
 def query_terms(j: int, count: int = 4, vocab: int = TERM_VOCAB) -> np.ndarray:
     """The distinct values, in order of first occurrence, of ``floor(vocab * default_rng(500 + j).random(count)^3)``."""
     t = np.floor(vocab * np.random.default_rng(500 + j).random(count) ** 3).astype(np.int64)

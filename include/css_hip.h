@@ -447,6 +447,65 @@ int css_index_search_hybrid_sparse(css_index* ix, const float* q_host /* [dim] *
                                    const uint32_t* allow_bits_host, float* D_host, int64_t* I_host,
                                    float* S_host /* may be NULL */, float* L_host /* may be NULL */);
 
+/* Per-row token matrices and MaxSim search (late interaction as a FIRST stage and as a re-rank stage without a forward
+ * pass: brute-force ColBERT, Vespa and Qdrant multi-vector, PyLate's index).  A row may carry a matrix of m token
+ * vectors of P bf16 components each, such as css_encoder_forward_tokens produces; a query is such a matrix too.  A third
+ * per-row list kind, independent of the term lists and the sparse vectors above: an index may carry any of them.
+ *  - Matrices.  P is a multiple of 32 in [32, CSS_MAX_TOKEN_DIM]; the first call fixes it, a later call with another P
+ *    is CSS_ERR_INVALID unless it rewrites from row0 == 0 (a call without rows only truncates: its P is not looked
+ *    at).  At most CSS_MAX_ROW_TOKEN_VECTORS tokens per row; empty rows are
+ *    allowed (a tombstone, a text whose every token was on the skiplist).  ColBERT's keep flags are applied BEFORE
+ *    storing: a dropped token is not stored, and there are no flags here.  css_index_set_tokens takes rows
+ *    [row0, row0 + n) as CSR (offsets_host [n + 1] from 0, in tokens; tok_host bf16 [offsets[n], P]) under the
+ *    APPEND-ONLY rules of css_index_set_sparse: with T the leading rows that have matrices, row0 == T appends,
+ *    row0 < T first drops the matrices of ALL rows >= row0, row0 > T and a range outside [0, ntotal) are
+ *    CSS_ERR_INVALID.  Offsets that do not start at 0 or that decrease, a row of too many tokens and a NaN or infinite
+ *    component are CSS_ERR_INVALID; the message names the row; all of it is checked before anything is written.
+ *    css_index_get_tokens reads rows [row0, row0 + n) back: offsets_out [n + 1] from 0, then the tokens (tok_out may be
+ *    NULL: a first call sizes the second).  css_index_token_rows gives T, css_index_token_dim gives P (0 while T == 0),
+ *    css_index_drop_tokens drops the matrices and frees their memory.
+ *  - Storage.  Nothing is allocated before the first css_index_set_tokens.  Then 2 P bytes per token and 8 per row
+ *    with a matrix, the row offsets mirrored on the host.  The matrices follow the rows: kept through capacity growth,
+ *    none for appended rows, forgotten by css_index_reset, compacted by css_index_remove_rows with the same keep bits --
+ *    afterwards css_index_get_tokens equals that of a fresh index built from the kept rows.
+ *  - The score.  For a query q [mq, P] bf16, 1 <= mq <= CSS_MAX_QUERY_TOKENS, finite components, and a row with
+ *    md >= 1 stored tokens d_t:
+ *        score = sum over s = 0 .. mq-1 (ascending, fp32) of  max over t of  dot(q_s, d_t)
+ *    with bf16 operands and fp32 accumulation on v_mfma_f32_16x16x32_bf16, K steps of 32 in ascending order: exactly
+ *    the value css_encoder_maxsim returns for the same bf16 rows with every token kept, bit for bit (the kernel keeps
+ *    that kernel's operand roles and lane-to-k mapping), whatever the grid and whatever the shard.  A row >= T, an
+ *    empty row and a masked row are a MISS: -inf in the column, never returned.
+ *  - css_index_search_maxsim.  One request per call, 1 <= k <= 128; P is the query's width and must equal
+ *    css_index_token_dim (any valid P while the index has no matrices).  The k best rows that are not a miss among the
+ *    allowed rows (allow_bits_host as in css_index_search_masked; a masked row is skipped before any of its tokens is
+ *    read), ranked by the score ALONE: larger is better on an index of either metric, ties to the lower id.
+ *    D = score, I = global ids.  Fewer than k hits, an index without matrices or an empty index give padding: I = -1,
+ *    D = -FLT_MAX.  On the device: k_tok_scores (2 P bytes per token of an allowed row read, 4 per row written),
+ *    k_sparse_topk over slices of the column, the part merge.  No dense row is read.  One upload, one wait; a search
+ *    never edits the index.
+ *  - css_index_maxsim_rows.  The scores of the n <= CSS_MAX_MAXSIM_ROWS named rows (global ids, any order, repeats
+ *    allowed), -inf for a row that is a miss: the re-rank stage without a forward pass.  An id outside the index is
+ *    CSS_ERR_INVALID; the message names its position.  The same kernel through a row list.
+ *  - css_index_set_token_blocks sets the grid of k_tok_scores (0: the library's choice -- resident blocks x CUs, and
+ *    fewer than 16 rows per wave where the rows are few; a set grid always gives a wave 16 rows at a time), a diagnostic
+ *    knob in the family of css_index_set_range_rows: the results do not depend on it. */
+#define CSS_MAX_TOKEN_DIM 128
+#define CSS_MAX_ROW_TOKEN_VECTORS 512   /* (CSS_MAX_ROW_TOKENS is the term lists' limit) */
+#define CSS_MAX_QUERY_TOKENS 64
+#define CSS_MAX_MAXSIM_ROWS 65536
+int css_index_set_tokens(css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host /* [n+1] */,
+                         const uint16_t* tok_host /* bf16 [offsets[n], P] */, int P);
+int css_index_get_tokens(css_index* ix, int64_t row0, int64_t n, int64_t* offsets_out /* [n+1], from 0 */,
+                         uint16_t* tok_out /* may be NULL */);
+int css_index_token_rows(css_index* ix, int64_t* rows_out);
+int css_index_token_dim(css_index* ix, int* dim_out);
+int css_index_drop_tokens(css_index* ix);
+int css_index_set_token_blocks(css_index* ix, int blocks);
+int css_index_search_maxsim(css_index* ix, const uint16_t* q_tok_host /* bf16 [mq, P] */, int mq, int P, int k,
+                            const uint32_t* allow_bits_host, float* D_host /* [k] */, int64_t* I_host /* [k] */);
+int css_index_maxsim_rows(css_index* ix, const uint16_t* q_tok_host /* bf16 [mq, P] */, int mq, int P,
+                          const int64_t* ids_host /* [n] */, int64_t n, float* scores_out /* [n] */);
+
 /* Significant terms (Elasticsearch's significant_terms aggregation, the keyword side of BERTopic): which terms set a
  * selection of rows apart from a background -- "what is in this cluster / this project / these hits".  Everything is
  * read from the term lists above; the rows' values play no part.  T = the leading rows that have lists.
