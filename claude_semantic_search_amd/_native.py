@@ -184,6 +184,12 @@ PROTOTYPES = {
     "css_index_set_token_blocks": (c_int, [c_void_p, c_int]),
     "css_index_search_maxsim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "css_index_maxsim_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "css_index_set_token_codec": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "css_index_get_token_codec": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_void_p, c_void_p,
+                                          c_void_p]),
+    "css_index_token_codec_bits": (c_int, [c_void_p, POINTER(c_int)]),
+    "css_index_get_token_codes": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "css_index_set_token_codes": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "css_index_search_diverse": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
                                          c_void_p]),
     "css_index_search_diverse_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p, c_void_p,

@@ -52,6 +52,10 @@
 //   k_tok_scores       css_index_search_maxsim / css_index_maxsim_rows: the MaxSim column of one query matrix over the
 //                      per-row token matrices, bf16 MFMA with the query in registers, a persistent grid; ranked by
 //                      k_sparse_topk and the part merge (css_tokens.h).   HBM bound
+//   k_tok_scores_c,    the same column over COMPRESSED matrices (css_index_set_token_codec: centroid id + residual
+//   k_tok_encode,      buckets per token): the B fragment is decoded in registers from codes, packed buckets and a
+//   k_tok_decode       gathered centroid row; the encoder (argmax over centroids on the bf16 MFMA, buckets, packing)
+//                      and the decoder of css_index_set_tokens / _get_tokens (css_token_codec.h)
 //   k_sig_count        css_index_subset_terms / _significant_terms: +1 per list entry of the selected rows into a
 //                      uint32 table [2^24], repeats merged in a per-block LDS table first; k_sig_score and the radix
 //                      select rank the terms (css_sigterms.h)
@@ -176,6 +180,16 @@ struct css_index {
     int64_t tk_rows = 0;
     int tk_dim = 0;
     int tk_blocks = 0;
+    // the token codec (css_index_set_token_codec, css_token_codec.h): tk_bits != 0 says that the index has one.  Then
+    // the matrices are stored COMPRESSED: tk_code [ntok] and tk_res [ntok, tk_dim * tk_bits / 8] in place of tk_tok,
+    // under the same offsets.  tk_cent bf16 [tk_ncent, tk_cdim]; tk_cw fp32 [32] = cutoffs [16] | weights [16], zeros
+    // behind the used entries; the *_h vectors mirror them on the host.  The codec outlives the matrices
+    DevBuf<unsigned short> tk_cent, tk_code;
+    DevBuf<float> tk_cw;
+    DevBuf<unsigned char> tk_res;
+    std::vector<uint16_t> tk_cent_h;
+    std::vector<float> tk_cw_h;
+    int tk_bits = 0, tk_ncent = 0, tk_cdim = 0;
     hipStream_t stream = nullptr;
     int num_cus = 256;
     // reusable workspaces (DevBuf: grown on demand, freed with the index; guarded by ws_mu)
@@ -2883,6 +2897,7 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 #include "css_lexical.h"
 #include "css_sparse.h"
 #include "css_tokens.h"
+#include "css_token_codec.h"
 #include "css_where.h"
 #include "css_sigterms.h"
 
@@ -3369,6 +3384,8 @@ int drop_tokens(css_index* ix) {
     ix->tk_dim = 0;
     ix->tk_off_h.clear();
     CSS_HIP_TRY(ix->tk_tok.drop());
+    CSS_HIP_TRY(ix->tk_code.drop());   // (the codec itself stays)
+    CSS_HIP_TRY(ix->tk_res.drop());
     CSS_HIP_TRY(ix->tk_off.drop());
     return CSS_OK;
 }
@@ -3608,7 +3625,8 @@ int compact_sparse(css_index* ix, const uint32_t* keep, SparseCompaction* sc) {
 
 // The token matrices through the same keep bits, OUT OF PLACE like compact_sparse, with k_tok_move.
 struct TokenCompaction {
-    DevBuf<unsigned short> tok;
+    DevBuf<unsigned short> tok, code;   // (a compressed store: code and res in place of tok)
+    DevBuf<unsigned char> res;
     DevBuf<uint32_t> map;
     DevBuf<int64_t> off;
     std::vector<int64_t> off_h;   // (read by the copy until the caller has waited)
@@ -3616,6 +3634,8 @@ struct TokenCompaction {
     bool built = false;
     void commit(css_index* ix) {
         ix->tk_tok.swap(tok);
+        ix->tk_code.swap(code);
+        ix->tk_res.swap(res);
         ix->tk_off.swap(off);
         ix->tk_off_h.swap(off_h);
         ix->tk_rows = (int64_t)ix->tk_off_h.size() - 1;
@@ -3642,14 +3662,30 @@ int compact_tokens(css_index* ix, const uint32_t* keep, TokenCompaction* tc) {
     }
     const size_t nT = tc->off_h.size() - 1, P = (size_t)ix->tk_dim;
     int rc;
-    if ((rc = tc->tok.grow_exact(std::max<size_t>((size_t)tc->off_h.back(), 1) * P, "hipMalloc(token matrices)")) != CSS_OK) return rc;
+    const size_t nE = std::max<size_t>((size_t)tc->off_h.back(), 1), RB = P * (size_t)ix->tk_bits / 8;
+    if (ix->tk_bits) {
+        if ((rc = tc->code.grow_exact(nE, "hipMalloc(token codes)")) != CSS_OK) return rc;
+        if ((rc = tc->res.grow_exact(nE * RB, "hipMalloc(token codes)")) != CSS_OK) return rc;
+    } else if ((rc = tc->tok.grow_exact(nE * P, "hipMalloc(token matrices)")) != CSS_OK) {
+        return rc;
+    }
     if ((rc = tc->off.grow_exact(nT + 1, "hipMalloc(token matrices)")) != CSS_OK) return rc;
     if ((rc = tc->map.grow_exact((size_t)T, "hipMalloc(token matrices)")) != CSS_OK) return rc;
     CSS_HIP_TRY(hipMemcpyAsync(tc->map.p, tc->map_h.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     CSS_HIP_TRY(hipMemcpyAsync(tc->off.p, tc->off_h.data(), (nT + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_tok_move, dim3((unsigned)((T + kWaves - 1) / kWaves)), dim3(256), 0, st,
-                       reinterpret_cast<const uint4*>(ix->tk_tok.p), (const int64_t*)ix->tk_off.p, (const uint32_t*)tc->map.p,
-                       (const int64_t*)tc->off.p, T, (int)(P / 8), reinterpret_cast<uint4*>(tc->tok.p));
+    const dim3 grid((unsigned)((T + kWaves - 1) / kWaves));
+    if (ix->tk_bits) {   // the codes, 2 bytes a token, and the packed buckets, 4 to 64
+        hipLaunchKernelGGL(k_tok_move_units<unsigned short>, grid, dim3(256), 0, st, (const unsigned short*)ix->tk_code.p,
+                           (const int64_t*)ix->tk_off.p, (const uint32_t*)tc->map.p, (const int64_t*)tc->off.p, T, 1, tc->code.p);
+        CSS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_tok_move_units<uint32_t>, grid, dim3(256), 0, st, reinterpret_cast<const uint32_t*>(ix->tk_res.p),
+                           (const int64_t*)ix->tk_off.p, (const uint32_t*)tc->map.p, (const int64_t*)tc->off.p, T, (int)(RB / 4),
+                           reinterpret_cast<uint32_t*>(tc->res.p));
+    } else {
+        hipLaunchKernelGGL(k_tok_move, grid, dim3(256), 0, st, reinterpret_cast<const uint4*>(ix->tk_tok.p),
+                           (const int64_t*)ix->tk_off.p, (const uint32_t*)tc->map.p, (const int64_t*)tc->off.p, T, (int)(P / 8),
+                           reinterpret_cast<uint4*>(tc->tok.p));
+    }
     CSS_LAUNCH_CHECK();
     tc->built = true;
     return CSS_OK;
@@ -5497,34 +5533,82 @@ inline bool bf16_finite(uint16_t v) { return (v & 0x7F80u) != 0x7F80u; }
 inline bool token_dim_ok(int P) { return P >= 32 && P <= CSS_MAX_TOKEN_DIM && P % 32 == 0; }
 }  // namespace
 
-int css_index_set_tokens(css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host, const uint16_t* tok_host, int P) {
-    CSS_REQUIRE(ix, "css_index_set_tokens: NULL index");
+namespace {
+constexpr int64_t kTokCodecPass = 1 << 18;   // tokens of one staging pass of encode / decode (64 MiB of bf16 at P = 128)
+
+const void* tok_encode_kernel(int P) {
+    return P == 32 ? (const void*)k_tok_encode<32> : P == 64 ? (const void*)k_tok_encode<64> : P == 96 ? (const void*)k_tok_encode<96>
+                                                                                                        : (const void*)k_tok_encode<128>;
+}
+
+// nE raw tokens on the host -> codes and packed buckets from token E0 on, through a staging buffer that dies with the
+// call: the raw tokens never stay in HBM.  Enqueued on `st`; the caller waits before `raw` goes.
+int tok_encode_enqueue(css_index* ix, const uint16_t* tok_host, int64_t E0, int64_t nE, DevBuf<unsigned short>& raw, hipStream_t st) {
+    const size_t P = (size_t)ix->tk_dim, RB = P * (size_t)ix->tk_bits / 8;
+    int rc;
+    if ((rc = raw.grow_exact((size_t)std::min(nE, kTokCodecPass) * P, "hipMalloc(token staging)")) != CSS_OK) return rc;
+    const void* fn = tok_encode_kernel((int)P);
+    for (int64_t c0 = 0; c0 < nE; c0 += kTokCodecPass) {
+        int64_t m = std::min(kTokCodecPass, nE - c0);
+        CSS_HIP_TRY(hipMemcpyAsync(raw.p, tok_host + (size_t)c0 * P, (size_t)m * P * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        const unsigned short *tok = raw.p, *cent = ix->tk_cent.p;
+        const float* cut = ix->tk_cw.p;
+        unsigned short* codes = ix->tk_code.p + E0 + c0;
+        unsigned char* res = ix->tk_res.p + (size_t)(E0 + c0) * RB;
+        int C = ix->tk_ncent, nbits = ix->tk_bits;
+        void* args[] = {&tok, &m, &cent, &C, &nbits, &cut, &codes, &res};
+        ProfScope ps("tok_encode", st);
+        CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)((m + 64 * kWaves - 1) / (64 * kWaves))), dim3(64 * kWaves), args, 0, st));
+    }
+    return CSS_OK;
+}
+
+// css_index_set_tokens and css_index_set_token_codes: the same rows, rules and bookkeeping.  as_codes: the payload is
+// canonical (codes_host, res_host) of the index's codec, stored as it is; otherwise bf16 matrices (tok_host), stored
+// raw on an index without a codec and encoded on the device on one that has a codec.
+int set_tokens_impl(const char* fn, css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host, const uint16_t* tok_host,
+                    int P, bool as_codes, const uint16_t* codes_host, const uint8_t* res_host) {
+    CSS_REQUIRE(ix, "%s: NULL index", fn);
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     std::lock_guard<std::mutex> wl(ix->ws_mu);   // (ws_pending)
     const int64_t T0 = ix->tk_rows;
-    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_set_tokens: rows [%lld, %lld + %lld) outside [0, %lld)",
+    const int bits = ix->tk_bits;
+    if (as_codes) {
+        CSS_REQUIRE(bits != 0, "%s: the index has no token codec (css_index_set_token_codec)", fn);
+        P = ix->tk_cdim;
+    }
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "%s: rows [%lld, %lld + %lld) outside [0, %lld)", fn,
                 (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
-    CSS_REQUIRE(row0 <= T0, "css_index_set_tokens: row0=%lld beyond the %lld rows that have matrices (matrices are append-only)",
+    CSS_REQUIRE(row0 <= T0, "%s: row0=%lld beyond the %lld rows that have matrices (matrices are append-only)", fn,
                 (long long)row0, (long long)T0);
-    CSS_REQUIRE(token_dim_ok(P), "css_index_set_tokens: P=%d must be a multiple of 32 in [32, %d]", P, CSS_MAX_TOKEN_DIM);
+    CSS_REQUIRE(token_dim_ok(P), "%s: P=%d must be a multiple of 32 in [32, %d]", fn, P, CSS_MAX_TOKEN_DIM);
+    CSS_REQUIRE(bits == 0 || n == 0 || P == ix->tk_cdim, "%s: P=%d, but the index's token codec has P=%d", fn, P, ix->tk_cdim);
     CSS_REQUIRE(T0 == 0 || n == 0 || P == ix->tk_dim || row0 == 0,
-                "css_index_set_tokens: P=%d, but the stored matrices have P=%d (only a rewrite from row 0 changes it)", P, ix->tk_dim);
-    CSS_REQUIRE(n == 0 || offsets_host, "css_index_set_tokens: offsets is NULL");
+                "%s: P=%d, but the stored matrices have P=%d (only a rewrite from row 0 changes it)", fn, P, ix->tk_dim);
+    CSS_REQUIRE(n == 0 || offsets_host, "%s: offsets is NULL", fn);
     // everything is looked at before anything is written
     if (n > 0) {
-        CSS_REQUIRE(offsets_host[0] == 0, "css_index_set_tokens: offsets start at %lld, not 0", (long long)offsets_host[0]);
+        CSS_REQUIRE(offsets_host[0] == 0, "%s: offsets start at %lld, not 0", fn, (long long)offsets_host[0]);
         for (int64_t i = 0; i < n; ++i) {
             const int64_t c = offsets_host[i + 1] - offsets_host[i];
-            CSS_REQUIRE(c >= 0, "css_index_set_tokens: offsets decrease at row %lld", (long long)(row0 + i));
-            CSS_REQUIRE(c <= CSS_MAX_ROW_TOKEN_VECTORS, "css_index_set_tokens: row %lld has %lld tokens (at most %d)", (long long)(row0 + i),
+            CSS_REQUIRE(c >= 0, "%s: offsets decrease at row %lld", fn, (long long)(row0 + i));
+            CSS_REQUIRE(c <= CSS_MAX_ROW_TOKEN_VECTORS, "%s: row %lld has %lld tokens (at most %d)", fn, (long long)(row0 + i),
                         (long long)c, CSS_MAX_ROW_TOKEN_VECTORS);
         }
-        CSS_REQUIRE(offsets_host[n] == 0 || tok_host, "css_index_set_tokens: tokens is NULL");
-        for (int64_t i = 0; i < n; ++i)
-            for (int64_t e = offsets_host[i] * P; e < offsets_host[i + 1] * P; ++e)
-                CSS_REQUIRE(bf16_finite(tok_host[e]), "css_index_set_tokens: component %lld of token %lld of row %lld is %s",
-                            (long long)(e % P), (long long)(e / P - offsets_host[i]), (long long)(row0 + i),
-                            (tok_host[e] & 0x7Fu) ? "NaN" : "infinite");
+        if (as_codes) {
+            CSS_REQUIRE(offsets_host[n] == 0 || (codes_host && res_host), "%s: codes or res is NULL", fn);
+            for (int64_t i = 0; i < n; ++i)
+                for (int64_t e = offsets_host[i]; e < offsets_host[i + 1]; ++e)
+                    CSS_REQUIRE((int)codes_host[e] < ix->tk_ncent, "%s: token %lld of row %lld has code %d, the codec has %d centroids",
+                                fn, (long long)(e - offsets_host[i]), (long long)(row0 + i), (int)codes_host[e], ix->tk_ncent);
+        } else {
+            CSS_REQUIRE(offsets_host[n] == 0 || tok_host, "%s: tokens is NULL", fn);
+            for (int64_t i = 0; i < n; ++i)
+                for (int64_t e = offsets_host[i] * P; e < offsets_host[i + 1] * P; ++e)
+                    CSS_REQUIRE(bf16_finite(tok_host[e]), "%s: component %lld of token %lld of row %lld is %s", fn,
+                                (long long)(e % P), (long long)(e / P - offsets_host[i]), (long long)(row0 + i),
+                                (tok_host[e] & 0x7Fu) ? "NaN" : "infinite");
+        }
     }
     if (n == 0 && row0 == T0) return CSS_OK;
     const int64_t E0 = T0 > 0 ? ix->tk_off_h[(size_t)row0] : 0;
@@ -5535,7 +5619,7 @@ int css_index_set_tokens(css_index* ix, int64_t row0, int64_t n, const int64_t* 
         for (int64_t i = 0; i <= n; ++i) off[(size_t)i] = E0 + (n > 0 ? offsets_host[i] : 0);
         ix->tk_off_h.reserve((size_t)(row0 + n) + 1);
     } catch (const std::bad_alloc&) {
-        css::set_error("css_index_set_tokens: out of host memory");
+        css::set_error("%s: out of host memory", fn);
         return CSS_ERR_OOM;
     }
     DeviceGuard g(ix->device);
@@ -5549,12 +5633,31 @@ int css_index_set_tokens(css_index* ix, int64_t row0, int64_t n, const int64_t* 
         ix->tk_off_h.resize((size_t)row0 + 1);
         ix->tk_rows = row0;
     }
+    DevBuf<unsigned short> raw;   // (encode's staging: read until the wait below)
     if (n > 0) {
         ix->tk_dim = P;   // (another P only from row 0: nothing of the old width is left)
-        const size_t sP = (size_t)P;
-        if ((rc = grow_keep(ix, ix->tk_tok, (size_t)E0 * sP, ((size_t)E0 + std::max<size_t>((size_t)nE, 1)) * sP, "hipMalloc(token matrices)")) != CSS_OK) return rc;
+        const size_t sP = (size_t)P, sE0 = (size_t)E0, sE1 = sE0 + std::max<size_t>((size_t)nE, 1);
+        if (bits == 0) {
+            if ((rc = grow_keep(ix, ix->tk_tok, sE0 * sP, sE1 * sP, "hipMalloc(token matrices)")) != CSS_OK) return rc;
+        } else {
+            const size_t RB = sP * (size_t)bits / 8;
+            if ((rc = grow_keep(ix, ix->tk_code, sE0, sE1, "hipMalloc(token codes)")) != CSS_OK) return rc;
+            if ((rc = grow_keep(ix, ix->tk_res, sE0 * RB, sE1 * RB, "hipMalloc(token codes)")) != CSS_OK) return rc;
+        }
         if ((rc = grow_keep(ix, ix->tk_off, (size_t)row0 + 1, (size_t)(row0 + n) + 1, "hipMalloc(token matrices)")) != CSS_OK) return rc;
-        if (nE) CSS_HIP_TRY(hipMemcpyAsync(ix->tk_tok.p + (size_t)E0 * sP, tok_host, (size_t)nE * sP * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        if (nE && bits == 0) {
+            CSS_HIP_TRY(hipMemcpyAsync(ix->tk_tok.p + sE0 * sP, tok_host, (size_t)nE * sP * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        } else if (nE && as_codes) {
+            const size_t RB = sP * (size_t)bits / 8;
+            CSS_HIP_TRY(hipMemcpyAsync(ix->tk_code.p + sE0, codes_host, (size_t)nE * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+            CSS_HIP_TRY(hipMemcpyAsync(ix->tk_res.p + sE0 * RB, res_host, (size_t)nE * RB, hipMemcpyHostToDevice, st));
+        } else if (nE) {
+            rc = tok_encode_enqueue(ix, tok_host, E0, nE, raw, st);
+            if (rc != CSS_OK) {
+                (void)hipStreamSynchronize(st);
+                return rc;
+            }
+        }
         CSS_HIP_TRY(hipMemcpyAsync(ix->tk_off.p + row0, off.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     }
     CSS_HIP_TRY(hipStreamSynchronize(st));   // (the copies read this call's matrices)
@@ -5563,23 +5666,167 @@ int css_index_set_tokens(css_index* ix, int64_t row0, int64_t n, const int64_t* 
     return CSS_OK;
 }
 
+// the rows of [row0, row0 + n) that have matrices as offsets from 0; *E0 = their first token, the return their count
+int64_t token_range(const css_index* ix, int64_t row0, int64_t n, int64_t* offsets_out, int64_t* E0) {
+    const int64_t T = ix->tk_rows;
+    const int64_t a = std::min(row0, T);
+    *E0 = T > 0 ? ix->tk_off_h[(size_t)a] : 0;
+    for (int64_t i = 0; i <= n; ++i) offsets_out[i] = T > 0 ? ix->tk_off_h[(size_t)std::min(row0 + i, T)] - *E0 : 0;
+    return offsets_out[n];
+}
+}  // namespace
+
+int css_index_set_tokens(css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host, const uint16_t* tok_host, int P) {
+    return set_tokens_impl("css_index_set_tokens", ix, row0, n, offsets_host, tok_host, P, false, nullptr, nullptr);
+}
+
+int css_index_set_token_codes(css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host, const uint16_t* codes_host,
+                              const uint8_t* res_host) {
+    return set_tokens_impl("css_index_set_token_codes", ix, row0, n, offsets_host, nullptr, 0, true, codes_host, res_host);
+}
+
 int css_index_get_tokens(css_index* ix, int64_t row0, int64_t n, int64_t* offsets_out, uint16_t* tok_out) {
     CSS_REQUIRE(ix, "css_index_get_tokens: NULL index");
     std::shared_lock<std::shared_mutex> lk(ix->mu);
     CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_get_tokens: rows [%lld, %lld + %lld) outside [0, %lld)",
                 (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
     CSS_REQUIRE(offsets_out, "css_index_get_tokens: offsets_out is NULL");
-    const int64_t T = ix->tk_rows;
-    const int64_t a = std::min(row0, T), e = std::min(row0 + n, T);   // the rows of the range that have matrices
-    const int64_t E0 = T > 0 ? ix->tk_off_h[(size_t)a] : 0;
-    for (int64_t i = 0; i <= n; ++i) offsets_out[i] = T > 0 ? ix->tk_off_h[(size_t)std::min(row0 + i, T)] - E0 : 0;
-    const int64_t nE = offsets_out[n];
-    if (e <= a || nE == 0 || !tok_out) return CSS_OK;
+    int64_t E0;
+    const int64_t nE = token_range(ix, row0, n, offsets_out, &E0);
+    if (nE == 0 || !tok_out) return CSS_OK;
     DeviceGuard g(ix->device);
     const size_t P = (size_t)ix->tk_dim;
-    CSS_HIP_TRY(hipMemcpy(tok_out, ix->tk_tok.p + (size_t)E0 * P, (size_t)nE * P * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    if (ix->tk_bits == 0) {
+        CSS_HIP_TRY(hipMemcpy(tok_out, ix->tk_tok.p + (size_t)E0 * P, (size_t)nE * P * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        return CSS_OK;
+    }
+    // a compressed store: the DECODED matrices, through a staging buffer of this call
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    const hipStream_t st = ix->stream;
+    const size_t RB = P * (size_t)ix->tk_bits / 8;
+    DevBuf<unsigned short> raw;
+    int rc;
+    if ((rc = raw.grow_exact((size_t)std::min(nE, kTokCodecPass) * P, "hipMalloc(token staging)")) != CSS_OK) return rc;
+    for (int64_t c0 = 0; c0 < nE; c0 += kTokCodecPass) {
+        const int64_t m = std::min(kTokCodecPass, nE - c0);
+        const int64_t threads = m * (int64_t)(P / 8);
+        hipLaunchKernelGGL(k_tok_decode, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st,
+                           (const unsigned short*)ix->tk_code.p + E0 + c0, (const unsigned char*)ix->tk_res.p + (size_t)(E0 + c0) * RB, m,
+                           (const unsigned short*)ix->tk_cent.p, (int)P, ix->tk_bits, (const float*)ix->tk_cw.p + 16, raw.p);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(tok_out + (size_t)c0 * P, raw.p, (size_t)m * P * sizeof(uint16_t), hipMemcpyDeviceToHost, st);
+        const hipError_t e2 = hipStreamSynchronize(st);   // (also after a failure: the copy writes this call's memory)
+        CSS_HIP_TRY(e);
+        CSS_HIP_TRY(e2);
+    }
     return CSS_OK;
 }
+
+int css_index_get_token_codes(css_index* ix, int64_t row0, int64_t n, int64_t* offsets_out, uint16_t* codes_out, uint8_t* res_out) {
+    CSS_REQUIRE(ix, "css_index_get_token_codes: NULL index");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    CSS_REQUIRE(ix->tk_bits != 0, "css_index_get_token_codes: the index has no token codec (css_index_set_token_codec)");
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && n <= ix->ntotal - row0, "css_index_get_token_codes: rows [%lld, %lld + %lld) outside [0, %lld)",
+                (long long)row0, (long long)row0, (long long)n, (long long)ix->ntotal);
+    CSS_REQUIRE(offsets_out, "css_index_get_token_codes: offsets_out is NULL");
+    int64_t E0;
+    const int64_t nE = token_range(ix, row0, n, offsets_out, &E0);
+    if (nE == 0 || (!codes_out && !res_out)) return CSS_OK;
+    DeviceGuard g(ix->device);
+    const size_t RB = (size_t)ix->tk_dim * (size_t)ix->tk_bits / 8;
+    if (codes_out) CSS_HIP_TRY(hipMemcpy(codes_out, ix->tk_code.p + E0, (size_t)nE * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    if (res_out) CSS_HIP_TRY(hipMemcpy(res_out, ix->tk_res.p + (size_t)E0 * RB, (size_t)nE * RB, hipMemcpyDeviceToHost));
+    return CSS_OK;
+}
+
+int css_index_set_token_codec(css_index* ix, const float* centroids_host, int C, int P, int nbits, const float* cutoffs_host,
+                              const float* weights_host) {
+    CSS_REQUIRE(ix, "css_index_set_token_codec: NULL index");
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    CSS_REQUIRE(ix->tk_rows == 0, "css_index_set_token_codec: %lld rows have token matrices (the codec changes only while there are none)",
+                (long long)ix->tk_rows);
+    std::vector<uint16_t> cent_h;
+    std::vector<float> cw_h;
+    if (centroids_host) {   // everything is checked before anything is allocated
+        CSS_REQUIRE(C >= 1 && C <= CSS_MAX_TOKEN_CENTROIDS, "css_index_set_token_codec: C=%d outside [1, %d]", C, CSS_MAX_TOKEN_CENTROIDS);
+        CSS_REQUIRE(token_dim_ok(P), "css_index_set_token_codec: P=%d must be a multiple of 32 in [32, %d]", P, CSS_MAX_TOKEN_DIM);
+        CSS_REQUIRE(nbits == 1 || nbits == 2 || nbits == 4, "css_index_set_token_codec: nbits=%d is none of 1, 2, 4", nbits);
+        CSS_REQUIRE(cutoffs_host && weights_host, "css_index_set_token_codec: cutoffs or weights is NULL");
+        const int nw = 1 << nbits;
+        for (int i = 0; i < nw - 1; ++i) {
+            CSS_REQUIRE(std::isfinite(cutoffs_host[i]), "css_index_set_token_codec: cutoff %d is not finite", i);
+            CSS_REQUIRE(i == 0 || cutoffs_host[i - 1] < cutoffs_host[i], "css_index_set_token_codec: cutoff %d does not ascend", i);
+        }
+        for (int i = 0; i < nw; ++i) CSS_REQUIRE(std::isfinite(weights_host[i]), "css_index_set_token_codec: weight %d is not finite", i);
+        try {
+            cent_h.resize((size_t)C * P);
+            cw_h.assign(32, 0.f);
+        } catch (const std::bad_alloc&) {
+            css::set_error("css_index_set_token_codec: out of host memory");
+            return CSS_ERR_OOM;
+        }
+        for (size_t e = 0; e < (size_t)C * P; ++e) {
+            uint32_t u;
+            memcpy(&u, centroids_host + e, sizeof u);
+            CSS_REQUIRE((u & 0xFFFFu) == 0, "css_index_set_token_codec: component %d of centroid %d is not a bf16 value (round it first)",
+                        (int)(e % P), (int)(e / P));
+            CSS_REQUIRE(bf16_finite((uint16_t)(u >> 16)), "css_index_set_token_codec: component %d of centroid %d is %s", (int)(e % P),
+                        (int)(e / P), (u & 0x7F0000u) ? "NaN" : "infinite");
+            cent_h[e] = (uint16_t)(u >> 16);
+        }
+        std::copy(cutoffs_host, cutoffs_host + nw - 1, cw_h.begin());
+        std::copy(weights_host, weights_host + nw, cw_h.begin() + 16);
+    }
+    DeviceGuard g(ix->device);
+    if (ix->ws_pending) CSS_HIP_TRY(hipEventSynchronize(ix->ws_ev));
+    CSS_HIP_TRY(hipStreamSynchronize(ix->stream));
+    DevBuf<unsigned short> cent;
+    DevBuf<float> cw;
+    int rc;
+    if (centroids_host) {
+        if ((rc = cent.grow_exact(cent_h.size(), "hipMalloc(token codec)")) != CSS_OK) return rc;
+        if ((rc = cw.grow_exact(cw_h.size(), "hipMalloc(token codec)")) != CSS_OK) return rc;
+        CSS_HIP_TRY(hipMemcpy(cent.p, cent_h.data(), cent_h.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        CSS_HIP_TRY(hipMemcpy(cw.p, cw_h.data(), cw_h.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if ((rc = drop_tokens(ix)) != CSS_OK) return rc;   // (no rows; buffers of the other storage form may be left)
+    ix->tk_cent.swap(cent);
+    ix->tk_cw.swap(cw);
+    ix->tk_cent_h.swap(cent_h);
+    ix->tk_cw_h.swap(cw_h);
+    ix->tk_bits = centroids_host ? nbits : 0;
+    ix->tk_ncent = centroids_host ? C : 0;
+    ix->tk_cdim = centroids_host ? P : 0;
+    return CSS_OK;
+}
+
+int css_index_get_token_codec(css_index* ix, int* C_out, int* P_out, int* nbits_out, float* centroids_out, float* cutoffs_out,
+                              float* weights_out) {
+    CSS_REQUIRE(ix, "css_index_get_token_codec: NULL index");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    if (C_out) *C_out = ix->tk_ncent;
+    if (P_out) *P_out = ix->tk_cdim;
+    if (nbits_out) *nbits_out = ix->tk_bits;
+    if (ix->tk_bits == 0) return CSS_OK;
+    const int nw = 1 << ix->tk_bits;
+    if (centroids_out)
+        for (size_t e = 0; e < ix->tk_cent_h.size(); ++e) {
+            const uint32_t u = (uint32_t)ix->tk_cent_h[e] << 16;
+            memcpy(centroids_out + e, &u, sizeof u);
+        }
+    if (cutoffs_out) std::copy(ix->tk_cw_h.begin(), ix->tk_cw_h.begin() + nw - 1, cutoffs_out);
+    if (weights_out) std::copy(ix->tk_cw_h.begin() + 16, ix->tk_cw_h.begin() + 16 + nw, weights_out);
+    return CSS_OK;
+}
+
+int css_index_token_codec_bits(css_index* ix, int* bits_out) {
+    CSS_REQUIRE(ix && bits_out, "css_index_token_codec_bits: NULL argument");
+    std::shared_lock<std::shared_mutex> lk(ix->mu);
+    *bits_out = ix->tk_bits;
+    return CSS_OK;
+}
+
 
 int css_index_token_rows(css_index* ix, int64_t* rows_out) {
     CSS_REQUIRE(ix && rows_out, "css_index_token_rows: NULL argument");
@@ -5637,14 +5884,35 @@ const void* tok_scores_kernel(int MT) {
     }
 }
 
+extern "C++" template <int P, int NB>
+const void* tok_scores_c_kernel_mt(int MT) {
+    switch (MT) {
+        case 1: return (const void*)k_tok_scores_c<P, 1, NB>;
+        case 2: return (const void*)k_tok_scores_c<P, 2, NB>;
+        case 3: return (const void*)k_tok_scores_c<P, 3, NB>;
+        default: return (const void*)k_tok_scores_c<P, 4, NB>;
+    }
+}
+extern "C++" template <int P>
+const void* tok_scores_c_kernel_p(int MT, int NB) {
+    return NB == 1 ? tok_scores_c_kernel_mt<P, 1>(MT) : NB == 2 ? tok_scores_c_kernel_mt<P, 2>(MT) : tok_scores_c_kernel_mt<P, 4>(MT);
+}
+const void* tok_scores_c_kernel(int P, int MT, int NB) {
+    return P == 32 ? tok_scores_c_kernel_p<32>(MT, NB) : P == 64 ? tok_scores_c_kernel_p<64>(MT, NB)
+         : P == 96 ? tok_scores_c_kernel_p<96>(MT, NB) : tok_scores_c_kernel_p<128>(MT, NB);
+}
+
 // The MaxSim column of the query (mq tokens of the index's P on the device) over positions [0, n) into `col`: the rows
 // 0 .. n - 1 (rows == null; `mask` as in the searches) or the n rows of the list; -inf where the row is a miss.
 // n > 0 and the index has matrices.  Enqueued on `st`.
 int tok_scores_enqueue(css_index* ix, const uint32_t* rows, int64_t n, const uint32_t* mask, const unsigned short* q, int mq,
                        float* col, hipStream_t st) {
-    const int P = ix->tk_dim, MT = (mq + 15) / 16;
-    const void* fn = P == 32 ? tok_scores_kernel<32>(MT) : P == 64 ? tok_scores_kernel<64>(MT) : P == 96 ? tok_scores_kernel<96>(MT)
-                                                                                                        : tok_scores_kernel<128>(MT);
+    const int P = ix->tk_dim, MT = (mq + 15) / 16, NB = ix->tk_bits;
+    const void* fn = NB    ? tok_scores_c_kernel(P, MT, NB)
+                   : P == 32 ? tok_scores_kernel<32>(MT)
+                   : P == 64 ? tok_scores_kernel<64>(MT)
+                   : P == 96 ? tok_scores_kernel<96>(MT)
+                             : tok_scores_kernel<128>(MT);
     // The grid: as many blocks as stay resident (no block waits for another, so the figure only sets the speed), and
     // the rows of a wave's turn: 16 for a scan, fewer where that would leave waves idle.  css_index_set_token_blocks
     // fixes the grid and with it 16 rows per turn
@@ -5660,6 +5928,15 @@ int tok_scores_enqueue(css_index* ix, const uint32_t* rows, int64_t n, const uin
     const unsigned short* tok = ix->tk_tok.p;
     const int64_t* off = ix->tk_off.p;
     int64_t nlist = ix->tk_rows;
+    if (NB) {   // a compressed store: codes, packed buckets, the centroid table and the 16 weights in place of the tokens
+        const unsigned short *codes = ix->tk_code.p, *cent = ix->tk_cent.p;
+        const unsigned char* res = ix->tk_res.p;
+        const float* wts = ix->tk_cw.p + 16;
+        void* cargs[] = {&codes, &res, &cent, &wts, &off, &nlist, &rows, &n, &mask, &q, &mq, &per, &col};
+        ProfScope ps("tok_scores_c", st);
+        CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * kWaves), cargs, 0, st));
+        return CSS_OK;
+    }
     void* args[] = {&tok, &off, &nlist, &rows, &n, &mask, &q, &mq, &per, &col};
     ProfScope ps("tok_scores", st);
     CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * kWaves), args, 0, st));

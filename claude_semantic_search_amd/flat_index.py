@@ -560,6 +560,197 @@ def maxsim_args(q_mat, k=None, ids=None, what: str = "search_maxsim"):
     return q, k, ids
 
 
+MAX_TOKEN_CENTROIDS = 65536   # CSS_MAX_TOKEN_CENTROIDS
+TOKEN_CODEC_BITS = (1, 2, 4)
+
+
+class TokenCodec(NamedTuple):
+    """A codec of token matrices (``css_index_set_token_codec``): ``centroids`` float32 ``[C, P]`` of bf16 values,
+    ``nbits`` in {1, 2, 4}, ``cutoffs`` float32 ``[2^nbits - 1]`` strictly ascending, ``weights`` float32 ``[2^nbits]``."""
+    centroids: np.ndarray
+    nbits: int
+    cutoffs: np.ndarray
+    weights: np.ndarray
+
+    @property
+    def P(self) -> int:
+        return int(self.centroids.shape[1])
+
+    @property
+    def res_bytes(self) -> int:
+        """Bytes of packed buckets per token."""
+        return self.P * int(self.nbits) // 8
+
+
+def token_codec_args(centroids, nbits, cutoffs, weights, P: Optional[int] = None, what: str = "set_token_codec") -> TokenCodec:
+    """The checked codec; what the library would refuse raises ``ValueError`` here: ``nbits`` not 1, 2 or 4, ``C``
+    outside [1, 65536], a width that is no multiple of 32 in [32, 128] or differs from ``P`` (the width of the matrices
+    it is to serve), a centroid component that is NaN, infinite or no bf16 value, cutoffs that are not ``2^nbits - 1``
+    finite strictly ascending values, weights that are not ``2^nbits`` finite values."""
+    try:
+        nb = int(nbits)
+    except (TypeError, ValueError):
+        nb = -1
+    if nb not in TOKEN_CODEC_BITS or nb != nbits:
+        raise ValueError(f"{what}: nbits={nbits!r} is none of 1, 2, 4")
+    c = np.asarray(centroids)
+    if c.dtype != np.float32:
+        raise ValueError(f"{what}: the centroids must be bf16-exact float32, got dtype {c.dtype}")
+    if c.ndim != 2:
+        raise ValueError(f"{what}: the centroids have shape {c.shape}, not [C, P]")
+    if not 1 <= c.shape[0] <= MAX_TOKEN_CENTROIDS:
+        raise ValueError(f"{what}: C={c.shape[0]} outside [1, {MAX_TOKEN_CENTROIDS}]")
+    if not _token_dim_ok(c.shape[1]):
+        raise ValueError(f"{what}: P={c.shape[1]} must be a multiple of 32 in [32, {nat.MAX_TOKEN_DIM}]")
+    if P is not None and int(P) != c.shape[1]:
+        raise ValueError(f"{what}: the centroids have P={c.shape[1]}, the token matrices P={int(P)}")
+    c = np.ascontiguousarray(c)
+    if not np.isfinite(c).all():
+        raise ValueError(f"{what}: centroid {int(np.flatnonzero(~np.isfinite(c).all(axis=1))[0])} has a NaN or infinite component")
+    if (c.view(np.uint32) & 0xFFFF).any():
+        raise ValueError(f"{what}: the centroids hold float32 values that are not bf16 values (round them first)")
+    cut = np.ascontiguousarray(np.asarray(cutoffs, dtype=np.float32).reshape(-1))
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+    if cut.shape[0] != (1 << nb) - 1:
+        raise ValueError(f"{what}: {cut.shape[0]} cutoffs for nbits={nb} (need {(1 << nb) - 1})")
+    if w.shape[0] != 1 << nb:
+        raise ValueError(f"{what}: {w.shape[0]} weights for nbits={nb} (need {1 << nb})")
+    if not np.isfinite(cut).all():
+        raise ValueError(f"{what}: a cutoff is NaN or infinite")
+    if not (np.diff(cut) > 0).all():
+        raise ValueError(f"{what}: the cutoffs are not strictly ascending")
+    if not np.isfinite(w).all():
+        raise ValueError(f"{what}: a weight is NaN or infinite")
+    return TokenCodec(c, nb, cut, w)
+
+
+def bf16_to_f32(bits) -> np.ndarray:
+    """float32 values of uint16 bf16 bit patterns (exact)."""
+    return (np.asarray(bits, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
+
+
+def f32_to_bf16_rne(x) -> np.ndarray:
+    """uint16 bf16 bit patterns of finite or infinite float32 values, rounded to nearest even (``v_cvt_pk_bf16_f32``)."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+def pack_buckets(buckets, nbits: int) -> np.ndarray:
+    """Canonical packing: buckets uint8 ``[E, P]`` -> uint8 ``[E, P * nbits / 8]``; component ``j`` in bits
+    ``[nbits * (j % (8 / nbits)), +nbits)`` of byte ``j * nbits / 8``."""
+    b = np.asarray(buckets, dtype=np.uint8)
+    per = 8 // nbits
+    b = b.reshape(b.shape[0], b.shape[1] // per, per).astype(np.uint32)
+    return (b << (nbits * np.arange(per, dtype=np.uint32))).sum(axis=2).astype(np.uint8)
+
+
+def unpack_buckets(res, nbits: int) -> np.ndarray:
+    """The inverse of ``pack_buckets``: uint8 ``[E, RB]`` -> buckets uint8 ``[E, RB * 8 / nbits]``."""
+    r = np.asarray(res, dtype=np.uint8)
+    per = 8 // nbits
+    b = (r[:, :, None] >> (nbits * np.arange(per, dtype=np.uint8))) & ((1 << nbits) - 1)
+    return b.reshape(r.shape[0], r.shape[1] * per).astype(np.uint8)
+
+
+def token_codec_assign(codec: TokenCodec, tok, chunk: int = 8192) -> np.ndarray:
+    """``code = argmax_c dot(d, centroid_c)``, ties to the lower ``c``, for bf16 tokens uint16 ``[E, P]``: uint16
+    ``[E]``.  The dots are float32 sums in numpy's order -- the device's on inputs whose dots are exact, within the
+    fp32 accumulation error of it otherwise."""
+    tok = np.asarray(tok, dtype=np.uint16).reshape(-1, codec.P)
+    ct = np.ascontiguousarray(codec.centroids.T)
+    out = np.empty(tok.shape[0], dtype=np.uint16)
+    for a in range(0, tok.shape[0], chunk):
+        out[a:a + chunk] = (bf16_to_f32(tok[a:a + chunk]) @ ct).argmax(axis=1)
+    return out
+
+
+def token_codec_encode(codec: TokenCodec, tok, codes=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The numpy double of ``k_tok_encode``: ``(codes uint16 [E], res uint8 [E, P * nbits / 8])`` in the canonical
+    layout.  Given ``codes`` (the device's, say) only the residual half runs: one float32 subtraction per component and
+    ``bucket = #{i : cutoffs[i] < r}``."""
+    tok = np.asarray(tok, dtype=np.uint16).reshape(-1, codec.P)
+    codes = token_codec_assign(codec, tok) if codes is None else np.asarray(codes, dtype=np.uint16).reshape(-1)
+    r = bf16_to_f32(tok) - codec.centroids[codes]
+    buckets = np.searchsorted(codec.cutoffs, r.reshape(-1), side="left").reshape(r.shape).astype(np.uint8)
+    return codes, pack_buckets(buckets, codec.nbits).reshape(tok.shape[0], codec.res_bytes)
+
+
+def token_codec_decode(codec: TokenCodec, codes, res) -> np.ndarray:
+    """The numpy double of ``k_tok_decode``: bf16 bits uint16 ``[E, P]`` of ``bf16_rne(centroid[code] + weights[bucket])``,
+    one float32 addition and one rounding; no renormalisation."""
+    codes = np.asarray(codes, dtype=np.uint16).reshape(-1)
+    b = unpack_buckets(np.asarray(res, dtype=np.uint8).reshape(codes.shape[0], codec.res_bytes), codec.nbits)
+    return f32_to_bf16_rne(codec.centroids[codes] + codec.weights[b]).reshape(codes.shape[0], codec.P)
+
+
+def token_codes_as_csr(offsets, codes, res, codec: TokenCodec, what: str = "set_token_codes"):
+    """Checked canonical codes ``(offsets int64 [n + 1], codes uint16 [E], res uint8 [E, RB])``; a code ``>= C``, wrong
+    shapes and offsets that do not describe ``E`` tokens raise ``ValueError``."""
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    codes = np.ascontiguousarray(codes, dtype=np.uint16).reshape(-1)
+    res = np.ascontiguousarray(res, dtype=np.uint8)
+    if off.shape[0] < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != codes.shape[0]:
+        raise ValueError(f"{what}: the offsets do not describe the {codes.shape[0]} codes")
+    if res.size != codes.shape[0] * codec.res_bytes:
+        raise ValueError(f"{what}: {res.size} bytes of buckets for {codes.shape[0]} tokens of {codec.res_bytes} bytes each")
+    lens = np.diff(off)
+    if lens.size and int(lens.max()) > MAX_ROW_TOKEN_VECTORS:
+        raise ValueError(f"{what}: row {int(lens.argmax())} (of this call) has {int(lens.max())} tokens "
+                         f"(at most {MAX_ROW_TOKEN_VECTORS})")
+    bad = np.flatnonzero(codes >= codec.centroids.shape[0])
+    if bad.size:
+        row = int(np.searchsorted(off, bad[0], side="right")) - 1
+        raise ValueError(f"{what}: token {int(bad[0] - off[row])} of row {row} (of this call) has code {int(codes[bad[0]])}, "
+                         f"the codec has {codec.centroids.shape[0]} centroids")
+    return off, codes, res.reshape(codes.shape[0], codec.res_bytes)
+
+
+def residual_quantiles(r, nbits: int) -> Tuple[np.ndarray, np.ndarray]:
+    """ColBERTv2's bucket boundaries and values from residual components ``r``: ``cutoffs[i - 1]`` is the ``i / 2^nbits``
+    quantile (``i = 1 .. 2^nbits - 1``), ``weights[i]`` the ``(i + 1/2) / 2^nbits`` quantile, float32.  Equal
+    neighbouring cutoffs (a sample without spread) are moved apart by one float32 step so that they ascend."""
+    nb = 1 << nbits
+    r = np.sort(np.asarray(r, dtype=np.float32).reshape(-1)).astype(np.float64)
+    cut = np.quantile(r, np.arange(1, nb) / nb).astype(np.float32)
+    w = np.quantile(r, (np.arange(nb) + 0.5) / nb).astype(np.float32)
+    for i in range(1, cut.shape[0]):
+        if not cut[i] > cut[i - 1]:
+            cut[i] = np.nextafter(cut[i - 1], np.float32(np.inf))
+    return cut, w
+
+
+def train_token_codec(mats, ncentroids: int, nbits: int = 2, niter: int = 20, seed: int = 0, device: int = 0,
+                      max_points_per_centroid: int = 256) -> TokenCodec:
+    """A codec trained on token matrices (any form ``set_tokens`` takes): a seeded sample of at most
+    ``max_points_per_centroid * ncentroids`` tokens goes as float32 rows into a temporary ``IndexFlat(P)``,
+    ``kmeans(ncentroids)`` runs on the GPU (``2 <= ncentroids <= 4096``, spherical), the centroids are rounded to bf16,
+    the sample is encoded on the device, and ``cutoffs`` / ``weights`` are the quantiles of the sample's residual
+    components (``residual_quantiles``).  The same call gives the same bytes."""
+    if int(nbits) not in TOKEN_CODEC_BITS:
+        raise ValueError(f"train_token_codec: nbits={nbits!r} is none of 1, 2, 4")
+    nc = int(ncentroids)
+    if not 2 <= nc <= 4096:
+        raise ValueError(f"train_token_codec: ncentroids={nc} outside [2, 4096]")
+    _, tok, P = tokens_as_csr(mats, what="train_token_codec")
+    if tok.shape[0] < nc:
+        raise ValueError(f"train_token_codec: {tok.shape[0]} tokens for {nc} centroids")
+    cap = max(int(max_points_per_centroid), 1) * nc
+    if tok.shape[0] > cap:
+        tok = tok[np.sort(np.random.default_rng(seed).choice(tok.shape[0], cap, replace=False))]
+    ix = IndexFlat(P, METRIC_INNER_PRODUCT, device)
+    try:
+        ix.add(bf16_to_f32(tok))
+        cent = bf16_to_f32(f32_to_bf16_rne(ix.kmeans(nc, niter=niter, seed=seed).centroids))
+        # the sample's codes from the device's encoder (buckets of a placeholder codec are not looked at)
+        ix.set_token_codec(TokenCodec(cent, 1, np.zeros(1, np.float32), np.zeros(2, np.float32)))
+        ix.set_tokens((np.arange(tok.shape[0] + 1, dtype=np.int64), tok, P))
+        _, codes, _ = ix.get_token_codes()
+    finally:
+        ix.close()
+    cut, w = residual_quantiles(bf16_to_f32(tok) - cent[codes], int(nbits))
+    return token_codec_args(cent, int(nbits), cut, w, what="train_token_codec")
+
+
 MAX_DIVERSE_FETCH = nat.MAX_DIVERSE_FETCH
 
 
@@ -1559,6 +1750,67 @@ class IndexFlat:
     def set_token_blocks(self, blocks: int) -> None:
         """The grid of the MaxSim kernel (0 = the library's choice); the result does not depend on it."""
         nat.check(nat.lib().css_index_set_token_blocks(self._handle(), int(blocks)))
+
+    # -- compressed token matrices (centroid + residual codes) ---------------------
+    def set_token_codec(self, codec: Optional[TokenCodec]) -> None:
+        """Store token matrices COMPRESSED from now on (``css_index_set_token_codec``): ``codec`` is a ``TokenCodec``
+        (or a ``(centroids, nbits, cutoffs, weights)`` tuple), ``None`` clears it.  Allowed only while no row has a
+        matrix.  With a codec ``set_tokens`` encodes on the GPU, ``get_tokens`` returns the DECODED matrices, and
+        ``search_maxsim`` / ``maxsim_ids`` score the decoded matrices bit for bit.  The codec survives ``drop_tokens``,
+        ``reset`` and ``remove_ids``."""
+        if codec is None:
+            nat.check(nat.lib().css_index_set_token_codec(self._handle(), None, 0, 0, 0, None, None))
+            return
+        c = token_codec_args(*codec)
+        nat.check(nat.lib().css_index_set_token_codec(self._handle(), c.centroids.ctypes.data, c.centroids.shape[0], c.P,
+                                                      c.nbits, c.cutoffs.ctypes.data, c.weights.ctypes.data))
+
+    @property
+    def token_codec_bits(self) -> int:
+        """Bits per residual component of the index's token codec; 0 = no codec."""
+        b = ctypes.c_int(0)
+        nat.check(nat.lib().css_index_token_codec_bits(self._handle(), ctypes.byref(b)))
+        return int(b.value)
+
+    def get_token_codec(self) -> Optional[TokenCodec]:
+        """The index's codec (``css_index_get_token_codec``), ``None`` without one."""
+        C, P, nb = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        fn, h = nat.lib().css_index_get_token_codec, self._handle()
+        nat.check(fn(h, ctypes.byref(C), ctypes.byref(P), ctypes.byref(nb), None, None, None))
+        if nb.value == 0:
+            return None
+        cent = np.empty((C.value, P.value), dtype=np.float32)
+        cut, w = np.empty((1 << nb.value) - 1, dtype=np.float32), np.empty(1 << nb.value, dtype=np.float32)
+        nat.check(fn(h, None, None, None, cent.ctypes.data, cut.ctypes.data, w.ctypes.data))
+        return TokenCodec(cent, int(nb.value), cut, w)
+
+    def get_token_codes(self, row0: int = 0, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The stored codes of rows ``[row0, row0 + n)`` (default: to the end) in the canonical layout, nothing decoded
+        (``css_index_get_token_codes``): ``(offsets int64 [n + 1] from 0, codes uint16 [E], res uint8 [E, P * nbits / 8])``."""
+        row0, n = self._row_range("get_token_codes", row0, n)
+        codec = self.get_token_codec()
+        if codec is None:
+            raise ValueError("get_token_codes: the index has no token codec")
+        off = np.zeros(n + 1, dtype=np.int64)
+        fn, h = nat.lib().css_index_get_token_codes, self._handle()
+        nat.check(fn(h, row0, n, off.ctypes.data, None, None))
+        codes = np.zeros(int(off[-1]), dtype=np.uint16)
+        res = np.zeros((int(off[-1]), codec.res_bytes), dtype=np.uint8)
+        if codes.size:
+            nat.check(fn(h, row0, n, off.ctypes.data, codes.ctypes.data, res.ctypes.data))
+        return off, codes, res
+
+    def set_token_codes(self, offsets, codes, res, row0: Optional[int] = None) -> None:
+        """Canonical codes as ``get_token_codes`` gives them, stored without encoding (``css_index_set_token_codes``):
+        save / load and shards.  The index needs the codec they were made with; the append-only rules of ``set_tokens``."""
+        codec = self.get_token_codec()
+        if codec is None:
+            raise ValueError("set_token_codes: the index has no token codec")
+        off, codes, res = token_codes_as_csr(offsets, codes, res, codec)
+        row0 = self.token_rows if row0 is None else int(row0)
+        nat.check(nat.lib().css_index_set_token_codes(self._handle(), row0, off.shape[0] - 1, off.ctypes.data,
+                                                      codes.ctypes.data if codes.size else None,
+                                                      res.ctypes.data if codes.size else None))
 
     def search_maxsim(self, q_mat, k: int, allow=None) -> Tuple[np.ndarray, np.ndarray]:
         """The ``k`` best rows for ONE query matrix ``[mq, P]`` by MaxSim with the rows' token matrices ALONE

@@ -784,6 +784,63 @@ class ShardedFlatIndex:
             tok[off[at]:off[at + m]] = np.asarray(ltok).reshape(-1, P)   # (a shard without matrices gives [0, 0])
         return off, self._sum_over_ranks(tok).astype(np.uint16).reshape(int(off[-1]), P)
 
+    # -- compressed token matrices ---------------------------------------------------------------------------------
+    def set_token_codec(self, codec) -> None:
+        """``IndexFlat.set_token_codec`` on every shard (collective: every rank passes the same codec; no
+        communication).  A row's codes and score depend on its own matrix, the codec and the query alone, so the sharded
+        results equal the single index's in bytes."""
+        self.local.set_token_codec(codec)
+
+    @property
+    def token_codec_bits(self) -> int:
+        return self.local.token_codec_bits
+
+    def get_token_codec(self):
+        return self.local.get_token_codec()
+
+    def set_token_codes(self, offsets, codes, res, row0: Optional[int] = None) -> None:
+        """``IndexFlat.set_token_codes`` in GLOBAL numbering (collective: every rank passes the same codes), routed
+        through the segment table like ``set_tokens``."""
+        from .flat_index import token_codes_as_csr
+
+        codec = self.get_token_codec()
+        if codec is None:
+            raise ValueError("set_token_codes: the index has no token codec")
+        off, codes, res = token_codes_as_csr(offsets, codes, res, codec)
+        n = off.shape[0] - 1
+        row0 = self._tokens_global if row0 is None else int(row0)
+        self._check_rows("set_token_codes", row0, n)
+        if row0 > self._tokens_global:
+            raise ValueError(f"set_token_codes: row0={row0} beyond the {self._tokens_global} rows that have matrices (matrices are append-only)")
+        if n == 0 and row0 == self._tokens_global:
+            return
+        local_row0, loff, (lcodes, lres) = self._local_csr(row0, off, (codes, res))
+        self.local.set_token_codes(loff, lcodes, lres, row0=local_row0)
+        self._tokens_global, self._token_dim = row0 + n, codec.P if n else self._token_dim
+
+    def get_token_codes(self, row0: int = 0, n: Optional[int] = None):
+        """``IndexFlat.get_token_codes`` of the GLOBAL rows ``[row0, row0 + n)`` on every rank (collective): summed over
+        the ranks as ``get_tokens`` is (exact: one contribution per entry)."""
+        codec = self.get_token_codec()
+        if codec is None:
+            raise ValueError("get_token_codes: the index has no token codec")
+        row0 = int(row0)
+        n = self.ntotal_global - row0 if n is None else int(n)
+        self._check_rows("get_token_codes", row0, n)
+        parts = [(lo - row0, m) + tuple(self.local.get_token_codes(l0, m)) for l0, lo, m in self._overlaps(row0, n)]
+        lens = np.zeros(n, dtype=np.int64)
+        for at, m, loff, _, _ in parts:
+            lens[at:at + m] = np.diff(loff)
+        lens = self._sum_over_ranks(lens)
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        both = np.zeros((int(off[-1]), 1 + codec.res_bytes), dtype=np.int32)   # [code | packed buckets] per token
+        for at, m, _, lcodes, lres in parts:
+            both[off[at]:off[at + m], 0] = lcodes
+            both[off[at]:off[at + m], 1:] = lres
+        both = self._sum_over_ranks(both)
+        return off, both[:, 0].astype(np.uint16), np.ascontiguousarray(both[:, 1:].astype(np.uint8))
+
     def search_maxsim(self, q_mat, k: int, allow=None):
         """``IndexFlat.search_maxsim`` over the shards (collective): ``(D, I)`` with global ids on every rank.  A row's
         score is a function of its own matrix and the query, so the merged result equals the single index's in bytes.
@@ -1161,6 +1218,22 @@ class ShardedIndexFacade:
 
     def drop_tokens(self) -> None:
         self.sh.drop_tokens()
+
+    def set_token_codec(self, codec) -> None:
+        self.sh.set_token_codec(codec)
+
+    @property
+    def token_codec_bits(self) -> int:
+        return self.sh.token_codec_bits
+
+    def get_token_codec(self):
+        return self.sh.get_token_codec()
+
+    def get_token_codes(self, row0: int = 0, n: Optional[int] = None):
+        return self.sh.get_token_codes(row0, n)
+
+    def set_token_codes(self, offsets, codes, res, row0: Optional[int] = None) -> None:
+        self.sh.set_token_codes(offsets, codes, res, row0=row0)
 
     def search_maxsim(self, q_mat, k: int, allow=None):
         return self.sh.search_maxsim(q_mat, int(k), allow=allow)

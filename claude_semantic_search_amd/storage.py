@@ -77,6 +77,12 @@ class StorageConfig:
     # filter that cannot be compiled with exactly the host's semantics falls back to the host loop.  It changes where
     # the allow mask of a search is computed, never what a search returns.  Off by default.
     attribute_filters: bool = False
+    # extension: store the chunks' token matrices (index_tokens / search_late) COMPRESSED, ColBERTv2's residual codec:
+    # a token is the id of its nearest centroid plus ``token_codec_bits`` (1, 2 or 4) per component -- 2 + P bits / 8
+    # bytes in place of 2 P.  The codec is trained on the first batch of encoded chunks with at most
+    # ``token_codec_centroids`` centroids (<= 4096).  0 = off: the matrices are stored as they are.
+    token_codec_bits: int = 0
+    token_codec_centroids: int = 4096
 
 
 @dataclass
@@ -361,6 +367,7 @@ class HybridStorage:
         self._tokens = _Synced()
         self._tokens_model: Optional[str] = None
         self._tokens_saved: Optional[Tuple[Optional[str], int, int]] = None
+        self._tokens_codec_model: Optional[str] = None   # the model whose tokens the index's token codec was trained on
         # search_sessions: dense group labels per session_id (order of first appearance by faiss_id)
         self._session_labels: Dict[str, int] = {}
         # search_recent: the half-life and reference time (days since the epoch) the priors are stored for; the newest
@@ -1269,9 +1276,17 @@ class HybridStorage:
         state = (self._tokens_model, rows, ntotal)
         if state == self._tokens_saved and self.tokens_path.exists():
             return
-        off, tok = ix.get_tokens(0, ntotal)
         tmp = str(self.tokens_path) + ".tmp.npz"
-        np.savez(tmp, offsets=off, tokens=tok, P=np.int64(tok.shape[1]), rows=np.int64(rows), model=np.array(self._tokens_model or ""))
+        codec = ix.get_token_codec() if getattr(ix, "token_codec_bits", 0) else None
+        if codec is not None:   # the COMPRESSED form: codec and canonical codes, never the decoded matrices
+            off, codes, res = ix.get_token_codes(0, ntotal)
+            np.savez(tmp, offsets=off, codes=codes, res=res, P=np.int64(codec.P), rows=np.int64(rows),
+                     model=np.array(self._tokens_model or ""), nbits=np.int64(codec.nbits),
+                     centroids=(np.ascontiguousarray(codec.centroids).view(np.uint32) >> 16).astype(np.uint16),
+                     cutoffs=codec.cutoffs, weights=codec.weights)
+        else:
+            off, tok = ix.get_tokens(0, ntotal)
+            np.savez(tmp, offsets=off, tokens=tok, P=np.int64(tok.shape[1]), rows=np.int64(rows), model=np.array(self._tokens_model or ""))
         os.replace(tmp, str(self.tokens_path))
         _fsync_dir(self.tokens_path.parent)
         self._tokens_saved = state
@@ -1284,12 +1299,24 @@ class HybridStorage:
             return
         try:
             with np.load(str(self.tokens_path)) as z:
-                off, tok = z["offsets"], z["tokens"]
+                compressed = "codes" in z.files
+                off = z["offsets"]
                 P, rows, model = int(z["P"]), int(z["rows"]), str(z["model"])
+                if compressed:
+                    codes, res = z["codes"], z["res"]
+                    codec = fi.TokenCodec((z["centroids"].astype(np.uint32) << 16).view(np.float32), int(z["nbits"]),
+                                          z["cutoffs"], z["weights"])
+                else:
+                    tok = z["tokens"]
             if off.shape[0] - 1 != ix.ntotal or not 0 < rows <= ix.ntotal:
                 self.logger.warning(f"{self.tokens_path.name} speaks of {off.shape[0] - 1} rows, the index has {ix.ntotal}: ignored")
                 return
-            ix.set_tokens((np.ascontiguousarray(off[:rows + 1]), tok[:int(off[rows])], P), row0=0)
+            if compressed:
+                ix.set_token_codec(codec)
+                ix.set_token_codes(np.ascontiguousarray(off[:rows + 1]), codes[:int(off[rows])], res[:int(off[rows])], row0=0)
+                self._tokens_codec_model = model or None
+            else:   # a file of the uncompressed shape: into an index without a codec
+                ix.set_tokens((np.ascontiguousarray(off[:rows + 1]), tok[:int(off[rows])], P), row0=0)
         except Exception as e:  # a corrupt or foreign file: the lazy sync encodes again
             self.logger.warning(f"Could not load the token matrices: {e}")
             return
@@ -1324,9 +1351,36 @@ class HybridStorage:
             for n, (fid, _) in enumerate(rows):
                 mats[fid - lo] = encoded[n]
                 keep[fid - lo] = flags[n] if flags is not None else None
+        if lo == 0:
+            self._token_codec_for(mats, keep, name)
         self.faiss_index.set_tokens(mats, keep=keep, row0=lo)
         self._tokens.rows, self._tokens_model = ntotal, name
         return len(rows)
+
+    def _token_codec_for(self, mats, keep, name: Optional[str]) -> None:
+        """Before the matrices are written from row 0: give the index the token codec that
+        ``StorageConfig.token_codec_bits`` asks for -- trained on this first batch of encoded chunks
+        (``train_token_codec``), once per index and model -- or take a codec away that the configuration no longer asks
+        for.  Fewer than 16 tokens train nothing: they are stored as they are."""
+        ix = self.faiss_index
+        bits = int(self.config.token_codec_bits)
+        have = int(getattr(ix, "token_codec_bits", 0))
+        if bits == 0 and have == 0:
+            return
+        if bits and not hasattr(ix, "set_token_codec"):
+            raise NotImplementedError("token_codec_bits needs an index with set_token_codec")
+        if bits and have == bits and self._tokens_codec_model == name:
+            return
+        off, tok, _ = fi.tokens_as_csr(mats, keep, what="index_tokens")
+        ix.drop_tokens()
+        if bits == 0 or tok.shape[0] < 16:
+            ix.set_token_codec(None)
+            self._tokens_codec_model = None
+            return
+        nc = int(min(max(int(self.config.token_codec_centroids), 2), 4096, tok.shape[0] // 8))
+        ix.set_token_codec(fi.train_token_codec((off, tok, tok.shape[1]), nc, nbits=bits, device=int(self.config.device)))
+        self._tokens_codec_model = name
+        self.logger.info(f"Trained a token codec: {nc} centroids, {bits} bits, on {tok.shape[0]} tokens")
 
     def index_tokens(self, late, batch_size: int = 32) -> int:
         """Give every live chunk that has none yet a token matrix (``LateInteraction.encode_documents`` of its stored

@@ -133,6 +133,26 @@ def token_matrices(n: int, P: int, seed: int, lattice=False, max_len: int = 40):
     return off, ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16), int(P)
 
 
+def clustered_token_matrices(n: int, P: int, seed: int, ncentres: int = 256, spread: float = 0.25, max_len: int = 40):
+    """Token matrices with the structure a token codec can find, in the CSR form and with the row lengths of
+    ``token_matrices``: ``ncentres`` Gaussian unit centres, every token one of them (uniformly drawn) plus Gaussian noise
+    of total length ``spread`` in expectation, scaled to unit length and rounded to bf16.  Gaussian unit vectors in 128
+    dimensions have no such structure: every token is nearly orthogonal to every centroid."""
+    rng = np.random.default_rng(seed)
+    lens = rng.integers(0, max_len + 1, size=n)
+    edge = np.asarray(TOKEN_EDGE_LENGTHS[:n], dtype=lens.dtype)
+    lens[:edge.shape[0]] = edge
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    E = int(off[-1])
+    centres = rng.standard_normal((ncentres, P))
+    centres /= np.linalg.norm(centres, axis=1, keepdims=True)
+    x = centres[rng.integers(0, ncentres, size=E)] + rng.standard_normal((E, P)) * (spread / np.sqrt(P))
+    x = (x / np.maximum(np.linalg.norm(x, axis=1, keepdims=True), 1e-30)).astype(np.float32)
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    return off, ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16), int(P)
+
+
 def query_terms(j: int, count: int = 4, vocab: int = TERM_VOCAB) -> np.ndarray:
     """The distinct values, in order of first occurrence, of ``floor(vocab * default_rng(500 + j).random(count)^3)``."""
     t = np.floor(vocab * np.random.default_rng(500 + j).random(count) ** 3).astype(np.int64)

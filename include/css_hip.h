@@ -506,6 +506,51 @@ int css_index_search_maxsim(css_index* ix, const uint16_t* q_tok_host /* bf16 [m
 int css_index_maxsim_rows(css_index* ix, const uint16_t* q_tok_host /* bf16 [mq, P] */, int mq, int P,
                           const int64_t* ids_host /* [n] */, int64_t n, float* scores_out /* [n] */);
 
+/* Compressed token matrices (ColBERTv2's residual compression): with a CODEC on the index a token is stored as the id
+ * of its best centroid plus an nbits bucket per component for the residual -- 2 + P nbits / 8 bytes in place of 2 P
+ * (34 in place of 256 at P = 128, nbits = 2) -- and MaxSim runs on the codes.  An index without a codec stores and
+ * scores exactly as above.
+ *  - The codec: C centroids [C, P], 1 <= C <= CSS_MAX_TOKEN_CENTROIDS, P a multiple of 32 in [32, CSS_MAX_TOKEN_DIM],
+ *    every component a finite fp32 value that IS a bf16 value (its low 16 bits are zero; anything else is refused:
+ *    rounding is the caller's decision); nbits in {1, 2, 4}; cutoffs [2^nbits - 1] fp32, finite and strictly ascending;
+ *    weights [2^nbits] fp32, finite.
+ *  - Encode, for a stored token d (bf16):  code = argmax over c of dot(d, centroid_c), ties to the lower c, the dot
+ *    formed as the score's dots are (bf16 operands, fp32 accumulation on v_mfma_f32_16x16x32_bf16, K steps of 32
+ *    ascending);  r_j = fp32(d_j) - fp32(centroid[code]_j), one IEEE fp32 subtraction;  bucket_j = #{i : cutoffs[i] <
+ *    r_j}  (np.searchsorted(cutoffs, r, side="left"), torch.bucketize).
+ *  - Decode:  d'_j = bf16_rne(fp32(centroid[code]_j) + weights[bucket_j]), one fp32 addition and one rounding to nearest
+ *    even.  There is NO renormalisation after decoding.  ColBERTv2 has one; it is left out so that a float32
+ *    restatement (numpy) gives the same bytes, and so that the score below has one definition.
+ *  - The score of a row is the score defined above of its DECODED matrix: bit for bit what css_encoder_maxsim returns
+ *    for css_index_get_tokens of that row with every token kept.
+ *  - Canonical code layout (what crosses this interface and goes to disk): codes uint16 [ntok]; res uint8
+ *    [ntok, P nbits / 8]; component j's bucket sits in bits [nbits (j % (8 / nbits)), + nbits) of byte j nbits / 8, least
+ *    significant first.
+ *  - css_index_set_token_codec is allowed only while the index has no matrices (css_index_token_rows == 0), else
+ *    CSS_ERR_INVALID; centroids_host == NULL clears the codec; everything is checked before anything is allocated.  The
+ *    codec survives css_index_drop_tokens, css_index_reset and css_index_remove_rows, which drop or move matrices only.
+ *    css_index_get_token_codec: any pointer may be NULL (sizes first, then contents); css_index_token_codec_bits: 0 =
+ *    no codec.
+ *  - With a codec, css_index_set_tokens takes the same CSR of bf16 matrices under the same rules and refusals, P must
+ *    equal the codec's, and it compresses on the device (k_tok_encode) through a staging buffer that dies with the
+ *    call: the raw tokens never stay in HBM.  css_index_get_tokens returns the DECODED matrices (k_tok_decode).
+ *    css_index_get_token_codes / css_index_set_token_codes move canonical (offsets, codes, res) without encoding or
+ *    decoding (save / load, shards); set follows the same append-only rules, needs a codec and refuses a code >= C,
+ *    naming the row.  css_index_search_maxsim and css_index_maxsim_rows are unchanged in signature, limits, padding,
+ *    masks, id_base and tie rule; on a compressed store they run k_tok_scores_c (2 + P nbits / 8 bytes per token of an
+ *    allowed row read from HBM, the centroid table through the caches).  css_index_remove_rows compacts codes and
+ *    packed buckets: afterwards css_index_get_token_codes equals that of a fresh index built from the kept rows. */
+#define CSS_MAX_TOKEN_CENTROIDS 65536
+int css_index_set_token_codec(css_index* ix, const float* centroids_host /* [C, P]; NULL clears */, int C, int P, int nbits,
+                              const float* cutoffs_host /* [2^nbits - 1] */, const float* weights_host /* [2^nbits] */);
+int css_index_get_token_codec(css_index* ix, int* C_out, int* P_out, int* nbits_out, float* centroids_out /* [C, P] */,
+                              float* cutoffs_out, float* weights_out);
+int css_index_token_codec_bits(css_index* ix, int* bits_out);
+int css_index_get_token_codes(css_index* ix, int64_t row0, int64_t n, int64_t* offsets_out /* [n+1], from 0 */,
+                              uint16_t* codes_out /* may be NULL */, uint8_t* res_out /* may be NULL */);
+int css_index_set_token_codes(css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host /* [n+1] */,
+                              const uint16_t* codes_host /* [offsets[n]] */, const uint8_t* res_host /* [offsets[n], P nbits / 8] */);
+
 /* Significant terms (Elasticsearch's significant_terms aggregation, the keyword side of BERTopic): which terms set a
  * selection of rows apart from a background -- "what is in this cluster / this project / these hits".  Everything is
  * read from the term lists above; the rows' values play no part.  T = the leading rows that have lists.
