@@ -184,6 +184,10 @@ PROTOTYPES = {
     "css_index_set_token_blocks": (c_int, [c_void_p, c_int]),
     "css_index_search_maxsim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "css_index_maxsim_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "css_index_maxsim_candidates": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                                            POINTER(c_int64)]),
+    "css_index_search_maxsim_pruned": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                                               POINTER(c_int64)]),
     "css_index_set_token_codec": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "css_index_get_token_codec": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_void_p, c_void_p,
                                           c_void_p]),

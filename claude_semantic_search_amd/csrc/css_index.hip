@@ -56,6 +56,10 @@
 //   k_tok_encode,      buckets per token): the B fragment is decoded in registers from codes, packed buckets and a
 //   k_tok_decode       gathered centroid row; the encoder (argmax over centroids on the bf16 MFMA, buckets, packing)
 //                      and the decoder of css_index_set_tokens / _get_tokens (css_token_codec.h)
+//   k_tok_ctable,      css_index_maxsim_candidates / css_index_search_maxsim_pruned: the query's dots with the codec's
+//   k_tok_ci,          centroids, the MaxSim of every row's CENTROIDS from its 2-byte codes and that table, and an exact
+//   k_sel_*            multi-block radix select of the best ncand rows in row order (css_token_prune.h); the exact pass
+//                      over the candidates is k_tok_scores_c through its row list
 //   k_sig_count        css_index_subset_terms / _significant_terms: +1 per list entry of the selected rows into a
 //                      uint32 table [2^24], repeats merged in a per-block LDS table first; k_sig_score and the radix
 //                      select rank the terms (css_sigterms.h)
@@ -302,6 +306,12 @@ struct css_index {
     DevBuf<unsigned short> tk_q;
     DevBuf<uint32_t> tk_ids;
     DevBuf<float> tk_col;
+    // css_index_maxsim_candidates / css_index_search_maxsim_pruned (css_token_prune.h): the centroid table [C][16 MT] of
+    // the call's query (at most 16 MB), the candidate rows and their approximate scores [ncand], and the select's words
+    // [4 x 256 bins | threshold key, need, all, count | 2 per block of the compaction].  The approximate column is
+    // lex_col, the exact one of the candidates tk_col, the part lists sp_pd / sp_pi
+    DevBuf<float> tk_ctab, tk_capx;
+    DevBuf<uint32_t> tk_cand, tk_sel;
     // css_index_kmeans_step (css_kmeans.h): the uploaded centroids [nc, dim]; their padded table [ncpad][dpad] with the
     // squared norms [ncpad] behind it; assignment and distance of every row; the member lists [ntotal] with
     // [nc + 1 offsets | nc + 1 block numbers | nc cursors]; and [KM_HDR words | nc counts | nc * dim sums] of int64
@@ -2898,6 +2908,7 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 #include "css_sparse.h"
 #include "css_tokens.h"
 #include "css_token_codec.h"
+#include "css_token_prune.h"
 #include "css_where.h"
 #include "css_sigterms.h"
 
@@ -6048,6 +6059,190 @@ int css_index_maxsim_rows(css_index* ix, const uint16_t* q_tok_host, int mq, int
     const hipError_t e = hipStreamSynchronize(st);   // (also after a failure: the copies read this call's memory)
     if (rc != CSS_OK) return rc;
     CSS_HIP_TRY(e);
+    return CSS_OK;
+}
+
+namespace {
+const void* tok_ctable_kernel(int P) {
+    return P == 32 ? (const void*)k_tok_ctable<32> : P == 64 ? (const void*)k_tok_ctable<64> : P == 96 ? (const void*)k_tok_ctable<96>
+                                                                                                        : (const void*)k_tok_ctable<128>;
+}
+
+// The candidates of the query (mq tokens on the device) among `rows`: the centroid table, the approximate column over
+// every row (lex_col), and the select of the best nc <= rows.n of it into tk_cand (ascending rows, 0xFFFFFFFF behind
+// the count) and tk_capx; the count is word kSelHist + 3 of tk_sel.  The index has a codec and matrices, rows.n > 0.
+// Everything is enqueued on `st`.  Caller holds ws_mu, a shared lock on mu and a turn at the workspaces.
+int tok_candidates_enqueue(css_index* ix, const Rows& rows, const unsigned short* q_dev, int mq, int64_t nc, const char* who,
+                           hipStream_t st) {
+    int rc;
+    CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "%s: %lld rows exceed the 32-bit row numbers of the lists", who, (long long)rows.n);
+    const int P = ix->tk_dim, MT = (mq + 15) / 16, W = 16 * MT, C = ix->tk_ncent;
+    const int64_t n = rows.n;
+    const int nblk = (int)((n + kSelSlice - 1) / kSelSlice);
+    if ((rc = ix->tk_ctab.grow((size_t)C * W)) != CSS_OK) return rc;
+    if ((rc = ix->lex_col.grow((size_t)n)) != CSS_OK) return rc;
+    if ((rc = ix->tk_cand.grow((size_t)nc)) != CSS_OK) return rc;
+    if ((rc = ix->tk_capx.grow((size_t)nc)) != CSS_OK) return rc;
+    if ((rc = ix->tk_sel.grow((size_t)kSelState + 2 * (size_t)nblk)) != CSS_OK) return rc;
+    // rows appended on another stream must have landed (the mask and the row count speak of them)
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    const unsigned short *cent = ix->tk_cent.p, *codes = ix->tk_code.p;
+    float* tab = ix->tk_ctab.p;
+    {
+        int mt = MT, c = C, m = mq;
+        void* args[] = {&cent, &c, &q_dev, &m, &mt, &tab};
+        ProfScope ps("tok_ctable", st);
+        CSS_HIP_TRY(hipLaunchKernel(tok_ctable_kernel(P), dim3((unsigned)((C + 16 * kWaves - 1) / (16 * kWaves))), dim3(64 * kWaves), args, 0, st));
+    }
+    {
+        const void* fn = W <= 16 ? (const void*)k_tok_ci<16> : W <= 32 ? (const void*)k_tok_ci<32> : (const void*)k_tok_ci<64>;
+        // the grid of tok_scores_enqueue: the resident blocks, or what css_index_set_token_blocks fixes
+        int64_t blocks = ix->tk_blocks;
+        int per = kTokTurn;
+        if (blocks == 0) {
+            int per_cu = 0;
+            CSS_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * kWaves, 0));
+            blocks = (int64_t)std::max(per_cu, 1) * ix->num_cus;
+            per = (int)std::min<int64_t>(kTokTurn, (n + blocks * kWaves - 1) / (blocks * kWaves));
+        }
+        blocks = std::min<int64_t>(blocks, (n + (int64_t)per * kWaves - 1) / ((int64_t)per * kWaves));
+        const float* ctab = tab;
+        const int64_t* off = ix->tk_off.p;
+        int64_t nlist = ix->tk_rows, nn = n;
+        const uint32_t *list = nullptr, *mask = rows.mask;
+        int w = W, m = mq;
+        float* col = ix->lex_col.p;
+        void* args[] = {&codes, &ctab, &w, &off, &nlist, &list, &nn, &mask, &m, &per, &col};
+        ProfScope ps("tok_ci", st);
+        CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * kWaves), args, 0, st));
+    }
+    ProfScope ps("tok_select", st);
+    uint32_t* sel = ix->tk_sel.p;
+    CSS_HIP_TRY(hipMemsetAsync(sel, 0, (size_t)kSelState * sizeof(uint32_t), st));
+    CSS_HIP_TRY(hipMemsetAsync(ix->tk_cand.p, 0xFF, (size_t)nc * sizeof(uint32_t), st));
+    const unsigned hblk = (unsigned)std::min(nblk, kSelMaxBlocks);
+    for (int pass = 0; pass < 4; ++pass) {
+        hipLaunchKernelGGL(k_sel_hist, dim3(hblk), dim3(256), 0, st, (const float*)ix->lex_col.p, n, (uint32_t)nc, pass, sel);
+        CSS_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_sel_count, dim3((unsigned)nblk), dim3(256), 0, st, (const float*)ix->lex_col.p, n, (uint32_t)nc,
+                       (const uint32_t*)sel, sel + kSelHist, sel + kSelState);
+    CSS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sel_write, dim3((unsigned)nblk), dim3(256), 0, st, (const float*)ix->lex_col.p, n,
+                       (const uint32_t*)(sel + kSelState), nblk, (uint32_t)nc, sel + kSelHist, ix->tk_cand.p, ix->tk_capx.p);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// what both entry points check of the call before anything is enqueued; under the call's locks
+int token_prune_check(const char* fn, const css_index* ix, int P, int64_t ncand) {
+    CSS_REQUIRE(ix->tk_bits != 0, "%s: the index has no token codec (css_index_set_token_codec)", fn);
+    CSS_REQUIRE(P == ix->tk_cdim, "%s: the query has P=%d, the index's token codec P=%d", fn, P, ix->tk_cdim);
+    CSS_REQUIRE(ncand >= 1 && ncand <= CSS_MAX_MAXSIM_ROWS, "%s: ncand=%lld outside [1, %d]", fn, (long long)ncand, CSS_MAX_MAXSIM_ROWS);
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_maxsim_candidates(css_index* ix, const uint16_t* q_tok_host, int mq, int P, int64_t ncand,
+                                const uint32_t* allow_bits_host, int64_t* ids_out, float* approx_out, int64_t* n_out) {
+    const char* fn = "css_index_maxsim_candidates";
+    CSS_REQUIRE(ix, "%s: NULL index", fn);
+    CSS_REQUIRE(ids_out && approx_out && n_out, "%s: NULL buffer", fn);
+    int rc = token_query_check(fn, q_tok_host, mq, P);
+    if (rc != CSS_OK) return rc;
+    HostCall hc(ix);
+    if ((rc = token_prune_check(fn, ix, P, ncand)) != CSS_OK) return rc;
+    *n_out = 0;
+    if (ix->tk_rows == 0 || hc.rows.n == 0) return CSS_OK;   // a codec without matrices: no candidates
+    const int64_t nc = std::min<int64_t>(ncand, hc.rows.n);
+    std::vector<float> Dh;
+    std::vector<int64_t> Ih;
+    try {
+        Dh.resize((size_t)nc + 1);
+        Ih.resize((size_t)nc + 1);
+    } catch (const std::bad_alloc&) {
+        css::set_error("%s: out of host memory", fn);
+        return CSS_ERR_OOM;
+    }
+    // the ONE upload: the query matrix; the results: nc [id | approximate score] entries and the count behind them
+    rc = hc.upload(allow_bits_host, ix->tk_q, (const unsigned short*)q_tok_host, (size_t)mq * P, (size_t)nc + 1);
+    if (rc == CSS_OK) {
+        const hipStream_t st = ix->stream;
+        WsTurn turn(ix, st);
+        rc = turn.rc;
+        if (rc == CSS_OK) rc = tok_candidates_enqueue(ix, hc.rows, ix->tk_q.p, mq, nc, fn, st);
+        if (rc == CSS_OK) {
+            hipLaunchKernelGGL(k_tok_cand_out, dim3((unsigned)((nc + 256) / 256)), dim3(256), 0, st, (const uint32_t*)ix->tk_cand.p,
+                               (const float*)ix->tk_capx.p, (const uint32_t*)(ix->tk_sel.p + kSelHist), nc, hc.rows.id_base,
+                               hc.d_out, hc.i_out);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) rc = css::hip_fail(e, "k_tok_cand_out", __FILE__, __LINE__);
+        }
+    }
+    if ((rc = hc.finish(rc, Dh.data(), Ih.data())) != CSS_OK) return rc;
+    const int64_t got = Ih[(size_t)nc];
+    memcpy(ids_out, Ih.data(), (size_t)got * sizeof(int64_t));
+    memcpy(approx_out, Dh.data(), (size_t)got * sizeof(float));
+    *n_out = got;
+    return CSS_OK;
+}
+
+int css_index_search_maxsim_pruned(css_index* ix, const uint16_t* q_tok_host, int mq, int P, int k, int64_t ncand,
+                                   const uint32_t* allow_bits_host, float* D_host, int64_t* I_host, int64_t* ncand_out) {
+    const char* fn = "css_index_search_maxsim_pruned";
+    CSS_REQUIRE(ix, "%s: NULL index", fn);
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "%s: k=%d outside [1, %d]", fn, k, CSS_KERNEL_MAX_K);
+    CSS_REQUIRE(D_host && I_host, "%s: NULL buffer", fn);
+    int rc = token_query_check(fn, q_tok_host, mq, P);
+    if (rc != CSS_OK) return rc;
+    HostCall hc(ix);
+    if ((rc = token_prune_check(fn, ix, P, ncand)) != CSS_OK) return rc;
+    CSS_REQUIRE(k <= ncand, "%s: k=%d exceeds ncand=%lld", fn, k, (long long)ncand);
+    float Dh[CSS_KERNEL_MAX_K + 1];
+    int64_t Ih[CSS_KERNEL_MAX_K + 1];
+    // the ONE upload: the query matrix; the results: k entries and the candidate count in the id slot behind them
+    rc = hc.upload(allow_bits_host, ix->tk_q, (const unsigned short*)q_tok_host, (size_t)mq * P, (size_t)k + 1);
+    if (rc == CSS_OK) {
+        const hipStream_t st = ix->stream;
+        WsTurn turn(ix, st);
+        rc = turn.rc;
+        if (rc == CSS_OK) rc = [&]() -> int {
+            int rc;
+            if (ix->tk_rows == 0 || hc.rows.n == 0) {   // a codec without matrices: the padded answer
+                hipLaunchKernelGGL(k_sparse_pad, dim3(1), dim3(128), 0, st, hc.d_out, hc.i_out, k);
+                CSS_LAUNCH_CHECK();
+                CSS_HIP_TRY(hipMemsetAsync(hc.i_out + k, 0, sizeof(int64_t), st));
+                return CSS_OK;
+            }
+            const int64_t nc = std::min<int64_t>(ncand, hc.rows.n);
+            if ((rc = tok_candidates_enqueue(ix, hc.rows, ix->tk_q.p, mq, nc, fn, st)) != CSS_OK) return rc;
+            // the exact scores of the candidates on the codes (a slot behind the count names no row: a miss) ...
+            const int64_t slice = sparse_topk_slice(nc);
+            const int parts = (int)((nc + slice - 1) / slice);
+            if ((rc = ix->tk_col.grow((size_t)nc)) != CSS_OK) return rc;
+            if ((rc = ix->sp_pd.grow((size_t)parts * k)) != CSS_OK) return rc;
+            if ((rc = ix->sp_pi.grow((size_t)parts * k)) != CSS_OK) return rc;
+            if ((rc = tok_scores_enqueue(ix, ix->tk_cand.p, nc, nullptr, ix->tk_q.p, mq, ix->tk_col.p, st)) != CSS_OK) return rc;
+            // ... their top-k by (score, position): the list ascends by row, so ties go to the lower id ...
+            {
+                ProfScope ps("sparse_topk", st);
+                hipLaunchKernelGGL(k_sparse_topk, dim3((unsigned)parts), dim3(256), 0, st, (const float*)ix->tk_col.p, nc, slice,
+                                   (const uint32_t*)nullptr, k, (int64_t)0, ix->sp_pd.p, ix->sp_pi.p);
+                CSS_LAUNCH_CHECK();
+            }
+            if ((rc = merge_parts(ix->sp_pd.p, ix->sp_pi.p, parts, k, k, 1, k, CSS_METRIC_IP, hc.d_out, hc.i_out, ix->device, st, fn)) != CSS_OK)
+                return rc;
+            // ... and the positions become ids
+            hipLaunchKernelGGL(k_tok_cand_ids, dim3(1), dim3(256), 0, st, (const uint32_t*)ix->tk_cand.p,
+                               (const uint32_t*)(ix->tk_sel.p + kSelHist), k, hc.rows.id_base, hc.d_out, hc.i_out);
+            CSS_LAUNCH_CHECK();
+            return CSS_OK;
+        }();
+    }
+    if ((rc = hc.finish(rc, Dh, Ih)) != CSS_OK) return rc;
+    memcpy(D_host, Dh, (size_t)k * sizeof(float));
+    memcpy(I_host, Ih, (size_t)k * sizeof(int64_t));
+    if (ncand_out) *ncand_out = Ih[k];
     return CSS_OK;
 }
 

@@ -751,6 +751,101 @@ def train_token_codec(mats, ncentroids: int, nbits: int = 2, niter: int = 20, se
     return token_codec_args(cent, int(nbits), cut, w, what="train_token_codec")
 
 
+def prune_args(k, ncand, what: str = "search_maxsim_pruned") -> Tuple[Optional[int], int]:
+    """The argument rules of ``maxsim_candidates`` (``k`` is ``None``) and ``search_maxsim_pruned``: ``(k, ncand)`` as
+    ints; ``1 <= ncand <= 65536``, ``1 <= k <= 128`` and ``k <= ncand``, else ``ValueError``."""
+    try:
+        nc = int(ncand)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: ncand={ncand!r} is no integer") from None
+    if nc != ncand or not 1 <= nc <= MAX_MAXSIM_ROWS:
+        raise ValueError(f"{what}: ncand={ncand!r} outside [1, {MAX_MAXSIM_ROWS}]")
+    if k is None:
+        return None, nc
+    k = int(k)
+    if k < 1 or k > MAX_HYBRID_K:
+        raise ValueError(f"{what}: k={k} outside [1, {MAX_HYBRID_K}]")
+    if k > nc:
+        raise ValueError(f"{what}: k={k} exceeds ncand={nc}")
+    return k, nc
+
+
+def _sum_ascending_f32(mx: np.ndarray) -> np.ndarray:
+    """float32 ``[n]``: the columns of ``mx [n, mq]`` added one after the other, the device's chain."""
+    acc = np.zeros(mx.shape[0], dtype=np.float32)
+    for s in range(mx.shape[1]):
+        acc = acc + mx[:, s]
+    return acc
+
+
+def token_centroid_scores(codec: TokenCodec, q) -> np.ndarray:
+    """The numpy double of ``k_tok_ctable``: ``S[c, s] = dot(q_s, centroid_c)``, float32 ``[C, mq]``, for ONE query matrix
+    of bf16 bits.  float32 sums in numpy's order -- the device's bits where the dots are exact, within the fp32
+    accumulation error of them otherwise."""
+    q = np.asarray(q, dtype=np.uint16).reshape(-1, codec.P)
+    return np.ascontiguousarray(codec.centroids @ bf16_to_f32(q).T, dtype=np.float32)
+
+
+def token_codec_approx(codec: TokenCodec, offsets, codes, q, S=None) -> np.ndarray:
+    """The numpy double of ``k_tok_ci``: ``A[r] = sum over s ascending (float32) of max over the row's tokens of
+    S[code_t, s]``, float32 ``[n]``, ``-inf`` for a row without tokens.  ``S``: a table to use in place of
+    ``token_centroid_scores(codec, q)``."""
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    codes = np.asarray(codes, dtype=np.uint16).reshape(-1)
+    S = token_centroid_scores(codec, q) if S is None else np.asarray(S, dtype=np.float32)
+    out = np.full(off.shape[0] - 1, -np.inf, dtype=np.float32)
+    live = np.flatnonzero(np.diff(off) > 0)
+    if live.size:
+        out[live] = _sum_ascending_f32(np.maximum.reduceat(S[codes], off[:-1][live], axis=0))
+    return out
+
+
+def maxsim_candidates_numpy(approx, ncand: int, allowed=None, id_base: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """Step 3 from an approximate column: the first ``ncand`` rows of ``lexsort((id, -A))`` among the allowed rows that
+    are no miss, returned in ASCENDING id order: ``(ids int64, approx float32)``."""
+    _, ncand = prune_args(None, ncand, "maxsim_candidates")
+    a = np.asarray(approx, dtype=np.float32).reshape(-1)
+    ok = a > -np.inf
+    if allowed is not None:
+        ok = ok & np.asarray(allowed, dtype=bool).reshape(-1)
+    rows = np.flatnonzero(ok)
+    take = np.sort(rows[np.lexsort((rows, -(a[rows] + np.float32(0.0))))][:ncand])
+    return take.astype(np.int64) + int(id_base), a[take]
+
+
+def token_codec_scores(codec: TokenCodec, offsets, codes, res, q, rows=None) -> np.ndarray:
+    """The exact MaxSim on the codes in float32 (decode, dots, maximum, ascending sum) of ``rows`` (default: every row):
+    ``-inf`` for a row without tokens.  The device's bits where the dots are exact."""
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    rows = np.arange(off.shape[0] - 1) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
+    codes = np.asarray(codes, dtype=np.uint16).reshape(-1)
+    res = np.asarray(res, dtype=np.uint8).reshape(codes.shape[0], codec.res_bytes)
+    q32 = bf16_to_f32(np.asarray(q, dtype=np.uint16).reshape(-1, codec.P))
+    lens = off[rows + 1] - off[rows]
+    out = np.full(rows.shape[0], -np.inf, dtype=np.float32)
+    live = np.flatnonzero(lens > 0)
+    if live.size:
+        idx = np.concatenate([np.arange(off[r], off[r + 1]) for r in rows[live]])
+        starts = np.concatenate([[0], np.cumsum(lens[live])[:-1]])
+        sim = bf16_to_f32(token_codec_decode(codec, codes[idx], res[idx])) @ q32.T      # [E', mq]
+        out[live] = _sum_ascending_f32(np.maximum.reduceat(sim.astype(np.float32), starts, axis=0))
+    return out
+
+
+def search_maxsim_pruned_numpy(codec: TokenCodec, offsets, codes, res, q, k: int, ncand: int, allowed=None,
+                               id_base: int = 0, approx=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The numpy double of ``search_maxsim_pruned`` (steps 2 to 4): ``(D float32 [1, k], I int64 [1, k])``.  ``approx``:
+    an approximate column to use in place of ``token_codec_approx`` (the device's, say)."""
+    k, ncand = prune_args(k, ncand)
+    a = token_codec_approx(codec, offsets, codes, q) if approx is None else approx
+    ids, _ = maxsim_candidates_numpy(a, ncand, allowed)
+    sc = token_codec_scores(codec, offsets, codes, res, q, rows=ids)
+    order = np.lexsort((ids, -sc))[:k]
+    D, I = np.full((1, k), -np.finfo(np.float32).max, np.float32), np.full((1, k), -1, np.int64)
+    D[0, :order.size], I[0, :order.size] = sc[order], ids[order] + int(id_base)
+    return D, I
+
+
 MAX_DIVERSE_FETCH = nat.MAX_DIVERSE_FETCH
 
 
@@ -1836,6 +1931,42 @@ class IndexFlat:
                                                   ids.ctypes.data if ids.size else None, ids.shape[0],
                                                   out.ctypes.data if ids.size else None))
         return out
+
+    # -- candidate generation for MaxSim on the codes (PLAID) ----------------------
+    def _prune_codec(self, what: str) -> None:
+        if self.token_codec_bits == 0:
+            raise ValueError(f"{what}: the index has no token codec (set_token_codec)")
+
+    def maxsim_candidates(self, q_mat, ncand: int, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The best ``ncand`` rows for ONE query matrix by the MaxSim of their tokens' CENTROIDS
+        (``css_index_maxsim_candidates``; the index needs a token codec): ``(ids int64, approx float32)`` in ASCENDING
+        id order, at most ``ncand`` of them -- the first ``ncand`` of ``lexsort((id, -approx))`` among the allowed rows
+        with tokens.  ``approx[r]`` is bit for bit the MaxSim of the matrix ``centroids[codes of r]``.  Only the 2-byte
+        codes are read."""
+        q, _, _ = maxsim_args(q_mat, what="maxsim_candidates")
+        _, ncand = prune_args(None, ncand, "maxsim_candidates")
+        self._prune_codec("maxsim_candidates")
+        ids, approx = np.empty(ncand, dtype=np.int64), np.empty(ncand, dtype=np.float32)
+        n = ctypes.c_int64(0)
+        bits, bits_ptr = self._allow_bits(allow)
+        nat.check(nat.lib().css_index_maxsim_candidates(self._handle(), q.ctypes.data, q.shape[0], q.shape[1], ncand, bits_ptr,
+                                                        ids.ctypes.data, approx.ctypes.data, ctypes.byref(n)))
+        return ids[:n.value].copy(), approx[:n.value].copy()
+
+    def search_maxsim_pruned(self, q_mat, k: int, ncand: int, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``search_maxsim`` over the ``ncand`` candidates of ``maxsim_candidates`` alone
+        (``css_index_search_maxsim_pruned``; the index needs a token codec): ``(D, I)``, each ``[1, k]``, the EXACT
+        scores on the codes of the ``k`` best candidates, ``D == maxsim_ids(q_mat, I)`` in bits, padded as
+        ``search_maxsim`` pads.  ``1 <= k <= 128``, ``k <= ncand <= 65536``.  With ``ncand`` at least the number of
+        allowed rows with tokens the answer is ``search_maxsim``'s in bytes."""
+        q, _, _ = maxsim_args(q_mat, what="search_maxsim_pruned")
+        k, ncand = prune_args(k, ncand)
+        self._prune_codec("search_maxsim_pruned")
+        D, I = np.empty((1, k), dtype=np.float32), np.empty((1, k), dtype=np.int64)
+        bits, bits_ptr = self._allow_bits(allow)
+        nat.check(nat.lib().css_index_search_maxsim_pruned(self._handle(), q.ctypes.data, q.shape[0], q.shape[1], k, ncand,
+                                                           bits_ptr, D.ctypes.data, I.ctypes.data, None))
+        return D, I
 
     # -- diversified search (MMR) --------------------------------------------
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False,

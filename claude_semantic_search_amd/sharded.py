@@ -869,6 +869,60 @@ class ShardedFlatIndex:
             out[own] = self.local.maxsim_ids(q, ids[own] if len(self.segments) == 1 else loc[own])
         return self._sum_over_ranks(out.view(np.int32)).view(np.float32)
 
+    def maxsim_candidates(self, q_mat, ncand: int, allow=None):
+        """``IndexFlat.maxsim_candidates`` over the shards (collective): ``(ids, approx)`` with global ids, ascending,
+        on every rank.  A row's approximate score is a function of its own codes, the codec and the query, and a
+        shard's best ``ncand`` hold its share of the global best ``ncand``: ONE all-gather of every rank's
+        ``[count | ids | approx]`` record, then every rank keeps the first ``ncand`` of ``lexsort((id, -approx))`` --
+        the single index's bytes."""
+        from .flat_index import maxsim_args, prune_args
+
+        q, _, _ = maxsim_args(q_mat, what="maxsim_candidates")
+        _, ncand = prune_args(None, ncand, "maxsim_candidates")
+        ids, approx = self.local.maxsim_candidates(q, ncand, allow=self._local_allow(allow))
+        ids = np.ascontiguousarray(self._to_global_np(np.asarray(ids, dtype=np.int64)))
+        approx = np.ascontiguousarray(approx, dtype=np.float32)
+        if self._single():
+            return ids, approx
+        n = ids.shape[0]
+        send = np.zeros(8 + 12 * ncand, dtype=np.uint8)
+        send[:8] = np.array([n], dtype=np.int64).view(np.uint8)
+        send[8:8 + 8 * n] = ids.view(np.uint8)
+        send[8 + 8 * ncand:8 + 8 * ncand + 4 * n] = approx.view(np.uint8)
+        recv = self._all_gather_host(send)
+        counts = [int(recv[r, :8].view(np.int64)[0]) for r in range(self.world)]
+        ids = np.concatenate([recv[r, 8:8 + 8 * c].view(np.int64) for r, c in enumerate(counts)])
+        approx = np.concatenate([recv[r, 8 + 8 * ncand:8 + 8 * ncand + 4 * c].view(np.float32) for r, c in enumerate(counts)])
+        take = np.lexsort((ids, -(approx + np.float32(0.0))))[:ncand]
+        take = take[np.argsort(ids[take], kind="stable")]
+        return np.ascontiguousarray(ids[take]), np.ascontiguousarray(approx[take])
+
+    def search_maxsim_pruned(self, q_mat, k: int, ncand: int, allow=None):
+        """``IndexFlat.search_maxsim_pruned`` over the shards (collective): ``(D, I)`` with global ids on every rank,
+        the single index's bytes.  Every rank forms the GLOBAL candidates (``maxsim_candidates``), scores its own
+        share exactly with ``maxsim_ids``, keeps its best ``k`` by ``(score descending, id)``, and the column exchange
+        of ``search_maxsim`` ranks the result."""
+        from .flat_index import maxsim_args, prune_args
+
+        q, _, _ = maxsim_args(q_mat, what="search_maxsim_pruned")
+        k, ncand = prune_args(k, ncand)
+        if self._single():
+            D, I = self.local.search_maxsim_pruned(q, k, ncand, allow=self._local_allow(allow))
+            return np.ascontiguousarray(D), np.ascontiguousarray(self._to_global_np(np.asarray(I, dtype=np.int64)))
+        ids, _ = self.maxsim_candidates(q, ncand, allow=allow)
+        loc = self._local_ids(ids)
+        own = np.flatnonzero(loc >= 0)
+        # (one segment: the local index adds id_base itself, so it is asked by global id and answers with it)
+        mine = ids[own] if len(self.segments) == 1 else loc[own]
+        D = np.full((1, k), -np.finfo(np.float32).max, dtype=np.float32)
+        I = np.full((1, k), -1, dtype=np.int64)
+        if own.size:
+            sc = np.asarray(self.local.maxsim_ids(q, mine), dtype=np.float32)
+            order = np.lexsort((ids[own], -sc))[:k]
+            D[0, :order.size], I[0, :order.size] = sc[order], mine[order]
+        I, (D,), _ = self._columns(I, (D,), metric=0)
+        return tuple(np.ascontiguousarray(a[..., :k]) for a in (D, I))
+
     # -- significant terms -------------------------------------------------------------------------------------
     def _exchange_counts(self, local_mask):
         """``(terms ascending, counts, rows)`` of the whole index for a mask over THIS shard's rows (``None``: every
@@ -1240,6 +1294,12 @@ class ShardedIndexFacade:
 
     def maxsim_ids(self, q_mat, ids) -> np.ndarray:
         return self.sh.maxsim_ids(q_mat, ids)
+
+    def maxsim_candidates(self, q_mat, ncand: int, allow=None):
+        return self.sh.maxsim_candidates(q_mat, int(ncand), allow=allow)
+
+    def search_maxsim_pruned(self, q_mat, k: int, ncand: int, allow=None):
+        return self.sh.search_maxsim_pruned(q_mat, int(k), int(ncand), allow=allow)
 
     def search_diverse(self, q, k: int, lam: float = 0.5, fetch: int = 0, normalize: bool = False, allow=None):
         return self.sh.search_diverse(np.asarray(q, dtype=np.float32), int(k), lam=lam, fetch=fetch, normalize=normalize,

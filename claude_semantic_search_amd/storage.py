@@ -83,6 +83,10 @@ class StorageConfig:
     # ``token_codec_centroids`` centroids (<= 4096).  0 = off: the matrices are stored as they are.
     token_codec_bits: int = 0
     token_codec_centroids: int = 4096
+    # Candidates of ``search_late`` on an index with a token codec: the chunks are first ranked by the MaxSim of their
+    # tokens' centroids (2 bytes per token read) and only the best ``late_candidates`` are decoded and scored exactly
+    # (``IndexFlat.search_maxsim_pruned``, PLAID's centroid interaction).  0 = exhaustive: every allowed chunk is scored.
+    late_candidates: int = 0
 
 
 @dataclass
@@ -1404,12 +1408,18 @@ class HybridStorage:
         (``late.encode_queries``) with the chunks' stored matrices, over ALL allowed rows inside the index
         (``IndexFlat.search_maxsim``); no dense row is read, no query embedding is needed and no text goes through the
         encoder again.  Each result's ``similarity`` is the MaxSim score, to which ``similarity_threshold`` applies.
-        Tombstones and filters as in ``search_sparse``."""
+        Tombstones and filters as in ``search_sparse``.  With ``StorageConfig.late_candidates > 0`` on an index with a
+        token codec only that many chunks, chosen by the MaxSim of their tokens' centroids, are scored exactly
+        (``IndexFlat.search_maxsim_pruned``): the scores returned are still exact, a chunk outside the candidates is
+        not seen."""
         self._require("late-interaction search", "set_tokens", "search_maxsim")
 
         def run(q, k, allow, ntotal, cfg):
             self._sync_tokens(ntotal, late)
             q_mat = late.encode_queries([query_text or ""])[0][0]
+            ncand = int(self.config.late_candidates)
+            if ncand > 0 and getattr(self.faiss_index, "token_codec_bits", 0) and hasattr(self.faiss_index, "search_maxsim_pruned"):
+                return self.faiss_index.search_maxsim_pruned(q_mat, k, min(max(ncand, k), fi.MAX_MAXSIM_ROWS), allow=allow)
             return self.faiss_index.search_maxsim(q_mat, k, allow=allow)
 
         return self._ranked_in_index(None, config, filters, fi.MAX_HYBRID_K, run)

@@ -551,6 +551,37 @@ int css_index_get_token_codes(css_index* ix, int64_t row0, int64_t n, int64_t* o
 int css_index_set_token_codes(css_index* ix, int64_t row0, int64_t n, const int64_t* offsets_host /* [n+1] */,
                               const uint16_t* codes_host /* [offsets[n]] */, const uint8_t* res_host /* [offsets[n], P nbits / 8] */);
 
+/* Candidate generation for MaxSim on a compressed store (PLAID's centroid interaction): rank every row by the MaxSim of
+ * its tokens' CENTROIDS -- 2 bytes per token read and a small table -- and decode and score exactly only the best
+ * ncand.  Both entry points need an index WITH a token codec (CSS_ERR_INVALID otherwise; the message says so), take
+ * the query matrix of css_index_search_maxsim (the same checks) with P = the codec's P, and 1 <= ncand <=
+ * CSS_MAX_MAXSIM_ROWS; everything is refused before anything is enqueued.  T, misses, masks and id_base as above.
+ *  - The centroid table.  S[c, s] = dot(q_s, centroid_c), c < C, s < mq, formed exactly as the score's dot of query
+ *    token s with a doc token equal to the bf16 centroid row c (bf16 operands, fp32 accumulation on
+ *    v_mfma_f32_16x16x32_bf16, query tokens as rows of A, centroids as columns of B, K steps of 32 ascending).
+ *  - The approximate score.  A[r] = sum over s ascending, fp32, of max over the row's tokens t of S[code_t, s]; a row
+ *    >= T, an empty row and a masked row are a miss and never a candidate.  By construction A[r] is, bit for bit, the
+ *    score defined above of the matrix centroids[codes of r]: what css_encoder_maxsim returns for those bf16 rows.
+ *  - The candidates.  The first ncand rows of lexsort((id, -A)) among the rows that are no miss: A compared as floats
+ *    (-0.0 == +0.0), ties to the lower id; fewer than ncand where fewer rows qualify.
+ *  - css_index_maxsim_candidates returns them in ASCENDING id order with their A: *n_out <= ncand entries of ids_out
+ *    and approx_out are written, the slots behind them are left alone.
+ *  - css_index_search_maxsim_pruned.  The exact score of the candidates on the codes (k_tok_scores_c through its row
+ *    list), then the k best by (score descending, id ascending), padded as css_index_search_maxsim pads; 1 <= k <=
+ *    CSS_KERNEL_MAX_K, k <= ncand.  D is exactly css_index_maxsim_rows of I, and whenever ncand >= the number of
+ *    allowed rows that are no miss the answer equals css_index_search_maxsim in bytes.  *ncand_out (may be NULL) = the
+ *    number of candidates that were scored.
+ *  - An index with a codec but no matrices returns no candidates and the padded answer.  On the device: k_tok_ctable,
+ *    k_tok_ci (its grid follows css_index_set_token_blocks; no atomics, the bits do not depend on it), an exact
+ *    multi-block radix select with an ordered compaction, k_tok_scores_c, k_sparse_topk and the part merge
+ *    (css_token_prune.h), all on the index's stream: one upload, one wait; a call never edits the index. */
+int css_index_maxsim_candidates(css_index* ix, const uint16_t* q_tok_host /* bf16 [mq, P] */, int mq, int P, int64_t ncand,
+                                const uint32_t* allow_bits_host, int64_t* ids_out /* [ncand], global, ascending */,
+                                float* approx_out /* [ncand] */, int64_t* n_out);
+int css_index_search_maxsim_pruned(css_index* ix, const uint16_t* q_tok_host /* bf16 [mq, P] */, int mq, int P, int k,
+                                   int64_t ncand, const uint32_t* allow_bits_host, float* D_host /* [k] */,
+                                   int64_t* I_host /* [k] */, int64_t* ncand_out /* may be NULL */);
+
 /* Significant terms (Elasticsearch's significant_terms aggregation, the keyword side of BERTopic): which terms set a
  * selection of rows apart from a background -- "what is in this cluster / this project / these hits".  Everything is
  * read from the term lists above; the rows' values play no part.  T = the leading rows that have lists.
