@@ -40,6 +40,8 @@ MAX_TOKEN_DIM = 128   # include/css_hip.h CSS_MAX_TOKEN_DIM
 MAX_ROW_TOKEN_VECTORS = 512   # include/css_hip.h CSS_MAX_ROW_TOKEN_VECTORS
 MAX_QUERY_TOKENS = 64   # include/css_hip.h CSS_MAX_QUERY_TOKENS
 MAX_MAXSIM_ROWS = 65536   # include/css_hip.h CSS_MAX_MAXSIM_ROWS
+MAX_MAXSIM_QUERIES = 1024   # include/css_hip.h CSS_MAX_MAXSIM_QUERIES
+MAXSIM_BATCH_GROUP = 8   # include/css_hip.h CSS_MAXSIM_BATCH_GROUP
 MAX_SIG_TERMS = 256   # include/css_hip.h CSS_MAX_SIG_TERMS
 MAX_FACET_BUCKETS = 1 << 20   # include/css_hip.h CSS_MAX_FACET_BUCKETS
 MAX_EXAMPLES = 16   # include/css_hip.h CSS_MAX_EXAMPLES
@@ -184,6 +186,8 @@ PROTOTYPES = {
     "css_index_set_token_blocks": (c_int, [c_void_p, c_int]),
     "css_index_search_maxsim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "css_index_maxsim_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "css_index_search_maxsim_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "css_index_last_maxsim_passes": (c_int, [c_void_p, POINTER(c_int)]),
     "css_index_maxsim_candidates": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                             POINTER(c_int64)]),
     "css_index_search_maxsim_pruned": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,

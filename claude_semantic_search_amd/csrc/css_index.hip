@@ -60,6 +60,10 @@
 //   k_tok_ci,          centroids, the MaxSim of every row's CENTROIDS from its 2-byte codes and that table, and an exact
 //   k_sel_*            multi-block radix select of the best ncand rows in row order (css_token_prune.h); the exact pass
 //                      over the candidates is k_tok_scores_c through its row list
+//   k_tok_scores_b     css_index_search_maxsim_batch: the MaxSim columns of a GROUP of 8 query matrices in one pass, raw
+//                      or compressed store: a block of 8 waves, one query per wave in registers, every 16-token tile
+//                      loaded (and decoded) once per block into an LDS ring in fragment order; ranked by
+//                      k_sparse_topk_cols and one part merge per group (css_tokens_batch.h)
 //   k_sig_count        css_index_subset_terms / _significant_terms: +1 per list entry of the selected rows into a
 //                      uint32 table [2^24], repeats merged in a per-block LDS table first; k_sig_score and the radix
 //                      select rank the terms (css_sigterms.h)
@@ -306,6 +310,9 @@ struct css_index {
     DevBuf<unsigned short> tk_q;
     DevBuf<uint32_t> tk_ids;
     DevBuf<float> tk_col;
+    // css_index_search_maxsim_batch: [offsets | matrices] of the batch as uploaded, and the scans of its last call
+    DevBuf<uint32_t> tk_bq;
+    int last_maxsim_passes = 0;
     // css_index_maxsim_candidates / css_index_search_maxsim_pruned (css_token_prune.h): the centroid table [C][16 MT] of
     // the call's query (at most 16 MB), the candidate rows and their approximate scores [ncand], and the select's words
     // [4 x 256 bins | threshold key, need, all, count | 2 per block of the compaction].  The approximate column is
@@ -2908,6 +2915,7 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 #include "css_sparse.h"
 #include "css_tokens.h"
 #include "css_token_codec.h"
+#include "css_tokens_batch.h"
 #include "css_token_prune.h"
 #include "css_where.h"
 #include "css_sigterms.h"
@@ -6002,6 +6010,153 @@ int css_index_search_maxsim(css_index* ix, const uint16_t* q_tok_host, int mq, i
     rc = hc.upload(allow_bits_host, ix->tk_q, (const unsigned short*)q_tok_host, (size_t)mq * P, (size_t)k);
     if (rc == CSS_OK) rc = search_maxsim_enqueue(ix, hc.rows, ix->tk_q.p, mq, k, hc.d_out, hc.i_out, ix->stream);
     return hc.finish(rc, D_host, I_host);
+}
+
+namespace {
+constexpr int kTokGroup = CSS_MAXSIM_BATCH_GROUP;
+static_assert(kTokGroup >= 4 && kTokGroup <= 16, "the waves of k_tok_scores_b's block");
+
+extern "C++" template <int P, int NB>
+const void* tok_scores_b_kernel_mt(int MT) {
+    switch (MT) {
+        case 1: return (const void*)k_tok_scores_b<P, 1, NB, kTokGroup>;
+        case 2: return (const void*)k_tok_scores_b<P, 2, NB, kTokGroup>;
+        case 3: return (const void*)k_tok_scores_b<P, 3, NB, kTokGroup>;
+        default: return (const void*)k_tok_scores_b<P, 4, NB, kTokGroup>;
+    }
+}
+extern "C++" template <int P>
+const void* tok_scores_b_kernel_p(int MT, int NB) {
+    return NB == 0 ? tok_scores_b_kernel_mt<P, 0>(MT) : NB == 1 ? tok_scores_b_kernel_mt<P, 1>(MT)
+         : NB == 2 ? tok_scores_b_kernel_mt<P, 2>(MT) : tok_scores_b_kernel_mt<P, 4>(MT);
+}
+const void* tok_scores_b_kernel(int P, int MT, int NB) {
+    return P == 32 ? tok_scores_b_kernel_p<32>(MT, NB) : P == 64 ? tok_scores_b_kernel_p<64>(MT, NB)
+         : P == 96 ? tok_scores_b_kernel_p<96>(MT, NB) : tok_scores_b_kernel_p<128>(MT, NB);
+}
+
+// The MaxSim columns of a group of 2 .. kTokGroup queries (tokens q, offsets qoff [ng + 1] on the device; mq_max: the
+// longest of them) over the rows 0 .. n - 1 into col [ng][n].  n > 0 and the index has matrices.  Enqueued on `st`.
+int tok_scores_group_enqueue(css_index* ix, int64_t n, const uint32_t* mask, const unsigned short* q, const int64_t* qoff, int ng,
+                             int mq_max, float* col, hipStream_t st) {
+    const int P = ix->tk_dim, MT = (mq_max + 15) / 16, NB = ix->tk_bits;
+    const void* fn = tok_scores_b_kernel(P, MT, NB);
+    // a persistent grid of resident blocks, as in tok_scores_enqueue; a block's turn is always 16 rows
+    int64_t blocks = ix->tk_blocks;
+    if (blocks == 0) {
+        int per_cu = 0;
+        CSS_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * kTokGroup, 0));
+        blocks = (int64_t)std::max(per_cu, 1) * ix->num_cus;
+    }
+    blocks = std::min<int64_t>(blocks, (n + kTokTurn - 1) / kTokTurn);
+    const unsigned short *tok = ix->tk_tok.p, *codes = ix->tk_code.p, *cent = ix->tk_cent.p;
+    const unsigned char* res = ix->tk_res.p;
+    const float* wts = NB ? ix->tk_cw.p + 16 : nullptr;
+    const int64_t* off = ix->tk_off.p;
+    int64_t nlist = ix->tk_rows;
+    void* args[] = {&tok, &codes, &res, &cent, &wts, &off, &nlist, &n, &mask, &q, &qoff, &ng, &col};
+    ProfScope ps(NB ? "tok_scores_bc" : "tok_scores_b", st);
+    CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * kTokGroup), args, 0, st));
+    return CSS_OK;
+}
+
+// css_index_search_maxsim_batch on the device: per group the columns, their top-k by slices and ONE part merge for the
+// group's queries.  qoff_h: the host's offsets; q_dev / qoff_dev: the uploaded batch.  Caller holds ws_mu and a shared
+// lock on mu.
+int search_maxsim_batch_enqueue(css_index* ix, const Rows& rows, const unsigned short* q_dev, const int64_t* qoff_dev,
+                                const int64_t* qoff_h, int nq, int k, float* D_dev, int64_t* I_dev, hipStream_t st) {
+    const char* who = "css_index_search_maxsim_batch";
+    int rc;
+    WsTurn turn(ix, st);
+    if (turn.rc != CSS_OK) return turn.rc;
+    ix->last_maxsim_passes = 0;
+    if (ix->tk_rows == 0 || rows.n == 0) {
+        const int total = nq * k;
+        hipLaunchKernelGGL(k_sparse_pad, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, D_dev, I_dev, total);
+        CSS_LAUNCH_CHECK();
+        return CSS_OK;
+    }
+    CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "%s: %lld rows exceed the 32-bit row numbers of the lists", who, (long long)rows.n);
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    const int64_t slice = sparse_topk_slice(rows.n);
+    const int parts = (int)((rows.n + slice - 1) / slice);
+    const int gmax = std::min(nq, kTokGroup);
+    if ((rc = ix->lex_col.grow((size_t)rows.n * gmax)) != CSS_OK) return rc;
+    if ((rc = ix->sp_pd.grow((size_t)parts * gmax * k)) != CSS_OK) return rc;
+    if ((rc = ix->sp_pi.grow((size_t)parts * gmax * k)) != CSS_OK) return rc;
+    for (int q0 = 0; q0 < nq; q0 += kTokGroup) {
+        const int ng = std::min(kTokGroup, nq - q0);
+        if (ng == 1) {   // the single call's kernel
+            if ((rc = tok_scores_enqueue(ix, nullptr, rows.n, rows.mask, q_dev + (size_t)qoff_h[q0] * ix->tk_dim,
+                                         (int)(qoff_h[q0 + 1] - qoff_h[q0]), ix->lex_col.p, st)) != CSS_OK) return rc;
+        } else {
+            int mq_max = 0;
+            for (int b = q0; b < q0 + ng; ++b) mq_max = std::max(mq_max, (int)(qoff_h[b + 1] - qoff_h[b]));
+            if ((rc = tok_scores_group_enqueue(ix, rows.n, rows.mask, q_dev, qoff_dev + q0, ng, mq_max, ix->lex_col.p, st)) != CSS_OK)
+                return rc;
+        }
+        ++ix->last_maxsim_passes;
+        {
+            ProfScope ps("sparse_topk", st);
+            hipLaunchKernelGGL(k_sparse_topk_cols, dim3((unsigned)parts, (unsigned)ng), dim3(256), 0, st, (const float*)ix->lex_col.p,
+                               rows.n, slice, rows.mask, k, rows.id_base, ix->sp_pd.p, ix->sp_pi.p);
+            CSS_LAUNCH_CHECK();
+        }
+        if ((rc = merge_parts(ix->sp_pd.p, ix->sp_pi.p, parts, (int64_t)ng * k, (int64_t)ng * k, ng, k, CSS_METRIC_IP,
+                              D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, ix->device, st, who)) != CSS_OK) return rc;
+    }
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_search_maxsim_batch(css_index* ix, const uint16_t* q_tok_host, const int64_t* q_offsets_host, int nq, int P, int k,
+                                  const uint32_t* allow_bits_host, float* D_host, int64_t* I_host) {
+    const char* fn = "css_index_search_maxsim_batch";
+    CSS_REQUIRE(ix, "%s: NULL index", fn);
+    CSS_REQUIRE(nq >= 1 && nq <= CSS_MAX_MAXSIM_QUERIES, "%s: nq=%d outside [1, %d]", fn, nq, CSS_MAX_MAXSIM_QUERIES);
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "%s: k=%d outside [1, %d]", fn, k, CSS_KERNEL_MAX_K);
+    CSS_REQUIRE(q_tok_host && q_offsets_host && D_host && I_host, "%s: NULL buffer", fn);
+    CSS_REQUIRE(token_dim_ok(P), "%s: P=%d must be a multiple of 32 in [32, %d]", fn, P, CSS_MAX_TOKEN_DIM);
+    CSS_REQUIRE(q_offsets_host[0] == 0, "%s: the offsets start at %lld, not at 0", fn, (long long)q_offsets_host[0]);
+    for (int b = 0; b < nq; ++b) {
+        const int64_t mq = q_offsets_host[b + 1] - q_offsets_host[b];
+        CSS_REQUIRE(mq >= 1 && mq <= CSS_MAX_QUERY_TOKENS, "%s: query %d has %lld tokens, outside [1, %d]", fn, b, (long long)mq,
+                    CSS_MAX_QUERY_TOKENS);
+    }
+    for (int b = 0; b < nq; ++b) {
+        const uint16_t* qb = q_tok_host + (size_t)q_offsets_host[b] * P;
+        const int cnt = (int)(q_offsets_host[b + 1] - q_offsets_host[b]) * P;
+        for (int i = 0; i < cnt; ++i)
+            CSS_REQUIRE(bf16_finite(qb[i]), "%s: component %d of token %d of query %d is %s", fn, i % P, i / P, b,
+                        (qb[i] & 0x7Fu) ? "NaN" : "infinite");
+    }
+    // the ONE upload: [offsets (int64) | the matrices], the matrices behind the offsets at a multiple of 16 bytes
+    const size_t ntok = (size_t)q_offsets_host[nq];
+    const size_t at = ((size_t)(nq + 1) * 2 + 3) / 4 * 4, q_words = ntok * P / 2;   // (P is even)
+    std::vector<uint32_t> in;
+    try {
+        in.assign(at + q_words, 0u);
+    } catch (const std::bad_alloc&) {
+        css::set_error("%s: out of host memory", fn);
+        return CSS_ERR_OOM;
+    }
+    memcpy(in.data(), q_offsets_host, (size_t)(nq + 1) * sizeof(int64_t));
+    memcpy(in.data() + at, q_tok_host, ntok * P * sizeof(uint16_t));
+    HostCall hc(ix);
+    CSS_REQUIRE(ix->tk_rows == 0 || P == ix->tk_dim, "%s: the queries have P=%d, the stored matrices P=%d", fn, P, ix->tk_dim);
+    int rc = hc.upload(allow_bits_host, ix->tk_bq, (const uint32_t*)in.data(), in.size(), (size_t)nq * k);
+    if (rc == CSS_OK)
+        rc = search_maxsim_batch_enqueue(ix, hc.rows, reinterpret_cast<const unsigned short*>(ix->tk_bq.p + at),
+                                         reinterpret_cast<const int64_t*>(ix->tk_bq.p), q_offsets_host, nq, k, hc.d_out, hc.i_out,
+                                         ix->stream);
+    return hc.finish(rc, D_host, I_host);
+}
+
+int css_index_last_maxsim_passes(css_index* ix, int* passes_out) {
+    CSS_REQUIRE(ix && passes_out, "css_index_last_maxsim_passes: NULL argument");
+    std::lock_guard<std::mutex> wl(ix->ws_mu);
+    *passes_out = ix->last_maxsim_passes;
+    return CSS_OK;
 }
 
 int css_index_maxsim_rows(css_index* ix, const uint16_t* q_tok_host, int mq, int P, const int64_t* ids_host, int64_t n,

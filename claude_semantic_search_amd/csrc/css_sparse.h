@@ -139,10 +139,10 @@ __global__ __launch_bounds__(256) void k_sparse_move(const unsigned long long* _
 }
 
 // The k best rows of col[0, n) that are not -inf and whose mask bit is set (mask null: every row), larger first, ties
-// to the lower row: block b's list into Dp / Ip [b][k] (global ids; -1 and -inf in empty slots).
-__global__ __launch_bounds__(256) void k_sparse_topk(const float* __restrict__ col, int64_t n, int64_t slice,
-                                                     const uint32_t* __restrict__ mask, int k, int64_t id_base,
-                                                     float* __restrict__ Dp, int64_t* __restrict__ Ip) {
+// to the lower row: block b's list (slice b of the column) into Dl / Il [k] (global ids; -1 and -inf in empty slots).
+__device__ __forceinline__ void sparse_topk_block(const float* __restrict__ col, int64_t n, int64_t slice,
+                                                  const uint32_t* __restrict__ mask, int k, int64_t id_base,
+                                                  float* __restrict__ Dl, int64_t* __restrict__ Il) {
     __shared__ float ls[kWaves][CSS_KERNEL_MAX_K];
     __shared__ uint32_t li[kWaves][CSS_KERNEL_MAX_K];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -176,9 +176,23 @@ __global__ __launch_bounds__(256) void k_sparse_topk(const float* __restrict__ c
         }
     for (int i = lane; i < k; i += 64) {
         const uint32_t id = li[0][i];
-        Dp[(size_t)blockIdx.x * k + i] = ls[0][i];
-        Ip[(size_t)blockIdx.x * k + i] = id == kInvalidRow ? (int64_t)-1 : id_base + (int64_t)id;
+        Dl[i] = ls[0][i];
+        Il[i] = id == kInvalidRow ? (int64_t)-1 : id_base + (int64_t)id;
     }
+}
+// block b's list into Dp / Ip [b][k]
+__global__ __launch_bounds__(256) void k_sparse_topk(const float* __restrict__ col, int64_t n, int64_t slice,
+                                                     const uint32_t* __restrict__ mask, int k, int64_t id_base,
+                                                     float* __restrict__ Dp, int64_t* __restrict__ Ip) {
+    sparse_topk_block(col, n, slice, mask, k, id_base, Dp + (size_t)blockIdx.x * k, Ip + (size_t)blockIdx.x * k);
+}
+// The same over the gridDim.y columns col[y][n] of a group of queries: block (b, y)'s list into Dp / Ip [b][y][k], the
+// part layout of merge_parts with nq = gridDim.y.
+__global__ __launch_bounds__(256) void k_sparse_topk_cols(const float* __restrict__ col, int64_t n, int64_t slice,
+                                                          const uint32_t* __restrict__ mask, int k, int64_t id_base,
+                                                          float* __restrict__ Dp, int64_t* __restrict__ Ip) {
+    const size_t o = ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * k;
+    sparse_topk_block(col + (size_t)blockIdx.y * (size_t)n, n, slice, mask, k, id_base, Dp + o, Ip + o);
 }
 
 // D / I of css_index_search_sparse where nothing can hit: every slot padded

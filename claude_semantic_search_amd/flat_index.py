@@ -453,6 +453,8 @@ def sparse_as_csr(vectors, what: str = "set_sparse") -> Tuple[np.ndarray, np.nda
 MAX_QUERY_TOKENS = nat.MAX_QUERY_TOKENS
 MAX_ROW_TOKEN_VECTORS = nat.MAX_ROW_TOKEN_VECTORS
 MAX_MAXSIM_ROWS = nat.MAX_MAXSIM_ROWS
+MAX_MAXSIM_QUERIES = nat.MAX_MAXSIM_QUERIES
+MAXSIM_BATCH_GROUP = nat.MAXSIM_BATCH_GROUP
 
 
 def _bf16_bits(m, what: str, name: str) -> np.ndarray:
@@ -558,6 +560,26 @@ def maxsim_args(q_mat, k=None, ids=None, what: str = "search_maxsim"):
         if ids.shape[0] > MAX_MAXSIM_ROWS:
             raise ValueError(f"{what}: {ids.shape[0]} ids (at most {MAX_MAXSIM_ROWS})")
     return q, k, ids
+
+
+def maxsim_batch_args(q_mats, k, what: str = "search_maxsim_batch"):
+    """The checked arguments of a batched MaxSim call: ``(offsets int64 [nq + 1], tokens uint16 [offsets[nq], P], k)``;
+    what the library would refuse raises ``ValueError`` here and names the query.  ``q_mats`` is a sequence of 1 to 1024
+    ``[mq_b, P]`` matrices, each as ``maxsim_args`` takes one, all of one P; ``1 <= k <= 128``."""
+    mats = list(q_mats)
+    if not 1 <= len(mats) <= MAX_MAXSIM_QUERIES:
+        raise ValueError(f"{what}: {len(mats)} queries outside [1, {MAX_MAXSIM_QUERIES}]")
+    qs, P = [], 0
+    for b, m in enumerate(mats):
+        q, _, _ = maxsim_args(m, what=f"{what}: query {b}")
+        if P and q.shape[1] != P:
+            raise ValueError(f"{what}: query {b} has P={q.shape[1]}, the queries before it P={P}")
+        P = q.shape[1]
+        qs.append(q)
+    _, k, _ = maxsim_args(qs[0], k, what=what)
+    off = np.zeros(len(qs) + 1, dtype=np.int64)
+    np.cumsum([q.shape[0] for q in qs], out=off[1:])
+    return off, np.ascontiguousarray(np.concatenate(qs), dtype=np.uint16), k
 
 
 MAX_TOKEN_CENTROIDS = 65536   # CSS_MAX_TOKEN_CENTROIDS
@@ -1920,6 +1942,28 @@ class IndexFlat:
         nat.check(nat.lib().css_index_search_maxsim(h, q.ctypes.data, q.shape[0], q.shape[1], k, bits_ptr, D.ctypes.data,
                                                     I.ctypes.data))
         return D, I
+
+    def search_maxsim_batch(self, q_mats, k: int, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``search_maxsim`` for a sequence of up to 1024 query matrices in one call
+        (``css_index_search_maxsim_batch``): ``(D [nq, k], I [nq, k])``, row ``b`` the bytes of
+        ``search_maxsim(q_mats[b], k, allow)``.  The token store is read once per group of ``MAXSIM_BATCH_GROUP``
+        queries, not once per query; ``allow`` is ONE mask for all of them."""
+        off, tok, k = maxsim_batch_args(q_mats, k)
+        nq = off.shape[0] - 1
+        D, I = np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int64)
+        h = self._handle()
+        bits, bits_ptr = self._allow_bits(allow)
+        nat.check(nat.lib().css_index_search_maxsim_batch(h, tok.ctypes.data, off.ctypes.data, nq, tok.shape[1], k, bits_ptr,
+                                                          D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    @property
+    def last_maxsim_passes(self) -> int:
+        """Diagnostics: the scans of the token store the last ``search_maxsim_batch`` call made, ``ceil(nq /
+        MAXSIM_BATCH_GROUP)``; 0 when it returned padding without scanning."""
+        n = ctypes.c_int(0)
+        nat.check(nat.lib().css_index_last_maxsim_passes(self._handle(), ctypes.byref(n)))
+        return int(n.value)
 
     def maxsim_ids(self, q_mat, ids) -> np.ndarray:
         """The MaxSim scores of the rows named by GLOBAL ``ids`` (any order, repeats allowed, at most 65536) for ONE

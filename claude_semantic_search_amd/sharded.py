@@ -853,6 +853,18 @@ class ShardedFlatIndex:
         I, (D,), _ = self._columns(I, (D,), metric=0)
         return tuple(np.ascontiguousarray(a[..., :k]) for a in (D, I))
 
+    def search_maxsim_batch(self, q_mats, k: int, allow=None):
+        """``IndexFlat.search_maxsim_batch`` over the shards (collective): ``(D [nq, k], I [nq, k])`` with global ids on
+        every rank, row ``b`` the bytes of ``search_maxsim(q_mats[b], k, allow)``: the local batch call, then the column
+        exchange of ``search_maxsim`` for all queries at once."""
+        from .flat_index import maxsim_batch_args
+
+        off, tok, k = maxsim_batch_args(q_mats, k)
+        D, I = self.local.search_maxsim_batch([tok[off[b]:off[b + 1]] for b in range(off.shape[0] - 1)], k,
+                                              allow=self._local_allow(allow))
+        I, (D,), _ = self._columns(I, (D,), metric=0)
+        return tuple(np.ascontiguousarray(a[..., :k]) for a in (D, I))
+
     def maxsim_ids(self, q_mat, ids) -> np.ndarray:
         """``IndexFlat.maxsim_ids`` of GLOBAL ``ids`` on every rank (collective): every id is routed to the shard that
         owns it through the segment table, the other shards contribute zero bits, then ONE ``_sum_over_ranks`` of the
@@ -1291,6 +1303,9 @@ class ShardedIndexFacade:
 
     def search_maxsim(self, q_mat, k: int, allow=None):
         return self.sh.search_maxsim(q_mat, int(k), allow=allow)
+
+    def search_maxsim_batch(self, q_mats, k: int, allow=None):
+        return self.sh.search_maxsim_batch(q_mats, int(k), allow=allow)
 
     def maxsim_ids(self, q_mat, ids) -> np.ndarray:
         return self.sh.maxsim_ids(q_mat, ids)

@@ -34,7 +34,7 @@ import threading
 from dataclasses import dataclass
 from datetime import datetime, timezone
 from pathlib import Path
-from typing import Any, Callable, Dict, List, NamedTuple, Optional, Tuple
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -1423,6 +1423,44 @@ class HybridStorage:
             return self.faiss_index.search_maxsim(q_mat, k, allow=allow)
 
         return self._ranked_in_index(None, config, filters, fi.MAX_HYBRID_K, run)
+
+    def search_late_many(self, query_texts: Sequence[str], late, config: Optional[SearchConfig] = None,
+                         filters: Optional[Dict[str, Any]] = None) -> List[List[SearchResult]]:
+        """``search_late`` for several queries at once: element ``i`` equals ``search_late(query_texts[i], late, config,
+        filters)`` in ids and score bits.  One ``late.encode_queries`` call (each query in a forward pass of its own, as
+        ``search_late`` encodes it), ONE allow mask and one ``IndexFlat.search_maxsim_batch`` -- the
+        token store is read once per group of queries, not once per query.  Where ``search_late`` goes through
+        ``search_maxsim_pruned`` (``late_candidates > 0`` on an index with a token codec) the candidate sets differ per
+        query and nothing is shared: the queries then run as single pruned calls."""
+        self._require("late-interaction search", "set_tokens", "search_maxsim", "search_maxsim_batch")
+        texts = [t or "" for t in query_texts]
+        if not texts:
+            return []
+        with self._lock:
+            frame = self._search_frame(config)
+            if frame is None or frame[0].top_k <= 0:
+                return [[] for _ in texts]
+            cfg, ntotal, _ = frame
+            allow = self._allow_for(filters, ntotal, tombstones_always=True)
+            k = cfg.top_k if (self.config.filter_pushdown or not filters) else max(cfg.top_k, cfg.max_results)
+            k = max(1, min(k, fi.MAX_HYBRID_K))
+            self._sync_tokens(ntotal, late)
+            # (one query per forward pass: the encoder picks its tiling by the tokens of a batch, so a query encoded
+            # beside others can differ in the last bits of its bf16 tokens from the matrix search_late forms for it)
+            q_mats = late.encode_queries(texts, batch_size=1)[0]
+            ncand = int(self.config.late_candidates)
+            if ncand > 0 and getattr(self.faiss_index, "token_codec_bits", 0) and hasattr(self.faiss_index, "search_maxsim_pruned"):
+                pairs = [self.faiss_index.search_maxsim_pruned(q, k, min(max(ncand, k), fi.MAX_MAXSIM_ROWS), allow=allow)
+                         for q in q_mats]
+                sims, ids = np.concatenate([p[0] for p in pairs]), np.concatenate([p[1] for p in pairs])
+            else:
+                sims, ids = [], []
+                for b0 in range(0, len(q_mats), fi.MAX_MAXSIM_QUERIES):
+                    d, i = self.faiss_index.search_maxsim_batch(q_mats[b0:b0 + fi.MAX_MAXSIM_QUERIES], k, allow=allow)
+                    sims.append(d)
+                    ids.append(i)
+                sims, ids = np.concatenate(sims), np.concatenate(ids)
+            return [self._results_in_rank_order(sims[b].tolist(), ids[b].tolist(), cfg, filters) for b in range(len(texts))]
 
     def search_reranked(self, query_text: str, query_embedding, reranker, config: Optional[SearchConfig] = None,
                         filters: Optional[Dict[str, Any]] = None, fetch: int = 50) -> List[Reranked]:

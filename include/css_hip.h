@@ -582,6 +582,30 @@ int css_index_search_maxsim_pruned(css_index* ix, const uint16_t* q_tok_host /* 
                                    int64_t ncand, const uint32_t* allow_bits_host, float* D_host /* [k] */,
                                    int64_t* I_host /* [k] */, int64_t* ncand_out /* may be NULL */);
 
+/* Batched MaxSim search: nq query matrices per call, the token store read once per GROUP of CSS_MAXSIM_BATCH_GROUP
+ * queries instead of once per query.  The matrices lie one behind the other in q_tok_host: query b owns tokens
+ * [q_offsets_host[b], q_offsets_host[b + 1]) (offsets from 0, ascending), all of one width P.
+ *  - Limits.  1 <= nq <= CSS_MAX_MAXSIM_QUERIES, 1 <= k <= 128, every query 1 .. CSS_MAX_QUERY_TOKENS tokens with
+ *    finite components, P as in css_index_search_maxsim.  allow_bits_host is ONE mask for all queries, as in
+ *    css_index_search_masked.  A refusal names the offending query (and token) and comes before anything is enqueued.
+ *  - Result.  Row b of D / I [nq, k] is, byte for byte, what css_index_search_maxsim returns for query b with the same
+ *    k and mask: the score above, padding, id_base, rows >= T, empty rows, an index without matrices; on raw and on
+ *    compressed stores.  The bits do not depend on the group a query falls into, on its slot, or on the grid.
+ *  - On the device.  Per group of G queries: k_tok_scores_b (css_tokens_batch.h: a block of G waves, one query per
+ *    wave, every 16-token tile loaded -- and on a compressed store decoded -- once per block and shared through LDS),
+ *    k_sparse_topk over the G columns, ONE part merge for the G queries.  A group of one query (nq = 1, or a remainder
+ *    of one) runs k_tok_scores / k_tok_scores_c as css_index_search_maxsim does.  Groups run back to back on the
+ *    index's stream; the column workspace is G x rows x 4 bytes whatever nq.  One upload (offsets and matrices), one
+ *    wait; the call never edits the index.  css_index_set_token_blocks sets the grid of k_tok_scores_b as well.
+ *  - css_index_last_maxsim_passes: the scans of the store the last batch call made, ceil(nq / G); 0 when it returned
+ *    padding without scanning (no matrices, no rows).  A diagnostic, as css_index_last_group_passes is. */
+#define CSS_MAX_MAXSIM_QUERIES 1024
+#define CSS_MAXSIM_BATCH_GROUP 8
+int css_index_search_maxsim_batch(css_index* ix, const uint16_t* q_tok_host /* bf16 [q_offsets[nq], P] */,
+                                  const int64_t* q_offsets_host /* [nq + 1], from 0 */, int nq, int P, int k,
+                                  const uint32_t* allow_bits_host, float* D_host /* [nq, k] */, int64_t* I_host /* [nq, k] */);
+int css_index_last_maxsim_passes(css_index* ix, int* passes_out);
+
 /* Significant terms (Elasticsearch's significant_terms aggregation, the keyword side of BERTopic): which terms set a
  * selection of rows apart from a background -- "what is in this cluster / this project / these hits".  Everything is
  * read from the term lists above; the rows' values play no part.  T = the leading rows that have lists.
