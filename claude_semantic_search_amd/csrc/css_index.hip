@@ -50,16 +50,18 @@
 //   k_sparse_topk      sparse vectors; ranked alone by slices of the column and the part merge, or handed to
 //                      k_scan_prior like the BM25 column (css_sparse.h).   HBM bound up to 32 terms
 //   k_tok_scores       css_index_search_maxsim / css_index_maxsim_rows: the MaxSim column of one query matrix over the
-//                      per-row token matrices, bf16 MFMA with the query in registers, a persistent grid; ranked by
-//                      k_sparse_topk and the part merge (css_tokens.h).   HBM bound
-//   k_tok_scores_c,    the same column over COMPRESSED matrices (css_index_set_token_codec: centroid id + residual
-//   k_tok_encode,      buckets per token): the B fragment is decoded in registers from codes, packed buckets and a
-//   k_tok_decode       gathered centroid row; the encoder (argmax over centroids on the bf16 MFMA, buckets, packing)
-//                      and the decoder of css_index_set_tokens / _get_tokens (css_token_codec.h)
+//                      per-row token matrices, bf16 MFMA with the query in registers, a persistent grid; raw matrices
+//                      (NB = 0) or COMPRESSED ones (NB = 1, 2, 4), whose B fragment is decoded in registers from codes,
+//                      packed buckets and a gathered centroid row; ranked by k_sparse_topk_cols and the part merge.
+//                      css_tokens.h, which also holds the ONE copy of the turn's head and tail, the query fragments,
+//                      the staged tile and the tile step that k_tok_scores_b and k_tok_ci share.   HBM bound
+//   k_tok_encode,      the token codec (css_index_set_token_codec: centroid id + residual buckets per token): the
+//   k_tok_decode,      encoder (argmax over centroids on the bf16 MFMA, buckets, packing), the decoder of
+//   k_tok_move_units   css_index_set_tokens / _get_tokens and the mover of css_index_remove_rows (css_token_codec.h)
 //   k_tok_ctable,      css_index_maxsim_candidates / css_index_search_maxsim_pruned: the query's dots with the codec's
 //   k_tok_ci,          centroids, the MaxSim of every row's CENTROIDS from its 2-byte codes and that table, and an exact
 //   k_sel_*            multi-block radix select of the best ncand rows in row order (css_token_prune.h); the exact pass
-//                      over the candidates is k_tok_scores_c through its row list
+//                      over the candidates is k_tok_scores through its row list
 //   k_tok_scores_b     css_index_search_maxsim_batch: the MaxSim columns of a GROUP of 8 query matrices in one pass, raw
 //                      or compressed store: a block of 8 waves, one query per wave in registers, every 16-token tile
 //                      loaded (and decoded) once per block into an LDS ring in fragment order; ranked by
@@ -2013,6 +2015,22 @@ int sweep_unrolled(const css_index* ix, bool main_stage, F&& f) {
     if (ix->dpad == 768) return main_stage ? f(IntC<TT768>(), std::true_type()) : f(IntC<TT768>(), std::false_type());
     return f(IntC<0>(), std::false_type());
 }
+// The same for the token kernels, whose instantiations are taken as const void* (the callers have checked the ranges).
+// tok_dim: f(P) with the token width P = 32 / 64 / 96 / 128.  tok_variant: f(P, MT, NB) with MT = 1 .. 4 tiles of 16
+// query tokens and NB = 0 (a raw store) / 1 / 2 / 4 bits of a bucket.
+template <typename F>
+const void* tok_dim(int P, F&& f) {
+    return P == 32 ? f(IntC<32>()) : P == 64 ? f(IntC<64>()) : P == 96 ? f(IntC<96>()) : f(IntC<128>());
+}
+template <typename F>
+const void* tok_variant(int P, int MT, int NB, F&& f) {
+    return tok_dim(P, [&](auto p) {
+        auto tiles = [&](auto nb) -> const void* {
+            return MT == 1 ? f(p, IntC<1>(), nb) : MT == 2 ? f(p, IntC<2>(), nb) : MT == 3 ? f(p, IntC<3>(), nb) : f(p, IntC<4>(), nb);
+        };
+        return NB == 0 ? tiles(IntC<0>()) : NB == 1 ? tiles(IntC<1>()) : NB == 2 ? tiles(IntC<2>()) : tiles(IntC<4>());
+    });
+}
 
 template <int NQ, int TT, int METRIC, bool FIX>
 int launch_scan_small_t(css_index* ix, const Rows& rows, const float* qpad, int nq_real, int k, int* gthr, const SweepGeom& sg,
@@ -2913,8 +2931,8 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 #include "css_knn_prior.h"
 #include "css_lexical.h"
 #include "css_sparse.h"
-#include "css_tokens.h"
 #include "css_token_codec.h"
+#include "css_tokens.h"
 #include "css_tokens_batch.h"
 #include "css_token_prune.h"
 #include "css_where.h"
@@ -3642,7 +3660,7 @@ int compact_sparse(css_index* ix, const uint32_t* keep, SparseCompaction* sc) {
     return CSS_OK;
 }
 
-// The token matrices through the same keep bits, OUT OF PLACE like compact_sparse, with k_tok_move.
+// The token matrices through the same keep bits, OUT OF PLACE like compact_sparse, with k_tok_move_units.
 struct TokenCompaction {
     DevBuf<unsigned short> tok, code;   // (a compressed store: code and res in place of tok)
     DevBuf<unsigned char> res;
@@ -3701,7 +3719,7 @@ int compact_tokens(css_index* ix, const uint32_t* keep, TokenCompaction* tc) {
                            (const int64_t*)ix->tk_off.p, (const uint32_t*)tc->map.p, (const int64_t*)tc->off.p, T, (int)(RB / 4),
                            reinterpret_cast<uint32_t*>(tc->res.p));
     } else {
-        hipLaunchKernelGGL(k_tok_move, grid, dim3(256), 0, st, reinterpret_cast<const uint4*>(ix->tk_tok.p),
+        hipLaunchKernelGGL(k_tok_move_units<uint4>, grid, dim3(256), 0, st, reinterpret_cast<const uint4*>(ix->tk_tok.p),
                            (const int64_t*)ix->tk_off.p, (const uint32_t*)tc->map.p, (const int64_t*)tc->off.p, T, (int)(P / 8),
                            reinterpret_cast<uint4*>(tc->tok.p));
     }
@@ -5555,18 +5573,13 @@ inline bool token_dim_ok(int P) { return P >= 32 && P <= CSS_MAX_TOKEN_DIM && P 
 namespace {
 constexpr int64_t kTokCodecPass = 1 << 18;   // tokens of one staging pass of encode / decode (64 MiB of bf16 at P = 128)
 
-const void* tok_encode_kernel(int P) {
-    return P == 32 ? (const void*)k_tok_encode<32> : P == 64 ? (const void*)k_tok_encode<64> : P == 96 ? (const void*)k_tok_encode<96>
-                                                                                                        : (const void*)k_tok_encode<128>;
-}
-
 // nE raw tokens on the host -> codes and packed buckets from token E0 on, through a staging buffer that dies with the
 // call: the raw tokens never stay in HBM.  Enqueued on `st`; the caller waits before `raw` goes.
 int tok_encode_enqueue(css_index* ix, const uint16_t* tok_host, int64_t E0, int64_t nE, DevBuf<unsigned short>& raw, hipStream_t st) {
     const size_t P = (size_t)ix->tk_dim, RB = P * (size_t)ix->tk_bits / 8;
     int rc;
     if ((rc = raw.grow_exact((size_t)std::min(nE, kTokCodecPass) * P, "hipMalloc(token staging)")) != CSS_OK) return rc;
-    const void* fn = tok_encode_kernel((int)P);
+    const void* fn = tok_dim((int)P, [](auto p) { return (const void*)k_tok_encode<decltype(p)::value>; });
     for (int64_t c0 = 0; c0 < nE; c0 += kTokCodecPass) {
         int64_t m = std::min(kTokCodecPass, nE - c0);
         CSS_HIP_TRY(hipMemcpyAsync(raw.p, tok_host + (size_t)c0 * P, (size_t)m * P * sizeof(uint16_t), hipMemcpyHostToDevice, st));
@@ -5882,43 +5895,56 @@ int css_index_set_token_blocks(css_index* ix, int blocks) {
 }
 
 namespace {
-// the checks that css_index_search_maxsim and css_index_maxsim_rows make of a query matrix
-int token_query_check(const char* fn, const uint16_t* q_tok_host, int mq, int P) {
-    CSS_REQUIRE(mq >= 1 && mq <= CSS_MAX_QUERY_TOKENS, "%s: mq=%d outside [1, %d]", fn, mq, CSS_MAX_QUERY_TOKENS);
-    CSS_REQUIRE(token_dim_ok(P), "%s: P=%d must be a multiple of 32 in [32, %d]", fn, P, CSS_MAX_TOKEN_DIM);
-    CSS_REQUIRE(q_tok_host, "%s: NULL buffer", fn);
-    for (int i = 0; i < mq * P; ++i)
-        CSS_REQUIRE(bf16_finite(q_tok_host[i]), "%s: component %d of query token %d is %s", fn, i % P, i / P,
-                    (q_tok_host[i] & 0x7Fu) ? "NaN" : "infinite");
+// The checks that every MaxSim call makes of a query matrix.  The length and the components are two halves, so that
+// css_index_search_maxsim_batch makes each of ALL its queries before the next (b >= 0: query b of a batch).
+int token_len_check(const char* fn, int64_t mq, int b) {
+    if (b < 0) CSS_REQUIRE(mq >= 1 && mq <= CSS_MAX_QUERY_TOKENS, "%s: mq=%d outside [1, %d]", fn, (int)mq, CSS_MAX_QUERY_TOKENS);
+    else CSS_REQUIRE(mq >= 1 && mq <= CSS_MAX_QUERY_TOKENS, "%s: query %d has %lld tokens, outside [1, %d]", fn, b, (long long)mq,
+                     CSS_MAX_QUERY_TOKENS);
     return CSS_OK;
 }
-
-extern "C++" template <int P>
-const void* tok_scores_kernel(int MT) {
-    switch (MT) {
-        case 1: return (const void*)k_tok_scores<P, 1>;
-        case 2: return (const void*)k_tok_scores<P, 2>;
-        case 3: return (const void*)k_tok_scores<P, 3>;
-        default: return (const void*)k_tok_scores<P, 4>;
+int token_finite_check(const char* fn, const uint16_t* q, int mq, int P, int b) {
+    for (int i = 0; i < mq * P; ++i) {
+        if (bf16_finite(q[i])) continue;
+        const char* what = (q[i] & 0x7Fu) ? "NaN" : "infinite";
+        if (b < 0) CSS_REQUIRE(false, "%s: component %d of query token %d is %s", fn, i % P, i / P, what);
+        else CSS_REQUIRE(false, "%s: component %d of token %d of query %d is %s", fn, i % P, i / P, b, what);
     }
+    return CSS_OK;
+}
+int token_query_check(const char* fn, const uint16_t* q_tok_host, int mq, int P) {
+    const int rc = token_len_check(fn, mq, -1);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(token_dim_ok(P), "%s: P=%d must be a multiple of 32 in [32, %d]", fn, P, CSS_MAX_TOKEN_DIM);
+    CSS_REQUIRE(q_tok_host, "%s: NULL buffer", fn);
+    return token_finite_check(fn, q_tok_host, mq, P, -1);
 }
 
-extern "C++" template <int P, int NB>
-const void* tok_scores_c_kernel_mt(int MT) {
-    switch (MT) {
-        case 1: return (const void*)k_tok_scores_c<P, 1, NB>;
-        case 2: return (const void*)k_tok_scores_c<P, 2, NB>;
-        case 3: return (const void*)k_tok_scores_c<P, 3, NB>;
-        default: return (const void*)k_tok_scores_c<P, 4, NB>;
+constexpr int kTokGroup = CSS_MAXSIM_BATCH_GROUP;
+static_assert(kTokGroup >= 4 && kTokGroup <= 16, "the waves of k_tok_scores_b's block");
+
+// the store as the kernels take it (css_tokens.h): a raw store has tokens, a compressed one codes, packed buckets, the
+// centroid table and the 16 weights
+TokStore tok_store(const css_index* ix) {
+    return TokStore{ix->tk_tok.p, ix->tk_code.p,  ix->tk_res.p, ix->tk_cent.p, ix->tk_bits ? ix->tk_cw.p + 16 : nullptr,
+                    ix->tk_off.p, ix->tk_rows};
+}
+
+// The grid of a token kernel `fn` (blocks of `threads` threads, `turns` turns at a time per block) over n > 0 rows: as
+// many blocks as stay resident (no block waits for another, so the figure only sets the speed), and into *per the rows
+// of a turn: kTokTurn for a scan, fewer where that would leave waves idle (per == null: the kernel's turn is always
+// kTokTurn rows).  css_index_set_token_blocks fixes the grid and with it kTokTurn rows per turn.
+int tok_grid(const css_index* ix, const void* fn, int threads, int64_t n, int turns, int* per, unsigned* grid) {
+    int64_t blocks = ix->tk_blocks, rows = kTokTurn;
+    if (blocks == 0) {
+        int per_cu = 0;
+        CSS_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0));
+        blocks = (int64_t)std::max(per_cu, 1) * ix->num_cus;
+        if (per) rows = std::min<int64_t>(kTokTurn, (n + blocks * turns - 1) / (blocks * turns));
     }
-}
-extern "C++" template <int P>
-const void* tok_scores_c_kernel_p(int MT, int NB) {
-    return NB == 1 ? tok_scores_c_kernel_mt<P, 1>(MT) : NB == 2 ? tok_scores_c_kernel_mt<P, 2>(MT) : tok_scores_c_kernel_mt<P, 4>(MT);
-}
-const void* tok_scores_c_kernel(int P, int MT, int NB) {
-    return P == 32 ? tok_scores_c_kernel_p<32>(MT, NB) : P == 64 ? tok_scores_c_kernel_p<64>(MT, NB)
-         : P == 96 ? tok_scores_c_kernel_p<96>(MT, NB) : tok_scores_c_kernel_p<128>(MT, NB);
+    if (per) *per = (int)rows;
+    *grid = (unsigned)std::min<int64_t>(blocks, (n + rows * turns - 1) / (rows * turns));
+    return CSS_OK;
 }
 
 // The MaxSim column of the query (mq tokens of the index's P on the device) over positions [0, n) into `col`: the rows
@@ -5926,188 +5952,101 @@ const void* tok_scores_c_kernel(int P, int MT, int NB) {
 // n > 0 and the index has matrices.  Enqueued on `st`.
 int tok_scores_enqueue(css_index* ix, const uint32_t* rows, int64_t n, const uint32_t* mask, const unsigned short* q, int mq,
                        float* col, hipStream_t st) {
-    const int P = ix->tk_dim, MT = (mq + 15) / 16, NB = ix->tk_bits;
-    const void* fn = NB    ? tok_scores_c_kernel(P, MT, NB)
-                   : P == 32 ? tok_scores_kernel<32>(MT)
-                   : P == 64 ? tok_scores_kernel<64>(MT)
-                   : P == 96 ? tok_scores_kernel<96>(MT)
-                             : tok_scores_kernel<128>(MT);
-    // The grid: as many blocks as stay resident (no block waits for another, so the figure only sets the speed), and
-    // the rows of a wave's turn: 16 for a scan, fewer where that would leave waves idle.  css_index_set_token_blocks
-    // fixes the grid and with it 16 rows per turn
-    int64_t blocks = ix->tk_blocks;
-    int per = kTokTurn;
-    if (blocks == 0) {
-        int per_cu = 0;
-        CSS_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * kWaves, 0));
-        blocks = (int64_t)std::max(per_cu, 1) * ix->num_cus;
-        per = (int)std::min<int64_t>(kTokTurn, (n + blocks * kWaves - 1) / (blocks * kWaves));
-    }
-    blocks = std::min<int64_t>(blocks, (n + (int64_t)per * kWaves - 1) / ((int64_t)per * kWaves));
-    const unsigned short* tok = ix->tk_tok.p;
-    const int64_t* off = ix->tk_off.p;
-    int64_t nlist = ix->tk_rows;
-    if (NB) {   // a compressed store: codes, packed buckets, the centroid table and the 16 weights in place of the tokens
-        const unsigned short *codes = ix->tk_code.p, *cent = ix->tk_cent.p;
-        const unsigned char* res = ix->tk_res.p;
-        const float* wts = ix->tk_cw.p + 16;
-        void* cargs[] = {&codes, &res, &cent, &wts, &off, &nlist, &rows, &n, &mask, &q, &mq, &per, &col};
-        ProfScope ps("tok_scores_c", st);
-        CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * kWaves), cargs, 0, st));
-        return CSS_OK;
-    }
-    void* args[] = {&tok, &off, &nlist, &rows, &n, &mask, &q, &mq, &per, &col};
-    ProfScope ps("tok_scores", st);
-    CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * kWaves), args, 0, st));
+    const void* fn = tok_variant(ix->tk_dim, (mq + 15) / 16, ix->tk_bits, [](auto p, auto mt, auto nb) {
+        return (const void*)k_tok_scores<decltype(p)::value, decltype(mt)::value, decltype(nb)::value>;
+    });
+    int rc, per;
+    unsigned grid;
+    if ((rc = tok_grid(ix, fn, 64 * kWaves, n, kWaves, &per, &grid)) != CSS_OK) return rc;
+    TokStore store = tok_store(ix);
+    void* args[] = {&store, &rows, &n, &mask, &q, &mq, &per, &col};
+    ProfScope ps(ix->tk_bits ? "tok_scores_c" : "tok_scores", st);
+    CSS_HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(64 * kWaves), args, 0, st));
     return CSS_OK;
-}
-
-// The MaxSim column, its top-k by slices, and the part merge.  Everything is enqueued on `st`; nothing waits for the
-// device.  Caller holds ws_mu and a shared lock on mu.
-int search_maxsim_enqueue(css_index* ix, const Rows& rows, const unsigned short* q_dev, int mq, int k, float* D_dev,
-                          int64_t* I_dev, hipStream_t st) {
-    int rc;
-    WsTurn turn(ix, st);
-    if (turn.rc != CSS_OK) return turn.rc;
-    if (ix->tk_rows == 0 || rows.n == 0) {
-        hipLaunchKernelGGL(k_sparse_pad, dim3(1), dim3(128), 0, st, D_dev, I_dev, k);
-        CSS_LAUNCH_CHECK();
-        return CSS_OK;
-    }
-    CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "css_index_search_maxsim: %lld rows exceed the 32-bit row numbers of the lists",
-                (long long)rows.n);
-    // rows appended on another stream must have landed (the mask and the row count speak of them)
-    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
-    const int64_t slice = sparse_topk_slice(rows.n);
-    const int parts = (int)((rows.n + slice - 1) / slice);
-    if ((rc = ix->lex_col.grow((size_t)rows.n)) != CSS_OK) return rc;
-    if ((rc = ix->sp_pd.grow((size_t)parts * k)) != CSS_OK) return rc;
-    if ((rc = ix->sp_pi.grow((size_t)parts * k)) != CSS_OK) return rc;
-    if ((rc = tok_scores_enqueue(ix, nullptr, rows.n, rows.mask, q_dev, mq, ix->lex_col.p, st)) != CSS_OK) return rc;
-    {
-        ProfScope ps("sparse_topk", st);
-        hipLaunchKernelGGL(k_sparse_topk, dim3((unsigned)parts), dim3(256), 0, st, (const float*)ix->lex_col.p, rows.n, slice,
-                           rows.mask, k, rows.id_base, ix->sp_pd.p, ix->sp_pi.p);
-        CSS_LAUNCH_CHECK();
-    }
-    // (larger is better whatever the index's metric: the parts merge as inner-product lists)
-    return merge_parts(ix->sp_pd.p, ix->sp_pi.p, parts, k, k, 1, k, CSS_METRIC_IP, D_dev, I_dev, ix->device, st,
-                       "css_index_search_maxsim");
-}
-}  // namespace
-
-int css_index_search_maxsim(css_index* ix, const uint16_t* q_tok_host, int mq, int P, int k, const uint32_t* allow_bits_host,
-                            float* D_host, int64_t* I_host) {
-    CSS_REQUIRE(ix, "css_index_search_maxsim: NULL index");
-    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "css_index_search_maxsim: k=%d outside [1, %d]", k, CSS_KERNEL_MAX_K);
-    CSS_REQUIRE(D_host && I_host, "css_index_search_maxsim: NULL buffer");
-    int rc = token_query_check("css_index_search_maxsim", q_tok_host, mq, P);
-    if (rc != CSS_OK) return rc;
-    HostCall hc(ix);
-    CSS_REQUIRE(ix->tk_rows == 0 || P == ix->tk_dim, "css_index_search_maxsim: the query has P=%d, the stored matrices P=%d", P,
-                ix->tk_dim);
-    // the ONE upload: the query matrix
-    rc = hc.upload(allow_bits_host, ix->tk_q, (const unsigned short*)q_tok_host, (size_t)mq * P, (size_t)k);
-    if (rc == CSS_OK) rc = search_maxsim_enqueue(ix, hc.rows, ix->tk_q.p, mq, k, hc.d_out, hc.i_out, ix->stream);
-    return hc.finish(rc, D_host, I_host);
-}
-
-namespace {
-constexpr int kTokGroup = CSS_MAXSIM_BATCH_GROUP;
-static_assert(kTokGroup >= 4 && kTokGroup <= 16, "the waves of k_tok_scores_b's block");
-
-extern "C++" template <int P, int NB>
-const void* tok_scores_b_kernel_mt(int MT) {
-    switch (MT) {
-        case 1: return (const void*)k_tok_scores_b<P, 1, NB, kTokGroup>;
-        case 2: return (const void*)k_tok_scores_b<P, 2, NB, kTokGroup>;
-        case 3: return (const void*)k_tok_scores_b<P, 3, NB, kTokGroup>;
-        default: return (const void*)k_tok_scores_b<P, 4, NB, kTokGroup>;
-    }
-}
-extern "C++" template <int P>
-const void* tok_scores_b_kernel_p(int MT, int NB) {
-    return NB == 0 ? tok_scores_b_kernel_mt<P, 0>(MT) : NB == 1 ? tok_scores_b_kernel_mt<P, 1>(MT)
-         : NB == 2 ? tok_scores_b_kernel_mt<P, 2>(MT) : tok_scores_b_kernel_mt<P, 4>(MT);
-}
-const void* tok_scores_b_kernel(int P, int MT, int NB) {
-    return P == 32 ? tok_scores_b_kernel_p<32>(MT, NB) : P == 64 ? tok_scores_b_kernel_p<64>(MT, NB)
-         : P == 96 ? tok_scores_b_kernel_p<96>(MT, NB) : tok_scores_b_kernel_p<128>(MT, NB);
 }
 
 // The MaxSim columns of a group of 2 .. kTokGroup queries (tokens q, offsets qoff [ng + 1] on the device; mq_max: the
 // longest of them) over the rows 0 .. n - 1 into col [ng][n].  n > 0 and the index has matrices.  Enqueued on `st`.
 int tok_scores_group_enqueue(css_index* ix, int64_t n, const uint32_t* mask, const unsigned short* q, const int64_t* qoff, int ng,
                              int mq_max, float* col, hipStream_t st) {
-    const int P = ix->tk_dim, MT = (mq_max + 15) / 16, NB = ix->tk_bits;
-    const void* fn = tok_scores_b_kernel(P, MT, NB);
-    // a persistent grid of resident blocks, as in tok_scores_enqueue; a block's turn is always 16 rows
-    int64_t blocks = ix->tk_blocks;
-    if (blocks == 0) {
-        int per_cu = 0;
-        CSS_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * kTokGroup, 0));
-        blocks = (int64_t)std::max(per_cu, 1) * ix->num_cus;
-    }
-    blocks = std::min<int64_t>(blocks, (n + kTokTurn - 1) / kTokTurn);
-    const unsigned short *tok = ix->tk_tok.p, *codes = ix->tk_code.p, *cent = ix->tk_cent.p;
-    const unsigned char* res = ix->tk_res.p;
-    const float* wts = NB ? ix->tk_cw.p + 16 : nullptr;
-    const int64_t* off = ix->tk_off.p;
-    int64_t nlist = ix->tk_rows;
-    void* args[] = {&tok, &codes, &res, &cent, &wts, &off, &nlist, &n, &mask, &q, &qoff, &ng, &col};
-    ProfScope ps(NB ? "tok_scores_bc" : "tok_scores_b", st);
-    CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * kTokGroup), args, 0, st));
+    const void* fn = tok_variant(ix->tk_dim, (mq_max + 15) / 16, ix->tk_bits, [](auto p, auto mt, auto nb) {
+        return (const void*)k_tok_scores_b<decltype(p)::value, decltype(mt)::value, decltype(nb)::value, kTokGroup>;
+    });
+    int rc;
+    unsigned grid;
+    if ((rc = tok_grid(ix, fn, 64 * kTokGroup, n, 1, nullptr, &grid)) != CSS_OK) return rc;
+    TokStore store = tok_store(ix);
+    void* args[] = {&store, &n, &mask, &q, &qoff, &ng, &col};
+    ProfScope ps(ix->tk_bits ? "tok_scores_bc" : "tok_scores_b", st);
+    CSS_HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(64 * kTokGroup), args, 0, st));
     return CSS_OK;
 }
 
-// css_index_search_maxsim_batch on the device: per group the columns, their top-k by slices and ONE part merge for the
-// group's queries.  qoff_h: the host's offsets; q_dev / qoff_dev: the uploaded batch.  Caller holds ws_mu and a shared
-// lock on mu.
-int search_maxsim_batch_enqueue(css_index* ix, const Rows& rows, const unsigned short* q_dev, const int64_t* qoff_dev,
-                                const int64_t* qoff_h, int nq, int k, float* D_dev, int64_t* I_dev, hipStream_t st) {
-    const char* who = "css_index_search_maxsim_batch";
+// The frame of the MaxSim searches: nq queries, in groups of at most `group`, over n positions (`mask` and `id_base` as
+// in the searches).  Per group, `scores(q0, ng, col)` enqueues the columns [ng][n] of the queries q0 .. q0 + ng - 1
+// into `colbuf`; then their top-k by slices and ONE part merge into D_dev / I_dev [q0 ..][k].  An index without
+// matrices, or n = 0: the padded answer.  Everything is enqueued on `st`; nothing waits for the device.  Caller holds
+// ws_mu, a shared lock on mu and a turn at the workspaces.  (The pruned search comes here behind its candidate step,
+// which has made the stream wait for the ingest already: the second wait for the same event is a no-op.)
+extern "C++" template <typename F>
+int tok_topk_enqueue(css_index* ix, DevBuf<float>& colbuf, int64_t n, const uint32_t* mask, int64_t id_base, int nq, int group,
+                     int k, float* D_dev, int64_t* I_dev, const char* who, hipStream_t st, F&& scores) {
     int rc;
-    WsTurn turn(ix, st);
-    if (turn.rc != CSS_OK) return turn.rc;
-    ix->last_maxsim_passes = 0;
-    if (ix->tk_rows == 0 || rows.n == 0) {
+    if (ix->tk_rows == 0 || n == 0) {
         const int total = nq * k;
         hipLaunchKernelGGL(k_sparse_pad, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, D_dev, I_dev, total);
         CSS_LAUNCH_CHECK();
         return CSS_OK;
     }
-    CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "%s: %lld rows exceed the 32-bit row numbers of the lists", who, (long long)rows.n);
+    CSS_REQUIRE(n < 0xFFFFFFFFll, "%s: %lld rows exceed the 32-bit row numbers of the lists", who, (long long)n);
+    // rows appended on another stream must have landed (the mask and the row count speak of them)
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
-    const int64_t slice = sparse_topk_slice(rows.n);
-    const int parts = (int)((rows.n + slice - 1) / slice);
-    const int gmax = std::min(nq, kTokGroup);
-    if ((rc = ix->lex_col.grow((size_t)rows.n * gmax)) != CSS_OK) return rc;
+    const int64_t slice = sparse_topk_slice(n);
+    const int parts = (int)((n + slice - 1) / slice), gmax = std::min(nq, group);
+    if ((rc = colbuf.grow((size_t)n * gmax)) != CSS_OK) return rc;
     if ((rc = ix->sp_pd.grow((size_t)parts * gmax * k)) != CSS_OK) return rc;
     if ((rc = ix->sp_pi.grow((size_t)parts * gmax * k)) != CSS_OK) return rc;
-    for (int q0 = 0; q0 < nq; q0 += kTokGroup) {
-        const int ng = std::min(kTokGroup, nq - q0);
-        if (ng == 1) {   // the single call's kernel
-            if ((rc = tok_scores_enqueue(ix, nullptr, rows.n, rows.mask, q_dev + (size_t)qoff_h[q0] * ix->tk_dim,
-                                         (int)(qoff_h[q0 + 1] - qoff_h[q0]), ix->lex_col.p, st)) != CSS_OK) return rc;
-        } else {
-            int mq_max = 0;
-            for (int b = q0; b < q0 + ng; ++b) mq_max = std::max(mq_max, (int)(qoff_h[b + 1] - qoff_h[b]));
-            if ((rc = tok_scores_group_enqueue(ix, rows.n, rows.mask, q_dev, qoff_dev + q0, ng, mq_max, ix->lex_col.p, st)) != CSS_OK)
-                return rc;
-        }
-        ++ix->last_maxsim_passes;
+    for (int q0 = 0; q0 < nq; q0 += group) {
+        const int ng = std::min(group, nq - q0);
+        if ((rc = scores(q0, ng, colbuf.p)) != CSS_OK) return rc;
         {
             ProfScope ps("sparse_topk", st);
-            hipLaunchKernelGGL(k_sparse_topk_cols, dim3((unsigned)parts, (unsigned)ng), dim3(256), 0, st, (const float*)ix->lex_col.p,
-                               rows.n, slice, rows.mask, k, rows.id_base, ix->sp_pd.p, ix->sp_pi.p);
+            hipLaunchKernelGGL(k_sparse_topk_cols, dim3((unsigned)parts, (unsigned)ng), dim3(256), 0, st, (const float*)colbuf.p, n,
+                               slice, mask, k, id_base, ix->sp_pd.p, ix->sp_pi.p);
             CSS_LAUNCH_CHECK();
         }
+        // (larger is better whatever the index's metric: the parts merge as inner-product lists)
         if ((rc = merge_parts(ix->sp_pd.p, ix->sp_pi.p, parts, (int64_t)ng * k, (int64_t)ng * k, ng, k, CSS_METRIC_IP,
                               D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, ix->device, st, who)) != CSS_OK) return rc;
     }
     return CSS_OK;
 }
 }  // namespace
+
+int css_index_search_maxsim(css_index* ix, const uint16_t* q_tok_host, int mq, int P, int k, const uint32_t* allow_bits_host,
+                            float* D_host, int64_t* I_host) {
+    const char* fn = "css_index_search_maxsim";
+    CSS_REQUIRE(ix, "%s: NULL index", fn);
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "%s: k=%d outside [1, %d]", fn, k, CSS_KERNEL_MAX_K);
+    CSS_REQUIRE(D_host && I_host, "%s: NULL buffer", fn);
+    int rc = token_query_check(fn, q_tok_host, mq, P);
+    if (rc != CSS_OK) return rc;
+    HostCall hc(ix);
+    CSS_REQUIRE(ix->tk_rows == 0 || P == ix->tk_dim, "%s: the query has P=%d, the stored matrices P=%d", fn, P, ix->tk_dim);
+    // the ONE upload: the query matrix
+    rc = hc.upload(allow_bits_host, ix->tk_q, (const unsigned short*)q_tok_host, (size_t)mq * P, (size_t)k);
+    if (rc == CSS_OK) {
+        const hipStream_t st = ix->stream;
+        const Rows& rows = hc.rows;
+        WsTurn turn(ix, st);
+        if ((rc = turn.rc) == CSS_OK)
+            rc = tok_topk_enqueue(ix, ix->lex_col, rows.n, rows.mask, rows.id_base, 1, 1, k, hc.d_out, hc.i_out, fn, st,
+                                  [&](int, int, float* col) {
+                                      return tok_scores_enqueue(ix, nullptr, rows.n, rows.mask, ix->tk_q.p, mq, col, st);
+                                  });
+    }
+    return hc.finish(rc, D_host, I_host);
+}
 
 int css_index_search_maxsim_batch(css_index* ix, const uint16_t* q_tok_host, const int64_t* q_offsets_host, int nq, int P, int k,
                                   const uint32_t* allow_bits_host, float* D_host, int64_t* I_host) {
@@ -6118,18 +6057,12 @@ int css_index_search_maxsim_batch(css_index* ix, const uint16_t* q_tok_host, con
     CSS_REQUIRE(q_tok_host && q_offsets_host && D_host && I_host, "%s: NULL buffer", fn);
     CSS_REQUIRE(token_dim_ok(P), "%s: P=%d must be a multiple of 32 in [32, %d]", fn, P, CSS_MAX_TOKEN_DIM);
     CSS_REQUIRE(q_offsets_host[0] == 0, "%s: the offsets start at %lld, not at 0", fn, (long long)q_offsets_host[0]);
-    for (int b = 0; b < nq; ++b) {
-        const int64_t mq = q_offsets_host[b + 1] - q_offsets_host[b];
-        CSS_REQUIRE(mq >= 1 && mq <= CSS_MAX_QUERY_TOKENS, "%s: query %d has %lld tokens, outside [1, %d]", fn, b, (long long)mq,
-                    CSS_MAX_QUERY_TOKENS);
-    }
-    for (int b = 0; b < nq; ++b) {
-        const uint16_t* qb = q_tok_host + (size_t)q_offsets_host[b] * P;
-        const int cnt = (int)(q_offsets_host[b + 1] - q_offsets_host[b]) * P;
-        for (int i = 0; i < cnt; ++i)
-            CSS_REQUIRE(bf16_finite(qb[i]), "%s: component %d of token %d of query %d is %s", fn, i % P, i / P, b,
-                        (qb[i] & 0x7Fu) ? "NaN" : "infinite");
-    }
+    int rc;
+    for (int b = 0; b < nq; ++b)
+        if ((rc = token_len_check(fn, q_offsets_host[b + 1] - q_offsets_host[b], b)) != CSS_OK) return rc;
+    for (int b = 0; b < nq; ++b)
+        if ((rc = token_finite_check(fn, q_tok_host + (size_t)q_offsets_host[b] * P, (int)(q_offsets_host[b + 1] - q_offsets_host[b]),
+                                     P, b)) != CSS_OK) return rc;
     // the ONE upload: [offsets (int64) | the matrices], the matrices behind the offsets at a multiple of 16 bytes
     const size_t ntok = (size_t)q_offsets_host[nq];
     const size_t at = ((size_t)(nq + 1) * 2 + 3) / 4 * 4, q_words = ntok * P / 2;   // (P is even)
@@ -6144,11 +6077,29 @@ int css_index_search_maxsim_batch(css_index* ix, const uint16_t* q_tok_host, con
     memcpy(in.data() + at, q_tok_host, ntok * P * sizeof(uint16_t));
     HostCall hc(ix);
     CSS_REQUIRE(ix->tk_rows == 0 || P == ix->tk_dim, "%s: the queries have P=%d, the stored matrices P=%d", fn, P, ix->tk_dim);
-    int rc = hc.upload(allow_bits_host, ix->tk_bq, (const uint32_t*)in.data(), in.size(), (size_t)nq * k);
-    if (rc == CSS_OK)
-        rc = search_maxsim_batch_enqueue(ix, hc.rows, reinterpret_cast<const unsigned short*>(ix->tk_bq.p + at),
-                                         reinterpret_cast<const int64_t*>(ix->tk_bq.p), q_offsets_host, nq, k, hc.d_out, hc.i_out,
-                                         ix->stream);
+    rc = hc.upload(allow_bits_host, ix->tk_bq, (const uint32_t*)in.data(), in.size(), (size_t)nq * k);
+    if (rc == CSS_OK) {
+        const hipStream_t st = ix->stream;
+        const Rows& rows = hc.rows;
+        const unsigned short* q_dev = reinterpret_cast<const unsigned short*>(ix->tk_bq.p + at);
+        const int64_t *qoff_dev = reinterpret_cast<const int64_t*>(ix->tk_bq.p), *qoff = q_offsets_host;
+        WsTurn turn(ix, st);
+        if ((rc = turn.rc) == CSS_OK) {
+            ix->last_maxsim_passes = 0;
+            // per group of kTokGroup queries ONE pass over the store; a group of one runs the single call's kernel
+            rc = tok_topk_enqueue(ix, ix->lex_col, rows.n, rows.mask, rows.id_base, nq, kTokGroup, k, hc.d_out, hc.i_out, fn, st,
+                                  [&](int q0, int ng, float* col) {
+                                      int mq_max = 0;
+                                      for (int b = q0; b < q0 + ng; ++b) mq_max = std::max(mq_max, (int)(qoff[b + 1] - qoff[b]));
+                                      const int rc = ng == 1 ? tok_scores_enqueue(ix, nullptr, rows.n, rows.mask,
+                                                                                  q_dev + (size_t)qoff[q0] * P, mq_max, col, st)
+                                                             : tok_scores_group_enqueue(ix, rows.n, rows.mask, q_dev, qoff_dev + q0, ng,
+                                                                                        mq_max, col, st);
+                                      if (rc == CSS_OK) ++ix->last_maxsim_passes;
+                                      return rc;
+                                  });
+        }
+    }
     return hc.finish(rc, D_host, I_host);
 }
 
@@ -6218,11 +6169,6 @@ int css_index_maxsim_rows(css_index* ix, const uint16_t* q_tok_host, int mq, int
 }
 
 namespace {
-const void* tok_ctable_kernel(int P) {
-    return P == 32 ? (const void*)k_tok_ctable<32> : P == 64 ? (const void*)k_tok_ctable<64> : P == 96 ? (const void*)k_tok_ctable<96>
-                                                                                                        : (const void*)k_tok_ctable<128>;
-}
-
 // The candidates of the query (mq tokens on the device) among `rows`: the centroid table, the approximate column over
 // every row (lex_col), and the select of the best nc <= rows.n of it into tk_cand (ascending rows, 0xFFFFFFFF behind
 // the count) and tk_capx; the count is word kSelHist + 3 of tk_sel.  The index has a codec and matrices, rows.n > 0.
@@ -6241,35 +6187,29 @@ int tok_candidates_enqueue(css_index* ix, const Rows& rows, const unsigned short
     if ((rc = ix->tk_sel.grow((size_t)kSelState + 2 * (size_t)nblk)) != CSS_OK) return rc;
     // rows appended on another stream must have landed (the mask and the row count speak of them)
     if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
-    const unsigned short *cent = ix->tk_cent.p, *codes = ix->tk_code.p;
+    const unsigned short* cent = ix->tk_cent.p;
     float* tab = ix->tk_ctab.p;
     {
+        const void* fn = tok_dim(P, [](auto p) { return (const void*)k_tok_ctable<decltype(p)::value>; });
         int mt = MT, c = C, m = mq;
         void* args[] = {&cent, &c, &q_dev, &m, &mt, &tab};
         ProfScope ps("tok_ctable", st);
-        CSS_HIP_TRY(hipLaunchKernel(tok_ctable_kernel(P), dim3((unsigned)((C + 16 * kWaves - 1) / (16 * kWaves))), dim3(64 * kWaves), args, 0, st));
+        CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)((C + 16 * kWaves - 1) / (16 * kWaves))), dim3(64 * kWaves), args, 0, st));
     }
     {
         const void* fn = W <= 16 ? (const void*)k_tok_ci<16> : W <= 32 ? (const void*)k_tok_ci<32> : (const void*)k_tok_ci<64>;
-        // the grid of tok_scores_enqueue: the resident blocks, or what css_index_set_token_blocks fixes
-        int64_t blocks = ix->tk_blocks;
-        int per = kTokTurn;
-        if (blocks == 0) {
-            int per_cu = 0;
-            CSS_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * kWaves, 0));
-            blocks = (int64_t)std::max(per_cu, 1) * ix->num_cus;
-            per = (int)std::min<int64_t>(kTokTurn, (n + blocks * kWaves - 1) / (blocks * kWaves));
-        }
-        blocks = std::min<int64_t>(blocks, (n + (int64_t)per * kWaves - 1) / ((int64_t)per * kWaves));
+        int per;
+        unsigned grid;
+        if ((rc = tok_grid(ix, fn, 64 * kWaves, n, kWaves, &per, &grid)) != CSS_OK) return rc;
+        TokStore store = tok_store(ix);
         const float* ctab = tab;
-        const int64_t* off = ix->tk_off.p;
-        int64_t nlist = ix->tk_rows, nn = n;
+        int64_t nn = n;
         const uint32_t *list = nullptr, *mask = rows.mask;
         int w = W, m = mq;
         float* col = ix->lex_col.p;
-        void* args[] = {&codes, &ctab, &w, &off, &nlist, &list, &nn, &mask, &m, &per, &col};
+        void* args[] = {&store, &ctab, &w, &list, &nn, &mask, &m, &per, &col};
         ProfScope ps("tok_ci", st);
-        CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * kWaves), args, 0, st));
+        CSS_HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(64 * kWaves), args, 0, st));
     }
     ProfScope ps("tok_select", st);
     uint32_t* sel = ix->tk_sel.p;
@@ -6363,7 +6303,7 @@ int css_index_search_maxsim_pruned(css_index* ix, const uint16_t* q_tok_host, in
         rc = turn.rc;
         if (rc == CSS_OK) rc = [&]() -> int {
             int rc;
-            if (ix->tk_rows == 0 || hc.rows.n == 0) {   // a codec without matrices: the padded answer
+            if (ix->tk_rows == 0 || hc.rows.n == 0) {   // a codec without matrices: the padded answer, no candidates
                 hipLaunchKernelGGL(k_sparse_pad, dim3(1), dim3(128), 0, st, hc.d_out, hc.i_out, k);
                 CSS_LAUNCH_CHECK();
                 CSS_HIP_TRY(hipMemsetAsync(hc.i_out + k, 0, sizeof(int64_t), st));
@@ -6371,22 +6311,11 @@ int css_index_search_maxsim_pruned(css_index* ix, const uint16_t* q_tok_host, in
             }
             const int64_t nc = std::min<int64_t>(ncand, hc.rows.n);
             if ((rc = tok_candidates_enqueue(ix, hc.rows, ix->tk_q.p, mq, nc, fn, st)) != CSS_OK) return rc;
-            // the exact scores of the candidates on the codes (a slot behind the count names no row: a miss) ...
-            const int64_t slice = sparse_topk_slice(nc);
-            const int parts = (int)((nc + slice - 1) / slice);
-            if ((rc = ix->tk_col.grow((size_t)nc)) != CSS_OK) return rc;
-            if ((rc = ix->sp_pd.grow((size_t)parts * k)) != CSS_OK) return rc;
-            if ((rc = ix->sp_pi.grow((size_t)parts * k)) != CSS_OK) return rc;
-            if ((rc = tok_scores_enqueue(ix, ix->tk_cand.p, nc, nullptr, ix->tk_q.p, mq, ix->tk_col.p, st)) != CSS_OK) return rc;
-            // ... their top-k by (score, position): the list ascends by row, so ties go to the lower id ...
-            {
-                ProfScope ps("sparse_topk", st);
-                hipLaunchKernelGGL(k_sparse_topk, dim3((unsigned)parts), dim3(256), 0, st, (const float*)ix->tk_col.p, nc, slice,
-                                   (const uint32_t*)nullptr, k, (int64_t)0, ix->sp_pd.p, ix->sp_pi.p);
-                CSS_LAUNCH_CHECK();
-            }
-            if ((rc = merge_parts(ix->sp_pd.p, ix->sp_pi.p, parts, k, k, 1, k, CSS_METRIC_IP, hc.d_out, hc.i_out, ix->device, st, fn)) != CSS_OK)
-                return rc;
+            // the exact scores of the candidates on the codes (a slot behind the count names no row: a miss) and their
+            // top-k by (score, position): the list ascends by row, so ties go to the lower id ...
+            if ((rc = tok_topk_enqueue(ix, ix->tk_col, nc, nullptr, 0, 1, 1, k, hc.d_out, hc.i_out, fn, st, [&](int, int, float* col) {
+                    return tok_scores_enqueue(ix, ix->tk_cand.p, nc, nullptr, ix->tk_q.p, mq, col, st);
+                })) != CSS_OK) return rc;
             // ... and the positions become ids
             hipLaunchKernelGGL(k_tok_cand_ids, dim3(1), dim3(256), 0, st, (const uint32_t*)ix->tk_cand.p,
                                (const uint32_t*)(ix->tk_sel.p + kSelHist), k, hc.rows.id_base, hc.d_out, hc.i_out);

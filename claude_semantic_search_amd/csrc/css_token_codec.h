@@ -1,7 +1,7 @@
 // css_token_codec.h -- residual compression of the flat index's token matrices (ColBERTv2's codec): a token is stored
 // as the id of its best centroid plus an nbits bucket per component for the residual, and MaxSim runs on the codes.
-// Included by css_index.hip behind css_tokens.h (it reuses TokAt, tok_next_doc / tok_next_tile, tok_row16_allmax,
-// kTokTurn, kTokPark, tok_v8s, v8bf, v4f, kWaves, kLexNoRow).  include/css_hip.h defines the codec in bits.
+// Included by css_index.hip in front of css_tokens.h, whose kernels decode with the primitives here (it reuses v8bf,
+// v4f, kWaves, kLexNoRow).  include/css_hip.h defines the codec in bits.
 //
 // Encode.  code = argmax_c dot(d, centroid_c), ties to the lower c, with the dot formed as k_maxsim forms its own (bf16
 // operands, fp32 accumulation on v_mfma_f32_16x16x32_bf16, K steps of 32 ascending); r_j = fp32(d_j) -
@@ -16,13 +16,12 @@
 // of nbits bytes per K step and a tile of 16 tokens is the 16 RB contiguous bytes that its wave reads whole: no
 // permutation between the canonical and the stored form.
 //
-// k_tok_scores_c<P, MT, NB> is k_tok_scores (css_tokens.h) with the B fragment decoded in registers: same turns, same
-// tile sequence, same MFMAs in the same order on the same operand values as k_tok_scores over the decoded matrices, so
-// the bits agree by construction.  Three stages in flight through three register buffers used in turn: the codes and
-// buckets of tile i + 2 are loaded (non-temporal: used once), the centroid fragments of tile i + 1 are gathered by its
-// codes (ordinary loads through the caches: the table is C x 2 P bytes and every wave re-reads it), tile i is decoded
-// and multiplied.  The weights sit in registers (NB <= 2: selects) or in 16 floats of LDS (NB = 4: distinct banks).
+// MaxSim on the codes is k_tok_scores<P, MT, NB> (css_tokens.h) with NB = nbits: its B fragment is decoded in registers
+// by tok_decode1 below.  The weights of a kernel sit in registers (NB <= 2: selects) or in 16 floats of LDS (NB = 4:
+// distinct banks).
 #pragma once
+
+typedef short tok_v8s __attribute__((ext_vector_type(8)));   // the 8 bf16 that a lane feeds to one K step
 
 template <int NB>
 __device__ __forceinline__ unsigned tok_res_load(const unsigned char* p) {   // NB bytes, zero extended; p is NB-aligned
@@ -34,147 +33,38 @@ __device__ __forceinline__ float tok_bf2f(short h) { return __uint_as_float((uns
 // the ONE decode: one fp32 addition, one rounding to nearest even
 __device__ __forceinline__ __bf16 tok_decode1(short c, float w) { return (__bf16)(tok_bf2f(c) + w); }
 
-// the weights of one kernel: the first four in registers, all 16 in LDS for NB = 4
+// the weights of one kernel: the first four in registers (four scalars, not an array), all 16 in LDS for NB = 4
+struct TokWeights {
+    const float* wl;
+    float w0, w1, w2, w3;
+};
 template <int NB>
-__device__ __forceinline__ float tok_weight(unsigned b, const float* wl, float w0, float w1, float w2, float w3) {
+__device__ __forceinline__ float tok_weight(unsigned b, const TokWeights& w) {
+    // (read before the selects: a select between the struct's members would keep the struct in memory)
+    const float w0 = w.w0, w1 = w.w1, w2 = w.w2, w3 = w.w3;
     if constexpr (NB == 1) return b ? w1 : w0;
-    else if constexpr (NB == 2) return (b & 2u) ? ((b & 1u) ? w3 : w2) : ((b & 1u) ? w1 : w0);
-    else return wl[b];
+    else if constexpr (NB == 2) {
+        // The weight's BITS, picked by masks from the bucket's two bits: u0 at 0, u1 at 1, u2 at 2, u3 at 3.  The four
+        // weights and their differences stay in SGPRs; selects would hold all four in VGPRs (a wave per SIMD in two
+        // instantiations) and a nested ?: is compiled into branches or into selects depending on where it is inlined.
+        const unsigned u0 = __float_as_uint(w0), u1 = __float_as_uint(w1), u2 = __float_as_uint(w2), u3 = __float_as_uint(w3);
+        const unsigned m0 = 0u - (b & 1u), m1 = 0u - (b >> 1);
+        return __uint_as_float(u0 ^ (m0 & (u0 ^ u1)) ^ (m1 & (u0 ^ u2)) ^ (m0 & m1 & (u0 ^ u1 ^ u2 ^ u3)));
+    }
+    else return w.wl[b];
 }
-
-template <int P, int MT, int NB>
-__global__ __launch_bounds__(64 * kWaves) void k_tok_scores_c(const unsigned short* __restrict__ codes,
-                                                              const unsigned char* __restrict__ res,
-                                                              const unsigned short* __restrict__ cent,
-                                                              const float* __restrict__ wts /* [16] */,
-                                                              const int64_t* __restrict__ off, int64_t nlist,
-                                                              const uint32_t* __restrict__ rows, int64_t n,
-                                                              const uint32_t* __restrict__ mask,
-                                                              const unsigned short* __restrict__ q, int mq, int per,
-                                                              float* __restrict__ col) {
-    static_assert(P % 32 == 0 && P >= 32 && P <= 128, "whole K steps of the MFMA");
-    static_assert(MT >= 1 && MT * 16 <= kTokQ, "the query's tiles");
-    static_assert(NB == 1 || NB == 2 || NB == 4, "bits of a bucket");
-    constexpr int KS = P / 32, RB = P * NB / 8;
-    __shared__ float park[kWaves][kTokTurn * kTokPark];
-    __shared__ float wl[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, g = lane >> 4;
-    const float ninf = -__builtin_inff();
+// Staged at the top of a kernel by every thread of its block (NB = 4: with a block barrier) from the table of 16 floats
+// (zeros behind 2^NB) into the block's 16 floats of LDS `wl`.  NB = 0, a raw store, has no table and reads nothing.
+template <int NB>
+__device__ __forceinline__ TokWeights tok_weights_stage(const float* __restrict__ wts, float* wl) {
+    static_assert(NB == 0 || NB == 1 || NB == 2 || NB == 4, "bits of a bucket (0: the raw store)");
+    TokWeights w = {wl, 0.f, 0.f, 0.f, 0.f};
     if constexpr (NB == 4) {
         if (threadIdx.x < 16) wl[threadIdx.x] = wts[threadIdx.x];
         __syncthreads();
     }
-    const float w0 = wts[0], w1 = wts[1], w2 = wts[2], w3 = wts[3];   // (the table always has 16 entries, zeros behind 2^NB)
-    v8bf qa[MT][KS];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int r = 16 * mt + lr;
-            const uint4 v = r < mq ? *reinterpret_cast<const uint4*>(q + (size_t)r * P + 32 * ks + 8 * g) : make_uint4(0u, 0u, 0u, 0u);
-            qa[mt][ks] = __builtin_bit_cast(v8bf, v);
-        }
-    float* mypark = park[wave];
-    struct CBuf {
-        unsigned code;
-        unsigned r[KS];
-        tok_v8s cf[KS];
-    };
-    const int64_t nturns = (n + per - 1) / per;   // (1 <= per <= kTokTurn)
-    for (int64_t turn = (int64_t)blockIdx.x * kWaves + wave; turn < nturns; turn += (int64_t)gridDim.x * kWaves) {
-        const int64_t pos = turn * per + lr;
-        int md_lane = 0;
-        int64_t beg_lane = 0;
-        if (lane < per && pos < n) {
-            const int64_t row = rows != nullptr ? (int64_t)rows[pos] : pos;
-            if (row < nlist && (mask == nullptr || ((mask[row >> 5] >> (row & 31)) & 1u))) {
-                beg_lane = off[row];
-                md_lane = (int)(off[row + 1] - beg_lane);
-            }
-        }
-        TokAt ld;   // the next tile to load ...
-        ld.live = (unsigned)__ballot(lane < per && md_lane > 0);
-        tok_next_doc(ld, md_lane, beg_lane);
-        TokAt at = ld;   // ... and the next to multiply
-        CBuf b0, b1, b2;
-        b0.code = b1.code = b2.code = 0u;   // (a buffer without a tile gathers centroid 0 and is never multiplied)
-        auto load = [&](CBuf& b) {
-            if (ld.j >= kTokTurn) return;
-            const size_t t = (size_t)ld.beg + (size_t)min(ld.t * 16 + lr, ld.md - 1);
-            b.code = __builtin_nontemporal_load(codes + t);
-            const unsigned char* rp = res + t * RB + NB * g;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) b.r[ks] = tok_res_load<NB>(rp + 4 * NB * ks);
-            tok_next_tile(ld, md_lane, beg_lane);
-        };
-        auto gather = [&](CBuf& b) {
-            const unsigned short* crow = cent + (size_t)b.code * P + 8 * g;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) b.cf[ks] = *reinterpret_cast<const tok_v8s*>(crow + 32 * ks);
-        };
-        v4f run[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) run[mt] = v4f{ninf, ninf, ninf, ninf};
-        // tile i sits in buffer i % 3; its step loads the codes of tile i + 2 and gathers the centroids of tile i + 1
-        auto step = [&](CBuf& cur, CBuf& nxt, CBuf& nn) {
-            load(nn);
-            gather(nxt);
-            v4f acc[MT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc[mt] = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                v8bf d;
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    d[j] = tok_decode1(cur.cf[ks][j], tok_weight<NB>((cur.r[ks] >> (NB * j)) & ((1u << NB) - 1u), wl, w0, w1, w2, w3));
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[mt][ks], d, acc[mt], 0, 0, 0);
-            }
-            const bool ok = at.t * 16 + lr < at.md;
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) run[mt][i] = fmaxf(run[mt][i], ok ? acc[mt][i] : ninf);
-            const int doc = at.j;
-            tok_next_tile(at, md_lane, beg_lane);
-            if (at.j == doc) return;
-            // the doc's last tile: its maxima are parked for the adds at the end of the turn
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float m = tok_row16_allmax(run[mt][i]);
-                    if (lr == 0) mypark[doc * kTokPark + mt * 16 + 4 * g + i] = m;
-                    run[mt][i] = ninf;
-                }
-        };
-        load(b0);
-        load(b1);
-        gather(b0);
-        while (true) {
-            if (at.j >= kTokTurn) break;
-            step(b0, b1, b2);
-            if (at.j >= kTokTurn) break;
-            step(b1, b2, b0);
-            if (at.j >= kTokTurn) break;
-            step(b2, b0, b1);
-        }
-        // (one wave writes and reads its own LDS rows: the LDS keeps a wave's accesses in order)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane < per && pos < n) {
-            float s = ninf;
-            if (md_lane > 0) {
-                s = 0.f;
-                const float* mx = mypark + lane * kTokPark;
-                for (int i = 0; i < mq; ++i) s += mx[i];
-            }
-            col[pos] = s;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
+    if constexpr (NB != 0) w.w0 = wts[0], w.w1 = wts[1], w.w2 = wts[2], w.w3 = wts[3];
+    return w;
 }
 
 // k_tok_encode<P>: a wave takes kEncTiles tiles of 16 tokens (A, in registers) against every tile of 16 centroids (B,
@@ -283,7 +173,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_tok_encode(const unsigned short
     }
 }
 
-// css_index_get_tokens on a compressed store: 8 components per thread, the decode of k_tok_scores_c.
+// css_index_get_tokens on a compressed store: 8 components per thread, the decode of k_tok_scores on the codes.
 __global__ __launch_bounds__(256) void k_tok_decode(const unsigned short* __restrict__ codes,
                                                     const unsigned char* __restrict__ res, int64_t ntok,
                                                     const unsigned short* __restrict__ cent, int P, int nbits,
@@ -302,8 +192,9 @@ __global__ __launch_bounds__(256) void k_tok_decode(const unsigned short* __rest
     *reinterpret_cast<uint4*>(out + (size_t)t * P + 8 * ch) = __builtin_bit_cast(uint4, d);
 }
 
-// The mover of css_index_remove_rows for a compressed store, k_tok_move in units of T: u units per token (uint16, 1: the
-// codes; uint32, RB / 4 = 1 .. 16: the packed buckets of 4 to 64 bytes).  One wave per source row r < nlist.
+// The mover of css_index_remove_rows, one wave per source row r < nlist: a kept row's tokens move to token noff[map[r]]
+// of the new buffer (map[r] = the row's new number, kLexNoRow when it goes), in units of T, u units per token (uint4,
+// P / 8: the raw tokens; uint16, 1: the codes; uint32, RB / 4 = 1 .. 16: the packed buckets of 4 to 64 bytes).
 template <typename T>
 __global__ __launch_bounds__(256) void k_tok_move_units(const T* __restrict__ src, const int64_t* __restrict__ off,
                                                         const uint32_t* __restrict__ map, const int64_t* __restrict__ noff,

@@ -1,7 +1,8 @@
 // css_token_prune.h -- candidate generation for MaxSim on a compressed store (PLAID's centroid interaction): rank every
 // row by the MaxSim of its tokens' CENTROIDS, which reads only the 2-byte code of a token and a small table, and leave
-// the decode to the few thousand best.  Included by css_index.hip behind css_token_codec.h (it reuses TokAt,
-// tok_next_doc, kTokTurn, kTokPark, kTokQ, v8bf, v4f, kWaves).  include/css_hip.h has the definitions in bits.
+// the decode to the few thousand best.  Included by css_index.hip behind css_tokens.h (it reuses TokStore, TokAt,
+// tok_next_doc, tok_turn_head / tok_turn_tail, tok_query_frags, kTokTurn, kTokPark, v8bf, v4f, kWaves).
+// include/css_hip.h has the definitions in bits.
 //
 // k_tok_ctable<P>.  S[c, s] = dot(q_s, centroid_c) into tab [C][W], W = 16 MT floats per centroid, formed as
 // k_tok_scores forms the dot of query token s with a doc token equal to centroid c: query tokens as rows of A, the 16
@@ -40,7 +41,6 @@ template <int P>
 __global__ __launch_bounds__(64 * kWaves) void k_tok_ctable(const unsigned short* __restrict__ cent, int C,
                                                             const unsigned short* __restrict__ q, int mq, int MT,
                                                             float* __restrict__ tab) {
-    static_assert(P % 32 == 0 && P >= 32 && P <= 128, "whole K steps of the MFMA");
     constexpr int KS = P / 32;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, g = lane >> 4;
     const int c0 = (blockIdx.x * kWaves + wave) * 16;
@@ -51,52 +51,39 @@ __global__ __launch_bounds__(64 * kWaves) void k_tok_ctable(const unsigned short
     for (int ks = 0; ks < KS; ++ks)
         b[ks] = __builtin_bit_cast(v8bf, *reinterpret_cast<const uint4*>(cent + (size_t)cc * P + 32 * ks + 8 * g));
     for (int mt = 0; mt < MT; ++mt) {
-        const int r = 16 * mt + lr;
+        v8bf a[1][KS];   // the query's tile mt
+        tok_query_frags<P, 1>(q + (size_t)16 * mt * P, mq - 16 * mt, lr, g, a);
         v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const uint4 v = r < mq ? *reinterpret_cast<const uint4*>(q + (size_t)r * P + 32 * ks + 8 * g) : make_uint4(0u, 0u, 0u, 0u);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, v), b[ks], acc, 0, 0, 0);
-        }
+        for (int ks = 0; ks < KS; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][ks], b[ks], acc, 0, 0, 0);
         // C/D: centroid column lr, the query rows 16 mt + 4 g + i
         if (c0 + lr < C) *reinterpret_cast<v4f*>(tab + (size_t)(c0 + lr) * W + 16 * mt + 4 * g) = acc;
     }
 }
 
 template <int WP>
-__global__ __launch_bounds__(64 * kWaves) void k_tok_ci(const unsigned short* __restrict__ codes,
-                                                        const float* __restrict__ tab, int W,
-                                                        const int64_t* __restrict__ off, int64_t nlist,
+__global__ __launch_bounds__(64 * kWaves) void k_tok_ci(const TokStore store, const float* __restrict__ tab, int W,
                                                         const uint32_t* __restrict__ rows, int64_t n,
                                                         const uint32_t* __restrict__ mask, int mq, int per,
                                                         float* __restrict__ col) {
     static_assert(WP == 16 || WP == 32 || WP == 64, "lanes of one token's table row");
     constexpr int TPI = 64 / WP, U = 8;   // tokens per instruction, instructions in flight
     __shared__ float park[kWaves][kTokTurn * kTokPark];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & (WP - 1), sub = lane / WP;
     const float ninf = -__builtin_inff();
     const float* trow = tab + min(s, W - 1);   // (W = 48 under WP = 64: the lanes beyond W re-read column W - 1)
     float* mypark = park[wave];
     const int64_t nturns = (n + per - 1) / per;   // (1 <= per <= kTokTurn)
     for (int64_t turn = (int64_t)blockIdx.x * kWaves + wave; turn < nturns; turn += (int64_t)gridDim.x * kWaves) {
-        const int64_t pos = turn * per + lr;
-        int md_lane = 0;
-        int64_t beg_lane = 0;
-        if (lane < per && pos < n) {
-            const int64_t row = rows != nullptr ? (int64_t)rows[pos] : pos;
-            if (row < nlist && (mask == nullptr || ((mask[row >> 5] >> (row & 31)) & 1u))) {
-                beg_lane = off[row];
-                md_lane = (int)(off[row + 1] - beg_lane);
-            }
-        }
-        TokAt ld;   // the next chunk of 64 tokens to load (t counts chunks here) ...
-        ld.live = (unsigned)__ballot(lane < per && md_lane > 0);
-        tok_next_doc(ld, md_lane, beg_lane);
+        int md_lane;
+        int64_t beg_lane, pos;
+        // the next chunk of 64 tokens to load (t counts chunks here) ...
+        TokAt ld = tok_turn_head(store, rows, n, mask, per, turn, lane, md_lane, beg_lane, pos);
         TokAt at = ld;   // ... and the next to look up
         auto load = [&]() -> unsigned {
             if (ld.j >= kTokTurn) return 0u;
-            const unsigned c = __builtin_nontemporal_load(codes + (size_t)ld.beg + (size_t)min(ld.t * 64 + lane, ld.md - 1));
+            const unsigned c = __builtin_nontemporal_load(store.codes + (size_t)ld.beg + (size_t)min(ld.t * 64 + lane, ld.md - 1));
             if (++ld.t * 64 >= ld.md) tok_next_doc(ld, md_lane, beg_lane);
             return c;
         };
@@ -128,20 +115,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_tok_ci(const unsigned short* __
             if (lane < WP && s < W) mypark[doc * kTokPark + s] = run;
             run = ninf;
         }
-        // (one wave writes and reads its own LDS rows: the LDS keeps a wave's accesses in order)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane < per && pos < n) {
-            float sum = ninf;
-            if (md_lane > 0) {
-                sum = 0.f;
-                const float* mx = mypark + lane * kTokPark;
-                for (int i = 0; i < mq; ++i) sum += mx[i];
-            }
-            col[pos] = sum;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        tok_turn_tail(mypark, lane, md_lane, mq, lane < per && pos < n, col, pos);
     }
 }
 

@@ -1,6 +1,6 @@
 """GPU: the batched MaxSim search -- ``IndexFlat.search_maxsim_batch`` / ``last_maxsim_passes``
 (``css_index_search_maxsim_batch``; kernels ``k_tok_scores_b<P, MT, NB, G>``, ``k_sparse_topk_cols`` and the part merge
-behind it; a group of one query runs ``k_tok_scores`` / ``k_tok_scores_c``).
+behind it; a group of one query runs ``k_tok_scores``).
 
 Truth is the float64 column and ONE ``lexsort`` of ``tests/tokens_fakes.py`` on the very arrays handed to the index,
 never the code under test; the single call ``search_maxsim`` is checked IN ADDITION for byte equality.  The inputs are

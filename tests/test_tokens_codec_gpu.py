@@ -1,7 +1,7 @@
 """GPU: compressed token matrices on the flat index -- ``IndexFlat.set_token_codec`` / ``get_token_codec`` /
 ``token_codec_bits`` / ``get_token_codes`` / ``set_token_codes`` and ``set_tokens`` / ``get_tokens`` / ``search_maxsim`` /
 ``maxsim_ids`` / ``remove_ids`` on an index with a codec (kernels ``k_tok_encode<P>``, ``k_tok_decode``,
-``k_tok_scores_c<P, MT, NB>``, ``k_tok_move_units``).
+``k_tok_scores<P, MT, NB>``, ``k_tok_move_units``).
 
 Lattice inputs (tests/tokens_codec_cases.py; tests/test_tokens_codec_host.py proves that they contain tied centroids,
 residuals on cutoffs and scores tied across rank k): no tolerance anywhere -- codes and decoded tokens equal the numpy
@@ -108,6 +108,24 @@ def test_lattice_codes_tokens_and_scores_are_exact(P, nbits, C):
     part = Matrices(dec.off[:cc.T_PART + 1], dec.tok[:dec.off[cc.T_PART]]).padded(N).scores64(q)
     assert (part[cc.T_PART:] == -np.inf).all()
     _check(ix.search_maxsim(q, 128), part, 128, f"{what}: rows >= T")
+    ix.close()
+
+
+@pytest.mark.parametrize("nids", (1, 5, 70))
+def test_maxsim_ids_of_a_few_rows_equals_search_maxsim_over_them(nids):
+    """A list so short that a wave's turn is ONE row (the default grid has more waves than 70 rows; one wave, five
+    waves, more than one block), on the codes: the same bits as the scan, whose turns are 16 rows, gives those rows."""
+    codec, ms, qs = cc.lattice(32, 2, 17)
+    ix = _index(codec, ms)
+    ids = np.random.default_rng(nids).permutation(N)[:nids]
+    allow = np.zeros(N, bool)
+    allow[ids] = True
+    for j, q in enumerate(qs):
+        D_, I = ix.search_maxsim(q, 128, allow=allow)
+        want = np.full(N, -np.inf, np.float32)
+        want[I[I >= 0]] = D_[I >= 0]
+        assert (I >= 0).sum() == (ms.lens[ids] > 0).sum()
+        assert np.array_equal(_bits(ix.maxsim_ids(q, ids)), _bits(want[ids])), f"query {j}, {nids} ids"
     ix.close()
 
 

@@ -1,6 +1,6 @@
 """GPU: token matrices on the flat index -- ``IndexFlat.set_tokens`` / ``get_tokens`` / ``token_rows`` / ``token_dim`` /
 ``drop_tokens`` / ``search_maxsim`` / ``maxsim_ids`` (``css_index_set_tokens`` ...; kernels ``k_tok_scores<P, MT>``,
-``k_tok_move``, ``k_sparse_topk`` and the part merge behind it).
+``k_tok_move_units``, ``k_sparse_topk`` and the part merge behind it).
 
 Truth is numpy on the very arrays handed to the index (``tests/tokens_fakes.py``: float64 MaxSim, one ``lexsort``), never
 the code under test; the inputs are those of ``tests/tokens_cases.py``, which ``tests/test_tokens_index_host.py`` proves

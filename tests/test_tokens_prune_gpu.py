@@ -1,6 +1,6 @@
 """GPU: candidate generation for MaxSim on the codes -- ``IndexFlat.maxsim_candidates`` / ``search_maxsim_pruned``
 (kernels ``k_tok_ctable<P>``, ``k_tok_ci<WP>``, the radix select ``k_sel_hist`` / ``k_sel_count`` / ``k_sel_write``, then
-the existing ``k_tok_scores_c`` over the candidate list).
+the existing ``k_tok_scores<P, MT, NB>`` over the candidate list).
 
 Lattice inputs (tests/tokens_prune_cases.py; tests/test_tokens_prune_host.py proves that rows tie on the approximate
 score across rank ncand, within and across the select's slices, that pruned answers differ from and equal the

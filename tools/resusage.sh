@@ -9,7 +9,7 @@ for line in sys.stdin:
     t=m.group(1)
     if t.startswith('Function Name:'):
         if cur: print(cur)
-        cur={'fn':t.split(':',1)[1].strip()[:70]}
+        cur={'fn':t.split(':',1)[1].strip()}
     else:
         k,v=t.split(':',1); 
         if k.strip() in ('VGPRs','AGPRs','TotalSGPRs','ScratchSize [bytes/lane]','Occupancy [waves/SIMD]','LDS Size [bytes/block]'): cur[k.strip().split(' ')[0]]=v.strip()

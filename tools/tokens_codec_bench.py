@@ -1,4 +1,4 @@
-"""What compressed token matrices cost and what they lose: k_tok_scores_c over codes next to k_tok_scores over the
+"""What compressed token matrices cost and what they lose: k_tok_scores on the codes (NB = nbits) next to k_tok_scores (NB = 0) over the
 decoded matrices, k_tok_encode, the stored bytes, and the score error of a trained codec on clustered synthetic tokens.
 The library's own kernel timing (css_prof_*), one process, the calls alternating in blocks.
 
@@ -8,7 +8,7 @@ The library's own kernel timing (css_prof_*), one process, the calls alternating
 Before anything is timed, per (P, nbits): the scores of 65 536 rows over the compressed store equal, in bits, those of a
 second index that holds the decoded matrices (get_tokens).  Then, with `docs` docs of `doc-tokens` tokens and a 32-token
 query, per P in (128, 96) and nbits in (1, 2, 4):
- (a) k_tok_scores_c inside search_maxsim: kernel time, the bytes the layout implies (2 + P nbits / 8 per token, 16 per
+ (a) k_tok_scores<P, MT, NB> inside search_maxsim (scope tok_scores_c): kernel time, the bytes the layout implies (2 + P nbits / 8 per token, 16 per
      row) and the rate they give;
  (b) k_tok_scores in the same session on the second index (2 P bytes per token);
  (d) maxsim_ids for 64 ids: the kernel and the whole call;

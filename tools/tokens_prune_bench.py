@@ -1,5 +1,5 @@
 """What candidate generation buys MaxSim on the codes: search_maxsim_pruned (k_tok_ctable, k_tok_ci, the radix select,
-k_tok_scores_c over the candidates, the top-k) next to the exhaustive search_maxsim on the same index.  The library's own
+k_tok_scores on the codes over the candidates, the top-k) next to the exhaustive search_maxsim on the same index.  The library's own
 kernel timing (css_prof_*), one process, the calls alternating in four blocks of 5.
 
     python tools/tokens_prune_bench.py [--docs 100000] [--doc-tokens 128] [--json profiles/tokens_prune.json]
@@ -11,7 +11,7 @@ the candidates are the first ncand of ONE lexsort of that column.  Then, with `d
 centroids and a 32-token query, per P in (128, 96) and nbits in (1, 2, 4):
  (a) k_tok_ctable; (b) k_tok_ci with the bytes it moves (2 per token and 16 per row from HBM, 4 x 32 per token gathered
      from the table through the caches) and the rates they give; (c) the select at ncand = 1024 / 4096 / 16 384;
- (d) the whole search_maxsim_pruned call at k = 10, next to k_tok_scores_c and the whole search_maxsim call of the
+ (d) the whole search_maxsim_pruned call at k = 10, next to the exhaustive k_tok_scores (scope tok_scores_c) and the whole search_maxsim call of the
      exhaustive path in the same process.
  (r) recall, reported and not asserted: synth.clustered_token_matrices, 20 000 docs, a trained codec with 1024
      centroids, 16 queries; the overlap of the pruned top-10 with the exhaustive top-10 on the same codes at
