@@ -188,6 +188,9 @@ PROTOTYPES = {
     "css_index_maxsim_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "css_index_search_maxsim_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "css_index_last_maxsim_passes": (c_int, [c_void_p, POINTER(c_int)]),
+    "css_index_maxsim_rows_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "css_index_search_rerank_maxsim": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                               c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "css_index_maxsim_candidates": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                             POINTER(c_int64)]),
     "css_index_search_maxsim_pruned": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,

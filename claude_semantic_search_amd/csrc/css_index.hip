@@ -66,6 +66,10 @@
 //                      or compressed store: a block of 8 waves, one query per wave in registers, every 16-token tile
 //                      loaded (and decoded) once per block into an LDS ring in fragment order; ranked by
 //                      k_sparse_topk_cols and one part merge per group (css_tokens_batch.h)
+//   k_tok_scores_l,    css_index_maxsim_rows_batch / css_index_search_rerank_maxsim: the MaxSim of many query matrices,
+//   k_rr_lists,        each over a row list of its own, in one launch (the query belongs to the turn; a wave reloads its
+//   k_rr_out           fragments when its turn's query changes); the pool lists of a dense search as row lists, and the
+//                      answer from the ranked positions (css_tokens_lists.h)
 //   k_sig_count        css_index_subset_terms / _significant_terms: +1 per list entry of the selected rows into a
 //                      uint32 table [2^24], repeats merged in a per-block LDS table first; k_sig_score and the radix
 //                      select rank the terms (css_sigterms.h)
@@ -315,6 +319,13 @@ struct css_index {
     // css_index_search_maxsim_batch: [offsets | matrices] of the batch as uploaded, and the scans of its last call
     DevBuf<uint32_t> tk_bq;
     int last_maxsim_passes = 0;
+    // css_index_search_rerank_maxsim: [dense queries | offsets | matrices] as uploaded, the [nq, fetch] pool lists of
+    // the search, their row numbers and MaxSim column, and [S | R] of the returned rows, the trailing 4-byte columns
+    // of the call's results (the ranked positions are sp_pd / sp_pi)
+    DevBuf<uint32_t> rr_in, rr_rows;
+    DevBuf<float> rr_d, rr_col;
+    DevBuf<int64_t> rr_i;
+    DevBuf<int32_t> rr_sr;
     // css_index_maxsim_candidates / css_index_search_maxsim_pruned (css_token_prune.h): the centroid table [C][16 MT] of
     // the call's query (at most 16 MB), the candidate rows and their approximate scores [ncand], and the select's words
     // [4 x 256 bins | threshold key, need, all, count | 2 per block of the compaction].  The approximate column is
@@ -2934,6 +2945,7 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 #include "css_token_codec.h"
 #include "css_tokens.h"
 #include "css_tokens_batch.h"
+#include "css_tokens_lists.h"
 #include "css_token_prune.h"
 #include "css_where.h"
 #include "css_sigterms.h"
@@ -6165,6 +6177,198 @@ int css_index_maxsim_rows(css_index* ix, const uint16_t* q_tok_host, int mq, int
     const hipError_t e = hipStreamSynchronize(st);   // (also after a failure: the copies read this call's memory)
     if (rc != CSS_OK) return rc;
     CSS_HIP_TRY(e);
+    return CSS_OK;
+}
+
+// ------------------------------------------------------------------ MaxSim over per-query row lists, two-stage search
+namespace {
+// What both list entry points check of their queries before anything is enqueued (the store's P under the call's locks)
+int token_batch_check(const char* fn, const uint16_t* q_tok_host, const int64_t* q_offsets_host, int nq, int P) {
+    CSS_REQUIRE(nq >= 1 && nq <= CSS_MAX_MAXSIM_QUERIES, "%s: nq=%d outside [1, %d]", fn, nq, CSS_MAX_MAXSIM_QUERIES);
+    CSS_REQUIRE(q_tok_host && q_offsets_host, "%s: NULL buffer", fn);
+    CSS_REQUIRE(token_dim_ok(P), "%s: P=%d must be a multiple of 32 in [32, %d]", fn, P, CSS_MAX_TOKEN_DIM);
+    CSS_REQUIRE(q_offsets_host[0] == 0, "%s: the offsets start at %lld, not at 0", fn, (long long)q_offsets_host[0]);
+    int rc;
+    for (int b = 0; b < nq; ++b)
+        if ((rc = token_len_check(fn, q_offsets_host[b + 1] - q_offsets_host[b], b)) != CSS_OK) return rc;
+    for (int b = 0; b < nq; ++b)
+        if ((rc = token_finite_check(fn, q_tok_host + (size_t)q_offsets_host[b] * P, (int)(q_offsets_host[b + 1] - q_offsets_host[b]),
+                                     P, b)) != CSS_OK) return rc;
+    return CSS_OK;
+}
+int token_batch_longest(const int64_t* qoff, int nq) {
+    int64_t m = 0;
+    for (int b = 0; b < nq; ++b) m = std::max(m, qoff[b + 1] - qoff[b]);
+    return (int)m;
+}
+
+// col[b][j] = the MaxSim of query b (tokens q, offsets qoff [nq + 1] on the device; mq_max: the longest) with row
+// lists[b][j] (kTokNoRow: none), -inf for a miss: ONE launch.  The index has matrices.  Enqueued on `st`.
+int tok_lists_enqueue(css_index* ix, const uint32_t* lists, int nq, int f, const unsigned short* q, const int64_t* qoff,
+                      int mq_max, float* col, hipStream_t st) {
+    const void* fn = tok_variant(ix->tk_dim, (mq_max + 15) / 16, ix->tk_bits, [](auto p, auto mt, auto nb) {
+        return (const void*)k_tok_scores_l<decltype(p)::value, decltype(mt)::value, decltype(nb)::value>;
+    });
+    int rc, per;
+    unsigned grid;
+    if ((rc = tok_grid(ix, fn, 64 * kWaves, (int64_t)nq * f, kWaves, &per, &grid)) != CSS_OK) return rc;
+    TokStore store = tok_store(ix);
+    void* args[] = {&store, &lists, &nq, &f, &q, &qoff, &per, &col};
+    ProfScope ps(ix->tk_bits ? "tok_scores_lc" : "tok_scores_l", st);
+    CSS_HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(64 * kWaves), args, 0, st));
+    return CSS_OK;
+}
+
+// The pool search (search_any_k: every mode, shadow policy and mask as css_index_search_masked has them) into the owned
+// pool lists, the lists as row numbers under `floor`, their MaxSim with the queries' matrices in one launch, the k best
+// POSITIONS of each list and the four outputs.  Everything is enqueued on `st`; nothing waits for the device.  Caller
+// holds ws_mu and a shared lock on mu.
+int search_rerank_enqueue(css_index* ix, const Rows& rows, const float* q_dev, int nq, int normalize_q,
+                          const unsigned short* tok_dev, const int64_t* qoff_dev, int mq_max, int fetch, int k, float floor,
+                          float* D_dev, int64_t* I_dev, float* S_dev, int32_t* R_dev, hipStream_t st) {
+    int rc;
+    const int64_t total = (int64_t)nq * k, pool = (int64_t)nq * fetch;
+    WsTurn turn(ix, st);   // (until the end: every kernel behind the search reads the pool lists)
+    if (turn.rc != CSS_OK) return turn.rc;
+    if (ix->tk_rows == 0) {   // no matrices: every pool entry is a miss
+        hipLaunchKernelGGL(k_rr_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, D_dev, I_dev, S_dev, R_dev);
+        CSS_LAUNCH_CHECK();
+        return CSS_OK;
+    }
+    CSS_REQUIRE(rows.n < 0xFFFFFFFFll, "css_index_search_rerank_maxsim: %lld rows exceed the 32-bit row numbers of the lists",
+                (long long)rows.n);
+    // rows appended on another stream must have landed (an empty pool search does not wait for them itself)
+    if (ix->ingest_pending) CSS_HIP_TRY(hipStreamWaitEvent(st, ix->ingest_ev, 0));
+    if ((rc = ix->rr_d.grow((size_t)pool)) != CSS_OK) return rc;
+    if ((rc = ix->rr_i.grow((size_t)pool)) != CSS_OK) return rc;
+    if ((rc = ix->rr_rows.grow((size_t)pool)) != CSS_OK) return rc;
+    if ((rc = ix->rr_col.grow((size_t)pool)) != CSS_OK) return rc;
+    if ((rc = ix->sp_pd.grow((size_t)total)) != CSS_OK) return rc;
+    if ((rc = ix->sp_pi.grow((size_t)total)) != CSS_OK) return rc;
+    if ((rc = search_any_k(ix, rows, q_dev, nq, fetch, normalize_q, ix->rr_d.p, ix->rr_i.p, st)) != CSS_OK) return rc;
+    {
+        ProfScope ps("rr_lists", st);
+        hipLaunchKernelGGL(k_rr_lists, dim3((unsigned)((pool + 255) / 256)), dim3(256), 0, st, (const int64_t*)ix->rr_i.p,
+                           (const float*)ix->rr_d.p, pool, rows.id_base, floor, ix->rr_rows.p);
+        CSS_LAUNCH_CHECK();
+    }
+    if ((rc = tok_lists_enqueue(ix, ix->rr_rows.p, nq, fetch, tok_dev, qoff_dev, mq_max, ix->rr_col.p, st)) != CSS_OK) return rc;
+    {
+        // one slice per list (no part merge), positions in place of ids: ties go to the lower POSITION
+        ProfScope ps("rr_topk", st);
+        hipLaunchKernelGGL(k_sparse_topk_cols, dim3(1, (unsigned)nq), dim3(256), 0, st, (const float*)ix->rr_col.p, (int64_t)fetch,
+                           (int64_t)fetch, (const uint32_t*)nullptr, k, (int64_t)0, ix->sp_pd.p, ix->sp_pi.p);
+        CSS_LAUNCH_CHECK();
+    }
+    ProfScope ps("rr_out", st);
+    hipLaunchKernelGGL(k_rr_out, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)ix->sp_pd.p,
+                       (const int64_t*)ix->sp_pi.p, (const float*)ix->rr_d.p, (const int64_t*)ix->rr_i.p, fetch, k, total, D_dev,
+                       I_dev, S_dev, R_dev);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+}  // namespace
+
+int css_index_maxsim_rows_batch(css_index* ix, const uint16_t* q_tok_host, const int64_t* q_offsets_host, int nq, int P,
+                                const int64_t* ids_host, int f, float* scores_out) {
+    const char* fn = "css_index_maxsim_rows_batch";
+    CSS_REQUIRE(ix, "%s: NULL index", fn);
+    int rc = token_batch_check(fn, q_tok_host, q_offsets_host, nq, P);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(f >= 1 && f <= CSS_MAX_K, "%s: f=%d outside [1, %d]", fn, f, CSS_MAX_K);
+    CSS_REQUIRE(ids_host && scores_out, "%s: NULL buffer", fn);
+    CallScope cs(ix);
+    CSS_REQUIRE(ix->tk_rows == 0 || P == ix->tk_dim, "%s: the queries have P=%d, the stored matrices P=%d", fn, P, ix->tk_dim);
+    const size_t total = (size_t)nq * f;
+    if (ix->tk_rows == 0) {   // no matrices: every row is a miss
+        for (size_t i = 0; i < total; ++i) scores_out[i] = -INFINITY;
+        return CSS_OK;
+    }
+    CSS_REQUIRE(cs.rows.n < 0xFFFFFFFFll, "%s: %lld rows exceed the 32-bit row numbers of the lists", fn, (long long)cs.rows.n);
+    // the ONE upload: [offsets (int64) | row numbers | the matrices], each part at a multiple of 16 bytes
+    const size_t ntok = (size_t)q_offsets_host[nq];
+    const size_t at_ids = ((size_t)(nq + 1) * 2 + 3) / 4 * 4, at_tok = at_ids + (total + 3) / 4 * 4, q_words = ntok * P / 2;
+    std::vector<uint32_t> in;
+    try {
+        in.assign(at_tok + q_words, 0u);
+    } catch (const std::bad_alloc&) {
+        css::set_error("%s: out of host memory", fn);
+        return CSS_ERR_OOM;
+    }
+    memcpy(in.data(), q_offsets_host, (size_t)(nq + 1) * sizeof(int64_t));
+    for (size_t i = 0; i < total; ++i) {   // an id outside the index names no row
+        const int64_t r = ids_host[i] - cs.rows.id_base;
+        in[at_ids + i] = (ids_host[i] >= cs.rows.id_base && r < cs.rows.n) ? (uint32_t)r : kTokNoRow;
+    }
+    memcpy(in.data() + at_tok, q_tok_host, ntok * P * sizeof(uint16_t));
+    const hipStream_t st = ix->stream;
+    if ((rc = ix->tk_bq.grow(in.size())) != CSS_OK) return rc;
+    if ((rc = ix->tk_col.grow(total)) != CSS_OK) return rc;
+    {
+        WsTurn turn(ix, st);
+        rc = turn.rc;
+        if (rc == CSS_OK) {
+            const hipError_t e = hipMemcpyAsync(ix->tk_bq.p, in.data(), in.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) rc = css::hip_fail(e, "hipMemcpyAsync(lists)", __FILE__, __LINE__);
+        }
+        if (rc == CSS_OK && ix->ingest_pending) {
+            const hipError_t e = hipStreamWaitEvent(st, ix->ingest_ev, 0);
+            if (e != hipSuccess) rc = css::hip_fail(e, "hipStreamWaitEvent(ingest)", __FILE__, __LINE__);
+        }
+        if (rc == CSS_OK)
+            rc = tok_lists_enqueue(ix, ix->tk_bq.p + at_ids, nq, f, reinterpret_cast<const unsigned short*>(ix->tk_bq.p + at_tok),
+                                   reinterpret_cast<const int64_t*>(ix->tk_bq.p), token_batch_longest(q_offsets_host, nq),
+                                   ix->tk_col.p, st);
+        if (rc == CSS_OK) {
+            const hipError_t e = hipMemcpyAsync(scores_out, ix->tk_col.p, total * sizeof(float), hipMemcpyDeviceToHost, st);
+            if (e != hipSuccess) rc = css::hip_fail(e, "hipMemcpyAsync(scores)", __FILE__, __LINE__);
+        }
+    }
+    const hipError_t e = hipStreamSynchronize(st);   // (also after a failure: the copies read this call's memory)
+    if (rc != CSS_OK) return rc;
+    CSS_HIP_TRY(e);
+    return CSS_OK;
+}
+
+int css_index_search_rerank_maxsim(css_index* ix, const float* q_host, int normalize_q, const uint16_t* q_tok_host,
+                                   const int64_t* q_offsets_host, int nq, int P, int fetch, int k, float floor,
+                                   const uint32_t* allow_bits_host, float* D_host, int64_t* I_host, float* S_host, int32_t* R_host) {
+    const char* fn = "css_index_search_rerank_maxsim";
+    CSS_REQUIRE(ix, "%s: NULL index", fn);
+    int rc = token_batch_check(fn, q_tok_host, q_offsets_host, nq, P);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(fetch >= 1 && fetch <= CSS_MAX_K, "%s: fetch=%d outside [1, %d]", fn, fetch, CSS_MAX_K);
+    CSS_REQUIRE(k >= 1 && k <= std::min(fetch, CSS_KERNEL_MAX_K), "%s: k=%d outside [1, min(fetch=%d, %d)]", fn, k, fetch,
+                CSS_KERNEL_MAX_K);
+    CSS_REQUIRE(q_host && D_host && I_host && S_host && R_host, "%s: NULL buffer", fn);
+    // the ONE upload: [dense queries (fp32) | offsets (int64) | the matrices], each part at a multiple of 16 bytes
+    const size_t ntok = (size_t)q_offsets_host[nq], n = (size_t)nq * k;
+    const size_t at_off = ((size_t)nq * ix->dim + 3) / 4 * 4, at_tok = at_off + ((size_t)(nq + 1) * 2 + 3) / 4 * 4;
+    std::vector<uint32_t> in;
+    std::vector<int32_t> sr;
+    try {
+        in.assign(at_tok + ntok * P / 2, 0u);
+        sr.assign(2 * n, 0);
+    } catch (const std::bad_alloc&) {
+        css::set_error("%s: out of host memory", fn);
+        return CSS_ERR_OOM;
+    }
+    memcpy(in.data(), q_host, (size_t)nq * ix->dim * sizeof(float));
+    memcpy(in.data() + at_off, q_offsets_host, (size_t)(nq + 1) * sizeof(int64_t));
+    memcpy(in.data() + at_tok, q_tok_host, ntok * P * sizeof(uint16_t));
+    HostCall hc(ix);
+    CSS_REQUIRE(ix->tk_rows == 0 || P == ix->tk_dim, "%s: the queries have P=%d, the stored matrices P=%d", fn, P, ix->tk_dim);
+    hc.cols = 2;   // [S | R]
+    rc = hc.upload(allow_bits_host, ix->rr_in, (const uint32_t*)in.data(), in.size(), n, &ix->rr_sr);
+    if (rc == CSS_OK)
+        rc = search_rerank_enqueue(ix, hc.rows, reinterpret_cast<const float*>(ix->rr_in.p), nq, normalize_q,
+                                   reinterpret_cast<const unsigned short*>(ix->rr_in.p + at_tok),
+                                   reinterpret_cast<const int64_t*>(ix->rr_in.p + at_off), token_batch_longest(q_offsets_host, nq),
+                                   fetch, k, floor, hc.d_out, hc.i_out, reinterpret_cast<float*>(hc.g_out), hc.g_out + n, ix->stream);
+    rc = hc.finish(rc, D_host, I_host, sr.data());
+    if (rc != CSS_OK) return rc;
+    memcpy(S_host, sr.data(), n * sizeof(float));
+    memcpy(R_host, sr.data() + n, n * sizeof(int32_t));
     return CSS_OK;
 }
 

@@ -582,6 +582,52 @@ def maxsim_batch_args(q_mats, k, what: str = "search_maxsim_batch"):
     return off, np.ascontiguousarray(np.concatenate(qs), dtype=np.uint16), k
 
 
+def rerank_args(q, q_mats, k, fetch, floor=None, d: Optional[int] = None, ids=None, what: str = "search_rerank_maxsim"):
+    """The checked arguments of the list calls: ``(a float32 [nq, d] or None, offsets int64 [nq + 1], tokens uint16
+    [offsets[nq], P], k or None, fetch, floor float, ids int64 [nq, fetch] or None)``; what the library would refuse raises
+    ``ValueError`` here, before the library is called, and names the query.  ``q_mats`` as ``maxsim_batch_args`` takes
+    them (1 to 1024 matrices of one P).  For ``search_rerank_maxsim``: ``q`` holds one dense row per matrix, ``1 <= fetch
+    <= 2048``, ``1 <= k <= min(fetch, 128)``, ``floor`` a number or ``None`` (NaN: no floor).  For ``maxsim_ids_batch``
+    (``q`` and ``k`` are ``None``): ``ids`` is ``[nq, f]`` with ``1 <= f <= 2048``, and ``fetch`` is taken from it."""
+    off, tok, _ = maxsim_batch_args(q_mats, None, what=what)
+    nq = off.shape[0] - 1
+    if ids is not None:
+        try:
+            ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64))
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: ids must be an integer array [nq, f], one list per query") from None
+        if ids.ndim != 2 or ids.shape[0] != nq:
+            raise ValueError(f"{what}: ids of shape {ids.shape} for {nq} queries, expected [{nq}, f]")
+        fetch = ids.shape[1]
+    try:
+        f = int(fetch)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: fetch={fetch!r} is no integer") from None
+    if f != fetch or not 1 <= f <= nat.MAX_K:
+        raise ValueError(f"{what}: {'f' if ids is not None else 'fetch'}={fetch!r} outside [1, {nat.MAX_K}]")
+    a = None
+    if q is not None:
+        a = _as_f32_2d(q, int(d), what)
+        if a.shape[0] != nq:
+            raise ValueError(f"{what}: {a.shape[0]} dense queries for {nq} query matrices")
+    if k is not None:
+        try:
+            kk = int(k)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: k={k!r} is no integer") from None
+        if kk != k or not 1 <= kk <= min(f, MAX_HYBRID_K):
+            raise ValueError(f"{what}: k={k!r} outside [1, min(fetch={f}, {MAX_HYBRID_K})]")
+        k = kk
+    if floor is None:
+        fl = float("nan")
+    else:
+        try:
+            fl = float(floor)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: floor={floor!r} is no number") from None
+    return a, off, tok, k, f, fl, ids
+
+
 MAX_TOKEN_CENTROIDS = 65536   # CSS_MAX_TOKEN_CENTROIDS
 TOKEN_CODEC_BITS = (1, 2, 4)
 
@@ -866,6 +912,64 @@ def search_maxsim_pruned_numpy(codec: TokenCodec, offsets, codes, res, q, k: int
     D, I = np.full((1, k), -np.finfo(np.float32).max, np.float32), np.full((1, k), -1, np.int64)
     D[0, :order.size], I[0, :order.size] = sc[order], ids[order] + int(id_base)
     return D, I
+
+
+def token_scores(offsets, tok, q, rows=None) -> np.ndarray:
+    """The MaxSim of ONE query matrix with the RAW matrices of ``rows`` (default: every row) in float32 (dots, maximum,
+    ascending sum), ``-inf`` for a row without tokens: ``token_codec_scores`` for a store without a codec.  The device's
+    bits where the dots are exact."""
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    rows = np.arange(off.shape[0] - 1) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
+    q32 = bf16_to_f32(np.asarray(q, dtype=np.uint16))
+    tok = np.asarray(tok, dtype=np.uint16).reshape(-1, q32.shape[1])
+    lens = off[rows + 1] - off[rows]
+    out = np.full(rows.shape[0], -np.inf, dtype=np.float32)
+    live = np.flatnonzero(lens > 0)
+    if live.size:
+        idx = np.concatenate([np.arange(off[r], off[r + 1]) for r in rows[live]])
+        starts = np.concatenate([[0], np.cumsum(lens[live])[:-1]])
+        sim = bf16_to_f32(tok[idx]) @ q32.T                                             # [E', mq]
+        out[live] = _sum_ascending_f32(np.maximum.reduceat(sim.astype(np.float32), starts, axis=0))
+    return out
+
+
+def maxsim_lists_numpy(offsets, q_mats, ids, tok=None, codec: Optional[TokenCodec] = None, codes=None, res=None,
+                       id_base: int = 0) -> np.ndarray:
+    """The numpy double of ``maxsim_ids_batch``: float32 ``[nq, f]``, entry ``(b, j)`` the MaxSim of ``q_mats[b]`` with row
+    ``ids[b, j] - id_base`` of the store -- raw (``tok``) through ``token_scores``, compressed (``codec, codes, res``)
+    through ``token_codec_scores`` -- and ``-inf`` for an id that names no row with a matrix."""
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    ids = np.asarray(ids, dtype=np.int64)
+    T = off.shape[0] - 1
+    out = np.full(ids.shape, -np.inf, dtype=np.float32)
+    for b, q in enumerate(q_mats):
+        r = ids[b] - int(id_base)
+        ok = np.flatnonzero((r >= 0) & (r < T))
+        if ok.size:
+            out[b, ok] = (token_scores(off, tok, q, r[ok]) if codec is None
+                          else token_codec_scores(codec, off, codes, res, q, r[ok]))
+    return out
+
+
+def search_rerank_maxsim_numpy(S0, I0, late, k: int, floor=None):
+    """The numpy double of the ranking of ``search_rerank_maxsim``: from the pool ``(S0, I0) [nq, fetch]`` of the dense
+    search and the MaxSim ``late [nq, fetch]`` of its entries, ``(D, I, S, R)``, each ``[nq, k]``: the entries with ``S0 <
+    floor``, the ``-1`` padding and the ``-inf`` scores dropped, then the first ``k`` of a STABLE descending sort by the
+    late score (ties keep the pool's order); padded with ``D = S = -FLT_MAX``, ``I = R = -1``."""
+    S0, I0 = np.asarray(S0, dtype=np.float32), np.asarray(I0, dtype=np.int64)
+    late = np.asarray(late, dtype=np.float32)
+    nq, k = S0.shape[0], int(k)
+    fmax = np.finfo(np.float32).max
+    D, S = np.full((nq, k), -fmax, np.float32), np.full((nq, k), -fmax, np.float32)
+    I, R = np.full((nq, k), -1, np.int64), np.full((nq, k), -1, np.int32)
+    for b in range(nq):
+        ok = (I0[b] >= 0) & (late[b] > -np.inf)
+        if floor is not None and floor == floor:
+            ok &= ~(S0[b] < np.float32(floor))
+        pos = np.flatnonzero(ok)
+        pos = pos[np.argsort(-(late[b, pos] + np.float32(0.0)), kind="stable")][:k]
+        D[b, :pos.size], I[b, :pos.size], S[b, :pos.size], R[b, :pos.size] = late[b, pos], I0[b, pos], S0[b, pos], pos
+    return D, I, S, R
 
 
 MAX_DIVERSE_FETCH = nat.MAX_DIVERSE_FETCH
@@ -1975,6 +2079,38 @@ class IndexFlat:
                                                   ids.ctypes.data if ids.size else None, ids.shape[0],
                                                   out.ctypes.data if ids.size else None))
         return out
+
+    def maxsim_ids_batch(self, q_mats, ids) -> np.ndarray:
+        """``maxsim_ids`` for a sequence of up to 1024 query matrices, each with its OWN list of ``f`` GLOBAL ids
+        (``ids [nq, f]``, ``1 <= f <= 2048``), in one call and one kernel launch (``css_index_maxsim_rows_batch``):
+        float32 ``[nq, f]``, entry ``(b, j)`` the bits of ``maxsim_ids(q_mats[b], [ids[b, j]])``.  ``-inf`` for a row
+        without tokens and, unlike the single call, for an id outside the index (the ``-1`` padding of a search, say)."""
+        _, off, tok, _, f, _, ids = rerank_args(None, q_mats, None, None, ids=ids, what="maxsim_ids_batch")
+        nq = off.shape[0] - 1
+        out = np.empty((nq, f), dtype=np.float32)
+        nat.check(nat.lib().css_index_maxsim_rows_batch(self._handle(), tok.ctypes.data, off.ctypes.data, nq, tok.shape[1],
+                                                        ids.ctypes.data, f, out.ctypes.data))
+        return out
+
+    def search_rerank_maxsim(self, q, q_mats, k: int, fetch: int, normalize: bool = False, floor=None,
+                             allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Two-stage search in one call (``css_index_search_rerank_maxsim``): the dense ``search(q, fetch, normalize,
+        allow)`` for a pool per query, the pool's rows re-ranked by the MaxSim of ``q_mats[b]`` with their stored token
+        matrices, and the ``k`` best by that score, ties in the pool's order.  ``(D, I, S, R)``, each ``[nq, k]``: the
+        MaxSim score, the global id, the row's dense score and (int32) its position in the pool.  ``floor``: pool
+        entries with a dense score ``< floor`` are left out (``None``: none are).  Rows without tokens are never
+        returned; missing entries pad with ``D = S = -FLT_MAX``, ``I = R = -1``.  ``D`` has the bits of ``maxsim_ids``,
+        the pool is ``search``'s; no id travels through the host.  ``1 <= k <= min(fetch, 128)``, ``fetch <= 2048``."""
+        a, off, tok, k, fetch, floor, _ = rerank_args(q, q_mats, k, fetch, floor, d=self.d)
+        nq = off.shape[0] - 1
+        D, I = np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int64)
+        S, R = np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int32)
+        h = self._handle()
+        bits, bits_ptr = self._allow_bits(allow)
+        nat.check(nat.lib().css_index_search_rerank_maxsim(h, a.ctypes.data, 1 if normalize else 0, tok.ctypes.data,
+                                                           off.ctypes.data, nq, tok.shape[1], fetch, k, floor, bits_ptr,
+                                                           D.ctypes.data, I.ctypes.data, S.ctypes.data, R.ctypes.data))
+        return D, I, S, R
 
     # -- candidate generation for MaxSim on the codes (PLAID) ----------------------
     def _prune_codec(self, what: str) -> None:

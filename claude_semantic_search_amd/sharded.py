@@ -881,6 +881,48 @@ class ShardedFlatIndex:
             out[own] = self.local.maxsim_ids(q, ids[own] if len(self.segments) == 1 else loc[own])
         return self._sum_over_ranks(out.view(np.int32)).view(np.float32)
 
+    def _max_over_ranks(self, a: np.ndarray) -> np.ndarray:
+        """ONE max all-reduce of a host array (none with one rank, or for nothing)."""
+        import torch
+
+        if self.world == 1 or a.size == 0:
+            return a
+        t = torch.from_numpy(a).to(self._exchange_device())
+        self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.group)
+        return t.cpu().numpy()
+
+    def maxsim_ids_batch(self, q_mats, ids) -> np.ndarray:
+        """``IndexFlat.maxsim_ids_batch`` of GLOBAL ``ids [nq, f]`` on every rank (collective): every rank scores its
+        own share with ONE local call (the ids of other shards name no row there: ``-inf``), then ONE max all-reduce
+        of the ``[nq, f]`` scores (exact: one contribution per id that is not ``-inf``)."""
+        from .flat_index import rerank_args
+
+        _, off, tok, _, _, _, ids = rerank_args(None, q_mats, None, None, ids=ids, what="maxsim_ids_batch")
+        mats = [tok[off[b]:off[b + 1]] for b in range(off.shape[0] - 1)]
+        # (one segment: the local index adds id_base itself, so it is asked by global id)
+        mine = np.where(self._local_ids(ids) >= 0, ids, -1) if len(self.segments) == 1 else self._local_ids(ids)
+        out = np.full(ids.shape, -np.inf, dtype=np.float32)
+        if (mine >= 0).any():
+            out = np.ascontiguousarray(self.local.maxsim_ids_batch(mats, mine), dtype=np.float32)
+        return self._max_over_ranks(out)
+
+    def search_rerank_maxsim(self, q, q_mats, k: int, fetch: int, normalize: bool = False, floor=None, allow=None):
+        """``IndexFlat.search_rerank_maxsim`` over the shards (collective): ``(D, I, S, R)`` with global ids on every
+        rank, the single index's bytes.  The sharded ``search`` gives every rank the GLOBAL pool, every rank scores
+        its own share of it (``maxsim_ids_batch``: one max all-reduce of ``[nq, fetch]`` scores), and every rank then
+        ranks with the stable sort of ``search_rerank_maxsim_numpy``."""
+        from .flat_index import rerank_args, search_rerank_maxsim_numpy
+
+        a, off, tok, k, fetch, floor, _ = rerank_args(q, q_mats, k, fetch, floor, d=self.d)
+        mats = [tok[off[b]:off[b + 1]] for b in range(off.shape[0] - 1)]
+        if self._single():
+            D, I, S, R = self.local.search_rerank_maxsim(a, mats, k, fetch, normalize=normalize, floor=floor,
+                                                         allow=self._local_allow(allow))
+            return D, np.ascontiguousarray(self._to_global_np(np.asarray(I, dtype=np.int64))), S, R
+        S0, I0 = self.search(a, fetch, normalize, allow=allow)
+        late = self.maxsim_ids_batch(mats, I0)
+        return search_rerank_maxsim_numpy(S0, I0, late, k, floor)
+
     def maxsim_candidates(self, q_mat, ncand: int, allow=None):
         """``IndexFlat.maxsim_candidates`` over the shards (collective): ``(ids, approx)`` with global ids, ascending,
         on every rank.  A row's approximate score is a function of its own codes, the codec and the query, and a
@@ -1309,6 +1351,12 @@ class ShardedIndexFacade:
 
     def maxsim_ids(self, q_mat, ids) -> np.ndarray:
         return self.sh.maxsim_ids(q_mat, ids)
+
+    def maxsim_ids_batch(self, q_mats, ids) -> np.ndarray:
+        return self.sh.maxsim_ids_batch(q_mats, ids)
+
+    def search_rerank_maxsim(self, q, q_mats, k: int, fetch: int, normalize: bool = False, floor=None, allow=None):
+        return self.sh.search_rerank_maxsim(q, q_mats, int(k), int(fetch), normalize=normalize, floor=floor, allow=allow)
 
     def maxsim_candidates(self, q_mat, ncand: int, allow=None):
         return self.sh.maxsim_candidates(q_mat, int(ncand), allow=allow)

@@ -1517,6 +1517,62 @@ class HybridStorage:
             scores = np.asarray(self.faiss_index.maxsim_ids(q_mat, ids), dtype=np.float32).reshape(-1)
         return [Reranked(hits[int(i)], float(scores[i]), int(i)) for i in np.argsort(-scores, kind="stable")[:cfg.top_k]]
 
+    def search_late_reranked_many(self, query_texts: Sequence[str], query_embeddings, late,
+                                  config: Optional[SearchConfig] = None, filters: Optional[Dict[str, Any]] = None,
+                                  fetch: int = 50) -> List[List[Reranked]]:
+        """``search_late_reranked`` for several queries at once, both stages inside the index: ONE
+        ``late.encode_queries`` call (each query in a forward pass of its own, as ``search_late_reranked`` encodes it),
+        ONE allow mask and one ``IndexFlat.search_rerank_maxsim`` per 1024 queries -- the dense search for the
+        ``max(fetch, top_k)`` best rows of every query, their MaxSim with the stored matrices in one kernel launch and
+        the ranking, with ``floor = similarity_threshold``; no id travels through the host between the stages.
+        On a store without tombstones and without filters (inner-product similarities, ``top_k <= 128``, every chunk
+        with at least one kept token) element ``i`` equals ``search_late_reranked(query_texts[i], query_embeddings[i],
+        late, config, fetch=fetch)`` in chunk ids, score bits and ``rank_before``.  Where the two differ:
+        tombstoned rows never enter the pool here -- they are always in the allow mask, so the pool holds ``fetch``
+        LIVE rows, where ``search_late_reranked`` without ``filter_pushdown`` lets a deleted row take a place of the
+        pool and drops it afterwards; ``filters`` are always pushed down into the mask, where ``search_late_reranked``
+        without ``filter_pushdown`` filters the best ``max_results`` rows on the host; a hit whose stored matrix is
+        empty is left out, where ``search_late_reranked`` returns it last with ``-inf``; the pool is at most 2048
+        rows and ``top_k`` at most 128."""
+        self._require("late-interaction re-ranking", "set_tokens", "search_rerank_maxsim")
+        texts = [t or "" for t in query_texts]
+        if not texts:
+            return []
+        with self._lock:
+            frame = self._search_frame(config)
+            if frame is None or frame[0].top_k <= 0:
+                return [[] for _ in texts]
+            cfg, ntotal, _ = frame
+            Q = np.ascontiguousarray(np.asarray(query_embeddings, dtype=np.float32).reshape(len(texts), -1))
+            n = min(max(int(fetch), cfg.top_k), fi.MAX_K)
+            k = max(1, min(cfg.top_k, n, fi.MAX_HYBRID_K))
+            tombstones = len(self.faiss_id_to_chunk_id) < ntotal
+            allow = self._mask_of(filters or {}, ntotal) if (filters or tombstones) else None
+            # the smallest float32 that is no less than the threshold: `s < floor` is then `s < threshold` for every float32 s
+            with np.errstate(over="ignore"):
+                floor = np.float32(cfg.similarity_threshold)
+                if float(floor) < float(cfg.similarity_threshold):
+                    floor = np.nextafter(floor, np.float32(np.inf))
+            self._sync_tokens(ntotal, late)
+            # (one query per forward pass: the encoder picks its tiling by the tokens of a batch, so a query encoded
+            # beside others can differ in the last bits of its bf16 tokens from the matrix search_late_reranked forms)
+            q_mats = late.encode_queries(texts, batch_size=1)[0]
+            out: List[List[Reranked]] = []
+            for b0 in range(0, len(texts), fi.MAX_MAXSIM_QUERIES):
+                b1 = min(b0 + fi.MAX_MAXSIM_QUERIES, len(texts))
+                D, I, S, R = self.faiss_index.search_rerank_maxsim(Q[b0:b1], q_mats[b0:b1], k, n,
+                                                                   normalize=self.config.normalize_embeddings,
+                                                                   floor=float(floor), allow=allow)
+                for b in range(b1 - b0):
+                    hits: List[Reranked] = []
+                    for d, fid, s, r in zip(D[b].tolist(), I[b].tolist(), S[b].tolist(), R[b].tolist()):
+                        chunk_id = self.faiss_id_to_chunk_id.get(fid) if fid >= 0 else None
+                        data = self._get_chunk_data(chunk_id) if chunk_id else None
+                        if data:
+                            hits.append(Reranked(self._make_result(chunk_id, s, data, cfg), float(d), int(r)))
+                    out.append(hits)
+            return out
+
     @staticmethod
     def _make_result(chunk_id: str, score: float, data: Dict[str, Any], cfg: SearchConfig) -> SearchResult:
         res = SearchResult(chunk_id=chunk_id, similarity=float(score))

@@ -606,6 +606,39 @@ int css_index_search_maxsim_batch(css_index* ix, const uint16_t* q_tok_host /* b
                                   const uint32_t* allow_bits_host, float* D_host /* [nq, k] */, int64_t* I_host /* [nq, k] */);
 int css_index_last_maxsim_passes(css_index* ix, int* passes_out);
 
+/* MaxSim over per-query row lists, and the two-stage search built on it: a dense first stage whose best `fetch` rows
+ * per query are re-ranked by MaxSim with the rows' stored matrices, in ONE call (Vespa's second phase, ColBERT as a
+ * re-ranker).  The queries' matrices are given as in css_index_search_maxsim_batch (tokens, offsets from 0, one P), with
+ * its limits and checks: 1 <= nq <= CSS_MAX_MAXSIM_QUERIES, every query 1 .. CSS_MAX_QUERY_TOKENS tokens with finite
+ * components, P equal to css_index_token_dim (any valid P while the index has no matrices).  Every refusal names the
+ * query, comes before anything is enqueued and leaves the index usable; neither call edits the index.
+ *  - css_index_maxsim_rows_batch is css_index_maxsim_rows for nq queries, each with its own list of f ids, 1 <= f <=
+ *    CSS_MAX_K: scores_out[b * f + j] has the bits of css_index_maxsim_rows(q_b, ids[b * f + j]), on raw and compressed
+ *    stores, -inf for a miss.  Unlike the single call, an id outside the index is no refusal: it names no row and
+ *    scores -inf (a list may carry the -1 padding of a search).  An index without matrices: all -inf.  One upload
+ *    [offsets | row numbers | matrices], ONE launch of k_tok_scores_l (css_tokens_lists.h), one copy back, one wait.
+ *  - css_index_search_rerank_maxsim.  q_host [nq, d] are the dense queries of the SAME nq requests; 1 <= fetch <=
+ *    CSS_MAX_K, 1 <= k <= min(fetch, CSS_KERNEL_MAX_K); floor is a float, NaN = no floor.  Row b of the answer is:
+ *    the pool (S0, I0) = css_index_search_masked(q_host, nq, fetch, normalize_q, allow_bits_host) of the same call
+ *    shape; drop the entries with S0 < floor (that comparison on an index of either metric) and the -1 padding; score
+ *    the rest with css_index_maxsim_rows(q_b, I0[b]); drop -inf; take the first k of a STABLE descending sort by that
+ *    score -- ties keep the pool's order.  D [nq, k] = the MaxSim score, I = the global id, S = the row's dense score
+ *    in the pool, R (int32) = its position in the pool.  Fewer than k entries, an index without matrices or without
+ *    rows: padding, D = S = -FLT_MAX, I = R = -1.
+ *    On the device, all on the index's stream under one turn at the workspaces: the pool search of css_index_search
+ *    into owned lists, k_rr_lists (ids to row numbers under the floor), k_tok_scores_l, k_sparse_topk_cols over the
+ *    [nq, fetch] columns by POSITION (one slice, no part merge) and k_rr_out.  One upload [dense queries | offsets |
+ *    matrices], one wait; no id travels through the host.  css_index_set_token_blocks sets the grid of k_tok_scores_l
+ *    as well; the bits do not depend on it, on nq or on a row's position in its list. */
+int css_index_maxsim_rows_batch(css_index* ix, const uint16_t* q_tok_host /* bf16 [q_offsets[nq], P] */,
+                                const int64_t* q_offsets_host /* [nq + 1], from 0 */, int nq, int P,
+                                const int64_t* ids_host /* [nq, f] */, int f, float* scores_out /* [nq, f] */);
+int css_index_search_rerank_maxsim(css_index* ix, const float* q_host /* [nq, d] */, int normalize_q,
+                                   const uint16_t* q_tok_host /* bf16 [q_offsets[nq], P] */,
+                                   const int64_t* q_offsets_host /* [nq + 1], from 0 */, int nq, int P, int fetch, int k,
+                                   float floor, const uint32_t* allow_bits_host, float* D_host /* [nq, k] */,
+                                   int64_t* I_host /* [nq, k] */, float* S_host /* [nq, k] */, int32_t* R_host /* [nq, k] */);
+
 /* Significant terms (Elasticsearch's significant_terms aggregation, the keyword side of BERTopic): which terms set a
  * selection of rows apart from a background -- "what is in this cluster / this project / these hits".  Everything is
  * read from the term lists above; the rows' values play no part.  T = the leading rows that have lists.
