@@ -18,7 +18,8 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import synth
-from .mpnet_encoder import BERT_SMALL_CFG, MpnetEncoder, _find_model_dir, _load_state_dict, parse_model_config
+from .head_model import HeadModel, rank_scores  # noqa: F401  (rank_scores: imported from here by callers)
+from .mpnet_encoder import length_sorted_batches, parse_model_config
 
 #: synthetic tensor ids of the head (the body uses 0-5 and 16 + 16 * layer + 0..15): (id, std) of pooler weight,
 #: pooler bias, classifier weight, classifier bias
@@ -100,76 +101,35 @@ def synth_head(hidden: int, seed: int) -> Dict[str, np.ndarray]:
             "cls_w": t("cls_w", hidden), "cls_b": t("cls_b", 1)}
 
 
-def rank_scores(scores: Sequence[float], documents: Optional[Sequence[str]] = None, top_k: Optional[int] = None,
-                return_documents: bool = False) -> List[dict]:
-    """``[{"corpus_id", "score"[, "text"]}]`` best first; ties go to the lower ``corpus_id``."""
-    s = np.asarray(scores, dtype=np.float32)
-    order = np.argsort(-s, kind="stable")
-    if top_k is not None:
-        order = order[:max(0, int(top_k))]
-    out = []
-    for i in order:
-        hit = {"corpus_id": int(i), "score": float(s[i])}
-        if return_documents:
-            hit["text"] = documents[int(i)]
-        out.append(hit)
-    return out
+class CrossEncoder(HeadModel):
+    _noun = "a cross-encoder"
+    _parse_config = staticmethod(parse_cross_encoder_config)
 
-
-class CrossEncoder:
     def __init__(self, model_name_or_path: Optional[str], device: int = 0, compute: str = "bf16",
                  max_length: Optional[int] = None, synthetic_seed: Optional[int] = None,
                  cfg_overrides: Optional[dict] = None):
-        self.model_dir = None
-        if synthetic_seed is None:
-            model_dir = _find_model_dir(model_name_or_path or "", None)
-            if model_dir is None:
-                raise FileNotFoundError(f"model '{model_name_or_path}' not found locally (no network): pass a directory "
-                                        "in HF layout, or synthetic_seed=<int> for seeded synthetic weights")
-            cfg = parse_cross_encoder_config(model_dir)
-            body, head = split_state_dict(_load_state_dict(model_dir))
-            over = dict(pooling=cfg["pooling"], normalize=cfg["normalize"])
-            over.update(cfg_overrides or {})
-            self.encoder = MpnetEncoder(str(model_dir), device=device, compute=compute, cfg_overrides=over, weights=body)
-            try:
-                self.encoder.set_head(head["pooler.dense.weight"], head["pooler.dense.bias"],
-                                      head["classifier.weight"], head["classifier.bias"])
-                if self.encoder.tokenizer is None:
-                    raise FileNotFoundError(self.encoder.tokenizer_problem)
-            except Exception:
-                self.encoder.close()
-                raise
-            self.tokenizer = self.encoder.tokenizer
-            self.model_dir = model_dir
-        else:
-            cfg = dict(BERT_SMALL_CFG, pooling="cls", normalize=False)
-            if cfg_overrides:
-                cfg.update(cfg_overrides)
-            if cfg.get("arch") != "bert":
-                raise ValueError(f"unsupported arch {cfg.get('arch')!r} for a cross-encoder (supported: 'bert')")
-            self.encoder = MpnetEncoder(synthetic_seed=synthetic_seed, device=device, compute=compute, cfg_overrides=cfg)
-            h = synth_head(int(cfg["hidden"]), synthetic_seed)
-            self.encoder.set_head(h["pooler_w"], h["pooler_b"], h["cls_w"], h["cls_b"])
-            self.tokenizer = self.encoder.tokenizer   # (HashTokenizer: any deterministic text -> ids map will do)
-        self.cfg = self.encoder.cfg
+        super().__init__(model_name_or_path, device, compute, synthetic_seed, cfg_overrides)
         limit = int(self.cfg["max_seq_len"])
         self.max_length = limit if max_length is None else int(max_length)
         if not 3 <= self.max_length <= limit:
-            self.encoder.close()
+            self.close()
             raise ValueError(f"max_length={self.max_length} outside [3, {limit}] (the encoder's max_seq_len)")
         if synthetic_seed is None:
             self.cls_id, self.sep_id = int(self.tokenizer.bos), int(self.tokenizer.eos)
         else:   # the hashing tokenizer has no [CLS] / [SEP]: bert-base-uncased's positions (never the pad id 0)
             self.cls_id, self.sep_id = (101, 102) if int(self.cfg["vocab"]) > 102 else (1, 2)
 
-    def close(self) -> None:
-        self.encoder.close()
+    # the head as set_head takes it: pooler weight, pooler bias, classifier weight, classifier bias
+    def _split(self, sd, cfg):
+        body, head = split_state_dict(sd)
+        return body, [head[k] for k in _HEAD_KEYS]
 
-    def __enter__(self) -> "CrossEncoder":
-        return self
+    def _synth(self, cfg, seed):
+        h = synth_head(int(cfg["hidden"]), seed)
+        return [h["pooler_w"], h["pooler_b"], h["cls_w"], h["cls_b"]]
 
-    def __exit__(self, *exc) -> None:
-        self.close()
+    def _attach(self, head) -> None:
+        self.encoder.set_head(*head)
 
     # -- pairs ----------------------------------------------------------------
     def _side_ids(self, texts: Sequence[str]) -> List[List[int]]:
@@ -198,18 +158,8 @@ class CrossEncoder:
             return np.zeros(0, dtype=np.float32)
         ids, seg = self.tokenize_pairs(pairs)
         out = np.empty(len(pairs), dtype=np.float32)
-        bs = max(1, int(batch_size))
-        order = sorted(range(len(ids)), key=lambda i: -len(ids[i]))
-        for s in range(0, len(order), bs):
-            idx = order[s:s + bs]
+        for idx in length_sorted_batches([len(s) for s in ids], batch_size):
             out[idx] = self.encoder.score_pair_ids([ids[i] for i in idx], [seg[i] for i in idx])
         if activation == "sigmoid":
             out = (1.0 / (1.0 + np.exp(-out.astype(np.float64)))).astype(np.float32)
         return out
-
-    def rank(self, query: str, documents: Sequence[str], top_k: Optional[int] = None,
-             return_documents: bool = False) -> List[dict]:
-        """``[{"corpus_id", "score"[, "text"]}]`` of ``documents`` against ``query``, best first; ties go to the lower
-        ``corpus_id``."""
-        documents = list(documents)
-        return rank_scores(self.predict([(query, d) for d in documents]), documents, top_k, return_documents)

@@ -120,35 +120,39 @@ struct css_encoder {
     float *tdelta = nullptr;     // BERT: tte[1] - tte[0] [H], added to the type-1 tokens of a pair batch
     std::vector<void*> extra;    // device buffers owned outside `params` (BERT fused QKV, pemb_eff)
     std::vector<LayerW> layers;
-    float* bias_tab = nullptr;  // [heads][2*maxL-1]
-    int* bucket_dev = nullptr;
+    css::DevBuf<float> bias_tab;  // [heads][2*maxL-1]
+    css::DevBuf<int> bucket_dev;
     bool weights_ready = false;
-    // activations (capacity in tokens / sequences)
-    int cap_tokens = 0, cap_seqs = 0, num_cus = 256;
-    float *x32 = nullptr, *pre32 = nullptr;          // [T, H] fp32
-    void *x16 = nullptr, *qkv = nullptr, *ctx = nullptr, *ffn = nullptr;  // operand-typed
-    long long* stats[2] = {nullptr, nullptr};        // [T][2] fixed-point row sums of the two pre tensors (folded-LN path)
+    int num_cus = 256;
+    // Every buffer below is a DevBuf: css_encoder_free deletes the encoder with its device current.  Buffers that grow
+    // together (the ensure_* functions) have no capacity of their own: the capacity is read from the member that is
+    // grown LAST, and that member is dropped FIRST, so a refused allocation leaves the capacity at 0 and the next call
+    // grows the whole group again.
+    // activations: token rows (capacity in tokens: ids_dev.cap) and sequence rows (capacity in rows of H: out_dev.cap)
+    css::DevBuf<float> x32, pre32;                   // [T, H] fp32
+    css::DevBuf<uint8_t> x16, qkv, ctx, ffn;         // operand-typed rows (bf16 or fp32), sized in bytes
+    css::DevBuf<long long> stats[2];                 // [T][2] fixed-point row sums of the two pre tensors (folded-LN path)
     bool x32_valid = true;                           // false after a folded-LN forward (x32 is not materialised there)
     float att_range = 1.2676506e30f;                 // 2^100: row-sum range of the reference-free softmax pass (attn_pass); 0 = always the SAFE pass
-    int32_t *ids_dev = nullptr, *cu_dev = nullptr;
-    float* out_dev = nullptr;
-    // css_encoder_forward_spans: span table [S][3], span rows [S, H], scores [S], query [H].  Grow-only and apart from
-    // the buffers above: no captured graph holds one of these pointers, so growing them leaves the graphs alone.
-    int cap_spans = 0;
-    int32_t* spans_dev = nullptr;
-    float *span_out_dev = nullptr, *span_scores_dev = nullptr, *span_q_dev = nullptr;
+    css::DevBuf<int32_t> ids_dev, cu_dev;
+    css::DevBuf<float> out_dev;
+    // css_encoder_forward_spans: span table [S][3], span rows [S, H], scores [S] (capacity in spans:
+    // span_scores_dev.cap), query [H].  Grow-only and apart from the buffers above: no captured graph holds one of these
+    // pointers, so growing them leaves the graphs alone.
+    css::DevBuf<int32_t> spans_dev;
+    css::DevBuf<float> span_out_dev, span_scores_dev, span_q_dev;
     // css_encoder_set_head / css_encoder_forward_pairs: head weights [H*H + H + H + 1] (Wp, bp, wc, bc), segment starts
-    // [B], logits [B].  Grow-only and apart from the activations, like the span buffers: no graph holds them.
-    float* head_dev = nullptr;
+    // [B], logits [B] (capacity in pairs: logits_dev.cap).  Grow-only and apart from the activations, like the span
+    // buffers: no graph holds them.
+    css::DevBuf<float> head_dev;
     bool head_set = false;
-    int cap_pairs = 0;
-    int32_t* seg_dev = nullptr;
-    float* logits_dev = nullptr;
+    css::DevBuf<int32_t> seg_dev;
+    css::DevBuf<float> logits_dev;
     // css_encoder_set_token_projection / css_encoder_forward_tokens / css_encoder_maxsim: projection [P][H] fp32
     // (tok_p == 0: none, the token vectors are the hidden states), and the host entry points' device copies: token
     // rows, query rows, both offset tables, keep flags, pairs, scores.  Grow-only and apart from the activations, like
     // the span buffers: no graph holds them.
-    float* tokw_dev = nullptr;
+    css::DevBuf<float> tokw_dev;
     int tok_p = 0;
     css::DevBuf<bf16_t> li_tok, li_q;
     css::DevBuf<int32_t> li_cuq, li_cud, li_pairs;
@@ -293,11 +297,12 @@ int build_params(css_encoder* e) {
 #undef AP
     if (bert) return CSS_OK;   // no relative position bias
     const int maxL = c.max_seq_len;
-    CSS_HIP_TRY(hipMalloc((void**)&e->bias_tab, (size_t)c.heads * (2 * maxL - 1) * sizeof(float)));
-    CSS_HIP_TRY(hipMalloc((void**)&e->bucket_dev, (size_t)(2 * maxL - 1) * sizeof(int)));
+    if ((rc = e->bias_tab.grow_exact((size_t)c.heads * (2 * maxL - 1), "hipMalloc(bias table)")) != CSS_OK ||
+        (rc = e->bucket_dev.grow_exact((size_t)(2 * maxL - 1), "hipMalloc(bias table)")) != CSS_OK)
+        return rc;
     std::vector<int> bucket(2 * maxL - 1);
     for (int r = 0; r < 2 * maxL - 1; ++r) bucket[r] = css_mpnet_rel_bucket(r - (maxL - 1), c.rel_buckets, 128);
-    CSS_HIP_TRY(hipMemcpy(e->bucket_dev, bucket.data(), bucket.size() * sizeof(int), hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(e->bucket_dev.p, bucket.data(), bucket.size() * sizeof(int), hipMemcpyHostToDevice));
     return CSS_OK;
 }
 
@@ -334,8 +339,8 @@ int finalize_weights(css_encoder* e) {
         hipLaunchKernelGGL(k_type_delta, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, st, e->tte, e->tdelta, (int)H);
     } else {
         const int n = c.heads * (2 * c.max_seq_len - 1);
-        hipLaunchKernelGGL(k_build_bias_tab, dim3((n + 255) / 256), dim3(256), 0, st, e->relw, e->bucket_dev, c.heads,
-                           c.max_seq_len, c.compute == 0 ? 1.44269504088896341f : 1.0f, e->bias_tab);
+        hipLaunchKernelGGL(k_build_bias_tab, dim3((n + 255) / 256), dim3(256), 0, st, e->relw, e->bucket_dev.p, c.heads,
+                           c.max_seq_len, c.compute == 0 ? 1.44269504088896341f : 1.0f, e->bias_tab.p);
     }
     CSS_LAUNCH_CHECK();
     CSS_HIP_TRY(hipStreamSynchronize(st));
@@ -348,45 +353,41 @@ int ensure_acts(css_encoder* e, int T, int B) {
     const size_t H = c.hidden, F = c.ffn;
     const size_t es = c.compute == 0 ? 2 : 4;
     T = std::max(T, 8 * B);  // pre32 also holds the [B][8][H] pooling partials
-    if (T > e->cap_tokens || B > e->cap_seqs) {
+    const bool more_tokens = (size_t)T > e->ids_dev.cap, more_seqs = (size_t)B * H > e->out_dev.cap;
+    if (more_tokens || more_seqs) {
         for (auto& kv : e->graphs)
             if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
         e->graphs.clear();  // captured pointers are about to change
     }
-    if (T > e->cap_tokens) {
-        void* ptrs[] = {e->x32, e->pre32, e->x16, e->qkv, e->ctx, e->ffn, e->ids_dev, e->stats[0], e->stats[1]};
-        for (void* p : ptrs)
-            if (p) CSS_HIP_TRY(hipFree(p));
-        e->cap_tokens = 0;
+    int rc;
+    if (more_tokens) {
+        CSS_HIP_TRY(e->ids_dev.drop());   // the capacity in tokens (struct css_encoder): 0 until every buffer has grown
         // GEMM tiles store whole 256-row tiles unconditionally: keep >= 256 slack rows
         const size_t cap = ((size_t)T + 255) / 256 * 256 + 256;
-        CSS_HIP_TRY(hipMalloc((void**)&e->x32, cap * H * 4));
-        CSS_HIP_TRY(hipMalloc((void**)&e->pre32, cap * H * 4));
-        // (+ cap * 64 bytes: the padding of the blocked layout the LayerNorm-folded path keeps in x16 / pre32 / ffn)
-        CSS_HIP_TRY(hipMalloc((void**)&e->x16, cap * H * es + cap * 64));
-        CSS_HIP_TRY(hipMalloc((void**)&e->qkv, cap * 3 * H * es));
-        CSS_HIP_TRY(hipMalloc((void**)&e->ctx, cap * H * es));
-        CSS_HIP_TRY(hipMalloc((void**)&e->ffn, cap * F * es + cap * 64));
-        CSS_HIP_TRY(hipMalloc((void**)&e->ids_dev, cap * sizeof(int32_t)));
-        e->stats[0] = e->stats[1] = nullptr;
+        const char* what = "hipMalloc(activations)";
+        // (+ cap * 64 bytes on x16 and ffn: once the padding of the blocked layout of the LayerNorm-folded path.  That
+        // layout has no padding today (preblk_rowstride), so no kernel reads or writes these bytes: they are slack)
+        if ((rc = e->x32.grow_exact(cap * H, what)) != CSS_OK || (rc = e->pre32.grow_exact(cap * H, what)) != CSS_OK ||
+            (rc = e->x16.grow_exact(cap * H * es + cap * 64, what)) != CSS_OK ||
+            (rc = e->qkv.grow_exact(cap * 3 * H * es, what)) != CSS_OK || (rc = e->ctx.grow_exact(cap * H * es, what)) != CSS_OK ||
+            (rc = e->ffn.grow_exact(cap * F * es + cap * 64, what)) != CSS_OK)
+            return rc;
         if (c.compute == 0) {
             for (int i = 0; i < 2; ++i) {
-                CSS_HIP_TRY(hipMalloc((void**)&e->stats[i], cap * 16));
-                CSS_HIP_TRY(hipMemset(e->stats[i], 0, cap * 16));  // slack rows: finite values
+                if ((rc = e->stats[i].grow_exact(cap * 2, what)) != CSS_OK) return rc;
+                CSS_HIP_TRY(hipMemset(e->stats[i].p, 0, cap * 16));  // slack rows: finite values
             }
             // the memsets run on the null stream, forwards on non-blocking streams: order them here, once per growth
             CSS_HIP_TRY(hipDeviceSynchronize());
         }
-        e->cap_tokens = (int)cap;
+        if ((rc = e->ids_dev.grow_exact(cap, what)) != CSS_OK) return rc;
     }
-    if (B > e->cap_seqs) {
-        if (e->cu_dev) CSS_HIP_TRY(hipFree(e->cu_dev));
-        if (e->out_dev) CSS_HIP_TRY(hipFree(e->out_dev));
-        e->cap_seqs = 0;
+    if (more_seqs) {
+        CSS_HIP_TRY(e->out_dev.drop());   // the capacity in sequences, as ids_dev above
         const size_t cap = (size_t)B + 64;
-        CSS_HIP_TRY(hipMalloc((void**)&e->cu_dev, (cap + 1) * sizeof(int32_t)));
-        CSS_HIP_TRY(hipMalloc((void**)&e->out_dev, cap * H * 4));
-        e->cap_seqs = (int)cap;
+        if ((rc = e->cu_dev.grow_exact(cap + 1, "hipMalloc(activations)")) != CSS_OK ||
+            (rc = e->out_dev.grow_exact(cap * H, "hipMalloc(activations)")) != CSS_OK)
+            return rc;
     }
     return CSS_OK;
 }
@@ -395,20 +396,14 @@ int ensure_acts(css_encoder* e, int T, int B) {
 // ends with a synchronise), so the old buffers can be freed at once.
 int ensure_spans(css_encoder* e, int S) {
     const size_t H = e->cfg.hidden;
-    if (!e->span_q_dev) CSS_HIP_TRY(hipMalloc((void**)&e->span_q_dev, H * 4));
-    if (S <= e->cap_spans) return CSS_OK;
-    void* ptrs[] = {e->spans_dev, e->span_out_dev, e->span_scores_dev};
-    for (void* p : ptrs)
-        if (p) CSS_HIP_TRY(hipFree(p));
-    e->spans_dev = nullptr;
-    e->span_out_dev = e->span_scores_dev = nullptr;
-    e->cap_spans = 0;
+    int rc = e->span_q_dev.grow_exact(H, "hipMalloc(spans)");
+    if (rc != CSS_OK || (size_t)S <= e->span_scores_dev.cap) return rc;
+    CSS_HIP_TRY(e->span_scores_dev.drop());   // the capacity in spans, as ids_dev in ensure_acts
     const size_t cap = (size_t)S + (size_t)S / 2 + 64;
-    CSS_HIP_TRY(hipMalloc((void**)&e->spans_dev, cap * 3 * sizeof(int32_t)));
-    CSS_HIP_TRY(hipMalloc((void**)&e->span_out_dev, cap * H * 4));
-    CSS_HIP_TRY(hipMalloc((void**)&e->span_scores_dev, cap * 4));
-    e->cap_spans = (int)cap;
-    return CSS_OK;
+    if ((rc = e->spans_dev.grow_exact(cap * 3, "hipMalloc(spans)")) != CSS_OK ||
+        (rc = e->span_out_dev.grow_exact(cap * H, "hipMalloc(spans)")) != CSS_OK)
+        return rc;
+    return e->span_scores_dev.grow_exact(cap, "hipMalloc(spans)");
 }
 
 // Tile shapes: 2x2 waves x (2x2) MFMA tiles = 128x128, or 2x4 waves x (4x2) tiles = 256x256
@@ -526,7 +521,7 @@ void launch_attention_bf16_t(css_encoder* e, const int32_t* cu, int B, int max_l
     const size_t lds = 4 * 8192 + (BIAS ? (size_t)(2 * maxL - 1 + 64) * 4 : 0);
     const int nqb = (max_len + 127) / 128;
     hipLaunchKernelGGL((k_attention_bf16<HD, BLK, BIAS>), dim3(B * nqb * e->cfg.heads), dim3(256), lds, st,
-                       (const bf16_t*)e->qkv, cu, e->bias_tab, maxL, e->cfg.hidden, (bf16_t*)e->ctx, nqb, e->cfg.heads,
+                       (const bf16_t*)e->qkv.p, cu, e->bias_tab.p, maxL, e->cfg.hidden, (bf16_t*)e->ctx.p, nqb, e->cfg.heads,
                        e->att_range);
 }
 
@@ -548,8 +543,8 @@ int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, 
     {
         ProfScope ps("enc_embed_ln", st);
         hipLaunchKernelGGL(k_embed_ln<H>, dim3((T + 3) / 4), dim3(256), 0, st, ids, cu, B, e->wemb, e->pemb_eff,
-                           e->embg, e->embb, c.ln_eps, c.vocab, c.max_pos, pos_offset(c), e->x32,
-                           BF ? (bf16_t*)e->x16 : nullptr, T, seg, e->tdelta);
+                           e->embg, e->embb, c.ln_eps, c.vocab, c.max_pos, pos_offset(c), e->x32.p,
+                           BF ? (bf16_t*)e->x16.p : nullptr, T, seg, e->tdelta);
         CSS_LAUNCH_CHECK();
     }
     const int maxL = c.max_seq_len;
@@ -557,61 +552,61 @@ int forward_typed(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, 
     // (the residual is the row the next GEMM reads anyway).
     // attention-output / FFN2 projection into `pre32` (fp32, or bf16 rows in bf16 mode)
     auto launch_branch_out = [&](const void* a, const void* w, const float* bias, int K, const char* prof) -> int {
-        if constexpr (BF) return launch_gemm<TIn, EPI_QKV>(a, w, bias, e->pre32, T, H, K, 0, 1.0f, e->num_cus, st, prof);
-        else return launch_gemm<TIn, EPI_RESID>(a, w, bias, e->pre32, T, H, K, 0, 1.0f, e->num_cus, st, prof);
+        if constexpr (BF) return launch_gemm<TIn, EPI_QKV>(a, w, bias, e->pre32.p, T, H, K, 0, 1.0f, e->num_cus, st, prof);
+        else return launch_gemm<TIn, EPI_RESID>(a, w, bias, e->pre32.p, T, H, K, 0, 1.0f, e->num_cus, st, prof);
     };
     // x = LN(pre + x); `last`: the fp32 row is needed by the pooling
     auto launch_ln = [&](const float* g, const float* b, bool last) -> int {
         ProfScope ps("enc_layernorm", st);
         const dim3 grid((T + 3) / 4), blk(256);
         if constexpr (BF)
-            hipLaunchKernelGGL((k_layernorm<H, bf16_t, bf16_t>), grid, blk, 0, st, (const bf16_t*)e->pre32, (const bf16_t*)e->x16, g, b,
-                               c.ln_eps, last ? e->x32 : (float*)nullptr, (bf16_t*)e->x16, T);
+            hipLaunchKernelGGL((k_layernorm<H, bf16_t, bf16_t>), grid, blk, 0, st, (const bf16_t*)e->pre32.p, (const bf16_t*)e->x16.p, g, b,
+                               c.ln_eps, last ? e->x32.p : (float*)nullptr, (bf16_t*)e->x16.p, T);
         else
-            hipLaunchKernelGGL((k_layernorm<H, float, float>), grid, blk, 0, st, (const float*)e->pre32, (const float*)e->x32, g, b,
-                               c.ln_eps, e->x32, (bf16_t*)nullptr, T);
+            hipLaunchKernelGGL((k_layernorm<H, float, float>), grid, blk, 0, st, (const float*)e->pre32.p, (const float*)e->x32.p, g, b,
+                               c.ln_eps, e->x32.p, (bf16_t*)nullptr, T);
         CSS_LAUNCH_CHECK();
         return CSS_OK;
     };
     for (int li = 0; li < c.num_layers; ++li) {
         const LayerW& L = e->layers[li];
-        const void* xin = BF ? e->x16 : (const void*)e->x32;
+        const void* xin = BF ? e->x16.p : (const void*)e->x32.p;
         const void* wqkv = BF ? (const void*)L.wqkv_h : (const void*)L.wqkv;
-        if ((rc = launch_gemm<TIn, EPI_QKV>(xin, wqkv, L.bqkv, e->qkv, T, 3 * H, H, H, qk_scale(c, BF), e->num_cus, st, "enc_gemm_qkv")) != CSS_OK)
+        if ((rc = launch_gemm<TIn, EPI_QKV>(xin, wqkv, L.bqkv, e->qkv.p, T, 3 * H, H, H, qk_scale(c, BF), e->num_cus, st, "enc_gemm_qkv")) != CSS_OK)
             return rc;
         {
             ProfScope ps("enc_attention", st);
             if constexpr (BF) {
                 launch_attention_bf16<false>(e, cu, B, max_len, st);
             } else if (H / c.heads == 64) {
-                hipLaunchKernelGGL(k_attention_f32<64>, dim3(B, max_len, c.heads), dim3(64), 0, st, (const float*)e->qkv, cu,
-                                   e->bias_tab, maxL, H, (float*)e->ctx);
+                hipLaunchKernelGGL(k_attention_f32<64>, dim3(B, max_len, c.heads), dim3(64), 0, st, (const float*)e->qkv.p, cu,
+                                   e->bias_tab.p, maxL, H, (float*)e->ctx.p);
             } else {
-                hipLaunchKernelGGL(k_attention_f32<32>, dim3(B, max_len, c.heads), dim3(64), 0, st, (const float*)e->qkv, cu,
-                                   e->bias_tab, maxL, H, (float*)e->ctx);
+                hipLaunchKernelGGL(k_attention_f32<32>, dim3(B, max_len, c.heads), dim3(64), 0, st, (const float*)e->qkv.p, cu,
+                                   e->bias_tab.p, maxL, H, (float*)e->ctx.p);
             }
             CSS_LAUNCH_CHECK();
         }
         const void* wo = BF ? (const void*)L.wo_h : (const void*)L.wo;
-        if ((rc = launch_branch_out(e->ctx, wo, L.bo, H, "enc_gemm_o")) != CSS_OK) return rc;
+        if ((rc = launch_branch_out(e->ctx.p, wo, L.bo, H, "enc_gemm_o")) != CSS_OK) return rc;
         if ((rc = launch_ln(L.ln1g, L.ln1b, false)) != CSS_OK) return rc;
-        xin = BF ? e->x16 : (const void*)e->x32;
+        xin = BF ? e->x16.p : (const void*)e->x32.p;
         const void* w1 = BF ? (const void*)L.w1_h : (const void*)L.w1;
-        if ((rc = launch_gemm<TIn, EPI_GELU>(xin, w1, L.b1, e->ffn, T, F, H, 0, 1.0f, e->num_cus, st, "enc_gemm_ffn1")) != CSS_OK)
+        if ((rc = launch_gemm<TIn, EPI_GELU>(xin, w1, L.b1, e->ffn.p, T, F, H, 0, 1.0f, e->num_cus, st, "enc_gemm_ffn1")) != CSS_OK)
             return rc;
         const void* w2 = BF ? (const void*)L.w2_h : (const void*)L.w2;
-        if ((rc = launch_branch_out(e->ffn, w2, L.b2, F, "enc_gemm_ffn2")) != CSS_OK) return rc;
+        if ((rc = launch_branch_out(e->ffn.p, w2, L.b2, F, "enc_gemm_ffn2")) != CSS_OK) return rc;
         if ((rc = launch_ln(L.ln2g, L.ln2b, li == c.num_layers - 1)) != CSS_OK) return rc;
     }
     {
         ProfScope ps("enc_pool", st);
         constexpr int kPoolSlices = 8;
         if (pooling == CSS_ENCODER_POOL_CLS) {
-            hipLaunchKernelGGL(k_pool_cls<H>, dim3(B), dim3(256), 0, st, e->x32, cu, normalize, out);
+            hipLaunchKernelGGL(k_pool_cls<H>, dim3(B), dim3(256), 0, st, e->x32.p, cu, normalize, out);
         } else {
             // partial sums live in pre32 (free after the last LayerNorm): [B][8][H] floats
-            hipLaunchKernelGGL(k_pool_partial<H>, dim3(B, kPoolSlices), dim3(256), 0, st, e->x32, cu, kPoolSlices, e->pre32);
-            hipLaunchKernelGGL(k_pool_final<H>, dim3(B), dim3(256), 0, st, e->pre32, cu, kPoolSlices, normalize, out);
+            hipLaunchKernelGGL(k_pool_partial<H>, dim3(B, kPoolSlices), dim3(256), 0, st, e->x32.p, cu, kPoolSlices, e->pre32.p);
+            hipLaunchKernelGGL(k_pool_final<H>, dim3(B), dim3(256), 0, st, e->pre32.p, cu, kPoolSlices, normalize, out);
         }
         CSS_LAUNCH_CHECK();
     }
@@ -626,11 +621,11 @@ int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, i
     const css_encoder_cfg& c = e->cfg;
     const int H = c.hidden, F = c.ffn;
     int rc;
-    bf16_t* pre[2] = {(bf16_t*)e->x16, (bf16_t*)e->pre32};
+    bf16_t* pre[2] = {(bf16_t*)e->x16.p, (bf16_t*)e->pre32.p};
     {
         ProfScope ps("enc_embed_ln", st);
         hipLaunchKernelGGL(k_embed_pre<768>, dim3((T + 15) / 16), dim3(256), 0, st, ids, cu, B, e->wemb, e->pemb_eff, c.vocab,
-                           c.max_pos, pos_offset(c), pre[0], e->stats[0], T, kStatScale1, kStatScale2, seg, e->tdelta);
+                           c.max_pos, pos_offset(c), pre[0], e->stats[0].p, T, kStatScale1, kStatScale2, seg, e->tdelta);
         CSS_LAUNCH_CHECK();
     }
     const float *g_in = e->embg, *b_in = e->embb;  // the LayerNorm that turns pre[0] into the layer input
@@ -640,9 +635,9 @@ int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, i
     for (int li = 0; li < c.num_layers; ++li) {
         const LayerW& L = e->layers[li];
         // x = LN(pre[0]) -> qkv; zeroes stats[1]
-        side.stats_in = e->stats[0];
-        side.stats_out = e->stats[1];
-        if ((rc = launch_gemm8p<EPI_AFF_QKV, true>(pre[0], L.wqkv_f, L.dqkv, e->qkv, T, 3 * H, H, H, qk_scale(c, true),
+        side.stats_in = e->stats[0].p;
+        side.stats_out = e->stats[1].p;
+        if ((rc = launch_gemm8p<EPI_AFF_QKV, true>(pre[0], L.wqkv_f, L.dqkv, e->qkv.p, T, 3 * H, H, H, qk_scale(c, true),
                                                    side, e->num_cus, st, "enc_gemm_qkv")) != CSS_OK)
             return rc;
         {
@@ -653,17 +648,17 @@ int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, i
         // pre[1] = ctx Wo^T + (bo + beta) + gamma (pre[0] - mu) rs; stats[1] += row sums
         side.pprev = pre[0];
         side.cvec = g_in;
-        if ((rc = launch_gemm8p<EPI_RES, true, 1>(e->ctx, L.wo_p, L.bo_f, pre[1], T, H, H, 0, 1.0f, side, e->num_cus, st, "enc_gemm_o")) != CSS_OK)
+        if ((rc = launch_gemm8p<EPI_RES, true, 1>(e->ctx.p, L.wo_p, L.bo_f, pre[1], T, H, H, 0, 1.0f, side, e->num_cus, st, "enc_gemm_o")) != CSS_OK)
             return rc;
         // x1 = LN1(pre[1]) -> ffn = gelu(x1 W1^T + b1); zeroes stats[0]
-        side.stats_in = e->stats[1];
-        side.stats_out = e->stats[0];
-        if ((rc = launch_gemm8p<EPI_AFF_GELU, true>(pre[1], L.w1_f, L.d1, e->ffn, T, F, H, 0, 1.0f, side, e->num_cus, st, "enc_gemm_ffn1")) != CSS_OK)
+        side.stats_in = e->stats[1].p;
+        side.stats_out = e->stats[0].p;
+        if ((rc = launch_gemm8p<EPI_AFF_GELU, true>(pre[1], L.w1_f, L.d1, e->ffn.p, T, F, H, 0, 1.0f, side, e->num_cus, st, "enc_gemm_ffn1")) != CSS_OK)
             return rc;
         // pre[0] = ffn W2^T + (b2 + beta1) + gamma1 (pre[1] - mu) rs; stats[0] += row sums
         side.pprev = pre[1];
         side.cvec = L.ln1g;
-        if ((rc = launch_gemm8p<EPI_RES, true>(e->ffn, L.w2_p, L.b2_f, pre[0], T, H, F, 0, 1.0f, side, e->num_cus, st, "enc_gemm_ffn2")) != CSS_OK)
+        if ((rc = launch_gemm8p<EPI_RES, true>(e->ffn.p, L.w2_p, L.b2_f, pre[0], T, H, F, 0, 1.0f, side, e->num_cus, st, "enc_gemm_ffn2")) != CSS_OK)
             return rc;
         g_in = L.ln2g;
         b_in = L.ln2b;
@@ -672,12 +667,12 @@ int forward_folded_bf16(css_encoder* e, const int32_t* ids, const int32_t* cu, i
         ProfScope ps("enc_pool", st);
         constexpr int kPoolSlices = 8;
         // partial sums live in ffn (free after the last FFN2; capacity >= 8 B rows of 8 H bytes): [B][8][H] floats
-        float* part = (float*)e->ffn;
+        float* part = (float*)e->ffn.p;
         if (pooling == CSS_ENCODER_POOL_CLS) {
-            hipLaunchKernelGGL(k_pool_cls_ln<768>, dim3(B), dim3(256), 0, st, (const bf16_t*)pre[0], e->stats[0], g_in, b_in,
+            hipLaunchKernelGGL(k_pool_cls_ln<768>, dim3(B), dim3(256), 0, st, (const bf16_t*)pre[0], e->stats[0].p, g_in, b_in,
                                1.0f / H, c.ln_eps, cu, normalize, out);
         } else {
-            hipLaunchKernelGGL(k_pool_partial_ln<768>, dim3(B, kPoolSlices), dim3(256), 0, st, (const bf16_t*)pre[0], e->stats[0],
+            hipLaunchKernelGGL(k_pool_partial_ln<768>, dim3(B, kPoolSlices), dim3(256), 0, st, (const bf16_t*)pre[0], e->stats[0].p,
                                g_in, b_in, 1.0f / H, c.ln_eps, cu, kPoolSlices, part);
             hipLaunchKernelGGL(k_pool_final<768>, dim3(B), dim3(256), 0, st, part, cu, kPoolSlices, normalize, out);
         }
@@ -722,30 +717,32 @@ int pool_spans(css_encoder* e, const int32_t* cu, int B, const int32_t* spans, i
     ProfScope ps("enc_span_pool", st);
     if (!e->x32_valid) {
         const LayerW& L = e->layers.back();
-        hipLaunchKernelGGL(k_span_pool_ln<768>, dim3(S), dim3(256), 0, st, (const bf16_t*)e->x16, e->stats[0], L.ln2g, L.ln2b,
+        hipLaunchKernelGGL(k_span_pool_ln<768>, dim3(S), dim3(256), 0, st, (const bf16_t*)e->x16.p, e->stats[0].p, L.ln2g, L.ln2b,
                            1.0f / c.hidden, c.ln_eps, cu, B, spans, normalize, q, span_out, scores);
     } else if (c.hidden == 384) {
-        hipLaunchKernelGGL(k_span_pool<384>, dim3(S), dim3(256), 0, st, e->x32, cu, B, spans, normalize, q, span_out, scores);
+        hipLaunchKernelGGL(k_span_pool<384>, dim3(S), dim3(256), 0, st, e->x32.p, cu, B, spans, normalize, q, span_out, scores);
     } else {
-        hipLaunchKernelGGL(k_span_pool<768>, dim3(S), dim3(256), 0, st, e->x32, cu, B, spans, normalize, q, span_out, scores);
+        hipLaunchKernelGGL(k_span_pool<768>, dim3(S), dim3(256), 0, st, e->x32.p, cu, B, spans, normalize, q, span_out, scores);
     }
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 
+// The span forward on `st`: forward, then one pooled row per span.  seq_out NULL: the sequence rows go to the encoder's
+// own buffer (out_dev).
+int forward_spans_any(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int T, int max_len, const int32_t* spans,
+                      int S, const float* q, int normalize, float* seq_out, float* span_out, float* scores, hipStream_t st) {
+    const int rc = forward_any(e, ids, cu, B, T, max_len, normalize, seq_out ? seq_out : e->out_dev.p, st);
+    return rc != CSS_OK ? rc : pool_spans(e, cu, B, spans, S, q, normalize, span_out, scores, st);
+}
+
 // Buffers of css_encoder_forward_pairs (host entry point); the stream is idle between calls, as for ensure_spans.
 int ensure_pairs(css_encoder* e, int B) {
-    if (B <= e->cap_pairs) return CSS_OK;
-    if (e->seg_dev) CSS_HIP_TRY(hipFree(e->seg_dev));
-    if (e->logits_dev) CSS_HIP_TRY(hipFree(e->logits_dev));
-    e->seg_dev = nullptr;
-    e->logits_dev = nullptr;
-    e->cap_pairs = 0;
+    if ((size_t)B <= e->logits_dev.cap) return CSS_OK;
+    CSS_HIP_TRY(e->logits_dev.drop());   // the capacity in pairs, as ids_dev in ensure_acts
     const size_t cap = (size_t)B + (size_t)B / 2 + 64;
-    CSS_HIP_TRY(hipMalloc((void**)&e->seg_dev, cap * sizeof(int32_t)));
-    CSS_HIP_TRY(hipMalloc((void**)&e->logits_dev, cap * 4));
-    e->cap_pairs = (int)cap;
-    return CSS_OK;
+    const int rc = e->seg_dev.grow_exact(cap, "hipMalloc(pairs)");
+    return rc != CSS_OK ? rc : e->logits_dev.grow_exact(cap, "hipMalloc(pairs)");
 }
 
 // What a pair forward needs of the encoder: BERT, weights and a head.
@@ -763,18 +760,18 @@ int check_pairs_state(const css_encoder* e, const char* fn) {
 // (k_ce_head: partial logits per slab of pooler rows; k_ce_head_sum: their sum + bc).
 int forward_pairs_any(css_encoder* e, const int32_t* ids, const int32_t* cu, const int32_t* seg, int B, int T, int max_len,
                       float* logits, hipStream_t st) {
-    int rc = forward_any(e, ids, cu, B, T, max_len, 0, e->out_dev, st, seg, CSS_ENCODER_POOL_CLS);
+    int rc = forward_any(e, ids, cu, B, T, max_len, 0, e->out_dev.p, st, seg, CSS_ENCODER_POOL_CLS);
     if (rc != CSS_OK) return rc;
     const size_t H = e->cfg.hidden;
-    const float *wp = e->head_dev, *bp = wp + H * H, *wc = bp + H, *bc = wc + H;
+    const float *wp = e->head_dev.p, *bp = wp + H * H, *wc = bp + H, *bc = wc + H;
     // partials [tiles][H / kCeSlab][kCeTile] live in pre32 (free after the last LayerNorm / the last FFN2 GEMM;
     // capacity >= 8 B rows of H floats, ensure_acts)
-    float* part = e->pre32;
+    float* part = e->pre32.p;
     ProfScope ps("enc_ce_head", st);
     const int nslab = (int)H / kCeSlab;
     const dim3 grid((B + kCeTile - 1) / kCeTile, nslab), blk(256);
-    if (H == 384) hipLaunchKernelGGL(k_ce_head<384>, grid, blk, 0, st, e->out_dev, wp, bp, wc, B, part);
-    else hipLaunchKernelGGL(k_ce_head<768>, grid, blk, 0, st, e->out_dev, wp, bp, wc, B, part);
+    if (H == 384) hipLaunchKernelGGL(k_ce_head<384>, grid, blk, 0, st, e->out_dev.p, wp, bp, wc, B, part);
+    else hipLaunchKernelGGL(k_ce_head<768>, grid, blk, 0, st, e->out_dev.p, wp, bp, wc, B, part);
     hipLaunchKernelGGL(k_ce_head_sum, dim3((B + 255) / 256), dim3(256), 0, st, part, bc, B, nslab, logits);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
@@ -799,6 +796,18 @@ int check_batch(const css_encoder* e, const int32_t* ids, const int32_t* cu, int
     return CSS_OK;
 }
 
+// Stages a checked host batch for a forward on the encoder's own stream: room for cu[B] tokens and B sequences, then
+// ids and cu into ids_dev / cu_dev.  Called with the lock held and the device current.  What follows a staged batch is
+// eager launches: the tiny-batch graphs replay css_encoder_forward only.
+int stage_batch(css_encoder* e, const int32_t* ids, const int32_t* cu, int B) {
+    const int T = cu[B];
+    const int rc = ensure_acts(e, T, B);
+    if (rc != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev.p, ids, (size_t)T * 4, hipMemcpyHostToDevice, e->stream));
+    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev.p, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    return CSS_OK;
+}
+
 // Width of a token vector: the projection's P, or the hidden size without one.
 int token_dim(const css_encoder* e) { return e->tok_p ? e->tok_p : e->cfg.hidden; }
 
@@ -807,20 +816,28 @@ int token_dim(const css_encoder* e) { return e->tok_p ? e->tok_p : e->cfg.hidden
 int write_tokens(css_encoder* e, int T, int normalize, bf16_t* tok_out, hipStream_t st) {
     const css_encoder_cfg& c = e->cfg;
     const int P = token_dim(e);
-    const float* W = e->tok_p ? e->tokw_dev : nullptr;
+    const float* W = e->tok_p ? e->tokw_dev.p : nullptr;
     ProfScope ps("enc_tok_vec", st);
     const dim3 grid((T + 15) / 16), blk(256);
     if (!e->x32_valid) {
         const LayerW& L = e->layers.back();
-        hipLaunchKernelGGL(k_tok_vec_ln<768>, grid, blk, 0, st, (const bf16_t*)e->x16, e->stats[0], L.ln2g, L.ln2b,
+        hipLaunchKernelGGL(k_tok_vec_ln<768>, grid, blk, 0, st, (const bf16_t*)e->x16.p, e->stats[0].p, L.ln2g, L.ln2b,
                            1.0f / c.hidden, c.ln_eps, T, W, P, normalize, tok_out);
     } else if (c.hidden == 384) {
-        hipLaunchKernelGGL(k_tok_vec<384>, grid, blk, 0, st, e->x32, T, W, P, normalize, tok_out);
+        hipLaunchKernelGGL(k_tok_vec<384>, grid, blk, 0, st, e->x32.p, T, W, P, normalize, tok_out);
     } else {
-        hipLaunchKernelGGL(k_tok_vec<768>, grid, blk, 0, st, e->x32, T, W, P, normalize, tok_out);
+        hipLaunchKernelGGL(k_tok_vec<768>, grid, blk, 0, st, e->x32.p, T, W, P, normalize, tok_out);
     }
     CSS_LAUNCH_CHECK();
     return CSS_OK;
+}
+
+// The token forward on `st`: forward, then one bf16 row per token into tok_out.  seq_out NULL: the sequence rows go to
+// the encoder's own buffer (out_dev).
+int forward_tokens_any(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int T, int max_len, int normalize,
+                       bf16_t* tok_out, float* seq_out, hipStream_t st) {
+    const int rc = forward_any(e, ids, cu, B, T, max_len, normalize, seq_out ? seq_out : e->out_dev.p, st);
+    return rc != CSS_OK ? rc : write_tokens(e, T, normalize, tok_out, st);
 }
 
 bool maxsim_width_ok(int P) { return (P % 32 == 0 && P >= 32 && P <= 128) || P == 384 || P == 768; }
@@ -863,6 +880,14 @@ int launch_maxsim(css_encoder* e, const bf16_t* q, const int32_t* cuq, int nq, c
     }
     css::set_error("css_encoder_maxsim: P=%d must be a multiple of 32 in [32, 128], or 384, or 768", P);
     return CSS_ERR_INVALID;
+}
+
+// Forward plus MaxSim on `st`: unit token rows of the batch into `tok`, then the scores of (query, sequence) pairs.
+int forward_maxsim_any(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int T, int max_len, const bf16_t* q,
+                       const int32_t* cuq, int nq, const uint8_t* keep, const int32_t* pairs, int np, float* scores,
+                       bf16_t* tok, hipStream_t st) {
+    const int rc = forward_tokens_any(e, ids, cu, B, T, max_len, 1, tok, nullptr, st);
+    return rc != CSS_OK ? rc : launch_maxsim(e, q, cuq, nq, tok, cu, B, keep, pairs, np, token_dim(e), scores, st);
 }
 
 // Host tables of a MaxSim call, checked before anything is enqueued: every query has 1..64 tokens, every doc at least
@@ -932,23 +957,23 @@ int mlm_rows(css_encoder* e, int T, float* g32, bf16_t* g16, hipStream_t st) {
         const LayerW& L = e->layers.back();
         {
             ProfScope ps("enc_mlm_rows", st);
-            hipLaunchKernelGGL(k_tok_vec_ln<768>, dim3((T + 15) / 16), blk, 0, st, (const bf16_t*)e->x16, e->stats[0], L.ln2g,
-                               L.ln2b, 1.0f / H, c.ln_eps, T, (const float*)nullptr, H, 0, (bf16_t*)e->ctx);
+            hipLaunchKernelGGL(k_tok_vec_ln<768>, dim3((T + 15) / 16), blk, 0, st, (const bf16_t*)e->x16.p, e->stats[0].p, L.ln2g,
+                               L.ln2b, 1.0f / H, c.ln_eps, T, (const float*)nullptr, H, 0, (bf16_t*)e->ctx.p);
             CSS_LAUNCH_CHECK();
         }
-        if ((rc = launch_gemm<bf16_t, EPI_GELU>(e->ctx, e->mlm_wd16.p, bd, e->qkv, T, H, H, 0, 1.0f, e->num_cus, st,
+        if ((rc = launch_gemm<bf16_t, EPI_GELU>(e->ctx.p, e->mlm_wd16.p, bd, e->qkv.p, T, H, H, 0, 1.0f, e->num_cus, st,
                                                 "enc_mlm_dense")) != CSS_OK)
             return rc;
         ProfScope ps("enc_mlm_ln", st);
-        hipLaunchKernelGGL((k_mlm_ln<768, bf16_t>), grid, blk, 0, st, (const bf16_t*)e->qkv, lg, lb, c.ln_eps, g32, g16, T);
+        hipLaunchKernelGGL((k_mlm_ln<768, bf16_t>), grid, blk, 0, st, (const bf16_t*)e->qkv.p, lg, lb, c.ln_eps, g32, g16, T);
         CSS_LAUNCH_CHECK();
         return CSS_OK;
     }
-    if ((rc = launch_gemm<float, EPI_GELU>(e->x32, W, bd, e->qkv, T, H, H, 0, 1.0f, e->num_cus, st, "enc_mlm_dense")) != CSS_OK)
+    if ((rc = launch_gemm<float, EPI_GELU>(e->x32.p, W, bd, e->qkv.p, T, H, H, 0, 1.0f, e->num_cus, st, "enc_mlm_dense")) != CSS_OK)
         return rc;
     ProfScope ps("enc_mlm_ln", st);
-    if (H == 384) hipLaunchKernelGGL((k_mlm_ln<384, float>), grid, blk, 0, st, (const float*)e->qkv, lg, lb, c.ln_eps, g32, g16, T);
-    else hipLaunchKernelGGL((k_mlm_ln<768, float>), grid, blk, 0, st, (const float*)e->qkv, lg, lb, c.ln_eps, g32, g16, T);
+    if (H == 384) hipLaunchKernelGGL((k_mlm_ln<384, float>), grid, blk, 0, st, (const float*)e->qkv.p, lg, lb, c.ln_eps, g32, g16, T);
+    else hipLaunchKernelGGL((k_mlm_ln<768, float>), grid, blk, 0, st, (const float*)e->qkv.p, lg, lb, c.ln_eps, g32, g16, T);
     CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
@@ -970,15 +995,28 @@ int launch_vocab_max(css_encoder* e, const void* rows, const int32_t* cu, int B,
     return CSS_OK;
 }
 
+// zmax of fp32 token rows on `st`.  In bf16 mode the rows are rounded once into sp_g16 first, a buffer of the encoder's
+// that only grows; growing frees the old one, so work that an earlier call enqueued on another stream must have
+// finished, as for the activations.
+int vocab_max_any(css_encoder* e, const float* rows, const int32_t* cu, int B, int T, unsigned* zmax, hipStream_t st) {
+    if (e->cfg.compute != 0) return launch_vocab_max(e, rows, cu, B, T, zmax, st);
+    const size_t n = (size_t)T * e->cfg.hidden;
+    const int rc = e->sp_g16.grow(n);
+    if (rc != CSS_OK) return rc;
+    hipLaunchKernelGGL(k_f32_to_bf16, dim3(1024), dim3(256), 0, st, rows, e->sp_g16.p, n);
+    CSS_LAUNCH_CHECK();
+    return launch_vocab_max(e, e->sp_g16.p, cu, B, T, zmax, st);
+}
+
 // Forward, head, vocabulary maximum and top-m on `st`.  g32: where the fp32 rows g go (the caller's rows_out, or
 // pre32, which is free after the forward); zmax: the caller's dense_out or sp_z.
 int forward_sparse_any(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int T, int max_len, int m, int32_t* terms,
                        float* weights, int32_t* nnz, unsigned* zmax, float* g32, hipStream_t st) {
-    int rc = forward_any(e, ids, cu, B, T, max_len, 0, e->out_dev, st);
+    int rc = forward_any(e, ids, cu, B, T, max_len, 0, e->out_dev.p, st);
     if (rc != CSS_OK) return rc;
     const bool bf = e->cfg.compute == 0;
-    if ((rc = mlm_rows(e, T, g32, bf ? (bf16_t*)e->ctx : nullptr, st)) != CSS_OK) return rc;
-    if ((rc = launch_vocab_max(e, bf ? (const void*)e->ctx : (const void*)g32, cu, B, T, zmax, st)) != CSS_OK) return rc;
+    if ((rc = mlm_rows(e, T, g32, bf ? (bf16_t*)e->ctx.p : nullptr, st)) != CSS_OK) return rc;
+    if ((rc = launch_vocab_max(e, bf ? (const void*)e->ctx.p : (const void*)g32, cu, B, T, zmax, st)) != CSS_OK) return rc;
     ProfScope ps("enc_vocab_topm", st);
     hipLaunchKernelGGL(k_vocab_topm, dim3(B), dim3(256), 0, st, (const unsigned*)zmax, e->cfg.vocab, m, terms, weights, nnz);
     CSS_LAUNCH_CHECK();
@@ -1058,13 +1096,8 @@ int css_encoder_free(css_encoder* e) {
         for (void* p : fp)
             if (p) (void)hipFree(p);
     }
-    void* ptrs[] = {e->bias_tab, e->bucket_dev, e->x32, e->pre32, e->x16, e->qkv, e->ctx, e->ffn, e->ids_dev,
-                    e->cu_dev, e->out_dev, e->stats[0], e->stats[1], e->spans_dev, e->span_out_dev, e->span_scores_dev,
-                    e->span_q_dev, e->head_dev, e->seg_dev, e->logits_dev, e->tokw_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    delete e;   // (frees every DevBuf member: the device is current)
     return CSS_OK;
 }
 
@@ -1170,13 +1203,13 @@ int css_encoder_debug_read(css_encoder* e, const char* what, float* out_host, in
     if (w == "x32") {
         CSS_REQUIRE(e->x32_valid, "css_encoder_debug_read: the last forward ran the LayerNorm-folded path, which does not "
                                   "materialise x32");
-        src = e->x32;
+        src = e->x32.p;
         typed = false;
     }
-    else if (w == "pre32") { src = e->pre32; typed = false; }
-    else if (w == "qkv") src = e->qkv;
-    else if (w == "ctx") src = e->ctx;
-    else if (w == "ffn") src = e->ffn;
+    else if (w == "pre32") { src = e->pre32.p; typed = false; }
+    else if (w == "qkv") src = e->qkv.p;
+    else if (w == "ctx") src = e->ctx.p;
+    else if (w == "ffn") src = e->ffn.p;
     CSS_REQUIRE(src != nullptr, "css_encoder_debug_read: unknown or unallocated buffer '%s'", what);
     CSS_HIP_TRY(hipDeviceSynchronize());
     if (typed && bf) {
@@ -1200,10 +1233,7 @@ int css_encoder_forward(css_encoder* e, const int32_t* ids, const int32_t* cu, i
     const int T = cu[B];
     std::lock_guard<std::mutex> lk(e->mu);
     DeviceGuard g(e->device);
-    rc = ensure_acts(e, T, B);
-    if (rc != CSS_OK) return rc;
-    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, e->stream));
-    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    if ((rc = stage_batch(e, ids, cu, B)) != CSS_OK) return rc;
     bool done = false;
     if (e->graphs_ok && T <= 64 && B <= 8 && !css::prof_enabled()) {
         // ~90 launches of a few microseconds each: replay them as one hipGraph
@@ -1213,7 +1243,7 @@ int css_encoder_forward(css_encoder* e, const int32_t* ids, const int32_t* cu, i
         if (ge.exec == nullptr && ge.uses == 2) {
             hipGraph_t graph = nullptr;
             if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int frc = forward_any(e, e->ids_dev, e->cu_dev, B, T, max_len, normalize, e->out_dev, e->stream);
+                const int frc = forward_any(e, e->ids_dev.p, e->cu_dev.p, B, T, max_len, normalize, e->out_dev.p, e->stream);
                 const hipError_t ce = hipStreamEndCapture(e->stream, &graph);
                 if (frc == CSS_OK && ce == hipSuccess && graph &&
                     hipGraphInstantiate(&ge.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
@@ -1234,9 +1264,9 @@ int css_encoder_forward(css_encoder* e, const int32_t* ids, const int32_t* cu, i
             done = true;
         }
     }
-    if (!done && (rc = forward_any(e, e->ids_dev, e->cu_dev, B, T, max_len, normalize, e->out_dev, e->stream)) != CSS_OK)
+    if (!done && (rc = forward_any(e, e->ids_dev.p, e->cu_dev.p, B, T, max_len, normalize, e->out_dev.p, e->stream)) != CSS_OK)
         return rc;
-    CSS_HIP_TRY(hipMemcpyAsync(out, e->out_dev, (size_t)B * e->cfg.hidden * 4, hipMemcpyDeviceToHost, e->stream));
+    CSS_HIP_TRY(hipMemcpyAsync(out, e->out_dev.p, (size_t)B * e->cfg.hidden * 4, hipMemcpyDeviceToHost, e->stream));
     CSS_HIP_TRY(hipStreamSynchronize(e->stream));
     return CSS_OK;
 }
@@ -1270,20 +1300,17 @@ int css_encoder_forward_spans(css_encoder* e, const int32_t* ids, const int32_t*
     const size_t H = e->cfg.hidden;
     std::lock_guard<std::mutex> lk(e->mu);
     DeviceGuard g(e->device);
-    if ((rc = ensure_acts(e, T, B)) != CSS_OK || (rc = ensure_spans(e, S)) != CSS_OK) return rc;
+    if ((rc = stage_batch(e, ids, cu, B)) != CSS_OK || (rc = ensure_spans(e, S)) != CSS_OK) return rc;
     hipStream_t st = e->stream;
-    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
-    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-    if (S) CSS_HIP_TRY(hipMemcpyAsync(e->spans_dev, spans, (size_t)S * 12, hipMemcpyHostToDevice, st));
-    if (q) CSS_HIP_TRY(hipMemcpyAsync(e->span_q_dev, q, H * 4, hipMemcpyHostToDevice, st));
-    // eager launches (the tiny-batch graphs replay css_encoder_forward only)
-    if ((rc = forward_any(e, e->ids_dev, e->cu_dev, B, T, max_len, normalize, e->out_dev, st)) != CSS_OK) return rc;
-    if ((rc = pool_spans(e, e->cu_dev, B, e->spans_dev, S, q ? e->span_q_dev : nullptr, normalize,
-                         span_out ? e->span_out_dev : nullptr, scores_out ? e->span_scores_dev : nullptr, st)) != CSS_OK)
+    if (S) CSS_HIP_TRY(hipMemcpyAsync(e->spans_dev.p, spans, (size_t)S * 12, hipMemcpyHostToDevice, st));
+    if (q) CSS_HIP_TRY(hipMemcpyAsync(e->span_q_dev.p, q, H * 4, hipMemcpyHostToDevice, st));
+    if ((rc = forward_spans_any(e, e->ids_dev.p, e->cu_dev.p, B, T, max_len, e->spans_dev.p, S, q ? e->span_q_dev.p : nullptr,
+                                normalize, nullptr, span_out ? e->span_out_dev.p : nullptr,
+                                scores_out ? e->span_scores_dev.p : nullptr, st)) != CSS_OK)
         return rc;
-    if (seq_out) CSS_HIP_TRY(hipMemcpyAsync(seq_out, e->out_dev, (size_t)B * H * 4, hipMemcpyDeviceToHost, st));
-    if (span_out && S) CSS_HIP_TRY(hipMemcpyAsync(span_out, e->span_out_dev, (size_t)S * H * 4, hipMemcpyDeviceToHost, st));
-    if (scores_out && S) CSS_HIP_TRY(hipMemcpyAsync(scores_out, e->span_scores_dev, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    if (seq_out) CSS_HIP_TRY(hipMemcpyAsync(seq_out, e->out_dev.p, (size_t)B * H * 4, hipMemcpyDeviceToHost, st));
+    if (span_out && S) CSS_HIP_TRY(hipMemcpyAsync(span_out, e->span_out_dev.p, (size_t)S * H * 4, hipMemcpyDeviceToHost, st));
+    if (scores_out && S) CSS_HIP_TRY(hipMemcpyAsync(scores_out, e->span_scores_dev.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
     CSS_HIP_TRY(hipStreamSynchronize(st));
     return CSS_OK;
 }
@@ -1296,13 +1323,10 @@ int css_encoder_forward_spans_dev(css_encoder* e, const int32_t* ids_dev, const 
     CSS_REQUIRE((q_dev != nullptr) == (scores_out_dev != nullptr), "css_encoder_forward_spans_dev: q and scores_out go together");
     std::lock_guard<std::mutex> lk(e->mu);
     DeviceGuard g(e->device);
-    int rc = ensure_acts(e, total_tokens, B);
+    const int rc = ensure_acts(e, total_tokens, B);
     if (rc != CSS_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    // (seq_out NULL: the sequence rows go to the encoder's own buffer)
-    if ((rc = forward_any(e, ids_dev, cu_dev, B, total_tokens, max_len, normalize, seq_out_dev ? seq_out_dev : e->out_dev, st)) != CSS_OK)
-        return rc;
-    return pool_spans(e, cu_dev, B, spans_dev, S, q_dev, normalize, span_out_dev, scores_out_dev, st);
+    return forward_spans_any(e, ids_dev, cu_dev, B, total_tokens, max_len, spans_dev, S, q_dev, normalize, seq_out_dev,
+                             span_out_dev, scores_out_dev, (hipStream_t)stream);
 }
 
 int css_encoder_set_head(css_encoder* e, const float* pooler_w, const float* pooler_b, const float* cls_w, const float* cls_b) {
@@ -1312,13 +1336,14 @@ int css_encoder_set_head(css_encoder* e, const float* pooler_w, const float* poo
     const size_t H = e->cfg.hidden;
     std::lock_guard<std::mutex> lk(e->mu);
     DeviceGuard g(e->device);
-    if (!e->head_dev) CSS_HIP_TRY(hipMalloc((void**)&e->head_dev, (H * H + 2 * H + 1) * 4));
+    const int rc = e->head_dev.grow_exact(H * H + 2 * H + 1, "hipMalloc(head)");
+    if (rc != CSS_OK) return rc;
     e->head_set = false;   // (a failed copy leaves no half-replaced head in use)
     // the stream is idle between calls (every host entry point ends with a synchronise)
-    CSS_HIP_TRY(hipMemcpy(e->head_dev, pooler_w, H * H * 4, hipMemcpyHostToDevice));
-    CSS_HIP_TRY(hipMemcpy(e->head_dev + H * H, pooler_b, H * 4, hipMemcpyHostToDevice));
-    CSS_HIP_TRY(hipMemcpy(e->head_dev + H * H + H, cls_w, H * 4, hipMemcpyHostToDevice));
-    CSS_HIP_TRY(hipMemcpy(e->head_dev + H * H + 2 * H, cls_b, 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(e->head_dev.p, pooler_w, H * H * 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(e->head_dev.p + H * H, pooler_b, H * 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(e->head_dev.p + H * H + H, cls_w, H * 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(e->head_dev.p + H * H + 2 * H, cls_b, 4, hipMemcpyHostToDevice));
     e->head_set = true;
     return CSS_OK;
 }
@@ -1338,14 +1363,11 @@ int css_encoder_forward_pairs(css_encoder* e, const int32_t* ids, const int32_t*
     std::lock_guard<std::mutex> lk(e->mu);
     if ((rc = check_pairs_state(e, "css_encoder_forward_pairs")) != CSS_OK) return rc;
     DeviceGuard g(e->device);
-    if ((rc = ensure_acts(e, T, B)) != CSS_OK || (rc = ensure_pairs(e, B)) != CSS_OK) return rc;
+    if ((rc = stage_batch(e, ids, cu, B)) != CSS_OK || (rc = ensure_pairs(e, B)) != CSS_OK) return rc;
     hipStream_t st = e->stream;
-    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
-    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-    CSS_HIP_TRY(hipMemcpyAsync(e->seg_dev, seg_starts, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    // eager launches (the tiny-batch graphs replay css_encoder_forward only)
-    if ((rc = forward_pairs_any(e, e->ids_dev, e->cu_dev, e->seg_dev, B, T, max_len, e->logits_dev, st)) != CSS_OK) return rc;
-    CSS_HIP_TRY(hipMemcpyAsync(logits_out, e->logits_dev, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    CSS_HIP_TRY(hipMemcpyAsync(e->seg_dev.p, seg_starts, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    if ((rc = forward_pairs_any(e, e->ids_dev.p, e->cu_dev.p, e->seg_dev.p, B, T, max_len, e->logits_dev.p, st)) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpyAsync(logits_out, e->logits_dev.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     CSS_HIP_TRY(hipStreamSynchronize(st));
     return CSS_OK;
 }
@@ -1372,10 +1394,11 @@ int css_encoder_set_token_projection(css_encoder* e, const float* W, int P) {
                 "css_encoder_set_token_projection: P=%d must be a multiple of 32 in [32, %d]", P, kTokMaxP);
     const size_t H = e->cfg.hidden;
     DeviceGuard g(e->device);
-    if (!e->tokw_dev) CSS_HIP_TRY(hipMalloc((void**)&e->tokw_dev, (size_t)kTokMaxP * H * 4));
-    e->tok_p = 0;   // (a failed copy leaves no half-replaced projection in use)
+    const int rc = e->tokw_dev.grow_exact((size_t)kTokMaxP * H, "hipMalloc(token projection)");
+    if (rc != CSS_OK) return rc;
+    e->tok_p = 0;  // (a failed copy leaves no half-replaced projection in use)
     // the stream is idle between calls (every host entry point ends with a synchronise)
-    CSS_HIP_TRY(hipMemcpy(e->tokw_dev, W, (size_t)P * H * 4, hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(e->tokw_dev.p, W, (size_t)P * H * 4, hipMemcpyHostToDevice));
     e->tok_p = P;
     return CSS_OK;
 }
@@ -1397,15 +1420,12 @@ int css_encoder_forward_tokens(css_encoder* e, const int32_t* ids, const int32_t
     std::lock_guard<std::mutex> lk(e->mu);
     DeviceGuard g(e->device);
     const size_t P = token_dim(e);
-    if ((rc = ensure_acts(e, T, B)) != CSS_OK || (rc = e->li_tok.grow((size_t)T * P)) != CSS_OK) return rc;
+    if ((rc = stage_batch(e, ids, cu, B)) != CSS_OK || (rc = e->li_tok.grow((size_t)T * P)) != CSS_OK) return rc;
     hipStream_t st = e->stream;
-    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
-    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-    // eager launches (the tiny-batch graphs replay css_encoder_forward only)
-    if ((rc = forward_any(e, e->ids_dev, e->cu_dev, B, T, max_len, normalize, e->out_dev, st)) != CSS_OK) return rc;
-    if ((rc = write_tokens(e, T, normalize, e->li_tok.p, st)) != CSS_OK) return rc;
+    if ((rc = forward_tokens_any(e, e->ids_dev.p, e->cu_dev.p, B, T, max_len, normalize, e->li_tok.p, nullptr, st)) != CSS_OK)
+        return rc;
     CSS_HIP_TRY(hipMemcpyAsync(tok_out, e->li_tok.p, (size_t)T * P * 2, hipMemcpyDeviceToHost, st));
-    if (seq_out) CSS_HIP_TRY(hipMemcpyAsync(seq_out, e->out_dev, (size_t)B * H * 4, hipMemcpyDeviceToHost, st));
+    if (seq_out) CSS_HIP_TRY(hipMemcpyAsync(seq_out, e->out_dev.p, (size_t)B * H * 4, hipMemcpyDeviceToHost, st));
     CSS_HIP_TRY(hipStreamSynchronize(st));
     return CSS_OK;
 }
@@ -1415,13 +1435,10 @@ int css_encoder_forward_tokens_dev(css_encoder* e, const int32_t* ids_dev, const
     CSS_REQUIRE(e && ids_dev && cu_dev && tok_out_dev, "css_encoder_forward_tokens_dev: NULL argument");
     std::lock_guard<std::mutex> lk(e->mu);
     DeviceGuard g(e->device);
-    int rc = ensure_acts(e, total_tokens, B);
+    const int rc = ensure_acts(e, total_tokens, B);
     if (rc != CSS_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    // (seq_out NULL: the sequence rows go to the encoder's own buffer)
-    if ((rc = forward_any(e, ids_dev, cu_dev, B, total_tokens, max_len, normalize, seq_out_dev ? seq_out_dev : e->out_dev, st)) != CSS_OK)
-        return rc;
-    return write_tokens(e, total_tokens, normalize, tok_out_dev, st);
+    return forward_tokens_any(e, ids_dev, cu_dev, B, total_tokens, max_len, normalize, tok_out_dev, seq_out_dev,
+                              (hipStream_t)stream);
 }
 
 int css_encoder_maxsim(css_encoder* e, const uint16_t* q_tok, const int32_t* cu_q, int nq, const uint16_t* d_tok,
@@ -1475,16 +1492,11 @@ int css_encoder_forward_maxsim(css_encoder* e, const int32_t* ids, const int32_t
     DeviceGuard g(e->device);
     const int P = token_dim(e);
     hipStream_t st = e->stream;
-    if ((rc = ensure_acts(e, T, B)) != CSS_OK || (rc = e->li_tok.grow((size_t)T * P)) != CSS_OK ||
+    if ((rc = stage_batch(e, ids, cu, B)) != CSS_OK || (rc = e->li_tok.grow((size_t)T * P)) != CSS_OK ||
         (rc = upload_maxsim(e, q_tok, cu_q, nq, d_keep, (size_t)T, pairs, np, P, st)) != CSS_OK)
         return rc;
-    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
-    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-    // eager launches (the tiny-batch graphs replay css_encoder_forward only)
-    if ((rc = forward_any(e, e->ids_dev, e->cu_dev, B, T, max_len, 1, e->out_dev, st)) != CSS_OK) return rc;
-    if ((rc = write_tokens(e, T, 1, e->li_tok.p, st)) != CSS_OK) return rc;
-    if ((rc = launch_maxsim(e, e->li_q.p, e->li_cuq.p, nq, e->li_tok.p, e->cu_dev, B, d_keep ? e->li_keep.p : nullptr,
-                            e->li_pairs.p, np, P, e->li_scores.p, st)) != CSS_OK)
+    if ((rc = forward_maxsim_any(e, e->ids_dev.p, e->cu_dev.p, B, T, max_len, e->li_q.p, e->li_cuq.p, nq,
+                                 d_keep ? e->li_keep.p : nullptr, e->li_pairs.p, np, e->li_scores.p, e->li_tok.p, st)) != CSS_OK)
         return rc;
     if (np) CSS_HIP_TRY(hipMemcpyAsync(scores_out, e->li_scores.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
     if (tok_out) CSS_HIP_TRY(hipMemcpyAsync(tok_out, e->li_tok.p, (size_t)T * P * 2, hipMemcpyDeviceToHost, st));
@@ -1501,17 +1513,13 @@ int css_encoder_forward_maxsim_dev(css_encoder* e, const int32_t* ids_dev, const
     CSS_REQUIRE(nq >= 1 && np >= 0, "css_encoder_forward_maxsim_dev: need nq >= 1, np >= 0 (got %d, %d)", nq, np);
     std::lock_guard<std::mutex> lk(e->mu);
     DeviceGuard g(e->device);
-    const int P = token_dim(e);
     int rc = ensure_acts(e, total_tokens, B);
     // (tok_out NULL: the token rows stay in the encoder's own buffer; growing it frees the old one, so work that an
     // earlier call enqueued on another stream must have finished, as for the activations)
-    if (rc == CSS_OK && !tok_out_dev) rc = e->li_tok.grow((size_t)total_tokens * P);
+    if (rc == CSS_OK && !tok_out_dev) rc = e->li_tok.grow((size_t)total_tokens * token_dim(e));
     if (rc != CSS_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    bf16_t* tok = tok_out_dev ? tok_out_dev : e->li_tok.p;
-    if ((rc = forward_any(e, ids_dev, cu_dev, B, total_tokens, max_len, 1, e->out_dev, st)) != CSS_OK) return rc;
-    if ((rc = write_tokens(e, total_tokens, 1, tok, st)) != CSS_OK) return rc;
-    return launch_maxsim(e, q_tok_dev, cu_q_dev, nq, tok, cu_dev, B, d_keep_dev, pairs_dev, np, P, scores_out_dev, st);
+    return forward_maxsim_any(e, ids_dev, cu_dev, B, total_tokens, max_len, q_tok_dev, cu_q_dev, nq, d_keep_dev, pairs_dev, np,
+                              scores_out_dev, tok_out_dev ? tok_out_dev : e->li_tok.p, (hipStream_t)stream);
 }
 
 int css_encoder_set_mlm_head(css_encoder* e, const float* dense_w, const float* dense_b, const float* ln_g, const float* ln_b,
@@ -1576,20 +1584,13 @@ int css_encoder_vocab_max(css_encoder* e, const float* rows, const int32_t* cu, 
     if (rc != CSS_OK) return rc;
     DeviceGuard g(e->device);
     const size_t T = (size_t)cu[B], H = e->cfg.hidden, V = e->cfg.vocab;
-    const bool bf = e->cfg.compute == 0;
     if ((rc = e->sp_rows.grow(T * H)) != CSS_OK || (rc = e->sp_cu.grow((size_t)B + 1)) != CSS_OK ||
-        (rc = e->sp_z.grow((size_t)B * V)) != CSS_OK || (bf && (rc = e->sp_g16.grow(T * H)) != CSS_OK))
+        (rc = e->sp_z.grow((size_t)B * V)) != CSS_OK)
         return rc;
     hipStream_t st = e->stream;
     CSS_HIP_TRY(hipMemcpyAsync(e->sp_rows.p, rows, T * H * 4, hipMemcpyHostToDevice, st));
     CSS_HIP_TRY(hipMemcpyAsync(e->sp_cu.p, cu, ((size_t)B + 1) * 4, hipMemcpyHostToDevice, st));
-    if (bf) {
-        hipLaunchKernelGGL(k_f32_to_bf16, dim3(1024), dim3(256), 0, st, (const float*)e->sp_rows.p, e->sp_g16.p, T * H);
-        CSS_LAUNCH_CHECK();
-    }
-    if ((rc = launch_vocab_max(e, bf ? (const void*)e->sp_g16.p : (const void*)e->sp_rows.p, e->sp_cu.p, B, (int)T, e->sp_z.p,
-                               st)) != CSS_OK)
-        return rc;
+    if ((rc = vocab_max_any(e, e->sp_rows.p, e->sp_cu.p, B, (int)T, e->sp_z.p, st)) != CSS_OK) return rc;
     CSS_HIP_TRY(hipMemcpyAsync(zmax_out, e->sp_z.p, (size_t)B * V * 4, hipMemcpyDeviceToHost, st));
     CSS_HIP_TRY(hipStreamSynchronize(st));
     return CSS_OK;
@@ -1603,18 +1604,7 @@ int css_encoder_vocab_max_dev(css_encoder* e, const float* rows_dev, const int32
     int rc = check_sparse_state(e, "css_encoder_vocab_max_dev");
     if (rc != CSS_OK) return rc;
     DeviceGuard g(e->device);
-    hipStream_t st = (hipStream_t)stream;
-    const void* rows = rows_dev;
-    if (e->cfg.compute == 0) {
-        // (the bf16 rounding of the rows lives in a buffer of the encoder's that only grows; growing frees the old one,
-        // so work that an earlier call enqueued on another stream must have finished, as for the activations)
-        const size_t n = (size_t)total_tokens * e->cfg.hidden;
-        if ((rc = e->sp_g16.grow(n)) != CSS_OK) return rc;
-        hipLaunchKernelGGL(k_f32_to_bf16, dim3(1024), dim3(256), 0, st, rows_dev, e->sp_g16.p, n);
-        CSS_LAUNCH_CHECK();
-        rows = e->sp_g16.p;
-    }
-    return launch_vocab_max(e, rows, cu_dev, B, total_tokens, reinterpret_cast<unsigned*>(zmax_out_dev), st);
+    return vocab_max_any(e, rows_dev, cu_dev, B, total_tokens, reinterpret_cast<unsigned*>(zmax_out_dev), (hipStream_t)stream);
 }
 
 int css_encoder_forward_sparse(css_encoder* e, const int32_t* ids, const int32_t* cu, int B, int m, int32_t* terms_out,
@@ -1630,21 +1620,18 @@ int css_encoder_forward_sparse(css_encoder* e, const int32_t* ids, const int32_t
     if ((rc = check_sparse_state(e, "css_encoder_forward_sparse")) != CSS_OK) return rc;
     DeviceGuard g(e->device);
     const size_t bm = (size_t)B * m;
-    if ((rc = ensure_acts(e, T, B)) != CSS_OK || (rc = e->sp_z.grow((size_t)B * V)) != CSS_OK ||
+    if ((rc = stage_batch(e, ids, cu, B)) != CSS_OK || (rc = e->sp_z.grow((size_t)B * V)) != CSS_OK ||
         (rc = e->sp_terms.grow(bm)) != CSS_OK || (rc = e->sp_w.grow(bm)) != CSS_OK || (rc = e->sp_nnz.grow(B)) != CSS_OK)
         return rc;
     hipStream_t st = e->stream;
-    CSS_HIP_TRY(hipMemcpyAsync(e->ids_dev, ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
-    CSS_HIP_TRY(hipMemcpyAsync(e->cu_dev, cu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-    // eager launches (the tiny-batch graphs replay css_encoder_forward only)
-    if ((rc = forward_sparse_any(e, e->ids_dev, e->cu_dev, B, T, max_len, m, e->sp_terms.p, e->sp_w.p, e->sp_nnz.p, e->sp_z.p,
-                                 e->pre32, st)) != CSS_OK)
+    if ((rc = forward_sparse_any(e, e->ids_dev.p, e->cu_dev.p, B, T, max_len, m, e->sp_terms.p, e->sp_w.p, e->sp_nnz.p, e->sp_z.p,
+                                 e->pre32.p, st)) != CSS_OK)
         return rc;
     CSS_HIP_TRY(hipMemcpyAsync(terms_out, e->sp_terms.p, bm * 4, hipMemcpyDeviceToHost, st));
     CSS_HIP_TRY(hipMemcpyAsync(weights_out, e->sp_w.p, bm * 4, hipMemcpyDeviceToHost, st));
     CSS_HIP_TRY(hipMemcpyAsync(nnz_out, e->sp_nnz.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     if (dense_out) CSS_HIP_TRY(hipMemcpyAsync(dense_out, e->sp_z.p, (size_t)B * V * 4, hipMemcpyDeviceToHost, st));
-    if (rows_out) CSS_HIP_TRY(hipMemcpyAsync(rows_out, e->pre32, (size_t)T * H * 4, hipMemcpyDeviceToHost, st));
+    if (rows_out) CSS_HIP_TRY(hipMemcpyAsync(rows_out, e->pre32.p, (size_t)T * H * 4, hipMemcpyDeviceToHost, st));
     CSS_HIP_TRY(hipStreamSynchronize(st));
     return CSS_OK;
 }
@@ -1667,7 +1654,7 @@ int css_encoder_forward_sparse_dev(css_encoder* e, const int32_t* ids_dev, const
     if (rc != CSS_OK) return rc;
     unsigned* z = dense_out_dev ? reinterpret_cast<unsigned*>(dense_out_dev) : e->sp_z.p;
     return forward_sparse_any(e, ids_dev, cu_dev, B, total_tokens, max_len, m, terms_out_dev, weights_out_dev, nnz_out_dev, z,
-                              rows_out_dev ? rows_out_dev : e->pre32, (hipStream_t)stream);
+                              rows_out_dev ? rows_out_dev : e->pre32.p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -18,8 +18,8 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import synth
-from .cross_encoder import rank_scores
-from .mpnet_encoder import BERT_SMALL_CFG, MpnetEncoder, _find_model_dir, _load_state_dict, parse_model_config
+from .head_model import HeadModel, distinct_queries
+from .mpnet_encoder import length_sorted_batches, parse_model_config
 
 #: synthetic tensor id and std of the token projection (the body uses 0-5 and 16 + 16 * layer + 0..15, the
 #: cross-encoder head 6-9)
@@ -113,50 +113,18 @@ def synth_projection(hidden: int, dim: int, seed: int) -> np.ndarray:
     return (np.float32(std) * v).astype(np.float32).reshape(dim, hidden)
 
 
-class LateInteraction:
+class LateInteraction(HeadModel):
+    _noun = "late interaction"
+    _normalize = True
+    _parse_config = staticmethod(parse_late_interaction_config)
+
     def __init__(self, model_name_or_path: Optional[str], device: int = 0, compute: str = "bf16",
                  synthetic_seed: Optional[int] = None, cfg_overrides: Optional[dict] = None, query_length: int = 32,
                  document_length: Optional[int] = None, query_marker_id: Optional[int] = 1,
                  document_marker_id: Optional[int] = 2, skip_ids: Sequence[int] = (), projection_dim: Optional[int] = 128,
                  encoder=None):
-        # encoder: an object with the late-interaction surface of MpnetEncoder (tests pass a fake; no GPU is touched)
-        self.model_dir = None
-        self._owns_encoder = encoder is None      # a caller's encoder stays the caller's: close() leaves it open
-        if encoder is not None:
-            self.encoder = encoder
-        elif synthetic_seed is None:
-            model_dir = _find_model_dir(model_name_or_path or "", None)
-            if model_dir is None:
-                raise FileNotFoundError(f"model '{model_name_or_path}' not found locally (no network): pass a directory "
-                                        "in HF layout, or synthetic_seed=<int> for seeded synthetic weights")
-            cfg = parse_late_interaction_config(model_dir)
-            body, W = split_projection(_load_state_dict(model_dir), int(cfg["hidden"]))
-            over = dict(pooling=cfg["pooling"], normalize=cfg["normalize"])
-            over.update(cfg_overrides or {})
-            self.encoder = MpnetEncoder(str(model_dir), device=device, compute=compute, cfg_overrides=over, weights=body)
-            try:
-                self.encoder.set_token_projection(W)
-                if self.encoder.tokenizer is None:
-                    raise FileNotFoundError(self.encoder.tokenizer_problem)
-            except Exception:
-                self.encoder.close()
-                raise
-            self.model_dir = model_dir
-        else:
-            cfg = dict(BERT_SMALL_CFG, pooling="cls", normalize=True)
-            if cfg_overrides:
-                cfg.update(cfg_overrides)
-            if cfg.get("arch") != "bert":
-                raise ValueError(f"unsupported arch {cfg.get('arch')!r} for late interaction (supported: 'bert')")
-            self.encoder = MpnetEncoder(synthetic_seed=synthetic_seed, device=device, compute=compute, cfg_overrides=cfg)
-            if projection_dim:
-                try:
-                    self.encoder.set_token_projection(synth_projection(int(cfg["hidden"]), int(projection_dim), synthetic_seed))
-                except Exception:
-                    self.encoder.close()
-                    raise
-        self.cfg = self.encoder.cfg
-        self.tokenizer = self.encoder.tokenizer
+        self._synth_dim = projection_dim   # rows of the synthetic projection (None / 0: none, P = H)
+        super().__init__(model_name_or_path, device, compute, synthetic_seed, cfg_overrides, encoder)
         limit = int(self.cfg["max_seq_len"])
         self.query_length = int(query_length)
         self.document_length = limit if document_length is None else int(document_length)
@@ -175,15 +143,15 @@ class LateInteraction:
             self.close()
             raise ValueError(problem)
 
-    def close(self) -> None:
-        if self._owns_encoder:
-            self.encoder.close()
+    # the head is the projection W [P, H], or None: the token vectors are the hidden states
+    def _split(self, sd, cfg):
+        return split_projection(sd, int(cfg["hidden"]))
 
-    def __enter__(self) -> "LateInteraction":
-        return self
+    def _synth(self, cfg, seed):
+        return synth_projection(int(cfg["hidden"]), int(self._synth_dim), seed) if self._synth_dim else None
 
-    def __exit__(self, *exc) -> None:
-        self.close()
+    def _attach(self, W) -> None:
+        self.encoder.set_token_projection(W)
 
     @property
     def token_dim(self) -> int:
@@ -207,10 +175,7 @@ class LateInteraction:
     # -- token matrices -----------------------------------------------------------
     def _encode(self, ids: List[List[int]], batch_size: int) -> List[np.ndarray]:
         mats: List[Optional[np.ndarray]] = [None] * len(ids)
-        bs = max(1, int(batch_size))
-        order = sorted(range(len(ids)), key=lambda i: -len(ids[i]))
-        for s in range(0, len(order), bs):
-            idx = order[s:s + bs]
+        for idx in length_sorted_batches([len(s) for s in ids], batch_size):
             for i, m in zip(idx, self.encoder.encode_tokens_ids([ids[i] for i in idx], normalize=True)):
                 mats[i] = np.array(m, copy=True)
         return mats
@@ -240,30 +205,15 @@ class LateInteraction:
         pairs = list(pairs)
         if not pairs:
             return np.zeros(0, dtype=np.float32)
-        qtexts: List[str] = []
-        qindex: Dict[str, int] = {}
-        for p in pairs:
-            if p[0] not in qindex:
-                qindex[p[0]] = len(qtexts)
-                qtexts.append(p[0])
+        qtexts, qindex = distinct_queries(pairs)
         q_mats, _ = self.encode_queries(qtexts, batch_size)
         ids = self.document_ids([p[1] for p in pairs])
         keep = self._keep(ids)
         out = np.empty(len(pairs), dtype=np.float32)
-        bs = max(1, int(batch_size))
-        order = sorted(range(len(ids)), key=lambda i: -len(ids[i]))
-        for s in range(0, len(order), bs):
-            idx = order[s:s + bs]
+        for idx in length_sorted_batches([len(s) for s in ids], batch_size):
             used = sorted({qindex[pairs[i][0]] for i in idx})
             local = {q: n for n, q in enumerate(used)}
             pr = [(local[qindex[pairs[i][0]]], n) for n, i in enumerate(idx)]
             out[idx] = self.encoder.score_late_ids([ids[i] for i in idx], [q_mats[q] for q in used], pairs=pr,
                                                    keep=[keep[i] for i in idx] if keep is not None else None)
         return out
-
-    def rank(self, query: str, documents: Sequence[str], top_k: Optional[int] = None,
-             return_documents: bool = False) -> List[dict]:
-        """``[{"corpus_id", "score"[, "text"]}]`` of ``documents`` against ``query``, best first; ties go to the lower
-        ``corpus_id``."""
-        documents = list(documents)
-        return rank_scores(self.predict([(query, d) for d in documents]), documents, top_k, return_documents)

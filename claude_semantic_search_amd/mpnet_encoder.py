@@ -225,6 +225,15 @@ def _load_state_dict(model_dir: Path) -> Dict[str, np.ndarray]:
     raise FileNotFoundError(f"no model.safetensors / pytorch_model.bin under {root}")
 
 
+def length_sorted_batches(lengths: Sequence[int], batch_size: int):
+    """Yields lists of at most ``batch_size`` indices into ``lengths``, longest first (equal lengths in input order).
+    Packed var-len batches have no padding; sorting only keeps a batch's attention tiles even."""
+    bs = max(1, int(batch_size))
+    order = sorted(range(len(lengths)), key=lambda i: -lengths[i])
+    for s in range(0, len(order), bs):
+        yield order[s:s + bs]
+
+
 class MpnetEncoder:
     def __init__(self, model_name_or_path: Optional[str] = "all-mpnet-base-v2", cache_folder: Optional[str] = None,
                  device: int = 0, compute: str = "bf16", synthetic_seed: Optional[int] = None,
@@ -337,11 +346,7 @@ class MpnetEncoder:
     def encode_ids(self, batch: Sequence[Sequence[int]], normalize: bool = True) -> np.ndarray:
         """One packed var-len batch through ``css_encoder_forward``."""
         B = len(batch)
-        lens = np.fromiter((len(s) for s in batch), dtype=np.int32, count=B)
-        cu = np.zeros(B + 1, dtype=np.int32)
-        np.cumsum(lens, out=cu[1:])
-        ids = np.concatenate([np.asarray(s, dtype=np.int32) for s in batch]) if B else np.zeros(0, np.int32)
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        ids, cu = self._pack_ids(batch)
         out = np.empty((B, self.cfg["hidden"]), dtype=np.float32)
         nat.check(nat.lib().css_encoder_forward(self._h, ids.ctypes.data, cu.ctypes.data, B, 1 if normalize else 0,
                                                 out.ctypes.data))
@@ -357,12 +362,8 @@ class MpnetEncoder:
         ``span_rows=False`` (scores only) leaves the span rows on the device and returns ``None`` for them."""
         B = len(batch)
         H = int(self.cfg["hidden"])
-        lens = np.fromiter((len(s) for s in batch), dtype=np.int32, count=B)
-        cu = np.zeros(B + 1, dtype=np.int32)
-        np.cumsum(lens, out=cu[1:])
-        ids = np.concatenate([np.asarray(s, dtype=np.int32) for s in batch]) if B else np.zeros(0, np.int32)
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
-        sp = np.ascontiguousarray(np.asarray(spans if len(spans) else np.zeros((0, 3)), dtype=np.int64))
+        ids, cu = self._pack_ids(batch)
+        sp =np.ascontiguousarray(np.asarray(spans if len(spans) else np.zeros((0, 3)), dtype=np.int64))
         if sp.ndim != 2 or sp.shape[1] != 3:
             raise ValueError(f"encode_spans_ids: spans must be [S, 3] = (sequence, begin, end) (got shape {sp.shape})")
         if sp.size and np.abs(sp).max() >= 2 ** 31:
@@ -410,10 +411,7 @@ class MpnetEncoder:
         if np.abs(seg).max() >= 2 ** 31:
             raise ValueError("score_pair_ids: seg_starts must fit int32")
         seg = np.ascontiguousarray(seg, dtype=np.int32)
-        lens = np.fromiter((len(s) for s in batch), dtype=np.int32, count=B)
-        cu = np.zeros(B + 1, dtype=np.int32)
-        np.cumsum(lens, out=cu[1:])
-        ids = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int32) for s in batch]), dtype=np.int32)
+        ids, cu = self._pack_ids(batch)
         out = np.empty(B, dtype=np.float32)
         nat.check(nat.lib().css_encoder_forward_pairs(self._h, ids.ctypes.data, cu.ctypes.data, seg.ctypes.data, B,
                                                       out.ctypes.data))
@@ -607,7 +605,7 @@ class MpnetEncoder:
         norm = bool(self.cfg.get("normalize", True) or normalize_embeddings)
         # Super-batches of 16 device batches: the next one is tokenised on a host thread (both the C++ tokenizer and
         # the forward release the GIL) while the GPU encodes the current one; texts are length-sorted inside a
-        # super-batch (packed var-len batches have no padding, sorting only keeps a batch's attention tiles even).
+        # super-batch (length_sorted_batches).
         span = max(16 * bs, 1024)
         starts = list(range(0, len(texts), span))
         bar = None
@@ -619,9 +617,7 @@ class MpnetEncoder:
             except Exception:
                 bar = None
         def run(base: int, toks) -> None:
-            order = sorted(range(len(toks)), key=lambda i: -len(toks[i]))
-            for s in range(0, len(order), bs):
-                idx = order[s:s + bs]
+            for idx in length_sorted_batches([len(t) for t in toks], bs):
                 # a Normalize() module of the model makes outputs unit norm regardless of the flag
                 out[[base + i for i in idx]] = self.encode_ids([toks[i] for i in idx], normalize=norm)
                 if bar is not None:

@@ -17,8 +17,8 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import synth
-from .cross_encoder import rank_scores
-from .mpnet_encoder import BERT_SMALL_CFG, MpnetEncoder, _find_model_dir, _load_state_dict, parse_model_config
+from .head_model import HeadModel, distinct_queries
+from .mpnet_encoder import length_sorted_batches, parse_model_config
 
 #: synthetic tensor id and std of the head's tensors (the body uses 0-5 and 16 + 16 * layer + 0..15, the cross-encoder
 #: head 6-9, the token projection 10); the decoder is tied
@@ -114,62 +114,28 @@ def synth_mlm_head(hidden: int, vocab: int, seed: int, bias_sigmas: float = SYNT
             "decoder_b": t("decoder_b", vocab, bias_sigmas * 0.02 * math.sqrt(hidden))}
 
 
-class SparseEncoder:
+class SparseEncoder(HeadModel):
+    _noun = "a sparse encoder"
+    _parse_config = staticmethod(parse_sparse_config)
+
     def __init__(self, model_name_or_path: Optional[str], device: int = 0, compute: str = "bf16",
                  max_length: Optional[int] = None, synthetic_seed: Optional[int] = None,
                  cfg_overrides: Optional[dict] = None, encoder=None):
-        # encoder: an object with the sparse surface of MpnetEncoder (tests pass a fake; no GPU is touched)
-        self.model_dir = None
-        self._owns_encoder = encoder is None      # a caller's encoder stays the caller's: close() leaves it open
-        if encoder is not None:
-            self.encoder = encoder
-        elif synthetic_seed is None:
-            model_dir = _find_model_dir(model_name_or_path or "", None)
-            if model_dir is None:
-                raise FileNotFoundError(f"model '{model_name_or_path}' not found locally (no network): pass a directory "
-                                        "in HF layout, or synthetic_seed=<int> for seeded synthetic weights")
-            cfg = parse_sparse_config(model_dir)
-            body, head = split_mlm_head(_load_state_dict(model_dir), int(cfg["hidden"]), int(cfg["vocab"]))
-            over = dict(pooling=cfg["pooling"], normalize=cfg["normalize"])
-            over.update(cfg_overrides or {})
-            self.encoder = MpnetEncoder(str(model_dir), device=device, compute=compute, cfg_overrides=over, weights=body)
-            try:
-                self.encoder.set_mlm_head(**head)
-                if self.encoder.tokenizer is None:
-                    raise FileNotFoundError(self.encoder.tokenizer_problem)
-            except Exception:
-                self.encoder.close()
-                raise
-            self.model_dir = model_dir
-        else:
-            cfg = dict(BERT_SMALL_CFG, pooling="cls", normalize=False)
-            if cfg_overrides:
-                cfg.update(cfg_overrides)
-            if cfg.get("arch") != "bert":
-                raise ValueError(f"unsupported arch {cfg.get('arch')!r} for a sparse encoder (supported: 'bert')")
-            self.encoder = MpnetEncoder(synthetic_seed=synthetic_seed, device=device, compute=compute, cfg_overrides=cfg)
-            try:
-                self.encoder.set_mlm_head(**synth_mlm_head(int(cfg["hidden"]), int(cfg["vocab"]), synthetic_seed))
-            except Exception:
-                self.encoder.close()
-                raise
-        self.cfg = self.encoder.cfg
-        self.tokenizer = self.encoder.tokenizer
+        super().__init__(model_name_or_path, device, compute, synthetic_seed, cfg_overrides, encoder)
         limit = int(self.cfg["max_seq_len"])
         self.max_length = limit if max_length is None else int(max_length)
         if not 2 <= self.max_length <= limit:
             self.close()
             raise ValueError(f"max_length={self.max_length} outside [2, {limit}] (the encoder's max_seq_len)")
 
-    def close(self) -> None:
-        if self._owns_encoder:
-            self.encoder.close()
+    def _split(self, sd, cfg):
+        return split_mlm_head(sd, int(cfg["hidden"]), int(cfg["vocab"]))
 
-    def __enter__(self) -> "SparseEncoder":
-        return self
+    def _synth(self, cfg, seed):
+        return synth_mlm_head(int(cfg["hidden"]), int(cfg["vocab"]), seed)
 
-    def __exit__(self, *exc) -> None:
-        self.close()
+    def _attach(self, head) -> None:
+        self.encoder.set_mlm_head(**head)
 
     # -- vectors ------------------------------------------------------------------
     def text_ids(self, texts: Sequence[str]) -> List[List[int]]:
@@ -185,10 +151,7 @@ class SparseEncoder:
         if not 1 <= m <= MAX_TERMS:
             raise ValueError(f"max_terms={m} outside [1, {MAX_TERMS}]")
         vecs: List[Optional[SparseVector]] = [None] * len(ids)
-        bs = max(1, int(batch_size))
-        order = sorted(range(len(ids)), key=lambda i: -len(ids[i]))
-        for s in range(0, len(order), bs):
-            idx = order[s:s + bs]
+        for idx in length_sorted_batches([len(s) for s in ids], batch_size):
             terms, weights, nnz = self.encoder.encode_sparse_ids([ids[i] for i in idx], m)[:3]
             for n, i in enumerate(idx):
                 k = min(int(nnz[n]), m)
@@ -222,22 +185,10 @@ class SparseEncoder:
         pairs = list(pairs)
         if not pairs:
             return np.zeros(0, dtype=np.float32)
-        qtexts: List[str] = []
-        qindex: Dict[str, int] = {}
-        for p in pairs:
-            if p[0] not in qindex:
-                qindex[p[0]] = len(qtexts)
-                qtexts.append(p[0])
+        qtexts, qindex = distinct_queries(pairs)
         q_vecs = self.encode_queries(qtexts, batch_size)
         d_vecs = self.encode_documents([p[1] for p in pairs], batch_size)
         return self.score(q_vecs, d_vecs, [(qindex[p[0]], n) for n, p in enumerate(pairs)])
-
-    def rank(self, query: str, documents: Sequence[str], top_k: Optional[int] = None,
-             return_documents: bool = False) -> List[dict]:
-        """``[{"corpus_id", "score"[, "text"]}]`` of ``documents`` against ``query``, best first; ties go to the lower
-        ``corpus_id``."""
-        documents = list(documents)
-        return rank_scores(self.predict([(query, d) for d in documents]), documents, top_k, return_documents)
 
     # -- reading a vector -------------------------------------------------------------
     def _word(self, term: int) -> str:
