@@ -49,6 +49,8 @@ _LAZY = {
     "MpnetEncoder": ".mpnet_encoder",
     "CrossEncoder": ".cross_encoder",
     "LateInteraction": ".late_interaction",
+    "FixedDimensionalEncoding": ".muvera",
+    "fde_numpy": ".muvera",
     "SparseEncoder": ".sparse_encoder",
     "SparseVector": ".sparse_encoder",
     "sparse_dot_numpy": ".sparse_encoder",

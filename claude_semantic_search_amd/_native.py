@@ -191,6 +191,11 @@ PROTOTYPES = {
     "css_index_maxsim_rows_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "css_index_search_rerank_maxsim": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                                c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_fde_create": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, POINTER(c_void_p)]),
+    "css_fde_free": (c_int, [c_void_p]),
+    "css_fde_dim": (c_int, [c_void_p, POINTER(c_int)]),
+    "css_fde_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "css_fde_encode_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "css_index_maxsim_candidates": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                             POINTER(c_int64)]),
     "css_index_search_maxsim_pruned": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,

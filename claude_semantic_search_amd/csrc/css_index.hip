@@ -2947,6 +2947,7 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 #include "css_tokens_batch.h"
 #include "css_tokens_lists.h"
 #include "css_token_prune.h"
+#include "css_fde.h"
 #include "css_where.h"
 #include "css_sigterms.h"
 
@@ -5904,6 +5905,187 @@ int css_index_set_token_blocks(css_index* ix, int blocks) {
     std::unique_lock<std::shared_mutex> lk(ix->mu);
     ix->tk_blocks = blocks;
     return CSS_OK;
+}
+
+// ---- fixed-dimensional encodings (css_fde.h; include/css_hip.h has the definition) ----
+}  // extern "C"
+
+// The encoder: its parameters, the material in the kernels' fragment order, and the buffers of the host form.  An object
+// of its own (no index): `mu` is its lock, `stream` its stream, and the host form is upload, launch, copies back and
+// ONE wait, like the frame of the search entry points.
+struct css_fde {
+    int P = 0, k_sim = 0, d_proj = 0, reps = 0, device = 0, num_cus = 256;
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+    std::atomic<int> blocks_per_cu{0};   // resident blocks of this encoder's kernel per CU (0: not asked yet)
+    DevBuf<uint4> planes_f;    // [reps][P / 32][64]
+    DevBuf<float4> proj_f;     // [reps][d_proj / 16][P / 16][64]
+    DevBuf<int64_t> off;       // the host form's offsets, tokens, rows and bucket bytes
+    DevBuf<unsigned short> tok;
+    DevBuf<float> out;
+    DevBuf<unsigned char> buckets;
+    int64_t dim() const { return (int64_t)reps * (1ll << k_sim) * d_proj; }
+};
+
+namespace {
+inline float bf16_value(uint16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
+
+int fde_enqueue(css_fde* f, const int64_t* off_dev, const uint16_t* tok_dev, int64_t n, int is_query, float* out_dev,
+                uint8_t* buckets_dev, hipStream_t st) {
+    if (n == 0) return CSS_OK;
+    FdeArgs a{off_dev, tok_dev, f->planes_f.p, f->proj_f.p, out_dev, buckets_dev, n, f->k_sim, f->d_proj, f->reps, is_query};
+    const int nbt = std::max(1, (1 << f->k_sim) / 16);
+    void (*fn)(const FdeArgs) = nullptr;
+#define CSS_FDE_P(PP) fn = nbt == 1 ? k_fde<PP, 1> : nbt == 2 ? k_fde<PP, 2> : k_fde<PP, 4>
+    switch (f->P) {
+        case 32: CSS_FDE_P(32); break;
+        case 64: CSS_FDE_P(64); break;
+        case 96: CSS_FDE_P(96); break;
+        default: CSS_FDE_P(128); break;
+    }
+#undef CSS_FDE_P
+    // a persistent grid: as many blocks as are resident at once (LDS allows four per CU, the registers of the
+    // instantiation fewer: the runtime knows), asked once per encoder -- it has ONE kernel
+    int per_cu = f->blocks_per_cu.load(std::memory_order_relaxed);
+    if (per_cu == 0) {
+        CSS_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, 64 * kWaves, 0));
+        per_cu = std::max(1, std::min(per_cu, 4));
+        f->blocks_per_cu.store(per_cu, std::memory_order_relaxed);
+    }
+    const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)f->num_cus * per_cu);
+    void* args[] = {&a};
+    ProfScope ps("fde", st);
+    CSS_HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid), dim3(64 * kWaves), args, 0, st));
+    return CSS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int css_fde_create(int P, int k_sim, int d_proj, int reps, const uint16_t* planes_host, const uint16_t* proj_host, int device,
+                   css_fde** out) {
+    CSS_REQUIRE(out != nullptr, "css_fde_create: out is NULL");
+    CSS_REQUIRE(token_dim_ok(P), "css_fde_create: P=%d must be a multiple of 32 in [32, %d]", P, CSS_MAX_TOKEN_DIM);
+    CSS_REQUIRE(k_sim >= 1 && k_sim <= CSS_FDE_MAX_KSIM, "css_fde_create: k_sim=%d outside [1, %d]", k_sim, CSS_FDE_MAX_KSIM);
+    CSS_REQUIRE(d_proj == 16 || d_proj == 32 || d_proj == 64, "css_fde_create: d_proj=%d is not 16, 32 or 64", d_proj);
+    CSS_REQUIRE(reps >= 1 && reps <= CSS_FDE_MAX_REPS, "css_fde_create: reps=%d outside [1, %d]", reps, CSS_FDE_MAX_REPS);
+    const int64_t dim = (int64_t)reps * (1ll << k_sim) * d_proj;
+    CSS_REQUIRE(dim <= 8192, "css_fde_create: dim = reps * 2^k_sim * d_proj = %lld exceeds 8192", (long long)dim);
+    CSS_REQUIRE(planes_host && proj_host, "css_fde_create: NULL material");
+    for (int64_t e = 0; e < (int64_t)reps * k_sim * P; ++e)
+        CSS_REQUIRE(bf16_finite(planes_host[e]), "css_fde_create: component %lld of row %lld of planes is %s", (long long)(e % P),
+                    (long long)(e / P), (planes_host[e] & 0x7Fu) ? "NaN" : "infinite");
+    for (int64_t e = 0; e < (int64_t)reps * d_proj * P; ++e)
+        CSS_REQUIRE(bf16_finite(proj_host[e]), "css_fde_create: component %lld of row %lld of proj is %s", (long long)(e % P),
+                    (long long)(e / P), (proj_host[e] & 0x7Fu) ? "NaN" : "infinite");
+    int rc = css::check_device(device);
+    if (rc != CSS_OK) return rc;
+    // the material in fragment order (css_fde.h): lane l = (column or row l & 15, group g = l >> 4)
+    const int KS = P / 32, PT = P / 16, JT = d_proj / 16;
+    std::vector<uint16_t> pl;
+    std::vector<float> pj;
+    try {
+        pl.assign((size_t)reps * KS * 64 * 8, 0);
+        pj.assign((size_t)reps * JT * PT * 64 * 4, 0.f);
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_fde_create: out of host memory");
+        return CSS_ERR_OOM;
+    }
+    for (int r = 0; r < reps; ++r)
+        for (int l = 0; l < 64; ++l) {
+            const int c = l & 15, g = l >> 4;
+            for (int ks = 0; ks < KS && c < k_sim; ++ks)
+                for (int j = 0; j < 8; ++j)
+                    pl[(((size_t)r * KS + ks) * 64 + l) * 8 + j] = planes_host[((size_t)r * k_sim + c) * P + 32 * ks + 8 * g + j];
+            for (int jt = 0; jt < JT; ++jt)
+                for (int pt = 0; pt < PT; ++pt)
+                    for (int i = 0; i < 4; ++i)
+                        pj[((((size_t)r * JT + jt) * PT + pt) * 64 + l) * 4 + i] =
+                            bf16_value(proj_host[((size_t)r * d_proj + 16 * jt + c) * P + 16 * pt + 4 * g + i]);
+        }
+    DeviceGuard g(device);
+    std::unique_ptr<css_fde> f(new css_fde());
+    f->P = P, f->k_sim = k_sim, f->d_proj = d_proj, f->reps = reps, f->device = device;
+    hipDeviceProp_t p;
+    if (hipGetDeviceProperties(&p, device) == hipSuccess) f->num_cus = p.multiProcessorCount;
+    if ((rc = f->planes_f.grow_exact(pl.size() / 8, "hipMalloc(fde planes)")) != CSS_OK) return rc;
+    if ((rc = f->proj_f.grow_exact(pj.size() / 4, "hipMalloc(fde proj)")) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpy(f->planes_f.p, pl.data(), pl.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(f->proj_f.p, pj.data(), pj.size() * sizeof(float), hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    *out = f.release();
+    return CSS_OK;
+}
+
+int css_fde_free(css_fde* f) {
+    if (!f) return CSS_OK;
+    DeviceGuard g(f->device);
+    (void)hipStreamSynchronize(f->stream);
+    (void)hipStreamDestroy(f->stream);
+    delete f;   // (the DevBufs free inside the guard; hipFree waits for what a _dev call enqueued)
+    return CSS_OK;
+}
+
+int css_fde_dim(const css_fde* f, int* dim_out) {
+    CSS_REQUIRE(f && dim_out, "css_fde_dim: NULL argument");
+    *dim_out = (int)f->dim();
+    return CSS_OK;
+}
+
+int css_fde_encode(css_fde* f, const int64_t* offsets_host, const uint16_t* tok_host, int64_t n, int is_query, float* out_host,
+                   uint8_t* buckets_out_host) {
+    CSS_REQUIRE(f, "css_fde_encode: NULL encoder");
+    CSS_REQUIRE(n >= 0, "css_fde_encode: n < 0");
+    if (n == 0) return CSS_OK;
+    CSS_REQUIRE(offsets_host && out_host, "css_fde_encode: NULL buffer");
+    // everything is looked at before anything is written.  (A query matrix may be as long as a document's: the
+    // 64-token limit is that of the MaxSim kernels, not of the encoding.)
+    const char* kind = is_query ? "query matrix" : "document";
+    CSS_REQUIRE(offsets_host[0] == 0, "css_fde_encode: offsets start at %lld, not 0", (long long)offsets_host[0]);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t c = offsets_host[i + 1] - offsets_host[i];
+        CSS_REQUIRE(c >= 0, "css_fde_encode: offsets decrease at %s %lld", kind, (long long)i);
+        CSS_REQUIRE(c <= CSS_MAX_ROW_TOKEN_VECTORS, "css_fde_encode: %s %lld has %lld tokens (at most %d)", kind, (long long)i,
+                    (long long)c, CSS_MAX_ROW_TOKEN_VECTORS);
+    }
+    const int64_t E = offsets_host[n];
+    const int P = f->P;
+    CSS_REQUIRE(E == 0 || tok_host, "css_fde_encode: tokens is NULL");
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t e = offsets_host[i] * P; e < offsets_host[i + 1] * P; ++e)
+            CSS_REQUIRE(bf16_finite(tok_host[e]), "css_fde_encode: component %lld of token %lld of %s %lld is %s", (long long)(e % P),
+                        (long long)(e / P - offsets_host[i]), kind, (long long)i, (tok_host[e] & 0x7Fu) ? "NaN" : "infinite");
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    const size_t dim = (size_t)f->dim(), nb = buckets_out_host ? (size_t)E * f->reps : 0;
+    int rc;
+    if ((rc = f->off.grow((size_t)n + 1)) != CSS_OK) return rc;
+    if ((rc = f->tok.grow(std::max<size_t>((size_t)E * P, 1))) != CSS_OK) return rc;
+    if ((rc = f->out.grow((size_t)n * dim)) != CSS_OK) return rc;
+    if (nb && (rc = f->buckets.grow(nb)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        CSS_HIP_TRY(hipMemcpyAsync(f->off.p, offsets_host, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        if (E) CSS_HIP_TRY(hipMemcpyAsync(f->tok.p, tok_host, (size_t)E * P * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        const int rc2 = fde_enqueue(f, f->off.p, f->tok.p, n, is_query, f->out.p, nb ? f->buckets.p : nullptr, st);
+        if (rc2 != CSS_OK) return rc2;
+        CSS_HIP_TRY(hipMemcpyAsync(out_host, f->out.p, (size_t)n * dim * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (nb) CSS_HIP_TRY(hipMemcpyAsync(buckets_out_host, f->buckets.p, nb, hipMemcpyDeviceToHost, st));
+        return CSS_OK;
+    }();
+    const hipError_t e = hipStreamSynchronize(st);   // the ONE wait (also of a failed call: the copies read the caller's memory)
+    if (rc == CSS_OK && e != hipSuccess) return css::hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    return rc;
+}
+
+int css_fde_encode_dev(css_fde* f, const int64_t* offsets_dev, const uint16_t* tok_dev, int64_t n, int64_t total_tokens,
+                       int is_query, float* out_dev, uint8_t* buckets_out_dev, void* stream) {
+    CSS_REQUIRE(f, "css_fde_encode_dev: NULL encoder");
+    CSS_REQUIRE(n >= 0 && total_tokens >= 0, "css_fde_encode_dev: n or total_tokens < 0");
+    if (n == 0) return CSS_OK;
+    CSS_REQUIRE(offsets_dev && out_dev && (tok_dev || total_tokens == 0), "css_fde_encode_dev: NULL buffer");
+    DeviceGuard g(f->device);
+    return fde_enqueue(f, offsets_dev, tok_dev, n, is_query, out_dev, buckets_out_dev, (hipStream_t)stream);
 }
 
 namespace {

@@ -2112,6 +2112,42 @@ class IndexFlat:
                                                            D.ctypes.data, I.ctypes.data, S.ctypes.data, R.ctypes.data))
         return D, I, S, R
 
+    # -- fixed-dimensional encodings (MUVERA) as the dense first stage -------------
+    def add_fde(self, fde, mats, keep=None) -> None:
+        """Append one row per token matrix: its fixed-dimensional encoding (``muvera.FixedDimensionalEncoding``,
+        encoded on the device and appended with ``add_dev``) as the dense row, the matrix itself (``set_tokens``) for
+        the re-rank.  Needs ``fde.dim == d`` and ``token_rows == ntotal`` before the call: every row is such a pair."""
+        import torch
+
+        if fde.dim != self.d:
+            raise ValueError(f"add_fde: the encoder's dim={fde.dim} is not the index's d={self.d}")
+        if self.token_rows != self.ntotal:
+            raise ValueError(f"add_fde: {self.token_rows} rows have token matrices, the index has {self.ntotal} rows")
+        # everything set_tokens could refuse is looked at BEFORE the rows are appended: rows without matrices would
+        # leave token_rows != ntotal for good
+        if fde.device != self.device:
+            raise ValueError(f"add_fde: the encoder is on device {fde.device}, the index on device {self.device}")
+        if self.token_codec_bits != 0:
+            raise ValueError("add_fde: the index has a token codec; add_fde stores raw matrices")
+        if self.token_dim not in (0, fde.P):
+            raise ValueError(f"add_fde: the stored matrices have P={self.token_dim}, the encoder P={fde.P}")
+        csr = tokens_as_csr(mats, keep, "add_fde")
+        if csr[1].shape[0] and csr[2] != fde.P:
+            raise ValueError(f"add_fde: the matrices have P={csr[2]}, the encoder P={fde.P}")
+        rows = fde.encode_documents_dev(csr)
+        self.add_dev(rows.data_ptr(), rows.shape[0], stream=torch.cuda.current_stream(rows.device).cuda_stream)
+        self.set_tokens(csr)
+
+    def search_fde(self, fde, q_mats, k: int, fetch: int, allow=None):
+        """``search_rerank_maxsim(fde.encode_queries(q_mats), q_mats, k, fetch, normalize=False, allow=allow)``: the pool
+        by the inner product of the encodings, re-ranked by the exact MaxSim; the same four results.  Inner-product
+        indexes only; the re-rank keeps its limit of 64 query tokens."""
+        if self.metric_type != METRIC_INNER_PRODUCT:
+            raise ValueError("search_fde: the index must use the inner-product metric")
+        if fde.dim != self.d:
+            raise ValueError(f"search_fde: the encoder's dim={fde.dim} is not the index's d={self.d}")
+        return self.search_rerank_maxsim(fde.encode_queries(q_mats), q_mats, k, fetch, normalize=False, allow=allow)
+
     # -- candidate generation for MaxSim on the codes (PLAID) ----------------------
     def _prune_codec(self, what: str) -> None:
         if self.token_codec_bits == 0:

@@ -639,6 +639,48 @@ int css_index_search_rerank_maxsim(css_index* ix, const float* q_host /* [nq, d]
                                    float floor, const uint32_t* allow_bits_host, float* D_host /* [nq, k] */,
                                    int64_t* I_host /* [nq, k] */, float* S_host /* [nq, k] */, int32_t* R_host /* [nq, k] */);
 
+/* Fixed-dimensional encodings (MUVERA, Dhulipala et al. 2024): a token matrix [m, P] bf16 becomes ONE fp32 row of
+ * dim = reps * B * d_proj, B = 2^k_sim, whose inner product with a query's row estimates the MaxSim (Chamfer) score:
+ * the first stage of a late-interaction search is then the dense search, the second css_index_search_rerank_maxsim.
+ * An encoder is an object of its own, not tied to an index.
+ *  - Parameters.  P a multiple of 32 in [32, CSS_MAX_TOKEN_DIM]; 1 <= k_sim <= CSS_FDE_MAX_KSIM; d_proj 16, 32 or 64;
+ *    1 <= reps <= CSS_FDE_MAX_REPS; dim <= 8192, the limit of css_index_create.
+ *  - Material, the caller's (the library has no random generator), as bf16 bits with finite components:
+ *    planes [reps * k_sim, P] and proj [reps * d_proj, P].
+ *  - Buckets.  Per token x_t and repetition r: bit_i = dot(x_t, planes[r * k_sim + i]) > 0, bf16 operands, fp32
+ *    accumulation on v_mfma_f32_16x16x32_bf16 with the K steps of 32 ascending (a dot of exactly 0 gives bit 0);
+ *    bucket(t, r) = sum_i bit_i << i.
+ *  - Sums.  Per (r, b): Y[p] = the fp32 sum of x_t[p] over the bucket's tokens, cnt = their number.
+ *  - Documents (is_query = 0).  An empty bucket takes the ONE token t* that minimises popcount(bucket(t*, r) xor b),
+ *    ties to the lowest t: Y = x_t*, cnt = 1.  out[(r * B + b) * d_proj + j] = (sum_p proj[r * d_proj + j][p] * Y[p]) /
+ *    (float)cnt: an fp32 sum and one correctly rounded fp32 division.  A matrix without tokens gives a row of zeros.
+ *  - Queries (is_query = 1).  The same without the fill and without the division; empty buckets are 0.
+ *  - The orders of the fp32 sums are the kernel's own but fixed: one wave owns a repetition of a matrix, so the same
+ *    matrix gives the same bytes whatever the batch around it, its position, the grid and the form (host or _dev).
+ *    On inputs whose products and partial sums are all representable, out is the float64 value bit for bit.
+ *    Otherwise every element lies within (cnt + P + 2) * 2^-24 * sum_p |proj_jp| * sum_{t in bucket} |x_tp| / cnt
+ *    (queries: without / cnt) of float64 for the same bucket assignment, and a bit may differ from float64's only
+ *    where |dot64| <= P * 2^-24 * sum_p |x_p * plane_p|.
+ *  - css_fde_encode: n matrices in CSR form (offsets from 0 in tokens, as css_index_set_tokens takes them), out_host
+ *    [n, dim]; buckets_out_host (may be NULL) receives bucket(t, r) as [offsets[n], reps] bytes.  CSS_ERR_INVALID,
+ *    checked before anything is written, the message names the matrix: offsets that do not start at 0 or that decrease,
+ *    a NaN or infinite component, a matrix of more than CSS_MAX_ROW_TOKEN_VECTORS tokens -- documents and queries alike
+ *    (a query matrix need NOT obey CSS_MAX_QUERY_TOKENS: that is the limit of the MaxSim kernels, and the re-rank
+ *    keeps it).  Uploads, one launch, copies back, ONE wait; calls on one encoder are serialised.
+ *  - css_fde_encode_dev: device pointers (16-byte aligned tokens), enqueued on `stream` without a wait or a check of
+ *    the contents; a matrix longer than the limit is encoded from its first CSS_MAX_ROW_TOKEN_VECTORS tokens. */
+#define CSS_FDE_MAX_KSIM 6
+#define CSS_FDE_MAX_REPS 64
+typedef struct css_fde css_fde;
+int css_fde_create(int P, int k_sim, int d_proj, int reps, const uint16_t* planes_host /* bf16 [reps * k_sim, P] */,
+                   const uint16_t* proj_host /* bf16 [reps * d_proj, P] */, int device, css_fde** out);
+int css_fde_free(css_fde* f);
+int css_fde_dim(const css_fde* f, int* dim_out);
+int css_fde_encode(css_fde* f, const int64_t* offsets_host /* [n + 1], from 0 */, const uint16_t* tok_host /* bf16 [offsets[n], P] */,
+                   int64_t n, int is_query, float* out_host /* [n, dim] */, uint8_t* buckets_out_host /* [offsets[n], reps] or NULL */);
+int css_fde_encode_dev(css_fde* f, const int64_t* offsets_dev, const uint16_t* tok_dev, int64_t n, int64_t total_tokens,
+                       int is_query, float* out_dev, uint8_t* buckets_out_dev /* or NULL */, void* stream);
+
 /* Significant terms (Elasticsearch's significant_terms aggregation, the keyword side of BERTopic): which terms set a
  * selection of rows apart from a background -- "what is in this cluster / this project / these hits".  Everything is
  * read from the term lists above; the rows' values play no part.  T = the leading rows that have lists.
