@@ -51,6 +51,9 @@ _LAZY = {
     "LateInteraction": ".late_interaction",
     "FixedDimensionalEncoding": ".muvera",
     "fde_numpy": ".muvera",
+    "IndexPQ": ".pq",
+    "ProductQuantizer": ".pq",
+    "train_product_quantizer": ".pq",
     "SparseEncoder": ".sparse_encoder",
     "SparseVector": ".sparse_encoder",
     "sparse_dot_numpy": ".sparse_encoder",

@@ -196,6 +196,18 @@ PROTOTYPES = {
     "css_fde_dim": (c_int, [c_void_p, POINTER(c_int)]),
     "css_fde_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "css_fde_encode_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "css_pq_create": (c_int, [c_int, c_void_p, c_int, POINTER(c_void_p)]),
+    "css_pq_free": (c_int, [c_void_p]),
+    "css_pq_dim": (c_int, [c_void_p, POINTER(c_int)]),
+    "css_pq_ntotal": (c_int, [c_void_p, POINTER(c_int64)]),
+    "css_pq_add": (c_int, [c_void_p, c_void_p, c_int64]),
+    "css_pq_add_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "css_pq_add_codes": (c_int, [c_void_p, c_void_p, c_int64]),
+    "css_pq_get_codes": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
+    "css_pq_reconstruct": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
+    "css_pq_search": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "css_pq_search_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_pq_last_passes": (c_int, [c_void_p, POINTER(c_int)]),
     "css_index_maxsim_candidates": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                             POINTER(c_int64)]),
     "css_index_search_maxsim_pruned": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,

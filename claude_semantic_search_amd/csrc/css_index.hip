@@ -2948,6 +2948,7 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 #include "css_tokens_lists.h"
 #include "css_token_prune.h"
 #include "css_fde.h"
+#include "css_pq.h"
 #include "css_where.h"
 #include "css_sigterms.h"
 
@@ -6086,6 +6087,372 @@ int css_fde_encode_dev(css_fde* f, const int64_t* offsets_dev, const uint16_t* t
     CSS_REQUIRE(offsets_dev && out_dev && (tok_dev || total_tokens == 0), "css_fde_encode_dev: NULL buffer");
     DeviceGuard g(f->device);
     return fde_enqueue(f, offsets_dev, tok_dev, n, is_query, out_dev, buckets_out_dev, (hipStream_t)stream);
+}
+
+// ---- the product-quantized row store (css_pq.h; include/css_hip.h has the definition) ----
+}  // extern "C"
+
+// The store: the bf16 codebooks, the codes plane by plane (css_pq.h) and the workspaces of its calls.  An object of
+// its own like css_fde: `mu` serialises the calls, `stream` is the stream of the host forms, which are upload, launches,
+// copies back and ONE wait.  A `_dev` form leaves `ev` behind on the caller's stream and the next call waits for it, so
+// the store and the workspaces are never used by two streams at once.
+struct css_pq {
+    int d = 0, M = 0, device = 0, num_cus = 256, last_passes = 0;
+    int64_t ntotal = 0, cap = 0;   // rows, and the rows the planes of `codes` are apart
+    hipStream_t stream = nullptr;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    std::mutex mu;
+    DevBuf<uint4> cb;              // [M][256] centroids of 8 bf16
+    DevBuf<unsigned char> codes;   // [M / 4][cap][4]
+    DevBuf<float> x, col, pd, d_out;   // x: uploaded rows or queries, decoded rows
+    DevBuf<unsigned char> flat;        // row-major codes on their way in or out
+    DevBuf<uint4> qf;
+    DevBuf<int64_t> pi, i_out;
+    DevBuf<uint32_t> mask;
+};
+
+namespace {
+inline uint16_t pq_bf16_rne_host(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+// every enqueue of a call goes behind what a `_dev` form left on another stream ...
+int pq_begin(css_pq* f, hipStream_t st) {
+    if (f->pending) CSS_HIP_TRY(hipStreamWaitEvent(st, f->ev, 0));
+    return CSS_OK;
+}
+// ... a `_dev` form leaves its mark, and a host form ends with the ONE wait (also when it failed: its copies read the
+// caller's memory)
+int pq_end_dev(css_pq* f, int rc, hipStream_t st) {
+    if (hipEventRecord(f->ev, st) == hipSuccess) f->pending = true;
+    return rc;
+}
+int pq_end_host(css_pq* f, int rc) {
+    const hipError_t e = hipStreamSynchronize(f->stream);
+    if (e == hipSuccess) f->pending = false;
+    if (rc == CSS_OK && e != hipSuccess) return css::hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    return rc;
+}
+
+// room for `rows` rows, the stored ones kept: a larger allocation, every plane copied to its new distance
+int pq_reserve(css_pq* f, int64_t rows, hipStream_t st) {
+    if (rows <= f->cap) return CSS_OK;
+    const int64_t ncap = std::max((rows + 63) / 64 * 64, 2 * f->cap);
+    DevBuf<unsigned char> nb;
+    int rc;
+    if ((rc = nb.grow_exact((size_t)ncap * f->M, "hipMalloc(pq codes)")) != CSS_OK) return rc;
+    if (f->ntotal)
+        CSS_HIP_TRY(hipMemcpy2DAsync(nb.p, (size_t)ncap * 4, f->codes.p, (size_t)f->cap * 4, (size_t)f->ntotal * 4, (size_t)f->M / 4,
+                                     hipMemcpyDeviceToDevice, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));   // (the old planes are freed when `nb` goes)
+    f->codes.swap(nb);
+    f->cap = ncap;
+    return CSS_OK;
+}
+
+// n fp32 rows on the device encoded behind the stored ones (room reserved by the caller)
+int pq_encode_enqueue(css_pq* f, const float* x_dev, int64_t n, hipStream_t st) {
+    ProfScope ps("pq_encode", st);
+    hipLaunchKernelGGL(k_pq_encode, dim3((unsigned)((n + kPqEncRows - 1) / kPqEncRows), (unsigned)((f->M + kPqEncSubq - 1) / kPqEncSubq)),
+                       dim3(256), 0, st, x_dev, n, f->M, (const uint4*)f->cb.p, f->codes.p, f->cap, f->ntotal);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// The search of nq raw fp32 queries on the device: their fragments, then per pass of 16 queries the score columns
+// (k_pq_scores), the top-k by slices (k_sparse_topk_cols) and ONE part merge into D_dev / I_dev [nq][k].
+int pq_search_enqueue(css_pq* f, const float* q_dev, int nq, int k, const uint32_t* mask_dev, float* D_dev, int64_t* I_dev,
+                      hipStream_t st) {
+    const int64_t n = f->ntotal;
+    f->last_passes = 0;
+    if (n == 0) {
+        const int total = nq * k;
+        hipLaunchKernelGGL(k_sparse_pad, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, D_dev, I_dev, total);
+        CSS_LAUNCH_CHECK();
+        return CSS_OK;
+    }
+    int rc;
+    const int KS = f->M / 4, passes = (nq + 15) / 16, gmax = std::min(nq, 16);
+    const int64_t slice = sparse_topk_slice(n);
+    const int parts = (int)((n + slice - 1) / slice);
+    if ((rc = f->qf.grow((size_t)passes * KS * 64)) != CSS_OK) return rc;
+    if ((rc = f->col.grow((size_t)n * gmax)) != CSS_OK) return rc;
+    if ((rc = f->pd.grow((size_t)parts * gmax * k)) != CSS_OK) return rc;
+    if ((rc = f->pi.grow((size_t)parts * gmax * k)) != CSS_OK) return rc;
+    // the largest row tile that still gives every CU two blocks: 16 / G codebook bytes are read per code byte
+    int G = 1;
+    for (int c : {8, 4, 2})
+        if ((n + 256 * c - 1) / (256 * c) >= 2ll * f->num_cus) {
+            G = c;
+            break;
+        }
+    void (*fn)(const PqScoreArgs) = G == 8 ? k_pq_scores<8> : G == 4 ? k_pq_scores<4> : G == 2 ? k_pq_scores<2> : k_pq_scores<1>;
+    if ((rc = css::ensure_dynamic_lds((const void*)fn, kPqSliceBytes, f->device)) != CSS_OK) return rc;
+    {
+        const int64_t total = (int64_t)passes * KS * 64;
+        hipLaunchKernelGGL(k_pq_queries, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, q_dev, nq, f->d, f->qf.p, total);
+        CSS_LAUNCH_CHECK();
+    }
+    const unsigned grid = (unsigned)((n + 256 * G - 1) / (256 * G));
+    for (int p = 0; p < passes; ++p) {
+        const int ng = std::min(16, nq - 16 * p);
+        PqScoreArgs a{f->codes.p, f->cb.p, f->qf.p + (size_t)p * KS * 64, mask_dev, f->col.p, n, f->cap, f->M, ng};
+        void* args[] = {&a};
+        {
+            ProfScope ps("pq_scores", st);
+            CSS_HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid), dim3(64 * kWaves), args, kPqSliceBytes, st));
+        }
+        {
+            ProfScope ps("sparse_topk", st);
+            hipLaunchKernelGGL(k_sparse_topk_cols, dim3((unsigned)parts, (unsigned)ng), dim3(256), 0, st, (const float*)f->col.p, n,
+                               slice, mask_dev, k, (int64_t)0, f->pd.p, f->pi.p);
+            CSS_LAUNCH_CHECK();
+        }
+        if ((rc = merge_parts(f->pd.p, f->pi.p, parts, (int64_t)ng * k, (int64_t)ng * k, ng, k, CSS_METRIC_IP,
+                              D_dev + (size_t)16 * p * k, I_dev + (size_t)16 * p * k, f->device, st, "css_pq_search")) != CSS_OK)
+            return rc;
+        ++f->last_passes;
+    }
+    return CSS_OK;
+}
+
+int pq_add_check(const char* fn, const css_pq* f, int64_t n) {
+    CSS_REQUIRE(f, "%s: NULL store", fn);
+    CSS_REQUIRE(n >= 0, "%s: n < 0", fn);
+    CSS_REQUIRE(f->ntotal + n < 0xFFFFFFFFll, "%s: %lld rows exceed the 32-bit row numbers of the lists", fn, (long long)(f->ntotal + n));
+    return CSS_OK;
+}
+int pq_search_check(const char* fn, const css_pq* f, int64_t nq, int k) {
+    CSS_REQUIRE(f, "%s: NULL store", fn);
+    CSS_REQUIRE(nq >= 1 && nq <= CSS_PQ_MAX_QUERIES, "%s: nq=%lld outside [1, %d]", fn, (long long)nq, CSS_PQ_MAX_QUERIES);
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "%s: k=%d outside [1, %d]", fn, k, CSS_KERNEL_MAX_K);
+    return CSS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int css_pq_create(int d, const float* codebooks_host, int device, css_pq** out) {
+    CSS_REQUIRE(out != nullptr, "css_pq_create: out is NULL");
+    CSS_REQUIRE(d >= 32 && d <= 8192 && d % 32 == 0, "css_pq_create: d=%d must be a multiple of 32 in [32, 8192]", d);
+    CSS_REQUIRE(codebooks_host, "css_pq_create: codebooks is NULL");
+    const int M = d / 8;
+    std::vector<uint16_t> cb;
+    try {
+        cb.resize((size_t)M * 256 * 8);
+    } catch (const std::bad_alloc&) {
+        css::set_error("css_pq_create: out of host memory");
+        return CSS_ERR_OOM;
+    }
+    for (size_t e = 0; e < cb.size(); ++e) {
+        const float v = codebooks_host[e];
+        const uint16_t h = std::isfinite(v) ? pq_bf16_rne_host(v) : 0;
+        CSS_REQUIRE(std::isfinite(v) && bf16_finite(h), "css_pq_create: component %d of centroid %d of codebooks[%d] is %s", (int)(e % 8),
+                    (int)(e / 8 % 256), (int)(e / 2048), std::isnan(v) ? "NaN" : std::isinf(v) ? "infinite" : "infinite once rounded to bf16");
+        cb[e] = h;
+    }
+    int rc = css::check_device(device);
+    if (rc != CSS_OK) return rc;
+    DeviceGuard g(device);
+    std::unique_ptr<css_pq> f(new css_pq());
+    f->d = d, f->M = M, f->device = device;
+    hipDeviceProp_t p;
+    if (hipGetDeviceProperties(&p, device) == hipSuccess) f->num_cus = p.multiProcessorCount;
+    if ((rc = f->cb.grow_exact((size_t)M * 256, "hipMalloc(pq codebooks)")) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpy(f->cb.p, cb.data(), cb.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    CSS_HIP_TRY(hipEventCreateWithFlags(&f->ev, hipEventDisableTiming));
+    *out = f.release();
+    return CSS_OK;
+}
+
+int css_pq_free(css_pq* f) {
+    if (!f) return CSS_OK;
+    DeviceGuard g(f->device);
+    if (f->pending) (void)hipEventSynchronize(f->ev);
+    if (f->stream) {
+        (void)hipStreamSynchronize(f->stream);
+        (void)hipStreamDestroy(f->stream);
+    }
+    if (f->ev) (void)hipEventDestroy(f->ev);
+    delete f;   // (the DevBufs free inside the guard)
+    return CSS_OK;
+}
+
+int css_pq_dim(const css_pq* f, int* dim_out) {
+    CSS_REQUIRE(f && dim_out, "css_pq_dim: NULL argument");
+    *dim_out = f->d;
+    return CSS_OK;
+}
+
+int css_pq_ntotal(css_pq* f, int64_t* ntotal_out) {
+    CSS_REQUIRE(f && ntotal_out, "css_pq_ntotal: NULL argument");
+    std::lock_guard<std::mutex> lk(f->mu);
+    *ntotal_out = f->ntotal;
+    return CSS_OK;
+}
+
+int css_pq_last_passes(css_pq* f, int* passes_out) {
+    CSS_REQUIRE(f && passes_out, "css_pq_last_passes: NULL argument");
+    std::lock_guard<std::mutex> lk(f->mu);
+    *passes_out = f->last_passes;
+    return CSS_OK;
+}
+
+int css_pq_add(css_pq* f, const float* x_host, int64_t n) {
+    int rc = pq_add_check("css_pq_add", f, n);
+    if (rc != CSS_OK || n == 0) return rc;
+    CSS_REQUIRE(x_host, "css_pq_add: x is NULL");
+    for (int64_t e = 0; e < n * f->d; ++e)
+        CSS_REQUIRE(std::isfinite(x_host[e]), "css_pq_add: component %lld of row %lld is %s", (long long)(e % f->d), (long long)(e / f->d),
+                    std::isnan(x_host[e]) ? "NaN" : "infinite");
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    if ((rc = pq_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = pq_reserve(f, f->ntotal + n, st)) != CSS_OK) return rc;
+    // in chunks of at most 2^17 rows through one upload buffer (the stream keeps copy and kernel in order)
+    const int64_t chunk = std::min<int64_t>(n, 1 << 17);
+    if ((rc = f->x.grow((size_t)chunk * f->d)) != CSS_OK) return rc;
+    const int64_t before = f->ntotal;
+    rc = [&]() -> int {
+        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+            const int64_t m = std::min(chunk, n - r0);
+            CSS_HIP_TRY(hipMemcpyAsync(f->x.p, x_host + (size_t)r0 * f->d, (size_t)m * f->d * sizeof(float), hipMemcpyHostToDevice, st));
+            const int rc2 = pq_encode_enqueue(f, f->x.p, m, st);
+            if (rc2 != CSS_OK) return rc2;
+            f->ntotal += m;
+        }
+        return CSS_OK;
+    }();
+    rc = pq_end_host(f, rc);
+    if (rc != CSS_OK) f->ntotal = before;
+    return rc;
+}
+
+int css_pq_add_dev(css_pq* f, const float* x_dev, int64_t n, void* stream) {
+    int rc = pq_add_check("css_pq_add_dev", f, n);
+    if (rc != CSS_OK || n == 0) return rc;
+    CSS_REQUIRE(x_dev, "css_pq_add_dev: x is NULL");
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if ((rc = pq_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = pq_reserve(f, f->ntotal + n, st)) != CSS_OK) return rc;
+    rc = pq_encode_enqueue(f, x_dev, n, st);
+    if (rc == CSS_OK) f->ntotal += n;
+    return pq_end_dev(f, rc, st);
+}
+
+int css_pq_add_codes(css_pq* f, const uint8_t* codes_host, int64_t n) {
+    int rc = pq_add_check("css_pq_add_codes", f, n);
+    if (rc != CSS_OK || n == 0) return rc;
+    CSS_REQUIRE(codes_host, "css_pq_add_codes: codes is NULL");
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    if ((rc = pq_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = pq_reserve(f, f->ntotal + n, st)) != CSS_OK) return rc;
+    if ((rc = f->flat.grow((size_t)n * f->M)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        CSS_HIP_TRY(hipMemcpyAsync(f->flat.p, codes_host, (size_t)n * f->M, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_pq_codes_move<true>, dim3((unsigned)((n * f->M + 255) / 256)), dim3(256), 0, st, f->flat.p, n, f->M,
+                           f->codes.p, f->cap, f->ntotal);
+        CSS_LAUNCH_CHECK();
+        return CSS_OK;
+    }();
+    rc = pq_end_host(f, rc);
+    if (rc == CSS_OK) f->ntotal += n;
+    return rc;
+}
+
+int css_pq_get_codes(css_pq* f, int64_t row0, int64_t n, uint8_t* codes_out_host) {
+    CSS_REQUIRE(f && codes_out_host, "css_pq_get_codes: NULL argument");
+    std::lock_guard<std::mutex> lk(f->mu);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && row0 + n <= f->ntotal, "css_pq_get_codes: rows [%lld, %lld) outside [0, %lld)", (long long)row0,
+                (long long)(row0 + n), (long long)f->ntotal);
+    if (n == 0) return CSS_OK;
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    int rc;
+    if ((rc = pq_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = f->flat.grow((size_t)n * f->M)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        hipLaunchKernelGGL(k_pq_codes_move<false>, dim3((unsigned)((n * f->M + 255) / 256)), dim3(256), 0, st, f->flat.p, n, f->M,
+                           f->codes.p, f->cap, row0);
+        CSS_LAUNCH_CHECK();
+        CSS_HIP_TRY(hipMemcpyAsync(codes_out_host, f->flat.p, (size_t)n * f->M, hipMemcpyDeviceToHost, st));
+        return CSS_OK;
+    }();
+    return pq_end_host(f, rc);
+}
+
+int css_pq_reconstruct(css_pq* f, int64_t row0, int64_t n, float* x_out_host) {
+    CSS_REQUIRE(f && x_out_host, "css_pq_reconstruct: NULL argument");
+    std::lock_guard<std::mutex> lk(f->mu);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && row0 + n <= f->ntotal, "css_pq_reconstruct: rows [%lld, %lld) outside [0, %lld)", (long long)row0,
+                (long long)(row0 + n), (long long)f->ntotal);
+    if (n == 0) return CSS_OK;
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    int rc;
+    if ((rc = pq_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = f->x.grow((size_t)n * f->d)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        ProfScope ps("pq_decode", st);
+        hipLaunchKernelGGL(k_pq_decode, dim3((unsigned)((n * f->M + 255) / 256)), dim3(256), 0, st, (const unsigned char*)f->codes.p,
+                           f->cap, row0, n, f->M, (const uint4*)f->cb.p, f->x.p);
+        CSS_LAUNCH_CHECK();
+        CSS_HIP_TRY(hipMemcpyAsync(x_out_host, f->x.p, (size_t)n * f->d * sizeof(float), hipMemcpyDeviceToHost, st));
+        return CSS_OK;
+    }();
+    return pq_end_host(f, rc);
+}
+
+int css_pq_search(css_pq* f, const float* q_host, int64_t nq, int k, const uint32_t* allow_bits_host, float* D_host, int64_t* I_host) {
+    int rc = pq_search_check("css_pq_search", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_host && D_host && I_host, "css_pq_search: NULL buffer");
+    for (int64_t e = 0; e < nq * f->d; ++e) {
+        const float v = q_host[e];
+        CSS_REQUIRE(std::isfinite(v) && bf16_finite(pq_bf16_rne_host(v)), "css_pq_search: component %lld of query %lld is %s",
+                    (long long)(e % f->d), (long long)(e / f->d), std::isnan(v) ? "NaN" : std::isinf(v) ? "infinite" : "infinite once rounded to bf16");
+    }
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    const size_t words = (size_t)((f->ntotal + 31) / 32), no = (size_t)nq * k;
+    const bool masked = allow_bits_host != nullptr && f->ntotal > 0;
+    if ((rc = pq_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = f->x.grow((size_t)nq * f->d)) != CSS_OK) return rc;
+    if ((rc = f->d_out.grow(no)) != CSS_OK) return rc;
+    if ((rc = f->i_out.grow(no)) != CSS_OK) return rc;
+    if (masked && (rc = f->mask.grow(words)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        CSS_HIP_TRY(hipMemcpyAsync(f->x.p, q_host, (size_t)nq * f->d * sizeof(float), hipMemcpyHostToDevice, st));
+        if (masked) CSS_HIP_TRY(hipMemcpyAsync(f->mask.p, allow_bits_host, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        const int rc2 = pq_search_enqueue(f, f->x.p, (int)nq, k, masked ? f->mask.p : nullptr, f->d_out.p, f->i_out.p, st);
+        if (rc2 != CSS_OK) return rc2;
+        CSS_HIP_TRY(hipMemcpyAsync(D_host, f->d_out.p, no * sizeof(float), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipMemcpyAsync(I_host, f->i_out.p, no * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        return CSS_OK;
+    }();
+    return pq_end_host(f, rc);
+}
+
+int css_pq_search_dev(css_pq* f, const float* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, float* D_dev, int64_t* I_dev,
+                      void* stream) {
+    int rc = pq_search_check("css_pq_search_dev", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_dev && D_dev && I_dev, "css_pq_search_dev: NULL buffer");
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if ((rc = pq_begin(f, st)) != CSS_OK) return rc;
+    rc = pq_search_enqueue(f, q_dev, (int)nq, k, f->ntotal > 0 ? allow_bits_dev : nullptr, D_dev, I_dev, st);
+    return pq_end_dev(f, rc, st);
 }
 
 namespace {

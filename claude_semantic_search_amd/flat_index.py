@@ -2148,6 +2148,23 @@ class IndexFlat:
             raise ValueError(f"search_fde: the encoder's dim={fde.dim} is not the index's d={self.d}")
         return self.search_rerank_maxsim(fde.encode_queries(q_mats), q_mats, k, fetch, normalize=False, allow=allow)
 
+    def search_fde_pq(self, fde, pq_index, q_mats, k: int, fetch: int):
+        """``search_fde`` with the encodings kept as product-quantizer codes: the pool of ``fetch <= 128`` rows per
+        query is ``pq_index.search(fde.encode_queries(q_mats), fetch)`` (a ``pq.IndexPQ`` whose row ``r`` is the
+        encoding of this index's row ``r``), re-ranked by ``maxsim_ids_batch`` on this index's token matrices and
+        ranked as ``search_rerank_maxsim`` ranks (``search_rerank_maxsim_numpy``): the same four results, ``S`` the
+        score on the codes.  This index need not hold the encodings at all."""
+        if fde.dim != pq_index.d:
+            raise ValueError(f"search_fde_pq: the encoder's dim={fde.dim} is not the store's d={pq_index.d}")
+        k, fetch = int(k), int(fetch)
+        if not 1 <= k <= fetch:
+            raise ValueError(f"search_fde_pq: k={k} outside [1, fetch={fetch}]")
+        S0, I0 = pq_index.search(fde.encode_queries(q_mats), fetch)
+        base = getattr(self, "_id_base", 0)
+        ids = np.where(I0 >= 0, I0 + base, -1)
+        D, I, S, R = search_rerank_maxsim_numpy(S0, ids, self.maxsim_ids_batch(q_mats, ids), k)
+        return D, I, S, R
+
     # -- candidate generation for MaxSim on the codes (PLAID) ----------------------
     def _prune_codec(self, what: str) -> None:
         if self.token_codec_bits == 0:

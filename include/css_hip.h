@@ -681,6 +681,51 @@ int css_fde_encode(css_fde* f, const int64_t* offsets_host /* [n + 1], from 0 */
 int css_fde_encode_dev(css_fde* f, const int64_t* offsets_dev, const uint16_t* tok_dev, int64_t n, int64_t total_tokens,
                        int is_query, float* out_dev, uint8_t* buckets_out_dev /* or NULL */, void* stream);
 
+/* The product-quantized row store: dense rows kept as codes only and scanned exhaustively, with a score defined in
+ * bits.  Not an approximate index structure: every row is scored by every search.  A store is an object of its own.
+ *  - Parameters.  d a multiple of 32 in [32, 8192]; sub-vectors of 8 components, M = d / 8 sub-quantizers of 256
+ *    centroids each; a stored row is M bytes (an fp32 row is 32 times that).
+ *  - Codebooks, the caller's (the library has no trainer): float32 [M, 256, 8], rounded to bf16 (round to nearest
+ *    even) at css_pq_create; a NaN or infinite component, or one that rounds to an infinite bf16, is CSS_ERR_INVALID.
+ *    cent[m][c][j] below is the bf16 value widened to fp32.
+ *  - Encode.  code[m] = argmin_c sum_j (x[8 m + j] - cent[m][c][j])^2 over the fp32 input x: every difference, product
+ *    and sum one IEEE fp32 operation (no contraction), the sum starting at 0 with j ascending, compared with a strict
+ *    "less" for c ascending, so ties go to the lower c.  A float32 restatement (pq.ProductQuantizer.encode_numpy)
+ *    gives the same bytes.
+ *  - Score (inner product only).  s(q, r) = sum_i bf16_rne(q_i) * cent[i / 8][code_r[i / 8]][i % 8]: bf16 operands, fp32
+ *    accumulation on v_mfma_f32_16x16x32_bf16 with the K steps of 32 components ascending and ONE accumulator per
+ *    (query, row) across the whole of d.  The bits of a score do not depend on the other queries of the call, on the
+ *    row's position, on the number of rows or on the form (host or _dev).  Where all products and partial sums are
+ *    representable the score is the float64 value; otherwise it lies within gamma_d * sum_i |q_i x_i| of it,
+ *    gamma_d = d 2^-24 / (1 - d 2^-24).
+ *  - Search.  D / I [nq, k], 1 <= k <= 128, best first, ties to the lower id (= row number); allow_bits as in
+ *    css_index_search_masked (NULL: every row); fewer than k rows: padding D = -FLT_MAX, I = -1.  The queries are
+ *    scored 16 at a time, each such pass one scan of the codes: css_pq_last_passes reports ceil(nq / 16) of the last
+ *    search (0 on an empty store).  A query component that is NaN, infinite or rounds to an infinite bf16 is
+ *    CSS_ERR_INVALID in the host form, checked before anything is written.
+ *  - css_pq_add encodes fp32 rows [n, d] behind the stored ones (non-finite components: CSS_ERR_INVALID, the message
+ *    names row and component); css_pq_add_codes appends rows that are codes already, [n, M] bytes row-major, the form
+ *    css_pq_get_codes returns; css_pq_reconstruct writes rows [row0, row0 + n) decoded to fp32 [n, d].
+ *  - The _dev forms take device pointers, enqueue on `stream` without a wait or a check of the contents (x_dev 16-byte
+ *    aligned); css_pq_add_dev waits for the stream only when the store has to grow.  Calls on one store are serialised,
+ *    and a call on another stream goes behind the _dev call before it. */
+#define CSS_PQ_MAX_QUERIES 65536
+typedef struct css_pq css_pq;
+int css_pq_create(int d, const float* codebooks_host /* [d / 8, 256, 8] */, int device, css_pq** out);
+int css_pq_free(css_pq* pq);
+int css_pq_dim(const css_pq* pq, int* dim_out);
+int css_pq_ntotal(css_pq* pq, int64_t* ntotal_out);
+int css_pq_add(css_pq* pq, const float* x_host /* [n, d] */, int64_t n);
+int css_pq_add_dev(css_pq* pq, const float* x_dev, int64_t n, void* stream);
+int css_pq_add_codes(css_pq* pq, const uint8_t* codes_host /* [n, d / 8] */, int64_t n);
+int css_pq_get_codes(css_pq* pq, int64_t row0, int64_t n, uint8_t* codes_out_host /* [n, d / 8] */);
+int css_pq_reconstruct(css_pq* pq, int64_t row0, int64_t n, float* x_out_host /* [n, d] */);
+int css_pq_search(css_pq* pq, const float* q_host /* [nq, d] */, int64_t nq, int k, const uint32_t* allow_bits_host,
+                  float* D_host /* [nq, k] */, int64_t* I_host /* [nq, k] */);
+int css_pq_search_dev(css_pq* pq, const float* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, float* D_dev,
+                      int64_t* I_dev, void* stream);
+int css_pq_last_passes(css_pq* pq, int* passes_out);
+
 /* Significant terms (Elasticsearch's significant_terms aggregation, the keyword side of BERTopic): which terms set a
  * selection of rows apart from a background -- "what is in this cluster / this project / these hits".  Everything is
  * read from the term lists above; the rows' values play no part.  T = the leading rows that have lists.
