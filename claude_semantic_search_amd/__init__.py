@@ -54,6 +54,7 @@ _LAZY = {
     "IndexPQ": ".pq",
     "ProductQuantizer": ".pq",
     "train_product_quantizer": ".pq",
+    "IndexBinaryFlat": ".binary",
     "SparseEncoder": ".sparse_encoder",
     "SparseVector": ".sparse_encoder",
     "sparse_dot_numpy": ".sparse_encoder",

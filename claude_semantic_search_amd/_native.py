@@ -208,6 +208,20 @@ PROTOTYPES = {
     "css_pq_search": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "css_pq_search_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "css_pq_last_passes": (c_int, [c_void_p, POINTER(c_int)]),
+    "css_bin_create": (c_int, [c_int, c_int, POINTER(c_void_p)]),
+    "css_bin_free": (c_int, [c_void_p]),
+    "css_bin_dim": (c_int, [c_void_p, POINTER(c_int)]),
+    "css_bin_ntotal": (c_int, [c_void_p, POINTER(c_int64)]),
+    "css_bin_add": (c_int, [c_void_p, c_void_p, c_int64]),
+    "css_bin_add_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "css_bin_add_codes": (c_int, [c_void_p, c_void_p, c_int64]),
+    "css_bin_get_codes": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
+    "css_bin_search": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "css_bin_search_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_bin_search_codes": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "css_bin_search_codes_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_bin_last_passes": (c_int, [c_void_p, POINTER(c_int)]),
+    "css_bin_set_waves": (c_int, [c_void_p, c_int]),
     "css_index_maxsim_candidates": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                             POINTER(c_int64)]),
     "css_index_search_maxsim_pruned": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,

@@ -2949,6 +2949,7 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 #include "css_token_prune.h"
 #include "css_fde.h"
 #include "css_pq.h"
+#include "css_binary.h"
 #include "css_where.h"
 #include "css_sigterms.h"
 
@@ -6453,6 +6454,376 @@ int css_pq_search_dev(css_pq* f, const float* q_dev, int64_t nq, int k, const ui
     if ((rc = pq_begin(f, st)) != CSS_OK) return rc;
     rc = pq_search_enqueue(f, q_dev, (int)nq, k, f->ntotal > 0 ? allow_bits_dev : nullptr, D_dev, I_dev, st);
     return pq_end_dev(f, rc, st);
+}
+
+// ---- the binary row store (css_binary.h; include/css_hip.h has the definition) ----
+}  // extern "C"
+
+// The store: the codes in word planes (css_binary.h) and the workspaces of its calls.  An object of its own with the
+// frame of css_pq: `mu` serialises the calls, the host forms are upload, launches, copies back and ONE wait on `stream`,
+// a `_dev` form leaves `ev` behind on the caller's stream and the next call waits for it.
+struct css_bin {
+    int d = 0, W = 0, device = 0, num_cus = 256, last_passes = 0, waves = 0;   // waves: css_bin_set_waves, 0 = automatic
+    int64_t ntotal = 0, cap = 0;   // rows, and the rows the planes of `codes` are apart
+    hipStream_t stream = nullptr;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    std::mutex mu;
+    DevBuf<unsigned> codes;        // [W][cap]
+    DevBuf<unsigned> qc, flat;     // the queries' planes [W][capq]; row-major codes on their way in or out
+    DevBuf<float> x;               // uploaded float rows or queries
+    DevBuf<unsigned long long> keys;   // [waves][queries of a pass][k]
+    DevBuf<int32_t> d_out;
+    DevBuf<int64_t> i_out;
+    DevBuf<uint32_t> mask;
+};
+
+namespace {
+int bin_begin(css_bin* f, hipStream_t st) {
+    if (f->pending) CSS_HIP_TRY(hipStreamWaitEvent(st, f->ev, 0));
+    return CSS_OK;
+}
+int bin_end_dev(css_bin* f, int rc, hipStream_t st) {
+    if (hipEventRecord(f->ev, st) == hipSuccess) f->pending = true;
+    return rc;
+}
+int bin_end_host(css_bin* f, int rc) {   // the ONE wait (also of a failed call: its copies read the caller's memory)
+    const hipError_t e = hipStreamSynchronize(f->stream);
+    if (e == hipSuccess) f->pending = false;
+    if (rc == CSS_OK && e != hipSuccess) return css::hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    return rc;
+}
+
+// room for `rows` rows, the stored ones kept: a larger allocation, every plane copied to its new distance
+int bin_reserve(css_bin* f, int64_t rows, hipStream_t st) {
+    if (rows <= f->cap) return CSS_OK;
+    const int64_t ncap = std::max((rows + 63) / 64 * 64, 2 * f->cap);
+    DevBuf<unsigned> nb;
+    int rc;
+    if ((rc = nb.grow_exact((size_t)ncap * f->W, "hipMalloc(binary codes)")) != CSS_OK) return rc;
+    if (f->ntotal)
+        CSS_HIP_TRY(hipMemcpy2DAsync(nb.p, (size_t)ncap * 4, f->codes.p, (size_t)f->cap * 4, (size_t)f->ntotal * 4, (size_t)f->W,
+                                     hipMemcpyDeviceToDevice, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));   // (the old planes are freed when `nb` goes)
+    f->codes.swap(nb);
+    f->cap = ncap;
+    return CSS_OK;
+}
+
+// n fp32 rows on the device binarized into rows first .. of the planes `codes` that lie `cap` rows apart
+int bin_encode_enqueue(const css_bin* f, const float* x_dev, int64_t n, unsigned* codes, int64_t cap, int64_t first, hipStream_t st) {
+    ProfScope ps("bin_encode", st);
+    const int64_t waves = n * ((f->d + 63) / 64);
+    hipLaunchKernelGGL(k_bin_encode, dim3((unsigned)std::min<int64_t>((waves + 3) / 4, 1 << 20)), dim3(256), 0, st, x_dev, n, f->d, codes,
+                       cap, first);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// row-major codes [n][W] on the device into (IN) or out of the planes, as above
+template <bool IN>
+int bin_move_enqueue(const css_bin* f, unsigned* flat_dev, int64_t n, unsigned* codes, int64_t cap, int64_t first, hipStream_t st) {
+    hipLaunchKernelGGL(k_bin_codes_move<IN>, dim3((unsigned)((n * f->W + 255) / 256)), dim3(256), 0, st, flat_dev, n, f->W, codes, cap,
+                       first);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// the planes of nq queries: room in f->qc, and the rows its planes lie apart
+int bin_query_room(css_bin* f, int nq, int* capq) {
+    *capq = (nq + 15) / 16 * 16;
+    return f->qc.grow((size_t)*capq * f->W);
+}
+
+// The search of the nq query codes in f->qc: per pass of 16 queries ONE scan that selects (k_bin_topk, a part per wave)
+// and the exact merge of the parts (k_bin_merge) into D_dev / I_dev [nq][k].
+int bin_search_enqueue(css_bin* f, int nq, int capq, int k, const uint32_t* mask_dev, int32_t* D_dev, int64_t* I_dev, hipStream_t st) {
+    const int64_t n = f->ntotal;
+    f->last_passes = 0;
+    if (n == 0) {
+        const int64_t total = (int64_t)nq * k;
+        hipLaunchKernelGGL(k_bin_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, total);
+        CSS_LAUNCH_CHECK();
+        return CSS_OK;
+    }
+    int rc;
+    const int passes = (nq + 15) / 16, gmax = std::min(nq, 16);
+    const int64_t steps = (n + 255) / 256;
+    // (the first pass has the most queries, so the most waves' worth of keys)
+    if ((rc = f->keys.grow((size_t)std::min<int64_t>(steps, f->waves > 0 ? f->waves : f->num_cus * 32) * gmax * k)) != CSS_OK) return rc;
+    for (int p = 0; p < passes; ++p) {
+        const int ng = std::min(16, nq - 16 * p);
+        void (*fn)(const BinTopkArgs) = ng == 1 ? k_bin_topk<1> : ng <= 4 ? k_bin_topk<4> : k_bin_topk<16>;
+        const size_t lds = (size_t)kBinWavesPerBlock * ng * k * sizeof(unsigned long long);
+        if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)fn, lds, f->device)) != CSS_OK) return rc;
+        // resident: the blocks of 4 waves a CU holds at the class's registers (8 / 4 / 2 waves per SIMD at 1 / 4 / 16
+        // queries) and at its lists' LDS (64 KB per block at k = 128 and 16 queries, of 160 KB); fewer waves when there
+        // are fewer steps of 256 rows; or what the caller set
+        const int by_regs = ng == 1 ? 8 : ng <= 4 ? 4 : 2, by_lds = (int)std::max<size_t>(1, 160 * 1024 / lds);
+        const int64_t want = std::min<int64_t>(steps, f->waves > 0 ? f->waves
+                                                                   : (int64_t)f->num_cus * std::min(by_regs, by_lds) * kBinWavesPerBlock);
+        const int64_t per = (steps + want - 1) / want * 256;
+        const int nwaves = (int)((n + per - 1) / per);
+        BinTopkArgs a{f->codes.p, f->qc.p, mask_dev, f->keys.p, n, f->cap, per, f->W, capq, 16 * p, ng, k, nwaves};
+        void* args[] = {&a};
+        {
+            ProfScope ps("bin_topk", st);
+            CSS_HIP_TRY(hipLaunchKernel((const void*)fn, dim3((unsigned)((nwaves + kBinWavesPerBlock - 1) / kBinWavesPerBlock)),
+                                        dim3(64 * kBinWavesPerBlock), args, lds, st));
+        }
+        {
+            ProfScope ps("bin_merge", st);
+            hipLaunchKernelGGL(k_bin_merge, dim3((unsigned)ng), dim3(kBinMergeThreads), (size_t)(f->d + 1) * sizeof(unsigned), st,
+                               (const unsigned long long*)f->keys.p, nwaves, ng, k, f->d, D_dev + (size_t)16 * p * k,
+                               I_dev + (size_t)16 * p * k);
+            CSS_LAUNCH_CHECK();
+        }
+        ++f->last_passes;
+    }
+    return CSS_OK;
+}
+
+int bin_add_check(const char* fn, const css_bin* f, int64_t n) {
+    CSS_REQUIRE(f, "%s: NULL store", fn);
+    CSS_REQUIRE(n >= 0, "%s: n < 0", fn);
+    CSS_REQUIRE(f->ntotal + n < 0xFFFFFFFFll, "%s: %lld rows exceed the 32-bit row numbers of the keys", fn, (long long)(f->ntotal + n));
+    return CSS_OK;
+}
+int bin_search_check(const char* fn, const css_bin* f, int64_t nq, int k) {
+    CSS_REQUIRE(f, "%s: NULL store", fn);
+    CSS_REQUIRE(nq >= 1 && nq <= CSS_BIN_MAX_QUERIES, "%s: nq=%lld outside [1, %d]", fn, (long long)nq, CSS_BIN_MAX_QUERIES);
+    CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "%s: k=%d outside [1, %d]", fn, k, CSS_KERNEL_MAX_K);
+    return CSS_OK;
+}
+int bin_finite_check(const char* fn, const char* what, const float* x, int64_t n, int d) {
+    for (int64_t e = 0; e < n * d; ++e)
+        CSS_REQUIRE(std::isfinite(x[e]), "%s: component %lld of %s %lld is %s", fn, (long long)(e % d), what, (long long)(e / d),
+                    std::isnan(x[e]) ? "NaN" : "infinite");
+    return CSS_OK;
+}
+
+// The host forms of the search: the queries as fp32 (`q_host`) or as codes (`qc_host`), uploaded and brought into planes,
+// the search, the copies back and the ONE wait.
+int bin_search_host(css_bin* f, const float* q_host, const uint8_t* qc_host, int64_t nq, int k, const uint32_t* allow_bits_host,
+                    int32_t* D_host, int64_t* I_host) {
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    const size_t words = (size_t)((f->ntotal + 31) / 32), no = (size_t)nq * k;
+    const bool masked = allow_bits_host != nullptr && f->ntotal > 0;
+    int rc, capq;
+    if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = bin_query_room(f, (int)nq, &capq)) != CSS_OK) return rc;
+    if (q_host && (rc = f->x.grow((size_t)nq * f->d)) != CSS_OK) return rc;
+    if (qc_host && (rc = f->flat.grow((size_t)nq * f->W)) != CSS_OK) return rc;
+    if ((rc = f->d_out.grow(no)) != CSS_OK) return rc;
+    if ((rc = f->i_out.grow(no)) != CSS_OK) return rc;
+    if (masked && (rc = f->mask.grow(words)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        int rc2;
+        if (q_host) {
+            CSS_HIP_TRY(hipMemcpyAsync(f->x.p, q_host, (size_t)nq * f->d * sizeof(float), hipMemcpyHostToDevice, st));
+            rc2 = bin_encode_enqueue(f, f->x.p, nq, f->qc.p, capq, 0, st);
+        } else {
+            CSS_HIP_TRY(hipMemcpyAsync(f->flat.p, qc_host, (size_t)nq * f->W * 4, hipMemcpyHostToDevice, st));
+            rc2 = bin_move_enqueue<true>(f, f->flat.p, nq, f->qc.p, capq, 0, st);
+        }
+        if (rc2 != CSS_OK) return rc2;
+        if (masked) CSS_HIP_TRY(hipMemcpyAsync(f->mask.p, allow_bits_host, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if ((rc2 = bin_search_enqueue(f, (int)nq, capq, k, masked ? f->mask.p : nullptr, f->d_out.p, f->i_out.p, st)) != CSS_OK) return rc2;
+        CSS_HIP_TRY(hipMemcpyAsync(D_host, f->d_out.p, no * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipMemcpyAsync(I_host, f->i_out.p, no * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        return CSS_OK;
+    }();
+    return bin_end_host(f, rc);
+}
+
+// The `_dev` forms: fp32 queries (`q_dev`) or codes (`qc_dev`) on the device, everything enqueued on the caller's stream.
+int bin_search_dev(css_bin* f, const float* q_dev, const uint8_t* qc_dev, int64_t nq, int k, const uint32_t* allow_bits_dev,
+                   int32_t* D_dev, int64_t* I_dev, hipStream_t st) {
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    int rc, capq;
+    if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = bin_query_room(f, (int)nq, &capq)) != CSS_OK) return rc;
+    rc = q_dev ? bin_encode_enqueue(f, q_dev, nq, f->qc.p, capq, 0, st)
+               : bin_move_enqueue<true>(f, reinterpret_cast<unsigned*>(const_cast<uint8_t*>(qc_dev)), nq, f->qc.p, capq, 0, st);
+    if (rc == CSS_OK) rc = bin_search_enqueue(f, (int)nq, capq, k, f->ntotal > 0 ? allow_bits_dev : nullptr, D_dev, I_dev, st);
+    return bin_end_dev(f, rc, st);
+}
+}  // namespace
+
+extern "C" {
+
+int css_bin_create(int d, int device, css_bin** out) {
+    CSS_REQUIRE(out != nullptr, "css_bin_create: out is NULL");
+    CSS_REQUIRE(d >= 32 && d <= 8192 && d % 32 == 0, "css_bin_create: d=%d must be a multiple of 32 in [32, 8192]", d);
+    int rc = css::check_device(device);
+    if (rc != CSS_OK) return rc;
+    DeviceGuard g(device);
+    std::unique_ptr<css_bin> f(new css_bin());
+    f->d = d, f->W = d / 32, f->device = device;
+    hipDeviceProp_t p;
+    if (hipGetDeviceProperties(&p, device) == hipSuccess) f->num_cus = p.multiProcessorCount;
+    CSS_HIP_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    CSS_HIP_TRY(hipEventCreateWithFlags(&f->ev, hipEventDisableTiming));
+    *out = f.release();
+    return CSS_OK;
+}
+
+int css_bin_free(css_bin* f) {
+    if (!f) return CSS_OK;
+    DeviceGuard g(f->device);
+    if (f->pending) (void)hipEventSynchronize(f->ev);
+    if (f->stream) {
+        (void)hipStreamSynchronize(f->stream);
+        (void)hipStreamDestroy(f->stream);
+    }
+    if (f->ev) (void)hipEventDestroy(f->ev);
+    delete f;   // (the DevBufs free inside the guard)
+    return CSS_OK;
+}
+
+int css_bin_dim(const css_bin* f, int* dim_out) {
+    CSS_REQUIRE(f && dim_out, "css_bin_dim: NULL argument");
+    *dim_out = f->d;
+    return CSS_OK;
+}
+
+int css_bin_ntotal(css_bin* f, int64_t* ntotal_out) {
+    CSS_REQUIRE(f && ntotal_out, "css_bin_ntotal: NULL argument");
+    std::lock_guard<std::mutex> lk(f->mu);
+    *ntotal_out = f->ntotal;
+    return CSS_OK;
+}
+
+int css_bin_last_passes(css_bin* f, int* passes_out) {
+    CSS_REQUIRE(f && passes_out, "css_bin_last_passes: NULL argument");
+    std::lock_guard<std::mutex> lk(f->mu);
+    *passes_out = f->last_passes;
+    return CSS_OK;
+}
+
+int css_bin_set_waves(css_bin* f, int waves) {
+    CSS_REQUIRE(f, "css_bin_set_waves: NULL store");
+    CSS_REQUIRE(waves >= 0 && waves <= CSS_BIN_MAX_WAVES, "css_bin_set_waves: waves=%d outside [0, %d]", waves, CSS_BIN_MAX_WAVES);
+    std::lock_guard<std::mutex> lk(f->mu);
+    f->waves = waves;
+    return CSS_OK;
+}
+
+int css_bin_add(css_bin* f, const float* x_host, int64_t n) {
+    int rc = bin_add_check("css_bin_add", f, n);
+    if (rc != CSS_OK || n == 0) return rc;
+    CSS_REQUIRE(x_host, "css_bin_add: x is NULL");
+    if ((rc = bin_finite_check("css_bin_add", "row", x_host, n, f->d)) != CSS_OK) return rc;
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = bin_reserve(f, f->ntotal + n, st)) != CSS_OK) return rc;
+    // in chunks of at most 2^17 rows through one upload buffer (the stream keeps copy and kernel in order)
+    const int64_t chunk = std::min<int64_t>(n, 1 << 17);
+    if ((rc = f->x.grow((size_t)chunk * f->d)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+            const int64_t m = std::min(chunk, n - r0);
+            CSS_HIP_TRY(hipMemcpyAsync(f->x.p, x_host + (size_t)r0 * f->d, (size_t)m * f->d * sizeof(float), hipMemcpyHostToDevice, st));
+            const int rc2 = bin_encode_enqueue(f, f->x.p, m, f->codes.p, f->cap, f->ntotal + r0, st);
+            if (rc2 != CSS_OK) return rc2;
+        }
+        return CSS_OK;
+    }();
+    rc = bin_end_host(f, rc);
+    if (rc == CSS_OK) f->ntotal += n;
+    return rc;
+}
+
+int css_bin_add_dev(css_bin* f, const float* x_dev, int64_t n, void* stream) {
+    int rc = bin_add_check("css_bin_add_dev", f, n);
+    if (rc != CSS_OK || n == 0) return rc;
+    CSS_REQUIRE(x_dev, "css_bin_add_dev: x is NULL");
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = bin_reserve(f, f->ntotal + n, st)) != CSS_OK) return rc;
+    rc = bin_encode_enqueue(f, x_dev, n, f->codes.p, f->cap, f->ntotal, st);
+    if (rc == CSS_OK) f->ntotal += n;
+    return bin_end_dev(f, rc, st);
+}
+
+int css_bin_add_codes(css_bin* f, const uint8_t* codes_host, int64_t n) {
+    int rc = bin_add_check("css_bin_add_codes", f, n);
+    if (rc != CSS_OK || n == 0) return rc;
+    CSS_REQUIRE(codes_host, "css_bin_add_codes: codes is NULL");
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = bin_reserve(f, f->ntotal + n, st)) != CSS_OK) return rc;
+    if ((rc = f->flat.grow((size_t)n * f->W)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        CSS_HIP_TRY(hipMemcpyAsync(f->flat.p, codes_host, (size_t)n * f->W * 4, hipMemcpyHostToDevice, st));
+        return bin_move_enqueue<true>(f, f->flat.p, n, f->codes.p, f->cap, f->ntotal, st);
+    }();
+    rc = bin_end_host(f, rc);
+    if (rc == CSS_OK) f->ntotal += n;
+    return rc;
+}
+
+int css_bin_get_codes(css_bin* f, int64_t row0, int64_t n, uint8_t* codes_out_host) {
+    CSS_REQUIRE(f && codes_out_host, "css_bin_get_codes: NULL argument");
+    std::lock_guard<std::mutex> lk(f->mu);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && row0 + n <= f->ntotal, "css_bin_get_codes: rows [%lld, %lld) outside [0, %lld)", (long long)row0,
+                (long long)(row0 + n), (long long)f->ntotal);
+    if (n == 0) return CSS_OK;
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    int rc;
+    if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = f->flat.grow((size_t)n * f->W)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        const int rc2 = bin_move_enqueue<false>(f, f->flat.p, n, f->codes.p, f->cap, row0, st);
+        if (rc2 != CSS_OK) return rc2;
+        CSS_HIP_TRY(hipMemcpyAsync(codes_out_host, f->flat.p, (size_t)n * f->W * 4, hipMemcpyDeviceToHost, st));
+        return CSS_OK;
+    }();
+    return bin_end_host(f, rc);
+}
+
+int css_bin_search(css_bin* f, const float* q_host, int64_t nq, int k, const uint32_t* allow_bits_host, int32_t* D_host,
+                   int64_t* I_host) {
+    int rc = bin_search_check("css_bin_search", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_host && D_host && I_host, "css_bin_search: NULL buffer");
+    if ((rc = bin_finite_check("css_bin_search", "query", q_host, nq, f->d)) != CSS_OK) return rc;
+    return bin_search_host(f, q_host, nullptr, nq, k, allow_bits_host, D_host, I_host);
+}
+
+int css_bin_search_codes(css_bin* f, const uint8_t* q_codes_host, int64_t nq, int k, const uint32_t* allow_bits_host,
+                         int32_t* D_host, int64_t* I_host) {
+    const int rc = bin_search_check("css_bin_search_codes", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_codes_host && D_host && I_host, "css_bin_search_codes: NULL buffer");
+    return bin_search_host(f, nullptr, q_codes_host, nq, k, allow_bits_host, D_host, I_host);
+}
+
+int css_bin_search_dev(css_bin* f, const float* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev,
+                       int64_t* I_dev, void* stream) {
+    const int rc = bin_search_check("css_bin_search_dev", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_dev && D_dev && I_dev, "css_bin_search_dev: NULL buffer");
+    return bin_search_dev(f, q_dev, nullptr, nq, k, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
+}
+
+int css_bin_search_codes_dev(css_bin* f, const uint8_t* q_codes_dev, int64_t nq, int k, const uint32_t* allow_bits_dev,
+                             int32_t* D_dev, int64_t* I_dev, void* stream) {
+    const int rc = bin_search_check("css_bin_search_codes_dev", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_codes_dev && D_dev && I_dev, "css_bin_search_codes_dev: NULL buffer");
+    CSS_REQUIRE((reinterpret_cast<uintptr_t>(q_codes_dev) & 3u) == 0, "css_bin_search_codes_dev: q_codes is not 4-byte aligned");
+    return bin_search_dev(f, nullptr, q_codes_dev, nq, k, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
 }
 
 namespace {

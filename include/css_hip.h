@@ -726,6 +726,55 @@ int css_pq_search_dev(css_pq* pq, const float* q_dev, int64_t nq, int k, const u
                       int64_t* I_dev, void* stream);
 int css_pq_last_passes(css_pq* pq, int* passes_out);
 
+/* The binary row store: dense rows kept as one sign bit per component and scanned exhaustively by Hamming distance
+ * (faiss.IndexBinaryFlat, the "ubinary" precision of sentence-transformers).  Training-free; every row is scored by
+ * every search; the whole result is integers.  A store is an object of its own.
+ *  - Row width.  d a multiple of 32 in [32, 8192]; a row is d / 8 bytes.
+ *  - Code.  Bit i of a row is x[i] > 0, so -0.0 and 0.0 give 0 (denormals above zero give 1; a NaN, which only the
+ *    _dev forms let through, gives 0).  At the ABI a row is uint8 [d / 8], exactly np.packbits(x > 0, axis=-1):
+ *    component 8 j + b is bit 7 - b of byte j.  Codes written by sentence-transformers or faiss go in unchanged.  The
+ *    layout in device memory is the library's business (word planes, csrc/css_binary.h).
+ *  - Distance.  h(q, r) = popcount(code_q xor code_r), an integer in [0, d].
+ *  - Search.  D int32 [nq, k], I int64 [nq, k], 1 <= k <= 128, 1 <= nq <= CSS_BIN_MAX_QUERIES; smallest distance first,
+ *    ties to the lower id (= row number); allow_bits as in css_index_search_masked (NULL: every row); fewer than k rows:
+ *    padding D = INT32_MAX, I = -1.  The bytes of the answer do not depend on the grid, on the other queries of the
+ *    call or on the form (host or _dev).
+ *  - Passes.  The queries are scanned 16 per pass over the codes, scan and selection in one kernel (no score column
+ *    exists): css_bin_last_passes reports ceil(nq / 16) of the last search, 0 on an empty store.
+ *  - css_bin_add / css_bin_add_dev binarize fp32 rows [n, d] on the device behind the stored ones; css_bin_add_codes
+ *    appends rows that are codes already, the form css_bin_get_codes returns for rows [row0, row0 + n).
+ *    css_bin_search / _dev binarize fp32 queries with the same kernel; css_bin_search_codes / _codes_dev take query
+ *    codes (the faiss form).
+ *  - Refusals.  In the host forms a NaN or infinite component of a float row or query is CSS_ERR_INVALID, the message
+ *    names row (or query) and component.  Arguments are checked before anything is enqueued.
+ *  - The _dev forms take device pointers (floats and codes 4-byte aligned), enqueue on `stream` without a wait or a
+ *    check of the contents; css_bin_add_dev waits for the stream only when the store has to grow.  Calls on one store
+ *    are serialised, and a call on another stream goes behind the _dev call before it.
+ *  - css_bin_set_waves: the number of scanning waves (= row ranges, each one part of the selection) of the next
+ *    searches, 0 = automatic (resident, every SIMD busy); at most CSS_BIN_MAX_WAVES, and never more than there are steps
+ *    of 256 rows.  A test and tuning hook: no answer depends on it. */
+#define CSS_BIN_MAX_QUERIES 65536
+#define CSS_BIN_MAX_WAVES 16384
+typedef struct css_bin css_bin;
+int css_bin_create(int d, int device, css_bin** out);
+int css_bin_free(css_bin* b);
+int css_bin_dim(const css_bin* b, int* dim_out);
+int css_bin_ntotal(css_bin* b, int64_t* ntotal_out);
+int css_bin_add(css_bin* b, const float* x_host /* [n, d] */, int64_t n);
+int css_bin_add_dev(css_bin* b, const float* x_dev, int64_t n, void* stream);
+int css_bin_add_codes(css_bin* b, const uint8_t* codes_host /* [n, d / 8] */, int64_t n);
+int css_bin_get_codes(css_bin* b, int64_t row0, int64_t n, uint8_t* codes_out_host /* [n, d / 8] */);
+int css_bin_search(css_bin* b, const float* q_host /* [nq, d] */, int64_t nq, int k, const uint32_t* allow_bits_host,
+                   int32_t* D_host /* [nq, k] */, int64_t* I_host /* [nq, k] */);
+int css_bin_search_dev(css_bin* b, const float* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev,
+                       int64_t* I_dev, void* stream);
+int css_bin_search_codes(css_bin* b, const uint8_t* q_codes_host /* [nq, d / 8] */, int64_t nq, int k,
+                         const uint32_t* allow_bits_host, int32_t* D_host, int64_t* I_host);
+int css_bin_search_codes_dev(css_bin* b, const uint8_t* q_codes_dev, int64_t nq, int k, const uint32_t* allow_bits_dev,
+                             int32_t* D_dev, int64_t* I_dev, void* stream);
+int css_bin_last_passes(css_bin* b, int* passes_out);
+int css_bin_set_waves(css_bin* b, int waves);
+
 /* Significant terms (Elasticsearch's significant_terms aggregation, the keyword side of BERTopic): which terms set a
  * selection of rows apart from a background -- "what is in this cluster / this project / these hits".  Everything is
  * read from the term lists above; the rows' values play no part.  T = the leading rows that have lists.
