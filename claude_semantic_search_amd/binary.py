@@ -55,6 +55,42 @@ def search_numpy(dist, k: int, allow=None) -> Tuple[np.ndarray, np.ndarray]:
     return D, I
 
 
+PAD_SCORE = np.iinfo(np.int32).min
+
+
+def quantize_queries_numpy(q) -> Tuple[np.ndarray, np.ndarray]:
+    """The int8 form of float queries ``[nq, d]`` as ``search_asym_float`` makes it, in float32 throughout:
+    ``a = max |q_i|``; all zeros if ``a`` is below the smallest normal float, else ``rint((q_i / a) * 127)``.  Returns
+    ``(q8 int8 [nq, d], a float32 [nq])``; ``a * score / 127`` estimates the float query's product with the signs."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    a = np.abs(q).max(axis=1) if q.shape[1] else np.zeros(q.shape[0], np.float32)
+    live = a.view(np.int32) >= 0x00800000
+    q8 = np.zeros(q.shape, dtype=np.int8)
+    with np.errstate(under="ignore"):
+        q8[live] = np.rint((q[live] / a[live, None]) * np.float32(127)).astype(np.int8)
+    return q8, a
+
+
+def asym_scores_numpy(q8, codes) -> np.ndarray:
+    """``sum_i q8_i (2 b_i - 1)`` of int8 queries ``[nq, d]`` against codes ``[n, d / 8]``: int64 ``[nq, n]``."""
+    signs = 2 * np.unpackbits(np.asarray(codes, dtype=np.uint8), axis=-1).astype(np.int32) - 1
+    return (np.asarray(q8, dtype=np.int8).astype(np.int32) @ signs.T).astype(np.int64)   # (|s| <= 2^20: exact in int32)
+
+
+def search_asym_numpy(scores, k: int, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The ranking of ``IndexBinaryFlat.search_asym`` from scores ``[nq, n]``: largest first, ties to the lower id, the
+    rows outside ``allow`` left out, padded with ``INT32_MIN`` / ``-1``."""
+    s = np.asarray(scores)
+    nq, n = s.shape
+    D = np.full((nq, k), PAD_SCORE, dtype=np.int32)
+    I = np.full((nq, k), -1, dtype=np.int64)
+    ids = np.arange(n) if allow is None else np.flatnonzero(np.asarray(allow))
+    for b in range(nq):
+        order = ids[np.lexsort((ids, -s[b, ids]))][:k]
+        D[b, :order.size], I[b, :order.size] = s[b, order], order
+    return D, I
+
+
 class IndexBinaryFlat:
     """The store on the GPU, in the faiss shape: ``add`` / ``search`` take codes (uint8 ``[n, d / 8]``),
     ``add_float`` / ``search_float`` take float32 rows and binarize them on the device.  Rows are numbered in the order
@@ -221,3 +257,35 @@ class IndexBinaryFlat:
 
         dev = self._tensor(codes, torch.uint8, self.code_size, "search_codes_dev", 1)
         return self._search_dev(nat.lib().css_bin_search_codes_dev, codes, dev, k, allow)
+
+    # ---- asymmetric searches: the query keeps its magnitudes at int8, the rows stay bits
+    def _queries_i8(self, q8, what: str) -> np.ndarray:
+        a = np.ascontiguousarray(q8)
+        if a.dtype != np.int8 or a.ndim != 2 or a.shape[1] != self.d:
+            raise ValueError(f"{what}: queries must be int8 [nq, {self.d}], got {a.dtype} {a.shape}")
+        return a
+
+    def search_asym(self, q8, k: int, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``(D int32, I int64)``, each ``[nq, k]``: the ``k`` rows with the largest ``sum_i q8_i (2 b_i - 1)`` for each
+        int8 query ``[nq, d]`` (every int8 value allowed), largest first, ties to the lower id; ``allow`` as in
+        ``search``.  Padding: ``INT32_MIN`` / ``-1``.  ``1 <= k <= 128``."""
+        return self._search_host(nat.lib().css_bin_search_asym_i8, self._queries_i8(q8, "search_asym"), k, allow)
+
+    def search_asym_float(self, q, k: int, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``search_asym`` of float32 queries ``[nq, d]``, quantized on the device as ``quantize_queries_numpy`` does."""
+        return self._search_host(nat.lib().css_bin_search_asym, self._rows(q, "search_asym_float"), k, allow)
+
+    def search_asym_dev(self, q, k: int, allow=None):
+        """``search_asym_float`` with a float32 torch tensor ``[nq, d]`` on the store's device, enqueued on torch's
+        current stream (``css_bin_search_asym_dev``): ``(D, I)`` as torch tensors there, the bytes of the host form."""
+        import torch
+
+        dev = self._tensor(q, torch.float32, self.d, "search_asym_dev", 1)
+        return self._search_dev(nat.lib().css_bin_search_asym_dev, q, dev, k, allow)
+
+    def search_asym_i8_dev(self, q8, k: int, allow=None):
+        """``search_asym`` with an int8 torch tensor ``[nq, d]`` on the store's device (``css_bin_search_asym_i8_dev``)."""
+        import torch
+
+        dev = self._tensor(q8, torch.int8, self.d, "search_asym_i8_dev", 1)
+        return self._search_dev(nat.lib().css_bin_search_asym_i8_dev, q8, dev, k, allow)

@@ -33,12 +33,15 @@
 // gives T = the distance of the k-th best and the number of keys below it; every key below T is taken; of the keys AT T
 // the lowest ids are wanted, and since part p's rows all precede part p + 1's and a part is sorted, those are the first
 // ones in (part, position) order: a count per part chunk, one prefix sum, one more walk.  A bitonic sort of the <= 128
-// taken keys orders them; the key splits into int32 distance and int64 id (INT32_MAX / -1 for padding).
+// taken keys orders them; the key splits into int32 distance and int64 id (INT32_MAX / -1 for padding).  The asymmetric
+// scores (below) span 2^21 + 1 values: k_bin_merge<true> finds T in two digit rounds over the same histogram.
 #pragma once
 
 constexpr unsigned long long kBinPad = ~0ull;
 constexpr int kBinWavesPerBlock = 4;
 constexpr int kBinMergeThreads = 1024;   // one block per query: its loads of the parts' keys are all the parallelism there is
+constexpr int kBinAsymBias = 1 << 20;    // an asymmetric score s, |s| <= 128 * 8192, has the key high word kBinAsymBias - s
+constexpr int kBinWideBins = (2 * kBinAsymBias >> 10) + 1;   // k_bin_merge<true>: the bins of its first digit round
 typedef const __attribute__((address_space(4))) unsigned* bin_const_words;
 
 // bit b of the byte at every byte position <-> bit 7 - b: packbits bytes (as a little-endian word) <-> plane word
@@ -97,16 +100,18 @@ __device__ __forceinline__ void bin_list_insert(unsigned long long* L, int k, un
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 }
 
-// The lane's rows row4 .. row4 + 3 at distances h[0 .. 3] (`ok`: which of them may enter) offered to the list Lq.  Every
+// The lane's rows row4 .. row4 + R - 1 at distances h[0 .. R) (`ok`: which of them may enter) offered to the list Lq
+// (R = 4 in the Hamming scan, 16 in the asymmetric one).  Every
 // lane puts forward its best pending row (the smallest distance, the lower row among equals); ONE ballot against the
 // threshold finds the lanes with a hit -- after warm-up there is none and the wave moves on; otherwise the lowest such
 // lane's row goes in and the ballot is taken again under the new threshold.
-__device__ __forceinline__ void bin_offer(unsigned long long* Lq, int k, const int (&h)[4], unsigned row4, unsigned ok, int bits,
+template <int R>
+__device__ __forceinline__ void bin_offer(unsigned long long* Lq, int k, const int (&h)[R], unsigned row4, unsigned ok, int bits,
                                           int lane) {
     for (;;) {
         unsigned best = 0xFFFFFFFFu, bj = 0u;
 #pragma unroll
-        for (unsigned j = 0; j < 4; ++j) {
+        for (unsigned j = 0; j < (unsigned)R; ++j) {
             const unsigned hj = (ok >> j) & 1u ? (unsigned)h[j] : 0xFFFFFFFFu;
             if (hj < best) best = hj, bj = j;
         }
@@ -187,45 +192,68 @@ __device__ __forceinline__ unsigned bin_block_prefix(unsigned* buf, unsigned min
     return ex;
 }
 
+// The bin of hist [nb] at which the running count reaches `want`, and the count below it, into *sT / *sBelow (left as
+// they are when the bins hold fewer than `want`); every thread owns a run of bins.  Ends with a barrier.
+__device__ __forceinline__ void bin_hist_kth(const unsigned* hist, int nb, unsigned* pre, unsigned want, int tid, unsigned* sT,
+                                             unsigned* sBelow) {
+    const int per = (nb + kBinMergeThreads - 1) / kBinMergeThreads, b0 = min(nb, tid * per), b1 = min(nb, b0 + per);
+    unsigned mine = 0u;
+    for (int b = b0; b < b1; ++b) mine += hist[b];
+    unsigned c = bin_block_prefix(pre, mine, tid);
+    if (c < want && c + mine >= want)   // (exactly one thread, if any)
+        for (int b = b0; b < b1; ++b) {
+            if (c + hist[b] >= want) {
+                *sT = (unsigned)b, *sBelow = c;
+                break;
+            }
+            c += hist[b];
+        }
+    __syncthreads();
+}
+
 // keys [nparts][nq][k] -> D / I [k] of query blockIdx.x: the k smallest keys, ascending.  Part p's rows all precede
-// part p + 1's.  Dynamic LDS: d + 1 histogram bins.
+// part p + 1's.  `top` is the largest high word a key can have.  !WIDE (Hamming: top = d): one histogram of top + 1 bins.
+// WIDE (the asymmetric scores, top = 2^21): the threshold in two digit rounds over the high word, its upper 11 bits
+// (2049 bins), then the lower 10 among the keys that share the upper digit of the k-th; D is 2^20 - the high word and
+// the padding INT32_MIN.  Dynamic LDS: (WIDE ? kBinWideBins : top + 1) bins.
+template <bool WIDE>
 __global__ __launch_bounds__(kBinMergeThreads) void k_bin_merge(const unsigned long long* __restrict__ keys, int nparts, int nq, int k,
-                                                                int d, int32_t* __restrict__ D, int64_t* __restrict__ I) {
-    extern __shared__ unsigned bin_hist[];   // [d + 1]
+                                                                int top, int32_t* __restrict__ D, int64_t* __restrict__ I) {
+    extern __shared__ unsigned bin_hist[];
     __shared__ unsigned pre[kBinMergeThreads];
     __shared__ unsigned long long sel[CSS_KERNEL_MAX_K];
-    __shared__ unsigned sT, sBelow, sCnt;
+    __shared__ unsigned sT, sBelow, sT2, sBelow2, sCnt;
     const int tid = threadIdx.x, q = blockIdx.x;
     const unsigned long long* kq = keys + (size_t)q * k;       // part p, entry j: kq[p * stride + j]
     const size_t stride = (size_t)nq * k;
-    for (int i = tid; i <= d; i += kBinMergeThreads) bin_hist[i] = 0u;
+    const int shift = WIDE ? 10 : 0, nb = (top >> shift) + 1;
+    for (int i = tid; i < nb; i += kBinMergeThreads) bin_hist[i] = 0u;
     if (tid < CSS_KERNEL_MAX_K) sel[tid] = kBinPad;
-    if (tid == 0) sT = (unsigned)d + 1u, sBelow = 0u, sCnt = 0u;   // fewer than k keys in all: everything is "below"
+    if (tid == 0) sT = (unsigned)nb, sBelow = 0u, sT2 = 0u, sBelow2 = 0u, sCnt = 0u;   // fewer than k keys in all: everything is "below"
     __syncthreads();
     const int total = nparts * k;
     for (int e = tid; e < total; e += kBinMergeThreads) {
         const int p = e / k, j = e - p * k;
         const unsigned long long key = kq[(size_t)p * stride + j];
-        if (key != kBinPad) atomicAdd(&bin_hist[(unsigned)(key >> 32)], 1u);
+        if (key != kBinPad) atomicAdd(&bin_hist[(unsigned)(key >> 32) >> shift], 1u);
     }
     __syncthreads();
-    // T = the first distance at which the running count reaches k; every thread owns a run of bins
-    {
-        const int nb = (d + 1 + kBinMergeThreads - 1) / kBinMergeThreads, b0 = tid * nb, b1 = min(d + 1, b0 + nb);
-        unsigned mine = 0u;
-        for (int b = b0; b < b1; ++b) mine += bin_hist[b];
-        unsigned c = bin_block_prefix(pre, mine, tid);
-        if (c < (unsigned)k && c + mine >= (unsigned)k)   // (exactly one thread, if any)
-            for (int b = b0; b < b1; ++b) {
-                if (c + bin_hist[b] >= (unsigned)k) {
-                    sT = (unsigned)b, sBelow = c;
-                    break;
-                }
-                c += bin_hist[b];
-            }
+    // T = the first distance at which the running count reaches k
+    bin_hist_kth(bin_hist, nb, pre, (unsigned)k, tid, &sT, &sBelow);
+    if (WIDE && sT < (unsigned)nb) {   // (block uniform) the second digit, among the keys whose first is sT
+        const unsigned T1 = sT;
+        for (int i = tid; i < 1024; i += kBinMergeThreads) bin_hist[i] = 0u;
+        __syncthreads();
+        for (int e = tid; e < total; e += kBinMergeThreads) {
+            const int p = e / k, j = e - p * k;
+            const unsigned long long key = kq[(size_t)p * stride + j];
+            if (key != kBinPad && (unsigned)(key >> 32) >> 10 == T1) atomicAdd(&bin_hist[(unsigned)(key >> 32) & 1023u], 1u);
+        }
+        __syncthreads();
+        bin_hist_kth(bin_hist, 1024, pre, (unsigned)k - sBelow, tid, &sT2, &sBelow2);
     }
-    __syncthreads();
-    const unsigned T = sT, below = sBelow, need = T <= (unsigned)d ? (unsigned)k - below : 0u;
+    const bool found = sT < (unsigned)nb;
+    const unsigned T = found ? (sT << shift | sT2) : 0xFFFFFFFFu, below = sBelow + sBelow2, need = found ? (unsigned)k - below : 0u;
     // every key below T, in any order, into sel[0 .. below)
     for (int e = tid; e < total; e += kBinMergeThreads) {
         const int p = e / k, j = e - p * k;
@@ -264,15 +292,187 @@ __global__ __launch_bounds__(kBinMergeThreads) void k_bin_merge(const unsigned l
         }
     if (tid < k) {
         const unsigned long long key = sel[tid];
-        D[(size_t)q * k + tid] = key == kBinPad ? INT32_MAX : (int32_t)(key >> 32);
+        const int32_t hw = (int32_t)(key >> 32);
+        D[(size_t)q * k + tid] = key == kBinPad ? (WIDE ? INT32_MIN : INT32_MAX) : WIDE ? kBinAsymBias - hw : hw;
         I[(size_t)q * k + tid] = key == kBinPad ? (int64_t)-1 : (int64_t)(key & 0xFFFFFFFFull);
     }
 }
 
-// the answer of a search of an empty store
-__global__ void k_bin_pad(int32_t* __restrict__ D, int64_t* __restrict__ I, int64_t total) {
+// the answer of a search of an empty store (`pad`: INT32_MAX for distances, INT32_MIN for scores)
+__global__ void k_bin_pad(int32_t* __restrict__ D, int64_t* __restrict__ I, int64_t total, int32_t pad) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total) return;
-    D[t] = INT32_MAX;
+    D[t] = pad;
     I[t] = -1;
+}
+
+// ------------------------------------------------------------------ asymmetric scoring: int8 queries against the bit codes
+// s(q, r) = sum_i q_i (2 b_i - 1), the query at int8 and the row as it lies in the planes (include/css_hip.h).  It is a GEMM
+// with one operand stored as bits, so it runs on v_mfma_i32_16x16x64_i8: the rows are the M side, decoded to 0 / 1 bytes ONCE
+// per row and K step (not once per row and query), the pass's 16 queries are the N side, and the kernel accumulates
+// t = sum_i q_i b_i; s = 2 t - sum_i q_i is applied per query in the epilogue.
+//
+// The tile.  A wave step covers 64 rows x 16 queries.  Lane (m = l & 15, g = l >> 4) loads ONE uint4 of plane 4 T + g at
+// rows base + 4 m .. + 3 (256 contiguous bytes per plane, four planes per wave instruction).  Word j of the four is the A
+// operand of row tile j (M index m = row base + 4 m + j), and feeds two K steps h = 0, 1.  A dot product does not care
+// about the order of K, so the lane takes the 16 bits that are cheapest to spread: VGPR i of K step h is
+// (word >> (4 h + i)) & 0x01010101, i.e. byte b holds bit 4 h + i + 8 b -- two VALU instructions per 4 bytes, 15 per word.
+// k_bin_asym_prep lays the queries out to match: the B operand of K step (T, h) holds in lane (n, g), VGPR i, byte b the
+// component 32 (4 T + g) + 4 h + i + 8 b of query n.  The MFMA leaves lane (n, G) with tile j's rows 4 G + r, r = 0 .. 3:
+// over the four tiles the 16 CONSECUTIVE rows base + 16 G + 4 r + j of ONE query, the shape bin_offer works on.
+//
+// Queries: up to d = 1024 the pass's fragments stay in registers (16 uint4 = 64 VGPRs); above that the block stages them
+// in LDS once (16 d bytes) and every K step reads its fragment from there (QLDS).
+//
+// Selection: as in k_bin_topk, per wave and query one ascending list of k keys in LDS, key = (2^20 - s) << 32 | row, so
+// that the larger score and then the lower id come first.  Per step every lane compares the best of its 16 rows with ITS
+// query's threshold and one ballot finds the queries with a hit (after warm-up: none); only those run bin_offer, their
+// four lanes putting rows forward.  No block barrier in the scan.
+struct BinAsymArgs {
+    const unsigned* __restrict__ codes;      // [W][cap]
+    const uint4* __restrict__ qf;            // this pass's query fragments [2 ceil(W / 4)][64]
+    const int* __restrict__ qsum;            // this pass's sum_i q_i [16]
+    const uint32_t* __restrict__ mask;       // allow bits or null
+    unsigned long long* __restrict__ keys;   // [nwaves][nq][k]
+    int64_t n, cap, per;                     // per: the rows of a wave's range, a multiple of 64
+    int W, nq, k, nwaves;                    // nq: the queries of this pass, 1 .. 16
+};
+
+// fp32 (F32) or int8 queries [nq][d] -> fragments qf [capq / 16][2 ceil(W / 4)][64] uint4 and sums qsum [capq]; one wave
+// per query slot, the slots past nq give zeros.  F32: a = max |q_i| (on the bits: |x| orders like its pattern), the query
+// is all zeros if a is below the smallest normal, else q8_i = rint((q_i / a) * 127), the division and the product each
+// rounded once (numpy float32 says the same; a denormal quotient gives 0 flushed or not).
+template <bool F32>
+__global__ __launch_bounds__(256) void k_bin_asym_prep(const void* __restrict__ q, int nq, int capq, int d, uint4* __restrict__ qf,
+                                                       int* __restrict__ qsum) {
+    const int lane = threadIdx.x & 63, qi = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (qi >= capq) return;
+    const int nT = (d / 32 + 3) / 4, n = qi & 15;
+    const float* qx = static_cast<const float*>(q) + (size_t)qi * d;
+    const signed char* q8 = static_cast<const signed char*>(q) + (size_t)qi * d;
+    float a = 0.f;
+    if (F32 && qi < nq) {
+        int top = 0;
+        for (int i = lane; i < d; i += 64) top = max(top, __float_as_int(qx[i]) & 0x7FFFFFFF);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) top = max(top, __shfl_xor(top, o));
+        a = top >= 0x00800000 ? __int_as_float(top) : 0.f;
+    }
+    unsigned* out = reinterpret_cast<unsigned*>(qf + (size_t)(qi >> 4) * 2 * nT * 64);
+    int sum = 0;
+    // word o of the query's share of the fragments: K step t = 2 T + h, lane group g, VGPR i
+    for (int o = lane; o < 32 * nT; o += 64) {
+        const int i = o & 3, g = (o >> 2) & 3, t = o >> 4;
+        unsigned word = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int c = 32 * (4 * (t >> 1) + g) + 4 * (t & 1) + i + 8 * b;
+            int v = 0;
+            if (qi < nq && c < d) {
+                if (F32) v = a > 0.f ? (int)rintf(__fmul_rn(__fdiv_rn(qx[c], a), 127.f)) : 0;
+                else v = q8[c];
+            }
+            sum += v;
+            word |= (unsigned)(v & 0xFF) << (8 * b);
+        }
+        out[((size_t)t * 64 + 16 * g + n) * 4 + i] = word;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) qsum[qi] = sum;
+}
+
+typedef int bin_v4i __attribute__((ext_vector_type(4)));
+
+// one plane group: the lane's four words against the K steps' fragments b0, b1, into the four row tiles
+__device__ __forceinline__ void bin_asym_step(const uint4 cw, const bin_v4i b0, const bin_v4i b1, bin_v4i (&acc)[4]) {
+    const unsigned w[4] = {cw.x, cw.y, cw.z, cw.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        constexpr unsigned M = 0x01010101u;
+        const bin_v4i a0{(int)(w[j] & M), (int)(w[j] >> 1 & M), (int)(w[j] >> 2 & M), (int)(w[j] >> 3 & M)};
+        const bin_v4i a1{(int)(w[j] >> 4 & M), (int)(w[j] >> 5 & M), (int)(w[j] >> 6 & M), (int)(w[j] >> 7 & M)};
+        acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b0, acc[j], 0, 0, 0);
+        acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b1, acc[j], 0, 0, 0);
+    }
+}
+
+template <bool QLDS>
+__global__ __launch_bounds__(64 * kBinWavesPerBlock) void k_bin_asym_topk(const BinAsymArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long bin_lists[];   // (QLDS: the fragments, then) [waves][nq][k]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, k = a.k;
+    const int nT = (a.W + 3) / 4, nqf = QLDS ? 2 * nT * 64 : 0;
+    const bin_v4i* qs = reinterpret_cast<const bin_v4i*>(bin_lists);
+    bin_v4i qr[QLDS ? 1 : 16];
+    if (QLDS) {
+        uint4* dst = reinterpret_cast<uint4*>(bin_lists);
+        for (int i = threadIdx.x; i < nqf; i += blockDim.x) dst[i] = a.qf[i];
+        __syncthreads();   // (the only barrier: before the scan, and before any wave leaves)
+    } else {
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const uint4 v = t < 2 * nT ? a.qf[t * 64 + lane] : make_uint4(0u, 0u, 0u, 0u);
+            qr[t] = bin_v4i{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
+        }
+    }
+    const int part = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (part >= a.nwaves) return;
+    unsigned long long* L = bin_lists + 2 * (size_t)nqf + (size_t)wave * a.nq * k;
+    for (int i = lane; i < a.nq * k; i += 64) L[i] = kBinPad;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+
+    const int64_t lo = (int64_t)part * a.per, hi = min(a.n, lo + a.per);
+    const int n = lane & 15, g = lane >> 4;
+    const int qsum = n < a.nq ? a.qsum[n] : 0;
+    const unsigned long long* Ln = L + (size_t)min(n, a.nq - 1) * k;
+    for (int64_t base = lo; base < hi; base += 64) {
+        const int64_t row4 = base + 4 * n;   // a multiple of 4: with row4 < n <= cap the uint4 lies within the plane
+        const bool in = row4 < hi;
+        const unsigned* cp = a.codes + (size_t)g * a.cap + row4;
+        bin_v4i acc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = bin_v4i{0, 0, 0, 0};
+        if (QLDS) {
+            for (int T = 0; T < nT; ++T) {
+                const uint4 cw = in && 4 * T + g < a.W ? *reinterpret_cast<const uint4*>(cp + (size_t)4 * T * a.cap) : make_uint4(0u, 0u, 0u, 0u);
+                bin_asym_step(cw, qs[(2 * T) * 64 + lane], qs[(2 * T + 1) * 64 + lane], acc);
+            }
+        } else {
+#pragma unroll
+            for (int T = 0; T < 8; ++T)
+                if (T < nT) {   // (wave uniform; the fragments are indexed at compile time)
+                    const uint4 cw = in && 4 * T + g < a.W ? *reinterpret_cast<const uint4*>(cp + (size_t)4 * T * a.cap) : make_uint4(0u, 0u, 0u, 0u);
+                    bin_asym_step(cw, qr[QLDS ? 0 : 2 * T], qr[QLDS ? 0 : 2 * T + 1], acc);
+                }
+        }
+        // the lane's 16 rows row16 .. + 15 of query n: tile j, register r is row row16 + 4 r + j.  Their allow bits sit
+        // in one mask word (row16 is a multiple of 16); rows past the range and query slots past nq: none
+        const int64_t row16 = base + 16 * g;
+        int h[16];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) h[4 * r + j] = kBinAsymBias + qsum - 2 * acc[j][r];
+        unsigned ok = 0u;
+        if (row16 < hi && n < a.nq) {
+            const int64_t left = hi - row16;
+            ok = left >= 16 ? 0xFFFFu : (1u << left) - 1u;
+            if (a.mask != nullptr) ok &= a.mask[row16 >> 5] >> (row16 & 31);
+        }
+        unsigned best = 0xFFFFFFFFu;
+#pragma unroll
+        for (unsigned j = 0; j < 16; ++j)
+            if ((ok >> j) & 1u) best = min(best, (unsigned)h[j]);
+        // every lane against ITS query's threshold, on the high words alone: `<=` may send a query to bin_offer that then
+        // finds no hit (a tie in score with a higher row), never the other way
+        unsigned long long hits = __ballot(ok != 0u && best <= (unsigned)(Ln[k - 1] >> 32));
+        unsigned qm = (unsigned)(hits | hits >> 16 | hits >> 32 | hits >> 48) & 0xFFFFu;
+        while (qm) {   // (wave uniform)
+            const int q = __builtin_ctz(qm);
+            qm &= qm - 1u;
+            bin_offer(L + (size_t)q * k, k, h, (unsigned)row16, n == q ? ok : 0u, 22, lane);
+        }
+    }
+    unsigned long long* out = a.keys + (size_t)part * a.nq * k;
+    for (int i = lane; i < a.nq * k; i += 64) out[i] = L[i];
 }

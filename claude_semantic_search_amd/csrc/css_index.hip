@@ -6472,6 +6472,8 @@ struct css_bin {
     DevBuf<unsigned> codes;        // [W][cap]
     DevBuf<unsigned> qc, flat;     // the queries' planes [W][capq]; row-major codes on their way in or out
     DevBuf<float> x;               // uploaded float rows or queries
+    DevBuf<uint4> qfrag;           // the asymmetric searches' query fragments [passes][2 ceil(W / 4)][64]
+    DevBuf<int> qsum;              // and the sums of their int8 components [16 passes]
     DevBuf<unsigned long long> keys;   // [waves][queries of a pass][k]
     DevBuf<int32_t> d_out;
     DevBuf<int64_t> i_out;
@@ -6535,51 +6537,82 @@ int bin_query_room(css_bin* f, int nq, int* capq) {
     return f->qc.grow((size_t)*capq * f->W);
 }
 
-// The search of the nq query codes in f->qc: per pass of 16 queries ONE scan that selects (k_bin_topk, a part per wave)
-// and the exact merge of the parts (k_bin_merge) into D_dev / I_dev [nq][k].
-int bin_search_enqueue(css_bin* f, int nq, int capq, int k, const uint32_t* mask_dev, int32_t* D_dev, int64_t* I_dev, hipStream_t st) {
+// The search of the nq queries a call has prepared: per pass of 16 queries ONE scan that selects (a part per wave) and
+// the exact merge of the parts (k_bin_merge) into D_dev / I_dev [nq][k].  Hamming (!asym): the query codes in f->qc
+// [W][capq], k_bin_topk.  Asymmetric: the int8 fragments in f->qfrag / f->qsum, k_bin_asym_topk in steps of 64 rows.
+int bin_search_enqueue(css_bin* f, bool asym, int nq, int capq, int k, const uint32_t* mask_dev, int32_t* D_dev, int64_t* I_dev,
+                       hipStream_t st) {
     const int64_t n = f->ntotal;
     f->last_passes = 0;
     if (n == 0) {
         const int64_t total = (int64_t)nq * k;
-        hipLaunchKernelGGL(k_bin_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, total);
+        hipLaunchKernelGGL(k_bin_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, total,
+                           asym ? INT32_MIN : INT32_MAX);
         CSS_LAUNCH_CHECK();
         return CSS_OK;
     }
     int rc;
-    const int passes = (nq + 15) / 16, gmax = std::min(nq, 16);
-    const int64_t steps = (n + 255) / 256;
+    const int passes = (nq + 15) / 16, gmax = std::min(nq, 16), rows = asym ? 64 : 256, nT = (f->W + 3) / 4;
+    const int64_t steps = (n + rows - 1) / rows;
     // (the first pass has the most queries, so the most waves' worth of keys)
     if ((rc = f->keys.grow((size_t)std::min<int64_t>(steps, f->waves > 0 ? f->waves : f->num_cus * 32) * gmax * k)) != CSS_OK) return rc;
     for (int p = 0; p < passes; ++p) {
         const int ng = std::min(16, nq - 16 * p);
-        void (*fn)(const BinTopkArgs) = ng == 1 ? k_bin_topk<1> : ng <= 4 ? k_bin_topk<4> : k_bin_topk<16>;
-        const size_t lds = (size_t)kBinWavesPerBlock * ng * k * sizeof(unsigned long long);
-        if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds((const void*)fn, lds, f->device)) != CSS_OK) return rc;
-        // resident: the blocks of 4 waves a CU holds at the class's registers (8 / 4 / 2 waves per SIMD at 1 / 4 / 16
-        // queries) and at its lists' LDS (64 KB per block at k = 128 and 16 queries, of 160 KB); fewer waves when there
-        // are fewer steps of 256 rows; or what the caller set
-        const int by_regs = ng == 1 ? 8 : ng <= 4 ? 4 : 2, by_lds = (int)std::max<size_t>(1, 160 * 1024 / lds);
-        const int64_t want = std::min<int64_t>(steps, f->waves > 0 ? f->waves
-                                                                   : (int64_t)f->num_cus * std::min(by_regs, by_lds) * kBinWavesPerBlock);
-        const int64_t per = (steps + want - 1) / want * 256;
+        const bool qlds = asym && f->W > 32;   // the fragments of more than 1024 components do not fit the registers
+        const void* fn = !asym     ? (ng == 1 ? (const void*)k_bin_topk<1> : ng <= 4 ? (const void*)k_bin_topk<4> : (const void*)k_bin_topk<16>)
+                         : qlds    ? (const void*)k_bin_asym_topk<true>
+                                   : (const void*)k_bin_asym_topk<false>;
+        // the waves of a block: 4, or as many as have room for their lists beside the fragments a QLDS block stages
+        const size_t per_wave = (size_t)ng * k * sizeof(unsigned long long), fixed = qlds ? (size_t)2 * nT * 64 * sizeof(uint4) : 0;
+        const int wpb = (int)std::min<size_t>(kBinWavesPerBlock, (160 * 1024 - fixed) / per_wave);
+        const size_t lds = fixed + wpb * per_wave;
+        if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds(fn, lds, f->device)) != CSS_OK) return rc;
+        // resident: the blocks a CU holds at the class's registers (Hamming: 8 / 4 / 2 waves per SIMD at 1 / 4 / 16
+        // queries; asymmetric: 3 with the fragments in registers, else 4) and at its LDS (64 KB per block at k = 128 and 16 queries, of 160 KB);
+        // fewer waves when there are fewer steps; or what the caller set
+        const int by_regs = asym ? (qlds ? 4 : 3) : ng == 1 ? 8 : ng <= 4 ? 4 : 2, by_lds = (int)std::max<size_t>(1, 160 * 1024 / lds);
+        const int64_t want = std::min<int64_t>(steps, f->waves > 0 ? f->waves : (int64_t)f->num_cus * std::min(by_regs, by_lds) * wpb);
+        const int64_t per = (steps + want - 1) / want * rows;
         const int nwaves = (int)((n + per - 1) / per);
         BinTopkArgs a{f->codes.p, f->qc.p, mask_dev, f->keys.p, n, f->cap, per, f->W, capq, 16 * p, ng, k, nwaves};
-        void* args[] = {&a};
+        BinAsymArgs b{f->codes.p, f->qfrag.p + (size_t)p * 2 * nT * 64, f->qsum.p + 16 * p, mask_dev, f->keys.p, n, f->cap, per, f->W, ng, k,
+                      nwaves};
+        void* args[] = {asym ? (void*)&b : (void*)&a};
         {
-            ProfScope ps("bin_topk", st);
-            CSS_HIP_TRY(hipLaunchKernel((const void*)fn, dim3((unsigned)((nwaves + kBinWavesPerBlock - 1) / kBinWavesPerBlock)),
-                                        dim3(64 * kBinWavesPerBlock), args, lds, st));
+            ProfScope ps(asym ? "bin_asym_topk" : "bin_topk", st);
+            CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)((nwaves + wpb - 1) / wpb)), dim3(64 * wpb), args, lds, st));
         }
         {
             ProfScope ps("bin_merge", st);
-            hipLaunchKernelGGL(k_bin_merge, dim3((unsigned)ng), dim3(kBinMergeThreads), (size_t)(f->d + 1) * sizeof(unsigned), st,
-                               (const unsigned long long*)f->keys.p, nwaves, ng, k, f->d, D_dev + (size_t)16 * p * k,
-                               I_dev + (size_t)16 * p * k);
+            int32_t* Dp = D_dev + (size_t)16 * p * k;
+            int64_t* Ip = I_dev + (size_t)16 * p * k;
+            if (asym)
+                hipLaunchKernelGGL(k_bin_merge<true>, dim3((unsigned)ng), dim3(kBinMergeThreads), (size_t)kBinWideBins * sizeof(unsigned), st,
+                                   (const unsigned long long*)f->keys.p, nwaves, ng, k, 2 * kBinAsymBias, Dp, Ip);
+            else
+                hipLaunchKernelGGL(k_bin_merge<false>, dim3((unsigned)ng), dim3(kBinMergeThreads), (size_t)(f->d + 1) * sizeof(unsigned), st,
+                                   (const unsigned long long*)f->keys.p, nwaves, ng, k, f->d, Dp, Ip);
             CSS_LAUNCH_CHECK();
         }
         ++f->last_passes;
     }
+    return CSS_OK;
+}
+
+// nq asymmetric queries on the device, fp32 (`q_dev`) or int8 (`q8_dev`), into the fragments and sums of their passes
+int bin_asym_prep_enqueue(css_bin* f, const float* q_dev, const int8_t* q8_dev, int nq, int* capq, hipStream_t st) {
+    int rc;
+    *capq = (nq + 15) / 16 * 16;
+    if ((rc = f->qfrag.grow((size_t)(*capq / 16) * 2 * ((f->W + 3) / 4) * 64)) != CSS_OK) return rc;
+    if ((rc = f->qsum.grow((size_t)*capq)) != CSS_OK) return rc;
+    ProfScope ps("bin_asym_prep", st);
+    if (q_dev)
+        hipLaunchKernelGGL(k_bin_asym_prep<true>, dim3((unsigned)(*capq / 4)), dim3(256), 0, st, (const void*)q_dev, nq, *capq, f->d, f->qfrag.p,
+                           f->qsum.p);
+    else
+        hipLaunchKernelGGL(k_bin_asym_prep<false>, dim3((unsigned)(*capq / 4)), dim3(256), 0, st, (const void*)q8_dev, nq, *capq, f->d,
+                           f->qfrag.p, f->qsum.p);
+    CSS_LAUNCH_CHECK();
     return CSS_OK;
 }
 
@@ -6602,35 +6635,51 @@ int bin_finite_check(const char* fn, const char* what, const float* x, int64_t n
     return CSS_OK;
 }
 
-// The host forms of the search: the queries as fp32 (`q_host`) or as codes (`qc_host`), uploaded and brought into planes,
-// the search, the copies back and the ONE wait.
-int bin_search_host(css_bin* f, const float* q_host, const uint8_t* qc_host, int64_t nq, int k, const uint32_t* allow_bits_host,
-                    int32_t* D_host, int64_t* I_host) {
+// What a search's queries are: fp32 binarized on the device or codes (Hamming), fp32 quantized on the device or int8
+// (asymmetric).
+enum BinQuery { kBinFloat, kBinCodes, kBinAsymFloat, kBinAsymI8 };
+
+// the queries `q` on the device into the form the scan reads, then the search
+int bin_query_search_enqueue(css_bin* f, BinQuery kind, const void* q, int nq, int k, const uint32_t* mask_dev, int32_t* D_dev, int64_t* I_dev,
+                             hipStream_t st) {
+    int rc, capq;
+    if (kind == kBinFloat || kind == kBinCodes) {
+        if ((rc = bin_query_room(f, nq, &capq)) != CSS_OK) return rc;
+        rc = kind == kBinFloat ? bin_encode_enqueue(f, static_cast<const float*>(q), nq, f->qc.p, capq, 0, st)
+                               : bin_move_enqueue<true>(f, static_cast<unsigned*>(const_cast<void*>(q)), nq, f->qc.p, capq, 0, st);
+    } else {
+        rc = bin_asym_prep_enqueue(f, kind == kBinAsymFloat ? static_cast<const float*>(q) : nullptr,
+                                   kind == kBinAsymI8 ? static_cast<const int8_t*>(q) : nullptr, nq, &capq, st);
+    }
+    if (rc != CSS_OK) return rc;
+    return bin_search_enqueue(f, kind == kBinAsymFloat || kind == kBinAsymI8, nq, capq, k, mask_dev, D_dev, I_dev, st);
+}
+
+// The host forms of the search: the queries uploaded (fp32 through f->x, codes and int8 through f->flat), prepared and
+// searched, the copies back and the ONE wait.
+int bin_search_host(css_bin* f, BinQuery kind, const void* q_host, int64_t nq, int k, const uint32_t* allow_bits_host, int32_t* D_host,
+                    int64_t* I_host) {
     std::lock_guard<std::mutex> lk(f->mu);
     DeviceGuard g(f->device);
     const hipStream_t st = f->stream;
     const size_t words = (size_t)((f->ntotal + 31) / 32), no = (size_t)nq * k;
-    const bool masked = allow_bits_host != nullptr && f->ntotal > 0;
-    int rc, capq;
+    const bool masked = allow_bits_host != nullptr && f->ntotal > 0, fp32 = kind == kBinFloat || kind == kBinAsymFloat;
+    // (a code is W words, an int8 query 8 W)
+    const size_t qbytes = (size_t)nq * f->W * (fp32 ? 32 * sizeof(float) : kind == kBinCodes ? 4 : 32);
+    int rc;
     if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
-    if ((rc = bin_query_room(f, (int)nq, &capq)) != CSS_OK) return rc;
-    if (q_host && (rc = f->x.grow((size_t)nq * f->d)) != CSS_OK) return rc;
-    if (qc_host && (rc = f->flat.grow((size_t)nq * f->W)) != CSS_OK) return rc;
+    if (fp32 && (rc = f->x.grow(qbytes / sizeof(float))) != CSS_OK) return rc;
+    if (!fp32 && (rc = f->flat.grow(qbytes / sizeof(unsigned))) != CSS_OK) return rc;
     if ((rc = f->d_out.grow(no)) != CSS_OK) return rc;
     if ((rc = f->i_out.grow(no)) != CSS_OK) return rc;
     if (masked && (rc = f->mask.grow(words)) != CSS_OK) return rc;
     rc = [&]() -> int {
         int rc2;
-        if (q_host) {
-            CSS_HIP_TRY(hipMemcpyAsync(f->x.p, q_host, (size_t)nq * f->d * sizeof(float), hipMemcpyHostToDevice, st));
-            rc2 = bin_encode_enqueue(f, f->x.p, nq, f->qc.p, capq, 0, st);
-        } else {
-            CSS_HIP_TRY(hipMemcpyAsync(f->flat.p, qc_host, (size_t)nq * f->W * 4, hipMemcpyHostToDevice, st));
-            rc2 = bin_move_enqueue<true>(f, f->flat.p, nq, f->qc.p, capq, 0, st);
-        }
-        if (rc2 != CSS_OK) return rc2;
+        void* q_dev = fp32 ? (void*)f->x.p : (void*)f->flat.p;
+        CSS_HIP_TRY(hipMemcpyAsync(q_dev, q_host, qbytes, hipMemcpyHostToDevice, st));
         if (masked) CSS_HIP_TRY(hipMemcpyAsync(f->mask.p, allow_bits_host, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        if ((rc2 = bin_search_enqueue(f, (int)nq, capq, k, masked ? f->mask.p : nullptr, f->d_out.p, f->i_out.p, st)) != CSS_OK) return rc2;
+        if ((rc2 = bin_query_search_enqueue(f, kind, q_dev, (int)nq, k, masked ? f->mask.p : nullptr, f->d_out.p, f->i_out.p, st)) != CSS_OK)
+            return rc2;
         CSS_HIP_TRY(hipMemcpyAsync(D_host, f->d_out.p, no * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         CSS_HIP_TRY(hipMemcpyAsync(I_host, f->i_out.p, no * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         return CSS_OK;
@@ -6638,17 +6687,14 @@ int bin_search_host(css_bin* f, const float* q_host, const uint8_t* qc_host, int
     return bin_end_host(f, rc);
 }
 
-// The `_dev` forms: fp32 queries (`q_dev`) or codes (`qc_dev`) on the device, everything enqueued on the caller's stream.
-int bin_search_dev(css_bin* f, const float* q_dev, const uint8_t* qc_dev, int64_t nq, int k, const uint32_t* allow_bits_dev,
-                   int32_t* D_dev, int64_t* I_dev, hipStream_t st) {
+// The `_dev` forms: the queries on the device, everything enqueued on the caller's stream.
+int bin_search_dev(css_bin* f, BinQuery kind, const void* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev,
+                   int64_t* I_dev, hipStream_t st) {
     std::lock_guard<std::mutex> lk(f->mu);
     DeviceGuard g(f->device);
-    int rc, capq;
+    int rc;
     if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
-    if ((rc = bin_query_room(f, (int)nq, &capq)) != CSS_OK) return rc;
-    rc = q_dev ? bin_encode_enqueue(f, q_dev, nq, f->qc.p, capq, 0, st)
-               : bin_move_enqueue<true>(f, reinterpret_cast<unsigned*>(const_cast<uint8_t*>(qc_dev)), nq, f->qc.p, capq, 0, st);
-    if (rc == CSS_OK) rc = bin_search_enqueue(f, (int)nq, capq, k, f->ntotal > 0 ? allow_bits_dev : nullptr, D_dev, I_dev, st);
+    rc = bin_query_search_enqueue(f, kind, q_dev, (int)nq, k, f->ntotal > 0 ? allow_bits_dev : nullptr, D_dev, I_dev, st);
     return bin_end_dev(f, rc, st);
 }
 }  // namespace
@@ -6798,7 +6844,7 @@ int css_bin_search(css_bin* f, const float* q_host, int64_t nq, int k, const uin
     if (rc != CSS_OK) return rc;
     CSS_REQUIRE(q_host && D_host && I_host, "css_bin_search: NULL buffer");
     if ((rc = bin_finite_check("css_bin_search", "query", q_host, nq, f->d)) != CSS_OK) return rc;
-    return bin_search_host(f, q_host, nullptr, nq, k, allow_bits_host, D_host, I_host);
+    return bin_search_host(f, kBinFloat, q_host, nq, k, allow_bits_host, D_host, I_host);
 }
 
 int css_bin_search_codes(css_bin* f, const uint8_t* q_codes_host, int64_t nq, int k, const uint32_t* allow_bits_host,
@@ -6806,7 +6852,7 @@ int css_bin_search_codes(css_bin* f, const uint8_t* q_codes_host, int64_t nq, in
     const int rc = bin_search_check("css_bin_search_codes", f, nq, k);
     if (rc != CSS_OK) return rc;
     CSS_REQUIRE(q_codes_host && D_host && I_host, "css_bin_search_codes: NULL buffer");
-    return bin_search_host(f, nullptr, q_codes_host, nq, k, allow_bits_host, D_host, I_host);
+    return bin_search_host(f, kBinCodes, q_codes_host, nq, k, allow_bits_host, D_host, I_host);
 }
 
 int css_bin_search_dev(css_bin* f, const float* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev,
@@ -6814,7 +6860,7 @@ int css_bin_search_dev(css_bin* f, const float* q_dev, int64_t nq, int k, const 
     const int rc = bin_search_check("css_bin_search_dev", f, nq, k);
     if (rc != CSS_OK) return rc;
     CSS_REQUIRE(q_dev && D_dev && I_dev, "css_bin_search_dev: NULL buffer");
-    return bin_search_dev(f, q_dev, nullptr, nq, k, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
+    return bin_search_dev(f, kBinFloat, q_dev, nq, k, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
 }
 
 int css_bin_search_codes_dev(css_bin* f, const uint8_t* q_codes_dev, int64_t nq, int k, const uint32_t* allow_bits_dev,
@@ -6823,7 +6869,40 @@ int css_bin_search_codes_dev(css_bin* f, const uint8_t* q_codes_dev, int64_t nq,
     if (rc != CSS_OK) return rc;
     CSS_REQUIRE(q_codes_dev && D_dev && I_dev, "css_bin_search_codes_dev: NULL buffer");
     CSS_REQUIRE((reinterpret_cast<uintptr_t>(q_codes_dev) & 3u) == 0, "css_bin_search_codes_dev: q_codes is not 4-byte aligned");
-    return bin_search_dev(f, nullptr, q_codes_dev, nq, k, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
+    return bin_search_dev(f, kBinCodes, q_codes_dev, nq, k, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
+}
+
+int css_bin_search_asym(css_bin* f, const float* q_host, int64_t nq, int k, const uint32_t* allow_bits_host, int32_t* D_host,
+                        int64_t* I_host) {
+    int rc = bin_search_check("css_bin_search_asym", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_host && D_host && I_host, "css_bin_search_asym: NULL buffer");
+    if ((rc = bin_finite_check("css_bin_search_asym", "query", q_host, nq, f->d)) != CSS_OK) return rc;
+    return bin_search_host(f, kBinAsymFloat, q_host, nq, k, allow_bits_host, D_host, I_host);
+}
+
+int css_bin_search_asym_dev(css_bin* f, const float* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev,
+                            int64_t* I_dev, void* stream) {
+    const int rc = bin_search_check("css_bin_search_asym_dev", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_dev && D_dev && I_dev, "css_bin_search_asym_dev: NULL buffer");
+    return bin_search_dev(f, kBinAsymFloat, q_dev, nq, k, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
+}
+
+int css_bin_search_asym_i8(css_bin* f, const int8_t* q_host, int64_t nq, int k, const uint32_t* allow_bits_host, int32_t* D_host,
+                           int64_t* I_host) {
+    const int rc = bin_search_check("css_bin_search_asym_i8", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_host && D_host && I_host, "css_bin_search_asym_i8: NULL buffer");
+    return bin_search_host(f, kBinAsymI8, q_host, nq, k, allow_bits_host, D_host, I_host);
+}
+
+int css_bin_search_asym_i8_dev(css_bin* f, const int8_t* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev,
+                               int64_t* I_dev, void* stream) {
+    const int rc = bin_search_check("css_bin_search_asym_i8_dev", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_dev && D_dev && I_dev, "css_bin_search_asym_i8_dev: NULL buffer");
+    return bin_search_dev(f, kBinAsymI8, q_dev, nq, k, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
 }
 
 namespace {

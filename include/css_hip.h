@@ -752,7 +752,18 @@ int css_pq_last_passes(css_pq* pq, int* passes_out);
  *    are serialised, and a call on another stream goes behind the _dev call before it.
  *  - css_bin_set_waves: the number of scanning waves (= row ranges, each one part of the selection) of the next
  *    searches, 0 = automatic (resident, every SIMD busy); at most CSS_BIN_MAX_WAVES, and never more than there are steps
- *    of 256 rows.  A test and tuning hook: no answer depends on it. */
+ *    of 256 rows.  A test and tuning hook: no answer depends on it.
+ *  - Asymmetric search (css_bin_search_asym*): the rows stay bits, the query keeps its magnitudes at int8.
+ *    Query: int8 [nq, d], every value allowed (-128 included).  Score: s(q, r) = sum_i q_i (2 b_i - 1) with b_i bit i
+ *    of the row, an int32 with |s| <= 128 * 8192 = 2^20.  Answer: D int32 (scores) and I int64, each [nq, k], the
+ *    LARGEST score first, ties to the lower id, rows outside allow_bits left out, padding D = INT32_MIN, I = -1; the
+ *    bytes do not depend on the grid, css_bin_set_waves, the batch or the form of the call.  The float forms
+ *    (css_bin_search_asym / _asym_dev) quantize each fp32 query on the device: a = max_i |q_i|; if a is below the
+ *    smallest normal float (compared on the bits) the int8 query is all zeros; otherwise q8_i = rint((q_i / a) * 127),
+ *    the division and the product each correctly rounded in fp32, rint to nearest even.  a * s / 127 is the caller's
+ *    float estimate of <q, sign(r)>: the library returns integers only.  The _i8 forms take the int8 query as it is.
+ *    Argument order, refusals, passes (16 queries per scan, css_bin_last_passes) and css_bin_set_waves (here: steps of
+ *    64 rows) are those of css_bin_search*; the codes are read as they lie, no second copy exists. */
 #define CSS_BIN_MAX_QUERIES 65536
 #define CSS_BIN_MAX_WAVES 16384
 typedef struct css_bin css_bin;
@@ -772,6 +783,14 @@ int css_bin_search_codes(css_bin* b, const uint8_t* q_codes_host /* [nq, d / 8] 
                          const uint32_t* allow_bits_host, int32_t* D_host, int64_t* I_host);
 int css_bin_search_codes_dev(css_bin* b, const uint8_t* q_codes_dev, int64_t nq, int k, const uint32_t* allow_bits_dev,
                              int32_t* D_dev, int64_t* I_dev, void* stream);
+int css_bin_search_asym(css_bin* b, const float* q_host /* [nq, d] */, int64_t nq, int k, const uint32_t* allow_bits_host,
+                        int32_t* D_host /* [nq, k] */, int64_t* I_host /* [nq, k] */);
+int css_bin_search_asym_dev(css_bin* b, const float* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev,
+                            int64_t* I_dev, void* stream);
+int css_bin_search_asym_i8(css_bin* b, const int8_t* q_host /* [nq, d] */, int64_t nq, int k, const uint32_t* allow_bits_host,
+                           int32_t* D_host, int64_t* I_host);
+int css_bin_search_asym_i8_dev(css_bin* b, const int8_t* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev,
+                               int64_t* I_dev, void* stream);
 int css_bin_last_passes(css_bin* b, int* passes_out);
 int css_bin_set_waves(css_bin* b, int waves);
 
