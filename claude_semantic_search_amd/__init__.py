@@ -55,6 +55,9 @@ _LAZY = {
     "ProductQuantizer": ".pq",
     "train_product_quantizer": ".pq",
     "IndexBinaryFlat": ".binary",
+    "IndexScalarQuantizer": ".sq",
+    "ScalarQuantizer": ".sq",
+    "train_scalar_quantizer": ".sq",
     "SparseEncoder": ".sparse_encoder",
     "SparseVector": ".sparse_encoder",
     "sparse_dot_numpy": ".sparse_encoder",

@@ -226,6 +226,21 @@ PROTOTYPES = {
     "css_bin_search_asym_i8_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "css_bin_last_passes": (c_int, [c_void_p, POINTER(c_int)]),
     "css_bin_set_waves": (c_int, [c_void_p, c_int]),
+    "css_sq_create": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, POINTER(c_void_p)]),
+    "css_sq_free": (c_int, [c_void_p]),
+    "css_sq_dim": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "css_sq_ntotal": (c_int, [c_void_p, POINTER(c_int64)]),
+    "css_sq_add": (c_int, [c_void_p, c_void_p, c_int64]),
+    "css_sq_add_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "css_sq_add_codes": (c_int, [c_void_p, c_void_p, c_int64]),
+    "css_sq_get_codes": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
+    "css_sq_reconstruct": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
+    "css_sq_search": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "css_sq_search_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_sq_search_i8": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "css_sq_search_i8_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "css_sq_last_passes": (c_int, [c_void_p, POINTER(c_int)]),
+    "css_sq_set_waves": (c_int, [c_void_p, c_int]),
     "css_index_maxsim_candidates": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                             POINTER(c_int64)]),
     "css_index_search_maxsim_pruned": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,

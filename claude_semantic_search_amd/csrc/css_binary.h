@@ -34,14 +34,27 @@
 // the lowest ids are wanted, and since part p's rows all precede part p + 1's and a part is sorted, those are the first
 // ones in (part, position) order: a count per part chunk, one prefix sum, one more walk.  A bitonic sort of the <= 128
 // taken keys orders them; the key splits into int32 distance and int64 id (INT32_MAX / -1 for padding).  The asymmetric
-// scores (below) span 2^21 + 1 values: k_bin_merge<true> finds T in two digit rounds over the same histogram.
+// scores (below) span 2^21 + 1 values: k_bin_merge<true> finds T in two digit rounds over the same histogram, and in
+// three for the up to 29 bits of the scalar-quantized store's keys (css_sq.h).
 #pragma once
 
 constexpr unsigned long long kBinPad = ~0ull;
 constexpr int kBinWavesPerBlock = 4;
 constexpr int kBinMergeThreads = 1024;   // one block per query: its loads of the parts' keys are all the parallelism there is
 constexpr int kBinAsymBias = 1 << 20;    // an asymmetric score s, |s| <= 128 * 8192, has the key high word kBinAsymBias - s
-constexpr int kBinWideBins = (2 * kBinAsymBias >> 10) + 1;   // k_bin_merge<true>: the bins of its first digit round
+// k_bin_merge<true>: the bits below the first digit of high words in [0, top], 10 per further round; the first digit
+// has at most 4097 values.  top = 2^21: 10 (2049 bins, then 1024); top < 2^29: 20 (at most 512 bins, then 1024 twice).
+__host__ __device__ constexpr int bin_wide_shift(int top) {
+    int bits = 0;
+    while (top >> bits) ++bits;
+    return bits <= 12 ? 0 : (bits - 12 + 9) / 10 * 10;
+}
+// its dynamic LDS in bins: the first round's, and the 1024 of a further round
+__host__ __device__ constexpr int bin_wide_bins(int top) {
+    const int shift = bin_wide_shift(top), first = (top >> shift) + 1;
+    return shift && first < 1024 ? 1024 : first;
+}
+constexpr int kBinWideBins = bin_wide_bins(2 * kBinAsymBias);
 typedef const __attribute__((address_space(4))) unsigned* bin_const_words;
 
 // bit b of the byte at every byte position <-> bit 7 - b: packbits bytes (as a little-endian word) <-> plane word
@@ -213,12 +226,13 @@ __device__ __forceinline__ void bin_hist_kth(const unsigned* hist, int nb, unsig
 
 // keys [nparts][nq][k] -> D / I [k] of query blockIdx.x: the k smallest keys, ascending.  Part p's rows all precede
 // part p + 1's.  `top` is the largest high word a key can have.  !WIDE (Hamming: top = d): one histogram of top + 1 bins.
-// WIDE (the asymmetric scores, top = 2^21): the threshold in two digit rounds over the high word, its upper 11 bits
-// (2049 bins), then the lower 10 among the keys that share the upper digit of the k-th; D is 2^20 - the high word and
-// the padding INT32_MIN.  Dynamic LDS: (WIDE ? kBinWideBins : top + 1) bins.
+// WIDE (scores, high word = bias - score in [0, top]): the threshold in digit rounds over the high word from the top,
+// the bits above bin_wide_shift(top) first, then 10 bits per round among the keys that share the upper digits of the
+// k-th (top = 2^21: 2049 bins, then 1024); D is bias - the high word and the padding INT32_MIN.  Dynamic LDS:
+// (WIDE ? bin_wide_bins(top) : top + 1) bins.
 template <bool WIDE>
 __global__ __launch_bounds__(kBinMergeThreads) void k_bin_merge(const unsigned long long* __restrict__ keys, int nparts, int nq, int k,
-                                                                int top, int32_t* __restrict__ D, int64_t* __restrict__ I) {
+                                                                int top, int bias, int32_t* __restrict__ D, int64_t* __restrict__ I) {
     extern __shared__ unsigned bin_hist[];
     __shared__ unsigned pre[kBinMergeThreads];
     __shared__ unsigned long long sel[CSS_KERNEL_MAX_K];
@@ -226,7 +240,7 @@ __global__ __launch_bounds__(kBinMergeThreads) void k_bin_merge(const unsigned l
     const int tid = threadIdx.x, q = blockIdx.x;
     const unsigned long long* kq = keys + (size_t)q * k;       // part p, entry j: kq[p * stride + j]
     const size_t stride = (size_t)nq * k;
-    const int shift = WIDE ? 10 : 0, nb = (top >> shift) + 1;
+    const int shift = WIDE ? bin_wide_shift(top) : 0, nb = (top >> shift) + 1;
     for (int i = tid; i < nb; i += kBinMergeThreads) bin_hist[i] = 0u;
     if (tid < CSS_KERNEL_MAX_K) sel[tid] = kBinPad;
     if (tid == 0) sT = (unsigned)nb, sBelow = 0u, sT2 = 0u, sBelow2 = 0u, sCnt = 0u;   // fewer than k keys in all: everything is "below"
@@ -240,20 +254,22 @@ __global__ __launch_bounds__(kBinMergeThreads) void k_bin_merge(const unsigned l
     __syncthreads();
     // T = the first distance at which the running count reaches k
     bin_hist_kth(bin_hist, nb, pre, (unsigned)k, tid, &sT, &sBelow);
-    if (WIDE && sT < (unsigned)nb) {   // (block uniform) the second digit, among the keys whose first is sT
-        const unsigned T1 = sT;
-        for (int i = tid; i < 1024; i += kBinMergeThreads) bin_hist[i] = 0u;
-        __syncthreads();
-        for (int e = tid; e < total; e += kBinMergeThreads) {
-            const int p = e / k, j = e - p * k;
-            const unsigned long long key = kq[(size_t)p * stride + j];
-            if (key != kBinPad && (unsigned)(key >> 32) >> 10 == T1) atomicAdd(&bin_hist[(unsigned)(key >> 32) & 1023u], 1u);
-        }
-        __syncthreads();
-        bin_hist_kth(bin_hist, 1024, pre, (unsigned)k - sBelow, tid, &sT2, &sBelow2);
-    }
     const bool found = sT < (unsigned)nb;
-    const unsigned T = found ? (sT << shift | sT2) : 0xFFFFFFFFu, below = sBelow + sBelow2, need = found ? (unsigned)k - below : 0u;
+    unsigned T = found ? sT : 0xFFFFFFFFu, below = sBelow;
+    if (WIDE && found)   // (block uniform) the next digit, among the keys whose upper digits are T
+        for (int s = shift - 10; s >= 0; s -= 10) {
+            for (int i = tid; i < 1024; i += kBinMergeThreads) bin_hist[i] = 0u;
+            __syncthreads();
+            for (int e = tid; e < total; e += kBinMergeThreads) {
+                const int p = e / k, j = e - p * k;
+                const unsigned long long key = kq[(size_t)p * stride + j];
+                if (key != kBinPad && (unsigned)(key >> 32) >> (s + 10) == T) atomicAdd(&bin_hist[(unsigned)(key >> 32) >> s & 1023u], 1u);
+            }
+            __syncthreads();
+            bin_hist_kth(bin_hist, 1024, pre, (unsigned)k - below, tid, &sT2, &sBelow2);
+            T = T << 10 | sT2, below += sBelow2;
+        }
+    const unsigned need = found ? (unsigned)k - below : 0u;
     // every key below T, in any order, into sel[0 .. below)
     for (int e = tid; e < total; e += kBinMergeThreads) {
         const int p = e / k, j = e - p * k;
@@ -293,7 +309,7 @@ __global__ __launch_bounds__(kBinMergeThreads) void k_bin_merge(const unsigned l
     if (tid < k) {
         const unsigned long long key = sel[tid];
         const int32_t hw = (int32_t)(key >> 32);
-        D[(size_t)q * k + tid] = key == kBinPad ? (WIDE ? INT32_MIN : INT32_MAX) : WIDE ? kBinAsymBias - hw : hw;
+        D[(size_t)q * k + tid] = key == kBinPad ? (WIDE ? INT32_MIN : INT32_MAX) : WIDE ? bias - hw : hw;
         I[(size_t)q * k + tid] = key == kBinPad ? (int64_t)-1 : (int64_t)(key & 0xFFFFFFFFull);
     }
 }

@@ -2950,6 +2950,7 @@ int facet_sweep(css_index* ix, const Rows& rows, const float* qpad, int nqc, flo
 #include "css_fde.h"
 #include "css_pq.h"
 #include "css_binary.h"
+#include "css_sq.h"
 #include "css_where.h"
 #include "css_sigterms.h"
 
@@ -6481,15 +6482,19 @@ struct css_bin {
 };
 
 namespace {
-int bin_begin(css_bin* f, hipStream_t st) {
+// (the frame and the argument checks are templates over the store: css_sq below has the same members)
+template <class Store>
+int bin_begin(Store* f, hipStream_t st) {
     if (f->pending) CSS_HIP_TRY(hipStreamWaitEvent(st, f->ev, 0));
     return CSS_OK;
 }
-int bin_end_dev(css_bin* f, int rc, hipStream_t st) {
+template <class Store>
+int bin_end_dev(Store* f, int rc, hipStream_t st) {
     if (hipEventRecord(f->ev, st) == hipSuccess) f->pending = true;
     return rc;
 }
-int bin_end_host(css_bin* f, int rc) {   // the ONE wait (also of a failed call: its copies read the caller's memory)
+template <class Store>
+int bin_end_host(Store* f, int rc) {   // the ONE wait (also of a failed call: its copies read the caller's memory)
     const hipError_t e = hipStreamSynchronize(f->stream);
     if (e == hipSuccess) f->pending = false;
     if (rc == CSS_OK && e != hipSuccess) return css::hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
@@ -6588,10 +6593,10 @@ int bin_search_enqueue(css_bin* f, bool asym, int nq, int capq, int k, const uin
             int64_t* Ip = I_dev + (size_t)16 * p * k;
             if (asym)
                 hipLaunchKernelGGL(k_bin_merge<true>, dim3((unsigned)ng), dim3(kBinMergeThreads), (size_t)kBinWideBins * sizeof(unsigned), st,
-                                   (const unsigned long long*)f->keys.p, nwaves, ng, k, 2 * kBinAsymBias, Dp, Ip);
+                                   (const unsigned long long*)f->keys.p, nwaves, ng, k, 2 * kBinAsymBias, kBinAsymBias, Dp, Ip);
             else
                 hipLaunchKernelGGL(k_bin_merge<false>, dim3((unsigned)ng), dim3(kBinMergeThreads), (size_t)(f->d + 1) * sizeof(unsigned), st,
-                                   (const unsigned long long*)f->keys.p, nwaves, ng, k, f->d, Dp, Ip);
+                                   (const unsigned long long*)f->keys.p, nwaves, ng, k, f->d, 0, Dp, Ip);
             CSS_LAUNCH_CHECK();
         }
         ++f->last_passes;
@@ -6616,13 +6621,15 @@ int bin_asym_prep_enqueue(css_bin* f, const float* q_dev, const int8_t* q8_dev, 
     return CSS_OK;
 }
 
-int bin_add_check(const char* fn, const css_bin* f, int64_t n) {
+template <class Store>
+int bin_add_check(const char* fn, const Store* f, int64_t n) {
     CSS_REQUIRE(f, "%s: NULL store", fn);
     CSS_REQUIRE(n >= 0, "%s: n < 0", fn);
     CSS_REQUIRE(f->ntotal + n < 0xFFFFFFFFll, "%s: %lld rows exceed the 32-bit row numbers of the keys", fn, (long long)(f->ntotal + n));
     return CSS_OK;
 }
-int bin_search_check(const char* fn, const css_bin* f, int64_t nq, int k) {
+template <class Store>
+int bin_search_check(const char* fn, const Store* f, int64_t nq, int k) {
     CSS_REQUIRE(f, "%s: NULL store", fn);
     CSS_REQUIRE(nq >= 1 && nq <= CSS_BIN_MAX_QUERIES, "%s: nq=%lld outside [1, %d]", fn, (long long)nq, CSS_BIN_MAX_QUERIES);
     CSS_REQUIRE(k >= 1 && k <= CSS_KERNEL_MAX_K, "%s: k=%d outside [1, %d]", fn, k, CSS_KERNEL_MAX_K);
@@ -6903,6 +6910,380 @@ int css_bin_search_asym_i8_dev(css_bin* f, const int8_t* q_dev, int64_t nq, int 
     if (rc != CSS_OK) return rc;
     CSS_REQUIRE(q_dev && D_dev && I_dev, "css_bin_search_asym_i8_dev: NULL buffer");
     return bin_search_dev(f, kBinAsymI8, q_dev, nq, k, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
+}
+
+// ---- the scalar-quantized row store (css_sq.h; include/css_hip.h has the definition) ----
+}  // extern "C"
+
+// The store: the ranges, the codes row-tile-major (css_sq.h) and the workspaces of its calls; the frame of css_bin.
+struct css_sq {
+    int d = 0, bits = 0, rb = 0, C = 0, bias = 0;   // rb: the bytes of a row; C: its chunks of 64; bias = 128 L d >= |score|
+    int device = 0, num_cus = 256, last_passes = 0, waves = 0;   // waves: css_sq_set_waves, 0 = automatic
+    int64_t ntotal = 0, cap = 0;   // rows, and the rows there is room for (whole groups of 64)
+    hipStream_t stream = nullptr;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    std::mutex mu;
+    std::vector<float> step_host;      // the host forms check the folded query q_i step_i
+    DevBuf<float> range, x;            // vmin [d] then step [d]; uploaded float rows or queries, decoded rows
+    DevBuf<uint4> codes, flat, qfrag;  // [cap / 64][C][4][64]; row-major codes or int8 queries in transit; [passes][nF][64]
+    DevBuf<int> qsum;                  // the sums of the int8 queries [16 passes]
+    DevBuf<unsigned long long> keys;   // [waves][queries of a pass][k]
+    DevBuf<int32_t> d_out;
+    DevBuf<int64_t> i_out;
+    DevBuf<uint32_t> mask;
+};
+
+namespace {
+inline size_t sq_units(const css_sq* f, int64_t rows) { return (size_t)((rows + 63) / 64) * f->C * 256; }   // uint4s of whole groups
+
+// room for `rows` rows: a larger allocation and ONE copy of the stored groups as they lie (no row moves within it)
+int sq_reserve(css_sq* f, int64_t rows, hipStream_t st) {
+    if (rows <= f->cap) return CSS_OK;
+    const int64_t ncap = std::max((rows + 63) / 64 * 64, 2 * f->cap);
+    DevBuf<uint4> nb;
+    int rc;
+    if ((rc = nb.grow_exact(sq_units(f, ncap), "hipMalloc(sq codes)")) != CSS_OK) return rc;
+    if (f->ntotal) CSS_HIP_TRY(hipMemcpyAsync(nb.p, f->codes.p, sq_units(f, f->ntotal) * sizeof(uint4), hipMemcpyDeviceToDevice, st));
+    CSS_HIP_TRY(hipStreamSynchronize(st));   // (the old codes are freed when `nb` goes)
+    f->codes.swap(nb);
+    f->cap = ncap;
+    return CSS_OK;
+}
+
+// n fp32 rows on the device encoded into rows first .. of the store
+int sq_encode_enqueue(const css_sq* f, const float* x_dev, int64_t n, int64_t first, hipStream_t st) {
+    ProfScope ps("sq_encode", st);
+    const dim3 grid((unsigned)std::min<int64_t>((n * (f->rb / 16) + 255) / 256, 1 << 20));
+    const float *vmin = f->range.p, *step = f->range.p + f->d;
+    if (f->bits == 8) hipLaunchKernelGGL(k_sq_encode<8>, grid, dim3(256), 0, st, x_dev, n, f->d, vmin, step, f->codes.p, f->C, first);
+    else hipLaunchKernelGGL(k_sq_encode<4>, grid, dim3(256), 0, st, x_dev, n, f->d, vmin, step, f->codes.p, f->C, first);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// row-major codes [n][rb] on the device into (IN) or out of the store at rows first ..
+template <bool IN>
+int sq_move_enqueue(const css_sq* f, uint4* flat_dev, int64_t n, int64_t first, hipStream_t st) {
+    const int G = f->rb / 16;
+    hipLaunchKernelGGL(k_sq_codes_move<IN>, dim3((unsigned)((n * G + 255) / 256)), dim3(256), 0, st, flat_dev, n, G, f->codes.p, f->C, first);
+    CSS_LAUNCH_CHECK();
+    return CSS_OK;
+}
+
+// The nq queries on the device, fp32 (`q_dev`: folded and quantized) or int8 (`q8_dev`: as they are), into the
+// fragments and sums of their passes (k_sq_prep); then per pass of 16 queries ONE scan that selects (k_sq_topk, a part
+// per wave) and the exact merge of the parts (k_bin_merge<true>) into D_dev / I_dev [nq][k].
+int sq_search_enqueue(css_sq* f, const float* q_dev, const int8_t* q8_dev, int nq, int k, const uint32_t* mask_dev, int32_t* D_dev,
+                      int64_t* I_dev, hipStream_t st) {
+    const int64_t n = f->ntotal;
+    f->last_passes = 0;
+    if (n == 0) {
+        const int64_t total = (int64_t)nq * k;
+        hipLaunchKernelGGL(k_bin_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, total, INT32_MIN);
+        CSS_LAUNCH_CHECK();
+        return CSS_OK;
+    }
+    int rc;
+    const int passes = (nq + 15) / 16, capq = 16 * passes, gmax = std::min(nq, 16), nF = (f->bits == 8 ? 1 : 2) * f->C;
+    const int top = 2 * f->bias, kbits = 32 - __builtin_clz((unsigned)top);
+    const int64_t steps = (n + 63) / 64;
+    if ((rc = f->qfrag.grow((size_t)passes * nF * 64)) != CSS_OK) return rc;
+    if ((rc = f->qsum.grow((size_t)capq)) != CSS_OK) return rc;
+    // (the first pass has the most queries, so the most waves' worth of keys)
+    if ((rc = f->keys.grow((size_t)std::min<int64_t>(steps, f->waves > 0 ? f->waves : f->num_cus * 32) * gmax * k)) != CSS_OK) return rc;
+    {
+        ProfScope ps("sq_prep", st);
+        if (q_dev)
+            hipLaunchKernelGGL(k_sq_prep<true>, dim3((unsigned)(capq / 4)), dim3(256), 0, st, (const void*)q_dev, nq, capq, f->d, f->bits,
+                               (const float*)(f->range.p + f->d), f->qfrag.p, f->qsum.p);
+        else
+            hipLaunchKernelGGL(k_sq_prep<false>, dim3((unsigned)(capq / 4)), dim3(256), 0, st, (const void*)q8_dev, nq, capq, f->d, f->bits,
+                               (const float*)nullptr, f->qfrag.p, f->qsum.p);
+        CSS_LAUNCH_CHECK();
+    }
+    const bool qlds = nF > kSqRegFrags;   // the fragments of more than 1024 components do not fit the registers
+    const void* fn = f->bits == 8 ? (qlds ? (const void*)k_sq_topk<8, true> : (const void*)k_sq_topk<8, false>)
+                                  : (qlds ? (const void*)k_sq_topk<4, true> : (const void*)k_sq_topk<4, false>);
+    for (int p = 0; p < passes; ++p) {
+        const int ng = std::min(16, nq - 16 * p);
+        // the waves of a block: 4, or as many as have room for their lists beside the fragments a QLDS block stages
+        const size_t per_wave = (size_t)ng * k * sizeof(unsigned long long), fixed = qlds ? (size_t)nF * 64 * sizeof(uint4) : 0;
+        const int wpb = (int)std::min<size_t>(kBinWavesPerBlock, (160 * 1024 - fixed) / per_wave);
+        const size_t lds = fixed + wpb * per_wave;
+        if (lds > 48 * 1024 && (rc = css::ensure_dynamic_lds(fn, lds, f->device)) != CSS_OK) return rc;
+        // resident: the blocks a CU holds at the kernel's registers (3 waves per SIMD with the fragments in registers,
+        // else 4) and at its LDS; fewer waves when there are fewer steps; or what the caller set
+        const int by_regs = qlds ? 4 : 3, by_lds = (int)std::max<size_t>(1, 160 * 1024 / lds);
+        const int64_t want = std::min<int64_t>(steps, f->waves > 0 ? f->waves : (int64_t)f->num_cus * std::min(by_regs, by_lds) * wpb);
+        const int64_t per = (steps + want - 1) / want * 64;
+        const int nwaves = (int)((n + per - 1) / per);
+        SqTopkArgs a{f->codes.p, f->qfrag.p + (size_t)p * nF * 64, f->qsum.p + 16 * p, mask_dev, f->keys.p, n, per, f->C, f->rb, ng, k, nwaves,
+                     f->bias, kbits};
+        void* args[] = {(void*)&a};
+        {
+            ProfScope ps("sq_topk", st);
+            CSS_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)((nwaves + wpb - 1) / wpb)), dim3(64 * wpb), args, lds, st));
+        }
+        {
+            ProfScope ps("sq_merge", st);
+            hipLaunchKernelGGL(k_bin_merge<true>, dim3((unsigned)ng), dim3(kBinMergeThreads), (size_t)bin_wide_bins(top) * sizeof(unsigned), st,
+                               (const unsigned long long*)f->keys.p, nwaves, ng, k, top, f->bias, D_dev + (size_t)16 * p * k,
+                               I_dev + (size_t)16 * p * k);
+            CSS_LAUNCH_CHECK();
+        }
+        ++f->last_passes;
+    }
+    return CSS_OK;
+}
+
+// The host forms of the search: the queries uploaded (fp32 through f->x, int8 through f->flat), searched, the copies
+// back and the ONE wait.
+int sq_search_host(css_sq* f, bool fp32, const void* q_host, int64_t nq, int k, const uint32_t* allow_bits_host, int32_t* D_host,
+                   int64_t* I_host) {
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    const size_t words = (size_t)((f->ntotal + 31) / 32), no = (size_t)nq * k, qbytes = (size_t)nq * f->d * (fp32 ? sizeof(float) : 1);
+    const bool masked = allow_bits_host != nullptr && f->ntotal > 0;
+    int rc;
+    if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
+    if (fp32 && (rc = f->x.grow(qbytes / sizeof(float))) != CSS_OK) return rc;
+    if (!fp32 && (rc = f->flat.grow(qbytes / sizeof(uint4))) != CSS_OK) return rc;   // (d is a multiple of 32)
+    if ((rc = f->d_out.grow(no)) != CSS_OK) return rc;
+    if ((rc = f->i_out.grow(no)) != CSS_OK) return rc;
+    if (masked && (rc = f->mask.grow(words)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        int rc2;
+        void* q_dev = fp32 ? (void*)f->x.p : (void*)f->flat.p;
+        CSS_HIP_TRY(hipMemcpyAsync(q_dev, q_host, qbytes, hipMemcpyHostToDevice, st));
+        if (masked) CSS_HIP_TRY(hipMemcpyAsync(f->mask.p, allow_bits_host, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if ((rc2 = sq_search_enqueue(f, fp32 ? f->x.p : nullptr, fp32 ? nullptr : (const int8_t*)f->flat.p, (int)nq, k,
+                                     masked ? f->mask.p : nullptr, f->d_out.p, f->i_out.p, st)) != CSS_OK)
+            return rc2;
+        CSS_HIP_TRY(hipMemcpyAsync(D_host, f->d_out.p, no * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        CSS_HIP_TRY(hipMemcpyAsync(I_host, f->i_out.p, no * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        return CSS_OK;
+    }();
+    return bin_end_host(f, rc);
+}
+
+// The `_dev` forms: the queries on the device, everything enqueued on the caller's stream.
+int sq_search_dev(css_sq* f, const float* q_dev, const int8_t* q8_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev,
+                  int64_t* I_dev, hipStream_t st) {
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    int rc;
+    if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
+    rc = sq_search_enqueue(f, q_dev, q8_dev, (int)nq, k, f->ntotal > 0 ? allow_bits_dev : nullptr, D_dev, I_dev, st);
+    return bin_end_dev(f, rc, st);
+}
+
+// The host forms that read rows [row0, row0 + n) out: codes (get_codes) or decoded floats, through `enqueue`.
+template <class Enqueue>
+int sq_read_rows(const char* fn, css_sq* f, int64_t row0, int64_t n, Enqueue enqueue) {
+    std::lock_guard<std::mutex> lk(f->mu);
+    CSS_REQUIRE(row0 >= 0 && n >= 0 && row0 + n <= f->ntotal, "%s: rows [%lld, %lld) outside [0, %lld)", fn, (long long)row0,
+                (long long)(row0 + n), (long long)f->ntotal);
+    if (n == 0) return CSS_OK;
+    DeviceGuard g(f->device);
+    int rc;
+    if ((rc = bin_begin(f, f->stream)) != CSS_OK) return rc;
+    return bin_end_host(f, enqueue(f->stream));
+}
+}  // namespace
+
+extern "C" {
+
+int css_sq_create(int d, int bits, const float* vmin_host, const float* step_host, int device, css_sq** out) {
+    CSS_REQUIRE(out != nullptr, "css_sq_create: out is NULL");
+    CSS_REQUIRE(d >= 32 && d <= 8192 && d % 32 == 0, "css_sq_create: d=%d must be a multiple of 32 in [32, 8192]", d);
+    CSS_REQUIRE(bits == 4 || bits == 8, "css_sq_create: bits=%d must be 4 or 8", bits);
+    CSS_REQUIRE(vmin_host && step_host, "css_sq_create: vmin or step is NULL");
+    for (int i = 0; i < d; ++i) {
+        CSS_REQUIRE(std::isfinite(vmin_host[i]), "css_sq_create: vmin[%d] is %s", i, std::isnan(vmin_host[i]) ? "NaN" : "infinite");
+        CSS_REQUIRE(std::isfinite(step_host[i]) && step_host[i] > 0.f, "css_sq_create: step[%d]=%g must be finite and above 0", i,
+                    (double)step_host[i]);
+    }
+    int rc = css::check_device(device);
+    if (rc != CSS_OK) return rc;
+    DeviceGuard g(device);
+    std::unique_ptr<css_sq> f(new css_sq());
+    f->d = d, f->bits = bits, f->rb = d * bits / 8, f->C = (f->rb + 63) / 64, f->bias = 128 * ((1 << bits) - 1) * d, f->device = device;
+    f->step_host.assign(step_host, step_host + d);
+    hipDeviceProp_t p;
+    if (hipGetDeviceProperties(&p, device) == hipSuccess) f->num_cus = p.multiProcessorCount;
+    if ((rc = f->range.grow_exact((size_t)2 * d, "hipMalloc(sq ranges)")) != CSS_OK) return rc;
+    CSS_HIP_TRY(hipMemcpy(f->range.p, vmin_host, (size_t)d * sizeof(float), hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipMemcpy(f->range.p + d, step_host, (size_t)d * sizeof(float), hipMemcpyHostToDevice));
+    CSS_HIP_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    CSS_HIP_TRY(hipEventCreateWithFlags(&f->ev, hipEventDisableTiming));
+    *out = f.release();
+    return CSS_OK;
+}
+
+int css_sq_free(css_sq* f) {
+    if (!f) return CSS_OK;
+    DeviceGuard g(f->device);
+    if (f->pending) (void)hipEventSynchronize(f->ev);
+    if (f->stream) {
+        (void)hipStreamSynchronize(f->stream);
+        (void)hipStreamDestroy(f->stream);
+    }
+    if (f->ev) (void)hipEventDestroy(f->ev);
+    delete f;   // (the DevBufs free inside the guard)
+    return CSS_OK;
+}
+
+int css_sq_dim(const css_sq* f, int* dim_out, int* bits_out) {
+    CSS_REQUIRE(f && dim_out && bits_out, "css_sq_dim: NULL argument");
+    *dim_out = f->d, *bits_out = f->bits;
+    return CSS_OK;
+}
+
+int css_sq_ntotal(css_sq* f, int64_t* ntotal_out) {
+    CSS_REQUIRE(f && ntotal_out, "css_sq_ntotal: NULL argument");
+    std::lock_guard<std::mutex> lk(f->mu);
+    *ntotal_out = f->ntotal;
+    return CSS_OK;
+}
+
+int css_sq_last_passes(css_sq* f, int* passes_out) {
+    CSS_REQUIRE(f && passes_out, "css_sq_last_passes: NULL argument");
+    std::lock_guard<std::mutex> lk(f->mu);
+    *passes_out = f->last_passes;
+    return CSS_OK;
+}
+
+int css_sq_set_waves(css_sq* f, int waves) {
+    CSS_REQUIRE(f, "css_sq_set_waves: NULL store");
+    CSS_REQUIRE(waves >= 0 && waves <= CSS_BIN_MAX_WAVES, "css_sq_set_waves: waves=%d outside [0, %d]", waves, CSS_BIN_MAX_WAVES);
+    std::lock_guard<std::mutex> lk(f->mu);
+    f->waves = waves;
+    return CSS_OK;
+}
+
+int css_sq_add(css_sq* f, const float* x_host, int64_t n) {
+    int rc = bin_add_check("css_sq_add", f, n);
+    if (rc != CSS_OK || n == 0) return rc;
+    CSS_REQUIRE(x_host, "css_sq_add: x is NULL");
+    if ((rc = bin_finite_check("css_sq_add", "row", x_host, n, f->d)) != CSS_OK) return rc;
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = sq_reserve(f, f->ntotal + n, st)) != CSS_OK) return rc;
+    // in chunks of at most 2^17 rows through one upload buffer (the stream keeps copy and kernel in order)
+    const int64_t chunk = std::min<int64_t>(n, 1 << 17);
+    if ((rc = f->x.grow((size_t)chunk * f->d)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+            const int64_t m = std::min(chunk, n - r0);
+            CSS_HIP_TRY(hipMemcpyAsync(f->x.p, x_host + (size_t)r0 * f->d, (size_t)m * f->d * sizeof(float), hipMemcpyHostToDevice, st));
+            const int rc2 = sq_encode_enqueue(f, f->x.p, m, f->ntotal + r0, st);
+            if (rc2 != CSS_OK) return rc2;
+        }
+        return CSS_OK;
+    }();
+    rc = bin_end_host(f, rc);
+    if (rc == CSS_OK) f->ntotal += n;
+    return rc;
+}
+
+int css_sq_add_dev(css_sq* f, const float* x_dev, int64_t n, void* stream) {
+    int rc = bin_add_check("css_sq_add_dev", f, n);
+    if (rc != CSS_OK || n == 0) return rc;
+    CSS_REQUIRE(x_dev, "css_sq_add_dev: x is NULL");
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = sq_reserve(f, f->ntotal + n, st)) != CSS_OK) return rc;
+    rc = sq_encode_enqueue(f, x_dev, n, f->ntotal, st);
+    if (rc == CSS_OK) f->ntotal += n;
+    return bin_end_dev(f, rc, st);
+}
+
+int css_sq_add_codes(css_sq* f, const uint8_t* codes_host, int64_t n) {
+    int rc = bin_add_check("css_sq_add_codes", f, n);
+    if (rc != CSS_OK || n == 0) return rc;
+    CSS_REQUIRE(codes_host, "css_sq_add_codes: codes is NULL");
+    std::lock_guard<std::mutex> lk(f->mu);
+    DeviceGuard g(f->device);
+    const hipStream_t st = f->stream;
+    if ((rc = bin_begin(f, st)) != CSS_OK) return rc;
+    if ((rc = sq_reserve(f, f->ntotal + n, st)) != CSS_OK) return rc;
+    if ((rc = f->flat.grow((size_t)n * f->rb / 16)) != CSS_OK) return rc;
+    rc = [&]() -> int {
+        CSS_HIP_TRY(hipMemcpyAsync(f->flat.p, codes_host, (size_t)n * f->rb, hipMemcpyHostToDevice, st));
+        return sq_move_enqueue<true>(f, f->flat.p, n, f->ntotal, st);
+    }();
+    rc = bin_end_host(f, rc);
+    if (rc == CSS_OK) f->ntotal += n;
+    return rc;
+}
+
+int css_sq_get_codes(css_sq* f, int64_t row0, int64_t n, uint8_t* codes_out_host) {
+    CSS_REQUIRE(f && codes_out_host, "css_sq_get_codes: NULL argument");
+    return sq_read_rows("css_sq_get_codes", f, row0, n, [&](hipStream_t st) -> int {
+        int rc;
+        if ((rc = f->flat.grow((size_t)n * f->rb / 16)) != CSS_OK) return rc;
+        if ((rc = sq_move_enqueue<false>(f, f->flat.p, n, row0, st)) != CSS_OK) return rc;
+        CSS_HIP_TRY(hipMemcpyAsync(codes_out_host, f->flat.p, (size_t)n * f->rb, hipMemcpyDeviceToHost, st));
+        return CSS_OK;
+    });
+}
+
+int css_sq_reconstruct(css_sq* f, int64_t row0, int64_t n, float* x_out_host) {
+    CSS_REQUIRE(f && x_out_host, "css_sq_reconstruct: NULL argument");
+    return sq_read_rows("css_sq_reconstruct", f, row0, n, [&](hipStream_t st) -> int {
+        int rc;
+        if ((rc = f->x.grow((size_t)n * f->d)) != CSS_OK) return rc;
+        const dim3 grid((unsigned)((n * (f->rb / 16) + 255) / 256));
+        const float *vmin = f->range.p, *step = f->range.p + f->d;
+        if (f->bits == 8)
+            hipLaunchKernelGGL(k_sq_reconstruct<8>, grid, dim3(256), 0, st, (const uint4*)f->codes.p, f->C, row0, n, f->d, vmin, step, f->x.p);
+        else
+            hipLaunchKernelGGL(k_sq_reconstruct<4>, grid, dim3(256), 0, st, (const uint4*)f->codes.p, f->C, row0, n, f->d, vmin, step, f->x.p);
+        CSS_LAUNCH_CHECK();
+        CSS_HIP_TRY(hipMemcpyAsync(x_out_host, f->x.p, (size_t)n * f->d * sizeof(float), hipMemcpyDeviceToHost, st));
+        return CSS_OK;
+    });
+}
+
+int css_sq_search(css_sq* f, const float* q_host, int64_t nq, int k, const uint32_t* allow_bits_host, int32_t* D_host, int64_t* I_host) {
+    int rc = bin_search_check("css_sq_search", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_host && D_host && I_host, "css_sq_search: NULL buffer");
+    if ((rc = bin_finite_check("css_sq_search", "query", q_host, nq, f->d)) != CSS_OK) return rc;
+    for (int64_t e = 0; e < nq * f->d; ++e)   // (step is fixed after create: no lock)
+        CSS_REQUIRE(std::isfinite(q_host[e] * f->step_host[e % f->d]), "css_sq_search: component %lld of query %lld times its step is infinite",
+                    (long long)(e % f->d), (long long)(e / f->d));
+    return sq_search_host(f, true, q_host, nq, k, allow_bits_host, D_host, I_host);
+}
+
+int css_sq_search_dev(css_sq* f, const float* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev, int64_t* I_dev,
+                      void* stream) {
+    const int rc = bin_search_check("css_sq_search_dev", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_dev && D_dev && I_dev, "css_sq_search_dev: NULL buffer");
+    return sq_search_dev(f, q_dev, nullptr, nq, k, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
+}
+
+int css_sq_search_i8(css_sq* f, const int8_t* q_host, int64_t nq, int k, const uint32_t* allow_bits_host, int32_t* D_host,
+                     int64_t* I_host) {
+    const int rc = bin_search_check("css_sq_search_i8", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_host && D_host && I_host, "css_sq_search_i8: NULL buffer");
+    return sq_search_host(f, false, q_host, nq, k, allow_bits_host, D_host, I_host);
+}
+
+int css_sq_search_i8_dev(css_sq* f, const int8_t* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev, int64_t* I_dev,
+                         void* stream) {
+    const int rc = bin_search_check("css_sq_search_i8_dev", f, nq, k);
+    if (rc != CSS_OK) return rc;
+    CSS_REQUIRE(q_dev && D_dev && I_dev, "css_sq_search_i8_dev: NULL buffer");
+    return sq_search_dev(f, nullptr, q_dev, nq, k, allow_bits_dev, D_dev, I_dev, (hipStream_t)stream);
 }
 
 namespace {

@@ -794,6 +794,63 @@ int css_bin_search_asym_i8_dev(css_bin* b, const int8_t* q_dev, int64_t nq, int 
 int css_bin_last_passes(css_bin* b, int* passes_out);
 int css_bin_set_waves(css_bin* b, int waves);
 
+/* The scalar-quantized row store: dense rows kept as one 8- or 4-bit code per component and nothing else, scanned
+ * exhaustively (faiss IndexScalarQuantizer QT_8bit / QT_4bit, Lucene int8_flat / int4_flat).  Training-light (a range
+ * per component, the caller's); every row is scored by every search; the whole result is integers.  A store is an
+ * object of its own.
+ *  - Quantizer.  d a multiple of 32 in [32, 8192]; bits 4 or 8, L = 2^bits - 1; float32 vmin[d] (finite) and step[d]
+ *    (finite and above 0).  Anything else is CSS_ERR_INVALID at css_sq_create, the message names the component.
+ *  - Encode.  c_i = clamp(rintf(__fdiv_rn(__fsub_rn(x_i, vmin_i), step_i)), 0, L): the difference, the quotient and
+ *    the rounding to an integer (ties to even) each ONE fp32 operation.  A NaN, which only the _dev forms let through,
+ *    gives 0.
+ *  - Decode (css_sq_reconstruct).  __fmaf_rn((float)c_i, step_i, vmin_i), one rounding.
+ *  - Codes at the ABI: row-major uint8.  8 bits: [n, d], byte i is c_i.  4 bits: [n, d / 2], component 2 j in the LOW
+ *    nibble of byte j and 2 j + 1 in the high one (the order of faiss).  The layout in device memory is the library's
+ *    business (row-tile-major, csrc/css_sq.h).
+ *  - Query.  <q, decode(r)> = sum_i q_i vmin_i + sum_i (q_i step_i) c_i, so the ranges fold into the query.  The
+ *    float forms (css_sq_search / _dev) make w_i = __fmul_rn(q_i, step_i), a = max_i |w_i|; if a is below the smallest
+ *    normal float (compared on the bits) the int8 query is all zeros, otherwise q8_i = rint((w_i / a) * 127), the
+ *    division and the product each correctly rounded in fp32, rint to nearest even, denormal w_i kept -- the rule of
+ *    css_bin_search_asym on w.  The _i8 forms take an int8 query as it is, every value allowed (-128 included), no
+ *    folding.
+ *  - Score.  s(q, r) = sum_i q8_i c_i, an int32 with |s| <= 8192 * 128 * 255 < 2^28.
+ *  - Answer.  D int32 (scores) and I int64, each [nq, k], 1 <= k <= 128, 1 <= nq <= CSS_BIN_MAX_QUERIES; the LARGEST
+ *    score first, ties to the lower id (= row number); allow_bits as in css_index_search_masked (NULL: every row);
+ *    padding D = INT32_MIN, I = -1.  The bytes do not depend on the grid, css_sq_set_waves, the batch, the order or
+ *    size of the adds, or the form of the call.  The library returns integers only: sum_i q_i vmin_i + a s / 127 is
+ *    the caller's float estimate of <q, decode(r)> (sq.estimate in Python).
+ *  - Passes.  16 queries per scan of the codes, scan and selection in one kernel (no score column exists);
+ *    css_sq_last_passes reports ceil(nq / 16) of the last search, 0 on an empty store.
+ *  - css_sq_add / _add_dev encode fp32 rows [n, d] on the device behind the stored ones; css_sq_add_codes appends
+ *    rows that are codes already, the form css_sq_get_codes returns for rows [row0, row0 + n).
+ *  - Refusals.  In the host forms a NaN or infinite component of a float row or query, or a query component whose
+ *    product with its step is infinite, is CSS_ERR_INVALID, the message names row (or query) and component.  Arguments
+ *    are checked before anything is enqueued.
+ *  - The _dev forms take device pointers (floats 4-byte aligned), enqueue on `stream` without a wait or a check of
+ *    the contents; css_sq_add_dev waits for the stream only when the store has to grow.  Calls on one store are
+ *    serialised, and a call on another stream goes behind the _dev call before it.
+ *  - css_sq_set_waves: as css_bin_set_waves, in steps of 64 rows.  A test and tuning hook: no answer depends on it. */
+typedef struct css_sq css_sq;
+int css_sq_create(int d, int bits, const float* vmin_host /* [d] */, const float* step_host /* [d] */, int device, css_sq** out);
+int css_sq_free(css_sq* s);
+int css_sq_dim(const css_sq* s, int* dim_out, int* bits_out);
+int css_sq_ntotal(css_sq* s, int64_t* ntotal_out);
+int css_sq_add(css_sq* s, const float* x_host /* [n, d] */, int64_t n);
+int css_sq_add_dev(css_sq* s, const float* x_dev, int64_t n, void* stream);
+int css_sq_add_codes(css_sq* s, const uint8_t* codes_host /* [n, d bits / 8] */, int64_t n);
+int css_sq_get_codes(css_sq* s, int64_t row0, int64_t n, uint8_t* codes_out_host /* [n, d bits / 8] */);
+int css_sq_reconstruct(css_sq* s, int64_t row0, int64_t n, float* x_out_host /* [n, d] */);
+int css_sq_search(css_sq* s, const float* q_host /* [nq, d] */, int64_t nq, int k, const uint32_t* allow_bits_host,
+                  int32_t* D_host /* [nq, k] */, int64_t* I_host /* [nq, k] */);
+int css_sq_search_dev(css_sq* s, const float* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev,
+                      int64_t* I_dev, void* stream);
+int css_sq_search_i8(css_sq* s, const int8_t* q_host /* [nq, d] */, int64_t nq, int k, const uint32_t* allow_bits_host,
+                     int32_t* D_host, int64_t* I_host);
+int css_sq_search_i8_dev(css_sq* s, const int8_t* q_dev, int64_t nq, int k, const uint32_t* allow_bits_dev, int32_t* D_dev,
+                         int64_t* I_dev, void* stream);
+int css_sq_last_passes(css_sq* s, int* passes_out);
+int css_sq_set_waves(css_sq* s, int waves);
+
 /* Significant terms (Elasticsearch's significant_terms aggregation, the keyword side of BERTopic): which terms set a
  * selection of rows apart from a background -- "what is in this cluster / this project / these hits".  Everything is
  * read from the term lists above; the rows' values play no part.  T = the leading rows that have lists.
